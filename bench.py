@@ -18,7 +18,13 @@ ball-query+group workgroups on the other CUs consume them. --path fused: TWO ker
 (pn2_farthest_point_sample_gather, pn2_query_ball_group_xyz). --path ops: the four reference-shaped
 operators one by one. All three produce the same outputs, parity-tested bit-exact against the oracle.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step` = wall
+milliseconds of one timed step). --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed
+step computed -- fps_idx, new_xyz, idx, pts_cnt, grouped_xyz -- as DIR/<name>.npy (index arrays as float64,
+coordinates as float32; about 22 MB). The clouds are seeded, so the same arguments give the same inputs on
+every run. --full: also every check and extra figure below, in the same invocation.
 
 Multi-GPU: the path shards by cloud with no data-path collective. With --gpus N > 1 and
 no RANK in the environment this script re-launches ITSELF under torch.distributed.run (one process per
@@ -27,12 +33,14 @@ every rank owns its own B=32 batch; --scaling strong: the global B=32 batch is s
 rank exactly as tf.slice does in the reference's tower loop (train_multi_gpu.py:185-188). Rank 0 prints
 ONE JSON line; `value` = clouds all ranks processed / max-over-ranks time of exactly K steps.
 
-Extra objects on the JSON line:
+Objects on the JSON line (all but `roofline` only with --full):
   roofline     -- the kernel IN THE TIMED REGION against HBM: SURVEY 8(d)'s 851,968 algorithmic bytes
                   per cloud x clouds per launch / the launch's average duration, HIP events on the
                   launch stream around the K timed steps. The path is bound by the FPS chain (1023
                   dependent block-wide arg-max rounds), so the fraction is tiny by construction; see
                   fps_latency_model and DESIGN.md.
+  verify       -- the last timed step's outputs against the four reference-shaped operators on the device, bit-exact
+                  (`verified`; None in a plain run); strong -- N > 1: the strong-scaling leg of a weak run.
   fps_latency_model -- rounds and nanoseconds per round of the FPS operator alone (the honest model).
   kernels / stage   -- every op-level kernel of the step the same way.
   d2           -- the same step on D2 clouds (uniform U[0,1)^3, radius 0.1: the reference harnesses'
@@ -559,6 +567,20 @@ def allreduce_leg(dev, dist, reps=20, cdev=None):
     return out
 
 
+DUMPED = ("fps_idx", "new_xyz", "idx", "pts_cnt", "grouped_xyz")
+
+
+def dump_outputs(stage, out_dir):
+    """--dump-outputs: the five arrays the timed path's last step left in the stage's buffers (what sample_and_group hands its
+    caller, plus the FPS indices and neighbour counts), as DIR/<name>.npy. Index arrays go out as float64 (exact), the
+    coordinates as float32."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(DUMPED, (stage.fps, stage.new_xyz, stage.idx, stage.cnt, stage.grouped)):
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype.kind == "i" else np.float32))
+
+
 def respawn(args):
     """--gpus N > 1 without a launcher: one process per GPU under torch.distributed.run, rendezvous on 127.0.0.1."""
     s = socket.socket()
@@ -586,7 +608,11 @@ def main():
     ap.add_argument("--streams", type=int, default=8, help="batches in flight for the extra `concurrent` figure (0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-extras", action="store_true", help="only the contract line (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also verify the outputs and measure every extra figure: per-kernel times, "
+                         "rooflines, D2 clouds, concurrent / batched throughput, CPU baselines, the strong leg and the all-reduce")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: verify, strong leg and all-reduce, no extra figures")
     ap.add_argument("--stub", action="store_true", help="CPU test mode: gloo, no kernels (tests/test_distributed.py)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="REHEARSAL of the N-rank path on a box with ONE GPU: every rank runs its shard on cuda:0 and the process group "
@@ -595,6 +621,10 @@ def main():
                          "per-rank verify, census, the strong-scaling leg; its figures are NOT scaling figures (the ranks share the "
                          "GPU) and the line says so (`rehearsal`)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.stub and args.dump_outputs:
+        ap.error("--dump-outputs needs the GPU path (no outputs in --stub mode)")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(respawn(args))
@@ -655,12 +685,14 @@ def main():
     elapsed = sharding.max_over_ranks(elapsed, cdev)     # whole-job time = slowest rank
     launch_s = (ev0.elapsed_time(ev1) * 1e-3 / args.steps) if ev0 is not None else elapsed / args.steps
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(stage, args.dump_outputs)       # before verify(), which reuses the stage's buffers
     # outputs of the LAST timed step against the four-operator path (and the overlapped launch's status word): every rank
     verified = None
-    if not args.stub:
+    if args.full and not args.stub:
         v = stage.verify(args.path)
         verified = dict(v, ok=bool(sharding.max_over_ranks(0.0 if v["ok"] else 1.0, cdev) == 0.0))   # ok = EVERY rank's outputs verified
-    extras = not args.no_extras and not args.stub
+    extras = args.full and not args.no_extras and not args.stub
     # who took part: every rank reports (rank, seed of its clouds, verify ok); rank 0 asserts the census is 0 .. N-1 with
     # N different seeds (weak scaling: every rank its own batch) and counts the ranks whose outputs verified
     seed = 1000 + (rank if args.scaling == "weak" else 0)
@@ -672,7 +704,7 @@ def main():
     # N > 1, weak run: the STRONG-scaling figure too, in the same invocation (one SCALE run captures both): ONE global B=32
     # batch sliced 32/N per rank, same barriers, same max-over-ranks clock
     strong = None
-    if world > 1 and args.scaling == "weak" and B % world == 0 and (args.share_gpu or not args.no_extras):
+    if args.full and world > 1 and args.scaling == "weak" and B % world == 0 and (args.share_gpu or not args.no_extras):
         lo, hi = sharding.shard_bounds(B, world, rank)
         st2 = StubStage(hi - lo) if args.stub else Stage(dev, synthetic.sphere_clouds(B, N, 1000)[lo:hi])
         step2 = st2.step(args.path)
@@ -695,7 +727,7 @@ def main():
                   "note": "the same K steps on ONE global B=32 batch sliced like tf.slice in the reference's tower loop "
                           "(train_multi_gpu.py:185-188); a rank with 32/N clouds still runs the whole 1023-round chain, so this "
                           "figure is expected flat in N (SURVEY 8e)"}
-    allred = allreduce_leg(dev, dist, cdev=cdev) if dist is not None else None
+    allred = allreduce_leg(dev, dist, cdev=cdev) if args.full and dist is not None else None
     conc = None
     if extras and args.streams > 1 and world == 1:
         conc = concurrent_throughput(dev, rank, args.path, args.streams, max(256, 32 * args.streams))

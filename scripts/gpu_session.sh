@@ -29,7 +29,7 @@ for step in "$@"; do
     tests_mlp) timeout 600 python -m pytest tests/test_sa_mlp_gpu.py tests/test_fp_mlp_gpu.py -m gpu -q -x > "$OUT/tests_mlp.log" 2>&1; tail -15 "$OUT/tests_mlp.log" ;;
     smoke)     timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; tail -2 "$OUT/smoke.log" ;;
     configs)   timeout 600 python scripts/config_shapes.py > "$OUT/config_shapes.json" 2> "$OUT/config_shapes.err"; tail -3 "$OUT/config_shapes.json" ;;
-    bench)     timeout 600 python bench.py > "$OUT/bench.log" 2>&1; tail -3 "$OUT/bench.log" ;;
+    bench)     timeout 600 python bench.py --full > "$OUT/bench.log" 2>&1; tail -3 "$OUT/bench.log" ;;
     trainbench) timeout 400 python scripts/train_mlp_bench.py 2> "$OUT/train_mlp_bench.err" | grep "^{" > "$OUT/train_mlp_bench.jsonl"; python - "$OUT/train_mlp_bench.jsonl" <<'PY'
 import json, sys
 for l in open(sys.argv[1]):
@@ -48,7 +48,7 @@ for l in open(sys.argv[1]):
 PY
     ;;
     trainrccl) timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 scripts/train_step_bench.py sem_seg --steps 8 --fused-only 2> "$OUT/train_rccl.err" | grep "^{" > "$OUT/train_step_rccl.jsonl"; cat "$OUT/train_step_rccl.jsonl" | cut -c1-400
-               timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --steps 20 --no-extras 2> "$OUT/bench_rccl.err" | grep "^{" > "$OUT/bench_rccl.json"; python -c "import json,sys; print(json.load(open(sys.argv[1]))['allreduce'])" "$OUT/bench_rccl.json" ;;
+               timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29518 bench.py --gpus 1 --steps 20 --full --no-extras 2> "$OUT/bench_rccl.err" | grep "^{" > "$OUT/bench_rccl.json"; python -c "import json,sys; print(json.load(open(sys.argv[1]))['allreduce'])" "$OUT/bench_rccl.json" ;;
     traincheck) PN2_TRAIN_OPTS=top_stored=0 timeout 300 python scripts/train_mlp_check.py > "$OUT/train_check_zfree.log" 2>&1; tail -1 "$OUT/train_check_zfree.log"; timeout 300 python scripts/train_mlp_check.py > "$OUT/train_check.log" 2>&1; tail -1 "$OUT/train_check.log" ;;
     traintests) timeout 1500 python -m pytest tests/test_train_mlp_gpu.py tests/test_train_golden_gpu.py tests/test_train_fuzz_gpu.py tests/test_whole_model_fp64_gpu.py tests/test_overlap_status_gpu.py tests/test_modules_gpu.py -m gpu -q > "$OUT/traintests.log" 2>&1; tail -25 "$OUT/traintests.log" ;;
     wholemodel) timeout 900 python scripts/whole_model_fp64.py --top 2> "$OUT/whole_model_fp64.err" | grep "^{" > "$OUT/whole_model_fp64.jsonl"; python - "$OUT/whole_model_fp64.jsonl" <<'PY'

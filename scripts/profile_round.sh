@@ -24,7 +24,7 @@ run_shapes() {  # name, command...: per-dispatch trace -> one row per (kernel, l
     local f=$(find "$OUT/$name" -name "*kernel_trace.csv" | head -1)
     [ -n "$f" ] && python $ROOT/scripts/per_shape_stats.py "$f" "$OUT/kernel_shapes_$name.csv" pn2::
 }
-B="python $ROOT/bench.py --no-cpu-baseline --streams 0 --steps 30 --warmup 3"
+B="python $ROOT/bench.py --full --no-cpu-baseline --streams 0 --steps 30 --warmup 3"
 BQ="python $ROOT/bench.py --no-extras --steps 30 --warmup 3"   # only the timed kernel(s)
 run_stats ops $B --path ops
 run_stats overlap $B --path overlap

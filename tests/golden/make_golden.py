@@ -99,9 +99,31 @@ def main():
         cases[name + "_xyz"] = xyz
         cases[name + "_idx"] = O.farthest_point_sample(m, xyz, literal=True)
     np.savez_compressed(os.path.join(OUT, "fps_literal.npz"), **cases)
+    live_crosscheck()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)))
+
+
+def live_crosscheck():
+    """live_crosscheck.npz: the inputs of tests/test_oracle.py::test_oracle_vs_live_reference_libs and the reference
+    functions' outputs on them (query_ball_point_cpu, group_point_cpu, threenn_cpu, threeinterpolate_cpu)."""
+    O.build(with_ref=True)
+    rng = np.random.default_rng(5)
+    cases = {}
+    for seed in range(3):
+        xyz = S.sphere_clouds(2, 300 + 50 * seed, seed)
+        q = xyz[:, :70].copy()
+        pts = rng.random((2, xyz.shape[1], 6), dtype=np.float32)
+        w = rng.random((2, xyz.shape[1], 3), dtype=np.float32)          # the shape of three_nn's output
+        f = rng.random((2, 70, 9), dtype=np.float32)
+        idx = O.ref_query_ball_point(0.25, 24, xyz, q)
+        d, i = O.ref_three_nn(xyz, q)
+        k = "s%d_" % seed
+        cases.update({k + "xyz": xyz, k + "points": pts, k + "weight": w, k + "features": f, k + "idx": idx,
+                      k + "grouped": O.ref_group_point(pts, idx), k + "dist": d, k + "nn_idx": i,
+                      k + "interpolated": O.ref_three_interpolate(f, i, w)})
+    np.savez_compressed(os.path.join(OUT, "live_crosscheck.npz"), **cases)
 
 
 if __name__ == "__main__":

@@ -122,7 +122,7 @@ def _run_bench(extra):
 def test_bench_spawns_its_own_ranks(scaling):
     """`python bench.py --gpus 2` with no launcher around it must itself start two ranks (the driver's
     command line), time the steps between barriers, and report the whole-job rate: stub step on CPU/gloo."""
-    line = _run_bench(["--gpus", "2", "--scaling", scaling])
+    line = _run_bench(["--gpus", "2", "--scaling", scaling, "--full"])
     assert line["n_gpus"] == 2 and line["steps"] == 5 and line["scaling"] == scaling
     per_rank = 32 if scaling == "weak" else 16
     assert abs(line["value"] - 2 * per_rank * 5 / (line["ms_per_step"] * 5e-3)) < 1e-6 * line["value"]
@@ -136,7 +136,7 @@ def test_bench_with_eight_ranks():
     """What the driver's 8-GPU run does, as far as a machine without GPUs can go: `bench.py --gpus 8`
     starts eight ranks itself, every rank takes part (ranks_seen), the weak run gives every rank its own seed, and the same
     invocation carries the strong-scaling figure (one global batch, 4 clouds per rank). Stub step, gloo."""
-    line = _run_bench(["--gpus", "8"])
+    line = _run_bench(["--gpus", "8", "--full"])
     assert line["n_gpus"] == 8 and line["scaling"] == "weak"
     assert line["ranks_seen"] == list(range(8)) and line["rank_seeds"] == [1000 + r for r in range(8)]
     assert line["collective_library"].startswith("gloo")
@@ -148,6 +148,7 @@ def test_bench_with_eight_ranks():
     strong = _run_bench(["--gpus", "8", "--scaling", "strong"])
     assert strong["n_gpus"] == 8 and strong["scaling"] == "strong" and strong["ranks_seen"] == list(range(8))
     assert strong["rank_seeds"] == [1000] * 8 and "strong" not in strong
+    assert "allreduce" not in strong                         # without --full: the timed steps and the line only
 
 
 def test_bench_single_rank_stub_line():

@@ -65,24 +65,28 @@ def test_fps_matches_literal_golden(oracle, golden_dir):
         assert np.array_equal(got, want), case
 
 
-# ------------------------------------------------- live cross-checks (container only)
-def test_oracle_vs_live_reference_libs(oracle):
-    if not oracle.ref_available("grouping") or not oracle.ref_available("interpolate"):
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(5)
+# ------------------------------------------------- cross-checks against the reference's functions
+def test_oracle_vs_live_reference_libs(oracle, golden_dir):
+    """The oracle against the reference's own CPU functions on the same inputs: their outputs as stored in
+    live_crosscheck.npz (tests/golden/make_golden.py), and -- where oracle/_ref is built -- the live functions too."""
+    g = _load(golden_dir, "live_crosscheck.npz")
+    live = oracle.ref_available("grouping") and oracle.ref_available("interpolate")
     for seed in range(3):
-        xyz = S.sphere_clouds(2, 300 + 50 * seed, seed)
+        k = "s%d_" % seed
+        xyz, pts, w, f = g[k + "xyz"], g[k + "points"], g[k + "weight"], g[k + "features"]
         q = xyz[:, :70].copy()
         idx, _ = oracle.query_ball_point(0.25, 24, xyz, q)
-        assert np.array_equal(idx, oracle.ref_query_ball_point(0.25, 24, xyz, q))
-        pts = rng.random((2, xyz.shape[1], 6), dtype=np.float32)
-        assert np.array_equal(oracle.group_point(pts, idx), oracle.ref_group_point(pts, idx))
+        assert np.array_equal(idx, g[k + "idx"])
+        assert np.array_equal(oracle.group_point(pts, idx), g[k + "grouped"])
         d, i = oracle.three_nn(xyz, q)
-        rd, ri = oracle.ref_three_nn(xyz, q)
-        assert np.array_equal(d, rd) and np.array_equal(i, ri)
-        w = rng.random(d.shape, dtype=np.float32)
-        f = rng.random((2, 70, 9), dtype=np.float32)
-        assert np.array_equal(oracle.three_interpolate(f, i, w), oracle.ref_three_interpolate(f, i, w))
+        assert np.array_equal(d, g[k + "dist"]) and np.array_equal(i, g[k + "nn_idx"])
+        assert np.array_equal(oracle.three_interpolate(f, i, w), g[k + "interpolated"])
+        if live:
+            assert np.array_equal(idx, oracle.ref_query_ball_point(0.25, 24, xyz, q))
+            assert np.array_equal(oracle.group_point(pts, idx), oracle.ref_group_point(pts, idx))
+            rd, ri = oracle.ref_three_nn(xyz, q)
+            assert np.array_equal(d, rd) and np.array_equal(i, ri)
+            assert np.array_equal(oracle.three_interpolate(f, i, w), oracle.ref_three_interpolate(f, i, w))
 
 
 # ------------------------------------------------------------- FPS tie rule & properties
