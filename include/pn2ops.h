@@ -128,7 +128,10 @@ int pn2_three_interpolate_grad_det(int b, int n, int c, int m, const float *grad
 /* ---- the same gradients as a segmented reduction (no reference counterpart) ----------------------
  * idx is inverted first (counting sort by target row), then one lane group sums the grad_out rows of
  * every output row: no float atomics, no zero-fill, ~3x the throughput of the atomic scatter from 16
- * channels up. deterministic != 0: per-element 64-bit fixed-point sums (identical bits on every run).
+ * channels up. deterministic != 0: identical bits on every run. A target row is summed in fp32 in ascending entry order --
+ * bit-identical to the reference's CPU loops -- when b >= 4, rows <= 24576, rows + entries <= 36864 (counters and list in
+ * 144 KiB of LDS) and the row has at most 1024 entries; every other row is a 64-bit fixed-point sum with one scale per
+ * element from the largest |addend| of the row (INTEGRATION.md C'').
  * ws: pn2_seg_grad_ws_bytes(b, rows, entries) bytes of uninitialised device scratch
  * (group_point: rows = n, entries = m * nsample; three_interpolate: rows = m, entries = 3 * n). */
 long long pn2_seg_grad_ws_bytes(int b, int rows, long long entries);

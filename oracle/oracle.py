@@ -184,6 +184,49 @@ def three_interpolate_grad(points_shape, idx, weight, grad_out):
     return gp
 
 
+def fixed_point_grad(rows, target, addend, shift=None):
+    """The reproducible mode's fixed-point scatter-add, restated in numpy (not a reference function).
+
+    target (e,) row numbers in [0, rows), addend (e, c) float32 -> (rows, c) float32. Per output element:
+      mx   = largest |addend| of the row's segment (in that channel), logc = ceil(log2(segment length));
+      k    = 62 - logc - (exponent field of mx - 126)                       (seg_grad.hip seg_shift)
+      fx   = sum of rint_half_even(addend * 2^k) in int64                    (order-independent)
+      out  = float32(float64(fx) * 2^-k)                                     (rounds twice, like the kernel)
+    A segment with a non-finite addend keeps the plain fp32 sum (in list order). Rows without entries are +0.
+    shift=k: one shift for every element instead (det_grad.hip: k from the largest addend of the whole call),
+    finite addends only. This is what seg_reduce_kernel computes for a row its index inversion left unsorted."""
+    target = np.asarray(target).reshape(-1).astype(np.int64)
+    a = np.ascontiguousarray(addend, dtype=np.float32)
+    a = a.reshape(target.size, a.shape[-1] if a.ndim > 1 else 1)
+    out = np.zeros((rows, a.shape[1]), np.float32)
+    if target.size == 0:
+        return out
+    order = np.argsort(target, kind="stable")
+    a = a[order]
+    lens_all = np.bincount(target, minlength=rows)
+    used = np.nonzero(lens_all)[0]
+    lens = lens_all[used]
+    starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    mx = np.maximum.reduceat(a.view(np.uint32) & np.uint32(0x7fffffff), starts, axis=0)
+    if shift is None:
+        logc = np.array([(int(n) - 1).bit_length() for n in lens], np.int64)
+        k = 62 - logc[:, None] - ((mx >> 23).astype(np.int64) - 126)
+    else:
+        k = np.full(mx.shape, int(shift), np.int64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        scaled = np.ldexp(a.astype(np.float64), np.repeat(k, lens, axis=0).astype(np.int32))
+        fx = np.where(np.isfinite(scaled), np.rint(scaled), 0.0).astype(np.int64)
+    total = np.add.reduceat(fx, starts, axis=0)
+    res = np.ldexp(total.astype(np.float64), (-k).astype(np.int32)).astype(np.float32)
+    nonfinite = mx >= np.uint32(0x7f800000)
+    if nonfinite.any():
+        with np.errstate(invalid="ignore", over="ignore"):
+            plain = np.add.reduceat(a, starts, axis=0, dtype=np.float32)
+        res = np.where(nonfinite, plain, res)
+    out[used] = res
+    return out
+
+
 def now():
     return lib().pn2_cpu_now()
 

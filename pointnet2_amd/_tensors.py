@@ -92,10 +92,10 @@ _deterministic = False
 
 
 def set_deterministic(flag):
-    """Route the scatter-add gradients (gather_point, group_point, three_interpolate) through the
-    order-independent fixed-point kernels (pn2_*_grad_det): identical bits on every run, at about
-    twice the accumulation traffic. Off by default, like the reference (fp32 atomics). Also switched
-    on by torch.use_deterministic_algorithms(True)."""
+    """Make the scatter-add gradients (gather_point, group_point, three_interpolate) reproducible: identical
+    bits on every run -- sorted segments summed in the reference CPU loop's order, or 64-bit fixed-point sums
+    (which rows get which: INTEGRATION.md C''). Off by default, like the reference (fp32 atomics). Also
+    switched on by torch.use_deterministic_algorithms(True)."""
     global _deterministic
     _deterministic = bool(flag)
 

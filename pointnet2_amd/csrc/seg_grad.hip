@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <numeric>
 #include <type_traits>
 
 namespace pn2 {
@@ -659,11 +660,11 @@ static long long seg_long_blocks(long long out_rows, int rows, bool wide)
     for (long long d = 0; d < rows; ++d)
         for (int sgn = 0; sgn < 2; ++sgn) {
             const long long r = sgn ? target - d : target + d;
-            if (r <= 0 || r >= rows || r > cap || std::__gcd(r, (long long)rows) != 1) continue;
+            if (r <= 0 || r >= rows || r > cap || std::gcd(r, (long long)rows) != 1) continue;
             return (cap - r) / rows * rows + r;                       // the largest q rows + r within the cap
         }
     long long wg = cap | 1;                                           // (rows per cloud of 1 or 2: nothing to spread)
-    while (wg > 1 && std::__gcd((long long)rows, wg) > 1) wg -= 2;
+    while (wg > 1 && std::gcd((long long)rows, wg) > 1) wg -= 2;
     return wg;
 }
 
