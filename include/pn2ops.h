@@ -513,6 +513,27 @@ int pn2_mlp_train_backward_ex(long long rows, int nlayers, const pn2_bn_layer *l
                               const float *x, int pool_rows, const float *out, const int *argsel, const float *zsel,
                               const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points,
                               int reproducible, void *ws, const pn2_train_opts *opts, void *stream);
+/* The pooling modes of pointnet_sa_module (utils/pointnet_util.py:128-142) in training mode, grouped input only (the entries
+ * above pool by max). pooling: 0 max (the _ex entries' path, bit for bit), 1 avg (out (groups, cout_L) = the mean over the
+ * group, padded ball-query slots included, :130-131), 2 weighted_avg (w = exp(-5 |grouped xyz|) normalised over the group,
+ * :132-138; group_all: |xyz|), 3 max_and_avg (out (groups, 2 cout_L) = concat([avg, max]), :139-142; the max half is
+ * pooling 0's output bit for bit). Modes 1-3 keep the top layer's pre-norm tensor (layers[L-1].z is always written and
+ * read: opts.top_stored does not apply) and reduce each group after the layer's batch moments; their backward forms the
+ * dense top gradient and runs the layers below as pooling 0 does. argsel / zsel (groups, cout_L): modes 0 and 3 only;
+ * pool_w (rows) f32: mode 2 only -- the normalised weights, written by forward, read by backward. Returns PN2_E_ARG for a
+ * pooling outside 0..3, PN2_E_NULL for modes 1-3 without `group`, before anything is launched.
+ * pn2_mlp_train_pool_supported: 1 where both directions run (rows and widths as for pn2_mlp_train_ws_bytes, pool_rows
+ * 16 or a multiple of 32), else 0. Workspaces: pn2_mlp_train_ws_bytes_pool (group_dims as for pn2_mlp_train_ws_bytes). */
+int pn2_mlp_train_pool_supported(long long rows, int nlayers, const int *widths, int pool_rows, int pooling);
+long long pn2_mlp_train_ws_bytes_pool(long long rows, int nlayers, const int *widths, int pool_rows, int pooling, int backward,
+                                      const int *group_dims, const pn2_train_opts *opts);
+int pn2_mlp_train_forward_pool(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                               int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
+                               const pn2_train_opts *opts, void *stream);
+int pn2_mlp_train_backward_pool(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel,
+                                const float *pool_w, const float *grad_out, float *grad_feat_rows, float *grad_points,
+                                int reproducible, void *ws, const pn2_train_opts *opts, void *stream);
 
 /* The input rows of a feature-propagation level's layer stack in ONE launch (pointnet_fp_module, utils/pointnet_util.py:211-219):
  * inverse-distance weights from three_nn's `dist`, three_interpolate of points2 (b,m,c2), concatenation with the skip features

@@ -95,6 +95,10 @@ _SIGNATURES = {
     "pn2_mlp_train_top_stored_ex": [_ll, _i, _vp, _i, _vp],
     "pn2_mlp_train_forward_ex": [_ll, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_mlp_train_backward_ex": [_ll, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "pn2_mlp_train_pool_supported": [_ll, _i, _vp, _i, _i],
+    "pn2_mlp_train_ws_bytes_pool": [_ll, _i, _vp, _i, _i, _i, _vp, _vp],
+    "pn2_mlp_train_forward_pool": [_ll, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_mlp_train_backward_pool": [_ll, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "pn2_fps_temp_floats": ctypes.c_longlong,
@@ -106,6 +110,7 @@ _RESTYPES = {
     "pn2_fp_mlp_ws_bytes": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_ex": ctypes.c_longlong,
+    "pn2_mlp_train_ws_bytes_pool": ctypes.c_longlong,
     "pn2_sample_and_group_status_offset": ctypes.c_longlong,
     "pn2_ball_threshold": ctypes.c_float,
     "pn2_version": ctypes.c_char_p,

@@ -682,6 +682,156 @@ __global__ __launch_bounds__(256) void tl_top_grad_kernel(long long rows, int N,
     }
 }
 
+// ---- pooled averages (pooling 1 avg, 2 weighted_avg, 3 max_and_avg; utils/pointnet_util.py:128-142) ----------------------
+// A mean does not commute with batch norm + ReLU the way a max does, so these modes keep z_L (the unpooled top layer of the FP
+// levels) and reduce each group after the layer's moments are final: out[g, c] = sum_k w_gk relu(a_c z_L[g ns + k, c] + c_c).
+// Padded ball-query slots (duplicates of the first hit) count, as in the reference's reduce_mean over nsample.
+
+// weighted_avg weights, one wave per group: w = exp(-5 |xyz[idx] - new_xyz|) / (sum over the group) (:132-138; the fp32 formula
+// of sa_mlp.hip); group_all (new_xyz NULL): |xyz|. The wave's butterfly sum has a fixed order and gives every lane the same bits.
+__global__ __launch_bounds__(256) void tl_pool_weights_kernel(long long groups, int ns, int n, int m, const float *__restrict__ xyz,
+                                                              const float *__restrict__ new_xyz, const int *__restrict__ idx,
+                                                              float *__restrict__ w)
+{
+    const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (g >= groups) return;
+    const long long cloud = g / m;
+    float cx = 0.0f, cy = 0.0f, cz = 0.0f;
+    if (new_xyz) { cx = new_xyz[g * 3]; cy = new_xyz[g * 3 + 1]; cz = new_xyz[g * 3 + 2]; }
+    float s = 0.0f;
+    for (int k = lane; k < ns; k += 64) {
+        const long long r = g * ns + k;
+        const int pt = idx ? idx[r] : k;
+        const float *p = xyz + (cloud * n + pt) * 3;
+        const float dx = __fsub_rn(p[0], cx), dy = __fsub_rn(p[1], cy), dz = __fsub_rn(p[2], cz);
+        const float e = expf(-5.0f * sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz))));
+        w[r] = e;
+        s = __fadd_rn(s, e);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s = __fadd_rn(s, __shfl_xor(s, o));
+    for (int k = lane; k < ns; k += 64) w[g * ns + k] = w[g * ns + k] / s;
+}
+
+// out[g, c] (pitch N, or 2 N with the max half `maxv` behind it: max_and_avg) = sum_k w relu(a z + c); w = pool_w, or 1 / ns
+__global__ __launch_bounds__(256) void tl_pool_avg_kernel(long long groups, int ns, int N, const float *__restrict__ z,
+                                                          const float *__restrict__ save, const float *__restrict__ pool_w,
+                                                          const float *__restrict__ maxv, float *__restrict__ out)
+{
+    const int n4 = N / 4, opitch = maxv ? 2 * N : N;
+    const long long total = groups * n4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long g = i / n4;
+        const int c = (int)(i - g * n4) * 4;
+        const float4 a = ld4(save + 2 * N + c), cc = ld4(save + 3 * N + c);
+        const float *zr = z + (size_t)g * ns * N + c;
+        float4 s = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll 4
+        for (int k = 0; k < ns; ++k) {
+            const float4 v = ld4(zr + (size_t)k * N);
+            float4 h;
+            h.x = vmax(__fadd_rn(__fmul_rn(a.x, v.x), cc.x), 0.0f);
+            h.y = vmax(__fadd_rn(__fmul_rn(a.y, v.y), cc.y), 0.0f);
+            h.z = vmax(__fadd_rn(__fmul_rn(a.z, v.z), cc.z), 0.0f);
+            h.w = vmax(__fadd_rn(__fmul_rn(a.w, v.w), cc.w), 0.0f);
+            if (pool_w) {
+                const float wk = pool_w[g * ns + k];
+                h.x = __fmul_rn(wk, h.x); h.y = __fmul_rn(wk, h.y); h.z = __fmul_rn(wk, h.z); h.w = __fmul_rn(wk, h.w);
+            }
+            s.x = __fadd_rn(s.x, h.x); s.y = __fadd_rn(s.y, h.y); s.z = __fadd_rn(s.z, h.z); s.w = __fadd_rn(s.w, h.w);
+        }
+        if (!pool_w) {
+            const float fn = (float)ns;
+            s.x = s.x / fn; s.y = s.y / fn; s.z = s.z / fn; s.w = s.w / fn;
+        }
+        *reinterpret_cast<float4 *>(out + g * opitch + c) = s;
+        if (maxv) *reinterpret_cast<float4 *>(out + g * opitch + N + c) = ld4(maxv + g * N + c);
+    }
+}
+
+// the averaged top layer's dense gradient (the pooled counterpart of tl_top_grad_kernel, same grid, same `stats` layout):
+// dy[row, c] = [a z + c > 0] (w_row g_avg[g, c] + [k == argsel[g, c]] g_max[g, c]); g_max / argsel only with max_and_avg.
+// A thread owns four channels (16-byte accesses) and a block 16 rows at a time: with tl_top_grad_kernel's 64 x 4 shape the
+// pass kept too few bytes in flight (576 us for 2 x 512 MB at the metric shape).
+__device__ __forceinline__ float4 tl_pool_dy4(long long r, int c, int ns, int N, float inv_ns, const float *gout, float4 zz,
+                                              float4 a, float4 cc, const float *pool_w, const int *argsel)
+{
+    const unsigned g = (unsigned)r / (unsigned)ns, k = (unsigned)r - g * (unsigned)ns;
+    const size_t go = (size_t)g * (argsel ? 2 * N : N) + c;
+    const float w = pool_w ? pool_w[r] : inv_ns;
+    const float4 ga = ld4(gout + go);
+    float4 q = make_float4(__fmul_rn(w, ga.x), __fmul_rn(w, ga.y), __fmul_rn(w, ga.z), __fmul_rn(w, ga.w));
+    if (argsel) {
+        const int4 s = *reinterpret_cast<const int4 *>(argsel + (size_t)g * N + c);
+        const float4 gm = ld4(gout + go + N);
+        if ((unsigned)s.x == k) q.x = __fadd_rn(q.x, gm.x);
+        if ((unsigned)s.y == k) q.y = __fadd_rn(q.y, gm.y);
+        if ((unsigned)s.z == k) q.z = __fadd_rn(q.z, gm.z);
+        if ((unsigned)s.w == k) q.w = __fadd_rn(q.w, gm.w);
+    }
+    q.x = __fadd_rn(__fmul_rn(a.x, zz.x), cc.x) > 0.0f ? q.x : 0.0f;
+    q.y = __fadd_rn(__fmul_rn(a.y, zz.y), cc.y) > 0.0f ? q.y : 0.0f;
+    q.z = __fadd_rn(__fmul_rn(a.z, zz.z), cc.z) > 0.0f ? q.z : 0.0f;
+    q.w = __fadd_rn(__fmul_rn(a.w, zz.w), cc.w) > 0.0f ? q.w : 0.0f;
+    return q;
+}
+
+__device__ __forceinline__ void tl_pool_acc(double *s1, double *s2, float4 q, float4 z)
+{
+    s1[0] += (double)q.x; s1[1] += (double)q.y; s1[2] += (double)q.z; s1[3] += (double)q.w;
+    s2[0] += (double)q.x * (double)z.x; s2[1] += (double)q.y * (double)z.y;
+    s2[2] += (double)q.z * (double)z.z; s2[3] += (double)q.w * (double)z.w;
+}
+
+// block (16 four-channel lanes x 16 row lanes) = 64 channels; grid (N / 64 rounded up, row parts <= kMaxParts)
+__global__ __launch_bounds__(256) void tl_pool_top_grad_kernel(long long rows, int ns, int N, const float *__restrict__ gout,
+                                                               const float *__restrict__ z, const float *__restrict__ save,
+                                                               const float *__restrict__ pool_w, const int *__restrict__ argsel,
+                                                               float *__restrict__ dy, double *__restrict__ stats)
+{
+    const int c = (blockIdx.x * 16 + (threadIdx.x & 15)) * 4;
+    const int ry = threadIdx.x >> 4;
+    const float inv_ns = 1.0f / (float)ns;
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+    if (c < N) {
+        const float4 a = ld4(save + 2 * N + c), cc = ld4(save + 3 * N + c);
+        const long long rstep = (long long)gridDim.y * 16;
+        long long r = (long long)blockIdx.y * 16 + ry;
+        for (; r + 3 * rstep < rows; r += 4 * rstep) {               // four rows per trip, the sums in row order
+            float4 z4[4], q4[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) z4[u] = ld4(z + (size_t)(r + u * rstep) * N + c);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) q4[u] = tl_pool_dy4(r + u * rstep, c, ns, N, inv_ns, gout, z4[u], a, cc, pool_w, argsel);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                *reinterpret_cast<float4 *>(dy + (size_t)(r + u * rstep) * N + c) = q4[u];
+                tl_pool_acc(s1, s2, q4[u], z4[u]);
+            }
+        }
+        for (; r < rows; r += rstep) {
+            const float4 zz = ld4(z + (size_t)r * N + c);
+            const float4 q = tl_pool_dy4(r, c, ns, N, inv_ns, gout, zz, a, cc, pool_w, argsel);
+            *reinterpret_cast<float4 *>(dy + (size_t)r * N + c) = q;
+            tl_pool_acc(s1, s2, q, zz);
+        }
+    }
+    __shared__ double sh[2][16][64];
+    const int x0 = (threadIdx.x & 15) * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { sh[0][ry][x0 + j] = s1[j]; sh[1][ry][x0 + j] = s2[j]; }
+    __syncthreads();
+    const int x = threadIdx.x, col = blockIdx.x * 64 + x;
+    if (x < 64 && col < N) {
+        double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { t1 += sh[0][i][x]; t2 += sh[1][i][x]; }
+        stats[((size_t)blockIdx.y * 2) * N + col] = t1;
+        stats[((size_t)blockIdx.y * 2 + 1) * N + col] = t2;
+    }
+}
+
 // ---- weight gradient: dW (KI x NO) = h^T dz, contraction over the rows -----------------------------------------------------
 struct TlWgrad {
     long long rows;
@@ -2475,15 +2625,17 @@ extern "C" int pn2_mlp_train_forward(long long rows, int nlayers, const pn2_bn_l
     return pn2_mlp_train_forward_ex(rows, nlayers, layers, group, x, pool_rows, out, argsel, zsel, ws, nullptr, stream);
 }
 
-extern "C" int pn2_mlp_train_forward_ex(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
-                                        const float *x, int pool_rows, float *out, int *argsel, float *zsel, void *ws,
-                                        const pn2_train_opts *opts, void *stream)
+// pooling: 0 max (the _ex entry), 1 avg, 2 weighted_avg, 3 max_and_avg (pn2_mlp_train_forward_pool; arguments checked there)
+static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
+                            int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
+                            const pn2_train_opts *opts, void *stream)
 {
     using namespace pn2;
     const Opts o = opts_of(opts);
     int widths[9];
     if (!layers_ok(rows, nlayers, layers, group, widths)) return PN2_E_ARG;
-    if ((!group && !x) || !out || !ws || (pool_rows && (!argsel || !zsel))) return PN2_E_NULL;
+    const bool want_max = pooling == 0 || pooling == 3;          // the extrema of the GEMM epilogue (E_POOL)
+    if ((!group && !x) || !out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w)) return PN2_E_NULL;
     if (pool_rows && (rows % pool_rows || (group && pool_rows != group->nsample))) return PN2_E_ARG;
     TlPlan pl;
     GroupDims gd;
@@ -2493,7 +2645,7 @@ extern "C" int pn2_mlp_train_forward_ex(long long rows, int nlayers, const pn2_b
     // forward: layer 1 on the vector units only WITHOUT features (with the input normals gathered per row the vector kernel
     // measured slower than the gathered GEMM: cls_msg forward 2.51 -> 2.57 ms; its backward counterpart is the one that pays)
     const bool coords_only = group && gd.cfeat == 0 && l1_coords_only(nlayers, widths, &gd, o);
-    const bool keep_top = top_stored(rows, nlayers, widths, pool_rows, o);
+    const bool keep_top = pooling != 0 || top_stored(rows, nlayers, widths, pool_rows, o);    // a mean needs z_L itself
     for (int l = 0; l < nlayers; ++l)
         if (!layers[l].z && (keep_top || l < nlayers - 1)) return PN2_E_NULL;
     hipStream_t st = as_stream(stream);
@@ -2568,7 +2720,7 @@ extern "C" int pn2_mlp_train_forward_ex(long long rows, int nlayers, const pn2_b
         else { amode = A_RELU; p.A = layers[l - 1].z; p.p0 = layers[l - 1].save + 2 * layers[l - 1].cout; p.p1 = layers[l - 1].save + 3 * layers[l - 1].cout; }
         p.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
         p.bias = nullptr;                                        // see the comment above the loop
-        p.emode = (last && pool_rows) ? E_POOL : E_STORE;
+        p.emode = (last && pool_rows && want_max) ? E_POOL : E_STORE;
         p.out = (last && !keep_top) ? nullptr : L.z;              // the pooled top layer of a large level is never written
         p.stats = reinterpret_cast<double *>(base + pl.stats[l]);
         if (p.emode == E_POOL) {
@@ -2586,15 +2738,28 @@ extern "C" int pn2_mlp_train_forward_ex(long long rows, int nlayers, const pn2_b
             if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
                                 reinterpret_cast<const double *>(base + pl.stats[l]), nparts, L.cout, (double)rows, L.gamma, L.beta,
                                 L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
-        if (last && pool_rows) {
+        // max_and_avg: the max half as pooling 0 computes it, into the workspace behind the plan; the average kernel places it
+        float *maxv = pooling == 3 ? reinterpret_cast<float *>(base + pl.total) : nullptr;
+        if (last && pool_rows && want_max) {
             const long long groups = rows / pool_rows;
             const int prow = pool_rows == 16 ? 16 : 32;
             long long blocks = (groups * L.cout + 255) / 256;
             if (blocks > 4096) blocks = 4096;
             if (int rc = launch(tl_pool_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, groups, L.cout, pool_rows / prow,
                                 prow, (const float *)p.pmax, (const int *)p.pamax, (const float *)L.gamma,
-                                (const float *)L.save, out, argsel, zsel)) return rc;
-        } else if (last) {
+                                (const float *)L.save, maxv ? maxv : out, argsel, zsel)) return rc;
+        }
+        if (last && pool_rows && pooling != 0) {
+            const long long groups = rows / pool_rows;
+            if (pooling == 2) {
+                if (int rc = launch(tl_pool_weights_kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, st, groups, pool_rows,
+                                    group->n, group->m, group->xyz, group->new_xyz, group->idx, pool_w)) return rc;
+            }
+            long long blocks = (groups * (L.cout / 4) + 255) / 256;
+            if (blocks > 8192) blocks = 8192;
+            if (int rc = launch(tl_pool_avg_kernel, dim3((unsigned)blocks), dim3(256), 0, st, groups, pool_rows, L.cout, (const float *)L.z,
+                                (const float *)L.save, (const float *)(pooling == 2 ? pool_w : nullptr), (const float *)maxv, out)) return rc;
+        } else if (last && !pool_rows) {
             const long long total4 = rows * L.cout / 4;
             long long blocks = (total4 + 255) / 256;
             if (blocks > 8192) blocks = 8192;
@@ -2603,6 +2768,13 @@ extern "C" int pn2_mlp_train_forward_ex(long long rows, int nlayers, const pn2_b
         }
     }
     return PN2_OK;
+}
+
+extern "C" int pn2_mlp_train_forward_ex(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                        const float *x, int pool_rows, float *out, int *argsel, float *zsel, void *ws,
+                                        const pn2_train_opts *opts, void *stream)
+{
+    return tl_train_forward(rows, nlayers, layers, group, x, pool_rows, 0, out, argsel, zsel, nullptr, ws, opts, stream);
 }
 
 extern "C" int pn2_mlp_train_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
@@ -2614,17 +2786,24 @@ extern "C" int pn2_mlp_train_backward(long long rows, int nlayers, const pn2_bn_
                                      grad_points, reproducible, ws, nullptr, stream);
 }
 
-extern "C" int pn2_mlp_train_backward_ex(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
-                                         const float *x, int pool_rows, const float *out, const int *argsel, const float *zsel,
-                                         const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points,
-                                         int reproducible, void *ws, const pn2_train_opts *opts, void *stream)
+// pooling 1-3 (pn2_mlp_train_backward_pool): the averaged top layer is an UNPOOLED one from here on -- its dense gradient
+// (tl_pool_top_grad_kernel) enters the passes of the FP levels' top layer, and everything below runs unchanged
+static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
+                             int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel, const float *pool_w,
+                             const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points, int reproducible,
+                             void *ws, const pn2_train_opts *opts, void *stream)
 {
     using namespace pn2;
     const Opts o = opts_of(opts);
     const int cus = device_cus();
     int widths[9];
     if (!layers_ok(rows, nlayers, layers, group, widths)) return PN2_E_ARG;
-    if ((!group && !x) || !out || !grad_out || !ws || (pool_rows && (!argsel || !zsel))) return PN2_E_NULL;
+    const bool want_max = pooling == 0 || pooling == 3;
+    if ((!group && !x) || !out || !grad_out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w))
+        return PN2_E_NULL;
+    const int avg_rows = pooling ? pool_rows : 0;       // > 0: the group size of the averaged top layer
+    if (pooling && (!group || avg_rows <= 0 || rows % avg_rows || avg_rows != group->nsample)) return PN2_E_ARG;
+    if (pooling) pool_rows = 0;
     for (int l = 0; l < nlayers; ++l)
         if (!layers[l].grad_weight || !layers[l].grad_gamma || !layers[l].grad_beta) return PN2_E_NULL;
     TlPlan pl;
@@ -2705,7 +2884,14 @@ extern "C" int pn2_mlp_train_backward_ex(long long rows, int nlayers, const pn2_
     const pn2_bn_layer &T = layers[nlayers - 1];
     int nparts[8];                                      // rows of each layer's partial-sum array
     // top of the stack: dy_L and its two column sums
-    if (pool_rows) {
+    if (avg_rows) {
+        long long gy = (rows + 255) / 256;
+        if (gy > kMaxParts) gy = kMaxParts;
+        nparts[nlayers - 1] = (int)gy;
+        if (int rc = launch(tl_pool_top_grad_kernel, dim3((unsigned)((T.cout + 63) / 64), (unsigned)gy), dim3(256), 0, st, rows, avg_rows,
+                            T.cout, grad_out, (const float *)T.z, (const float *)T.save, pool_w, pooling == 3 ? argsel : nullptr, ga,
+                            reinterpret_cast<double *>(base + pl.stats[nlayers - 1]))) return rc;
+    } else if (pool_rows) {
         const long long groups = rows / pool_rows;
         long long gy = (groups + 63) / 64;
         if (gy > kMaxParts) gy = kMaxParts;
@@ -3011,4 +3197,67 @@ extern "C" int pn2_mlp_train_backward_ex(long long rows, int nlayers, const pn2_
         float *tmp = gcur; gcur = gnext; gnext = tmp;
     }
     return sd.join();                                              // everything of this call is ordered before what the caller enqueues next
+}
+
+extern "C" int pn2_mlp_train_backward_ex(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                         const float *x, int pool_rows, const float *out, const int *argsel, const float *zsel,
+                                         const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points,
+                                         int reproducible, void *ws, const pn2_train_opts *opts, void *stream)
+{
+    return tl_train_backward(rows, nlayers, layers, group, x, pool_rows, 0, out, argsel, zsel, nullptr, grad_out, grad_x,
+                             grad_feat_rows, grad_points, reproducible, ws, opts, stream);
+}
+
+// ---- the pooling modes of the training node (pn2_mlp_train_*_pool, include/pn2ops.h) -------------------------------------
+namespace pn2 {
+// 0 ok, else the PN2_E_* code the entries return before anything is launched
+static int pool_args(int pool_rows, int pooling, bool grouped)
+{
+    if (pooling < 0 || pooling > 3) return PN2_E_ARG;
+    if (pooling == 0) return PN2_OK;
+    if (!grouped) return PN2_E_NULL;
+    return pool_rows > 0 ? PN2_OK : PN2_E_ARG;
+}
+}  // namespace pn2
+
+extern "C" int pn2_mlp_train_pool_supported(long long rows, int nlayers, const int *widths, int pool_rows, int pooling)
+{
+    pn2::TlPlan pl;
+    if (!widths || nlayers < 1 || nlayers > 8 || pooling < 0 || pooling > 3 || (pooling && pool_rows <= 0)) return 0;
+    if (pool_rows && rows % pool_rows) return 0;
+    const pn2::Opts o = pn2::opts_of(nullptr);
+    if (!pn2::tl_plan(rows, nlayers, widths, pool_rows, 0, pl, nullptr, o)) return 0;
+    return pn2::tl_plan(rows, nlayers, widths, pooling ? 0 : pool_rows, 1, pl, nullptr, o) ? 1 : 0;
+}
+
+extern "C" long long pn2_mlp_train_ws_bytes_pool(long long rows, int nlayers, const int *widths, int pool_rows, int pooling,
+                                                 int backward, const int *group_dims, const pn2_train_opts *opts)
+{
+    if (pooling == 0) return pn2_mlp_train_ws_bytes_ex(rows, nlayers, widths, pool_rows, backward, group_dims, opts);
+    if (pooling < 0 || pooling > 3 || pool_rows <= 0 || !widths || nlayers < 1 || nlayers > 8) return -1;
+    const long long b = pn2_mlp_train_ws_bytes_ex(rows, nlayers, widths, backward ? 0 : pool_rows, backward, group_dims, opts);
+    if (b < 0 || backward || pooling != 3 || rows % pool_rows) return b;
+    return b + (long long)pn2::align_up((size_t)(rows / pool_rows) * widths[nlayers] * sizeof(float));   // the max half (forward)
+}
+
+extern "C" int pn2_mlp_train_forward_pool(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                          int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
+                                          const pn2_train_opts *opts, void *stream)
+{
+    if (int rc = pn2::pool_args(pool_rows, pooling, group != nullptr)) return rc;
+    if (pooling == 0)
+        return tl_train_forward(rows, nlayers, layers, group, nullptr, pool_rows, 0, out, argsel, zsel, nullptr, ws, opts, stream);
+    return tl_train_forward(rows, nlayers, layers, group, nullptr, pool_rows, pooling, out, pooling == 3 ? argsel : nullptr,
+                            pooling == 3 ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, ws, opts, stream);
+}
+
+extern "C" int pn2_mlp_train_backward_pool(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                           int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel,
+                                           const float *pool_w, const float *grad_out, float *grad_feat_rows, float *grad_points,
+                                           int reproducible, void *ws, const pn2_train_opts *opts, void *stream)
+{
+    if (int rc = pn2::pool_args(pool_rows, pooling, group != nullptr)) return rc;
+    return tl_train_backward(rows, nlayers, layers, group, nullptr, pool_rows, pooling, out, pooling == 3 || pooling == 0 ? argsel : nullptr,
+                             pooling == 3 || pooling == 0 ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, grad_out, nullptr,
+                             grad_feat_rows, grad_points, reproducible, ws, opts, stream);
 }

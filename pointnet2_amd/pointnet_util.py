@@ -197,15 +197,18 @@ class PointnetSAModule(nn.Module):
         return sa_mlp.supported(cin, self.mlp.widths, self.nsample)
 
     def _train_fused_ok(self, xyz, points):
-        """Training (batch-statistics batch norm, autograd) with max pooling on a stack pn2_mlp_train_forward covers:
-        conv 1x1 + BN + ReLU triples, rows a multiple of 32, nsample 16 or a multiple of 32 (train_mlp.py)."""
-        if not self.fused_mlp or not self.training or self.pooling != "max" or not xyz.is_cuda:
+        """Training (batch-statistics batch norm, autograd) on a stack pn2_mlp_train_forward covers: conv 1x1 + BN + ReLU
+        triples, rows a multiple of 32, nsample 16 or a multiple of 32 (train_mlp.py); avg / weighted_avg / max_and_avg
+        where pn2_mlp_train_pool_supported says so."""
+        if not self.fused_mlp or not self.training or not xyz.is_cuda:
             return False
         if (torch.is_grad_enabled() and xyz.requires_grad) or (points is not None and not self.use_xyz):
             return False
         b, n, _ = xyz.shape
         ns = n if self.group_all else self.nsample
         rows = b * (1 if self.group_all else self.npoint) * ns
+        if self.pooling != "max":
+            return train_mlp.pool_supported(self.mlp.net, rows, ns, self.pooling)
         return train_mlp.stack_supported(self.mlp.net, rows, ns, True)
 
     def _packed(self, device, nsample=None):
@@ -256,7 +259,7 @@ class PointnetSAModule(nn.Module):
         new_xyz, idx = g.new_xyz_for(xyz), g.idx
         if self._train_fused_ok(xyz, points):
             self.last_path = "fused_train"
-            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True)
+            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling)
             return new_xyz, self._post(out), idx
         if self._fused_ok(xyz, points):
             self.last_path = "fused"
@@ -275,20 +278,20 @@ class PointnetSAModule(nn.Module):
             return self._forward_on(xyz, points, geometry.wait())
         if self._train_fused_ok(xyz, points):
             # training: the level's geometry in the fused launches, then ONE autograd node for gather + layer stack
-            # (batch-statistics batch norm) + max-pool, forward and backward on the matrix cores (train_mlp.py)
+            # (batch-statistics batch norm) + pooling, forward and backward on the matrix cores (train_mlp.py)
             self.last_path = "fused_train"
             if self.group_all:
                 b, n, _ = xyz.shape
                 new_xyz = torch.zeros((b, 1, 3), dtype=torch.float32, device=xyz.device)
                 idx = torch.arange(n, dtype=torch.int32, device=xyz.device).reshape(1, 1, n).repeat(b, 1, 1)
-                out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True)
+                out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True, self.pooling)
                 return new_xyz, self._post(out), idx
             if self.knn:
                 _, new_xyz = farthest_point_sample_gather(self.npoint, xyz)
                 _, idx = knn_point(self.nsample, xyz, new_xyz)
             else:
                 _, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
-            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True)
+            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling)
             return new_xyz, self._post(out), idx
         if self.group_all and self._fused_ok(xyz, points):
             # sample_and_group_all (:59-84) + the layer stack + reduce_max in ONE kernel: new_xyz = origin, the

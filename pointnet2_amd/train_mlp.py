@@ -128,7 +128,22 @@ def stack_supported(net, rows, pool_rows=0, grouped=True):
 
 class _Level:
     """Non-tensor description of one call (what the autograd node needs besides its differentiable inputs)."""
-    __slots__ = ("pairs", "rows", "pool_rows", "xyz", "new_xyz", "idx", "b", "n", "m", "nsample", "xyz_first", "grouped")
+    __slots__ = ("pairs", "rows", "pool_rows", "xyz", "new_xyz", "idx", "b", "n", "m", "nsample", "xyz_first", "grouped", "pooling")
+
+
+# pointnet_sa_module's pooling modes (utils/pointnet_util.py:128-142) -> the library's codes (pn2_mlp_train_forward_pool)
+POOLING = {"max": 0, "avg": 1, "weighted_avg": 2, "max_and_avg": 3}
+
+
+def pool_supported(net, rows, ns, pooling):
+    """Can the fused training node run this stack with this pooling on `rows` grouped rows in groups of `ns`?"""
+    code = POOLING.get(pooling)
+    if code is None or not stack_supported(net, rows, ns, True):
+        return False
+    pairs = conv_bn_pairs(net)
+    widths = [pairs[0][0].in_channels] + [c.out_channels for c, _ in pairs]
+    arr = (ctypes.c_int * len(widths))(*widths)
+    return bool(_C.lib().pn2_mlp_train_pool_supported(rows, len(widths) - 1, arr, ns, code))
 
 
 def _layer_array(level, weights, biases, gammas, betas, zs, saves, grads=None, update_running=True):
@@ -177,6 +192,13 @@ def _ws(rows, widths, pool_rows, backward, dev, gdims=None, opts=None):
     arr = (ctypes.c_int * len(widths))(*widths)
     nbytes = _C.lib().pn2_mlp_train_ws_bytes_ex(rows, len(widths) - 1, arr, pool_rows, backward, gdims, opts)
     require(nbytes >= 0, "pn2_mlp_train: unsupported stack (rows %% 32, widths %% 4, pool group 16 or a multiple of 32)")
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+
+
+def _ws_pool(rows, widths, pool_rows, code, backward, dev, gdims=None, opts=None):
+    arr = (ctypes.c_int * len(widths))(*widths)
+    nbytes = _C.lib().pn2_mlp_train_ws_bytes_pool(rows, len(widths) - 1, arr, pool_rows, code, backward, gdims, opts)
+    require(nbytes >= 0, "pn2_mlp_train: unsupported stack or pooling")
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
 
 
@@ -232,31 +254,44 @@ class _TrainMLP(torch.autograd.Function):
         widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
         warr = (ctypes.c_int * len(widths))(*widths)
         opts = _opts()
-        keep_top = bool(_C.lib().pn2_mlp_train_top_stored_ex(rows, n, warr, level.pool_rows, opts))
+        code = level.pooling if level.pool_rows else 0
+        # (the averaging modes always keep z_L: a mean does not commute with batch norm + ReLU)
+        keep_top = code != 0 or bool(_C.lib().pn2_mlp_train_top_stored_ex(rows, n, warr, level.pool_rows, opts))
         # pre-norm tensors z_l, the only activations kept; the pooled top layer's is not even written on large levels
         zs = [torch.empty((rows, w), dtype=torch.float32, device=dev) if (keep_top or l < n - 1) else None
               for l, w in enumerate(widths[1:])]
         saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
         cl = widths[-1]
+        pool_w = None
         if level.pool_rows:
             groups = rows // level.pool_rows
-            out = torch.empty((groups, cl), dtype=torch.float32, device=dev)
-            argsel = torch.empty((groups, cl), dtype=torch.int32, device=dev)
-            zsel = torch.empty((groups, cl), dtype=torch.float32, device=dev)
+            out = torch.empty((groups, 2 * cl if code == 3 else cl), dtype=torch.float32, device=dev)
+            # argsel / zsel: the max's selection (max, max_and_avg); an empty placeholder for the averages
+            argsel = torch.empty((groups, cl) if code in (0, 3) else (0,), dtype=torch.int32, device=dev)
+            zsel = torch.empty((groups, cl), dtype=torch.float32, device=dev) if code in (0, 3) else None
+            if code == 2:
+                pool_w = torch.empty((rows,), dtype=torch.float32, device=dev)
         else:
             out = torch.empty((rows, cl), dtype=torch.float32, device=dev)
             argsel = zsel = None
-        ws = _ws(rows, widths, level.pool_rows, 0, dev, _group_dims(level, x), opts)
         arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
         grp = _group_struct(level, x) if level.grouped else None
-        with on_device(dev):
-            _C.check(_C.lib().pn2_mlp_train_forward_ex(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
-                                                       None if level.grouped else ptr(x), level.pool_rows, ptr(out), ptr(argsel),
-                                                       ptr(zsel), ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward")
+        if code:
+            ws = _ws_pool(rows, widths, level.pool_rows, code, 0, dev, _group_dims(level, x), opts)
+            with on_device(dev):
+                _C.check(_C.lib().pn2_mlp_train_forward_pool(rows, n, arr, ctypes.byref(grp), level.pool_rows, code, ptr(out),
+                                                             ptr(argsel) if code == 3 else None, ptr(zsel), ptr(pool_w), ptr(ws),
+                                                             opts, stream_ptr(dev)), "mlp_train_forward_pool")
+        else:
+            ws = _ws(rows, widths, level.pool_rows, 0, dev, _group_dims(level, x), opts)
+            with on_device(dev):
+                _C.check(_C.lib().pn2_mlp_train_forward_ex(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
+                                                           None if level.grouped else ptr(x), level.pool_rows, ptr(out), ptr(argsel),
+                                                           ptr(zsel), ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward")
         nbt = [bn.num_batches_tracked for _, bn in level.pairs if bn.track_running_stats and bn.num_batches_tracked is not None]
         if nbt:
             torch._foreach_add_(nbt, 1)                        # one launch for the level's counters
-        ctx.level, ctx.widths = level, widths
+        ctx.level, ctx.widths, ctx.code = level, widths, code
         ctx.opts = dict(_OPTS)                              # backward must see the organisation forward ran under
         ctx.has_x = x is not None
         ctx.nbias = [b is not None for b in biases]
@@ -264,7 +299,7 @@ class _TrainMLP(torch.autograd.Function):
         saved = [t for t in [x] if t is not None] + weights + [b for b in biases if b is not None] + gammas + betas + \
             [z for z in zs if z is not None] + saves + [out]
         if level.pool_rows:
-            saved += [argsel, zsel]
+            saved += [argsel] + [t for t in (zsel, pool_w) if t is not None]
             ctx.mark_non_differentiable(argsel)
         ctx.save_for_backward(*saved)
         if level.pool_rows:
@@ -284,7 +319,10 @@ class _TrainMLP(torch.autograd.Function):
         zs = [sv.pop(0) if has else None for has in ctx.nz]
         saves = [sv.pop(0) for _ in range(n)]
         out = sv.pop(0)
-        argsel, zsel = (sv.pop(0), sv.pop(0)) if level.pool_rows else (None, None)
+        code = ctx.code
+        argsel = sv.pop(0) if level.pool_rows else None
+        zsel = sv.pop(0) if level.pool_rows and code in (0, 3) else None
+        pool_w = sv.pop(0) if code == 2 else None
         dev = out.device
         rows = level.rows
         grad_out = f32(grad_out, "grad_out")
@@ -307,7 +345,8 @@ class _TrainMLP(torch.autograd.Function):
             grad_rows = torch.empty((rows, x.shape[2]), dtype=torch.float32, device=dev)
         elif need_x:
             grad_x = torch.empty((rows, widths[0]), dtype=torch.float32, device=dev)
-        ws = _ws(rows, widths, level.pool_rows, 1, dev, gdims, opts)
+        ws = _ws_pool(rows, widths, level.pool_rows, code, 1, dev, gdims, opts) if code else \
+            _ws(rows, widths, level.pool_rows, 1, dev, gdims, opts)
         if _KEEP_WS[0]:
             _KEEP_WS[1] = (ws, rows, widths, level.pool_rows)
         arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
@@ -315,11 +354,18 @@ class _TrainMLP(torch.autograd.Function):
             arr[l].grad_accumulate = 1 if direct[l] else 0
         grp = _group_struct(level, x) if level.grouped else None
         with on_device(dev):
-            _C.check(_C.lib().pn2_mlp_train_backward_ex(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
-                                                        None if level.grouped else ptr(x), level.pool_rows, ptr(out), ptr(argsel),
-                                                        ptr(zsel), ptr(grad_out), ptr(grad_x), ptr(grad_rows), ptr(grad_pts),
-                                                        1 if is_deterministic() else 0, ptr(ws), opts, stream_ptr(dev)),
-                     "mlp_train_backward")
+            if code:
+                _C.check(_C.lib().pn2_mlp_train_backward_pool(rows, n, arr, ctypes.byref(grp), level.pool_rows, code, ptr(out),
+                                                              ptr(argsel) if code == 3 else None, ptr(zsel), ptr(pool_w),
+                                                              ptr(grad_out), ptr(grad_rows), ptr(grad_pts),
+                                                              1 if is_deterministic() else 0, ptr(ws), opts, stream_ptr(dev)),
+                         "mlp_train_backward_pool")
+            else:
+                _C.check(_C.lib().pn2_mlp_train_backward_ex(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
+                                                            None if level.grouped else ptr(x), level.pool_rows, ptr(out), ptr(argsel),
+                                                            ptr(zsel), ptr(grad_out), ptr(grad_x), ptr(grad_rows), ptr(grad_pts),
+                                                            1 if is_deterministic() else 0, ptr(ws), opts, stream_ptr(dev)),
+                         "mlp_train_backward")
             if grad_pts is not None:
                 grad_x = grad_pts
             if grad_rows is not None:
@@ -364,11 +410,15 @@ def _params(pairs):
     return out
 
 
-def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True):
-    """Training-mode shared MLP + max-pool of one SA level / one MSG scale.
+def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max"):
+    """Training-mode shared MLP + pooling of one SA level / one MSG scale.
     net: nn.Sequential of (Conv2d 1x1, BatchNorm2d, ReLU) triples; xyz (b,n,3); new_xyz (b,m,3) or None and idx
     (b,m,nsample) i32 or None (both None: the group_all level); points (b,n,c) or None.
-    -> (b, m, cout) pooled features (differentiable w.r.t. points and the parameters), argsel (b, m, cout) i32."""
+    pooling: "max" (default), "avg", "weighted_avg" or "max_and_avg" (utils/pointnet_util.py:128-142; the last gives
+    (b, m, 2 cout) = concat([avg, max])).
+    -> (b, m, cout) pooled features (differentiable w.r.t. points and the parameters), argsel (b, m, cout) i32 -- the max's
+    selection; None for avg and weighted_avg."""
+    require(pooling in POOLING, "unknown pooling %r" % (pooling,))
     pairs = conv_bn_pairs(net)
     require(pairs is not None, "sa_mlp_train expects Conv 1x1 + BatchNorm + ReLU triples")
     xyz = f32(xyz, "xyz")
@@ -392,6 +442,7 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True):
     lv.b, lv.n = b, n
     lv.rows = b * lv.m * lv.nsample
     lv.pool_rows = lv.nsample
+    lv.pooling = POOLING[pooling]
     if points is not None:
         points = f32(points, "points")
         require(points.dim() == 3 and tuple(points.shape[:2]) == (b, n),
@@ -400,8 +451,12 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True):
     cin = 3 + (points.shape[2] if points is not None else 0)
     require(pairs[0][0].in_channels == cin, "the first layer expects %d channels, got %d" % (pairs[0][0].in_channels, cin))
     require(stack_supported(net, lv.rows, lv.pool_rows, True), "unsupported stack for the fused training path")
+    require(lv.pooling == 0 or pool_supported(net, lv.rows, lv.pool_rows, pooling),
+            "unsupported stack for the fused training path with pooling %r" % (pooling,))
     same_device(xyz, pairs[0][0].weight)
     out, argsel = _TrainMLP.apply(lv, points, *_params(pairs))
+    if lv.pooling in (1, 2):
+        return out.view(b, lv.m, -1), None
     return out.view(b, lv.m, -1), argsel.view(b, lv.m, -1)
 
 
@@ -424,7 +479,7 @@ def fp_mlp_train(net, x, cin=None):
     lv.pairs, lv.grouped, lv.xyz_first = pairs, False, True
     lv.xyz = lv.new_xyz = lv.idx = None
     lv.b, lv.n, lv.m, lv.nsample = b, n, 0, 0
-    lv.rows, lv.pool_rows = b * n, 0
+    lv.rows, lv.pool_rows, lv.pooling = b * n, 0, 0
     require(stack_supported(net, lv.rows, 0, False), "unsupported stack for the fused training path")
     require(pairs[0][0].in_channels == c, "the first layer expects %d channels, got %d" % (pairs[0][0].in_channels, c))
     params = _params(pairs)
