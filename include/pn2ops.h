@@ -535,6 +535,35 @@ int pn2_mlp_train_backward_pool(long long rows, int nlayers, const pn2_bn_layer 
                                 const float *pool_w, const float *grad_out, float *grad_feat_rows, float *grad_points,
                                 int reproducible, void *ws, const pn2_train_opts *opts, void *stream);
 
+/* The training node of a feature-propagation level (pointnet_fp_module, utils/pointnet_util.py:211-226) with the interpolation
+ * INSIDE it. Layer 1 and three_interpolate are both linear, so
+ *     z_1 = [interp(points2), points1] W_1 = interp(points2 W1a) + points1 W1b
+ * (W1a: the first c2 input rows of layers[0]'s weight, W1b: the last c1 -- the reference's concat order, :219). Passes
+ * (csrc/train_mlp_fp.hip): forward Q = points2 W1a over the b m KNOWN points, z_1 = points1 W1b + (Q[i1] w1 + Q[i2] w2) + Q[i3] w3
+ * over the b n rows with its batch moments, layers 2..L as pn2_mlp_train_forward; backward layers L..2 as
+ * pn2_mlp_train_backward, then dz_1, S = three_interpolate_grad(dz_1) onto (b m, cout_1) (pn2_three_interpolate_grad_seg;
+ * `reproducible` = its sorted-segment mode), dW1a = points2^T S and grad_points2 = S W1a^T over the b m known points,
+ * dW1b = points1^T dz_1 and grad_points1 = dz_1 W1b^T over the b n rows. The (b, n, c2 + c1) input and its gradient are never
+ * written. weight (b, n, 3): the interpolation weights from dist, bit-identical to pn2_fp_interp_concat's, written by forward
+ * and read by backward. layers[0].cin = c2 + c1 (neither needs to be a multiple of 4), weights and grad_weight in the conv
+ * layout; b n a multiple of 32; at most 7 layers; pn2_mlp_train_fp_supported says which widths run. grad_points2 /
+ * grad_points1: NULL = not wanted. Argument errors return PN2_E_ARG / PN2_E_NULL before anything is launched. */
+typedef struct pn2_fp_src {
+    int b, n, m, c2, c1;
+    const float *points2;          /* (b,m,c2) features of the known points */
+    const float *points1;          /* (b,n,c1) skip features; NULL iff c1 == 0 */
+    const int *idx;                /* (b,n,3) three_nn's indices */
+    const float *dist;             /* (b,n,3) three_nn's squared distances (forward) */
+} pn2_fp_src;
+int pn2_mlp_train_fp_supported(int b, int n, int m, int c2, int c1, int nlayers, const int *widths /* c2 + c1, cout_1 .. cout_L */);
+long long pn2_mlp_train_ws_bytes_fp(int b, int n, int m, int c2, int c1, int nlayers, const int *widths, int backward,
+                                    const pn2_train_opts *opts);
+int pn2_mlp_train_forward_fp(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *src, float *out, float *weight, void *ws,
+                             const pn2_train_opts *opts, void *stream);
+int pn2_mlp_train_backward_fp(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *src, const float *weight, const float *out,
+                              const float *grad_out, float *grad_points2, float *grad_points1, int reproducible, void *ws,
+                              const pn2_train_opts *opts, void *stream);
+
 /* The input rows of a feature-propagation level's layer stack in ONE launch (pointnet_fp_module, utils/pointnet_util.py:211-219):
  * inverse-distance weights from three_nn's `dist`, three_interpolate of points2 (b,m,c2), concatenation with the skip features
  * points1 (b,n,c1; NULL with c1 = 0), zero columns up to `pitch` (a multiple of 4 >= c2 + c1: the training entry points read

@@ -99,6 +99,10 @@ _SIGNATURES = {
     "pn2_mlp_train_ws_bytes_pool": [_ll, _i, _vp, _i, _i, _i, _vp, _vp],
     "pn2_mlp_train_forward_pool": [_ll, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_mlp_train_backward_pool": [_ll, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "pn2_mlp_train_fp_supported": [_i, _i, _i, _i, _i, _i, _vp],
+    "pn2_mlp_train_ws_bytes_fp": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp],
+    "pn2_mlp_train_forward_fp": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_mlp_train_backward_fp": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "pn2_fps_temp_floats": ctypes.c_longlong,
@@ -111,6 +115,7 @@ _RESTYPES = {
     "pn2_mlp_train_ws_bytes": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_ex": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_pool": ctypes.c_longlong,
+    "pn2_mlp_train_ws_bytes_fp": ctypes.c_longlong,
     "pn2_sample_and_group_status_offset": ctypes.c_longlong,
     "pn2_ball_threshold": ctypes.c_float,
     "pn2_version": ctypes.c_char_p,

@@ -849,6 +849,7 @@ struct TlWgrad {
     int group_rows;
     float *partial;             // [slab][workgroup][tus * tts tiles][1024]
     size_t partial_cap;         // host side: bytes planned for `partial` (0 = unchecked); a launch whose slabs need more is refused
+    int kout;                   // host side: rows of dW the reduction writes (0 = KI; a zero-padded input: its true width)
     int tus, tts, tslabs;       // tiles of h / of dz per slab; slabs along dz
     // ---- the layer's DATA gradient in the same pass (template flag DY; one slab only): dy_{l-1} = (second operand) . Wt,
     // contraction over the k tiles the block image already holds, see "One pass per layer" below
@@ -1933,6 +1934,7 @@ struct TlPlan {
     size_t l1p;                 // layer 1 per point: forward P (b n, cout_1); backward S (b n, cout_1)
     size_t l1seg, l1part, l1coef;   // backward: scratch of the segmented reduction, dW1x partials (256, 3, cout_1), identity coefficients
     size_t l1xg, l1mom, l1a;        // backward, level without features: centred coordinates of every row, their moments, x^T dy_1 partials
+    size_t fpw, fp2, fp1, fpg2;     // FP level (FpL1): W1b's operand tiles, zero-padded points2 / points1, grad_points2 staged
     size_t tickets;             // kFinTickets counters of the folded finalisations (TlFin), zeroed by the direction's pack launch
     size_t total;
 };
@@ -1949,6 +1951,39 @@ static inline int top_cols(int kin, int cl) { return tiles(cl) * 32 + tiles(kin)
 
 // group dims as the C ABI passes them to the workspace query: b, n, m, nsample, cfeat, has_idx
 struct GroupDims { int b, n, m, nsample, cfeat, has_idx; };
+
+// An FP level whose layer 1 runs once per KNOWN point (pn2_mlp_train_*_fp; its kernels and entry points: train_mlp_fp.hip)
+struct FpL1 {
+    int b, n, m, c2, c1;
+    int c2p, c1p;                    // the widths rounded up to a multiple of 4 (the GEMMs read rows 16 bytes at a time)
+    long long rows, bm, mp;          // b n unknown points; b m known points, and that rounded up to a multiple of 32
+    const float *points2, *points1;
+    const int *idx;
+    const float *dist;
+    float *weight_out;               // forward: the interpolation weights (b,n,3)
+    const float *weight;             // backward: the same
+    float *grad_points2, *grad_points1;
+    bool pad2() const { return mp != bm || c2p != c2; }     // points2 enters as a zero-padded copy (mp, c2p)
+    bool pad1() const { return c1 > 0 && c1p != c1; }       // points1 as a zero-padded copy (rows, c1p)
+    bool gstage2() const { return mp != bm; }               // grad_points2 is written to the workspace (mp rows), then copied
+};
+
+static FpL1 fp_l1(const pn2_fp_src *s)
+{
+    FpL1 f;
+    memset(&f, 0, sizeof(f));
+    f.b = s->b; f.n = s->n; f.m = s->m; f.c2 = s->c2; f.c1 = s->c1;
+    f.c2p = (s->c2 + 3) / 4 * 4; f.c1p = (s->c1 + 3) / 4 * 4;
+    f.rows = (long long)s->b * s->n; f.bm = (long long)s->b * s->m; f.mp = (f.bm + 31) / 32 * 32;
+    f.points2 = s->points2; f.points1 = s->points1; f.idx = s->idx; f.dist = s->dist;
+    return f;
+}
+
+// ---- defined in train_mlp_fp.hip ----
+int fp_launch_pad(const float *src, long long rows_in, int c, long long rows_out, int cp, float *dst, hipStream_t st);
+int fp_launch_l1_forward(long long rows, int n, int m, int C, const int *idx, const float *dist, float *weight, const float *Q,
+                         float *z, bool add, double *stats, int max_parts, hipStream_t st, int *nparts);
+int fp_launch_l1_dz(long long rows, int C, const float *z, float *g, const float *coef, hipStream_t st);
 
 // Is layer 1 of this grouped level evaluated once per POINT (tl_l1_forward_kernel)? One rule for forward, backward, the
 // workspace sizes and the caller's allocation of the feature gradient.
@@ -2025,7 +2060,7 @@ static WgradShape wgrad_plan_shape(long long rows, int KI, int NO, bool gather, 
 }
 
 static bool tl_plan(long long rows, int nlayers, const int *widths, int pool_rows, int backward, TlPlan &pl,
-                    const GroupDims *gd, const Opts &o)
+                    const GroupDims *gd, const Opts &o, const FpL1 *fp = nullptr)
 {
     if (rows <= 0 || rows % 32 || rows >= (1ll << 31) || nlayers < 1 || nlayers > 8) return false;
     if (pool_rows && pool_rows != 16 && pool_rows % 32) return false;
@@ -2042,6 +2077,10 @@ static bool tl_plan(long long rows, int nlayers, const int *widths, int pool_row
             const long long bn = (long long)gd->b * gd->n;
             const GemmShape gp = backward ? gemm_shape(bn, cout, gd->cfeat, o) : gemm_shape(bn, gd->cfeat, cout, o);
             if (gp.pack_bytes > pb) pb = gp.pack_bytes;
+        }
+        if (l == 0 && fp) {                                          // W1a's tiles for the GEMMs over the known points
+            const GemmShape ga = backward ? gemm_shape(fp->mp, cout, fp->c2, o) : gemm_shape(fp->mp, fp->c2p, cout, o);
+            if (ga.pack_bytes > pb) pb = ga.pack_bytes;
         }
         pl.pack[l] = off; off = align_up(off + pb);
         pl.stats[l] = off; off = align_up(off + sizeof(double) * 2 * cout * kMaxParts);
@@ -2078,6 +2117,15 @@ static bool tl_plan(long long rows, int nlayers, const int *widths, int pool_row
             if (w.partial_bytes > p1) p1 = w.partial_bytes;
             if (w.partial2_bytes > p2) p2 = w.partial2_bytes;
         }
+        if (fp) {                                                    // dW1a over the known points, dW1b over the rows
+            for (int h = 0; h < 2; ++h) {
+                if (h == 1 && fp->c1 == 0) break;
+                const WgradShape w = h == 0 ? wgrad_plan_shape(fp->mp, fp->c2p, widths[1], false, o)
+                                            : wgrad_plan_shape(rows, fp->c1p, widths[1], false, o);
+                if (w.partial_bytes > p1) p1 = w.partial_bytes;
+                if (w.partial2_bytes > p2) p2 = w.partial2_bytes;
+            }
+        }
         pl.partial = off; off = align_up(off + p1);
         pl.partial2 = off; off = align_up(off + p2);
         pl.partial_cap = p1;
@@ -2106,6 +2154,23 @@ static bool tl_plan(long long rows, int nlayers, const int *widths, int pool_row
         pl.l1xg = off; off = align_up(off + (size_t)rows * 16);
         pl.l1mom = off; off = align_up(off + (size_t)kMaxParts * 9 * sizeof(double));
         pl.l1a = off; off = align_up(off + (size_t)kMaxParts * 3 * widths[1] * sizeof(double));
+    }
+    if (fp) {
+        const int C1 = widths[1];
+        pl.l1p = off; off = align_up(off + (size_t)fp->mp * C1 * 4);              // forward Q, backward S: (mp, C1)
+        if (fp->c1 > 0) {
+            const size_t wb = backward ? gemm_shape(rows, C1, fp->c1, o).pack_bytes : gemm_shape(rows, fp->c1p, C1, o).pack_bytes;
+            pl.fpw = off; off = align_up(off + wb);
+        }
+        if (fp->pad2()) { pl.fp2 = off; off = align_up(off + (size_t)fp->mp * fp->c2p * 4); }
+        if (fp->pad1()) { pl.fp1 = off; off = align_up(off + (size_t)rows * fp->c1p * 4); }
+        if (backward) {
+            const long long sb = pn2_seg_grad_ws_bytes(fp->b, fp->m, 3ll * fp->n);
+            if (sb < 0) return false;
+            pl.l1seg = off; off = align_up(off + (size_t)sb);
+            pl.l1coef = off; off = align_up(off + (size_t)3 * C1 * 4);
+            if (fp->gstage2()) { pl.fpg2 = off; off = align_up(off + (size_t)fp->mp * fp->c2 * 4); }
+        }
     }
     pl.tickets = off; off = align_up(off + sizeof(unsigned) * kFinTickets);
     pl.total = off;
@@ -2287,7 +2352,7 @@ static int launch_wgrad_reduce(const TlWgrad &p, const WgradShape &w, float *par
     long long blocks = (total + 31) / 32;
     if (blocks > 4096) blocks = 4096;
     return launch(tl_wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float *)p.partial, w.nw, w.tus, w.tts, w.tslabs,
-                  p.KI, p.NO, L.grad_weight, L.w_stride_k, L.w_stride_n, plain, L.grad_accumulate);
+                  p.kout > 0 ? p.kout : p.KI, p.NO, L.grad_weight, L.w_stride_k, L.w_stride_n, plain, L.grad_accumulate);
 }
 
 // One launch for a layer's data-gradient GEMM (its workgroups first) and its weight-gradient pass (tl_pair_kernel), then the
@@ -2464,7 +2529,8 @@ struct SideStream {
     }
 };
 
-static bool layers_ok(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, int *widths)
+static bool layers_ok(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, int *widths,
+                      const FpL1 *fp = nullptr)
 {
     if (!layers || nlayers < 1 || nlayers > 8) return false;
     for (int l = 0; l < nlayers; ++l) {
@@ -2480,6 +2546,8 @@ static bool layers_ok(long long rows, int nlayers, const pn2_bn_layer *layers, c
         if ((long long)group->b * group->m * group->nsample != rows) return false;
         if (layers[0].cin != 3 + (group->points ? group->cfeat : 0)) return false;
         if (!group->idx && group->nsample != group->n) return false;
+    } else if (fp) {
+        if (layers[0].cin != fp->c2 + fp->c1 || fp->rows != rows) return false;
     } else if (layers[0].cin % 4) {
         return false;
     }
@@ -2628,19 +2696,19 @@ extern "C" int pn2_mlp_train_forward(long long rows, int nlayers, const pn2_bn_l
 // pooling: 0 max (the _ex entry), 1 avg, 2 weighted_avg, 3 max_and_avg (pn2_mlp_train_forward_pool; arguments checked there)
 static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
                             int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
-                            const pn2_train_opts *opts, void *stream)
+                            const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr)
 {
     using namespace pn2;
     const Opts o = opts_of(opts);
     int widths[9];
-    if (!layers_ok(rows, nlayers, layers, group, widths)) return PN2_E_ARG;
+    if (!layers_ok(rows, nlayers, layers, group, widths, fp)) return PN2_E_ARG;
     const bool want_max = pooling == 0 || pooling == 3;          // the extrema of the GEMM epilogue (E_POOL)
-    if ((!group && !x) || !out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w)) return PN2_E_NULL;
+    if ((!group && !x && !fp) || !out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w)) return PN2_E_NULL;
     if (pool_rows && (rows % pool_rows || (group && pool_rows != group->nsample))) return PN2_E_ARG;
     TlPlan pl;
     GroupDims gd;
     if (group) gd = group_dims(group);
-    if (!tl_plan(rows, nlayers, widths, pool_rows, 0, pl, group ? &gd : nullptr, o)) return PN2_E_ARG;
+    if (!tl_plan(rows, nlayers, widths, pool_rows, 0, pl, group ? &gd : nullptr, o, fp)) return PN2_E_ARG;
     const bool per_point = group && l1_per_point(nlayers, widths, &gd, o);
     // forward: layer 1 on the vector units only WITHOUT features (with the input normals gathered per row the vector kernel
     // measured slower than the gathered GEMM: cls_msg forward 2.51 -> 2.57 ms; its backward counterpart is the one that pays)
@@ -2659,7 +2727,14 @@ static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *lay
         for (int l = 0; l < nlayers; ++l) {
             const pn2_bn_layer &L = layers[l];
             if (l == 0 && coords_only) continue;                 // no matrix-core pass at all
-            if (l == 0 && per_point) {                            // only the feature rows of W_1: P = points . W1f
+            if (l == 0 && fp) {                                   // W1a for the known points' GEMM, W1b for the one over the rows
+                add_pack_job(jobs, nj, L.weight, L.w_stride_k, L.w_stride_n, gemm_shape(fp->mp, fp->c2, L.cout, o), base + pl.pack[l]);
+                if (fp->c1 > 0)
+                    add_pack_job(jobs, nj, L.weight + (long long)fp->c2 * L.w_stride_k, L.w_stride_k, L.w_stride_n,
+                                 gemm_shape(rows, fp->c1, L.cout, o), base + pl.fpw);
+                continue;
+            }
+            if (l == 0 && per_point) {                           // only the feature rows of W_1: P = points . W1f
                 const TlGather gt = make_gather(group);
                 add_pack_job(jobs, nj, L.weight + gt.feat_off * L.w_stride_k, L.w_stride_k, L.w_stride_n,
                              gemm_shape((long long)gd.b * gd.n, gt.cfeat, L.cout, o), base + pl.pack[l]);
@@ -2679,6 +2754,56 @@ static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *lay
         const pn2_bn_layer &L = layers[l];
         const GemmShape g = gemm_shape(rows, L.cin, L.cout, o);
         const bool last = l == nlayers - 1;
+        if (l == 0 && fp) {
+            // layer 1 of an FP level once per KNOWN point (train_mlp_fp.hip): Q = points2 W1a over the b m known points,
+            // z_1 = points1 W1b over the rows, then one pass adds the interpolated rows of Q and sums the batch moments
+            float *Q = reinterpret_cast<float *>(base + pl.l1p);
+            const float *p2 = fp->points2, *p1 = fp->points1;
+            if (fp->pad2()) {
+                float *d = reinterpret_cast<float *>(base + pl.fp2);
+                if (int rc = fp_launch_pad(fp->points2, fp->bm, fp->c2, fp->mp, fp->c2p, d, st)) return rc;
+                p2 = d;
+            }
+            if (fp->pad1()) {
+                float *d = reinterpret_cast<float *>(base + pl.fp1);
+                if (int rc = fp_launch_pad(fp->points1, rows, fp->c1, rows, fp->c1p, d, st)) return rc;
+                p1 = d;
+            }
+            {
+                TlGemm q;                                         // no moments: Q is not z_1
+                memset(&q, 0, sizeof(q));
+                q.rows = fp->mp;
+                q.A = p2;
+                q.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
+                q.emode = E_STORE;
+                q.out = Q;
+                if (int rc = launch_gemm(A_PLAIN, q, gemm_shape(fp->mp, fp->c2p, L.cout, o), st, o)) return rc;
+            }
+            if (fp->c1 > 0) {
+                TlGemm q;
+                memset(&q, 0, sizeof(q));
+                q.rows = rows;
+                q.A = p1;
+                q.wpacked = reinterpret_cast<const u32x4 *>(base + pl.fpw);
+                q.emode = E_STORE;
+                q.out = L.z;
+                if (int rc = launch_gemm(A_PLAIN, q, gemm_shape(rows, fp->c1p, L.cout, o), st, o)) return rc;
+            }
+            int np = 0;
+            if (int rc = fp_launch_l1_forward(rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z, fp->c1 > 0,
+                                              reinterpret_cast<double *>(base + pl.stats[l]), kMaxParts, st, &np)) return rc;
+            if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
+                                reinterpret_cast<const double *>(base + pl.stats[l]), np, L.cout, (double)rows, L.gamma,
+                                L.beta, L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
+            if (last) {
+                const long long total4 = rows * L.cout / 4;
+                long long blocks = (total4 + 255) / 256;
+                if (blocks > 8192) blocks = 8192;
+                if (int rc = launch(tl_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, total4, L.cout, (const float *)L.z,
+                                    (const float *)L.save, out)) return rc;
+            }
+            continue;
+        }
         if (l == 0 && per_point) {
             // layer 1 once per point (tl_l1_forward_kernel): P = points . W1f over the b n points, then one pass over the rows
             const TlGather gt = make_gather(group);
@@ -2791,15 +2916,15 @@ extern "C" int pn2_mlp_train_backward(long long rows, int nlayers, const pn2_bn_
 static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
                              int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel, const float *pool_w,
                              const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points, int reproducible,
-                             void *ws, const pn2_train_opts *opts, void *stream)
+                             void *ws, const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr)
 {
     using namespace pn2;
     const Opts o = opts_of(opts);
     const int cus = device_cus();
     int widths[9];
-    if (!layers_ok(rows, nlayers, layers, group, widths)) return PN2_E_ARG;
+    if (!layers_ok(rows, nlayers, layers, group, widths, fp)) return PN2_E_ARG;
     const bool want_max = pooling == 0 || pooling == 3;
-    if ((!group && !x) || !out || !grad_out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w))
+    if ((!group && !x && !fp) || !out || !grad_out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w))
         return PN2_E_NULL;
     const int avg_rows = pooling ? pool_rows : 0;       // > 0: the group size of the averaged top layer
     if (pooling && (!group || avg_rows <= 0 || rows % avg_rows || avg_rows != group->nsample)) return PN2_E_ARG;
@@ -2809,12 +2934,13 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
     TlPlan pl;
     GroupDims gd;
     if (group) gd = group_dims(group);
-    if (!tl_plan(rows, nlayers, widths, pool_rows, 1, pl, group ? &gd : nullptr, o)) return PN2_E_ARG;
+    if (!tl_plan(rows, nlayers, widths, pool_rows, 1, pl, group ? &gd : nullptr, o, fp)) return PN2_E_ARG;
     hipStream_t st = as_stream(stream);
     char *base = static_cast<char *>(ws);
     const bool per_point = group && l1_per_point(nlayers, widths, &gd, o);
     const bool coords_only = group && l1_coords_only(nlayers, widths, &gd, o);
-    const bool want_dx = group ? ((per_point ? grad_points : grad_feat_rows) && group->points && group->cfeat > 0) : grad_x != nullptr;
+    const bool want_dx = fp ? (fp->grad_points2 || fp->grad_points1)
+                       : group ? ((per_point ? grad_points : grad_feat_rows) && group->points && group->cfeat > 0) : grad_x != nullptr;
     const bool ztop = !top_stored(rows, nlayers, widths, pool_rows, o);     // pooled top layer without z_L (tl_top_mats_kernel)
     for (int l = 0; l < nlayers; ++l)
         if (!layers[l].z && !(ztop && l == nlayers - 1)) return PN2_E_NULL;
@@ -2831,7 +2957,7 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
             // size rule leaves it off; fuse_wgrad = PN2_OPT_ON forces it)
             wz[l] = wgrad_shape(rows, L.cin, top_cols(L.cin, L.cout), false, cus, PN2_OPT_OFF);
             if (o.fuse_wgrad == PN2_OPT_ON) fz[l] = fuse_shape(rows, wz[l], tiles(L.cout) * 32 + L.cin, L.cin, o, false);
-        } else if (!(l == 0 && (group || !want_dx))) {
+        } else if (!(l == 0 && (group || fp || !want_dx))) {
             wz[l] = wgrad_shape(rows, L.cin, L.cout, false, cus, PN2_OPT_OFF);
             fz[l] = fuse_shape(rows, wz[l], L.cout, L.cin, o);
         }
@@ -2852,6 +2978,12 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                     memset(&gg, 0, sizeof(gg));
                     gg.K = L.cout; gg.N = L.cin; gg.tk = fz[l].tk; gg.tn = fz[l].nt; gg.ns = fz[l].nt; gg.slabs = 1;
                     add_pack_job(jobs, nj, L.weight, L.w_stride_n, L.w_stride_k, gg, base + pl.pack[l]);
+                } else if (l == 0 && fp) {                        // W1a^T, W1b^T: the data gradients of points2 / points1
+                    if (fp->grad_points2)
+                        add_pack_job(jobs, nj, L.weight, L.w_stride_n, L.w_stride_k, gemm_shape(fp->mp, L.cout, fp->c2, o), base + pl.pack[l]);
+                    if (fp->grad_points1 && fp->c1 > 0)
+                        add_pack_job(jobs, nj, L.weight + (long long)fp->c2 * L.w_stride_k, L.w_stride_n, L.w_stride_k,
+                                     gemm_shape(rows, L.cout, fp->c1, o), base + pl.fpw);
                 } else if (l == 0 && group) {
                     // layer 1 of a grouped level: only the FEATURE rows of W_1 (the grouped xyz takes no gradient here);
                     // per point: the same tiles, for the GEMM over the b n points
@@ -2863,7 +2995,7 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                 }
             }
         }
-        if (per_point && nj > 0) {                                // the identity coefficients of layer 1's per-point weight gradient
+        if ((per_point || fp) && nj > 0) {                        // the identity coefficients of layer 1's per-point weight gradient
             jobs.ident = reinterpret_cast<float *>(base + pl.l1coef);
             jobs.ident_c = layers[0].cout;
         }
@@ -3048,6 +3180,66 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
             }
             // ... in one pass over dy_1 and z_1
             if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, reinterpret_cast<float *>(base + pl.l1part), false, st)) return rc;
+            break;
+        }
+        if (l == 0 && fp) {
+            // ---- layer 1 of an FP level per KNOWN point (train_mlp_fp.hip): dz_1 in place, its interpolation gradient S onto
+            // the known points, then each half of W_1 -- a weight gradient and a data gradient over its own rows
+            float *S = reinterpret_cast<float *>(base + pl.l1p), *ident = reinterpret_cast<float *>(base + pl.l1coef);
+            float *part2 = reinterpret_cast<float *>(base + pl.partial2);
+            if (int rc = fp_launch_l1_dz(rows, L.cout, L.z, gcur, coef, st)) return rc;
+            if (int rc = pn2_three_interpolate_grad_seg(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx, fp->weight, S, base + pl.l1seg,
+                                                        reproducible, stream)) return rc;
+            if (fp->mp > fp->bm)                                  // the padding rows of S meet the zero rows of points2's copy
+                if (int rc = clear_async(S + fp->bm * L.cout, sizeof(float) * (size_t)(fp->mp - fp->bm) * L.cout, st)) return rc;
+            if (!ident_written)
+                if (int rc = launch(tl_identity_coef_kernel, dim3((unsigned)((3 * L.cout + 127) / 128)), dim3(128), 0, st, L.cout, ident)) return rc;
+            const float *p2 = fp->points2, *p1 = fp->points1;
+            if (fp->pad2()) {
+                float *d = reinterpret_cast<float *>(base + pl.fp2);
+                if (int rc = fp_launch_pad(fp->points2, fp->bm, fp->c2, fp->mp, fp->c2p, d, st)) return rc;
+                p2 = d;
+            }
+            if (fp->pad1()) {
+                float *d = reinterpret_cast<float *>(base + pl.fp1);
+                if (int rc = fp_launch_pad(fp->points1, rows, fp->c1, rows, fp->c1p, d, st)) return rc;
+                p1 = d;
+            }
+            // dW_half = A^T D (rows kc of the weight gradient from row koff) and, when wanted, gout = D W_half^T
+            auto half = [&](long long hr, int kp, int kc, const float *A, const float *D, size_t pack, float *gout, int koff)
+                __attribute__((always_inline)) -> int {
+                TlWgrad w;
+                memset(&w, 0, sizeof(w));
+                w.rows = hr; w.KI = kp; w.kout = kc; w.amode = A_PLAIN; w.A = A;
+                w.dmode = A_DZ; w.NO = L.cout; w.Z = D; w.G = D; w.coef = ident;
+                w.partial = reinterpret_cast<float *>(base + pl.partial); w.partial_cap = pl.partial_cap;
+                pn2_bn_layer Lh = L;
+                Lh.grad_weight = L.grad_weight + (long long)koff * L.w_stride_k;
+                const WgradShape ws_ = wgrad_shape(hr, kp, L.cout, false, cus, o.wgrad_two_per_cu);
+                if (!gout) return launch_wgrad(w, ws_, part2, Lh, st);
+                const GemmShape g = gemm_shape(hr, L.cout, kc, o);
+                TlGemm p;
+                memset(&p, 0, sizeof(p));
+                p.rows = hr;
+                p.A = D;
+                p.wpacked = reinterpret_cast<const u32x4 *>(base + pack);
+                p.emode = E_PLAIN;
+                p.out = gout; p.out_pitch = kc; p.col0 = 0; p.col1 = kc;
+                int rc = kNoPair;
+                if (pair_wanted(hr, o)) rc = launch_pair(A_PLAIN, p, g, w, ws_, part2, Lh, st, o, nullptr);
+                if (rc == kNoPair) {
+                    if ((rc = sd.fork())) return rc;
+                    if ((rc = launch_wgrad(w, ws_, part2, Lh, ss))) return rc;
+                    rc = launch_gemm(A_PLAIN, p, g, st, o);
+                }
+                return rc;
+            };
+            float *g2 = (fp->grad_points2 && fp->gstage2()) ? reinterpret_cast<float *>(base + pl.fpg2) : fp->grad_points2;
+            if (int rc = half(fp->mp, fp->c2p, fp->c2, p2, S, pl.pack[l], g2, 0)) return rc;
+            if (g2 && g2 != fp->grad_points2)
+                if (int rc = fp_launch_pad(g2, fp->bm, fp->c2, fp->bm, fp->c2, fp->grad_points2, st)) return rc;
+            if (fp->c1 > 0)
+                if (int rc = half(rows, fp->c1p, fp->c1, p1, gcur, pl.fpw, fp->grad_points1, fp->c2)) return rc;
             break;
         }
         if (l == 0 && per_point) {
@@ -3261,3 +3453,34 @@ extern "C" int pn2_mlp_train_backward_pool(long long rows, int nlayers, const pn
                              pooling == 3 || pooling == 0 ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, grad_out, nullptr,
                              grad_feat_rows, grad_points, reproducible, ws, opts, stream);
 }
+
+// ---- the FP level with layer 1 per known point (pn2_mlp_train_*_fp: entry points and argument checks in train_mlp_fp.hip) ----
+namespace pn2 {
+long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts)
+{
+    const FpL1 f = fp_l1(s);
+    TlPlan pl;
+    if (!tl_plan(f.rows, nlayers, widths, 0, backward, pl, nullptr, opts_of(opts), &f)) return -1;
+    return (long long)pl.total;
+}
+
+int tl_fp_forward(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *s, float *out, float *weight, void *ws,
+                  const pn2_train_opts *opts, void *stream)
+{
+    FpL1 f = fp_l1(s);
+    f.weight_out = weight;
+    return tl_train_forward(f.rows, nlayers, layers, nullptr, nullptr, 0, 0, out, nullptr, nullptr, nullptr, ws, opts, stream, &f);
+}
+
+int tl_fp_backward(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *s, const float *weight, const float *out,
+                   const float *grad_out, float *grad_points2, float *grad_points1, int reproducible, void *ws,
+                   const pn2_train_opts *opts, void *stream)
+{
+    FpL1 f = fp_l1(s);
+    f.weight = weight;
+    f.grad_points2 = grad_points2;
+    f.grad_points1 = grad_points1;
+    return tl_train_backward(f.rows, nlayers, layers, nullptr, nullptr, 0, 0, out, nullptr, nullptr, nullptr, grad_out, nullptr,
+                             nullptr, nullptr, reproducible, ws, opts, stream, &f);
+}
+}  // namespace pn2

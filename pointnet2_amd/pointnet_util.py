@@ -523,6 +523,9 @@ class PointnetFPModule(nn.Module):
         if self.fused_mlp and self.training and points2.is_cuda and use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
                 train_mlp.stack_supported(self.mlp.net, xyz1.shape[0] * xyz1.shape[1], 0, False):
             self.last_path = "fused_train"
+            if train_mlp.fp_level_preferred(xyz1.shape[0], xyz1.shape[1], points2.shape[1], points2.shape[2]) and \
+                    train_mlp.fp_level_supported(self.mlp.net, xyz1.shape[0], xyz1.shape[1], points2.shape[1], points2.shape[2], c1):
+                return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist)     # :212-226 as one node
             x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
             return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1)
         inv = 1.0 / torch.clamp(dist, min=1e-10)                                # :212
@@ -549,9 +552,13 @@ class PointnetFPModule(nn.Module):
             # kernels, one split + the segmented scatter of three_interpolate's gradient
             self.last_path = "fused_train"
             dist, idx = three_nn(xyz1, xyz2)                                    # :211
+            c1 = points1.shape[2] if points1 is not None else 0
+            if train_mlp.fp_level_preferred(xyz1.shape[0], xyz1.shape[1], xyz2.shape[1], points2.shape[2]) and \
+                    train_mlp.fp_level_supported(self.mlp.net, xyz1.shape[0], xyz1.shape[1], xyz2.shape[1], points2.shape[2], c1):
+                # weights, interpolation, concatenation and the stack as ONE node, layer 1 once per known point (train_mlp_fp.hip)
+                return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist)     # :212-226
             x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
-            c = points2.shape[2] + (points1.shape[2] if points1 is not None else 0)
-            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=c)
+            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1)
         idx, weight = three_nn_weights(xyz1, xyz2)                              # :211-215
         return self._after_weights(points1, points2, idx, weight)
 

@@ -34,6 +34,11 @@ class BnLayer(ctypes.Structure):           # pn2_bn_layer
                 ("running_var_biased", _i)]
 
 
+class FpSrc(ctypes.Structure):             # pn2_fp_src
+    _fields_ = [("b", _i), ("n", _i), ("m", _i), ("c2", _i), ("c1", _i), ("points2", _vp), ("points1", _vp), ("idx", _vp),
+                ("dist", _vp)]
+
+
 class TrainOpts(ctypes.Structure):         # pn2_train_opts: 0 = automatic, 1 = off, 2 = on
     _fields_ = [("top_stored", _i), ("top_sparse", _i), ("l1_per_point", _i), ("l1_coords", _i), ("force_stream", _i),
                 ("max_ns", _i), ("nt", _i), ("fuse_wgrad", _i), ("wgrad_two_per_cu", _i), ("side_stream", _i),
@@ -494,3 +499,167 @@ def fp_mlp_train(net, x, cin=None):
         params[0] = torch.nn.functional.pad(w, (0, 0) * (w.dim() - 2) + (0, pad))
     out = _TrainMLP.apply(lv, x, *params)
     return out.view(b, n, -1)
+
+
+# ---- a feature-propagation level as ONE node with the interpolation inside (pn2_mlp_train_*_fp, csrc/train_mlp_fp.hip) ----
+class _FpLevel:
+    __slots__ = ("pairs", "rows", "b", "n", "m", "c2", "c1", "idx", "dist")
+
+
+def fp_level_supported(net, b, n, m, c2, c1):
+    """Can the FP training node (layer 1 per known point, pn2_mlp_train_*_fp) run this stack on b clouds of n unknown and m
+    known points with c2 interpolated and c1 skip channels?"""
+    pairs = conv_bn_pairs(net)
+    if not pairs or len(pairs) > 7 or pairs[0][0].in_channels != c2 + c1 or not stack_supported(net, b * n, 0, False):
+        return False
+    widths = [c2 + c1] + [c.out_channels for c, _ in pairs]
+    arr = (ctypes.c_int * len(widths))(*widths)
+    return bool(_C.lib().pn2_mlp_train_fp_supported(b, n, m, c2, c1, len(pairs), arr))
+
+
+# Where the modules take the node. It no longer forms the interpolated part of layer 1's input on the b (n - m) rows that are
+# not known points, and pays for it with a few more latency-bound passes (two layer-1 GEMMs instead of one, the dz / scatter
+# launches). Summed kernel time of one warm forward + backward (profiles/fp_train/README.md), node vs current path, and the
+# saved elements b (n - m) c2: sem_seg FP4 391 vs 463 us (7.3 M), part_seg FP3 317 vs 338 (3.1 M), part_seg FP1 287 vs 375
+# (2.1 M) -- and the other way round at part_seg FP2 219 vs 214 (1.6 M), sem_seg FP3 213 vs 208 (1.6 M), FP2 200 vs 172
+# (0.4 M), FP1 199 vs 192 (0.2 M).
+FP_NODE_MIN_SAVED = 1_800_000
+
+
+def fp_level_preferred(b, n, m, c2):
+    """Is the FP node faster than fp_interp_concat + fp_mlp_train at this size (FP_NODE_MIN_SAVED)? Results do not depend on it."""
+    return b * (n - m) * c2 >= FP_NODE_MIN_SAVED
+
+
+def _fp_src(level, points2, points1):
+    s = FpSrc()
+    s.b, s.n, s.m, s.c2, s.c1 = level.b, level.n, level.m, level.c2, level.c1
+    s.points2, s.points1, s.idx, s.dist = ptr(points2), ptr(points1), ptr(level.idx), ptr(level.dist)
+    return s
+
+
+def _ws_fp(level, widths, backward, dev, opts):
+    arr = (ctypes.c_int * len(widths))(*widths)
+    nbytes = _C.lib().pn2_mlp_train_ws_bytes_fp(level.b, level.n, level.m, level.c2, level.c1, len(widths) - 1, arr, backward, opts)
+    require(nbytes >= 0, "pn2_mlp_train_ws_bytes_fp: unsupported level")
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+
+
+class _TrainFP(torch.autograd.Function):
+    """inputs: level, points2 (b,m,c2), points1 (b,n,c1) or None, then per layer conv.weight, conv.bias (or None), bn.weight,
+    bn.bias. Saved: the inputs, the interpolation weights, the parameters, the pre-norm tensors z_l."""
+
+    @staticmethod
+    def forward(ctx, level, points2, points1, *params):
+        n = len(level.pairs)
+        weights = [f32(params[4 * l], "weight") for l in range(n)]
+        biases = [params[4 * l + 1] for l in range(n)]
+        gammas, betas = [params[4 * l + 2] for l in range(n)], [params[4 * l + 3] for l in range(n)]
+        dev = weights[0].device
+        rows = level.rows
+        widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
+        opts = _opts()
+        zs = [torch.empty((rows, w), dtype=torch.float32, device=dev) for w in widths[1:]]
+        saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
+        out = torch.empty((rows, widths[-1]), dtype=torch.float32, device=dev)
+        weight = torch.empty((level.b, level.n, 3), dtype=torch.float32, device=dev)
+        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
+        src = _fp_src(level, points2, points1)
+        ws = _ws_fp(level, widths, 0, dev, opts)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_mlp_train_forward_fp(n, arr, ctypes.byref(src), ptr(out), ptr(weight), ptr(ws), opts,
+                                                       stream_ptr(dev)), "mlp_train_forward_fp")
+        nbt = [bn.num_batches_tracked for _, bn in level.pairs if bn.track_running_stats and bn.num_batches_tracked is not None]
+        if nbt:
+            torch._foreach_add_(nbt, 1)
+        ctx.level, ctx.widths = level, widths
+        ctx.opts = dict(_OPTS)
+        ctx.has_p1 = points1 is not None
+        ctx.nbias = [b is not None for b in biases]
+        ctx.mark_non_differentiable(weight)
+        ctx.save_for_backward(*([points2] + ([points1] if points1 is not None else []) + [weight] + weights +
+                                [b for b in biases if b is not None] + gammas + betas + zs + saves + [out]))
+        return out, weight
+
+    @staticmethod
+    def backward(ctx, grad_out, _unused):
+        level, widths = ctx.level, ctx.widths
+        n = len(level.pairs)
+        sv = list(ctx.saved_tensors)
+        points2 = sv.pop(0)
+        points1 = sv.pop(0) if ctx.has_p1 else None
+        weight = sv.pop(0)
+        weights = [sv.pop(0) for _ in range(n)]
+        biases = [sv.pop(0) if has else None for has in ctx.nbias]
+        gammas = [sv.pop(0) for _ in range(n)]
+        betas = [sv.pop(0) for _ in range(n)]
+        zs = [sv.pop(0) for _ in range(n)]
+        saves = [sv.pop(0) for _ in range(n)]
+        out = sv.pop(0)
+        dev = out.device
+        grad_out = f32(grad_out, "grad_out")
+        grads, direct = [], []
+        for l, (conv, bn) in enumerate(level.pairs):
+            slots = (_grad_slot(conv.weight, weights[l]), _grad_slot(bn.weight, gammas[l]), _grad_slot(bn.bias, betas[l])) \
+                if _ACCUMULATE[0] else (None, None, None)
+            direct.append(all(t is not None for t in slots))
+            grads.append(slots if direct[-1] else
+                         (torch.empty_like(weights[l]), torch.empty_like(gammas[l]), torch.empty_like(betas[l])))
+        g2 = torch.empty_like(points2) if ctx.needs_input_grad[1] else None
+        g1 = torch.empty_like(points1) if points1 is not None and ctx.needs_input_grad[2] else None
+        opts = _opts_from(ctx.opts)
+        ws = _ws_fp(level, widths, 1, dev, opts)
+        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
+        for l in range(n):
+            arr[l].grad_accumulate = 1 if direct[l] else 0
+        src = _fp_src(level, points2, points1)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_mlp_train_backward_fp(n, arr, ctypes.byref(src), ptr(weight), ptr(out), ptr(grad_out), ptr(g2),
+                                                        ptr(g1), 1 if is_deterministic() else 0, ptr(ws), opts, stream_ptr(dev)),
+                     "mlp_train_backward_fp")
+        result = [None, g2, g1]
+        zero = None
+        off = 0
+        for l in range(n):
+            if direct[l]:
+                result += [None, None, None, None]
+            else:
+                if zero is None and biases[l] is not None:
+                    zero = torch.zeros((sum(widths[1:]),), dtype=torch.float32, device=dev)
+                gb = zero[off:off + widths[l + 1]] if biases[l] is not None else None
+                result += [grads[l][0], gb, grads[l][1], grads[l][2]]
+            off += widths[l + 1]
+        return tuple(result)
+
+
+def fp_level_train(net, points2, points1, idx, dist, return_weight=False):
+    """Training-mode feature-propagation level with the interpolation inside ONE autograd node (pointnet_fp_module,
+    utils/pointnet_util.py:211-226): inverse-distance weights from three_nn's squared distances `dist` (b,n,3) and `idx`
+    (b,n,3) i32, three_interpolate of points2 (b,m,c2), concatenation with the skip features points1 (b,n,c1) or None, and the
+    layer stack `net` (Conv 1x1 + BatchNorm + ReLU triples, batch statistics). Layer 1 runs once per KNOWN point
+    (z_1 = interp(points2 W1a) + points1 W1b); the (b,n,c2+c1) input never exists. -> (b,n,cout), differentiable w.r.t.
+    points2, points1 and every parameter (and the weights (b,n,3) with return_weight)."""
+    pairs = conv_bn_pairs(net)
+    require(pairs is not None, "fp_level_train expects Conv 1x1 + BatchNorm + ReLU triples")
+    points2, idx, dist = f32(points2, "points2"), i32(idx, "idx"), f32(dist, "dist")
+    require(points2.dim() == 3, "points2 must be (b, m, c2), got %s" % (tuple(points2.shape),))
+    b, m, c2 = points2.shape
+    require(idx.dim() == 3 and idx.shape[0] == b and idx.shape[2] == 3, "idx must be (b, n, 3), got %s" % (tuple(idx.shape),))
+    require(tuple(dist.shape) == tuple(idx.shape), "dist must have idx's shape %s" % (tuple(idx.shape),))
+    n = idx.shape[1]
+    c1 = 0
+    if points1 is not None:
+        points1 = f32(points1, "points1")
+        require(points1.dim() == 3 and tuple(points1.shape[:2]) == (b, n),
+                "points1 must be (b, n, c1) with (b, n) = %s, got %s" % ((b, n), tuple(points1.shape)))
+        c1 = points1.shape[2]
+        same_device(points2, points1, idx, dist, pairs[0][0].weight)
+    else:
+        same_device(points2, idx, dist, pairs[0][0].weight)
+    require(pairs[0][0].in_channels == c2 + c1, "the first layer expects %d channels, got %d" % (pairs[0][0].in_channels, c2 + c1))
+    require(fp_level_supported(net, b, n, m, c2, c1), "unsupported level for the FP training node")
+    lv = _FpLevel()
+    lv.pairs, lv.rows, lv.b, lv.n, lv.m, lv.c2, lv.c1, lv.idx, lv.dist = pairs, b * n, b, n, m, c2, c1, idx, dist
+    out, weight = _TrainFP.apply(lv, points2, points1, *_params(pairs))
+    out = out.view(b, n, -1)
+    return (out, weight) if return_weight else out
