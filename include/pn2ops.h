@@ -535,6 +535,32 @@ int pn2_mlp_train_backward_pool(long long rows, int nlayers, const pn2_bn_layer 
                                 const float *pool_w, const float *grad_out, float *grad_feat_rows, float *grad_points,
                                 int reproducible, void *ws, const pn2_train_opts *opts, void *stream);
 
+/* The coordinate gradients of the SA training node: what GroupPoint's and GatherPoint's registered gradients carry through
+ * grouped_xyz - new_xyz (utils/pointnet_util.py:44-46, :179-180). pn2_mlp_train_backward_xyz takes the arguments of
+ * pn2_mlp_train_backward_pool plus grad_xyz (b,n,3) and grad_new_xyz (b,m,3), both WRITTEN (not accumulated): with W1x the
+ * three coordinate rows of layers[0]'s weight and dz_1 the gradient at layer 1's pre-norm output,
+ *     g_r = dz_1[r,:] . W1x^T,   grad_xyz[i,p] = sum of g_r over the rows that name point p,   grad_new_xyz[i,j] = - sum_k g_(i,j,k)
+ * (group_all: grad_xyz[i,k] = g_r). grad_new_xyz is d / d new_xyz alone: the centroids' own dependence on xyz (GatherPoint)
+ * is the caller's. Every other result is pn2_mlp_train_backward_pool's; forward is pn2_mlp_train_forward_pool. Passes
+ * (csrc/train_mlp_xyz.hip): one over (dy_1, z_1) for the rows g, one over g for the centroids, the 3-channel segmented
+ * reduction pn2_group_point_grad_seg for the points (`reproducible` = its sorted-segment mode) -- or, where layer 1 runs once
+ * per point, grad_xyz = S . W1x^T from the scattered dz_1 backward holds anyway. A level without features keeps dy_1 and
+ * tl_l1_dz_kernel's pass (its moment form never writes dy_1). Both new pointers NULL: pn2_mlp_train_backward_pool exactly.
+ * Otherwise, before anything is launched: PN2_E_ARG for pooling 2 (weighted_avg: its weights depend on xyz, and |grouped xyz|
+ * has no derivative at the centroid, a member of its own ball) or grad_new_xyz without group->new_xyz; PN2_E_NULL without
+ * `group`, without grad_xyz, or with group->new_xyz but no grad_new_xyz. ws: pn2_mlp_train_ws_bytes_xyz bytes (>= the _pool
+ * backward workspace; -1 where unsupported). pn2_mlp_train_xyz_supported: 1 where pn2_mlp_train_pool_supported says 1, the
+ * pooling is 0, 1 or 3 and group_dims (b, n, m, nsample, cfeat, idx != NULL; NULL = judge the shape alone) fit rows and
+ * widths[0] = 3 + cfeat; else 0. */
+int pn2_mlp_train_xyz_supported(long long rows, int nlayers, const int *widths, int pool_rows, int pooling, const int *group_dims);
+long long pn2_mlp_train_ws_bytes_xyz(long long rows, int nlayers, const int *widths, int pool_rows, int pooling,
+                                     const int *group_dims, const pn2_train_opts *opts);
+int pn2_mlp_train_backward_xyz(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                               int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel,
+                               const float *pool_w, const float *grad_out, float *grad_feat_rows, float *grad_points,
+                               float *grad_xyz, float *grad_new_xyz, int reproducible, void *ws, const pn2_train_opts *opts,
+                               void *stream);
+
 /* The training node of a feature-propagation level (pointnet_fp_module, utils/pointnet_util.py:211-226) with the interpolation
  * INSIDE it. Layer 1 and three_interpolate are both linear, so
  *     z_1 = [interp(points2), points1] W_1 = interp(points2 W1a) + points1 W1b

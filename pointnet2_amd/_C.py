@@ -99,6 +99,9 @@ _SIGNATURES = {
     "pn2_mlp_train_ws_bytes_pool": [_ll, _i, _vp, _i, _i, _i, _vp, _vp],
     "pn2_mlp_train_forward_pool": [_ll, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_mlp_train_backward_pool": [_ll, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "pn2_mlp_train_xyz_supported": [_ll, _i, _vp, _i, _i, _vp],
+    "pn2_mlp_train_ws_bytes_xyz": [_ll, _i, _vp, _i, _i, _vp, _vp],
+    "pn2_mlp_train_backward_xyz": [_ll, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
     "pn2_mlp_train_fp_supported": [_i, _i, _i, _i, _i, _i, _vp],
     "pn2_mlp_train_ws_bytes_fp": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "pn2_mlp_train_forward_fp": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -115,6 +118,7 @@ _RESTYPES = {
     "pn2_mlp_train_ws_bytes": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_ex": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_pool": ctypes.c_longlong,
+    "pn2_mlp_train_ws_bytes_xyz": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_fp": ctypes.c_longlong,
     "pn2_sample_and_group_status_offset": ctypes.c_longlong,
     "pn2_ball_threshold": ctypes.c_float,

@@ -1985,6 +1985,14 @@ int fp_launch_l1_forward(long long rows, int n, int m, int C, const int *idx, co
                          float *z, bool add, double *stats, int max_parts, hipStream_t st, int *nparts);
 int fp_launch_l1_dz(long long rows, int C, const float *z, float *g, const float *coef, hipStream_t st);
 
+// ---- defined in train_mlp_xyz.hip: the coordinate gradients (pn2_mlp_train_backward_xyz) ----
+int xyz_launch_rows(long long rows, int C, const float *G, const float *Z, const float *coef, const int *argsel, int group_rows,
+                    const float *wx, long long sk, long long sn, float *out, hipStream_t st);
+int xyz_launch_centroids(long long groups, int ns, const float *g, float *out, hipStream_t st);
+// the workspace behind TlPlan::total when the coordinate gradients are wanted: g (rows, 3) of a level with idx, then the scratch
+// of its segmented reduction (not where layer 1 runs per point: grad_xyz comes from S there)
+struct XyzPlan { size_t g, seg, total; };
+
 // Is layer 1 of this grouped level evaluated once per POINT (tl_l1_forward_kernel)? One rule for forward, backward, the
 // workspace sizes and the caller's allocation of the feature gradient.
 static bool l1_per_point(int nlayers, const int *widths, const GroupDims *g, const Opts &o)
@@ -2174,6 +2182,23 @@ static bool tl_plan(long long rows, int nlayers, const int *widths, int pool_row
     }
     pl.tickets = off; off = align_up(off + sizeof(unsigned) * kFinTickets);
     pl.total = off;
+    return true;
+}
+
+static bool xyz_plan(const TlPlan &pl, long long rows, int nlayers, const int *widths, const GroupDims &gd, const Opts &o, XyzPlan &x)
+{
+    size_t off = pl.total;
+    x.g = x.seg = off;
+    if (gd.has_idx) {
+        off = align_up(off + (size_t)rows * 3 * sizeof(float));
+        x.seg = off;
+        if (!l1_per_point(nlayers, widths, &gd, o)) {
+            const long long sb = pn2_seg_grad_ws_bytes(gd.b, gd.n, (long long)gd.m * gd.nsample);
+            if (sb < 0) return false;
+            off = align_up(off + (size_t)sb);
+        }
+    }
+    x.total = off;
     return true;
 }
 
@@ -2916,13 +2941,15 @@ extern "C" int pn2_mlp_train_backward(long long rows, int nlayers, const pn2_bn_
 static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
                              int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel, const float *pool_w,
                              const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points, int reproducible,
-                             void *ws, const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr)
+                             void *ws, const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr,
+                             float *grad_xyz = nullptr, float *grad_new_xyz = nullptr)
 {
     using namespace pn2;
     const Opts o = opts_of(opts);
     const int cus = device_cus();
     int widths[9];
     if (!layers_ok(rows, nlayers, layers, group, widths, fp)) return PN2_E_ARG;
+    const bool want_xyz = group && grad_xyz;            // the coordinate gradients (pn2_mlp_train_backward_xyz, train_mlp_xyz.hip)
     const bool want_max = pooling == 0 || pooling == 3;
     if ((!group && !x && !fp) || !out || !grad_out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w))
         return PN2_E_NULL;
@@ -2935,6 +2962,9 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
     GroupDims gd;
     if (group) gd = group_dims(group);
     if (!tl_plan(rows, nlayers, widths, pool_rows, 1, pl, group ? &gd : nullptr, o, fp)) return PN2_E_ARG;
+    XyzPlan xp;
+    memset(&xp, 0, sizeof(xp));
+    if (want_xyz && !xyz_plan(pl, rows, nlayers, widths, gd, o, xp)) return PN2_E_ARG;
     hipStream_t st = as_stream(stream);
     char *base = static_cast<char *>(ws);
     const bool per_point = group && l1_per_point(nlayers, widths, &gd, o);
@@ -3038,6 +3068,25 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                             grad_out, (const float *)T.z, ga, reinterpret_cast<double *>(base + pl.stats[nlayers - 1]))) return rc;
     }
     float *gcur = ga, *gnext = gb;                      // dy of the current layer (dense case) / of the layer below
+    // The coordinate gradients, from layer 1's dz_1 = s G - c0 - c1 Z (cf == nullptr: G is dz_1 itself; sel: the pooled
+    // single-layer stack, G = gq): g_r = dz_1[r] . W1x^T per row, grad_new_xyz = minus the group sums, grad_xyz = the rows
+    // scattered onto the points -- or, where backward has dz_1 on the points already (S, layer 1 per point), S . W1x^T
+    auto xyz_pass = [&](const float *G, const float *Z, const float *cf, const int *sel, const float *S) -> int {
+        const pn2_bn_layer &L1 = layers[0];
+        const float *wx = L1.weight + make_gather(group).xyz_off * L1.w_stride_k;
+        if (!group->idx)                                  // group_all: row k of cloud i IS point k, no centroid
+            return xyz_launch_rows(rows, L1.cout, G, Z, cf, sel, gd.nsample, wx, L1.w_stride_k, L1.w_stride_n, grad_xyz, st);
+        float *g3 = reinterpret_cast<float *>(base + xp.g);
+        if (grad_new_xyz || !S) {
+            if (int rc = xyz_launch_rows(rows, L1.cout, G, Z, cf, sel, gd.nsample, wx, L1.w_stride_k, L1.w_stride_n, g3, st)) return rc;
+            if (grad_new_xyz)
+                if (int rc = xyz_launch_centroids(rows / gd.nsample, gd.nsample, g3, grad_new_xyz, st)) return rc;
+        }
+        if (S)
+            return xyz_launch_rows((long long)gd.b * gd.n, L1.cout, S, nullptr, nullptr, nullptr, 1, wx, L1.w_stride_k, L1.w_stride_n,
+                                   grad_xyz, st);
+        return pn2_group_point_grad_seg(gd.b, gd.n, 3, gd.m, gd.nsample, g3, group->idx, grad_xyz, base + xp.seg, reproducible, stream);
+    };
     int l1_moment_parts = 0;                            // > 0: layer 1's weight gradient comes from moments (TlWgrad::l1x)
     // weight-gradient launches on a helper stream beside the data-gradient chain (SideStream above): OPT-IN. Measured
     // (scripts/lab_ab.sh side_stream, profiles/r04/README.md): every fork / join is a cross-queue dependency of ~10 us on this
@@ -3180,6 +3229,8 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
             }
             // ... in one pass over dy_1 and z_1
             if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, reinterpret_cast<float *>(base + pl.l1part), false, st)) return rc;
+            if (want_xyz)
+                if (int rc = xyz_pass(gcur, L.z, coef, nullptr, nullptr)) return rc;
             break;
         }
         if (l == 0 && fp) {
@@ -3252,6 +3303,8 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
             if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, part, true, st)) return rc;
             if (int rc = pn2_group_point_grad_seg(gd.b, gd.n, L.cout, gd.m, gd.nsample, gcur, group->idx, S, base + pl.l1seg,
                                                   reproducible, stream)) return rc;
+            if (want_xyz)                                         // (gcur holds dz_1 now)
+                if (int rc = xyz_pass(gcur, nullptr, nullptr, nullptr, S)) return rc;
             if (!ident_written)
                 if (int rc = launch(tl_identity_coef_kernel, dim3((unsigned)((3 * L.cout + 127) / 128)), dim3(128), 0, st, L.cout, ident)) return rc;
             {
@@ -3286,6 +3339,8 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
             }
             break;
         }
+        if (l == 0 && want_xyz)                                     // the generic gathered layer 1: from (dy_1, z_1), which nothing below overwrites
+            if (int rc = xyz_pass(pooled_top ? gq : gcur, L.z, coef, pooled_top ? argsel : nullptr, nullptr)) return rc;
         // weight gradient
         {
             TlWgrad w;
@@ -3318,7 +3373,8 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                 }
                 w.dy_nt_store = o.nt == PN2_OPT_OFF ? 0 : o.nt == PN2_OPT_ON ? 1 : (size_t)rows * L.cin * sizeof(float) >= ((size_t)128 << 20);
                 w.xr_off = (int)fz[l].xr_off;
-                if (l == 1 && coords_only && gd.cfeat == 0 && !pooled_top) {            // (a pooled two-layer stack keeps the pass over dy_1: its dz comes from the routed gradient)
+                // (not with the coordinate gradients: g_r needs dy_1 row by row, so it is written and tl_l1_dz_kernel's pass runs)
+                if (l == 1 && coords_only && gd.cfeat == 0 && !pooled_top && !want_xyz) {            // (a pooled two-layer stack keeps the pass over dy_1: its dz comes from the routed gradient)
                     // the layer below takes the three centred coordinates: dy_1 is wanted only as x^T dy_1 (TlWgrad::l1x) -- never
                     // written, and tl_l1_dz_kernel's pass over (dy_1, z_1) is replaced by nine moments of x
                     const pn2_bn_layer &D = layers[0];
@@ -3453,6 +3509,33 @@ extern "C" int pn2_mlp_train_backward_pool(long long rows, int nlayers, const pn
                              pooling == 3 || pooling == 0 ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, grad_out, nullptr,
                              grad_feat_rows, grad_points, reproducible, ws, opts, stream);
 }
+
+// ---- the coordinate gradients (pn2_mlp_train_*_xyz: entry points, argument checks and kernels in train_mlp_xyz.hip) ----
+namespace pn2 {
+long long tl_xyz_ws_bytes(long long rows, int nlayers, const int *widths, int pool_rows, int pooling, const int *group_dims,
+                          const pn2_train_opts *opts)
+{
+    if (!widths || !group_dims || nlayers < 1 || nlayers > 8) return -1;
+    const GroupDims gd = {group_dims[0], group_dims[1], group_dims[2], group_dims[3], group_dims[4], group_dims[5]};
+    const Opts o = opts_of(opts);
+    TlPlan pl;
+    if (!tl_plan(rows, nlayers, widths, pooling ? 0 : pool_rows, 1, pl, &gd, o)) return -1;      // as pn2_mlp_train_ws_bytes_pool
+    XyzPlan xp;
+    if (!xyz_plan(pl, rows, nlayers, widths, gd, o, xp)) return -1;
+    return (long long)xp.total;
+}
+
+int tl_xyz_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, int pool_rows, int pooling,
+                    const float *out, const int *argsel, const float *zsel, const float *pool_w, const float *grad_out,
+                    float *grad_feat_rows, float *grad_points, float *grad_xyz, float *grad_new_xyz, int reproducible, void *ws,
+                    const pn2_train_opts *opts, void *stream)
+{
+    if (int rc = pool_args(pool_rows, pooling, group != nullptr)) return rc;
+    return tl_train_backward(rows, nlayers, layers, group, nullptr, pool_rows, pooling, out, pooling == 3 || pooling == 0 ? argsel : nullptr,
+                             pooling == 3 || pooling == 0 ? zsel : nullptr, nullptr, grad_out, nullptr, grad_feat_rows, grad_points,
+                             reproducible, ws, opts, stream, nullptr, grad_xyz, grad_new_xyz);
+}
+}  // namespace pn2
 
 // ---- the FP level with layer 1 per known point (pn2_mlp_train_*_fp: entry points and argument checks in train_mlp_fp.hip) ----
 namespace pn2 {

@@ -168,6 +168,9 @@ class PointnetSAModule(nn.Module):
         c = self.mlp.c_out * (2 if pooling == "max_and_avg" else 1)
         self.mlp2 = _SharedMLP(c, mlp2, bn) if mlp2 else None
         self.fused_mlp = True          # eval-mode forward may use the fused MFMA kernel (sa_mlp.py)
+        # training with an xyz that requires a gradient: take the fused node with its coordinate gradients
+        # (train_mlp.sa_mlp_train(..., xyz_grad=True)) instead of the layer-by-layer path. Opt-in.
+        self.fused_xyz_grad = False
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
@@ -202,11 +205,15 @@ class PointnetSAModule(nn.Module):
         where pn2_mlp_train_pool_supported says so."""
         if not self.fused_mlp or not self.training or not xyz.is_cuda:
             return False
-        if (torch.is_grad_enabled() and xyz.requires_grad) or (points is not None and not self.use_xyz):
+        want_xyz = torch.is_grad_enabled() and xyz.requires_grad
+        if (want_xyz and not self.fused_xyz_grad) or (points is not None and not self.use_xyz):
             return False
         b, n, _ = xyz.shape
         ns = n if self.group_all else self.nsample
         rows = b * (1 if self.group_all else self.npoint) * ns
+        if want_xyz:                               # (never weighted_avg: its weights depend on xyz)
+            return train_mlp.xyz_grad_supported(self.mlp.net, rows, ns, self.pooling, b, n, 1 if self.group_all else self.npoint,
+                                                points.shape[2] if points is not None else 0, not self.group_all)
         if self.pooling != "max":
             return train_mlp.pool_supported(self.mlp.net, rows, ns, self.pooling)
         return train_mlp.stack_supported(self.mlp.net, rows, ns, True)
@@ -255,11 +262,12 @@ class PointnetSAModule(nn.Module):
     def _forward_on(self, xyz, points, g):
         """forward() on a geometry computed ahead (geometry.py): the layer stack only, same paths, same results -- and the same
         gradients: with xyz.requires_grad the centroids are re-gathered differentiably (SAGeometry.new_xyz_for; the fused
-        paths below are not taken then, _train_fused_ok / _fused_ok refuse an xyz that needs a gradient)."""
+        training node is taken then only with fused_xyz_grad, the inference kernels never)."""
         new_xyz, idx = g.new_xyz_for(xyz), g.idx
         if self._train_fused_ok(xyz, points):
             self.last_path = "fused_train"
-            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling)
+            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling,
+                                            xyz_grad=torch.is_grad_enabled() and xyz.requires_grad)
             return new_xyz, self._post(out), idx
         if self._fused_ok(xyz, points):
             self.last_path = "fused"
@@ -280,18 +288,21 @@ class PointnetSAModule(nn.Module):
             # training: the level's geometry in the fused launches, then ONE autograd node for gather + layer stack
             # (batch-statistics batch norm) + pooling, forward and backward on the matrix cores (train_mlp.py)
             self.last_path = "fused_train"
+            want_xyz = torch.is_grad_enabled() and xyz.requires_grad     # (fused_xyz_grad: the node differentiates the coordinates too)
             if self.group_all:
                 b, n, _ = xyz.shape
                 new_xyz = torch.zeros((b, 1, 3), dtype=torch.float32, device=xyz.device)
                 idx = torch.arange(n, dtype=torch.int32, device=xyz.device).reshape(1, 1, n).repeat(b, 1, 1)
-                out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True, self.pooling)
+                out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True, self.pooling, xyz_grad=want_xyz)
                 return new_xyz, self._post(out), idx
             if self.knn:
-                _, new_xyz = farthest_point_sample_gather(self.npoint, xyz)
+                fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz)
                 _, idx = knn_point(self.nsample, xyz, new_xyz)
             else:
-                _, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
-            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling)
+                fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
+            if want_xyz:                                              # the centroids' path back to xyz: GatherPoint's gradient (:40)
+                new_xyz = mark_fps_ordered(gather_point(xyz, fps_idx))
+            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling, xyz_grad=want_xyz)
             return new_xyz, self._post(out), idx
         if self.group_all and self._fused_ok(xyz, points):
             # sample_and_group_all (:59-84) + the layer stack + reduce_max in ONE kernel: new_xyz = origin, the
@@ -364,6 +375,7 @@ class PointnetSAModuleMSG(nn.Module):
         feat = 3 if c_in == 0 else (c_in + 3 if use_xyz else c_in)
         self.mlps = nn.ModuleList([_SharedMLP(feat, widths, bn) for widths in mlp_list])
         self.fused_mlp = True          # eval-mode forward may use the fused MFMA kernel (sa_mlp.py)
+        self.fused_xyz_grad = False    # see PointnetSAModule: the fused training node for an xyz that requires a gradient (opt-in)
         self.last_path = None
         self._pack_cache = {}
 
@@ -423,11 +435,16 @@ class PointnetSAModuleMSG(nn.Module):
         return new_xyz, torch.cat(outs, dim=2)
 
     def _train_fused_ok(self, xyz, points):
-        if not self.fused_mlp or not self.training or not xyz.is_cuda or (torch.is_grad_enabled() and xyz.requires_grad):
+        want_xyz = torch.is_grad_enabled() and xyz.requires_grad
+        if not self.fused_mlp or not self.training or not xyz.is_cuda or (want_xyz and not self.fused_xyz_grad):
             return False
         if points is not None and not self.use_xyz:
             return False
         rows = xyz.shape[0] * self.npoint
+        if want_xyz:
+            cfeat = points.shape[2] if points is not None else 0
+            return all(train_mlp.xyz_grad_supported(mlp.net, rows * ns, ns, "max", xyz.shape[0], xyz.shape[1], self.npoint, cfeat)
+                       for mlp, ns in zip(self.mlps, self.nsample_list))
         return all(train_mlp.stack_supported(mlp.net, rows * ns, ns, True) for mlp, ns in zip(self.mlps, self.nsample_list))
 
     def forward(self, xyz, points, geometry=None):
@@ -439,11 +456,14 @@ class PointnetSAModuleMSG(nn.Module):
             # training: grouping launches as in inference, then one autograd node per scale (train_mlp.py);
             # channel order features FIRST (:184)
             self.last_path = "fused_train"
+            want_xyz = torch.is_grad_enabled() and xyz.requires_grad     # (fused_xyz_grad: autograd adds the scales' coordinate gradients)
             if g is None:
-                new_xyz, scales = self._group_scales(xyz, True)
+                new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
+                if want_xyz:                                          # GatherPoint's gradient (:173)
+                    new_xyz = mark_fps_ordered(gather_point(xyz, fps_idx))
             else:
-                new_xyz, scales = g.new_xyz, [(idx, None) for idx in g.idx]
-            outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False)[0]
+                new_xyz, scales = g.new_xyz_for(xyz), [(idx, None) for idx in g.idx]
+            outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False, xyz_grad=want_xyz)[0]
                     for mlp, (idx, _) in zip(self.mlps, scales)]
             return new_xyz, torch.cat(outs, dim=2)
         self.last_path = "unfused"

@@ -133,7 +133,8 @@ def stack_supported(net, rows, pool_rows=0, grouped=True):
 
 class _Level:
     """Non-tensor description of one call (what the autograd node needs besides its differentiable inputs)."""
-    __slots__ = ("pairs", "rows", "pool_rows", "xyz", "new_xyz", "idx", "b", "n", "m", "nsample", "xyz_first", "grouped", "pooling")
+    __slots__ = ("pairs", "rows", "pool_rows", "xyz", "new_xyz", "idx", "b", "n", "m", "nsample", "xyz_first", "grouped", "pooling",
+                 "xyz_grad")
 
 
 # pointnet_sa_module's pooling modes (utils/pointnet_util.py:128-142) -> the library's codes (pn2_mlp_train_forward_pool)
@@ -149,6 +150,20 @@ def pool_supported(net, rows, ns, pooling):
     widths = [pairs[0][0].in_channels] + [c.out_channels for c, _ in pairs]
     arr = (ctypes.c_int * len(widths))(*widths)
     return bool(_C.lib().pn2_mlp_train_pool_supported(rows, len(widths) - 1, arr, ns, code))
+
+
+def xyz_grad_supported(net, rows, ns, pooling, b, n, m, cfeat, has_idx=True):
+    """Can the fused training node also return the gradients with respect to xyz and new_xyz (sa_mlp_train(..., xyz_grad=True))
+    for this stack on `rows` = b m ns grouped rows of b clouds of n points with cfeat feature channels? Mirrors
+    pn2_mlp_train_xyz_supported: every pooling but weighted_avg, wherever pool_supported says yes. has_idx=False: group_all."""
+    code = POOLING.get(pooling)
+    if code is None or code == 2 or not stack_supported(net, rows, ns, True):
+        return False
+    pairs = conv_bn_pairs(net)
+    widths = [pairs[0][0].in_channels] + [c.out_channels for c, _ in pairs]
+    arr = (ctypes.c_int * len(widths))(*widths)
+    gdims = (ctypes.c_int * 6)(b, n, m, ns, cfeat, 1 if has_idx else 0)
+    return bool(_C.lib().pn2_mlp_train_xyz_supported(rows, len(widths) - 1, arr, ns, code, gdims))
 
 
 def _layer_array(level, weights, biases, gammas, betas, zs, saves, grads=None, update_running=True):
@@ -200,6 +215,13 @@ def _ws(rows, widths, pool_rows, backward, dev, gdims=None, opts=None):
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
 
 
+def _ws_xyz(rows, widths, pool_rows, code, dev, gdims, opts=None):
+    arr = (ctypes.c_int * len(widths))(*widths)
+    nbytes = _C.lib().pn2_mlp_train_ws_bytes_xyz(rows, len(widths) - 1, arr, pool_rows, code, gdims, opts)
+    require(nbytes >= 0, "pn2_mlp_train: unsupported stack or pooling for the coordinate gradients")
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+
+
 def _ws_pool(rows, widths, pool_rows, code, backward, dev, gdims=None, opts=None):
     arr = (ctypes.c_int * len(widths))(*widths)
     nbytes = _C.lib().pn2_mlp_train_ws_bytes_pool(rows, len(widths) - 1, arr, pool_rows, code, backward, gdims, opts)
@@ -245,11 +267,12 @@ def _grad_slot(param, like):
 
 
 class _TrainMLP(torch.autograd.Function):
-    """inputs: level, x (points (b,n,c) when grouped -- may be None -- else the (rows, cin) input), then per layer
-    conv.weight, conv.bias (or None), bn.weight, bn.bias."""
+    """inputs: level, x (points (b,n,c) when grouped -- may be None -- else the (rows, cin) input), xyz and new_xyz (the
+    level's own tensors when their gradients are wanted, level.xyz_grad; else None: the coordinates are constants of the node),
+    then per layer conv.weight, conv.bias (or None), bn.weight, bn.bias."""
 
     @staticmethod
-    def forward(ctx, level, x, *params):
+    def forward(ctx, level, x, xyz_in, new_xyz_in, *params):
         n = len(level.pairs)
         weights = [f32(params[4 * l], "weight") for l in range(n)]
         biases = [params[4 * l + 1] for l in range(n)]
@@ -339,6 +362,9 @@ class _TrainMLP(torch.autograd.Function):
             grads.append(slots if direct[-1] else
                          (torch.empty_like(weights[l]), torch.empty_like(gammas[l]), torch.empty_like(betas[l])))
         need_x = ctx.needs_input_grad[1] and x is not None
+        # the coordinate gradients (sa_mlp_train(..., xyz_grad=True)): written by the library, both or neither
+        want_xyz = bool(getattr(level, "xyz_grad", False)) and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        grad_xyz = grad_new_xyz = None
         grad_x = grad_rows = grad_pts = None
         gdims = _group_dims(level, x)
         warr = (ctypes.c_int * len(widths))(*widths)
@@ -350,8 +376,14 @@ class _TrainMLP(torch.autograd.Function):
             grad_rows = torch.empty((rows, x.shape[2]), dtype=torch.float32, device=dev)
         elif need_x:
             grad_x = torch.empty((rows, widths[0]), dtype=torch.float32, device=dev)
-        ws = _ws_pool(rows, widths, level.pool_rows, code, 1, dev, gdims, opts) if code else \
-            _ws(rows, widths, level.pool_rows, 1, dev, gdims, opts)
+        if want_xyz:
+            grad_xyz = torch.empty((level.b, level.n, 3), dtype=torch.float32, device=dev)
+            if level.new_xyz is not None:
+                grad_new_xyz = torch.empty((level.b, level.m, 3), dtype=torch.float32, device=dev)
+            ws = _ws_xyz(rows, widths, level.pool_rows, code, dev, gdims, opts)
+        else:
+            ws = _ws_pool(rows, widths, level.pool_rows, code, 1, dev, gdims, opts) if code else \
+                _ws(rows, widths, level.pool_rows, 1, dev, gdims, opts)
         if _KEEP_WS[0]:
             _KEEP_WS[1] = (ws, rows, widths, level.pool_rows)
         arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
@@ -359,7 +391,13 @@ class _TrainMLP(torch.autograd.Function):
             arr[l].grad_accumulate = 1 if direct[l] else 0
         grp = _group_struct(level, x) if level.grouped else None
         with on_device(dev):
-            if code:
+            if want_xyz:
+                _C.check(_C.lib().pn2_mlp_train_backward_xyz(rows, n, arr, ctypes.byref(grp), level.pool_rows, code, ptr(out),
+                                                             ptr(argsel) if code in (0, 3) else None, ptr(zsel), None,
+                                                             ptr(grad_out), ptr(grad_rows), ptr(grad_pts), ptr(grad_xyz),
+                                                             ptr(grad_new_xyz), 1 if is_deterministic() else 0, ptr(ws), opts,
+                                                             stream_ptr(dev)), "mlp_train_backward_xyz")
+            elif code:
                 _C.check(_C.lib().pn2_mlp_train_backward_pool(rows, n, arr, ctypes.byref(grp), level.pool_rows, code, ptr(out),
                                                               ptr(argsel) if code == 3 else None, ptr(zsel), ptr(pool_w),
                                                               ptr(grad_out), ptr(grad_rows), ptr(grad_pts),
@@ -392,7 +430,8 @@ class _TrainMLP(torch.autograd.Function):
                 else:
                     _C.check(_C.lib().pn2_group_point_grad(b, npts, c, m, ns, ptr(grad_rows), ptr(level.idx), ptr(grad_x),
                                                            stream_ptr(dev)), "group_point_grad")
-        result = [None, grad_x if need_x else None]
+        result = [None, grad_x if need_x else None, grad_xyz if ctx.needs_input_grad[2] else None,
+                  grad_new_xyz if ctx.needs_input_grad[3] else None]
         # the conv bias gradients: exactly zero under batch norm (one zero buffer, one fill launch, a view per layer)
         zero = None
         off = 0
@@ -415,12 +454,16 @@ def _params(pairs):
     return out
 
 
-def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max"):
+def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", xyz_grad=False):
     """Training-mode shared MLP + pooling of one SA level / one MSG scale.
     net: nn.Sequential of (Conv2d 1x1, BatchNorm2d, ReLU) triples; xyz (b,n,3); new_xyz (b,m,3) or None and idx
     (b,m,nsample) i32 or None (both None: the group_all level); points (b,n,c) or None.
     pooling: "max" (default), "avg", "weighted_avg" or "max_and_avg" (utils/pointnet_util.py:128-142; the last gives
     (b, m, 2 cout) = concat([avg, max])).
+    xyz_grad: xyz and new_xyz are differentiable inputs of the node too (GroupPoint's and GatherPoint's gradients through
+    grouped_xyz - new_xyz, :44-46; pn2_mlp_train_backward_xyz) -- every pooling but weighted_avg. The gradient of new_xyz is
+    returned for new_xyz itself: pass new_xyz = gather_point(xyz, fps_idx) and autograd adds the centroids' path back to xyz.
+    Default False: the coordinates are constants of the node (no gradient flows to them), outputs and saved tensors the same bits.
     -> (b, m, cout) pooled features (differentiable w.r.t. points and the parameters), argsel (b, m, cout) i32 -- the max's
     selection; None for avg and weighted_avg."""
     require(pooling in POOLING, "unknown pooling %r" % (pooling,))
@@ -459,7 +502,14 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max"):
     require(lv.pooling == 0 or pool_supported(net, lv.rows, lv.pool_rows, pooling),
             "unsupported stack for the fused training path with pooling %r" % (pooling,))
     same_device(xyz, pairs[0][0].weight)
-    out, argsel = _TrainMLP.apply(lv, points, *_params(pairs))
+    lv.xyz_grad = bool(xyz_grad)
+    if lv.xyz_grad:
+        require(xyz_grad_supported(net, lv.rows, lv.pool_rows, pooling, b, n, lv.m, points.shape[2] if points is not None else 0,
+                                   idx is not None),
+                "the fused training path has no coordinate gradients for this level (pooling %r)" % (pooling,))
+        out, argsel = _TrainMLP.apply(lv, points, lv.xyz, lv.new_xyz, *_params(pairs))
+    else:
+        out, argsel = _TrainMLP.apply(lv, points, None, None, *_params(pairs))
     if lv.pooling in (1, 2):
         return out.view(b, lv.m, -1), None
     return out.view(b, lv.m, -1), argsel.view(b, lv.m, -1)
@@ -497,7 +547,8 @@ def fp_mlp_train(net, x, cin=None):
             x = torch.nn.functional.pad(x, (0, pad))
         w = params[0]
         params[0] = torch.nn.functional.pad(w, (0, 0) * (w.dim() - 2) + (0, pad))
-    out = _TrainMLP.apply(lv, x, *params)
+    lv.xyz_grad = False
+    out = _TrainMLP.apply(lv, x, None, None, *params)
     return out.view(b, n, -1)
 
 
