@@ -590,6 +590,38 @@ int pn2_mlp_train_backward_fp(int nlayers, const pn2_bn_layer *layers, const pn2
                               const float *grad_out, float *grad_points2, float *grad_points1, int reproducible, void *ws,
                               const pn2_train_opts *opts, void *stream);
 
+/* The training node with FROZEN batch-norm statistics (csrc/train_mlp_frozen.hip): every layer normalises with its RUNNING
+ * statistics (torch.nn.BatchNorm in eval()) -- gradients through a model in eval(), fine-tuning with frozen batch norms.
+ * layers[l].running_mean / running_var are REQUIRED (PN2_E_NULL without them) and only read; momentum is ignored. With the
+ * stored z = h W (without the conv bias): invstd = 1 / sqrt(running_var + eps), a = gamma invstd, m' = running_mean - bias,
+ * c = beta - a m' -- `save` keeps its layout (m', invstd, a, c) -- y = relu(a z + c), dz = a dy, grad_beta = sum dy,
+ * grad_gamma = (sum dy z - m' grad_beta) invstd, grad_bias = a grad_beta (NOT zero here: the bias no longer cancels).
+ * One entry pair serves grouped rows (group != NULL, x NULL, pool_rows = nsample, pooling 0..3 as
+ * pn2_mlp_train_forward_pool) and plain rows (group NULL, x (rows, cin_1), pool_rows 0, pooling 0); the arguments are those
+ * of pn2_mlp_train_forward_pool / pn2_mlp_train_backward_xyz plus x / grad_x and
+ *   grad_bias: NULL, or nlayers pointers (cout_l each, or NULL) that receive the conv-bias gradients; layers[l].grad_accumulate
+ *              applies to them as to the other three.
+ * grad_xyz / grad_new_xyz: both NULL or as pn2_mlp_train_backward_xyz (weighted_avg refused with PN2_E_ARG).
+ * A layer whose grad_weight, grad_gamma, grad_beta and grad_bias slot are ALL NULL wants no parameter gradient: it runs no
+ * weight-gradient pass and sums nothing, and the chain stops at the lowest layer that still needs something (a parameter
+ * gradient, or layer 1's input / coordinate gradient). Otherwise grad_weight, grad_gamma and grad_beta must all be given
+ * (PN2_E_NULL). Workspaces: pn2_mlp_train_ws_bytes_frozen (want_xyz: backward with the coordinate gradients); where it runs:
+ * pn2_mlp_train_frozen_supported (= the _pool / _xyz queries). pn2_train_opts as in the other entries (fold_finalize has
+ * nothing to fold and is ignored); `reproducible` likewise. Argument errors return PN2_E_ARG / PN2_E_NULL before anything is
+ * launched: pooling outside 0..3, rows not a multiple of 32, group and x both or neither, missing running statistics. */
+int pn2_mlp_train_frozen_supported(long long rows, int nlayers, const int *widths, int pool_rows, int pooling,
+                                   const int *group_dims, int want_xyz);
+long long pn2_mlp_train_ws_bytes_frozen(long long rows, int nlayers, const int *widths, int pool_rows, int pooling, int backward,
+                                        const int *group_dims, int want_xyz, const pn2_train_opts *opts);
+int pn2_mlp_train_forward_frozen(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                 const float *x, int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w,
+                                 void *ws, const pn2_train_opts *opts, void *stream);
+int pn2_mlp_train_backward_frozen(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                  const float *x, int pool_rows, int pooling, const float *out, const int *argsel,
+                                  const float *zsel, const float *pool_w, const float *grad_out, float *grad_x,
+                                  float *grad_feat_rows, float *grad_points, float *grad_xyz, float *grad_new_xyz,
+                                  float *const *grad_bias, int reproducible, void *ws, const pn2_train_opts *opts, void *stream);
+
 /* The input rows of a feature-propagation level's layer stack in ONE launch (pointnet_fp_module, utils/pointnet_util.py:211-219):
  * inverse-distance weights from three_nn's `dist`, three_interpolate of points2 (b,m,c2), concatenation with the skip features
  * points1 (b,n,c1; NULL with c1 = 0), zero columns up to `pitch` (a multiple of 4 >= c2 + c1: the training entry points read

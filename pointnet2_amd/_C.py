@@ -102,6 +102,11 @@ _SIGNATURES = {
     "pn2_mlp_train_xyz_supported": [_ll, _i, _vp, _i, _i, _vp],
     "pn2_mlp_train_ws_bytes_xyz": [_ll, _i, _vp, _i, _i, _vp, _vp],
     "pn2_mlp_train_backward_xyz": [_ll, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "pn2_mlp_train_frozen_supported": [_ll, _i, _vp, _i, _i, _vp, _i],
+    "pn2_mlp_train_ws_bytes_frozen": [_ll, _i, _vp, _i, _i, _i, _vp, _i, _vp],
+    "pn2_mlp_train_forward_frozen": [_ll, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_mlp_train_backward_frozen": [_ll, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                      _vp, _vp, _vp],
     "pn2_mlp_train_fp_supported": [_i, _i, _i, _i, _i, _i, _vp],
     "pn2_mlp_train_ws_bytes_fp": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "pn2_mlp_train_forward_fp": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -120,6 +125,7 @@ _RESTYPES = {
     "pn2_mlp_train_ws_bytes_pool": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_xyz": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_fp": ctypes.c_longlong,
+    "pn2_mlp_train_ws_bytes_frozen": ctypes.c_longlong,
     "pn2_sample_and_group_status_offset": ctypes.c_longlong,
     "pn2_ball_threshold": ctypes.c_float,
     "pn2_version": ctypes.c_char_p,

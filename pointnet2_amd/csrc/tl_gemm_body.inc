@@ -1,6 +1,8 @@
 // Body of the training GEMM pass (train_mlp.hip: tl_gemm_kernel, and the GEMM range of tl_pair_kernel). Included as TEXT into
 // the kernel that runs it, with the names in scope that it uses: NS, AMODE (compile-time), `p` (the kernel's TlGemm argument
-// itself or a reference to it), PN2_BX / PN2_BY / PN2_GX (the workgroup's position in its (gx, slabs) grid and gx).
+// itself or a reference to it), PN2_BX / PN2_BY / PN2_GX (the workgroup's position in its (gx, slabs) grid and gx), PN2_STATS
+// (compile-time bool: false = the "no statistics" variant of the frozen-statistics node, train_mlp_frozen.hip -- no per-tile
+// sums, no sd1 / sd2 registers, no LDS reduction, no partial row; p.stats is not looked at).
 // Text, not a function: as an inlined function taking the argument struct by reference the stand-alone kernels compiled
 // differently -- the struct's fields became values live from the kernel's start instead of scalar loads at their uses, and
 // the weight-gradient kernels that carry the data gradient went 100-400 bytes per lane deeper into scratch.
@@ -172,7 +174,7 @@
                     s1 = __fadd_rn(s1, val[v]);
                     s2 = fmaf(val[v], val[v], s2);
                 }
-                if (ok && !(p.lab & 2)) {
+                if (PN2_STATS && ok && !(p.lab & 2)) {
                     sd1[t] += (double)s1;
                     sd2[t] += (double)s2;
                 }
@@ -240,11 +242,15 @@
                         const float g = y > 0.0f ? __fadd_rn(acc[t][v], ep2[t]) : 0.0f;   // ReLU of the layer below
                         if (p.nt) bstore<true>(g, ro, voff, (8 * (v >> 2) + (v & 3)) * p.N * 4);
                         else bstore<false>(g, ro, voff, (8 * (v >> 2) + (v & 3)) * p.N * 4);
-                        s1 = __fadd_rn(s1, g);
-                        s2 = fmaf(g, zz[v], s2);
+                        if (PN2_STATS) {
+                            s1 = __fadd_rn(s1, g);
+                            s2 = fmaf(g, zz[v], s2);
+                        }
                     }
-                    sd1[t] += (double)s1;
-                    sd2[t] += (double)s2;
+                    if (PN2_STATS) {
+                        sd1[t] += (double)s1;
+                        sd2[t] += (double)s2;
+                    }
                 }
             } else {
                 if (eactive && col >= p.col0 && col < p.col1) {
@@ -294,7 +300,7 @@
     } else {
         while (s0.valid) consume(s0, s0);
     }
-    if (p.emode != E_PLAIN && p.stats) {
+    if (PN2_STATS && p.emode != E_PLAIN && p.stats) {
         // per-channel sums of this workgroup's rows: the eight waves' partial sums meet in LDS and leave as ONE row of the
         // (row workgroups, 2, N) partial array -- no atomics (2048 waves adding into the same 2N addresses serialise in the
         // L2 for ~100 us per pass), and the finalisation kernel adds the rows in a fixed order

@@ -29,6 +29,7 @@
 // and a two-stage reduction sums the waves' slabs (fp64 in the last stage) in a fixed order: the result does not
 // depend on timing.
 #include "sa_mlp_common.h"
+#include "train_mlp_frozen.h"     // TlFrozen, FrozenSums, the per-channel launches of the frozen-statistics node
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -224,6 +225,7 @@ struct TlGemm {
     int prow;                   // 32 or 16
     int nt;                     // streaming (non-temporal) stores: outputs that do not fit the 256 MB Infinity Cache anyway
     int lab;                    // lab builds of the timing study only (PN2_TL_LAB): 1 = no stores, 2 = no statistics; 0 in production
+    int nostats;                // 1: the kernel's compile-time "no statistics" variant (frozen batch-norm statistics); stats is NULL then
     TlFin fin;                  // the per-channel finalisation of `stats`, by the workgroup that finishes last (fin.ticket != nullptr)
 };
 
@@ -451,16 +453,19 @@ __device__ __forceinline__ f32x16 tl_finish(const ARaw &r, const RowCtx &rc, int
     return x;
 }
 
-template <int NS, int AMODE>
+// STATS = false: the pass sums nothing (TlGemm::nostats: frozen batch-norm statistics, train_mlp_frozen.hip)
+template <int NS, int AMODE, bool STATS = true>
 __global__ __launch_bounds__(kTlThreads) void tl_gemm_kernel(const TlGemm p)
 {
 #define PN2_BX blockIdx.x
 #define PN2_BY blockIdx.y
 #define PN2_GX gridDim.x
+#define PN2_STATS STATS
 #include "tl_gemm_body.inc"
 #undef PN2_BX
 #undef PN2_BY
 #undef PN2_GX
+#undef PN2_STATS
 }
 
 // ---- weights -> three-level bf16 operand tiles, on the device ---------------------------------------------------------
@@ -612,7 +617,7 @@ __global__ __launch_bounds__(256) void tl_pool_grad_kernel(long long groups, int
     sh[0][ry][threadIdx.x & 63] = s1;
     sh[1][ry][threadIdx.x & 63] = s2;
     __syncthreads();
-    if (ry == 0 && c < N) {
+    if (stats && ry == 0 && c < N) {                 // (stats == nullptr: a top layer that wants no parameter gradient, frozen statistics)
         const int x = threadIdx.x & 63;
         stats[((size_t)blockIdx.y * 2) * N + c] = sh[0][0][x] + sh[0][1][x] + sh[0][2][x] + sh[0][3][x];
         stats[((size_t)blockIdx.y * 2 + 1) * N + c] = sh[1][0][x] + sh[1][1][x] + sh[1][2][x] + sh[1][3][x];
@@ -675,7 +680,7 @@ __global__ __launch_bounds__(256) void tl_top_grad_kernel(long long rows, int N,
     sh[0][ry][threadIdx.x & 63] = s1;
     sh[1][ry][threadIdx.x & 63] = s2;
     __syncthreads();
-    if (ry == 0 && c < N) {
+    if (stats && ry == 0 && c < N) {                 // (stats == nullptr: a top layer that wants no parameter gradient, frozen statistics)
         const int x = threadIdx.x & 63;
         stats[((size_t)blockIdx.y * 2) * N + c] = sh[0][0][x] + sh[0][1][x] + sh[0][2][x] + sh[0][3][x];
         stats[((size_t)blockIdx.y * 2 + 1) * N + c] = sh[1][0][x] + sh[1][1][x] + sh[1][2][x] + sh[1][3][x];
@@ -823,7 +828,7 @@ __global__ __launch_bounds__(256) void tl_pool_top_grad_kernel(long long rows, i
     for (int j = 0; j < 4; ++j) { sh[0][ry][x0 + j] = s1[j]; sh[1][ry][x0 + j] = s2[j]; }
     __syncthreads();
     const int x = threadIdx.x, col = blockIdx.x * 64 + x;
-    if (x < 64 && col < N) {
+    if (stats && x < 64 && col < N) {
         double t1 = 0.0, t2 = 0.0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) { t1 += sh[0][i][x]; t2 += sh[1][i][x]; }
@@ -1161,7 +1166,9 @@ __global__ __launch_bounds__(kTlThreads) void tl_pair_kernel(const TlGemm pg, co
 #define PN2_BX sbx
 #define PN2_BY sby
 #define PN2_GX ga
+#define PN2_STATS true                  // (the pair keeps the sums as a run-time choice: p.stats may be NULL under frozen statistics)
 #include "tl_gemm_body.inc"
+#undef PN2_STATS
 #undef PN2_BX
 #undef PN2_BY
 #undef PN2_GX
@@ -1553,6 +1560,7 @@ __global__ __launch_bounds__(kL1Threads) void tl_l1_forward_kernel(const TlL1 p)
             }
         }
     }
+    if (!p.stats) return;                       // frozen statistics (train_mlp_frozen.hip): nobody reads the batch moments
     __shared__ double red[2][kL1Threads][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { red[0][threadIdx.x][i] = (double)s1[i]; red[1][threadIdx.x][i] = (double)s2[i]; }
@@ -2256,7 +2264,7 @@ static int launch_gemm_ns(int amode, const TlGemm &p, const GemmShape &g, dim3 g
 {
 #define PN2_TL_CASE(M)                                                                   \
     case M: {                                                                            \
-        auto kern = tl_gemm_kernel<NS, M>;                                               \
+        auto kern = p.nostats ? tl_gemm_kernel<NS, M, false> : tl_gemm_kernel<NS, M, true>; \
         if (int rc = allow_dynamic_lds(kern, lds)) return rc;                            \
         return launch(kern, grid, dim3(kTlThreads), lds, st, p);                         \
     }
@@ -2659,7 +2667,7 @@ static int launch_l1_forward(long long rows, const GroupDims &gd, const pn2_grou
 
 // dz_1 (in place when `store`) and dW1x -> rows [xyz_off, xyz_off + 3) of the layer's weight gradient
 static int launch_l1_dz(long long rows, const GroupDims &gd, const pn2_group_src *group, const pn2_bn_layer &L, float *dy,
-                        const float *coef, float *part, bool store, hipStream_t st)
+                        const float *coef, float *part, bool store, hipStream_t st, bool wgrad = true)
 {
     const TlGather gt = make_gather(group);
     TlL1 q;
@@ -2676,6 +2684,7 @@ static int launch_l1_dz(long long rows, const GroupDims &gd, const pn2_group_src
     if (int rc = store ? launch(tl_l1_dz_kernel<true, false>, dim3((unsigned)blocks), dim3(kL1Threads), 0, st, q)
                  : feat ? launch(tl_l1_dz_kernel<false, true>, dim3((unsigned)blocks), dim3(kL1Threads), 0, st, q)
                         : launch(tl_l1_dz_kernel<false, false>, dim3((unsigned)blocks), dim3(kL1Threads), 0, st, q)) return rc;
+    if (!wgrad) return PN2_OK;                                    // dz_1 alone (frozen statistics, no parameter gradient wanted)
     return launch(tl_l1_wx_reduce_kernel, dim3((unsigned)((nin * L.cout + 7) / 8)), dim3(256), 0, st, (const float *)part, (int)blocks,
                   L.cout, nin, L.grad_weight + gt.xyz_off * L.w_stride_k, L.grad_weight + gt.feat_off * L.w_stride_k, L.w_stride_k,
                   L.w_stride_n, L.grad_accumulate);
@@ -2721,12 +2730,13 @@ extern "C" int pn2_mlp_train_forward(long long rows, int nlayers, const pn2_bn_l
 // pooling: 0 max (the _ex entry), 1 avg, 2 weighted_avg, 3 max_and_avg (pn2_mlp_train_forward_pool; arguments checked there)
 static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
                             int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
-                            const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr)
+                            const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr, const pn2::TlFrozen *fr = nullptr)
 {
     using namespace pn2;
     const Opts o = opts_of(opts);
     int widths[9];
     if (!layers_ok(rows, nlayers, layers, group, widths, fp)) return PN2_E_ARG;
+    if (fr && fp) return PN2_E_ARG;                              // (the FP node with layer 1 per known point has no frozen form)
     const bool want_max = pooling == 0 || pooling == 3;          // the extrema of the GEMM epilogue (E_POOL)
     if ((!group && !x && !fp) || !out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w)) return PN2_E_NULL;
     if (pool_rows && (rows % pool_rows || (group && pool_rows != group->nsample))) return PN2_E_ARG;
@@ -2767,10 +2777,14 @@ static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *lay
                 add_pack_job(jobs, nj, L.weight, L.w_stride_k, L.w_stride_n, gemm_shape(rows, L.cin, L.cout, o), base + pl.pack[l]);
             }
         }
-        fold = fold_wanted(o) && nj > 0;                          // (the pack launch zeroes the tickets)
+        fold = fold_wanted(o) && nj > 0 && !fr;                   // (the pack launch zeroes the tickets; frozen: nothing to fold)
         if (fold) jobs.tickets = tickets;
         if (int rc = launch_pack_jobs(jobs, nj, st)) return rc;
     }
+    if (fr)                                                       // every layer's (m', invstd, a, c) from the running statistics
+        if (int rc = frozen_launch_save(nlayers, layers, st)) return rc;
+    // a layer's batch moments: summed by its pass, or not at all under frozen statistics
+    auto moments = [&](int l) -> double * { return fr ? nullptr : reinterpret_cast<double *>(base + pl.stats[l]); };
     // The conv bias is NOT added to the pre-norm tensors: batch normalisation removes any per-channel constant, so
     // z_l := h W_l gives the same output, the same gradients (the bias gradient is zero) and the same batch variance; only
     // the batch MEAN that enters the running average is mean(z_l) + b_l (tl_bn_finalize_kernel). It is more than a saved
@@ -2846,7 +2860,8 @@ static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *lay
                 if (int rc = launch_gemm(A_PLAIN, q, gp, st, o)) return rc;
             }
             int np = 0;
-            if (int rc = launch_l1_forward(rows, gd, group, L, P, reinterpret_cast<double *>(base + pl.stats[l]), st, &np)) return rc;
+            if (int rc = launch_l1_forward(rows, gd, group, L, P, moments(l), st, &np)) return rc;
+            if (fr) continue;
             if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
                                 reinterpret_cast<const double *>(base + pl.stats[l]), np, L.cout, (double)rows, L.gamma,
                                 L.beta, L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
@@ -2855,7 +2870,8 @@ static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *lay
         if (l == 0 && coords_only) {
             // a level without features: z_1 = b + (xyz - c) W1 in one pass on the vector units (tl_l1_forward_kernel, no P)
             int np = 0;
-            if (int rc = launch_l1_forward(rows, gd, group, L, nullptr, reinterpret_cast<double *>(base + pl.stats[l]), st, &np)) return rc;
+            if (int rc = launch_l1_forward(rows, gd, group, L, nullptr, moments(l), st, &np)) return rc;
+            if (fr) continue;
             if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
                                 reinterpret_cast<const double *>(base + pl.stats[l]), np, L.cout, (double)rows, L.gamma,
                                 L.beta, L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
@@ -2872,7 +2888,8 @@ static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *lay
         p.bias = nullptr;                                        // see the comment above the loop
         p.emode = (last && pool_rows && want_max) ? E_POOL : E_STORE;
         p.out = (last && !keep_top) ? nullptr : L.z;              // the pooled top layer of a large level is never written
-        p.stats = reinterpret_cast<double *>(base + pl.stats[l]);
+        p.stats = moments(l);
+        p.nostats = fr ? 1 : 0;                                   // the GEMM's compile-time "no statistics" variant
         if (p.emode == E_POOL) {
             const long long parts = rows / (pool_rows == 16 ? 16 : 32);
             float *pp = reinterpret_cast<float *>(base + pl.pool);
@@ -2884,7 +2901,7 @@ static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *lay
         int nparts = 0;
         if (fold) p.fin = fin_forward(L, rows, p.stats, tickets + l);
         if (int rc = launch_gemm(amode, p, g, st, o, &nparts)) return rc;
-        if (!fold)
+        if (!fold && !fr)
             if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
                                 reinterpret_cast<const double *>(base + pl.stats[l]), nparts, L.cout, (double)rows, L.gamma, L.beta,
                                 L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
@@ -2942,13 +2959,14 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                              int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel, const float *pool_w,
                              const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points, int reproducible,
                              void *ws, const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr,
-                             float *grad_xyz = nullptr, float *grad_new_xyz = nullptr)
+                             float *grad_xyz = nullptr, float *grad_new_xyz = nullptr, const pn2::TlFrozen *fr = nullptr)
 {
     using namespace pn2;
     const Opts o = opts_of(opts);
     const int cus = device_cus();
     int widths[9];
     if (!layers_ok(rows, nlayers, layers, group, widths, fp)) return PN2_E_ARG;
+    if (fr && fp) return PN2_E_ARG;
     const bool want_xyz = group && grad_xyz;            // the coordinate gradients (pn2_mlp_train_backward_xyz, train_mlp_xyz.hip)
     const bool want_max = pooling == 0 || pooling == 3;
     if ((!group && !x && !fp) || !out || !grad_out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w))
@@ -2956,8 +2974,15 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
     const int avg_rows = pooling ? pool_rows : 0;       // > 0: the group size of the averaged top layer
     if (pooling && (!group || avg_rows <= 0 || rows % avg_rows || avg_rows != group->nsample)) return PN2_E_ARG;
     if (pooling) pool_rows = 0;
-    for (int l = 0; l < nlayers; ++l)
-        if (!layers[l].grad_weight || !layers[l].grad_gamma || !layers[l].grad_beta) return PN2_E_NULL;
+    // frozen statistics: a layer whose four gradient slots are all NULL wants no parameter gradient -- no weight-gradient pass,
+    // no per-channel sums (batch statistics cannot allow that: dz itself needs the sums)
+    bool skip[8] = {false, false, false, false, false, false, false, false};
+    for (int l = 0; l < nlayers; ++l) {
+        const bool all3 = layers[l].grad_weight && layers[l].grad_gamma && layers[l].grad_beta;
+        const bool any = layers[l].grad_weight || layers[l].grad_gamma || layers[l].grad_beta || (fr && fr->grad_bias && fr->grad_bias[l]);
+        if (fr && !any) { skip[l] = true; continue; }
+        if (!all3) return PN2_E_NULL;
+    }
     TlPlan pl;
     GroupDims gd;
     if (group) gd = group_dims(group);
@@ -2976,11 +3001,19 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
         if (!layers[l].z && !(ztop && l == nlayers - 1)) return PN2_E_NULL;
     // Which layers run their data gradient inside the weight-gradient pass (one pass over the layer's activations instead of
     // two, tl_wgrad_kernel<.., DY>): decided here, once, for the packing below and the launches
+    // frozen statistics: the chain stops at the lowest layer that still needs something (lo; 0 otherwise), and a layer takes
+    // a data gradient from above only where something below it is wanted
+    int lo = 0;
+    if (fr)
+        while (lo < nlayers - 1 && skip[lo] && !(lo == 0 && (want_dx || want_xyz))) ++lo;
+    auto below = [&](int l) { return l > lo || (l == 0 && want_dx); };
+    auto sums_of = [&](int l) -> double * { return skip[l] ? nullptr : reinterpret_cast<double *>(base + pl.stats[l]); };
     FuseShape fz[8];
     WgradShape wz[8];
     memset(fz, 0, sizeof(fz));
-    for (int l = 0; l < nlayers; ++l) {
+    for (int l = lo; l < nlayers; ++l) {
         const pn2_bn_layer &L = layers[l];
+        if (skip[l] || (l > 0 && !below(l))) continue;              // no weight-gradient pass to fuse into / no data gradient to fuse
         if (ztop && l == nlayers - 1) {
             // (the z-free pooled top layer in one pass is correct and tested, but not yet faster than its three kernels -- 690 vs
             // 590 us at the metric shape: two waves carry the whole data gradient, 72 MFMAs on transposed reads each -- so the
@@ -3000,9 +3033,9 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
         TlPackJobs jobs;                                          // W_l^T of every data-gradient GEMM, one launch
         memset(&jobs, 0, sizeof(jobs));
         int nj = 0;
-        for (int l = 0; l < nlayers; ++l) {
+        for (int l = lo; l < nlayers; ++l) {
             const pn2_bn_layer &L = layers[l];
-            if ((l > 0 || want_dx) && !(ztop && l == nlayers - 1)) {      // dy_{l-1} = dz_l . W_l^T
+            if (below(l) && !(ztop && l == nlayers - 1)) {               // dy_{l-1} = dz_l . W_l^T
                 if (fz[l].ok) {                                   // every output tile in ONE slab (the fused pass keeps W^T resident)
                     GemmShape gg;
                     memset(&gg, 0, sizeof(gg));
@@ -3030,9 +3063,14 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
             jobs.ident_c = layers[0].cout;
         }
         ident_written = jobs.ident != nullptr;
-        fold = fold_wanted(o) && nj > 0;                          // (the pack launch zeroes the tickets)
+        fold = fold_wanted(o) && nj > 0 && !fr;                   // (the pack launch zeroes the tickets)
         if (fold) jobs.tickets = tickets;
         if (int rc = launch_pack_jobs(jobs, nj, st)) return rc;
+    }
+    if (fr) {                                                     // dz = a dy for every layer, known before the first pass
+        float *cf[8];
+        for (int l = 0; l < nlayers; ++l) cf[l] = reinterpret_cast<float *>(base + pl.coef[l]);
+        if (int rc = frozen_launch_coef(nlayers, layers, cf, st)) return rc;
     }
     bool folded[8] = {false, false, false, false, false, false, false, false};     // layers whose backward finalisation ran inside the pass above
     // the data-gradient GEMM that sums (dy, dy z) of layer l - 1 also turns the sums into that layer's gradients and coefficients
@@ -3052,20 +3090,20 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
         nparts[nlayers - 1] = (int)gy;
         if (int rc = launch(tl_pool_top_grad_kernel, dim3((unsigned)((T.cout + 63) / 64), (unsigned)gy), dim3(256), 0, st, rows, avg_rows,
                             T.cout, grad_out, (const float *)T.z, (const float *)T.save, pool_w, pooling == 3 ? argsel : nullptr, ga,
-                            reinterpret_cast<double *>(base + pl.stats[nlayers - 1]))) return rc;
+                            sums_of(nlayers - 1))) return rc;
     } else if (pool_rows) {
         const long long groups = rows / pool_rows;
         long long gy = (groups + 63) / 64;
         if (gy > kMaxParts) gy = kMaxParts;
         nparts[nlayers - 1] = (int)gy;
         if (int rc = launch(tl_pool_grad_kernel, dim3((unsigned)((T.cout + 63) / 64), (unsigned)gy), dim3(256), 0, st, groups, T.cout, out,
-                            grad_out, zsel, gq, reinterpret_cast<double *>(base + pl.stats[nlayers - 1]))) return rc;
+                            grad_out, zsel, gq, sums_of(nlayers - 1))) return rc;
     } else {
         long long gy = (rows + 255) / 256;
         if (gy > kMaxParts) gy = kMaxParts;
         nparts[nlayers - 1] = (int)gy;
         if (int rc = launch(tl_top_grad_kernel, dim3((unsigned)((T.cout + 63) / 64), (unsigned)gy), dim3(256), 0, st, rows, T.cout, out,
-                            grad_out, (const float *)T.z, ga, reinterpret_cast<double *>(base + pl.stats[nlayers - 1]))) return rc;
+                            grad_out, (const float *)T.z, ga, sums_of(nlayers - 1))) return rc;
     }
     float *gcur = ga, *gnext = gb;                      // dy of the current layer (dense case) / of the layer below
     // The coordinate gradients, from layer 1's dz_1 = s G - c0 - c1 Z (cf == nullptr: G is dz_1 itself; sel: the pooled
@@ -3095,10 +3133,10 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
     SideStream sd;
     if (int rc = sd.init(st, o.side_stream == PN2_OPT_ON)) return rc;
     hipStream_t ss = sd.get();
-    for (int l = nlayers - 1; l >= 0; --l) {
+    for (int l = nlayers - 1; l >= lo; --l) {
         const pn2_bn_layer &L = layers[l];
         float *coef = reinterpret_cast<float *>(base + pl.coef[l]);
-        if (!folded[l])
+        if (!folded[l] && !fr)
             if (int rc = launch(tl_bn_backward_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
                                 reinterpret_cast<const double *>(base + pl.stats[l]), nparts[l], L.cout, (double)rows, L.gamma,
                                 (const float *)L.save, L.grad_gamma, L.grad_beta, coef, L.grad_accumulate)) return rc;
@@ -3142,7 +3180,7 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                 w.dy_out = gnext;
                 w.dy_zprev = D.z; w.dy_ea = D.save + 2 * D.cout; w.dy_ec = D.save + 3 * D.cout;
                 w.dy_bias = rowc;
-                w.dy_stats = reinterpret_cast<double *>(base + pl.stats[l - 1]);
+                w.dy_stats = sums_of(l - 1);
                 w.dy_nt_store = o.nt == PN2_OPT_OFF ? 0 : o.nt == PN2_OPT_ON ? 1 : (size_t)rows * K * sizeof(float) >= ((size_t)128 << 20);
                 if (int rc = launch_wgrad(w, wz[l], reinterpret_cast<float *>(base + pl.partial2), L, st, sf)) return rc;
                 long long blocks = ((long long)K * NF + 255) / 256;
@@ -3161,8 +3199,9 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                 // z_{l-1}: one launch for both where the pair has a kernel (tl_pair_kernel)
                 const TopSShape ts = top_s_shape(rows, pool_rows, K, NF, o);
                 double *s64 = ts.ok ? reinterpret_cast<double *>(base + pl.tops64) : nullptr;
+                const bool wg = !skip[l];                          // (frozen statistics: a layer without parameter gradients)
                 if (int rc = sd.fork()) return rc;                 // the weight gradient's kernels beside the data gradient below
-                if (ts.ok) {
+                if (ts.ok && wg) {
                     TlTopS q;
                     memset(&q, 0, sizeof(q));
                     q.groups = rows / pool_rows; q.ns = pool_rows; q.K = K; q.NF = NF;
@@ -3196,21 +3235,24 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                 p.emode = E_MASK;
                 p.out = gnext;
                 p.zprev = D.z; p.ea = D.save + 2 * D.cout; p.ec = D.save + 3 * D.cout;
-                p.stats = reinterpret_cast<double *>(base + pl.stats[l - 1]);
+                p.stats = sums_of(l - 1);
+                p.nostats = (fr && !p.stats) ? 1 : 0;
                 fold_below(p, l);
                 int np = 0, rc = kNoPair;
-                if (pair_wanted(rows, o)) rc = launch_pair(A_FILL, p, g, w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st, o, &np, sf);
+                if (wg && pair_wanted(rows, o)) rc = launch_pair(A_FILL, p, g, w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st, o, &np, sf);
                 if (rc == kNoPair) {
-                    if ((rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, ss, sf))) return rc;
+                    if (wg && (rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, ss, sf))) return rc;
                     rc = launch_gemm(A_FILL, p, g, st, o, &np);
                 }
                 if (rc) return rc;
                 nparts[l - 1] = np;
                 long long blocks = ((long long)K * NF + 255) / 256;
                 if (blocks > 4096) blocks = 4096;
-                if (int rc2 = launch(tl_top_wgrad_fix_kernel, dim3((unsigned)blocks), dim3(256), 0, ss, (const double *)sf, ldw, K, NF,
-                                     tfw * 32, tfw * 32 + tiles(K) * 32, L.weight, L.w_stride_k, L.w_stride_n, (const float *)coef,
-                                     (const float *)nullptr, L.grad_weight, (const double *)s64, L.grad_accumulate)) return rc2;
+                if (wg) {
+                    if (int rc2 = launch(tl_top_wgrad_fix_kernel, dim3((unsigned)blocks), dim3(256), 0, ss, (const double *)sf, ldw, K, NF,
+                                         tfw * 32, tfw * 32 + tiles(K) * 32, L.weight, L.w_stride_k, L.w_stride_n, (const float *)coef,
+                                         (const float *)nullptr, L.grad_weight, (const double *)s64, L.grad_accumulate)) return rc2;
+                }
             }
             float *tmp = gcur; gcur = gnext; gnext = tmp;
             continue;
@@ -3228,7 +3270,8 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                 break;
             }
             // ... in one pass over dy_1 and z_1
-            if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, reinterpret_cast<float *>(base + pl.l1part), false, st)) return rc;
+            if (!skip[l])
+                if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, reinterpret_cast<float *>(base + pl.l1part), false, st)) return rc;
             if (want_xyz)
                 if (int rc = xyz_pass(gcur, L.z, coef, nullptr, nullptr)) return rc;
             break;
@@ -3300,11 +3343,24 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
             const long long bn = (long long)gd.b * gd.n;
             float *S = reinterpret_cast<float *>(base + pl.l1p), *part = reinterpret_cast<float *>(base + pl.l1part);
             float *ident = reinterpret_cast<float *>(base + pl.l1coef);
-            if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, part, true, st)) return rc;
+            if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, part, true, st, !skip[l])) return rc;
             if (int rc = pn2_group_point_grad_seg(gd.b, gd.n, L.cout, gd.m, gd.nsample, gcur, group->idx, S, base + pl.l1seg,
                                                   reproducible, stream)) return rc;
             if (want_xyz)                                         // (gcur holds dz_1 now)
                 if (int rc = xyz_pass(gcur, nullptr, nullptr, nullptr, S)) return rc;
+            if (skip[l]) {                                        // frozen statistics, no dW_1 wanted: the data gradient alone
+                if (!want_dx) break;
+                const GemmShape g = gemm_shape(bn, L.cout, gt.cfeat, o);
+                TlGemm p;
+                memset(&p, 0, sizeof(p));
+                p.rows = bn;
+                p.A = S;
+                p.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
+                p.emode = E_PLAIN;
+                p.out = grad_points; p.out_pitch = gt.cfeat; p.col0 = 0; p.col1 = gt.cfeat;
+                if (int rc = launch_gemm(A_PLAIN, p, g, st, o)) return rc;
+                break;
+            }
             if (!ident_written)
                 if (int rc = launch(tl_identity_coef_kernel, dim3((unsigned)((3 * L.cout + 127) / 128)), dim3(128), 0, st, L.cout, ident)) return rc;
             {
@@ -3367,14 +3423,14 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                     const pn2_bn_layer &D = layers[l - 1];
                     w.dy_out = gnext;
                     w.dy_zprev = D.z; w.dy_ea = D.save + 2 * D.cout; w.dy_ec = D.save + 3 * D.cout;
-                    w.dy_stats = reinterpret_cast<double *>(base + pl.stats[l - 1]);
+                    w.dy_stats = sums_of(l - 1);
                 } else {
                     w.dy_out = grad_x;
                 }
                 w.dy_nt_store = o.nt == PN2_OPT_OFF ? 0 : o.nt == PN2_OPT_ON ? 1 : (size_t)rows * L.cin * sizeof(float) >= ((size_t)128 << 20);
                 w.xr_off = (int)fz[l].xr_off;
                 // (not with the coordinate gradients: g_r needs dy_1 row by row, so it is written and tl_l1_dz_kernel's pass runs)
-                if (l == 1 && coords_only && gd.cfeat == 0 && !pooled_top && !want_xyz) {            // (a pooled two-layer stack keeps the pass over dy_1: its dz comes from the routed gradient)
+                if (l == 1 && coords_only && gd.cfeat == 0 && !pooled_top && !want_xyz && !skip[0]) {            // (a pooled two-layer stack keeps the pass over dy_1: its dz comes from the routed gradient)
                     // the layer below takes the three centred coordinates: dy_1 is wanted only as x^T dy_1 (TlWgrad::l1x) -- never
                     // written, and tl_l1_dz_kernel's pass over (dy_1, z_1) is replaced by nine moments of x
                     const pn2_bn_layer &D = layers[0];
@@ -3397,8 +3453,9 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                 continue;
             }
             const WgradShape ws_ = wgrad_shape(rows, L.cin, L.cout, w.amode == A_GATHER, cus, o.wgrad_two_per_cu);
-            if (!(l > 0 || want_dx)) {                             // no data gradient below this layer
-                if (int rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st)) return rc;
+            if (!below(l)) {                                       // no data gradient below this layer
+                if (!skip[l])
+                    if (int rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st)) return rc;
             } else {
                 // data gradient: independent of the weight gradient -- ONE launch for both where the pair has a kernel
                 // (tl_pair_kernel), else the weight gradient first (on the helper stream when that is asked for)
@@ -3419,7 +3476,8 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                     p.zprev = D.z;
                     p.ea = D.save + 2 * D.cout;
                     p.ec = D.save + 3 * D.cout;
-                    p.stats = reinterpret_cast<double *>(base + pl.stats[l - 1]);
+                    p.stats = sums_of(l - 1);
+                    p.nostats = (fr && !p.stats) ? 1 : 0;
                     fold_below(p, l);
                 } else {
                     p.emode = E_PLAIN;
@@ -3432,7 +3490,11 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
                 }
                 const int amode = pooled_top ? A_DZ_POOL : A_DZ;
                 int np = 0, rc = kNoPair;
-                if (pair_wanted(rows, o)) rc = launch_pair(amode, p, g, w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st, o, &np);
+                if (skip[l]) {                                      // frozen statistics, no parameter gradient: the data gradient alone
+                    rc = launch_gemm(amode, p, g, st, o, &np);
+                } else if (pair_wanted(rows, o)) {
+                    rc = launch_pair(amode, p, g, w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st, o, &np);
+                }
                 if (rc == kNoPair) {
                     if ((rc = sd.fork())) return rc;               // beside the data-gradient GEMM
                     if ((rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, ss))) return rc;
@@ -3443,6 +3505,16 @@ static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *la
             }
         }
         float *tmp = gcur; gcur = gnext; gnext = tmp;
+    }
+    if (fr) {
+        // the per-channel sums of every layer -> grad_gamma, grad_beta, grad_bias: one launch, behind the last pass (nothing waits for it)
+        FrozenSums fs[8];
+        for (int l = 0; l < nlayers; ++l) {
+            fs[l].skip = skip[l];
+            fs[l].stats = skip[l] ? nullptr : reinterpret_cast<const double *>(base + pl.stats[l]);
+            fs[l].nparts = skip[l] ? 0 : nparts[l];
+        }
+        if (int rc = frozen_launch_grads(nlayers, layers, fs, fr->grad_bias, st)) return rc;
     }
     return sd.join();                                              // everything of this call is ordered before what the caller enqueues next
 }
@@ -3534,6 +3606,32 @@ int tl_xyz_backward(long long rows, int nlayers, const pn2_bn_layer *layers, con
     return tl_train_backward(rows, nlayers, layers, group, nullptr, pool_rows, pooling, out, pooling == 3 || pooling == 0 ? argsel : nullptr,
                              pooling == 3 || pooling == 0 ? zsel : nullptr, nullptr, grad_out, nullptr, grad_feat_rows, grad_points,
                              reproducible, ws, opts, stream, nullptr, grad_xyz, grad_new_xyz);
+}
+}  // namespace pn2
+
+// ---- frozen batch-norm statistics (pn2_mlp_train_*_frozen: entry points, argument checks and kernels in train_mlp_frozen.hip) ----
+namespace pn2 {
+int tl_frozen_forward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
+                      int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
+                      const pn2_train_opts *opts, void *stream)
+{
+    const TlFrozen fr = {nullptr};
+    const bool want_max = pooling == 0 || pooling == 3;
+    return tl_train_forward(rows, nlayers, layers, group, x, pool_rows, pooling, out, want_max ? argsel : nullptr,
+                            want_max ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, ws, opts, stream, nullptr, &fr);
+}
+
+int tl_frozen_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
+                       int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel, const float *pool_w,
+                       const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points, float *grad_xyz,
+                       float *grad_new_xyz, float *const *grad_bias, int reproducible, void *ws, const pn2_train_opts *opts,
+                       void *stream)
+{
+    const TlFrozen fr = {grad_bias};
+    const bool want_max = pooling == 0 || pooling == 3;
+    return tl_train_backward(rows, nlayers, layers, group, x, pool_rows, pooling, out, want_max ? argsel : nullptr,
+                             want_max ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, grad_out, grad_x, grad_feat_rows,
+                             grad_points, reproducible, ws, opts, stream, nullptr, grad_xyz, grad_new_xyz, &fr);
 }
 }  // namespace pn2
 

@@ -171,10 +171,37 @@ class PointnetSAModule(nn.Module):
         # training with an xyz that requires a gradient: take the fused node with its coordinate gradients
         # (train_mlp.sa_mlp_train(..., xyz_grad=True)) instead of the layer-by-layer path. Opt-in.
         self.fused_xyz_grad = False
+        # gradients through a stack whose batch norms are all in eval() (the module in eval(), or in train() with its batch norms
+        # frozen): take the fused node with frozen statistics (train_mlp.sa_mlp_train(..., frozen=True)) instead of the
+        # layer-by-layer path; last_path "fused_frozen". Opt-in.
+        self.fused_frozen_bn = False
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
         self._lvl_buffers = None
+
+    def _frozen_ok(self, xyz, points):
+        """Autograd through a stack whose batch norms all normalise with their running statistics (fused_frozen_bn): something
+        must want a gradient -- an input (xyz only with fused_xyz_grad, as in training) or a parameter of the stack -- and
+        pn2_mlp_train_frozen_supported must cover the level. What the batch-statistics node refuses is refused here too."""
+        if not self.fused_frozen_bn or not self.fused_mlp or not torch.is_grad_enabled() or not xyz.is_cuda:
+            return False
+        want_xyz = xyz.requires_grad
+        if (want_xyz and not self.fused_xyz_grad) or (points is not None and not self.use_xyz):
+            return False
+        if not (want_xyz or (points is not None and points.requires_grad) or any(p.requires_grad for p in self.mlp.net.parameters())):
+            return False
+        b, n, _ = xyz.shape
+        ns = n if self.group_all else self.nsample
+        m = 1 if self.group_all else self.npoint
+        dims = (b, n, m, points.shape[2] if points is not None else 0, not self.group_all) if want_xyz else None
+        return train_mlp.frozen_supported(self.mlp.net, b * m * ns, ns, True, self.pooling, dims)
+
+    def _train_mode(self, xyz, points):
+        """"fused_train" (batch statistics), "fused_frozen" (running statistics, opt-in) or None: which fused autograd node."""
+        if self._train_fused_ok(xyz, points):
+            return "fused_train"
+        return "fused_frozen" if self._frozen_ok(xyz, points) else None
 
     def _level_buffers(self):
         if not self.reuse_buffers:
@@ -264,10 +291,11 @@ class PointnetSAModule(nn.Module):
         gradients: with xyz.requires_grad the centroids are re-gathered differentiably (SAGeometry.new_xyz_for; the fused
         training node is taken then only with fused_xyz_grad, the inference kernels never)."""
         new_xyz, idx = g.new_xyz_for(xyz), g.idx
-        if self._train_fused_ok(xyz, points):
-            self.last_path = "fused_train"
+        mode = self._train_mode(xyz, points)
+        if mode is not None:
+            self.last_path = mode
             out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling,
-                                            xyz_grad=torch.is_grad_enabled() and xyz.requires_grad)
+                                            xyz_grad=torch.is_grad_enabled() and xyz.requires_grad, frozen=mode == "fused_frozen")
             return new_xyz, self._post(out), idx
         if self._fused_ok(xyz, points):
             self.last_path = "fused"
@@ -284,16 +312,20 @@ class PointnetSAModule(nn.Module):
     def forward(self, xyz, points, geometry=None):
         if geometry is not None and not self.group_all:
             return self._forward_on(xyz, points, geometry.wait())
-        if self._train_fused_ok(xyz, points):
+        mode = self._train_mode(xyz, points)
+        if mode is not None:
             # training: the level's geometry in the fused launches, then ONE autograd node for gather + layer stack
-            # (batch-statistics batch norm) + pooling, forward and backward on the matrix cores (train_mlp.py)
-            self.last_path = "fused_train"
+            # (batch-statistics batch norm -- or, "fused_frozen", the running statistics) + pooling, forward and backward on the
+            # matrix cores (train_mlp.py)
+            self.last_path = mode
+            frozen = mode == "fused_frozen"
             want_xyz = torch.is_grad_enabled() and xyz.requires_grad     # (fused_xyz_grad: the node differentiates the coordinates too)
             if self.group_all:
                 b, n, _ = xyz.shape
                 new_xyz = torch.zeros((b, 1, 3), dtype=torch.float32, device=xyz.device)
                 idx = torch.arange(n, dtype=torch.int32, device=xyz.device).reshape(1, 1, n).repeat(b, 1, 1)
-                out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True, self.pooling, xyz_grad=want_xyz)
+                out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True, self.pooling, xyz_grad=want_xyz,
+                                                frozen=frozen)
                 return new_xyz, self._post(out), idx
             if self.knn:
                 fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz)
@@ -302,7 +334,8 @@ class PointnetSAModule(nn.Module):
                 fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
             if want_xyz:                                              # the centroids' path back to xyz: GatherPoint's gradient (:40)
                 new_xyz = mark_fps_ordered(gather_point(xyz, fps_idx))
-            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling, xyz_grad=want_xyz)
+            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling, xyz_grad=want_xyz,
+                                            frozen=frozen)
             return new_xyz, self._post(out), idx
         if self.group_all and self._fused_ok(xyz, points):
             # sample_and_group_all (:59-84) + the layer stack + reduce_max in ONE kernel: new_xyz = origin, the
@@ -376,6 +409,7 @@ class PointnetSAModuleMSG(nn.Module):
         self.mlps = nn.ModuleList([_SharedMLP(feat, widths, bn) for widths in mlp_list])
         self.fused_mlp = True          # eval-mode forward may use the fused MFMA kernel (sa_mlp.py)
         self.fused_xyz_grad = False    # see PointnetSAModule: the fused training node for an xyz that requires a gradient (opt-in)
+        self.fused_frozen_bn = False   # see PointnetSAModule: the fused node with frozen batch-norm statistics (opt-in)
         self.last_path = None
         self._pack_cache = {}
 
@@ -447,15 +481,31 @@ class PointnetSAModuleMSG(nn.Module):
                        for mlp, ns in zip(self.mlps, self.nsample_list))
         return all(train_mlp.stack_supported(mlp.net, rows * ns, ns, True) for mlp, ns in zip(self.mlps, self.nsample_list))
 
+    def _frozen_ok(self, xyz, points):
+        """See PointnetSAModule._frozen_ok: every scale's batch norms in eval(), something wants a gradient."""
+        if not self.fused_frozen_bn or not self.fused_mlp or not torch.is_grad_enabled() or not xyz.is_cuda:
+            return False
+        want_xyz = xyz.requires_grad
+        if (want_xyz and not self.fused_xyz_grad) or (points is not None and not self.use_xyz):
+            return False
+        if not (want_xyz or (points is not None and points.requires_grad) or any(p.requires_grad for p in self.mlps.parameters())):
+            return False
+        b, n, _ = xyz.shape
+        cfeat = points.shape[2] if points is not None else 0
+        return all(train_mlp.frozen_supported(mlp.net, b * self.npoint * ns, ns, True, "max",
+                                              (b, n, self.npoint, cfeat, True) if want_xyz else None)
+                   for mlp, ns in zip(self.mlps, self.nsample_list))
+
     def forward(self, xyz, points, geometry=None):
         g = None if geometry is None else geometry.wait()          # a geometry computed ahead (geometry.py): same results
         if self._fused_ok(xyz, points):
             self.last_path = "fused"
             return self._forward_fused(xyz, points, g)
-        if self._train_fused_ok(xyz, points):
+        mode = "fused_train" if self._train_fused_ok(xyz, points) else "fused_frozen" if self._frozen_ok(xyz, points) else None
+        if mode is not None:
             # training: grouping launches as in inference, then one autograd node per scale (train_mlp.py);
-            # channel order features FIRST (:184)
-            self.last_path = "fused_train"
+            # channel order features FIRST (:184). "fused_frozen": the same with the running statistics (fused_frozen_bn)
+            self.last_path = mode
             want_xyz = torch.is_grad_enabled() and xyz.requires_grad     # (fused_xyz_grad: autograd adds the scales' coordinate gradients)
             if g is None:
                 new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
@@ -463,7 +513,7 @@ class PointnetSAModuleMSG(nn.Module):
                     new_xyz = mark_fps_ordered(gather_point(xyz, fps_idx))
             else:
                 new_xyz, scales = g.new_xyz_for(xyz), [(idx, None) for idx in g.idx]
-            outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False, xyz_grad=want_xyz)[0]
+            outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False, xyz_grad=want_xyz, frozen=mode == "fused_frozen")[0]
                     for mlp, (idx, _) in zip(self.mlps, scales)]
             return new_xyz, torch.cat(outs, dim=2)
         self.last_path = "unfused"
@@ -501,10 +551,21 @@ class PointnetFPModule(nn.Module):
         super().__init__()
         self.mlp = _SharedMLP(c_in, mlp, bn)
         self.fused_mlp = True          # eval-mode forward may use the fused kernel (csrc/fp_mlp.hip)
+        self.fused_frozen_bn = False   # see PointnetSAModule: the fused node with frozen batch-norm statistics (opt-in)
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
         self._lvl_buffers = None
+
+    def _frozen_ok(self, x1, x2, rows):
+        """Autograd through the stack with every batch norm in eval() (fused_frozen_bn): an input (x1 / x2: the tensors the
+        stack's input is made of) or a parameter wants a gradient, and the frozen node covers `rows` plain rows. The level then
+        runs fp_interp_concat + fp_mlp_train(frozen=True) whatever fp_level_preferred says (the one-node form has no frozen mode)."""
+        if not self.fused_frozen_bn or not self.fused_mlp or not torch.is_grad_enabled() or not x2.is_cuda:
+            return False
+        if not (x2.requires_grad or (x1 is not None and x1.requires_grad) or any(p.requires_grad for p in self.mlp.net.parameters())):
+            return False
+        return train_mlp.frozen_supported(self.mlp.net, rows, 0, False)
 
     def _fused_kind(self, points1, points2, npoints):
         """The fused kernel for this call (sa_mlp.fp_kind: cooperative below 16384 unknown points, streamed
@@ -548,6 +609,11 @@ class PointnetFPModule(nn.Module):
                 return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist)     # :212-226 as one node
             x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
             return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1)
+        if use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
+                self._frozen_ok(points1, points2, xyz1.shape[0] * xyz1.shape[1]):
+            self.last_path = "fused_frozen"
+            x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
+            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, frozen=True)
         inv = 1.0 / torch.clamp(dist, min=1e-10)                                # :212
         weight = inv / inv.sum(dim=2, keepdim=True)                             # :213-215
         return self._after_weights(points1, points2, idx, weight)
@@ -579,6 +645,14 @@ class PointnetFPModule(nn.Module):
                 return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist)     # :212-226
             x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
             return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1)
+        if use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
+                self._frozen_ok(points1, points2, xyz1.shape[0] * xyz1.shape[1]):
+            # gradients through batch norms in eval(): the same launches with the running statistics (fused_frozen_bn)
+            self.last_path = "fused_frozen"
+            dist, idx = three_nn(xyz1, xyz2)                                    # :211
+            c1 = points1.shape[2] if points1 is not None else 0
+            x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
+            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, frozen=True)
         idx, weight = three_nn_weights(xyz1, xyz2)                              # :211-215
         return self._after_weights(points1, points2, idx, weight)
 
@@ -591,6 +665,9 @@ class PointnetFPModule(nn.Module):
             # training: the layer stack with batch-statistics batch norm as one autograd node (train_mlp.py)
             self.last_path = "fused_train"
             return train_mlp.fp_mlp_train(self.mlp.net, x)
+        if self._frozen_ok(None, x, x.shape[0] * x.shape[1]):
+            self.last_path = "fused_frozen"
+            return train_mlp.fp_mlp_train(self.mlp.net, x, frozen=True)
         self.last_path = "unfused"
         x = self.mlp(x.permute(0, 2, 1).unsqueeze(2))                           # (b, C, 1, n)
         return x.squeeze(2).permute(0, 2, 1).contiguous()

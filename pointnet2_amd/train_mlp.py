@@ -134,7 +134,7 @@ def stack_supported(net, rows, pool_rows=0, grouped=True):
 class _Level:
     """Non-tensor description of one call (what the autograd node needs besides its differentiable inputs)."""
     __slots__ = ("pairs", "rows", "pool_rows", "xyz", "new_xyz", "idx", "b", "n", "m", "nsample", "xyz_first", "grouped", "pooling",
-                 "xyz_grad")
+                 "xyz_grad", "frozen")
 
 
 # pointnet_sa_module's pooling modes (utils/pointnet_util.py:128-142) -> the library's codes (pn2_mlp_train_forward_pool)
@@ -164,6 +164,42 @@ def xyz_grad_supported(net, rows, ns, pooling, b, n, m, cfeat, has_idx=True):
     arr = (ctypes.c_int * len(widths))(*widths)
     gdims = (ctypes.c_int * 6)(b, n, m, ns, cfeat, 1 if has_idx else 0)
     return bool(_C.lib().pn2_mlp_train_xyz_supported(rows, len(widths) - 1, arr, ns, code, gdims))
+
+
+def frozen_supported(net, rows, pool_rows=0, grouped=True, pooling="max", xyz_dims=None):
+    """The mirror of stack_supported for a stack whose batch norms ALL normalise with their running statistics (`not
+    bn.training`, with track_running_stats): can the frozen-statistics node (pn2_mlp_train_*_frozen; sa_mlp_train /
+    fp_mlp_train with frozen=True) run it on `rows` rows? A mixed stack (some batch norms frozen, some not) is not supported.
+    xyz_dims = (b, n, m, cfeat, has_idx): with the coordinate gradients as well (xyz_grad=True)."""
+    pairs = conv_bn_pairs(net)
+    code = POOLING.get(pooling)
+    if not pairs or len(pairs) > 8 or code is None or rows <= 0 or rows % 32 or rows >= 2 ** 31:
+        return False
+    if grouped and (pool_rows <= 0 or (pool_rows != 16 and pool_rows % 32)):
+        return False
+    if not grouped and (pool_rows or code):
+        return False
+    for conv, bn in pairs:
+        if conv.out_channels % 4 or not bn.affine or bn.training:
+            return False
+        if not bn.track_running_stats or bn.running_mean is None or bn.running_var is None:
+            return False
+        if any(t is not None and t.dtype != torch.float32 for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean,
+                                                                      bn.running_var)):
+            return False
+    if code == 0 and xyz_dims is None:
+        return True                # as stack_supported: the max path needs no query of the library (the entries check their plan)
+    cin = pairs[0][0].in_channels
+    widths = [cin if grouped else (cin + 3) // 4 * 4] + [c.out_channels for c, _ in pairs]   # plain rows: zero-padded (fp_mlp_train)
+    arr = (ctypes.c_int * len(widths))(*widths)
+    gdims = None
+    if xyz_dims is not None:
+        if not grouped or code == 2:
+            return False
+        b, n, m, cfeat, has_idx = xyz_dims
+        gdims = (ctypes.c_int * 6)(b, n, m, pool_rows, cfeat, 1 if has_idx else 0)
+    return bool(_C.lib().pn2_mlp_train_frozen_supported(rows, len(widths) - 1, arr, pool_rows, code, gdims,
+                                                        1 if xyz_dims is not None else 0))
 
 
 def _layer_array(level, weights, biases, gammas, betas, zs, saves, grads=None, update_running=True):
@@ -226,6 +262,14 @@ def _ws_pool(rows, widths, pool_rows, code, backward, dev, gdims=None, opts=None
     arr = (ctypes.c_int * len(widths))(*widths)
     nbytes = _C.lib().pn2_mlp_train_ws_bytes_pool(rows, len(widths) - 1, arr, pool_rows, code, backward, gdims, opts)
     require(nbytes >= 0, "pn2_mlp_train: unsupported stack or pooling")
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+
+
+def _ws_frozen(rows, widths, pool_rows, code, backward, dev, gdims, want_xyz, opts=None):
+    arr = (ctypes.c_int * len(widths))(*widths)
+    nbytes = _C.lib().pn2_mlp_train_ws_bytes_frozen(rows, len(widths) - 1, arr, pool_rows, code, backward, gdims,
+                                                    1 if want_xyz else 0, opts)
+    require(nbytes >= 0, "pn2_mlp_train: unsupported stack or pooling for frozen batch-norm statistics")
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
 
 
@@ -304,7 +348,16 @@ class _TrainMLP(torch.autograd.Function):
             argsel = zsel = None
         arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
         grp = _group_struct(level, x) if level.grouped else None
-        if code:
+        frozen = bool(getattr(level, "frozen", False))
+        if frozen:
+            # running statistics (bn.eval()): read, never written -- no counter either (pn2_mlp_train_forward_frozen)
+            ws = _ws_frozen(rows, widths, level.pool_rows, code, 0, dev, _group_dims(level, x), False, opts)
+            with on_device(dev):
+                _C.check(_C.lib().pn2_mlp_train_forward_frozen(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
+                                                               None if level.grouped else ptr(x), level.pool_rows, code, ptr(out),
+                                                               ptr(argsel) if code in (0, 3) else None, ptr(zsel), ptr(pool_w),
+                                                               ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward_frozen")
+        elif code:
             ws = _ws_pool(rows, widths, level.pool_rows, code, 0, dev, _group_dims(level, x), opts)
             with on_device(dev):
                 _C.check(_C.lib().pn2_mlp_train_forward_pool(rows, n, arr, ctypes.byref(grp), level.pool_rows, code, ptr(out),
@@ -317,7 +370,7 @@ class _TrainMLP(torch.autograd.Function):
                                                            None if level.grouped else ptr(x), level.pool_rows, ptr(out), ptr(argsel),
                                                            ptr(zsel), ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward")
         nbt = [bn.num_batches_tracked for _, bn in level.pairs if bn.track_running_stats and bn.num_batches_tracked is not None]
-        if nbt:
+        if nbt and not frozen:
             torch._foreach_add_(nbt, 1)                        # one launch for the level's counters
         ctx.level, ctx.widths, ctx.code = level, widths, code
         ctx.opts = dict(_OPTS)                              # backward must see the organisation forward ran under
@@ -355,7 +408,34 @@ class _TrainMLP(torch.autograd.Function):
         rows = level.rows
         grad_out = f32(grad_out, "grad_out")
         grads, direct = [], []
+        frozen = bool(getattr(level, "frozen", False))
+        needs, gbias = [], [None] * n          # frozen: which of (weight, bias, gamma, beta) want a gradient; the bias gradients
+        small, soff = None, 0                  # frozen: ONE buffer for the per-channel gradients (gamma, beta, bias) of every layer
         for l, (conv, bn) in enumerate(level.pairs):
+            if frozen:
+                # NULL slots for a layer none of whose parameters wants a gradient: the library then runs no weight-gradient
+                # pass for it. Otherwise the three tensors the kernels write are all given (scratch for an unwanted one).
+                need = [bool(ctx.needs_input_grad[4 + 4 * l + k]) for k in range(4)]
+                needs.append(need)
+                if not any(need):
+                    direct.append(False)
+                    grads.append((None, None, None))
+                    continue
+                srcs = ((conv.weight, weights[l]), (conv.bias, biases[l]), (bn.weight, gammas[l]), (bn.bias, betas[l]))
+                slots = [_grad_slot(p, like) if (_ACCUMULATE[0] and nd) else None for (p, like), nd in zip(srcs, need)]
+                d = _ACCUMULATE[0] and all(s is not None for s, nd in zip(slots, need) if nd)     # direct: every WANTED slot exists
+                direct.append(d)
+                if small is None:              # (a level is bound by the host's enqueue rate: one allocation, not three per layer)
+                    small = torch.empty((3 * sum(widths[1:]),), dtype=torch.float32, device=dev)
+                w = widths[l + 1]
+                vec = [small[soff + k * w:soff + (k + 1) * w] for k in range(3)]
+                soff += 3 * w
+                # (a direct layer's UNWANTED slot is scratch the kernels add into and nobody reads: never returned)
+                grads.append((slots[0] if (d and need[0]) else torch.empty_like(weights[l]),
+                              slots[2] if (d and need[2]) else vec[0], slots[3] if (d and need[3]) else vec[1]))
+                if need[1]:
+                    gbias[l] = slots[1] if d else vec[2]
+                continue
             slots = (_grad_slot(conv.weight, weights[l]), _grad_slot(bn.weight, gammas[l]), _grad_slot(bn.bias, betas[l])) \
                 if _ACCUMULATE[0] else (None, None, None)
             direct.append(all(t is not None for t in slots))
@@ -380,18 +460,31 @@ class _TrainMLP(torch.autograd.Function):
             grad_xyz = torch.empty((level.b, level.n, 3), dtype=torch.float32, device=dev)
             if level.new_xyz is not None:
                 grad_new_xyz = torch.empty((level.b, level.m, 3), dtype=torch.float32, device=dev)
+        if frozen:
+            ws = _ws_frozen(rows, widths, level.pool_rows, code, 1, dev, gdims, want_xyz, opts)
+        elif want_xyz:
             ws = _ws_xyz(rows, widths, level.pool_rows, code, dev, gdims, opts)
         else:
             ws = _ws_pool(rows, widths, level.pool_rows, code, 1, dev, gdims, opts) if code else \
                 _ws(rows, widths, level.pool_rows, 1, dev, gdims, opts)
         if _KEEP_WS[0]:
             _KEEP_WS[1] = (ws, rows, widths, level.pool_rows)
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
+        # (frozen: the library wants the running statistics named in both directions; it only ever reads them)
+        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=frozen)
         for l in range(n):
             arr[l].grad_accumulate = 1 if direct[l] else 0
         grp = _group_struct(level, x) if level.grouped else None
         with on_device(dev):
-            if want_xyz:
+            if frozen:
+                gb_arr = (ctypes.c_void_p * n)(*[ptr(t) for t in gbias])
+                _C.check(_C.lib().pn2_mlp_train_backward_frozen(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
+                                                                None if level.grouped else ptr(x), level.pool_rows, code, ptr(out),
+                                                                ptr(argsel) if code in (0, 3) else None, ptr(zsel), ptr(pool_w),
+                                                                ptr(grad_out), ptr(grad_x), ptr(grad_rows), ptr(grad_pts),
+                                                                ptr(grad_xyz), ptr(grad_new_xyz), gb_arr,
+                                                                1 if is_deterministic() else 0, ptr(ws), opts, stream_ptr(dev)),
+                         "mlp_train_backward_frozen")
+            elif want_xyz:
                 _C.check(_C.lib().pn2_mlp_train_backward_xyz(rows, n, arr, ctypes.byref(grp), level.pool_rows, code, ptr(out),
                                                              ptr(argsel) if code in (0, 3) else None, ptr(zsel), None,
                                                              ptr(grad_out), ptr(grad_rows), ptr(grad_pts), ptr(grad_xyz),
@@ -436,7 +529,14 @@ class _TrainMLP(torch.autograd.Function):
         zero = None
         off = 0
         for l in range(n):
-            if direct[l]:                                  # added into .grad by the kernels (zero for the bias: nothing to add)
+            if frozen:                                     # the conv bias takes a real gradient under frozen statistics
+                if direct[l] or not any(needs[l]):
+                    result += [None, None, None, None]
+                else:
+                    nd = needs[l]
+                    result += [grads[l][0] if nd[0] else None, gbias[l], grads[l][1] if nd[2] else None,
+                               grads[l][2] if nd[3] else None]
+            elif direct[l]:                                # added into .grad by the kernels (zero for the bias: nothing to add)
                 result += [None, None, None, None]
             else:
                 if zero is None and biases[l] is not None:
@@ -454,7 +554,7 @@ def _params(pairs):
     return out
 
 
-def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", xyz_grad=False):
+def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", xyz_grad=False, frozen=False):
     """Training-mode shared MLP + pooling of one SA level / one MSG scale.
     net: nn.Sequential of (Conv2d 1x1, BatchNorm2d, ReLU) triples; xyz (b,n,3); new_xyz (b,m,3) or None and idx
     (b,m,nsample) i32 or None (both None: the group_all level); points (b,n,c) or None.
@@ -464,6 +564,9 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
     grouped_xyz - new_xyz, :44-46; pn2_mlp_train_backward_xyz) -- every pooling but weighted_avg. The gradient of new_xyz is
     returned for new_xyz itself: pass new_xyz = gather_point(xyz, fps_idx) and autograd adds the centroids' path back to xyz.
     Default False: the coordinates are constants of the node (no gradient flows to them), outputs and saved tensors the same bits.
+    frozen: the stack's batch norms are all in eval() and normalise with their RUNNING statistics (pn2_mlp_train_*_frozen,
+    frozen_supported): the statistics and num_batches_tracked are not touched, the conv biases take a real gradient, and
+    parameters that need no gradient get none (a layer none of whose parameters needs one runs no weight-gradient pass).
     -> (b, m, cout) pooled features (differentiable w.r.t. points and the parameters), argsel (b, m, cout) i32 -- the max's
     selection; None for avg and weighted_avg."""
     require(pooling in POOLING, "unknown pooling %r" % (pooling,))
@@ -498,13 +601,19 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
         same_device(xyz, points)
     cin = 3 + (points.shape[2] if points is not None else 0)
     require(pairs[0][0].in_channels == cin, "the first layer expects %d channels, got %d" % (pairs[0][0].in_channels, cin))
-    require(stack_supported(net, lv.rows, lv.pool_rows, True), "unsupported stack for the fused training path")
-    require(lv.pooling == 0 or pool_supported(net, lv.rows, lv.pool_rows, pooling),
-            "unsupported stack for the fused training path with pooling %r" % (pooling,))
+    lv.frozen = bool(frozen)
+    if lv.frozen:
+        require(frozen_supported(net, lv.rows, lv.pool_rows, True, pooling,
+                                 (b, n, lv.m, points.shape[2] if points is not None else 0, idx is not None) if xyz_grad else None),
+                "unsupported stack for the fused training path with frozen batch-norm statistics (pooling %r)" % (pooling,))
+    else:
+        require(stack_supported(net, lv.rows, lv.pool_rows, True), "unsupported stack for the fused training path")
+        require(lv.pooling == 0 or pool_supported(net, lv.rows, lv.pool_rows, pooling),
+                "unsupported stack for the fused training path with pooling %r" % (pooling,))
     same_device(xyz, pairs[0][0].weight)
     lv.xyz_grad = bool(xyz_grad)
     if lv.xyz_grad:
-        require(xyz_grad_supported(net, lv.rows, lv.pool_rows, pooling, b, n, lv.m, points.shape[2] if points is not None else 0,
+        require(lv.frozen or xyz_grad_supported(net, lv.rows, lv.pool_rows, pooling, b, n, lv.m, points.shape[2] if points is not None else 0,
                                    idx is not None),
                 "the fused training path has no coordinate gradients for this level (pooling %r)" % (pooling,))
         out, argsel = _TrainMLP.apply(lv, points, lv.xyz, lv.new_xyz, *_params(pairs))
@@ -515,10 +624,11 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
     return out.view(b, lv.m, -1), argsel.view(b, lv.m, -1)
 
 
-def fp_mlp_train(net, x, cin=None):
+def fp_mlp_train(net, x, cin=None, frozen=False):
     """Training-mode shared MLP of one FP level on plain rows: x (b, n, cin) -> (b, n, cout).
     cin: the first layer's input width when x already carries zero columns up to a multiple of 4 behind it
-    (tf_interpolate.fp_interp_concat writes them); default: x's own width (padded here if odd)."""
+    (tf_interpolate.fp_interp_concat writes them); default: x's own width (padded here if odd).
+    frozen: the batch norms normalise with their running statistics (see sa_mlp_train)."""
     pairs = conv_bn_pairs(net)
     require(pairs is not None, "fp_mlp_train expects Conv 1x1 + BatchNorm + ReLU triples")
     x = f32(x, "x")
@@ -535,7 +645,9 @@ def fp_mlp_train(net, x, cin=None):
     lv.xyz = lv.new_xyz = lv.idx = None
     lv.b, lv.n, lv.m, lv.nsample = b, n, 0, 0
     lv.rows, lv.pool_rows, lv.pooling = b * n, 0, 0
-    require(stack_supported(net, lv.rows, 0, False), "unsupported stack for the fused training path")
+    lv.frozen = bool(frozen)
+    require(frozen_supported(net, lv.rows, 0, False) if lv.frozen else stack_supported(net, lv.rows, 0, False),
+            "unsupported stack for the fused training path")
     require(pairs[0][0].in_channels == c, "the first layer expects %d channels, got %d" % (pairs[0][0].in_channels, c))
     params = _params(pairs)
     x = x.reshape(b * n, x.shape[2])
