@@ -251,11 +251,13 @@ _REF_SYMS = {
         "farthestpointsamplingLauncher": "_Z29farthestpointsamplingLauncheriiiPKfPfPi",
         "gatherpointLauncher": "_Z19gatherpointLauncheriiiPKfPKiPf",
         "probsampleLauncher": "_Z18probsampleLauncheriiiPKfS0_PfPi",
+        "scatteraddpointLauncher": "_Z23scatteraddpointLauncheriiiPKfPKiPf",
     }),
     "grouping_gpu": ("libref_grouping_gpu.so", {
         "queryBallPointLauncher": "_Z22queryBallPointLauncheriiifiPKfS0_PiS1_",
         "groupPointLauncher": "_Z18groupPointLauncheriiiiiPKfPKiPf",
         "selectionSortLauncher": "_Z21selectionSortLauncheriiiiPKfPiPf",
+        "groupPointGradLauncher": "_Z22groupPointGradLauncheriiiiiPKfPKiPf",
     }),
 }
 _ref_libs = {}

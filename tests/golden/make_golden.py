@@ -2,7 +2,8 @@
 
 Run in the build container only (needs /root/reference and `make -C oracle ref`):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py          (every fixture)
+    python tests/golden/make_golden.py fps      (fps_literal.npz only: needs the oracle, not the reference)
 
 Each fixture stores seeded inputs and the outputs of the reference's own CPU
 functions compiled unmodified from the reference tree (oracle/_ref/libref_*.so):
@@ -24,8 +25,9 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import oracle as O  # noqa: E402
+from fps_cases import FPS_LITERAL_CASES, crc32_of  # noqa: E402
 from pointnet2_amd import synthetic as S  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
@@ -86,23 +88,25 @@ def main():
         os.close(devnull)
     np.savez_compressed(os.path.join(OUT, "selection_sort_ref.npz"), dist=dist, k=np.int32(3), outi=outi, out=out)
 
-    # ---- FPS: literal kernel emulation (see module docstring)
-    cases = {}
-    for name, xyz, m in [
-        ("d1", S.sphere_clouds(2, 1024, 31), 256),
-        ("dup", S.duplicated_clouds(2, 700, 32), 300),
-        ("drop", S.dropout_clouds(2, 1024, 33), 200),
-        ("same", S.identical_clouds(1, 600, 34), 40),
-        ("lattice", S.lattice_clouds(2, 1500, 35), 400),
-        ("small", S.uniform_clouds(2, 37, 36), 37),
-    ]:
-        cases[name + "_xyz"] = xyz
-        cases[name + "_idx"] = O.farthest_point_sample(m, xyz, literal=True)
-    np.savez_compressed(os.path.join(OUT, "fps_literal.npz"), **cases)
+    fps_literal()
     live_crosscheck()
     for f in sorted(os.listdir(OUT)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(OUT, f)))
+
+
+def fps_literal():
+    """fps_literal.npz: the literal kernel emulation (see module docstring) on every case of tests/fps_cases.py. The first
+    fixture's six cases keep their coordinates; the others store the indices and a CRC32 of the regenerated input."""
+    cases = {}
+    for name, make, m, stores_xyz in FPS_LITERAL_CASES:
+        xyz = np.ascontiguousarray(make(), dtype=np.float32)
+        if stores_xyz:
+            cases[name + "_xyz"] = xyz
+        else:
+            cases[name + "_crc"] = crc32_of(xyz)
+        cases[name + "_idx"] = O.farthest_point_sample(m, xyz, literal=True)
+    np.savez_compressed(os.path.join(OUT, "fps_literal.npz"), **cases)
 
 
 def live_crosscheck():
@@ -127,4 +131,8 @@ def live_crosscheck():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["fps"]:
+        fps_literal()
+        print("fps_literal.npz", os.path.getsize(os.path.join(OUT, "fps_literal.npz")))
+    else:
+        main()

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from pointnet2_amd import synthetic as S
+from fps_cases import FPS_LITERAL_CASES, FPS_LITERAL_NAMES, load_case
 
 
 def _load(golden_dir, name):
@@ -58,11 +59,17 @@ def test_selection_sort_known_answer(oracle, golden_dir):
 
 
 def test_fps_matches_literal_golden(oracle, golden_dir):
+    """The oracle's restatement against the stored indices of the literal emulator, on every case of tests/fps_cases.py;
+    all cases run, the failing ones are named together."""
     g = _load(golden_dir, "fps_literal.npz")
-    for case in ("d1", "dup", "drop", "same", "lattice", "small"):
-        xyz, want = g[case + "_xyz"], g[case + "_idx"]
+    assert FPS_LITERAL_NAMES[:6] == ["d1", "dup", "drop", "same", "lattice", "small"]
+    bad = []
+    for case in FPS_LITERAL_NAMES:
+        xyz, want = load_case(g, case)
         got = oracle.farthest_point_sample(want.shape[1], xyz)
-        assert np.array_equal(got, want), case
+        if not np.array_equal(got, want):
+            bad.append((case, tuple(np.argwhere(got != want)[0])))
+    assert not bad, "oracle != literal emulator, (case, first differing (cloud, sample)): %s" % bad
 
 
 # ------------------------------------------------- cross-checks against the reference's functions
@@ -102,6 +109,13 @@ def test_fps_restatement_equals_literal_on_adversarial(oracle):
         a = oracle.farthest_point_sample(m, xyz)
         b = oracle.farthest_point_sample(m, xyz, literal=True)
         assert np.array_equal(a, b)
+    # the shared case table, both functions live (the stored indices are test_fps_matches_literal_golden's business)
+    bad = []
+    for name, make, m, _ in FPS_LITERAL_CASES:
+        xyz = np.ascontiguousarray(make(), dtype=np.float32)
+        if not np.array_equal(oracle.farthest_point_sample(m, xyz), oracle.farthest_point_sample(m, xyz, literal=True)):
+            bad.append(name)
+    assert not bad, bad
 
 
 def test_fps_tie_rule_differs_from_lowest_index(oracle):

@@ -272,11 +272,13 @@ def test_fps_gather_fused(cuda, oracle):
 
 def test_fps_golden(cuda, golden_dir):
     import pointnet2_amd as P
+    from fps_cases import FPS_LITERAL_NAMES, load_case
     g = _load(golden_dir, "fps_literal.npz")
-    for case in ("d1", "dup", "drop", "same", "lattice", "small"):
-        want = g[case + "_idx"]
-        got = host(P.farthest_point_sample(want.shape[1], dev(g[case + "_xyz"], cuda)))
-        assert np.array_equal(got, want), case
+    assert FPS_LITERAL_NAMES[:6] == ["d1", "dup", "drop", "same", "lattice", "small"]
+    for case in FPS_LITERAL_NAMES:
+        xyz, want = load_case(g, case)
+        got = host(P.farthest_point_sample(want.shape[1], dev(xyz, cuda)))
+        assert np.array_equal(got, want), "%s: first mismatch at %s" % (case, np.argwhere(got != want)[:3])
 
 
 # ----------------------------------------------------------------- gather_point
