@@ -33,14 +33,17 @@
 //     1 ulp) of its candidate lanes (an LDS atomic maximum on the fp32 bit patterns: the values are >= 0; issued as a plain
 //     ds_max_u32 -- hipcc turns atomicMax into a readlane loop over the active lanes). One barrier, the only one of the batch.
 //   * PICK (picker). Lane i takes candidate i (key from the list, x, y, z, k from the mirror). Per sample, hand-scheduled (the
-//     asm block below): the winner lane alone (exec = one lane) stores its (x, y, z, k) row and then the new count to LDS and
-//     leaves the contest; three v_readlane of its coordinates; the reference's distance (tf_sampling_g.cu:141-144) from the
+//     asm block below: 33 instructions, no pad, ~273 cycles at 4096 rank slots against 291 for the 40 before --
+//     profiles/fps_picker/README.md): the winner lane alone (exec = one lane) stores its (x, y, z, k) row and then the new count
+//     to LDS, hands its coordinates to scalar registers (three v_readfirstlane inside that window) and leaves the contest; the
+//     reference's distance (tf_sampling_g.cu:141-144) from the
 //     sample to the other candidates, nine vector instructions; and, interleaved with those, the 32-bit wave ladder
 //     (v_max_i32 with the DPP operand folded in) over the values as they were BEFORE the update -- values only fall, so a lane
 //     that still holds that maximum afterwards is the arg-max if it is the only one (99 % of the samples); otherwise the exact
 //     arg-max (value ladder, 64-bit keys among equal values, the pruned tier's ladder). A sample is accepted while its value
 //     bits are >= the bound; the first sample of a batch always is: the list holds every updater wave's best lane, so its
-//     maximum is the global one.
+//     maximum is the global one. The loop counts nothing: a list has at most 64 valid lanes, so it ends by the bound exit; only a
+//     batch that could pass the end of the output row (fewer than 64 samples left) runs the compiler's counted form.
 //   * APPLY (updaters, behind the picker). A wave polls the count, takes up to 64 / GW new samples at a time -- lane l tests
 //     sample l / GW against the box of the wave's group l % GW: one distance-to-box computation for 64 (sample, group) pairs --
 //     and updates the touched groups, group by group (packed fp32, as in the pruned tier; no key work: keys are only needed at
@@ -164,6 +167,16 @@ __device__ unsigned long long g_bt_stats[16];
 #endif
 #ifndef PN2_BT_ASM_LOOP
 #define PN2_BT_ASM_LOOP 1
+#endif
+// lab switches of the hand-scheduled sample loop (each cut measured alone: profiles/fps_picker/README.md)
+#ifndef PN2_BT_RFL
+#define PN2_BT_RFL 1                 // the winner's coordinates by v_readfirstlane while exec is its lane (0: s_ff1 + three v_readlane)
+#endif
+#ifndef PN2_BT_NOCTR
+#define PN2_BT_NOCTR 1               // no sample counter in the loop: the bound exit ends a list (0: s_add / s_cmp / s_cbranch per sample)
+#endif
+#ifndef PN2_BT_FILL
+#define PN2_BT_FILL 1                // the add of na in the ladder's last wait state, the two pads no rule asks for dropped (0: three s_nop)
 #endif
 #ifndef PN2_BT_G0
 #define PN2_BT_G0 0.10f               // initial 1 - theta / (last sample value)
@@ -299,19 +312,99 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             argmax();                                                            // the batch's first sample: always (the global arg-max)
             const int amax = min(m - j, kBtCand);
             unsigned raddr = ring_base, na = 1u;
+            // The compiler's form of the sample loop. It is the whole loop where PN2_BT_ASM_LOOP is 0, and the loop of the batches
+            // that can reach the end of the output row (PN2_BT_NOCTR below): the only form that counts its samples.
+            auto pick_counted = [&]() __attribute__((always_inline)) {
+                for (;;) {
+                    // the winner lane alone stores its row and then the new count: two LDS writes of one wave execute in order, so a
+                    // reader that sees the count sees the row (no wait in between, none behind). It also leaves the contest (-1.0f).
+                    asm volatile("s_mov_b64 exec, %1\n\t"
+                                 "ds_write_b128 %2, %3\n\t"
+                                 "ds_write_b32 %4, %5\n\t"
+                                 "v_mov_b32 %0, 0xbf800000\n\t"
+                                 "s_mov_b64 exec, -1"
+                                 : "+v"(cval) : "s"(eq), "v"(raddr), "v"(cand), "v"(count_addr), "v"(na) : "memory");
+                    const int wl = (int)__builtin_ctzll(eq);
+                    raddr += 16u; na += 1u;
+                    a = __builtin_amdgcn_readfirstlane(a + 1);                   // scalar loop control
+                    vlastb = bh;
+                    if (a >= amax) break;
+                    // SPECULATION: the maximum of the values as they are BEFORE this sample's update is computed in the shadow of the
+                    // update. Values only fall: a lane that still holds that maximum afterwards is the arg-max -- if it is the only one.
+                    // (A sample of value 0 ends the batch by itself: nothing is above the bound afterwards.)
+                    const int ms = __builtin_amdgcn_readlane(bt_wave_max_i32_lane63(cval), 63);
+                    const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand.x), wl));
+                    const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand.y), wl));
+                    const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand.z), wl));
+                    const float d = sqdist(cand.x, cand.y, cand.z, sx, sy, sz);  // tf_sampling_g.cu:141-143
+                    cval = __float_as_int(vmin_f32(d, __int_as_float(cval)));    // :144
+                    if (ms < boundb) break;                                      // nothing above the bound is left, whatever the update did
+                    eq = __ballot(cval == ms);
+                    bh = ms;
+                    if (__popcll(eq) != 1) {
+                        PN2_BT_STAT(12, 1);
+                        argmax();
+                        if (bh < boundb) break;
+                    }
+                }
+            };
 #if PN2_BT_ASM_LOOP
-            // The sample loop, hand-scheduled (the compiler's version of the same loop -- #else below -- takes three taken
+            // The sample loop, hand-scheduled (the compiler's version of the same loop -- pick_counted above -- takes three taken
             // branches and six more scalar moves per sample; on a lone wave every instruction is an issue slot of ~8 cycles):
             //   publish: the winner lane alone (exec = eq) stores its row and then the new count -- two LDS writes of one wave
-            //     execute in order, so a reader that sees the count sees the row; no wait in between, none behind -- and leaves
-            //     the contest (-1.0f);
+            //     execute in order, so a reader that sees the count sees the row; no wait in between, none behind --, hands its
+            //     coordinates to the scalar registers (PN2_BT_RFL: v_readfirstlane reads the one active lane; no lane number, no
+            //     v_readlane that waits for one) and leaves the contest (-1.0f);
             //   SPECULATION: the maximum of the values as they are BEFORE this sample's update is computed in the shadow of the
             //     update (the DPP steps need two independent instructions between them anyway). Values only fall: a lane that
             //     still holds that maximum afterwards is the arg-max -- if it is the only one. A sample of value 0 ends the batch by
             //     itself: nothing is above the bound afterwards.
+            //   NO SAMPLE COUNTER (PN2_BT_NOCTR): a list has at most 64 valid lanes and every taken lane is -1.0f, so after the last
+            //     of them the ladder's maximum is 0 (lanes without a DPP source read 0) or negative -- below the bound, which is >= 1
+            //     as an integer (second-best bits + 1) -- and the loop leaves by the bound exit. The count is read back from na
+            //     behind the loop. Only the end of the output row needs a count inside the loop: a batch with fewer than 64
+            //     samples left to write (the last one or two of a cloud) runs pick_counted instead.
+            // Wait states (inline asm gets none from the compiler; the rules are the ones hipcc pads its own code for on gfx950):
+            //   a VALU write of a VGPR -> a DPP read of it: 2 (between two ladder steps: two instructions of the distance, in
+            //     front of the last step the adds of raddr and na -- PN2_BT_FILL; the winner's -1.0f is written four ahead);
+            //   a VALU write of a VGPR -> v_readlane / v_readfirstlane of it: 1 (v_min_f32 stands between the ladder and ms);
+            //   v_readlane / v_readfirstlane writes an SGPR -> a VALU reads it: 2 (s_cmp + s_cbranch between ms and the v_cmp;
+            //     the sample's coordinates are read four or more instructions after they are written); a scalar read needs none;
+            //   exec is written by scalar moves only (a VALU write of exec would cost the DPP steps 5).
             // reason: 0 = the batch is full / the cloud is done, 1 = nothing above the bound is left, 2 = the speculative maximum
             // is gone or not unique (the exact arg-max below decides, then the loop resumes).
+#if PN2_BT_RFL
+#define PN2_BT_A_WINNER_IN  "v_readfirstlane_b32 %[sx], %[cx]\n\tv_readfirstlane_b32 %[sy], %[cy]\n\tv_readfirstlane_b32 %[sz], %[cz]\n\t"
+#define PN2_BT_A_LANE       ""
+#define PN2_BT_A_SXY        ""
+#define PN2_BT_A_SZ         ""
+#else
+#define PN2_BT_A_WINNER_IN  ""
+#define PN2_BT_A_LANE       "s_ff1_i32_b64 %[wl], %[eq]\n\t"
+#define PN2_BT_A_SXY        "v_readlane_b32 %[sx], %[cx], %[wl]\n\tv_readlane_b32 %[sy], %[cy], %[wl]\n\t"
+#define PN2_BT_A_SZ         "v_readlane_b32 %[sz], %[cz], %[wl]\n\t"
+#endif
+#if PN2_BT_NOCTR
+#define PN2_BT_A_COUNT      ""
+#define PN2_BT_A_FULL       ""
+#else
+#define PN2_BT_A_COUNT      "s_add_i32 %[a], %[a], 1\n\t"
+#define PN2_BT_A_FULL       "s_cmp_ge_i32 %[a], %[amax]\n\ts_cbranch_scc1 2f\n\t"
+#endif
+#if PN2_BT_FILL
+#define PN2_BT_A_ADDS_EARLY ""
+#define PN2_BT_A_PAD_DPP    "v_add_u32 %[raddr], 16, %[raddr]\n\tv_add_u32 %[na], 1, %[na]\n\t"   /* the two wait states in front of the last ladder step */
+#define PN2_BT_A_PAD        ""
+#else
+#define PN2_BT_A_ADDS_EARLY "v_add_u32 %[raddr], 16, %[raddr]\n\tv_add_u32 %[na], 1, %[na]\n\t"
+#define PN2_BT_A_PAD_DPP    "s_nop 1\n\t"
+#define PN2_BT_A_PAD        "s_nop 0\n\t"
+#endif
             const float cx = cand.x, cy = cand.y, cz = cand.z;
+#if PN2_BT_NOCTR
+            if (amax < kBtCand) pick_counted();
+            else
+#endif
             for (;;) {
                 int reason, t_wl, t_sx, t_sy, t_sz, t_ms, t_cnt;
                 int v_t;
@@ -324,36 +417,34 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                     "s_mov_b64 exec, %[eq]\n\t"
                     "ds_write_b128 %[raddr], %[cand]\n\t"
                     "ds_write_b32 %[caddr], %[na]\n\t"
-                    "v_mov_b32 %[cval], 0xbf800000\n\t"
+                    "v_mov_b32 %[cval], 0xbf800000\n\t"           // four instructions ahead of the ladder's first step
+                    PN2_BT_A_WINNER_IN
                     "s_mov_b64 exec, -1\n\t"
-                    "s_ff1_i32_b64 %[wl], %[eq]\n\t"
-                    "s_add_i32 %[a], %[a], 1\n\t"
-                    "v_add_u32 %[raddr], 16, %[raddr]\n\t"
-                    "v_add_u32 %[na], 1, %[na]\n\t"
-                    "s_cmp_ge_i32 %[a], %[amax]\n\t"
-                    "s_cbranch_scc1 2f\n\t"
-                    "v_readlane_b32 %[sx], %[cx], %[wl]\n\t"
-                    "v_readlane_b32 %[sy], %[cy], %[wl]\n\t"
+                    PN2_BT_A_LANE
+                    PN2_BT_A_COUNT
+                    PN2_BT_A_ADDS_EARLY
+                    PN2_BT_A_FULL
+                    PN2_BT_A_SXY
                     "v_max_i32_dpp %[t], %[cval], %[cval] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                    "v_readlane_b32 %[sz], %[cz], %[wl]\n\t"
+                    PN2_BT_A_SZ
                     "v_subrev_f32 %[dx], %[sx], %[cx]\n\t"
-                    "v_max_i32_dpp %[t], %[t], %[t] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
                     "v_subrev_f32 %[dy], %[sy], %[cy]\n\t"
+                    "v_max_i32_dpp %[t], %[t], %[t] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
                     "v_subrev_f32 %[dz], %[sz], %[cz]\n\t"
-                    "v_max_i32_dpp %[t], %[t], %[t] row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
                     "v_mul_f32 %[dx], %[dx], %[dx]\n\t"
+                    "v_max_i32_dpp %[t], %[t], %[t] row_half_mirror row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
                     "v_mul_f32 %[dy], %[dy], %[dy]\n\t"
-                    "v_max_i32_dpp %[t], %[t], %[t] row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
                     "v_mul_f32 %[dz], %[dz], %[dz]\n\t"
+                    "v_max_i32_dpp %[t], %[t], %[t] row_mirror row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
                     "v_add_f32 %[dx], %[dx], %[dy]\n\t"
-                    "v_max_i32_dpp %[t], %[t], %[t] row_bcast:15 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
                     "v_add_f32 %[dx], %[dx], %[dz]\n\t"
-                    "s_nop 0\n\t"
+                    "v_max_i32_dpp %[t], %[t], %[t] row_bcast:15 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                    PN2_BT_A_PAD_DPP
                     "v_max_i32_dpp %[t], %[t], %[t] row_bcast:31 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                    "v_min_f32 %[cval], %[dx], %[cval]\n\t"
-                    "s_nop 0\n\t"
+                    "v_min_f32 %[cval], %[dx], %[cval]\n\t"       // the wait state between the ladder's last step and the v_readlane
+                    PN2_BT_A_PAD
                     "v_readlane_b32 %[ms], %[t], 63\n\t"
-                    "s_nop 0\n\t"
+                    PN2_BT_A_PAD
                     "s_cmp_lt_i32 %[ms], %[bound]\n\t"
                     "s_cbranch_scc1 3f\n\t"
                     "v_cmp_eq_u32_e64 %[eq], %[ms], %[cval]\n\t"
@@ -362,13 +453,18 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                     "s_cbranch_scc1 0b\n\t"
                     "s_mov_b32 %[reason], 2\n\t"
                     "s_branch 4f\n\t"
+#if !PN2_BT_NOCTR
                     "2:\n\t"
                     "s_mov_b32 %[reason], 0\n\t"
                     "s_branch 4f\n\t"
+#endif
                     "3:\n\t"
                     "s_mov_b32 %[reason], 1\n\t"
                     "4:"
-                    : [cval] "+v"(cval), [raddr] "+v"(raddr), [na] "+v"(na), [eq] "+s"(eq), [a] "+s"(a), [bh] "+s"(bh),
+                    : [cval] "+v"(cval), [raddr] "+v"(raddr), [na] "+v"(na), [eq] "+s"(eq), [bh] "+s"(bh),
+#if !PN2_BT_NOCTR
+                      [a] "+s"(a),
+#endif
                       [reason] "=&s"(reason), [wl] "=&s"(t_wl), [sx] "=&s"(t_sx), [sy] "=&s"(t_sy), [sz] "=&s"(t_sz), [ms] "=&s"(t_ms), [cnt] "=&s"(t_cnt),
                       [t] "=&v"(v_t), [dx] "=&v"(v_dx), [dy] "=&v"(v_dy), [dz] "=&v"(v_dz)
                     : [cand] "v"(cand), [caddr] "v"(count_addr), [cx] "v"(cx), [cy] "v"(cy), [cz] "v"(cz), [amax] "s"(amax), [bound] "s"(boundb)
@@ -379,39 +475,20 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 argmax();
                 if (bh < boundb) break;
             }
+#if PN2_BT_NOCTR
+            a = __builtin_amdgcn_readfirstlane((int)na) - 1;                     // na is the count the next sample would publish
+#endif
+#undef PN2_BT_A_WINNER_IN
+#undef PN2_BT_A_LANE
+#undef PN2_BT_A_SXY
+#undef PN2_BT_A_SZ
+#undef PN2_BT_A_COUNT
+#undef PN2_BT_A_FULL
+#undef PN2_BT_A_ADDS_EARLY
+#undef PN2_BT_A_PAD_DPP
+#undef PN2_BT_A_PAD
 #else
-            for (;;) {
-                // the winner lane alone stores its row and then the new count: two LDS writes of one wave execute in order, so a
-                // reader that sees the count sees the row (no wait in between, none behind). It also leaves the contest (-1.0f).
-                asm volatile("s_mov_b64 exec, %1\n\t"
-                             "ds_write_b128 %2, %3\n\t"
-                             "ds_write_b32 %4, %5\n\t"
-                             "v_mov_b32 %0, 0xbf800000\n\t"
-                             "s_mov_b64 exec, -1"
-                             : "+v"(cval) : "s"(eq), "v"(raddr), "v"(cand), "v"(count_addr), "v"(na) : "memory");
-                const int wl = (int)__builtin_ctzll(eq);
-                raddr += 16u; na += 1u;
-                a = __builtin_amdgcn_readfirstlane(a + 1);                       // scalar loop control
-                vlastb = bh;
-                if (a >= amax) break;
-                // SPECULATION: the maximum of the values as they are BEFORE this sample's update is computed in the shadow of the
-                // update. Values only fall: a lane that still holds that maximum afterwards is the arg-max -- if it is the only one.
-                // (A sample of value 0 ends the batch by itself: nothing is above the bound afterwards.)
-                const int ms = __builtin_amdgcn_readlane(bt_wave_max_i32_lane63(cval), 63);
-                const float sx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand.x), wl));
-                const float sy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand.y), wl));
-                const float sz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand.z), wl));
-                const float d = sqdist(cand.x, cand.y, cand.z, sx, sy, sz);      // tf_sampling_g.cu:141-143
-                cval = __float_as_int(vmin_f32(d, __int_as_float(cval)));        // :144
-                if (ms < boundb) break;                                          // nothing above the bound is left, whatever the update did
-                eq = __ballot(cval == ms);
-                bh = ms;
-                if (__popcll(eq) != 1) {
-                    PN2_BT_STAT(12, 1);
-                    argmax();
-                    if (bh < boundb) break;
-                }
-            }
+            pick_counted();
 #endif
             if (vlastb == 0) { fill = true; fill_k = __builtin_amdgcn_readlane(__float_as_int(cand.w), (int)__builtin_ctzll(eq)); }   // every running distance is 0 from here on
             const long long q3 = PN2_BT_CLOCK();
