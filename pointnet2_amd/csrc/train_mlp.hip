@@ -29,7 +29,7 @@
 // and a two-stage reduction sums the waves' slabs (fp64 in the last stage) in a fixed order: the result does not
 // depend on timing.
 #include "sa_mlp_common.h"
-#include "train_mlp_frozen.h"     // TlFrozen, FrozenSums, the per-channel launches of the frozen-statistics node
+#include "train_mlp_internal.h"   // TlCall, FpL1, GroupDims; the launches of train_mlp_fp / _xyz / _frozen.hip
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1849,7 +1849,7 @@ static GemmShape gemm_shape(long long rows, int K, int N, const Opts &o)
     return g;
 }
 
-struct WgradShape { int tus, tts, uslabs, tslabs, tpw, upw, two; long long gridx, nw, nchunks; size_t e, lds, lds_dy, partial_bytes, partial2_bytes; };
+struct WgradShape { int tus, tts, uslabs, tslabs, tpw, upw, two; long long gridx, nw, nchunks; size_t e, lds, lds_dy, partial_bytes; };
 
 static WgradShape wgrad_shape(long long rows, int KI, int NO, bool gather = false, int cus = 256, int two_opt = PN2_OPT_AUTO)
 {
@@ -1893,7 +1893,6 @@ static WgradShape wgrad_shape(long long rows, int KI, int NO, bool gather = fals
     w.lds_dy = 0;
     w.nchunks = w.nw > 32 ? (w.nw + 31) / 32 : 0;
     w.partial_bytes = slabs * w.nw * w.e * sizeof(float);
-    w.partial2_bytes = slabs * (size_t)w.nchunks * w.e * sizeof(float);
     return w;
 }
 
@@ -1934,9 +1933,8 @@ struct TlPlan {
     size_t pool;                // forward: pmax, pamax (2 arrays of parts_total x cout_L)
     size_t gq;                  // backward, pooled: (groups, cout_L)
     size_t ga, gb;              // backward: dy ping-pong (rows, max width)
-    size_t partial, partial2;   // backward: weight-gradient partial sums
-    size_t partial_cap;         // ... and the bytes planned for `partial` (launch_wgrad / launch_pair refuse a larger shape; `partial2` is the
-                                // second-stage buffer of the former two-launch reduction: still planned, no longer written)
+    size_t partial;             // backward: weight-gradient partial sums
+    size_t partial_cap;         // ... and the bytes planned for them (launch_wgrad / launch_pair refuse a larger shape)
     size_t topw, topsf;         // backward, pooled top layer without z_L: stacked fp32 weight + constant row; [S | G | sumh] fp64
     size_t tops_part, tops_part2, tops64;   // ... its routed part on the vector units: partials (two stages), S (K, C_L) fp64
     size_t l1p;                 // layer 1 per point: forward P (b n, cout_1); backward S (b n, cout_1)
@@ -1957,46 +1955,6 @@ static bool top_stored(long long rows, int nlayers, const int *widths, int pool_
 }
 static inline int top_cols(int kin, int cl) { return tiles(cl) * 32 + tiles(kin) * 32 + 32; }
 
-// group dims as the C ABI passes them to the workspace query: b, n, m, nsample, cfeat, has_idx
-struct GroupDims { int b, n, m, nsample, cfeat, has_idx; };
-
-// An FP level whose layer 1 runs once per KNOWN point (pn2_mlp_train_*_fp; its kernels and entry points: train_mlp_fp.hip)
-struct FpL1 {
-    int b, n, m, c2, c1;
-    int c2p, c1p;                    // the widths rounded up to a multiple of 4 (the GEMMs read rows 16 bytes at a time)
-    long long rows, bm, mp;          // b n unknown points; b m known points, and that rounded up to a multiple of 32
-    const float *points2, *points1;
-    const int *idx;
-    const float *dist;
-    float *weight_out;               // forward: the interpolation weights (b,n,3)
-    const float *weight;             // backward: the same
-    float *grad_points2, *grad_points1;
-    bool pad2() const { return mp != bm || c2p != c2; }     // points2 enters as a zero-padded copy (mp, c2p)
-    bool pad1() const { return c1 > 0 && c1p != c1; }       // points1 as a zero-padded copy (rows, c1p)
-    bool gstage2() const { return mp != bm; }               // grad_points2 is written to the workspace (mp rows), then copied
-};
-
-static FpL1 fp_l1(const pn2_fp_src *s)
-{
-    FpL1 f;
-    memset(&f, 0, sizeof(f));
-    f.b = s->b; f.n = s->n; f.m = s->m; f.c2 = s->c2; f.c1 = s->c1;
-    f.c2p = (s->c2 + 3) / 4 * 4; f.c1p = (s->c1 + 3) / 4 * 4;
-    f.rows = (long long)s->b * s->n; f.bm = (long long)s->b * s->m; f.mp = (f.bm + 31) / 32 * 32;
-    f.points2 = s->points2; f.points1 = s->points1; f.idx = s->idx; f.dist = s->dist;
-    return f;
-}
-
-// ---- defined in train_mlp_fp.hip ----
-int fp_launch_pad(const float *src, long long rows_in, int c, long long rows_out, int cp, float *dst, hipStream_t st);
-int fp_launch_l1_forward(long long rows, int n, int m, int C, const int *idx, const float *dist, float *weight, const float *Q,
-                         float *z, bool add, double *stats, int max_parts, hipStream_t st, int *nparts);
-int fp_launch_l1_dz(long long rows, int C, const float *z, float *g, const float *coef, hipStream_t st);
-
-// ---- defined in train_mlp_xyz.hip: the coordinate gradients (pn2_mlp_train_backward_xyz) ----
-int xyz_launch_rows(long long rows, int C, const float *G, const float *Z, const float *coef, const int *argsel, int group_rows,
-                    const float *wx, long long sk, long long sn, float *out, hipStream_t st);
-int xyz_launch_centroids(long long groups, int ns, const float *g, float *out, hipStream_t st);
 // the workspace behind TlPlan::total when the coordinate gradients are wanted: g (rows, 3) of a level with idx, then the scratch
 // of its segmented reduction (not where layer 1 runs per point: grad_xyz comes from S there)
 struct XyzPlan { size_t g, seg, total; };
@@ -2113,25 +2071,22 @@ static bool tl_plan(long long rows, int nlayers, const int *widths, int pool_row
         if (pool_rows) { pl.gq = off; off = align_up(off + (size_t)(rows / pool_rows) * cl * 4); }
         pl.ga = off; off = align_up(off + (size_t)rows * maxw * 4);
         pl.gb = off; off = align_up(off + (size_t)rows * maxw * 4);
-        size_t p1 = 0, p2 = 0;
+        size_t p1 = 0;
         const bool ztop = !top_stored(rows, nlayers, widths, pool_rows, o);
         for (int l = 0; l < nlayers; ++l) {
             const bool zt = ztop && l == nlayers - 1;
             for (int gat = 0; gat < (l == 0 ? 2 : 1); ++gat) {      // layer 1 may be a gathered input (other slab shape)
                 const WgradShape w = wgrad_plan_shape(rows, widths[l], zt ? top_cols(widths[l], widths[l + 1]) : widths[l + 1], gat != 0, o);
                 if (w.partial_bytes > p1) p1 = w.partial_bytes;
-                if (w.partial2_bytes > p2) p2 = w.partial2_bytes;
             }
             if (zt) {                                              // without the routed tiles (tl_top_s_kernel takes them)
                 const WgradShape w = wgrad_plan_shape(rows, widths[l], top_cols(widths[l], 0), false, o);
                 if (w.partial_bytes > p1) p1 = w.partial_bytes;
-                if (w.partial2_bytes > p2) p2 = w.partial2_bytes;
             }
         }
         if (l1_per_point(nlayers, widths, gd, o)) {                  // dW1f = points^T S over the b n points
             const WgradShape w = wgrad_plan_shape((long long)gd->b * gd->n, gd->cfeat, widths[1], false, o);
             if (w.partial_bytes > p1) p1 = w.partial_bytes;
-            if (w.partial2_bytes > p2) p2 = w.partial2_bytes;
         }
         if (fp) {                                                    // dW1a over the known points, dW1b over the rows
             for (int h = 0; h < 2; ++h) {
@@ -2139,11 +2094,9 @@ static bool tl_plan(long long rows, int nlayers, const int *widths, int pool_row
                 const WgradShape w = h == 0 ? wgrad_plan_shape(fp->mp, fp->c2p, widths[1], false, o)
                                             : wgrad_plan_shape(rows, fp->c1p, widths[1], false, o);
                 if (w.partial_bytes > p1) p1 = w.partial_bytes;
-                if (w.partial2_bytes > p2) p2 = w.partial2_bytes;
             }
         }
         pl.partial = off; off = align_up(off + p1);
-        pl.partial2 = off; off = align_up(off + p2);
         pl.partial_cap = p1;
         if (ztop) {
             const int kin = widths[nlayers - 1];
@@ -2344,10 +2297,9 @@ static int launch_wgrad_tpw(const TlWgrad &p, const WgradShape &w, dim3 grid, hi
                                 : launch_wgrad_kern<TPW, false, D_DZ>(p, w, grid, st);
 }
 
-static int launch_wgrad_reduce(const TlWgrad &p, const WgradShape &w, float *partial2, const pn2_bn_layer &L, hipStream_t st, double *plain);
+static int launch_wgrad_reduce(const TlWgrad &p, const WgradShape &w, const pn2_bn_layer &L, hipStream_t st, double *plain);
 
-static int launch_wgrad(TlWgrad &p, const WgradShape &w, float *partial2, const pn2_bn_layer &L, hipStream_t st,
-                        double *plain = nullptr)
+static int launch_wgrad(TlWgrad &p, const WgradShape &w, const pn2_bn_layer &L, hipStream_t st, double *plain = nullptr)
 {
     if (p.partial_cap && w.partial_bytes > p.partial_cap) return PN2_E_ARG;   // never write past the planned buffer
     p.tus = w.tus; p.tts = w.tts; p.tslabs = w.tslabs;
@@ -2374,13 +2326,12 @@ static int launch_wgrad(TlWgrad &p, const WgradShape &w, float *partial2, const 
                     h[wv * 6 + 3] / nb, h[wv * 6 + 4] / nb, h[wv * 6 + 5] / nb);
     }
 #endif
-    return launch_wgrad_reduce(p, w, partial2, L, st, plain);
+    return launch_wgrad_reduce(p, w, L, st, plain);
 }
 
 // the sum of the workgroups' slabs -> the caller's weight gradient (or `plain`, fp64, for the pooled top layer's fix-up)
-static int launch_wgrad_reduce(const TlWgrad &p, const WgradShape &w, float *partial2, const pn2_bn_layer &L, hipStream_t st, double *plain)
+static int launch_wgrad_reduce(const TlWgrad &p, const WgradShape &w, const pn2_bn_layer &L, hipStream_t st, double *plain)
 {
-    (void)partial2;                                                // (the second stage's buffer of the two-launch reduction)
     const long long total = (long long)w.uslabs * w.tslabs * (long long)w.e;     // floats of the slab layout
     long long blocks = (total + 31) / 32;
     if (blocks > 4096) blocks = 4096;
@@ -2393,8 +2344,8 @@ static int launch_wgrad_reduce(const TlWgrad &p, const WgradShape &w, float *par
 // other. The table = the pairs the size rules produce at the levels of the four reference networks below 0.5 M rows
 // (scripts/train_pairs.py lists them); a level of other widths simply takes the two launches.
 constexpr int kNoPair = -12345;
-static int launch_pair(int amode, TlGemm &pg, const GemmShape &g, TlWgrad &pw, const WgradShape &w, float *partial2, const pn2_bn_layer &L,
-                       hipStream_t st, const Opts &o, int *nparts, double *plain = nullptr)
+static int launch_pair(int amode, TlGemm &pg, const GemmShape &g, TlWgrad &pw, const WgradShape &w, const pn2_bn_layer &L, hipStream_t st,
+                       const Opts &o, int *nparts, double *plain = nullptr)
 {
     if (pw.dy_w) return kNoPair;
     if (pw.partial_cap && w.partial_bytes > pw.partial_cap) return PN2_E_ARG;   // never write past the planned buffer
@@ -2413,7 +2364,7 @@ static int launch_pair(int amode, TlGemm &pg, const GemmShape &g, TlWgrad &pw, c
         const unsigned total = ga.x * ga.y + (unsigned)w.gridx * (unsigned)(w.uslabs * w.tslabs);                        \
         if (int rc = launch(kern, dim3(total), dim3(kTlThreads), lds, st, pg, pw, ga.x, ga.y, (unsigned)w.gridx)) return rc; \
         if (nparts) *nparts = (int)ga.x;                                                                                 \
-        return launch_wgrad_reduce(pw, w, partial2, L, st, plain);                                                       \
+        return launch_wgrad_reduce(pw, w, L, st, plain);                                                                 \
     }
     PN2_PAIR(A_DZ, 1, D_DZ, 1, 1)
     PN2_PAIR(A_DZ, 1, D_DZ, 1, 2)
@@ -2594,7 +2545,7 @@ extern "C" long long pn2_mlp_train_ws_bytes_ex(long long rows, int nlayers, cons
 {
     pn2::TlPlan pl;
     pn2::GroupDims gd;
-    if (group_dims) gd = {group_dims[0], group_dims[1], group_dims[2], group_dims[3], group_dims[4], group_dims[5]};
+    if (group_dims) gd = pn2::group_dims_of(group_dims);
     if (!widths || !pn2::tl_plan(rows, nlayers, widths, pool_rows, backward, pl, group_dims ? &gd : nullptr, pn2::opts_of(opts))) return -1;
     return (long long)pl.total;
 }
@@ -2609,7 +2560,7 @@ extern "C" long long pn2_mlp_train_ws_bytes(long long rows, int nlayers, const i
 extern "C" int pn2_mlp_train_layer1_per_point_ex(int nlayers, const int *widths, const int *group_dims, const pn2_train_opts *opts)
 {
     if (!widths || !group_dims || nlayers < 1 || nlayers > 8) return 0;
-    const pn2::GroupDims gd = {group_dims[0], group_dims[1], group_dims[2], group_dims[3], group_dims[4], group_dims[5]};
+    const pn2::GroupDims gd = pn2::group_dims_of(group_dims);
     return pn2::l1_per_point(nlayers, widths, &gd, pn2::opts_of(opts)) ? 1 : 0;
 }
 extern "C" int pn2_mlp_train_layer1_per_point(int nlayers, const int *widths, const int *group_dims)
@@ -2691,6 +2642,7 @@ static int launch_l1_dz(long long rows, const GroupDims &gd, const pn2_group_src
 }
 }  // namespace pn2
 
+
 namespace pn2 {
 // Per-channel finalisations inside the launches that produce their sums (TlFin): OPT-IN. Measured (rocprofv3 per-dispatch
 // traces, profiles/r04/fold_finalize_experiment.txt): the folded pass is 5-7 us longer on a level of 4,096 rows (sem_seg SA4:
@@ -2719,6 +2671,882 @@ static TlFin fin_backward(const pn2_bn_layer &L, long long rows, double *stats, 
     f.accumulate = L.grad_accumulate;
     return f;
 }
+
+// 0 ok, else the PN2_E_* code the pooling entries return before anything is launched
+int tl_pool_args(int pool_rows, int pooling, bool grouped)
+{
+    if (pooling < 0 || pooling > 3) return PN2_E_ARG;
+    if (pooling == 0) return PN2_OK;
+    if (!grouped) return PN2_E_NULL;
+    return pool_rows > 0 ? PN2_OK : PN2_E_ARG;
+}
+
+// Which of argsel / zsel / pool_w a pooling mode uses: the max's selection for max and max_and_avg (the extrema of the GEMM
+// epilogue, E_POOL), the weights for weighted_avg. The others never reach a check or a kernel, whatever the caller passed.
+static TlCall tl_pool_buffers(TlCall c)
+{
+    if (c.pooling != 0 && c.pooling != 3) { c.argsel = nullptr; c.zsel = nullptr; }
+    if (c.pooling != 2) c.pool_w = nullptr;
+    return c;
+}
+
+// a GEMM over the dense rows A against the operand tiles at `wpacked`
+static TlGemm dense_gemm(long long rows, const float *A, const void *wpacked)
+{
+    TlGemm p;
+    memset(&p, 0, sizeof(p));
+    p.rows = rows;
+    p.A = A;
+    p.wpacked = reinterpret_cast<const u32x4 *>(wpacked);
+    return p;
+}
+
+// ... that stores its product and sums no moments (forward: the per-point products of layer 1)
+static TlGemm store_gemm(long long rows, const float *A, const void *wpacked, float *out)
+{
+    TlGemm p = dense_gemm(rows, A, wpacked);
+    p.emode = E_STORE;
+    p.out = out;
+    return p;
+}
+
+// the epilogue of a data gradient that leaves the stack: `cols` plain columns, no mask, no sums
+static void plain_out(TlGemm &p, float *out, int cols)
+{
+    p.emode = E_PLAIN;
+    p.out = out; p.out_pitch = cols; p.col0 = 0; p.col1 = cols;
+}
+
+// What both directions of a call work from: the call (its pooling buffers normalised), the rules' overrides, the workspace
+struct TlRun {
+    const TlCall c;
+    const Opts o;
+    const FpL1 *const fp;            // the FP level with layer 1 per known point, or nullptr
+    char *const base;
+    const hipStream_t st;
+    int widths[9];
+    TlPlan pl;
+    GroupDims gd;
+    bool fold = false;               // a layer's per-channel finalisation inside the pass that sums for it (TlFin)
+
+    explicit TlRun(const TlCall &call)
+        : c(tl_pool_buffers(call)), o(opts_of(call.opts)), fp(c.has_fp ? &c.fp : nullptr), base(static_cast<char *>(call.ws)),
+          st(as_stream(call.stream)) {}
+    TlRun(const TlRun &) = delete;
+    TlRun &operator=(const TlRun &) = delete;
+
+    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(base + off); }
+    unsigned *tickets() const { return at<unsigned>(pl.tickets); }
+    double *stats(int l) const { return at<double>(pl.stats[l]); }
+    bool want_max() const { return c.pooling == 0 || c.pooling == 3; }
+
+    // the checks both directions make first, in this order
+    int check_inputs()
+    {
+        if (!layers_ok(c.rows, c.nlayers, c.layers, c.group, widths, fp)) return PN2_E_ARG;
+        if (c.frozen && fp) return PN2_E_ARG;                     // (the FP node with layer 1 per known point has no frozen form)
+        return PN2_OK;
+    }
+    bool pool_buffers_missing(int pool_rows) const
+    {
+        return (pool_rows && want_max() && (!c.argsel || !c.zsel)) || (c.pooling == 2 && !c.pool_w);
+    }
+    bool plan(int pool_rows, int backward)
+    {
+        if (c.group) gd = group_dims(c.group);
+        return tl_plan(c.rows, c.nlayers, widths, pool_rows, backward, pl, c.group ? &gd : nullptr, o, fp);
+    }
+
+    // The FP node's inputs as the GEMMs read them: zero-padded copies of points2 / points1 where their shapes need one
+    int fp_padded_inputs(const float *&p2, const float *&p1) const
+    {
+        p2 = fp->points2; p1 = fp->points1;
+        if (fp->pad2()) {
+            float *d = at<float>(pl.fp2);
+            if (int rc = fp_launch_pad(fp->points2, fp->bm, fp->c2, fp->mp, fp->c2p, d, st)) return rc;
+            p2 = d;
+        }
+        if (fp->pad1()) {
+            float *d = at<float>(pl.fp1);
+            if (int rc = fp_launch_pad(fp->points1, c.rows, fp->c1, c.rows, fp->c1p, d, st)) return rc;
+            p1 = d;
+        }
+        return PN2_OK;
+    }
+};
+
+// ---- forward ----------------------------------------------------------------------------------------------------------------
+struct Fwd : TlRun {
+    using TlRun::TlRun;
+    bool per_point = false, coords_only = false, keep_top = true;
+
+    float *out() const { return const_cast<float *>(c.out); }     // (TlCall: forward writes these)
+
+    // every layer's weights -> operand tiles, one launch
+    int pack_weights()
+    {
+        TlPackJobs jobs;
+        memset(&jobs, 0, sizeof(jobs));
+        int nj = 0;
+        for (int l = 0; l < c.nlayers; ++l) {
+            const pn2_bn_layer &L = c.layers[l];
+            if (l == 0 && coords_only) continue;                 // no matrix-core pass at all
+            if (l == 0 && fp) {                                   // W1a for the known points' GEMM, W1b for the one over the rows
+                add_pack_job(jobs, nj, L.weight, L.w_stride_k, L.w_stride_n, gemm_shape(fp->mp, fp->c2, L.cout, o), base + pl.pack[l]);
+                if (fp->c1 > 0)
+                    add_pack_job(jobs, nj, L.weight + (long long)fp->c2 * L.w_stride_k, L.w_stride_k, L.w_stride_n,
+                                 gemm_shape(c.rows, fp->c1, L.cout, o), base + pl.fpw);
+                continue;
+            }
+            if (l == 0 && per_point) {                           // only the feature rows of W_1: P = points . W1f
+                const TlGather gt = make_gather(c.group);
+                add_pack_job(jobs, nj, L.weight + gt.feat_off * L.w_stride_k, L.w_stride_k, L.w_stride_n,
+                             gemm_shape((long long)gd.b * gd.n, gt.cfeat, L.cout, o), base + pl.pack[l]);
+            } else {
+                add_pack_job(jobs, nj, L.weight, L.w_stride_k, L.w_stride_n, gemm_shape(c.rows, L.cin, L.cout, o), base + pl.pack[l]);
+            }
+        }
+        fold = fold_wanted(o) && nj > 0 && !c.frozen;             // (the pack launch zeroes the tickets; frozen: nothing to fold)
+        if (fold) jobs.tickets = tickets();
+        return launch_pack_jobs(jobs, nj, st);
+    }
+
+    // a layer's batch moments: summed by its pass, or not at all under frozen statistics
+    double *moments(int l) const { return c.frozen ? nullptr : stats(l); }
+
+    // the np partial rows of layer l's moments -> its (mean, invstd, a, c) and running statistics; nothing under frozen ones
+    int finalize_moments(int l, int np) const
+    {
+        if (c.frozen) return PN2_OK;
+        const pn2_bn_layer &L = c.layers[l];
+        return launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st, (const double *)stats(l), np, L.cout,
+                      (double)c.rows, L.gamma, L.beta, L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias,
+                      L.running_var_biased);
+    }
+
+    // an unpooled top layer: out = relu(a z_L + c)
+    int apply(const pn2_bn_layer &L) const
+    {
+        const long long total4 = c.rows * L.cout / 4;
+        long long blocks = (total4 + 255) / 256;
+        if (blocks > 8192) blocks = 8192;
+        return launch(tl_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, total4, L.cout, (const float *)L.z, (const float *)L.save,
+                      out());
+    }
+
+    // layer 1 of an FP level once per KNOWN point (train_mlp_fp.hip): Q = points2 W1a over the b m known points,
+    // z_1 = points1 W1b over the rows, then one pass adds the interpolated rows of Q and sums the batch moments
+    int layer1_fp()
+    {
+        const pn2_bn_layer &L = c.layers[0];
+        float *Q = at<float>(pl.l1p);
+        const float *p2, *p1;
+        if (int rc = fp_padded_inputs(p2, p1)) return rc;
+        TlGemm q = store_gemm(fp->mp, p2, base + pl.pack[0], Q);  // no moments: Q is not z_1
+        if (int rc = launch_gemm(A_PLAIN, q, gemm_shape(fp->mp, fp->c2p, L.cout, o), st, o)) return rc;
+        if (fp->c1 > 0) {
+            TlGemm q1 = store_gemm(c.rows, p1, base + pl.fpw, L.z);
+            if (int rc = launch_gemm(A_PLAIN, q1, gemm_shape(c.rows, fp->c1p, L.cout, o), st, o)) return rc;
+        }
+        int np = 0;
+        if (int rc = fp_launch_l1_forward(c.rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z, fp->c1 > 0,
+                                          stats(0), kMaxParts, st, &np)) return rc;
+        if (int rc = finalize_moments(0, np)) return rc;
+        return c.nlayers == 1 ? apply(L) : PN2_OK;
+    }
+
+    // layer 1 once per point (tl_l1_forward_kernel): P = points . W1f over the b n points, then one pass over the rows
+    int layer1_per_point()
+    {
+        const pn2_bn_layer &L = c.layers[0];
+        const TlGather gt = make_gather(c.group);
+        const long long bn = (long long)gd.b * gd.n;
+        float *P = at<float>(pl.l1p);
+        TlGemm q = store_gemm(bn, c.group->points, base + pl.pack[0], P);
+        if (int rc = launch_gemm(A_PLAIN, q, gemm_shape(bn, gt.cfeat, L.cout, o), st, o)) return rc;
+        int np = 0;
+        if (int rc = launch_l1_forward(c.rows, gd, c.group, L, P, moments(0), st, &np)) return rc;
+        return finalize_moments(0, np);
+    }
+
+    // a level without features: z_1 = b + (xyz - c) W1 in one pass on the vector units (tl_l1_forward_kernel, no P)
+    int layer1_coords_only()
+    {
+        int np = 0;
+        if (int rc = launch_l1_forward(c.rows, gd, c.group, c.layers[0], nullptr, moments(0), st, &np)) return rc;
+        return finalize_moments(0, np);
+    }
+
+    // a layer as one GEMM over the rows, with the pooling of the top layer behind it
+    int generic_layer(int l)
+    {
+        const pn2_bn_layer &L = c.layers[l];
+        const long long rows = c.rows;
+        const int pool_rows = c.pool_rows, pooling = c.pooling;
+        const GemmShape g = gemm_shape(rows, L.cin, L.cout, o);
+        const bool last = l == c.nlayers - 1;
+        TlGemm p;
+        memset(&p, 0, sizeof(p));
+        p.rows = rows;
+        int amode;
+        if (l == 0 && c.group) { amode = A_GATHER; p.g = make_gather(c.group); }
+        else if (l == 0) { amode = A_PLAIN; p.A = c.x; }
+        else { const pn2_bn_layer &D = c.layers[l - 1]; amode = A_RELU; p.A = D.z; p.p0 = D.save + 2 * D.cout; p.p1 = D.save + 3 * D.cout; }
+        p.wpacked = at<const u32x4>(pl.pack[l]);
+        p.bias = nullptr;                                        // see the comment above the layer loop
+        p.emode = (last && pool_rows && want_max()) ? E_POOL : E_STORE;
+        p.out = (last && !keep_top) ? nullptr : L.z;              // the pooled top layer of a large level is never written
+        p.stats = moments(l);
+        p.nostats = c.frozen ? 1 : 0;                             // the GEMM's compile-time "no statistics" variant
+        if (p.emode == E_POOL) {
+            const long long parts = rows / (pool_rows == 16 ? 16 : 32);
+            float *pp = at<float>(pl.pool);
+            p.pmax = pp;
+            p.pamax = reinterpret_cast<int *>(pp + parts * L.cout);
+            p.pool_gamma = L.gamma;
+            p.prow = pool_rows == 16 ? 16 : 32;
+        }
+        int nparts = 0;
+        if (fold) p.fin = fin_forward(L, rows, p.stats, tickets() + l);
+        if (int rc = launch_gemm(amode, p, g, st, o, &nparts)) return rc;
+        if (!fold)
+            if (int rc = finalize_moments(l, nparts)) return rc;
+        // max_and_avg: the max half as pooling 0 computes it, into the workspace behind the plan; the average kernel places it
+        float *maxv = pooling == 3 ? at<float>(pl.total) : nullptr;
+        if (last && pool_rows && want_max()) {
+            const long long groups = rows / pool_rows;
+            const int prow = pool_rows == 16 ? 16 : 32;
+            long long blocks = (groups * L.cout + 255) / 256;
+            if (blocks > 4096) blocks = 4096;
+            if (int rc = launch(tl_pool_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, groups, L.cout, pool_rows / prow,
+                                prow, (const float *)p.pmax, (const int *)p.pamax, (const float *)L.gamma,
+                                (const float *)L.save, maxv ? maxv : out(), const_cast<int *>(c.argsel), const_cast<float *>(c.zsel))) return rc;
+        }
+        if (last && pool_rows && pooling != 0) {
+            const long long groups = rows / pool_rows;
+            if (pooling == 2) {
+                if (int rc = launch(tl_pool_weights_kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, st, groups, pool_rows,
+                                    c.group->n, c.group->m, c.group->xyz, c.group->new_xyz, c.group->idx, const_cast<float *>(c.pool_w))) return rc;
+            }
+            long long blocks = (groups * (L.cout / 4) + 255) / 256;
+            if (blocks > 8192) blocks = 8192;
+            return launch(tl_pool_avg_kernel, dim3((unsigned)blocks), dim3(256), 0, st, groups, pool_rows, L.cout, (const float *)L.z,
+                          (const float *)L.save, c.pool_w, (const float *)maxv, out());
+        }
+        return (last && !pool_rows) ? apply(L) : PN2_OK;
+    }
+
+    int run()
+    {
+        if (int rc = check_inputs()) return rc;
+        if ((!c.group && !c.x && !fp) || !c.out || !c.ws || pool_buffers_missing(c.pool_rows)) return PN2_E_NULL;
+        if (c.pool_rows && (c.rows % c.pool_rows || (c.group && c.pool_rows != c.group->nsample))) return PN2_E_ARG;
+        if (!plan(c.pool_rows, 0)) return PN2_E_ARG;
+        per_point = c.group && l1_per_point(c.nlayers, widths, &gd, o);
+        // forward: layer 1 on the vector units only WITHOUT features (with the input normals gathered per row the vector kernel
+        // measured slower than the gathered GEMM: cls_msg forward 2.51 -> 2.57 ms; its backward counterpart is the one that pays)
+        coords_only = c.group && gd.cfeat == 0 && l1_coords_only(c.nlayers, widths, &gd, o);
+        keep_top = c.pooling != 0 || top_stored(c.rows, c.nlayers, widths, c.pool_rows, o);    // a mean needs z_L itself
+        for (int l = 0; l < c.nlayers; ++l)
+            if (!c.layers[l].z && (keep_top || l < c.nlayers - 1)) return PN2_E_NULL;
+        if (int rc = pack_weights()) return rc;
+        if (c.frozen)                                             // every layer's (m', invstd, a, c) from the running statistics
+            if (int rc = frozen_launch_save(c.nlayers, c.layers, st)) return rc;
+        // The conv bias is NOT added to the pre-norm tensors: batch normalisation removes any per-channel constant, so
+        // z_l := h W_l gives the same output, the same gradients (the bias gradient is zero) and the same batch variance; only
+        // the batch MEAN that enters the running average is mean(z_l) + b_l (tl_bn_finalize_kernel). It is more than a saved
+        // add: the folded form a z + c loses accuracy with |mean| / std of a channel, and a bias is pure mean.
+        for (int l = 0; l < c.nlayers; ++l) {
+            const int rc = l > 0 ? generic_layer(l) : fp ? layer1_fp() : per_point ? layer1_per_point()
+                         : coords_only ? layer1_coords_only() : generic_layer(0);
+            if (rc) return rc;
+        }
+        return PN2_OK;
+    }
+};
+
+// pooling: 0 max, 1 avg, 2 weighted_avg, 3 max_and_avg (pn2_mlp_train_forward_pool checks it)
+int tl_train_forward(const TlCall &call) { return Fwd(call).run(); }
+
+// ---- backward ---------------------------------------------------------------------------------------------------------------
+// pooling 1-3 (pn2_mlp_train_backward_pool): the averaged top layer is an UNPOOLED one from here on -- its dense gradient
+// (tl_pool_top_grad_kernel) enters the passes of the FP levels' top layer, and everything below runs unchanged
+struct Bwd : TlRun {
+    using TlRun::TlRun;
+    const int cus = device_cus();
+    long long rows = 0;
+    int nlayers = 0;
+    const pn2_bn_layer *layers = nullptr;
+    XyzPlan xp;
+    // decided once
+    int pool_rows = 0, avg_rows = 0;                    // the max's group size; > 0: the group size of the averaged top layer
+    bool want_xyz = false, want_dx = false, per_point = false, coords_only = false;
+    bool ztop = false;                                  // pooled top layer without z_L (tl_top_mats_kernel)
+    bool skip[8] = {false, false, false, false, false, false, false, false};
+    int lo = 0;
+    FuseShape fz[8];
+    WgradShape wz[8];
+    // running
+    bool ident_written = false;
+    bool folded[8] = {false, false, false, false, false, false, false, false};     // layers whose backward finalisation ran inside the pass above
+    int nparts[8];                                      // rows of each layer's partial-sum array
+    float *gq = nullptr;                                // the pooled gradient (groups, cout_L)
+    float *gcur = nullptr, *gnext = nullptr;            // dy of the current layer (dense case) / of the layer below
+    int l1_moment_parts = 0;                            // > 0: layer 1's weight gradient comes from moments (TlWgrad::l1x)
+    // weight-gradient launches on a helper stream beside the data-gradient chain (SideStream above): OPT-IN. Measured
+    // (scripts/lab_ab.sh side_stream, profiles/r04/README.md): every fork / join is a cross-queue dependency of ~10 us on this
+    // runtime, three pairs per level -- sem_seg SA2 280 -> 330 us, SA4 250 -> 305, FP4 335 -> 380; only the group_all level
+    // (three wide layers over 4,096 rows) gains, 431 -> 379 us. The size rule therefore never switches it on.
+    SideStream sd;
+
+    float *coef(int l) const { return at<float>(pl.coef[l]); }
+    bool below(int l) const { return l > lo || (l == 0 && want_dx); }
+    double *sums_of(int l) const { return skip[l] ? nullptr : stats(l); }
+    bool pooled_top(int l) const { return pool_rows && l == nlayers - 1; }
+
+    // the arguments, the plan, and everything that is decided once
+    int prepare()
+    {
+        rows = c.rows; nlayers = c.nlayers; layers = c.layers;
+        if (int rc = check_inputs()) return rc;
+        want_xyz = c.group && c.grad_xyz;               // the coordinate gradients (pn2_mlp_train_backward_xyz, train_mlp_xyz.hip)
+        if ((!c.group && !c.x && !fp) || !c.out || !c.grad_out || !c.ws || pool_buffers_missing(c.pool_rows)) return PN2_E_NULL;
+        avg_rows = c.pooling ? c.pool_rows : 0;
+        if (c.pooling && (!c.group || avg_rows <= 0 || rows % avg_rows || avg_rows != c.group->nsample)) return PN2_E_ARG;
+        pool_rows = c.pooling ? 0 : c.pool_rows;
+        // frozen statistics: a layer whose four gradient slots are all NULL wants no parameter gradient -- no weight-gradient pass,
+        // no per-channel sums (batch statistics cannot allow that: dz itself needs the sums)
+        for (int l = 0; l < nlayers; ++l) {
+            const bool all3 = layers[l].grad_weight && layers[l].grad_gamma && layers[l].grad_beta;
+            const bool any = layers[l].grad_weight || layers[l].grad_gamma || layers[l].grad_beta ||
+                             (c.frozen && c.grad_bias && c.grad_bias[l]);
+            if (c.frozen && !any) { skip[l] = true; continue; }
+            if (!all3) return PN2_E_NULL;
+        }
+        if (!plan(pool_rows, 1)) return PN2_E_ARG;
+        memset(&xp, 0, sizeof(xp));
+        if (want_xyz && !xyz_plan(pl, rows, nlayers, widths, gd, o, xp)) return PN2_E_ARG;
+        per_point = c.group && l1_per_point(nlayers, widths, &gd, o);
+        coords_only = c.group && l1_coords_only(nlayers, widths, &gd, o);
+        want_dx = fp ? (fp->grad_points2 || fp->grad_points1)
+                : c.group ? ((per_point ? c.grad_points : c.grad_feat_rows) && c.group->points && c.group->cfeat > 0) : c.grad_x != nullptr;
+        ztop = !top_stored(rows, nlayers, widths, pool_rows, o);
+        for (int l = 0; l < nlayers; ++l)
+            if (!layers[l].z && !(ztop && l == nlayers - 1)) return PN2_E_NULL;
+        // frozen statistics: the chain stops at the lowest layer that still needs something (lo; 0 otherwise), and a layer takes
+        // a data gradient from above only where something below it is wanted
+        if (c.frozen)
+            while (lo < nlayers - 1 && skip[lo] && !(lo == 0 && (want_dx || want_xyz))) ++lo;
+        // Which layers run their data gradient inside the weight-gradient pass (one pass over the layer's activations instead of
+        // two, tl_wgrad_kernel<.., DY>): decided here, once, for the packing below and the launches
+        memset(fz, 0, sizeof(fz));
+        for (int l = lo; l < nlayers; ++l) {
+            const pn2_bn_layer &L = layers[l];
+            if (skip[l] || (l > 0 && !below(l))) continue;              // no weight-gradient pass to fuse into / no data gradient to fuse
+            if (ztop && l == nlayers - 1) {
+                // (the z-free pooled top layer in one pass is correct and tested, but not yet faster than its three kernels -- 690 vs
+                // 590 us at the metric shape: two waves carry the whole data gradient, 72 MFMAs on transposed reads each -- so the
+                // size rule leaves it off; fuse_wgrad = PN2_OPT_ON forces it)
+                wz[l] = wgrad_shape(rows, L.cin, top_cols(L.cin, L.cout), false, cus, PN2_OPT_OFF);
+                if (o.fuse_wgrad == PN2_OPT_ON) fz[l] = fuse_shape(rows, wz[l], tiles(L.cout) * 32 + L.cin, L.cin, o, false);
+            } else if (!(l == 0 && (c.group || fp || !want_dx))) {
+                wz[l] = wgrad_shape(rows, L.cin, L.cout, false, cus, PN2_OPT_OFF);
+                fz[l] = fuse_shape(rows, wz[l], L.cout, L.cin, o);
+            }
+            if (fz[l].ok) { wz[l].lds_dy = fz[l].lds; wz[l].upw = fz[l].upw; }
+        }
+        gq = at<float>(pl.gq);
+        gcur = at<float>(pl.ga); gnext = at<float>(pl.gb);
+        return PN2_OK;
+    }
+
+    // W_l^T of every data-gradient GEMM, one launch
+    int pack_weights()
+    {
+        TlPackJobs jobs;
+        memset(&jobs, 0, sizeof(jobs));
+        int nj = 0;
+        for (int l = lo; l < nlayers; ++l) {
+            const pn2_bn_layer &L = layers[l];
+            if (below(l) && !(ztop && l == nlayers - 1)) {               // dy_{l-1} = dz_l . W_l^T
+                if (fz[l].ok) {                                   // every output tile in ONE slab (the fused pass keeps W^T resident)
+                    add_pack_job(jobs, nj, L.weight, L.w_stride_n, L.w_stride_k, one_slab(L.cout, L.cin, fz[l]), base + pl.pack[l]);
+                } else if (l == 0 && fp) {                        // W1a^T, W1b^T: the data gradients of points2 / points1
+                    if (fp->grad_points2)
+                        add_pack_job(jobs, nj, L.weight, L.w_stride_n, L.w_stride_k, gemm_shape(fp->mp, L.cout, fp->c2, o), base + pl.pack[l]);
+                    if (fp->grad_points1 && fp->c1 > 0)
+                        add_pack_job(jobs, nj, L.weight + (long long)fp->c2 * L.w_stride_k, L.w_stride_n, L.w_stride_k,
+                                     gemm_shape(rows, L.cout, fp->c1, o), base + pl.fpw);
+                } else if (l == 0 && c.group) {
+                    // layer 1 of a grouped level: only the FEATURE rows of W_1 (the grouped xyz takes no gradient here);
+                    // per point: the same tiles, for the GEMM over the b n points
+                    const TlGather gt = make_gather(c.group);
+                    add_pack_job(jobs, nj, L.weight + gt.feat_off * L.w_stride_k, L.w_stride_n, L.w_stride_k,
+                                 gemm_shape(per_point ? (long long)gd.b * gd.n : rows, L.cout, gt.cfeat, o), base + pl.pack[l]);
+                } else {
+                    add_pack_job(jobs, nj, L.weight, L.w_stride_n, L.w_stride_k, gemm_shape(rows, L.cout, L.cin, o), base + pl.pack[l]);
+                }
+            }
+        }
+        if ((per_point || fp) && nj > 0) {                        // the identity coefficients of layer 1's per-point weight gradient
+            jobs.ident = at<float>(pl.l1coef);
+            jobs.ident_c = layers[0].cout;
+        }
+        ident_written = jobs.ident != nullptr;
+        fold = fold_wanted(o) && nj > 0 && !c.frozen;             // (the pack launch zeroes the tickets)
+        if (fold) jobs.tickets = tickets();
+        return launch_pack_jobs(jobs, nj, st);
+    }
+
+    // the operand tiles of a data gradient that rides in the weight-gradient pass: every output tile in one slab
+    static GemmShape one_slab(int K, int N, const FuseShape &f)
+    {
+        GemmShape gg;
+        memset(&gg, 0, sizeof(gg));
+        gg.K = K; gg.N = N; gg.tk = f.tk; gg.tn = f.nt; gg.ns = f.nt; gg.slabs = 1;
+        return gg;
+    }
+
+    // frozen statistics: dz = a dy for every layer, known before the first pass
+    int frozen_coefficients() const
+    {
+        float *cf[8];
+        for (int l = 0; l < nlayers; ++l) cf[l] = coef(l);
+        return frozen_launch_coef(nlayers, layers, cf, st);
+    }
+
+    // top of the stack: dy_L and its two column sums
+    int top_gradient()
+    {
+        const pn2_bn_layer &T = layers[nlayers - 1];
+        const long long groups = pool_rows ? rows / pool_rows : 0;
+        long long gy = pool_rows ? (groups + 63) / 64 : (rows + 255) / 256;
+        if (gy > kMaxParts) gy = kMaxParts;
+        nparts[nlayers - 1] = (int)gy;
+        const dim3 grid((unsigned)((T.cout + 63) / 64), (unsigned)gy);
+        double *sums = sums_of(nlayers - 1);
+        if (avg_rows)
+            return launch(tl_pool_top_grad_kernel, grid, dim3(256), 0, st, rows, avg_rows, T.cout, c.grad_out, (const float *)T.z,
+                          (const float *)T.save, c.pool_w, c.pooling == 3 ? c.argsel : nullptr, gcur, sums);
+        if (pool_rows)
+            return launch(tl_pool_grad_kernel, grid, dim3(256), 0, st, groups, T.cout, c.out, c.grad_out, c.zsel, gq, sums);
+        return launch(tl_top_grad_kernel, grid, dim3(256), 0, st, rows, T.cout, c.out, c.grad_out, (const float *)T.z, gcur, sums);
+    }
+
+    // The coordinate gradients, from layer 1's dz_1 = s G - c0 - c1 Z (cf == nullptr: G is dz_1 itself; sel: the pooled
+    // single-layer stack, G = gq): g_r = dz_1[r] . W1x^T per row, grad_new_xyz = minus the group sums, grad_xyz = the rows
+    // scattered onto the points -- or, where backward has dz_1 on the points already (S, layer 1 per point), S . W1x^T
+    int xyz_pass(const float *G, const float *Z, const float *cf, const int *sel, const float *S) const
+    {
+        const pn2_bn_layer &L1 = layers[0];
+        const pn2_group_src *group = c.group;
+        const float *wx = L1.weight + make_gather(group).xyz_off * L1.w_stride_k;
+        if (!group->idx)                                  // group_all: row k of cloud i IS point k, no centroid
+            return xyz_launch_rows(rows, L1.cout, G, Z, cf, sel, gd.nsample, wx, L1.w_stride_k, L1.w_stride_n, c.grad_xyz, st);
+        float *g3 = at<float>(xp.g);
+        if (c.grad_new_xyz || !S) {
+            if (int rc = xyz_launch_rows(rows, L1.cout, G, Z, cf, sel, gd.nsample, wx, L1.w_stride_k, L1.w_stride_n, g3, st)) return rc;
+            if (c.grad_new_xyz)
+                if (int rc = xyz_launch_centroids(rows / gd.nsample, gd.nsample, g3, c.grad_new_xyz, st)) return rc;
+        }
+        if (S)
+            return xyz_launch_rows((long long)gd.b * gd.n, L1.cout, S, nullptr, nullptr, nullptr, 1, wx, L1.w_stride_k, L1.w_stride_n,
+                                   c.grad_xyz, st);
+        return pn2_group_point_grad_seg(gd.b, gd.n, 3, gd.m, gd.nsample, g3, group->idx, c.grad_xyz, base + xp.seg, c.reproducible, c.stream);
+    }
+
+    // a weight-gradient pass into the planned partial sums
+    TlWgrad wgrad_into_partial(long long wrows, int KI) const
+    {
+        TlWgrad w;
+        memset(&w, 0, sizeof(w));
+        w.rows = wrows;
+        w.KI = KI;
+        w.partial = at<float>(pl.partial); w.partial_cap = pl.partial_cap;
+        return w;
+    }
+
+    // the first operand of a layer's passes: h_{l-1} = relu(a z_{l-1} + c) of the layer below
+    static void relu_input(TlWgrad &w, const pn2_bn_layer &D)
+    {
+        w.amode = A_RELU; w.A = D.z; w.pa = D.save + 2 * D.cout; w.pc = D.save + 3 * D.cout;
+    }
+
+    // the data gradient's epilogue into the layer below: dy_{l-1} masked by that layer's ReLU, its (dy, dy z) summed -- and,
+    // folded, the sums turned into that layer's gradients and coefficients by the same launch
+    void into_below(TlGemm &p, int l)
+    {
+        const pn2_bn_layer &D = layers[l - 1];
+        p.emode = E_MASK;
+        p.out = gnext;
+        p.zprev = D.z; p.ea = D.save + 2 * D.cout; p.ec = D.save + 3 * D.cout;
+        p.stats = sums_of(l - 1);
+        p.nostats = (c.frozen && !p.stats) ? 1 : 0;
+        if (!fold) return;
+        p.fin = fin_backward(D, rows, p.stats, coef(l - 1), tickets() + (l - 1));
+        folded[l - 1] = true;
+    }
+
+    // ... the same epilogue where the data gradient rides in the weight-gradient pass
+    void dy_into_below(TlWgrad &w, int l) const
+    {
+        const pn2_bn_layer &D = layers[l - 1];
+        w.dy_out = gnext;
+        w.dy_zprev = D.z; w.dy_ea = D.save + 2 * D.cout; w.dy_ec = D.save + 3 * D.cout;
+        w.dy_stats = sums_of(l - 1);
+    }
+
+    void dy_in_wgrad(TlWgrad &w, int l, int cols) const
+    {
+        w.dy_w = at<const u32x4>(pl.pack[l]);
+        w.xr_off = (int)fz[l].xr_off;
+        w.dy_tk = fz[l].tk; w.dy_nt = fz[l].nt; w.single = fz[l].single;
+        w.dy_cols = cols; w.dy_pitch = cols;
+        w.dy_nt_store = o.nt == PN2_OPT_OFF ? 0 : o.nt == PN2_OPT_ON ? 1 : (size_t)rows * cols * sizeof(float) >= ((size_t)128 << 20);
+    }
+
+    // A data gradient beside the weight gradient of the same layer, independent passes over the same activations: ONE launch
+    // for both where the pair has a kernel (tl_pair_kernel), else the weight gradient first (on the helper stream when that
+    // is asked for), then the GEMM. pair_rows: the row count the pair rule looks at.
+    int beside(int amode, TlGemm &p, const GemmShape &g, TlWgrad &w, const WgradShape &ws, const pn2_bn_layer &L, long long pair_rows,
+               int *np, double *plain = nullptr)
+    {
+        int rc = kNoPair;
+        if (pair_wanted(pair_rows, o)) rc = launch_pair(amode, p, g, w, ws, L, st, o, np, plain);
+        if (rc == kNoPair) {
+            if ((rc = sd.fork())) return rc;
+            if ((rc = launch_wgrad(w, ws, L, sd.get(), plain))) return rc;
+            rc = launch_gemm(amode, p, g, st, o, np);
+        }
+        return rc;
+    }
+
+    int identity_coefficients(int C) const
+    {
+        if (ident_written) return PN2_OK;
+        return launch(tl_identity_coef_kernel, dim3((unsigned)((3 * C + 127) / 128)), dim3(128), 0, st, C, at<float>(pl.l1coef));
+    }
+
+    // layer l's per-channel sums -> grad_gamma, grad_beta and the coefficients of dz_l (unless the pass above did it, or the
+    // statistics are frozen); then the helper stream's reads of the dy buffer this layer's data gradient overwrites
+    int begin_layer(int l)
+    {
+        const pn2_bn_layer &L = layers[l];
+        if (!folded[l] && !c.frozen)
+            if (int rc = launch(tl_bn_backward_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
+                                (const double *)stats(l), nparts[l], L.cout, (double)rows, L.gamma, (const float *)L.save,
+                                L.grad_gamma, L.grad_beta, coef(l), L.grad_accumulate)) return rc;
+        return sd.join();
+    }
+
+    // ---- the pooled top layer in terms of its input h = relu(a z_{l-1} + c): see tl_top_mats_kernel
+    int pooled_top_without_z(int l)
+    {
+        const pn2_bn_layer &L = layers[l], &D = layers[l - 1];
+        const int K = L.cin, NF = L.cout, tf = tiles(NF), NFp = tf * 32, ld = top_cols(K, NF);
+        float *wp = at<float>(pl.topw), *rowc = wp + (size_t)(NFp + K) * K;
+        double *sf = at<double>(pl.topsf);
+        {
+            long long blocks = ((long long)(NFp + K + 1) * K + 255) / 256;
+            if (blocks > 4096) blocks = 4096;
+            if (int rc = launch(tl_top_mats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, L.weight, L.w_stride_k, L.w_stride_n,
+                                K, NF, NFp, (const float *)coef(l), (const float *)nullptr, wp, rowc)) return rc;    // z_L = h W: no bias term
+        }
+        // both variants: the routed gradient and h as the dense kernel's second operand, tl_top_wgrad_fix_kernel behind it
+        TlWgrad w = wgrad_into_partial(rows, K);
+        relu_input(w, D);
+        w.dmode = A_FILL;
+        w.G = gq; w.argsel = c.argsel; w.coef = coef(l); w.group_rows = pool_rows;
+        auto fix = [&](int ldw, int tfw, const double *s64, hipStream_t s) {
+            long long blocks = ((long long)K * NF + 255) / 256;
+            if (blocks > 4096) blocks = 4096;
+            return launch(tl_top_wgrad_fix_kernel, dim3((unsigned)blocks), dim3(256), 0, s, (const double *)sf, ldw, K, NF, tfw * 32,
+                          tfw * 32 + tiles(K) * 32, L.weight, L.w_stride_k, L.w_stride_n, (const float *)coef(l),
+                          (const float *)nullptr, L.grad_weight, s64, L.grad_accumulate);
+        };
+        if (fz[l].ok) {
+            // ---- ONE pass over z_{l-1}: the routed gradient and h as operand tiles of the block image serve the weight
+            // gradient (S, Gram matrix, column sums: tl_top_wgrad_fix_kernel combines them) AND the data gradient
+            // dy_{l-1} = [s dy routed | h] . [W^T ; -M] - r, masked by the layer below (as separate kernels z_{l-1} crossed
+            // HBM in the data-gradient GEMM, in tl_top_s_kernel and in the Gram pass)
+            if (int rc = launch_pack(wp, K, 1, one_slab(NFp + K, K, fz[l]), base + pl.pack[l], st)) return rc;
+            w.NO = ld; w.tf = tf; w.NF = NF;
+            w.xshare = 1;                                     // one slab: the "h again" tiles are the first operand's
+            dy_in_wgrad(w, l, K);
+            w.dy_tf = tf;
+            dy_into_below(w, l);
+            w.dy_bias = rowc;
+            if (int rc = launch_wgrad(w, wz[l], L, st, sf)) return rc;
+            nparts[l - 1] = (int)wz[l].gridx;
+            return fix(ld, tf, nullptr, st);
+        }
+        // weight gradient: the routed part S on the vector units (tl_top_s_kernel) when its shape allows, the Gram
+        // matrix h^T h and the column sums of h from the dense kernel, combined by tl_top_wgrad_fix_kernel;
+        // data gradient: the GEMM over [routed gradient | h]. The dense kernel and the GEMM are independent passes over
+        // z_{l-1}: one launch for both where the pair has a kernel (tl_pair_kernel)
+        const TopSShape ts = top_s_shape(rows, pool_rows, K, NF, o);
+        double *s64 = ts.ok ? at<double>(pl.tops64) : nullptr;
+        const bool wg = !skip[l];                          // (frozen statistics: a layer without parameter gradients)
+        if (int rc = sd.fork()) return rc;                 // the weight gradient's kernels beside the data gradient below
+        if (ts.ok && wg) {
+            TlTopS q;
+            memset(&q, 0, sizeof(q));
+            q.groups = rows / pool_rows; q.ns = pool_rows; q.K = K; q.NF = NF;
+            q.z = D.z; q.pa = D.save + 2 * D.cout; q.pc = D.save + 3 * D.cout;
+            q.gq = gq; q.argsel = c.argsel; q.coef = coef(l);
+            q.partial = at<float>(pl.tops_part);
+            if (int rc = launch_top_s(q, ts, at<float>(pl.tops_part2), s64, sd.get())) return rc;
+        }
+        const int tfw = ts.ok ? 0 : tf, ldw = ts.ok ? top_cols(K, 0) : ld;       // operand tiles of the dense kernel
+        w.NO = ldw; w.tf = tfw; w.NF = ts.ok ? 0 : NF;
+        const WgradShape ws_ = wgrad_shape(rows, K, ldw, false, cus, o.wgrad_two_per_cu);
+        w.xshare = ws_.uslabs == 1;
+        const GemmShape g = gemm_shape(rows, NFp + K, K, o);
+        if (int rc = launch_pack(wp, K, 1, g, base + pl.pack[l], st)) return rc;
+        TlGemm p;
+        memset(&p, 0, sizeof(p));
+        p.rows = rows;
+        p.tk0 = tf; p.K0 = NF; p.K1 = K;
+        p.G = gq; p.argsel = c.argsel; p.p0 = coef(l); p.group_rows = pool_rows;
+        p.A2 = D.z; p.q0 = D.save + 2 * D.cout; p.q1 = D.save + 3 * D.cout;
+        p.wpacked = at<const u32x4>(pl.pack[l]);
+        p.bias = rowc;
+        into_below(p, l);
+        int np = 0;
+        if (int rc = wg ? beside(A_FILL, p, g, w, ws_, L, rows, &np, sf) : launch_gemm(A_FILL, p, g, st, o, &np)) return rc;
+        nparts[l - 1] = np;
+        return wg ? fix(ldw, tfw, s64, sd.get()) : PN2_OK;
+    }
+
+    // ---- a level without features (or with a few whose gradient nobody wants -- the network's input normals): the
+    // first layer's weight gradient on the vector units
+    int layer1_coords_only()
+    {
+        const pn2_bn_layer &L = layers[0];
+        if (l1_moment_parts) {                                // ... from x^T dy_1 of the pass above and the moments of x
+            const TlGather gt = make_gather(c.group);
+            return launch(tl_l1_wx_combine_kernel, dim3((unsigned)((3 * L.cout + 7) / 8)), dim3(256), 0, st,
+                          (const double *)at<double>(pl.l1mom), l1_moment_parts, (const double *)at<double>(pl.l1a), nparts[0], L.cout,
+                          L.cout, (const float *)coef(0), L.weight + gt.xyz_off * L.w_stride_k, L.w_stride_k, L.w_stride_n,
+                          L.grad_weight + gt.xyz_off * L.w_stride_k, L.grad_accumulate);
+        }
+        // ... in one pass over dy_1 and z_1
+        if (!skip[0])
+            if (int rc = launch_l1_dz(rows, gd, c.group, L, gcur, coef(0), at<float>(pl.l1part), false, st)) return rc;
+        return want_xyz ? xyz_pass(gcur, L.z, coef(0), nullptr, nullptr) : PN2_OK;
+    }
+
+    // Layer 1 per point / per known point, one half of W_1: dW_half = A^T D over hr rows (rows kc of the weight gradient from
+    // row koff; kp: A's width as read) and, when gout is wanted, gout = D W_half^T beside it. D is dz_1 itself: the weight
+    // gradient's pass takes the identity coefficients, which the caller has made sure of (identity_coefficients).
+    int l1_half(long long hr, int kp, int kc, const float *A, const float *D, size_t pack, float *gout, int koff, long long pair_rows)
+    {
+        const pn2_bn_layer &L = layers[0];
+        TlWgrad w = wgrad_into_partial(hr, kp);
+        w.kout = kc; w.amode = A_PLAIN; w.A = A;
+        w.dmode = A_DZ; w.NO = L.cout; w.Z = D; w.G = D; w.coef = at<float>(pl.l1coef);
+        pn2_bn_layer Lh = L;
+        Lh.grad_weight = L.grad_weight + (long long)koff * L.w_stride_k;
+        const WgradShape ws_ = wgrad_shape(hr, kp, L.cout, false, cus, o.wgrad_two_per_cu);
+        if (!gout) return launch_wgrad(w, ws_, Lh, st);
+        TlGemm p = dense_gemm(hr, D, base + pack);
+        plain_out(p, gout, kc);
+        return beside(A_PLAIN, p, gemm_shape(hr, L.cout, kc, o), w, ws_, Lh, pair_rows, nullptr);
+    }
+
+    // ---- layer 1 of an FP level per KNOWN point (train_mlp_fp.hip): dz_1 in place, its interpolation gradient S onto
+    // the known points, then each half of W_1 -- a weight gradient and a data gradient over its own rows
+    int layer1_fp()
+    {
+        const pn2_bn_layer &L = layers[0];
+        float *S = at<float>(pl.l1p);
+        if (int rc = fp_launch_l1_dz(rows, L.cout, L.z, gcur, coef(0), st)) return rc;
+        if (int rc = pn2_three_interpolate_grad_seg(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx, fp->weight, S, base + pl.l1seg,
+                                                    c.reproducible, c.stream)) return rc;
+        if (fp->mp > fp->bm)                                  // the padding rows of S meet the zero rows of points2's copy
+            if (int rc = clear_async(S + fp->bm * L.cout, sizeof(float) * (size_t)(fp->mp - fp->bm) * L.cout, st)) return rc;
+        if (int rc = identity_coefficients(L.cout)) return rc;
+        const float *p2, *p1;
+        if (int rc = fp_padded_inputs(p2, p1)) return rc;
+        float *g2 = (fp->grad_points2 && fp->gstage2()) ? at<float>(pl.fpg2) : fp->grad_points2;
+        if (int rc = l1_half(fp->mp, fp->c2p, fp->c2, p2, S, pl.pack[0], g2, 0, fp->mp)) return rc;
+        if (g2 && g2 != fp->grad_points2)
+            if (int rc = fp_launch_pad(g2, fp->bm, fp->c2, fp->bm, fp->c2, fp->grad_points2, st)) return rc;
+        if (fp->c1 > 0) return l1_half(rows, fp->c1p, fp->c1, p1, gcur, pl.fpw, fp->grad_points1, fp->c2, rows);
+        return PN2_OK;
+    }
+
+    // ---- layer 1 once per point (see tl_l1_forward_kernel): dz_1 and dW1x in one pass over the rows, the scatter of
+    // dz_1 onto the points, then two GEMMs over the b n points
+    int layer1_per_point()
+    {
+        const pn2_bn_layer &L = layers[0];
+        const TlGather gt = make_gather(c.group);
+        const long long bn = (long long)gd.b * gd.n;
+        float *S = at<float>(pl.l1p);
+        if (int rc = launch_l1_dz(rows, gd, c.group, L, gcur, coef(0), at<float>(pl.l1part), true, st, !skip[0])) return rc;
+        if (int rc = pn2_group_point_grad_seg(gd.b, gd.n, L.cout, gd.m, gd.nsample, gcur, c.group->idx, S, base + pl.l1seg,
+                                              c.reproducible, c.stream)) return rc;
+        if (want_xyz)                                         // (gcur holds dz_1 now)
+            if (int rc = xyz_pass(gcur, nullptr, nullptr, nullptr, S)) return rc;
+        if (skip[0]) {                                        // frozen statistics, no dW_1 wanted: the data gradient alone
+            if (!want_dx) return PN2_OK;
+            TlGemm p = dense_gemm(bn, S, base + pl.pack[0]);
+            plain_out(p, c.grad_points, gt.cfeat);
+            return launch_gemm(A_PLAIN, p, gemm_shape(bn, L.cout, gt.cfeat, o), st, o);
+        }
+        if (int rc = identity_coefficients(L.cout)) return rc;
+        // dW1f = points^T S; dPoints = S W1f^T: beside it, in one launch where the pair has a kernel
+        // (the pair rule looks at the level's rows here, not at the b n points)
+        return l1_half(bn, gt.cfeat, gt.cfeat, c.group->points, S, pl.pack[0], want_dx ? c.grad_points : nullptr, gt.feat_off, rows);
+    }
+
+    // ---- every other layer: the weight gradient from (dy_l, z_l, the layer's input), the data gradient into the layer below
+    int generic_layer(int l)
+    {
+        const pn2_bn_layer &L = layers[l];
+        const bool ptop = pooled_top(l);
+        if (l == 0 && want_xyz)                                     // the generic gathered layer 1: from (dy_1, z_1), which nothing below overwrites
+            if (int rc = xyz_pass(ptop ? gq : gcur, L.z, coef(0), ptop ? c.argsel : nullptr, nullptr)) return rc;
+        // weight gradient
+        TlWgrad w = wgrad_into_partial(rows, L.cin);
+        if (l == 0 && c.group) { w.amode = A_GATHER; w.g = make_gather(c.group); }
+        else if (l == 0) { w.amode = A_PLAIN; w.A = c.x; }
+        else relu_input(w, layers[l - 1]);
+        w.dmode = ptop ? A_DZ_POOL : A_DZ;
+        w.NO = L.cout;
+        w.Z = L.z;
+        w.G = ptop ? gq : gcur;
+        w.argsel = c.argsel;
+        w.coef = coef(l);
+        w.group_rows = pool_rows;
+        if (fz[l].ok) {
+            // ... and the data gradient in the same pass over (dy_l, z_l, z_{l-1}), see tl_wgrad_kernel
+            dy_in_wgrad(w, l, L.cin);
+            w.dy_tf = 0; w.dy_acopy = fz[l].acopy;
+            if (l > 0) dy_into_below(w, l);
+            else w.dy_out = c.grad_x;
+            // (not with the coordinate gradients: g_r needs dy_1 row by row, so it is written and tl_l1_dz_kernel's pass runs)
+            if (l == 1 && coords_only && gd.cfeat == 0 && !ptop && !want_xyz && !skip[0]) {            // (a pooled two-layer stack keeps the pass over dy_1: its dz comes from the routed gradient)
+                // the layer below takes the three centred coordinates: dy_1 is wanted only as x^T dy_1 (TlWgrad::l1x) -- never
+                // written, and tl_l1_dz_kernel's pass over (dy_1, z_1) is replaced by nine moments of x
+                const pn2_bn_layer &D = layers[0];
+                TlL1 q;
+                memset(&q, 0, sizeof(q));
+                q.rows = rows; q.n = gd.n; q.m = gd.m; q.nsample = gd.nsample; q.C = D.cout;
+                q.xyz = c.group->xyz; q.new_xyz = c.group->new_xyz; q.idx = c.group->idx;
+                long long xb = (rows + kL1XrowsThreads - 1) / kL1XrowsThreads;
+                if (xb > kMaxParts) xb = kMaxParts;
+                l1_moment_parts = (int)xb;
+                if (int rc = launch(tl_l1_xrows_kernel, dim3((unsigned)xb), dim3(kL1XrowsThreads), 0, st, q, at<float4>(pl.l1xg),
+                                    at<double>(pl.l1mom))) return rc;
+                w.l1x = at<const float4>(pl.l1xg);
+                w.l1a = at<double>(pl.l1a);
+                w.dy_out = nullptr;
+            }
+            if (int rc = launch_wgrad(w, wz[l], L, st)) return rc;
+            if (l > 0) nparts[l - 1] = (int)wz[l].gridx;
+            return PN2_OK;
+        }
+        const WgradShape ws_ = wgrad_shape(rows, L.cin, L.cout, w.amode == A_GATHER, cus, o.wgrad_two_per_cu);
+        if (!below(l))                                         // no data gradient below this layer
+            return skip[l] ? PN2_OK : launch_wgrad(w, ws_, L, st);
+        // data gradient: independent of the weight gradient -- ONE launch for both where the pair has a kernel
+        // (tl_pair_kernel), else the weight gradient first (on the helper stream when that is asked for)
+        const int cfeat = (l == 0 && c.group) ? make_gather(c.group).cfeat : 0;
+        const GemmShape g = (l == 0 && c.group) ? gemm_shape(rows, L.cout, cfeat, o) : gemm_shape(rows, L.cout, L.cin, o);
+        TlGemm p = dense_gemm(rows, L.z, base + pl.pack[l]);
+        p.G = ptop ? gq : gcur;
+        p.argsel = c.argsel;
+        p.p0 = coef(l); p.p1 = coef(l) + L.cout; p.p2 = coef(l) + 2 * L.cout;
+        p.group_rows = pool_rows;
+        if (l > 0) into_below(p, l);
+        else if (c.group) plain_out(p, c.grad_feat_rows, cfeat);
+        else plain_out(p, c.grad_x, L.cin);
+        const int amode = ptop ? A_DZ_POOL : A_DZ;
+        int np = 0;
+        // (frozen statistics, no parameter gradient: the data gradient alone)
+        if (int rc = skip[l] ? launch_gemm(amode, p, g, st, o, &np) : beside(amode, p, g, w, ws_, L, rows, &np)) return rc;
+        if (l > 0) nparts[l - 1] = np;
+        return PN2_OK;
+    }
+
+    // frozen statistics: the per-channel sums of every layer -> grad_gamma, grad_beta, grad_bias: one launch, behind the last
+    // pass (nothing waits for it)
+    int frozen_gradients() const
+    {
+        FrozenSums fs[8];
+        for (int l = 0; l < nlayers; ++l) {
+            fs[l].skip = skip[l];
+            fs[l].stats = skip[l] ? nullptr : stats(l);
+            fs[l].nparts = skip[l] ? 0 : nparts[l];
+        }
+        return frozen_launch_grads(nlayers, layers, fs, c.grad_bias, st);
+    }
+
+    int run()
+    {
+        if (int rc = prepare()) return rc;
+        if (int rc = pack_weights()) return rc;
+        if (c.frozen)
+            if (int rc = frozen_coefficients()) return rc;
+        if (int rc = top_gradient()) return rc;
+        if (int rc = sd.init(st, o.side_stream == PN2_OPT_ON)) return rc;
+        // top down; a layer-1 form is the last stage of its call, so nothing reads gcur / gnext behind it
+        for (int l = nlayers - 1; l >= lo; --l) {
+            if (int rc = begin_layer(l)) return rc;
+            const int rc = (pooled_top(l) && ztop) ? pooled_top_without_z(l)
+                         : l > 0 ? generic_layer(l)
+                         : (coords_only && !(gd.cfeat > 0 && want_dx)) ? layer1_coords_only()
+                         : fp ? layer1_fp()
+                         : per_point ? layer1_per_point()
+                         : generic_layer(0);
+            if (rc) return rc;
+            float *tmp = gcur; gcur = gnext; gnext = tmp;
+        }
+        if (c.frozen)
+            if (int rc = frozen_gradients()) return rc;
+        return sd.join();                                          // everything of this call is ordered before what the caller enqueues next
+    }
+};
+
+int tl_train_backward(const TlCall &call) { return Bwd(call).run(); }
+
+// a grouped level or plain rows, the max pool when pool_rows > 0 (the entries without a pooling argument)
+static TlCall max_call(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x, int pool_rows,
+                       const float *out, const int *argsel, const float *zsel, void *ws, const pn2_train_opts *opts, void *stream)
+{
+    TlCall c{};
+    c.rows = rows; c.nlayers = nlayers; c.layers = layers;
+    c.group = group; c.x = x;
+    c.pool_rows = pool_rows;
+    c.out = out; c.argsel = argsel; c.zsel = zsel;
+    c.ws = ws; c.opts = opts; c.stream = stream;
+    return c;
+}
+
+// the workspace of the coordinate gradients behind the node's own (pn2_mlp_train_ws_bytes_xyz, train_mlp_xyz.hip)
+long long tl_xyz_ws_bytes(long long rows, int nlayers, const int *widths, int pool_rows, int pooling, const int *group_dims,
+                          const pn2_train_opts *opts)
+{
+    if (!widths || !group_dims || nlayers < 1 || nlayers > 8) return -1;
+    const GroupDims gd = group_dims_of(group_dims);
+    const Opts o = opts_of(opts);
+    TlPlan pl;
+    if (!tl_plan(rows, nlayers, widths, pooling ? 0 : pool_rows, 1, pl, &gd, o)) return -1;      // as pn2_mlp_train_ws_bytes_pool
+    XyzPlan xp;
+    if (!xyz_plan(pl, rows, nlayers, widths, gd, o, xp)) return -1;
+    return (long long)xp.total;
+}
+
+// the workspace of the FP level with layer 1 per known point (pn2_mlp_train_ws_bytes_fp, train_mlp_fp.hip)
+long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts)
+{
+    const FpL1 f = fp_l1(s);
+    TlPlan pl;
+    if (!tl_plan(f.rows, nlayers, widths, 0, backward, pl, nullptr, opts_of(opts), &f)) return -1;
+    return (long long)pl.total;
+}
 }  // namespace pn2
 
 extern "C" int pn2_mlp_train_forward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
@@ -2727,221 +3555,11 @@ extern "C" int pn2_mlp_train_forward(long long rows, int nlayers, const pn2_bn_l
     return pn2_mlp_train_forward_ex(rows, nlayers, layers, group, x, pool_rows, out, argsel, zsel, ws, nullptr, stream);
 }
 
-// pooling: 0 max (the _ex entry), 1 avg, 2 weighted_avg, 3 max_and_avg (pn2_mlp_train_forward_pool; arguments checked there)
-static int tl_train_forward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
-                            int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
-                            const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr, const pn2::TlFrozen *fr = nullptr)
-{
-    using namespace pn2;
-    const Opts o = opts_of(opts);
-    int widths[9];
-    if (!layers_ok(rows, nlayers, layers, group, widths, fp)) return PN2_E_ARG;
-    if (fr && fp) return PN2_E_ARG;                              // (the FP node with layer 1 per known point has no frozen form)
-    const bool want_max = pooling == 0 || pooling == 3;          // the extrema of the GEMM epilogue (E_POOL)
-    if ((!group && !x && !fp) || !out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w)) return PN2_E_NULL;
-    if (pool_rows && (rows % pool_rows || (group && pool_rows != group->nsample))) return PN2_E_ARG;
-    TlPlan pl;
-    GroupDims gd;
-    if (group) gd = group_dims(group);
-    if (!tl_plan(rows, nlayers, widths, pool_rows, 0, pl, group ? &gd : nullptr, o, fp)) return PN2_E_ARG;
-    const bool per_point = group && l1_per_point(nlayers, widths, &gd, o);
-    // forward: layer 1 on the vector units only WITHOUT features (with the input normals gathered per row the vector kernel
-    // measured slower than the gathered GEMM: cls_msg forward 2.51 -> 2.57 ms; its backward counterpart is the one that pays)
-    const bool coords_only = group && gd.cfeat == 0 && l1_coords_only(nlayers, widths, &gd, o);
-    const bool keep_top = pooling != 0 || top_stored(rows, nlayers, widths, pool_rows, o);    // a mean needs z_L itself
-    for (int l = 0; l < nlayers; ++l)
-        if (!layers[l].z && (keep_top || l < nlayers - 1)) return PN2_E_NULL;
-    hipStream_t st = as_stream(stream);
-    char *base = static_cast<char *>(ws);
-    unsigned *tickets = reinterpret_cast<unsigned *>(base + pl.tickets);
-    bool fold = false;                                            // the finalisation of a layer's batch moments inside the pass that sums them
-    {
-        TlPackJobs jobs;                                          // every layer's weights -> operand tiles, one launch
-        memset(&jobs, 0, sizeof(jobs));
-        int nj = 0;
-        for (int l = 0; l < nlayers; ++l) {
-            const pn2_bn_layer &L = layers[l];
-            if (l == 0 && coords_only) continue;                 // no matrix-core pass at all
-            if (l == 0 && fp) {                                   // W1a for the known points' GEMM, W1b for the one over the rows
-                add_pack_job(jobs, nj, L.weight, L.w_stride_k, L.w_stride_n, gemm_shape(fp->mp, fp->c2, L.cout, o), base + pl.pack[l]);
-                if (fp->c1 > 0)
-                    add_pack_job(jobs, nj, L.weight + (long long)fp->c2 * L.w_stride_k, L.w_stride_k, L.w_stride_n,
-                                 gemm_shape(rows, fp->c1, L.cout, o), base + pl.fpw);
-                continue;
-            }
-            if (l == 0 && per_point) {                           // only the feature rows of W_1: P = points . W1f
-                const TlGather gt = make_gather(group);
-                add_pack_job(jobs, nj, L.weight + gt.feat_off * L.w_stride_k, L.w_stride_k, L.w_stride_n,
-                             gemm_shape((long long)gd.b * gd.n, gt.cfeat, L.cout, o), base + pl.pack[l]);
-            } else {
-                add_pack_job(jobs, nj, L.weight, L.w_stride_k, L.w_stride_n, gemm_shape(rows, L.cin, L.cout, o), base + pl.pack[l]);
-            }
-        }
-        fold = fold_wanted(o) && nj > 0 && !fr;                   // (the pack launch zeroes the tickets; frozen: nothing to fold)
-        if (fold) jobs.tickets = tickets;
-        if (int rc = launch_pack_jobs(jobs, nj, st)) return rc;
-    }
-    if (fr)                                                       // every layer's (m', invstd, a, c) from the running statistics
-        if (int rc = frozen_launch_save(nlayers, layers, st)) return rc;
-    // a layer's batch moments: summed by its pass, or not at all under frozen statistics
-    auto moments = [&](int l) -> double * { return fr ? nullptr : reinterpret_cast<double *>(base + pl.stats[l]); };
-    // The conv bias is NOT added to the pre-norm tensors: batch normalisation removes any per-channel constant, so
-    // z_l := h W_l gives the same output, the same gradients (the bias gradient is zero) and the same batch variance; only
-    // the batch MEAN that enters the running average is mean(z_l) + b_l (tl_bn_finalize_kernel). It is more than a saved
-    // add: the folded form a z + c loses accuracy with |mean| / std of a channel, and a bias is pure mean.
-    for (int l = 0; l < nlayers; ++l) {
-        const pn2_bn_layer &L = layers[l];
-        const GemmShape g = gemm_shape(rows, L.cin, L.cout, o);
-        const bool last = l == nlayers - 1;
-        if (l == 0 && fp) {
-            // layer 1 of an FP level once per KNOWN point (train_mlp_fp.hip): Q = points2 W1a over the b m known points,
-            // z_1 = points1 W1b over the rows, then one pass adds the interpolated rows of Q and sums the batch moments
-            float *Q = reinterpret_cast<float *>(base + pl.l1p);
-            const float *p2 = fp->points2, *p1 = fp->points1;
-            if (fp->pad2()) {
-                float *d = reinterpret_cast<float *>(base + pl.fp2);
-                if (int rc = fp_launch_pad(fp->points2, fp->bm, fp->c2, fp->mp, fp->c2p, d, st)) return rc;
-                p2 = d;
-            }
-            if (fp->pad1()) {
-                float *d = reinterpret_cast<float *>(base + pl.fp1);
-                if (int rc = fp_launch_pad(fp->points1, rows, fp->c1, rows, fp->c1p, d, st)) return rc;
-                p1 = d;
-            }
-            {
-                TlGemm q;                                         // no moments: Q is not z_1
-                memset(&q, 0, sizeof(q));
-                q.rows = fp->mp;
-                q.A = p2;
-                q.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-                q.emode = E_STORE;
-                q.out = Q;
-                if (int rc = launch_gemm(A_PLAIN, q, gemm_shape(fp->mp, fp->c2p, L.cout, o), st, o)) return rc;
-            }
-            if (fp->c1 > 0) {
-                TlGemm q;
-                memset(&q, 0, sizeof(q));
-                q.rows = rows;
-                q.A = p1;
-                q.wpacked = reinterpret_cast<const u32x4 *>(base + pl.fpw);
-                q.emode = E_STORE;
-                q.out = L.z;
-                if (int rc = launch_gemm(A_PLAIN, q, gemm_shape(rows, fp->c1p, L.cout, o), st, o)) return rc;
-            }
-            int np = 0;
-            if (int rc = fp_launch_l1_forward(rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z, fp->c1 > 0,
-                                              reinterpret_cast<double *>(base + pl.stats[l]), kMaxParts, st, &np)) return rc;
-            if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
-                                reinterpret_cast<const double *>(base + pl.stats[l]), np, L.cout, (double)rows, L.gamma,
-                                L.beta, L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
-            if (last) {
-                const long long total4 = rows * L.cout / 4;
-                long long blocks = (total4 + 255) / 256;
-                if (blocks > 8192) blocks = 8192;
-                if (int rc = launch(tl_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, total4, L.cout, (const float *)L.z,
-                                    (const float *)L.save, out)) return rc;
-            }
-            continue;
-        }
-        if (l == 0 && per_point) {
-            // layer 1 once per point (tl_l1_forward_kernel): P = points . W1f over the b n points, then one pass over the rows
-            const TlGather gt = make_gather(group);
-            const long long bn = (long long)gd.b * gd.n;
-            float *P = reinterpret_cast<float *>(base + pl.l1p);
-            {
-                const GemmShape gp = gemm_shape(bn, gt.cfeat, L.cout, o);
-                TlGemm q;
-                memset(&q, 0, sizeof(q));
-                q.rows = bn;
-                q.A = group->points;
-                q.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-                q.emode = E_STORE;
-                q.out = P;
-                if (int rc = launch_gemm(A_PLAIN, q, gp, st, o)) return rc;
-            }
-            int np = 0;
-            if (int rc = launch_l1_forward(rows, gd, group, L, P, moments(l), st, &np)) return rc;
-            if (fr) continue;
-            if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
-                                reinterpret_cast<const double *>(base + pl.stats[l]), np, L.cout, (double)rows, L.gamma,
-                                L.beta, L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
-            continue;
-        }
-        if (l == 0 && coords_only) {
-            // a level without features: z_1 = b + (xyz - c) W1 in one pass on the vector units (tl_l1_forward_kernel, no P)
-            int np = 0;
-            if (int rc = launch_l1_forward(rows, gd, group, L, nullptr, moments(l), st, &np)) return rc;
-            if (fr) continue;
-            if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
-                                reinterpret_cast<const double *>(base + pl.stats[l]), np, L.cout, (double)rows, L.gamma,
-                                L.beta, L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
-            continue;
-        }
-        TlGemm p;
-        memset(&p, 0, sizeof(p));
-        p.rows = rows;
-        int amode;
-        if (l == 0 && group) { amode = A_GATHER; p.g = make_gather(group); }
-        else if (l == 0) { amode = A_PLAIN; p.A = x; }
-        else { amode = A_RELU; p.A = layers[l - 1].z; p.p0 = layers[l - 1].save + 2 * layers[l - 1].cout; p.p1 = layers[l - 1].save + 3 * layers[l - 1].cout; }
-        p.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-        p.bias = nullptr;                                        // see the comment above the loop
-        p.emode = (last && pool_rows && want_max) ? E_POOL : E_STORE;
-        p.out = (last && !keep_top) ? nullptr : L.z;              // the pooled top layer of a large level is never written
-        p.stats = moments(l);
-        p.nostats = fr ? 1 : 0;                                   // the GEMM's compile-time "no statistics" variant
-        if (p.emode == E_POOL) {
-            const long long parts = rows / (pool_rows == 16 ? 16 : 32);
-            float *pp = reinterpret_cast<float *>(base + pl.pool);
-            p.pmax = pp;
-            p.pamax = reinterpret_cast<int *>(pp + parts * L.cout);
-            p.pool_gamma = L.gamma;
-            p.prow = pool_rows == 16 ? 16 : 32;
-        }
-        int nparts = 0;
-        if (fold) p.fin = fin_forward(L, rows, p.stats, tickets + l);
-        if (int rc = launch_gemm(amode, p, g, st, o, &nparts)) return rc;
-        if (!fold && !fr)
-            if (int rc = launch(tl_bn_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
-                                reinterpret_cast<const double *>(base + pl.stats[l]), nparts, L.cout, (double)rows, L.gamma, L.beta,
-                                L.running_mean, L.running_var, L.momentum, L.eps, L.save, L.bias, L.running_var_biased)) return rc;
-        // max_and_avg: the max half as pooling 0 computes it, into the workspace behind the plan; the average kernel places it
-        float *maxv = pooling == 3 ? reinterpret_cast<float *>(base + pl.total) : nullptr;
-        if (last && pool_rows && want_max) {
-            const long long groups = rows / pool_rows;
-            const int prow = pool_rows == 16 ? 16 : 32;
-            long long blocks = (groups * L.cout + 255) / 256;
-            if (blocks > 4096) blocks = 4096;
-            if (int rc = launch(tl_pool_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, groups, L.cout, pool_rows / prow,
-                                prow, (const float *)p.pmax, (const int *)p.pamax, (const float *)L.gamma,
-                                (const float *)L.save, maxv ? maxv : out, argsel, zsel)) return rc;
-        }
-        if (last && pool_rows && pooling != 0) {
-            const long long groups = rows / pool_rows;
-            if (pooling == 2) {
-                if (int rc = launch(tl_pool_weights_kernel, dim3((unsigned)((groups + 3) / 4)), dim3(256), 0, st, groups, pool_rows,
-                                    group->n, group->m, group->xyz, group->new_xyz, group->idx, pool_w)) return rc;
-            }
-            long long blocks = (groups * (L.cout / 4) + 255) / 256;
-            if (blocks > 8192) blocks = 8192;
-            if (int rc = launch(tl_pool_avg_kernel, dim3((unsigned)blocks), dim3(256), 0, st, groups, pool_rows, L.cout, (const float *)L.z,
-                                (const float *)L.save, (const float *)(pooling == 2 ? pool_w : nullptr), (const float *)maxv, out)) return rc;
-        } else if (last && !pool_rows) {
-            const long long total4 = rows * L.cout / 4;
-            long long blocks = (total4 + 255) / 256;
-            if (blocks > 8192) blocks = 8192;
-            if (int rc = launch(tl_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, total4, L.cout, (const float *)L.z,
-                                (const float *)L.save, out)) return rc;
-        }
-    }
-    return PN2_OK;
-}
-
 extern "C" int pn2_mlp_train_forward_ex(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
                                         const float *x, int pool_rows, float *out, int *argsel, float *zsel, void *ws,
                                         const pn2_train_opts *opts, void *stream)
 {
-    return tl_train_forward(rows, nlayers, layers, group, x, pool_rows, 0, out, argsel, zsel, nullptr, ws, opts, stream);
+    return pn2::tl_train_forward(pn2::max_call(rows, nlayers, layers, group, x, pool_rows, out, argsel, zsel, ws, opts, stream));
 }
 
 extern "C" int pn2_mlp_train_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
@@ -2953,593 +3571,19 @@ extern "C" int pn2_mlp_train_backward(long long rows, int nlayers, const pn2_bn_
                                      grad_points, reproducible, ws, nullptr, stream);
 }
 
-// pooling 1-3 (pn2_mlp_train_backward_pool): the averaged top layer is an UNPOOLED one from here on -- its dense gradient
-// (tl_pool_top_grad_kernel) enters the passes of the FP levels' top layer, and everything below runs unchanged
-static int tl_train_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
-                             int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel, const float *pool_w,
-                             const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points, int reproducible,
-                             void *ws, const pn2_train_opts *opts, void *stream, const pn2::FpL1 *fp = nullptr,
-                             float *grad_xyz = nullptr, float *grad_new_xyz = nullptr, const pn2::TlFrozen *fr = nullptr)
-{
-    using namespace pn2;
-    const Opts o = opts_of(opts);
-    const int cus = device_cus();
-    int widths[9];
-    if (!layers_ok(rows, nlayers, layers, group, widths, fp)) return PN2_E_ARG;
-    if (fr && fp) return PN2_E_ARG;
-    const bool want_xyz = group && grad_xyz;            // the coordinate gradients (pn2_mlp_train_backward_xyz, train_mlp_xyz.hip)
-    const bool want_max = pooling == 0 || pooling == 3;
-    if ((!group && !x && !fp) || !out || !grad_out || !ws || (pool_rows && want_max && (!argsel || !zsel)) || (pooling == 2 && !pool_w))
-        return PN2_E_NULL;
-    const int avg_rows = pooling ? pool_rows : 0;       // > 0: the group size of the averaged top layer
-    if (pooling && (!group || avg_rows <= 0 || rows % avg_rows || avg_rows != group->nsample)) return PN2_E_ARG;
-    if (pooling) pool_rows = 0;
-    // frozen statistics: a layer whose four gradient slots are all NULL wants no parameter gradient -- no weight-gradient pass,
-    // no per-channel sums (batch statistics cannot allow that: dz itself needs the sums)
-    bool skip[8] = {false, false, false, false, false, false, false, false};
-    for (int l = 0; l < nlayers; ++l) {
-        const bool all3 = layers[l].grad_weight && layers[l].grad_gamma && layers[l].grad_beta;
-        const bool any = layers[l].grad_weight || layers[l].grad_gamma || layers[l].grad_beta || (fr && fr->grad_bias && fr->grad_bias[l]);
-        if (fr && !any) { skip[l] = true; continue; }
-        if (!all3) return PN2_E_NULL;
-    }
-    TlPlan pl;
-    GroupDims gd;
-    if (group) gd = group_dims(group);
-    if (!tl_plan(rows, nlayers, widths, pool_rows, 1, pl, group ? &gd : nullptr, o, fp)) return PN2_E_ARG;
-    XyzPlan xp;
-    memset(&xp, 0, sizeof(xp));
-    if (want_xyz && !xyz_plan(pl, rows, nlayers, widths, gd, o, xp)) return PN2_E_ARG;
-    hipStream_t st = as_stream(stream);
-    char *base = static_cast<char *>(ws);
-    const bool per_point = group && l1_per_point(nlayers, widths, &gd, o);
-    const bool coords_only = group && l1_coords_only(nlayers, widths, &gd, o);
-    const bool want_dx = fp ? (fp->grad_points2 || fp->grad_points1)
-                       : group ? ((per_point ? grad_points : grad_feat_rows) && group->points && group->cfeat > 0) : grad_x != nullptr;
-    const bool ztop = !top_stored(rows, nlayers, widths, pool_rows, o);     // pooled top layer without z_L (tl_top_mats_kernel)
-    for (int l = 0; l < nlayers; ++l)
-        if (!layers[l].z && !(ztop && l == nlayers - 1)) return PN2_E_NULL;
-    // Which layers run their data gradient inside the weight-gradient pass (one pass over the layer's activations instead of
-    // two, tl_wgrad_kernel<.., DY>): decided here, once, for the packing below and the launches
-    // frozen statistics: the chain stops at the lowest layer that still needs something (lo; 0 otherwise), and a layer takes
-    // a data gradient from above only where something below it is wanted
-    int lo = 0;
-    if (fr)
-        while (lo < nlayers - 1 && skip[lo] && !(lo == 0 && (want_dx || want_xyz))) ++lo;
-    auto below = [&](int l) { return l > lo || (l == 0 && want_dx); };
-    auto sums_of = [&](int l) -> double * { return skip[l] ? nullptr : reinterpret_cast<double *>(base + pl.stats[l]); };
-    FuseShape fz[8];
-    WgradShape wz[8];
-    memset(fz, 0, sizeof(fz));
-    for (int l = lo; l < nlayers; ++l) {
-        const pn2_bn_layer &L = layers[l];
-        if (skip[l] || (l > 0 && !below(l))) continue;              // no weight-gradient pass to fuse into / no data gradient to fuse
-        if (ztop && l == nlayers - 1) {
-            // (the z-free pooled top layer in one pass is correct and tested, but not yet faster than its three kernels -- 690 vs
-            // 590 us at the metric shape: two waves carry the whole data gradient, 72 MFMAs on transposed reads each -- so the
-            // size rule leaves it off; fuse_wgrad = PN2_OPT_ON forces it)
-            wz[l] = wgrad_shape(rows, L.cin, top_cols(L.cin, L.cout), false, cus, PN2_OPT_OFF);
-            if (o.fuse_wgrad == PN2_OPT_ON) fz[l] = fuse_shape(rows, wz[l], tiles(L.cout) * 32 + L.cin, L.cin, o, false);
-        } else if (!(l == 0 && (group || fp || !want_dx))) {
-            wz[l] = wgrad_shape(rows, L.cin, L.cout, false, cus, PN2_OPT_OFF);
-            fz[l] = fuse_shape(rows, wz[l], L.cout, L.cin, o);
-        }
-        if (fz[l].ok) { wz[l].lds_dy = fz[l].lds; wz[l].upw = fz[l].upw; }
-    }
-    bool ident_written = false;
-    unsigned *tickets = reinterpret_cast<unsigned *>(base + pl.tickets);
-    bool fold = false;
-    {
-        TlPackJobs jobs;                                          // W_l^T of every data-gradient GEMM, one launch
-        memset(&jobs, 0, sizeof(jobs));
-        int nj = 0;
-        for (int l = lo; l < nlayers; ++l) {
-            const pn2_bn_layer &L = layers[l];
-            if (below(l) && !(ztop && l == nlayers - 1)) {               // dy_{l-1} = dz_l . W_l^T
-                if (fz[l].ok) {                                   // every output tile in ONE slab (the fused pass keeps W^T resident)
-                    GemmShape gg;
-                    memset(&gg, 0, sizeof(gg));
-                    gg.K = L.cout; gg.N = L.cin; gg.tk = fz[l].tk; gg.tn = fz[l].nt; gg.ns = fz[l].nt; gg.slabs = 1;
-                    add_pack_job(jobs, nj, L.weight, L.w_stride_n, L.w_stride_k, gg, base + pl.pack[l]);
-                } else if (l == 0 && fp) {                        // W1a^T, W1b^T: the data gradients of points2 / points1
-                    if (fp->grad_points2)
-                        add_pack_job(jobs, nj, L.weight, L.w_stride_n, L.w_stride_k, gemm_shape(fp->mp, L.cout, fp->c2, o), base + pl.pack[l]);
-                    if (fp->grad_points1 && fp->c1 > 0)
-                        add_pack_job(jobs, nj, L.weight + (long long)fp->c2 * L.w_stride_k, L.w_stride_n, L.w_stride_k,
-                                     gemm_shape(rows, L.cout, fp->c1, o), base + pl.fpw);
-                } else if (l == 0 && group) {
-                    // layer 1 of a grouped level: only the FEATURE rows of W_1 (the grouped xyz takes no gradient here);
-                    // per point: the same tiles, for the GEMM over the b n points
-                    const TlGather gt = make_gather(group);
-                    add_pack_job(jobs, nj, L.weight + gt.feat_off * L.w_stride_k, L.w_stride_n, L.w_stride_k,
-                                 gemm_shape(per_point ? (long long)gd.b * gd.n : rows, L.cout, gt.cfeat, o), base + pl.pack[l]);
-                } else {
-                    add_pack_job(jobs, nj, L.weight, L.w_stride_n, L.w_stride_k, gemm_shape(rows, L.cout, L.cin, o), base + pl.pack[l]);
-                }
-            }
-        }
-        if ((per_point || fp) && nj > 0) {                        // the identity coefficients of layer 1's per-point weight gradient
-            jobs.ident = reinterpret_cast<float *>(base + pl.l1coef);
-            jobs.ident_c = layers[0].cout;
-        }
-        ident_written = jobs.ident != nullptr;
-        fold = fold_wanted(o) && nj > 0 && !fr;                   // (the pack launch zeroes the tickets)
-        if (fold) jobs.tickets = tickets;
-        if (int rc = launch_pack_jobs(jobs, nj, st)) return rc;
-    }
-    if (fr) {                                                     // dz = a dy for every layer, known before the first pass
-        float *cf[8];
-        for (int l = 0; l < nlayers; ++l) cf[l] = reinterpret_cast<float *>(base + pl.coef[l]);
-        if (int rc = frozen_launch_coef(nlayers, layers, cf, st)) return rc;
-    }
-    bool folded[8] = {false, false, false, false, false, false, false, false};     // layers whose backward finalisation ran inside the pass above
-    // the data-gradient GEMM that sums (dy, dy z) of layer l - 1 also turns the sums into that layer's gradients and coefficients
-    auto fold_below = [&](TlGemm &q, int l) {
-        if (!fold || l < 1) return;
-        q.fin = fin_backward(layers[l - 1], rows, q.stats, reinterpret_cast<float *>(base + pl.coef[l - 1]), tickets + (l - 1));
-        folded[l - 1] = true;
-    };
-    float *ga = reinterpret_cast<float *>(base + pl.ga), *gb = reinterpret_cast<float *>(base + pl.gb);
-    float *gq = reinterpret_cast<float *>(base + pl.gq);
-    const pn2_bn_layer &T = layers[nlayers - 1];
-    int nparts[8];                                      // rows of each layer's partial-sum array
-    // top of the stack: dy_L and its two column sums
-    if (avg_rows) {
-        long long gy = (rows + 255) / 256;
-        if (gy > kMaxParts) gy = kMaxParts;
-        nparts[nlayers - 1] = (int)gy;
-        if (int rc = launch(tl_pool_top_grad_kernel, dim3((unsigned)((T.cout + 63) / 64), (unsigned)gy), dim3(256), 0, st, rows, avg_rows,
-                            T.cout, grad_out, (const float *)T.z, (const float *)T.save, pool_w, pooling == 3 ? argsel : nullptr, ga,
-                            sums_of(nlayers - 1))) return rc;
-    } else if (pool_rows) {
-        const long long groups = rows / pool_rows;
-        long long gy = (groups + 63) / 64;
-        if (gy > kMaxParts) gy = kMaxParts;
-        nparts[nlayers - 1] = (int)gy;
-        if (int rc = launch(tl_pool_grad_kernel, dim3((unsigned)((T.cout + 63) / 64), (unsigned)gy), dim3(256), 0, st, groups, T.cout, out,
-                            grad_out, zsel, gq, sums_of(nlayers - 1))) return rc;
-    } else {
-        long long gy = (rows + 255) / 256;
-        if (gy > kMaxParts) gy = kMaxParts;
-        nparts[nlayers - 1] = (int)gy;
-        if (int rc = launch(tl_top_grad_kernel, dim3((unsigned)((T.cout + 63) / 64), (unsigned)gy), dim3(256), 0, st, rows, T.cout, out,
-                            grad_out, (const float *)T.z, ga, sums_of(nlayers - 1))) return rc;
-    }
-    float *gcur = ga, *gnext = gb;                      // dy of the current layer (dense case) / of the layer below
-    // The coordinate gradients, from layer 1's dz_1 = s G - c0 - c1 Z (cf == nullptr: G is dz_1 itself; sel: the pooled
-    // single-layer stack, G = gq): g_r = dz_1[r] . W1x^T per row, grad_new_xyz = minus the group sums, grad_xyz = the rows
-    // scattered onto the points -- or, where backward has dz_1 on the points already (S, layer 1 per point), S . W1x^T
-    auto xyz_pass = [&](const float *G, const float *Z, const float *cf, const int *sel, const float *S) -> int {
-        const pn2_bn_layer &L1 = layers[0];
-        const float *wx = L1.weight + make_gather(group).xyz_off * L1.w_stride_k;
-        if (!group->idx)                                  // group_all: row k of cloud i IS point k, no centroid
-            return xyz_launch_rows(rows, L1.cout, G, Z, cf, sel, gd.nsample, wx, L1.w_stride_k, L1.w_stride_n, grad_xyz, st);
-        float *g3 = reinterpret_cast<float *>(base + xp.g);
-        if (grad_new_xyz || !S) {
-            if (int rc = xyz_launch_rows(rows, L1.cout, G, Z, cf, sel, gd.nsample, wx, L1.w_stride_k, L1.w_stride_n, g3, st)) return rc;
-            if (grad_new_xyz)
-                if (int rc = xyz_launch_centroids(rows / gd.nsample, gd.nsample, g3, grad_new_xyz, st)) return rc;
-        }
-        if (S)
-            return xyz_launch_rows((long long)gd.b * gd.n, L1.cout, S, nullptr, nullptr, nullptr, 1, wx, L1.w_stride_k, L1.w_stride_n,
-                                   grad_xyz, st);
-        return pn2_group_point_grad_seg(gd.b, gd.n, 3, gd.m, gd.nsample, g3, group->idx, grad_xyz, base + xp.seg, reproducible, stream);
-    };
-    int l1_moment_parts = 0;                            // > 0: layer 1's weight gradient comes from moments (TlWgrad::l1x)
-    // weight-gradient launches on a helper stream beside the data-gradient chain (SideStream above): OPT-IN. Measured
-    // (scripts/lab_ab.sh side_stream, profiles/r04/README.md): every fork / join is a cross-queue dependency of ~10 us on this
-    // runtime, three pairs per level -- sem_seg SA2 280 -> 330 us, SA4 250 -> 305, FP4 335 -> 380; only the group_all level
-    // (three wide layers over 4,096 rows) gains, 431 -> 379 us. The size rule therefore never switches it on.
-    SideStream sd;
-    if (int rc = sd.init(st, o.side_stream == PN2_OPT_ON)) return rc;
-    hipStream_t ss = sd.get();
-    for (int l = nlayers - 1; l >= lo; --l) {
-        const pn2_bn_layer &L = layers[l];
-        float *coef = reinterpret_cast<float *>(base + pl.coef[l]);
-        if (!folded[l] && !fr)
-            if (int rc = launch(tl_bn_backward_finalize_kernel, dim3((unsigned)((L.cout + 7) / 8)), dim3(256), 0, st,
-                                reinterpret_cast<const double *>(base + pl.stats[l]), nparts[l], L.cout, (double)rows, L.gamma,
-                                (const float *)L.save, L.grad_gamma, L.grad_beta, coef, L.grad_accumulate)) return rc;
-        if (int rc = sd.join()) return rc;                          // the helper's reads of the dy buffer this layer's data gradient overwrites
-        const bool pooled_top = pool_rows && l == nlayers - 1;
-        if (pooled_top && ztop) {
-            // ---- the pooled top layer in terms of its input h = relu(a z_{l-1} + c): see tl_top_mats_kernel
-            const pn2_bn_layer &D = layers[l - 1];
-            const int K = L.cin, NF = L.cout, tf = tiles(NF), NFp = tf * 32, ld = top_cols(K, NF);
-            float *wp = reinterpret_cast<float *>(base + pl.topw), *rowc = wp + (size_t)(NFp + K) * K;
-            double *sf = reinterpret_cast<double *>(base + pl.topsf);
-            {
-                long long blocks = ((long long)(NFp + K + 1) * K + 255) / 256;
-                if (blocks > 4096) blocks = 4096;
-                if (int rc = launch(tl_top_mats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, L.weight, L.w_stride_k, L.w_stride_n,
-                                    K, NF, NFp, (const float *)coef, (const float *)nullptr, wp, rowc)) return rc;    // z_L = h W: no bias term
-            }
-            if (fz[l].ok) {
-                // ---- ONE pass over z_{l-1}: the routed gradient and h as operand tiles of the block image serve the weight
-                // gradient (S, Gram matrix, column sums: tl_top_wgrad_fix_kernel combines them) AND the data gradient
-                // dy_{l-1} = [s dy routed | h] . [W^T ; -M] - r, masked by the layer below (as separate kernels z_{l-1} crossed
-                // HBM in the data-gradient GEMM, in tl_top_s_kernel and in the Gram pass)
-                GemmShape gg;
-                memset(&gg, 0, sizeof(gg));
-                gg.K = NFp + K; gg.N = K; gg.tk = fz[l].tk; gg.tn = fz[l].nt; gg.ns = fz[l].nt; gg.slabs = 1;
-                if (int rc = launch_pack(wp, K, 1, gg, base + pl.pack[l], st)) return rc;
-                TlWgrad w;
-                memset(&w, 0, sizeof(w));
-                w.rows = rows;
-                w.KI = K;
-                w.amode = A_RELU; w.A = D.z; w.pa = D.save + 2 * D.cout; w.pc = D.save + 3 * D.cout;
-                w.dmode = A_FILL;
-                w.NO = ld; w.tf = tf; w.NF = NF;
-                w.G = gq; w.argsel = argsel; w.coef = coef; w.group_rows = pool_rows;
-                w.partial = reinterpret_cast<float *>(base + pl.partial); w.partial_cap = pl.partial_cap;
-                w.xshare = 1;                                     // one slab: the "h again" tiles are the first operand's
-                w.dy_w = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-                w.xr_off = (int)fz[l].xr_off;
-                w.dy_tk = fz[l].tk; w.dy_nt = fz[l].nt; w.dy_tf = tf; w.single = fz[l].single;
-                w.dy_cols = K; w.dy_pitch = K;
-                w.dy_out = gnext;
-                w.dy_zprev = D.z; w.dy_ea = D.save + 2 * D.cout; w.dy_ec = D.save + 3 * D.cout;
-                w.dy_bias = rowc;
-                w.dy_stats = sums_of(l - 1);
-                w.dy_nt_store = o.nt == PN2_OPT_OFF ? 0 : o.nt == PN2_OPT_ON ? 1 : (size_t)rows * K * sizeof(float) >= ((size_t)128 << 20);
-                if (int rc = launch_wgrad(w, wz[l], reinterpret_cast<float *>(base + pl.partial2), L, st, sf)) return rc;
-                long long blocks = ((long long)K * NF + 255) / 256;
-                if (blocks > 4096) blocks = 4096;
-                if (int rc = launch(tl_top_wgrad_fix_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const double *)sf, ld, K, NF,
-                                    tf * 32, tf * 32 + tiles(K) * 32, L.weight, L.w_stride_k, L.w_stride_n, (const float *)coef,
-                                    (const float *)nullptr, L.grad_weight, (const double *)nullptr, L.grad_accumulate)) return rc;
-                nparts[l - 1] = (int)wz[l].gridx;
-                float *tmp = gcur; gcur = gnext; gnext = tmp;
-                continue;
-            }
-            {
-                // weight gradient: the routed part S on the vector units (tl_top_s_kernel) when its shape allows, the Gram
-                // matrix h^T h and the column sums of h from the dense kernel, combined by tl_top_wgrad_fix_kernel;
-                // data gradient: the GEMM over [routed gradient | h]. The dense kernel and the GEMM are independent passes over
-                // z_{l-1}: one launch for both where the pair has a kernel (tl_pair_kernel)
-                const TopSShape ts = top_s_shape(rows, pool_rows, K, NF, o);
-                double *s64 = ts.ok ? reinterpret_cast<double *>(base + pl.tops64) : nullptr;
-                const bool wg = !skip[l];                          // (frozen statistics: a layer without parameter gradients)
-                if (int rc = sd.fork()) return rc;                 // the weight gradient's kernels beside the data gradient below
-                if (ts.ok && wg) {
-                    TlTopS q;
-                    memset(&q, 0, sizeof(q));
-                    q.groups = rows / pool_rows; q.ns = pool_rows; q.K = K; q.NF = NF;
-                    q.z = D.z; q.pa = D.save + 2 * D.cout; q.pc = D.save + 3 * D.cout;
-                    q.gq = gq; q.argsel = argsel; q.coef = coef;
-                    q.partial = reinterpret_cast<float *>(base + pl.tops_part);
-                    if (int rc = launch_top_s(q, ts, reinterpret_cast<float *>(base + pl.tops_part2), s64, ss)) return rc;
-                }
-                const int tfw = ts.ok ? 0 : tf, ldw = ts.ok ? top_cols(K, 0) : ld;       // operand tiles of the dense kernel
-                TlWgrad w;
-                memset(&w, 0, sizeof(w));
-                w.rows = rows;
-                w.KI = K;
-                w.amode = A_RELU; w.A = D.z; w.pa = D.save + 2 * D.cout; w.pc = D.save + 3 * D.cout;
-                w.dmode = A_FILL;
-                w.NO = ldw; w.tf = tfw; w.NF = ts.ok ? 0 : NF;
-                w.G = gq; w.argsel = argsel; w.coef = coef; w.group_rows = pool_rows;
-                w.partial = reinterpret_cast<float *>(base + pl.partial); w.partial_cap = pl.partial_cap;
-                const WgradShape ws_ = wgrad_shape(rows, K, ldw, false, cus, o.wgrad_two_per_cu);
-                w.xshare = ws_.uslabs == 1;
-                const GemmShape g = gemm_shape(rows, NFp + K, K, o);
-                if (int rc = launch_pack(wp, K, 1, g, base + pl.pack[l], st)) return rc;
-                TlGemm p;
-                memset(&p, 0, sizeof(p));
-                p.rows = rows;
-                p.tk0 = tf; p.K0 = NF; p.K1 = K;
-                p.G = gq; p.argsel = argsel; p.p0 = coef; p.group_rows = pool_rows;
-                p.A2 = D.z; p.q0 = D.save + 2 * D.cout; p.q1 = D.save + 3 * D.cout;
-                p.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-                p.bias = rowc;
-                p.emode = E_MASK;
-                p.out = gnext;
-                p.zprev = D.z; p.ea = D.save + 2 * D.cout; p.ec = D.save + 3 * D.cout;
-                p.stats = sums_of(l - 1);
-                p.nostats = (fr && !p.stats) ? 1 : 0;
-                fold_below(p, l);
-                int np = 0, rc = kNoPair;
-                if (wg && pair_wanted(rows, o)) rc = launch_pair(A_FILL, p, g, w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st, o, &np, sf);
-                if (rc == kNoPair) {
-                    if (wg && (rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, ss, sf))) return rc;
-                    rc = launch_gemm(A_FILL, p, g, st, o, &np);
-                }
-                if (rc) return rc;
-                nparts[l - 1] = np;
-                long long blocks = ((long long)K * NF + 255) / 256;
-                if (blocks > 4096) blocks = 4096;
-                if (wg) {
-                    if (int rc2 = launch(tl_top_wgrad_fix_kernel, dim3((unsigned)blocks), dim3(256), 0, ss, (const double *)sf, ldw, K, NF,
-                                         tfw * 32, tfw * 32 + tiles(K) * 32, L.weight, L.w_stride_k, L.w_stride_n, (const float *)coef,
-                                         (const float *)nullptr, L.grad_weight, (const double *)s64, L.grad_accumulate)) return rc2;
-                }
-            }
-            float *tmp = gcur; gcur = gnext; gnext = tmp;
-            continue;
-        }
-        if (l == 0 && coords_only && !(gd.cfeat > 0 && want_dx)) {
-            // ---- a level without features (or with a few whose gradient nobody wants -- the network's input normals): the
-            // first layer's weight gradient on the vector units
-            if (l1_moment_parts) {                                // ... from x^T dy_1 of the pass above and the moments of x
-                const TlGather gt = make_gather(group);
-                if (int rc = launch(tl_l1_wx_combine_kernel, dim3((unsigned)((3 * L.cout + 7) / 8)), dim3(256), 0, st,
-                                    reinterpret_cast<const double *>(base + pl.l1mom), l1_moment_parts,
-                                    reinterpret_cast<const double *>(base + pl.l1a), nparts[0], L.cout, L.cout, (const float *)coef,
-                                    L.weight + gt.xyz_off * L.w_stride_k, L.w_stride_k, L.w_stride_n,
-                                    L.grad_weight + gt.xyz_off * L.w_stride_k, L.grad_accumulate)) return rc;
-                break;
-            }
-            // ... in one pass over dy_1 and z_1
-            if (!skip[l])
-                if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, reinterpret_cast<float *>(base + pl.l1part), false, st)) return rc;
-            if (want_xyz)
-                if (int rc = xyz_pass(gcur, L.z, coef, nullptr, nullptr)) return rc;
-            break;
-        }
-        if (l == 0 && fp) {
-            // ---- layer 1 of an FP level per KNOWN point (train_mlp_fp.hip): dz_1 in place, its interpolation gradient S onto
-            // the known points, then each half of W_1 -- a weight gradient and a data gradient over its own rows
-            float *S = reinterpret_cast<float *>(base + pl.l1p), *ident = reinterpret_cast<float *>(base + pl.l1coef);
-            float *part2 = reinterpret_cast<float *>(base + pl.partial2);
-            if (int rc = fp_launch_l1_dz(rows, L.cout, L.z, gcur, coef, st)) return rc;
-            if (int rc = pn2_three_interpolate_grad_seg(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx, fp->weight, S, base + pl.l1seg,
-                                                        reproducible, stream)) return rc;
-            if (fp->mp > fp->bm)                                  // the padding rows of S meet the zero rows of points2's copy
-                if (int rc = clear_async(S + fp->bm * L.cout, sizeof(float) * (size_t)(fp->mp - fp->bm) * L.cout, st)) return rc;
-            if (!ident_written)
-                if (int rc = launch(tl_identity_coef_kernel, dim3((unsigned)((3 * L.cout + 127) / 128)), dim3(128), 0, st, L.cout, ident)) return rc;
-            const float *p2 = fp->points2, *p1 = fp->points1;
-            if (fp->pad2()) {
-                float *d = reinterpret_cast<float *>(base + pl.fp2);
-                if (int rc = fp_launch_pad(fp->points2, fp->bm, fp->c2, fp->mp, fp->c2p, d, st)) return rc;
-                p2 = d;
-            }
-            if (fp->pad1()) {
-                float *d = reinterpret_cast<float *>(base + pl.fp1);
-                if (int rc = fp_launch_pad(fp->points1, rows, fp->c1, rows, fp->c1p, d, st)) return rc;
-                p1 = d;
-            }
-            // dW_half = A^T D (rows kc of the weight gradient from row koff) and, when wanted, gout = D W_half^T
-            auto half = [&](long long hr, int kp, int kc, const float *A, const float *D, size_t pack, float *gout, int koff)
-                __attribute__((always_inline)) -> int {
-                TlWgrad w;
-                memset(&w, 0, sizeof(w));
-                w.rows = hr; w.KI = kp; w.kout = kc; w.amode = A_PLAIN; w.A = A;
-                w.dmode = A_DZ; w.NO = L.cout; w.Z = D; w.G = D; w.coef = ident;
-                w.partial = reinterpret_cast<float *>(base + pl.partial); w.partial_cap = pl.partial_cap;
-                pn2_bn_layer Lh = L;
-                Lh.grad_weight = L.grad_weight + (long long)koff * L.w_stride_k;
-                const WgradShape ws_ = wgrad_shape(hr, kp, L.cout, false, cus, o.wgrad_two_per_cu);
-                if (!gout) return launch_wgrad(w, ws_, part2, Lh, st);
-                const GemmShape g = gemm_shape(hr, L.cout, kc, o);
-                TlGemm p;
-                memset(&p, 0, sizeof(p));
-                p.rows = hr;
-                p.A = D;
-                p.wpacked = reinterpret_cast<const u32x4 *>(base + pack);
-                p.emode = E_PLAIN;
-                p.out = gout; p.out_pitch = kc; p.col0 = 0; p.col1 = kc;
-                int rc = kNoPair;
-                if (pair_wanted(hr, o)) rc = launch_pair(A_PLAIN, p, g, w, ws_, part2, Lh, st, o, nullptr);
-                if (rc == kNoPair) {
-                    if ((rc = sd.fork())) return rc;
-                    if ((rc = launch_wgrad(w, ws_, part2, Lh, ss))) return rc;
-                    rc = launch_gemm(A_PLAIN, p, g, st, o);
-                }
-                return rc;
-            };
-            float *g2 = (fp->grad_points2 && fp->gstage2()) ? reinterpret_cast<float *>(base + pl.fpg2) : fp->grad_points2;
-            if (int rc = half(fp->mp, fp->c2p, fp->c2, p2, S, pl.pack[l], g2, 0)) return rc;
-            if (g2 && g2 != fp->grad_points2)
-                if (int rc = fp_launch_pad(g2, fp->bm, fp->c2, fp->bm, fp->c2, fp->grad_points2, st)) return rc;
-            if (fp->c1 > 0)
-                if (int rc = half(rows, fp->c1p, fp->c1, p1, gcur, pl.fpw, fp->grad_points1, fp->c2)) return rc;
-            break;
-        }
-        if (l == 0 && per_point) {
-            // ---- layer 1 once per point (see tl_l1_forward_kernel): dz_1 and dW1x in one pass over the rows, the scatter of
-            // dz_1 onto the points, then two GEMMs over the b n points
-            const TlGather gt = make_gather(group);
-            const long long bn = (long long)gd.b * gd.n;
-            float *S = reinterpret_cast<float *>(base + pl.l1p), *part = reinterpret_cast<float *>(base + pl.l1part);
-            float *ident = reinterpret_cast<float *>(base + pl.l1coef);
-            if (int rc = launch_l1_dz(rows, gd, group, L, gcur, coef, part, true, st, !skip[l])) return rc;
-            if (int rc = pn2_group_point_grad_seg(gd.b, gd.n, L.cout, gd.m, gd.nsample, gcur, group->idx, S, base + pl.l1seg,
-                                                  reproducible, stream)) return rc;
-            if (want_xyz)                                         // (gcur holds dz_1 now)
-                if (int rc = xyz_pass(gcur, nullptr, nullptr, nullptr, S)) return rc;
-            if (skip[l]) {                                        // frozen statistics, no dW_1 wanted: the data gradient alone
-                if (!want_dx) break;
-                const GemmShape g = gemm_shape(bn, L.cout, gt.cfeat, o);
-                TlGemm p;
-                memset(&p, 0, sizeof(p));
-                p.rows = bn;
-                p.A = S;
-                p.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-                p.emode = E_PLAIN;
-                p.out = grad_points; p.out_pitch = gt.cfeat; p.col0 = 0; p.col1 = gt.cfeat;
-                if (int rc = launch_gemm(A_PLAIN, p, g, st, o)) return rc;
-                break;
-            }
-            if (!ident_written)
-                if (int rc = launch(tl_identity_coef_kernel, dim3((unsigned)((3 * L.cout + 127) / 128)), dim3(128), 0, st, L.cout, ident)) return rc;
-            {
-                TlWgrad w;                                        // dW1f = points^T S
-                memset(&w, 0, sizeof(w));
-                w.rows = bn; w.KI = gt.cfeat; w.amode = A_PLAIN; w.A = group->points;
-                w.dmode = A_DZ; w.NO = L.cout; w.Z = S; w.G = S; w.coef = ident;
-                w.partial = reinterpret_cast<float *>(base + pl.partial); w.partial_cap = pl.partial_cap;
-                pn2_bn_layer Lf = L;
-                Lf.grad_weight = L.grad_weight + gt.feat_off * L.w_stride_k;
-                const WgradShape ws_ = wgrad_shape(bn, gt.cfeat, L.cout, false, cus, o.wgrad_two_per_cu);
-                if (!want_dx) {
-                    if (int rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), Lf, st)) return rc;
-                    break;
-                }
-                const GemmShape g = gemm_shape(bn, L.cout, gt.cfeat, o);      // dPoints = S W1f^T: beside it, in one launch where the pair has a kernel
-                TlGemm p;
-                memset(&p, 0, sizeof(p));
-                p.rows = bn;
-                p.A = S;
-                p.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-                p.emode = E_PLAIN;
-                p.out = grad_points; p.out_pitch = gt.cfeat; p.col0 = 0; p.col1 = gt.cfeat;
-                int rc = kNoPair;
-                if (pair_wanted(rows, o)) rc = launch_pair(A_PLAIN, p, g, w, ws_, reinterpret_cast<float *>(base + pl.partial2), Lf, st, o, nullptr);
-                if (rc == kNoPair) {
-                    if ((rc = sd.fork())) return rc;
-                    if ((rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), Lf, ss))) return rc;
-                    rc = launch_gemm(A_PLAIN, p, g, st, o);
-                }
-                if (rc) return rc;
-            }
-            break;
-        }
-        if (l == 0 && want_xyz)                                     // the generic gathered layer 1: from (dy_1, z_1), which nothing below overwrites
-            if (int rc = xyz_pass(pooled_top ? gq : gcur, L.z, coef, pooled_top ? argsel : nullptr, nullptr)) return rc;
-        // weight gradient
-        {
-            TlWgrad w;
-            memset(&w, 0, sizeof(w));
-            w.rows = rows;
-            w.KI = L.cin;
-            if (l == 0 && group) { w.amode = A_GATHER; w.g = make_gather(group); }
-            else if (l == 0) { w.amode = A_PLAIN; w.A = x; }
-            else { w.amode = A_RELU; w.A = layers[l - 1].z; w.pa = layers[l - 1].save + 2 * layers[l - 1].cout; w.pc = layers[l - 1].save + 3 * layers[l - 1].cout; }
-            w.dmode = pooled_top ? A_DZ_POOL : A_DZ;
-            w.NO = L.cout;
-            w.Z = L.z;
-            w.G = pooled_top ? gq : gcur;
-            w.argsel = argsel;
-            w.coef = coef;
-            w.group_rows = pool_rows;
-            w.partial = reinterpret_cast<float *>(base + pl.partial); w.partial_cap = pl.partial_cap;
-            if (fz[l].ok) {
-                // ... and the data gradient in the same pass over (dy_l, z_l, z_{l-1}), see tl_wgrad_kernel
-                w.dy_w = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-                w.dy_tk = fz[l].tk; w.dy_nt = fz[l].nt; w.dy_tf = 0; w.single = fz[l].single; w.dy_acopy = fz[l].acopy;
-                w.dy_cols = L.cin; w.dy_pitch = L.cin;
-                if (l > 0) {
-                    const pn2_bn_layer &D = layers[l - 1];
-                    w.dy_out = gnext;
-                    w.dy_zprev = D.z; w.dy_ea = D.save + 2 * D.cout; w.dy_ec = D.save + 3 * D.cout;
-                    w.dy_stats = sums_of(l - 1);
-                } else {
-                    w.dy_out = grad_x;
-                }
-                w.dy_nt_store = o.nt == PN2_OPT_OFF ? 0 : o.nt == PN2_OPT_ON ? 1 : (size_t)rows * L.cin * sizeof(float) >= ((size_t)128 << 20);
-                w.xr_off = (int)fz[l].xr_off;
-                // (not with the coordinate gradients: g_r needs dy_1 row by row, so it is written and tl_l1_dz_kernel's pass runs)
-                if (l == 1 && coords_only && gd.cfeat == 0 && !pooled_top && !want_xyz && !skip[0]) {            // (a pooled two-layer stack keeps the pass over dy_1: its dz comes from the routed gradient)
-                    // the layer below takes the three centred coordinates: dy_1 is wanted only as x^T dy_1 (TlWgrad::l1x) -- never
-                    // written, and tl_l1_dz_kernel's pass over (dy_1, z_1) is replaced by nine moments of x
-                    const pn2_bn_layer &D = layers[0];
-                    TlL1 q;
-                    memset(&q, 0, sizeof(q));
-                    q.rows = rows; q.n = gd.n; q.m = gd.m; q.nsample = gd.nsample; q.C = D.cout;
-                    q.xyz = group->xyz; q.new_xyz = group->new_xyz; q.idx = group->idx;
-                    long long xb = (rows + kL1XrowsThreads - 1) / kL1XrowsThreads;
-                    if (xb > kMaxParts) xb = kMaxParts;
-                    l1_moment_parts = (int)xb;
-                    if (int rc = launch(tl_l1_xrows_kernel, dim3((unsigned)xb), dim3(kL1XrowsThreads), 0, st, q, reinterpret_cast<float4 *>(base + pl.l1xg),
-                                        reinterpret_cast<double *>(base + pl.l1mom))) return rc;
-                    w.l1x = reinterpret_cast<const float4 *>(base + pl.l1xg);
-                    w.l1a = reinterpret_cast<double *>(base + pl.l1a);
-                    w.dy_out = nullptr;
-                }
-                if (int rc = launch_wgrad(w, wz[l], reinterpret_cast<float *>(base + pl.partial2), L, st)) return rc;
-                if (l > 0) nparts[l - 1] = (int)wz[l].gridx;
-                float *tmp = gcur; gcur = gnext; gnext = tmp;
-                continue;
-            }
-            const WgradShape ws_ = wgrad_shape(rows, L.cin, L.cout, w.amode == A_GATHER, cus, o.wgrad_two_per_cu);
-            if (!below(l)) {                                       // no data gradient below this layer
-                if (!skip[l])
-                    if (int rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st)) return rc;
-            } else {
-                // data gradient: independent of the weight gradient -- ONE launch for both where the pair has a kernel
-                // (tl_pair_kernel), else the weight gradient first (on the helper stream when that is asked for)
-                const GemmShape g = (l == 0 && group) ? gemm_shape(rows, L.cout, make_gather(group).cfeat, o) : gemm_shape(rows, L.cout, L.cin, o);
-                TlGemm p;
-                memset(&p, 0, sizeof(p));
-                p.rows = rows;
-                p.A = L.z;
-                p.G = pooled_top ? gq : gcur;
-                p.argsel = argsel;
-                p.p0 = coef; p.p1 = coef + L.cout; p.p2 = coef + 2 * L.cout;
-                p.group_rows = pool_rows;
-                p.wpacked = reinterpret_cast<const u32x4 *>(base + pl.pack[l]);
-                if (l > 0) {
-                    const pn2_bn_layer &D = layers[l - 1];
-                    p.emode = E_MASK;
-                    p.out = gnext;
-                    p.zprev = D.z;
-                    p.ea = D.save + 2 * D.cout;
-                    p.ec = D.save + 3 * D.cout;
-                    p.stats = sums_of(l - 1);
-                    p.nostats = (fr && !p.stats) ? 1 : 0;
-                    fold_below(p, l);
-                } else {
-                    p.emode = E_PLAIN;
-                    if (group) {
-                        const TlGather gt = make_gather(group);
-                        p.out = grad_feat_rows; p.out_pitch = gt.cfeat; p.col0 = 0; p.col1 = gt.cfeat;
-                    } else {
-                        p.out = grad_x; p.out_pitch = L.cin; p.col0 = 0; p.col1 = L.cin;
-                    }
-                }
-                const int amode = pooled_top ? A_DZ_POOL : A_DZ;
-                int np = 0, rc = kNoPair;
-                if (skip[l]) {                                      // frozen statistics, no parameter gradient: the data gradient alone
-                    rc = launch_gemm(amode, p, g, st, o, &np);
-                } else if (pair_wanted(rows, o)) {
-                    rc = launch_pair(amode, p, g, w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, st, o, &np);
-                }
-                if (rc == kNoPair) {
-                    if ((rc = sd.fork())) return rc;               // beside the data-gradient GEMM
-                    if ((rc = launch_wgrad(w, ws_, reinterpret_cast<float *>(base + pl.partial2), L, ss))) return rc;
-                    rc = launch_gemm(amode, p, g, st, o, &np);
-                }
-                if (rc) return rc;
-                if (l > 0) nparts[l - 1] = np;
-            }
-        }
-        float *tmp = gcur; gcur = gnext; gnext = tmp;
-    }
-    if (fr) {
-        // the per-channel sums of every layer -> grad_gamma, grad_beta, grad_bias: one launch, behind the last pass (nothing waits for it)
-        FrozenSums fs[8];
-        for (int l = 0; l < nlayers; ++l) {
-            fs[l].skip = skip[l];
-            fs[l].stats = skip[l] ? nullptr : reinterpret_cast<const double *>(base + pl.stats[l]);
-            fs[l].nparts = skip[l] ? 0 : nparts[l];
-        }
-        if (int rc = frozen_launch_grads(nlayers, layers, fs, fr->grad_bias, st)) return rc;
-    }
-    return sd.join();                                              // everything of this call is ordered before what the caller enqueues next
-}
-
 extern "C" int pn2_mlp_train_backward_ex(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
                                          const float *x, int pool_rows, const float *out, const int *argsel, const float *zsel,
                                          const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points,
                                          int reproducible, void *ws, const pn2_train_opts *opts, void *stream)
 {
-    return tl_train_backward(rows, nlayers, layers, group, x, pool_rows, 0, out, argsel, zsel, nullptr, grad_out, grad_x,
-                             grad_feat_rows, grad_points, reproducible, ws, opts, stream);
+    pn2::TlCall c = pn2::max_call(rows, nlayers, layers, group, x, pool_rows, out, argsel, zsel, ws, opts, stream);
+    c.grad_out = grad_out;
+    c.grad_x = grad_x; c.grad_feat_rows = grad_feat_rows; c.grad_points = grad_points;
+    c.reproducible = reproducible;
+    return pn2::tl_train_backward(c);
 }
 
 // ---- the pooling modes of the training node (pn2_mlp_train_*_pool, include/pn2ops.h) -------------------------------------
-namespace pn2 {
-// 0 ok, else the PN2_E_* code the entries return before anything is launched
-static int pool_args(int pool_rows, int pooling, bool grouped)
-{
-    if (pooling < 0 || pooling > 3) return PN2_E_ARG;
-    if (pooling == 0) return PN2_OK;
-    if (!grouped) return PN2_E_NULL;
-    return pool_rows > 0 ? PN2_OK : PN2_E_ARG;
-}
-}  // namespace pn2
-
 extern "C" int pn2_mlp_train_pool_supported(long long rows, int nlayers, const int *widths, int pool_rows, int pooling)
 {
     pn2::TlPlan pl;
@@ -3564,11 +3608,10 @@ extern "C" int pn2_mlp_train_forward_pool(long long rows, int nlayers, const pn2
                                           int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
                                           const pn2_train_opts *opts, void *stream)
 {
-    if (int rc = pn2::pool_args(pool_rows, pooling, group != nullptr)) return rc;
-    if (pooling == 0)
-        return tl_train_forward(rows, nlayers, layers, group, nullptr, pool_rows, 0, out, argsel, zsel, nullptr, ws, opts, stream);
-    return tl_train_forward(rows, nlayers, layers, group, nullptr, pool_rows, pooling, out, pooling == 3 ? argsel : nullptr,
-                            pooling == 3 ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, ws, opts, stream);
+    if (int rc = pn2::tl_pool_args(pool_rows, pooling, group != nullptr)) return rc;
+    pn2::TlCall c = pn2::max_call(rows, nlayers, layers, group, nullptr, pool_rows, out, argsel, zsel, ws, opts, stream);
+    c.pooling = pooling; c.pool_w = pool_w;
+    return pn2::tl_train_forward(c);
 }
 
 extern "C" int pn2_mlp_train_backward_pool(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
@@ -3576,92 +3619,11 @@ extern "C" int pn2_mlp_train_backward_pool(long long rows, int nlayers, const pn
                                            const float *pool_w, const float *grad_out, float *grad_feat_rows, float *grad_points,
                                            int reproducible, void *ws, const pn2_train_opts *opts, void *stream)
 {
-    if (int rc = pn2::pool_args(pool_rows, pooling, group != nullptr)) return rc;
-    return tl_train_backward(rows, nlayers, layers, group, nullptr, pool_rows, pooling, out, pooling == 3 || pooling == 0 ? argsel : nullptr,
-                             pooling == 3 || pooling == 0 ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, grad_out, nullptr,
-                             grad_feat_rows, grad_points, reproducible, ws, opts, stream);
+    if (int rc = pn2::tl_pool_args(pool_rows, pooling, group != nullptr)) return rc;
+    pn2::TlCall c = pn2::max_call(rows, nlayers, layers, group, nullptr, pool_rows, out, argsel, zsel, ws, opts, stream);
+    c.pooling = pooling; c.pool_w = pool_w;
+    c.grad_out = grad_out;
+    c.grad_feat_rows = grad_feat_rows; c.grad_points = grad_points;
+    c.reproducible = reproducible;
+    return pn2::tl_train_backward(c);
 }
-
-// ---- the coordinate gradients (pn2_mlp_train_*_xyz: entry points, argument checks and kernels in train_mlp_xyz.hip) ----
-namespace pn2 {
-long long tl_xyz_ws_bytes(long long rows, int nlayers, const int *widths, int pool_rows, int pooling, const int *group_dims,
-                          const pn2_train_opts *opts)
-{
-    if (!widths || !group_dims || nlayers < 1 || nlayers > 8) return -1;
-    const GroupDims gd = {group_dims[0], group_dims[1], group_dims[2], group_dims[3], group_dims[4], group_dims[5]};
-    const Opts o = opts_of(opts);
-    TlPlan pl;
-    if (!tl_plan(rows, nlayers, widths, pooling ? 0 : pool_rows, 1, pl, &gd, o)) return -1;      // as pn2_mlp_train_ws_bytes_pool
-    XyzPlan xp;
-    if (!xyz_plan(pl, rows, nlayers, widths, gd, o, xp)) return -1;
-    return (long long)xp.total;
-}
-
-int tl_xyz_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, int pool_rows, int pooling,
-                    const float *out, const int *argsel, const float *zsel, const float *pool_w, const float *grad_out,
-                    float *grad_feat_rows, float *grad_points, float *grad_xyz, float *grad_new_xyz, int reproducible, void *ws,
-                    const pn2_train_opts *opts, void *stream)
-{
-    if (int rc = pool_args(pool_rows, pooling, group != nullptr)) return rc;
-    return tl_train_backward(rows, nlayers, layers, group, nullptr, pool_rows, pooling, out, pooling == 3 || pooling == 0 ? argsel : nullptr,
-                             pooling == 3 || pooling == 0 ? zsel : nullptr, nullptr, grad_out, nullptr, grad_feat_rows, grad_points,
-                             reproducible, ws, opts, stream, nullptr, grad_xyz, grad_new_xyz);
-}
-}  // namespace pn2
-
-// ---- frozen batch-norm statistics (pn2_mlp_train_*_frozen: entry points, argument checks and kernels in train_mlp_frozen.hip) ----
-namespace pn2 {
-int tl_frozen_forward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
-                      int pool_rows, int pooling, float *out, int *argsel, float *zsel, float *pool_w, void *ws,
-                      const pn2_train_opts *opts, void *stream)
-{
-    const TlFrozen fr = {nullptr};
-    const bool want_max = pooling == 0 || pooling == 3;
-    return tl_train_forward(rows, nlayers, layers, group, x, pool_rows, pooling, out, want_max ? argsel : nullptr,
-                            want_max ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, ws, opts, stream, nullptr, &fr);
-}
-
-int tl_frozen_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
-                       int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel, const float *pool_w,
-                       const float *grad_out, float *grad_x, float *grad_feat_rows, float *grad_points, float *grad_xyz,
-                       float *grad_new_xyz, float *const *grad_bias, int reproducible, void *ws, const pn2_train_opts *opts,
-                       void *stream)
-{
-    const TlFrozen fr = {grad_bias};
-    const bool want_max = pooling == 0 || pooling == 3;
-    return tl_train_backward(rows, nlayers, layers, group, x, pool_rows, pooling, out, want_max ? argsel : nullptr,
-                             want_max ? zsel : nullptr, pooling == 2 ? pool_w : nullptr, grad_out, grad_x, grad_feat_rows,
-                             grad_points, reproducible, ws, opts, stream, nullptr, grad_xyz, grad_new_xyz, &fr);
-}
-}  // namespace pn2
-
-// ---- the FP level with layer 1 per known point (pn2_mlp_train_*_fp: entry points and argument checks in train_mlp_fp.hip) ----
-namespace pn2 {
-long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts)
-{
-    const FpL1 f = fp_l1(s);
-    TlPlan pl;
-    if (!tl_plan(f.rows, nlayers, widths, 0, backward, pl, nullptr, opts_of(opts), &f)) return -1;
-    return (long long)pl.total;
-}
-
-int tl_fp_forward(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *s, float *out, float *weight, void *ws,
-                  const pn2_train_opts *opts, void *stream)
-{
-    FpL1 f = fp_l1(s);
-    f.weight_out = weight;
-    return tl_train_forward(f.rows, nlayers, layers, nullptr, nullptr, 0, 0, out, nullptr, nullptr, nullptr, ws, opts, stream, &f);
-}
-
-int tl_fp_backward(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *s, const float *weight, const float *out,
-                   const float *grad_out, float *grad_points2, float *grad_points1, int reproducible, void *ws,
-                   const pn2_train_opts *opts, void *stream)
-{
-    FpL1 f = fp_l1(s);
-    f.weight = weight;
-    f.grad_points2 = grad_points2;
-    f.grad_points1 = grad_points1;
-    return tl_train_backward(f.rows, nlayers, layers, nullptr, nullptr, 0, 0, out, nullptr, nullptr, nullptr, grad_out, nullptr,
-                             nullptr, nullptr, reproducible, ws, opts, stream, &f);
-}
-}  // namespace pn2

@@ -1,6 +1,6 @@
 // train_mlp_fp.hip -- the training node of a feature-propagation level (pointnet_fp_module, utils/pointnet_util.py:211-226)
 // with layer 1 evaluated once per KNOWN point: the entry points, their argument checks and the kernels only this level type
-// needs. The passes themselves are train_mlp.hip's (tl_fp_forward / tl_fp_backward there). gfx950.
+// needs. The passes themselves are train_mlp.hip's (tl_train_forward / tl_train_backward with TlCall::fp). gfx950.
 //
 // Layer 1 and the interpolation are both linear, so
 //     z_1 = [interp(points2), points1] W_1 = interp(points2 W1a) + points1 W1b
@@ -17,19 +17,9 @@
 // each pair in one launch where the shapes have a pair kernel. The concatenated (b, n, c2 + c1) input and its gradient are
 // never written. Widths that are no multiple of 4 enter as zero-padded copies of points2 / points1 alone, and b m known
 // points as a copy of points2 padded to a multiple of 32 rows.
-#include "pn2_device.h"
-
-#include <string.h>
+#include "train_mlp_internal.h"
 
 namespace pn2 {
-
-// ---- defined in train_mlp.hip (arguments checked here first) ----
-long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts);
-int tl_fp_forward(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *s, float *out, float *weight, void *ws,
-                  const pn2_train_opts *opts, void *stream);
-int tl_fp_backward(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *s, const float *weight, const float *out,
-                   const float *grad_out, float *grad_points2, float *grad_points1, int reproducible, void *ws,
-                   const pn2_train_opts *opts, void *stream);
 
 constexpr int kFpThreads = 512, kFpU = 4;
 
@@ -210,6 +200,27 @@ static int fp_layer_widths(int nlayers, const pn2_bn_layer *layers, int *widths)
     return PN2_OK;
 }
 
+// the checks both directions make first, in this order
+static int fp_level_args(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *src)
+{
+    if (!src) return PN2_E_NULL;
+    int widths[9];
+    if (int rc = fp_dims(src)) return rc;
+    if (int rc = fp_layer_widths(nlayers, layers, widths)) return rc;
+    return fp_widths_ok(nlayers, widths, src) ? PN2_OK : PN2_E_ARG;
+}
+
+static TlCall fp_call(int nlayers, const pn2_bn_layer *layers, const FpL1 &f, const float *out, void *ws, const pn2_train_opts *opts,
+                      void *stream)
+{
+    TlCall c{};
+    c.rows = f.rows; c.nlayers = nlayers; c.layers = layers;
+    c.has_fp = true; c.fp = f;
+    c.out = out;
+    c.ws = ws; c.opts = opts; c.stream = stream;
+    return c;
+}
+
 }  // namespace pn2
 
 extern "C" int pn2_mlp_train_fp_supported(int b, int n, int m, int c2, int c1, int nlayers, const int *widths)
@@ -233,14 +244,12 @@ extern "C" int pn2_mlp_train_forward_fp(int nlayers, const pn2_bn_layer *layers,
                                         void *ws, const pn2_train_opts *opts, void *stream)
 {
     using namespace pn2;
-    if (!src) return PN2_E_NULL;
-    int widths[9];
-    if (int rc = fp_dims(src)) return rc;
-    if (int rc = fp_layer_widths(nlayers, layers, widths)) return rc;
-    if (!fp_widths_ok(nlayers, widths, src)) return PN2_E_ARG;
+    if (int rc = fp_level_args(nlayers, layers, src)) return rc;
     if (src->c1 == 0 && src->points1) return PN2_E_ARG;
     if (!src->points2 || !src->idx || !src->dist || (src->c1 > 0 && !src->points1) || !out || !weight || !ws) return PN2_E_NULL;
-    return tl_fp_forward(nlayers, layers, src, out, weight, ws, opts, stream);
+    FpL1 f = fp_l1(src);
+    f.weight_out = weight;
+    return tl_train_forward(fp_call(nlayers, layers, f, out, ws, opts, stream));
 }
 
 extern "C" int pn2_mlp_train_backward_fp(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *src, const float *weight,
@@ -248,12 +257,15 @@ extern "C" int pn2_mlp_train_backward_fp(int nlayers, const pn2_bn_layer *layers
                                          int reproducible, void *ws, const pn2_train_opts *opts, void *stream)
 {
     using namespace pn2;
-    if (!src) return PN2_E_NULL;
-    int widths[9];
-    if (int rc = fp_dims(src)) return rc;
-    if (int rc = fp_layer_widths(nlayers, layers, widths)) return rc;
-    if (!fp_widths_ok(nlayers, widths, src)) return PN2_E_ARG;
+    if (int rc = fp_level_args(nlayers, layers, src)) return rc;
     if (src->c1 == 0 && (src->points1 || grad_points1)) return PN2_E_ARG;
     if (!src->points2 || !src->idx || (src->c1 > 0 && !src->points1) || !weight || !out || !grad_out || !ws) return PN2_E_NULL;
-    return tl_fp_backward(nlayers, layers, src, weight, out, grad_out, grad_points2, grad_points1, reproducible, ws, opts, stream);
+    FpL1 f = fp_l1(src);
+    f.weight = weight;
+    f.grad_points2 = grad_points2;
+    f.grad_points1 = grad_points1;
+    TlCall c = fp_call(nlayers, layers, f, out, ws, opts, stream);
+    c.grad_out = grad_out;
+    c.reproducible = reproducible;
+    return tl_train_backward(c);
 }

@@ -1,6 +1,6 @@
 // train_mlp_frozen.hip -- the training node with FROZEN batch-norm statistics (pn2_mlp_train_*_frozen): the entry points,
 // their argument checks and the three per-channel kernels only this mode needs. The passes themselves are train_mlp.hip's
-// (tl_train_forward / tl_train_backward with a TlFrozen). gfx950.
+// (tl_train_forward / tl_train_backward with TlCall::frozen). gfx950.
 //
 // A batch norm in eval() normalises with its running statistics (torch.nn.BatchNorm, training = False): gradients through a
 // model in eval() (saliency, adversarial points, test-time optimisation) and fine-tuning with frozen batch norms. Per layer,
@@ -16,10 +16,9 @@
 //               last pass (tl_frozen_grads_kernel); a layer whose gradient slots are all NULL runs no weight-gradient pass and
 //               sums nothing, and the chain stops at the lowest layer that still needs something
 // Running statistics are read, never written.
-#include "train_mlp_frozen.h"
+#include "train_mlp_internal.h"
 
 #include <limits.h>
-#include <string.h>
 
 namespace pn2 {
 
@@ -147,6 +146,20 @@ static int frozen_args(long long rows, int nlayers, const pn2_bn_layer *layers, 
     return PN2_OK;
 }
 
+static TlCall frozen_call(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, const float *x,
+                          int pool_rows, int pooling, const float *out, const int *argsel, const float *zsel, const float *pool_w,
+                          void *ws, const pn2_train_opts *opts, void *stream)
+{
+    TlCall c{};
+    c.rows = rows; c.nlayers = nlayers; c.layers = layers;
+    c.group = group; c.x = x;
+    c.pool_rows = pool_rows; c.pooling = pooling;
+    c.frozen = true;
+    c.out = out; c.argsel = argsel; c.zsel = zsel; c.pool_w = pool_w;
+    c.ws = ws; c.opts = opts; c.stream = stream;
+    return c;
+}
+
 }  // namespace pn2
 
 extern "C" int pn2_mlp_train_frozen_supported(long long rows, int nlayers, const int *widths, int pool_rows, int pooling,
@@ -170,7 +183,8 @@ extern "C" int pn2_mlp_train_forward_frozen(long long rows, int nlayers, const p
                                             float *pool_w, void *ws, const pn2_train_opts *opts, void *stream)
 {
     if (int rc = pn2::frozen_args(rows, nlayers, layers, group, x, pool_rows, pooling)) return rc;
-    return pn2::tl_frozen_forward(rows, nlayers, layers, group, x, pool_rows, pooling, out, argsel, zsel, pool_w, ws, opts, stream);
+    return pn2::tl_train_forward(pn2::frozen_call(rows, nlayers, layers, group, x, pool_rows, pooling, out, argsel, zsel, pool_w, ws,
+                                                  opts, stream));
 }
 
 extern "C" int pn2_mlp_train_backward_frozen(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
@@ -189,6 +203,11 @@ extern "C" int pn2_mlp_train_backward_frozen(long long rows, int nlayers, const 
         if (group->m <= 0 || group->nsample <= 0 || (long long)group->m * group->nsample > INT_MAX ||
             (long long)group->b * group->n > INT_MAX) return PN2_E_ARG;
     }
-    return pn2::tl_frozen_backward(rows, nlayers, layers, group, x, pool_rows, pooling, out, argsel, zsel, pool_w, grad_out, grad_x,
-                                   grad_feat_rows, grad_points, grad_xyz, grad_new_xyz, grad_bias, reproducible, ws, opts, stream);
+    pn2::TlCall c = pn2::frozen_call(rows, nlayers, layers, group, x, pool_rows, pooling, out, argsel, zsel, pool_w, ws, opts, stream);
+    c.grad_out = grad_out;
+    c.grad_x = grad_x; c.grad_feat_rows = grad_feat_rows; c.grad_points = grad_points;
+    c.grad_xyz = grad_xyz; c.grad_new_xyz = grad_new_xyz;
+    c.grad_bias = grad_bias;
+    c.reproducible = reproducible;
+    return pn2::tl_train_backward(c);
 }

@@ -1,6 +1,6 @@
 // train_mlp_xyz.hip -- the coordinate gradients of the SA training node (pn2_mlp_train_backward_xyz): the entry points, their
 // argument checks and the two kernels only this gradient needs. The passes themselves are train_mlp.hip's
-// (tl_xyz_backward there). gfx950.
+// (tl_train_backward with TlCall::grad_xyz). gfx950.
 //
 // The reference differentiates a set-abstraction level with respect to the coordinates: GroupPoint and GatherPoint register
 // gradients, and d loss / d xyz flows through grouped_xyz - new_xyz (utils/pointnet_util.py:44-46, :179-180) into layer 1.
@@ -14,20 +14,11 @@
 // (tl_l1_forward_kernel) backward has already scattered dz_1 onto the points as S (b n, cout_1), and grad_xyz = S . W1x^T is
 // the same kernel over the b n points: no second scatter. weighted_avg pooling is refused: its weights exp(-5 |grouped xyz|)
 // depend on xyz, and the norm has no derivative at the centroid, which is a member of its own ball.
-#include "pn2_device.h"
+#include "train_mlp_internal.h"
 
 #include <limits.h>
-#include <string.h>
 
 namespace pn2 {
-
-// ---- defined in train_mlp.hip (arguments checked here first) ----
-long long tl_xyz_ws_bytes(long long rows, int nlayers, const int *widths, int pool_rows, int pooling, const int *group_dims,
-                          const pn2_train_opts *opts);
-int tl_xyz_backward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group, int pool_rows, int pooling,
-                    const float *out, const int *argsel, const float *zsel, const float *pool_w, const float *grad_out,
-                    float *grad_feat_rows, float *grad_points, float *grad_xyz, float *grad_new_xyz, int reproducible, void *ws,
-                    const pn2_train_opts *opts, void *stream);
 
 struct TlXyz {
     long long rows;
@@ -235,6 +226,16 @@ extern "C" int pn2_mlp_train_backward_xyz(long long rows, int nlayers, const pn2
     if (!group->new_xyz && grad_new_xyz) return PN2_E_ARG;
     if (group->m <= 0 || group->nsample <= 0 || (long long)group->m * group->nsample > INT_MAX ||
         (long long)group->b * group->n > INT_MAX) return PN2_E_ARG;
-    return pn2::tl_xyz_backward(rows, nlayers, layers, group, pool_rows, pooling, out, argsel, zsel, pool_w, grad_out, grad_feat_rows,
-                                grad_points, grad_xyz, grad_new_xyz, reproducible, ws, opts, stream);
+    if (int rc = pn2::tl_pool_args(pool_rows, pooling, true)) return rc;
+    pn2::TlCall c{};
+    c.rows = rows; c.nlayers = nlayers; c.layers = layers;
+    c.group = group;
+    c.pool_rows = pool_rows; c.pooling = pooling;
+    c.out = out; c.argsel = argsel; c.zsel = zsel;                  // (pool_w: weighted_avg was refused above)
+    c.grad_out = grad_out;
+    c.grad_feat_rows = grad_feat_rows; c.grad_points = grad_points;
+    c.grad_xyz = grad_xyz; c.grad_new_xyz = grad_new_xyz;
+    c.reproducible = reproducible;
+    c.ws = ws; c.opts = opts; c.stream = stream;
+    return pn2::tl_train_backward(c);
 }

@@ -96,6 +96,10 @@ def options(**kw):
         _OPTS.update(old)
 
 
+def _widths_array(widths):
+    return (ctypes.c_int * len(widths))(*widths)
+
+
 def conv_bn_pairs(net):
     """[(conv, bn)] of an nn.Sequential of Conv (1x1) + BatchNorm + ReLU triples, or None if it is anything else."""
     mods, out = list(net), []
@@ -148,8 +152,7 @@ def pool_supported(net, rows, ns, pooling):
         return False
     pairs = conv_bn_pairs(net)
     widths = [pairs[0][0].in_channels] + [c.out_channels for c, _ in pairs]
-    arr = (ctypes.c_int * len(widths))(*widths)
-    return bool(_C.lib().pn2_mlp_train_pool_supported(rows, len(widths) - 1, arr, ns, code))
+    return bool(_C.lib().pn2_mlp_train_pool_supported(rows, len(widths) - 1, _widths_array(widths), ns, code))
 
 
 def xyz_grad_supported(net, rows, ns, pooling, b, n, m, cfeat, has_idx=True):
@@ -161,9 +164,8 @@ def xyz_grad_supported(net, rows, ns, pooling, b, n, m, cfeat, has_idx=True):
         return False
     pairs = conv_bn_pairs(net)
     widths = [pairs[0][0].in_channels] + [c.out_channels for c, _ in pairs]
-    arr = (ctypes.c_int * len(widths))(*widths)
     gdims = (ctypes.c_int * 6)(b, n, m, ns, cfeat, 1 if has_idx else 0)
-    return bool(_C.lib().pn2_mlp_train_xyz_supported(rows, len(widths) - 1, arr, ns, code, gdims))
+    return bool(_C.lib().pn2_mlp_train_xyz_supported(rows, len(widths) - 1, _widths_array(widths), ns, code, gdims))
 
 
 def frozen_supported(net, rows, pool_rows=0, grouped=True, pooling="max", xyz_dims=None):
@@ -191,14 +193,13 @@ def frozen_supported(net, rows, pool_rows=0, grouped=True, pooling="max", xyz_di
         return True                # as stack_supported: the max path needs no query of the library (the entries check their plan)
     cin = pairs[0][0].in_channels
     widths = [cin if grouped else (cin + 3) // 4 * 4] + [c.out_channels for c, _ in pairs]   # plain rows: zero-padded (fp_mlp_train)
-    arr = (ctypes.c_int * len(widths))(*widths)
     gdims = None
     if xyz_dims is not None:
         if not grouped or code == 2:
             return False
         b, n, m, cfeat, has_idx = xyz_dims
         gdims = (ctypes.c_int * 6)(b, n, m, pool_rows, cfeat, 1 if has_idx else 0)
-    return bool(_C.lib().pn2_mlp_train_frozen_supported(rows, len(widths) - 1, arr, pool_rows, code, gdims,
+    return bool(_C.lib().pn2_mlp_train_frozen_supported(rows, len(widths) - 1, _widths_array(widths), pool_rows, code, gdims,
                                                         1 if xyz_dims is not None else 0))
 
 
@@ -244,33 +245,29 @@ def _group_dims(level, points):
                               1 if level.idx is not None else 0)
 
 
-def _ws(rows, widths, pool_rows, backward, dev, gdims=None, opts=None):
-    arr = (ctypes.c_int * len(widths))(*widths)
-    nbytes = _C.lib().pn2_mlp_train_ws_bytes_ex(rows, len(widths) - 1, arr, pool_rows, backward, gdims, opts)
-    require(nbytes >= 0, "pn2_mlp_train: unsupported stack (rows %% 32, widths %% 4, pool group 16 or a multiple of 32)")
+def _workspace(query_name, dev, error_text, *args):
+    """The scratch buffer of one call, sized by the library's query `query_name(*args)`."""
+    nbytes = getattr(_C.lib(), query_name)(*args)
+    require(nbytes >= 0, error_text)
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
 
 
-def _ws_xyz(rows, widths, pool_rows, code, dev, gdims, opts=None):
-    arr = (ctypes.c_int * len(widths))(*widths)
-    nbytes = _C.lib().pn2_mlp_train_ws_bytes_xyz(rows, len(widths) - 1, arr, pool_rows, code, gdims, opts)
-    require(nbytes >= 0, "pn2_mlp_train: unsupported stack or pooling for the coordinate gradients")
-    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
-
-
-def _ws_pool(rows, widths, pool_rows, code, backward, dev, gdims=None, opts=None):
-    arr = (ctypes.c_int * len(widths))(*widths)
-    nbytes = _C.lib().pn2_mlp_train_ws_bytes_pool(rows, len(widths) - 1, arr, pool_rows, code, backward, gdims, opts)
-    require(nbytes >= 0, "pn2_mlp_train: unsupported stack or pooling")
-    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
-
-
-def _ws_frozen(rows, widths, pool_rows, code, backward, dev, gdims, want_xyz, opts=None):
-    arr = (ctypes.c_int * len(widths))(*widths)
-    nbytes = _C.lib().pn2_mlp_train_ws_bytes_frozen(rows, len(widths) - 1, arr, pool_rows, code, backward, gdims,
-                                                    1 if want_xyz else 0, opts)
-    require(nbytes >= 0, "pn2_mlp_train: unsupported stack or pooling for frozen batch-norm statistics")
-    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+def _level_workspace(level, widths, code, backward, dev, gdims, opts, want_xyz=False):
+    """... of an SA / plain-rows node: the query that belongs to the level's mode."""
+    head = (level.rows, len(widths) - 1, _widths_array(widths), level.pool_rows)
+    if level.frozen:
+        return _workspace("pn2_mlp_train_ws_bytes_frozen", dev,
+                          "pn2_mlp_train: unsupported stack or pooling for frozen batch-norm statistics",
+                          *head, code, backward, gdims, 1 if want_xyz else 0, opts)
+    if want_xyz:
+        return _workspace("pn2_mlp_train_ws_bytes_xyz", dev, "pn2_mlp_train: unsupported stack or pooling for the coordinate gradients",
+                          *head, code, gdims, opts)
+    if code:
+        return _workspace("pn2_mlp_train_ws_bytes_pool", dev, "pn2_mlp_train: unsupported stack or pooling", *head, code, backward, gdims,
+                          opts)
+    return _workspace("pn2_mlp_train_ws_bytes_ex", dev,
+                      "pn2_mlp_train: unsupported stack (rows %% 32, widths %% 4, pool group 16 or a multiple of 32)",
+                      *head, backward, gdims, opts)
 
 
 _KEEP_WS = [False, None]          # diagnostics (scripts/train_mlp_check.py): keep the last backward's workspace
@@ -310,6 +307,47 @@ def _grad_slot(param, like):
     return g
 
 
+def _unpack_params(params, n):
+    """A node's *params -> weights, biases (entries may be None), gammas, betas of its n layers."""
+    return ([f32(params[4 * l], "weight") for l in range(n)], [params[4 * l + 1] for l in range(n)],
+            [params[4 * l + 2] for l in range(n)], [params[4 * l + 3] for l in range(n)])
+
+
+def _count_batch(pairs):
+    nbt = [bn.num_batches_tracked for _, bn in pairs if bn.track_running_stats and bn.num_batches_tracked is not None]
+    if nbt:
+        torch._foreach_add_(nbt, 1)                            # one launch for the level's counters
+
+
+def _batch_stat_grads(pairs, weights, gammas, betas):
+    """Batch statistics: per layer the (weight, gamma, beta) gradients the kernels write -- the parameters' own .grad where the
+    kernels may add into it (`direct`, set_accumulate_into_grad), else fresh tensors."""
+    grads, direct = [], []
+    for l, (conv, bn) in enumerate(pairs):
+        slots = (_grad_slot(conv.weight, weights[l]), _grad_slot(bn.weight, gammas[l]), _grad_slot(bn.bias, betas[l])) \
+            if _ACCUMULATE[0] else (None, None, None)
+        direct.append(all(t is not None for t in slots))
+        grads.append(slots if direct[-1] else
+                     (torch.empty_like(weights[l]), torch.empty_like(gammas[l]), torch.empty_like(betas[l])))
+    return grads, direct
+
+
+def _batch_stat_results(grads, direct, biases, widths, dev):
+    """... and what the node returns for them, four per layer. The conv bias gradients are exactly zero under batch norm (one
+    zero buffer, one fill launch, a view per layer)."""
+    result, zero, off = [], None, 0
+    for l in range(len(grads)):
+        if direct[l]:                                          # added into .grad by the kernels (zero for the bias: nothing to add)
+            result += [None, None, None, None]
+        else:
+            if zero is None and biases[l] is not None:
+                zero = torch.zeros((sum(widths[1:]),), dtype=torch.float32, device=dev)
+            gb = zero[off:off + widths[l + 1]] if biases[l] is not None else None
+            result += [grads[l][0], gb, grads[l][1], grads[l][2]]
+        off += widths[l + 1]
+    return result
+
+
 class _TrainMLP(torch.autograd.Function):
     """inputs: level, x (points (b,n,c) when grouped -- may be None -- else the (rows, cin) input), xyz and new_xyz (the
     level's own tensors when their gradients are wanted, level.xyz_grad; else None: the coordinates are constants of the node),
@@ -318,13 +356,11 @@ class _TrainMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, level, x, xyz_in, new_xyz_in, *params):
         n = len(level.pairs)
-        weights = [f32(params[4 * l], "weight") for l in range(n)]
-        biases = [params[4 * l + 1] for l in range(n)]
-        gammas, betas = [params[4 * l + 2] for l in range(n)], [params[4 * l + 3] for l in range(n)]
+        weights, biases, gammas, betas = _unpack_params(params, n)
         dev = weights[0].device
         rows = level.rows
         widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
-        warr = (ctypes.c_int * len(widths))(*widths)
+        warr = _widths_array(widths)
         opts = _opts()
         code = level.pooling if level.pool_rows else 0
         # (the averaging modes always keep z_L: a mean does not commute with batch norm + ReLU)
@@ -348,30 +384,26 @@ class _TrainMLP(torch.autograd.Function):
             argsel = zsel = None
         arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
         grp = _group_struct(level, x) if level.grouped else None
-        frozen = bool(getattr(level, "frozen", False))
-        if frozen:
+        ws = _level_workspace(level, widths, code, 0, dev, _group_dims(level, x), opts)
+        if level.frozen:
             # running statistics (bn.eval()): read, never written -- no counter either (pn2_mlp_train_forward_frozen)
-            ws = _ws_frozen(rows, widths, level.pool_rows, code, 0, dev, _group_dims(level, x), False, opts)
             with on_device(dev):
                 _C.check(_C.lib().pn2_mlp_train_forward_frozen(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
                                                                None if level.grouped else ptr(x), level.pool_rows, code, ptr(out),
                                                                ptr(argsel) if code in (0, 3) else None, ptr(zsel), ptr(pool_w),
                                                                ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward_frozen")
         elif code:
-            ws = _ws_pool(rows, widths, level.pool_rows, code, 0, dev, _group_dims(level, x), opts)
             with on_device(dev):
                 _C.check(_C.lib().pn2_mlp_train_forward_pool(rows, n, arr, ctypes.byref(grp), level.pool_rows, code, ptr(out),
                                                              ptr(argsel) if code == 3 else None, ptr(zsel), ptr(pool_w), ptr(ws),
                                                              opts, stream_ptr(dev)), "mlp_train_forward_pool")
         else:
-            ws = _ws(rows, widths, level.pool_rows, 0, dev, _group_dims(level, x), opts)
             with on_device(dev):
                 _C.check(_C.lib().pn2_mlp_train_forward_ex(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
                                                            None if level.grouped else ptr(x), level.pool_rows, ptr(out), ptr(argsel),
                                                            ptr(zsel), ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward")
-        nbt = [bn.num_batches_tracked for _, bn in level.pairs if bn.track_running_stats and bn.num_batches_tracked is not None]
-        if nbt and not frozen:
-            torch._foreach_add_(nbt, 1)                        # one launch for the level's counters
+        if not level.frozen:
+            _count_batch(level.pairs)
         ctx.level, ctx.widths, ctx.code = level, widths, code
         ctx.opts = dict(_OPTS)                              # backward must see the organisation forward ran under
         ctx.has_x = x is not None
@@ -407,12 +439,12 @@ class _TrainMLP(torch.autograd.Function):
         dev = out.device
         rows = level.rows
         grad_out = f32(grad_out, "grad_out")
-        grads, direct = [], []
-        frozen = bool(getattr(level, "frozen", False))
+        frozen = level.frozen
         needs, gbias = [], [None] * n          # frozen: which of (weight, bias, gamma, beta) want a gradient; the bias gradients
-        small, soff = None, 0                  # frozen: ONE buffer for the per-channel gradients (gamma, beta, bias) of every layer
-        for l, (conv, bn) in enumerate(level.pairs):
-            if frozen:
+        if frozen:
+            grads, direct = [], []
+            small, soff = None, 0              # ONE buffer for the per-channel gradients (gamma, beta, bias) of every layer
+            for l, (conv, bn) in enumerate(level.pairs):
                 # NULL slots for a layer none of whose parameters wants a gradient: the library then runs no weight-gradient
                 # pass for it. Otherwise the three tensors the kernels write are all given (scratch for an unwanted one).
                 need = [bool(ctx.needs_input_grad[4 + 4 * l + k]) for k in range(4)]
@@ -435,19 +467,15 @@ class _TrainMLP(torch.autograd.Function):
                               slots[2] if (d and need[2]) else vec[0], slots[3] if (d and need[3]) else vec[1]))
                 if need[1]:
                     gbias[l] = slots[1] if d else vec[2]
-                continue
-            slots = (_grad_slot(conv.weight, weights[l]), _grad_slot(bn.weight, gammas[l]), _grad_slot(bn.bias, betas[l])) \
-                if _ACCUMULATE[0] else (None, None, None)
-            direct.append(all(t is not None for t in slots))
-            grads.append(slots if direct[-1] else
-                         (torch.empty_like(weights[l]), torch.empty_like(gammas[l]), torch.empty_like(betas[l])))
+        else:
+            grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
         need_x = ctx.needs_input_grad[1] and x is not None
         # the coordinate gradients (sa_mlp_train(..., xyz_grad=True)): written by the library, both or neither
-        want_xyz = bool(getattr(level, "xyz_grad", False)) and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        want_xyz = level.xyz_grad and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
         grad_xyz = grad_new_xyz = None
         grad_x = grad_rows = grad_pts = None
         gdims = _group_dims(level, x)
-        warr = (ctypes.c_int * len(widths))(*widths)
+        warr = _widths_array(widths)
         opts = _opts_from(ctx.opts)
         per_point = level.grouped and bool(_C.lib().pn2_mlp_train_layer1_per_point_ex(n, warr, gdims, opts))
         if need_x and level.grouped and per_point:
@@ -460,13 +488,7 @@ class _TrainMLP(torch.autograd.Function):
             grad_xyz = torch.empty((level.b, level.n, 3), dtype=torch.float32, device=dev)
             if level.new_xyz is not None:
                 grad_new_xyz = torch.empty((level.b, level.m, 3), dtype=torch.float32, device=dev)
-        if frozen:
-            ws = _ws_frozen(rows, widths, level.pool_rows, code, 1, dev, gdims, want_xyz, opts)
-        elif want_xyz:
-            ws = _ws_xyz(rows, widths, level.pool_rows, code, dev, gdims, opts)
-        else:
-            ws = _ws_pool(rows, widths, level.pool_rows, code, 1, dev, gdims, opts) if code else \
-                _ws(rows, widths, level.pool_rows, 1, dev, gdims, opts)
+        ws = _level_workspace(level, widths, code, 1, dev, gdims, opts, want_xyz)
         if _KEEP_WS[0]:
             _KEEP_WS[1] = (ws, rows, widths, level.pool_rows)
         # (frozen: the library wants the running statistics named in both directions; it only ever reads them)
@@ -525,25 +547,15 @@ class _TrainMLP(torch.autograd.Function):
                                                            stream_ptr(dev)), "group_point_grad")
         result = [None, grad_x if need_x else None, grad_xyz if ctx.needs_input_grad[2] else None,
                   grad_new_xyz if ctx.needs_input_grad[3] else None]
-        # the conv bias gradients: exactly zero under batch norm (one zero buffer, one fill launch, a view per layer)
-        zero = None
-        off = 0
-        for l in range(n):
-            if frozen:                                     # the conv bias takes a real gradient under frozen statistics
-                if direct[l] or not any(needs[l]):
-                    result += [None, None, None, None]
-                else:
-                    nd = needs[l]
-                    result += [grads[l][0] if nd[0] else None, gbias[l], grads[l][1] if nd[2] else None,
-                               grads[l][2] if nd[3] else None]
-            elif direct[l]:                                # added into .grad by the kernels (zero for the bias: nothing to add)
+        if not frozen:
+            return tuple(result + _batch_stat_results(grads, direct, biases, widths, dev))
+        for l in range(n):                                     # the conv bias takes a real gradient under frozen statistics
+            if direct[l] or not any(needs[l]):
                 result += [None, None, None, None]
             else:
-                if zero is None and biases[l] is not None:
-                    zero = torch.zeros((sum(widths[1:]),), dtype=torch.float32, device=dev)
-                gb = zero[off:off + widths[l + 1]] if biases[l] is not None else None
-                result += [grads[l][0], gb, grads[l][1], grads[l][2]]
-            off += widths[l + 1]
+                nd = needs[l]
+                result += [grads[l][0] if nd[0] else None, gbias[l], grads[l][1] if nd[2] else None,
+                           grads[l][2] if nd[3] else None]
         return tuple(result)
 
 
@@ -676,8 +688,7 @@ def fp_level_supported(net, b, n, m, c2, c1):
     if not pairs or len(pairs) > 7 or pairs[0][0].in_channels != c2 + c1 or not stack_supported(net, b * n, 0, False):
         return False
     widths = [c2 + c1] + [c.out_channels for c, _ in pairs]
-    arr = (ctypes.c_int * len(widths))(*widths)
-    return bool(_C.lib().pn2_mlp_train_fp_supported(b, n, m, c2, c1, len(pairs), arr))
+    return bool(_C.lib().pn2_mlp_train_fp_supported(b, n, m, c2, c1, len(pairs), _widths_array(widths)))
 
 
 # Where the modules take the node. It no longer forms the interpolated part of layer 1's input on the b (n - m) rows that are
@@ -702,10 +713,8 @@ def _fp_src(level, points2, points1):
 
 
 def _ws_fp(level, widths, backward, dev, opts):
-    arr = (ctypes.c_int * len(widths))(*widths)
-    nbytes = _C.lib().pn2_mlp_train_ws_bytes_fp(level.b, level.n, level.m, level.c2, level.c1, len(widths) - 1, arr, backward, opts)
-    require(nbytes >= 0, "pn2_mlp_train_ws_bytes_fp: unsupported level")
-    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
+    return _workspace("pn2_mlp_train_ws_bytes_fp", dev, "pn2_mlp_train_ws_bytes_fp: unsupported level", level.b, level.n, level.m,
+                      level.c2, level.c1, len(widths) - 1, _widths_array(widths), backward, opts)
 
 
 class _TrainFP(torch.autograd.Function):
@@ -715,9 +724,7 @@ class _TrainFP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, level, points2, points1, *params):
         n = len(level.pairs)
-        weights = [f32(params[4 * l], "weight") for l in range(n)]
-        biases = [params[4 * l + 1] for l in range(n)]
-        gammas, betas = [params[4 * l + 2] for l in range(n)], [params[4 * l + 3] for l in range(n)]
+        weights, biases, gammas, betas = _unpack_params(params, n)
         dev = weights[0].device
         rows = level.rows
         widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
@@ -732,9 +739,7 @@ class _TrainFP(torch.autograd.Function):
         with on_device(dev):
             _C.check(_C.lib().pn2_mlp_train_forward_fp(n, arr, ctypes.byref(src), ptr(out), ptr(weight), ptr(ws), opts,
                                                        stream_ptr(dev)), "mlp_train_forward_fp")
-        nbt = [bn.num_batches_tracked for _, bn in level.pairs if bn.track_running_stats and bn.num_batches_tracked is not None]
-        if nbt:
-            torch._foreach_add_(nbt, 1)
+        _count_batch(level.pairs)
         ctx.level, ctx.widths = level, widths
         ctx.opts = dict(_OPTS)
         ctx.has_p1 = points1 is not None
@@ -761,13 +766,7 @@ class _TrainFP(torch.autograd.Function):
         out = sv.pop(0)
         dev = out.device
         grad_out = f32(grad_out, "grad_out")
-        grads, direct = [], []
-        for l, (conv, bn) in enumerate(level.pairs):
-            slots = (_grad_slot(conv.weight, weights[l]), _grad_slot(bn.weight, gammas[l]), _grad_slot(bn.bias, betas[l])) \
-                if _ACCUMULATE[0] else (None, None, None)
-            direct.append(all(t is not None for t in slots))
-            grads.append(slots if direct[-1] else
-                         (torch.empty_like(weights[l]), torch.empty_like(gammas[l]), torch.empty_like(betas[l])))
+        grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
         g2 = torch.empty_like(points2) if ctx.needs_input_grad[1] else None
         g1 = torch.empty_like(points1) if points1 is not None and ctx.needs_input_grad[2] else None
         opts = _opts_from(ctx.opts)
@@ -780,19 +779,7 @@ class _TrainFP(torch.autograd.Function):
             _C.check(_C.lib().pn2_mlp_train_backward_fp(n, arr, ctypes.byref(src), ptr(weight), ptr(out), ptr(grad_out), ptr(g2),
                                                         ptr(g1), 1 if is_deterministic() else 0, ptr(ws), opts, stream_ptr(dev)),
                      "mlp_train_backward_fp")
-        result = [None, g2, g1]
-        zero = None
-        off = 0
-        for l in range(n):
-            if direct[l]:
-                result += [None, None, None, None]
-            else:
-                if zero is None and biases[l] is not None:
-                    zero = torch.zeros((sum(widths[1:]),), dtype=torch.float32, device=dev)
-                gb = zero[off:off + widths[l + 1]] if biases[l] is not None else None
-                result += [grads[l][0], gb, grads[l][1], grads[l][2]]
-            off += widths[l + 1]
-        return tuple(result)
+        return tuple([None, g2, g1] + _batch_stat_results(grads, direct, biases, widths, dev))
 
 
 def fp_level_train(net, points2, points1, idx, dist, return_weight=False):
