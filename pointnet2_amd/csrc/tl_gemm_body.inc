@@ -1,4 +1,4 @@
-// Body of the training GEMM pass (train_mlp.hip: tl_gemm_kernel, and the GEMM range of tl_pair_kernel). Included as TEXT into
+// Body of the training GEMM pass (train_mlp_gemm.hip: tl_gemm_kernel, and the GEMM range of train_mlp_pair.hip's tl_pair_kernel). Included as TEXT into
 // the kernel that runs it, with the names in scope that it uses: NS, AMODE (compile-time), `p` (the kernel's TlGemm argument
 // itself or a reference to it), PN2_BX / PN2_BY / PN2_GX (the workgroup's position in its (gx, slabs) grid and gx), PN2_STATS
 // (compile-time bool: false = the "no statistics" variant of the frozen-statistics node, train_mlp_frozen.hip -- no per-tile
@@ -325,6 +325,6 @@
                 if (p.fin.ticket) tl_fin_store(dst, sum); else *dst = sum;      // folded finalisation: write-through (TlFin)
             }
         }
-        // the finalisation of these sums, by the workgroup of this pass that finishes last (TlFin in train_mlp.hip)
+        // the finalisation of these sums, by the workgroup of this pass that finishes last (TlFin, train_mlp_kernels.h; tl_fin_tail, train_mlp_device.h)
         if (p.fin.ticket) tl_fin_tail<kTlThreads>(p.fin, smem);
     }

@@ -1,4 +1,4 @@
-// Body of the weight-gradient pass (train_mlp.hip: tl_wgrad_kernel, and the weight-gradient range of tl_pair_kernel).
+// Body of the weight-gradient pass (train_mlp_wgrad.hip: tl_wgrad_kernel, and the weight-gradient range of train_mlp_pair.hip's tl_pair_kernel).
 // Included as TEXT (see tl_gemm_body.inc) with TPW, UPW, GATHER, DCLS, DY, L1X (compile-time), `p` (the TlWgrad argument) and
 // PN2_BX / PN2_BY / PN2_GX in scope.
     extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -118,7 +118,7 @@ __global__ __launch_bounds__(kFpThreads) void tl_fp_l1_forward_kernel(long long 
     }
 }
 
-// dz_1 = s dy_1 - c0 - c1 z_1, the operations of the GEMMs' A_DZ prologue (train_mlp.hip, tl_finish), in place over dy_1
+// dz_1 = s dy_1 - c0 - c1 z_1, the operations of the GEMMs' A_DZ prologue (train_mlp_device.h, tl_finish), in place over dy_1
 __global__ __launch_bounds__(256) void tl_fp_l1_dz_kernel(long long total4, int C, const float *__restrict__ z, float *g,
                                                           const float *__restrict__ coef)
 {

@@ -1,6 +1,8 @@
-// train_mlp_internal.h -- what the four files of the training node share: train_mlp.hip (the passes and their plan) and
-// train_mlp_fp.hip / train_mlp_xyz.hip / train_mlp_frozen.hip (the entry points, argument checks and kernels of one node
-// type each). Every extern "C" entry checks its arguments, fills a TlCall and hands it to tl_train_forward / tl_train_backward.
+// train_mlp_internal.h -- what the files of the training node share. train_mlp.hip is its host side (the size rules, the plan,
+// the passes of both directions); train_mlp_gemm / _wgrad / _pair / _top / _l1 / _small.hip hold one kernel family each with its
+// launch functions (train_mlp_kernels.h); train_mlp_fp.hip / train_mlp_xyz.hip / train_mlp_frozen.hip the entry points, argument
+// checks and kernels of one node type each. Every extern "C" entry checks its arguments, fills a TlCall and hands it to
+// tl_train_forward / tl_train_backward.
 #pragma once
 #include "pn2_device.h"
 
@@ -71,6 +73,19 @@ struct TlCall {
     const pn2_train_opts *opts;
     void *stream;
 };
+
+// The organisation overrides of a call (include/pn2ops.h: pn2_train_opts; NULL = every rule automatic). They travel as an
+// argument through every rule and launch: the library reads no environment variable and keeps no mode.
+typedef pn2_train_opts Opts;
+
+// ---- launch shapes: made by the size rules of train_mlp.hip (gemm_shape, wgrad_shape, fuse_shape, top_s_shape), read by its
+// plan and by the launch functions of the kernel families ----
+struct GemmShape { int K, N, tk, tn, ns, slabs, resident; size_t lds, pack_bytes; };
+struct WgradShape { int tus, tts, uslabs, tslabs, tpw, upw, two; long long gridx, nw, nchunks; size_t e, lds, lds_dy, partial_bytes; };
+// the layer's data gradient inside its weight-gradient pass (tl_wgrad_kernel<.., DY>; ok = false: two passes)
+struct FuseShape { bool ok; int tk, nt, single, acopy, upw; size_t lds, xr_off, pack_bytes; };
+// launch shape of tl_top_s_kernel (ok = false: the dense kernel takes the routed gradient as operand tiles)
+struct TopSShape { bool ok; int GB, KC, NLD, ld, gridx, gridy, nchunks; size_t lds, part_bytes, part2_bytes; };
 
 // ---- train_mlp.hip: the passes (arguments checked by the entries first) and the workspace queries that need the plan ----
 int tl_train_forward(const TlCall &call);

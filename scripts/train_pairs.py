@@ -1,7 +1,7 @@
 """Which (data-gradient GEMM, weight-gradient pass) shape pairs the size rules of csrc/train_mlp.hip produce at the training
-levels of the four reference networks: the table of launch_pair (tl_pair_kernel instantiations). A Python restatement of
+levels of the four reference networks: the table of launch_pair (tl_pair_kernel instantiations, csrc/train_mlp_pair.hip). A Python restatement of
 gemm_shape / wgrad_shape / top_stored / top_s_shape's size rule; `PN2_PAIR_TRACE` lab builds print what a run asks for
-that the table lacks (scripts/build_mlp_labs.sh train_mlp pairtrace:-DPN2_PAIR_TRACE)."""
+that the table lacks (scripts/build_mlp_labs.sh train_mlp_pair pairtrace:-DPN2_PAIR_TRACE)."""
 def tiles(c): return (c+31)//32
 def gemm_shape(rows,K,N):
     tk,tn=tiles(K),tiles(N)
