@@ -28,14 +28,20 @@
 //   * COLLECT (updaters, once per batch). Every lane computes the best key and the second-best VALUE of its P slots. Lanes whose
 //     best value is >= theta are candidate lanes: at most 64 / W per wave -- a wave with more raises its own threshold by
 //     bisection on the value bits, a wave with none (or with too many equal values) falls back to its exact best lane (one
-//     64-bit wave ladder). A candidate lane writes its best key to the wave's part of the list; the wave's BOUND -- the smallest
-//     value bits a sample must have for the list to be complete -- is the maximum of its threshold and of (second-best value +
-//     1 ulp) of its candidate lanes (an LDS atomic maximum on the fp32 bit patterns: the values are >= 0; issued as a plain
-//     ds_max_u32 -- hipcc turns atomicMax into a readlane loop over the active lanes). One barrier, the only one of the batch.
-//   * PICK (picker). Lane i takes candidate i (key from the list, x, y, z, k from the mirror). Per sample, hand-scheduled (the
-//     asm block below: 33 instructions, no pad, ~273 cycles at 4096 rank slots against 291 for the 40 before --
-//     profiles/fps_picker/README.md): the winner lane alone (exec = one lane) stores its (x, y, z, k) row and then the new count
-//     to LDS, hands its coordinates to scalar registers (three v_readfirstlane inside that window) and leaves the contest; the
+//     64-bit wave ladder). A candidate lane writes its best key to the wave's part of the list; the BOUND -- the smallest
+//     value bits a sample must have for the list to be complete -- is the maximum over the waves of their thresholds and of
+//     (second-best value + 1 ulp) of their candidate lanes: ONE word of the batch that every wave raises (an LDS atomic maximum
+//     on the fp32 bit patterns: the values are >= 0; issued as a plain ds_max_u32 -- hipcc turns atomicMax into a readlane loop
+//     over the active lanes; same-address atomics of several waves serialise in the LDS unit in a few cycles each). The waves'
+//     candidate counts go into one total the same way (ds_add_u32). One barrier, the only one of the batch.
+//   * READ (picker, behind the barrier). Lane i takes place i of the list: the key's high word is the value, its low word the
+//     mirror row (x, y, z, k). The places no wave filled hold the invalid key (a negative word | row 0) that the picker wrote there a
+//     batch earlier, in its idle time, so there is no count per wave to load and compare; bound and total come with one 8-byte
+//     load, and one 16-byte store clears the other parity's bound, total and count (profiles/fps_turnaround/README.md).
+//   * PICK (picker). Per sample, hand-scheduled (the
+//     asm block below: 32 instructions, no pad; 33 measured ~273 cycles at 4096 rank slots against 291 for the 40 before --
+//     profiles/fps_picker/README.md): the winner lane alone (exec = one lane) stores its (x, y, z, k) row and then adds 1 to the
+//     count in LDS, hands its coordinates to scalar registers (three v_readfirstlane inside that window) and leaves the contest; the
 //     reference's distance (tf_sampling_g.cu:141-144) from the
 //     sample to the other candidates, nine vector instructions; and, interleaved with those, the 32-bit wave ladder
 //     (v_max_i32 with the DPP operand folded in) over the values as they were BEFORE the update -- values only fall, so a lane
@@ -49,7 +55,8 @@
 //     and updates the touched groups, group by group (packed fp32, as in the pruned tier; no key work: keys are only needed at
 //     COLLECT). The skip test uses the value of the previous batch's LAST sample as v* (no running distance is above it).
 //   * theta = (1 - g) * (value of the last sample); g adapts so that the list stays about half full. The picker decides
-//     and publishes theta with the end-of-batch flag.
+//     and publishes theta with the end-of-batch flag (behind the last pick, where the updaters are still applying: moved
+//     ahead of the sample loop the adaptation sits on the chain and cost the metric 3 % -- profiles/fps_turnaround/README.md).
 //
 // Once a sample's value is 0 every running distance is 0 and the reference keeps selecting point 0 (its tie rule): the rest of
 // the output is filled directly.
@@ -62,7 +69,7 @@
 //
 // Hand-offs inside the workgroup: LDS only. The picker's row store and count store come from the same lane (LDS executes a
 // wave's operations in order), counts are release stores / acquire loads at workgroup scope. Double-buffered by batch parity:
-// list, counts, bounds and the header; the sample ring is single (a batch's samples are consumed before the next barrier).
+// list, bound, total and the header; the sample ring is single (a batch's samples are consumed before the next barrier).
 // Chains of different clouds now differ in length (the lists are the data's): 248-261 us over the 32 clouds of a bench batch.
 #pragma once
 #include "fps_pruned_body.h"
@@ -79,15 +86,20 @@ constexpr int kBtT = kBtUT + PN2_WAVE;         // + the picker
 constexpr unsigned kBtEnd = 0x100u, kBtFill = 0x200u, kBtCountMask = 0xffu;
 
 struct BtXchg {
-    double list[kBtCand];                      // wave w's candidates at [w * cap, w * cap + cnt[w]), cap = 64 / W
-    unsigned cnt[kBtMaxW];
+    double list[kBtCand];                      // wave w's candidates from w * cap on, cap = 64 / W; the other places hold the invalid key
+    unsigned cnt[kBtMaxW];                     // lab only (PN2_BT_READ1 = 0): one count and one bound word per updater wave
     unsigned bound[kBtMaxW];
+    // one 16-byte row that the picker clears in one store and reads (bmax, total) in one 8-byte load
+    unsigned bmax;                             // the batch's bound: LDS maximum over every wave's threshold and candidate lanes
+    unsigned total;                            // candidate lanes of the batch, all waves (LDS add): only the adaptation of g reads it
     unsigned count;                            // samples of this batch published so far | kBtEnd | kBtFill
+    unsigned spare0;
     unsigned single;                           // after this batch: that many samples one per exchange (SLOW BATCHES below)
     unsigned theta, vlast;                     // for the NEXT collect: threshold bits, value bits of the batch's last sample
-    unsigned pad[4];
+    unsigned spare1;
 };
-static_assert(sizeof(BtXchg) % 16 == 0, "16-byte rows");
+static_assert(sizeof(BtXchg) == 8 * kBtCand + 8 * kBtMaxW + 32, "the size the LDS budget of every geometry was measured with");
+static_assert(sizeof(BtXchg) % 16 == 0 && offsetof(BtXchg, bmax) % 16 == 0, "16-byte rows");
 
 // P = slots per updater thread, UT = updater threads
 __host__ __device__ constexpr size_t fps_batch_xchg_offset(int P, int UT = kBtUT) { return (fps_pruned_lds_bytes(P, UT) + 15) & ~(size_t)15; }
@@ -123,11 +135,24 @@ __device__ __forceinline__ int bt_wave_max_i32_lane63(int v)
     return v;
 }
 
+// The key of a list place that no wave filled: the DOUBLE -1.0, high word 0xBFF00000, low word 0. As a candidate value the high
+// word is the float -1.875: negative, so below every value as an integer like the -1.0f (0xBF800000) a taken lane holds, and kept
+// by v_min_f32 against any distance; the low word is mirror row 0. The word 0xBF800000 itself would do the same and was measured
+// 0.002 ms per step slower on the benchmark (-1.0 is an inline constant of the 64-bit move; the other pattern takes two literal
+// moves and a register pair that lives across the batch loop): profiles/fps_turnaround/README.md.
+__device__ __forceinline__ double kBtInvalidKey() { return -1.0; }
+
 // LDS atomic maximum without the compiler's wave-level pre-reduction (a readlane loop over the active lanes: ~50 cycles per
 // lane on a lone wave; the LDS unit serialises same-address atomics in a few cycles each)
 __device__ __forceinline__ void lds_max_u32(unsigned *p, unsigned v)
 {
     asm volatile("ds_max_u32 %0, %1" :: "v"((unsigned)(size_t)p), "v"(v) : "memory");
+}
+
+// LDS add without a return value: same-address adds of several waves serialise in the LDS unit like the maxima above
+__device__ __forceinline__ void lds_add_u32(unsigned *p, unsigned v)
+{
+    asm volatile("ds_add_u32 %0, %1" :: "v"((unsigned)(size_t)p), "v"(v) : "memory");
 }
 
 // Where the batched tier exists and pays (measured, profiles/r06/fps_batch.txt): 513..8192 rank slots (1024 / 2048: 8 / 16 groups,
@@ -177,6 +202,13 @@ __device__ unsigned long long g_bt_stats[16];
 #endif
 #ifndef PN2_BT_FILL
 #define PN2_BT_FILL 1                // the add of na in the ladder's last wait state, the two pads no rule asks for dropped (0: three s_nop)
+#endif
+// lab switches of the hand-over between two lists (each cut measured alone: profiles/fps_turnaround/README.md)
+#ifndef PN2_BT_READ1
+#define PN2_BT_READ1 1               // READ: one bound word and one total for the batch, unused list places preset to the invalid key (0: a count and a bound word per wave, reduced by the picker)
+#endif
+#ifndef PN2_BT_CADD
+#define PN2_BT_CADD 1                // sample loop: the count word by ds_add_u32, bh = ms in the wait state the add of na filled (0: ds_write_b32 of na, v_add_u32 na, s_mov on the back edge)
 #endif
 #ifndef PN2_BT_G0
 #define PN2_BT_G0 0.10f               // initial 1 - theta / (last sample value)
@@ -235,6 +267,10 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
         __builtin_amdgcn_s_setprio(3);           // it shares SIMD 0 with updater wave 0 and is the chain
 #endif
         for (int i = lane; i < (int)(2 * sizeof(BtXchg) / 4); i += PN2_WAVE) reinterpret_cast<unsigned *>(xch)[i] = 0u;   // counts, bounds, flags
+#if PN2_BT_READ1
+        xch[0].list[lane] = kBtInvalidKey();     // (below); behind the zeroes: a wave's LDS writes execute in order
+        xch[1].list[lane] = kBtInvalidKey();
+#endif
         for (int i = 0; i < kPrPrologueBarriers; ++i) __syncthreads();
         long long e0 = 0;
         for (; j < jE; ++j) {                    // the updaters' early rounds: one barrier each
@@ -254,6 +290,16 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
         if (j < m)
         for (;;) {
             const long long q0 = PN2_BT_CLOCK();
+#if PN2_BT_READ1
+            // The NEXT batch's list, every place to the invalid key: high word negative -- below every value as an integer and kept by
+            // v_min_f32 --, low word 0 -- mirror row 0. The updaters then write their candidates over it and the picker needs no
+            // count per wave to tell a candidate from an empty place. Nobody else touches that buffer now: the picker took its keys
+            // into registers a whole batch ago (behind the previous barrier), this batch's COLLECT writes the other parity, the
+            // one-per-exchange rounds exchange through the pruned layout's wave keys, and the updaters write it again only in
+            // the COLLECT that follows this batch's end flag -- a store of this wave behind this one (LDS executes a wave's
+            // operations in order), which they acquire first.
+            xch[par ^ 1].list[lane] = kBtInvalidKey();
+#endif
             // SLOW BATCHES, in the idle time (the clock's latency too: s_memtime shares the LDS counter, behind the barrier it sat
             // on the list read): the batch that just ended into the decayed sums, then the decision
             {
@@ -276,6 +322,20 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             __syncthreads();                     // the list of this batch is complete
             const long long q1 = PN2_BT_CLOCK();
             BtXchg &X = xch[par];
+            typedef float bt_f4 __attribute__((ext_vector_type(4)));
+#if PN2_BT_READ1
+            // The other parity's bound, total and count, one store: everybody is past the batch that used them, and the updaters
+            // raise them again only behind this batch's end flag (a later store of this wave, which they acquire first) -- written
+            // behind the barrier, read by nobody before the next one, like the per-wave words this row replaces.
+            if (lane == 0) *reinterpret_cast<uint4 *>(&xch[par ^ 1].bmax) = make_uint4(0u, 0u, 0u, 0u);
+            const uint2 bt2 = *reinterpret_cast<const uint2 *>(&X.bmax);            // same address in every lane: LDS broadcast
+            const double key = X.list[lane];
+            const unsigned lowc = (unsigned)__double2loint(key);                    // an empty place: row 0
+            const bt_f4 cand = *reinterpret_cast<const bt_f4 *>(&lds_rank[lowc]);   // x, y, z, bits of k
+            const int boundb = __builtin_amdgcn_readfirstlane((int)bt2.x);
+            const int total = __builtin_amdgcn_readfirstlane((int)bt2.y);
+            int cval = __double2hiint(key);                                         // an empty place: 0xBFF00000, negative
+#else
             if (lane == 0) __hip_atomic_store(&xch[par ^ 1].count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // everybody is past the batch that used it
             const uint4 c4 = *reinterpret_cast<const uint4 *>(X.cnt), c5 = *reinterpret_cast<const uint4 *>(X.cnt + 4);      // waves beyond W: 0
             const uint4 b4 = *reinterpret_cast<const uint4 *>(X.bound), b5 = *reinterpret_cast<const uint4 *>(X.bound + 4);
@@ -283,11 +343,11 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             const unsigned cw = X.cnt[lane / CAP];
             const bool valid = (unsigned)(lane & (CAP - 1)) < cw;
             const unsigned lowc = valid ? (unsigned)__double2loint(key) : 0u;
-            typedef float bt_f4 __attribute__((ext_vector_type(4)));
             const bt_f4 cand = *reinterpret_cast<const bt_f4 *>(&lds_rank[lowc]);   // x, y, z, bits of k
             const int boundb = __builtin_amdgcn_readfirstlane((int)max(max(max(b4.x, b4.y), max(b4.z, b4.w)), max(max(b5.x, b5.y), max(b5.z, b5.w))));
             const int total = __builtin_amdgcn_readfirstlane((int)(c4.x + c4.y + c4.z + c4.w + c5.x + c5.y + c5.z + c5.w));
             int cval = valid ? __double2hiint(key) : (int)0xBF800000;             // -1.0f: below every value as an integer, kept by v_min_f32
+#endif
             const int clo = (int)lowc;
             int a = 0;
             int vlastb = 0;
@@ -359,17 +419,19 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             //     update (the DPP steps need two independent instructions between them anyway). Values only fall: a lane that
             //     still holds that maximum afterwards is the arg-max -- if it is the only one. A sample of value 0 ends the batch by
             //     itself: nothing is above the bound afterwards.
-            //   NO SAMPLE COUNTER (PN2_BT_NOCTR): a list has at most 64 valid lanes and every taken lane is -1.0f, so after the last
+            //   NO SAMPLE COUNTER (PN2_BT_NOCTR): a list has at most 64 valid lanes, every taken lane is -1.0f and every empty place negative too, so after the last
             //     of them the ladder's maximum is 0 (lanes without a DPP source read 0) or negative -- below the bound, which is >= 1
             //     as an integer (second-best bits + 1) -- and the loop leaves by the bound exit. The count is read back from na
             //     behind the loop. Only the end of the output row needs a count inside the loop: a batch with fewer than 64
             //     samples left to write (the last one or two of a cloud) runs pick_counted instead.
             // Wait states (inline asm gets none from the compiler; the rules are the ones hipcc pads its own code for on gfx950):
             //   a VALU write of a VGPR -> a DPP read of it: 2 (between two ladder steps: two instructions of the distance, in
-            //     front of the last step the adds of raddr and na -- PN2_BT_FILL; the winner's -1.0f is written four ahead);
+            //     front of the last step the add of raddr and bh = ms, a scalar move: any instruction is a wait state --
+            //     PN2_BT_FILL, PN2_BT_CADD; the winner's -1.0f is written four ahead);
             //   a VALU write of a VGPR -> v_readlane / v_readfirstlane of it: 1 (v_min_f32 stands between the ladder and ms);
             //   v_readlane / v_readfirstlane writes an SGPR -> a VALU reads it: 2 (s_cmp + s_cbranch between ms and the v_cmp;
-            //     the sample's coordinates are read four or more instructions after they are written); a scalar read needs none;
+            //     the sample's coordinates are read four or more instructions after they are written); a scalar read needs none
+            //     (bh = ms reads the ms of the pass before, a whole pass after the v_readlane that wrote it);
             //   exec is written by scalar moves only (a VALU write of exec would cost the DPP steps 5).
             // reason: 0 = the batch is full / the cloud is done, 1 = nothing above the bound is left, 2 = the speculative maximum
             // is gone or not unique (the exact arg-max below decides, then the loop resumes).
@@ -391,12 +453,34 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
 #define PN2_BT_A_COUNT      "s_add_i32 %[a], %[a], 1\n\t"
 #define PN2_BT_A_FULL       "s_cmp_ge_i32 %[a], %[amax]\n\ts_cbranch_scc1 2f\n\t"
 #endif
+            // COUNT BY ADD (PN2_BT_CADD): the winner lane adds 1 to the count word (ds_add_u32, no return) instead of storing na, so
+            // na and its v_add_u32 leave the loop. The word is 0 when a batch starts (the picker cleared it behind the previous
+            // barrier) and holds the count alone until the end flag's store; the row store and the add come from one lane, in order,
+            // like the two stores before. The wait state the add of na filled takes the back edge's s_mov (bh = ms: the value of
+            // the sample just published; ms enters the block equal to bh, so the first pass changes nothing), which leaves the
+            // loop's head. The count is read back from the ring address behind the loop.
+#if PN2_BT_CADD
+#define PN2_BT_A_PUBCOUNT   "ds_add_u32 %[caddr], %[one]\n\t"
+#define PN2_BT_A_NA         ""
+#else
+#define PN2_BT_A_PUBCOUNT   "ds_write_b32 %[caddr], %[na]\n\t"
+#define PN2_BT_A_NA         "v_add_u32 %[na], 1, %[na]\n\t"
+#endif
+#if PN2_BT_CADD && PN2_BT_FILL
+#define PN2_BT_A_HEAD       "0:\n\t"
+#define PN2_BT_A_BH         "s_mov_b32 %[bh], %[ms]\n\t"
+#define PN2_BT_A_MS         "+s"
+#else
+#define PN2_BT_A_HEAD       "s_branch 1f\n\t0:\n\ts_mov_b32 %[bh], %[ms]\n\t1:\n\t"   /* the speculative maximum stood: it is the next sample's value */
+#define PN2_BT_A_BH         ""
+#define PN2_BT_A_MS         "=&s"
+#endif
 #if PN2_BT_FILL
 #define PN2_BT_A_ADDS_EARLY ""
-#define PN2_BT_A_PAD_DPP    "v_add_u32 %[raddr], 16, %[raddr]\n\tv_add_u32 %[na], 1, %[na]\n\t"   /* the two wait states in front of the last ladder step */
+#define PN2_BT_A_PAD_DPP    "v_add_u32 %[raddr], 16, %[raddr]\n\t" PN2_BT_A_NA PN2_BT_A_BH   /* the two wait states in front of the last ladder step */
 #define PN2_BT_A_PAD        ""
 #else
-#define PN2_BT_A_ADDS_EARLY "v_add_u32 %[raddr], 16, %[raddr]\n\tv_add_u32 %[na], 1, %[na]\n\t"
+#define PN2_BT_A_ADDS_EARLY "v_add_u32 %[raddr], 16, %[raddr]\n\t" PN2_BT_A_NA
 #define PN2_BT_A_PAD_DPP    "s_nop 1\n\t"
 #define PN2_BT_A_PAD        "s_nop 0\n\t"
 #endif
@@ -406,17 +490,15 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             else
 #endif
             for (;;) {
-                int reason, t_wl, t_sx, t_sy, t_sz, t_ms, t_cnt;
+                int reason, t_wl, t_sx, t_sy, t_sz, t_cnt;
+                int t_ms = bh;                                                   // (PN2_BT_CADD: read by the block, see above)
                 int v_t;
                 float v_dx, v_dy, v_dz;
                 asm volatile(
-                    "s_branch 1f\n\t"
-                    "0:\n\t"
-                    "s_mov_b32 %[bh], %[ms]\n\t"                  // the speculative maximum stood: it is the next sample's value
-                    "1:\n\t"
+                    PN2_BT_A_HEAD
                     "s_mov_b64 exec, %[eq]\n\t"
                     "ds_write_b128 %[raddr], %[cand]\n\t"
-                    "ds_write_b32 %[caddr], %[na]\n\t"
+                    PN2_BT_A_PUBCOUNT
                     "v_mov_b32 %[cval], 0xbf800000\n\t"           // four instructions ahead of the ladder's first step
                     PN2_BT_A_WINNER_IN
                     "s_mov_b64 exec, -1\n\t"
@@ -465,9 +547,9 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
 #if !PN2_BT_NOCTR
                       [a] "+s"(a),
 #endif
-                      [reason] "=&s"(reason), [wl] "=&s"(t_wl), [sx] "=&s"(t_sx), [sy] "=&s"(t_sy), [sz] "=&s"(t_sz), [ms] "=&s"(t_ms), [cnt] "=&s"(t_cnt),
+                      [reason] "=&s"(reason), [wl] "=&s"(t_wl), [sx] "=&s"(t_sx), [sy] "=&s"(t_sy), [sz] "=&s"(t_sz), [ms] PN2_BT_A_MS(t_ms), [cnt] "=&s"(t_cnt),
                       [t] "=&v"(v_t), [dx] "=&v"(v_dx), [dy] "=&v"(v_dy), [dz] "=&v"(v_dz)
-                    : [cand] "v"(cand), [caddr] "v"(count_addr), [cx] "v"(cx), [cy] "v"(cy), [cz] "v"(cz), [amax] "s"(amax), [bound] "s"(boundb)
+                    : [cand] "v"(cand), [caddr] "v"(count_addr), [cx] "v"(cx), [cy] "v"(cy), [cz] "v"(cz), [amax] "s"(amax), [bound] "s"(boundb), [one] "v"(1u)
                     : "memory", "scc");
                 vlastb = bh;                                                     // the value of the sample published last
                 if (reason != 2) break;
@@ -476,7 +558,11 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 if (bh < boundb) break;
             }
 #if PN2_BT_NOCTR
+#if PN2_BT_CADD
+            a = (int)((unsigned)__builtin_amdgcn_readfirstlane((int)raddr) - ring_base) >> 4;   // one ring row per sample (pick_counted moves it too)
+#else
             a = __builtin_amdgcn_readfirstlane((int)na) - 1;                     // na is the count the next sample would publish
+#endif
 #endif
 #undef PN2_BT_A_WINNER_IN
 #undef PN2_BT_A_LANE
@@ -484,6 +570,11 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
 #undef PN2_BT_A_SZ
 #undef PN2_BT_A_COUNT
 #undef PN2_BT_A_FULL
+#undef PN2_BT_A_PUBCOUNT
+#undef PN2_BT_A_NA
+#undef PN2_BT_A_HEAD
+#undef PN2_BT_A_BH
+#undef PN2_BT_A_MS
 #undef PN2_BT_A_ADDS_EARLY
 #undef PN2_BT_A_PAD_DPP
 #undef PN2_BT_A_PAD
@@ -522,7 +613,8 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
         pn2_f2 (&zz)[P / 2] = S.zz;
         float (&md)[P] = S.md;
         unsigned (&low)[P] = S.low;
-        // (only wave w ever raises bound[.][w]; the picker has zeroed the exchange area before the prologue's barriers)
+        // (the picker has zeroed the exchange area before the prologue's barriers and clears a parity's bound, total and count behind
+        // the barrier of the batch in between)
         // lane l tests samples against the box of THIS wave's group l % GW
         float blx, bly, blz, bhx, bhy, bhz;
         {
@@ -700,17 +792,28 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             if ((mask >> lane) & 1ull) {
                 const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
                 X.list[w * CAP + pos] = kl;
+#if PN2_BT_READ1
+                lds_max_u32(&X.bmax, __float_as_uint(sec) + 1u);
+#else
                 lds_max_u32(&X.bound[w], __float_as_uint(sec) + 1u);
+#endif
             }
             if (lane == 0) {
+#if PN2_BT_READ1
+                lds_add_u32(&X.total, (unsigned)cnt);     // every wave into the batch's two words: the picker reads them as they are
+                lds_max_u32(&X.bmax, thb);
+#else
                 X.cnt[w] = (unsigned)cnt;
                 lds_max_u32(&X.bound[w], thb);
+#endif
             }
             const long long u1 = PN2_BT_CLOCK();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the asm LDS operations above are invisible to the compiler's counters
             __syncthreads();
             const long long u2 = PN2_BT_CLOCK();
+#if !PN2_BT_READ1
             if (lane == 0) xch[par ^ 1].bound[w] = 0u;            // next batch's word of this wave (nobody reads it before the next barrier)
+#endif
             // ---- APPLY: the picker's samples as they appear ----------------------------------------------------------------------------
             int done = 0;
             unsigned c;
