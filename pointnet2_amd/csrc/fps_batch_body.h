@@ -34,6 +34,11 @@
 //     on the fp32 bit patterns: the values are >= 0; issued as a plain ds_max_u32 -- hipcc turns atomicMax into a readlane loop
 //     over the active lanes; same-address atomics of several waves serialise in the LDS unit in a few cycles each). The waves'
 //     candidate counts go into one total the same way (ds_add_u32). One barrier, the only one of the batch.
+//     The second-best value comes from triples of slots (v_max3 / v_med3: 9 instructions at eight slots for 16,
+//     PN2_BT_SEC3). The common outcome -- between 1 and 64 / W lanes reach theta -- is decided on the scalar popcount of the
+//     ballot and goes straight to the list write with exec set from the ballot mask; bisection and the exact fallback stand
+//     beside that way with a copy of the write (PN2_BT_CTAIL): 43 instructions from the first v_max_f64 to the barrier for 77
+//     (profiles/fps_updaters/README.md).
 //   * READ (picker, behind the barrier). Lane i takes place i of the list: the key's high word is the value, its low word the
 //     mirror row (x, y, z, k). The places no wave filled hold the invalid key (a negative word | row 0) that the picker wrote there a
 //     batch earlier, in its idle time, so there is no count per wave to load and compare; bound and total come with one 8-byte
@@ -50,10 +55,12 @@
 //     bits are >= the bound; the first sample of a batch always is: the list holds every updater wave's best lane, so its
 //     maximum is the global one. The loop counts nothing: a list has at most 64 valid lanes, so it ends by the bound exit; only a
 //     batch that could pass the end of the output row (fewer than 64 samples left) runs the compiler's counted form.
-//   * APPLY (updaters, behind the picker). A wave polls the count, takes up to 64 / GW new samples at a time -- lane l tests
-//     sample l / GW against the box of the wave's group l % GW: one distance-to-box computation for 64 (sample, group) pairs --
+//   * APPLY (updaters, behind the picker). A wave polls the count, takes up to CH = 64 / GW new samples at a time -- lane l tests
+//     sample l % CH against the box of the wave's group l / CH: one distance-to-box computation for 64 (sample, group) pairs --
 //     and updates the touched groups, group by group (packed fp32, as in the pruned tier; no key work: keys are only needed at
-//     COLLECT). The skip test uses the value of the previous batch's LAST sample as v* (no running distance is above it).
+//     COLLECT). A group's bits of the touched mask are one field of a scalar word and a bit's number is the lane that holds
+//     the sample (PN2_BT_GBITS): an untouched group costs a field extract and a branch, a sample s_ff1, s_bitset0 and the
+//     loop's compare. The skip test uses the value of the previous batch's LAST sample as v* (no running distance is above it).
 //   * theta = (1 - g) * (value of the last sample); g adapts so that the list stays about half full. The picker decides
 //     and publishes theta with the end-of-batch flag (behind the last pick, where the updaters are still applying: moved
 //     ahead of the sample loop the adaptation sits on the chain and cost the metric 3 % -- profiles/fps_turnaround/README.md).
@@ -118,6 +125,49 @@ __device__ __forceinline__ float vmed3_f32(float a, float b, float c)
     return r;
 }
 
+__device__ __forceinline__ float vmax3_f32(float a, float b, float c)
+{
+    float r;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+// The second largest (as a multiset) of P running distances. Leaves are TRIPLES of slots -- (v_max3, v_med3) are the two largest
+// of three --, two left over make a pair (v_max, v_min), one left over joins at the end; three (largest, second) pairs merge into
+// max3 of the largest and max(med3 of the largest, max3 of the seconds): a second that does not belong to the overall largest is
+// below its own largest, which is at most the median. The last merge needs no largest. 1 / 3 / 9 / 19 instructions at 2 / 4 / 8 /
+// 16 slots against 2 / 6 / 16 / 36 for the network of pairs. Running distances are never NaN (v_min_f32 keeps the non-NaN
+// operand and they start at 1e38) and never -0, so every form returns the same bits.
+template <int P>
+__device__ __forceinline__ float bt_second_best(const float (&v)[P])
+{
+    static_assert(P == 2 || P == 4 || P == 8 || P == 16, "slots per updater thread");
+    constexpr int NT = P / 3, REM = P % 3, K = NT + (REM == 2 ? 1 : 0), KF = K >= 3 ? 3 : K;   // pairs, pairs at the last merge
+    float h[K > 0 ? K : 1], l[K > 0 ? K : 1];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) { h[i] = vmax3_f32(v[3 * i], v[3 * i + 1], v[3 * i + 2]); l[i] = vmed3_f32(v[3 * i], v[3 * i + 1], v[3 * i + 2]); }
+    if constexpr (REM == 2) { h[NT] = vmax_f32(v[P - 2], v[P - 1]); l[NT] = vmin_f32(v[P - 2], v[P - 1]); }
+    int k = K;
+#pragma unroll
+    while (k > 3) {                                 // (16 slots: five pairs) the last three into one
+        const float hm = vmed3_f32(h[k - 3], h[k - 2], h[k - 1]), lm = vmax3_f32(l[k - 3], l[k - 2], l[k - 1]);
+        h[k - 3] = vmax3_f32(h[k - 3], h[k - 2], h[k - 1]);
+        l[k - 3] = vmax_f32(hm, lm);
+        k -= 2;
+    }
+    if constexpr (REM == 1) {                       // one slot left over: merge all the way, then the median of (largest, second, slot)
+        if constexpr (KF == 3) {
+            const float hm = vmed3_f32(h[0], h[1], h[2]), lm = vmax3_f32(l[0], l[1], l[2]);
+            h[0] = vmax3_f32(h[0], h[1], h[2]);
+            l[0] = vmax_f32(hm, lm);
+        }
+        return vmed3_f32(h[0], l[0], v[P - 1]);
+    } else {
+        if constexpr (KF == 3) return vmax_f32(vmed3_f32(h[0], h[1], h[2]), vmax3_f32(l[0], l[1], l[2]));
+        else return l[0];
+    }
+}
+
 // wave-wide signed maximum, result in lane 63: the DPP operand rides on the v_max itself (VOP2), one instruction per step.
 // Lanes without a source (bound_ctrl:0 reads 0) combine with 0 -- harmless for a maximum of values of which at least one is >= 0.
 __device__ __forceinline__ int bt_wave_max_i32_lane63(int v)
@@ -170,8 +220,9 @@ inline bool fps_batch_pays(int ranks, int m) { return fps_batch_covers(ranks) &&
 // lab: [0] batches, [1] samples, [2] exact fallbacks, [3] bisection steps, [4] sum of list sizes, [5] (group, sample) updates,
 // [6] picker cycles in READ, [7] picker cycles in PICK, [8] picker cycles waiting at the barrier, [9] updater 0 cycles in COLLECT,
 // [10] updater 0 cycles from the barrier to the end flag, [11] tie resolutions, [12] speculation misses, [13] samples taken one per
-// exchange after slow batches, [14] such runs
-__device__ unsigned long long g_bt_stats[16];
+// exchange after slow batches, [14] such runs; updater 0: [15] cycles from seeing the end flag to arriving at the next list barrier
+// (epilogue + COLLECT), [16] chunks, [17] polls that found nothing, [18] (group, sample) updates taken on the dense path
+__device__ unsigned long long g_bt_stats[24];
 #ifndef PN2_BT_STATS_FROM
 #define PN2_BT_STATS_FROM 0
 #endif
@@ -210,6 +261,16 @@ __device__ unsigned long long g_bt_stats[16];
 #ifndef PN2_BT_CADD
 #define PN2_BT_CADD 1                // sample loop: the count word by ds_add_u32, bh = ms in the wait state the add of na filled (0: ds_write_b32 of na, v_add_u32 na, s_mov on the back edge)
 #endif
+// lab switches of the updater waves' cuts (each measured alone: profiles/fps_updaters/README.md)
+#ifndef PN2_BT_SEC3
+#define PN2_BT_SEC3 1                // COLLECT: the second-best value over triples of slots, v_max3 / v_med3 (0: pairs, v_max / v_min / v_med3 per node)
+#endif
+#ifndef PN2_BT_CTAIL
+#define PN2_BT_CTAIL 1               // COLLECT: 0 < cnt <= CAP goes straight to the list write, exec set from the ballot mask (0: one tail behind bisection and fallback, (mask >> lane) & 1 in vector registers)
+#endif
+#ifndef PN2_BT_GBITS
+#define PN2_BT_GBITS 1               // APPLY: lane l tests sample l % CH against group l / CH, so a group's bits of the touched mask are one 32-bit field whose bit numbers are lane numbers (0: sample l / GW, group l % GW, strided 64-bit masks)
+#endif
 #ifndef PN2_BT_G0
 #define PN2_BT_G0 0.10f               // initial 1 - theta / (last sample value)
 #endif
@@ -243,6 +304,8 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
     constexpr int GW = P / GS;                         // groups per updater wave
     constexpr int CAP = kBtCand / W;                   // candidate lanes per updater wave
     constexpr int BT = UT + PN2_WAVE;                  // threads of the workgroup
+    constexpr int CH = PN2_WAVE / GW;                  // samples per APPLY chunk: one lane per (sample, group) pair
+    constexpr bool GB = PN2_BT_GBITS && GW > 1;        // lane l: sample l % CH, group l / CH (else sample l / GW, group l % GW; one group: the same)
     static_assert((W * GW == 32 && (W == 4 || W == 8)) || (W == 8 && (GW == 2 || GW == 1)),
                   "32 groups on four or eight updater waves; 16 / 8 groups (2048 / 1024 rank slots) on eight");
     float4 *lds_rank = reinterpret_cast<float4 *>(smem + 256);
@@ -615,11 +678,11 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
         unsigned (&low)[P] = S.low;
         // (the picker has zeroed the exchange area before the prologue's barriers and clears a parity's bound, total and count behind
         // the barrier of the batch in between)
-        // lane l tests samples against the box of THIS wave's group l % GW
+        // lane l tests samples against the box of THIS wave's group l / CH (PN2_BT_GBITS; l % GW without)
         float blx, bly, blz, bhx, bhy, bhz;
         {
             const float *gbox = reinterpret_cast<const float *>(smem + 256 + (size_t)16 * NS + (size_t)kPrHistRows * kPrBins * 4);
-            const float *o = gbox + (w * GW + (lane & (GW - 1))) * 8;
+            const float *o = gbox + (w * GW + (GB ? lane / CH : (lane & (GW - 1)))) * 8;
             blx = o[0]; bly = o[1]; blz = o[2]; bhx = o[4]; bhy = o[5]; bhz = o[6];
         }
         pn2_f2 sxy = {0.f, 0.f}, syy = {0.f, 0.f}, szk = {0.f, 0.f};   // the sample in the LOW halves (fps_body.h: the high-half broadcast form is not safe)
@@ -727,6 +790,7 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
         };
         if (jE > 1) single_rounds(jE);
         int par = 0;
+        long long uend = 0;                          // lab: the clock when the previous batch's end flag was seen
         if (j < m)
         for (;;) {
             BtXchg &X = xch[par];
@@ -737,9 +801,18 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             {
                 // best key and the two largest values of the lane's P slots (straight-line: 2 P - 1 tournament nodes)
                 double kd[P];
-                float hv[P / 2], lv[P / 2];
 #pragma unroll
                 for (int p = 0; p < P; ++p) kd[p] = __hiloint2double(__float_as_int(md[p]), (int)low[p]);
+#if PN2_BT_SEC3
+#pragma unroll
+                for (int st = 1; st < P; st <<= 1)
+#pragma unroll
+                    for (int i = 0; i + st < P; i += 2 * st)
+                        asm("v_max_f64 %0, %1, %2" : "=v"(kd[i]) : "v"(kd[i]), "v"(kd[i + st]));
+                kl = kd[0];
+                sec = bt_second_best<P>(md);
+#else
+                float hv[P / 2], lv[P / 2];
 #pragma unroll
                 for (int i = 0; i < P / 2; ++i) { hv[i] = vmax_f32(md[2 * i], md[2 * i + 1]); lv[i] = vmin_f32(md[2 * i], md[2 * i + 1]); }
 #pragma unroll
@@ -757,11 +830,36 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                     }
                 kl = kd[0];
                 sec = lv[0];
+#endif
             }
             const unsigned vb = (unsigned)__double2hiint(kl);
             unsigned long long mask = __ballot(vb >= thetab);
             int cnt = __popcll(mask);
             unsigned thb = thetab;                   // this wave's threshold: its points outside the list are below it
+#if PN2_BT_CTAIL && PN2_BT_READ1
+            // The list write, the same code at the end of both ways below so that the common one carries no copies for the other:
+            // exec = the candidate lanes (the ballot mask as it is: every lane of an updater wave is active here), their keys to the
+            // wave's places and their second-best values + 1 ulp into the bound; then lane 0 alone, the wave's count into the total
+            // and its threshold into the bound. Scalar writes of exec need no wait state in front of the LDS operations (the
+            // picker's publish does the same).
+            static_assert(offsetof(BtXchg, total) == offsetof(BtXchg, bmax) + 4, "one address register for both words");
+            auto list_write = [&](const unsigned long long mk, const int c, const unsigned th) __attribute__((always_inline)) {
+                const unsigned pos = __builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+                asm volatile("s_mov_b64 exec, %[mk]\n\t"
+                             "ds_write_b64 %[la], %[kl]\n\t"
+                             "ds_max_u32 %[ba], %[sec1]\n\t"
+                             "s_mov_b64 exec, 1\n\t"
+                             "ds_add_u32 %[ba], %[c] offset:4\n\t"
+                             "ds_max_u32 %[ba], %[th]\n\t"
+                             "s_mov_b64 exec, -1"
+                             :: [mk] "s"(mk), [la] "v"((unsigned)(size_t)&X.list[w * CAP] + 8u * pos), [kl] "v"(kl),
+                                [ba] "v"((unsigned)(size_t)&X.bmax), [sec1] "v"(__float_as_uint(sec) + 1u), [c] "v"((unsigned)c), [th] "v"(th)
+                             : "memory");
+            };
+            if ((unsigned)(cnt - 1) < (unsigned)CAP) {
+                list_write(mask, cnt, thb);          // 0 < cnt <= CAP: theta stands, no fallback
+            } else {
+#endif
             bool exact = false;
             if (cnt > CAP) {
                 unsigned lob = thetab, hib = vlastb + 1u;       // more than CAP lanes at lob, none at hib
@@ -789,6 +887,12 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 mask = mk;
                 cnt = 1;
             }
+#if PN2_BT_CTAIL && PN2_BT_READ1
+                // (the compiler carries this way's mask through the bisection's loop in vector registers: back to a scalar pair)
+                list_write(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(mask >> 32)) << 32) |
+                               (unsigned)__builtin_amdgcn_readfirstlane((int)mask), cnt, thb);
+            }
+#else
             if ((mask >> lane) & 1ull) {
                 const int pos = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
                 X.list[w * CAP + pos] = kl;
@@ -807,7 +911,9 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 lds_max_u32(&X.bound[w], thb);
 #endif
             }
+#endif
             const long long u1 = PN2_BT_CLOCK();
+            if (w == 0 && uend) PN2_BT_STAT(15, u1 - uend);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the asm LDS operations above are invisible to the compiler's counters
             __syncthreads();
             const long long u2 = PN2_BT_CLOCK();
@@ -825,45 +931,71 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 const int avail = (int)(c & kBtCountMask);
                 if (avail == done) {
                     if (c & kBtEnd) break;
+                    if (w == 0) PN2_BT_STAT(17, 1);
                     __builtin_amdgcn_s_sleep(1);
                     continue;
                 }
-                constexpr int CH = PN2_WAVE / GW;                                 // samples per chunk: lane l tests sample l / GW against group l % GW
+                if (w == 0) PN2_BT_STAT(16, 1);
                 constexpr unsigned long long kStride = GW == 8 ? 0x0101010101010101ull : GW == 4 ? 0x1111111111111111ull
                                                        : GW == 2 ? 0x5555555555555555ull : ~0ull;   // one bit per sample
                 const int np = min(avail - done, CH);
-                const int pi = lane / GW;                                        // this lane's sample of the chunk
+                const int pi = GB ? (lane & (CH - 1)) : lane / GW;               // this lane's sample of the chunk
                 const float4 s = ring[done + (pi < np ? pi : 0)];
                 const float ax = __fsub_rn(s.x, __builtin_amdgcn_fmed3f(s.x, blx, bhx));
                 const float ay = __fsub_rn(s.y, __builtin_amdgcn_fmed3f(s.y, bly, bhy));
                 const float az = __fsub_rn(s.z, __builtin_amdgcn_fmed3f(s.z, blz, bhz));
                 const float bd = __fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az));
                 unsigned long long touched = ~__ballot(bd >= thr);               // NaN -> not far -> updated
-                if (np * GW < 64) touched &= (1ull << (np * GW)) - 1ull;
+                if constexpr (GB) {
+                    // the lanes of samples np .. CH - 1 leave: the same np bits of every group's field (CH <= 32: both words alike)
+                    constexpr unsigned kRep = CH == 32 ? 1u : CH == 16 ? 0x00010001u : 0x01010101u;
+                    if (np < CH) { const unsigned vm = ((1u << np) - 1u) * kRep; touched &= ((unsigned long long)vm << 32) | vm; }
+                } else {
+                    if (np * GW < 64) touched &= (1ull << (np * GW)) - 1ull;
+                }
                 // group by group (static): the samples that reach group g, straight into that group's update -- no dispatch on a
                 // group number (three compare-and-branch pairs per (group, sample) otherwise)
                 if (touched) {
                     // the first samples of a cloud reach most groups: then every sample of the chunk updates all of the wave's
                     // groups in straight-line code (an update of an untouched group changes nothing)
                     if (2 * __popcll(touched) >= GW * np) {
+                        if (w == 0) PN2_BT_STAT(18, GW * np);
                         for (int p = 0; p < np; ++p) {
-                            sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.x), p * GW));
-                            syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.y), p * GW));
-                            szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.z), p * GW));
+                            const int sl = GB ? p : p * GW;                      // a lane that holds sample p
+                            sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.x), sl));
+                            syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.y), sl));
+                            szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.z), sl));
                             update_all();
                         }
                     } else {
                         auto one_group = [&](auto gic) __attribute__((always_inline)) {
                             constexpr int g8 = decltype(gic)::value;
-                            unsigned long long mg = touched & (kStride << g8);
-                            while (mg) {
-                                const int sl = (int)__builtin_ctzll(mg) & ~(GW - 1);
-                                mg &= mg - 1ull;
-                                sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.x), sl));
-                                syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.y), sl));
-                                szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.z), sl));
-                                PN2_BT_STAT(5, 1);
-                                update_group(gic);
+                            if constexpr (GB) {
+                                // the group's field of the mask, one scalar word: bit p = sample p = lane p of the chunk's ring read.
+                                // An untouched group costs the field extract and a branch; a sample costs s_ff1, one s_bitset0
+                                // and the loop's compare.
+                                unsigned mg = (unsigned)(touched >> (g8 * CH));
+                                if constexpr (CH < 32) mg &= (1u << CH) - 1u;
+                                while (mg) {
+                                    const int sl = (int)__builtin_ctz(mg);
+                                    asm("s_bitset0_b32 %0, %1" : "+s"(mg) : "s"(sl));
+                                    sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.x), sl));
+                                    syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.y), sl));
+                                    szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.z), sl));
+                                    PN2_BT_STAT(5, 1);
+                                    update_group(gic);
+                                }
+                            } else {
+                                unsigned long long mg = touched & (kStride << g8);
+                                while (mg) {
+                                    const int sl = (int)__builtin_ctzll(mg) & ~(GW - 1);
+                                    mg &= mg - 1ull;
+                                    sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.x), sl));
+                                    syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.y), sl));
+                                    szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.z), sl));
+                                    PN2_BT_STAT(5, 1);
+                                    update_group(gic);
+                                }
                             }
                         };
                         one_group(std::integral_constant<int, 0>());
@@ -878,6 +1010,7 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 done += np;
             }
             const long long u3 = PN2_BT_CLOCK();
+            uend = u3;
             if (w == 0) { PN2_BT_STAT(9, u1 - u0); PN2_BT_STAT(10, u3 - u2); }
             const int a = (int)(c & kBtCountMask);
             // ---- the batch's samples leave in one store ------------------------------------------------------------------------------

@@ -74,7 +74,7 @@ int main(int argc, char **argv)
                 const float us_half = timed(5, [&]() { vs[vi].run(m / 2); });
 #ifdef PN2_BT_STATS
                 if (vi == 3) {
-                    unsigned long long z[16] = {0}, st[16];
+                    unsigned long long z[24] = {0}, st[24];
                     CK(hipMemcpyToSymbol(HIP_SYMBOL(pn2::g_bt_stats), z, sizeof(z)));
                     vs[vi].run(m); CK(hipDeviceSynchronize());
                     CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(pn2::g_bt_stats), sizeof(st)));
@@ -83,6 +83,8 @@ int main(int argc, char **argv)
                            "   cycles per batch: picker read %.0f, pick %.0f (%.0f per sample), picker at the barrier %.0f | updater 0: collect %.0f, barrier -> end flag %.0f\n",
                            st[0], st[1], (double)st[1] / st[0], st[2], st[3], (double)st[4] / st[0], st[5], st[11], st[12], st[14], st[13], (double)st[6] / st[0], (double)st[7] / st[0],
                            (double)st[7] / st[1], (double)st[8] / st[0], (double)st[9] / st[0], (double)st[10] / st[0]);
+                    printf("   updater 0 per batch: end flag -> next list barrier %.0f cycles, chunks %.1f, polls that found nothing %.1f, (group, sample) updates on the dense path %.1f\n",
+                           (double)st[15] / st[0], (double)st[16] / st[0], (double)st[17] / st[0], (double)st[18] / st[0]);
                 }
 #endif
                 printf("%-10s n=%5d %s m=%4d : %7.1f us, prologue (m=1) %6.1f us, %6.1f ns/round overall, %6.1f ns/round in the second half  %s\n",
