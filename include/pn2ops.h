@@ -147,6 +147,44 @@ int pn2_group_point_grad_seg(int b, int n, int c, int m, int nsample, const floa
 int pn2_three_interpolate_grad_seg(int b, int n, int c, int m, const float *grad_out, const int *idx,
                                    const float *weight, float *grad_points, void *ws, int deterministic, void *stream);
 
+/* ---- index plans: the inversion of an index tensor as a call of its own ----
+ * The inversion above depends on idx alone -- not on the gradient, the channel count or the mode's arithmetic. A PLAN is the
+ * inverse of one index tensor in caller-owned device memory of pn2_seg_plan_bytes(b, rows, entries) bytes (uninitialised; 4-byte
+ * aligned; rows / entries as for pn2_seg_grad_ws_bytes). One build call writes it -- the same kernels, chosen by the same rules,
+ * as inside pn2_*_grad_seg; kernels only, so the call can be captured --, and any number of pn2_*_grad_planned calls then READ it
+ * and never write it: at any channel count, in both modes, from several streams at once (behind the build in stream order).
+ *   sorted != 0 selects the sorting inversion wherever `deterministic` of pn2_*_grad_seg does. A plan built with sorted = 1
+ *   serves both modes: deterministic = 1 on it returns the bits of pn2_*_grad_seg(deterministic = 1), deterministic = 0 the
+ *   default mode's sums. deterministic = 1 on a plan built with sorted = 0 is still identical from run to run, but sums EVERY
+ *   row in fixed point (all its sorted flags are 0).
+ *   A plan is valid for exactly the idx contents it was built from; keeping the two together is the caller's contract, as with
+ *   every pointer pair of this ABI.
+ * Beside the workspace layout of pn2_*_grad_seg a plan holds a TABLE of each cloud's long rows (long_count[b], long_rows[b][cap],
+ * cap = entries / 32 + 1; rows of at least long_from references, in no particular order), written by the build while it has the
+ * counts. The table walk of the default mode's long-row part deals the table's entries to its workgroups round-robin, so it is
+ * balanced wherever the long rows are (the walk of pn2_seg_grad_plan relies on them sitting at the low point numbers of every cloud).
+ * pn2_seg_plan_layout (host only; tests, maintainers): byte offsets inside a plan of start int[b][rows + 1], sorted int[b][rows],
+ * list int[b][entries], long_count, long_rows; the long-row threshold; the table's capacity per cloud.
+ * The planned gradient calls take the arguments of pn2_*_grad_seg with `plan` in place of idx and ws. Argument errors return
+ * PN2_E_* before anything is launched (a NULL plan: PN2_E_NULL), b == 0 returns PN2_OK, entries == 0 zero-fills grad_points
+ * without reading the plan (building a plan of such a shape is a no-op). *_ex: variant of the default mode's long-row part,
+ * 0 = the library's choice (today the stride walk: the faster one on ball-query lists), 1 = the stride walk of
+ * pn2_*_grad_seg, 2 = the table walk (the one to ask for when the long rows are not at the low point numbers: kNN lists,
+ * lists of the caller's own; more than 2048 clouds take the stride walk all the same); other values PN2_E_ARG. The variants
+ * return identical bits. */
+long long pn2_seg_plan_bytes(int b, int rows, long long entries);
+int pn2_seg_plan_layout(int b, int rows, long long entries, long long *offsets5, int *long_from, long long *long_cap);
+int pn2_group_point_plan(int b, int n, int m, int nsample, const int *idx, int sorted, void *plan, void *stream);
+int pn2_three_interpolate_plan(int b, int n, int m, const int *idx, int sorted, void *plan, void *stream);
+int pn2_group_point_grad_planned(int b, int n, int c, int m, int nsample, const float *grad_out, const void *plan,
+                                 float *grad_points, int deterministic, void *stream);
+int pn2_three_interpolate_grad_planned(int b, int n, int c, int m, const float *grad_out, const void *plan,
+                                       const float *weight, float *grad_points, int deterministic, void *stream);
+int pn2_group_point_grad_planned_ex(int b, int n, int c, int m, int nsample, const float *grad_out, const void *plan,
+                                    float *grad_points, int deterministic, int variant, void *stream);
+int pn2_three_interpolate_grad_planned_ex(int b, int n, int c, int m, const float *grad_out, const void *plan,
+                                          const float *weight, float *grad_points, int deterministic, int variant, void *stream);
+
 /* ---- grouped local MLP + max-pool of a set-abstraction layer, fused, on the matrix cores ---------
  * (no reference kernel; replaces for INFERENCE the TF graph of utils/pointnet_util.py:44-50 + :117-127:
  *  group_point(xyz)-new_xyz ++ group_point(points) -> 3 x [conv2d 1x1 + batch_norm + ReLU] -> reduce_max
@@ -422,6 +460,11 @@ typedef struct pn2_group_src {     /* the rows of a grouped tensor (pointnet_uti
     const float *new_xyz;          /* (b,m,3), subtracted from the grouped xyz; NULL: no centroid (group_all) */
     const float *points;           /* (b,n,cfeat) or NULL */
     const int *idx;                /* (b,m,nsample); NULL: sample k of the group is point k (group_all: m = 1, nsample = n) */
+    const void *idx_plan;          /* pn2_group_point_plan(b, n, m, nsample, idx, ...) of THIS idx, or NULL. With a plan the
+                                      backward calls reduce from it (pn2_group_point_grad_planned) and invert nothing; NULL =
+                                      they invert idx themselves, as before. The struct gained this trailing field with the
+                                      index plans (56 -> 64 bytes): callers MUST zero-initialise pn2_group_src (memset / = {0})
+                                      before filling it. */
 } pn2_group_src;
 
 typedef struct pn2_bn_layer {
@@ -580,6 +623,10 @@ typedef struct pn2_fp_src {
     const float *points1;          /* (b,n,c1) skip features; NULL iff c1 == 0 */
     const int *idx;                /* (b,n,3) three_nn's indices */
     const float *dist;             /* (b,n,3) three_nn's squared distances (forward) */
+    const void *idx_plan;          /* pn2_three_interpolate_plan(b, n, m, idx, ...) of THIS idx, or NULL: backward reduces from
+                                      it (pn2_three_interpolate_grad_planned) instead of inverting idx. The struct gained this
+                                      trailing field with the index plans (56 -> 64 bytes): callers MUST zero-initialise
+                                      pn2_fp_src (memset / = {0}) before filling it. */
 } pn2_fp_src;
 int pn2_mlp_train_fp_supported(int b, int n, int m, int c2, int c1, int nlayers, const int *widths /* c2 + c1, cout_1 .. cout_L */);
 long long pn2_mlp_train_ws_bytes_fp(int b, int n, int m, int c2, int c1, int nlayers, const int *widths, int backward,
@@ -635,6 +682,10 @@ int pn2_fp_interp_concat(int b, int n, int m, int c2, int c1, int pitch, const f
 int pn2_fp_interp_concat_grad(int b, int n, int m, int c2, int c1, int pitch, const float *grad_x, const int *idx,
                               const float *weight, float *grad_points2, float *grad_points1, float *scratch, void *ws_seg,
                               int deterministic, void *stream);
+/* the same from an index plan of idx (pn2_three_interpolate_plan(b, n, m, idx, ...)) in place of idx and ws_seg */
+int pn2_fp_interp_concat_grad_planned(int b, int n, int m, int c2, int c1, int pitch, const float *grad_x, const void *plan,
+                                      const float *weight, float *grad_points2, float *grad_points1, float *scratch,
+                                      int deterministic, void *stream);
 
 /* diagnostics: byte offsets inside the BACKWARD workspace of the two dy buffers ((rows, max width) each; after a
  * backward of L layers they hold dy_{L-1}, dy_{L-2}, ... alternately, starting with gb when pooled) and of the

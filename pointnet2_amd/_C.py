@@ -56,6 +56,15 @@ _SIGNATURES = {
     "pn2_seg_grad_plan": [_i, ctypes.c_longlong, _i, ctypes.c_longlong, _vp, _vp],
     "pn2_group_point_grad_seg": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
     "pn2_three_interpolate_grad_seg": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "pn2_seg_plan_bytes": [_i, _i, _ll],
+    "pn2_seg_plan_layout": [_i, _i, _ll, _vp, _vp, _vp],
+    "pn2_group_point_plan": [_i, _i, _i, _i, _vp, _i, _vp, _vp],
+    "pn2_three_interpolate_plan": [_i, _i, _i, _vp, _i, _vp, _vp],
+    "pn2_group_point_grad_planned": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp],
+    "pn2_three_interpolate_grad_planned": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
+    "pn2_group_point_grad_planned_ex": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "pn2_three_interpolate_grad_planned_ex": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "pn2_fp_interp_concat_grad_planned": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "pn2_sa_mlp3_config": [_i, _i, _i, _i, _i, _vp, _vp, _vp],
     "pn2_sa_mlp3_pack": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_sa_mlp3_maxpool": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
@@ -117,6 +126,7 @@ _RESTYPES = {
     "pn2_fps_ordered_ws_bytes": ctypes.c_longlong,
     "pn2_det_grad_ws_bytes": ctypes.c_longlong,
     "pn2_seg_grad_ws_bytes": ctypes.c_longlong,
+    "pn2_seg_plan_bytes": ctypes.c_longlong,
     "pn2_sample_and_group_ws_bytes": ctypes.c_longlong,
     "pn2_sa_mlp3_ws_bytes": ctypes.c_longlong,
     "pn2_fp_mlp_ws_bytes": ctypes.c_longlong,

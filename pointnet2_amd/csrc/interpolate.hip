@@ -525,9 +525,10 @@ extern "C" int pn2_fp_interp_concat(int b, int n, int m, int c2, int c1, int pit
                   points2, points1, idx, dist, out, weight);
 }
 
-extern "C" int pn2_fp_interp_concat_grad(int b, int n, int m, int c2, int c1, int pitch, const float *grad_x, const int *idx,
-                                         const float *weight, float *grad_points2, float *grad_points1, float *scratch,
-                                         void *ws_seg, int deterministic, void *stream)
+// idx + ws_seg (the inversion runs here), or an index plan of idx (pn2_three_interpolate_plan; nothing is inverted)
+static int fp_interp_concat_grad(int b, int n, int m, int c2, int c1, int pitch, const float *grad_x, const int *idx, const void *plan,
+                                 const float *weight, float *grad_points2, float *grad_points1, float *scratch, void *ws_seg,
+                                 int deterministic, void *stream)
 {
     using namespace pn2;
     if (b < 0 || n < 0 || m <= 0 || c2 <= 0 || c1 < 0 || pitch < c2 + c1) return PN2_E_SHAPE;
@@ -540,11 +541,29 @@ extern "C" int pn2_fp_interp_concat_grad(int b, int n, int m, int c2, int c1, in
         }
         return PN2_OK;
     }
-    if (!grad_x || !idx || !weight || !scratch || !ws_seg || !grad_points2) return PN2_E_NULL;
+    if (!grad_x || !(plan ? plan : (const void *)idx) || !weight || !scratch || !(plan ? plan : (const void *)ws_seg) || !grad_points2)
+        return PN2_E_NULL;
     const long long elems = rows * (c2 + (grad_points1 ? c1 : 0));
     if (int rc = launch(fp_split_grad_kernel, dim3(grid_for(elems)), dim3(kThreads), 0, as_stream(stream), elems, c2,
                         grad_points1 ? c1 : 0, pitch, grad_x, scratch, grad_points1)) return rc;
+    if (plan) return pn2_three_interpolate_grad_planned(b, n, c2, m, scratch, plan, weight, grad_points2, deterministic, stream);
     return pn2_three_interpolate_grad_seg(b, n, c2, m, scratch, idx, weight, grad_points2, ws_seg, deterministic, stream);
+}
+
+extern "C" int pn2_fp_interp_concat_grad(int b, int n, int m, int c2, int c1, int pitch, const float *grad_x, const int *idx,
+                                         const float *weight, float *grad_points2, float *grad_points1, float *scratch,
+                                         void *ws_seg, int deterministic, void *stream)
+{
+    return fp_interp_concat_grad(b, n, m, c2, c1, pitch, grad_x, idx, nullptr, weight, grad_points2, grad_points1, scratch, ws_seg,
+                                 deterministic, stream);
+}
+
+extern "C" int pn2_fp_interp_concat_grad_planned(int b, int n, int m, int c2, int c1, int pitch, const float *grad_x, const void *plan,
+                                                 const float *weight, float *grad_points2, float *grad_points1, float *scratch,
+                                                 int deterministic, void *stream)
+{
+    return fp_interp_concat_grad(b, n, m, c2, c1, pitch, grad_x, nullptr, plan, weight, grad_points2, grad_points1, scratch, nullptr,
+                                 deterministic, stream);
 }
 
 // variant: 0 = the library's choice, 1 = the sweep (three_nn_kernel), 2 = the cell list (PN2_E_ARG where it does not exist:

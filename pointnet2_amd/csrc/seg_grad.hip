@@ -56,18 +56,26 @@ __global__ __launch_bounds__(kSegThreads) void seg_count_kernel(long long total,
 }
 
 // one workgroup per cloud: exclusive scan of the counts -> start[0..rows], cursor = start
-__global__ __launch_bounds__(1024) void seg_scan_kernel(int rows, int *__restrict__ start, int *__restrict__ cursor)
+// long_count != NULL (an index plan is being built): the rows of long_from references or more are appended to the cloud's table
+// long_rows[cloud][cap] in whatever order the lanes arrive (cap > entries / long_from: the table cannot overflow)
+__global__ __launch_bounds__(1024) void seg_scan_kernel(int rows, int *__restrict__ start, int *__restrict__ cursor, int long_from,
+                                                        long long cap, int *__restrict__ long_count, int *__restrict__ long_rows)
 {
     __shared__ int wsum[16];
     __shared__ int carry_s;
+    __shared__ int ntab;
     int *cnt = cursor + (size_t)blockIdx.x * rows;              // counts were accumulated in the cursor array
     int *st = start + (size_t)blockIdx.x * (rows + 1);
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) carry_s = 0;
+    if (t == 0) { carry_s = 0; ntab = 0; }
     __syncthreads();
     for (int base = 0; base < rows; base += 1024) {
         const int r = base + t;
         const int v = r < rows ? cnt[r] : 0;
+        if (long_count && v >= long_from) {
+            const int slot = atomicAdd(&ntab, 1);
+            if (slot < cap) long_rows[blockIdx.x * cap + slot] = r;
+        }
         int incl = v;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -86,7 +94,10 @@ __global__ __launch_bounds__(1024) void seg_scan_kernel(int rows, int *__restric
         if (t == 1023) carry_s = off + incl;
         __syncthreads();
     }
-    if (t == 0) st[rows] = carry_s;
+    if (t == 0) {
+        st[rows] = carry_s;
+        if (long_count) long_count[blockIdx.x] = (int)(ntab < cap ? ntab : cap);
+    }
 }
 
 __global__ __launch_bounds__(kSegThreads) void seg_fill_kernel(long long total, long long entries, int rows,
@@ -148,20 +159,22 @@ __device__ __forceinline__ void seg_rank_sort(int *llist, int beg, int len, int 
 template <bool SORT, bool LDSLIST = SORT, bool RUNS = false, int KEEP = 0>
 __global__ __launch_bounds__(1024) void seg_invert_lds_kernel(long long entries, int rows, const int *__restrict__ idx,
                                                               int *__restrict__ start, int *__restrict__ sorted,
-                                                              int *__restrict__ list)
+                                                              int *__restrict__ list, int long_from, long long cap,
+                                                              int *__restrict__ long_count, int *__restrict__ long_rows)
 {
     extern __shared__ int smem_i[];
     int *cnt = smem_i;                                            // [rows]
     int *llist = smem_i + rows;                                   // [entries] when SORT
     __shared__ int wsum[16];
     __shared__ int carry_s;
+    __shared__ int ntab;                                          // long rows listed so far (long_count != NULL: see seg_scan_kernel)
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int *my = idx + (size_t)blockIdx.x * entries;
     int *st = start + (size_t)blockIdx.x * (rows + 1);
     int *flags = sorted + (size_t)blockIdx.x * rows;
     int *out = list + (size_t)blockIdx.x * entries;
     for (int r = t; r < rows; r += 1024) cnt[r] = 0;
-    if (t == 0) carry_s = 0;
+    if (t == 0) { carry_s = 0; ntab = 0; }
     __syncthreads();
     // (both passes over idx fetch eight entries per thread before they touch the counters: a loop of load -> LDS atomic pays
     // the global latency per entry -- 24 per thread at sem_seg FP4, where the inversion was 17 us of the gradient's 45)
@@ -215,6 +228,10 @@ __global__ __launch_bounds__(1024) void seg_invert_lds_kernel(long long entries,
     for (int base = 0; base < rows; base += 1024) {
         const int r = base + t;
         const int v = r < rows ? cnt[r] : 0;
+        if (long_count && v >= long_from) {                       // the counts are in hand here and nowhere later
+            const int slot = atomicAdd(&ntab, 1);
+            if (slot < cap) long_rows[blockIdx.x * cap + slot] = r;
+        }
         int incl = v;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -233,7 +250,10 @@ __global__ __launch_bounds__(1024) void seg_invert_lds_kernel(long long entries,
         if (t == 1023) carry_s = off + incl;
         __syncthreads();
     }
-    if (t == 0) st[rows] = carry_s;
+    if (t == 0) {
+        st[rows] = carry_s;
+        if (long_count) long_count[blockIdx.x] = (int)(ntab < cap ? ntab : cap);
+    }
     auto place = [&](long long b0, const int (&v)[kInvU]) __attribute__((always_inline)) {
         int pos[kInvU];
         bool ok[kInvU];
@@ -500,17 +520,99 @@ inline int seg_long_from(long long entries, int rows)
 }
 constexpr int kSegLongThreads = 512;
 
+// One long row summed by the whole workgroup (every thread calls it with the same row): the 512 / LPR lane groups take every
+// (512 / LPR)-th batch of four entries, the partial rows meet in LDS and are added in group order. Which workgroup sums a row,
+// and how it found it, does not enter the result.
+template <int LPR, int SRC_DIV>
+__device__ __forceinline__ void seg_long_row(long long row, long long i, int rbeg, int rlen, long long entries, int c,
+                                             const float *__restrict__ grad_out, const float *__restrict__ weight,
+                                             const int *__restrict__ list, float *__restrict__ out)
+{
+    constexpr int NG = kSegLongThreads / LPR;                      // lane groups per workgroup
+    __shared__ float4 part[kSegLongThreads];                       // [NG][LPR]
+    const int t = threadIdx.x, g = t / LPR, gl = t % LPR;
+    const int *seg = list + i * entries + rbeg;
+    const float *src = grad_out + (size_t)i * (entries / SRC_DIV) * c;
+    const float *wsrc = weight ? weight + (size_t)i * entries : nullptr;
+    // a lane owns the float4s gl and gl + LPR of the row (the second one where the row is wider than LPR float4s:
+    // c = 320 on 64 lanes -- as a second pass over the segment it cost the whole pass again for a quarter of the
+    // lanes); rows wider than 2 LPR float4s take more sweeps of the segment
+    const int per = c / 4;
+    for (int f0 = 0; f0 < per; f0 += 2 * LPR) {
+        const int fa = f0 + gl, fb = f0 + LPR + gl;
+        const bool oka = fa < per, okb = fb < per;
+        const int ca = (oka ? fa : 0) * 4, cb = (okb ? fb : 0) * 4;
+        const bool wide = f0 + LPR < per;               // workgroup-uniform: somebody owns a second float4
+        float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
+        // eight row loads in flight per lane either way: two batches of four entries (one float4 each), or one
+        // batch with both float4s of the lane
+        auto sweep = [&](auto widec) __attribute__((always_inline)) {
+            constexpr bool WIDE = decltype(widec)::value;
+            constexpr int NE = 8;                     // (wide rows too: a 1000-entry row of c = 320 is the end of the launch -- 32 entries per batch made it 31 dependent batches)
+            // (fetching the NEXT batch's entry numbers ahead of this batch's rows -- one round trip per batch instead of two
+            // -- was measured: c = 320 172 -> 163 us, c = 128 38.5 -> 42.7: not kept)
+            for (int p = g * 4; p < rlen; p += NG * NE) {
+                int e[NE];
+                float wq[NE];
+                float4 va[NE], vb[WIDE ? NE : 1];
+#pragma unroll
+                for (int u = 0; u < NE; ++u) {
+                    const int pe = p + (u >> 2) * NG * 4 + (u & 3);
+                    e[u] = seg[pe < rlen ? pe : rlen - 1];
+                }
+#pragma unroll
+                for (int u = 0; u < NE; ++u) {
+                    const float *rowp = src + (size_t)(e[u] / SRC_DIV) * c;
+                    va[u] = *reinterpret_cast<const float4 *>(rowp + ca);
+                    if (WIDE) vb[u] = *reinterpret_cast<const float4 *>(rowp + cb);
+                    wq[u] = wsrc ? wsrc[e[u]] : 1.0f;
+                }
+#pragma unroll
+                for (int u = 0; u < NE; ++u) {
+                    const int pe = p + (u >> 2) * NG * 4 + (u & 3);
+                    if (pe < rlen) {
+                        float4 x = va[u];
+                        if (wsrc) { x.x = __fmul_rn(x.x, wq[u]); x.y = __fmul_rn(x.y, wq[u]); x.z = __fmul_rn(x.z, wq[u]); x.w = __fmul_rn(x.w, wq[u]); }
+                        acc0.x = __fadd_rn(acc0.x, x.x); acc0.y = __fadd_rn(acc0.y, x.y); acc0.z = __fadd_rn(acc0.z, x.z); acc0.w = __fadd_rn(acc0.w, x.w);
+                        if (WIDE) {
+                            float4 y = vb[u];
+                            if (wsrc) { y.x = __fmul_rn(y.x, wq[u]); y.y = __fmul_rn(y.y, wq[u]); y.z = __fmul_rn(y.z, wq[u]); y.w = __fmul_rn(y.w, wq[u]); }
+                            acc1.x = __fadd_rn(acc1.x, y.x); acc1.y = __fadd_rn(acc1.y, y.y); acc1.z = __fadd_rn(acc1.z, y.z); acc1.w = __fadd_rn(acc1.w, y.w);
+                        }
+                    }
+                }
+            }
+        };
+        if (wide) sweep(std::true_type()); else sweep(std::false_type());
+        for (int half = 0; half < (wide ? 2 : 1); ++half) {
+            float4 mine = acc0;
+            if (half) mine = acc1;
+            part[g * LPR + gl] = mine;
+            __syncthreads();
+            const bool okh = half ? okb : oka;
+            if (g == 0 && okh) {
+                float4 sum = part[gl];
+#pragma unroll 4
+                for (int k = 1; k < NG; ++k) {
+                    const float4 o = part[k * LPR + gl];
+                    sum.x = __fadd_rn(sum.x, o.x); sum.y = __fadd_rn(sum.y, o.y); sum.z = __fadd_rn(sum.z, o.z); sum.w = __fadd_rn(sum.w, o.w);
+                }
+                *reinterpret_cast<float4 *>(out + row * c + (half ? cb : ca)) = sum;
+            }
+            __syncthreads();
+        }
+    }
+}
+
 template <int LPR, int SRC_DIV>
 __device__ __forceinline__ void seg_reduce_long_body(unsigned blk, unsigned nblk, long long out_rows, int rows, long long entries, int c,
                                                      const float *__restrict__ grad_out, const float *__restrict__ weight,
                                                      const int *__restrict__ start, const int *__restrict__ list,
                                                      float *__restrict__ out, int long_from)
 {
-    constexpr int NG = kSegLongThreads / LPR;                      // lane groups per workgroup
-    __shared__ float4 part[kSegLongThreads];                       // [NG][LPR]
     __shared__ int row_beg[kSegLongThreads], row_len[kSegLongThreads];
     __shared__ unsigned long long long_mask[kSegLongThreads / 64];
-    const int t = threadIdx.x, g = t / LPR, gl = t % LPR, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     // the workgroup looks at rows blockIdx.x + k gridDim.x (long rows sit at the low indices of every cloud: interleaved, they
     // spread over the workgroups), 512 of them per pass, one per thread
     for (long long base = blk; base < out_rows; base += (long long)nblk * kSegLongThreads) {
@@ -534,79 +636,7 @@ __device__ __forceinline__ void seg_reduce_long_body(unsigned blk, unsigned nblk
                 todo &= todo - 1;
                 const int q = w2 * 64 + bit;                        // the thread slot that looked at this row
                 const long long row = base + (long long)q * nblk;
-                const long long i = row / rows;
-                const int rbeg = row_beg[q], rlen = row_len[q];
-                const int *seg = list + i * entries + rbeg;
-                const float *src = grad_out + (size_t)i * (entries / SRC_DIV) * c;
-                const float *wsrc = weight ? weight + (size_t)i * entries : nullptr;
-                // a lane owns the float4s gl and gl + LPR of the row (the second one where the row is wider than LPR float4s:
-                // c = 320 on 64 lanes -- as a second pass over the segment it cost the whole pass again for a quarter of the
-                // lanes); rows wider than 2 LPR float4s take more sweeps of the segment
-                const int per = c / 4;
-                for (int f0 = 0; f0 < per; f0 += 2 * LPR) {
-                    const int fa = f0 + gl, fb = f0 + LPR + gl;
-                    const bool oka = fa < per, okb = fb < per;
-                    const int ca = (oka ? fa : 0) * 4, cb = (okb ? fb : 0) * 4;
-                    const bool wide = f0 + LPR < per;               // workgroup-uniform: somebody owns a second float4
-                    float4 acc0 = make_float4(0.f, 0.f, 0.f, 0.f), acc1 = acc0;
-                    // eight row loads in flight per lane either way: two batches of four entries (one float4 each), or one
-                    // batch with both float4s of the lane
-                    auto sweep = [&](auto widec) __attribute__((always_inline)) {
-                        constexpr bool WIDE = decltype(widec)::value;
-                        constexpr int NE = 8;                     // (wide rows too: a 1000-entry row of c = 320 is the end of the launch -- 32 entries per batch made it 31 dependent batches)
-                        // (fetching the NEXT batch's entry numbers ahead of this batch's rows -- one round trip per batch instead of two
-                        // -- was measured: c = 320 172 -> 163 us, c = 128 38.5 -> 42.7: not kept)
-                        for (int p = g * 4; p < rlen; p += NG * NE) {
-                            int e[NE];
-                            float wq[NE];
-                            float4 va[NE], vb[WIDE ? NE : 1];
-#pragma unroll
-                            for (int u = 0; u < NE; ++u) {
-                                const int pe = p + (u >> 2) * NG * 4 + (u & 3);
-                                e[u] = seg[pe < rlen ? pe : rlen - 1];
-                            }
-#pragma unroll
-                            for (int u = 0; u < NE; ++u) {
-                                const float *rowp = src + (size_t)(e[u] / SRC_DIV) * c;
-                                va[u] = *reinterpret_cast<const float4 *>(rowp + ca);
-                                if (WIDE) vb[u] = *reinterpret_cast<const float4 *>(rowp + cb);
-                                wq[u] = wsrc ? wsrc[e[u]] : 1.0f;
-                            }
-#pragma unroll
-                            for (int u = 0; u < NE; ++u) {
-                                const int pe = p + (u >> 2) * NG * 4 + (u & 3);
-                                if (pe < rlen) {
-                                    float4 x = va[u];
-                                    if (wsrc) { x.x = __fmul_rn(x.x, wq[u]); x.y = __fmul_rn(x.y, wq[u]); x.z = __fmul_rn(x.z, wq[u]); x.w = __fmul_rn(x.w, wq[u]); }
-                                    acc0.x = __fadd_rn(acc0.x, x.x); acc0.y = __fadd_rn(acc0.y, x.y); acc0.z = __fadd_rn(acc0.z, x.z); acc0.w = __fadd_rn(acc0.w, x.w);
-                                    if (WIDE) {
-                                        float4 y = vb[u];
-                                        if (wsrc) { y.x = __fmul_rn(y.x, wq[u]); y.y = __fmul_rn(y.y, wq[u]); y.z = __fmul_rn(y.z, wq[u]); y.w = __fmul_rn(y.w, wq[u]); }
-                                        acc1.x = __fadd_rn(acc1.x, y.x); acc1.y = __fadd_rn(acc1.y, y.y); acc1.z = __fadd_rn(acc1.z, y.z); acc1.w = __fadd_rn(acc1.w, y.w);
-                                    }
-                                }
-                            }
-                        }
-                    };
-                    if (wide) sweep(std::true_type()); else sweep(std::false_type());
-                    for (int half = 0; half < (wide ? 2 : 1); ++half) {
-                        float4 mine = acc0;
-                        if (half) mine = acc1;
-                        part[g * LPR + gl] = mine;
-                        __syncthreads();
-                        const bool okh = half ? okb : oka;
-                        if (g == 0 && okh) {
-                            float4 sum = part[gl];
-#pragma unroll 4
-                            for (int k = 1; k < NG; ++k) {
-                                const float4 o = part[k * LPR + gl];
-                                sum.x = __fadd_rn(sum.x, o.x); sum.y = __fadd_rn(sum.y, o.y); sum.z = __fadd_rn(sum.z, o.z); sum.w = __fadd_rn(sum.w, o.w);
-                            }
-                            *reinterpret_cast<float4 *>(out + row * c + (half ? cb : ca)) = sum;
-                        }
-                        __syncthreads();
-                    }
-                }
+                seg_long_row<LPR, SRC_DIV>(row, row / rows, row_beg[q], row_len[q], entries, c, grad_out, weight, list, out);
             }
         }
         __syncthreads();                                            // row_beg / row_len / long_mask are rewritten by the next pass
@@ -614,20 +644,102 @@ __device__ __forceinline__ void seg_reduce_long_body(unsigned blk, unsigned nblk
 }
 
 
+
+// The same long-row part for a launch that has an index PLAN (pn2_*_plan): the plan lists every cloud's long rows (long_count[b],
+// long_rows[b][cap], written by the inversion while it had the counts), so nothing is assumed about WHERE the long rows are --
+// kNN lists and user-supplied idx put them anywhere, and long rows at row numbers congruent modulo the stride are all one
+// workgroup's in the walk above. Table entries are dealt round-robin: workgroup w takes the flat slots w, w + nblk, ...; a slot
+// maps to (cloud, entry) through the running sum of the counts, which every workgroup forms once in LDS (one load per thread and
+// a scan: a walk over the clouds with one dependent load each cost 6 us at 32 clouds). As in the stride walk, one thread per
+// slot then looks its row up (table entry, then its start pair), and the workgroup sums the rows it found one after the other.
+// The order of a cloud's table depends on timing; a row's sum (seg_long_row) does not depend on who computes it.
+constexpr int kSegTableClouds = 2048;                              // clouds whose running sum fits the LDS array (more: the stride walk)
+
+template <int LPR, int SRC_DIV>
+__device__ __forceinline__ void seg_reduce_table_body(unsigned blk, unsigned nblk, int b, int rows, long long entries, int c,
+                                                      const float *__restrict__ grad_out, const float *__restrict__ weight,
+                                                      const int *__restrict__ start, const int *__restrict__ list,
+                                                      const int *__restrict__ long_count, const int *__restrict__ long_rows,
+                                                      long long cap, float *__restrict__ out)
+{
+    __shared__ int cum[kSegTableClouds + 1];                       // cum[i]: flat slot of cloud i's first table entry
+    __shared__ int row_id[kSegLongThreads], row_beg[kSegLongThreads], row_len[kSegLongThreads];
+    __shared__ int wsum[kSegLongThreads / 64];
+    __shared__ int carry_s;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    if (t == 0) { carry_s = 0; cum[0] = 0; }
+    __syncthreads();
+    for (int c0 = 0; c0 < b; c0 += kSegLongThreads) {
+        const int i = c0 + t;
+        int v = i < b ? long_count[i] : 0;
+        v = v < 0 ? 0 : (long long)v > cap ? (int)cap : v;
+        int incl = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(incl, o);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        int off = carry_s;
+        for (int k = 0; k < wv; ++k) off += wsum[k];
+        if (i < b) cum[i + 1] = off + incl;
+        __syncthreads();
+        if (t == kSegLongThreads - 1) carry_s = off + incl;
+        __syncthreads();
+    }
+    const long long total = cum[b];
+    for (long long s0 = blk; s0 < total; s0 += (long long)nblk * kSegLongThreads) {
+        const long long s = s0 + (long long)t * nblk;
+        int id = -1, beg = 0, len = 0;
+        if (s < total) {
+            int lo = 0, hi = b - 1;                                  // the last cloud whose first slot is <= s
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (cum[mid] <= s) lo = mid; else hi = mid - 1;
+            }
+            const int r = long_rows[lo * cap + (s - cum[lo])];
+            if ((unsigned)r < (unsigned)rows) {                      // (anything else is not a plan of this shape: nothing is read through it)
+                const int *st = start + (long long)lo * (rows + 1) + r;
+                beg = st[0];
+                len = st[1] - beg;
+                id = lo * rows + r;
+            }
+        }
+        row_id[t] = id; row_beg[t] = beg; row_len[t] = len;
+        __syncthreads();
+        const long long left = (total - s0 + nblk - 1) / nblk;       // slots of this pass (workgroup-uniform)
+        const int npass = left < kSegLongThreads ? (int)left : kSegLongThreads;
+        for (int q = 0; q < npass; ++q) {
+            const int row = row_id[q];                              // workgroup-uniform
+            if (row < 0) continue;
+            seg_long_row<LPR, SRC_DIV>(row, row / rows, row_beg[q], row_len[q], entries, c, grad_out, weight, list, out);
+        }
+        __syncthreads();                                            // row_id / row_beg / row_len are rewritten by the next pass
+    }
+}
+
 // ONE launch for both (default mode): blocks [0, nlong) sum the long rows -- dependent chains of row loads, dispatched first --,
 // the other blocks the short rows at streaming rate beside them (as two launches: 18 + 38 us at cls_ssg L2, 107 + 147 at
 // cls_msg L2; the long-row kernel alone uses a fraction of the memory system)
-template <int LPR, int SRC_DIV, bool WIDE = false>
+// TABLE: the long rows come from a plan's table (seg_reduce_table_body) instead of the stride walk; the short part is the same.
+template <int LPR, int SRC_DIV, bool WIDE = false, bool TABLE = false>
 __global__ __launch_bounds__(kSegLongThreads) void seg_reduce_split_kernel(unsigned nlong, long long out_rows, int rows, long long entries,
                                                                            int c, const float *__restrict__ grad_out,
                                                                            const float *__restrict__ weight,
                                                                            const int *__restrict__ start,
                                                                            const int *__restrict__ sorted,
-                                                                           const int *__restrict__ list, float *__restrict__ out, int long_from)
+                                                                           const int *__restrict__ list, float *__restrict__ out, int long_from,
+                                                                           const int *__restrict__ long_count,
+                                                                           const int *__restrict__ long_rows, long long cap)
 {
-    if (blockIdx.x < nlong)
-        seg_reduce_long_body<LPR, SRC_DIV>(blockIdx.x, nlong, out_rows, rows, entries, c, grad_out, weight, start, list, out, long_from);
-    else {
+    if (blockIdx.x < nlong) {
+        if (TABLE)
+            seg_reduce_table_body<LPR, SRC_DIV>(blockIdx.x, nlong, (int)(out_rows / rows), rows, entries, c, grad_out, weight, start, list,
+                                                long_count, long_rows, cap, out);
+        else
+            seg_reduce_long_body<LPR, SRC_DIV>(blockIdx.x, nlong, out_rows, rows, entries, c, grad_out, weight, start, list, out, long_from);
+    } else {
         // Workgroups go to the eight XCDs round-robin, each XCD has an L2 of its own, and a gradient row of three_interpolate is
         // referenced by THREE target rows: target rows dealt to workgroups in launch order put those three readers on three XCDs
         // (PMC traffic 2.7 x algorithmic at sem_seg FP4). Every eighth workgroup -- one XCD -- therefore takes one CONTIGUOUS
@@ -668,9 +780,15 @@ static long long seg_long_blocks(long long out_rows, int rows, bool wide)
     return wg;
 }
 
+// the long-row table of an index plan (all NULL / 0: no plan, or the stride walk was asked for)
+struct SegTable {
+    int *count, *rows;
+    long long cap;
+};
+
 template <bool DET, int SRC_DIV>
 static int launch_reduce(long long out_rows, int rows, long long entries, int c, const float *grad_out, const float *weight,
-                         const SegWs &w, float *out, hipStream_t st)
+                         const SegWs &w, float *out, hipStream_t st, const SegTable &tab = SegTable{nullptr, nullptr, 0})
 {
     // 16-byte row accesses need 16-byte aligned bases (a C-ABI caller may pass a sub-allocated pointer)
     const bool vec4 = (c & 3) == 0 && ((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
@@ -688,11 +806,12 @@ static int launch_reduce(long long out_rows, int rows, long long entries, int c,
                with wg = rows = 512 every cloud's row r went to workgroup r and thirty workgroups did all the work (1758 us) */ \
             const long long wg = seg_long_blocks(out_rows, rows, L >= 64);                                           \
             const unsigned ga = (seg_grid(threads, kSegLongThreads) + 7u) & ~7u;   /* a multiple of 8: seg_reduce_split_kernel's XCD map */ \
-            if (L == 64 && per > 64 && per <= 128)              /* c in (256, 512]: both float4s of a lane in one sweep */ \
-                return launch((seg_reduce_split_kernel<64, SRC_DIV, true>), dim3((unsigned)wg + ga), dim3(kSegLongThreads), 0, st, \
-                              (unsigned)wg, out_rows, rows, entries, c, grad_out, weight, w.start, w.sorted, w.list, out, seg_long_from(entries, rows)); \
-            return launch((seg_reduce_split_kernel<(L >= 16 ? L : 16), SRC_DIV>), dim3((unsigned)wg + ga), dim3(kSegLongThreads), 0, st, \
-                          (unsigned)wg, out_rows, rows, entries, c, grad_out, weight, w.start, w.sorted, w.list, out, seg_long_from(entries, rows)); \
+            const bool wide2 = L == 64 && per > 64 && per <= 128;   /* c in (256, 512]: both float4s of a lane in one sweep */ \
+            auto kern = wide2 ? (tab.count ? seg_reduce_split_kernel<64, SRC_DIV, true, true> : seg_reduce_split_kernel<64, SRC_DIV, true, false>) \
+                              : (tab.count ? seg_reduce_split_kernel<(L >= 16 ? L : 16), SRC_DIV, false, true>               \
+                                           : seg_reduce_split_kernel<(L >= 16 ? L : 16), SRC_DIV, false, false>);            \
+            return launch(kern, dim3((unsigned)wg + ga), dim3(kSegLongThreads), 0, st, (unsigned)wg, out_rows, rows, entries, c, grad_out, \
+                          weight, w.start, w.sorted, w.list, out, seg_long_from(entries, rows), tab.count, tab.rows, tab.cap); \
         }                                                                                                            \
         if (vec4)                                                                                                    \
             return launch((seg_reduce_kernel<L, true, DET, SRC_DIV>), dim3(seg_grid(threads)), dim3(kSegThreads), 0, st, \
@@ -705,13 +824,13 @@ static int launch_reduce(long long out_rows, int rows, long long entries, int c,
     return PN2_E_TOO_LARGE;
 }
 
-// invert idx (b clouds x `entries` references into `rows` targets), then reduce
+// invert idx (b clouds x `entries` references into `rows` targets) into w; tab.count != NULL: list the long rows too (a plan)
 template <int SRC_DIV>
-static int seg_grad(int b, int rows, long long entries, int c, const float *grad_out, const int *idx, const float *weight,
-                    float *out, void *ws, int deterministic, hipStream_t st)
+static int seg_invert(int b, int rows, long long entries, const int *idx, const SegWs &w, const SegTable &tab, int deterministic,
+                      hipStream_t st)
 {
-    SegWs w = seg_ws(ws, b, rows, entries);
     const long long total = (long long)b * entries;
+    const int long_from = seg_long_from(entries, rows);
     if (rows <= kSegLdsRows && b >= 4) {
         // enough clouds to spread over CUs: the whole inversion of a cloud in one workgroup, LDS counters
         const size_t with_list = sizeof(int) * ((size_t)rows + (size_t)entries);
@@ -728,16 +847,84 @@ static int seg_grad(int b, int rows, long long entries, int c, const float *grad
             else if (nb == 4) kern = seg_invert_lds_kernel<false, true, RUNS, 4>;
         }
         if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        if (int rc = launch(kern, dim3(b), dim3(1024), lds, st, entries, rows, idx, w.start, w.sorted, w.list)) return rc;
-    } else {
+        return launch(kern, dim3(b), dim3(1024), lds, st, entries, rows, idx, w.start, w.sorted, w.list, long_from, tab.cap, tab.count,
+                      tab.rows);
+    }
     if (int rc = clear_async(w.cursor, 2 * sizeof(int) * (size_t)b * rows, st)) return rc;   // counters and sorted flags
     if (int rc = launch(seg_count_kernel, dim3(seg_grid(total)), dim3(kSegThreads), 0, st, total, entries, rows, idx, w.cursor)) return rc;
-    if (int rc = launch(seg_scan_kernel, dim3(b), dim3(1024), 0, st, rows, w.start, w.cursor)) return rc;
-    if (int rc = launch(seg_fill_kernel, dim3(seg_grid(total)), dim3(kSegThreads), 0, st, total, entries, rows, idx, w.cursor, w.list)) return rc;
-    }
+    if (int rc = launch(seg_scan_kernel, dim3(b), dim3(1024), 0, st, rows, w.start, w.cursor, long_from, tab.cap, tab.count, tab.rows)) return rc;
+    return launch(seg_fill_kernel, dim3(seg_grid(total)), dim3(kSegThreads), 0, st, total, entries, rows, idx, w.cursor, w.list);
+}
+
+// invert, then reduce
+template <int SRC_DIV>
+static int seg_grad(int b, int rows, long long entries, int c, const float *grad_out, const int *idx, const float *weight,
+                    float *out, void *ws, int deterministic, hipStream_t st)
+{
+    SegWs w = seg_ws(ws, b, rows, entries);
+    if (int rc = seg_invert<SRC_DIV>(b, rows, entries, idx, w, SegTable{nullptr, nullptr, 0}, deterministic, st)) return rc;
     const long long out_rows = (long long)b * rows;
     return deterministic ? launch_reduce<true, SRC_DIV>(out_rows, rows, entries, c, grad_out, weight, w, out, st)
                          : launch_reduce<false, SRC_DIV>(out_rows, rows, entries, c, grad_out, weight, w, out, st);
+}
+
+// ---- index plans: the inversion as a call of its own --------------------------------------------------------------------------
+// A plan is the workspace above (the cursor array is scratch of the build and dead afterwards) followed by the long-row table:
+//   start int[b (rows + 1)] | cursor int[b rows] | sorted int[b rows] | list int[b entries] | long_count int[b] | long_rows int[b cap]
+// cap = entries / 32 + 1: a table row has at least seg_long_from() >= 32 references, so a cloud has at most entries / 32 of them.
+// The gradient calls only read it (every kernel parameter that points into it is const int * __restrict__).
+static inline long long seg_table_cap(long long entries) { return entries / 32 + 1; }
+
+struct SegPlan {
+    SegWs w;
+    SegTable tab;
+};
+static inline SegPlan seg_plan(const void *plan, int b, int rows, long long entries)
+{
+    SegPlan p;
+    p.w = seg_ws(const_cast<void *>(plan), b, rows, entries);
+    p.tab.count = p.w.list + (size_t)b * entries;
+    p.tab.rows = p.tab.count + b;
+    p.tab.cap = seg_table_cap(entries);
+    return p;
+}
+
+template <int SRC_DIV>
+static int seg_plan_build(int b, int rows, long long entries, const int *idx, int sorted, void *plan, void *stream)
+{
+    if (b == 0) return PN2_OK;
+    if (!plan) return PN2_E_NULL;
+    if (entries > INT_MAX || (long long)b * rows > INT_MAX) return PN2_E_TOO_LARGE;
+    if (entries == 0) return PN2_OK;                                  // the gradient of such a shape is a zero fill: it reads no plan
+    if (!idx) return PN2_E_NULL;
+    if (reinterpret_cast<uintptr_t>(plan) & 3u) return PN2_E_ARG;
+    const SegPlan p = seg_plan(plan, b, rows, entries);
+    return seg_invert<SRC_DIV>(b, rows, entries, idx, p.w, p.tab, sorted, as_stream(stream));
+}
+
+// variant: 0 = the library's choice, 1 = stride walk, 2 = table walk (default mode's long-row part; ignored where a launch has none)
+template <int SRC_DIV>
+static int seg_grad_planned(int b, int rows, long long entries, int c, const float *grad_out, const void *plan, const float *weight,
+                            float *out, int deterministic, int variant, void *stream)
+{
+    if (variant < 0 || variant > 2) return PN2_E_ARG;
+    if (b == 0) return PN2_OK;
+    if (!out) return PN2_E_NULL;
+    if (entries > INT_MAX || (long long)b * rows > INT_MAX) return PN2_E_TOO_LARGE;
+    hipStream_t st = as_stream(stream);
+    if (entries == 0) return clear_async(out, sizeof(float) * (size_t)b * rows * c, st);
+    if (!grad_out || !plan || (SRC_DIV == 3 && !weight)) return PN2_E_NULL;
+    if (reinterpret_cast<uintptr_t>(plan) & 3u) return PN2_E_ARG;
+    SegPlan p = seg_plan(plan, b, rows, entries);
+    // The library's choice is the stride walk: on ball-query lists -- every level of the reference networks -- the table walk is
+    // no faster and at cls_ssg L2 slower by more than the spread of two runs (26.5 against 24.3 us, +-0.1; 165.9 / 167.2 at
+    // cls_msg L2, 15.8 / 15.8 at sem_seg FP4: three dependent loads stand before a workgroup's first row instead of one). Where
+    // the long rows are NOT at the low point numbers the table walk is the one that stays balanced (long rows at congruent row
+    // numbers: 40 against 732 us): callers with such lists ask for variant 2 (profiles/seg_plan/).
+    if (variant != 2 || b > kSegTableClouds) p.tab = SegTable{nullptr, nullptr, 0};
+    const long long out_rows = (long long)b * rows;
+    return deterministic ? launch_reduce<true, SRC_DIV>(out_rows, rows, entries, c, grad_out, weight, p.w, out, st)
+                         : launch_reduce<false, SRC_DIV>(out_rows, rows, entries, c, grad_out, weight, p.w, out, st, p.tab);
 }
 
 }  // namespace pn2
@@ -795,4 +982,67 @@ extern "C" int pn2_three_interpolate_grad_seg(int b, int n, int c, int m, const 
     }
     if (!grad_out || !idx || !weight) return PN2_E_NULL;
     return seg_grad<3>(b, m, entries, c, grad_out, idx, weight, grad_points, ws, deterministic, st);
+}
+
+// ---- index plans (see seg_plan above) ------------------------------------------------------------------------------------------
+extern "C" long long pn2_seg_plan_bytes(int b, int rows, long long entries)
+{
+    if (b <= 0 || rows <= 0 || entries < 0) return 16;
+    return pn2_seg_grad_ws_bytes(b, rows, entries) + (long long)sizeof(int) * ((long long)b + (long long)b * pn2::seg_table_cap(entries));
+}
+
+extern "C" int pn2_seg_plan_layout(int b, int rows, long long entries, long long *offsets5, int *long_from, long long *long_cap)
+{
+    using namespace pn2;
+    if (b <= 0 || rows <= 0 || entries < 0) return PN2_E_SHAPE;
+    if (offsets5) {
+        const long long i4 = (long long)sizeof(int);
+        offsets5[0] = 0;                                              // start
+        offsets5[1] = i4 * ((long long)b * (rows + 1) + (long long)b * rows);   // sorted
+        offsets5[2] = offsets5[1] + i4 * b * rows;                    // list
+        offsets5[3] = offsets5[2] + i4 * b * entries;                 // long_count
+        offsets5[4] = offsets5[3] + i4 * b;                           // long_rows
+    }
+    if (long_from) *long_from = seg_long_from(entries, rows);
+    if (long_cap) *long_cap = seg_table_cap(entries);
+    return PN2_OK;
+}
+
+extern "C" int pn2_group_point_plan(int b, int n, int m, int nsample, const int *idx, int sorted, void *plan, void *stream)
+{
+    if (b < 0 || n <= 0 || m < 0 || nsample < 0) return PN2_E_SHAPE;
+    return pn2::seg_plan_build<1>(b, n, (long long)m * nsample, idx, sorted, plan, stream);
+}
+
+extern "C" int pn2_three_interpolate_plan(int b, int n, int m, const int *idx, int sorted, void *plan, void *stream)
+{
+    if (b < 0 || n < 0 || m <= 0) return PN2_E_SHAPE;
+    return pn2::seg_plan_build<3>(b, m, (long long)n * 3, idx, sorted, plan, stream);
+}
+
+extern "C" int pn2_group_point_grad_planned_ex(int b, int n, int c, int m, int nsample, const float *grad_out, const void *plan,
+                                               float *grad_points, int deterministic, int variant, void *stream)
+{
+    if (b < 0 || n <= 0 || c <= 0 || m < 0 || nsample < 0) return PN2_E_SHAPE;
+    return pn2::seg_grad_planned<1>(b, n, (long long)m * nsample, c, grad_out, plan, nullptr, grad_points, deterministic, variant, stream);
+}
+
+extern "C" int pn2_group_point_grad_planned(int b, int n, int c, int m, int nsample, const float *grad_out, const void *plan,
+                                            float *grad_points, int deterministic, void *stream)
+{
+    return pn2_group_point_grad_planned_ex(b, n, c, m, nsample, grad_out, plan, grad_points, deterministic, 0, stream);
+}
+
+extern "C" int pn2_three_interpolate_grad_planned_ex(int b, int n, int c, int m, const float *grad_out, const void *plan,
+                                                     const float *weight, float *grad_points, int deterministic, int variant,
+                                                     void *stream)
+{
+    if (b < 0 || n < 0 || c <= 0 || m <= 0) return PN2_E_SHAPE;
+    return pn2::seg_grad_planned<3>(b, m, (long long)n * 3, c, grad_out, plan, weight, grad_points, deterministic, variant, stream);
+}
+
+extern "C" int pn2_three_interpolate_grad_planned(int b, int n, int c, int m, const float *grad_out, const void *plan,
+                                                  const float *weight, float *grad_points, int deterministic, void *stream)
+{
+    return pn2_three_interpolate_grad_planned_ex(b, n, c, m, grad_out, plan, weight, grad_points, deterministic, 0, stream);
 }

@@ -1074,6 +1074,8 @@ struct Bwd : TlRun {
         if (S)
             return xyz_launch_rows((long long)gd.b * gd.n, L1.cout, S, nullptr, nullptr, nullptr, 1, wx, L1.w_stride_k, L1.w_stride_n,
                                    c.grad_xyz, st);
+        if (group->idx_plan)                              // the level's index plan: nothing is inverted here
+            return pn2_group_point_grad_planned(gd.b, gd.n, 3, gd.m, gd.nsample, g3, group->idx_plan, c.grad_xyz, c.reproducible, c.stream);
         return pn2_group_point_grad_seg(gd.b, gd.n, 3, gd.m, gd.nsample, g3, group->idx, c.grad_xyz, base + xp.seg, c.reproducible, c.stream);
     }
 
@@ -1273,8 +1275,10 @@ struct Bwd : TlRun {
         const pn2_bn_layer &L = layers[0];
         float *S = at<float>(pl.l1p);
         if (int rc = fp_launch_l1_dz(rows, L.cout, L.z, gcur, coef(0), st)) return rc;
-        if (int rc = pn2_three_interpolate_grad_seg(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx, fp->weight, S, base + pl.l1seg,
-                                                    c.reproducible, c.stream)) return rc;
+        if (int rc = fp->idx_plan ? pn2_three_interpolate_grad_planned(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx_plan, fp->weight, S,
+                                                                       c.reproducible, c.stream)
+                                  : pn2_three_interpolate_grad_seg(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx, fp->weight, S,
+                                                                   base + pl.l1seg, c.reproducible, c.stream)) return rc;
         if (fp->mp > fp->bm)                                  // the padding rows of S meet the zero rows of points2's copy
             if (int rc = clear_async(S + fp->bm * L.cout, sizeof(float) * (size_t)(fp->mp - fp->bm) * L.cout, st)) return rc;
         if (int rc = identity_coefficients(L.cout)) return rc;
@@ -1297,8 +1301,10 @@ struct Bwd : TlRun {
         const long long bn = (long long)gd.b * gd.n;
         float *S = at<float>(pl.l1p);
         if (int rc = launch_l1_dz(rows, gd, c.group, L, gcur, coef(0), at<float>(pl.l1part), true, st, !skip[0])) return rc;
-        if (int rc = pn2_group_point_grad_seg(gd.b, gd.n, L.cout, gd.m, gd.nsample, gcur, c.group->idx, S, base + pl.l1seg,
-                                              c.reproducible, c.stream)) return rc;
+        if (int rc = c.group->idx_plan ? pn2_group_point_grad_planned(gd.b, gd.n, L.cout, gd.m, gd.nsample, gcur, c.group->idx_plan, S,
+                                                                      c.reproducible, c.stream)
+                                       : pn2_group_point_grad_seg(gd.b, gd.n, L.cout, gd.m, gd.nsample, gcur, c.group->idx, S,
+                                                                  base + pl.l1seg, c.reproducible, c.stream)) return rc;
         if (want_xyz)                                         // (gcur holds dz_1 now)
             if (int rc = xyz_pass(gcur, nullptr, nullptr, nullptr, S)) return rc;
         if (skip[0]) {                                        // frozen statistics, no dW_1 wanted: the data gradient alone

@@ -21,6 +21,7 @@ struct FpL1 {
     long long rows, bm, mp;          // b n unknown points; b m known points, and that rounded up to a multiple of 32
     const float *points2, *points1;
     const int *idx;
+    const void *idx_plan;            // pn2_three_interpolate_plan of idx, or NULL: backward inverts idx itself
     const float *dist;
     float *weight_out;               // forward: the interpolation weights (b,n,3)
     const float *weight;             // backward: the same
@@ -37,7 +38,7 @@ inline FpL1 fp_l1(const pn2_fp_src *s)
     f.b = s->b; f.n = s->n; f.m = s->m; f.c2 = s->c2; f.c1 = s->c1;
     f.c2p = (s->c2 + 3) / 4 * 4; f.c1p = (s->c1 + 3) / 4 * 4;
     f.rows = (long long)s->b * s->n; f.bm = (long long)s->b * s->m; f.mp = (f.bm + 31) / 32 * 32;
-    f.points2 = s->points2; f.points1 = s->points1; f.idx = s->idx; f.dist = s->dist;
+    f.points2 = s->points2; f.points1 = s->points1; f.idx = s->idx; f.idx_plan = s->idx_plan; f.dist = s->dist;
     return f;
 }
 

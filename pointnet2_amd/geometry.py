@@ -23,6 +23,7 @@ them, only their stream differs (inside captured graphs the overlapped launch nu
 """
 import torch
 
+from .index_plan import IndexPlan, index_plan
 from .tf_interpolate import three_nn
 
 
@@ -52,17 +53,34 @@ class _Ready:
         return self
 
 
+def _plan_buffers(plan):
+    """The device buffers of a level's plan(s): they travel with the level's tensors (tensors(), static_copy(), copy_())."""
+    if plan is None:
+        return []
+    return [p.buffer for p in (plan if isinstance(plan, (list, tuple)) else [plan])]
+
+
+def _plan_clone(plan):
+    if plan is None:
+        return None
+    if isinstance(plan, (list, tuple)):
+        return [_plan_clone(p) for p in plan]
+    return IndexPlan(plan.buffer.clone(), plan.b, plan.rows, plan.entries, plan.kind, plan.sorted)
+
+
 class SAGeometry(_Ready):
     """One set-abstraction level: new_xyz (b, m, 3) and idx (b, m, nsample) i32 -- a list of idx, one per radius, for an
     MSG level (pointnet_util.py:156-197). fps_idx (b, m) i32: the samples' indices, kept so that a consumer whose xyz needs a
     gradient can rebuild new_xyz = gather_point(xyz, fps_idx) differentiably (the reference registers a gradient for
-    GatherPoint, tf_sampling.py:43-47); None for a geometry that was copied without it."""
+    GatherPoint, tf_sampling.py:43-47); None for a geometry that was copied without it. plan: the IndexPlan of idx (a list of
+    them, one per radius, for an MSG level) or None -- the level's training backward then inverts idx nowhere (index_plan.py)."""
 
-    __slots__ = ("new_xyz", "idx", "fps_idx")
+    __slots__ = ("new_xyz", "idx", "fps_idx", "plan")
 
-    def __init__(self, new_xyz, idx, fps_idx=None):
-        self.new_xyz, self.idx, self.fps_idx = new_xyz, idx, fps_idx
-        self._init([new_xyz] + (list(idx) if isinstance(idx, (list, tuple)) else [idx]) + ([fps_idx] if fps_idx is not None else []))
+    def __init__(self, new_xyz, idx, fps_idx=None, plan=None):
+        self.new_xyz, self.idx, self.fps_idx, self.plan = new_xyz, idx, fps_idx, plan
+        self._init([new_xyz] + (list(idx) if isinstance(idx, (list, tuple)) else [idx]) + ([fps_idx] if fps_idx is not None else []) +
+                   _plan_buffers(plan))
 
     def new_xyz_for(self, xyz):
         """new_xyz as the consumer must use it: the precomputed tensor, or -- when xyz needs a gradient -- the same values
@@ -80,11 +98,11 @@ class SAGeometry(_Ready):
 class FPGeometry(_Ready):
     """One feature-propagation level: three_nn's dist / idx (b, n, 3) (pointnet_util.py:211)."""
 
-    __slots__ = ("dist", "idx")
+    __slots__ = ("dist", "idx", "plan")
 
-    def __init__(self, dist, idx):
-        self.dist, self.idx = dist, idx
-        self._init([dist, idx])
+    def __init__(self, dist, idx, plan=None):
+        self.dist, self.idx, self.plan = dist, idx, plan
+        self._init([dist, idx] + _plan_buffers(plan))
 
 
 class NetworkGeometry:
@@ -104,12 +122,14 @@ class NetworkGeometry:
     def static_copy(self):
         """The same geometry in tensors of its own, without events."""
         sa = [None if g is None else SAGeometry(g.new_xyz.clone(), [i.clone() for i in g.idx] if isinstance(g.idx, (list, tuple))
-                                                else g.idx.clone(), None if g.fps_idx is None else g.fps_idx.clone()) for g in self.sa]
-        fp = [None if g is None else FPGeometry(g.dist.clone(), g.idx.clone()) for g in self.fp]
+                                                else g.idx.clone(), None if g.fps_idx is None else g.fps_idx.clone(), _plan_clone(g.plan))
+              for g in self.sa]
+        fp = [None if g is None else FPGeometry(g.dist.clone(), g.idx.clone(), _plan_clone(g.plan)) for g in self.fp]
         return NetworkGeometry(sa, fp)
 
     def copy_(self, other):
-        """Refill this (static) geometry from another one of the same shapes, on the current stream."""
+        """Refill this (static) geometry from another one of the same shapes, on the current stream (index plans included: a
+        plan holds offsets only, so a copy of its bytes is the plan of the copied idx)."""
         for dst, src in zip(self.tensors(), other.tensors()):
             dst.copy_(src)
         return self
@@ -126,9 +146,13 @@ class GeometryAhead:
 
     high_priority: ask for a high-priority queue for the geometry stream (the chains are short kernels whose latency is the
     point; the layer stacks would otherwise queue in front of them).
+    plans: build every level's index plan too, right behind the launch that wrote its idx (index_plan.py; kernels only, so
+    compute() stays capturable): the training backward of a level that is given such a geometry inverts nothing. sorted as
+    is_deterministic() says when the geometry is computed.
     """
 
-    def __init__(self, sa_modules, fp_pairs=(), device=None, high_priority=True):
+    def __init__(self, sa_modules, fp_pairs=(), device=None, high_priority=True, plans=False):
+        self.plans = bool(plans)
         self.sa_modules = list(sa_modules)
         self.fp_pairs = [tuple(p) for p in fp_pairs]
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -144,7 +168,7 @@ class GeometryAhead:
         with torch.no_grad():
             for mod in self.sa_modules:
                 src = level_xyz[-1]
-                g = None if src is None else mod.geometry(src)
+                g = None if src is None else (mod.geometry(src, plans=True) if self.plans else mod.geometry(src))
                 sa.append(g if g is None or mark is None else g.mark(mark))
                 level_xyz.append(None if g is None else g.new_xyz)
             for i, j in self.fp_pairs:
@@ -152,7 +176,7 @@ class GeometryAhead:
                     fp.append(None)
                     continue
                 dist, idx = three_nn(level_xyz[i], level_xyz[j])
-                g = FPGeometry(dist, idx)
+                g = FPGeometry(dist, idx, index_plan(idx, level_xyz[j].shape[1], "interpolate") if self.plans else None)
                 fp.append(g if mark is None else g.mark(mark))
         return NetworkGeometry(sa, fp)
 

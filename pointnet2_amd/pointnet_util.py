@@ -23,6 +23,7 @@ from ._tensors import use_segmented_grad
 from . import sa_mlp
 from . import train_mlp
 from .geometry import SAGeometry
+from .index_plan import index_plan
 
 
 def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, fused=None):
@@ -171,6 +172,10 @@ class PointnetSAModule(nn.Module):
         # training with an xyz that requires a gradient: take the fused node with its coordinate gradients
         # (train_mlp.sa_mlp_train(..., xyz_grad=True)) instead of the layer-by-layer path. Opt-in.
         self.fused_xyz_grad = False
+        # training without a geometry: build the level's index plan where idx is born (index_plan.py), so that the backward
+        # inverts idx nowhere -- and the two scatters of an xyz_grad backward share one inversion. A geometry's own plans
+        # (GeometryAhead(..., plans=True)) are used whatever this says. Opt-in.
+        self.index_plans = False
         # gradients through a stack whose batch norms are all in eval() (the module in eval(), or in train() with its batch norms
         # frozen): take the fused node with frozen statistics (train_mlp.sa_mlp_train(..., frozen=True)) instead of the
         # layer-by-layer path; last_path "fused_frozen". Opt-in.
@@ -274,9 +279,10 @@ class PointnetSAModule(nn.Module):
             self._packed(device)
         return self
 
-    def geometry(self, xyz):
+    def geometry(self, xyz, plans=False):
         """This level's sampling and grouping alone (:40-46; what forward() launches before its layer stack) -> SAGeometry, or
-        None for a group_all level (no sampling, the group is the cloud). geometry.GeometryAhead calls it on its own stream."""
+        None for a group_all level (no sampling, the group is the cloud). geometry.GeometryAhead calls it on its own stream.
+        plans: with the index plan of idx, built right behind the launch that wrote it."""
         if self.group_all:
             return None
         if self.knn:
@@ -284,7 +290,7 @@ class PointnetSAModule(nn.Module):
             _, idx = knn_point(self.nsample, xyz, new_xyz)
         else:
             fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
-        return SAGeometry(new_xyz, idx, fps_idx)
+        return SAGeometry(new_xyz, idx, fps_idx, index_plan(idx, xyz.shape[1], "group") if plans else None)
 
     def _forward_on(self, xyz, points, g):
         """forward() on a geometry computed ahead (geometry.py): the layer stack only, same paths, same results -- and the same
@@ -294,16 +300,20 @@ class PointnetSAModule(nn.Module):
         mode = self._train_mode(xyz, points)
         if mode is not None:
             self.last_path = mode
+            plan = getattr(g, "plan", None)
+            if plan is None and self.index_plans and torch.is_grad_enabled():
+                plan = index_plan(idx, xyz.shape[1], "group")
             out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling,
-                                            xyz_grad=torch.is_grad_enabled() and xyz.requires_grad, frozen=mode == "fused_frozen")
+                                            xyz_grad=torch.is_grad_enabled() and xyz.requires_grad, frozen=mode == "fused_frozen",
+                                            plan=plan)
             return new_xyz, self._post(out), idx
         if self._fused_ok(xyz, points):
             self.last_path = "fused"
             return new_xyz, self._post(sa_mlp.sa_mlp_pool(xyz, new_xyz, points, idx, self._packed(xyz.device), self.pooling)), idx
         self.last_path = "unfused"
-        grouped_xyz = group_point(xyz, idx) - new_xyz.unsqueeze(2)            # :45-46
+        grouped_xyz = group_point(xyz, idx, plan=getattr(g, "plan", None)) - new_xyz.unsqueeze(2)            # :45-46
         if points is not None:
-            grouped_points = group_point(points, idx)                         # :48
+            grouped_points = group_point(points, idx, plan=getattr(g, "plan", None))            # :48
             new_points = torch.cat([grouped_xyz, grouped_points], dim=-1) if self.use_xyz else grouped_points   # :50
         else:
             new_points = grouped_xyz
@@ -334,8 +344,9 @@ class PointnetSAModule(nn.Module):
                 fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
             if want_xyz:                                              # the centroids' path back to xyz: GatherPoint's gradient (:40)
                 new_xyz = mark_fps_ordered(gather_point(xyz, fps_idx))
+            plan = index_plan(idx, xyz.shape[1], "group") if self.index_plans and torch.is_grad_enabled() else None
             out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling, xyz_grad=want_xyz,
-                                            frozen=frozen)
+                                            frozen=frozen, plan=plan)
             return new_xyz, self._post(out), idx
         if self.group_all and self._fused_ok(xyz, points):
             # sample_and_group_all (:59-84) + the layer stack + reduce_max in ONE kernel: new_xyz = origin, the
@@ -410,6 +421,7 @@ class PointnetSAModuleMSG(nn.Module):
         self.fused_mlp = True          # eval-mode forward may use the fused MFMA kernel (sa_mlp.py)
         self.fused_xyz_grad = False    # see PointnetSAModule: the fused training node for an xyz that requires a gradient (opt-in)
         self.fused_frozen_bn = False   # see PointnetSAModule: the fused node with frozen batch-norm statistics (opt-in)
+        self.index_plans = False       # see PointnetSAModule: one index plan per radius, built where its idx is born (opt-in)
         self.last_path = None
         self._pack_cache = {}
 
@@ -452,10 +464,12 @@ class PointnetSAModuleMSG(nn.Module):
             scales += [(i, g) for i, _, g in rest]
         return (new_xyz, scales, fps_idx) if with_fps else (new_xyz, scales)
 
-    def geometry(self, xyz):
-        """This level's sampling and every radius' grouping alone (:173-180) -> SAGeometry with one idx per radius."""
+    def geometry(self, xyz, plans=False):
+        """This level's sampling and every radius' grouping alone (:173-180) -> SAGeometry with one idx per radius (plans: and
+        one index plan per radius)."""
         new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
-        return SAGeometry(new_xyz, [idx for idx, _ in scales], fps_idx)
+        return SAGeometry(new_xyz, [idx for idx, _ in scales], fps_idx,
+                          [index_plan(idx, xyz.shape[1], "group") for idx, _ in scales] if plans else None)
 
     def _forward_fused(self, xyz, points, g=None):
         """Inference: the grouping launches of _group_scales (or a geometry computed ahead), then one fused MLP + max-pool
@@ -513,8 +527,14 @@ class PointnetSAModuleMSG(nn.Module):
                     new_xyz = mark_fps_ordered(gather_point(xyz, fps_idx))
             else:
                 new_xyz, scales = g.new_xyz_for(xyz), [(idx, None) for idx in g.idx]
-            outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False, xyz_grad=want_xyz, frozen=mode == "fused_frozen")[0]
-                    for mlp, (idx, _) in zip(self.mlps, scales)]
+            plans = getattr(g, "plan", None)
+            if plans is None and self.index_plans and torch.is_grad_enabled():
+                plans = [index_plan(idx, xyz.shape[1], "group") for idx, _ in scales]
+            if plans is None:
+                plans = [None] * len(scales)
+            outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False, xyz_grad=want_xyz, frozen=mode == "fused_frozen",
+                                           plan=plan)[0]
+                    for mlp, (idx, _), plan in zip(self.mlps, scales, plans)]
             return new_xyz, torch.cat(outs, dim=2)
         self.last_path = "unfused"
         fused = g is not None or not (torch.is_grad_enabled() and xyz.requires_grad)
@@ -552,10 +572,17 @@ class PointnetFPModule(nn.Module):
         self.mlp = _SharedMLP(c_in, mlp, bn)
         self.fused_mlp = True          # eval-mode forward may use the fused kernel (csrc/fp_mlp.hip)
         self.fused_frozen_bn = False   # see PointnetSAModule: the fused node with frozen batch-norm statistics (opt-in)
+        self.index_plans = False       # see PointnetSAModule: the index plan of three_nn's idx, built behind three_nn (opt-in)
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
         self._lvl_buffers = None
+
+    def _plan_of(self, idx, m, plan=None):
+        """The level's index plan: the geometry's, or (index_plans) one built here, behind the launch that wrote idx."""
+        if plan is None and self.index_plans and torch.is_grad_enabled():
+            plan = index_plan(idx, m, "interpolate")
+        return plan
 
     def _frozen_ok(self, x1, x2, rows):
         """Autograd through the stack with every batch norm in eval() (fused_frozen_bn): an input (x1 / x2: the tensors the
@@ -604,19 +631,20 @@ class PointnetFPModule(nn.Module):
         if self.fused_mlp and self.training and points2.is_cuda and use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
                 train_mlp.stack_supported(self.mlp.net, xyz1.shape[0] * xyz1.shape[1], 0, False):
             self.last_path = "fused_train"
+            plan = self._plan_of(idx, points2.shape[1], getattr(g, "plan", None))
             if train_mlp.fp_level_preferred(xyz1.shape[0], xyz1.shape[1], points2.shape[1], points2.shape[2]) and \
                     train_mlp.fp_level_supported(self.mlp.net, xyz1.shape[0], xyz1.shape[1], points2.shape[1], points2.shape[2], c1):
-                return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist)     # :212-226 as one node
-            x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
+                return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist, plan=plan)     # :212-226 as one node
+            x, _ = fp_interp_concat(points2, points1, idx, dist, plan=plan)     # :212-219
             return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1)
         if use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
                 self._frozen_ok(points1, points2, xyz1.shape[0] * xyz1.shape[1]):
             self.last_path = "fused_frozen"
-            x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
+            x, _ = fp_interp_concat(points2, points1, idx, dist, plan=self._plan_of(idx, points2.shape[1], getattr(g, "plan", None)))   # :212-219
             return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, frozen=True)
         inv = 1.0 / torch.clamp(dist, min=1e-10)                                # :212
         weight = inv / inv.sum(dim=2, keepdim=True)                             # :213-215
-        return self._after_weights(points1, points2, idx, weight)
+        return self._after_weights(points1, points2, idx, weight, getattr(g, "plan", None))
 
     def forward(self, xyz1, xyz2, points1, points2, geometry=None):
         if geometry is not None:
@@ -638,12 +666,13 @@ class PointnetFPModule(nn.Module):
             # kernels, one split + the segmented scatter of three_interpolate's gradient
             self.last_path = "fused_train"
             dist, idx = three_nn(xyz1, xyz2)                                    # :211
+            plan = self._plan_of(idx, xyz2.shape[1])
             c1 = points1.shape[2] if points1 is not None else 0
             if train_mlp.fp_level_preferred(xyz1.shape[0], xyz1.shape[1], xyz2.shape[1], points2.shape[2]) and \
                     train_mlp.fp_level_supported(self.mlp.net, xyz1.shape[0], xyz1.shape[1], xyz2.shape[1], points2.shape[2], c1):
                 # weights, interpolation, concatenation and the stack as ONE node, layer 1 once per known point (train_mlp_fp.hip)
-                return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist)     # :212-226
-            x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
+                return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist, plan=plan)     # :212-226
+            x, _ = fp_interp_concat(points2, points1, idx, dist, plan=plan)     # :212-219
             return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1)
         if use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
                 self._frozen_ok(points1, points2, xyz1.shape[0] * xyz1.shape[1]):
@@ -651,14 +680,14 @@ class PointnetFPModule(nn.Module):
             self.last_path = "fused_frozen"
             dist, idx = three_nn(xyz1, xyz2)                                    # :211
             c1 = points1.shape[2] if points1 is not None else 0
-            x, _ = fp_interp_concat(points2, points1, idx, dist)                # :212-219
+            x, _ = fp_interp_concat(points2, points1, idx, dist, plan=self._plan_of(idx, xyz2.shape[1]))   # :212-219
             return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, frozen=True)
         idx, weight = three_nn_weights(xyz1, xyz2)                              # :211-215
         return self._after_weights(points1, points2, idx, weight)
 
-    def _after_weights(self, points1, points2, idx, weight):
+    def _after_weights(self, points1, points2, idx, weight, plan=None):
         """:216-226 of the layer-by-layer path."""
-        interpolated = three_interpolate(points2, idx, weight)                  # :216
+        interpolated = three_interpolate(points2, idx, weight, plan=plan)       # :216
         x = torch.cat([interpolated, points1], dim=2) if points1 is not None else interpolated   # :219
         if self.fused_mlp and self.training and x.is_cuda and \
                 train_mlp.stack_supported(self.mlp.net, x.shape[0] * x.shape[1], 0, False):

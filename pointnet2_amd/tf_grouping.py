@@ -429,10 +429,11 @@ def _group_point_launch(points, idx, out=None):
 
 class _GroupPoint(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, points, idx):
+    def forward(ctx, points, idx, plan=None):
         out = _group_point_launch(points, idx)
         ctx.save_for_backward(idx)
         ctx.shape = tuple(points.shape)
+        ctx.plan = plan
         return out
 
     @staticmethod
@@ -444,7 +445,11 @@ class _GroupPoint(torch.autograd.Function):
         dev = grad_out.device
         grad_points = torch.empty((b, n, c), dtype=torch.float32, device=dev)   # zero-filled by the library
         with on_device(dev):
-            if use_segmented_grad(b, n, c):
+            if use_segmented_grad(b, n, c) and ctx.plan is not None:   # idx was inverted where it was born (index_plan.py)
+                _C.check(_C.lib().pn2_group_point_grad_planned(b, n, c, m, ns, ptr(grad_out), ptr(ctx.plan.buffer), ptr(grad_points),
+                                                               1 if is_deterministic() else 0, stream_ptr(dev)),
+                         "group_point_grad")
+            elif use_segmented_grad(b, n, c):
                 ws = seg_workspace(_C.lib(), b, n, m * ns, dev)
                 _C.check(_C.lib().pn2_group_point_grad_seg(b, n, c, m, ns, ptr(grad_out), ptr(idx), ptr(grad_points),
                                                            ptr(ws), 1 if is_deterministic() else 0, stream_ptr(dev)),
@@ -456,26 +461,30 @@ class _GroupPoint(torch.autograd.Function):
             else:
                 _C.check(_C.lib().pn2_group_point_grad(b, n, c, m, ns, ptr(grad_out), ptr(idx), ptr(grad_points),
                                                        stream_ptr(dev)), "group_point_grad")
-        return grad_points, None
+        return grad_points, None, None
 
 
-def group_point(points, idx, out=None):
+def group_point(points, idx, out=None, plan=None):
     """points (b, ndataset, channel) f32, idx (b, npoint, nsample) i32
     -> (b, npoint, nsample, channel) f32.
 
     reference: tf_grouping.py:33-41, op GroupPoint tf_grouping.cpp:143-171.
     out: optional preallocated result (inference: no autograd node is built for it).
+    plan: an IndexPlan of this idx (index_plan(idx, ndataset, "group")): the backward reduces from it and inverts nothing
+    (ignored where the gradient is the atomic scatter: use_segmented_grad).
     """
     points = f32(points, "points")
     idx = i32(idx, "idx")
     require(points.dim() == 3, "GroupPoint expects (batch_size, num_points, channel) points shape")
     require(idx.dim() == 3 and idx.shape[0] == points.shape[0],
             "GroupPoint expects (batch_size, npoints, nsample) idx shape")
-    same_device(points, idx)
+    dev = same_device(points, idx)
+    if plan is not None:
+        plan.check("group", points.shape[0], points.shape[1], idx.shape[1] * idx.shape[2], dev)
     if out is not None:
         require(not (points.requires_grad and torch.is_grad_enabled()), "out= is for inference: points requires grad")
         return _group_point_launch(points, idx, out)
-    return _GroupPoint.apply(points, idx)
+    return _GroupPoint.apply(points, idx, plan)
 
 
 def knn_point(k, xyz1, xyz2):

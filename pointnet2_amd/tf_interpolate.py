@@ -50,10 +50,11 @@ def _three_interpolate_launch(points, idx, weight, out=None):
 
 class _ThreeInterpolate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, points, idx, weight):
+    def forward(ctx, points, idx, weight, plan=None):
         out = _three_interpolate_launch(points, idx, weight)
         ctx.save_for_backward(idx, weight)
         ctx.shape = tuple(points.shape)
+        ctx.plan = plan
         return out
 
     @staticmethod
@@ -65,7 +66,11 @@ class _ThreeInterpolate(torch.autograd.Function):
         dev = grad_out.device
         grad_points = torch.empty((b, m, c), dtype=torch.float32, device=dev)   # zero-filled by the library
         with on_device(dev):
-            if use_segmented_grad(b, m, c):
+            if use_segmented_grad(b, m, c) and ctx.plan is not None:   # idx was inverted where it was born (index_plan.py)
+                _C.check(_C.lib().pn2_three_interpolate_grad_planned(b, n, c, m, ptr(grad_out), ptr(ctx.plan.buffer), ptr(weight),
+                                                                     ptr(grad_points), 1 if is_deterministic() else 0,
+                                                                     stream_ptr(dev)), "three_interpolate_grad")
+            elif use_segmented_grad(b, m, c):
                 ws = seg_workspace(_C.lib(), b, m, 3 * n, dev)
                 _C.check(_C.lib().pn2_three_interpolate_grad_seg(b, n, c, m, ptr(grad_out), ptr(idx), ptr(weight),
                                                                  ptr(grad_points), ptr(ws),
@@ -80,12 +85,14 @@ class _ThreeInterpolate(torch.autograd.Function):
                 _C.check(_C.lib().pn2_three_interpolate_grad(b, n, c, m, ptr(grad_out), ptr(idx), ptr(weight),
                                                              ptr(grad_points), stream_ptr(dev)),
                          "three_interpolate_grad")
-        return grad_points, None, None
+        return grad_points, None, None, None
 
 
-def three_interpolate(points, idx, weight, out=None):
+def three_interpolate(points, idx, weight, out=None, plan=None):
     """points (b, m, c) f32 known features, idx (b, n, 3) i32, weight (b, n, 3) f32
     -> (b, n, c) f32. out: optional preallocated result (inference: no autograd node is built for it).
+    plan: an IndexPlan of this idx (index_plan(idx, m, "interpolate")): the backward reduces from it and inverts nothing
+    (ignored where the gradient is the atomic scatter: use_segmented_grad).
 
     reference: tf_interpolate.py:19-28, op ThreeInterpolate tf_interpolate.cpp:191-222.
     """
@@ -96,18 +103,20 @@ def three_interpolate(points, idx, weight, out=None):
     b = points.shape[0]
     require(idx.dim() == 3 and idx.shape[0] == b and idx.shape[2] == 3, "ThreeInterpolate expects (b,n,3) idx shape")
     require(weight.dim() == 3 and weight.shape == idx.shape, "ThreeInterpolate expects (b,n,3) weight shape")
-    same_device(points, idx, weight)
+    dev = same_device(points, idx, weight)
+    if plan is not None:
+        plan.check("interpolate", b, points.shape[1], 3 * idx.shape[1], dev)
     if out is not None:
         require(not (points.requires_grad and torch.is_grad_enabled()), "out= is for inference: points requires grad")
         return _three_interpolate_launch(points, idx, weight, out)
-    return _ThreeInterpolate.apply(points, idx, weight)
+    return _ThreeInterpolate.apply(points, idx, weight, plan)
 
 
 class _FPInterpConcat(torch.autograd.Function):
     """inputs: points2 (b,m,c2), points1 (b,n,c1) or None, idx (b,n,3) i32, dist (b,n,3) f32 (three_nn's), pitch."""
 
     @staticmethod
-    def forward(ctx, points2, points1, idx, dist, pitch):
+    def forward(ctx, points2, points1, idx, dist, pitch, plan=None):
         b, m, c2 = points2.shape
         n = idx.shape[1]
         c1 = points1.shape[2] if points1 is not None else 0
@@ -119,6 +128,7 @@ class _FPInterpConcat(torch.autograd.Function):
                                                    ptr(out), ptr(weight), stream_ptr(dev)), "fp_interp_concat")
         ctx.save_for_backward(idx, weight)
         ctx.dims = (b, n, m, c2, c1, pitch)
+        ctx.plan = plan
         ctx.mark_non_differentiable(weight)
         return out, weight
 
@@ -132,20 +142,26 @@ class _FPInterpConcat(torch.autograd.Function):
         g2 = torch.empty((b, m, c2), dtype=torch.float32, device=dev)                 # zero-filled by the library
         g1 = torch.empty((b, n, c1), dtype=torch.float32, device=dev) if need1 else None
         scratch = torch.empty((b, n, c2), dtype=torch.float32, device=dev)
-        ws = seg_workspace(_C.lib(), b, m, 3 * n, dev)
         with on_device(dev):
-            _C.check(_C.lib().pn2_fp_interp_concat_grad(b, n, m, c2, c1, pitch, ptr(grad_x), ptr(idx), ptr(weight), ptr(g2), ptr(g1),
-                                                        ptr(scratch), ptr(ws), 1 if is_deterministic() else 0, stream_ptr(dev)),
-                     "fp_interp_concat_grad")
-        return (g2 if need2 else None), g1, None, None, None
+            if ctx.plan is not None:                                    # idx was inverted where it was born (index_plan.py)
+                _C.check(_C.lib().pn2_fp_interp_concat_grad_planned(b, n, m, c2, c1, pitch, ptr(grad_x), ptr(ctx.plan.buffer),
+                                                                    ptr(weight), ptr(g2), ptr(g1), ptr(scratch),
+                                                                    1 if is_deterministic() else 0, stream_ptr(dev)),
+                         "fp_interp_concat_grad")
+            else:
+                ws = seg_workspace(_C.lib(), b, m, 3 * n, dev)
+                _C.check(_C.lib().pn2_fp_interp_concat_grad(b, n, m, c2, c1, pitch, ptr(grad_x), ptr(idx), ptr(weight), ptr(g2), ptr(g1),
+                                                            ptr(scratch), ptr(ws), 1 if is_deterministic() else 0, stream_ptr(dev)),
+                         "fp_interp_concat_grad")
+        return (g2 if need2 else None), g1, None, None, None, None
 
 
-def fp_interp_concat(points2, points1, idx, dist, pad_to=4):
+def fp_interp_concat(points2, points1, idx, dist, pad_to=4, plan=None):
     """The input rows of pointnet_fp_module's layer stack (pointnet_util.py:211-219) in ONE launch: inverse-distance weights
     from three_nn's squared distances, three_interpolate(points2, idx, weight), concat with the skip features points1 (or
     None), zero columns up to a multiple of `pad_to`. -> x (b, n, pitch), weight (b, n, 3). Same formulas as the operators;
     differentiable w.r.t. points2 and points1 (one launch for the split + the segmented scatter of three_interpolate's
-    gradient)."""
+    gradient). plan: an IndexPlan of idx (index_plan(idx, m, "interpolate")): the backward inverts nothing."""
     points2 = f32(points2, "points2")
     idx = i32(idx, "idx")
     dist = f32(dist, "dist")
@@ -162,4 +178,6 @@ def fp_interp_concat(points2, points1, idx, dist, pad_to=4):
     else:
         same_device(points2, idx, dist)
     pitch = (c + pad_to - 1) // pad_to * pad_to
-    return _FPInterpConcat.apply(points2, points1, idx, dist, pitch)
+    if plan is not None:
+        plan.check("interpolate", b, points2.shape[1], 3 * idx.shape[1], points2.device)
+    return _FPInterpConcat.apply(points2, points1, idx, dist, pitch, plan)

@@ -24,7 +24,7 @@ _vp, _i, _ll, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_fl
 
 class GroupSrc(ctypes.Structure):          # pn2_group_src
     _fields_ = [("b", _i), ("n", _i), ("m", _i), ("nsample", _i), ("cfeat", _i), ("xyz_first", _i),
-                ("xyz", _vp), ("new_xyz", _vp), ("points", _vp), ("idx", _vp)]
+                ("xyz", _vp), ("new_xyz", _vp), ("points", _vp), ("idx", _vp), ("idx_plan", _vp)]
 
 
 class BnLayer(ctypes.Structure):           # pn2_bn_layer
@@ -36,7 +36,7 @@ class BnLayer(ctypes.Structure):           # pn2_bn_layer
 
 class FpSrc(ctypes.Structure):             # pn2_fp_src
     _fields_ = [("b", _i), ("n", _i), ("m", _i), ("c2", _i), ("c1", _i), ("points2", _vp), ("points1", _vp), ("idx", _vp),
-                ("dist", _vp)]
+                ("dist", _vp), ("idx_plan", _vp)]
 
 
 class TrainOpts(ctypes.Structure):         # pn2_train_opts: 0 = automatic, 1 = off, 2 = on
@@ -138,7 +138,7 @@ def stack_supported(net, rows, pool_rows=0, grouped=True):
 class _Level:
     """Non-tensor description of one call (what the autograd node needs besides its differentiable inputs)."""
     __slots__ = ("pairs", "rows", "pool_rows", "xyz", "new_xyz", "idx", "b", "n", "m", "nsample", "xyz_first", "grouped", "pooling",
-                 "xyz_grad", "frozen")
+                 "xyz_grad", "frozen", "plan")
 
 
 # pointnet_sa_module's pooling modes (utils/pointnet_util.py:128-142) -> the library's codes (pn2_mlp_train_forward_pool)
@@ -234,6 +234,8 @@ def _group_struct(level, points):
     g.cfeat = points.shape[2] if points is not None else 0
     g.xyz_first = 1 if level.xyz_first else 0
     g.xyz, g.new_xyz, g.points, g.idx = ptr(level.xyz), ptr(level.new_xyz), ptr(points), ptr(level.idx)
+    if level.plan is not None:                 # backward's scatters onto the points reduce from it and invert nothing
+        g.idx_plan = ptr(level.plan.buffer)
     return g
 
 
@@ -533,6 +535,10 @@ class _TrainMLP(torch.autograd.Function):
                 grad_x = torch.empty((b, npts, c), dtype=torch.float32, device=dev)
                 if level.idx is None:                      # group_all: row k of cloud i IS point k
                     grad_x = grad_rows.view(b, npts, c)
+                elif use_segmented_grad(b, npts, c) and level.plan is not None:
+                    _C.check(_C.lib().pn2_group_point_grad_planned(b, npts, c, m, ns, ptr(grad_rows), ptr(level.plan.buffer),
+                                                                   ptr(grad_x), 1 if is_deterministic() else 0, stream_ptr(dev)),
+                             "group_point_grad")
                 elif use_segmented_grad(b, npts, c):
                     sws = seg_workspace(_C.lib(), b, npts, m * ns, dev)
                     _C.check(_C.lib().pn2_group_point_grad_seg(b, npts, c, m, ns, ptr(grad_rows), ptr(level.idx), ptr(grad_x),
@@ -566,7 +572,7 @@ def _params(pairs):
     return out
 
 
-def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", xyz_grad=False, frozen=False):
+def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", xyz_grad=False, frozen=False, plan=None):
     """Training-mode shared MLP + pooling of one SA level / one MSG scale.
     net: nn.Sequential of (Conv2d 1x1, BatchNorm2d, ReLU) triples; xyz (b,n,3); new_xyz (b,m,3) or None and idx
     (b,m,nsample) i32 or None (both None: the group_all level); points (b,n,c) or None.
@@ -579,6 +585,8 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
     frozen: the stack's batch norms are all in eval() and normalise with their RUNNING statistics (pn2_mlp_train_*_frozen,
     frozen_supported): the statistics and num_batches_tracked are not touched, the conv biases take a real gradient, and
     parameters that need no gradient get none (a layer none of whose parameters needs one runs no weight-gradient pass).
+    plan: an IndexPlan of idx (index_plan(idx, n, "group")): the backward's scatters onto the points -- the features' and, with
+    xyz_grad, the coordinates' -- reduce from it, and idx is inverted nowhere in the backward.
     -> (b, m, cout) pooled features (differentiable w.r.t. points and the parameters), argsel (b, m, cout) i32 -- the max's
     selection; None for avg and weighted_avg."""
     require(pooling in POOLING, "unknown pooling %r" % (pooling,))
@@ -602,6 +610,10 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
                 "new_xyz must be (b, m, 3) = %s, got %s" % ((b, idx.shape[1], 3), tuple(new_xyz.shape)))
         same_device(xyz, lv.new_xyz, lv.idx)
         lv.m, lv.nsample = idx.shape[1], idx.shape[2]
+    lv.plan = None
+    if plan is not None:
+        require(idx is not None, "a group_all level has no idx and takes no plan")
+        lv.plan = plan.check("group", b, n, lv.m * lv.nsample, xyz.device)
     lv.b, lv.n = b, n
     lv.rows = b * lv.m * lv.nsample
     lv.pool_rows = lv.nsample
@@ -654,7 +666,7 @@ def fp_mlp_train(net, x, cin=None, frozen=False):
     same_device(x, pairs[0][0].weight)
     lv = _Level()
     lv.pairs, lv.grouped, lv.xyz_first = pairs, False, True
-    lv.xyz = lv.new_xyz = lv.idx = None
+    lv.xyz = lv.new_xyz = lv.idx = lv.plan = None
     lv.b, lv.n, lv.m, lv.nsample = b, n, 0, 0
     lv.rows, lv.pool_rows, lv.pooling = b * n, 0, 0
     lv.frozen = bool(frozen)
@@ -678,7 +690,7 @@ def fp_mlp_train(net, x, cin=None, frozen=False):
 
 # ---- a feature-propagation level as ONE node with the interpolation inside (pn2_mlp_train_*_fp, csrc/train_mlp_fp.hip) ----
 class _FpLevel:
-    __slots__ = ("pairs", "rows", "b", "n", "m", "c2", "c1", "idx", "dist")
+    __slots__ = ("pairs", "rows", "b", "n", "m", "c2", "c1", "idx", "dist", "plan")
 
 
 def fp_level_supported(net, b, n, m, c2, c1):
@@ -709,6 +721,8 @@ def _fp_src(level, points2, points1):
     s = FpSrc()
     s.b, s.n, s.m, s.c2, s.c1 = level.b, level.n, level.m, level.c2, level.c1
     s.points2, s.points1, s.idx, s.dist = ptr(points2), ptr(points1), ptr(level.idx), ptr(level.dist)
+    if level.plan is not None:                 # backward's interpolation gradient reduces from it and inverts nothing
+        s.idx_plan = ptr(level.plan.buffer)
     return s
 
 
@@ -782,13 +796,14 @@ class _TrainFP(torch.autograd.Function):
         return tuple([None, g2, g1] + _batch_stat_results(grads, direct, biases, widths, dev))
 
 
-def fp_level_train(net, points2, points1, idx, dist, return_weight=False):
+def fp_level_train(net, points2, points1, idx, dist, return_weight=False, plan=None):
     """Training-mode feature-propagation level with the interpolation inside ONE autograd node (pointnet_fp_module,
     utils/pointnet_util.py:211-226): inverse-distance weights from three_nn's squared distances `dist` (b,n,3) and `idx`
     (b,n,3) i32, three_interpolate of points2 (b,m,c2), concatenation with the skip features points1 (b,n,c1) or None, and the
     layer stack `net` (Conv 1x1 + BatchNorm + ReLU triples, batch statistics). Layer 1 runs once per KNOWN point
     (z_1 = interp(points2 W1a) + points1 W1b); the (b,n,c2+c1) input never exists. -> (b,n,cout), differentiable w.r.t.
-    points2, points1 and every parameter (and the weights (b,n,3) with return_weight)."""
+    points2, points1 and every parameter (and the weights (b,n,3) with return_weight).
+    plan: an IndexPlan of idx (index_plan(idx, m, "interpolate")): the backward inverts nothing."""
     pairs = conv_bn_pairs(net)
     require(pairs is not None, "fp_level_train expects Conv 1x1 + BatchNorm + ReLU triples")
     points2, idx, dist = f32(points2, "points2"), i32(idx, "idx"), f32(dist, "dist")
@@ -810,6 +825,7 @@ def fp_level_train(net, points2, points1, idx, dist, return_weight=False):
     require(fp_level_supported(net, b, n, m, c2, c1), "unsupported level for the FP training node")
     lv = _FpLevel()
     lv.pairs, lv.rows, lv.b, lv.n, lv.m, lv.c2, lv.c1, lv.idx, lv.dist = pairs, b * n, b, n, m, c2, c1, idx, dist
+    lv.plan = None if plan is None else plan.check("interpolate", b, m, 3 * n, points2.device)
     out, weight = _TrainFP.apply(lv, points2, points1, *_params(pairs))
     out = out.view(b, n, -1)
     return (out, weight) if return_weight else out

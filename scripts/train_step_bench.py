@@ -166,6 +166,9 @@ def main():
                          "(pointnet2_amd.geometry.GeometryAhead). Measured: no gain at best (2.80 against 2.78 ms on cls_ssg) and 2-3x "
                          "SLOWER whenever the runtime puts the two streams into one hardware queue (7.0 / 11.2 ms on cls_ssg / sem_seg in "
                          "some process layouts) -- profiles/r05/geometry_ahead.txt; the captured form (--graph) does not have that problem")
+    ap.add_argument("--index-plans", action="store_true",
+                    help="additionally run fused_direct with index_plans = True on every module (pointnet2_amd/index_plan.py: every "
+                         "level's idx is inverted once, in the forward, and no backward inverts anything)")
     args = ap.parse_args()
     distributed = "RANK" in os.environ
     rank, world = 0, 1
@@ -192,12 +195,18 @@ def main():
         variants = [("layer_by_layer", False, False), ("fused", True, False), ("fused_direct", True, True)]
         if args.ahead:
             variants.append(("fused_direct_ahead", True, True))
+        if args.index_plans:
+            variants.append(("fused_direct_plans", True, True))
         for key, fused, direct in (variants[1:] if args.fused_only else variants):
             train_mlp.set_accumulate_into_grad(direct)
             model = ctor().to(dev)
             model.load_state_dict(state)
             model.train()
             set_fused(model, fused)
+            if key.endswith("_plans"):
+                for mod in model.modules():
+                    if hasattr(mod, "index_plans"):
+                        mod.index_plans = True
             bucket = sharding.GradBucket(model.parameters())
             opt = torch.optim.SGD(model.parameters(), lr=1e-3, momentum=0.9)
             # one step for the gradient comparison (same weights, same batch)
@@ -221,6 +230,12 @@ def main():
                     except Exception as e:                       # noqa: BLE001 -- a capture torch refuses is a result, not a crash
                         row[gkey] = {"error": repr(e)[:300]}
                         torch.cuda.synchronize()
+            if key == "fused_direct_plans" and args.graph and not distributed:
+                try:
+                    row[key + "_graph"] = graph_step(model, opt, bucket, x, labels, args.steps)
+                except Exception as e:                           # noqa: BLE001
+                    row[key + "_graph"] = {"error": repr(e)[:300]}
+                    torch.cuda.synchronize()
             del model, opt, bucket
             torch.cuda.empty_cache()
         train_mlp.set_accumulate_into_grad(False)
@@ -232,6 +247,8 @@ def main():
             row["speedup_direct"] = round(row["layer_by_layer"]["step_ms"] / row["fused_direct"]["step_ms"], 2)
             if "fused_direct_ahead" in row:
                 row["speedup_direct_ahead"] = round(row["layer_by_layer"]["step_ms"] / row["fused_direct_ahead"]["step_ms"], 2)
+        if "fused_direct_plans" in grads and "fused_direct" in grads:
+            row["plans_grad_rel_diff"] = float((grads["fused_direct_plans"][1] - grads["fused_direct"][1]).norm() / grads["fused_direct"][1].norm())
         if "fused" in grads and "fused_direct" in grads:
             row["direct_grad_rel_diff"] = float((grads["fused_direct"][1] - grads["fused"][1]).norm() / grads["fused"][1].norm())
         if rank == 0:

@@ -5,6 +5,9 @@ of one forward + backward (torch.cuda.max_memory_allocated):
                         fused_xyz_grad off runs for such an xyz)
     (b) node_xyz        train_mlp.sa_mlp_train(..., xyz_grad=True): the fused node with grad_xyz and grad_new_xyz
     (c) node            the fused node, coordinates constant (no gradient to them)
+    (d) node_xyz_plan   (b) with the level's index plan built in the forward (a module with index_plans = True): the two scatters
+                        of the backward -- coordinates and features -- reduce from one inversion instead of inverting idx twice
+    (e) node_xyz_given  (b) with a plan built beforehand (a geometry computed ahead with plans=True): no inversion in the iteration
 (b) - (c) is the cost of the feature; (a) / (b) its gain. new_xyz is a leaf here: gather_point's own backward is the same launch
 on every path. Writes JSON lines.
     python scripts/train_xyz_bench.py [--iters 20] [--warmup 5] [--levels metric,SA2] [--only b]   (--only: one path, for a profiler)"""
@@ -18,7 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pointnet2_amd.pointnet_util as U  # noqa: E402
-from pointnet2_amd import train_mlp  # noqa: E402
+from pointnet2_amd import index_plan, train_mlp  # noqa: E402
 from pointnet2_amd.tf_grouping import group_point  # noqa: E402
 
 # name, b, n, m, ns, cfeat, widths, xyz_first
@@ -78,6 +81,17 @@ def main():
             out, _ = train_mlp.sa_mlp_train(net.net, xyz, new_xyz, feats, idx, xyz_first, xyz_grad=True)
             torch.autograd.grad(out, params + coords, gw)
 
+        given = None if group_all else index_plan(idx, n, "group")
+
+        def node_xyz_plan():
+            out, _ = train_mlp.sa_mlp_train(net.net, xyz, new_xyz, feats, idx, xyz_first, xyz_grad=True,
+                                            plan=None if group_all else index_plan(idx, n, "group"))
+            torch.autograd.grad(out, params + coords, gw)
+
+        def node_xyz_given():
+            out, _ = train_mlp.sa_mlp_train(net.net, xyz, new_xyz, feats, idx, xyz_first, xyz_grad=True, plan=given)
+            torch.autograd.grad(out, params + coords, gw)
+
         def node():
             out, _ = train_mlp.sa_mlp_train(net.net, xyz, new_xyz, feats, idx, xyz_first)
             torch.autograd.grad(out, params, gw)
@@ -96,7 +110,8 @@ def main():
         gdims = (b, n, m, ns, cfeat, 0 if group_all else 1)
         row = {"level": name, "rows": rows, "iters": a.iters,
                "supported": train_mlp.xyz_grad_supported(net.net, rows, ns, "max", b, n, m, cfeat, not group_all), "group_dims": gdims}
-        for tag, key, fn in (("a", "layer_by_layer", layer_by_layer), ("b", "node_xyz", node_xyz), ("c", "node", node)):
+        for tag, key, fn in (("a", "layer_by_layer", layer_by_layer), ("b", "node_xyz", node_xyz), ("c", "node", node),
+                             ("d", "node_xyz_plan", node_xyz_plan), ("e", "node_xyz_given", node_xyz_given)):
             if tag not in a.only:
                 continue
             torch.cuda.synchronize()
