@@ -321,6 +321,35 @@ int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *
  * once per workgroup, 3 x 3 x 3 cells visited per unknown point, an exactness test on the third-best distance and a sweep for
  * the points that fail it; PN2_E_ARG below 64 or above 8192 known points). */
 int pn2_three_nn_ex(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx, int variant, void *stream);
+/* ---- ragged batches: per-cloud point counts (DESIGN.md "Ragged batches") ----------------------------------------------------
+ * Layout: a padded tensor (b, n, 3) plus `lengths` (b) int32 in DEVICE memory, 1 <= lengths[c] <= n; cloud c is rows
+ * 0 .. lengths[c]-1 of its slab. THE SLICE RULE: for every entry below the result for cloud c is bit- and index-identical to
+ * the dense entry applied to that slice alone (b = 1, n = lengths[c]), FPS tie rule included (rank (k mod 512) Q_c + k / 512,
+ * Q_c = ceil(lengths[c] / 512)). Rows at or beyond lengths[c] are never read: they may hold NaN, Inf or anything else.
+ * The host never reads `lengths` (no synchronisation; stream-ordered and capturable like the dense twins); the kernels clamp
+ * a length into 1..n for memory safety only -- validating is the caller's business (Python: pointnet2_amd.check_lengths).
+ * A NULL lengths is PN2_E_NULL; the other argument checks and codes are the dense entries'.
+ *
+ * pn2_farthest_point_sample_ragged: the register tier only (every point updated every round, csrc/fps_body.h), one workgroup
+ *   per cloud, geometry chosen from the padded n; PN2_E_TOO_LARGE for n > 16384. out_xyz (b,m,3) may be NULL.
+ *   m > lengths[c] behaves as the dense operator with npoint > n.
+ * pn2_query_ball_group_xyz_ragged: xyz1 ragged (lengths1), the queries xyz2 (b,m,3) dense; kernel / cells_qpb as
+ *   pn2_query_ball_group_xyz_ex (a cloud below 64 points takes the sweep inside the cell-list kernel); grouped_xyz NULL =
+ *   plain query_ball_point.
+ * pn2_knn_point_ragged: the envelope of pn2_knn_point (n <= 14336, k <= n); where k > lengths1[c] the entries from
+ *   lengths1[c] on repeat entry 0 of their row (val and idx), so every row is fully written.
+ * pn2_three_nn_ragged: the UNKNOWN side xyz1 is ragged, the known side xyz2 (b,m,3) dense; variant as pn2_three_nn_ex.
+ *   Rows at or beyond lengths1[c] are written as idx (0,0,0), dist (0,0,0). */
+int pn2_farthest_point_sample_ragged(int b, int n, int m, const float *inp, const int *lengths, int *out, float *out_xyz,
+                                     void *stream);
+int pn2_query_ball_group_xyz_ragged(int b, int n, int m, float radius, int nsample, const float *xyz1, const int *lengths1,
+                                    const float *xyz2, int subtract_centroid, int *idx, int *pts_cnt, float *grouped_xyz,
+                                    int kernel, int cells_qpb, void *stream);
+int pn2_knn_point_ragged(int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2, float *val, int *idx,
+                         void *stream);
+int pn2_three_nn_ragged(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2, float *dist, int *idx,
+                        int variant, void *stream);
+
 /* pn2_group_point / pn2_three_interpolate with the kernel choice per call (parity tests force every kernel,
  * scripts/bw_probe.py times them). group: 0 automatic, 1 flat first-generation kernels, 2 row kernels,
  * 3 row kernels with non-temporal stores; three_interpolate: 0 automatic, 1 flat, 2 row kernel, 3 row kernel with

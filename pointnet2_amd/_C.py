@@ -120,6 +120,10 @@ _SIGNATURES = {
     "pn2_mlp_train_ws_bytes_fp": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "pn2_mlp_train_forward_fp": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_mlp_train_backward_fp": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "pn2_farthest_point_sample_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pn2_query_ball_group_xyz_ragged": [_i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "pn2_knn_point_ragged": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_three_nn_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
 }
 _RESTYPES = {
     "pn2_fps_temp_floats": ctypes.c_longlong,

@@ -54,6 +54,53 @@ def ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _lengths_tensor(lengths, name):
+    """An int32 / int64 tensor, or a sequence of ints -> an integer tensor (wherever it lives); anything else: ValueError."""
+    if not isinstance(lengths, torch.Tensor):
+        try:
+            lengths = torch.as_tensor(lengths)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("%s must be an int32 / int64 tensor or a sequence of ints" % name)
+    require(lengths.dtype in (torch.int32, torch.int64), "%s must be int32 or int64, got %s" % (name, lengths.dtype))
+    return lengths
+
+
+def lengths_for(lengths, ref, name="lengths"):
+    """The shape check of ragged_lengths against the batch size of `ref` (the operator's first tensor argument), made before
+    anything else is looked at: a wrong lengths shape is reported as such whatever else is wrong with the call."""
+    t = _lengths_tensor(lengths, name)
+    b = ref.shape[0] if isinstance(ref, torch.Tensor) and ref.dim() >= 1 else None
+    require(t.dim() == 1 and (b is None or t.shape[0] == b),
+            "%s must have shape (batch_size,)%s, got %s" % (name, "" if b is None else " = (%d,)" % b, tuple(t.shape)))
+    return t
+
+
+def ragged_lengths(lengths, b, dev, name="lengths"):
+    """The per-cloud point counts of a ragged batch as the kernels take them: a contiguous int32 tensor (b,) on `dev`.
+    Accepts an int32 / int64 tensor or a sequence; a tensor already on the device is converted there (no host
+    synchronisation; the VALUES are not looked at -- that is check_lengths, where the batch is built)."""
+    t = _lengths_tensor(lengths, name)
+    require(t.dim() == 1 and t.shape[0] == b, "%s must have shape (batch_size,) = (%d,), got %s" % (name, b, tuple(t.shape)))
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def check_lengths(lengths, n, b=None):
+    """Validate the per-cloud point counts of a ragged batch padded to n points: an int32 / int64 tensor (or a sequence) of
+    shape (b,) with 1 <= lengths[i] <= n. Raises ValueError. This is the ONE place that looks at the values, and it
+    synchronises: call it once where the batch is built -- the operators never do (their kernels clamp a bad length into
+    1..n for memory safety and compute on that). b: the batch size, when the caller wants the shape checked against it.
+    -> lengths as an int32 tensor (on the device it came from)."""
+    t = _lengths_tensor(lengths, "lengths")
+    require(t.dim() == 1, "lengths must have shape (batch_size,), got %s" % (tuple(t.shape),))
+    require(b is None or t.shape[0] == int(b), "lengths must have shape (%s,), got %s" % (b, tuple(t.shape)))
+    require(int(n) >= 1, "n must be positive")
+    if t.numel():
+        lo, hi = int(t.min()), int(t.max())
+        require(lo >= 1, "lengths must be at least 1 (found %d)" % lo)
+        require(hi <= int(n), "lengths must not exceed the padded size n = %d (found %d)" % (int(n), hi))
+    return t.to(torch.int32)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 

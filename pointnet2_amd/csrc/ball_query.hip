@@ -51,8 +51,35 @@ __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(int n, int m, in
                                           nullptr, idx, pts_cnt, grouped, subtract, smem);
 }
 
+// Ragged batch (pn2_query_ball_group_xyz_ragged): cloud c holds lengths1[c] <= n points in its padded (n, 3) slab. The
+// workgroup hands the body its own slabs as cloud 0 with n = n_c: staging, the +inf pad and the sweep bounds are those of the
+// dense kernel on the slice, rows at or beyond n_c are never addressed. The LDS is sized on the host for the padded n (both
+// layouts grow with n). The length is clamped into 1..n for memory safety only.
+__device__ __forceinline__ int bq_ragged_length(const int *__restrict__ lengths, int cloud, int n)
+{
+    return min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
+}
+
 template <bool LDS_CLOUD, bool FUSE>
-static int launch_bq(int b, int n, int m, float thr, int nsample, const float *xyz1, const float *xyz2, int *idx,
+__global__ __launch_bounds__(kBqThreads) void ball_query_ragged_kernel(int n, int m, int nsample, float thr, int qpb,
+                                                                       const float *__restrict__ xyz1,
+                                                                       const int *__restrict__ lengths,
+                                                                       const float *__restrict__ xyz2, int *__restrict__ idx,
+                                                                       int *__restrict__ pts_cnt,
+                                                                       float *__restrict__ grouped, int subtract)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c = blockIdx.y;
+    const int nc = bq_ragged_length(lengths, c, n);
+    const int q0 = blockIdx.x * qpb;
+    const size_t rows = (size_t)c * m;
+    bq_block_body<LDS_CLOUD, FUSE, false>(nc, m, nsample, thr, 0, q0, min(q0 + qpb, m), xyz1 + (size_t)c * n * 3, xyz2 + rows * 3,
+                                          nullptr, nullptr, idx ? idx + rows * nsample : nullptr, pts_cnt ? pts_cnt + rows : nullptr,
+                                          grouped ? grouped + rows * nsample * 3 : nullptr, subtract, smem);
+}
+
+template <bool LDS_CLOUD, bool FUSE>
+static int launch_bq(int b, int n, int m, float thr, int nsample, const float *xyz1, const int *lengths, const float *xyz2, int *idx,
                      int *pts_cnt, float *grouped, int subtract, hipStream_t st)
 {
     // aim at ~2 workgroups per CU over the whole launch; each stages the cloud once
@@ -65,6 +92,12 @@ static int launch_bq(int b, int n, int m, float thr, int nsample, const float *x
     const int gx = (m + qpb - 1) / qpb;
     const size_t lds = (LDS_CLOUD ? sizeof(float4) * (size_t)((n + 127) & ~127) : 0) + sizeof(int) * (size_t)nsample * kGran;
     if (lds > 160 * 1024) return PN2_E_TOO_LARGE;
+    if (lengths) {
+        auto kern = ball_query_ragged_kernel<LDS_CLOUD, FUSE>;
+        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+        return launch(kern, dim3(gx, b), dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, lengths, xyz2, idx, pts_cnt, grouped,
+                      subtract);
+    }
     auto kern = ball_query_kernel<LDS_CLOUD, FUSE>;
     if (int rc = allow_dynamic_lds(kern, lds)) return rc;
     if (int rc = launch(kern, dim3(gx, b), dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, xyz2, idx,
@@ -89,6 +122,37 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_kernel(int b, i
     const int q0 = part * qpb;
     bq_cells_block_body<NT, LPQ, FUSE, false, true>(n, m, nsample, thr, radius, cloud, q0, min(q0 + qpb, m), xyz1, xyz2,   // BLK: crowded balls walk the first half of the indices first (ball_query_body.h)
                                      nullptr, nullptr, idx, pts_cnt, grouped, subtract, smem);
+}
+
+// The cell-list kernel on a ragged batch. A cloud below 64 points takes the sweep body at once (block-uniform; the host keeps
+// such clouds off the cell list in the dense dispatch too, bq_use_cells); larger ones bin their own n_c points, and the
+// body's own fallback (coarse grid, crowded cells) uses the sweep layout inside the same LDS, sized for the padded n.
+template <int NT, int LPQ, bool FUSE>
+__global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_ragged_kernel(int b, int n, int m, int nsample, float thr,
+                                                                             float radius, int qpb, int parts,
+                                                                             const float *__restrict__ xyz1,
+                                                                             const int *__restrict__ lengths,
+                                                                             const float *__restrict__ xyz2,
+                                                                             int *__restrict__ idx,
+                                                                             int *__restrict__ pts_cnt,
+                                                                             float *__restrict__ grouped, int subtract)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int cloud, part;
+    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
+    const int nc = bq_ragged_length(lengths, cloud, n);
+    const int q0 = part * qpb, q1 = min(q0 + qpb, m);
+    const size_t rows = (size_t)cloud * m;
+    const float *__restrict__ x1 = xyz1 + (size_t)cloud * n * 3;
+    const float *__restrict__ x2 = xyz2 + rows * 3;
+    int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
+    int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
+    float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
+    if (nc < 64)
+        bq_block_body<true, FUSE, false, NT>(nc, m, nsample, thr, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og, subtract, smem);
+    else
+        bq_cells_block_body<NT, LPQ, FUSE, false, true>(nc, m, nsample, thr, radius, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og,
+                                                        subtract, smem);
 }
 
 static size_t bq_sweep_lds_bytes(int n, int nsample, int nthreads = kBqThreads)
@@ -129,7 +193,7 @@ static bool bq_use_cells(int b, int n, int m, int kernel)
 }
 
 template <int NT, int LPQ, bool FUSE>
-static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsample, const float *xyz1,
+static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsample, const float *xyz1, const int *lengths,
                            const float *xyz2, int *idx, int *pts_cnt, float *grouped, int subtract, int opt_qpb,
                            hipStream_t st)
 {
@@ -142,6 +206,12 @@ static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsa
     const int gx = (m + qpb - 1) / qpb;
     const size_t a = bq_cells_lds_bytes(n, nsample, LPQ, NT), s = bq_sweep_lds_bytes(n, nsample, NT);
     const size_t lds = a > s ? a : s;                       // the fallback inside the kernel uses the sweep layout
+    if (lengths) {
+        auto kern = ball_query_cells_ragged_kernel<NT, LPQ, FUSE>;
+        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+        return launch(kern, dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx, xyz1, lengths, xyz2, idx,
+                      pts_cnt, grouped, subtract);
+    }
     auto kern = ball_query_cells_kernel<NT, LPQ, FUSE>;
     if (int rc = allow_dynamic_lds(kern, lds)) return rc;
     if (int rc = launch(kern, dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx,
@@ -151,12 +221,12 @@ static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsa
 
 template <bool FUSE>
 static int dispatch_bq_cells(BqCellsGeom g, int b, int n, int m, float thr, float radius, int nsample,
-                             const float *xyz1, const float *xyz2, int *idx, int *pts_cnt, float *grouped,
+                             const float *xyz1, const int *lengths, const float *xyz2, int *idx, int *pts_cnt, float *grouped,
                              int subtract, int qpb, hipStream_t st)
 {
 #define PN2_BQ_CASE(NT, LPQ) \
     if (g.nthreads == NT && g.lpq == LPQ) \
-        return launch_bq_cells<NT, LPQ, FUSE>(b, n, m, thr, radius, nsample, xyz1, xyz2, idx, pts_cnt, grouped, subtract, qpb, st)
+        return launch_bq_cells<NT, LPQ, FUSE>(b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, qpb, st)
     PN2_BQ_CASE(1024, 8);
     PN2_BQ_CASE(1024, 16);
     PN2_BQ_CASE(512, 8);
@@ -166,8 +236,10 @@ static int dispatch_bq_cells(BqCellsGeom g, int b, int n, int m, float thr, floa
     return PN2_E_TOO_LARGE;
 }
 
+// lengths: NULL = every cloud holds n points (the dense kernels); else the ragged kernels
 static int ball_query_common(int b, int n, int m, float radius, int nsample, const float *xyz1, const float *xyz2,
-                             int subtract, int *idx, int *pts_cnt, float *grouped, bool fuse, BqOpts opt, void *stream)
+                             int subtract, int *idx, int *pts_cnt, float *grouped, bool fuse, BqOpts opt, void *stream,
+                             const int *lengths = nullptr)
 {
     if (opt.kernel < 0 || opt.kernel > 3 || opt.qpb < 0) return PN2_E_ARG;
     if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;   // tf_grouping.cpp:71,74
@@ -183,13 +255,13 @@ static int ball_query_common(int b, int n, int m, float radius, int nsample, con
                      sizeof(float4) * (size_t)((n + 127) & ~127) + sizeof(int) * (size_t)nsample * kBqWaves * kBqQpw <= 160 * 1024;
     BqCellsGeom geom;
     if (bq_use_cells(b, n, m, opt.kernel) && bq_cells_pick(n, nsample, opt.kernel, geom))
-        return fuse ? dispatch_bq_cells<true>(geom, b, n, m, thr, radius, nsample, xyz1, xyz2, idx, pts_cnt, grouped, subtract, opt.qpb, st)
-                    : dispatch_bq_cells<false>(geom, b, n, m, thr, radius, nsample, xyz1, xyz2, idx, pts_cnt, nullptr, 0, opt.qpb, st);
+        return fuse ? dispatch_bq_cells<true>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, opt.qpb, st)
+                    : dispatch_bq_cells<false>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, opt.qpb, st);
     if (fuse)
-        return lds ? launch_bq<true, true>(b, n, m, thr, nsample, xyz1, xyz2, idx, pts_cnt, grouped, subtract, st)
-                   : launch_bq<false, true>(b, n, m, thr, nsample, xyz1, xyz2, idx, pts_cnt, grouped, subtract, st);
-    return lds ? launch_bq<true, false>(b, n, m, thr, nsample, xyz1, xyz2, idx, pts_cnt, nullptr, 0, st)
-               : launch_bq<false, false>(b, n, m, thr, nsample, xyz1, xyz2, idx, pts_cnt, nullptr, 0, st);
+        return lds ? launch_bq<true, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st)
+                   : launch_bq<false, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st);
+    return lds ? launch_bq<true, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st)
+               : launch_bq<false, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st);
 }
 
 }  // namespace pn2
@@ -239,4 +311,20 @@ extern "C" int pn2_query_ball_group_xyz_ex(int b, int n, int m, float radius, in
 {
     return pn2::ball_query_common(b, n, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt,
                                   grouped_xyz, grouped_xyz != nullptr, {kernel, cells_qpb}, stream);
+}
+
+// Ragged batch: cloud c of xyz1 is xyz1[c, :lengths1[c]] of a padded (b, n, 3) tensor, lengths1 (b) int32 on the device, never
+// read by the host; the queries xyz2 (b, m, 3) are dense. Result per cloud = pn2_query_ball_group_xyz_ex on the slice, for
+// every `kernel`. grouped_xyz == NULL: plain query_ball_point.
+extern "C" int pn2_query_ball_group_xyz_ragged(int b, int n, int m, float radius, int nsample, const float *xyz1, const int *lengths1,
+                                               const float *xyz2, int subtract_centroid, int *idx, int *pts_cnt, float *grouped_xyz,
+                                               int kernel, int cells_qpb, void *stream)
+{
+    if (kernel < 0 || kernel > 3 || cells_qpb < 0) return PN2_E_ARG;
+    if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;
+    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (!lengths1) return PN2_E_NULL;
+    return pn2::ball_query_common(b, n, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt,
+                                  grouped_xyz, grouped_xyz != nullptr, {kernel, cells_qpb}, stream, lengths1);
 }

@@ -51,6 +51,23 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(int n, int m, int Q, const f
     fps_reg_body<T, P, LDSXYZ, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
 }
 
+// Ragged batch (pn2_farthest_point_sample_ragged): cloud c holds lengths[c] <= n points in its padded (n, 3) slab. The
+// workgroup hands the body its own slab as cloud 0 with n = n_c and Q = ceil(n_c / 512): the tie ranks, the dealing and the
+// padding slots are then exactly those of the dense kernel on the slice, and rows at or beyond n_c are never addressed
+// (fps_body.h: valid = ... && k < n). T, P and the LDS size come from the padded n: T P >= 512 ceil(n / 512) >= 512 Q_c.
+// The length is clamped into 1..n for memory safety only (check_lengths is the validation).
+template <int T, int P, bool LDSXYZ>
+__global__ __launch_bounds__(T) void fps_reg_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
+                                                           int *__restrict__ out, float *__restrict__ out_xyz)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c = blockIdx.x;
+    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[c]), 1), n);
+    const int Qc = (nc + kRefThreads - 1) / kRefThreads;
+    fps_reg_body<T, P, LDSXYZ, false>(nc, m, Qc, 0, xyz + (size_t)c * n * 3, out + (size_t)c * m,
+                                      out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr, nullptr, smem);
+}
+
 // Pruned tier (fps_pruned_body.h): kd-grouped slots, per-round box tests, only the groups the new sample can reach are
 // updated. 2049..8192 rank slots, chains long enough to pay for the kd build.
 template <int P, int GS>
@@ -308,6 +325,15 @@ static int launch_reg(int b, int n, int m, int Q, const float *inp, int *out, fl
     return PN2_OK;
 }
 
+template <int T, int P, bool LDSXYZ>
+static int launch_reg_ragged(int b, int n, int m, const float *inp, const int *lengths, int *out, float *oxyz, hipStream_t st)
+{
+    const size_t lds = 256 + (LDSXYZ ? sizeof(float4) : sizeof(int)) * (size_t)T * P;
+    auto kern = fps_reg_ragged_kernel<T, P, LDSXYZ>;
+    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+    return launch(kern, dim3(b), dim3(T), lds, st, n, m, inp, lengths, out, oxyz);
+}
+
 template <int P, int GS>
 static int launch_pruned(int b, int n, int m, int Q, const float *inp, int *out, float *oxyz, hipStream_t st)
 {
@@ -454,6 +480,34 @@ extern "C" int pn2_farthest_point_sample_variant(int variant, int b, int n, int 
 {
     if (variant < PN2_FPS_AUTO || variant > PN2_FPS_BATCH) return PN2_E_ARG;
     return fps_entry(b, n, m, inp, temp, out, out_xyz, stream, variant);
+}
+
+// Ragged batch: cloud c is inp[c, :lengths[c]] of a padded (b, n, 3) tensor, lengths (b) int32 on the device, never read by
+// the host. Result per cloud = pn2_farthest_point_sample_gather on the slice, tie rule included. Register tier only (the
+// geometry fps_entry picks for PN2_FPS_FULL at the padded n); PN2_E_TOO_LARGE beyond 16384 points. out_xyz may be NULL.
+extern "C" int pn2_farthest_point_sample_ragged(int b, int n, int m, const float *inp, const int *lengths, int *out, float *out_xyz,
+                                                void *stream)
+{
+    using namespace pn2;
+    if (m <= 0 || b == 0) return PN2_OK;
+    if (b < 0 || n <= 0) return PN2_E_SHAPE;
+    if (!inp || !out || !lengths) return PN2_E_NULL;
+    if (n > kMaxRegPoints) return PN2_E_TOO_LARGE;
+    if ((long long)b * n * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
+    hipStream_t st = as_stream(stream);
+    const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
+    const int T = ranks <= 2048 ? 256 : 512;
+    const int P = next_pow2((ranks + T - 1) / T);
+#define PN2_FPS_RAGGED(TT, PP) \
+    if (T == TT && P == PP) return launch_reg_ragged<TT, PP, ((long long)TT * PP <= kMaxLdsSlots)>(b, n, m, inp, lengths, out, out_xyz, st)
+    PN2_FPS_RAGGED(256, 2);
+    PN2_FPS_RAGGED(256, 4);
+    PN2_FPS_RAGGED(256, 8);
+    PN2_FPS_RAGGED(512, 8);
+    PN2_FPS_RAGGED(512, 16);
+    PN2_FPS_RAGGED(512, 32);
+#undef PN2_FPS_RAGGED
+    return PN2_E_ARG;
 }
 
 // farthest_point_sample for input the caller BELIEVES to be in farthest-point order already (the previous level's samples:

@@ -67,15 +67,28 @@ __device__ __forceinline__ void nn_merge(double &b1, double &b2, double &b3)
     nn_insert(o3, b1, b2, b3);
 }
 
-__global__ __launch_bounds__(kNnThreads) void three_nn_kernel(int n, int m, const float *__restrict__ xyz1,
-                                                              const float *__restrict__ xyz2,
-                                                              float *__restrict__ dist, int *__restrict__ idx)
+// Rows at or beyond a ragged cloud's length: idx (0,0,0), dist (0,0,0) -- never read from xyz1, and torch.empty outputs are
+// fully defined (finite weights downstream, three_interpolate in range).
+__device__ __forceinline__ void nn_zero_row(float *__restrict__ od, int *__restrict__ oi)
 {
-    __shared__ float4 tile[kNnTile];
-    const int bi = blockIdx.y;
+    od[0] = 0.0f; od[1] = 0.0f; od[2] = 0.0f;
+    oi[0] = 0; oi[1] = 0; oi[2] = 0;
+}
+
+// Workgroup body of the sweep. nv = valid unknown points of cloud bi: n in the dense kernel; in the ragged one the cloud's own
+// length -- rows nv .. n-1 are then zero-filled and never read (RAGGED; the dense instantiation has none of it).
+template <bool RAGGED>
+__device__ __forceinline__ void three_nn_sweep_body(int n, int nv, int m, int bi, const float *__restrict__ xyz1,
+                                                    const float *__restrict__ xyz2, float *__restrict__ dist,
+                                                    int *__restrict__ idx, float4 *tile)
+{
     const int sub = threadIdx.x & 3;                       // lane of the quad
     const int j = blockIdx.x * kNnPoints + (threadIdx.x >> 2);
-    const bool live = j < n;
+    const bool live = j < nv;
+    if (RAGGED && (int)blockIdx.x * kNnPoints >= nv) {     // block-uniform: nothing but padding rows here
+        if (j < n && sub == 0) nn_zero_row(dist + ((size_t)bi * n + j) * 3, idx + ((size_t)bi * n + j) * 3);
+        return;
+    }
     const float *u = xyz1 + ((size_t)bi * n + (live ? j : 0)) * 3;
     const float ux = u[0], uy = u[1], uz = u[2];
     const float *__restrict__ known = xyz2 + (size_t)bi * m * 3;
@@ -121,6 +134,27 @@ __global__ __launch_bounds__(kNnThreads) void three_nn_kernel(int n, int m, cons
         od[2] = __int_as_float(__double2hiint(b3));
         oi[0] = __double2loint(b1); oi[1] = __double2loint(b2); oi[2] = __double2loint(b3);
     }
+    if (RAGGED && !live && j < n && sub == 0) nn_zero_row(dist + ((size_t)bi * n + j) * 3, idx + ((size_t)bi * n + j) * 3);
+}
+
+__global__ __launch_bounds__(kNnThreads) void three_nn_kernel(int n, int m, const float *__restrict__ xyz1,
+                                                              const float *__restrict__ xyz2,
+                                                              float *__restrict__ dist, int *__restrict__ idx)
+{
+    __shared__ float4 tile[kNnTile];
+    three_nn_sweep_body<false>(n, n, m, blockIdx.y, xyz1, xyz2, dist, idx, tile);
+}
+
+// Ragged unknown side (pn2_three_nn_ragged): cloud c has lengths[c] <= n unknown points; the known side is dense. The length
+// is clamped into 1..n for memory safety only.
+__global__ __launch_bounds__(kNnThreads) void three_nn_ragged_kernel(int n, int m, const float *__restrict__ xyz1,
+                                                                     const int *__restrict__ lengths,
+                                                                     const float *__restrict__ xyz2,
+                                                                     float *__restrict__ dist, int *__restrict__ idx)
+{
+    __shared__ float4 tile[kNnTile];
+    const int nv = min(max(__builtin_amdgcn_readfirstlane(lengths[blockIdx.y]), 1), n);
+    three_nn_sweep_body<true>(n, nv, m, blockIdx.y, xyz1, xyz2, dist, idx, tile);
 }
 
 
@@ -159,24 +193,31 @@ __device__ __forceinline__ void nn_merge_dpp(double &b1, double &b2, double &b3)
     nn_insert(o3, b1, b2, b3);
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_kernel(int n, int m, int rows_per_part, int parts, int b, float factor,
-                                                            const float *__restrict__ xyz1, const float *__restrict__ xyz2,
-                                                            float *__restrict__ dist, int *__restrict__ idx)
+// Workgroup body; lengths (RAGGED only): the clouds' numbers of valid unknown points -- a workgroup's rows at or beyond its
+// cloud's length are zero-filled and never read, and a workgroup made of such rows alone leaves before the binning.
+template <int NT, bool RAGGED>
+__device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_part, int parts, int b, float factor,
+                                                    const float *__restrict__ xyz1, const int *__restrict__ lengths,
+                                                    const float *__restrict__ xyz2, float *__restrict__ dist,
+                                                    int *__restrict__ idx, char *smem)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     float4 *sorted = reinterpret_cast<float4 *>(smem);                                  // [m] known points in cell order, .w = index
     int *tab = reinterpret_cast<int *>(smem + sizeof(float4) * (size_t)((m + 3) & ~3)); // tab[c] = start of cell c, tab[c + 1] = its end
     float *misc = reinterpret_cast<float *>(tab + kBqTabInts);
     int *fail = reinterpret_cast<int *>(reinterpret_cast<char *>(misc) + kBqMiscBytes); // [0] = count, [1 ..] = rows to sweep
     int cloud, part;
     decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int rb = part * rows_per_part, re = min(rb + rows_per_part, n);
+    const int nv = RAGGED ? min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n) : n;
+    const int rb = part * rows_per_part, re = min(rb + rows_per_part, nv);
     const float *__restrict__ known = xyz2 + (size_t)cloud * m * 3;
     const float *__restrict__ unk = xyz1 + (size_t)cloud * n * 3;
     float *__restrict__ od = dist + (size_t)cloud * n * 3;
     int *__restrict__ oi = idx + (size_t)cloud * n * 3;
     const int t = threadIdx.x, lane = t & 63, sub = t & 3;
+    if (RAGGED) {
+        for (int r = max(rb, nv) + t; r < min(rb + rows_per_part, n); r += NT) nn_zero_row(od + (size_t)r * 3, oi + (size_t)r * 3);
+        if (rb >= nv) return;                              // block-uniform
+    }
     const double empty = __hiloint2double(0x7F800000, 0);  // (+inf : 0) = the reference's (float)1e40, index 0 (:67)
 
     if (t == 0) { tab[0] = 0; fail[0] = 0; }
@@ -289,6 +330,25 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_kernel(i
             oi[(size_t)j * 3 + 0] = __double2loint(b1); oi[(size_t)j * 3 + 1] = __double2loint(b2); oi[(size_t)j * 3 + 2] = __double2loint(b3);
         }
     }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_kernel(int n, int m, int rows_per_part, int parts, int b, float factor,
+                                                            const float *__restrict__ xyz1, const float *__restrict__ xyz2,
+                                                            float *__restrict__ dist, int *__restrict__ idx)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    three_nn_cells_body<NT, false>(n, m, rows_per_part, parts, b, factor, xyz1, nullptr, xyz2, dist, idx, smem);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_ragged_kernel(int n, int m, int rows_per_part, int parts, int b,
+                                                            float factor, const float *__restrict__ xyz1,
+                                                            const int *__restrict__ lengths, const float *__restrict__ xyz2,
+                                                            float *__restrict__ dist, int *__restrict__ idx)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    three_nn_cells_body<NT, true>(n, m, rows_per_part, parts, b, factor, xyz1, lengths, xyz2, dist, idx, smem);
 }
 
 static size_t three_nn_cells_lds(int m, int rows_per_part)
@@ -568,7 +628,9 @@ extern "C" int pn2_fp_interp_concat_grad_planned(int b, int n, int m, int c2, in
 
 // variant: 0 = the library's choice, 1 = the sweep (three_nn_kernel), 2 = the cell list (PN2_E_ARG where it does not exist:
 // fewer than 64 or more than 8192 known points)
-static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx, int variant, void *stream)
+// lengths: NULL = the dense kernels; else the ragged ones (valid unknown points per cloud, device memory)
+static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx, int variant, void *stream,
+                          const int *lengths = nullptr)
 {
     using namespace pn2;
     if (b < 0 || n < 0 || m < 0) return PN2_E_SHAPE;
@@ -592,6 +654,12 @@ static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *x
         const size_t lds = three_nn_cells_lds(m, rows);
 #define PN2_NN_CELLS(NT)                                                                                                          \
         {                                                                                                                         \
+            if (lengths) {                                                                                                        \
+                auto kern = three_nn_cells_ragged_kernel<NT>;                                                                     \
+                if (int rc = allow_dynamic_lds(kern, lds)) return rc;                                                             \
+                return launch(kern, dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor,  \
+                              xyz1, lengths, xyz2, dist, idx);                                                                    \
+            }                                                                                                                     \
             auto kern = three_nn_cells_kernel<NT>;                                                                                \
             if (int rc = allow_dynamic_lds(kern, lds)) return rc;                                                                 \
             return launch(kern, dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor, xyz1, xyz2,  \
@@ -602,6 +670,9 @@ static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *x
         PN2_NN_CELLS(kNnCellsThreads)
 #undef PN2_NN_CELLS
     }
+    if (lengths)
+        return launch(three_nn_ragged_kernel, dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n, m,
+                      xyz1, lengths, xyz2, dist, idx);
     return launch(three_nn_kernel, dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n, m, xyz1, xyz2,
                   dist, idx);
 }
@@ -616,6 +687,19 @@ extern "C" int pn2_three_nn_ex(int b, int n, int m, const float *xyz1, const flo
                                void *stream)
 {
     return three_nn_entry(b, n, m, xyz1, xyz2, dist, idx, variant, stream);
+}
+
+// Ragged unknown side: cloud c of xyz1 is xyz1[c, :lengths1[c]] of a padded (b, n, 3) tensor, lengths1 (b) int32 on the device,
+// never read by the host; xyz2 (b, m, 3) is dense. Valid rows = pn2_three_nn_ex on the slice for every variant; rows at or
+// beyond lengths1[c] are written as idx (0,0,0), dist (0,0,0).
+extern "C" int pn2_three_nn_ragged(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2, float *dist, int *idx,
+                                   int variant, void *stream)
+{
+    if (variant < 0 || variant > 2) return PN2_E_ARG;
+    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;     // a cloud holds at least one unknown point
+    if (b == 0) return PN2_OK;
+    if (!lengths1) return PN2_E_NULL;
+    return three_nn_entry(b, n, m, xyz1, xyz2, dist, idx, variant, stream, lengths1);
 }
 
 static int three_interpolate_entry(int b, int m, int c, int n, const float *points, const int *idx, const float *weight,

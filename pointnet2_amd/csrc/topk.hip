@@ -147,22 +147,19 @@ __device__ __forceinline__ void knn_find_bin(const int *hist, int lane, int want
     before = __shfl(bef, src);
 }
 
-__global__ __launch_bounds__(64) void knn_wave_kernel(int n, int m, int k, const float *__restrict__ xyz1,
-                                                      const float *__restrict__ xyz2, float *__restrict__ oval,
-                                                      int *__restrict__ oidx)
+// One wave, one query: `pts` the n points of the query's cloud, `q` the query, entries row * k .. of oval / oidx its output
+// (the first min(k, n) are written). Shared by the dense kernel and the ragged one (n = the cloud's own length there).
+__device__ __forceinline__ void knn_wave_body(int n, int k, const float *__restrict__ pts, const float *__restrict__ q,
+                                              float *__restrict__ oval, int *__restrict__ oidx, size_t row, char *smem)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     float *val = reinterpret_cast<float *>(smem);                                  // [n]  the distance row
     int *ind = reinterpret_cast<int *>(smem + sizeof(float) * (size_t)n);          // [n]  only for the fallback
     int *hist = ind + n;                                                           // [256]
     unsigned *ckey = reinterpret_cast<unsigned *>(hist + 256);                     // [kKnnCap] order-preserving value key
     int *cpos = reinterpret_cast<int *>(ckey + kKnnCap);                           // [kKnnCap] current slot
     int *cidx = cpos + kKnnCap;                                                    // [kKnnCap] original index
-    const size_t row = blockIdx.x;                               // query number over all clouds
-    const size_t cloud = row / m;
     const int lane = threadIdx.x;
-    const float *pts = xyz1 + cloud * n * 3;
-    const float qx = xyz2[row * 3 + 0], qy = xyz2[row * 3 + 1], qz = xyz2[row * 3 + 2];
+    const float qx = q[0], qy = q[1], qz = q[2];
     unsigned lmin = 0xffffffffu;                                  // smallest key among this lane's elements
     for (int s = lane; s < n; s += 64) {
         const float d = sqdist_key(pts[s * 3 + 0], pts[s * 3 + 1], pts[s * 3 + 2], qx, qy, qz);   // NaN sign cleared (pn2_device.h)
@@ -272,6 +269,39 @@ __global__ __launch_bounds__(64) void knn_wave_kernel(int n, int m, int k, const
     }
 }
 
+__global__ __launch_bounds__(64) void knn_wave_kernel(int n, int m, int k, const float *__restrict__ xyz1,
+                                                      const float *__restrict__ xyz2, float *__restrict__ oval,
+                                                      int *__restrict__ oidx)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t row = blockIdx.x;                               // query number over all clouds
+    const size_t cloud = row / m;
+    knn_wave_body(n, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
+}
+
+// Ragged batch (pn2_knn_point_ragged): the query's cloud holds lengths[cloud] <= n points in its padded slab; the body runs
+// on those alone (LDS laid out for n_c, sized on the host for n). k > n_c: the row's entries from n_c on repeat entry 0, the
+// way a ball query pads with its first hit, so every row is fully written. The length is clamped for memory safety only.
+__global__ __launch_bounds__(64) void knn_wave_ragged_kernel(int n, int m, int k, const float *__restrict__ xyz1,
+                                                             const int *__restrict__ lengths, const float *__restrict__ xyz2,
+                                                             float *__restrict__ oval, int *__restrict__ oidx)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t row = blockIdx.x;
+    const size_t cloud = row / m;
+    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
+    knn_wave_body(nc, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
+    if (k > nc) {                                                // wave-uniform
+        float *ov = oval + row * k;
+        int *oi = oidx + row * k;
+        __syncthreads();                                         // one wave: orders the body's global stores before the reads below
+        __threadfence_block();
+        const float v0 = ov[0];
+        const int i0 = oi[0];
+        for (int s = nc + (int)threadIdx.x; s < k; s += 64) { ov[s] = v0; oi[s] = i0; }
+    }
+}
+
 // fallback for very long rows: the reference's own mapping (one thread per row)
 __global__ __launch_bounds__(64) void selection_sort_serial_kernel(long long rows, int n, int k,
                                                                    const float *__restrict__ dist,
@@ -337,4 +367,23 @@ extern "C" int pn2_knn_point(int b, int n, int m, int k, const float *xyz1, cons
     if (int rc = allow_dynamic_lds(kern, lds)) return rc;
     if (int rc = launch(kern, dim3((unsigned)rows), dim3(64), lds, as_stream(stream), n, m, k, xyz1, xyz2, val, idx)) return rc;
     return PN2_OK;
+}
+
+// Ragged batch: cloud c of xyz1 is xyz1[c, :lengths1[c]] of a padded (b, n, 3) tensor, lengths1 (b) int32 on the device, never
+// read by the host. The first min(k, n_c) entries of a row = pn2_knn_point on the slice; the rest repeat entry 0.
+extern "C" int pn2_knn_point_ragged(int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2, float *val,
+                                    int *idx, void *stream)
+{
+    using namespace pn2;
+    if (k <= 0) return PN2_E_ARG;
+    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
+    const long long rows = (long long)b * m;
+    if (rows == 0) return PN2_OK;
+    if (!xyz1 || !lengths1 || !xyz2 || !val || !idx) return PN2_E_NULL;
+    if (rows > INT_MAX || k > n) return PN2_E_TOO_LARGE;
+    if (n > kSortMaxLdsN - 2048) return PN2_E_TOO_LARGE;
+    const size_t lds = 8 * (size_t)n + sizeof(int) * (256 + 3 * (size_t)kKnnCap);
+    auto kern = knn_wave_ragged_kernel;
+    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+    return launch(kern, dim3((unsigned)rows), dim3(64), lds, as_stream(stream), n, m, k, xyz1, lengths1, xyz2, val, idx);
 }

@@ -19,14 +19,14 @@ from .tf_sampling import farthest_point_sample, farthest_point_sample_gather, ga
 from .tf_grouping import (query_ball_point, group_point, knn_point, query_ball_group_xyz,
                           query_ball_group_xyz_msg, sample_and_group_xyz)
 from .tf_interpolate import three_nn, three_interpolate, fp_interp_concat
-from ._tensors import use_segmented_grad
+from ._tensors import lengths_for, ragged_lengths, use_segmented_grad
 from . import sa_mlp
 from . import train_mlp
-from .geometry import SAGeometry
+from .geometry import FPGeometry, SAGeometry
 from .index_plan import index_plan
 
 
-def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, fused=None):
+def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, fused=None, lengths=None):
     """reference: pointnet_util.py:22-56.
 
     xyz (b, ndataset, 3), points (b, ndataset, channel) or None
@@ -36,22 +36,27 @@ def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=Tr
     fused: use the fused kernels for the xyz branch (bit-identical values): the single overlapped
     launch of csrc/sa_fused.hip (or, with knn, FPS+gather in one launch). Default: whenever xyz
     needs no gradient.
+    lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]], points[i, :lengths[i]]): sampling
+    and grouping see each cloud's own points only (the ragged operators; FPS + gather and ball query + group as two
+    launches), idx names valid rows only, so the padding rows are never gathered.
     """
     if fused is None:
         fused = not (torch.is_grad_enabled() and xyz.requires_grad)
+    if lengths is not None:
+        lengths = lengths_for(lengths, xyz)
     if fused and not knn:
-        _, new_xyz, idx, _, grouped_xyz = sample_and_group_xyz(npoint, radius, nsample, xyz, True)   # :40-46
+        _, new_xyz, idx, _, grouped_xyz = sample_and_group_xyz(npoint, radius, nsample, xyz, True, lengths=lengths)   # :40-46
     elif fused:
-        _, new_xyz = farthest_point_sample_gather(npoint, xyz)                # :40 in one launch
+        _, new_xyz = farthest_point_sample_gather(npoint, xyz, lengths=lengths)   # :40 in one launch
     else:
-        new_xyz = mark_fps_ordered(gather_point(xyz, farthest_point_sample(npoint, xyz)))   # :40
+        new_xyz = mark_fps_ordered(gather_point(xyz, farthest_point_sample(npoint, xyz, lengths=lengths)))   # :40
     if fused and not knn:
         pass
     elif knn:
-        _, idx = knn_point(nsample, xyz, new_xyz)                             # :42
+        _, idx = knn_point(nsample, xyz, new_xyz, lengths1=lengths)           # :42
         grouped_xyz = group_point(xyz, idx) - new_xyz.unsqueeze(2)
     else:
-        idx, _ = query_ball_point(radius, nsample, xyz, new_xyz)              # :44
+        idx, _ = query_ball_point(radius, nsample, xyz, new_xyz, lengths1=lengths)   # :44
         grouped_xyz = group_point(xyz, idx)                                   # :45
         grouped_xyz = grouped_xyz - new_xyz.unsqueeze(2)                      # :46 translation normalisation
     if points is not None:
@@ -79,9 +84,11 @@ def sample_and_group_all(xyz, points, use_xyz=True):
     return new_xyz, new_points, idx, grouped_xyz
 
 
-def three_nn_weights(xyz1, xyz2):
-    """Inverse-squared-distance weights of pointnet_fp_module (pointnet_util.py:211-215)."""
-    dist, idx = three_nn(xyz1, xyz2)
+def three_nn_weights(xyz1, xyz2, lengths1=None):
+    """Inverse-squared-distance weights of pointnet_fp_module (pointnet_util.py:211-215).
+    lengths1: (b,) per-cloud counts of a ragged unknown side (three_nn): rows beyond the length get idx (0,0,0) and the
+    finite weights (1/3, 1/3, 1/3)."""
+    dist, idx = three_nn(xyz1, xyz2, lengths1=lengths1)
     dist = torch.clamp(dist, min=1e-10)                                       # :212
     inv = 1.0 / dist
     norm = inv.sum(dim=2, keepdim=True)                                       # :213
@@ -279,17 +286,23 @@ class PointnetSAModule(nn.Module):
             self._packed(device)
         return self
 
-    def geometry(self, xyz, plans=False):
+    def geometry(self, xyz, plans=False, lengths=None):
         """This level's sampling and grouping alone (:40-46; what forward() launches before its layer stack) -> SAGeometry, or
         None for a group_all level (no sampling, the group is the cloud). geometry.GeometryAhead calls it on its own stream.
-        plans: with the index plan of idx, built right behind the launch that wrote it."""
+        plans: with the index plan of idx, built right behind the launch that wrote it.
+        lengths: (b,) per-cloud point counts of a ragged batch: the ragged operators (each cloud's geometry is the dense
+        geometry of its slice; idx and fps_idx name valid rows only). ValueError for a group_all level."""
         if self.group_all:
+            if lengths is not None:
+                raise ValueError("group_all with lengths: the group would contain the padding rows")
             return None
+        if lengths is not None:
+            lengths = ragged_lengths(lengths, xyz.shape[0], xyz.device)
         if self.knn:
-            fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz)
-            _, idx = knn_point(self.nsample, xyz, new_xyz)
+            fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths)
+            _, idx = knn_point(self.nsample, xyz, new_xyz, lengths1=lengths)
         else:
-            fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
+            fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True, lengths=lengths)
         return SAGeometry(new_xyz, idx, fps_idx, index_plan(idx, xyz.shape[1], "group") if plans else None)
 
     def _forward_on(self, xyz, points, g):
@@ -319,7 +332,17 @@ class PointnetSAModule(nn.Module):
             new_points = grouped_xyz
         return self._stack_and_pool(new_xyz, new_points, idx, grouped_xyz)
 
-    def forward(self, xyz, points, geometry=None):
+    def forward(self, xyz, points, geometry=None, lengths=None):
+        """lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]], points[i, :lengths[i]]).
+        The level's geometry comes from the ragged operators, the layer stack from the same paths as ever (_forward_on): idx
+        names valid rows only, so rows beyond a length are never gathered -- they must be finite (coordinates too when the
+        module trains: a training node may run its first layer once per point, padding rows included, and a NaN times a zero
+        gradient is a NaN), they influence no output and no gradient, and their own gradients are exactly zero. Not for group_all levels (ValueError)."""
+        if lengths is not None:
+            if self.group_all:
+                raise ValueError("group_all with lengths: the group would contain the padding rows")
+            if geometry is None:
+                return self._forward_on(xyz, points, self.geometry(xyz, lengths=lengths))
         if geometry is not None and not self.group_all:
             return self._forward_on(xyz, points, geometry.wait())
         mode = self._train_mode(xyz, points)
@@ -464,10 +487,17 @@ class PointnetSAModuleMSG(nn.Module):
             scales += [(i, g) for i, _, g in rest]
         return (new_xyz, scales, fps_idx) if with_fps else (new_xyz, scales)
 
-    def geometry(self, xyz, plans=False):
+    def geometry(self, xyz, plans=False, lengths=None):
         """This level's sampling and every radius' grouping alone (:173-180) -> SAGeometry with one idx per radius (plans: and
-        one index plan per radius)."""
-        new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
+        one index plan per radius). lengths: (b,) per-cloud point counts of a ragged batch: ragged FPS + gather, then one
+        ragged ball query per radius (the one-binning multi-radius launch is not offered for ragged input)."""
+        if lengths is not None:
+            lengths = ragged_lengths(lengths, xyz.shape[0], xyz.device)
+            fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths)
+            scales = [query_ball_group_xyz(r, k, xyz, new_xyz, True, lengths1=lengths)[0::2]
+                      for r, k in zip(self.radius_list, self.nsample_list)]
+        else:
+            new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
         return SAGeometry(new_xyz, [idx for idx, _ in scales], fps_idx,
                           [index_plan(idx, xyz.shape[1], "group") for idx, _ in scales] if plans else None)
 
@@ -510,7 +540,11 @@ class PointnetSAModuleMSG(nn.Module):
                                               (b, n, self.npoint, cfeat, True) if want_xyz else None)
                    for mlp, ns in zip(self.mlps, self.nsample_list))
 
-    def forward(self, xyz, points, geometry=None):
+    def forward(self, xyz, points, geometry=None, lengths=None):
+        """lengths: (b,) per-cloud point counts of a ragged batch, see PointnetSAModule.forward: the ragged geometry, then the
+        paths a geometry computed ahead takes."""
+        if lengths is not None and geometry is None:
+            geometry = self.geometry(xyz, lengths=lengths)
         g = None if geometry is None else geometry.wait()          # a geometry computed ahead (geometry.py): same results
         if self._fused_ok(xyz, points):
             self.last_path = "fused"
@@ -646,7 +680,40 @@ class PointnetFPModule(nn.Module):
         weight = inv / inv.sum(dim=2, keepdim=True)                             # :213-215
         return self._after_weights(points1, points2, idx, weight, getattr(g, "plan", None))
 
-    def forward(self, xyz1, xyz2, points1, points2, geometry=None):
+    def _forward_ragged(self, xyz1, xyz2, points1, points2, lengths1, geometry=None):
+        """forward() with a ragged unknown side: cloud i's unknown points are xyz1[i, :lengths1[i]] (points1 likewise; the
+        known side is a previous level's dense output). three_nn never reads the padding rows; output rows beyond a length
+        are exactly zero. eval(): the existing paths on all rows (the padding rows of points1 must be finite), then a
+        torch.where. train(): the batch statistics must cover the valid rows only, so the valid rows of interpolate + concat
+        are compacted to (1, total, C), the layer stack runs layer by layer on them and the result is scattered back --
+        plain PyTorch, last_path "unfused_ragged", synchronises (the row list is built on the host's schedule)."""
+        b, n = xyz1.shape[0], xyz1.shape[1]
+        dev = xyz1.device
+        lens = ragged_lengths(lengths1, b, dev, "lengths1")
+        valid = torch.arange(n, device=dev, dtype=torch.int32).unsqueeze(0) < lens.unsqueeze(1)      # (b, n), no host sync
+        if geometry is not None:
+            g = geometry.wait()
+        else:
+            dist, idx = three_nn(xyz1, xyz2, lengths1=lens)                     # :211
+            g = FPGeometry(dist, idx, self._plan_of(idx, xyz2.shape[1]))
+        if not self.training:
+            out = self._forward_on(xyz1, points1, points2, g)
+            return torch.where(valid.unsqueeze(2), out, torch.zeros((), dtype=out.dtype, device=dev))
+        self.last_path = "unfused_ragged"
+        inv = 1.0 / torch.clamp(g.dist, min=1e-10)                              # :212
+        weight = inv / inv.sum(dim=2, keepdim=True)                             # :213-215
+        interpolated = three_interpolate(points2, g.idx, weight, plan=getattr(g, "plan", None))   # :216
+        x = torch.cat([interpolated, points1], dim=2) if points1 is not None else interpolated   # :219
+        rows = valid.reshape(-1).nonzero().squeeze(1)                           # (total,): synchronises
+        xv = x.reshape(b * n, x.shape[2]).index_select(0, rows)                 # the valid rows of all clouds, (total, C)
+        y = self.mlp(xv.t().unsqueeze(0).unsqueeze(3))                          # (1, C, total, 1): statistics over the valid rows
+        yv = y[0, :, :, 0].t()
+        out = torch.zeros((b * n, yv.shape[1]), dtype=yv.dtype, device=dev).index_copy(0, rows, yv)
+        return out.reshape(b, n, yv.shape[1])
+
+    def forward(self, xyz1, xyz2, points1, points2, geometry=None, lengths1=None):
+        if lengths1 is not None:
+            return self._forward_ragged(xyz1, xyz2, points1, points2, lengths1, geometry)
         if geometry is not None:
             return self._forward_on(xyz1, points1, points2, geometry.wait())
         kind = self._fused_kind(points1, points2, xyz1.shape[0] * xyz1.shape[1])

@@ -10,8 +10,8 @@ NoGradient (:21, :32).
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, use_segmented_grad, det_workspace, f32, i32, is_deterministic, on_device, ptr, require,
-                       same_device, seg_workspace, stream_ptr)
+from ._tensors import (out_or_empty, use_segmented_grad, det_workspace, f32, i32, is_deterministic, lengths_for, on_device, ptr,
+                       ragged_lengths, require, same_device, seg_workspace, stream_ptr)
 
 
 # Ball-query kernel choice passed with every call (pn2_query_ball_group_xyz_ex): 0 automatic, 1 sweep,
@@ -25,15 +25,19 @@ def set_ball_query_kernel(kernel=0, cells_qpb=0):
     _BQ_KERNEL[0], _BQ_KERNEL[1] = int(kernel), int(cells_qpb)
 
 
-def query_ball_point(radius, nsample, xyz1, xyz2, out=None):
+def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None):
     """radius float, nsample int, xyz1 (b, ndataset, 3), xyz2 (b, npoint, 3)
     -> idx (b, npoint, nsample) i32, pts_cnt (b, npoint) i32.
+    lengths1: (b,) per-cloud point counts of a ragged xyz1 (cloud i is xyz1[i, :lengths1[i]]): each cloud's result is the
+    dense operator's on its slice, rows beyond the length are never read. None = every cloud holds all ndataset points.
 
     reference: tf_grouping.py:8-20, op QueryBallPoint tf_grouping.cpp:67-106.
     out: optional preallocated (idx, pts_cnt).
     """
     require(float(radius) > 0, "QueryBallPoint expects positive radius")
     require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
+    if lengths1 is not None:
+        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
@@ -45,6 +49,13 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None):
     ns = int(nsample)
     idx = out_or_empty(out[0] if out is not None else None, (b, m, ns), torch.int32, dev, "out[0]")
     cnt = out_or_empty(out[1] if out is not None else None, (b, m), torch.int32, dev, "out[1]")
+    if lengths1 is not None:
+        lens = ragged_lengths(lengths1, b, dev, "lengths1")
+        with on_device(dev):
+            _C.check(_C.lib().pn2_query_ball_group_xyz_ragged(b, n, m, float(radius), ns, ptr(xyz1), ptr(lens), ptr(xyz2), 0, ptr(idx),
+                                                              ptr(cnt), None, _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)),
+                     "query_ball_point")
+        return idx, cnt
     with on_device(dev):
         if _BQ_KERNEL[0] or _BQ_KERNEL[1]:
             _C.check(_C.lib().pn2_query_ball_group_xyz_ex(b, n, m, float(radius), ns, ptr(xyz1), ptr(xyz2), 0, ptr(idx),
@@ -56,16 +67,19 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None):
     return idx, cnt
 
 
-def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, want_idx=True):
+def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None):
     """Fused query_ball_point + group_point(xyz1, idx) [- centroid] in one pass
     (what pointnet_util.py:44-46 does with three ops). No reference counterpart
     (SURVEY.md 8f1); NOT differentiable -- used on the inference path and by
     sample_and_group when xyz does not require grad.
 
     -> idx (b,m,nsample) i32 or None, pts_cnt (b,m) i32, grouped_xyz (b,m,nsample,3) f32
+    lengths1: (b,) per-cloud point counts of a ragged xyz1, see query_ball_point.
     """
     require(float(radius) > 0, "QueryBallPoint expects positive radius")
     require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
+    if lengths1 is not None:
+        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
@@ -78,6 +92,14 @@ def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, wa
     idx = torch.empty((b, m, ns), dtype=torch.int32, device=dev) if want_idx else None
     cnt = torch.empty((b, m), dtype=torch.int32, device=dev)
     grouped = torch.empty((b, m, ns, 3), dtype=torch.float32, device=dev)
+    if lengths1 is not None:
+        lens = ragged_lengths(lengths1, b, dev, "lengths1")
+        with on_device(dev):
+            _C.check(_C.lib().pn2_query_ball_group_xyz_ragged(b, n, m, float(radius), ns, ptr(xyz1), ptr(lens), ptr(xyz2),
+                                                              1 if subtract_centroid else 0, ptr(idx), ptr(cnt), ptr(grouped),
+                                                              _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)),
+                     "query_ball_group_xyz")
+        return idx, cnt, grouped
     with on_device(dev):
         _C.check(_C.lib().pn2_query_ball_group_xyz_ex(b, n, m, float(radius), ns, ptr(xyz1), ptr(xyz2),
                                                       1 if subtract_centroid else 0, ptr(idx), ptr(cnt), ptr(grouped),
@@ -320,16 +342,16 @@ def check_overlapped_launches(device=None):
         _check_status(ent, wait=True)
 
 
-def _two_launch_path(m, radius, ns, xyz, subtract_centroid, ordered=None):
+def _two_launch_path(m, radius, ns, xyz, subtract_centroid, ordered=None, lengths=None):
     """farthest_point_sample_gather + query_ball_group_xyz: what the overlapped launch computes, in two launches.
     ordered: the farthest-point-order hint of the CALLER's tensor (None = read it from xyz)."""
     from .tf_sampling import farthest_point_sample_gather
-    fps_idx, new_xyz = farthest_point_sample_gather(m, xyz, ordered=ordered)
-    idx, cnt, grouped = query_ball_group_xyz(radius, ns, xyz, new_xyz, subtract_centroid)
+    fps_idx, new_xyz = farthest_point_sample_gather(m, xyz, ordered=ordered, lengths=lengths)
+    idx, cnt, grouped = query_ball_group_xyz(radius, ns, xyz, new_xyz, subtract_centroid, lengths1=lengths)
     return fps_idx, new_xyz, idx, cnt, grouped
 
 
-def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, ordered=None):
+def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, ordered=None, lengths=None):
     """The xyz half of sample_and_group (pointnet_util.py:40-46) in ONE launch: farthest point
     sampling, gather, ball query and grouping of xyz, with the ball queries running on the idle CUs
     while the FPS chain is still selecting (csrc/sa_fused.hip). Bit-identical to the separate
@@ -339,6 +361,9 @@ def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, o
     tensors they return (read from the caller's tensor object BEFORE any conversion: a dtype / layout copy does not carry it);
     True / False = say so explicitly. A wrong True costs a check (11-14 us), never a result (tf_sampling.py).
 
+    lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]]): always the two launches
+    (ragged farthest_point_sample_gather, ragged query_ball_group_xyz) -- the overlapped launch is not offered for ragged input.
+
     -> fps_idx (b,m) i32, new_xyz (b,m,3) f32, idx (b,m,nsample) i32, pts_cnt (b,m) i32,
        grouped_xyz (b,m,nsample,3) f32
     """
@@ -346,6 +371,8 @@ def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, o
     require(float(radius) > 0, "QueryBallPoint expects positive radius")
     require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
     from .tf_sampling import mark_fps_ordered, ordered_hint, ordered_worthwhile
+    if lengths is not None:
+        lengths = lengths_for(lengths, xyz)
     if ordered is None:
         ordered = isinstance(xyz, torch.Tensor) and ordered_hint(xyz, int(npoint))
     xyz = f32(xyz, "xyz")
@@ -353,6 +380,8 @@ def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, o
     b, n, _ = xyz.shape
     m, ns = int(npoint), int(nsample)
     dev = xyz.device
+    if lengths is not None:
+        return _two_launch_path(m, radius, ns, xyz, subtract_centroid, False, ragged_lengths(lengths, b, dev))
     lib = _C.lib()
     ordered = bool(ordered) and ordered_worthwhile(xyz, m)
     if b == 0 or not _OVERLAP[0] or not (b <= 256 and 64 <= n <= 8192 and ns <= 256) or ordered:
@@ -487,9 +516,12 @@ def group_point(points, idx, out=None, plan=None):
     return _GroupPoint.apply(points, idx, plan)
 
 
-def knn_point(k, xyz1, xyz2):
+def knn_point(k, xyz1, xyz2, lengths1=None):
     """k int, xyz1 (b, ndataset, c), xyz2 (b, npoint, c) -> val (b, npoint, k) f32
     squared L2 distances, idx (b, npoint, k) i32.
+    lengths1: (b,) per-cloud point counts of a ragged xyz1 (cloud i is xyz1[i, :lengths1[i]]; 3-D points, at most 14336 per
+    padded cloud, k <= ndataset -- ValueError outside): the first min(k, lengths1[i]) entries of a row are the dense
+    operator's on the slice, and where k > lengths1[i] the rest repeat entry 0 (the way a ball query pads with its first hit).
 
     reference: tf_grouping.py:48-73 -- a pairwise squared-distance matrix
     reduce_sum((xyz1-xyz2)**2, -1) followed by select_top_k and a slice.
@@ -497,6 +529,8 @@ def knn_point(k, xyz1, xyz2):
     (pn2_knn_point); other channel counts build the matrix with torch elementwise ops (same per-pair
     arithmetic: differences, squares, a left-to-right sum over c) and run the HIP selection sort.
     """
+    if lengths1 is not None:
+        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz2.dim() == 3 and xyz1.shape[0] == xyz2.shape[0] and
@@ -504,6 +538,17 @@ def knn_point(k, xyz1, xyz2):
     b, n, c = xyz1.shape
     m = xyz2.shape[1]
     require(int(k) > 0, "SelectionSort expects positive k")
+    if lengths1 is not None:
+        require(c == 3 and n <= 14336 and int(k) <= n,
+                "knn_point with lengths1 expects 3-D points, at most 14336 points per (padded) cloud and k <= ndataset")
+        dev = same_device(xyz1, xyz2)
+        lens = ragged_lengths(lengths1, b, dev, "lengths1")
+        val = torch.empty((b, m, int(k)), dtype=torch.float32, device=dev)
+        idx = torch.empty((b, m, int(k)), dtype=torch.int32, device=dev)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_knn_point_ragged(b, n, m, int(k), ptr(xyz1), ptr(lens), ptr(xyz2), ptr(val), ptr(idx),
+                                                   stream_ptr(dev)), "knn_point")
+        return val, idx
     if c == 3 and n <= 14336 and int(k) <= n:
         # one kernel, no (b, m, n) tensors: the distance row lives in LDS (csrc/topk.hip, pn2_knn_point)
         dev = same_device(xyz1, xyz2)

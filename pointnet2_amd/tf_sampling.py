@@ -11,8 +11,8 @@ ProbSample are NoGradient (:22, :57).
 import torch
 
 from . import _C
-from ._tensors import (det_workspace, f32, i32, is_deterministic, on_device, out_or_empty, ptr, require, same_device,
-                       stream_ptr)
+from ._tensors import (det_workspace, f32, i32, is_deterministic, lengths_for, on_device, out_or_empty, ptr, ragged_lengths,
+                       require, same_device, stream_ptr)
 
 
 def prob_sample(inp, inpr):
@@ -98,6 +98,8 @@ _FPS_VARIANT = [FPS_AUTO]
 
 
 def set_fps_variant(variant=FPS_AUTO):
+    """Does not apply to calls with `lengths` (ragged batches): those always run the register tier, one workgroup per cloud
+    (pn2_farthest_point_sample_ragged); the pruned and batched tiers are not offered for ragged input."""
     require(int(variant) in (FPS_AUTO, FPS_FULL, FPS_PRUNED, FPS_BATCH), "fps variant must be 0 (auto), 1 (full), 2 (pruned) or 3 (batched)")
     _FPS_VARIANT[0] = int(variant)
 
@@ -153,8 +155,23 @@ def ordered_workspace(lib, dev, stream, b):
     return ws
 
 
-def farthest_point_sample_gather(npoint, inp, ordered=None):
+FPS_RAGGED_MAX_POINTS = 16384           # the register tier's envelope (pn2_farthest_point_sample_ragged)
+
+
+def _fps_ragged(m, inp, lengths, out, new_xyz, op):
+    b, n, _ = inp.shape
+    require(n <= FPS_RAGGED_MAX_POINTS, "%s with lengths supports at most %d points per (padded) cloud, got %d"
+            % (op, FPS_RAGGED_MAX_POINTS, n))
+    dev = inp.device
+    lens = ragged_lengths(lengths, b, dev)
+    with on_device(dev):
+        _C.check(_C.lib().pn2_farthest_point_sample_ragged(b, n, m, ptr(inp), ptr(lens), ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
+
+
+def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None):
     """Fused farthest_point_sample + gather_point (pointnet_util.py:40 in one launch).
+    lengths: (b,) per-cloud point counts of a ragged batch (cloud i is inp[i, :lengths[i]]): each cloud's result is the
+    dense operator's on its slice, rows beyond the length are never read. None = every cloud holds all n points.
 
     npoint int, inp (b, ndataset, 3) f32 -> idx (b, npoint) i32, new_xyz (b, npoint, 3) f32
     with new_xyz == gather_point(inp, idx) bit for bit. No reference counterpart
@@ -163,6 +180,8 @@ def farthest_point_sample_gather(npoint, inp, ordered=None):
     farthest-point order (same results either way).
     """
     require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
+    if lengths is not None:
+        lengths = lengths_for(lengths, inp)
     if ordered is None:                                    # (before detach(): the hint is an attribute of the caller's tensor object)
         ordered = isinstance(inp, torch.Tensor) and ordered_hint(inp, npoint)
     inp = f32(inp.detach() if isinstance(inp, torch.Tensor) else inp, "inp")
@@ -173,6 +192,9 @@ def farthest_point_sample_gather(npoint, inp, ordered=None):
     dev = inp.device
     out = torch.empty((b, m), dtype=torch.int32, device=dev)
     new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=dev)
+    if lengths is not None:
+        _fps_ragged(m, inp, lengths, out, new_xyz, "farthest_point_sample_gather")
+        return out, mark_fps_ordered(new_xyz)
     lib = _C.lib()
     tf = lib.pn2_fps_temp_floats(b, n)
     temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None
@@ -191,14 +213,17 @@ def farthest_point_sample_gather(npoint, inp, ordered=None):
     return out, mark_fps_ordered(new_xyz)
 
 
-def farthest_point_sample(npoint, inp, out=None):
+def farthest_point_sample(npoint, inp, out=None, lengths=None):
     """npoint int, inp (b, ndataset, 3) f32 -> (b, npoint) i32, first index 0.
+    lengths: (b,) per-cloud point counts of a ragged batch, see farthest_point_sample_gather.
 
     reference: tf_sampling.py:48-56, op FarthestPointSample tf_sampling.cpp:95-123,
     kernel tf_sampling_g.cu:105-170 (tie rule: smallest (k mod 512, k)).
     out: optional preallocated (b, npoint) i32 result.
     """
     require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
+    if lengths is not None:
+        lengths = lengths_for(lengths, inp)
     hinted = isinstance(inp, torch.Tensor) and ordered_hint(inp, npoint)      # the previous level's samples: checked short cut
     inp = f32(inp.detach() if isinstance(inp, torch.Tensor) else inp, "inp")
     require(inp.dim() == 3 and inp.shape[2] == 3, "FarthestPointSample expects (batch_size,num_points,3) inp shape")
@@ -207,6 +232,9 @@ def farthest_point_sample(npoint, inp, out=None):
     m = int(npoint)
     dev = inp.device
     out = out_or_empty(out, (b, m), torch.int32, dev)
+    if lengths is not None:
+        _fps_ragged(m, inp, lengths, out, None, "farthest_point_sample")
+        return out
     lib = _C.lib()
     tf = lib.pn2_fps_temp_floats(b, n)
     temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None   # allocate_temp, tf_sampling.cpp:115
