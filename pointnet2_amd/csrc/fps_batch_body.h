@@ -55,7 +55,10 @@
 //     bits are >= the bound; the first sample of a batch always is: the list holds every updater wave's best lane, so its
 //     maximum is the global one. The loop counts nothing: a list has at most 64 valid lanes, so it ends by the bound exit; only a
 //     batch that could pass the end of the output row (fewer than 64 samples left) runs the compiler's counted form.
-//   * APPLY (updaters, behind the picker). A wave polls the count, takes up to CH = 64 / GW new samples at a time -- lane l tests
+//   * APPLY (updaters, behind the picker). A wave polls the count and reads, in the same LDS round trip, its lanes' ring rows
+//     (row done + the lane's sample, clamped to the ring: PN2_BT_RING1) -- two reads back to back, one wait: LDS serves a wave's
+//     operations in order and the picker stores a row before it adds to the count, so what lies below the count read is
+//     complete and the lanes beyond it leave by the np mask. It takes up to CH = 64 / GW new samples at a time -- lane l tests
 //     sample l % CH against the box of the wave's group l / CH: one distance-to-box computation for 64 (sample, group) pairs --
 //     and updates the touched groups, group by group (packed fp32, as in the pruned tier; no key work: keys are only needed at
 //     COLLECT). A group's bits of the touched mask are one field of a scalar word and a bit's number is the lane that holds
@@ -221,10 +224,18 @@ inline bool fps_batch_pays(int ranks, int m) { return fps_batch_covers(ranks) &&
 // [6] picker cycles in READ, [7] picker cycles in PICK, [8] picker cycles waiting at the barrier, [9] updater 0 cycles in COLLECT,
 // [10] updater 0 cycles from the barrier to the end flag, [11] tie resolutions, [12] speculation misses, [13] samples taken one per
 // exchange after slow batches, [14] such runs; updater 0: [15] cycles from seeing the end flag to arriving at the next list barrier
-// (epilogue + COLLECT), [16] chunks, [17] polls that found nothing, [18] (group, sample) updates taken on the dense path
-__device__ unsigned long long g_bt_stats[24];
+// (epilogue + COLLECT), [16] chunks, [17] polls that found nothing, [18] (group, sample) updates taken on the dense path, [19] cycles
+// around the poll's wait (count word; with PN2_BT_RING1 the ring row too), [20] from there to the ring row's arrival (readfirstlane,
+// compare, branch, the chunk counter's atomic and, without PN2_BT_RING1, the row's own round trip), [21] two clock reads back to back,
+// all three per chunk and only with PN2_BT_STATS_CHUNK (default 1: the three clock reads and atomics per chunk make updater 0 later
+// than it is -- the per-wave figures that follow are taken with 0); every updater wave w:
+// [24 + w] cycles behind the first arriver at the list barrier, [32 + w] times it was the last to arrive
+__device__ unsigned long long g_bt_stats[40];
 #ifndef PN2_BT_STATS_FROM
 #define PN2_BT_STATS_FROM 0
+#endif
+#ifndef PN2_BT_STATS_CHUNK
+#define PN2_BT_STATS_CHUNK 1
 #endif
 #define PN2_BT_STAT(i, v) do { if (lane == 0 && cloud == 0 && j >= PN2_BT_STATS_FROM) atomicAdd(&g_bt_stats[i], (unsigned long long)(v)); } while (0)
 #define PN2_BT_CLOCK() __builtin_readcyclecounter()
@@ -270,6 +281,13 @@ __device__ unsigned long long g_bt_stats[24];
 #endif
 #ifndef PN2_BT_GBITS
 #define PN2_BT_GBITS 1               // APPLY: lane l tests sample l % CH against group l / CH, so a group's bits of the touched mask are one 32-bit field whose bit numbers are lane numbers (0: sample l / GW, group l % GW, strided 64-bit masks)
+#endif
+// lab switches of the APPLY chunk's LDS reads (each measured alone: profiles/fps_apply/README.md)
+#ifndef PN2_BT_RING1
+#define PN2_BT_RING1 1               // APPLY: the lane's ring row read behind the count word, one wait for both (0: the row read waits for the count, two dependent LDS round trips per chunk)
+#endif
+#ifndef PN2_BT_SSRC
+#define PN2_BT_SSRC 1                // APPLY: the sample as an SGPR pair of the packed subtract, op_sel_hi:[1,0] (0: v_readlane + v_mov into the low half of a register pair)
 #endif
 #ifndef PN2_BT_G0
 #define PN2_BT_G0 0.10f               // initial 1 - theta / (last sample value)
@@ -686,16 +704,30 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             blx = o[0]; bly = o[1]; blz = o[2]; bhx = o[4]; bhy = o[5]; bhz = o[6];
         }
         pn2_f2 sxy = {0.f, 0.f}, syy = {0.f, 0.f}, szk = {0.f, 0.f};   // the sample in the LOW halves (fps_body.h: the high-half broadcast form is not safe)
-        auto update_group = [&](auto gic) __attribute__((always_inline)) {
+        // PN2_BT_SSRC: APPLY's samples come out of v_readlane, that is in scalar registers. v_pk_add_f32 takes an SGPR pair as a
+        // source and op_sel_hi:[1,0] makes both halves read the pair's LOW word, like the low-half broadcast of a register pair:
+        // the three v_mov into the low halves go away (21 instructions per sparse update for 24). The pairs' high words are set
+        // once per kernel and never read. scripts/pk_hazard_lab.hip: the form returns the bits of the register-pair form and of
+        // __fsub_rn in both halves, normal and denormal operands, alone, beside a VALU kernel and beside an MFMA kernel, with 0, 1,
+        // 2 and 5 wait states behind the v_readlane that writes the pair (the compiler puts none there).
+        typedef unsigned bt_u2 __attribute__((ext_vector_type(2)));
+        bt_u2 ssx = {0u, 0u}, ssy = {0u, 0u}, ssz = {0u, 0u};
+        auto pk_sub_bcast_s = [](pn2_f2 a, bt_u2 sp) __attribute__((always_inline)) {
+            pn2_f2 r;
+            asm volatile("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "s"(sp));
+            return r;
+        };
+        auto update_group = [&](auto gic, auto scalar_sample) __attribute__((always_inline)) {
             constexpr int gi = decltype(gic)::value;
+            constexpr bool SS = decltype(scalar_sample)::value;                  // the sample is in ssx / ssy / ssz (else sxy / syy / szk)
             constexpr int H = GS / 2;
             pn2_f2 dx[H], dy[H], dz[H];
 #pragma unroll
-            for (int h = 0; h < H; ++h) dx[h] = pk_sub_bcast_lo(xx[gi * H + h], sxy);
+            for (int h = 0; h < H; ++h) dx[h] = SS ? pk_sub_bcast_s(xx[gi * H + h], ssx) : pk_sub_bcast_lo(xx[gi * H + h], sxy);
 #pragma unroll
-            for (int h = 0; h < H; ++h) dy[h] = pk_sub_bcast_lo(yy[gi * H + h], syy);
+            for (int h = 0; h < H; ++h) dy[h] = SS ? pk_sub_bcast_s(yy[gi * H + h], ssy) : pk_sub_bcast_lo(yy[gi * H + h], syy);
 #pragma unroll
-            for (int h = 0; h < H; ++h) dz[h] = pk_sub_bcast_lo(zz[gi * H + h], szk);
+            for (int h = 0; h < H; ++h) dz[h] = SS ? pk_sub_bcast_s(zz[gi * H + h], ssz) : pk_sub_bcast_lo(zz[gi * H + h], szk);
 #pragma unroll
             for (int h = 0; h < H; ++h) dx[h] = pk_mul(dx[h], dx[h]);
 #pragma unroll
@@ -713,20 +745,20 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 md[p0 + 1] = vmin_f32(dx[h].y, md[p0 + 1]);
             }
         };
-        auto update_all = [&]() __attribute__((always_inline)) {
-            update_group(std::integral_constant<int, 0>());
-            if constexpr (GW >= 2) update_group(std::integral_constant<int, 1>());
-            if constexpr (GW >= 4) { update_group(std::integral_constant<int, 2>()); update_group(std::integral_constant<int, 3>()); }
+        auto update_all = [&](auto ss) __attribute__((always_inline)) {
+            update_group(std::integral_constant<int, 0>(), ss);
+            if constexpr (GW >= 2) update_group(std::integral_constant<int, 1>(), ss);
+            if constexpr (GW >= 4) { update_group(std::integral_constant<int, 2>(), ss); update_group(std::integral_constant<int, 3>(), ss); }
             if constexpr (GW == 8) {
-                update_group(std::integral_constant<int, 4>()); update_group(std::integral_constant<int, 5>());
-                update_group(std::integral_constant<int, 6>()); update_group(std::integral_constant<int, 7>());
+                update_group(std::integral_constant<int, 4>(), ss); update_group(std::integral_constant<int, 5>(), ss);
+                update_group(std::integral_constant<int, 6>(), ss); update_group(std::integral_constant<int, 7>(), ss);
             }
         };
         // sample 0 is point 0 (tf_sampling_g.cu:114-116): every slot against it
         {
             const float4 s = lds_rank[NS - 1];
             sxy.x = s.x; syy.x = s.y; szk.x = s.z;
-            update_all();
+            update_all(std::false_type());
         }
         if (t == 0) {
             dst[0] = 0;
@@ -776,7 +808,7 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 }
                 if constexpr (P >= PN2_BT_PACKED_FROM) {                         // (16 slots on single registers: spills at 576 threads)
                     sxy.x = s.x; syy.x = s.y; szk.x = s.z;
-                    update_all();
+                    update_all(std::false_type());
                 } else {
 #pragma unroll
                     for (int p = 0; p < P; ++p) {
@@ -914,9 +946,25 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
 #endif
             const long long u1 = PN2_BT_CLOCK();
             if (w == 0 && uend) PN2_BT_STAT(15, u1 - uend);
+#if defined(PN2_BT_STATS) && PN2_BT_READ1
+            if (lane == 0) X.cnt[w] = (unsigned)u1;              // lab: this wave's arrival (the per-wave count words are free with PN2_BT_READ1)
+#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the asm LDS operations above are invisible to the compiler's counters
             __syncthreads();
             const long long u2 = PN2_BT_CLOCK();
+#if defined(PN2_BT_STATS) && PN2_BT_READ1
+            // lab: how far behind the first arriver this wave reached the list barrier, and whether it was the last. Nobody writes
+            // this parity's words again before the barrier after next.
+            {
+                int first = 0, last = 0;
+                for (int i = 0; i < W; ++i) {
+                    const int d = (int)(X.cnt[i] - (unsigned)u1);
+                    first = min(first, d); last = max(last, d);
+                }
+                PN2_BT_STAT(24 + w, -first);
+                PN2_BT_STAT(32 + w, last == 0);
+            }
+#endif
 #if !PN2_BT_READ1
             if (lane == 0) xch[par ^ 1].bound[w] = 0u;            // next batch's word of this wave (nobody reads it before the next barrier)
 #endif
@@ -925,8 +973,54 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             unsigned c;
             // v* of the skip test: the previous batch's last sample value bounds every running distance (fps_pruned_body: the exact skip)
             const float thr = __fadd_rn(__fmul_rn(__uint_as_float(vlastb), 1.00001f), 1e-30f);
+            const int pi = GB ? (lane & (CH - 1)) : lane / GW;                   // this lane's sample of a chunk
+            typedef std::integral_constant<bool, PN2_BT_SSRC != 0> bt_ss;
+            auto sample_in = [&](const float4 &s4, const int sl) __attribute__((always_inline)) {   // sample <- lane sl of the chunk's ring read
+#if PN2_BT_SSRC
+                ssx.x = (unsigned)__builtin_amdgcn_readlane(__float_as_int(s4.x), sl);
+                ssy.x = (unsigned)__builtin_amdgcn_readlane(__float_as_int(s4.y), sl);
+                ssz.x = (unsigned)__builtin_amdgcn_readlane(__float_as_int(s4.z), sl);
+#else
+                sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s4.x), sl));
+                syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s4.y), sl));
+                szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s4.z), sl));
+#endif
+            };
+#if PN2_BT_RING1
+            // ONE LDS ROUND TRIP PER CHUNK (PN2_BT_RING1). The count word and this lane's ring row are read back to back and waited
+            // for once: the row's address hangs on `done` and the lane, not on the count. LDS serves a wave's operations in order,
+            // so the row's read is served behind the count's; the picker's winner lane stores a row and then adds to the count, in
+            // order too. So every row below the count just read is complete. Rows at or beyond it may be stale or half written:
+            // their lanes leave by the np mask below as before (without the cut they re-read row `done`). The row index is clamped
+            // to the ring's 64 rows (done + the lane's sample reaches 78 at 16 samples per chunk, 126 at 64). The compiler puts a
+            // wait behind an acquire load, so the two reads and their single wait are one asm statement (list_write above does
+            // the same); the wait is the acquire. A poll that finds nothing wastes the row's read and nothing else.
+            typedef float bt_f3 __attribute__((ext_vector_type(3)));
+            unsigned poll_addr = (unsigned)(size_t)&X.count;
+            unsigned row0_addr = (unsigned)(size_t)ring + 16u * (unsigned)pi, row_last_addr = (unsigned)(size_t)ring + 16u * (kBtCand - 1);
+            asm("" : "+v"(poll_addr), "+v"(row0_addr), "+v"(row_last_addr));   // three registers of the batch: not worked out again in every poll
+#endif
             for (;;) {
+#ifdef PN2_BT_STATS
+                const long long w0 = PN2_BT_CLOCK();
+#endif
+#if PN2_BT_RING1
+                bt_f3 srow;
+                asm volatile("ds_read_b32 %[c], %[ca]\n\t"
+                             "ds_read_b96 %[s], %[ra]\n\t"
+                             "s_waitcnt lgkmcnt(0)"
+                             : [c] "=&v"(c), [s] "=&v"(srow)
+                             : [ca] "v"(poll_addr), [ra] "v"(min(row0_addr + 16u * (unsigned)done, row_last_addr))
+                             : "memory");
+#else
                 c = __hip_atomic_load(&X.count, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+#ifdef PN2_BT_STATS
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");               // lab: the count's wait inside [19]
+#endif
+#endif
+#ifdef PN2_BT_STATS
+                const long long w1 = PN2_BT_CLOCK();
+#endif
                 c = (unsigned)__builtin_amdgcn_readfirstlane((int)c);
                 const int avail = (int)(c & kBtCountMask);
                 if (avail == done) {
@@ -939,8 +1033,24 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                 constexpr unsigned long long kStride = GW == 8 ? 0x0101010101010101ull : GW == 4 ? 0x1111111111111111ull
                                                        : GW == 2 ? 0x5555555555555555ull : ~0ull;   // one bit per sample
                 const int np = min(avail - done, CH);
-                const int pi = GB ? (lane & (CH - 1)) : lane / GW;               // this lane's sample of the chunk
+#if PN2_BT_RING1
+                const float4 s = make_float4(srow.x, srow.y, srow.z, 0.f);      // (w, the point's index, is not used here)
+#else
                 const float4 s = ring[done + (pi < np ? pi : 0)];
+#endif
+#ifdef PN2_BT_STATS
+                // lab: updater 0's cycles inside the chunk's two waits -- [19] around the count's (the poll's) wait, [20] around the
+                // ring row's (PN2_BT_RING1: nothing is left to wait for), [21] two clock reads with nothing in between, the cost
+                // each of the two figures carries
+                if (PN2_BT_STATS_CHUNK && w == 0) {
+#if !PN2_BT_RING1
+                    asm volatile("s_waitcnt lgkmcnt(0)" :: "v"(s.x), "v"(s.y), "v"(s.z) : "memory");
+#endif
+                    const long long w2 = PN2_BT_CLOCK();
+                    const long long w3 = PN2_BT_CLOCK();
+                    PN2_BT_STAT(19, w1 - w0); PN2_BT_STAT(20, w2 - w1); PN2_BT_STAT(21, w3 - w2);
+                }
+#endif
                 const float ax = __fsub_rn(s.x, __builtin_amdgcn_fmed3f(s.x, blx, bhx));
                 const float ay = __fsub_rn(s.y, __builtin_amdgcn_fmed3f(s.y, bly, bhy));
                 const float az = __fsub_rn(s.z, __builtin_amdgcn_fmed3f(s.z, blz, bhz));
@@ -962,10 +1072,8 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                         if (w == 0) PN2_BT_STAT(18, GW * np);
                         for (int p = 0; p < np; ++p) {
                             const int sl = GB ? p : p * GW;                      // a lane that holds sample p
-                            sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.x), sl));
-                            syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.y), sl));
-                            szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.z), sl));
-                            update_all();
+                            sample_in(s, sl);
+                            update_all(bt_ss());
                         }
                     } else {
                         auto one_group = [&](auto gic) __attribute__((always_inline)) {
@@ -979,22 +1087,18 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                                 while (mg) {
                                     const int sl = (int)__builtin_ctz(mg);
                                     asm("s_bitset0_b32 %0, %1" : "+s"(mg) : "s"(sl));
-                                    sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.x), sl));
-                                    syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.y), sl));
-                                    szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.z), sl));
+                                    sample_in(s, sl);
                                     PN2_BT_STAT(5, 1);
-                                    update_group(gic);
+                                    update_group(gic, bt_ss());
                                 }
                             } else {
                                 unsigned long long mg = touched & (kStride << g8);
                                 while (mg) {
                                     const int sl = (int)__builtin_ctzll(mg) & ~(GW - 1);
                                     mg &= mg - 1ull;
-                                    sxy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.x), sl));
-                                    syy.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.y), sl));
-                                    szk.x = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s.z), sl));
+                                    sample_in(s, sl);
                                     PN2_BT_STAT(5, 1);
-                                    update_group(gic);
+                                    update_group(gic, bt_ss());
                                 }
                             }
                         };

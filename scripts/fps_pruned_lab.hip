@@ -74,7 +74,7 @@ int main(int argc, char **argv)
                 const float us_half = timed(5, [&]() { vs[vi].run(m / 2); });
 #ifdef PN2_BT_STATS
                 if (vi == 3) {
-                    unsigned long long z[24] = {0}, st[24];
+                    unsigned long long z[40] = {0}, st[40];
                     CK(hipMemcpyToSymbol(HIP_SYMBOL(pn2::g_bt_stats), z, sizeof(z)));
                     vs[vi].run(m); CK(hipDeviceSynchronize());
                     CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(pn2::g_bt_stats), sizeof(st)));
@@ -85,6 +85,15 @@ int main(int argc, char **argv)
                            (double)st[7] / st[1], (double)st[8] / st[0], (double)st[9] / st[0], (double)st[10] / st[0]);
                     printf("   updater 0 per batch: end flag -> next list barrier %.0f cycles, chunks %.1f, polls that found nothing %.1f, (group, sample) updates on the dense path %.1f\n",
                            (double)st[15] / st[0], (double)st[16] / st[0], (double)st[17] / st[0], (double)st[18] / st[0]);
+                    // the chunk's two waits (each figure carries one clock read, [21]) and every updater wave's arrival at the list barrier
+                    const double ch = st[16] ? (double)st[16] : 1.0;
+                    printf("   updater 0 per chunk: cycles around the poll's wait %.0f, from there to the ring row %.0f, two clock reads back to back %.0f\n",
+                           (double)st[19] / ch, (double)st[20] / ch, (double)st[21] / ch);
+                    printf("   list barrier, cycles behind the first arriver per batch, waves 0..7:");
+                    for (int i = 0; i < 8; ++i) printf(" %.0f", (double)st[24 + i] / st[0]);
+                    printf(" | times last:");
+                    for (int i = 0; i < 8; ++i) printf(" %llu", st[32 + i]);
+                    printf("\n");
                 }
 #endif
                 printf("%-10s n=%5d %s m=%4d : %7.1f us, prologue (m=1) %6.1f us, %6.1f ns/round overall, %6.1f ns/round in the second half  %s\n",

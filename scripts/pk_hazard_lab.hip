@@ -123,6 +123,64 @@ __global__ __launch_bounds__(256) void probe(unsigned long long *bad, int iters)
     if (cnt) atomicAdd(bad, cnt);
 }
 
+// The sample as a SCALAR operand of the packed subtract: v_pk_add_f32 d, x, s[20:21] op_sel_hi:[1,0] with the neg modifiers, the
+// pair's low word written by a v_readlane NOPS wait states ahead, its high word a NaN pattern that nothing may read. Compared, bit
+// for bit and in both halves, with the VGPR form (fps_body.h's pk_sub_bcast_lo: the same modifiers on a register pair whose low
+// half a v_mov filled) and with __fsub_rn. The sample is another lane's value in every pass, so a subtract that reads the pair
+// before the v_readlane's write has landed sees the previous pass's sample and is counted. DEN: inputs around and below the
+// smallest normal number, so operands and differences are denormal. Inline asm cannot name one half of a register pair, hence
+// the fixed pair and the clobbers.
+template <int NOPS, int DEN>
+__global__ __launch_bounds__(256) void probe_ssrc(unsigned long long *bad, int iters)
+{
+    unsigned s = threadIdx.x * 2654435761u + blockIdx.x * 40503u + 12345u;
+    auto rnd = [&]() { s = s * 1664525u + 1013904223u; return (s >> 8) * (1.0f / 16777216.0f); };
+    const float scale = DEN ? 2.0e-38f : 1.0f;
+    const f2 x = {rnd() * scale, rnd() * scale};
+    unsigned long long cnt = 0;
+    for (int i = 0; i < iters; ++i) {
+        const float vs = rnd() * scale;
+        const int ln = (i * 7) & 63;
+        f2 rs;
+#define SSRC(N)                                                                                                          \
+        asm volatile("s_mov_b32 s21, 0x7fc00001\n\t"                                                                     \
+                     "v_readlane_b32 s20, %[vs], %[ln]\n\t" N                                                            \
+                     "v_pk_add_f32 %[rs], %[x], s[20:21] op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]"                      \
+                     : [rs] "=&v"(rs) : [x] "v"(x), [vs] "v"(vs), [ln] "s"(ln) : "s20", "s21")
+        if (NOPS == 0) SSRC(NOPSTR_0);
+        if (NOPS == 1) SSRC(NOPSTR_1);
+        if (NOPS == 2) SSRC(NOPSTR_2);
+        if (NOPS == 5) SSRC(NOPSTR_5);
+#undef SSRC
+        const float sv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vs), ln));
+        const f2 sp = {sv, __uint_as_float(0x7fc00001u)};
+        f2 rv;
+        asm volatile("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(rv) : "v"(x), "v"(sp));
+        const float c0 = __fsub_rn(x.x, sv), c1 = __fsub_rn(x.y, sv);
+        cnt += (__float_as_uint(rs.x) != __float_as_uint(rv.x)) + (__float_as_uint(rs.y) != __float_as_uint(rv.y));
+        cnt += (__float_as_uint(rs.x) != __float_as_uint(c0)) + (__float_as_uint(rs.y) != __float_as_uint(c1));
+    }
+    if (cnt) atomicAdd(bad, cnt);
+}
+
+template <int NOPS, int DEN>
+static void run_ssrc(const char *name, unsigned long long *d_bad, float *sink, hipStream_t sv, hipStream_t sa)
+{
+    for (int ag = 0; ag < 3; ++ag) {
+        CK(hipMemset(d_bad, 0, 8));
+        for (int r = 0; r < 20; ++r) {
+            if (ag == 1) hipLaunchKernelGGL(ag_mfma, dim3(2048), dim3(256), 0, sa, sink, 4000);
+            if (ag == 2) hipLaunchKernelGGL(ag_valu, dim3(2048), dim3(256), 0, sa, sink, 20000);
+            hipLaunchKernelGGL((probe_ssrc<NOPS, DEN>), dim3(64), dim3(256), 0, sv, d_bad, 2000);
+            if (ag == 1) hipLaunchKernelGGL(ag_mfma, dim3(2048), dim3(256), 0, sa, sink, 4000);
+        }
+        CK(hipDeviceSynchronize());
+        unsigned long long h; CK(hipMemcpy(&h, d_bad, 8, hipMemcpyDeviceToHost));
+        printf("%-28s %-10s: %llu halves differ from the VGPR form or from __fsub_rn (of %llu comparisons)\n", name,
+               ag == 0 ? "alone" : ag == 1 ? "beside mfma" : "beside valu", h, 20ull * 64 * 256 * 2000 * 4);
+    }
+}
+
 template <int MODE>
 static void run(const char *name, unsigned long long *d_bad, float *sink, hipStream_t sv, hipStream_t sa)
 {
@@ -152,5 +210,11 @@ int main()
     run<202>("asm, low-half, no neg", d_bad, sink, sv, sa);
     run<0>("asm, no wait states", d_bad, sink, sv, sa);
     run<1>("asm, 1 wait state", d_bad, sink, sv, sa);
+    run_ssrc<0, 0>("sgpr source, 0 wait states", d_bad, sink, sv, sa);
+    run_ssrc<1, 0>("sgpr source, 1 wait state", d_bad, sink, sv, sa);
+    run_ssrc<2, 0>("sgpr source, 2 wait states", d_bad, sink, sv, sa);
+    run_ssrc<5, 0>("sgpr source, 5 wait states", d_bad, sink, sv, sa);
+    run_ssrc<0, 1>("sgpr source, 0 ws, denormal", d_bad, sink, sv, sa);
+    run_ssrc<2, 1>("sgpr source, 2 ws, denormal", d_bad, sink, sv, sa);
     return 0;
 }
