@@ -170,3 +170,21 @@ def use_segmented_grad(b, rows, c):
 def seg_workspace(lib, b, rows, entries, device):
     nbytes = lib.pn2_seg_grad_ws_bytes(b, rows, entries)
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=device)
+
+
+def scatter_grad(lib, op, head, idx, plan, tail, b, rows, c, entries, dev):
+    """THE rule for which reduction a scatter-add gradient (op = "group_point" / "three_interpolate": `entries` gradient rows
+    per cloud summed into (b, rows, c)) takes -- INTEGRATION.md C'' states it, every caller goes through here:
+    segmented (use_segmented_grad) from the index plan where idx was inverted when it was born, else inverting idx in a
+    workspace; otherwise, in deterministic mode, 64-bit fixed-point sums; otherwise fp32 atomics.
+    Calls pn2_<op>_grad{_planned,_seg,_det,}(*head, plan or idx, *tail, [workspace,] [deterministic,] stream) -> its return code."""
+    det = 1 if is_deterministic() else 0
+    if use_segmented_grad(b, rows, c):
+        if plan is not None:
+            return getattr(lib, "pn2_%s_grad_planned" % op)(*head, ptr(plan.buffer), *tail, det, stream_ptr(dev))
+        ws = seg_workspace(lib, b, rows, entries, dev)
+        return getattr(lib, "pn2_%s_grad_seg" % op)(*head, ptr(idx), *tail, ptr(ws), det, stream_ptr(dev))
+    if det:
+        ws = det_workspace(lib, b, rows, c, dev)
+        return getattr(lib, "pn2_%s_grad_det" % op)(*head, ptr(idx), *tail, ptr(ws), stream_ptr(dev))
+    return getattr(lib, "pn2_%s_grad" % op)(*head, ptr(idx), *tail, stream_ptr(dev))

@@ -85,14 +85,16 @@ class SAGeometry(_Ready):
     def new_xyz_for(self, xyz):
         """new_xyz as the consumer must use it: the precomputed tensor, or -- when xyz needs a gradient -- the same values
         gathered from xyz by the differentiable operator, so that the centroid term of d / d xyz is not lost (the geometry
-        itself is computed from xyz.detach())."""
+        itself is computed from xyz.detach()). The re-gathered tensor carries the farthest-point-order hint the sampling operators
+        leave on their own new_xyz (tf_sampling.mark_fps_ordered): it never changes a result, it lets the next level's sampling
+        take the checked identity."""
         if not (torch.is_grad_enabled() and xyz.requires_grad):
             return self.new_xyz
         if self.fps_idx is None:
             raise ValueError("this geometry carries no sample indices, and xyz requires a gradient: the centroids cannot be "
                              "rebuilt differentiably -- compute the geometry with GeometryAhead / module.geometry(), or detach xyz")
-        from .tf_sampling import gather_point
-        return gather_point(xyz, self.fps_idx)
+        from .tf_sampling import gather_point, mark_fps_ordered
+        return mark_fps_ordered(gather_point(xyz, self.fps_idx))
 
 
 class FPGeometry(_Ready):

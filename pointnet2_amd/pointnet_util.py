@@ -70,12 +70,18 @@ def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=Tr
     return new_xyz, new_points, idx, grouped_xyz
 
 
-def sample_and_group_all(xyz, points, use_xyz=True):
-    """reference: pointnet_util.py:59-84 (one group holding every point, centroid (0,0,0))."""
+def _all_in_one_group(xyz):
+    """The geometry of a group_all level (:72-74): one centroid at the origin, one group naming every point."""
     b, n, _ = xyz.shape
     new_xyz = torch.zeros((b, 1, 3), dtype=torch.float32, device=xyz.device)
     idx = torch.arange(n, dtype=torch.int32, device=xyz.device).reshape(1, 1, n).repeat(b, 1, 1)
-    grouped_xyz = xyz.reshape(b, 1, n, 3)
+    return new_xyz, idx
+
+
+def sample_and_group_all(xyz, points, use_xyz=True):
+    """reference: pointnet_util.py:59-84 (one group holding every point, centroid (0,0,0))."""
+    new_xyz, idx = _all_in_one_group(xyz)
+    grouped_xyz = xyz.reshape(xyz.shape[0], 1, xyz.shape[1], 3)
     if points is not None:
         new_points = torch.cat([xyz, points], dim=2) if use_xyz else points
         new_points = new_points.unsqueeze(1)
@@ -84,16 +90,18 @@ def sample_and_group_all(xyz, points, use_xyz=True):
     return new_xyz, new_points, idx, grouped_xyz
 
 
+def _inverse_distance_weights(dist):
+    """three_nn's squared distances -> the interpolation weights of pointnet_fp_module (pointnet_util.py:212-215)."""
+    inv = 1.0 / torch.clamp(dist, min=1e-10)                                  # :212
+    return inv / inv.sum(dim=2, keepdim=True)                                 # :213-215
+
+
 def three_nn_weights(xyz1, xyz2, lengths1=None):
     """Inverse-squared-distance weights of pointnet_fp_module (pointnet_util.py:211-215).
     lengths1: (b,) per-cloud counts of a ragged unknown side (three_nn): rows beyond the length get idx (0,0,0) and the
     finite weights (1/3, 1/3, 1/3)."""
     dist, idx = three_nn(xyz1, xyz2, lengths1=lengths1)
-    dist = torch.clamp(dist, min=1e-10)                                       # :212
-    inv = 1.0 / dist
-    norm = inv.sum(dim=2, keepdim=True)                                       # :213
-    weight = inv / norm                                                       # :215
-    return idx, weight
+    return idx, _inverse_distance_weights(dist)
 
 
 def use_tf_moving_variance(model, flag=True):
@@ -118,6 +126,51 @@ def _no_packing_under_capture():
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
         raise RuntimeError("the fused MLP weights are not packed yet (or changed): call module.prepare_fused(device) -- "
                            "or run one eager eval forward -- before capturing a graph")
+
+
+def _train_fused_ok(mod, stacks, pooling, group_all, xyz, points):
+    """Training (batch-statistics batch norm, autograd) of a set-abstraction module on stacks pn2_mlp_train_forward covers: conv
+    1x1 + BN + ReLU triples, rows a multiple of 32, nsample 16 or a multiple of 32 (train_mlp.py); avg / weighted_avg /
+    max_and_avg where pn2_mlp_train_pool_supported says so. stacks: [(net, nsample)] -- the module's one stack, or one per
+    radius of an MSG module (which asks with pooling "max"); every one of them must be covered."""
+    if not mod.fused_mlp or not mod.training or not xyz.is_cuda:
+        return False
+    want_xyz = torch.is_grad_enabled() and xyz.requires_grad
+    if (want_xyz and not mod.fused_xyz_grad) or (points is not None and not mod.use_xyz):
+        return False
+    b, n, _ = xyz.shape
+    m = 1 if group_all else mod.npoint
+    if want_xyz:                                   # (never weighted_avg: its weights depend on xyz)
+        cfeat = points.shape[2] if points is not None else 0
+        return all(train_mlp.xyz_grad_supported(net, b * m * ns, ns, pooling, b, n, m, cfeat, not group_all) for net, ns in stacks)
+    if pooling != "max":
+        return all(train_mlp.pool_supported(net, b * m * ns, ns, pooling) for net, ns in stacks)
+    return all(train_mlp.stack_supported(net, b * m * ns, ns, True) for net, ns in stacks)
+
+
+def _frozen_ok(mod, stacks, pooling, group_all, xyz, points):
+    """Autograd through stacks whose batch norms all normalise with their running statistics (fused_frozen_bn): something
+    must want a gradient -- an input (xyz only with fused_xyz_grad, as in training) or a parameter of a stack -- and
+    pn2_mlp_train_frozen_supported must cover every stack. What the batch-statistics node refuses is refused here too."""
+    if not mod.fused_frozen_bn or not mod.fused_mlp or not torch.is_grad_enabled() or not xyz.is_cuda:
+        return False
+    want_xyz = xyz.requires_grad
+    if (want_xyz and not mod.fused_xyz_grad) or (points is not None and not mod.use_xyz):
+        return False
+    if not (want_xyz or (points is not None and points.requires_grad) or
+            any(p.requires_grad for net, _ in stacks for p in net.parameters())):
+        return False
+    b, n, _ = xyz.shape
+    m = 1 if group_all else mod.npoint
+    dims = (b, n, m, points.shape[2] if points is not None else 0, not group_all) if want_xyz else None
+    return all(train_mlp.frozen_supported(net, b * m * ns, ns, True, pooling, dims) for net, ns in stacks)
+
+
+def _train_mode(mod, stacks, pooling, group_all, xyz, points):
+    """"fused_train" (batch statistics), "fused_frozen" (running statistics, opt-in) or None: which fused autograd node."""
+    if _train_fused_ok(mod, stacks, pooling, group_all, xyz, points):
+        return "fused_train"
+    return "fused_frozen" if _frozen_ok(mod, stacks, pooling, group_all, xyz, points) else None
 
 
 class _SharedMLP(nn.Module):
@@ -192,28 +245,10 @@ class PointnetSAModule(nn.Module):
         self._pack_cache = None
         self._lvl_buffers = None
 
-    def _frozen_ok(self, xyz, points):
-        """Autograd through a stack whose batch norms all normalise with their running statistics (fused_frozen_bn): something
-        must want a gradient -- an input (xyz only with fused_xyz_grad, as in training) or a parameter of the stack -- and
-        pn2_mlp_train_frozen_supported must cover the level. What the batch-statistics node refuses is refused here too."""
-        if not self.fused_frozen_bn or not self.fused_mlp or not torch.is_grad_enabled() or not xyz.is_cuda:
-            return False
-        want_xyz = xyz.requires_grad
-        if (want_xyz and not self.fused_xyz_grad) or (points is not None and not self.use_xyz):
-            return False
-        if not (want_xyz or (points is not None and points.requires_grad) or any(p.requires_grad for p in self.mlp.net.parameters())):
-            return False
-        b, n, _ = xyz.shape
-        ns = n if self.group_all else self.nsample
-        m = 1 if self.group_all else self.npoint
-        dims = (b, n, m, points.shape[2] if points is not None else 0, not self.group_all) if want_xyz else None
-        return train_mlp.frozen_supported(self.mlp.net, b * m * ns, ns, True, self.pooling, dims)
-
     def _train_mode(self, xyz, points):
-        """"fused_train" (batch statistics), "fused_frozen" (running statistics, opt-in) or None: which fused autograd node."""
-        if self._train_fused_ok(xyz, points):
-            return "fused_train"
-        return "fused_frozen" if self._frozen_ok(xyz, points) else None
+        """The module-level _train_mode on this module's one stack (a group_all level's group is the whole cloud)."""
+        return _train_mode(self, [(self.mlp.net, xyz.shape[1] if self.group_all else self.nsample)], self.pooling, self.group_all,
+                           xyz, points)
 
     def _level_buffers(self):
         if not self.reuse_buffers:
@@ -237,25 +272,6 @@ class PointnetSAModule(nn.Module):
         if self.group_all:                         # only the cooperative kernel gathers a whole cloud without idx
             return sa_mlp.supported(cin, self.mlp.widths, xyz.shape[1]) and sa_mlp.kind(cin, self.mlp.widths, xyz.shape[1]) == "cooperative"
         return sa_mlp.supported(cin, self.mlp.widths, self.nsample)
-
-    def _train_fused_ok(self, xyz, points):
-        """Training (batch-statistics batch norm, autograd) on a stack pn2_mlp_train_forward covers: conv 1x1 + BN + ReLU
-        triples, rows a multiple of 32, nsample 16 or a multiple of 32 (train_mlp.py); avg / weighted_avg / max_and_avg
-        where pn2_mlp_train_pool_supported says so."""
-        if not self.fused_mlp or not self.training or not xyz.is_cuda:
-            return False
-        want_xyz = torch.is_grad_enabled() and xyz.requires_grad
-        if (want_xyz and not self.fused_xyz_grad) or (points is not None and not self.use_xyz):
-            return False
-        b, n, _ = xyz.shape
-        ns = n if self.group_all else self.nsample
-        rows = b * (1 if self.group_all else self.npoint) * ns
-        if want_xyz:                               # (never weighted_avg: its weights depend on xyz)
-            return train_mlp.xyz_grad_supported(self.mlp.net, rows, ns, self.pooling, b, n, 1 if self.group_all else self.npoint,
-                                                points.shape[2] if points is not None else 0, not self.group_all)
-        if self.pooling != "max":
-            return train_mlp.pool_supported(self.mlp.net, rows, ns, self.pooling)
-        return train_mlp.stack_supported(self.mlp.net, rows, ns, True)
 
     def _packed(self, device, nsample=None):
         """Folded + packed weights, rebuilt when a parameter or a running statistic changed."""
@@ -305,91 +321,81 @@ class PointnetSAModule(nn.Module):
             fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True, lengths=lengths)
         return SAGeometry(new_xyz, idx, fps_idx, index_plan(idx, xyz.shape[1], "group") if plans else None)
 
-    def _forward_on(self, xyz, points, g):
-        """forward() on a geometry computed ahead (geometry.py): the layer stack only, same paths, same results -- and the same
-        gradients: with xyz.requires_grad the centroids are re-gathered differentiably (SAGeometry.new_xyz_for; the fused
-        training node is taken then only with fused_xyz_grad, the inference kernels never)."""
-        new_xyz, idx = g.new_xyz_for(xyz), g.idx
-        mode = self._train_mode(xyz, points)
-        if mode is not None:
-            self.last_path = mode
-            plan = getattr(g, "plan", None)
+    def _forward_on(self, xyz, points, g, path=None):
+        """The layer stack on a geometry -- forward()'s own or one computed ahead (geometry.py): same paths, same results, and
+        the same gradients: with xyz.requires_grad the centroids are re-gathered differentiably (SAGeometry.new_xyz_for; the
+        fused training node is taken then only with fused_xyz_grad, the inference kernels never). The only place where
+        sa_mlp_train and sa_mlp_pool are called with an idx. path: the last_path forward() has already decided on."""
+        if path is None:
+            path = self._train_mode(xyz, points) or ("fused" if self._fused_ok(xyz, points) else "unfused")
+        self.last_path = path
+        new_xyz, idx, plan = g.new_xyz_for(xyz), g.idx, getattr(g, "plan", None)
+        if path in ("fused_train", "fused_frozen"):
+            # ONE autograd node for gather + layer stack (batch-statistics batch norm -- or, "fused_frozen", the running
+            # statistics) + pooling, forward and backward on the matrix cores (train_mlp.py)
             if plan is None and self.index_plans and torch.is_grad_enabled():
                 plan = index_plan(idx, xyz.shape[1], "group")
             out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling,
-                                            xyz_grad=torch.is_grad_enabled() and xyz.requires_grad, frozen=mode == "fused_frozen",
+                                            xyz_grad=torch.is_grad_enabled() and xyz.requires_grad, frozen=path == "fused_frozen",
                                             plan=plan)
             return new_xyz, self._post(out), idx
-        if self._fused_ok(xyz, points):
-            self.last_path = "fused"
+        if path == "fused":
             return new_xyz, self._post(sa_mlp.sa_mlp_pool(xyz, new_xyz, points, idx, self._packed(xyz.device), self.pooling)), idx
-        self.last_path = "unfused"
-        grouped_xyz = group_point(xyz, idx, plan=getattr(g, "plan", None)) - new_xyz.unsqueeze(2)            # :45-46
+        grouped_xyz = group_point(xyz, idx, plan=plan) - new_xyz.unsqueeze(2)   # :45-46
         if points is not None:
-            grouped_points = group_point(points, idx, plan=getattr(g, "plan", None))            # :48
+            grouped_points = group_point(points, idx, plan=plan)                 # :48
             new_points = torch.cat([grouped_xyz, grouped_points], dim=-1) if self.use_xyz else grouped_points   # :50
         else:
             new_points = grouped_xyz
         return self._stack_and_pool(new_xyz, new_points, idx, grouped_xyz)
 
+    def _forward_all(self, xyz, points, mode):
+        """A group_all level on the fused kernels: sample_and_group_all (:59-84) + the layer stack + pooling as the training node
+        (mode) or as the cooperative inference kernel; new_xyz = origin, the group is the whole cloud, channels [xyz, features]."""
+        new_xyz, idx = _all_in_one_group(xyz)
+        if mode is not None:
+            self.last_path = mode
+            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True, self.pooling,
+                                            xyz_grad=torch.is_grad_enabled() and xyz.requires_grad, frozen=mode == "fused_frozen")
+        else:
+            self.last_path = "fused"
+            out = sa_mlp.sa_mlp_maxpool(xyz, None, points, None, self._packed(xyz.device, xyz.shape[1]))
+        return new_xyz, self._post(out), idx
+
     def forward(self, xyz, points, geometry=None, lengths=None):
-        """lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]], points[i, :lengths[i]]).
-        The level's geometry comes from the ragged operators, the layer stack from the same paths as ever (_forward_on): idx
+        """Resolve the level's geometry, then run the layer stack on it (_forward_on): a geometry computed ahead
+        (geometry=), the ragged operators' (lengths=), or this call's own (geometry()) for the training nodes and for the
+        inference kernel behind kNN or a pooling other than max. Three routes are not "geometry, then stack" and stay apart:
+        a group_all level (no sampling; _forward_all), the single C call sa_mlp.sa_level (eval, ball query, max pooling: it
+        owns the level's buffers) and the layer-by-layer path without a geometry (sample_and_group's own launches, or the
+        differentiable operator sequence when xyz needs a gradient).
+
+        lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]], points[i, :lengths[i]]): idx
         names valid rows only, so rows beyond a length are never gathered -- they must be finite (coordinates too when the
         module trains: a training node may run its first layer once per point, padding rows included, and a NaN times a zero
         gradient is a NaN), they influence no output and no gradient, and their own gradients are exactly zero. Not for group_all levels (ValueError)."""
-        if lengths is not None:
-            if self.group_all:
-                raise ValueError("group_all with lengths: the group would contain the padding rows")
-            if geometry is None:
-                return self._forward_on(xyz, points, self.geometry(xyz, lengths=lengths))
-        if geometry is not None and not self.group_all:
-            return self._forward_on(xyz, points, geometry.wait())
+        if lengths is not None and self.group_all:
+            raise ValueError("group_all with lengths: the group would contain the padding rows")
         mode = self._train_mode(xyz, points)
-        if mode is not None:
-            # training: the level's geometry in the fused launches, then ONE autograd node for gather + layer stack
-            # (batch-statistics batch norm -- or, "fused_frozen", the running statistics) + pooling, forward and backward on the
-            # matrix cores (train_mlp.py)
-            self.last_path = mode
-            frozen = mode == "fused_frozen"
-            want_xyz = torch.is_grad_enabled() and xyz.requires_grad     # (fused_xyz_grad: the node differentiates the coordinates too)
-            if self.group_all:
-                b, n, _ = xyz.shape
-                new_xyz = torch.zeros((b, 1, 3), dtype=torch.float32, device=xyz.device)
-                idx = torch.arange(n, dtype=torch.int32, device=xyz.device).reshape(1, 1, n).repeat(b, 1, 1)
-                out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True, self.pooling, xyz_grad=want_xyz,
-                                                frozen=frozen)
-                return new_xyz, self._post(out), idx
-            if self.knn:
-                fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz)
-                _, idx = knn_point(self.nsample, xyz, new_xyz)
-            else:
-                fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
-            if want_xyz:                                              # the centroids' path back to xyz: GatherPoint's gradient (:40)
-                new_xyz = mark_fps_ordered(gather_point(xyz, fps_idx))
-            plan = index_plan(idx, xyz.shape[1], "group") if self.index_plans and torch.is_grad_enabled() else None
-            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, idx, True, self.pooling, xyz_grad=want_xyz,
-                                            frozen=frozen, plan=plan)
-            return new_xyz, self._post(out), idx
-        if self.group_all and self._fused_ok(xyz, points):
-            # sample_and_group_all (:59-84) + the layer stack + reduce_max in ONE kernel: new_xyz = origin, the
-            # group is the whole cloud, channels [xyz, features]
-            self.last_path = "fused"
-            b, n, _ = xyz.shape
-            new_xyz = torch.zeros((b, 1, 3), dtype=torch.float32, device=xyz.device)
-            idx = torch.arange(n, dtype=torch.int32, device=xyz.device).reshape(1, 1, n).repeat(b, 1, 1)
-            return new_xyz, self._post(sa_mlp.sa_mlp_maxpool(xyz, None, points, None, self._packed(xyz.device, n))), idx
-        if self._fused_ok(xyz, points):
+        if self.group_all and (mode is not None or self._fused_ok(xyz, points)):
+            return self._forward_all(xyz, points, mode)
+        fused = mode is None and self._fused_ok(xyz, points)      # (a group_all level that got here says no once more)
+        if self.group_all:
+            g = None
+        elif geometry is not None:
+            g = geometry.wait()
+        elif lengths is not None:
+            g = self.geometry(xyz, lengths=lengths)
+        elif mode is not None or (fused and (self.knn or self.pooling != "max")):
+            g = self.geometry(xyz, plans=mode is not None and self.index_plans and torch.is_grad_enabled())
+        else:
+            g = None
+        if g is not None:
+            return self._forward_on(xyz, points, g, mode or ("fused" if fused else "unfused"))
+        if fused:
             # ONE C call (csrc/levels.hip): FPS + ball query in the overlapped launch, then one kernel from idx to the
             # pooled features: the (b, npoint, nsample, C) tensors of pointnet_util.py:44-50 and :117-127 never exist
             self.last_path = "fused"
-            if self.knn:                                              # :41-42: the k nearest points instead of the ball, same stack kernel
-                _, new_xyz = farthest_point_sample_gather(self.npoint, xyz)
-                _, idx = knn_point(self.nsample, xyz, new_xyz)
-                return new_xyz, self._post(sa_mlp.sa_mlp_pool(xyz, new_xyz, points, idx, self._packed(xyz.device), self.pooling)), idx
-            if self.pooling != "max":                                 # the overlapped launch, then the stack with this pooling
-                _, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True)
-                return new_xyz, self._post(sa_mlp.sa_mlp_pool(xyz, new_xyz, points, idx, self._packed(xyz.device), self.pooling)), idx
             new_xyz, out, idx, _, _, _ = sa_mlp.sa_level(self.npoint, self.radius, self.nsample, xyz, points,
                                                           self._packed(xyz.device), self._level_buffers())
             return new_xyz, self._post(out), idx
@@ -501,76 +507,34 @@ class PointnetSAModuleMSG(nn.Module):
         return SAGeometry(new_xyz, [idx for idx, _ in scales], fps_idx,
                           [index_plan(idx, xyz.shape[1], "group") for idx, _ in scales] if plans else None)
 
-    def _forward_fused(self, xyz, points, g=None):
-        """Inference: the grouping launches of _group_scales (or a geometry computed ahead), then one fused MLP + max-pool
-        kernel per scale; no grouped tensor is ever materialised."""
+    def _forward_fused(self, xyz, points, g):
+        """Inference: the grouping launches of _group_scales (g None; no geometry object on the eager path, which is bound by
+        the host) or a geometry, then one fused MLP + max-pool kernel per scale; no grouped tensor is ever materialised."""
         if g is None:
             new_xyz, scales = self._group_scales(xyz, True)
+            idxs = [idx for idx, _ in scales]
         else:
-            new_xyz, scales = g.new_xyz, [(idx, None) for idx in g.idx]
-        outs = [sa_mlp.sa_mlp_maxpool(xyz, new_xyz, points, idx, self._packed(si, xyz.device))
-                for si, (idx, _) in enumerate(scales)]
+            new_xyz, idxs = g.new_xyz, g.idx
+        outs = [sa_mlp.sa_mlp_maxpool(xyz, new_xyz, points, idx, self._packed(si, xyz.device)) for si, idx in enumerate(idxs)]
         return new_xyz, torch.cat(outs, dim=2)
 
-    def _train_fused_ok(self, xyz, points):
+    def _forward_train(self, xyz, points, g, mode):
+        """Training on a geometry: one autograd node per scale (train_mlp.py); channel order features FIRST (:184).
+        "fused_frozen": the same with the running statistics (fused_frozen_bn). With xyz.requires_grad (fused_xyz_grad) the
+        centroids are re-gathered differentiably and autograd adds the scales' coordinate gradients."""
+        new_xyz = g.new_xyz_for(xyz)
+        plans = getattr(g, "plan", None)
+        if plans is None and self.index_plans and torch.is_grad_enabled():
+            plans = [index_plan(idx, xyz.shape[1], "group") for idx in g.idx]
         want_xyz = torch.is_grad_enabled() and xyz.requires_grad
-        if not self.fused_mlp or not self.training or not xyz.is_cuda or (want_xyz and not self.fused_xyz_grad):
-            return False
-        if points is not None and not self.use_xyz:
-            return False
-        rows = xyz.shape[0] * self.npoint
-        if want_xyz:
-            cfeat = points.shape[2] if points is not None else 0
-            return all(train_mlp.xyz_grad_supported(mlp.net, rows * ns, ns, "max", xyz.shape[0], xyz.shape[1], self.npoint, cfeat)
-                       for mlp, ns in zip(self.mlps, self.nsample_list))
-        return all(train_mlp.stack_supported(mlp.net, rows * ns, ns, True) for mlp, ns in zip(self.mlps, self.nsample_list))
+        outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False, xyz_grad=want_xyz, frozen=mode == "fused_frozen",
+                                       plan=plan)[0]
+                for mlp, idx, plan in zip(self.mlps, g.idx, plans or [None] * len(g.idx))]
+        return new_xyz, torch.cat(outs, dim=2)
 
-    def _frozen_ok(self, xyz, points):
-        """See PointnetSAModule._frozen_ok: every scale's batch norms in eval(), something wants a gradient."""
-        if not self.fused_frozen_bn or not self.fused_mlp or not torch.is_grad_enabled() or not xyz.is_cuda:
-            return False
-        want_xyz = xyz.requires_grad
-        if (want_xyz and not self.fused_xyz_grad) or (points is not None and not self.use_xyz):
-            return False
-        if not (want_xyz or (points is not None and points.requires_grad) or any(p.requires_grad for p in self.mlps.parameters())):
-            return False
-        b, n, _ = xyz.shape
-        cfeat = points.shape[2] if points is not None else 0
-        return all(train_mlp.frozen_supported(mlp.net, b * self.npoint * ns, ns, True, "max",
-                                              (b, n, self.npoint, cfeat, True) if want_xyz else None)
-                   for mlp, ns in zip(self.mlps, self.nsample_list))
-
-    def forward(self, xyz, points, geometry=None, lengths=None):
-        """lengths: (b,) per-cloud point counts of a ragged batch, see PointnetSAModule.forward: the ragged geometry, then the
-        paths a geometry computed ahead takes."""
-        if lengths is not None and geometry is None:
-            geometry = self.geometry(xyz, lengths=lengths)
-        g = None if geometry is None else geometry.wait()          # a geometry computed ahead (geometry.py): same results
-        if self._fused_ok(xyz, points):
-            self.last_path = "fused"
-            return self._forward_fused(xyz, points, g)
-        mode = "fused_train" if self._train_fused_ok(xyz, points) else "fused_frozen" if self._frozen_ok(xyz, points) else None
-        if mode is not None:
-            # training: grouping launches as in inference, then one autograd node per scale (train_mlp.py);
-            # channel order features FIRST (:184). "fused_frozen": the same with the running statistics (fused_frozen_bn)
-            self.last_path = mode
-            want_xyz = torch.is_grad_enabled() and xyz.requires_grad     # (fused_xyz_grad: autograd adds the scales' coordinate gradients)
-            if g is None:
-                new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
-                if want_xyz:                                          # GatherPoint's gradient (:173)
-                    new_xyz = mark_fps_ordered(gather_point(xyz, fps_idx))
-            else:
-                new_xyz, scales = g.new_xyz_for(xyz), [(idx, None) for idx in g.idx]
-            plans = getattr(g, "plan", None)
-            if plans is None and self.index_plans and torch.is_grad_enabled():
-                plans = [index_plan(idx, xyz.shape[1], "group") for idx, _ in scales]
-            if plans is None:
-                plans = [None] * len(scales)
-            outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False, xyz_grad=want_xyz, frozen=mode == "fused_frozen",
-                                           plan=plan)[0]
-                    for mlp, (idx, _), plan in zip(self.mlps, scales, plans)]
-            return new_xyz, torch.cat(outs, dim=2)
-        self.last_path = "unfused"
+    def _forward_layers(self, xyz, points, g):
+        """Layer by layer (:173-195). g None: this call's own launches -- _group_scales' grouped_xyz, or the differentiable
+        operator sequence when xyz needs a gradient."""
         fused = g is not None or not (torch.is_grad_enabled() and xyz.requires_grad)
         scales = None
         if g is not None:
@@ -596,6 +560,23 @@ class PointnetSAModuleMSG(nn.Module):
             x = mlp(grouped.permute(0, 3, 1, 2))
             outs.append(x.max(dim=3)[0])                                        # :193
         return new_xyz, torch.cat(outs, dim=1).permute(0, 2, 1).contiguous()    # :195
+
+    def forward(self, xyz, points, geometry=None, lengths=None):
+        """Resolve the level's geometry -- computed ahead (geometry=), the ragged operators' (lengths=, see
+        PointnetSAModule.forward) or, for the training nodes, this call's own (geometry()) -- then one function per path on it.
+        Without a geometry the inference kernels and the layer-by-layer path keep their own launches (_group_scales)."""
+        if geometry is None and lengths is not None:
+            geometry = self.geometry(xyz, lengths=lengths)
+        g = None if geometry is None else geometry.wait()
+        if self._fused_ok(xyz, points):
+            self.last_path = "fused"
+            return self._forward_fused(xyz, points, g)
+        mode = _train_mode(self, [(mlp.net, ns) for mlp, ns in zip(self.mlps, self.nsample_list)], "max", False, xyz, points)
+        if mode is not None:
+            self.last_path = mode
+            return self._forward_train(xyz, points, g or self.geometry(xyz, plans=self.index_plans and torch.is_grad_enabled()), mode)
+        self.last_path = "unfused"
+        return self._forward_layers(xyz, points, g)
 
 
 class PointnetFPModule(nn.Module):
@@ -654,31 +635,44 @@ class PointnetFPModule(nn.Module):
             self._packed(c2, c1, kind, device)
         return self
 
+    def _train_mode(self, points1, points2, rows):
+        """"fused_train" / "fused_frozen" / None: which fused autograd node runs the stack behind ONE launch for weights +
+        interpolation + concatenation. Only where that launch's gradient is the segmented scatter (use_segmented_grad)."""
+        if not use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]):
+            return None
+        if self.fused_mlp and self.training and points2.is_cuda and train_mlp.stack_supported(self.mlp.net, rows, 0, False):
+            return "fused_train"
+        return "fused_frozen" if self._frozen_ok(points1, points2, rows) else None
+
     def _forward_on(self, xyz1, points1, points2, g):
         """forward() on three_nn's result computed ahead (geometry.py): everything after :211, same paths, same results."""
-        dist, idx = g.dist, g.idx
         kind = self._fused_kind(points1, points2, xyz1.shape[0] * xyz1.shape[1])
-        c1 = points1.shape[2] if points1 is not None else 0
         if kind is not None:
             self.last_path = "fused"
-            return sa_mlp.fp_mlp(points2, points1, idx, dist, self._packed(points2.shape[2], c1, kind, points2.device))
-        if self.fused_mlp and self.training and points2.is_cuda and use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
-                train_mlp.stack_supported(self.mlp.net, xyz1.shape[0] * xyz1.shape[1], 0, False):
-            self.last_path = "fused_train"
-            plan = self._plan_of(idx, points2.shape[1], getattr(g, "plan", None))
-            if train_mlp.fp_level_preferred(xyz1.shape[0], xyz1.shape[1], points2.shape[1], points2.shape[2]) and \
-                    train_mlp.fp_level_supported(self.mlp.net, xyz1.shape[0], xyz1.shape[1], points2.shape[1], points2.shape[2], c1):
-                return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist, plan=plan)     # :212-226 as one node
-            x, _ = fp_interp_concat(points2, points1, idx, dist, plan=plan)     # :212-219
-            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1)
-        if use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
-                self._frozen_ok(points1, points2, xyz1.shape[0] * xyz1.shape[1]):
-            self.last_path = "fused_frozen"
-            x, _ = fp_interp_concat(points2, points1, idx, dist, plan=self._plan_of(idx, points2.shape[1], getattr(g, "plan", None)))   # :212-219
-            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, frozen=True)
-        inv = 1.0 / torch.clamp(dist, min=1e-10)                                # :212
-        weight = inv / inv.sum(dim=2, keepdim=True)                             # :213-215
-        return self._after_weights(points1, points2, idx, weight, getattr(g, "plan", None))
+            c1 = points1.shape[2] if points1 is not None else 0
+            return sa_mlp.fp_mlp(points2, points1, g.idx, g.dist, self._packed(points2.shape[2], c1, kind, points2.device))
+        return self._stack_on(xyz1, points1, points2, g)
+
+    def _stack_on(self, xyz1, points1, points2, g):
+        """Everything after :211 but the inference kernels, on three_nn's result g (dist, idx and perhaps a plan)."""
+        dist, idx, plan = g.dist, g.idx, getattr(g, "plan", None)
+        b, n = xyz1.shape[0], xyz1.shape[1]
+        m, c2 = points2.shape[1], points2.shape[2]
+        c1 = points1.shape[2] if points1 is not None else 0
+        mode = self._train_mode(points1, points2, b * n)
+        if mode is None:                                                        # layer by layer
+            return self._after_weights(points1, points2, idx, _inverse_distance_weights(dist), plan)
+        # ONE launch for weights + interpolation + concatenation (+ the zero pad of an odd width), then the layer stack as one
+        # autograd node (train_mlp.py) with batch-statistics batch norm -- or, "fused_frozen", the running statistics; backward:
+        # the stack's kernels, one split + the segmented scatter of three_interpolate's gradient
+        self.last_path = mode
+        plan = self._plan_of(idx, m, plan)
+        if mode == "fused_train" and train_mlp.fp_level_preferred(b, n, m, c2) and \
+                train_mlp.fp_level_supported(self.mlp.net, b, n, m, c2, c1):
+            # weights, interpolation, concatenation and the stack as ONE node, layer 1 once per known point (train_mlp_fp.hip)
+            return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist, plan=plan)     # :212-226
+        x, _ = fp_interp_concat(points2, points1, idx, dist, plan=plan)         # :212-219
+        return train_mlp.fp_mlp_train(self.mlp.net, x, cin=c2 + c1, frozen=mode == "fused_frozen")
 
     def _forward_ragged(self, xyz1, xyz2, points1, points2, lengths1, geometry=None):
         """forward() with a ragged unknown side: cloud i's unknown points are xyz1[i, :lengths1[i]] (points1 likewise; the
@@ -700,9 +694,7 @@ class PointnetFPModule(nn.Module):
             out = self._forward_on(xyz1, points1, points2, g)
             return torch.where(valid.unsqueeze(2), out, torch.zeros((), dtype=out.dtype, device=dev))
         self.last_path = "unfused_ragged"
-        inv = 1.0 / torch.clamp(g.dist, min=1e-10)                              # :212
-        weight = inv / inv.sum(dim=2, keepdim=True)                             # :213-215
-        interpolated = three_interpolate(points2, g.idx, weight, plan=getattr(g, "plan", None))   # :216
+        interpolated = three_interpolate(points2, g.idx, _inverse_distance_weights(g.dist), plan=getattr(g, "plan", None))   # :212-216
         x = torch.cat([interpolated, points1], dim=2) if points1 is not None else interpolated   # :219
         rows = valid.reshape(-1).nonzero().squeeze(1)                           # (total,): synchronises
         xv = x.reshape(b * n, x.shape[2]).index_select(0, rows)                 # the valid rows of all clouds, (total, C)
@@ -712,6 +704,9 @@ class PointnetFPModule(nn.Module):
         return out.reshape(b, n, yv.shape[1])
 
     def forward(self, xyz1, xyz2, points1, points2, geometry=None, lengths1=None):
+        """three_nn -- computed ahead (geometry=) or here -- then the stack on its result (_stack_on). One route stays apart:
+        inference without a geometry is ONE C call (sa_mlp.fp_level: three_nn and the level's kernel; it owns the level's
+        buffers). lengths1: a ragged unknown side, see _forward_ragged."""
         if lengths1 is not None:
             return self._forward_ragged(xyz1, xyz2, points1, points2, lengths1, geometry)
         if geometry is not None:
@@ -726,31 +721,7 @@ class PointnetFPModule(nn.Module):
                 self._lvl_buffers = sa_mlp.LevelBuffers()
             return sa_mlp.fp_level(xyz1, xyz2, points1, points2, self._packed(points2.shape[2], c1, kind, points2.device),
                                    self._lvl_buffers if self.reuse_buffers else None)
-        if self.fused_mlp and self.training and points2.is_cuda and use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
-                train_mlp.stack_supported(self.mlp.net, xyz1.shape[0] * xyz1.shape[1], 0, False):
-            # training: three_nn, then ONE launch for weights + interpolation + concatenation (+ the zero pad of an odd width),
-            # then the layer stack with batch-statistics batch norm as one autograd node (train_mlp.py); backward: the stack's
-            # kernels, one split + the segmented scatter of three_interpolate's gradient
-            self.last_path = "fused_train"
-            dist, idx = three_nn(xyz1, xyz2)                                    # :211
-            plan = self._plan_of(idx, xyz2.shape[1])
-            c1 = points1.shape[2] if points1 is not None else 0
-            if train_mlp.fp_level_preferred(xyz1.shape[0], xyz1.shape[1], xyz2.shape[1], points2.shape[2]) and \
-                    train_mlp.fp_level_supported(self.mlp.net, xyz1.shape[0], xyz1.shape[1], xyz2.shape[1], points2.shape[2], c1):
-                # weights, interpolation, concatenation and the stack as ONE node, layer 1 once per known point (train_mlp_fp.hip)
-                return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist, plan=plan)     # :212-226
-            x, _ = fp_interp_concat(points2, points1, idx, dist, plan=plan)     # :212-219
-            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1)
-        if use_segmented_grad(points2.shape[0], points2.shape[1], points2.shape[2]) and \
-                self._frozen_ok(points1, points2, xyz1.shape[0] * xyz1.shape[1]):
-            # gradients through batch norms in eval(): the same launches with the running statistics (fused_frozen_bn)
-            self.last_path = "fused_frozen"
-            dist, idx = three_nn(xyz1, xyz2)                                    # :211
-            c1 = points1.shape[2] if points1 is not None else 0
-            x, _ = fp_interp_concat(points2, points1, idx, dist, plan=self._plan_of(idx, xyz2.shape[1]))   # :212-219
-            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, frozen=True)
-        idx, weight = three_nn_weights(xyz1, xyz2)                              # :211-215
-        return self._after_weights(points1, points2, idx, weight)
+        return self._stack_on(xyz1, points1, points2, FPGeometry(*three_nn(xyz1, xyz2)))                  # :211
 
     def _after_weights(self, points1, points2, idx, weight, plan=None):
         """:216-226 of the layer-by-layer path."""

@@ -10,8 +10,8 @@ NoGradient (:21, :32).
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, use_segmented_grad, det_workspace, f32, i32, is_deterministic, lengths_for, on_device, ptr,
-                       ragged_lengths, require, same_device, seg_workspace, stream_ptr)
+from ._tensors import (out_or_empty, f32, i32, lengths_for, on_device, ptr, ragged_lengths, require, same_device, scatter_grad,
+                       stream_ptr)
 
 
 # Ball-query kernel choice passed with every call (pn2_query_ball_group_xyz_ex): 0 automatic, 1 sweep,
@@ -474,22 +474,8 @@ class _GroupPoint(torch.autograd.Function):
         dev = grad_out.device
         grad_points = torch.empty((b, n, c), dtype=torch.float32, device=dev)   # zero-filled by the library
         with on_device(dev):
-            if use_segmented_grad(b, n, c) and ctx.plan is not None:   # idx was inverted where it was born (index_plan.py)
-                _C.check(_C.lib().pn2_group_point_grad_planned(b, n, c, m, ns, ptr(grad_out), ptr(ctx.plan.buffer), ptr(grad_points),
-                                                               1 if is_deterministic() else 0, stream_ptr(dev)),
-                         "group_point_grad")
-            elif use_segmented_grad(b, n, c):
-                ws = seg_workspace(_C.lib(), b, n, m * ns, dev)
-                _C.check(_C.lib().pn2_group_point_grad_seg(b, n, c, m, ns, ptr(grad_out), ptr(idx), ptr(grad_points),
-                                                           ptr(ws), 1 if is_deterministic() else 0, stream_ptr(dev)),
-                         "group_point_grad")
-            elif is_deterministic():
-                ws = det_workspace(_C.lib(), b, n, c, dev)
-                _C.check(_C.lib().pn2_group_point_grad_det(b, n, c, m, ns, ptr(grad_out), ptr(idx), ptr(grad_points),
-                                                           ptr(ws), stream_ptr(dev)), "group_point_grad")
-            else:
-                _C.check(_C.lib().pn2_group_point_grad(b, n, c, m, ns, ptr(grad_out), ptr(idx), ptr(grad_points),
-                                                       stream_ptr(dev)), "group_point_grad")
+            _C.check(scatter_grad(_C.lib(), "group_point", (b, n, c, m, ns, ptr(grad_out)), idx, ctx.plan, (ptr(grad_points),),
+                                  b, n, c, m * ns, dev), "group_point_grad")
         return grad_points, None, None
 
 

@@ -10,8 +10,8 @@ gradient w.r.t. `points` only (tf_interpolate.py:29-34); ThreeNN is NoGradient (
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, use_segmented_grad, det_workspace, f32, i32, is_deterministic, lengths_for, on_device, ptr,
-                       ragged_lengths, require, same_device, seg_workspace, stream_ptr)
+from ._tensors import (out_or_empty, f32, i32, is_deterministic, lengths_for, on_device, ptr, ragged_lengths, require, same_device,
+                       scatter_grad, seg_workspace, stream_ptr)
 
 
 def three_nn(xyz1, xyz2, out=None, lengths1=None):
@@ -76,25 +76,8 @@ class _ThreeInterpolate(torch.autograd.Function):
         dev = grad_out.device
         grad_points = torch.empty((b, m, c), dtype=torch.float32, device=dev)   # zero-filled by the library
         with on_device(dev):
-            if use_segmented_grad(b, m, c) and ctx.plan is not None:   # idx was inverted where it was born (index_plan.py)
-                _C.check(_C.lib().pn2_three_interpolate_grad_planned(b, n, c, m, ptr(grad_out), ptr(ctx.plan.buffer), ptr(weight),
-                                                                     ptr(grad_points), 1 if is_deterministic() else 0,
-                                                                     stream_ptr(dev)), "three_interpolate_grad")
-            elif use_segmented_grad(b, m, c):
-                ws = seg_workspace(_C.lib(), b, m, 3 * n, dev)
-                _C.check(_C.lib().pn2_three_interpolate_grad_seg(b, n, c, m, ptr(grad_out), ptr(idx), ptr(weight),
-                                                                 ptr(grad_points), ptr(ws),
-                                                                 1 if is_deterministic() else 0, stream_ptr(dev)),
-                         "three_interpolate_grad")
-            elif is_deterministic():
-                ws = det_workspace(_C.lib(), b, m, c, dev)
-                _C.check(_C.lib().pn2_three_interpolate_grad_det(b, n, c, m, ptr(grad_out), ptr(idx), ptr(weight),
-                                                                 ptr(grad_points), ptr(ws), stream_ptr(dev)),
-                         "three_interpolate_grad")
-            else:
-                _C.check(_C.lib().pn2_three_interpolate_grad(b, n, c, m, ptr(grad_out), ptr(idx), ptr(weight),
-                                                             ptr(grad_points), stream_ptr(dev)),
-                         "three_interpolate_grad")
+            _C.check(scatter_grad(_C.lib(), "three_interpolate", (b, n, c, m, ptr(grad_out)), idx, ctx.plan,
+                                  (ptr(weight), ptr(grad_points)), b, m, c, 3 * n, dev), "three_interpolate_grad")
         return grad_points, None, None, None
 
 

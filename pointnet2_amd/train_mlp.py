@@ -16,8 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _C
-from ._tensors import (det_workspace, f32, i32, is_deterministic, on_device, ptr, require, same_device, seg_workspace,
-                       stream_ptr, use_segmented_grad)
+from ._tensors import f32, i32, is_deterministic, on_device, ptr, require, same_device, scatter_grad, stream_ptr
 
 _vp, _i, _ll, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 
@@ -350,6 +349,70 @@ def _batch_stat_results(grads, direct, biases, widths, dev):
     return result
 
 
+def _frozen_stat_grads(pairs, weights, biases, gammas, betas, widths, needs, dev):
+    """Frozen statistics: per layer the (weight, gamma, beta) gradients the kernels write and the conv bias gradient (real
+    under frozen statistics) -> grads, direct, gbias. needs[l]: which of the layer's (weight, bias, gamma, beta) want a gradient.
+    NULL slots for a layer none of whose parameters wants one: the library then runs no weight-gradient pass for it. Otherwise
+    the three tensors the kernels write are all given (scratch for an unwanted one)."""
+    grads, direct, gbias = [], [], [None] * len(pairs)
+    small, soff = None, 0                  # ONE buffer for the per-channel gradients (gamma, beta, bias) of every layer
+    for l, (conv, bn) in enumerate(pairs):
+        need = needs[l]
+        if not any(need):
+            direct.append(False)
+            grads.append((None, None, None))
+            continue
+        srcs = ((conv.weight, weights[l]), (conv.bias, biases[l]), (bn.weight, gammas[l]), (bn.bias, betas[l]))
+        slots = [_grad_slot(p, like) if (_ACCUMULATE[0] and nd) else None for (p, like), nd in zip(srcs, need)]
+        d = _ACCUMULATE[0] and all(s is not None for s, nd in zip(slots, need) if nd)     # direct: every WANTED slot exists
+        direct.append(d)
+        if small is None:                  # (a level is bound by the host's enqueue rate: one allocation, not three per layer)
+            small = torch.empty((3 * sum(widths[1:]),), dtype=torch.float32, device=dev)
+        w = widths[l + 1]
+        vec = [small[soff + k * w:soff + (k + 1) * w] for k in range(3)]
+        soff += 3 * w
+        # (a direct layer's UNWANTED slot is scratch the kernels add into and nobody reads: never returned)
+        grads.append((slots[0] if (d and need[0]) else torch.empty_like(weights[l]),
+                      slots[2] if (d and need[2]) else vec[0], slots[3] if (d and need[3]) else vec[1]))
+        if need[1]:
+            gbias[l] = slots[1] if d else vec[2]
+    return grads, direct, gbias
+
+
+def _frozen_stat_results(grads, direct, gbias, needs):
+    """... and what the node returns for them, four per layer: only what was wanted, nothing for a direct layer."""
+    result = []
+    for l, nd in enumerate(needs):
+        if direct[l] or not any(nd):
+            result += [None, None, None, None]
+        else:
+            result += [grads[l][0] if nd[0] else None, gbias[l], grads[l][1] if nd[2] else None, grads[l][2] if nd[3] else None]
+    return result
+
+
+def _save_layers(ctx, head, weights, biases, gammas, betas, zs, saves, out, tail=()):
+    """save_for_backward of a training node: its own leading tensors, then per layer the weights, the biases and pre-norm tensors
+    that exist, gammas, betas and statistics, the output, its own trailing tensors. _saved_layers is the inverse."""
+    ctx.nhead = len(head)
+    ctx.nbias = [b is not None for b in biases]
+    ctx.nz = [z is not None for z in zs]
+    ctx.save_for_backward(*head, *weights, *[b for b in biases if b is not None], *gammas, *betas, *[z for z in zs if z is not None],
+                          *saves, out, *tail)
+
+
+def _saved_layers(ctx, n):
+    """-> head, weights, biases, gammas, betas, zs, saves, out, tail as _save_layers was given them (None where nothing was)."""
+    sv = list(ctx.saved_tensors)
+    head = [sv.pop(0) for _ in range(ctx.nhead)]
+    weights = [sv.pop(0) for _ in range(n)]
+    biases = [sv.pop(0) if has else None for has in ctx.nbias]
+    gammas = [sv.pop(0) for _ in range(n)]
+    betas = [sv.pop(0) for _ in range(n)]
+    zs = [sv.pop(0) if has else None for has in ctx.nz]
+    saves = [sv.pop(0) for _ in range(n)]
+    return head, weights, biases, gammas, betas, zs, saves, sv.pop(0), sv
+
+
 class _TrainMLP(torch.autograd.Function):
     """inputs: level, x (points (b,n,c) when grouped -- may be None -- else the (rows, cin) input), xyz and new_xyz (the
     level's own tensors when their gradients are wanted, level.xyz_grad; else None: the coordinates are constants of the node),
@@ -387,88 +450,48 @@ class _TrainMLP(torch.autograd.Function):
         arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
         grp = _group_struct(level, x) if level.grouped else None
         ws = _level_workspace(level, widths, code, 0, dev, _group_dims(level, x), opts)
-        if level.frozen:
-            # running statistics (bn.eval()): read, never written -- no counter either (pn2_mlp_train_forward_frozen)
-            with on_device(dev):
-                _C.check(_C.lib().pn2_mlp_train_forward_frozen(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
-                                                               None if level.grouped else ptr(x), level.pool_rows, code, ptr(out),
+        gptr, xptr = (ctypes.byref(grp), None) if level.grouped else (None, ptr(x))
+        with on_device(dev):
+            if level.frozen:        # running statistics (bn.eval()): read, never written -- no counter either
+                _C.check(_C.lib().pn2_mlp_train_forward_frozen(rows, n, arr, gptr, xptr, level.pool_rows, code, ptr(out),
                                                                ptr(argsel) if code in (0, 3) else None, ptr(zsel), ptr(pool_w),
                                                                ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward_frozen")
-        elif code:
-            with on_device(dev):
-                _C.check(_C.lib().pn2_mlp_train_forward_pool(rows, n, arr, ctypes.byref(grp), level.pool_rows, code, ptr(out),
+            elif code:              # avg / weighted_avg / max_and_avg (grouped levels only)
+                _C.check(_C.lib().pn2_mlp_train_forward_pool(rows, n, arr, gptr, level.pool_rows, code, ptr(out),
                                                              ptr(argsel) if code == 3 else None, ptr(zsel), ptr(pool_w), ptr(ws),
                                                              opts, stream_ptr(dev)), "mlp_train_forward_pool")
-        else:
-            with on_device(dev):
-                _C.check(_C.lib().pn2_mlp_train_forward_ex(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
-                                                           None if level.grouped else ptr(x), level.pool_rows, ptr(out), ptr(argsel),
+            else:
+                _C.check(_C.lib().pn2_mlp_train_forward_ex(rows, n, arr, gptr, xptr, level.pool_rows, ptr(out), ptr(argsel),
                                                            ptr(zsel), ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward")
         if not level.frozen:
             _count_batch(level.pairs)
         ctx.level, ctx.widths, ctx.code = level, widths, code
         ctx.opts = dict(_OPTS)                              # backward must see the organisation forward ran under
-        ctx.has_x = x is not None
-        ctx.nbias = [b is not None for b in biases]
-        ctx.nz = [z is not None for z in zs]
-        saved = [t for t in [x] if t is not None] + weights + [b for b in biases if b is not None] + gammas + betas + \
-            [z for z in zs if z is not None] + saves + [out]
-        if level.pool_rows:
-            saved += [argsel] + [t for t in (zsel, pool_w) if t is not None]
-            ctx.mark_non_differentiable(argsel)
-        ctx.save_for_backward(*saved)
-        if level.pool_rows:
-            return out, argsel
-        return out
+        if not level.pool_rows:
+            _save_layers(ctx, [x], weights, biases, gammas, betas, zs, saves, out)
+            return out
+        ctx.mark_non_differentiable(argsel)
+        _save_layers(ctx, [x] if x is not None else [], weights, biases, gammas, betas, zs, saves, out,
+                     [argsel] + [t for t in (zsel, pool_w) if t is not None])
+        return out, argsel
 
     @staticmethod
     def backward(ctx, grad_out, *unused):
         level, widths = ctx.level, ctx.widths
         n = len(level.pairs)
-        sv = list(ctx.saved_tensors)
-        x = sv.pop(0) if ctx.has_x else None
-        weights = [sv.pop(0) for _ in range(n)]
-        biases = [sv.pop(0) if has else None for has in ctx.nbias]
-        gammas = [sv.pop(0) for _ in range(n)]
-        betas = [sv.pop(0) for _ in range(n)]
-        zs = [sv.pop(0) if has else None for has in ctx.nz]
-        saves = [sv.pop(0) for _ in range(n)]
-        out = sv.pop(0)
+        head, weights, biases, gammas, betas, zs, saves, out, tail = _saved_layers(ctx, n)
+        x = head[0] if head else None
         code = ctx.code
-        argsel = sv.pop(0) if level.pool_rows else None
-        zsel = sv.pop(0) if level.pool_rows and code in (0, 3) else None
-        pool_w = sv.pop(0) if code == 2 else None
+        argsel = tail.pop(0) if level.pool_rows else None
+        zsel = tail.pop(0) if level.pool_rows and code in (0, 3) else None
+        pool_w = tail.pop(0) if code == 2 else None
         dev = out.device
         rows = level.rows
         grad_out = f32(grad_out, "grad_out")
         frozen = level.frozen
-        needs, gbias = [], [None] * n          # frozen: which of (weight, bias, gamma, beta) want a gradient; the bias gradients
         if frozen:
-            grads, direct = [], []
-            small, soff = None, 0              # ONE buffer for the per-channel gradients (gamma, beta, bias) of every layer
-            for l, (conv, bn) in enumerate(level.pairs):
-                # NULL slots for a layer none of whose parameters wants a gradient: the library then runs no weight-gradient
-                # pass for it. Otherwise the three tensors the kernels write are all given (scratch for an unwanted one).
-                need = [bool(ctx.needs_input_grad[4 + 4 * l + k]) for k in range(4)]
-                needs.append(need)
-                if not any(need):
-                    direct.append(False)
-                    grads.append((None, None, None))
-                    continue
-                srcs = ((conv.weight, weights[l]), (conv.bias, biases[l]), (bn.weight, gammas[l]), (bn.bias, betas[l]))
-                slots = [_grad_slot(p, like) if (_ACCUMULATE[0] and nd) else None for (p, like), nd in zip(srcs, need)]
-                d = _ACCUMULATE[0] and all(s is not None for s, nd in zip(slots, need) if nd)     # direct: every WANTED slot exists
-                direct.append(d)
-                if small is None:              # (a level is bound by the host's enqueue rate: one allocation, not three per layer)
-                    small = torch.empty((3 * sum(widths[1:]),), dtype=torch.float32, device=dev)
-                w = widths[l + 1]
-                vec = [small[soff + k * w:soff + (k + 1) * w] for k in range(3)]
-                soff += 3 * w
-                # (a direct layer's UNWANTED slot is scratch the kernels add into and nobody reads: never returned)
-                grads.append((slots[0] if (d and need[0]) else torch.empty_like(weights[l]),
-                              slots[2] if (d and need[2]) else vec[0], slots[3] if (d and need[3]) else vec[1]))
-                if need[1]:
-                    gbias[l] = slots[1] if d else vec[2]
+            needs = [[bool(ctx.needs_input_grad[4 + 4 * l + k]) for k in range(4)] for l in range(n)]
+            grads, direct, gbias = _frozen_stat_grads(level.pairs, weights, biases, gammas, betas, widths, needs, dev)
         else:
             grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
         need_x = ctx.needs_input_grad[1] and x is not None
@@ -529,40 +552,20 @@ class _TrainMLP(torch.autograd.Function):
             if grad_pts is not None:
                 grad_x = grad_pts
             if grad_rows is not None:
-                # the grouped feature rows' gradient back onto the points: the segmented scatter of group_point's backward
+                # the grouped feature rows' gradient back onto the points: group_point's backward (_tensors.scatter_grad)
                 b, npts, c = x.shape
                 m, ns = level.m, level.nsample
-                grad_x = torch.empty((b, npts, c), dtype=torch.float32, device=dev)
                 if level.idx is None:                      # group_all: row k of cloud i IS point k
                     grad_x = grad_rows.view(b, npts, c)
-                elif use_segmented_grad(b, npts, c) and level.plan is not None:
-                    _C.check(_C.lib().pn2_group_point_grad_planned(b, npts, c, m, ns, ptr(grad_rows), ptr(level.plan.buffer),
-                                                                   ptr(grad_x), 1 if is_deterministic() else 0, stream_ptr(dev)),
-                             "group_point_grad")
-                elif use_segmented_grad(b, npts, c):
-                    sws = seg_workspace(_C.lib(), b, npts, m * ns, dev)
-                    _C.check(_C.lib().pn2_group_point_grad_seg(b, npts, c, m, ns, ptr(grad_rows), ptr(level.idx), ptr(grad_x),
-                                                               ptr(sws), 1 if is_deterministic() else 0, stream_ptr(dev)),
-                             "group_point_grad")
-                elif is_deterministic():                   # few channels on a small batch: the fixed-point scatter, as group_point's backward
-                    dws = det_workspace(_C.lib(), b, npts, c, dev)
-                    _C.check(_C.lib().pn2_group_point_grad_det(b, npts, c, m, ns, ptr(grad_rows), ptr(level.idx), ptr(grad_x),
-                                                               ptr(dws), stream_ptr(dev)), "group_point_grad")
                 else:
-                    _C.check(_C.lib().pn2_group_point_grad(b, npts, c, m, ns, ptr(grad_rows), ptr(level.idx), ptr(grad_x),
-                                                           stream_ptr(dev)), "group_point_grad")
+                    grad_x = torch.empty((b, npts, c), dtype=torch.float32, device=dev)
+                    _C.check(scatter_grad(_C.lib(), "group_point", (b, npts, c, m, ns, ptr(grad_rows)), level.idx, level.plan,
+                                          (ptr(grad_x),), b, npts, c, m * ns, dev), "group_point_grad")
         result = [None, grad_x if need_x else None, grad_xyz if ctx.needs_input_grad[2] else None,
                   grad_new_xyz if ctx.needs_input_grad[3] else None]
-        if not frozen:
-            return tuple(result + _batch_stat_results(grads, direct, biases, widths, dev))
-        for l in range(n):                                     # the conv bias takes a real gradient under frozen statistics
-            if direct[l] or not any(needs[l]):
-                result += [None, None, None, None]
-            else:
-                nd = needs[l]
-                result += [grads[l][0] if nd[0] else None, gbias[l], grads[l][1] if nd[2] else None,
-                           grads[l][2] if nd[3] else None]
-        return tuple(result)
+        if frozen:                                             # (the conv bias takes a real gradient under frozen statistics)
+            return tuple(result + _frozen_stat_results(grads, direct, gbias, needs))
+        return tuple(result + _batch_stat_results(grads, direct, biases, widths, dev))
 
 
 def _params(pairs):
@@ -756,28 +759,17 @@ class _TrainFP(torch.autograd.Function):
         _count_batch(level.pairs)
         ctx.level, ctx.widths = level, widths
         ctx.opts = dict(_OPTS)
-        ctx.has_p1 = points1 is not None
-        ctx.nbias = [b is not None for b in biases]
         ctx.mark_non_differentiable(weight)
-        ctx.save_for_backward(*([points2] + ([points1] if points1 is not None else []) + [weight] + weights +
-                                [b for b in biases if b is not None] + gammas + betas + zs + saves + [out]))
+        _save_layers(ctx, [points2] + ([points1] if points1 is not None else []) + [weight], weights, biases, gammas, betas, zs,
+                     saves, out)
         return out, weight
 
     @staticmethod
     def backward(ctx, grad_out, _unused):
         level, widths = ctx.level, ctx.widths
         n = len(level.pairs)
-        sv = list(ctx.saved_tensors)
-        points2 = sv.pop(0)
-        points1 = sv.pop(0) if ctx.has_p1 else None
-        weight = sv.pop(0)
-        weights = [sv.pop(0) for _ in range(n)]
-        biases = [sv.pop(0) if has else None for has in ctx.nbias]
-        gammas = [sv.pop(0) for _ in range(n)]
-        betas = [sv.pop(0) for _ in range(n)]
-        zs = [sv.pop(0) for _ in range(n)]
-        saves = [sv.pop(0) for _ in range(n)]
-        out = sv.pop(0)
+        head, weights, biases, gammas, betas, zs, saves, out, _ = _saved_layers(ctx, n)
+        points2, points1, weight = head[0], (head[1] if len(head) == 3 else None), head[-1]
         dev = out.device
         grad_out = f32(grad_out, "grad_out")
         grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
