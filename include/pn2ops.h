@@ -698,6 +698,38 @@ int pn2_mlp_train_backward_frozen(long long rows, int nlayers, const pn2_bn_laye
                                   float *grad_feat_rows, float *grad_points, float *grad_xyz, float *grad_new_xyz,
                                   float *const *grad_bias, int reproducible, void *ws, const pn2_train_opts *opts, void *stream);
 
+/* The training node on the plain rows of a RAGGED batch (csrc/train_mlp_ragged.hip): b clouds padded to n rows each, x and out
+ * (b n, C) as in pn2_mlp_train_forward_ex / _backward_ex with group == NULL and pool_rows == 0, and lengths (b) i32 ON THE
+ * DEVICE: row c n + i is VALID iff i < clamp(lengths[c], 1, n) (the clamp of the ragged operators above). The batch moments,
+ * the running statistics and every gradient are those of the valid rows alone -- what the dense entries compute on the
+ * compacted rows. A padding row of x and of grad_out may hold anything, NaN and Inf included: it is never used (selects, not
+ * products); out and grad_x are exactly zero (all-zero bits) there, and so is layers[l].z. The host never reads lengths: the
+ * calls are stream-ordered, make no host synchronisation and no memset, and can be captured in a graph whose replays see
+ * whatever lengths holds then. The row count of the statistics is N_valid = sum of the clamped lengths; the unbiased running
+ * variance takes N_valid / max(N_valid - 1, 1). A batch with fewer than 2 valid rows has no variance to speak of (the batch
+ * variance is 0, every output is relu(beta)): that is the caller's business, as it is with a dense batch of one row.
+ * mask: the caller's buffer of 16 + 4 (b n / 32) bytes, 8-byte aligned, that FORWARD writes (N_valid as a double, then one
+ * 32-bit validity word per 32 rows -- a word may hold the tail of one cloud, its padding and the head of the next) and
+ * BACKWARD reads: keep it with layers[l].z and save between the two calls. backward takes lengths for symmetry and does not
+ * read it.
+ * Organisation: the masked passes run one fixed organisation (a data-gradient GEMM and a weight-gradient pass per layer, the
+ * finalisations as launches of their own); the pn2_train_opts fields fuse_wgrad, pair_launch, side_stream and fold_finalize
+ * are IGNORED, and those that apply to grouped or pooled levels have nothing to act on; the others (force_stream, max_ns, nt,
+ * wgrad_two_per_cu) act as in the dense entries. grad_accumulate and running_var_biased likewise. Results are reproducible
+ * run to run (fixed summation orders), and with every length equal to n they are the dense entries' results bit for bit
+ * (fold_finalize aside, whose sums take another fixed order).
+ * _supported: 1 where b n is a positive multiple of 32 below 2^31 and the dense plain-rows node takes the widths (cin_1 and
+ * every cout a multiple of 4, 1..8 layers); _ws_bytes_ragged: -1 where it is 0. Before anything is launched: PN2_E_NULL
+ * for a NULL lengths or mask (and the dense entries' NULL checks), PN2_E_ARG for b n not a positive multiple of 32 (and the
+ * dense entries' argument checks). */
+int pn2_mlp_train_ragged_supported(int b, int n, int nlayers, const int *widths);
+long long pn2_mlp_train_ws_bytes_ragged(int b, int n, int nlayers, const int *widths, int backward, const pn2_train_opts *opts);
+int pn2_mlp_train_forward_ragged(int b, int n, const int *lengths, int nlayers, const pn2_bn_layer *layers, const float *x,
+                                 float *out, void *mask, void *ws, const pn2_train_opts *opts, void *stream);
+int pn2_mlp_train_backward_ragged(int b, int n, const int *lengths, int nlayers, const pn2_bn_layer *layers, const float *x,
+                                  const float *out, const float *grad_out, float *grad_x, const void *mask, void *ws,
+                                  const pn2_train_opts *opts, void *stream);
+
 /* The input rows of a feature-propagation level's layer stack in ONE launch (pointnet_fp_module, utils/pointnet_util.py:211-219):
  * inverse-distance weights from three_nn's `dist`, three_interpolate of points2 (b,m,c2), concatenation with the skip features
  * points1 (b,n,c1; NULL with c1 = 0), zero columns up to `pitch` (a multiple of 4 >= c2 + c1: the training entry points read

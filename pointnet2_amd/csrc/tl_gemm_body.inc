@@ -2,7 +2,10 @@
 // the kernel that runs it, with the names in scope that it uses: NS, AMODE (compile-time), `p` (the kernel's TlGemm argument
 // itself or a reference to it), PN2_BX / PN2_BY / PN2_GX (the workgroup's position in its (gx, slabs) grid and gx), PN2_STATS
 // (compile-time bool: false = the "no statistics" variant of the frozen-statistics node, train_mlp_frozen.hip -- no per-tile
-// sums, no sd1 / sd2 registers, no LDS reduction, no partial row; p.stats is not looked at).
+// sums, no sd1 / sd2 registers, no LDS reduction, no partial row; p.stats is not looked at), PN2_MASKED (compile-time bool: true =
+// the rows of a ragged batch, train_mlp_ragged.hip -- the lane's row of the A operand is taken as ZERO where its bit of the
+// item's validity word p.mask[item] is clear, a select behind the prologue: whatever the row holds, NaN included, never enters
+// a product; a zero row gives a zero output row, adds nothing to the sums and fails E_MASK's test. false: p.mask is not looked at).
 // Text, not a function: as an inlined function taking the argument struct by reference the stand-alone kernels compiled
 // differently -- the struct's fields became values live from the kernel's start instead of scalar loads at their uses, and
 // the weight-gradient kernels that carry the data gradient went 100-400 bytes per lane deeper into scratch.
@@ -74,7 +77,7 @@
     // the MFMAs in two register slots: these passes move 0.5-1 KB per MFMA, so what they need is bytes in flight
     // (8 KB per wave, 64 KB per CU). Gathered rows (layer 1 of an SA level) take two steps: the point index is fetched
     // when the slot is assigned, the coordinates / features it points to one step later, so neither wait is exposed.
-    struct Slot { ARaw raw; RowCtx rc; long long round, row0, row; int u; bool active, valid, pending; };
+    struct Slot { ARaw raw; RowCtx rc; long long round, row0, row; int u; bool active, valid, pending; unsigned mw; };
     auto assign = [&](Slot &sl, long long round, int u) {
         sl.round = round; sl.u = u; sl.valid = round < rounds;
         const long long item = round * kTlWaves + wave;
@@ -82,6 +85,7 @@
         sl.active = sl.valid && item < items;
         sl.rc = tl_row_ctx<AMODE>(p, sl.row, sl.active);
         sl.pending = sl.valid;
+        if (PN2_MASKED) sl.mw = p.mask[sl.active ? item : 0];     // wave-uniform: a scalar load, beside the vector loads in flight
     };
     auto fetch = [&](Slot &sl) {
         if (sl.pending) tl_load_raw<AMODE>(p, sl.row0, sl.row, sl.rc, sl.u, hl, sl.active, sl.raw);
@@ -126,7 +130,13 @@
 #pragma unroll
                 for (int v = 0; v < 16; ++v) acc[t][v] = 0.0f;
         }
-        const ActSplit sp = split_act(tl_finish<AMODE>(sl.raw, sl.rc, sl.u, p.tk0, hl, lp0, lp1, lp2));
+        f32x16 xa = tl_finish<AMODE>(sl.raw, sl.rc, sl.u, p.tk0, hl, lp0, lp1, lp2);
+        if (PN2_MASKED) {                                          // a padding row is absent: h = 0 / dz = 0, by a select
+            const bool rv = (sl.mw >> s) & 1u;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) xa[v] = rv ? xa[v] : 0.0f;
+        }
+        const ActSplit sp = split_act(xa);
         const bool last = sl.u + 1 == p.tk;
         const long long erow0 = sl.row0, eitem = sl.round * kTlWaves + wave;
         const bool eactive = sl.active;

@@ -1,6 +1,22 @@
 // Body of the weight-gradient pass (train_mlp_wgrad.hip: tl_wgrad_kernel, and the weight-gradient range of train_mlp_pair.hip's tl_pair_kernel).
 // Included as TEXT (see tl_gemm_body.inc) with TPW, UPW, GATHER, DCLS, DY, L1X (compile-time), `p` (the TlWgrad argument) and
-// PN2_BX / PN2_BY / PN2_GX in scope.
+// PN2_BX / PN2_BY / PN2_GX in scope, and PN2_MASKED (compile-time bool: true = the rows of a ragged batch, train_mlp_ragged.hip:
+// the validity word p.mask[block] travels two blocks ahead like the unit loads -- a scalar load, so the vector loads keep their
+// one instruction sequence -- and wg_store_unit<.., true> zeroes the padding rows of both operands; false: p.mask is not looked at).
+// The masked text is taken in and out by the PREPROCESSOR (PN2_MW_*), not by an `if` on a constant: with the word as one more
+// reference parameter of the lambdas below, two of tl_pair_kernel's dense instantiations went 16-20 bytes per lane deeper into
+// scratch, although nothing read it.
+#if PN2_MASKED
+#define PN2_MW_PARAM , unsigned &mw
+#define PN2_MW_ARG(X) , X
+#define PN2_MW_LOAD(INB, B) mw = p.mask[(INB) ? (B) : 0];
+#define PN2_MW_STORE(I) wg_store_unit<DCLS, true>(un[I], r[I], lane, img, zr, zpitch, imgA, p.tus, mw)
+#else
+#define PN2_MW_PARAM
+#define PN2_MW_ARG(X)
+#define PN2_MW_LOAD(INB, B)
+#define PN2_MW_STORE(I) wg_store_unit<DCLS>(un[I], r[I], lane, img, zr, zpitch, imgA, p.tus)
+#endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // uniform: scalar branches
     const int us = PN2_BY / p.tslabs, ts = PN2_BY % p.tslabs;
@@ -15,6 +31,9 @@
 #pragma unroll
         for (int v = 0; v < 16; ++v) acc[i][v] = 0.0f;
     WgRaw ra[UPW], rb[UPW];
+#if PN2_MASKED
+    unsigned mwa = 0u, mwb = 0u;
+#endif
     WgUnit un[UPW];
     // (measured: taking the unit loads away from the waves that produce the data gradient -- the block's critical path --
     // made the pass slower, 286 -> 306 us at the metric shape: the other waves' second unit costs more than it frees)
@@ -73,8 +92,9 @@
         const int nz = (p.single ? 1 : 2) * 32 * zpitch;
         for (int i = threadIdx.x; i < nz; i += kTlThreads) zr0[i] = 0.0f;
     }
-    auto load = [&](long long b, WgRaw (&r)[UPW]) __attribute__((always_inline)) {   // the same instruction sequence for every wave and block
+    auto load = [&](long long b, WgRaw (&r)[UPW] PN2_MW_PARAM) __attribute__((always_inline)) {   // the same instruction sequence for every wave and block
         const bool inb = b < blocks;
+        PN2_MW_LOAD(inb, b)
         const long long row0 = (inb ? b : 0) * 32;
         const int grp_u = (int)((unsigned)row0 / (unsigned)grows), off_u = (int)row0 - grp_u * grows;
 #pragma unroll
@@ -110,11 +130,11 @@
         const rsrc_t rx = make_rsrc(inb ? p.l1x + (size_t)b * 32 : nullptr, inb ? 512u : 0u);
         return bload4(rx, (lane & 31) * 16, 0);
     };
-    auto block = [&](long long b, WgRaw (&r)[UPW], u32x4 *img, float *zr, u32x4 *imgA, float4 *xr, float4 &xp, auto role) __attribute__((always_inline)) {
+    auto block = [&](long long b, WgRaw (&r)[UPW] PN2_MW_PARAM, u32x4 *img, float *zr, u32x4 *imgA, float4 *xr, float4 &xp, auto role) __attribute__((always_inline)) {
         constexpr bool ROLE = decltype(role)::value;
         PN2_TICK(5)
 #pragma unroll
-        for (int i = 0; i < UPW; ++i) wg_store_unit<DCLS>(un[i], r[i], lane, img, zr, zpitch, imgA, p.tus);
+        for (int i = 0; i < UPW; ++i) PN2_MW_STORE(i);
         if (L1X && ROLE && dyt == 0 && lane < 32) xr[lane] = xp;
         PN2_TICK(0)
         __syncthreads();
@@ -122,7 +142,7 @@
         const int hl = lane >> 5, col = dyt * 32 + (lane & 31);
         const int voff = (ROLE && col < p.dy_cols) ? (4 * hl * p.dy_pitch + col) * 4 : kWgOob;
         const int rstep = uni(p.dy_pitch * 4);
-        load(b + 2 * step, r);
+        load(b + 2 * step, r PN2_MW_ARG(mw));
         if (L1X && ROLE && dyt == 0) xp = xload(b + 2 * step);
         tiles_of_wave(img);
         PN2_TICK(2)
@@ -229,13 +249,13 @@
         }
     }
     long long blk = PN2_BX;
-    load(blk, ra);
-    load(blk + step, rb);
+    load(blk, ra PN2_MW_ARG(mwa));
+    load(blk + step, rb PN2_MW_ARG(mwb));
     if (L1X && DY && dyt == 0) { xpa = xload(blk); xpb = xload(blk + step); }
     auto run = [&](auto role) __attribute__((always_inline)) {
         for (; blk < blocks; blk += 2 * step) {
-            block(blk, ra, img0, zr0, ia0, xr0, xpa, role);
-            if (blk + step < blocks) block(blk + step, rb, img1, zr1, ia1, xr1, xpb, role);      // uniform over the workgroup
+            block(blk, ra PN2_MW_ARG(mwa), img0, zr0, ia0, xr0, xpa, role);
+            if (blk + step < blocks) block(blk + step, rb PN2_MW_ARG(mwb), img1, zr1, ia1, xr1, xpb, role);      // uniform over the workgroup
         }
     };
     if (DY && dyt >= 0) run(std::true_type{}); else run(std::false_type{});
@@ -274,3 +294,7 @@
             }
         }
     }
+#undef PN2_MW_PARAM
+#undef PN2_MW_ARG
+#undef PN2_MW_LOAD
+#undef PN2_MW_STORE

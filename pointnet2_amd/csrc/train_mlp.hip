@@ -55,6 +55,15 @@ static inline Opts opts_of(const pn2_train_opts *o)
     memset(&d, 0, sizeof(d));
     return o ? *o : d;
 }
+// The rows of a ragged batch (TlCall::mask, train_mlp_ragged.hip) run ONE organisation: a data-gradient GEMM and a weight-gradient
+// pass per layer, every finalisation a launch of its own -- the masked kernels exist for those passes only. The other fields
+// keep the caller's values.
+static inline Opts ragged_opts(const pn2_train_opts *o)
+{
+    Opts d = opts_of(o);
+    d.fuse_wgrad = PN2_OPT_OFF; d.pair_launch = PN2_OPT_OFF; d.side_stream = PN2_OPT_OFF; d.fold_finalize = PN2_OPT_OFF;
+    return d;
+}
 static inline int pick_ns(int tn, const Opts &o)
 {
     const int cap = (o.max_ns == 1 || o.max_ns == 2) ? o.max_ns : 4;      // results never depend on it
@@ -664,7 +673,7 @@ struct TlRun {
     bool fold = false;               // a layer's per-channel finalisation inside the pass that sums for it (TlFin)
 
     explicit TlRun(const TlCall &call)
-        : c(tl_pool_buffers(call)), o(opts_of(call.opts)), fp(c.has_fp ? &c.fp : nullptr), base(static_cast<char *>(call.ws)),
+        : c(tl_pool_buffers(call)), o(call.mask ? ragged_opts(call.opts) : opts_of(call.opts)), fp(c.has_fp ? &c.fp : nullptr), base(static_cast<char *>(call.ws)),
           st(as_stream(call.stream)) {}
     TlRun(const TlRun &) = delete;
     TlRun &operator=(const TlRun &) = delete;
@@ -673,12 +682,14 @@ struct TlRun {
     unsigned *tickets() const { return at<unsigned>(pl.tickets); }
     double *stats(int l) const { return at<double>(pl.stats[l]); }
     bool want_max() const { return c.pooling == 0 || c.pooling == 3; }
+    const unsigned *mask_words() const { return c.mask ? ragged_words(c.mask) : nullptr; }     // ragged rows, or nullptr
 
     // the checks both directions make first, in this order
     int check_inputs()
     {
         if (!layers_ok(c.rows, c.nlayers, c.layers, c.group, widths, fp)) return PN2_E_ARG;
         if (c.frozen && fp) return PN2_E_ARG;                     // (the FP node with layer 1 per known point has no frozen form)
+        if (c.mask && (c.group || fp || c.frozen || c.pool_rows)) return PN2_E_ARG;      // (the row mask: plain rows, batch statistics)
         return PN2_OK;
     }
     bool pool_buffers_missing(int pool_rows) const
@@ -753,6 +764,9 @@ struct Fwd : TlRun {
     {
         if (c.frozen) return PN2_OK;
         const pn2_bn_layer &L = c.layers[l];
+        if (c.mask)                                               // ragged rows: the count is the number of valid rows, on the device
+            return launch_bn_finalize_counted(stats(l), np, L.cout, ragged_count(c.mask), L.gamma, L.beta, L.running_mean, L.running_var,
+                                              L.momentum, L.eps, L.save, L.bias, L.running_var_biased, st);
         return launch_bn_finalize(stats(l), np, L.cout, (double)c.rows, L.gamma, L.beta, L.running_mean, L.running_var, L.momentum, L.eps,
                                   L.save, L.bias, L.running_var_biased, st);
     }
@@ -760,6 +774,7 @@ struct Fwd : TlRun {
     // an unpooled top layer: out = relu(a z_L + c)
     int apply(const pn2_bn_layer &L) const
     {
+        if (c.mask) return launch_apply_masked(c.rows * L.cout / 4, L.cout, L.z, L.save, mask_words(), out(), st);
         return launch_apply(c.rows * L.cout / 4, L.cout, L.z, L.save, out(), st);
     }
 
@@ -827,6 +842,7 @@ struct Fwd : TlRun {
         p.out = (last && !keep_top) ? nullptr : L.z;              // the pooled top layer of a large level is never written
         p.stats = moments(l);
         p.nostats = c.frozen ? 1 : 0;                             // the GEMM's compile-time "no statistics" variant
+        p.mask = mask_words();
         if (p.emode == E_POOL) {
             const long long parts = rows / (pool_rows == 16 ? 16 : 32);
             float *pp = at<float>(pl.pool);
@@ -863,6 +879,7 @@ struct Fwd : TlRun {
     {
         if (int rc = check_inputs()) return rc;
         if ((!c.group && !c.x && !fp) || !c.out || !c.ws || pool_buffers_missing(c.pool_rows)) return PN2_E_NULL;
+        if (c.mask && !c.lengths) return PN2_E_NULL;
         if (c.pool_rows && (c.rows % c.pool_rows || (c.group && c.pool_rows != c.group->nsample))) return PN2_E_ARG;
         if (!plan(c.pool_rows, 0)) return PN2_E_ARG;
         per_point = c.group && l1_per_point(c.nlayers, widths, &gd, o);
@@ -872,6 +889,8 @@ struct Fwd : TlRun {
         keep_top = c.pooling != 0 || top_stored(c.rows, c.nlayers, widths, c.pool_rows, o);    // a mean needs z_L itself
         for (int l = 0; l < c.nlayers; ++l)
             if (!c.layers[l].z && (keep_top || l < c.nlayers - 1)) return PN2_E_NULL;
+        if (c.mask)                                               // ragged rows: lengths -> the validity words and the count
+            if (int rc = launch_ragged_mask(c.rg_b, c.rg_n, c.lengths, c.mask, st)) return rc;
         if (int rc = pack_weights()) return rc;
         if (c.frozen)                                             // every layer's (m', invstd, a, c) from the running statistics
             if (int rc = frozen_launch_save(c.nlayers, c.layers, st)) return rc;
@@ -1157,8 +1176,10 @@ struct Bwd : TlRun {
     {
         const pn2_bn_layer &L = layers[l];
         if (!folded[l] && !c.frozen)
-            if (int rc = launch_bn_backward_finalize(stats(l), nparts[l], L.cout, (double)rows, L.gamma, L.save, L.grad_gamma, L.grad_beta,
-                                                     coef(l), L.grad_accumulate, st)) return rc;
+            if (int rc = c.mask ? launch_bn_backward_finalize_counted(stats(l), nparts[l], L.cout, ragged_count(c.mask), L.gamma, L.save,
+                                                                      L.grad_gamma, L.grad_beta, coef(l), L.grad_accumulate, st)
+                                : launch_bn_backward_finalize(stats(l), nparts[l], L.cout, (double)rows, L.gamma, L.save, L.grad_gamma,
+                                                              L.grad_beta, coef(l), L.grad_accumulate, st)) return rc;
         return sd.join();
     }
 
@@ -1338,6 +1359,7 @@ struct Bwd : TlRun {
         w.argsel = c.argsel;
         w.coef = coef(l);
         w.group_rows = pool_rows;
+        w.mask = mask_words();
         if (fz[l].ok) {
             // ... and the data gradient in the same pass over (dy_l, z_l, z_{l-1}), see tl_wgrad_kernel
             dy_in_wgrad(w, l, L.cin);
@@ -1374,6 +1396,7 @@ struct Bwd : TlRun {
         p.argsel = c.argsel;
         p.p0 = coef(l); p.p1 = coef(l) + L.cout; p.p2 = coef(l) + 2 * L.cout;
         p.group_rows = pool_rows;
+        p.mask = mask_words();
         if (l > 0) into_below(p, l);
         else if (c.group) plain_out(p, c.grad_feat_rows, cfeat);
         else plain_out(p, c.grad_x, L.cin);
@@ -1451,6 +1474,14 @@ long long tl_xyz_ws_bytes(long long rows, int nlayers, const int *widths, int po
     XyzPlan xp;
     if (!xyz_plan(pl, rows, nlayers, widths, gd, o, xp)) return -1;
     return (long long)xp.total;
+}
+
+// the workspace of the plain rows of a ragged batch (pn2_mlp_train_ws_bytes_ragged, train_mlp_ragged.hip): under ragged_opts
+long long tl_ragged_ws_bytes(long long rows, int nlayers, const int *widths, int backward, const pn2_train_opts *opts)
+{
+    TlPlan pl;
+    if (!tl_plan(rows, nlayers, widths, 0, backward, pl, nullptr, ragged_opts(opts))) return -1;
+    return (long long)pl.total;
 }
 
 // the workspace of the FP level with layer 1 per known point (pn2_mlp_train_ws_bytes_fp, train_mlp_fp.hip)

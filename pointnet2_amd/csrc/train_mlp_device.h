@@ -517,9 +517,12 @@ __device__ __forceinline__ int wg_swz(int lane, int e) { return lane ^ (((lane >
 // as 2-byte stores (each lane holds ONE channel of eight rows; the transposition has to happen somewhere, and here it is
 // spread over the eight producer waves instead of eight 2-byte reads per fragment in the two consumer waves). The 16-byte
 // slot index is XOR-ed with (g | hl << 1 | q << 2): without it the 64 lanes of one store hit four banks.
-template <int DCLS>
+//
+// MASKED (ragged rows, train_mlp_ragged.hip): mw is the validity word of the block; the unit's eight rows 16 e + 8 hl + j whose
+// bit is clear enter BOTH operands as zero (selects behind the prologues): h^T dz gets nothing from a padding row, whatever it holds.
+template <int DCLS, bool MASKED = false>
 __device__ __forceinline__ void wg_store_unit(const WgUnit &w, const WgRaw &r, int lane, u32x4 *img, float *zr = nullptr, int zpitch = 0,
-                                              u32x4 *imgA = nullptr, int tus = 0)
+                                              u32x4 *imgA = nullptr, int tus = 0, unsigned mw = 0xffffffffu)
 {
     if (w.kind == K_NONE || w.kind == K_ONES) return;             // nothing / written once before the loop
     if (zr && w.kind == K_H && w.relu && w.tile * 32 + 32 <= zpitch) {
@@ -566,6 +569,11 @@ __device__ __forceinline__ void wg_store_unit(const WgUnit &w, const WgRaw &r, i
             const float dy = DCLS == D_DZPOOL ? (r.sel - r.off == j ? r.gq : 0.0f) : r.g[j];
             x[j] = w.voff == kWgOob ? 0.0f : __fsub_rn(__fsub_rn(__fmul_rn(w.p0, dy), w.p1), __fmul_rn(w.p2, r.z[j]));
         }
+    }
+    if (MASKED) {
+        const unsigned mb = mw >> (16 * w.e + 8 * (lane >> 5));
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = ((mb >> j) & 1u) ? x[j] : 0.0f;
     }
     const ActSplit sp = split_act(x);                             // registers 0..7 -> p[0][level]
     o[0] = sp.p[0][0];

@@ -15,11 +15,13 @@ __global__ __launch_bounds__(kTlThreads) void tl_gemm_kernel(const TlGemm p)
 #define PN2_BY blockIdx.y
 #define PN2_GX gridDim.x
 #define PN2_STATS STATS
+#define PN2_MASKED false
 #include "tl_gemm_body.inc"
 #undef PN2_BX
 #undef PN2_BY
 #undef PN2_GX
 #undef PN2_STATS
+#undef PN2_MASKED
 }
 
 // ---- weights -> three-level bf16 operand tiles, on the device ---------------------------------------------------------
@@ -131,6 +133,7 @@ int launch_gemm(int amode, TlGemm &p, const GemmShape &g, hipStream_t st, const 
     const dim3 grid = prep_gemm(p, g, o);
     if (nparts) *nparts = (int)grid.x;
     if (p.fin.ticket) { p.fin.total = grid.x * grid.y; p.fin.nparts = (int)grid.x; }
+    if (p.mask) return launch_gemm_masked(amode, p, g, grid, st);      // ragged rows: kernels of their own (train_mlp_ragged.hip)
     if (g.ns == 4) return launch_gemm_ns<4>(amode, p, g, grid, st);
     if (g.ns == 2) return launch_gemm_ns<2>(amode, p, g, grid, st);
     return launch_gemm_ns<1>(amode, p, g, grid, st);

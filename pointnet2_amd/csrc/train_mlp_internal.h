@@ -59,6 +59,12 @@ struct TlCall {
     // before the first pass, the per-channel sums of backward feed only grad_gamma / grad_beta / grad_bias (one launch for
     // all layers behind the last pass), and a layer that wants no parameter gradient runs no weight-gradient pass at all.
     bool frozen;
+    // Plain rows of a RAGGED batch (train_mlp_ragged.hip): row c n + i is valid iff i < clamp(lengths[c], 1, n). `mask` is the
+    // caller's buffer (the valid-row count, one validity word per 32 rows): forward writes it from `lengths` before its first
+    // pass, backward reads it. nullptr: every row is valid.
+    void *mask;
+    const int *lengths;              // forward only
+    int rg_b, rg_n;
     // forward writes these, backward reads them. Whichever of argsel / zsel / pool_w the pooling mode does not use is
     // ignored, whatever the caller passed (tl_pool_buffers)
     const float *out;
@@ -95,6 +101,7 @@ int tl_pool_args(int pool_rows, int pooling, bool grouped);     // 0, or the PN2
 long long tl_xyz_ws_bytes(long long rows, int nlayers, const int *widths, int pool_rows, int pooling, const int *group_dims,
                           const pn2_train_opts *opts);
 long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts);
+long long tl_ragged_ws_bytes(long long rows, int nlayers, const int *widths, int backward, const pn2_train_opts *opts);
 
 // ---- train_mlp_fp.hip ----
 int fp_launch_pad(const float *src, long long rows_in, int c, long long rows_out, int cp, float *dst, hipStream_t st);

@@ -85,6 +85,7 @@ struct TlGemm {
     int lab;                    // lab builds of the timing study only (PN2_TL_LAB, prep_gemm): 1 = no stores, 2 = no statistics; 0 in production
     int nostats;                // 1: the kernel's compile-time "no statistics" variant (frozen batch-norm statistics); stats is NULL then
     TlFin fin;                  // the per-channel finalisation of `stats`, by the workgroup that finishes last (fin.ticket != nullptr)
+    const unsigned *mask;       // ragged rows (train_mlp_ragged.hip): bit r & 31 of word r / 32 = row r is valid; nullptr: every row is
 };
 
 // ---- weights -> three-level bf16 operand tiles, on the device (tl_pack_kernel, train_mlp_gemm.hip) ----
@@ -136,6 +137,7 @@ struct TlWgrad {
     double *l1a;                // (gridDim.x, 3, dy_pitch): sum over this workgroup's rows of x[k] * dy[.][col]
     int xr_off;                 // byte offset of the coordinate rows in LDS
     unsigned long long *timing; // lab builds (PN2_WG_TIMING, launch_wgrad): per-wave cycle counts of the block loop's phases, workgroup 0
+    const unsigned *mask;       // ragged rows (train_mlp_ragged.hip): the validity word of every 32-row block, or nullptr
 };
 
 // ---- the ROUTED part of the pooled top layer's weight gradient on the vector units (tl_top_s_kernel, train_mlp_top.hip) ----
@@ -230,5 +232,25 @@ int launch_pool_avg(long long groups, int ns, int N, const float *z, const float
 int launch_pool_top_grad(long long rows, int ns, int N, const float *gout, const float *z, const float *save, const float *pool_w,
                          const int *argsel, float *dy, double *stats, int parts, hipStream_t st);
 int launch_identity_coef(int C, float *coef, hipStream_t st);
+// ... the two finalisations with the row count read from device memory (ragged rows: the number of valid rows)
+int launch_bn_finalize_counted(const double *stats, int nparts, int N, const double *count, const float *gamma, const float *beta,
+                               float *running_mean, float *running_var, float momentum, float eps, float *save, const float *bias,
+                               int var_biased, hipStream_t st);
+int launch_bn_backward_finalize_counted(const double *stats, int nparts, int N, const double *count, const float *gamma,
+                                        const float *save, float *grad_gamma, float *grad_beta, float *coef, int accumulate,
+                                        hipStream_t st);
+
+// ---- train_mlp_ragged.hip: plain rows of a ragged batch (pn2_mlp_train_*_ragged) ----
+// The caller's mask buffer: the number of valid rows as a double, then one validity word per 32 rows
+constexpr size_t kRaggedWordsOff = 16;
+inline const double *ragged_count(const void *mask) { return static_cast<const double *>(mask); }
+inline const unsigned *ragged_words(const void *mask)
+{
+    return reinterpret_cast<const unsigned *>(static_cast<const char *>(mask) + kRaggedWordsOff);
+}
+int launch_ragged_mask(int b, int n, const int *lengths, void *mask, hipStream_t st);
+int launch_gemm_masked(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st);
+int launch_wgrad_masked(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st);
+int launch_apply_masked(long long total4, int N, const float *z, const float *save, const unsigned *mask, float *out, hipStream_t st);
 
 }  // namespace pn2

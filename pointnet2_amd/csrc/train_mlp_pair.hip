@@ -28,8 +28,10 @@ __global__ __launch_bounds__(kTlThreads) void tl_pair_kernel(const TlGemm pg, co
 #define PN2_BY sby
 #define PN2_GX ga
 #define PN2_STATS true                  // (the pair keeps the sums as a run-time choice: p.stats may be NULL under frozen statistics)
+#define PN2_MASKED false
 #include "tl_gemm_body.inc"
 #undef PN2_STATS
+#undef PN2_MASKED
 #undef PN2_BX
 #undef PN2_BY
 #undef PN2_GX
@@ -40,7 +42,9 @@ __global__ __launch_bounds__(kTlThreads) void tl_pair_kernel(const TlGemm pg, co
 #define PN2_BX sbx
 #define PN2_BY sby
 #define PN2_GX gw
+#define PN2_MASKED false
 #include "tl_wgrad_body.inc"
+#undef PN2_MASKED
 #undef PN2_BX
 #undef PN2_BY
 #undef PN2_GX

@@ -49,6 +49,37 @@ __global__ __launch_bounds__(256) void tl_bn_backward_finalize_kernel(const doub
     tl_bn_backward_finalize_channel(c, N, s1, s2, count, gamma, save, grad_gamma, grad_beta, coef, accumulate);
 }
 
+// ... the same two with the row count read from device memory: the plain rows of a ragged batch (train_mlp_ragged.hip), whose
+// count is the number of valid rows -- a sum of clamped lengths the host never sees
+__global__ __launch_bounds__(256) void tl_bn_finalize_counted_kernel(const double *__restrict__ stats, int nparts, int N,
+                                                                     const double *__restrict__ count, const float *__restrict__ gamma,
+                                                                     const float *__restrict__ beta, float *running_mean,
+                                                                     float *running_var, float momentum, float eps,
+                                                                     float *__restrict__ save, const float *__restrict__ bias,
+                                                                     int var_biased)
+{
+    double s1, s2;
+    tl_sum_parts(stats, nparts, N, s1, s2);
+    const int c = blockIdx.x * 8 + (threadIdx.x & 7);
+    if (threadIdx.x >= 8 || c >= N) return;
+    tl_bn_finalize_channel(c, N, s1, s2, *count, gamma, beta, running_mean, running_var, momentum, eps, save, bias, var_biased);
+}
+
+__global__ __launch_bounds__(256) void tl_bn_backward_finalize_counted_kernel(const double *__restrict__ stats, int nparts, int N,
+                                                                              const double *__restrict__ count,
+                                                                              const float *__restrict__ gamma,
+                                                                              const float *__restrict__ save,
+                                                                              float *__restrict__ grad_gamma,
+                                                                              float *__restrict__ grad_beta, float *__restrict__ coef,
+                                                                              int accumulate)
+{
+    double s1, s2;
+    tl_sum_parts(stats, nparts, N, s1, s2);
+    const int c = blockIdx.x * 8 + (threadIdx.x & 7);
+    if (threadIdx.x >= 8 || c >= N) return;
+    tl_bn_backward_finalize_channel(c, N, s1, s2, *count, gamma, save, grad_gamma, grad_beta, coef, accumulate);
+}
+
 // pool: partial extrema of z (the max where gamma >= 0, else the min) -> out = relu(a zsel + c), the sample the gradient flows to, zsel
 __global__ void tl_pool_finalize_kernel(long long groups, int N, int parts, int prow, const float *__restrict__ pmax,
                                         const int *__restrict__ pamax, const float *__restrict__ gamma,
@@ -356,6 +387,22 @@ int launch_bn_backward_finalize(const double *stats, int nparts, int N, double c
 {
     return launch(tl_bn_backward_finalize_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, stats, nparts, N, count, gamma, save,
                   grad_gamma, grad_beta, coef, accumulate);
+}
+
+int launch_bn_finalize_counted(const double *stats, int nparts, int N, const double *count, const float *gamma, const float *beta,
+                               float *running_mean, float *running_var, float momentum, float eps, float *save, const float *bias,
+                               int var_biased, hipStream_t st)
+{
+    return launch(tl_bn_finalize_counted_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, stats, nparts, N, count, gamma, beta,
+                  running_mean, running_var, momentum, eps, save, bias, var_biased);
+}
+
+int launch_bn_backward_finalize_counted(const double *stats, int nparts, int N, const double *count, const float *gamma,
+                                        const float *save, float *grad_gamma, float *grad_beta, float *coef, int accumulate,
+                                        hipStream_t st)
+{
+    return launch(tl_bn_backward_finalize_counted_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, stats, nparts, N, count, gamma,
+                  save, grad_gamma, grad_beta, coef, accumulate);
 }
 
 int launch_pool_finalize(long long groups, int N, int parts, int prow, const float *pmax, const int *pamax, const float *gamma,

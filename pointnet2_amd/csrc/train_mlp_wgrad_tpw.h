@@ -28,7 +28,9 @@ __global__ __launch_bounds__(kTlThreads) void tl_wgrad_kernel(const TlWgrad p)
 #define PN2_BX blockIdx.x
 #define PN2_BY blockIdx.y
 #define PN2_GX gridDim.x
+#define PN2_MASKED false
 #include "tl_wgrad_body.inc"
+#undef PN2_MASKED
 #undef PN2_BX
 #undef PN2_BY
 #undef PN2_GX

@@ -588,6 +588,10 @@ class PointnetFPModule(nn.Module):
         self.fused_mlp = True          # eval-mode forward may use the fused kernel (csrc/fp_mlp.hip)
         self.fused_frozen_bn = False   # see PointnetSAModule: the fused node with frozen batch-norm statistics (opt-in)
         self.index_plans = False       # see PointnetSAModule: the index plan of three_nn's idx, built behind three_nn (opt-in)
+        # train() with a ragged unknown side (lengths1=): fp_interp_concat + the fused node with a row mask
+        # (train_mlp.fp_mlp_train(..., lengths=)) instead of the compacting layer-by-layer path: no host synchronisation, nothing
+        # compacted, capturable; last_path "fused_train_ragged". Opt-in, like fused_frozen_bn (_forward_ragged).
+        self.fused_ragged_train = False
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
@@ -680,7 +684,12 @@ class PointnetFPModule(nn.Module):
         are exactly zero. eval(): the existing paths on all rows (the padding rows of points1 must be finite), then a
         torch.where. train(): the batch statistics must cover the valid rows only, so the valid rows of interpolate + concat
         are compacted to (1, total, C), the layer stack runs layer by layer on them and the result is scattered back --
-        plain PyTorch, last_path "unfused_ragged", synchronises (the row list is built on the host's schedule)."""
+        plain PyTorch, last_path "unfused_ragged", synchronises (the row list is built on the host's schedule).
+        With fused_ragged_train (opt-in), CUDA tensors and a stack the masked node covers (_train_mode says "fused_train" and
+        train_mlp.ragged_supported): ONE launch for weights + interpolation + concatenation on all rows, then the stack as one
+        autograd node whose passes skip the padding rows (fp_mlp_train(..., lengths=)); last_path "fused_train_ragged". The
+        host reads nothing, the index plan is _stack_on's. The one-node form (fp_level_train) has no mask: this route is
+        taken even where fp_level_preferred would choose it."""
         b, n = xyz1.shape[0], xyz1.shape[1]
         dev = xyz1.device
         lens = ragged_lengths(lengths1, b, dev, "lengths1")
@@ -693,6 +702,13 @@ class PointnetFPModule(nn.Module):
         if not self.training:
             out = self._forward_on(xyz1, points1, points2, g)
             return torch.where(valid.unsqueeze(2), out, torch.zeros((), dtype=out.dtype, device=dev))
+        if self.fused_ragged_train and xyz1.is_cuda and self._train_mode(points1, points2, b * n) == "fused_train" and \
+                train_mlp.ragged_supported(self.mlp.net, b, n):
+            self.last_path = "fused_train_ragged"
+            c1 = points1.shape[2] if points1 is not None else 0
+            plan = self._plan_of(g.idx, xyz2.shape[1], getattr(g, "plan", None))
+            x, _ = fp_interp_concat(points2, points1, g.idx, g.dist, plan=plan)                   # :212-219, on every row
+            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, lengths=lens)
         self.last_path = "unfused_ragged"
         interpolated = three_interpolate(points2, g.idx, _inverse_distance_weights(g.dist), plan=getattr(g, "plan", None))   # :212-216
         x = torch.cat([interpolated, points1], dim=2) if points1 is not None else interpolated   # :219

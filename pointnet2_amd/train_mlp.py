@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _C
-from ._tensors import f32, i32, is_deterministic, on_device, ptr, require, same_device, scatter_grad, stream_ptr
+from ._tensors import f32, i32, is_deterministic, on_device, ptr, ragged_lengths, require, same_device, scatter_grad, stream_ptr
 
 _vp, _i, _ll, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
 
@@ -200,6 +200,17 @@ def frozen_supported(net, rows, pool_rows=0, grouped=True, pooling="max", xyz_di
         gdims = (ctypes.c_int * 6)(b, n, m, pool_rows, cfeat, 1 if has_idx else 0)
     return bool(_C.lib().pn2_mlp_train_frozen_supported(rows, len(widths) - 1, _widths_array(widths), pool_rows, code, gdims,
                                                         1 if xyz_dims is not None else 0))
+
+
+def ragged_supported(net, b, n):
+    """Can the fused training node run this stack on the plain rows of a RAGGED batch -- b clouds padded to n rows, batch
+    statistics over the valid rows only (fp_mlp_train(..., lengths=), pn2_mlp_train_*_ragged)? Mirrors
+    pn2_mlp_train_ragged_supported: b n a positive multiple of 32, and a stack stack_supported takes as plain rows."""
+    if b <= 0 or n <= 0 or not stack_supported(net, b * n, 0, False):
+        return False
+    pairs = conv_bn_pairs(net)
+    widths = [(pairs[0][0].in_channels + 3) // 4 * 4] + [c.out_channels for c, _ in pairs]      # zero-padded (fp_mlp_train)
+    return bool(_C.lib().pn2_mlp_train_ragged_supported(b, n, len(pairs), _widths_array(widths)))
 
 
 def _layer_array(level, weights, biases, gammas, betas, zs, saves, grads=None, update_running=True):
@@ -568,6 +579,59 @@ class _TrainMLP(torch.autograd.Function):
         return tuple(result + _batch_stat_results(grads, direct, biases, widths, dev))
 
 
+class _TrainMLPRagged(torch.autograd.Function):
+    """_TrainMLP's sibling for the plain rows of a ragged batch (pn2_mlp_train_*_ragged): inputs level, x (rows, cin), lengths
+    (b,) i32 on the device, then the parameters. Saved besides _TrainMLP's tensors: the validity mask forward wrote. The host
+    never reads lengths: no synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, level, x, lengths, *params):
+        n = len(level.pairs)
+        weights, biases, gammas, betas = _unpack_params(params, n)
+        dev = weights[0].device
+        rows = level.rows
+        widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
+        warr = _widths_array(widths)
+        opts = _opts()
+        zs = [torch.empty((rows, w), dtype=torch.float32, device=dev) for w in widths[1:]]
+        saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
+        out = torch.empty((rows, widths[-1]), dtype=torch.float32, device=dev)
+        mask = torch.empty((2 + (rows // 32 + 1) // 2,), dtype=torch.int64, device=dev)      # 16 + 4 (rows / 32) bytes, 8-byte aligned
+        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
+        ws = _workspace("pn2_mlp_train_ws_bytes_ragged", dev, "pn2_mlp_train_ragged: unsupported stack (b n % 32, widths % 4)",
+                        level.b, level.n, n, warr, 0, opts)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_mlp_train_forward_ragged(level.b, level.n, ptr(lengths), n, arr, ptr(x), ptr(out), ptr(mask), ptr(ws),
+                                                           opts, stream_ptr(dev)), "mlp_train_forward_ragged")
+        _count_batch(level.pairs)
+        ctx.level, ctx.widths = level, widths
+        ctx.opts = dict(_OPTS)
+        _save_layers(ctx, [x], weights, biases, gammas, betas, zs, saves, out, [mask, lengths])
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        level, widths = ctx.level, ctx.widths
+        n = len(level.pairs)
+        head, weights, biases, gammas, betas, zs, saves, out, tail = _saved_layers(ctx, n)
+        x, mask, lengths = head[0], tail[0], tail[1]
+        dev = out.device
+        grad_out = f32(grad_out, "grad_out")
+        grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
+        grad_x = torch.empty((level.rows, widths[0]), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        opts = _opts_from(ctx.opts)
+        ws = _workspace("pn2_mlp_train_ws_bytes_ragged", dev, "pn2_mlp_train_ragged: unsupported stack", level.b, level.n, n,
+                        _widths_array(widths), 1, opts)
+        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
+        for l in range(n):
+            arr[l].grad_accumulate = 1 if direct[l] else 0
+        with on_device(dev):
+            _C.check(_C.lib().pn2_mlp_train_backward_ragged(level.b, level.n, ptr(lengths), n, arr, ptr(x), ptr(out), ptr(grad_out),
+                                                            ptr(grad_x), ptr(mask), ptr(ws), opts, stream_ptr(dev)),
+                     "mlp_train_backward_ragged")
+        return tuple([None, grad_x, None] + _batch_stat_results(grads, direct, biases, widths, dev))
+
+
 def _params(pairs):
     out = []
     for conv, bn in pairs:
@@ -651,16 +715,26 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
     return out.view(b, lv.m, -1), argsel.view(b, lv.m, -1)
 
 
-def fp_mlp_train(net, x, cin=None, frozen=False):
+def fp_mlp_train(net, x, cin=None, frozen=False, lengths=None):
     """Training-mode shared MLP of one FP level on plain rows: x (b, n, cin) -> (b, n, cout).
     cin: the first layer's input width when x already carries zero columns up to a multiple of 4 behind it
     (tf_interpolate.fp_interp_concat writes them); default: x's own width (padded here if odd).
-    frozen: the batch norms normalise with their running statistics (see sa_mlp_train)."""
+    frozen: the batch norms normalise with their running statistics (see sa_mlp_train).
+    lengths: (b,) per-cloud row counts of a ragged batch (cloud i is x[i, :lengths[i]]; an int32 / int64 tensor or a sequence,
+    ragged_lengths): the batch statistics, the running averages and every gradient are those of the valid rows alone, as if the
+    stack had run on the compacted rows (ragged_supported; pn2_mlp_train_*_ragged). The padding rows of x and of the output's
+    gradient may hold anything, NaN included; the output and the gradient of x are exactly zero there. Nothing is compacted and
+    the host never reads the lengths (no synchronisation; a length outside 1..n is clamped, check_lengths is where values are
+    looked at). A batch with fewer than two valid rows has no variance: the caller's business. Not with frozen=True
+    (ValueError: eval() + a torch.where already differentiates correctly there)."""
     pairs = conv_bn_pairs(net)
     require(pairs is not None, "fp_mlp_train expects Conv 1x1 + BatchNorm + ReLU triples")
     x = f32(x, "x")
     require(x.dim() == 3, "x must be (b, n, cin), got %s" % (tuple(x.shape),))
     b, n, c = x.shape
+    if lengths is not None:
+        require(not frozen, "fp_mlp_train: lengths= is not offered with frozen=True")
+        lengths = ragged_lengths(lengths, b, x.device)
     if cin is not None and cin != c:
         require(cin < c and c % 4 == 0 and c - cin < 4, "x must be cin columns zero-padded to a multiple of 4")
         prepadded, c = True, cin
@@ -675,6 +749,7 @@ def fp_mlp_train(net, x, cin=None, frozen=False):
     lv.frozen = bool(frozen)
     require(frozen_supported(net, lv.rows, 0, False) if lv.frozen else stack_supported(net, lv.rows, 0, False),
             "unsupported stack for the fused training path")
+    require(lengths is None or ragged_supported(net, b, n), "unsupported stack for the fused training path on ragged rows")
     require(pairs[0][0].in_channels == c, "the first layer expects %d channels, got %d" % (pairs[0][0].in_channels, c))
     params = _params(pairs)
     x = x.reshape(b * n, x.shape[2])
@@ -687,7 +762,10 @@ def fp_mlp_train(net, x, cin=None, frozen=False):
         w = params[0]
         params[0] = torch.nn.functional.pad(w, (0, 0) * (w.dim() - 2) + (0, pad))
     lv.xyz_grad = False
-    out = _TrainMLP.apply(lv, x, None, None, *params)
+    if lengths is not None:
+        out = _TrainMLPRagged.apply(lv, x, lengths, *params)
+    else:
+        out = _TrainMLP.apply(lv, x, None, None, *params)
     return out.view(b, n, -1)
 
 
