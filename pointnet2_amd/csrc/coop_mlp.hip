@@ -424,9 +424,25 @@ bool mlp_coop_pick(int cin, int nlayers, const int *widths, MlpCoopConfig &cfg)
     return true;
 }
 
-// the (.., .., > 512) grouped stacks run their last layer in pool_gemm_kernel: the packed array then holds the
-// cooperative kernel's stream of layers 1-2 followed by the last layer in GEMM order (same number of pairs)
-bool mlp_coop_gemm_last(const MlpCoopConfig &c, int fp) { return !fp && c.q3 == 8; }
+// The instantiated kernels: X(gather, q1, q2, q3, route). kCoopFused: the whole stack in coop_mlp_kernel. kCoopGemmLast (the
+// grouped stacks with a last layer wider than 512): layers 1-2 in coop_mlp_kernel<.., q1, q2, 0, SPLIT_OUT>, the last layer in
+// pool_gemm_kernel -- the packed array then holds the cooperative kernel's stream of layers 1-2 followed by the last
+// layer in GEMM order (same number of pairs).
+constexpr int kCoopNone = -1, kCoopFused = 0, kCoopGemmLast = 1;
+#define PN2_COOP_SHAPES(X)                                                                                            \
+    X(kGatherGrouped, 1, 1, 2, kCoopFused) X(kGatherGrouped, 2, 2, 4, kCoopFused) X(kGatherGrouped, 2, 4, 8, kCoopGemmLast) \
+    X(kGatherInterp, 1, 1, 0, kCoopFused) X(kGatherInterp, 2, 1, 0, kCoopFused) X(kGatherInterp, 2, 2, 0, kCoopFused)  \
+    X(kGatherInterp, 1, 1, 1, kCoopFused) X(kGatherInterp, 2, 2, 2, kCoopFused)
+
+static int coop_route(const MlpCoopConfig &c, int fp)
+{
+#define PN2_COOP_ROUTE(G, A, B, C, ROUTE) \
+    if (fp == (G == kGatherInterp) && c.q1 == A && c.q2 == B && c.q3 == C) return ROUTE;
+    PN2_COOP_SHAPES(PN2_COOP_ROUTE)
+#undef PN2_COOP_ROUTE
+    return kCoopNone;
+}
+bool mlp_coop_has_kernel(const MlpCoopConfig &c, int fp) { return coop_route(c, fp) != kCoopNone; }
 
 static long long coop_pairs(const MlpCoopConfig &c)
 {
@@ -435,7 +451,7 @@ static long long coop_pairs(const MlpCoopConfig &c)
 size_t mlp_coop_w_floats(const MlpCoopConfig &c) { return (size_t)coop_pairs(c) * kPairWords; }
 size_t mlp_coop_ws_bytes(const MlpCoopConfig &c, int fp, long long rows, int nsample)
 {
-    if (!mlp_coop_gemm_last(c, fp)) return 0;
+    if (coop_route(c, fp) != kCoopGemmLast) return 0;
     return sizeof(float) * kPairWords * (size_t)rows * ((nsample + 31) / 32) * (4 * c.q2);
 }
 size_t mlp_coop_b_floats(const MlpCoopConfig &c) { return (size_t)(4 * (c.q1 + c.q2 + c.q3)) * 32; }
@@ -447,7 +463,7 @@ void mlp_coop_pack(const MlpCoopConfig &c, int cin, int nlayers, const int *widt
     float *wp = wpacked;
     const int tin[3] = {c.ti, 4 * c.q1, 4 * c.q2}, qq[3] = {c.q1, c.q2, c.q3};
     const int kin[3] = {cin, widths[0], nlayers > 1 ? widths[1] : 0};
-    const bool gemm_last = krow_is_grouped && mlp_coop_gemm_last(c, 0);
+    const bool gemm_last = krow_is_grouped && coop_route(c, 0) == kCoopGemmLast;
     for (int L = 0; L < nlayers; ++L) {
         if (L == 2 && gemm_last) {                             // [column block][contraction tile][tile of the block]
             for (int cb = 0; cb < 4 * qq[2] / kGemmColTiles; ++cb)
@@ -467,26 +483,22 @@ void mlp_coop_pack(const MlpCoopConfig &c, int cin, int nlayers, const int *widt
             for (int ch = 0; ch < 32 * 4 * qq[2]; ++ch) *bp++ = ch < widths[2] ? bs[2][ch] : 0.0f;
             continue;
         }
-        for (int t = 0; t < 4 * qq[L]; ++t)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int v = 0; v < 16; ++v) {
-                    const int ch = 32 * t + mlp_chan(v, hh);
-                    *bp++ = (L < nlayers && ch < widths[L]) ? bs[L][ch] : 0.0f;
-                }
+        bp = mlp_pack_bias(bp, L < nlayers ? bs[L] : nullptr, L < nlayers ? widths[L] : 0, 4 * qq[L]);
     }
 }
 
-template <int GATHER, int Q1, int Q2, int Q3>
+template <int GATHER, int Q1, int Q2, int Q3, bool SPLIT_OUT = false>
 static int launch_coop(const CoopParams &p, long long units, hipStream_t st)
 {
     const size_t lds = sizeof(float) * kPairWords * (size_t)(4 * Q1 + (Q3 > 0 ? 4 * Q2 : 0)) + sizeof(float) * 32 * (size_t)(4 * (Q1 + Q2 + Q3));
-    auto kern = coop_mlp_kernel<GATHER, Q1, Q2, Q3>;
+    auto kern = coop_mlp_kernel<GATHER, Q1, Q2, Q3, SPLIT_OUT>;
     if (int rc = allow_dynamic_lds(kern, lds)) return rc;
     long long blocks = units < 512 ? units : 512;
     return launch(kern, dim3((unsigned)blocks), dim3(kMlpThreads), lds, st, p);
 }
 
 // layers 1-2 by the cooperative kernel into `ws` (three-level operand tiles), the last layer + pool as a GEMM
+template <int Q1, int Q2>
 static int launch_gemm_last(const MlpCoopConfig &c, const CoopParams &p_in, void *ws, hipStream_t st)
 {
     if (!ws) return PN2_E_NULL;
@@ -495,13 +507,7 @@ static int launch_gemm_last(const MlpCoopConfig &c, const CoopParams &p_in, void
     p.split = 1;
     float *final_out = p.out;
     p.out = (float *)ws;
-    {
-        auto kern = coop_mlp_kernel<kGatherGrouped, 2, 4, 0, true>;
-        const size_t lds = sizeof(float) * kPairWords * (size_t)(4 * 2) + sizeof(float) * 32 * (size_t)(4 * (2 + 4));
-        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        const long long units = p.rows * parts;
-        if (int rc = launch(kern, dim3((unsigned)(units < 512 ? units : 512)), dim3(kMlpThreads), lds, st, p)) return rc;
-    }
+    if (int rc = launch_coop<kGatherGrouped, Q1, Q2, 0, true>(p, p.rows * parts, st)) return rc;
     const size_t two_layers = (size_t)kPairWords * 4 * (size_t)(c.ti * c.q1 + 4 * c.q1 * c.q2);      // words of layers 1-2
     const float *wgemm = p.wp + two_layers, *b3 = p.bp + 32 * (size_t)(4 * (c.q1 + c.q2));
     const size_t lds = sizeof(u32x4) * 2 * kGemmStageVec + sizeof(int) * 32 * kGemmColTiles;
@@ -511,39 +517,31 @@ static int launch_gemm_last(const MlpCoopConfig &c, const CoopParams &p_in, void
                   p.rows, (const float *)ws, wgemm, b3, final_out);
 }
 
-int mlp_coop_launch(const MlpCoopConfig &c, int fp, const CoopParams &p_in, hipStream_t st, void *ws)
+template <int G, int Q1, int Q2, int Q3, int ROUTE>
+static int launch_coop_shape(const MlpCoopConfig &c, const CoopParams &p_in, hipStream_t st, void *ws)
 {
-    if (mlp_coop_gemm_last(c, fp)) return launch_gemm_last(c, p_in, ws, st);
-    CoopParams p = p_in;
-    const int parts = (p.nsample + 31) / 32;
-    p.split = (!fp && parts > 1 && p.rows < 256) ? 1 : 0;          // few large groups: one work unit per 32-sample part
-    if (p.split) {
-        if (int rc = clear_async(p.out, sizeof(float) * (size_t)p.rows * p.cout, st)) return rc;
+    if constexpr (ROUTE == kCoopGemmLast) {
+        return launch_gemm_last<Q1, Q2>(c, p_in, ws, st);
+    } else {
+        constexpr bool fp = G == kGatherInterp;
+        CoopParams p = p_in;
+        const int parts = (p.nsample + 31) / 32;
+        p.split = (!fp && parts > 1 && p.rows < 256) ? 1 : 0;          // few large groups: one work unit per 32-sample part
+        if (p.split) {
+            if (int rc = clear_async(p.out, sizeof(float) * (size_t)p.rows * p.cout, st)) return rc;
+        }
+        const long long units = fp ? (p.rows + 31) / 32 : (p.split ? p.rows * parts : p.rows);
+        return launch_coop<G, Q1, Q2, Q3>(p, units, st);
     }
-    const long long units = fp ? (p.rows + 31) / 32 : (p.split ? p.rows * parts : p.rows);
-#define PN2_COOP_CASE(G, A, B, C) \
-    if (fp == (G == kGatherInterp) && c.q1 == A && c.q2 == B && c.q3 == C) return launch_coop<G, A, B, C>(p, units, st)
-    PN2_COOP_CASE(kGatherGrouped, 1, 1, 2);
-    PN2_COOP_CASE(kGatherGrouped, 2, 2, 4);
-    PN2_COOP_CASE(kGatherInterp, 1, 1, 0);
-    PN2_COOP_CASE(kGatherInterp, 2, 1, 0);
-    PN2_COOP_CASE(kGatherInterp, 2, 2, 0);
-    PN2_COOP_CASE(kGatherInterp, 1, 1, 1);
-    PN2_COOP_CASE(kGatherInterp, 2, 2, 2);
-#undef PN2_COOP_CASE
-    return PN2_E_TOO_LARGE;
 }
 
-bool mlp_coop_has_kernel(const MlpCoopConfig &c, int fp)
+int mlp_coop_launch(const MlpCoopConfig &c, int fp, const CoopParams &p_in, hipStream_t st, void *ws)
 {
-    static const int sa[][3] = {{1, 1, 2}, {2, 2, 4}, {2, 4, 8}};
-    static const int fpk[][3] = {{1, 1, 0}, {2, 1, 0}, {2, 2, 0}, {1, 1, 1}, {2, 2, 2}};
-    if (fp) {
-        for (const auto &k : fpk) if (c.q1 == k[0] && c.q2 == k[1] && c.q3 == k[2]) return true;
-    } else {
-        for (const auto &k : sa) if (c.q1 == k[0] && c.q2 == k[1] && c.q3 == k[2]) return true;
-    }
-    return false;
+#define PN2_COOP_LAUNCH(G, A, B, C, ROUTE) \
+    if (fp == (G == kGatherInterp) && c.q1 == A && c.q2 == B && c.q3 == C) return launch_coop_shape<G, A, B, C, ROUTE>(c, p_in, st, ws);
+    PN2_COOP_SHAPES(PN2_COOP_LAUNCH)
+#undef PN2_COOP_LAUNCH
+    return PN2_E_TOO_LARGE;
 }
 
 }  // namespace pn2

@@ -31,9 +31,6 @@
 // (pointnet2_part_seg.py:31-33, pointnet2_sem_seg.py:34-37) -- and any number of input channels.
 #include "sa_mlp_common.h"
 
-#include <limits.h>
-#include <stdlib.h>
-
 namespace pn2 {
 
 __device__ __forceinline__ float fp_interp3(float p1, float p2, float p3, float w1, float w2, float w3)
@@ -222,193 +219,59 @@ __global__ __launch_bounds__(kMlpThreads) void fp_mlp_stream_kernel(int n, int m
 #undef PN2_NEXT_STAGE
 }
 
-struct FpConfig { int ti, tif, t1, t2, t3; };        // ti: tiles of skip channels (c1), tif: tiles of known features (c2)
+// the instantiated tile shapes, smallest first within two and within three layers: X(t1, t2, t3), t3 == 0: two layers
+#define PN2_FP_SHAPES(X) X(4, 4, 0) X(8, 4, 0) X(8, 8, 0) X(4, 4, 4) X(8, 4, 4) X(8, 8, 4) X(8, 8, 8)
 
-// tile shapes with an instantiated kernel; widths are padded up to them with zero weights
-static bool fp_pick(int c2, int c1, int nlayers, const int *widths, FpConfig &cfg)
+// widths are padded up to a shape's with zero weights
+bool fp_stream_pick(int c2, int c1, int nlayers, const int *widths, FpConfig &cfg)
 {
     if (c2 < 1 || c1 < 0 || (nlayers != 2 && nlayers != 3)) return false;
     for (int i = 0; i < nlayers; ++i)
         if (widths[i] < 1 || widths[i] > 256) return false;
-    static const int kShapes[][3] = {{4, 4, 0}, {8, 4, 0}, {8, 8, 0}, {4, 4, 4}, {8, 4, 4}, {8, 8, 4}, {8, 8, 8}};
-    for (const auto &sh : kShapes) {
-        if ((sh[2] != 0) != (nlayers == 3)) continue;
-        if (widths[0] <= 32 * sh[0] && widths[1] <= 32 * sh[1] && (nlayers == 2 || widths[2] <= 32 * sh[2])) {
-            cfg = {(c1 + 31) / 32, (c2 + 31) / 32, sh[0], sh[1], sh[2]};
-            return true;
-        }
+#define PN2_FP_FITS(A, B, C)                                                                                           \
+    if ((C != 0) == (nlayers == 3) && widths[0] <= 32 * A && widths[1] <= 32 * B && (nlayers == 2 || widths[2] <= 32 * C)) { \
+        cfg = {(c1 + 31) / 32, (c2 + 31) / 32, A, B, C};                                                               \
+        return true;                                                                                                   \
     }
+    PN2_FP_SHAPES(PN2_FP_FITS)
+#undef PN2_FP_FITS
     return false;
 }
 
-// packed weights: [this kernel's stream: skip rows of layer 1 (padded to a stage), layer 2, layer 3]
-// [per-point kernel: known-feature rows of layer 1, one stream per 128 output channels]
+// this kernel's stream: skip rows of layer 1 (padded to a stage), layer 2, layer 3; biases [layer 1][layer 2][layer 3]
 static long long fp_main_pairs(const FpConfig &c) { return (long long)pad_to_stage(c.ti * c.t1) + c.t2 * c.t1 + c.t3 * c.t2; }
-static long long fp_point_pairs(const FpConfig &c) { return (long long)c.tif * c.t1; }       // t1 is 4 or 8: whole stages
-static long long fp_pairs(const FpConfig &c) { return fp_main_pairs(c) + fp_point_pairs(c); }
-// bias: [layer 1][layer 2][layer 3][128 zeros: the per-point kernel adds no bias, the interpolation weights multiply Q only]
-static long long fp_bias_floats(int t1, int t2, int t3) { return (long long)(t1 + t2 + t3) * 32 + 128; }
+size_t fp_stream_w_floats(const FpConfig &c) { return (size_t)fp_main_pairs(c) * kPairWords; }
+size_t fp_stream_b_floats(const FpConfig &c) { return (size_t)(c.t1 + c.t2 + c.t3) * 32; }
 
-// Q = points2 . W1a: few known points (most FP levels) -> one workgroup per (item, output tile), no staging;
-// many -> the streamed per-point kernel, 128 output channels per launch
-
-static int fp_point_layer(int t1, long long known_rows, int c2, int tif, const float *points2, const float *wpoint,
-                          const float *zero_bias, float *pre, hipStream_t st)
+// skip_row: row of ws[0] of skip channel k (the rows behind the interpolated channels)
+void fp_stream_pack(const FpConfig &c, int c1, int nlayers, const int *widths, const int *skip_row, const float *const *ws,
+                    const float *const *bs, float *wpacked, float *bpacked)
 {
-    if (point_layer_prefers_few_rows(known_rows, t1, tif)) return point_layer_few_rows_launch(t1, c2, known_rows, tif, points2, wpoint, nullptr, pre, st);
-    for (int half = 0; half < t1 / 4; ++half)
-        if (int rc = point_layer_launch(4, c2, known_rows, tif, points2, wpoint + (size_t)half * tif * 4 * kPairWords, zero_bias,
-                                        pre, 32 * t1, 128 * half, st)) return rc;
-    return PN2_OK;
+    float *wp = wpacked, *bp = bpacked;
+    for (int u = 0; u < c.ti; ++u)
+        for (int t = 0; t < c.t1; ++t) wp = mlp_pack_pair_x6(wp, ws[0], c1, widths[0], t, u, skip_row);
+    wp = mlp_pack_stage_padding(wp, c.ti * c.t1);
+    for (int t = 0; t < c.t2; ++t)
+        for (int u = 0; u < c.t1; ++u) wp = mlp_pack_pair_x6(wp, ws[1], widths[0], widths[1], t, u, nullptr);
+    for (int t = 0; t < c.t3; ++t)
+        for (int u = 0; u < c.t2; ++u) wp = mlp_pack_pair_x6(wp, ws[2], widths[1], widths[2], t, u, nullptr);
+    const int tout[3] = {c.t1, c.t2, c.t3};
+    for (int L = 0; L < nlayers; ++L) bp = mlp_pack_bias(bp, bs[L], widths[L], tout[L]);
 }
 
-template <int T1, int T2, int T3>
-static int launch_fp(const FpConfig &c, long long rows, int b, int n, int m, int c2, int c1, int cout, const float *points2,
-                     const float *points1, const int *idx, const float *dist, const float *wp, const float *bp, float *out,
-                     float *pre, hipStream_t st)
+int fp_stream_launch(const FpConfig &c, long long rows, int n, int m, int c1, int cout, const float *pre, const float *points1,
+                     const int *idx, const float *dist, const float *wp, const float *bp, float *out, hipStream_t st)
 {
-    const float *wpoint = wp + (size_t)fp_main_pairs(c) * kPairWords, *zeros = bp + (size_t)(T1 + T2 + T3) * 32;
-    if (int rc = fp_point_layer(T1, (long long)b * m, c2, c.tif, points2, wpoint, zeros, pre, st)) return rc;
-    const long long groups = (rows + 31) / 32;
-    long long blocks = (groups + 3) / 4;
-    if (blocks > 256) blocks = 256;                               // persistent, one workgroup per CU: every workgroup streams the weights
-    return launch((fp_mlp_stream_kernel<T1, T2, T3>), dim3((unsigned)blocks), dim3(kMlpThreads), 0, st, n, m, c1, cout,
-                  rows, c.ti, (const float *)pre, points1, idx, dist, wp, bp, out);
+    decltype(&fp_mlp_stream_kernel<4, 4, 0>) kern = nullptr;
+#define PN2_FP_KERNEL(A, B, C) \
+    if (c.t1 == A && c.t2 == B && c.t3 == C) kern = fp_mlp_stream_kernel<A, B, C>;
+    PN2_FP_SHAPES(PN2_FP_KERNEL)
+#undef PN2_FP_KERNEL
+    if (!kern) return PN2_E_TOO_LARGE;
+    const long long blocks = ((rows + 31) / 32 + 3) / 4;          // four 32-point items per workgroup
+    // persistent, at most one workgroup per CU: every workgroup streams the weights
+    return launch(kern, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(kMlpThreads), 0, st, n, m, c1, cout, rows, c.ti, pre,
+                  points1, idx, dist, wp, bp, out);
 }
 
 }  // namespace pn2
-
-// kind: 0 = one wave per 32 points, weights streamed through LDS (this file: many points);
-//       1 = four waves per 32 points (coop_mlp.hip: few points, wide layers). Same results, different packing.
-// tiles4 = {tiles of skip channels, tiles of layer 1, 2, 3}.
-extern "C" int pn2_fp_mlp_config(int c2, int c1, int nlayers, const int *widths, int kind, int *tiles4, long long *w_floats,
-                                 long long *b_floats)
-{
-    using namespace pn2;
-    if (c2 <= 0 || c1 < 0 || !widths || (kind != 0 && kind != 1)) return PN2_E_ARG;
-    if (kind == 1) {
-        MlpCoopConfig cc;
-        if (!mlp_coop_pick(c1, nlayers, widths, cc) || !mlp_coop_has_kernel(cc, 1)) return PN2_E_TOO_LARGE;
-        if (tiles4) { tiles4[0] = cc.ti; tiles4[1] = 4 * cc.q1; tiles4[2] = 4 * cc.q2; tiles4[3] = 4 * cc.q3; }
-        if (w_floats) *w_floats = (long long)mlp_coop_w_floats(cc) + (long long)((c2 + 31) / 32) * 4 * cc.q1 * kPairWords;
-        if (b_floats) *b_floats = (long long)mlp_coop_b_floats(cc) + 128;
-        return PN2_OK;
-    }
-    FpConfig c;
-    if (!fp_pick(c2, c1, nlayers, widths, c)) return PN2_E_TOO_LARGE;
-    if (tiles4) { tiles4[0] = c.ti; tiles4[1] = c.t1; tiles4[2] = c.t2; tiles4[3] = c.t3; }
-    if (w_floats) *w_floats = fp_pairs(c) * kPairWords;
-    if (b_floats) *b_floats = fp_bias_floats(c.t1, c.t2, c.t3);
-    return PN2_OK;
-}
-
-// Scratch of a pn2_fp_mlp call: Q = points2 . W1a, one row of the padded first width per known point.
-extern "C" long long pn2_fp_mlp_ws_bytes(int b, int m, int c2, int c1, int nlayers, const int *widths, int kind)
-{
-    using namespace pn2;
-    if (b <= 0 || m <= 0 || c2 <= 0 || c1 < 0 || !widths || (kind != 0 && kind != 1)) return 0;
-    int t1;
-    if (kind == 1) {
-        MlpCoopConfig cc;
-        if (!mlp_coop_pick(c1, nlayers, widths, cc) || !mlp_coop_has_kernel(cc, 1)) return 0;
-        t1 = 4 * cc.q1;
-    } else {
-        FpConfig c;
-        if (!fp_pick(c2, c1, nlayers, widths, c)) return 0;
-        t1 = c.t1;
-    }
-    return (long long)sizeof(float) * b * m * 32 * t1;
-}
-
-// Host code: permute (cin_i, cout_i) row-major weights (rows of layer 1 in the reference's concat order
-// [interpolated, points1]) into the tile-pair streams the chosen kernel and the per-point kernel consume.
-extern "C" int pn2_fp_mlp_pack(int c2, int c1, int nlayers, const int *widths, int kind, const float *const *w,
-                               const float *const *bias, float *wpacked, float *bpacked)
-{
-    using namespace pn2;
-    if (c2 <= 0 || c1 < 0 || !widths || !w || !bias || !wpacked || !bpacked) return PN2_E_NULL;
-    if (kind != 0 && kind != 1) return PN2_E_ARG;
-    const int tif = (c2 + 31) / 32;
-    int *skip_row = (int *)malloc(sizeof(int) * (size_t)(c1 > 0 ? c1 : 1));
-    for (int k = 0; k < c1; ++k) skip_row[k] = c2 + k;              // rows of w[0] behind the interpolated channels
-    int t1, t2, t3;
-    float *wp = wpacked, *bp = bpacked;
-    if (kind == 1) {
-        MlpCoopConfig cc;
-        if (!mlp_coop_pick(c1, nlayers, widths, cc) || !mlp_coop_has_kernel(cc, 1)) { free(skip_row); return PN2_E_TOO_LARGE; }
-        mlp_coop_pack(cc, c1, nlayers, widths, skip_row, w, bias, wpacked, bpacked, false);
-        wp += mlp_coop_w_floats(cc);
-        bp += mlp_coop_b_floats(cc);
-        t1 = 4 * cc.q1; t2 = 4 * cc.q2; t3 = 4 * cc.q3;
-    } else {
-        FpConfig c;
-        if (!fp_pick(c2, c1, nlayers, widths, c)) { free(skip_row); return PN2_E_TOO_LARGE; }
-        for (int u = 0; u < c.ti; ++u)
-            for (int t = 0; t < c.t1; ++t) wp = mlp_pack_pair_x6(wp, w[0], c1, widths[0], t, u, skip_row);
-        for (int i = c.ti * c.t1; i < pad_to_stage(c.ti * c.t1); ++i)
-            for (int j = 0; j < kPairWords; ++j) *wp++ = 0.0f;
-        for (int t = 0; t < c.t2; ++t)
-            for (int u = 0; u < c.t1; ++u) wp = mlp_pack_pair_x6(wp, w[1], widths[0], widths[1], t, u, nullptr);
-        for (int t = 0; t < c.t3; ++t)
-            for (int u = 0; u < c.t2; ++u) wp = mlp_pack_pair_x6(wp, w[2], widths[1], widths[2], t, u, nullptr);
-        const int tout[3] = {c.t1, c.t2, c.t3};
-        for (int L = 0; L < 3; ++L)
-            for (int t = 0; t < tout[L]; ++t)
-                for (int hh = 0; hh < 2; ++hh)
-                    for (int v = 0; v < 16; ++v) {
-                        const int ch = 32 * t + mlp_chan(v, hh);
-                        *bp++ = (L < nlayers && ch < widths[L]) ? bias[L][ch] : 0.0f;
-                    }
-        t1 = c.t1; t2 = c.t2; t3 = c.t3;
-    }
-    (void)t2; (void)t3;
-    free(skip_row);
-    // the per-point kernel's streams: known-feature rows of layer 1, 128 output channels (4 tiles) per stream, feature
-    // tiles outermost
-    for (int half = 0; half < t1 / 4; ++half)
-        for (int u = 0; u < tif; ++u)
-            for (int t = 4 * half; t < 4 * half + 4; ++t) wp = mlp_pack_pair_x6(wp, w[0], c2, widths[0], t, u, nullptr);
-    for (int i = 0; i < 128; ++i) *bp++ = 0.0f;
-    return PN2_OK;
-}
-
-extern "C" int pn2_fp_mlp(int b, int n, int m, int c2, int c1, const float *points2, const float *points1, const int *idx,
-                          const float *dist, int nlayers, const int *widths, int kind, const float *wpacked,
-                          const float *bpacked, float *out, void *ws, void *stream)
-{
-    using namespace pn2;
-    if (b < 0 || n < 0 || m <= 0 || c2 <= 0 || c1 < 0) return PN2_E_SHAPE;
-    if (!widths) return PN2_E_NULL;
-    if (kind != 0 && kind != 1) return PN2_E_ARG;
-    FpConfig c;
-    MlpCoopConfig cc;
-    if (kind == 0 ? !fp_pick(c2, c1, nlayers, widths, c)
-                  : !(mlp_coop_pick(c1, nlayers, widths, cc) && mlp_coop_has_kernel(cc, 1))) return PN2_E_TOO_LARGE;
-    const long long rows = (long long)b * n;
-    if (rows == 0) return PN2_OK;
-    if (!points2 || (c1 > 0 && !points1) || !idx || !dist || !wpacked || !bpacked || !out || !ws) return PN2_E_NULL;
-    if ((long long)m * c2 > INT_MAX) return PN2_E_TOO_LARGE;
-    const int cout = widths[nlayers - 1];
-    hipStream_t st = as_stream(stream);
-    if (kind == 1) {
-        const int t1 = 4 * cc.q1, tif = (c2 + 31) / 32;
-        const float *wpoint = wpacked + mlp_coop_w_floats(cc), *zeros = bpacked + mlp_coop_b_floats(cc);
-        if (int rc = fp_point_layer(t1, (long long)b * m, c2, tif, points2, wpoint, zeros, (float *)ws, st)) return rc;
-        CoopParams p = {n, m, 0, c2, c1, cout, cc.ti, rows, nullptr, nullptr, (const float *)ws, c1 > 0 ? points1 : nullptr, idx, dist,
-                        wpacked, bpacked, out, 0};
-        return mlp_coop_launch(cc, 1, p, st, nullptr);
-    }
-#define PN2_FP_CASE(A, B, C)                                                                                           \
-    if (c.t1 == A && c.t2 == B && c.t3 == C)                                                                            \
-        return launch_fp<A, B, C>(c, rows, b, n, m, c2, c1, cout, points2, points1, idx, dist, wpacked, bpacked, out, \
-                                  (float *)ws, st)
-    PN2_FP_CASE(4, 4, 0);
-    PN2_FP_CASE(8, 4, 0);
-    PN2_FP_CASE(8, 8, 0);
-    PN2_FP_CASE(4, 4, 4);
-    PN2_FP_CASE(8, 4, 4);
-    PN2_FP_CASE(8, 8, 4);
-    PN2_FP_CASE(8, 8, 8);
-#undef PN2_FP_CASE
-    return PN2_E_TOO_LARGE;
-}

@@ -33,7 +33,7 @@
 // (e = 0, 1) of input tile u the index k = 32u + 8((8e + j) >> 2) + 4(l >> 5) + (j & 3) makes the B operand of step e
 // EXACTLY accumulator registers 8e .. 8e + 7 of the previous layer's tile u (after the split into levels): the
 // activations never move between layers -- no LDS round trip, no shuffles. The weights are stored pre-permuted to
-// match (pn2_sa_mlp3_pack), in LDS, one ds_read_b128 per lane, level and K16 step.
+// match (mlp_resident_pack), in LDS, one ds_read_b128 per lane, level and K16 step.
 // The LAST layer swaps the two MFMA operands (their lane maps are the same: index l & 31, slots by l >> 5),
 // which yields the untransposed H (samples x channels): a lane then holds 16 SAMPLES of one
 // channel, so the max-pool is 15 lane-local v_max plus one exchange with lane l ^ 32, and bias + ReLU
@@ -41,9 +41,6 @@
 // Pooling across lanes instead (the first version) cost 5 cross-lane steps for each of 64 registers.
 // Eight waves (two per SIMD) share one copy of the weights in LDS.
 #include "sa_mlp_common.h"
-
-#include <stdlib.h>
-#include <string.h>
 
 namespace pn2 {
 
@@ -573,71 +570,52 @@ __global__ __launch_bounds__(NT) void sa_mlp3_pair_kernel(int n, int m, int nsam
     }
 }
 
-// ---- host side: bf16 levels of the weights ------------------------------------------------------------------
-static unsigned short bf16_nearest_even(float f)
-{
-    unsigned int u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);      // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
+// ---- host side ---------------------------------------------------------------------------------------------
+// the instantiated tile configurations, smallest first: X(t1, t2, t3)
+#define PN2_RESIDENT_SHAPES(X) X(1, 1, 2) X(2, 2, 4) X(2, 3, 4)
 
-static float bf16_value(unsigned short b)
-{
-    const unsigned int u = (unsigned int)b << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
+size_t mlp_resident_w_floats(const MlpResidentConfig &c) { return mlp_w_floats(c.t1, 1) + mlp_w_floats(c.t2, c.t1) + mlp_w_floats(c.t3, c.t2); }
+size_t mlp_resident_b_floats(const MlpResidentConfig &c) { return mlp_b_floats(c.t1) + mlp_b_floats(c.t2) + mlp_b_floats(c.t3); }
+static size_t resident_lds_bytes(const MlpResidentConfig &c) { return sizeof(float) * (mlp_resident_w_floats(c) + mlp_resident_b_floats(c)); }
 
-void mlp_split_weight(float w, unsigned short out[3])
+// smallest instantiated tile configuration that covers (c1, c2, c3) with a one-tile input, if its weights fit in LDS;
+// padded channels carry zero weights and zero bias, cost MFMA time and never reach memory
+bool mlp_resident_pick(int cin, int c1, int c2, int c3, MlpResidentConfig &cfg)
 {
-    out[0] = bf16_nearest_even(w);
-    const float r1 = w - bf16_value(out[0]);              // exact: the residual of a nearest rounding fits in fp32
-    out[1] = bf16_nearest_even(r1);
-    const float r2 = r1 - bf16_value(out[1]);
-    out[2] = bf16_nearest_even(r2);
-}
-
-// value for K16 step e, level, lane l, slot j = level of W[krow(32u + mlp_chan(8e + j, l >> 5))][32t + (l & 31)]
-float *mlp_pack_pair_x6(float *wp, const float *w, int kin, int nout, int t, int u, const int *krow)
-{
-    unsigned short *o = reinterpret_cast<unsigned short *>(wp);
-    for (int e = 0; e < 2; ++e)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 8; ++j) {
-                const int k = 32 * u + mlp_chan(8 * e + j, lane >> 5), nn = 32 * t + (lane & 31);
-                const float val = (k < kin && nn < nout) ? w[(size_t)(krow ? krow[k] : k) * nout + nn] : 0.0f;
-                unsigned short lv[3];
-                mlp_split_weight(val, lv);
-                for (int level = 0; level < 3; ++level) o[(((e * 3 + level) * 64 + lane) * 8) + j] = lv[level];
-            }
-    return wp + kPairWords;
-}
-
-struct MlpConfig { int t1, t2, t3; };
-
-// smallest instantiated tile configuration that covers (c1, c2, c3); padded channels carry zero
-// weights and zero bias, cost MFMA time and never reach memory
-static bool mlp_pick(int c1, int c2, int c3, MlpConfig &cfg)
-{
-    static const MlpConfig kConfigs[] = {{1, 1, 2}, {2, 2, 4}, {2, 3, 4}};
-    for (const MlpConfig &c : kConfigs)
-        if (c1 <= 32 * c.t1 && c2 <= 32 * c.t2 && c3 <= 32 * c.t3) { cfg = c; return true; }
+    if (cin > 32) return false;
+#define PN2_RESIDENT_FITS(A, B, C)                                                \
+    if (c1 <= 32 * A && c2 <= 32 * B && c3 <= 32 * C) {                           \
+        cfg = {A, B, C};                                                          \
+        return resident_lds_bytes(cfg) <= (size_t)kMlpMaxLds;                     \
+    }
+    PN2_RESIDENT_SHAPES(PN2_RESIDENT_FITS)
+#undef PN2_RESIDENT_FITS
     return false;
 }
 
-static size_t mlp_total_w(const MlpConfig &c) { return mlp_w_floats(c.t1, 1) + mlp_w_floats(c.t2, c.t1) + mlp_w_floats(c.t3, c.t2); }
-static size_t mlp_total_b(const MlpConfig &c) { return mlp_b_floats(c.t1) + mlp_b_floats(c.t2) + mlp_b_floats(c.t3); }
+// xyz_first: see pn2_sa_mlp3_pack (include/pn2ops.h); the kernel's channel order of layer 1 is [xyz, features]
+void mlp_resident_pack(const MlpResidentConfig &c, int cin, int c1, int c2, int c3, int xyz_first, const float *const *ws,
+                       const float *const *bs, float *wpacked, float *bpacked)
+{
+    const int cfeat = cin - 3;
+    const int kin[3] = {cin, c1, c2}, nout[3] = {c1, c2, c3};
+    const int tin[3] = {1, c.t1, c.t2}, tout[3] = {c.t1, c.t2, c.t3};
+    int krow[32];
+    for (int k = 0; k < 32; ++k) krow[k] = (!xyz_first && k < cin) ? (k < 3 ? cfeat + k : k - 3) : k;
+    float *wp = wpacked, *bp = bpacked;
+    for (int L = 0; L < 3; ++L) {
+        for (int t = 0; t < tout[L]; ++t)
+            for (int u = 0; u < tin[L]; ++u) wp = mlp_pack_pair_x6(wp, ws[L], kin[L], nout[L], t, u, L == 0 ? krow : nullptr);
+        bp = mlp_pack_bias(bp, bs[L], nout[L], tout[L]);
+    }
+}
 
 template <int T1, int T2, int T3>
 static int launch_mlp(int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz, const float *new_xyz,
                       const float *points, const int *idx, const float *wp, const float *bp, float *out, hipStream_t st, int variant,
                       int pooling = 0)
 {
-    const MlpConfig cfg = {T1, T2, T3};
-    const size_t lds = sizeof(float) * (mlp_total_w(cfg) + mlp_total_b(cfg));
+    const size_t lds = resident_lds_bytes({T1, T2, T3});
     if (lds > (size_t)kMlpMaxLds) return PN2_E_TOO_LARGE;
     const long long rows = (long long)b * m;
     const bool half = nsample == 16;
@@ -649,261 +627,45 @@ static int launch_mlp(int b, int n, int m, int nsample, int cfeat, int c3, const
     // ~8k items (metric shape 139 -> 131 us, cls_ssg SA1 36 -> 33), neutral below; four waves x two items is no faster than
     // one item per wave (142 us): kept for tests / A-B only
     if (variant == 0 && pair_ok && groups >= 8192) variant = 3;
+    // persistent (at most 256 workgroups): every workgroup stages the weights once, its waves share that copy
+    auto run = [&](auto kern, int threads, int items_per_wave) -> int {
+        const int per_block = threads / 64 * items_per_wave;
+        const long long blocks = (groups + per_block - 1) / per_block;
+        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+        return launch(kern, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(threads), lds, st, n, m, nsample, cfeat, c3, rows, xyz,
+                      new_xyz, points, idx, wp, bp, out);
+    };
     if (pooling != 0) {
         // avg / weighted_avg / max_and_avg (pointnet_util.py:130-140): one item per wave, eight waves (sa_mlp3_kernel<.., POOL>)
-        constexpr int NT = 512;
-        long long blocks = (groups + NT / 64 - 1) / (NT / 64);
-        if (blocks > 256) blocks = 256;
-#define PN2_POOL_CASE(P)                                                                                                      \
-        if (pooling == P) {                                                                                                   \
-            auto kern = half ? sa_mlp3_kernel<T1, T2, T3, 16, NT, P> : sa_mlp3_kernel<T1, T2, T3, 32, NT, P>;                 \
-            if (int rc = allow_dynamic_lds(kern, lds)) return rc;                                                             \
-            return launch(kern, dim3((unsigned)blocks), dim3(NT), lds, st, n, m, nsample, cfeat, c3, rows, xyz, new_xyz, points, \
-                          idx, wp, bp, out);                                                                                  \
-        }
+#define PN2_POOL_CASE(P) \
+        if (pooling == P) return run(half ? sa_mlp3_kernel<T1, T2, T3, 16, 512, P> : sa_mlp3_kernel<T1, T2, T3, 32, 512, P>, 512, 1);
         PN2_POOL_CASE(1) PN2_POOL_CASE(2) PN2_POOL_CASE(3)
 #undef PN2_POOL_CASE
         return PN2_E_ARG;
     }
     if (pair_ok && variant >= 2) {
         if constexpr (T2 <= 2) {
-          if (variant == 2) {                                           // four waves x two items
-            long long blocks = (groups + 7) / 8;
-            if (blocks > 256) blocks = 256;
-            auto kern = half ? sa_mlp3_pair_kernel<T1, T2, T3, 16, 256> : sa_mlp3_pair_kernel<T1, T2, T3, 32, 256>;
-            if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-            return launch(kern, dim3((unsigned)blocks), dim3(256), lds, st, n, m, nsample, cfeat, c3, rows, xyz, new_xyz, points, idx,
-                          wp, bp, out);
-          }
-          // eight waves x two items (fits 256 registers)
-            long long blocks = (groups + 15) / 16;
-            if (blocks > 256) blocks = 256;
-            auto kern = half ? sa_mlp3_pair_kernel<T1, T2, T3, 16, 512> : sa_mlp3_pair_kernel<T1, T2, T3, 32, 512>;
-            if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-            return launch(kern, dim3((unsigned)blocks), dim3(512), lds, st, n, m, nsample, cfeat, c3, rows, xyz, new_xyz, points, idx,
-                          wp, bp, out);
+            if (variant == 2)                                         // four waves x two items
+                return run(half ? sa_mlp3_pair_kernel<T1, T2, T3, 16, 256> : sa_mlp3_pair_kernel<T1, T2, T3, 32, 256>, 256, 2);
+            // eight waves x two items (fits 256 registers)
+            return run(half ? sa_mlp3_pair_kernel<T1, T2, T3, 16, 512> : sa_mlp3_pair_kernel<T1, T2, T3, 32, 512>, 512, 2);
         }
     }
-    // eight waves share one copy of the weights (two per SIMD: one wave's operand splitting overlaps the other's
-    // MFMAs) when a wave fits in 256 registers; persistent: every workgroup stages the weights once
-    constexpr int NT = 512;
-    long long blocks = (groups + NT / 64 - 1) / (NT / 64);
-    long long cap = 256;
-    if (blocks > cap) blocks = cap;
-    auto kern = half ? sa_mlp3_kernel<T1, T2, T3, 16, NT> : sa_mlp3_kernel<T1, T2, T3, 32, NT>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    if (int rc = launch(kern, dim3((unsigned)blocks), dim3(NT), lds, st, n, m, nsample, cfeat, c3, rows, xyz, new_xyz,
-                       points, idx, wp, bp, out)) return rc;
-    return PN2_OK;
+    // eight waves x one item (two waves per SIMD: one wave's operand splitting overlaps the other's MFMAs) when a wave fits
+    // in 256 registers
+    return run(half ? sa_mlp3_kernel<T1, T2, T3, 16, 512> : sa_mlp3_kernel<T1, T2, T3, 32, 512>, 512, 1);
 }
 
-// Which kernel runs a stack: the resident one when the input is narrow and the weights fit in LDS, the
-// streamed one (sa_mlp_stream.hip) up to widths (128,128,256), else the cooperative one (coop_mlp.hip: wide
-// stacks such as (256,256,512) and the group_all level's (256,512,1024); any nsample, masked).
-// kind: 0 resident, 1 streamed, 2 cooperative.
-static bool mlp_choose(int cin, int c1, int c2, int c3, int nsample, int &kind, MlpConfig &rc, MlpStreamConfig &sc,
-                       MlpCoopConfig &cc)
+int mlp_resident_launch(const MlpResidentConfig &c, int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz,
+                        const float *new_xyz, const float *points, const int *idx, const float *wp, const float *bp,
+                        float *out, hipStream_t st, int variant, int pooling)
 {
-    const bool whole = nsample == 16 || (nsample > 0 && nsample % 32 == 0);
-    if (whole && cin <= 32 && mlp_pick(c1, c2, c3, rc) &&
-        sizeof(float) * (mlp_total_w(rc) + mlp_total_b(rc)) <= (size_t)kMlpMaxLds) {
-        kind = 0;
-        return true;
-    }
-    if (whole && nsample != 16 && mlp_stream_pick(cin, c1, c2, c3, sc)) {
-        kind = 1;
-        return true;
-    }
-    const int widths[3] = {c1, c2, c3};
-    if (nsample > 0 && mlp_coop_pick(cin, 3, widths, cc) && mlp_coop_has_kernel(cc, 0)) {
-        kind = 2;
-        return true;
-    }
-    return false;
+#define PN2_RESIDENT_LAUNCH(A, B, C)                 \
+    if (c.t1 == A && c.t2 == B && c.t3 == C)         \
+        return launch_mlp<A, B, C>(b, n, m, nsample, cfeat, c3, xyz, new_xyz, points, idx, wp, bp, out, st, variant, pooling);
+    PN2_RESIDENT_SHAPES(PN2_RESIDENT_LAUNCH)
+#undef PN2_RESIDENT_LAUNCH
+    return PN2_E_TOO_LARGE;
 }
 
 }  // namespace pn2
-
-extern "C" int pn2_sa_mlp3_config(int cin, int c1, int c2, int c3, int nsample, int *info4, long long *w_floats,
-                                  long long *b_floats)
-{
-    using namespace pn2;
-    if (cin < 3 || c1 <= 0 || c2 <= 0 || c3 <= 0) return PN2_E_ARG;
-    if (nsample <= 0) return PN2_E_ARG;
-    int kind;
-    MlpConfig rc;
-    MlpStreamConfig sc;
-    MlpCoopConfig cc;
-    if (!mlp_choose(cin, c1, c2, c3, nsample, kind, rc, sc, cc)) return PN2_E_TOO_LARGE;
-    if (info4) {
-        info4[0] = kind;
-        info4[1] = kind == 2 ? 4 * cc.q1 : kind ? sc.t1 : rc.t1;
-        info4[2] = kind == 2 ? 4 * cc.q2 : kind ? sc.t2 : rc.t2;
-        info4[3] = kind == 2 ? 4 * cc.q3 : kind ? sc.t3 : rc.t3;
-    }
-    if (w_floats) *w_floats = (long long)(kind == 2 ? mlp_coop_w_floats(cc) : kind ? mlp_stream_w_floats(sc) : mlp_total_w(rc));
-    if (b_floats) *b_floats = (long long)(kind == 2 ? mlp_coop_b_floats(cc) : kind ? mlp_stream_b_floats(sc) : mlp_total_b(rc));
-    return PN2_OK;
-}
-
-// Host-side packing (plain C loops, no device work): w_i is (cin_i, cout_i) row-major -- the layout of
-// the reference's conv kernel [1,1,cin,cout] (tf_util.py:113-117) -- with batch norm already folded in.
-// xyz_first: rows of w1 are [xyz (3), features] (pointnet_util.py:50, single-scale modules) or
-// [features, xyz (3)] (:184, the MSG module).
-extern "C" int pn2_sa_mlp3_pack(int cin, int c1, int c2, int c3, int nsample, int xyz_first, const float *w1,
-                                const float *bias1, const float *w2, const float *bias2, const float *w3,
-                                const float *bias3, float *wpacked, float *bpacked)
-{
-    using namespace pn2;
-    int kind;
-    MlpConfig cfg;
-    MlpStreamConfig sc;
-    MlpCoopConfig cc;
-    if (cin < 3 || c1 <= 0 || c2 <= 0 || c3 <= 0 || !mlp_choose(cin, c1, c2, c3, nsample, kind, cfg, sc, cc)) return PN2_E_TOO_LARGE;
-    if (!w1 || !w2 || !w3 || !bias1 || !bias2 || !bias3 || !wpacked || !bpacked) return PN2_E_NULL;
-    const float *ws[3] = {w1, w2, w3}, *bs[3] = {bias1, bias2, bias3};
-    if (kind == 1) {
-        mlp_stream_pack(sc, cin, c1, c2, c3, xyz_first, ws, bs, wpacked, bpacked);
-        return PN2_OK;
-    }
-    if (kind == 2) {
-        // kernel channel order of layer 1: [features, xyz]; caller's weight rows: [xyz, features] when xyz_first
-        const int cf = cin - 3, widths[3] = {c1, c2, c3};
-        int *krow = (int *)malloc(sizeof(int) * (size_t)cin);
-        for (int k = 0; k < cin; ++k) krow[k] = xyz_first ? (k < cf ? 3 + k : k - cf) : k;
-        mlp_coop_pack(cc, cin, 3, widths, krow, ws, bs, wpacked, bpacked, true);
-        free(krow);
-        return PN2_OK;
-    }
-    const int cfeat = cin - 3;
-    const int kin[3] = {cin, c1, c2}, nout[3] = {c1, c2, c3};
-    const int tin[3] = {1, cfg.t1, cfg.t2}, tout[3] = {cfg.t1, cfg.t2, cfg.t3};
-    float *wp = wpacked, *bp = bpacked;
-    for (int L = 0; L < 3; ++L) {
-        // kernel channel order of layer 1: [xyz, features]
-        int krow[32];
-        for (int k = 0; k < 32; ++k) krow[k] = (L == 0 && !xyz_first && k < cin) ? (k < 3 ? cfeat + k : k - 3) : k;
-        for (int t = 0; t < tout[L]; ++t)
-            for (int u = 0; u < tin[L]; ++u) wp = mlp_pack_pair_x6(wp, ws[L], kin[L], nout[L], t, u, L == 0 ? krow : nullptr);
-        for (int t = 0; t < tout[L]; ++t)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int v = 0; v < 16; ++v) {
-                    const int ch = 32 * t + mlp_chan(v, hh);
-                    *bp++ = ch < nout[L] ? bs[L][ch] : 0.0f;
-                }
-    }
-    return PN2_OK;
-}
-
-// Scratch pn2_sa_mlp3_maxpool needs for this call: the streamed kernel keeps the per-point part of layer 1 there
-// (b * n rows of the padded first width); stacks with a last layer wider than 512 (the group_all level) keep the
-// second layer's output there, in operand form, for the GEMM that runs the last layer; 0 otherwise.
-extern "C" long long pn2_sa_mlp3_ws_bytes(int b, int n, int m, int cin, int c1, int c2, int c3, int nsample)
-{
-    using namespace pn2;
-    int kind;
-    MlpConfig rc;
-    MlpStreamConfig sc;
-    MlpCoopConfig cc;
-    if (b <= 0 || n <= 0 || m <= 0 || cin < 3 || c1 <= 0 || c2 <= 0 || c3 <= 0 || nsample <= 0) return 0;
-    if (!mlp_choose(cin, c1, c2, c3, nsample, kind, rc, sc, cc)) return 0;
-    if (kind == 1) return (long long)mlp_stream_ws_bytes(sc, (long long)b * n);
-    if (kind == 2) return (long long)mlp_coop_ws_bytes(cc, 0, (long long)b * m, nsample);
-    return 0;
-}
-
-extern "C" int pn2_sa_mlp3_maxpool(int b, int n, int m, int nsample, int cfeat, const float *xyz, const float *new_xyz,
-                                   const float *points, const int *idx, int c1, int c2, int c3, const float *wpacked,
-                                   const float *bpacked, float *out, void *ws, void *stream)
-{
-    return pn2_sa_mlp3_maxpool_ex(b, n, m, nsample, cfeat, xyz, new_xyz, points, idx, c1, c2, c3, wpacked, bpacked, out, ws, 0, stream);
-}
-
-// pn2_sa_mlp3_maxpool with the reference's other pooling modes (utils/pointnet_util.py:128-140). pooling: 0 max, 1 avg,
-// 2 weighted_avg, 3 max_and_avg (out is (b, m, 2 c3): [avg, max], the reference's concat order :142). Modes 1-3 exist for the
-// stacks the RESIDENT and the STREAMED kernel cover (pn2_sa_mlp3_config kind 0 / 1: widths up to (128, 128, 256), nsample 16 or
-// a multiple of 32; ws as for pn2_sa_mlp3_maxpool) -- the cooperative kernel's shapes return PN2_E_TOO_LARGE and the caller
-// evaluates the level layer by layer.
-extern "C" int pn2_sa_mlp3_pool_supported(int cin, int c1, int c2, int c3, int nsample, int pooling)
-{
-    using namespace pn2;
-    if (pooling < 0 || pooling > 3 || cin < 3 || c1 <= 0 || c2 <= 0 || c3 <= 0 || nsample <= 0) return 0;
-    int kind;
-    MlpConfig rc;
-    MlpStreamConfig sc;
-    MlpCoopConfig cc;
-    if (!mlp_choose(cin, c1, c2, c3, nsample, kind, rc, sc, cc)) return 0;
-    return pooling == 0 || kind != 2;
-}
-
-extern "C" int pn2_sa_mlp3_pool(int b, int n, int m, int nsample, int cfeat, const float *xyz, const float *new_xyz,
-                                const float *points, const int *idx, int c1, int c2, int c3, const float *wpacked,
-                                const float *bpacked, int pooling, float *out, void *ws, void *stream)
-{
-    using namespace pn2;
-    if (pooling < 0 || pooling > 3) return PN2_E_ARG;
-    if (pooling == 0)
-        return pn2_sa_mlp3_maxpool_ex(b, n, m, nsample, cfeat, xyz, new_xyz, points, idx, c1, c2, c3, wpacked, bpacked, out, ws, 0, stream);
-    if (b < 0 || n <= 0 || m < 0 || cfeat < 0) return PN2_E_SHAPE;
-    if (nsample <= 0) return PN2_E_ARG;
-    if (b == 0 || m == 0) return PN2_OK;
-    if (!xyz || !new_xyz || !idx || !wpacked || !bpacked || !out || (cfeat > 0 && !points)) return PN2_E_NULL;
-    int kind;
-    MlpConfig cfg;
-    MlpStreamConfig sc;
-    MlpCoopConfig cc;
-    if (!mlp_choose(3 + cfeat, c1, c2, c3, nsample, kind, cfg, sc, cc) || kind == 2) return PN2_E_TOO_LARGE;
-    hipStream_t st = as_stream(stream);
-    const float *pts = cfeat > 0 ? points : nullptr;
-    if (kind == 1)
-        return mlp_stream_launch(sc, b, n, m, nsample, cfeat, c3, xyz, new_xyz, pts ? pts : xyz, idx, wpacked, bpacked, out, ws, st, pooling);
-#define PN2_MLP_CASE(A, B, C) \
-    if (cfg.t1 == A && cfg.t2 == B && cfg.t3 == C) \
-        return launch_mlp<A, B, C>(b, n, m, nsample, cfeat, c3, xyz, new_xyz, pts, idx, wpacked, bpacked, out, st, 1, pooling)
-    PN2_MLP_CASE(1, 1, 2);
-    PN2_MLP_CASE(2, 2, 4);
-    PN2_MLP_CASE(2, 3, 4);
-#undef PN2_MLP_CASE
-    return PN2_E_TOO_LARGE;
-}
-
-// variant: the organisation of the resident kernel -- 0: by the size rule, 1: one item per wave, 2 / 3: two items per wave
-// (four / eight waves per workgroup) wherever that kernel covers the shape (results are bit-identical; tests and A/B timing)
-extern "C" int pn2_sa_mlp3_maxpool_ex(int b, int n, int m, int nsample, int cfeat, const float *xyz, const float *new_xyz,
-                                      const float *points, const int *idx, int c1, int c2, int c3, const float *wpacked,
-                                      const float *bpacked, float *out, void *ws, int variant, void *stream)
-{
-    using namespace pn2;
-    if (variant < 0 || variant > 3) return PN2_E_ARG;
-    if (b < 0 || n <= 0 || m < 0 || cfeat < 0) return PN2_E_SHAPE;
-    if (nsample <= 0) return PN2_E_ARG;
-    if (b == 0 || m == 0) return PN2_OK;
-    // idx == NULL and new_xyz == NULL together: the group_all level (sample_and_group_all, pointnet_util.py:59-84):
-    // m = 1, the group is the whole cloud in index order (nsample = n), no centroid subtraction
-    const bool group_all = !idx && !new_xyz;
-    if (group_all && (m != 1 || nsample != n)) return PN2_E_ARG;
-    if (!xyz || (!group_all && (!new_xyz || !idx)) || !wpacked || !bpacked || !out || (cfeat > 0 && !points)) return PN2_E_NULL;
-    int kind;
-    MlpConfig cfg;
-    MlpStreamConfig sc;
-    MlpCoopConfig cc;
-    if (!mlp_choose(3 + cfeat, c1, c2, c3, nsample, kind, cfg, sc, cc)) return PN2_E_TOO_LARGE;
-    if (group_all && kind != 2) return PN2_E_TOO_LARGE;           // only the cooperative kernel gathers without idx
-    hipStream_t st = as_stream(stream);
-    const float *pts = cfeat > 0 ? points : nullptr;
-    if (kind == 2) {
-        CoopParams p = {n, m, nsample, cfeat, 0, c3, cc.ti, (long long)b * m, xyz, new_xyz, pts, nullptr, idx, nullptr,
-                        wpacked, bpacked, out, 0};
-        return mlp_coop_launch(cc, 0, p, st, ws);
-    }
-    if (kind == 1)
-        return mlp_stream_launch(sc, b, n, m, nsample, cfeat, c3, xyz, new_xyz, pts ? pts : xyz, idx, wpacked, bpacked, out, ws, st);
-#define PN2_MLP_CASE(A, B, C) \
-    if (cfg.t1 == A && cfg.t2 == B && cfg.t3 == C) \
-        return launch_mlp<A, B, C>(b, n, m, nsample, cfeat, c3, xyz, new_xyz, pts, idx, wpacked, bpacked, out, st, variant)
-    PN2_MLP_CASE(1, 1, 2);
-    PN2_MLP_CASE(2, 2, 4);
-    PN2_MLP_CASE(2, 3, 4);
-#undef PN2_MLP_CASE
-    return PN2_E_TOO_LARGE;
-}

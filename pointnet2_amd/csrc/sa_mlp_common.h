@@ -1,6 +1,7 @@
 // sa_mlp_common.h -- helpers shared by the fused-MLP kernels (sa_mlp.hip: weights resident in LDS; sa_mlp_stream.hip:
 // weights streamed through LDS + the per-point layers; coop_mlp.hip: four waves per item + the last-layer GEMM;
-// fp_mlp.hip: feature propagation). See sa_mlp.hip for the formulation and the arithmetic.
+// fp_mlp.hip: feature propagation), and the host interface of each family (packers: mlp_pack.hip; plans and C entry
+// points: mlp_entry.hip). See sa_mlp.hip for the formulation and the arithmetic.
 #pragma once
 #include "pn2_device.h"
 
@@ -106,11 +107,27 @@ __device__ __forceinline__ f32x16 mma_x6(const u32x4 (&w)[3], const u32x4 (&x)[3
     return acc;
 }
 
-// host side: the three bf16 levels of one weight
-void mlp_split_weight(float w, unsigned short out[3]);
-// one 32x32 tile pair of a (kin, nout) row-major weight matrix in the split operand layout (kPairWords words)
+// ---- host side: packing (mlp_pack.hip) ----------------------------------------------------------------
+// one 32x32 tile pair of a (kin, nout) row-major weight matrix in the split operand layout (kPairWords words); krow:
+// kernel channel -> caller's weight row, or nullptr
 float *mlp_pack_pair_x6(float *wp, const float *w, int kin, int nout, int t, int u, const int *krow);
+// `tiles` output tiles of a layer's bias in operand order [t][h][v] (channel 32t + mlp_chan(v, h)); channels from nout
+// on are zero, bias == nullptr: all of them
+float *mlp_pack_bias(float *bp, const float *bias, int nout, int tiles);
+// zero pairs behind `pairs` pairs of a stream, up to a whole stage (pad_to_stage below)
+float *mlp_pack_stage_padding(float *wp, int pairs);
 
+// ---- resident variant (sa_mlp.hip): all three layers' weights stay in LDS --------------------------------
+struct MlpResidentConfig { int t1, t2, t3; };           // 32-channel output tiles of the three layers; one input tile
+bool mlp_resident_pick(int cin, int c1, int c2, int c3, MlpResidentConfig &cfg);
+size_t mlp_resident_w_floats(const MlpResidentConfig &c);
+size_t mlp_resident_b_floats(const MlpResidentConfig &c);
+void mlp_resident_pack(const MlpResidentConfig &c, int cin, int c1, int c2, int c3, int xyz_first, const float *const *ws,
+                       const float *const *bs, float *wpacked, float *bpacked);
+// variant: 0 by the size rule, 1 one item per wave, 2 / 3 two items per wave (four / eight waves per workgroup)
+int mlp_resident_launch(const MlpResidentConfig &c, int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz,
+                        const float *new_xyz, const float *points, const int *idx, const float *wp, const float *bp,
+                        float *out, hipStream_t st, int variant, int pooling = 0);
 
 // ---- streamed variant (sa_mlp_stream.hip) ------------------------------------------------------------
 constexpr int kMlpStagePairs = 4;          // 32x32 weight tile pairs per LDS stage (24 KiB in three-level form)
@@ -175,8 +192,17 @@ size_t mlp_coop_w_floats(const MlpCoopConfig &c);
 size_t mlp_coop_b_floats(const MlpCoopConfig &c);
 void mlp_coop_pack(const MlpCoopConfig &c, int cin, int nlayers, const int *widths, const int *krow, const float *const *ws,
                    const float *const *bs, float *wpacked, float *bpacked, bool krow_is_grouped);
-bool mlp_coop_gemm_last(const MlpCoopConfig &c, int fp);
 size_t mlp_coop_ws_bytes(const MlpCoopConfig &c, int fp, long long rows, int nsample);
 int mlp_coop_launch(const MlpCoopConfig &c, int fp, const CoopParams &p, hipStream_t st, void *ws);
+
+// ---- feature propagation, one wave per 32 points (fp_mlp.hip) ---------------------------------------------
+struct FpConfig { int ti, tif, t1, t2, t3; };        // ti: tiles of skip channels (c1), tif: tiles of known features (c2)
+bool fp_stream_pick(int c2, int c1, int nlayers, const int *widths, FpConfig &cfg);
+size_t fp_stream_w_floats(const FpConfig &c);        // this kernel's own stream and biases; the per-point kernel's follow
+size_t fp_stream_b_floats(const FpConfig &c);
+void fp_stream_pack(const FpConfig &c, int c1, int nlayers, const int *widths, const int *skip_row, const float *const *ws,
+                    const float *const *bs, float *wpacked, float *bpacked);
+int fp_stream_launch(const FpConfig &c, long long rows, int n, int m, int c1, int cout, const float *pre, const float *points1,
+                     const int *idx, const float *dist, const float *wp, const float *bp, float *out, hipStream_t st);
 
 }  // namespace pn2

@@ -411,15 +411,19 @@ __global__ __launch_bounds__(kStreamThreads) void sa_mlp3_stream_kernel(int n, i
 #undef PN2_STREAM_COMMIT
 #undef PN2_NEXT_STAGE
 
+// the instantiated tile shapes, smallest first: X(t1, t2, t3)
+#define PN2_STREAM_SHAPES(X) X(2, 2, 4) X(4, 4, 8)
+
 bool mlp_stream_pick(int cin, int c1, int c2, int c3, MlpStreamConfig &cfg)
 {
-    static const int kShapes[][3] = {{2, 2, 4}, {4, 4, 8}};
     if (cin < 3 || cin > 32 * 12) return false;
-    for (const auto &sh : kShapes)
-        if (c1 <= 32 * sh[0] && c2 <= 32 * sh[1] && c3 <= 32 * sh[2]) {
-            cfg = {(cin - 3 + 31) / 32, sh[0], sh[1], sh[2]};          // ti: tiles of FEATURE channels (the per-point layer)
-            return true;
-        }
+#define PN2_STREAM_FITS(A, B, C)                                                                                       \
+    if (c1 <= 32 * A && c2 <= 32 * B && c3 <= 32 * C) {                                                                \
+        cfg = {(cin - 3 + 31) / 32, A, B, C};              /* ti: tiles of FEATURE channels (the per-point layer) */    \
+        return true;                                                                                                   \
+    }
+    PN2_STREAM_SHAPES(PN2_STREAM_FITS)
+#undef PN2_STREAM_FITS
     return false;
 }
 
@@ -449,8 +453,7 @@ void mlp_stream_pack(const MlpStreamConfig &c, int cin, int c1, int c2, int c3, 
         for (int u = 0; u < c.t2; ++u) wp = mlp_pack_pair_x6(wp, ws[2], c2, c3, t, u, nullptr);
     for (int u = 0; u < c.ti; ++u)                        // the per-point layer: feature tiles outermost
         for (int t = 0; t < c.t1; ++t) wp = mlp_pack_pair_x6(wp, ws[0], cfeat, c1, t, u, frow);
-    for (int i = c.ti * c.t1; i < pad_to_stage(c.ti * c.t1); ++i)
-        for (int j = 0; j < kPairWords; ++j) *wp++ = 0.0f;
+    wp = mlp_pack_stage_padding(wp, c.ti * c.t1);
     float *tmp = (float *)malloc(sizeof(float) * kPairWords);
     for (int t = 0; t < c.t1; ++t) {                      // xyz rows: channels 0-2 live in K16 step 0 of input tile 0
         mlp_pack_pair_x6(tmp, ws[0], 3, c1, t, 0, xrow);
@@ -461,13 +464,7 @@ void mlp_stream_pack(const MlpStreamConfig &c, int cin, int c1, int c2, int c3, 
     free(frow);
     const int nout[3] = {c1, c2, c3}, tout[3] = {c.t1, c.t2, c.t3};
     float *bp = bpacked;
-    for (int L = 0; L < 3; ++L)
-        for (int t = 0; t < tout[L]; ++t)
-            for (int hh = 0; hh < 2; ++hh)
-                for (int v = 0; v < 16; ++v) {
-                    const int ch = 32 * t + mlp_chan(v, hh);
-                    *bp++ = ch < nout[L] ? bs[L][ch] : 0.0f;
-                }
+    for (int L = 0; L < 3; ++L) bp = mlp_pack_bias(bp, bs[L], nout[L], tout[L]);
 }
 
 // pre (rows, out_stride)[:, col0 : col0 + 32 t1] = points (rows, cfeat) . W + bias; t1 = 2 or 4 output tiles
@@ -539,10 +536,11 @@ int mlp_stream_launch(const MlpStreamConfig &c, int b, int n, int m, int nsample
 {
     if (nsample <= 0 || nsample % 32 != 0) return PN2_E_ARG;
     if (!ws) return PN2_E_NULL;
-    if (c.t1 == 2 && c.t2 == 2 && c.t3 == 4)
-        return launch_stream<2, 2, 4>(c, b, n, m, nsample, cfeat, c3, xyz, new_xyz, points, idx, wp, bp, out, (float *)ws, st, pooling);
-    if (c.t1 == 4 && c.t2 == 4 && c.t3 == 8)
-        return launch_stream<4, 4, 8>(c, b, n, m, nsample, cfeat, c3, xyz, new_xyz, points, idx, wp, bp, out, (float *)ws, st, pooling);
+#define PN2_STREAM_LAUNCH(A, B, C)                   \
+    if (c.t1 == A && c.t2 == B && c.t3 == C)         \
+        return launch_stream<A, B, C>(c, b, n, m, nsample, cfeat, c3, xyz, new_xyz, points, idx, wp, bp, out, (float *)ws, st, pooling);
+    PN2_STREAM_SHAPES(PN2_STREAM_LAUNCH)
+#undef PN2_STREAM_LAUNCH
     return PN2_E_TOO_LARGE;
 }
 

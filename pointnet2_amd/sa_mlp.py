@@ -37,12 +37,7 @@ def fold_batch_norm(conv_weight, conv_bias, bn=None):
     return w.float().cpu().numpy(), b.float().cpu().numpy()
 
 
-def supported(cin, widths, nsample):
-    """Can pn2_sa_mlp3_maxpool run this layer stack? (host-only check, needs the built library)"""
-    if len(widths) != 3 or cin < 3 or nsample is None or nsample <= 0:
-        return False
-    return _C.lib().pn2_sa_mlp3_config(int(cin), int(widths[0]), int(widths[1]), int(widths[2]), int(nsample), None, None,
-                                       None) == 0
+KINDS = ("resident", "streamed", "cooperative")          # pn2_sa_mlp3_config's info4[0]
 
 
 def kind(cin, widths, nsample):
@@ -51,7 +46,12 @@ def kind(cin, widths, nsample):
     if len(widths) != 3 or _C.lib().pn2_sa_mlp3_config(int(cin), int(widths[0]), int(widths[1]), int(widths[2]), int(nsample), info,
                                                         None, None) != 0:
         return None
-    return ("resident", "streamed", "cooperative")[info[0]]
+    return KINDS[info[0]]
+
+
+def supported(cin, widths, nsample):
+    """Can pn2_sa_mlp3_maxpool run this layer stack? (host-only check, needs the built library)"""
+    return nsample is not None and kind(cin, widths, nsample) is not None
 
 
 class PackedMLP3:
@@ -73,7 +73,7 @@ class PackedMLP3:
         info = (ctypes.c_int * 4)()
         _C.check(lib.pn2_sa_mlp3_config(self.cin, *self.widths, self.nsample, info, ctypes.byref(wf), ctypes.byref(bf)),
                  "sa_mlp3_config")
-        self.kind = ("resident", "streamed", "cooperative")[info[0]]
+        self.kind = KINDS[info[0]]
         wp = np.empty(wf.value, np.float32)
         bp = np.empty(bf.value, np.float32)
         _C.check(lib.pn2_sa_mlp3_pack(self.cin, *self.widths, self.nsample, 1 if xyz_first else 0, ws[0].ctypes.data,
@@ -86,53 +86,28 @@ class PackedMLP3:
 
 def _same_kernel(packed, ns):
     """Would pn2_sa_mlp3_config choose the same kernel (hence the same packed layout) for this nsample?"""
-    info = (ctypes.c_int * 4)()
-    if _C.lib().pn2_sa_mlp3_config(packed.cin, *packed.widths, int(ns), info, None, None) != 0:
-        return False
-    return ("resident", "streamed", "cooperative")[info[0]] == packed.kind
+    return kind(packed.cin, packed.widths, ns) == packed.kind
 
 
-def sa_mlp_maxpool(xyz, new_xyz, points, idx, packed):
-    """xyz (b,n,3), new_xyz (b,m,3), points (b,n,c) or None, idx (b,m,nsample) i32, packed: PackedMLP3
-    -> (b, m, c3) f32 = max over nsample of the three-layer MLP of [xyz[idx]-new_xyz, points[idx]].
-    new_xyz is None and idx is None: the group_all level (sample_and_group_all, pointnet_util.py:59-84) ->
-    (b, 1, c3) = max over all n points of the MLP of [xyz, points] (no centroid)."""
+def _level_inputs(xyz, points, packed):
+    """xyz (b,n,3) and points (b,n,c) or None of a level as float32 tensors, checked against the packed stack
+    -> xyz, points, b, n, cfeat."""
     xyz = f32(xyz, "xyz")
+    require(xyz.dim() == 3 and xyz.shape[2] == 3, "xyz must be (b, n, 3)")
     b, n, _ = xyz.shape
-    if idx is None and new_xyz is None:
-        m, ns = 1, n
-    else:
-        new_xyz, idx = f32(new_xyz, "new_xyz"), i32(idx, "idx")
-        m, ns = idx.shape[1], idx.shape[2]
     cfeat = 0
     if points is not None:
         points = f32(points, "points")
+        require(points.dim() == 3 and tuple(points.shape[:2]) == (b, n), "points must be (b, n, c) like xyz")
         cfeat = points.shape[2]
     require(3 + cfeat == packed.cin, "packed MLP expects %d input channels, got %d" % (packed.cin, 3 + cfeat))
-    require(xyz.dim() == 3 and xyz.shape[2] == 3, "xyz must be (b, n, 3)")
-    if idx is not None:
-        require(new_xyz.dim() == 3 and tuple(new_xyz.shape) == (b, m, 3), "new_xyz must be (b, m, 3) with idx (b, m, nsample)")
-        require(idx.dim() == 3 and idx.shape[0] == b, "idx must be (b, m, nsample)")
-    if points is not None:
-        require(points.dim() == 3 and tuple(points.shape[:2]) == (b, n), "points must be (b, n, c) like xyz")
-    # the packed layout belongs to the kernel pn2_sa_mlp3_config chose for packed.nsample; another nsample
-    # is fine as long as the library would choose the same kernel for it
-    require(ns == packed.nsample or _same_kernel(packed, ns),
-            "weights were packed for nsample=%d (%s kernel); nsample=%d needs a different layout"
-            % (packed.nsample, packed.kind, ns))
-    tensors = [t for t in (xyz, new_xyz, idx, points, packed.wp) if t is not None]
-    dev = same_device(*tensors)
-    out = torch.empty((b, m, packed.widths[2]), dtype=torch.float32, device=dev)
-    ws = None                                      # scratch is the caller's (per-point layer 1 / input of the last-layer GEMM)
-    nbytes = _C.lib().pn2_sa_mlp3_ws_bytes(b, n, m, packed.cin, packed.widths[0], packed.widths[1], packed.widths[2], ns)
-    if nbytes:
-        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev)
-    with on_device(dev):
-        _C.check(_C.lib().pn2_sa_mlp3_maxpool_ex(b, n, m, ns, cfeat, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx),
-                                                 packed.widths[0], packed.widths[1], packed.widths[2], ptr(packed.wp),
-                                                 ptr(packed.bp), ptr(out), ptr(ws), _RESIDENT_VARIANT, stream_ptr(dev)),
-                 "sa_mlp3_maxpool")
-    return out
+    return xyz, points, b, n, cfeat
+
+
+def _scratch(lib, packed, b, n, m, ns, dev):
+    """The caller's scratch of a call (per-point layer 1 / input of the last-layer GEMM), or None."""
+    nbytes = lib.pn2_sa_mlp3_ws_bytes(b, n, m, packed.cin, packed.widths[0], packed.widths[1], packed.widths[2], ns)
+    return torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev) if nbytes else None
 
 
 POOLING = {"max": 0, "avg": 1, "weighted_avg": 2, "max_and_avg": 3}    # pn2_sa_mlp3_pool's codes (pointnet_util.py:128-140)
@@ -147,38 +122,53 @@ def pool_supported(cin, widths, nsample, pooling):
                                                     POOLING[pooling]))
 
 
+def _pooled_mlp(xyz, new_xyz, points, idx, packed, pooling):
+    """The one body of sa_mlp_maxpool ("max": the only mode with the group_all form and set_resident_variant) and sa_mlp_pool."""
+    xyz, points, b, n, cfeat = _level_inputs(xyz, points, packed)
+    if pooling == "max" and idx is None and new_xyz is None:
+        m, ns = 1, n
+    else:
+        new_xyz, idx = f32(new_xyz, "new_xyz"), i32(idx, "idx")
+        m, ns = idx.shape[1], idx.shape[2]
+        require(new_xyz.dim() == 3 and tuple(new_xyz.shape) == (b, m, 3), "new_xyz must be (b, m, 3) with idx (b, m, nsample)")
+        require(idx.dim() == 3 and idx.shape[0] == b, "idx must be (b, m, nsample)")
+    # the packed layout belongs to the kernel pn2_sa_mlp3_config chose for packed.nsample; another nsample
+    # is fine as long as the library would choose the same kernel for it
+    require(ns == packed.nsample or _same_kernel(packed, ns),
+            "weights were packed for nsample=%d (%s kernel); nsample=%d needs a different layout"
+            % (packed.nsample, packed.kind, ns))
+    if pooling != "max":
+        require(pool_supported(packed.cin, packed.widths, ns, pooling), "no fused kernel for pooling=%r on this stack" % (pooling,))
+    dev = same_device(*[t for t in (xyz, new_xyz, idx, points, packed.wp) if t is not None])
+    c1, c2, c3 = packed.widths
+    out = torch.empty((b, m, 2 * c3 if pooling == "max_and_avg" else c3), dtype=torch.float32, device=dev)
+    lib = _C.lib()
+    ws = _scratch(lib, packed, b, n, m, ns, dev)
+    with on_device(dev):
+        if pooling == "max":
+            _C.check(lib.pn2_sa_mlp3_maxpool_ex(b, n, m, ns, cfeat, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx), c1, c2, c3,
+                                                ptr(packed.wp), ptr(packed.bp), ptr(out), ptr(ws), _RESIDENT_VARIANT,
+                                                stream_ptr(dev)), "sa_mlp3_maxpool")
+        else:
+            _C.check(lib.pn2_sa_mlp3_pool(b, n, m, ns, cfeat, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx), c1, c2, c3,
+                                          ptr(packed.wp), ptr(packed.bp), POOLING[pooling], ptr(out), ptr(ws), stream_ptr(dev)),
+                     "sa_mlp3_pool")
+    return out
+
+
+def sa_mlp_maxpool(xyz, new_xyz, points, idx, packed):
+    """xyz (b,n,3), new_xyz (b,m,3), points (b,n,c) or None, idx (b,m,nsample) i32, packed: PackedMLP3
+    -> (b, m, c3) f32 = max over nsample of the three-layer MLP of [xyz[idx]-new_xyz, points[idx]].
+    new_xyz is None and idx is None: the group_all level (sample_and_group_all, pointnet_util.py:59-84) ->
+    (b, 1, c3) = max over all n points of the MLP of [xyz, points] (no centroid)."""
+    return _pooled_mlp(xyz, new_xyz, points, idx, packed, "max")
+
+
 def sa_mlp_pool(xyz, new_xyz, points, idx, packed, pooling):
     """sa_mlp_maxpool with the reference's other pooling modes (pointnet_util.py:128-140): "avg", "weighted_avg" ->
     (b, m, c3); "max_and_avg" -> (b, m, 2 c3) = [avg, max]; "max" = sa_mlp_maxpool."""
-    if pooling == "max":
-        return sa_mlp_maxpool(xyz, new_xyz, points, idx, packed)
     require(pooling in POOLING, "unknown pooling %r" % (pooling,))
-    xyz, new_xyz, idx = f32(xyz, "xyz"), f32(new_xyz, "new_xyz"), i32(idx, "idx")
-    b, n, _ = xyz.shape
-    m, ns = idx.shape[1], idx.shape[2]
-    cfeat = 0
-    if points is not None:
-        points = f32(points, "points")
-        cfeat = points.shape[2]
-        require(points.dim() == 3 and tuple(points.shape[:2]) == (b, n), "points must be (b, n, c) like xyz")
-    require(3 + cfeat == packed.cin, "packed MLP expects %d input channels, got %d" % (packed.cin, 3 + cfeat))
-    require(xyz.dim() == 3 and xyz.shape[2] == 3, "xyz must be (b, n, 3)")
-    require(tuple(new_xyz.shape) == (b, m, 3) and idx.dim() == 3 and idx.shape[0] == b, "new_xyz must be (b, m, 3) with idx (b, m, nsample)")
-    require(ns == packed.nsample or _same_kernel(packed, ns),
-            "weights were packed for nsample=%d (%s kernel); nsample=%d needs a different layout" % (packed.nsample, packed.kind, ns))
-    require(pool_supported(packed.cin, packed.widths, ns, pooling), "no fused kernel for pooling=%r on this stack" % (pooling,))
-    dev = same_device(*[t for t in (xyz, new_xyz, idx, points, packed.wp) if t is not None])
-    c3 = packed.widths[2]
-    out = torch.empty((b, m, 2 * c3 if pooling == "max_and_avg" else c3), dtype=torch.float32, device=dev)
-    ws = None
-    nbytes = _C.lib().pn2_sa_mlp3_ws_bytes(b, n, m, packed.cin, packed.widths[0], packed.widths[1], c3, ns)
-    if nbytes:
-        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev)
-    with on_device(dev):
-        _C.check(_C.lib().pn2_sa_mlp3_pool(b, n, m, ns, cfeat, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx), packed.widths[0],
-                                           packed.widths[1], c3, ptr(packed.wp), ptr(packed.bp), POOLING[pooling], ptr(out), ptr(ws),
-                                           stream_ptr(dev)), "sa_mlp3_pool")
-    return out
+    return _pooled_mlp(xyz, new_xyz, points, idx, packed, pooling)
 
 
 # ---- feature propagation: three_nn weights + three_interpolate + concat + MLP in one kernel ------------------
@@ -281,18 +271,10 @@ def sa_level(npoint, radius, nsample, xyz, points, packed, buffers=None, ordered
     from . import tf_sampling as TS
     if ordered is None:
         ordered = isinstance(xyz, torch.Tensor) and TS.ordered_hint(xyz, int(npoint))
-    xyz = f32(xyz, "xyz")
-    require(xyz.dim() == 3 and xyz.shape[2] == 3, "xyz must be (b, n, 3)")
-    b, n, _ = xyz.shape
+    xyz, points, b, n, cfeat = _level_inputs(xyz, points, packed)
     m, ns = int(npoint), int(nsample)
     require(m > 0 and ns > 0 and float(radius) > 0, "npoint, nsample and radius must be positive")
     require(b > 0, "sa_level: empty batch")                # (PointnetSAModule sends b == 0 through the operator path)
-    cfeat = 0
-    if points is not None:
-        points = f32(points, "points")
-        require(points.dim() == 3 and tuple(points.shape[:2]) == (b, n), "points must be (b, n, c) like xyz")
-        cfeat = points.shape[2]
-    require(3 + cfeat == packed.cin, "packed MLP expects %d input channels, got %d" % (packed.cin, 3 + cfeat))
     require(ns == packed.nsample or _same_kernel(packed, ns), "weights were packed for another kernel (nsample %d)" % packed.nsample)
     dev = same_device(xyz, packed.wp) if points is None else same_device(xyz, points, packed.wp)
     lib = _C.lib()
@@ -306,8 +288,7 @@ def sa_level(npoint, radius, nsample, xyz, points, packed, buffers=None, ordered
         cnt = torch.empty((b, m), dtype=torch.int32, device=dev)
         grouped = torch.empty((b, m, ns, 3), dtype=torch.float32, device=dev)
         out = torch.empty((b, m, packed.widths[2]), dtype=torch.float32, device=dev)
-        nbytes = lib.pn2_sa_mlp3_ws_bytes(b, n, m, packed.cin, packed.widths[0], packed.widths[1], packed.widths[2], ns)
-        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev) if nbytes else None
+        ws = _scratch(lib, packed, b, n, m, ns, dev)
         tf = lib.pn2_fps_temp_floats(b, n)
         temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None
         if buffers is not None:
