@@ -730,6 +730,36 @@ int pn2_mlp_train_backward_ragged(int b, int n, const int *lengths, int nlayers,
                                   const float *out, const float *grad_out, float *grad_x, const void *mask, void *ws,
                                   const pn2_train_opts *opts, void *stream);
 
+/* The feature-propagation node pn2_mlp_train_*_fp (layer 1 once per KNOWN point, the (b, n, c2 + c1) input never written) with
+ * a RAGGED unknown side (csrc/train_mlp_fp_ragged.hip): the b n unknown points are b clouds padded to n rows, lengths (b) i32 ON
+ * THE DEVICE, row c n + i VALID iff i < clamp(lengths[c], 1, n); the b m known points are dense (a previous level's output).
+ * src, out, weight, grad_points2 / grad_points1 and `reproducible` as in pn2_mlp_train_forward_fp / _backward_fp (pn2_fp_src is
+ * unchanged); lengths and mask as in pn2_mlp_train_forward_ragged / _backward_ragged: the same buffer of 16 + 4 (b n / 32) bytes,
+ * 8-byte aligned, written by forward (N_valid, one validity word per 32 rows), read by backward, to be kept with layers[l].z.
+ * The batch moments, the running statistics and every gradient are those of the valid rows alone -- what the dense entries
+ * compute on the compacted rows. Two selects beyond the plain-rows ragged node's make a padding row absent: where z_1 is formed
+ * (nothing of idx, dist, Q or of the points1 W1b product is used there; z_1 = +0.0, weight = (0, 0, 0), nothing enters the
+ * moments) and where dz_1 is formed (+0.0 instead of -c0). A padding row of points1, dist and grad_out may hold anything, NaN
+ * and Inf included; out, grad_points1, weight and layers[l].z are all-zero bits there. The known-points half (Q = points2 W1a,
+ * dW1a, grad_points2) runs dense; the rows half (dW1b, grad_points1) runs the masked weight-gradient kernel and the masked GEMM.
+ * idx ON PADDING ROWS MUST HOLD INDICES IN [0, m): the interpolation gradient reads idx on every row (pn2_three_nn_ragged
+ * writes (0, 0, 0) there); with the zero weights those rows add 0 * 0 to known point 0 of their cloud.
+ * The host never reads lengths: stream-ordered, no host synchronisation, no memset, capturable in a graph whose replays see
+ * whatever lengths holds then. Organisation, pn2_train_opts, grad_accumulate, running_var_biased, reproducibility: as the
+ * plain-rows ragged entries; with every length equal to n the results are pn2_mlp_train_*_fp's bit for bit (fold_finalize aside).
+ * _supported: 1 where pn2_mlp_train_fp_supported is 1 and b n is a positive multiple of 32; _ws_bytes_fp_ragged: -1 where the
+ * dense query is. Before anything is launched: PN2_E_NULL for a NULL lengths (forward) or mask and the dense _fp entries' NULL
+ * checks, PN2_E_ARG as the dense _fp entries. backward takes lengths for symmetry and does not read it. */
+int pn2_mlp_train_fp_ragged_supported(int b, int n, int m, int c2, int c1, int nlayers, const int *widths);
+long long pn2_mlp_train_ws_bytes_fp_ragged(int b, int n, int m, int c2, int c1, int nlayers, const int *widths, int backward,
+                                           const pn2_train_opts *opts);
+int pn2_mlp_train_forward_fp_ragged(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *src, const int *lengths, float *out,
+                                    float *weight, void *mask, void *ws, const pn2_train_opts *opts, void *stream);
+int pn2_mlp_train_backward_fp_ragged(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *src, const int *lengths,
+                                     const float *weight, const float *out, const float *grad_out, float *grad_points2,
+                                     float *grad_points1, int reproducible, const void *mask, void *ws, const pn2_train_opts *opts,
+                                     void *stream);
+
 /* The input rows of a feature-propagation level's layer stack in ONE launch (pointnet_fp_module, utils/pointnet_util.py:211-219):
  * inverse-distance weights from three_nn's `dist`, three_interpolate of points2 (b,m,c2), concatenation with the skip features
  * points1 (b,n,c1; NULL with c1 = 0), zero columns up to `pitch` (a multiple of 4 >= c2 + c1: the training entry points read

@@ -124,6 +124,10 @@ _SIGNATURES = {
     "pn2_mlp_train_ws_bytes_ragged": [_i, _i, _i, _vp, _i, _vp],
     "pn2_mlp_train_forward_ragged": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_mlp_train_backward_ragged": [_i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_mlp_train_fp_ragged_supported": [_i, _i, _i, _i, _i, _i, _vp],
+    "pn2_mlp_train_ws_bytes_fp_ragged": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp],
+    "pn2_mlp_train_forward_fp_ragged": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_mlp_train_backward_fp_ragged": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "pn2_farthest_point_sample_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pn2_query_ball_group_xyz_ragged": [_i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
     "pn2_knn_point_ragged": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -145,6 +149,7 @@ _RESTYPES = {
     "pn2_mlp_train_ws_bytes_fp": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_frozen": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_ragged": ctypes.c_longlong,
+    "pn2_mlp_train_ws_bytes_fp_ragged": ctypes.c_longlong,
     "pn2_sample_and_group_status_offset": ctypes.c_longlong,
     "pn2_ball_threshold": ctypes.c_float,
     "pn2_version": ctypes.c_char_p,

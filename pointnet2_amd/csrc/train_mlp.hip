@@ -39,7 +39,7 @@
 //     train_mlp_l1.hip     layer 1 of a grouped level on the vector units (tl_l1_*)
 //     train_mlp_small.hip  per-channel finalisations, the top of the stack, the pooling modes
 // train_mlp_device.h is the device code they share; train_mlp_fp / _xyz / _frozen.hip hold the entry points and kernels of
-// one node type each (train_mlp_internal.h).
+// one node type each (train_mlp_internal.h); train_mlp_ragged.hip / train_mlp_fp_ragged.hip the kernels that take a row mask.
 #include "train_mlp_kernels.h"    // the parameter structs and launches of the kernels; TlCall, the shape structs (train_mlp_internal.h)
 
 #include <string.h>
@@ -689,7 +689,7 @@ struct TlRun {
     {
         if (!layers_ok(c.rows, c.nlayers, c.layers, c.group, widths, fp)) return PN2_E_ARG;
         if (c.frozen && fp) return PN2_E_ARG;                     // (the FP node with layer 1 per known point has no frozen form)
-        if (c.mask && (c.group || fp || c.frozen || c.pool_rows)) return PN2_E_ARG;      // (the row mask: plain rows, batch statistics)
+        if (c.mask && (c.group || c.frozen || c.pool_rows)) return PN2_E_ARG;      // (the row mask: plain rows or the FP node, batch statistics)
         return PN2_OK;
     }
     bool pool_buffers_missing(int pool_rows) const
@@ -779,7 +779,10 @@ struct Fwd : TlRun {
     }
 
     // layer 1 of an FP level once per KNOWN point (train_mlp_fp.hip): Q = points2 W1a over the b m known points,
-    // z_1 = points1 W1b over the rows, then one pass adds the interpolated rows of Q and sums the batch moments
+    // z_1 = points1 W1b over the rows, then one pass adds the interpolated rows of Q and sums the batch moments.
+    // Ragged rows (c.mask): the known points are a previous level's dense output, so Q stays dense; points1 W1b stays the dense
+    // store GEMM too -- rows are independent, a NaN padding row of points1 stays in its row of z_1 -- and the masked layer-1 pass
+    // (train_mlp_fp_ragged.hip) never reads that row and overwrites it with zeros.
     int layer1_fp()
     {
         const pn2_bn_layer &L = c.layers[0];
@@ -793,8 +796,10 @@ struct Fwd : TlRun {
             if (int rc = launch_gemm(A_PLAIN, q1, gemm_shape(c.rows, fp->c1p, L.cout, o), st, o)) return rc;
         }
         int np = 0;
-        if (int rc = fp_launch_l1_forward(c.rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z, fp->c1 > 0,
-                                          stats(0), kMaxParts, st, &np)) return rc;
+        if (int rc = c.mask ? fp_launch_l1_forward_masked(c.rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z,
+                                                          fp->c1 > 0, mask_words(), stats(0), kMaxParts, st, &np)
+                            : fp_launch_l1_forward(c.rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z, fp->c1 > 0,
+                                                   stats(0), kMaxParts, st, &np)) return rc;
         if (int rc = finalize_moments(0, np)) return rc;
         return c.nlayers == 1 ? apply(L) : PN2_OK;
     }
@@ -1274,28 +1279,38 @@ struct Bwd : TlRun {
     // Layer 1 per point / per known point, one half of W_1: dW_half = A^T D over hr rows (rows kc of the weight gradient from
     // row koff; kp: A's width as read) and, when gout is wanted, gout = D W_half^T beside it. D is dz_1 itself: the weight
     // gradient's pass takes the identity coefficients, which the caller has made sure of (identity_coefficients).
-    int l1_half(long long hr, int kp, int kc, const float *A, const float *D, size_t pack, float *gout, int koff, long long pair_rows)
+    // masked: the hr rows are the level's ragged rows (the FP node's points1 half). Both launches are then the MASKED kernels
+    // (train_mlp_ragged.hip), which select zero for a padding row of A (points1 may hold NaN there) and of D: nothing of it enters
+    // dW_half, and its row of gout is 0 + 0 products = all-zero bits. (D's padding rows are zeros in memory already, so the dense
+    // GEMM would give the same; the masked one does not depend on that.) ragged_opts has no pair launch: two launches.
+    int l1_half(long long hr, int kp, int kc, const float *A, const float *D, size_t pack, float *gout, int koff, long long pair_rows,
+                bool masked = false)
     {
         const pn2_bn_layer &L = layers[0];
         TlWgrad w = wgrad_into_partial(hr, kp);
         w.kout = kc; w.amode = A_PLAIN; w.A = A;
         w.dmode = A_DZ; w.NO = L.cout; w.Z = D; w.G = D; w.coef = at<float>(pl.l1coef);
+        if (masked) w.mask = mask_words();
         pn2_bn_layer Lh = L;
         Lh.grad_weight = L.grad_weight + (long long)koff * L.w_stride_k;
         const WgradShape ws_ = wgrad_shape(hr, kp, L.cout, false, cus, o.wgrad_two_per_cu);
         if (!gout) return launch_wgrad(w, ws_, Lh, st);
         TlGemm p = dense_gemm(hr, D, base + pack);
+        if (masked) p.mask = mask_words();
         plain_out(p, gout, kc);
         return beside(A_PLAIN, p, gemm_shape(hr, L.cout, kc, o), w, ws_, Lh, pair_rows, nullptr);
     }
 
     // ---- layer 1 of an FP level per KNOWN point (train_mlp_fp.hip): dz_1 in place, its interpolation gradient S onto
-    // the known points, then each half of W_1 -- a weight gradient and a data gradient over its own rows
+    // the known points, then each half of W_1 -- a weight gradient and a data gradient over its own rows. Ragged rows (c.mask):
+    // dz_1 by the masked pass (zero on padding rows, where the interpolation weights are zero too: S gets 0 * 0 from them), the
+    // known-points half dense, the rows half masked (l1_half)
     int layer1_fp()
     {
         const pn2_bn_layer &L = layers[0];
         float *S = at<float>(pl.l1p);
-        if (int rc = fp_launch_l1_dz(rows, L.cout, L.z, gcur, coef(0), st)) return rc;
+        if (int rc = c.mask ? fp_launch_l1_dz_masked(rows, L.cout, L.z, gcur, coef(0), mask_words(), st)
+                            : fp_launch_l1_dz(rows, L.cout, L.z, gcur, coef(0), st)) return rc;
         if (int rc = fp->idx_plan ? pn2_three_interpolate_grad_planned(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx_plan, fp->weight, S,
                                                                        c.reproducible, c.stream)
                                   : pn2_three_interpolate_grad_seg(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx, fp->weight, S,
@@ -1309,7 +1324,7 @@ struct Bwd : TlRun {
         if (int rc = l1_half(fp->mp, fp->c2p, fp->c2, p2, S, pl.pack[0], g2, 0, fp->mp)) return rc;
         if (g2 && g2 != fp->grad_points2)
             if (int rc = fp_launch_pad(g2, fp->bm, fp->c2, fp->bm, fp->c2, fp->grad_points2, st)) return rc;
-        if (fp->c1 > 0) return l1_half(rows, fp->c1p, fp->c1, p1, gcur, pl.fpw, fp->grad_points1, fp->c2, rows);
+        if (fp->c1 > 0) return l1_half(rows, fp->c1p, fp->c1, p1, gcur, pl.fpw, fp->grad_points1, fp->c2, rows, c.mask != nullptr);
         return PN2_OK;
     }
 
@@ -1484,12 +1499,13 @@ long long tl_ragged_ws_bytes(long long rows, int nlayers, const int *widths, int
     return (long long)pl.total;
 }
 
-// the workspace of the FP level with layer 1 per known point (pn2_mlp_train_ws_bytes_fp, train_mlp_fp.hip)
-long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts)
+// the workspace of the FP level with layer 1 per known point (pn2_mlp_train_ws_bytes_fp, train_mlp_fp.hip); ragged: of its
+// form with a row mask (pn2_mlp_train_ws_bytes_fp_ragged), planned under ragged_opts as its passes run
+long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts, bool ragged)
 {
     const FpL1 f = fp_l1(s);
     TlPlan pl;
-    if (!tl_plan(f.rows, nlayers, widths, 0, backward, pl, nullptr, opts_of(opts), &f)) return -1;
+    if (!tl_plan(f.rows, nlayers, widths, 0, backward, pl, nullptr, ragged ? ragged_opts(opts) : opts_of(opts), &f)) return -1;
     return (long long)pl.total;
 }
 }  // namespace pn2

@@ -269,3 +269,62 @@ extern "C" int pn2_mlp_train_backward_fp(int nlayers, const pn2_bn_layer *layers
     c.reproducible = reproducible;
     return tl_train_backward(c);
 }
+
+// ---- the same node with a RAGGED unknown side (pn2_mlp_train_*_fp_ragged, include/pn2ops.h): TlCall::mask beside TlCall::fp.
+// The masked layer-1 passes are train_mlp_fp_ragged.hip's, everything else the masked passes of the plain-rows ragged node
+// (train_mlp_ragged.hip) under its one organisation (ragged_opts, train_mlp.hip). pn2_fp_src is the dense entries'.
+extern "C" int pn2_mlp_train_fp_ragged_supported(int b, int n, int m, int c2, int c1, int nlayers, const int *widths)
+{
+    using namespace pn2;
+    if (!pn2_mlp_train_fp_supported(b, n, m, c2, c1, nlayers, widths)) return 0;
+    const long long rows = (long long)b * n;
+    if (rows <= 0 || rows % 32) return 0;
+    const pn2_fp_src s = {b, n, m, c2, c1, nullptr, nullptr, nullptr, nullptr};
+    return tl_fp_ws_bytes(&s, nlayers, widths, 0, nullptr, true) > 0 && tl_fp_ws_bytes(&s, nlayers, widths, 1, nullptr, true) > 0 ? 1 : 0;
+}
+
+extern "C" long long pn2_mlp_train_ws_bytes_fp_ragged(int b, int n, int m, int c2, int c1, int nlayers, const int *widths, int backward,
+                                                      const pn2_train_opts *opts)
+{
+    using namespace pn2;
+    const pn2_fp_src s = {b, n, m, c2, c1, nullptr, nullptr, nullptr, nullptr};
+    if (fp_dims(&s) || !fp_widths_ok(nlayers, widths, &s)) return -1;
+    return tl_fp_ws_bytes(&s, nlayers, widths, backward, opts, true);
+}
+
+extern "C" int pn2_mlp_train_forward_fp_ragged(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *src, const int *lengths,
+                                               float *out, float *weight, void *mask, void *ws, const pn2_train_opts *opts, void *stream)
+{
+    using namespace pn2;
+    if (!lengths || !mask) return PN2_E_NULL;
+    if (int rc = fp_level_args(nlayers, layers, src)) return rc;
+    if (src->c1 == 0 && src->points1) return PN2_E_ARG;
+    if (!src->points2 || !src->idx || !src->dist || (src->c1 > 0 && !src->points1) || !out || !weight || !ws) return PN2_E_NULL;
+    FpL1 f = fp_l1(src);
+    f.weight_out = weight;
+    TlCall c = fp_call(nlayers, layers, f, out, ws, opts, stream);
+    c.mask = mask; c.lengths = lengths; c.rg_b = src->b; c.rg_n = src->n;
+    return tl_train_forward(c);
+}
+
+extern "C" int pn2_mlp_train_backward_fp_ragged(int nlayers, const pn2_bn_layer *layers, const pn2_fp_src *src, const int *lengths,
+                                                const float *weight, const float *out, const float *grad_out, float *grad_points2,
+                                                float *grad_points1, int reproducible, const void *mask, void *ws,
+                                                const pn2_train_opts *opts, void *stream)
+{
+    using namespace pn2;
+    (void)lengths;                                                 // taken for symmetry: backward reads the mask forward wrote
+    if (!mask) return PN2_E_NULL;
+    if (int rc = fp_level_args(nlayers, layers, src)) return rc;
+    if (src->c1 == 0 && (src->points1 || grad_points1)) return PN2_E_ARG;
+    if (!src->points2 || !src->idx || (src->c1 > 0 && !src->points1) || !weight || !out || !grad_out || !ws) return PN2_E_NULL;
+    FpL1 f = fp_l1(src);
+    f.weight = weight;
+    f.grad_points2 = grad_points2;
+    f.grad_points1 = grad_points1;
+    TlCall c = fp_call(nlayers, layers, f, out, ws, opts, stream);
+    c.mask = const_cast<void *>(mask); c.rg_b = src->b; c.rg_n = src->n;
+    c.grad_out = grad_out;
+    c.reproducible = reproducible;
+    return tl_train_backward(c);
+}

@@ -592,6 +592,13 @@ class PointnetFPModule(nn.Module):
         # (train_mlp.fp_mlp_train(..., lengths=)) instead of the compacting layer-by-layer path: no host synchronisation, nothing
         # compacted, capturable; last_path "fused_train_ragged". Opt-in, like fused_frozen_bn (_forward_ragged).
         self.fused_ragged_train = False
+        # ... and, with fused_ragged_train on, the ONE-NODE form with a row mask (train_mlp.fp_level_train(..., lengths=)) where
+        # the dense route would take the one-node form (fp_level_preferred) and train_mlp.fp_level_ragged_supported: layer 1 once
+        # per known point, the (b, n, c2 + c1) tensor and its gradient never written; last_path "fused_train_ragged_node".
+        # Opt-in of its own. Measured (profiles/ragged_fp_node/README.md, warm forward + backward): sem_seg FP4 0.66-0.67 ->
+        # 0.64 ms and 288 -> 231 MB peak; part_seg FP3 0.525-0.530 -> 0.521-0.524 ms, which is within the spread of the medians
+        # -- NOT faster there -- and 158 -> 132 MB peak. Folding it into the size rule is a later change.
+        self.fused_ragged_node = False
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
@@ -688,8 +695,11 @@ class PointnetFPModule(nn.Module):
         With fused_ragged_train (opt-in), CUDA tensors and a stack the masked node covers (_train_mode says "fused_train" and
         train_mlp.ragged_supported): ONE launch for weights + interpolation + concatenation on all rows, then the stack as one
         autograd node whose passes skip the padding rows (fp_mlp_train(..., lengths=)); last_path "fused_train_ragged". The
-        host reads nothing, the index plan is _stack_on's. The one-node form (fp_level_train) has no mask: this route is
-        taken even where fp_level_preferred would choose it."""
+        host reads nothing, the index plan is _stack_on's. With fused_ragged_node as well (opt-in), where the dense route would
+        take the one-node form (fp_level_preferred) and train_mlp.fp_level_ragged_supported says yes: weights, interpolation,
+        concatenation and the stack as ONE node with the row mask inside, layer 1 once per known point
+        (fp_level_train(..., lengths=)); last_path "fused_train_ragged_node". Without that attribute the two-launch route is
+        taken even where fp_level_preferred would choose the node."""
         b, n = xyz1.shape[0], xyz1.shape[1]
         dev = xyz1.device
         lens = ragged_lengths(lengths1, b, dev, "lengths1")
@@ -704,9 +714,14 @@ class PointnetFPModule(nn.Module):
             return torch.where(valid.unsqueeze(2), out, torch.zeros((), dtype=out.dtype, device=dev))
         if self.fused_ragged_train and xyz1.is_cuda and self._train_mode(points1, points2, b * n) == "fused_train" and \
                 train_mlp.ragged_supported(self.mlp.net, b, n):
-            self.last_path = "fused_train_ragged"
             c1 = points1.shape[2] if points1 is not None else 0
-            plan = self._plan_of(g.idx, xyz2.shape[1], getattr(g, "plan", None))
+            m, c2 = xyz2.shape[1], points2.shape[2]
+            plan = self._plan_of(g.idx, m, getattr(g, "plan", None))
+            if self.fused_ragged_node and train_mlp.fp_level_preferred(b, n, m, c2) and \
+                    train_mlp.fp_level_ragged_supported(self.mlp.net, b, n, m, c2, c1):
+                self.last_path = "fused_train_ragged_node"
+                return train_mlp.fp_level_train(self.mlp.net, points2, points1, g.idx, g.dist, plan=plan, lengths=lens)     # :212-226
+            self.last_path = "fused_train_ragged"
             x, _ = fp_interp_concat(points2, points1, g.idx, g.dist, plan=plan)                   # :212-219, on every row
             return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, lengths=lens)
         self.last_path = "unfused_ragged"

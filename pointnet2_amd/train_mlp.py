@@ -784,6 +784,16 @@ def fp_level_supported(net, b, n, m, c2, c1):
     return bool(_C.lib().pn2_mlp_train_fp_supported(b, n, m, c2, c1, len(pairs), _widths_array(widths)))
 
 
+def fp_level_ragged_supported(net, b, n, m, c2, c1):
+    """... and with a RAGGED unknown side (fp_level_train(..., lengths=), pn2_mlp_train_*_fp_ragged): where fp_level_supported
+    holds and b n is a positive multiple of 32. Mirrors pn2_mlp_train_fp_ragged_supported."""
+    if b <= 0 or n <= 0 or (b * n) % 32 or not fp_level_supported(net, b, n, m, c2, c1):
+        return False
+    pairs = conv_bn_pairs(net)
+    widths = [c2 + c1] + [c.out_channels for c, _ in pairs]
+    return bool(_C.lib().pn2_mlp_train_fp_ragged_supported(b, n, m, c2, c1, len(pairs), _widths_array(widths)))
+
+
 # Where the modules take the node. It no longer forms the interpolated part of layer 1's input on the b (n - m) rows that are
 # not known points, and pays for it with a few more latency-bound passes (two layer-1 GEMMs instead of one, the dz / scatter
 # launches). Summed kernel time of one warm forward + backward (profiles/fp_train/README.md), node vs current path, and the
@@ -807,8 +817,9 @@ def _fp_src(level, points2, points1):
     return s
 
 
-def _ws_fp(level, widths, backward, dev, opts):
-    return _workspace("pn2_mlp_train_ws_bytes_fp", dev, "pn2_mlp_train_ws_bytes_fp: unsupported level", level.b, level.n, level.m,
+def _ws_fp(level, widths, backward, dev, opts, ragged=False):
+    query = "pn2_mlp_train_ws_bytes_fp_ragged" if ragged else "pn2_mlp_train_ws_bytes_fp"
+    return _workspace(query, dev, query + ": unsupported level", level.b, level.n, level.m,
                       level.c2, level.c1, len(widths) - 1, _widths_array(widths), backward, opts)
 
 
@@ -866,14 +877,79 @@ class _TrainFP(torch.autograd.Function):
         return tuple([None, g2, g1] + _batch_stat_results(grads, direct, biases, widths, dev))
 
 
-def fp_level_train(net, points2, points1, idx, dist, return_weight=False, plan=None):
+class _TrainFPRagged(torch.autograd.Function):
+    """_TrainFP's sibling for a ragged unknown side (pn2_mlp_train_*_fp_ragged), as _TrainMLPRagged is to _TrainMLP: inputs
+    level, points2, points1 or None, lengths (b,) i32 on the device, then the parameters. The node owns the validity mask: forward
+    writes it, it is saved with the z_l. The host never reads lengths: no synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, level, points2, points1, lengths, *params):
+        n = len(level.pairs)
+        weights, biases, gammas, betas = _unpack_params(params, n)
+        dev = weights[0].device
+        rows = level.rows
+        widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
+        opts = _opts()
+        zs = [torch.empty((rows, w), dtype=torch.float32, device=dev) for w in widths[1:]]
+        saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
+        out = torch.empty((rows, widths[-1]), dtype=torch.float32, device=dev)
+        weight = torch.empty((level.b, level.n, 3), dtype=torch.float32, device=dev)
+        mask = torch.empty((2 + (rows // 32 + 1) // 2,), dtype=torch.int64, device=dev)      # 16 + 4 (rows / 32) bytes, 8-byte aligned
+        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
+        src = _fp_src(level, points2, points1)
+        ws = _ws_fp(level, widths, 0, dev, opts, ragged=True)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_mlp_train_forward_fp_ragged(n, arr, ctypes.byref(src), ptr(lengths), ptr(out), ptr(weight), ptr(mask),
+                                                              ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward_fp_ragged")
+        _count_batch(level.pairs)
+        ctx.level, ctx.widths = level, widths
+        ctx.opts = dict(_OPTS)
+        ctx.mark_non_differentiable(weight)
+        _save_layers(ctx, [points2] + ([points1] if points1 is not None else []) + [weight], weights, biases, gammas, betas, zs,
+                     saves, out, [mask, lengths])
+        return out, weight
+
+    @staticmethod
+    def backward(ctx, grad_out, _unused):
+        level, widths = ctx.level, ctx.widths
+        n = len(level.pairs)
+        head, weights, biases, gammas, betas, zs, saves, out, tail = _saved_layers(ctx, n)
+        points2, points1, weight = head[0], (head[1] if len(head) == 3 else None), head[-1]
+        mask, lengths = tail[0], tail[1]
+        dev = out.device
+        grad_out = f32(grad_out, "grad_out")
+        grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
+        g2 = torch.empty_like(points2) if ctx.needs_input_grad[1] else None
+        g1 = torch.empty_like(points1) if points1 is not None and ctx.needs_input_grad[2] else None
+        opts = _opts_from(ctx.opts)
+        ws = _ws_fp(level, widths, 1, dev, opts, ragged=True)
+        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
+        for l in range(n):
+            arr[l].grad_accumulate = 1 if direct[l] else 0
+        src = _fp_src(level, points2, points1)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_mlp_train_backward_fp_ragged(n, arr, ctypes.byref(src), ptr(lengths), ptr(weight), ptr(out),
+                                                               ptr(grad_out), ptr(g2), ptr(g1), 1 if is_deterministic() else 0,
+                                                               ptr(mask), ptr(ws), opts, stream_ptr(dev)),
+                     "mlp_train_backward_fp_ragged")
+        return tuple([None, g2, g1, None] + _batch_stat_results(grads, direct, biases, widths, dev))
+
+
+def fp_level_train(net, points2, points1, idx, dist, return_weight=False, plan=None, lengths=None):
     """Training-mode feature-propagation level with the interpolation inside ONE autograd node (pointnet_fp_module,
     utils/pointnet_util.py:211-226): inverse-distance weights from three_nn's squared distances `dist` (b,n,3) and `idx`
     (b,n,3) i32, three_interpolate of points2 (b,m,c2), concatenation with the skip features points1 (b,n,c1) or None, and the
     layer stack `net` (Conv 1x1 + BatchNorm + ReLU triples, batch statistics). Layer 1 runs once per KNOWN point
     (z_1 = interp(points2 W1a) + points1 W1b); the (b,n,c2+c1) input never exists. -> (b,n,cout), differentiable w.r.t.
     points2, points1 and every parameter (and the weights (b,n,3) with return_weight).
-    plan: an IndexPlan of idx (index_plan(idx, m, "interpolate")): the backward inverts nothing."""
+    plan: an IndexPlan of idx (index_plan(idx, m, "interpolate")): the backward inverts nothing.
+    lengths: (b,) per-cloud counts of a ragged UNKNOWN side (cloud i's unknown points are rows [0, lengths[i]) of points1 / idx /
+    dist; an int32 / int64 tensor or a sequence, ragged_lengths; the known side points2 is dense): the batch statistics, the
+    running averages and every gradient are those of the valid rows alone, as on the compacted rows (fp_level_ragged_supported;
+    pn2_mlp_train_*_fp_ragged). The padding rows of points1, dist and the output's gradient may hold anything, NaN included; the
+    output, the gradient of points1 and the returned weights are exactly zero there. idx must hold indices in [0, m) on the
+    padding rows too (three_nn(..., lengths1=) writes (0, 0, 0)). The host never reads the lengths (no synchronisation; a length
+    outside 1..n is clamped)."""
     pairs = conv_bn_pairs(net)
     require(pairs is not None, "fp_level_train expects Conv 1x1 + BatchNorm + ReLU triples")
     points2, idx, dist = f32(points2, "points2"), i32(idx, "idx"), f32(dist, "dist")
@@ -893,9 +969,15 @@ def fp_level_train(net, points2, points1, idx, dist, return_weight=False, plan=N
         same_device(points2, idx, dist, pairs[0][0].weight)
     require(pairs[0][0].in_channels == c2 + c1, "the first layer expects %d channels, got %d" % (pairs[0][0].in_channels, c2 + c1))
     require(fp_level_supported(net, b, n, m, c2, c1), "unsupported level for the FP training node")
+    if lengths is not None:
+        lengths = ragged_lengths(lengths, b, points2.device)
+        require(fp_level_ragged_supported(net, b, n, m, c2, c1), "unsupported level for the FP training node on ragged rows")
     lv = _FpLevel()
     lv.pairs, lv.rows, lv.b, lv.n, lv.m, lv.c2, lv.c1, lv.idx, lv.dist = pairs, b * n, b, n, m, c2, c1, idx, dist
     lv.plan = None if plan is None else plan.check("interpolate", b, m, 3 * n, points2.device)
-    out, weight = _TrainFP.apply(lv, points2, points1, *_params(pairs))
+    if lengths is not None:
+        out, weight = _TrainFPRagged.apply(lv, points2, points1, lengths, *_params(pairs))
+    else:
+        out, weight = _TrainFP.apply(lv, points2, points1, *_params(pairs))
     out = out.view(b, n, -1)
     return (out, weight) if return_weight else out
