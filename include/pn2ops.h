@@ -760,6 +760,33 @@ int pn2_mlp_train_backward_fp_ragged(int nlayers, const pn2_bn_layer *layers, co
                                      float *grad_points1, int reproducible, const void *mask, void *ws, const pn2_train_opts *opts,
                                      void *stream);
 
+/* What a ragged training call launches on the matrix cores: host logic, no device work (tests, maintainers). The two entries
+ * take the arguments of pn2_mlp_train_ws_bytes_ragged / _ws_bytes_fp_ragged without `backward` and describe BOTH directions of
+ * one call that wants every gradient (grad_x; grad_points2 and grad_points1), in launch order: forward layers 1..L, then
+ * backward layers L..1, per layer the weight-gradient pass before the data-gradient GEMM. They evaluate the size rules the
+ * launches evaluate (csrc/train_mlp.hip: ragged_opts, gemm_shape, wgrad_shape, the GEMM's grid and nt rule), so a record names
+ * the kernel instantiation that pass runs. passes: cap records of PN2_RAGGED_PLAN_FIELDS ints each, or NULL to count; returns
+ * the number of passes (records beyond cap are not written), or PN2_E_ARG where the _supported query says 0, PN2_E_NULL
+ * without widths. A record:
+ *   [0] kind: 0 = GEMM (tl_gemm_masked_kernel<NS, AMODE> when masked, else tl_gemm_kernel), 1 = weight-gradient pass
+ *       (tl_wgrad_masked_kernel<TPW, UPW> when masked, else tl_wgrad_kernel)
+ *   [1] 0 forward, 1 backward   [2] layer, 1-based   [3] 1: the masked kernel, 0: the dense one   [4] rows
+ *   [5] K, [6] N: GEMM: contraction and output channels as the shape rule gets them; weight gradient: input and output channels
+ *   GEMM:            [7] NS  [8] AMODE (0 A_PLAIN, 2 A_RELU, 3 A_DZ)  [9] 1 resident weights, 0 streamed  [10] column slabs
+ *                    [11] 1: non-temporal stores (opts.nt, else from 128 MB of output)  [12] grid x  [13] 0
+ *   weight gradient: [7] TPW [8] UPW  [9] `two` (two workgroups per CU)  [10] slabs (input slabs x output slabs)
+ *                    [11] input tiles per slab  [12] grid x  [13] output tiles per slab
+ * The FP node's vector-unit passes (z_1 and dz_1 with the mask, the interpolation gradient) and the per-channel finalisations are
+ * not listed; its layer 1 appears as its two halves: the known-points half (forward Q = points2 W1a; backward dW1a and
+ * grad_points2, b m rows rounded up to 32) with [3] = 0, the rows half (forward points1 W1b, a dense store GEMM, [3] = 0;
+ * backward dW1b and grad_points1, [3] = 1) -- absent with c1 = 0.
+ * NS, AMODE, residency, slabs, nt, TPW and UPW depend on the shape and opts alone. `two` and grid x of a weight-gradient pass
+ * depend on the CU count of the current device, which is taken as 256 where there is no device: do not rely on them there. */
+#define PN2_RAGGED_PLAN_FIELDS 14
+int pn2_mlp_train_ragged_plan(int b, int n, int nlayers, const int *widths, const pn2_train_opts *opts, int *passes, int cap);
+int pn2_mlp_train_fp_ragged_plan(int b, int n, int m, int c2, int c1, int nlayers, const int *widths, const pn2_train_opts *opts,
+                                 int *passes, int cap);
+
 /* The input rows of a feature-propagation level's layer stack in ONE launch (pointnet_fp_module, utils/pointnet_util.py:211-219):
  * inverse-distance weights from three_nn's `dist`, three_interpolate of points2 (b,m,c2), concatenation with the skip features
  * points1 (b,n,c1; NULL with c1 = 0), zero columns up to `pitch` (a multiple of 4 >= c2 + c1: the training entry points read

@@ -128,6 +128,8 @@ _SIGNATURES = {
     "pn2_mlp_train_ws_bytes_fp_ragged": [_i, _i, _i, _i, _i, _i, _vp, _i, _vp],
     "pn2_mlp_train_forward_fp_ragged": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_mlp_train_backward_fp_ragged": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "pn2_mlp_train_ragged_plan": [_i, _i, _i, _vp, _vp, _vp, _i],
+    "pn2_mlp_train_fp_ragged_plan": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i],
     "pn2_farthest_point_sample_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pn2_query_ball_group_xyz_ragged": [_i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
     "pn2_knn_point_ragged": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -1508,7 +1508,109 @@ long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, in
     if (!tl_plan(f.rows, nlayers, widths, 0, backward, pl, nullptr, ragged ? ragged_opts(opts) : opts_of(opts), &f)) return -1;
     return (long long)pl.total;
 }
+
+// ---- what a ragged call launches on the matrix cores (pn2_mlp_train_ragged_plan / _fp_ragged_plan, include/pn2ops.h): host
+// logic for tests and maintainers. It walks the layers as Fwd::run / Bwd::run do under a row mask -- ragged_opts: no fused data
+// gradient, no pair launch, so generic_layer is launch_wgrad then launch_gemm, and l1_half the same -- and asks the rules the
+// launches ask: gemm_shape, wgrad_shape with the device's CU count and the caller's wgrad_two_per_cu, prep_gemm for grid and nt.
+struct RaggedPlanOut {
+    int *rec;
+    int cap, n;
+    const Opts o;
+    const int cus;
+    int *next()
+    {
+        int *r = (rec && n < cap) ? rec + (size_t)n * PN2_RAGGED_PLAN_FIELDS : nullptr;
+        ++n;
+        if (r) memset(r, 0, sizeof(int) * PN2_RAGGED_PLAN_FIELDS);
+        return r;
+    }
+    void head(int *r, int kind, int backward, int layer, bool masked, long long rows, int K, int N) const
+    {
+        r[0] = kind; r[1] = backward; r[2] = layer + 1; r[3] = masked ? 1 : 0; r[4] = (int)rows; r[5] = K; r[6] = N;
+    }
+    // a GEMM over `rows` rows, K -> N channels, as launch_gemm(amode, p, gemm_shape(rows, K, N, o), st, o) shapes it
+    void gemm(int backward, int layer, bool masked, long long rows, int amode, int K, int N)
+    {
+        const GemmShape g = gemm_shape(rows, K, N, o);
+        TlGemm p;
+        memset(&p, 0, sizeof(p));
+        p.rows = rows;
+        const dim3 grid = prep_gemm(p, g, o);
+        int *r = next();
+        if (!r) return;
+        head(r, 0, backward, layer, masked, rows, K, N);
+        r[7] = g.ns; r[8] = amode; r[9] = g.resident ? 1 : 0; r[10] = g.slabs; r[11] = p.nt; r[12] = (int)grid.x;
+    }
+    // a weight-gradient pass over `rows` rows, KI input and NO output channels, as launch_wgrad(w, wgrad_shape(...), L, st) shapes it
+    void wgrad(int layer, bool masked, long long rows, int KI, int NO)
+    {
+        const WgradShape w = wgrad_shape(rows, KI, NO, false, cus, o.wgrad_two_per_cu);
+        int *r = next();
+        if (!r) return;
+        head(r, 1, 1, layer, masked, rows, KI, NO);
+        r[7] = w.tpw; r[8] = w.upw; r[9] = w.two ? 1 : 0; r[10] = w.uslabs * w.tslabs; r[11] = w.tus; r[12] = (int)w.gridx; r[13] = w.tts;
+    }
+    // layers lo..L-1 of a direction where they are Fwd / Bwd::generic_layer with the mask (plain rows: from layer 0; FP: from 1)
+    void generic_forward(long long rows, int nlayers, const int *widths, int lo)
+    {
+        for (int l = lo; l < nlayers; ++l) gemm(0, l, true, rows, l == 0 ? A_PLAIN : A_RELU, widths[l], widths[l + 1]);
+    }
+    void generic_backward(long long rows, int nlayers, const int *widths, int lo)
+    {
+        for (int l = nlayers - 1; l >= lo; --l) {
+            wgrad(l, true, rows, widths[l], widths[l + 1]);
+            gemm(1, l, true, rows, A_DZ, widths[l + 1], widths[l]);    // (below(l): l > 0, or grad_x wanted)
+        }
+    }
+};
+
+int tl_ragged_plan(long long rows, int nlayers, const int *widths, const pn2_train_opts *opts, int *passes, int cap)
+{
+    RaggedPlanOut po = {passes, cap, 0, ragged_opts(opts), device_cus()};
+    po.generic_forward(rows, nlayers, widths, 0);
+    po.generic_backward(rows, nlayers, widths, 0);
+    return po.n;
+}
+
+int tl_fp_ragged_plan(const pn2_fp_src *s, int nlayers, const int *widths, const pn2_train_opts *opts, int *passes, int cap)
+{
+    const FpL1 f = fp_l1(s);
+    const int C1 = widths[1];
+    RaggedPlanOut po = {passes, cap, 0, ragged_opts(opts), device_cus()};
+    // Fwd::layer1_fp: Q over the known points and points1 W1b over the rows, both dense store GEMMs
+    po.gemm(0, 0, false, f.mp, A_PLAIN, f.c2p, C1);
+    if (f.c1 > 0) po.gemm(0, 0, false, f.rows, A_PLAIN, f.c1p, C1);
+    po.generic_forward(f.rows, nlayers, widths, 1);
+    po.generic_backward(f.rows, nlayers, widths, 1);
+    // Bwd::layer1_fp -> l1_half: the known-points half dense, the rows half masked
+    po.wgrad(0, false, f.mp, f.c2p, C1);
+    po.gemm(1, 0, false, f.mp, A_PLAIN, C1, f.c2);
+    if (f.c1 > 0) {
+        po.wgrad(0, true, f.rows, f.c1p, C1);
+        po.gemm(1, 0, true, f.rows, A_PLAIN, C1, f.c1);
+    }
+    return po.n;
+}
 }  // namespace pn2
+
+extern "C" int pn2_mlp_train_ragged_plan(int b, int n, int nlayers, const int *widths, const pn2_train_opts *opts, int *passes, int cap)
+{
+    if (!widths) return PN2_E_NULL;
+    if (cap < 0 || !pn2_mlp_train_ragged_supported(b, n, nlayers, widths)) return PN2_E_ARG;
+    return pn2::tl_ragged_plan((long long)b * n, nlayers, widths, opts, passes, cap);
+}
+
+extern "C" int pn2_mlp_train_fp_ragged_plan(int b, int n, int m, int c2, int c1, int nlayers, const int *widths,
+                                            const pn2_train_opts *opts, int *passes, int cap)
+{
+    if (!widths) return PN2_E_NULL;
+    if (cap < 0 || !pn2_mlp_train_fp_ragged_supported(b, n, m, c2, c1, nlayers, widths)) return PN2_E_ARG;
+    pn2_fp_src s;
+    memset(&s, 0, sizeof(s));
+    s.b = b; s.n = n; s.m = m; s.c2 = c2; s.c1 = c1;
+    return pn2::tl_fp_ragged_plan(&s, nlayers, widths, opts, passes, cap);
+}
 
 extern "C" int pn2_mlp_train_forward(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
                                      const float *x, int pool_rows, float *out, int *argsel, float *zsel, void *ws, void *stream)

@@ -213,6 +213,35 @@ def ragged_supported(net, b, n):
     return bool(_C.lib().pn2_mlp_train_ragged_supported(b, n, len(pairs), _widths_array(widths)))
 
 
+_PLAN_FIELDS = 14                    # PN2_RAGGED_PLAN_FIELDS
+_PLAN_AMODES = {0: "A_PLAIN", 2: "A_RELU", 3: "A_DZ"}
+
+
+def ragged_plan(b, n, widths, fp=None):
+    """What one ragged forward + backward launches on the matrix cores under the options in force (options(...)), from the
+    library's own size rules (pn2_mlp_train_ragged_plan; fp=(m, c2, c1): pn2_mlp_train_fp_ragged_plan): host logic, no device
+    work (tests, maintainers). widths: cin_1 (a multiple of 4; FP: c2 + c1), cout_1 .. cout_L. -> one dict per pass in launch
+    order: kind "gemm" (ns, amode, resident, slabs, nt, grid) or "wgrad" (tpw, upw, two, slabs, tus, tts, grid), backward,
+    layer (1-based), masked, rows, K, N. `two` and a weight gradient's grid follow the device's CU count (256 without one)."""
+    warr, opts = _widths_array(widths), _opts()
+    head = (b, n) + (tuple(fp) if fp is not None else ()) + (len(widths) - 1, warr, opts)
+    fn = _C.lib().pn2_mlp_train_fp_ragged_plan if fp is not None else _C.lib().pn2_mlp_train_ragged_plan
+    count = fn(*head, None, 0)
+    require(count >= 0, "ragged_plan: unsupported shape (%s)" % _C.PN2_ERRORS.get(count, count))
+    buf = (ctypes.c_int * (count * _PLAN_FIELDS))()
+    require(fn(*head, buf, count) == count, "ragged_plan: the pass count changed between two queries")
+    passes = []
+    for i in range(count):
+        r = buf[i * _PLAN_FIELDS:(i + 1) * _PLAN_FIELDS]
+        p = dict(kind="wgrad" if r[0] else "gemm", backward=bool(r[1]), layer=r[2], masked=bool(r[3]), rows=r[4], K=r[5], N=r[6])
+        if r[0]:
+            p.update(tpw=r[7], upw=r[8], two=bool(r[9]), slabs=r[10], tus=r[11], grid=r[12], tts=r[13])
+        else:
+            p.update(ns=r[7], amode=_PLAN_AMODES[r[8]], resident=bool(r[9]), slabs=r[10], nt=bool(r[11]), grid=r[12])
+        passes.append(p)
+    return passes
+
+
 def _layer_array(level, weights, biases, gammas, betas, zs, saves, grads=None, update_running=True):
     n = len(level.pairs)
     arr = (BnLayer * n)()
