@@ -731,7 +731,7 @@ int pn2_mlp_train_backward_ragged(int b, int n, const int *lengths, int nlayers,
                                   const pn2_train_opts *opts, void *stream);
 
 /* The feature-propagation node pn2_mlp_train_*_fp (layer 1 once per KNOWN point, the (b, n, c2 + c1) input never written) with
- * a RAGGED unknown side (csrc/train_mlp_fp_ragged.hip): the b n unknown points are b clouds padded to n rows, lengths (b) i32 ON
+ * a RAGGED unknown side (csrc/train_mlp_fp.hip): the b n unknown points are b clouds padded to n rows, lengths (b) i32 ON
  * THE DEVICE, row c n + i VALID iff i < clamp(lengths[c], 1, n); the b m known points are dense (a previous level's output).
  * src, out, weight, grad_points2 / grad_points1 and `reproducible` as in pn2_mlp_train_forward_fp / _backward_fp (pn2_fp_src is
  * unchanged); lengths and mask as in pn2_mlp_train_forward_ragged / _backward_ragged: the same buffer of 16 + 4 (b n / 32) bytes,

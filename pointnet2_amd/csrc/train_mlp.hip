@@ -39,7 +39,8 @@
 //     train_mlp_l1.hip     layer 1 of a grouped level on the vector units (tl_l1_*)
 //     train_mlp_small.hip  per-channel finalisations, the top of the stack, the pooling modes
 // train_mlp_device.h is the device code they share; train_mlp_fp / _xyz / _frozen.hip hold the entry points and kernels of
-// one node type each (train_mlp_internal.h); train_mlp_ragged.hip / train_mlp_fp_ragged.hip the kernels that take a row mask.
+// one node type each (train_mlp_internal.h); train_mlp_ragged.hip the plain rows of a ragged batch. A kernel that takes a row mask
+// stands beside its dense twin; here c.mask only selects an ARGUMENT (mask_words(), row_count()), the launch function the kernel.
 #include "train_mlp_kernels.h"    // the parameter structs and launches of the kernels; TlCall, the shape structs (train_mlp_internal.h)
 
 #include <string.h>
@@ -683,6 +684,7 @@ struct TlRun {
     double *stats(int l) const { return at<double>(pl.stats[l]); }
     bool want_max() const { return c.pooling == 0 || c.pooling == 3; }
     const unsigned *mask_words() const { return c.mask ? ragged_words(c.mask) : nullptr; }     // ragged rows, or nullptr
+    const double *row_count() const { return c.mask ? ragged_count(c.mask) : nullptr; }        // ... their valid rows, on the device
 
     // the checks both directions make first, in this order
     int check_inputs()
@@ -764,25 +766,21 @@ struct Fwd : TlRun {
     {
         if (c.frozen) return PN2_OK;
         const pn2_bn_layer &L = c.layers[l];
-        if (c.mask)                                               // ragged rows: the count is the number of valid rows, on the device
-            return launch_bn_finalize_counted(stats(l), np, L.cout, ragged_count(c.mask), L.gamma, L.beta, L.running_mean, L.running_var,
-                                              L.momentum, L.eps, L.save, L.bias, L.running_var_biased, st);
-        return launch_bn_finalize(stats(l), np, L.cout, (double)c.rows, L.gamma, L.beta, L.running_mean, L.running_var, L.momentum, L.eps,
-                                  L.save, L.bias, L.running_var_biased, st);
+        return launch_bn_finalize(stats(l), np, L.cout, (double)c.rows, row_count(), L.gamma, L.beta, L.running_mean, L.running_var,
+                                  L.momentum, L.eps, L.save, L.bias, L.running_var_biased, st);
     }
 
     // an unpooled top layer: out = relu(a z_L + c)
     int apply(const pn2_bn_layer &L) const
     {
-        if (c.mask) return launch_apply_masked(c.rows * L.cout / 4, L.cout, L.z, L.save, mask_words(), out(), st);
-        return launch_apply(c.rows * L.cout / 4, L.cout, L.z, L.save, out(), st);
+        return launch_apply(c.rows * L.cout / 4, L.cout, L.z, L.save, mask_words(), out(), st);
     }
 
     // layer 1 of an FP level once per KNOWN point (train_mlp_fp.hip): Q = points2 W1a over the b m known points,
     // z_1 = points1 W1b over the rows, then one pass adds the interpolated rows of Q and sums the batch moments.
     // Ragged rows (c.mask): the known points are a previous level's dense output, so Q stays dense; points1 W1b stays the dense
     // store GEMM too -- rows are independent, a NaN padding row of points1 stays in its row of z_1 -- and the masked layer-1 pass
-    // (train_mlp_fp_ragged.hip) never reads that row and overwrites it with zeros.
+    // (tl_fp_l1_forward_masked_kernel) never reads that row and overwrites it with zeros.
     int layer1_fp()
     {
         const pn2_bn_layer &L = c.layers[0];
@@ -796,10 +794,8 @@ struct Fwd : TlRun {
             if (int rc = launch_gemm(A_PLAIN, q1, gemm_shape(c.rows, fp->c1p, L.cout, o), st, o)) return rc;
         }
         int np = 0;
-        if (int rc = c.mask ? fp_launch_l1_forward_masked(c.rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z,
-                                                          fp->c1 > 0, mask_words(), stats(0), kMaxParts, st, &np)
-                            : fp_launch_l1_forward(c.rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z, fp->c1 > 0,
-                                                   stats(0), kMaxParts, st, &np)) return rc;
+        if (int rc = fp_launch_l1_forward(c.rows, fp->n, fp->m, L.cout, fp->idx, fp->dist, fp->weight_out, Q, L.z, fp->c1 > 0, mask_words(),
+                                          stats(0), kMaxParts, st, &np)) return rc;
         if (int rc = finalize_moments(0, np)) return rc;
         return c.nlayers == 1 ? apply(L) : PN2_OK;
     }
@@ -1181,10 +1177,8 @@ struct Bwd : TlRun {
     {
         const pn2_bn_layer &L = layers[l];
         if (!folded[l] && !c.frozen)
-            if (int rc = c.mask ? launch_bn_backward_finalize_counted(stats(l), nparts[l], L.cout, ragged_count(c.mask), L.gamma, L.save,
-                                                                      L.grad_gamma, L.grad_beta, coef(l), L.grad_accumulate, st)
-                                : launch_bn_backward_finalize(stats(l), nparts[l], L.cout, (double)rows, L.gamma, L.save, L.grad_gamma,
-                                                              L.grad_beta, coef(l), L.grad_accumulate, st)) return rc;
+            if (int rc = launch_bn_backward_finalize(stats(l), nparts[l], L.cout, (double)rows, row_count(), L.gamma, L.save, L.grad_gamma,
+                                                     L.grad_beta, coef(l), L.grad_accumulate, st)) return rc;
         return sd.join();
     }
 
@@ -1279,24 +1273,24 @@ struct Bwd : TlRun {
     // Layer 1 per point / per known point, one half of W_1: dW_half = A^T D over hr rows (rows kc of the weight gradient from
     // row koff; kp: A's width as read) and, when gout is wanted, gout = D W_half^T beside it. D is dz_1 itself: the weight
     // gradient's pass takes the identity coefficients, which the caller has made sure of (identity_coefficients).
-    // masked: the hr rows are the level's ragged rows (the FP node's points1 half). Both launches are then the MASKED kernels
+    // mask: the hr rows are the level's ragged rows (the FP node's points1 half). Both launches are then the MASKED kernels
     // (train_mlp_ragged.hip), which select zero for a padding row of A (points1 may hold NaN there) and of D: nothing of it enters
     // dW_half, and its row of gout is 0 + 0 products = all-zero bits. (D's padding rows are zeros in memory already, so the dense
     // GEMM would give the same; the masked one does not depend on that.) ragged_opts has no pair launch: two launches.
     int l1_half(long long hr, int kp, int kc, const float *A, const float *D, size_t pack, float *gout, int koff, long long pair_rows,
-                bool masked = false)
+                const unsigned *mask = nullptr)
     {
         const pn2_bn_layer &L = layers[0];
         TlWgrad w = wgrad_into_partial(hr, kp);
         w.kout = kc; w.amode = A_PLAIN; w.A = A;
         w.dmode = A_DZ; w.NO = L.cout; w.Z = D; w.G = D; w.coef = at<float>(pl.l1coef);
-        if (masked) w.mask = mask_words();
+        w.mask = mask;
         pn2_bn_layer Lh = L;
         Lh.grad_weight = L.grad_weight + (long long)koff * L.w_stride_k;
         const WgradShape ws_ = wgrad_shape(hr, kp, L.cout, false, cus, o.wgrad_two_per_cu);
         if (!gout) return launch_wgrad(w, ws_, Lh, st);
         TlGemm p = dense_gemm(hr, D, base + pack);
-        if (masked) p.mask = mask_words();
+        p.mask = mask;
         plain_out(p, gout, kc);
         return beside(A_PLAIN, p, gemm_shape(hr, L.cout, kc, o), w, ws_, Lh, pair_rows, nullptr);
     }
@@ -1309,8 +1303,7 @@ struct Bwd : TlRun {
     {
         const pn2_bn_layer &L = layers[0];
         float *S = at<float>(pl.l1p);
-        if (int rc = c.mask ? fp_launch_l1_dz_masked(rows, L.cout, L.z, gcur, coef(0), mask_words(), st)
-                            : fp_launch_l1_dz(rows, L.cout, L.z, gcur, coef(0), st)) return rc;
+        if (int rc = fp_launch_l1_dz(rows, L.cout, L.z, gcur, coef(0), mask_words(), st)) return rc;
         if (int rc = fp->idx_plan ? pn2_three_interpolate_grad_planned(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx_plan, fp->weight, S,
                                                                        c.reproducible, c.stream)
                                   : pn2_three_interpolate_grad_seg(fp->b, fp->n, L.cout, fp->m, gcur, fp->idx, fp->weight, S,
@@ -1324,7 +1317,7 @@ struct Bwd : TlRun {
         if (int rc = l1_half(fp->mp, fp->c2p, fp->c2, p2, S, pl.pack[0], g2, 0, fp->mp)) return rc;
         if (g2 && g2 != fp->grad_points2)
             if (int rc = fp_launch_pad(g2, fp->bm, fp->c2, fp->bm, fp->c2, fp->grad_points2, st)) return rc;
-        if (fp->c1 > 0) return l1_half(rows, fp->c1p, fp->c1, p1, gcur, pl.fpw, fp->grad_points1, fp->c2, rows, c.mask != nullptr);
+        if (fp->c1 > 0) return l1_half(rows, fp->c1p, fp->c1, p1, gcur, pl.fpw, fp->grad_points1, fp->c2, rows, mask_words());
         return PN2_OK;
     }
 

@@ -17,6 +17,26 @@
 // each pair in one launch where the shapes have a pair kernel. The concatenated (b, n, c2 + c1) input and its gradient are
 // never written. Widths that are no multiple of 4 enter as zero-padded copies of points2 / points1 alone, and b m known
 // points as a copy of points2 padded to a multiple of 32 rows.
+//
+// A RAGGED unknown side (pn2_mlp_train_*_fp_ragged). The two vector-unit passes have masked twins, kernels of their own beside
+// the dense ones. Row r of the b n unknown points is valid iff bit r & 31 of validity word r >> 5 is set (the mask buffer of
+// pn2_mlp_train_*_ragged, written by tl_ragged_mask_kernel from `lengths`; train_mlp_ragged.hip). The two values DESIGN.md
+// section 4.11 names are taken as zero on a padding row, by SELECTS (points1, dist, grad_out may hold NaN there):
+//   z_1   where it is formed: nothing of idx, dist, Q or of what the points1 W1b GEMM left in the row is used; the row is
+//         written as +0.0, its weights as (0, 0, 0), and it adds nothing to the partial moments;
+//   dz_1  where it is formed: s dy_1 - c0 - c1 z_1 would be -c0; the row is written as +0.0.
+// Everything behind them (layers 2..L, the weight gradients, the interpolation gradient) then meets zero rows.
+// With every row valid the masked forward kernel runs the dense kernel's operations on the dense kernel's rows in the dense
+// kernel's order (same thread <-> (row lane, 4 columns) mapping, chunking, kFpU, partial-moment layout): the same bits.
+//
+// idx on padding rows. The interpolation gradient behind the dz pass (pn2_three_interpolate_grad_seg / _planned) reads idx and
+// weight on EVERY row, so padding rows must hold indices in [0, m): ragged three_nn writes (0, 0, 0) there, and with the zero
+// weights written here those rows add 0 * 0 to known point 0 of their cloud -- one long segment per short cloud, which the
+// segmented kernels handle, and the same as on the fp_interp_concat route. That cost is not addressed here.
+//
+// The dense and the masked kernel of a pass stay TWINS: one `template <bool MASKED>` body inlined into both changes the
+// generated code of all four (e % q4 against e / q4, the fallback row `base` against 0, ...), so merging the bodies is a change
+// of its own with a GPU timing, not a tidying.
 #include "train_mlp_internal.h"
 
 namespace pn2 {
@@ -118,6 +138,87 @@ __global__ __launch_bounds__(kFpThreads) void tl_fp_l1_forward_kernel(long long 
     }
 }
 
+// tl_fp_l1_forward_kernel with the row mask. A lane whose row is padding (or past the end) redirects its loads of idx, dist
+// and Q to row c n of its cloud (row 0 past the end), which is valid by the clamp of the lengths to 1..n -- the dense kernel's
+// `base` may itself be padding -- and does not read z at all; what it computes from there is dropped by the selects below.
+__global__ __launch_bounds__(kFpThreads) void tl_fp_l1_forward_masked_kernel(long long rows, int n, int m, int C,
+                                                                              const int *__restrict__ idx, const float *__restrict__ dist,
+                                                                              float *__restrict__ weight, const float *__restrict__ Q,
+                                                                              float *z, int add, const unsigned *__restrict__ mask,
+                                                                              double *__restrict__ stats)
+{
+    const int qpr = C / 4, q = threadIdx.x % qpr, rl = threadIdx.x / qpr, rpb = kFpThreads / qpr, col = 4 * q;
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+    const long long stride = rpb, span = (long long)kFpU * stride;
+    const long long chunk = (rows + (long long)gridDim.x * span - 1) / ((long long)gridDim.x * span) * span;
+    const long long first = (long long)blockIdx.x * chunk, stop = first + chunk < rows ? first + chunk : rows;
+    for (long long base = first + rl; base < stop; base += span) {
+        long long row[kFpU], src[kFpU];
+        bool inb[kFpU], ok[kFpU];
+        float w[kFpU][3];
+        const float *qa[kFpU][3];
+#pragma unroll
+        for (int u = 0; u < kFpU; ++u) {
+            const long long rr = base + u * stride;
+            inb[u] = rr < rows;
+            row[u] = inb[u] ? rr : 0;
+            ok[u] = inb[u] && ((mask[row[u] >> 5] >> (unsigned)(row[u] & 31)) & 1u);
+            src[u] = ok[u] ? rr : row[u] / n * n;                 // the cloud's first row: always valid
+        }
+#pragma unroll
+        for (int u = 0; u < kFpU; ++u) {
+            const long long r = src[u];
+            const float *dp = dist + r * 3;
+            const int *ip = idx + r * 3;
+            // the weights exactly as pn2_fp_interp_concat forms them (csrc/interpolate.hip, pointnet_util.py:212-215)
+            const float r1 = __fdiv_rn(1.0f, fmaxf(dp[0], 1e-10f)), r2 = __fdiv_rn(1.0f, fmaxf(dp[1], 1e-10f)),
+                        r3 = __fdiv_rn(1.0f, fmaxf(dp[2], 1e-10f));
+            const float norm = __fadd_rn(__fadd_rn(r1, r2), r3);
+            w[u][0] = __fdiv_rn(r1, norm); w[u][1] = __fdiv_rn(r2, norm); w[u][2] = __fdiv_rn(r3, norm);
+            if (q == 0 && inb[u] && weight) {
+                float *wp = weight + row[u] * 3;
+                wp[0] = ok[u] ? w[u][0] : 0.0f; wp[1] = ok[u] ? w[u][1] : 0.0f; wp[2] = ok[u] ? w[u][2] : 0.0f;
+            }
+            const float *qb = Q + (r / n) * (long long)m * C + col;
+            qa[u][0] = qb + (long long)ip[0] * C; qa[u][1] = qb + (long long)ip[1] * C; qa[u][2] = qb + (long long)ip[2] * C;
+        }
+        float4 a[kFpU][3], zo[kFpU];
+#pragma unroll
+        for (int u = 0; u < kFpU; ++u) {
+            a[u][0] = fp_ld4(qa[u][0]); a[u][1] = fp_ld4(qa[u][1]); a[u][2] = fp_ld4(qa[u][2]);
+            zo[u] = (add && ok[u]) ? fp_ld4(z + row[u] * C + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < kFpU; ++u) {
+            float v[4] = {fp_interp3(a[u][0].x, a[u][1].x, a[u][2].x, w[u][0], w[u][1], w[u][2]),
+                          fp_interp3(a[u][0].y, a[u][1].y, a[u][2].y, w[u][0], w[u][1], w[u][2]),
+                          fp_interp3(a[u][0].z, a[u][1].z, a[u][2].z, w[u][0], w[u][1], w[u][2]),
+                          fp_interp3(a[u][0].w, a[u][1].w, a[u][2].w, w[u][0], w[u][1], w[u][2])};
+            if (add) { v[0] = __fadd_rn(v[0], zo[u].x); v[1] = __fadd_rn(v[1], zo[u].y); v[2] = __fadd_rn(v[2], zo[u].z); v[3] = __fadd_rn(v[3], zo[u].w); }
+            if (ok[u]) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { s1[i] += (double)v[i]; s2[i] += (double)v[i] * (double)v[i]; }
+                *reinterpret_cast<float4 *>(z + row[u] * C + col) = make_float4(v[0], v[1], v[2], v[3]);
+            } else if (inb[u]) {
+                *reinterpret_cast<float4 *>(z + row[u] * C + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    }
+    __shared__ double red[2][kFpThreads][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { red[0][threadIdx.x][i] = s1[i]; red[1][threadIdx.x][i] = s2[i]; }
+    __syncthreads();
+    if (rl == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            double x = 0.0, y = 0.0;
+            for (int k = 0; k < rpb; ++k) { x += red[0][k * qpr + q][i]; y += red[1][k * qpr + q][i]; }
+            stats[((size_t)blockIdx.x * 2) * C + col + i] = x;
+            stats[((size_t)blockIdx.x * 2 + 1) * C + col + i] = y;
+        }
+    }
+}
+
 // dz_1 = s dy_1 - c0 - c1 z_1, the operations of the GEMMs' A_DZ prologue (train_mlp_device.h, tl_finish), in place over dy_1
 __global__ __launch_bounds__(256) void tl_fp_l1_dz_kernel(long long total4, int C, const float *__restrict__ z, float *g,
                                                           const float *__restrict__ coef)
@@ -132,6 +233,26 @@ __global__ __launch_bounds__(256) void tl_fp_l1_dz_kernel(long long total4, int 
         o.y = __fsub_rn(__fsub_rn(__fmul_rn(s.y, dy.y), c0.y), __fmul_rn(c1.y, zz.y));
         o.z = __fsub_rn(__fsub_rn(__fmul_rn(s.z, dy.z), c0.z), __fmul_rn(c1.z, zz.z));
         o.w = __fsub_rn(__fsub_rn(__fmul_rn(s.w, dy.w), c0.w), __fmul_rn(c1.w, zz.w));
+        reinterpret_cast<float4 *>(g)[e] = o;
+    }
+}
+
+// tl_fp_l1_dz_kernel with the row mask: dz_1 = valid ? s dy_1 - c0 - c1 z_1 : +0.0, in place over dy_1
+__global__ __launch_bounds__(256) void tl_fp_l1_dz_masked_kernel(long long total4, int C, const float *__restrict__ z, float *g,
+                                                                 const float *__restrict__ coef, const unsigned *__restrict__ mask)
+{
+    const int q4 = C / 4;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total4; e += (long long)gridDim.x * 256) {
+        const long long row = e / q4;
+        const int col = (int)(e - row * q4) * 4;
+        const bool rv = (mask[row >> 5] >> (unsigned)(row & 31)) & 1u;
+        const float4 dy = reinterpret_cast<const float4 *>(g)[e], zz = reinterpret_cast<const float4 *>(z)[e];
+        const float4 s = fp_ld4(coef + col), c0 = fp_ld4(coef + C + col), c1 = fp_ld4(coef + 2 * C + col);
+        float4 o;
+        o.x = rv ? __fsub_rn(__fsub_rn(__fmul_rn(s.x, dy.x), c0.x), __fmul_rn(c1.x, zz.x)) : 0.0f;
+        o.y = rv ? __fsub_rn(__fsub_rn(__fmul_rn(s.y, dy.y), c0.y), __fmul_rn(c1.y, zz.y)) : 0.0f;
+        o.z = rv ? __fsub_rn(__fsub_rn(__fmul_rn(s.z, dy.z), c0.z), __fmul_rn(c1.z, zz.z)) : 0.0f;
+        o.w = rv ? __fsub_rn(__fsub_rn(__fmul_rn(s.w, dy.w), c0.w), __fmul_rn(c1.w, zz.w)) : 0.0f;
         reinterpret_cast<float4 *>(g)[e] = o;
     }
 }
@@ -151,23 +272,27 @@ int fp_launch_pad(const float *src, long long rows_in, int c, long long rows_out
     return launch(tl_fp_pad_kernel, dim3(grid_of(total, 4096)), dim3(256), 0, st, rows_in, c, total, cp, src, dst);
 }
 
-// z_1 (rows, C) = interp(Q) [+ z_1 when `add`]; the weights to `weight`; (nparts, 2, C) fp64 partial moments
+// z_1 (rows, C) = interp(Q) [+ z_1 when `add`]; the weights to `weight`; (nparts, 2, C) fp64 partial moments.
+// mask: the validity words of a ragged unknown side (the masked twin runs), or nullptr: every row is valid
 int fp_launch_l1_forward(long long rows, int n, int m, int C, const int *idx, const float *dist, float *weight, const float *Q,
-                         float *z, bool add, double *stats, int max_parts, hipStream_t st, int *nparts)
+                         float *z, bool add, const unsigned *mask, double *stats, int max_parts, hipStream_t st, int *nparts)
 {
     const int rpb = kFpThreads / (C / 4);
     long long blocks = (rows + (long long)rpb * kFpU - 1) / ((long long)rpb * kFpU);
     if (blocks > max_parts) blocks = max_parts;
     *nparts = (int)blocks;
-    return launch(tl_fp_l1_forward_kernel, dim3((unsigned)blocks), dim3(kFpThreads), 0, st, rows, n, m, C, idx, dist, weight, Q, z,
-                  add ? 1 : 0, stats);
+    const dim3 grid((unsigned)blocks), block(kFpThreads);
+    if (mask) return launch(tl_fp_l1_forward_masked_kernel, grid, block, 0, st, rows, n, m, C, idx, dist, weight, Q, z, add ? 1 : 0, mask, stats);
+    return launch(tl_fp_l1_forward_kernel, grid, block, 0, st, rows, n, m, C, idx, dist, weight, Q, z, add ? 1 : 0, stats);
 }
 
-// dz_1 = s dy_1 - c0 - c1 z_1 in place over dy_1 (coef: (3, C))
-int fp_launch_l1_dz(long long rows, int C, const float *z, float *g, const float *coef, hipStream_t st)
+// dz_1 = s dy_1 - c0 - c1 z_1 in place over dy_1 (coef: (3, C)); mask as above: +0.0 on a padding row
+int fp_launch_l1_dz(long long rows, int C, const float *z, float *g, const float *coef, const unsigned *mask, hipStream_t st)
 {
     const long long total4 = rows * C / 4;
-    return launch(tl_fp_l1_dz_kernel, dim3(grid_of(total4, 8192)), dim3(256), 0, st, total4, C, z, g, coef);
+    const dim3 grid(grid_of(total4, 8192));
+    if (mask) return launch(tl_fp_l1_dz_masked_kernel, grid, dim3(256), 0, st, total4, C, z, g, coef, mask);
+    return launch(tl_fp_l1_dz_kernel, grid, dim3(256), 0, st, total4, C, z, g, coef);
 }
 
 // ---- argument checks ----
@@ -271,7 +396,7 @@ extern "C" int pn2_mlp_train_backward_fp(int nlayers, const pn2_bn_layer *layers
 }
 
 // ---- the same node with a RAGGED unknown side (pn2_mlp_train_*_fp_ragged, include/pn2ops.h): TlCall::mask beside TlCall::fp.
-// The masked layer-1 passes are train_mlp_fp_ragged.hip's, everything else the masked passes of the plain-rows ragged node
+// The masked layer-1 passes are the twins above, everything else the masked passes of the plain-rows ragged node
 // (train_mlp_ragged.hip) under its one organisation (ragged_opts, train_mlp.hip). pn2_fp_src is the dense entries'.
 extern "C" int pn2_mlp_train_fp_ragged_supported(int b, int n, int m, int c2, int c1, int nlayers, const int *widths)
 {

@@ -133,7 +133,7 @@ int launch_gemm(int amode, TlGemm &p, const GemmShape &g, hipStream_t st, const 
     const dim3 grid = prep_gemm(p, g, o);
     if (nparts) *nparts = (int)grid.x;
     if (p.fin.ticket) { p.fin.total = grid.x * grid.y; p.fin.nparts = (int)grid.x; }
-    if (p.mask) return launch_gemm_masked(amode, p, g, grid, st);      // ragged rows: kernels of their own (train_mlp_ragged.hip)
+    if (p.mask) return launch_masked_gemm(amode, p, g, grid, st);      // ragged rows: kernels of their own (train_mlp_ragged.hip)
     if (g.ns == 4) return launch_gemm_ns<4>(amode, p, g, grid, st);
     if (g.ns == 2) return launch_gemm_ns<2>(amode, p, g, grid, st);
     return launch_gemm_ns<1>(amode, p, g, grid, st);

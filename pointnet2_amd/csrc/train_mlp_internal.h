@@ -1,8 +1,10 @@
 // train_mlp_internal.h -- what the files of the training node share. train_mlp.hip is its host side (the size rules, the plan,
 // the passes of both directions); train_mlp_gemm / _wgrad / _pair / _top / _l1 / _small.hip hold one kernel family each with its
 // launch functions (train_mlp_kernels.h); train_mlp_fp.hip / train_mlp_xyz.hip / train_mlp_frozen.hip the entry points, argument
-// checks and kernels of one node type each (train_mlp_fp_ragged.hip: the FP node's two vector-unit passes with a row mask). Every extern "C" entry checks its arguments, fills a TlCall and hands it to
-// tl_train_forward / tl_train_backward.
+// checks and kernels of one node type each (train_mlp_ragged.hip: the plain rows of a ragged batch, and the masked GEMM and
+// weight-gradient kernels). A kernel that takes a row mask stands beside its dense twin, and the launch function of the pair
+// chooses between them. Every extern "C" entry checks its arguments, fills a TlCall and hands it to tl_train_forward /
+// tl_train_backward.
 #pragma once
 #include "pn2_device.h"
 
@@ -60,7 +62,7 @@ struct TlCall {
     // all layers behind the last pass), and a layer that wants no parameter gradient runs no weight-gradient pass at all.
     bool frozen;
     // Plain rows of a RAGGED batch (train_mlp_ragged.hip), or an FP level whose unknown side is ragged (has_fp; rg_b = fp.b,
-    // rg_n = fp.n; train_mlp_fp_ragged.hip): row c n + i is valid iff i < clamp(lengths[c], 1, n). `mask` is the
+    // rg_n = fp.n; train_mlp_fp.hip): row c n + i is valid iff i < clamp(lengths[c], 1, n). `mask` is the
     // caller's buffer (the valid-row count, one validity word per 32 rows): forward writes it from `lengths` before its first
     // pass, backward reads it. nullptr: every row is valid.
     void *mask;
@@ -107,14 +109,10 @@ long long tl_ragged_ws_bytes(long long rows, int nlayers, const int *widths, int
 
 // ---- train_mlp_fp.hip ----
 int fp_launch_pad(const float *src, long long rows_in, int c, long long rows_out, int cp, float *dst, hipStream_t st);
+// (mask: the validity words of a ragged unknown side, or nullptr: every row is valid)
 int fp_launch_l1_forward(long long rows, int n, int m, int C, const int *idx, const float *dist, float *weight, const float *Q,
-                         float *z, bool add, double *stats, int max_parts, hipStream_t st, int *nparts);
-int fp_launch_l1_dz(long long rows, int C, const float *z, float *g, const float *coef, hipStream_t st);
-
-// ---- train_mlp_fp_ragged.hip: the same two passes with the validity words of a ragged unknown side ----
-int fp_launch_l1_forward_masked(long long rows, int n, int m, int C, const int *idx, const float *dist, float *weight, const float *Q,
-                                float *z, bool add, const unsigned *mask, double *stats, int max_parts, hipStream_t st, int *nparts);
-int fp_launch_l1_dz_masked(long long rows, int C, const float *z, float *g, const float *coef, const unsigned *mask, hipStream_t st);
+                         float *z, bool add, const unsigned *mask, double *stats, int max_parts, hipStream_t st, int *nparts);
+int fp_launch_l1_dz(long long rows, int C, const float *z, float *g, const float *coef, const unsigned *mask, hipStream_t st);
 
 // ---- train_mlp_xyz.hip: the coordinate gradients (pn2_mlp_train_backward_xyz) ----
 int xyz_launch_rows(long long rows, int C, const float *G, const float *Z, const float *coef, const int *argsel, int group_rows,

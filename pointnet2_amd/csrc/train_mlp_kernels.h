@@ -213,16 +213,17 @@ int launch_l1_wx_combine(const double *mom, int nmom, const double *l1a, int npa
                          const float *wx, long long skx, long long sn, float *gw, int accumulate, hipStream_t st);
 
 // ---- train_mlp_small.hip: the per-channel and pooling kernels, one launch each (parts: rows of the partial-sum array) ----
-int launch_bn_finalize(const double *stats, int nparts, int N, double count, const float *gamma, const float *beta,
+// (count: the row count read from device memory -- ragged rows: the number of valid rows -- or nullptr: `rows`)
+int launch_bn_finalize(const double *stats, int nparts, int N, double rows, const double *count, const float *gamma, const float *beta,
                        float *running_mean, float *running_var, float momentum, float eps, float *save, const float *bias,
                        int var_biased, hipStream_t st);
-int launch_bn_backward_finalize(const double *stats, int nparts, int N, double count, const float *gamma, const float *save,
-                                float *grad_gamma, float *grad_beta, float *coef, int accumulate, hipStream_t st);
+int launch_bn_backward_finalize(const double *stats, int nparts, int N, double rows, const double *count, const float *gamma,
+                                const float *save, float *grad_gamma, float *grad_beta, float *coef, int accumulate, hipStream_t st);
 int launch_pool_finalize(long long groups, int N, int parts, int prow, const float *pmax, const int *pamax, const float *gamma,
                          const float *save, float *out, int *argsel, float *zsel, hipStream_t st);
 int launch_pool_grad(long long groups, int N, const float *out, const float *gout, const float *zsel, float *gq, double *stats,
                      int parts, hipStream_t st);
-int launch_apply(long long total4, int N, const float *z, const float *save, float *out, hipStream_t st);
+int launch_apply(long long total4, int N, const float *z, const float *save, const unsigned *mask, float *out, hipStream_t st);
 int launch_top_grad(long long rows, int N, const float *out, const float *gout, const float *z, float *dy, double *stats, int parts,
                     hipStream_t st);
 int launch_pool_weights(long long groups, int ns, int n, int m, const float *xyz, const float *new_xyz, const int *idx, float *w,
@@ -232,13 +233,6 @@ int launch_pool_avg(long long groups, int ns, int N, const float *z, const float
 int launch_pool_top_grad(long long rows, int ns, int N, const float *gout, const float *z, const float *save, const float *pool_w,
                          const int *argsel, float *dy, double *stats, int parts, hipStream_t st);
 int launch_identity_coef(int C, float *coef, hipStream_t st);
-// ... the two finalisations with the row count read from device memory (ragged rows: the number of valid rows)
-int launch_bn_finalize_counted(const double *stats, int nparts, int N, const double *count, const float *gamma, const float *beta,
-                               float *running_mean, float *running_var, float momentum, float eps, float *save, const float *bias,
-                               int var_biased, hipStream_t st);
-int launch_bn_backward_finalize_counted(const double *stats, int nparts, int N, const double *count, const float *gamma,
-                                        const float *save, float *grad_gamma, float *grad_beta, float *coef, int accumulate,
-                                        hipStream_t st);
 
 // ---- train_mlp_ragged.hip: plain rows of a ragged batch (pn2_mlp_train_*_ragged) ----
 // The caller's mask buffer: the number of valid rows as a double, then one validity word per 32 rows
@@ -249,8 +243,7 @@ inline const unsigned *ragged_words(const void *mask)
     return reinterpret_cast<const unsigned *>(static_cast<const char *>(mask) + kRaggedWordsOff);
 }
 int launch_ragged_mask(int b, int n, const int *lengths, void *mask, hipStream_t st);
-int launch_gemm_masked(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st);
-int launch_wgrad_masked(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st);
-int launch_apply_masked(long long total4, int N, const float *z, const float *save, const unsigned *mask, float *out, hipStream_t st);
+int launch_masked_gemm(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st);
+int launch_masked_wgrad(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st);
 
 }  // namespace pn2

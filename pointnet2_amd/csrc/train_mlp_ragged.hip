@@ -13,7 +13,9 @@
 //
 // What is here: the kernel that turns `lengths` into one validity word per 32 rows and the count; the MASKED instantiations of
 // the GEMM body (A_PLAIN / A_RELU / A_DZ) and of the weight-gradient body (dense rows, D_DZ) -- kernels of their own, the dense
-// ones are not touched; the masked apply; the entry points. The host side is train_mlp.hip's, under one fixed organisation
+// ones are not touched, launch_gemm / launch_wgrad come here when the call has a mask; the entry points. The small masked and
+// counted kernels stand beside their dense twins (train_mlp_small.hip: the apply, the finalisations; train_mlp_fp.hip: the FP
+// node's layer-1 passes) behind ONE launch function per pair. The host side is train_mlp.hip's, under one fixed organisation
 // (ragged_opts there): a data-gradient GEMM and a weight-gradient pass per layer, finalisations as launches of their own.
 #include "train_mlp_device.h"
 
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(kTlThreads) void tl_gemm_masked_kernel(const TlGemm
 }
 
 template <int NS>
-static int launch_gemm_masked_ns(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st)
+static int launch_masked_gemm_ns(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st)
 {
 #define PN2_TL_CASE(M)                                                       \
     case M: {                                                                \
@@ -101,12 +103,12 @@ static int launch_gemm_masked_ns(int amode, const TlGemm &p, const GemmShape &g,
     return PN2_E_ARG;
 }
 
-int launch_gemm_masked(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st)
+int launch_masked_gemm(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st)
 {
     if (!p.mask || p.nostats || p.fin.ticket) return PN2_E_ARG;    // (no frozen form, no folded finalisation: its count is a value)
-    if (g.ns == 4) return launch_gemm_masked_ns<4>(amode, p, g, grid, st);
-    if (g.ns == 2) return launch_gemm_masked_ns<2>(amode, p, g, grid, st);
-    return launch_gemm_masked_ns<1>(amode, p, g, grid, st);
+    if (g.ns == 4) return launch_masked_gemm_ns<4>(amode, p, g, grid, st);
+    if (g.ns == 2) return launch_masked_gemm_ns<2>(amode, p, g, grid, st);
+    return launch_masked_gemm_ns<1>(amode, p, g, grid, st);
 }
 
 // ---- the weight-gradient pass with the row mask (tl_wgrad_body.inc, PN2_MASKED): dense rows, dz from (dy, z) ----
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(kTlThreads) void tl_wgrad_masked_kernel(const TlWgr
 }
 
 template <int TPW>
-static int launch_wgrad_masked_tpw(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st)
+static int launch_masked_wgrad_tpw(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st)
 {
 #define PN2_WG_CASE(U)                                                          \
     if (w.upw == U) {                                                           \
@@ -140,37 +142,11 @@ static int launch_wgrad_masked_tpw(const TlWgrad &p, const WgradShape &w, dim3 g
     return PN2_E_ARG;
 }
 
-int launch_wgrad_masked(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st)
+int launch_masked_wgrad(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st)
 {
     if (!p.mask || p.dy_w || p.dmode != A_DZ || (p.amode != A_PLAIN && p.amode != A_RELU)) return PN2_E_ARG;
-    return w.tpw == 1 ? launch_wgrad_masked_tpw<1>(p, w, grid, st) : w.tpw == 2 ? launch_wgrad_masked_tpw<2>(p, w, grid, st)
-                                                                                 : launch_wgrad_masked_tpw<4>(p, w, grid, st);
-}
-
-// ---- out = relu(a z + c) on the valid rows, exactly 0 on the others (tl_apply_kernel with the mask) ----
-__global__ __launch_bounds__(256) void tl_apply_masked_kernel(long long total4, int N, const float *__restrict__ z,
-                                                              const float *__restrict__ save, const unsigned *__restrict__ mask,
-                                                              float *__restrict__ out)
-{
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
-        const long long row = (i * 4) / N;
-        const int c = (int)(i * 4 - row * N);
-        const bool rv = (mask[row >> 5] >> (unsigned)(row & 31)) & 1u;
-        const float4 zz = ld4(z + i * 4), a = ld4(save + 2 * N + c), cc = ld4(save + 3 * N + c);
-        float4 o;
-        o.x = rv ? vmax(__fadd_rn(__fmul_rn(a.x, zz.x), cc.x), 0.0f) : 0.0f;
-        o.y = rv ? vmax(__fadd_rn(__fmul_rn(a.y, zz.y), cc.y), 0.0f) : 0.0f;
-        o.z = rv ? vmax(__fadd_rn(__fmul_rn(a.z, zz.z), cc.z), 0.0f) : 0.0f;
-        o.w = rv ? vmax(__fadd_rn(__fmul_rn(a.w, zz.w), cc.w), 0.0f) : 0.0f;
-        *reinterpret_cast<float4 *>(out + i * 4) = o;
-    }
-}
-
-int launch_apply_masked(long long total4, int N, const float *z, const float *save, const unsigned *mask, float *out, hipStream_t st)
-{
-    long long blocks = (total4 + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    return launch(tl_apply_masked_kernel, dim3((unsigned)blocks), dim3(256), 0, st, total4, N, z, save, mask, out);
+    return w.tpw == 1 ? launch_masked_wgrad_tpw<1>(p, w, grid, st) : w.tpw == 2 ? launch_masked_wgrad_tpw<2>(p, w, grid, st)
+                                                                                 : launch_masked_wgrad_tpw<4>(p, w, grid, st);
 }
 
 // b clouds of n rows -> the row count the node runs on, or 0: not a positive multiple of 32 below 2^31

@@ -170,6 +170,25 @@ __global__ __launch_bounds__(256) void tl_apply_kernel(long long total4, int N, 
     }
 }
 
+// ... on the rows of a ragged batch (train_mlp_ragged.hip): out = relu(a z + c) on the valid rows, exactly 0 on the others
+__global__ __launch_bounds__(256) void tl_apply_masked_kernel(long long total4, int N, const float *__restrict__ z,
+                                                              const float *__restrict__ save, const unsigned *__restrict__ mask,
+                                                              float *__restrict__ out)
+{
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+        const long long row = (i * 4) / N;
+        const int c = (int)(i * 4 - row * N);
+        const bool rv = (mask[row >> 5] >> (unsigned)(row & 31)) & 1u;
+        const float4 zz = ld4(z + i * 4), a = ld4(save + 2 * N + c), cc = ld4(save + 3 * N + c);
+        float4 o;
+        o.x = rv ? vmax(__fadd_rn(__fmul_rn(a.x, zz.x), cc.x), 0.0f) : 0.0f;
+        o.y = rv ? vmax(__fadd_rn(__fmul_rn(a.y, zz.y), cc.y), 0.0f) : 0.0f;
+        o.z = rv ? vmax(__fadd_rn(__fmul_rn(a.z, zz.z), cc.z), 0.0f) : 0.0f;
+        o.w = rv ? vmax(__fadd_rn(__fmul_rn(a.w, zz.w), cc.w), 0.0f) : 0.0f;
+        *reinterpret_cast<float4 *>(out + i * 4) = o;
+    }
+}
+
 // unpooled top layer backward: dy = grad_out . [out > 0] (rows, N) + its two column sums
 __global__ __launch_bounds__(256) void tl_top_grad_kernel(long long rows, int N, const float *__restrict__ out,
                                                           const float *__restrict__ gout, const float *__restrict__ z,
@@ -374,35 +393,28 @@ __global__ void tl_identity_coef_kernel(int C, float *__restrict__ coef)       /
 }
 
 // ---- launches (parts: rows of the kernel's partial-sum array = gridDim.y, the caller's choice) ----
-int launch_bn_finalize(const double *stats, int nparts, int N, double count, const float *gamma, const float *beta,
+// count: the row count on the device (ragged rows: the number of valid rows), or nullptr: `rows`
+int launch_bn_finalize(const double *stats, int nparts, int N, double rows, const double *count, const float *gamma, const float *beta,
                        float *running_mean, float *running_var, float momentum, float eps, float *save, const float *bias,
                        int var_biased, hipStream_t st)
 {
-    return launch(tl_bn_finalize_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, stats, nparts, N, count, gamma, beta,
-                  running_mean, running_var, momentum, eps, save, bias, var_biased);
+    const dim3 grid((unsigned)((N + 7) / 8));
+    if (count)
+        return launch(tl_bn_finalize_counted_kernel, grid, dim3(256), 0, st, stats, nparts, N, count, gamma, beta, running_mean,
+                      running_var, momentum, eps, save, bias, var_biased);
+    return launch(tl_bn_finalize_kernel, grid, dim3(256), 0, st, stats, nparts, N, rows, gamma, beta, running_mean, running_var,
+                  momentum, eps, save, bias, var_biased);
 }
 
-int launch_bn_backward_finalize(const double *stats, int nparts, int N, double count, const float *gamma, const float *save,
-                                float *grad_gamma, float *grad_beta, float *coef, int accumulate, hipStream_t st)
+int launch_bn_backward_finalize(const double *stats, int nparts, int N, double rows, const double *count, const float *gamma,
+                                const float *save, float *grad_gamma, float *grad_beta, float *coef, int accumulate, hipStream_t st)
 {
-    return launch(tl_bn_backward_finalize_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, stats, nparts, N, count, gamma, save,
-                  grad_gamma, grad_beta, coef, accumulate);
-}
-
-int launch_bn_finalize_counted(const double *stats, int nparts, int N, const double *count, const float *gamma, const float *beta,
-                               float *running_mean, float *running_var, float momentum, float eps, float *save, const float *bias,
-                               int var_biased, hipStream_t st)
-{
-    return launch(tl_bn_finalize_counted_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, stats, nparts, N, count, gamma, beta,
-                  running_mean, running_var, momentum, eps, save, bias, var_biased);
-}
-
-int launch_bn_backward_finalize_counted(const double *stats, int nparts, int N, const double *count, const float *gamma,
-                                        const float *save, float *grad_gamma, float *grad_beta, float *coef, int accumulate,
-                                        hipStream_t st)
-{
-    return launch(tl_bn_backward_finalize_counted_kernel, dim3((unsigned)((N + 7) / 8)), dim3(256), 0, st, stats, nparts, N, count, gamma,
-                  save, grad_gamma, grad_beta, coef, accumulate);
+    const dim3 grid((unsigned)((N + 7) / 8));
+    if (count)
+        return launch(tl_bn_backward_finalize_counted_kernel, grid, dim3(256), 0, st, stats, nparts, N, count, gamma, save, grad_gamma,
+                      grad_beta, coef, accumulate);
+    return launch(tl_bn_backward_finalize_kernel, grid, dim3(256), 0, st, stats, nparts, N, rows, gamma, save, grad_gamma, grad_beta,
+                  coef, accumulate);
 }
 
 int launch_pool_finalize(long long groups, int N, int parts, int prow, const float *pmax, const int *pamax, const float *gamma,
@@ -421,10 +433,12 @@ int launch_pool_grad(long long groups, int N, const float *out, const float *gou
                   stats);
 }
 
-int launch_apply(long long total4, int N, const float *z, const float *save, float *out, hipStream_t st)
+// mask: the validity words of ragged rows, or nullptr: every row is valid
+int launch_apply(long long total4, int N, const float *z, const float *save, const unsigned *mask, float *out, hipStream_t st)
 {
     long long blocks = (total4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
+    if (mask) return launch(tl_apply_masked_kernel, dim3((unsigned)blocks), dim3(256), 0, st, total4, N, z, save, mask, out);
     return launch(tl_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, total4, N, z, save, out);
 }
 

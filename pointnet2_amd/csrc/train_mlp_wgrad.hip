@@ -94,7 +94,7 @@ int launch_wgrad(TlWgrad &p, const WgradShape &w, const pn2_bn_layer &L, hipStre
     (void)clear_async(tbuf, 48 * sizeof(unsigned long long), st);
     p.timing = tbuf;
 #endif
-    int rc = p.mask ? launch_wgrad_masked(p, w, grid, st)          // ragged rows: kernels of their own (train_mlp_ragged.hip)
+    int rc = p.mask ? launch_masked_wgrad(p, w, grid, st)          // ragged rows: kernels of their own (train_mlp_ragged.hip)
            : w.tpw == 1 ? launch_wgrad_tpw<1>(p, w, grid, st) : w.tpw == 2 ? launch_wgrad_tpw<2>(p, w, grid, st)
                                                                              : launch_wgrad_tpw<4>(p, w, grid, st);
     if (rc) return rc;

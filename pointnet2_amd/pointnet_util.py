@@ -664,26 +664,28 @@ class PointnetFPModule(nn.Module):
             return sa_mlp.fp_mlp(points2, points1, g.idx, g.dist, self._packed(points2.shape[2], c1, kind, points2.device))
         return self._stack_on(xyz1, points1, points2, g)
 
-    def _stack_on(self, xyz1, points1, points2, g):
-        """Everything after :211 but the inference kernels, on three_nn's result g (dist, idx and perhaps a plan)."""
+    def _stack_on(self, xyz1, points1, points2, g, lengths=None, node_ok=train_mlp.fp_level_supported, paths=None):
+        """Everything after :211 but the inference kernels, on three_nn's result g (dist, idx and perhaps a plan).
+        lengths: _forward_ragged's fused case -- it has found the mode to be "fused_train" and gives its own condition for the
+        one-node form (node_ok) and its last_path values (paths: of concat + stack, of the node)."""
         dist, idx, plan = g.dist, g.idx, getattr(g, "plan", None)
         b, n = xyz1.shape[0], xyz1.shape[1]
         m, c2 = points2.shape[1], points2.shape[2]
         c1 = points1.shape[2] if points1 is not None else 0
-        mode = self._train_mode(points1, points2, b * n)
+        mode = self._train_mode(points1, points2, b * n) if lengths is None else "fused_train"
         if mode is None:                                                        # layer by layer
             return self._after_weights(points1, points2, idx, _inverse_distance_weights(dist), plan)
         # ONE launch for weights + interpolation + concatenation (+ the zero pad of an odd width), then the layer stack as one
         # autograd node (train_mlp.py) with batch-statistics batch norm -- or, "fused_frozen", the running statistics; backward:
         # the stack's kernels, one split + the segmented scatter of three_interpolate's gradient
-        self.last_path = mode
         plan = self._plan_of(idx, m, plan)
-        if mode == "fused_train" and train_mlp.fp_level_preferred(b, n, m, c2) and \
-                train_mlp.fp_level_supported(self.mlp.net, b, n, m, c2, c1):
+        node = mode == "fused_train" and train_mlp.fp_level_preferred(b, n, m, c2) and node_ok(self.mlp.net, b, n, m, c2, c1)
+        self.last_path = paths[node] if paths else mode
+        if node:
             # weights, interpolation, concatenation and the stack as ONE node, layer 1 once per known point (train_mlp_fp.hip)
-            return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist, plan=plan)     # :212-226
-        x, _ = fp_interp_concat(points2, points1, idx, dist, plan=plan)         # :212-219
-        return train_mlp.fp_mlp_train(self.mlp.net, x, cin=c2 + c1, frozen=mode == "fused_frozen")
+            return train_mlp.fp_level_train(self.mlp.net, points2, points1, idx, dist, plan=plan, lengths=lengths)     # :212-226
+        x, _ = fp_interp_concat(points2, points1, idx, dist, plan=plan)         # :212-219, on every row
+        return train_mlp.fp_mlp_train(self.mlp.net, x, cin=c2 + c1, frozen=mode == "fused_frozen", lengths=lengths)
 
     def _forward_ragged(self, xyz1, xyz2, points1, points2, lengths1, geometry=None):
         """forward() with a ragged unknown side: cloud i's unknown points are xyz1[i, :lengths1[i]] (points1 likewise; the
@@ -714,16 +716,8 @@ class PointnetFPModule(nn.Module):
             return torch.where(valid.unsqueeze(2), out, torch.zeros((), dtype=out.dtype, device=dev))
         if self.fused_ragged_train and xyz1.is_cuda and self._train_mode(points1, points2, b * n) == "fused_train" and \
                 train_mlp.ragged_supported(self.mlp.net, b, n):
-            c1 = points1.shape[2] if points1 is not None else 0
-            m, c2 = xyz2.shape[1], points2.shape[2]
-            plan = self._plan_of(g.idx, m, getattr(g, "plan", None))
-            if self.fused_ragged_node and train_mlp.fp_level_preferred(b, n, m, c2) and \
-                    train_mlp.fp_level_ragged_supported(self.mlp.net, b, n, m, c2, c1):
-                self.last_path = "fused_train_ragged_node"
-                return train_mlp.fp_level_train(self.mlp.net, points2, points1, g.idx, g.dist, plan=plan, lengths=lens)     # :212-226
-            self.last_path = "fused_train_ragged"
-            x, _ = fp_interp_concat(points2, points1, g.idx, g.dist, plan=plan)                   # :212-219, on every row
-            return train_mlp.fp_mlp_train(self.mlp.net, x, cin=points2.shape[2] + c1, lengths=lens)
+            return self._stack_on(xyz1, points1, points2, g, lens, paths=("fused_train_ragged", "fused_train_ragged_node"),
+                                  node_ok=lambda *level: self.fused_ragged_node and train_mlp.fp_level_ragged_supported(*level))
         self.last_path = "unfused_ragged"
         interpolated = three_interpolate(points2, g.idx, _inverse_distance_weights(g.dist), plan=getattr(g, "plan", None))   # :212-216
         x = torch.cat([interpolated, points1], dim=2) if points1 is not None else interpolated   # :219

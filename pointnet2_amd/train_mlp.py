@@ -115,6 +115,13 @@ def conv_bn_pairs(net):
     return out
 
 
+def _stack_widths(pairs, padded=False):
+    """cin_1, cout_1 .. cout_L as the library's queries take them; padded: plain rows, whose input width fp_mlp_train
+    zero-pads to a multiple of 4."""
+    cin = pairs[0][0].in_channels
+    return [(cin + 3) // 4 * 4 if padded else cin] + [c.out_channels for c, _ in pairs]
+
+
 def stack_supported(net, rows, pool_rows=0, grouped=True):
     """Can pn2_mlp_train_forward run this stack on `rows` rows? (host-side check)"""
     pairs = conv_bn_pairs(net)
@@ -149,8 +156,7 @@ def pool_supported(net, rows, ns, pooling):
     code = POOLING.get(pooling)
     if code is None or not stack_supported(net, rows, ns, True):
         return False
-    pairs = conv_bn_pairs(net)
-    widths = [pairs[0][0].in_channels] + [c.out_channels for c, _ in pairs]
+    widths = _stack_widths(conv_bn_pairs(net))
     return bool(_C.lib().pn2_mlp_train_pool_supported(rows, len(widths) - 1, _widths_array(widths), ns, code))
 
 
@@ -161,8 +167,7 @@ def xyz_grad_supported(net, rows, ns, pooling, b, n, m, cfeat, has_idx=True):
     code = POOLING.get(pooling)
     if code is None or code == 2 or not stack_supported(net, rows, ns, True):
         return False
-    pairs = conv_bn_pairs(net)
-    widths = [pairs[0][0].in_channels] + [c.out_channels for c, _ in pairs]
+    widths = _stack_widths(conv_bn_pairs(net))
     gdims = (ctypes.c_int * 6)(b, n, m, ns, cfeat, 1 if has_idx else 0)
     return bool(_C.lib().pn2_mlp_train_xyz_supported(rows, len(widths) - 1, _widths_array(widths), ns, code, gdims))
 
@@ -190,8 +195,7 @@ def frozen_supported(net, rows, pool_rows=0, grouped=True, pooling="max", xyz_di
             return False
     if code == 0 and xyz_dims is None:
         return True                # as stack_supported: the max path needs no query of the library (the entries check their plan)
-    cin = pairs[0][0].in_channels
-    widths = [cin if grouped else (cin + 3) // 4 * 4] + [c.out_channels for c, _ in pairs]   # plain rows: zero-padded (fp_mlp_train)
+    widths = _stack_widths(pairs, padded=not grouped)
     gdims = None
     if xyz_dims is not None:
         if not grouped or code == 2:
@@ -208,9 +212,8 @@ def ragged_supported(net, b, n):
     pn2_mlp_train_ragged_supported: b n a positive multiple of 32, and a stack stack_supported takes as plain rows."""
     if b <= 0 or n <= 0 or not stack_supported(net, b * n, 0, False):
         return False
-    pairs = conv_bn_pairs(net)
-    widths = [(pairs[0][0].in_channels + 3) // 4 * 4] + [c.out_channels for c, _ in pairs]      # zero-padded (fp_mlp_train)
-    return bool(_C.lib().pn2_mlp_train_ragged_supported(b, n, len(pairs), _widths_array(widths)))
+    widths = _stack_widths(conv_bn_pairs(net), padded=True)
+    return bool(_C.lib().pn2_mlp_train_ragged_supported(b, n, len(widths) - 1, _widths_array(widths)))
 
 
 _PLAN_FIELDS = 14                    # PN2_RAGGED_PLAN_FIELDS
@@ -293,8 +296,11 @@ def _workspace(query_name, dev, error_text, *args):
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=dev)
 
 
-def _level_workspace(level, widths, code, backward, dev, gdims, opts, want_xyz=False):
+def _level_workspace(level, widths, code, backward, dev, gdims, opts, want_xyz=False, ragged=False):
     """... of an SA / plain-rows node: the query that belongs to the level's mode."""
+    if ragged:
+        return _workspace("pn2_mlp_train_ws_bytes_ragged", dev, "pn2_mlp_train_ragged: unsupported stack (b n % 32, widths % 4)",
+                          level.b, level.n, len(widths) - 1, _widths_array(widths), backward, opts)
     head = (level.rows, len(widths) - 1, _widths_array(widths), level.pool_rows)
     if level.frozen:
         return _workspace("pn2_mlp_train_ws_bytes_frozen", dev,
@@ -430,9 +436,62 @@ def _frozen_stat_results(grads, direct, gbias, needs):
     return result
 
 
-def _save_layers(ctx, head, weights, biases, gammas, betas, zs, saves, out, tail=()):
+def _forward_stack(level, params, keep_top=None):
+    """What every node's forward begins with -> n, dev, widths, the options in force, the layer array and `layers` for
+    _save_layers: the parameters unpacked, the pre-norm tensors z_l -- the only activations kept -- and the per-channel
+    statistics. keep_top(n, widths array, opts) false: the top layer's z is not even written (a pooled top layer on a large level)."""
+    n = len(level.pairs)
+    weights, biases, gammas, betas = _unpack_params(params, n)
+    dev = weights[0].device
+    widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
+    opts = _opts()
+    top = keep_top is None or keep_top(n, _widths_array(widths), opts)
+    zs = [torch.empty((level.rows, w), dtype=torch.float32, device=dev) if (top or l < n - 1) else None
+          for l, w in enumerate(widths[1:])]
+    saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
+    return n, dev, widths, opts, _layer_array(level, weights, biases, gammas, betas, zs, saves), (weights, biases, gammas, betas, zs, saves)
+
+
+def _backward_stack(ctx, needs=None):
+    """What every node's backward begins with -> the node's own saved tensors (head, out, tail), dev, the options forward ran
+    under, the layer array with the parameters' gradient slots, and `pgrads` for _param_grads. needs: frozen statistics -- per
+    layer which of (weight, bias, gamma, beta) want a gradient; None: batch statistics."""
+    level, widths = ctx.level, ctx.widths
+    n = len(level.pairs)
+    head, weights, biases, gammas, betas, zs, saves, out, tail = _saved_layers(ctx, n)
+    dev = out.device
+    gbias = None
+    if needs is not None:
+        grads, direct, gbias = _frozen_stat_grads(level.pairs, weights, biases, gammas, betas, widths, needs, dev)
+    else:
+        grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
+    # (frozen: the library wants the running statistics named in both directions; it only ever reads them)
+    arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=needs is not None)
+    for l in range(n):
+        arr[l].grad_accumulate = 1 if direct[l] else 0
+    return head, out, tail, dev, _opts_from(ctx.opts), arr, (needs, grads, direct, gbias, biases, widths, dev)
+
+
+def _param_grads(pgrads):
+    """... and what the node returns for the parameters, four per layer."""
+    needs, grads, direct, gbias, biases, widths, dev = pgrads
+    if needs is not None:                                      # (the conv bias takes a real gradient under frozen statistics)
+        return _frozen_stat_results(grads, direct, gbias, needs)
+    return _batch_stat_results(grads, direct, biases, widths, dev)
+
+
+def _ragged_mask(rows, dev):
+    """The buffer a node owns on ragged rows: forward writes it (the valid-row count, one validity word per 32 rows), backward
+    reads it. 16 + 4 (rows / 32) bytes, 8-byte aligned."""
+    return torch.empty((2 + (rows // 32 + 1) // 2,), dtype=torch.int64, device=dev)
+
+
+def _save_layers(ctx, level, widths, layers, head, out, tail=()):
     """save_for_backward of a training node: its own leading tensors, then per layer the weights, the biases and pre-norm tensors
     that exist, gammas, betas and statistics, the output, its own trailing tensors. _saved_layers is the inverse."""
+    weights, biases, gammas, betas, zs, saves = layers
+    ctx.level, ctx.widths = level, widths
+    ctx.opts = dict(_OPTS)                                  # backward must see the organisation forward ran under
     ctx.nhead = len(head)
     ctx.nbias = [b is not None for b in biases]
     ctx.nz = [z is not None for z in zs]
@@ -456,24 +515,18 @@ def _saved_layers(ctx, n):
 class _TrainMLP(torch.autograd.Function):
     """inputs: level, x (points (b,n,c) when grouped -- may be None -- else the (rows, cin) input), xyz and new_xyz (the
     level's own tensors when their gradients are wanted, level.xyz_grad; else None: the coordinates are constants of the node),
-    then per layer conv.weight, conv.bias (or None), bn.weight, bn.bias."""
+    lengths ((b,) i32 on the device: the plain rows of a RAGGED batch, pn2_mlp_train_*_ragged; else None), then per layer
+    conv.weight, conv.bias (or None), bn.weight, bn.bias. On ragged rows the node owns the validity mask: forward writes it, it
+    is saved behind everything else with lengths, and the host never reads lengths -- no synchronisation in either direction."""
 
     @staticmethod
-    def forward(ctx, level, x, xyz_in, new_xyz_in, *params):
-        n = len(level.pairs)
-        weights, biases, gammas, betas = _unpack_params(params, n)
-        dev = weights[0].device
+    def forward(ctx, level, x, xyz_in, new_xyz_in, lengths, *params):
         rows = level.rows
-        widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
-        warr = _widths_array(widths)
-        opts = _opts()
         code = level.pooling if level.pool_rows else 0
-        # (the averaging modes always keep z_L: a mean does not commute with batch norm + ReLU)
-        keep_top = code != 0 or bool(_C.lib().pn2_mlp_train_top_stored_ex(rows, n, warr, level.pool_rows, opts))
-        # pre-norm tensors z_l, the only activations kept; the pooled top layer's is not even written on large levels
-        zs = [torch.empty((rows, w), dtype=torch.float32, device=dev) if (keep_top or l < n - 1) else None
-              for l, w in enumerate(widths[1:])]
-        saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
+        ragged = lengths is not None
+        # (the averaging modes always keep z_L: a mean does not commute with batch norm + ReLU; ragged rows are never pooled)
+        n, dev, widths, opts, arr, layers = _forward_stack(level, params, lambda n, warr, opts: code != 0 or ragged or bool(
+            _C.lib().pn2_mlp_train_top_stored_ex(rows, n, warr, level.pool_rows, opts)))
         cl = widths[-1]
         pool_w = None
         if level.pool_rows:
@@ -487,12 +540,15 @@ class _TrainMLP(torch.autograd.Function):
         else:
             out = torch.empty((rows, cl), dtype=torch.float32, device=dev)
             argsel = zsel = None
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
+        mask = _ragged_mask(rows, dev) if ragged else None
         grp = _group_struct(level, x) if level.grouped else None
-        ws = _level_workspace(level, widths, code, 0, dev, _group_dims(level, x), opts)
+        ws = _level_workspace(level, widths, code, 0, dev, _group_dims(level, x), opts, ragged=ragged)
         gptr, xptr = (ctypes.byref(grp), None) if level.grouped else (None, ptr(x))
         with on_device(dev):
-            if level.frozen:        # running statistics (bn.eval()): read, never written -- no counter either
+            if ragged:
+                _C.check(_C.lib().pn2_mlp_train_forward_ragged(level.b, level.n, ptr(lengths), n, arr, xptr, ptr(out), ptr(mask),
+                                                               ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward_ragged")
+            elif level.frozen:      # running statistics (bn.eval()): read, never written -- no counter either
                 _C.check(_C.lib().pn2_mlp_train_forward_frozen(rows, n, arr, gptr, xptr, level.pool_rows, code, ptr(out),
                                                                ptr(argsel) if code in (0, 3) else None, ptr(zsel), ptr(pool_w),
                                                                ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward_frozen")
@@ -505,44 +561,37 @@ class _TrainMLP(torch.autograd.Function):
                                                            ptr(zsel), ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward")
         if not level.frozen:
             _count_batch(level.pairs)
-        ctx.level, ctx.widths, ctx.code = level, widths, code
-        ctx.opts = dict(_OPTS)                              # backward must see the organisation forward ran under
+        ctx.code = code
         if not level.pool_rows:
-            _save_layers(ctx, [x], weights, biases, gammas, betas, zs, saves, out)
+            _save_layers(ctx, level, widths, layers, [x], out, [mask, lengths] if ragged else ())
             return out
         ctx.mark_non_differentiable(argsel)
-        _save_layers(ctx, [x] if x is not None else [], weights, biases, gammas, betas, zs, saves, out,
+        _save_layers(ctx, level, widths, layers, [x] if x is not None else [], out,
                      [argsel] + [t for t in (zsel, pool_w) if t is not None])
         return out, argsel
 
     @staticmethod
     def backward(ctx, grad_out, *unused):
-        level, widths = ctx.level, ctx.widths
+        level, widths, code = ctx.level, ctx.widths, ctx.code
         n = len(level.pairs)
-        head, weights, biases, gammas, betas, zs, saves, out, tail = _saved_layers(ctx, n)
+        frozen = level.frozen
+        # (the parameters stand behind level, x, xyz, new_xyz and lengths)
+        head, out, tail, dev, opts, arr, pgrads = _backward_stack(
+            ctx, [[bool(ctx.needs_input_grad[5 + 4 * l + k]) for k in range(4)] for l in range(n)] if frozen else None)
         x = head[0] if head else None
-        code = ctx.code
         argsel = tail.pop(0) if level.pool_rows else None
         zsel = tail.pop(0) if level.pool_rows and code in (0, 3) else None
         pool_w = tail.pop(0) if code == 2 else None
-        dev = out.device
+        mask, lengths = tail if tail else (None, None)         # ragged rows: what forward saved last
         rows = level.rows
         grad_out = f32(grad_out, "grad_out")
-        frozen = level.frozen
-        if frozen:
-            needs = [[bool(ctx.needs_input_grad[4 + 4 * l + k]) for k in range(4)] for l in range(n)]
-            grads, direct, gbias = _frozen_stat_grads(level.pairs, weights, biases, gammas, betas, widths, needs, dev)
-        else:
-            grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
         need_x = ctx.needs_input_grad[1] and x is not None
         # the coordinate gradients (sa_mlp_train(..., xyz_grad=True)): written by the library, both or neither
         want_xyz = level.xyz_grad and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
         grad_xyz = grad_new_xyz = None
         grad_x = grad_rows = grad_pts = None
         gdims = _group_dims(level, x)
-        warr = _widths_array(widths)
-        opts = _opts_from(ctx.opts)
-        per_point = level.grouped and bool(_C.lib().pn2_mlp_train_layer1_per_point_ex(n, warr, gdims, opts))
+        per_point = level.grouped and bool(_C.lib().pn2_mlp_train_layer1_per_point_ex(n, _widths_array(widths), gdims, opts))
         if need_x and level.grouped and per_point:
             grad_pts = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)      # written by the library itself
         elif need_x and level.grouped:
@@ -553,17 +602,17 @@ class _TrainMLP(torch.autograd.Function):
             grad_xyz = torch.empty((level.b, level.n, 3), dtype=torch.float32, device=dev)
             if level.new_xyz is not None:
                 grad_new_xyz = torch.empty((level.b, level.m, 3), dtype=torch.float32, device=dev)
-        ws = _level_workspace(level, widths, code, 1, dev, gdims, opts, want_xyz)
+        ws = _level_workspace(level, widths, code, 1, dev, gdims, opts, want_xyz, ragged=mask is not None)
         if _KEEP_WS[0]:
             _KEEP_WS[1] = (ws, rows, widths, level.pool_rows)
-        # (frozen: the library wants the running statistics named in both directions; it only ever reads them)
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=frozen)
-        for l in range(n):
-            arr[l].grad_accumulate = 1 if direct[l] else 0
         grp = _group_struct(level, x) if level.grouped else None
         with on_device(dev):
-            if frozen:
-                gb_arr = (ctypes.c_void_p * n)(*[ptr(t) for t in gbias])
+            if mask is not None:
+                _C.check(_C.lib().pn2_mlp_train_backward_ragged(level.b, level.n, ptr(lengths), n, arr, ptr(x), ptr(out), ptr(grad_out),
+                                                                ptr(grad_x), ptr(mask), ptr(ws), opts, stream_ptr(dev)),
+                         "mlp_train_backward_ragged")
+            elif frozen:
+                gb_arr = (ctypes.c_void_p * n)(*[ptr(t) for t in pgrads[3]])
                 _C.check(_C.lib().pn2_mlp_train_backward_frozen(rows, n, arr, ctypes.byref(grp) if grp is not None else None,
                                                                 None if level.grouped else ptr(x), level.pool_rows, code, ptr(out),
                                                                 ptr(argsel) if code in (0, 3) else None, ptr(zsel), ptr(pool_w),
@@ -602,63 +651,8 @@ class _TrainMLP(torch.autograd.Function):
                     _C.check(scatter_grad(_C.lib(), "group_point", (b, npts, c, m, ns, ptr(grad_rows)), level.idx, level.plan,
                                           (ptr(grad_x),), b, npts, c, m * ns, dev), "group_point_grad")
         result = [None, grad_x if need_x else None, grad_xyz if ctx.needs_input_grad[2] else None,
-                  grad_new_xyz if ctx.needs_input_grad[3] else None]
-        if frozen:                                             # (the conv bias takes a real gradient under frozen statistics)
-            return tuple(result + _frozen_stat_results(grads, direct, gbias, needs))
-        return tuple(result + _batch_stat_results(grads, direct, biases, widths, dev))
-
-
-class _TrainMLPRagged(torch.autograd.Function):
-    """_TrainMLP's sibling for the plain rows of a ragged batch (pn2_mlp_train_*_ragged): inputs level, x (rows, cin), lengths
-    (b,) i32 on the device, then the parameters. Saved besides _TrainMLP's tensors: the validity mask forward wrote. The host
-    never reads lengths: no synchronisation in either direction."""
-
-    @staticmethod
-    def forward(ctx, level, x, lengths, *params):
-        n = len(level.pairs)
-        weights, biases, gammas, betas = _unpack_params(params, n)
-        dev = weights[0].device
-        rows = level.rows
-        widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
-        warr = _widths_array(widths)
-        opts = _opts()
-        zs = [torch.empty((rows, w), dtype=torch.float32, device=dev) for w in widths[1:]]
-        saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
-        out = torch.empty((rows, widths[-1]), dtype=torch.float32, device=dev)
-        mask = torch.empty((2 + (rows // 32 + 1) // 2,), dtype=torch.int64, device=dev)      # 16 + 4 (rows / 32) bytes, 8-byte aligned
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
-        ws = _workspace("pn2_mlp_train_ws_bytes_ragged", dev, "pn2_mlp_train_ragged: unsupported stack (b n % 32, widths % 4)",
-                        level.b, level.n, n, warr, 0, opts)
-        with on_device(dev):
-            _C.check(_C.lib().pn2_mlp_train_forward_ragged(level.b, level.n, ptr(lengths), n, arr, ptr(x), ptr(out), ptr(mask), ptr(ws),
-                                                           opts, stream_ptr(dev)), "mlp_train_forward_ragged")
-        _count_batch(level.pairs)
-        ctx.level, ctx.widths = level, widths
-        ctx.opts = dict(_OPTS)
-        _save_layers(ctx, [x], weights, biases, gammas, betas, zs, saves, out, [mask, lengths])
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        level, widths = ctx.level, ctx.widths
-        n = len(level.pairs)
-        head, weights, biases, gammas, betas, zs, saves, out, tail = _saved_layers(ctx, n)
-        x, mask, lengths = head[0], tail[0], tail[1]
-        dev = out.device
-        grad_out = f32(grad_out, "grad_out")
-        grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
-        grad_x = torch.empty((level.rows, widths[0]), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        opts = _opts_from(ctx.opts)
-        ws = _workspace("pn2_mlp_train_ws_bytes_ragged", dev, "pn2_mlp_train_ragged: unsupported stack", level.b, level.n, n,
-                        _widths_array(widths), 1, opts)
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
-        for l in range(n):
-            arr[l].grad_accumulate = 1 if direct[l] else 0
-        with on_device(dev):
-            _C.check(_C.lib().pn2_mlp_train_backward_ragged(level.b, level.n, ptr(lengths), n, arr, ptr(x), ptr(out), ptr(grad_out),
-                                                            ptr(grad_x), ptr(mask), ptr(ws), opts, stream_ptr(dev)),
-                     "mlp_train_backward_ragged")
-        return tuple([None, grad_x, None] + _batch_stat_results(grads, direct, biases, widths, dev))
+                  grad_new_xyz if ctx.needs_input_grad[3] else None, None]
+        return tuple(result + _param_grads(pgrads))
 
 
 def _params(pairs):
@@ -736,9 +730,9 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
         require(lv.frozen or xyz_grad_supported(net, lv.rows, lv.pool_rows, pooling, b, n, lv.m, points.shape[2] if points is not None else 0,
                                    idx is not None),
                 "the fused training path has no coordinate gradients for this level (pooling %r)" % (pooling,))
-        out, argsel = _TrainMLP.apply(lv, points, lv.xyz, lv.new_xyz, *_params(pairs))
+        out, argsel = _TrainMLP.apply(lv, points, lv.xyz, lv.new_xyz, None, *_params(pairs))
     else:
-        out, argsel = _TrainMLP.apply(lv, points, None, None, *_params(pairs))
+        out, argsel = _TrainMLP.apply(lv, points, None, None, None, *_params(pairs))
     if lv.pooling in (1, 2):
         return out.view(b, lv.m, -1), None
     return out.view(b, lv.m, -1), argsel.view(b, lv.m, -1)
@@ -791,11 +785,7 @@ def fp_mlp_train(net, x, cin=None, frozen=False, lengths=None):
         w = params[0]
         params[0] = torch.nn.functional.pad(w, (0, 0) * (w.dim() - 2) + (0, pad))
     lv.xyz_grad = False
-    if lengths is not None:
-        out = _TrainMLPRagged.apply(lv, x, lengths, *params)
-    else:
-        out = _TrainMLP.apply(lv, x, None, None, *params)
-    return out.view(b, n, -1)
+    return _TrainMLP.apply(lv, x, None, None, lengths, *params).view(b, n, -1)
 
 
 # ---- a feature-propagation level as ONE node with the interpolation inside (pn2_mlp_train_*_fp, csrc/train_mlp_fp.hip) ----
@@ -809,8 +799,7 @@ def fp_level_supported(net, b, n, m, c2, c1):
     pairs = conv_bn_pairs(net)
     if not pairs or len(pairs) > 7 or pairs[0][0].in_channels != c2 + c1 or not stack_supported(net, b * n, 0, False):
         return False
-    widths = [c2 + c1] + [c.out_channels for c, _ in pairs]
-    return bool(_C.lib().pn2_mlp_train_fp_supported(b, n, m, c2, c1, len(pairs), _widths_array(widths)))
+    return bool(_C.lib().pn2_mlp_train_fp_supported(b, n, m, c2, c1, len(pairs), _widths_array(_stack_widths(pairs))))
 
 
 def fp_level_ragged_supported(net, b, n, m, c2, c1):
@@ -818,9 +807,8 @@ def fp_level_ragged_supported(net, b, n, m, c2, c1):
     holds and b n is a positive multiple of 32. Mirrors pn2_mlp_train_fp_ragged_supported."""
     if b <= 0 or n <= 0 or (b * n) % 32 or not fp_level_supported(net, b, n, m, c2, c1):
         return False
-    pairs = conv_bn_pairs(net)
-    widths = [c2 + c1] + [c.out_channels for c, _ in pairs]
-    return bool(_C.lib().pn2_mlp_train_fp_ragged_supported(b, n, m, c2, c1, len(pairs), _widths_array(widths)))
+    widths = _stack_widths(conv_bn_pairs(net))
+    return bool(_C.lib().pn2_mlp_train_fp_ragged_supported(b, n, m, c2, c1, len(widths) - 1, _widths_array(widths)))
 
 
 # Where the modules take the node. It no longer forms the interpolated part of layer 1's input on the b (n - m) rows that are
@@ -853,115 +841,56 @@ def _ws_fp(level, widths, backward, dev, opts, ragged=False):
 
 
 class _TrainFP(torch.autograd.Function):
-    """inputs: level, points2 (b,m,c2), points1 (b,n,c1) or None, then per layer conv.weight, conv.bias (or None), bn.weight,
-    bn.bias. Saved: the inputs, the interpolation weights, the parameters, the pre-norm tensors z_l."""
-
-    @staticmethod
-    def forward(ctx, level, points2, points1, *params):
-        n = len(level.pairs)
-        weights, biases, gammas, betas = _unpack_params(params, n)
-        dev = weights[0].device
-        rows = level.rows
-        widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
-        opts = _opts()
-        zs = [torch.empty((rows, w), dtype=torch.float32, device=dev) for w in widths[1:]]
-        saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
-        out = torch.empty((rows, widths[-1]), dtype=torch.float32, device=dev)
-        weight = torch.empty((level.b, level.n, 3), dtype=torch.float32, device=dev)
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
-        src = _fp_src(level, points2, points1)
-        ws = _ws_fp(level, widths, 0, dev, opts)
-        with on_device(dev):
-            _C.check(_C.lib().pn2_mlp_train_forward_fp(n, arr, ctypes.byref(src), ptr(out), ptr(weight), ptr(ws), opts,
-                                                       stream_ptr(dev)), "mlp_train_forward_fp")
-        _count_batch(level.pairs)
-        ctx.level, ctx.widths = level, widths
-        ctx.opts = dict(_OPTS)
-        ctx.mark_non_differentiable(weight)
-        _save_layers(ctx, [points2] + ([points1] if points1 is not None else []) + [weight], weights, biases, gammas, betas, zs,
-                     saves, out)
-        return out, weight
-
-    @staticmethod
-    def backward(ctx, grad_out, _unused):
-        level, widths = ctx.level, ctx.widths
-        n = len(level.pairs)
-        head, weights, biases, gammas, betas, zs, saves, out, _ = _saved_layers(ctx, n)
-        points2, points1, weight = head[0], (head[1] if len(head) == 3 else None), head[-1]
-        dev = out.device
-        grad_out = f32(grad_out, "grad_out")
-        grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
-        g2 = torch.empty_like(points2) if ctx.needs_input_grad[1] else None
-        g1 = torch.empty_like(points1) if points1 is not None and ctx.needs_input_grad[2] else None
-        opts = _opts_from(ctx.opts)
-        ws = _ws_fp(level, widths, 1, dev, opts)
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
-        for l in range(n):
-            arr[l].grad_accumulate = 1 if direct[l] else 0
-        src = _fp_src(level, points2, points1)
-        with on_device(dev):
-            _C.check(_C.lib().pn2_mlp_train_backward_fp(n, arr, ctypes.byref(src), ptr(weight), ptr(out), ptr(grad_out), ptr(g2),
-                                                        ptr(g1), 1 if is_deterministic() else 0, ptr(ws), opts, stream_ptr(dev)),
-                     "mlp_train_backward_fp")
-        return tuple([None, g2, g1] + _batch_stat_results(grads, direct, biases, widths, dev))
-
-
-class _TrainFPRagged(torch.autograd.Function):
-    """_TrainFP's sibling for a ragged unknown side (pn2_mlp_train_*_fp_ragged), as _TrainMLPRagged is to _TrainMLP: inputs
-    level, points2, points1 or None, lengths (b,) i32 on the device, then the parameters. The node owns the validity mask: forward
-    writes it, it is saved with the z_l. The host never reads lengths: no synchronisation in either direction."""
+    """inputs: level, points2 (b,m,c2), points1 (b,n,c1) or None, lengths ((b,) i32 on the device: a ragged unknown side,
+    pn2_mlp_train_*_fp_ragged; else None), then per layer conv.weight, conv.bias (or None), bn.weight, bn.bias. Saved: the inputs,
+    the interpolation weights, the parameters, the pre-norm tensors z_l -- and, as on _TrainMLP's ragged rows, the validity mask
+    the node owns and lengths, last."""
 
     @staticmethod
     def forward(ctx, level, points2, points1, lengths, *params):
-        n = len(level.pairs)
-        weights, biases, gammas, betas = _unpack_params(params, n)
-        dev = weights[0].device
-        rows = level.rows
-        widths = [weights[0].shape[1]] + [c.out_channels for c, _ in level.pairs]
-        opts = _opts()
-        zs = [torch.empty((rows, w), dtype=torch.float32, device=dev) for w in widths[1:]]
-        saves = [torch.empty((4, w), dtype=torch.float32, device=dev) for w in widths[1:]]
-        out = torch.empty((rows, widths[-1]), dtype=torch.float32, device=dev)
+        n, dev, widths, opts, arr, layers = _forward_stack(level, params)
+        ragged = lengths is not None
+        out = torch.empty((level.rows, widths[-1]), dtype=torch.float32, device=dev)
         weight = torch.empty((level.b, level.n, 3), dtype=torch.float32, device=dev)
-        mask = torch.empty((2 + (rows // 32 + 1) // 2,), dtype=torch.int64, device=dev)      # 16 + 4 (rows / 32) bytes, 8-byte aligned
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves)
+        mask = _ragged_mask(level.rows, dev) if ragged else None
         src = _fp_src(level, points2, points1)
-        ws = _ws_fp(level, widths, 0, dev, opts, ragged=True)
+        ws = _ws_fp(level, widths, 0, dev, opts, ragged)
         with on_device(dev):
-            _C.check(_C.lib().pn2_mlp_train_forward_fp_ragged(n, arr, ctypes.byref(src), ptr(lengths), ptr(out), ptr(weight), ptr(mask),
-                                                              ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward_fp_ragged")
+            if ragged:
+                _C.check(_C.lib().pn2_mlp_train_forward_fp_ragged(n, arr, ctypes.byref(src), ptr(lengths), ptr(out), ptr(weight),
+                                                                  ptr(mask), ptr(ws), opts, stream_ptr(dev)),
+                         "mlp_train_forward_fp_ragged")
+            else:
+                _C.check(_C.lib().pn2_mlp_train_forward_fp(n, arr, ctypes.byref(src), ptr(out), ptr(weight), ptr(ws), opts,
+                                                           stream_ptr(dev)), "mlp_train_forward_fp")
         _count_batch(level.pairs)
-        ctx.level, ctx.widths = level, widths
-        ctx.opts = dict(_OPTS)
         ctx.mark_non_differentiable(weight)
-        _save_layers(ctx, [points2] + ([points1] if points1 is not None else []) + [weight], weights, biases, gammas, betas, zs,
-                     saves, out, [mask, lengths])
+        _save_layers(ctx, level, widths, layers, [points2] + ([points1] if points1 is not None else []) + [weight], out,
+                     [mask, lengths] if ragged else ())
         return out, weight
 
     @staticmethod
     def backward(ctx, grad_out, _unused):
         level, widths = ctx.level, ctx.widths
         n = len(level.pairs)
-        head, weights, biases, gammas, betas, zs, saves, out, tail = _saved_layers(ctx, n)
+        head, out, tail, dev, opts, arr, pgrads = _backward_stack(ctx)
         points2, points1, weight = head[0], (head[1] if len(head) == 3 else None), head[-1]
-        mask, lengths = tail[0], tail[1]
-        dev = out.device
+        mask, lengths = tail if tail else (None, None)
         grad_out = f32(grad_out, "grad_out")
-        grads, direct = _batch_stat_grads(level.pairs, weights, gammas, betas)
         g2 = torch.empty_like(points2) if ctx.needs_input_grad[1] else None
         g1 = torch.empty_like(points1) if points1 is not None and ctx.needs_input_grad[2] else None
-        opts = _opts_from(ctx.opts)
-        ws = _ws_fp(level, widths, 1, dev, opts, ragged=True)
-        arr = _layer_array(level, weights, biases, gammas, betas, zs, saves, grads, update_running=False)
-        for l in range(n):
-            arr[l].grad_accumulate = 1 if direct[l] else 0
+        ws = _ws_fp(level, widths, 1, dev, opts, mask is not None)
         src = _fp_src(level, points2, points1)
+        det = 1 if is_deterministic() else 0
         with on_device(dev):
-            _C.check(_C.lib().pn2_mlp_train_backward_fp_ragged(n, arr, ctypes.byref(src), ptr(lengths), ptr(weight), ptr(out),
-                                                               ptr(grad_out), ptr(g2), ptr(g1), 1 if is_deterministic() else 0,
-                                                               ptr(mask), ptr(ws), opts, stream_ptr(dev)),
-                     "mlp_train_backward_fp_ragged")
-        return tuple([None, g2, g1, None] + _batch_stat_results(grads, direct, biases, widths, dev))
+            if mask is not None:
+                _C.check(_C.lib().pn2_mlp_train_backward_fp_ragged(n, arr, ctypes.byref(src), ptr(lengths), ptr(weight), ptr(out),
+                                                                   ptr(grad_out), ptr(g2), ptr(g1), det, ptr(mask), ptr(ws), opts,
+                                                                   stream_ptr(dev)), "mlp_train_backward_fp_ragged")
+            else:
+                _C.check(_C.lib().pn2_mlp_train_backward_fp(n, arr, ctypes.byref(src), ptr(weight), ptr(out), ptr(grad_out), ptr(g2),
+                                                            ptr(g1), det, ptr(ws), opts, stream_ptr(dev)), "mlp_train_backward_fp")
+        return tuple([None, g2, g1, None] + _param_grads(pgrads))
 
 
 def fp_level_train(net, points2, points1, idx, dist, return_weight=False, plan=None, lengths=None):
@@ -1004,9 +933,6 @@ def fp_level_train(net, points2, points1, idx, dist, return_weight=False, plan=N
     lv = _FpLevel()
     lv.pairs, lv.rows, lv.b, lv.n, lv.m, lv.c2, lv.c1, lv.idx, lv.dist = pairs, b * n, b, n, m, c2, c1, idx, dist
     lv.plan = None if plan is None else plan.check("interpolate", b, m, 3 * n, points2.device)
-    if lengths is not None:
-        out, weight = _TrainFPRagged.apply(lv, points2, points1, lengths, *_params(pairs))
-    else:
-        out, weight = _TrainFP.apply(lv, points2, points1, *_params(pairs))
+    out, weight = _TrainFP.apply(lv, points2, points1, lengths, *_params(pairs))
     out = out.view(b, n, -1)
     return (out, weight) if return_weight else out

@@ -1,5 +1,5 @@
 """The FP training node with a RAGGED unknown side (train_mlp.fp_level_train(..., lengths=), pn2_mlp_train_*_fp_ragged,
-csrc/train_mlp_fp_ragged.hip) on the GPU: layer 1 once per known point with a row mask inside -- batch statistics, running
+csrc/train_mlp_fp.hip) on the GPU: layer 1 once per known point with a row mask inside -- batch statistics, running
 averages and every gradient over the valid rows only, the (b, n, c2 + c1) tensor never written.
 
 Case A: b 4, n 1024, m 256, lengths (1024, 700, 300, 64), c2 35, c1 6, stack 64 -> 32: both zero-pad copies (35 -> 36, 6 -> 8);
@@ -408,7 +408,7 @@ def test_module_takes_the_node_only_where_asked_and_preferred(cuda, monkeypatch)
                 continue
             grads = torch.autograd.grad(out, [a2, a1] + list(mod.mlp.net.parameters()), gout, retain_graph=True)
             fn = out.grad_fn
-            while type(fn).__name__ != "_TrainFPRaggedBackward":
+            while type(fn).__name__ != "_TrainFPBackward":
                 fn = fn.next_functions[0][0]
             saved = fn.saved_tensors[:-2]
             nl = len(case["mlp"])

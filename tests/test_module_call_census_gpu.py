@@ -55,6 +55,8 @@ CASES = [
     ("fp_eval", "fp", {}, {}, "eval", False, ALL),
     ("fp_train_node", "fp_node", {}, {}, "train", False, ("plain", "geometry")),
     ("fp_train_concat", "fp", {}, {}, "train", False, ALL),
+    ("fp_train_ragged", "fp", {}, {"fused_ragged_train": True}, "train", False, ("lengths",)),
+    ("fp_train_ragged_node", "fp_node", {}, {"fused_ragged_train": True, "fused_ragged_node": True}, "train", False, ("lengths",)),
     ("fp_frozen", "fp", {}, {"fused_frozen_bn": True}, "frozen", False, ("plain", "geometry")),
     ("fp_unfused_train", "fp", {}, {"fused_mlp": False}, "train", False, ("plain", "geometry")),
     ("fp_unfused_eval", "fp", {}, {"fused_mlp": False}, "eval", False, ("plain", "geometry")),
