@@ -305,7 +305,7 @@ int pn2_query_ball_group_xyz_ex(int b, int n, int m, float radius, int nsample, 
 
 /* Multi-radius form for multi-scale grouping (pointnet_sa_module_msg, utils/pointnet_util.py:175-186: one
  * query_ball_point + group_point + centroid subtraction PER RADIUS over the same xyz / new_xyz): the cloud is
- * staged and binned ONCE per workgroup (cells sized for the smallest radius) and queried once per radius.
+ * staged and binned ONCE per workgroup (cells sized for the bin radius, see the plan entry below) and queried once per radius.
  * radii / nsamples: HOST arrays of nscales (<= 4) entries; idx / pts_cnt / grouped_xyz: HOST arrays of nscales
  * DEVICE pointers, scale i shaped (b,m,nsamples[i]) / (b,m) / (b,m,nsamples[i],3); the arrays themselves or
  * single entries of pts_cnt and of one of idx / grouped_xyz may be NULL. Every output is bit-identical to
@@ -315,6 +315,18 @@ int pn2_query_ball_group_xyz_ex(int b, int n, int m, float radius, int nsample, 
 int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
                                  const float *xyz1, const float *xyz2, int subtract_centroid, int *const *idx,
                                  int *const *pts_cnt, float *const *grouped_xyz, void *stream);
+
+/* What pn2_query_ball_group_xyz_msg launches for these shapes: host only, no device, and the launcher takes its decision through
+ * the same function. Returns the launcher's code for the shapes (PN2_E_ARG / PN2_E_SHAPE as there, with nothing written;
+ * PN2_E_TOO_LARGE: no LDS geometry fits, info[0] = 0). info (PN2_BQ_MSG_PLAN_FIELDS ints, may be NULL):
+ *   [0] threads per workgroup (0: nothing is launched -- b = 0, m = 0 or an error)   [1] LDS cap of the chosen geometry, bytes
+ *   [2] dynamic LDS requested, bytes   [3] use_cells: 1 = the workgroups try to bin their cloud, 0 = staged and swept
+ *   [4] qpb, queries per workgroup (a multiple of the workgroup's granule: may exceed m)   [5] parts, workgroups per cloud
+ *   [6 + i] lanes per query (8, 16 or 32) of scale i's pass over the cell list, 0 from nscales on
+ * bin_radius (may be NULL): the radius the cells are sized for -- the second smallest of three or more radii, else the smallest. */
+#define PN2_BQ_MSG_PLAN_FIELDS 10
+int pn2_query_ball_group_xyz_msg_plan(int b, int n, int m, int nscales, const float *radii, const int *nsamples, int *info,
+                                      float *bin_radius);
 
 /* pn2_three_nn with the kernel chosen by the caller (results never depend on it; tests force each, scripts time them):
  * 0 = the library's choice, 1 = the sweep of every known point (round 1), 2 = the cell list (round 6: the known points binned

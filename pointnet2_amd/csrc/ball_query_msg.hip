@@ -149,40 +149,36 @@ static size_t msg_pick_lpq(int n, int nthreads, size_t cap, int qpb, BqScales &s
     return stride;
 }
 
-template <int NT>
-static int launch_msg(int b, int n, int m, int use_cells, int max_ns, int qpb, size_t wave_stride, const BqScales &sc,
-                      const float *xyz1, const float *xyz2, int subtract, hipStream_t st)
-{
-    const int parts = (m + qpb - 1) / qpb;
-    const size_t cells = sizeof(float4) * (size_t)n + sizeof(int) * (size_t)kBqTabInts + (size_t)(NT / 64) * wave_stride + kBqMiscBytes;
-    const size_t sweep = msg_sweep_bytes(n, max_ns, NT);
-    const size_t lds = cells > sweep ? cells : sweep;
-    auto kern = ball_query_msg_kernel<NT>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3((unsigned)parts * b), dim3(NT), lds, st, b, n, m, qpb, parts, use_cells, max_ns, (int)wave_stride, sc,
-                  xyz1, xyz2, subtract);
-}
+// Everything the host decides about one call, taken ONCE: the launcher and pn2_query_ball_group_xyz_msg_plan both read it from
+// msg_plan below, so what the plan entry reports is what is launched.
+struct MsgPlan {
+    int nt;                               // threads per workgroup; 0: nothing to launch (b == 0 or m == 0)
+    size_t cap, lds, wave_stride;         // LDS cap of the geometry, dynamic LDS requested, bytes between two waves' areas
+    int use_cells, qpb, parts, max_ns;
+    BqScales sc;                          // thr, radius, nsample, lpq per scale and bin_radius; the output pointers are the launcher's
+};
 
-}  // namespace pn2
-
-extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
-                                            const float *xyz1, const float *xyz2, int subtract_centroid, int *const *idx,
-                                            int *const *pts_cnt, float *const *grouped_xyz, void *stream)
+// The checks of the arguments that need no pointer but radii / nsamples (the launcher looks at its output pointers next).
+static int msg_check_args(int b, int n, int m, int nscales, const float *radii, const int *nsamples)
 {
-    using namespace pn2;
     if (nscales <= 0 || nscales > kBqMaxScales || !radii || !nsamples) return PN2_E_ARG;
     if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
     for (int i = 0; i < nscales; ++i)
         if (!(radii[i] > 0.0f) || nsamples[i] <= 0) return PN2_E_ARG;   // tf_grouping.cpp:71,74
-    BqScales sc;
+    return PN2_OK;
+}
+
+static int msg_plan(int b, int n, int m, int nscales, const float *radii, const int *nsamples, MsgPlan &p)
+{
+    if (int rc = msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
+    p.nt = 0;
+    p.cap = p.lds = p.wave_stride = 0;
+    p.use_cells = p.qpb = p.parts = p.max_ns = 0;
+    BqScales &sc = p.sc;
     sc.count = nscales;
-    int max_ns = 0;
     for (int i = 0; i < nscales; ++i) {
-        sc.s[i] = {pn2_ball_threshold(radii[i]), radii[i], nsamples[i], 8, idx ? idx[i] : nullptr,
-                   pts_cnt ? pts_cnt[i] : nullptr, grouped_xyz ? grouped_xyz[i] : nullptr};
-        if (!sc.s[i].idx && !sc.s[i].grouped) return PN2_E_NULL;
-        max_ns = nsamples[i] > max_ns ? nsamples[i] : max_ns;
-        if ((long long)b * m * nsamples[i] * 3 > (1ll << 40)) return PN2_E_TOO_LARGE;
+        sc.s[i] = {pn2_ball_threshold(radii[i]), radii[i], nsamples[i], 8, nullptr, nullptr, nullptr};
+        p.max_ns = nsamples[i] > p.max_ns ? nsamples[i] : p.max_ns;
     }
     // Cell size: the SECOND smallest radius when there are three or more (else the smallest). Cells sized for
     // the smallest radius make every larger radius walk "wide" runs (whole y-ranges of a z-slab, every x): at
@@ -196,23 +192,80 @@ extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, co
         }
         sc.bin_radius = (nscales >= 3) ? r2 : r1;
     }
+    for (int i = 0; i < nscales; ++i)
+        if ((long long)b * m * nsamples[i] * 3 > (1ll << 40)) return PN2_E_TOO_LARGE;
     if (b == 0 || m == 0) return PN2_OK;
-    if (!xyz1 || !xyz2) return PN2_E_NULL;
     if ((long long)b * n * 3 > INT_MAX) return PN2_E_TOO_LARGE;
     if (n > kBqCellsMaxPoints) return PN2_E_TOO_LARGE;          // callers launch the single-radius operator per scale
     // the binning pass is amortised over every radius of the level: worth it from mid-sized clouds on
-    const int use_cells = n >= 1024 && (long long)b * m * nscales >= 8192;
-    hipStream_t st = as_stream(stream);
+    p.use_cells = n >= 1024 && (long long)b * m * nscales >= 8192;
     // geometry: two 512-thread workgroups per CU when everything fits in half the LDS, else one of 1024, else one of 512
     struct Geom { int nt; size_t cap; };
     static const Geom order[] = {{512, 80 * 1024}, {1024, 160 * 1024}, {512, 160 * 1024}};
     for (const Geom &g : order) {
-        if (msg_sweep_bytes(n, max_ns, g.nt) > g.cap) continue;
-        const int qpb = msg_qpb(b, m, g.nt, use_cells);
+        if (msg_sweep_bytes(n, p.max_ns, g.nt) > g.cap) continue;
+        const int qpb = msg_qpb(b, m, g.nt, p.use_cells);
         const size_t stride = msg_pick_lpq(n, g.nt, g.cap, qpb, sc);
         if (!stride) continue;
-        if (g.nt == 1024) return launch_msg<1024>(b, n, m, use_cells, max_ns, qpb, stride, sc, xyz1, xyz2, subtract_centroid, st);
-        return launch_msg<512>(b, n, m, use_cells, max_ns, qpb, stride, sc, xyz1, xyz2, subtract_centroid, st);
+        const size_t cells = sizeof(float4) * (size_t)n + sizeof(int) * (size_t)kBqTabInts + (size_t)(g.nt / 64) * stride + kBqMiscBytes;
+        const size_t sweep = msg_sweep_bytes(n, p.max_ns, g.nt);
+        p.nt = g.nt;
+        p.cap = g.cap;
+        p.lds = cells > sweep ? cells : sweep;
+        p.wave_stride = stride;
+        p.qpb = qpb;
+        p.parts = (m + qpb - 1) / qpb;
+        return PN2_OK;
     }
     return PN2_E_TOO_LARGE;
+}
+
+template <int NT>
+static int launch_msg(int b, int n, int m, const MsgPlan &p, const float *xyz1, const float *xyz2, int subtract, hipStream_t st)
+{
+    auto kern = ball_query_msg_kernel<NT>;
+    if (int rc = allow_dynamic_lds(kern, p.lds)) return rc;
+    return launch(kern, dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
+                  (int)p.wave_stride, p.sc, xyz1, xyz2, subtract);
+}
+
+}  // namespace pn2
+
+extern "C" int pn2_query_ball_group_xyz_msg_plan(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
+                                                 int *info, float *bin_radius)
+{
+    using namespace pn2;
+    MsgPlan p;
+    const int rc = msg_plan(b, n, m, nscales, radii, nsamples, p);
+    if (rc == PN2_E_ARG || rc == PN2_E_SHAPE) return rc;         // nothing to report about such arguments
+    if (bin_radius) *bin_radius = p.sc.bin_radius;
+    if (info) {
+        const bool chosen = rc == PN2_OK && p.nt > 0;
+        const int head[6] = {p.nt, (int)p.cap, (int)p.lds, p.use_cells, p.qpb, p.parts};
+        for (int i = 0; i < 6; ++i) info[i] = head[i];
+        for (int i = 0; i < kBqMaxScales; ++i) info[6 + i] = (chosen && i < nscales) ? p.sc.s[i].lpq : 0;
+    }
+    return rc;
+}
+
+extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
+                                            const float *xyz1, const float *xyz2, int subtract_centroid, int *const *idx,
+                                            int *const *pts_cnt, float *const *grouped_xyz, void *stream)
+{
+    using namespace pn2;
+    if (int rc = msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
+    for (int i = 0; i < nscales; ++i)
+        if (!(idx && idx[i]) && !(grouped_xyz && grouped_xyz[i])) return PN2_E_NULL;
+    MsgPlan p;
+    if (int rc = msg_plan(b, n, m, nscales, radii, nsamples, p)) return rc;
+    if (p.nt == 0) return PN2_OK;                                // b == 0 or m == 0
+    if (!xyz1 || !xyz2) return PN2_E_NULL;
+    for (int i = 0; i < nscales; ++i) {
+        p.sc.s[i].idx = idx ? idx[i] : nullptr;
+        p.sc.s[i].cnt = pts_cnt ? pts_cnt[i] : nullptr;
+        p.sc.s[i].grouped = grouped_xyz ? grouped_xyz[i] : nullptr;
+    }
+    hipStream_t st = as_stream(stream);
+    if (p.nt == 1024) return launch_msg<1024>(b, n, m, p, xyz1, xyz2, subtract_centroid, st);
+    return launch_msg<512>(b, n, m, p, xyz1, xyz2, subtract_centroid, st);
 }

@@ -166,6 +166,25 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     return outs
 
 
+def query_ball_group_xyz_msg_plan(radius_list, nsample_list, b, n, m):
+    """What query_ball_group_xyz_msg launches for these shapes, from the launcher's own decision function
+    (pn2_query_ball_group_xyz_msg_plan): host logic, no device.
+
+    -> dict(rc, threads, lds_cap, lds_bytes, use_cells, qpb, parts, lpq=[per scale], bin_radius); rc is the launcher's code
+    (-4: no LDS geometry fits, the operator falls back to one launch per radius); threads == 0 when nothing is launched."""
+    import ctypes
+    k = len(radius_list)
+    radii = (ctypes.c_float * max(k, 1))(*[float(r) for r in radius_list])
+    nss = (ctypes.c_int * max(k, 1))(*[int(s) for s in nsample_list])
+    info = (ctypes.c_int * 10)()
+    bin_radius = ctypes.c_float(0.0)
+    rc = _C.lib().pn2_query_ball_group_xyz_msg_plan(int(b), int(n), int(m), k, radii, nss, info, ctypes.byref(bin_radius))
+    if rc in (-2, -3):
+        _C.check(rc, "query_ball_group_xyz_msg_plan")
+    return dict(rc=rc, threads=info[0], lds_cap=info[1], lds_bytes=info[2], use_cells=info[3], qpb=info[4], parts=info[5],
+                lpq=list(info[6:6 + k]), bin_radius=bin_radius.value)
+
+
 # The single overlapped launch (csrc/sa_fused.hip) is the default of sample_and_group_xyz. It can be switched
 # off -- set_overlapped_launch(False) or PN2_OVERLAP=0 in the environment at import -- in favour of the
 # two-launch path (farthest_point_sample_gather + query_ball_group_xyz): same outputs, ~2.5 % slower at the
