@@ -73,13 +73,16 @@ int pn2_query_ball_point(int b, int n, int m, float radius, int nsample, const f
                          int *idx, int *pts_cnt, void *stream);
 
 /* replaces selectionSortLauncher(b,n,m,k,dist,outi,out)  tf_grouping.cpp:108, tf_grouping_g.cu:129-132
- * dist (b,m,n) -> outi (b,m,n) i32, out (b,m,n) f32; the first k of each row are the k smallest, ascending */
+ * dist (b,m,n) -> outi (b,m,n) i32, out (b,m,n) f32; the first k of each row are the k smallest, ascending.
+ * NaN of either sign follows the reference's `<` comparisons at every row length: one in the unsorted tail is never
+ * selected, and a round whose own slot holds one swaps nothing (it stays there). */
 int pn2_selection_sort(int b, int n, int m, int k, const float *dist, int *outi, float *out, void *stream);
 
 /* knn_point (tf_grouping.py:48-73) in one kernel, without the (b,m,n) distance/index tensors: the distance
  * row ((dx*dx)+(dy*dy))+(dz*dz) of a query is built in LDS, the same k swap rounds as selectionSortLauncher
  * run on it, and only the first k (value, index) pairs are written -- identical to slicing the reference's
- * outputs, ties included. xyz1 (b,n,3), xyz2 (b,m,3) -> val (b,m,k) f32, idx (b,m,k) i32.
+ * outputs, ties included. Rows with NaN distances are outside that claim: a NaN sorts last here, where the reference's
+ * rounds leave one found at a slot below k in place. xyz1 (b,n,3), xyz2 (b,m,3) -> val (b,m,k) f32, idx (b,m,k) i32.
  * PN2_E_TOO_LARGE for n > 14336 or k > n (callers keep the matrix + pn2_selection_sort path). */
 int pn2_knn_point(int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx,
                   void *stream);

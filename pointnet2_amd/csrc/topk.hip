@@ -22,11 +22,14 @@ namespace pn2 {
 constexpr int kSortMaxLdsN = 16384;   // 8 B per element -> 128 KiB
 
 // map a float to a uint whose unsigned order equals the float `<` order;
-// +0 and -0 compare equal under `<`, so both map to the same key.
+// +0 and -0 compare equal under `<`, so both map to the same key. `c < mv` is
+// false for a NaN c of either sign: every NaN takes the top key, above +Inf
+// (by its bits a NaN with the sign set would sort below -Inf and win every round).
 __device__ __forceinline__ unsigned orderable(float f)
 {
     if (f == 0.0f) f = 0.0f;   // folds -0 into +0
     const unsigned u = (unsigned)__float_as_int(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -57,7 +60,7 @@ __global__ __launch_bounds__(64) void selection_sort_wave_kernel(int n, int k, c
             best = other < best ? other : best;
         }
         const int mn = (int)(unsigned)best;
-        if (lane == 0 && mn != s) {
+        if (lane == 0 && mn != s && !isnan(val[s])) {             // a NaN at slot s: no `c < mv` holds, the round swaps nothing
             const float tv = val[mn]; val[mn] = val[s]; val[s] = tv;
             const int ti = ind[mn]; ind[mn] = ind[s]; ind[s] = ti;
         }
