@@ -320,7 +320,8 @@ int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *
                                  int *const *pts_cnt, float *const *grouped_xyz, void *stream);
 
 /* What pn2_query_ball_group_xyz_msg launches for these shapes: host only, no device, and the launcher takes its decision through
- * the same function. Returns the launcher's code for the shapes (PN2_E_ARG / PN2_E_SHAPE as there, with nothing written;
+ * the same function. It describes pn2_query_ball_group_xyz_msg_ragged (below, "ragged batches") as well: that launch takes every
+ * host decision from the padded n, so threads, LDS, use_cells, qpb, parts and lanes per query are the same. Returns the launcher's code for the shapes (PN2_E_ARG / PN2_E_SHAPE as there, with nothing written;
  * PN2_E_TOO_LARGE: no LDS geometry fits, info[0] = 0). info (PN2_BQ_MSG_PLAN_FIELDS ints, may be NULL):
  *   [0] threads per workgroup (0: nothing is launched -- b = 0, m = 0 or an error)   [1] LDS cap of the chosen geometry, bytes
  *   [2] dynamic LDS requested, bytes   [3] use_cells: 1 = the workgroups try to bin their cloud, 0 = staged and swept
@@ -351,6 +352,14 @@ int pn2_three_nn_ex(int b, int n, int m, const float *xyz1, const float *xyz2, f
  * pn2_query_ball_group_xyz_ragged: xyz1 ragged (lengths1), the queries xyz2 (b,m,3) dense; kernel / cells_qpb as
  *   pn2_query_ball_group_xyz_ex (a cloud below 64 points takes the sweep inside the cell-list kernel); grouped_xyz NULL =
  *   plain query_ball_point.
+ * pn2_query_ball_group_xyz_msg_ragged: pn2_query_ball_group_xyz_msg with xyz1 ragged (lengths1), the queries xyz2 (b,m,3) dense:
+ *   ONE launch, one staging / binning of each cloud's own lengths1[c] points for every radius. Per cloud and radius the outputs
+ *   are pn2_query_ball_group_xyz_msg's on the slice, hence pn2_query_ball_group_xyz_ragged's called per radius, bit for bit;
+ *   every output entry is written. Geometry, LDS, qpb and lanes per query come from the padded n
+ *   (pn2_query_ball_group_xyz_msg_plan describes this launch too); on the device a cloud below 64 points is swept without
+ *   binning, a larger one bins its own points and the give-up rules apply to its own grid. Codes as the dense entry
+ *   (PN2_E_TOO_LARGE for n > 8192 or when no LDS geometry fits: call pn2_query_ball_group_xyz_ragged per radius then);
+ *   b = 0 or m = 0 is PN2_OK before lengths1 is looked at.
  * pn2_knn_point_ragged: the envelope of pn2_knn_point (n <= 14336, k <= n); where k > lengths1[c] the entries from
  *   lengths1[c] on repeat entry 0 of their row (val and idx), so every row is fully written.
  * pn2_three_nn_ragged: the UNKNOWN side xyz1 is ragged, the known side xyz2 (b,m,3) dense; variant as pn2_three_nn_ex.
@@ -360,6 +369,9 @@ int pn2_farthest_point_sample_ragged(int b, int n, int m, const float *inp, cons
 int pn2_query_ball_group_xyz_ragged(int b, int n, int m, float radius, int nsample, const float *xyz1, const int *lengths1,
                                     const float *xyz2, int subtract_centroid, int *idx, int *pts_cnt, float *grouped_xyz,
                                     int kernel, int cells_qpb, void *stream);
+int pn2_query_ball_group_xyz_msg_ragged(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
+                                        const float *xyz1, const int *lengths1, const float *xyz2, int subtract_centroid,
+                                        int *const *idx, int *const *pts_cnt, float *const *grouped_xyz, void *stream);
 int pn2_knn_point_ragged(int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2, float *val, int *idx,
                          void *stream);
 int pn2_three_nn_ragged(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2, float *dist, int *idx,

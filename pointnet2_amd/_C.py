@@ -133,6 +133,7 @@ _SIGNATURES = {
     "pn2_mlp_train_fp_ragged_plan": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i],
     "pn2_farthest_point_sample_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pn2_query_ball_group_xyz_ragged": [_i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "pn2_query_ball_group_xyz_msg_ragged": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "pn2_knn_point_ragged": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_three_nn_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
 }

@@ -54,12 +54,7 @@ __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(int n, int m, in
 // Ragged batch (pn2_query_ball_group_xyz_ragged): cloud c holds lengths1[c] <= n points in its padded (n, 3) slab. The
 // workgroup hands the body its own slabs as cloud 0 with n = n_c: staging, the +inf pad and the sweep bounds are those of the
 // dense kernel on the slice, rows at or beyond n_c are never addressed. The LDS is sized on the host for the padded n (both
-// layouts grow with n). The length is clamped into 1..n for memory safety only.
-__device__ __forceinline__ int bq_ragged_length(const int *__restrict__ lengths, int cloud, int n)
-{
-    return min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
-}
-
+// layouts grow with n). The length is clamped into 1..n for memory safety only (bq_ragged_length, ball_query_body.h).
 template <bool LDS_CLOUD, bool FUSE>
 __global__ __launch_bounds__(kBqThreads) void ball_query_ragged_kernel(int n, int m, int nsample, float thr, int qpb,
                                                                        const float *__restrict__ xyz1,

@@ -129,6 +129,13 @@ __device__ __forceinline__ int bq_poll_sample(const unsigned long long *tagged, 
     }
 }
 
+// Ragged batches (ball_query.hip, ball_query_msg.hip): the point count of cloud `cloud`, read from the device array and clamped
+// into 1..n for memory safety only; wave-uniform.
+__device__ __forceinline__ int bq_ragged_length(const int *__restrict__ lengths, int cloud, int n)
+{
+    return min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
+}
+
 // One workgroup's share of the ball queries of cloud `bi`: queries [q0, q1).
 // POLL: the query points are not read from xyz2; they are the FPS samples of the same launch, taken
 // from the tagged index stream as soon as they exist (and written to new_xyz on the way).

@@ -35,16 +35,15 @@ struct BqScales {
     BqScale s[kBqMaxScales];
 };
 
+// One workgroup's share of a cloud -- queries [q0, q1) of cloud `cloud`, every radius -- shared by the dense and the ragged
+// kernel below. n: the points of the cloud (the LDS layout and every loop bound follow it); xyz1 / xyz2: bases such that the
+// cloud's slab is xyz1 + cloud n 3 and its queries xyz2 + cloud m 3; out_rows: rows of m-major output in front of row
+// cloud m + j (0 when the scales' pointers are the tensors' bases and `cloud` does the addressing). Block-uniform throughout.
 template <int NT>
-__global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int n, int m, int qpb, int parts,
-                                                                    int use_cells, int max_ns, int wave_stride_b, BqScales sc,
-                                                                    const float *__restrict__ xyz1,
-                                                                    const float *__restrict__ xyz2, int subtract)
+__device__ __forceinline__ void bq_msg_block_body(int n, int m, int cloud, int q0, int q1, int use_cells, int max_ns,
+                                                  int wave_stride_b, const BqScales &sc, const float *__restrict__ xyz1,
+                                                  const float *__restrict__ xyz2, int subtract, size_t out_rows, char *smem)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int cloud, part;
-    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int q0 = part * qpb, q1 = min(q0 + qpb, m);
     const float *__restrict__ data = xyz1 + (size_t)cloud * n * 3;
 
     // cell-list layout (ball_query_body.h), wave areas sized for the largest nsample of the level
@@ -70,6 +69,9 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int
     if (cells) {
         for (int i = 0; i < sc.count; ++i) {
             const BqScale &s = sc.s[i];
+            int *const s_idx = s.idx ? s.idx + out_rows * (size_t)s.nsample : nullptr;
+            int *const s_cnt = s.cnt ? s.cnt + out_rows : nullptr;
+            float *const s_grouped = s.grouped ? s.grouped + out_rows * (size_t)s.nsample * 3 : nullptr;
             const float reach = s.radius * 1.001f;
             const float fx = fminf(1.0f, (2.0f * reach * g.ix + 1.0f) / (float)g.gx);
             const float fy = fminf(1.0f, (2.0f * reach * g.iy + 1.0f) / (float)g.gy);
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int
             if (__builtin_amdgcn_readfirstlane((int)(fx * fy * fz >= 0.5f))) continue;   // block-uniform: the grid is the workgroup's
 #define PN2_MSG_LOOP(LPQ)                                                                                           \
     bq_cells_query_loop<NT, LPQ, true, false>(n, m, s.nsample, s.thr, s.radius, s.radius * 1.001f, cloud, q0, q1, g, data, \
-                                              xyz2, nullptr, nullptr, s.idx, s.cnt, s.grouped, subtract, sorted, tab,  \
+                                              xyz2, nullptr, nullptr, s_idx, s_cnt, s_grouped, subtract, sorted, tab, \
                                               wave_area, wave_stride)
             if (s.lpq == 8) PN2_MSG_LOOP(8);                      // block-uniform
             else if (s.lpq == 16) PN2_MSG_LOOP(16);
@@ -103,9 +105,52 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int
     for (int i = 0; i < sc.count; ++i) {
         if (!((todo >> i) & 1u)) continue;
         const BqScale &s = sc.s[i];
-        bq_block_body<true, true, false, NT, true>(n, m, s.nsample, s.thr, cloud, q0, q1, xyz1, xyz2, nullptr, nullptr, s.idx,
-                                                   s.cnt, s.grouped, subtract, smem, 1u, max_ns);
+        bq_block_body<true, true, false, NT, true>(n, m, s.nsample, s.thr, cloud, q0, q1, xyz1, xyz2, nullptr, nullptr,
+                                                   s.idx ? s.idx + out_rows * (size_t)s.nsample : nullptr,
+                                                   s.cnt ? s.cnt + out_rows : nullptr,
+                                                   s.grouped ? s.grouped + out_rows * (size_t)s.nsample * 3 : nullptr, subtract,
+                                                   smem, 1u, max_ns);
     }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int n, int m, int qpb, int parts,
+                                                                    int use_cells, int max_ns, int wave_stride_b, BqScales sc,
+                                                                    const float *__restrict__ xyz1,
+                                                                    const float *__restrict__ xyz2, int subtract)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int cloud, part;
+    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
+    const int q0 = part * qpb;
+    bq_msg_block_body<NT>(n, m, cloud, q0, min(q0 + qpb, m), use_cells, max_ns, wave_stride_b, sc, xyz1, xyz2, subtract, 0, smem);
+}
+
+// Ragged batch (pn2_query_ball_group_xyz_msg_ragged): cloud c holds nc = lengths1[c] <= n points in its padded (n, 3) slab. The
+// workgroup hands the body n = nc, cloud 0 and the cloud's own slabs of the padded tensors, the outputs moved by the cloud's
+// c m rows: layout, staging, binning, the +inf pad and every loop bound are those of the dense kernel on the slice, and rows
+// at or beyond nc are never addressed. Everything the HOST decided -- geometry, lanes per query, wave_stride, LDS bytes -- was
+// sized for the padded n (msg_plan), and what fits n fits nc: the sorted array (16 nc bytes), the sweep copy's npad = nc
+// rounded up to 128 and bq_cells_wave_bytes(nc, ., lpq) (windows of 4096 points) are all non-decreasing in the point count,
+// and wave_stride is passed in, never re-derived from nc. Per cloud, block-uniform: below 64 points the binning is skipped and
+// the cloud is swept (the rule of ball_query_cells_ragged_kernel); larger clouds bin their own nc points, so bq_build_grid's
+// give-up rules and the half-of-the-grid rule of the body apply to that cloud's grid. No global atomics, no memset, nothing
+// that waits on another workgroup.
+template <int NT>
+__global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_ragged_kernel(int b, int n, int m, int qpb, int parts,
+                                                                           int use_cells, int max_ns, int wave_stride_b,
+                                                                           BqScales sc, const float *__restrict__ xyz1,
+                                                                           const int *__restrict__ lengths1,
+                                                                           const float *__restrict__ xyz2, int subtract)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int cloud, part;
+    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
+    const int nc = bq_ragged_length(lengths1, cloud, n);
+    const int q0 = part * qpb;
+    const size_t rows = (size_t)cloud * m;
+    bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, m), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
+                          xyz1 + (size_t)cloud * n * 3, xyz2 + rows * 3, subtract, rows, smem);
 }
 
 static size_t msg_sweep_bytes(int n, int max_ns, int nthreads)
@@ -221,8 +266,15 @@ static int msg_plan(int b, int n, int m, int nscales, const float *radii, const 
 }
 
 template <int NT>
-static int launch_msg(int b, int n, int m, const MsgPlan &p, const float *xyz1, const float *xyz2, int subtract, hipStream_t st)
+static int launch_msg(int b, int n, int m, const MsgPlan &p, const float *xyz1, const int *lengths1, const float *xyz2, int subtract,
+                      hipStream_t st)
 {
+    if (lengths1) {                                              // the same plan: every host decision is taken from the padded n
+        auto kern = ball_query_msg_ragged_kernel<NT>;
+        if (int rc = allow_dynamic_lds(kern, p.lds)) return rc;
+        return launch(kern, dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
+                      (int)p.wave_stride, p.sc, xyz1, lengths1, xyz2, subtract);
+    }
     auto kern = ball_query_msg_kernel<NT>;
     if (int rc = allow_dynamic_lds(kern, p.lds)) return rc;
     return launch(kern, dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
@@ -248,9 +300,10 @@ extern "C" int pn2_query_ball_group_xyz_msg_plan(int b, int n, int m, int nscale
     return rc;
 }
 
-extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
-                                            const float *xyz1, const float *xyz2, int subtract_centroid, int *const *idx,
-                                            int *const *pts_cnt, float *const *grouped_xyz, void *stream)
+// lengths1: NULL = every cloud holds n points (the dense kernel); else the ragged kernel
+static int msg_run(int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *xyz1, const int *lengths1,
+                   const float *xyz2, int subtract_centroid, int *const *idx, int *const *pts_cnt, float *const *grouped_xyz,
+                   void *stream)
 {
     using namespace pn2;
     if (int rc = msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
@@ -266,6 +319,28 @@ extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, co
         p.sc.s[i].grouped = grouped_xyz ? grouped_xyz[i] : nullptr;
     }
     hipStream_t st = as_stream(stream);
-    if (p.nt == 1024) return launch_msg<1024>(b, n, m, p, xyz1, xyz2, subtract_centroid, st);
-    return launch_msg<512>(b, n, m, p, xyz1, xyz2, subtract_centroid, st);
+    if (p.nt == 1024) return launch_msg<1024>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st);
+    return launch_msg<512>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st);
+}
+
+extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
+                                            const float *xyz1, const float *xyz2, int subtract_centroid, int *const *idx,
+                                            int *const *pts_cnt, float *const *grouped_xyz, void *stream)
+{
+    return msg_run(b, n, m, nscales, radii, nsamples, xyz1, nullptr, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream);
+}
+
+// Ragged batch: cloud c of xyz1 is xyz1[c, :lengths1[c]] of a padded (b, n, 3) tensor, lengths1 (b) int32 on the device, never
+// read by the host; the queries xyz2 (b, m, 3) are dense. Result per cloud and radius = pn2_query_ball_group_xyz_msg on the
+// slice = pn2_query_ball_group_xyz_ragged per radius. Codes in the order of the single-radius ragged entry: attributes and
+// extents, then nothing to do, then a NULL lengths1, then the dense entry's remaining checks.
+extern "C" int pn2_query_ball_group_xyz_msg_ragged(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
+                                                   const float *xyz1, const int *lengths1, const float *xyz2,
+                                                   int subtract_centroid, int *const *idx, int *const *pts_cnt,
+                                                   float *const *grouped_xyz, void *stream)
+{
+    if (int rc = pn2::msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (!lengths1) return PN2_E_NULL;
+    return msg_run(b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream);
 }

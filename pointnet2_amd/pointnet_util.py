@@ -451,6 +451,10 @@ class PointnetSAModuleMSG(nn.Module):
         self.fused_xyz_grad = False    # see PointnetSAModule: the fused training node for an xyz that requires a gradient (opt-in)
         self.fused_frozen_bn = False   # see PointnetSAModule: the fused node with frozen batch-norm statistics (opt-in)
         self.index_plans = False       # see PointnetSAModule: one index plan per radius, built where its idx is born (opt-in)
+        # geometry(lengths=): every radius of a ragged level in ONE multi-radius launch (query_ball_group_xyz_msg(..., lengths1=):
+        # each cloud staged and binned once) instead of one ragged ball query per radius -- same bits. Opt-in; measured in
+        # profiles/ragged_msg/README.md.
+        self.ragged_one_launch = False
         self.last_path = None
         self._pack_cache = {}
 
@@ -496,12 +500,17 @@ class PointnetSAModuleMSG(nn.Module):
     def geometry(self, xyz, plans=False, lengths=None):
         """This level's sampling and every radius' grouping alone (:173-180) -> SAGeometry with one idx per radius (plans: and
         one index plan per radius). lengths: (b,) per-cloud point counts of a ragged batch: ragged FPS + gather, then one
-        ragged ball query per radius (the one-binning multi-radius launch is not offered for ragged input)."""
+        ragged ball query per radius -- or, with ragged_one_launch, ONE ragged multi-radius launch for all radii (the first
+        included: there is no overlapped launch with lengths to serve it); the results are the same bit for bit."""
         if lengths is not None:
             lengths = ragged_lengths(lengths, xyz.shape[0], xyz.device)
             fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths)
-            scales = [query_ball_group_xyz(r, k, xyz, new_xyz, True, lengths1=lengths)[0::2]
-                      for r, k in zip(self.radius_list, self.nsample_list)]
+            if self.ragged_one_launch:
+                scales = [(i, g) for i, _, g in query_ball_group_xyz_msg(self.radius_list, self.nsample_list, xyz, new_xyz, True,
+                                                                         lengths1=lengths)]
+            else:
+                scales = [query_ball_group_xyz(r, k, xyz, new_xyz, True, lengths1=lengths)[0::2]
+                          for r, k in zip(self.radius_list, self.nsample_list)]
         else:
             new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
         return SAGeometry(new_xyz, [idx for idx, _ in scales], fps_idx,

@@ -108,11 +108,13 @@ def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, wa
     return idx, cnt, grouped
 
 
-def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_centroid=True, want_idx=True):
+def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None):
     """Every radius of a multi-scale-grouping level in ONE launch: the cloud is staged and binned once
     per workgroup and queried once per radius (pn2_query_ball_group_xyz_msg; reference loop
     pointnet_util.py:175-186 runs query_ball_point + group_point + subtraction per radius).
     Bit-identical to query_ball_group_xyz called per radius. Not differentiable.
+    lengths1: (b,) per-cloud point counts of a ragged xyz1, see query_ball_point (pn2_query_ball_group_xyz_msg_ragged: still one
+    launch, every cloud's own points staged and binned once); bit-identical to query_ball_group_xyz(..., lengths1=) per radius.
 
     -> [(idx (b,m,ns_i) i32 or None, pts_cnt (b,m) i32, grouped_xyz (b,m,ns_i,3) f32) for every scale]
     """
@@ -122,6 +124,8 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     require(len(radius_list) == len(nsample_list) and 1 <= len(radius_list), "one nsample per radius")
     require(all(r > 0 for r in radius_list), "QueryBallPoint expects positive radius")
     require(all(k > 0 for k in nsample_list), "QueryBallPoint expects positive nsample")
+    if lengths1 is not None:
+        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
@@ -131,8 +135,9 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
     ns_count = len(radius_list)
+    lens = ragged_lengths(lengths1, b, dev, "lengths1") if lengths1 is not None else None
     if ns_count > 4 or n > 8192:                                  # outside the multi-radius kernel's envelope
-        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx)
+        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens)
                 for r, k in zip(radius_list, nsample_list)]
     # one allocation per dtype, carved into per-scale views (allocations dominate the host time of this call)
     tot = sum(nsample_list)
@@ -155,12 +160,16 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     pc = (ctypes.c_void_p * ns_count)(*[ptr(o[1]) for o in outs])
     pg = (ctypes.c_void_p * ns_count)(*[ptr(o[2]) for o in outs])
     with on_device(dev):
-        rc = _C.lib().pn2_query_ball_group_xyz_msg(b, n, m, ns_count, radii, nss, ptr(xyz1), ptr(xyz2),
-                                                   1 if subtract_centroid else 0, pi, pc, pg, stream_ptr(dev))
+        if lens is not None:
+            rc = _C.lib().pn2_query_ball_group_xyz_msg_ragged(b, n, m, ns_count, radii, nss, ptr(xyz1), ptr(lens), ptr(xyz2),
+                                                              1 if subtract_centroid else 0, pi, pc, pg, stream_ptr(dev))
+        else:
+            rc = _C.lib().pn2_query_ball_group_xyz_msg(b, n, m, ns_count, radii, nss, ptr(xyz1), ptr(xyz2),
+                                                       1 if subtract_centroid else 0, pi, pc, pg, stream_ptr(dev))
     if rc == -4:
         # PN2_E_TOO_LARGE: no LDS geometry fits this combination (e.g. n = 8192 with nsample >= 127 on a later radius);
         # nothing has been launched -- the per-radius operator covers every shape
-        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx)
+        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens)
                 for r, k in zip(radius_list, nsample_list)]
     _C.check(rc, "query_ball_group_xyz_msg")
     return outs
