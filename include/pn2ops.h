@@ -377,6 +377,39 @@ int pn2_knn_point_ragged(int b, int n, int m, int k, const float *xyz1, const in
 int pn2_three_nn_ragged(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2, float *dist, int *idx,
                         int variant, void *stream);
 
+/* ---- ragged batches, the second side: per-cloud sample counts and a ragged query / known side ---------------------------------
+ * A second count array (b) int32 in DEVICE memory joins `lengths`: for FPS `npoints` -- cloud c yields m_c = npoints[c] samples --,
+ * for the pair operators `lengths2` -- cloud c has m_c = lengths2[c] valid rows of xyz2 (b,m,3). Never read by the host, clamped
+ * on the device into 1..m for memory safety only. THE PAIR SLICE RULE: for cloud c and rows j < m_c the result is bit- and
+ * index-identical to the dense entry on (xyz1[c, :lengths1[c]], xyz2[c, :m_c]) alone; for FPS that is the first m_c samples of
+ * the slice (the chain is prefix-consistent, sample 0 is point 0), and m_c > lengths[c] behaves as the dense operator with
+ * npoint > n. Rows of xyz1 at or beyond lengths1[c] and rows of xyz2 at or beyond m_c are never read. Output rows j >= m_c are
+ * fully written with fixed values:
+ *   pn2_farthest_point_sample_ragged_counts     out[c, j] = out[c, 0] = 0, out_xyz[c, j] = out_xyz[c, 0] (sample 0 repeated)
+ *   pn2_query_ball_group_xyz_ragged_pair        idx row all 0, pts_cnt 0, grouped_xyz all +0.0 (with or without subtract_centroid)
+ *   pn2_query_ball_group_xyz_msg_ragged_pair    the same for every radius
+ *   pn2_knn_point_ragged_pair                   idx row all 0, val row all +0.0
+ *   pn2_three_nn_ragged_pair                    the ragged side is the KNOWN side: no new output rows; rows beyond lengths1[c]
+ *                                               stay (0,0,0) / (0,0,0); m_c < 3 gives the dense operator's +inf / index 0 entries,
+ *                                               and every index is below m_c
+ * A workgroup or wave that holds such rows only writes them and leaves before any staging, binning or barrier. BOTH count
+ * arrays are required (NULL: PN2_E_NULL; a caller with one dense side passes an array of full counts); validation order, codes
+ * and envelopes are those of the one-sided twin above, and every host decision (geometry, queries per workgroup, LDS bytes, the
+ * multi-radius plan) is taken from the padded n and m. Stream-ordered, no memset, nothing read on the host: capturable. */
+int pn2_farthest_point_sample_ragged_counts(int b, int n, int m, const float *inp, const int *lengths, const int *npoints,
+                                            int *out, float *out_xyz, void *stream);
+int pn2_query_ball_group_xyz_ragged_pair(int b, int n, int m, float radius, int nsample, const float *xyz1, const int *lengths1,
+                                         const float *xyz2, const int *lengths2, int subtract_centroid, int *idx, int *pts_cnt,
+                                         float *grouped_xyz, int kernel, int cells_qpb, void *stream);
+int pn2_query_ball_group_xyz_msg_ragged_pair(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
+                                             const float *xyz1, const int *lengths1, const float *xyz2, const int *lengths2,
+                                             int subtract_centroid, int *const *idx, int *const *pts_cnt,
+                                             float *const *grouped_xyz, void *stream);
+int pn2_knn_point_ragged_pair(int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2,
+                              const int *lengths2, float *val, int *idx, void *stream);
+int pn2_three_nn_ragged_pair(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2, const int *lengths2,
+                             float *dist, int *idx, int variant, void *stream);
+
 /* pn2_group_point / pn2_three_interpolate with the kernel choice per call (parity tests force every kernel,
  * scripts/bw_probe.py times them). group: 0 automatic, 1 flat first-generation kernels, 2 row kernels,
  * 3 row kernels with non-temporal stores; three_interpolate: 0 automatic, 1 flat, 2 row kernel, 3 row kernel with

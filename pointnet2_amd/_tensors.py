@@ -84,6 +84,12 @@ def ragged_lengths(lengths, b, dev, name="lengths"):
     return t.to(device=dev, dtype=torch.int32).contiguous()
 
 
+def full_counts(b, n, dev):
+    """The count array of a DENSE side for the two-sided ragged entries (they require both arrays): (b,) int32 of n, made on
+    `dev` -- no host synchronisation, capturable."""
+    return torch.full((b,), int(n), dtype=torch.int32, device=dev)
+
+
 def check_lengths(lengths, n, b=None):
     """Validate the per-cloud point counts of a ragged batch padded to n points: an int32 / int64 tensor (or a sequence) of
     shape (b,) with 1 <= lengths[i] <= n. Raises ValueError. This is the ONE place that looks at the values, and it

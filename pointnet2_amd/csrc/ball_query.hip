@@ -73,9 +73,36 @@ __global__ __launch_bounds__(kBqThreads) void ball_query_ragged_kernel(int n, in
                                           grouped ? grouped + rows * nsample * 3 : nullptr, subtract, smem);
 }
 
+// Ragged on both sides (pn2_query_ball_group_xyz_ragged_pair): cloud c also holds only m_c = lengths2[c] valid queries. The
+// workgroup sweeps [q0, min(q0 + qpb, m_c)) -- the body never reads a query row at or beyond its q1 --, fills its rows from m_c
+// on (bq_fill_rows) and, when it holds nothing else, leaves before the staging (block-uniform).
+template <bool LDS_CLOUD, bool FUSE>
+__global__ __launch_bounds__(kBqThreads) void ball_query_ragged_pair_kernel(int n, int m, int nsample, float thr, int qpb,
+                                                                            const float *__restrict__ xyz1,
+                                                                            const int *__restrict__ lengths,
+                                                                            const float *__restrict__ xyz2,
+                                                                            const int *__restrict__ lengths2, int *__restrict__ idx,
+                                                                            int *__restrict__ pts_cnt,
+                                                                            float *__restrict__ grouped, int subtract)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c = blockIdx.y;
+    const int nc = bq_ragged_length(lengths, c, n);
+    const int mc = bq_ragged_count(lengths2, c, m);
+    const int q0 = blockIdx.x * qpb;
+    const size_t rows = (size_t)c * m;
+    int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
+    int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
+    float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
+    bq_fill_rows<kBqThreads>(max(q0, mc), min(q0 + qpb, m), nsample, oi, oc, og);
+    if (q0 >= mc) return;
+    bq_block_body<LDS_CLOUD, FUSE, false>(nc, m, nsample, thr, 0, q0, min(q0 + qpb, mc), xyz1 + (size_t)c * n * 3, xyz2 + rows * 3,
+                                          nullptr, nullptr, oi, oc, og, subtract, smem);
+}
+
 template <bool LDS_CLOUD, bool FUSE>
 static int launch_bq(int b, int n, int m, float thr, int nsample, const float *xyz1, const int *lengths, const float *xyz2, int *idx,
-                     int *pts_cnt, float *grouped, int subtract, hipStream_t st)
+                     int *pts_cnt, float *grouped, int subtract, hipStream_t st, const int *lengths2 = nullptr)
 {
     // aim at ~2 workgroups per CU over the whole launch; each stages the cloud once
     constexpr int kGran = kBqWaves * kBqQpw;
@@ -87,6 +114,12 @@ static int launch_bq(int b, int n, int m, float thr, int nsample, const float *x
     const int gx = (m + qpb - 1) / qpb;
     const size_t lds = (LDS_CLOUD ? sizeof(float4) * (size_t)((n + 127) & ~127) : 0) + sizeof(int) * (size_t)nsample * kGran;
     if (lds > 160 * 1024) return PN2_E_TOO_LARGE;
+    if (lengths2) {
+        auto kern = ball_query_ragged_pair_kernel<LDS_CLOUD, FUSE>;
+        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+        return launch(kern, dim3(gx, b), dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, lengths, xyz2, lengths2, idx, pts_cnt,
+                      grouped, subtract);
+    }
     if (lengths) {
         auto kern = ball_query_ragged_kernel<LDS_CLOUD, FUSE>;
         if (int rc = allow_dynamic_lds(kern, lds)) return rc;
@@ -150,6 +183,40 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_ragged_kernel(i
                                                         subtract, smem);
 }
 
+// The cell-list kernel, ragged on both sides: the query range ends at m_c = lengths2[c], the rows from m_c on are filled, and a
+// workgroup of fill rows alone leaves before the binning (block-uniform). "Below 64 points: sweep" as above.
+template <int NT, int LPQ, bool FUSE>
+__global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_ragged_pair_kernel(int b, int n, int m, int nsample, float thr,
+                                                                                  float radius, int qpb, int parts,
+                                                                                  const float *__restrict__ xyz1,
+                                                                                  const int *__restrict__ lengths,
+                                                                                  const float *__restrict__ xyz2,
+                                                                                  const int *__restrict__ lengths2,
+                                                                                  int *__restrict__ idx,
+                                                                                  int *__restrict__ pts_cnt,
+                                                                                  float *__restrict__ grouped, int subtract)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int cloud, part;
+    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
+    const int nc = bq_ragged_length(lengths, cloud, n);
+    const int mc = bq_ragged_count(lengths2, cloud, m);
+    const int q0 = part * qpb, q1 = min(q0 + qpb, mc);
+    const size_t rows = (size_t)cloud * m;
+    const float *__restrict__ x1 = xyz1 + (size_t)cloud * n * 3;
+    const float *__restrict__ x2 = xyz2 + rows * 3;
+    int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
+    int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
+    float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
+    bq_fill_rows<NT>(max(q0, mc), min(q0 + qpb, m), nsample, oi, oc, og);
+    if (q0 >= mc) return;
+    if (nc < 64)
+        bq_block_body<true, FUSE, false, NT>(nc, m, nsample, thr, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og, subtract, smem);
+    else
+        bq_cells_block_body<NT, LPQ, FUSE, false, true>(nc, m, nsample, thr, radius, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og,
+                                                        subtract, smem);
+}
+
 static size_t bq_sweep_lds_bytes(int n, int nsample, int nthreads = kBqThreads)
 {
     return sizeof(float4) * (size_t)((n + 127) & ~127) + sizeof(int) * (size_t)nsample * (nthreads / 64) * kBqQpw;
@@ -190,7 +257,7 @@ static bool bq_use_cells(int b, int n, int m, int kernel)
 template <int NT, int LPQ, bool FUSE>
 static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsample, const float *xyz1, const int *lengths,
                            const float *xyz2, int *idx, int *pts_cnt, float *grouped, int subtract, int opt_qpb,
-                           hipStream_t st)
+                           hipStream_t st, const int *lengths2 = nullptr)
 {
     constexpr int kGran = (NT / 64) * (64 / LPQ);               // queries per workgroup trip
     long long total = (long long)b * m;
@@ -201,6 +268,12 @@ static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsa
     const int gx = (m + qpb - 1) / qpb;
     const size_t a = bq_cells_lds_bytes(n, nsample, LPQ, NT), s = bq_sweep_lds_bytes(n, nsample, NT);
     const size_t lds = a > s ? a : s;                       // the fallback inside the kernel uses the sweep layout
+    if (lengths2) {
+        auto kern = ball_query_cells_ragged_pair_kernel<NT, LPQ, FUSE>;
+        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+        return launch(kern, dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx, xyz1, lengths, xyz2,
+                      lengths2, idx, pts_cnt, grouped, subtract);
+    }
     if (lengths) {
         auto kern = ball_query_cells_ragged_kernel<NT, LPQ, FUSE>;
         if (int rc = allow_dynamic_lds(kern, lds)) return rc;
@@ -217,11 +290,11 @@ static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsa
 template <bool FUSE>
 static int dispatch_bq_cells(BqCellsGeom g, int b, int n, int m, float thr, float radius, int nsample,
                              const float *xyz1, const int *lengths, const float *xyz2, int *idx, int *pts_cnt, float *grouped,
-                             int subtract, int qpb, hipStream_t st)
+                             int subtract, int qpb, hipStream_t st, const int *lengths2 = nullptr)
 {
 #define PN2_BQ_CASE(NT, LPQ) \
     if (g.nthreads == NT && g.lpq == LPQ) \
-        return launch_bq_cells<NT, LPQ, FUSE>(b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, qpb, st)
+        return launch_bq_cells<NT, LPQ, FUSE>(b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, qpb, st, lengths2)
     PN2_BQ_CASE(1024, 8);
     PN2_BQ_CASE(1024, 16);
     PN2_BQ_CASE(512, 8);
@@ -231,10 +304,11 @@ static int dispatch_bq_cells(BqCellsGeom g, int b, int n, int m, float thr, floa
     return PN2_E_TOO_LARGE;
 }
 
-// lengths: NULL = every cloud holds n points (the dense kernels); else the ragged kernels
+// lengths: NULL = every cloud holds n points (the dense kernels); else the ragged kernels. lengths2 (with lengths only): the
+// valid queries per cloud, the *_ragged_pair kernels
 static int ball_query_common(int b, int n, int m, float radius, int nsample, const float *xyz1, const float *xyz2,
                              int subtract, int *idx, int *pts_cnt, float *grouped, bool fuse, BqOpts opt, void *stream,
-                             const int *lengths = nullptr)
+                             const int *lengths = nullptr, const int *lengths2 = nullptr)
 {
     if (opt.kernel < 0 || opt.kernel > 3 || opt.qpb < 0) return PN2_E_ARG;
     if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;   // tf_grouping.cpp:71,74
@@ -250,13 +324,13 @@ static int ball_query_common(int b, int n, int m, float radius, int nsample, con
                      sizeof(float4) * (size_t)((n + 127) & ~127) + sizeof(int) * (size_t)nsample * kBqWaves * kBqQpw <= 160 * 1024;
     BqCellsGeom geom;
     if (bq_use_cells(b, n, m, opt.kernel) && bq_cells_pick(n, nsample, opt.kernel, geom))
-        return fuse ? dispatch_bq_cells<true>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, opt.qpb, st)
-                    : dispatch_bq_cells<false>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, opt.qpb, st);
+        return fuse ? dispatch_bq_cells<true>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, opt.qpb, st, lengths2)
+                    : dispatch_bq_cells<false>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, opt.qpb, st, lengths2);
     if (fuse)
-        return lds ? launch_bq<true, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st)
-                   : launch_bq<false, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st);
-    return lds ? launch_bq<true, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st)
-               : launch_bq<false, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st);
+        return lds ? launch_bq<true, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st, lengths2)
+                   : launch_bq<false, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st, lengths2);
+    return lds ? launch_bq<true, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st, lengths2)
+               : launch_bq<false, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st, lengths2);
 }
 
 }  // namespace pn2
@@ -322,4 +396,21 @@ extern "C" int pn2_query_ball_group_xyz_ragged(int b, int n, int m, float radius
     if (!lengths1) return PN2_E_NULL;
     return pn2::ball_query_common(b, n, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt,
                                   grouped_xyz, grouped_xyz != nullptr, {kernel, cells_qpb}, stream, lengths1);
+}
+
+// Ragged on both sides: cloud c additionally holds only lengths2[c] valid rows of xyz2 (b int32 on the device, clamped into
+// 1..m, never read by the host). Rows below lengths2[c] = pn2_query_ball_group_xyz_ex on (xyz1[c, :lengths1[c]],
+// xyz2[c, :lengths2[c]]) for every `kernel`; the rows from lengths2[c] on are written as idx 0, pts_cnt 0, grouped_xyz +0.0 and
+// their queries are never read. Codes in the order of pn2_query_ball_group_xyz_ragged; both count arrays are required.
+extern "C" int pn2_query_ball_group_xyz_ragged_pair(int b, int n, int m, float radius, int nsample, const float *xyz1,
+                                                    const int *lengths1, const float *xyz2, const int *lengths2, int subtract_centroid,
+                                                    int *idx, int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb, void *stream)
+{
+    if (kernel < 0 || kernel > 3 || cells_qpb < 0) return PN2_E_ARG;
+    if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;
+    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (!lengths1 || !lengths2) return PN2_E_NULL;
+    return pn2::ball_query_common(b, n, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt,
+                                  grouped_xyz, grouped_xyz != nullptr, {kernel, cells_qpb}, stream, lengths1, lengths2);
 }

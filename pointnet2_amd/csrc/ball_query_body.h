@@ -136,6 +136,31 @@ __device__ __forceinline__ int bq_ragged_length(const int *__restrict__ lengths,
     return min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
 }
 
+// Ragged QUERY side (the *_ragged_pair kernels): cloud `cloud` holds counts[cloud] valid rows of its (m, 3) query slab, clamped
+// into 1..m for memory safety only; wave-uniform.
+__device__ __forceinline__ int bq_ragged_count(const int *__restrict__ counts, int cloud, int m)
+{
+    return min(max(__builtin_amdgcn_readfirstlane(counts[cloud]), 1), m);
+}
+
+// The output rows [r0, r1) of one cloud (idx / pts_cnt / grouped already moved to the cloud's row 0) that belong to no valid
+// query: idx all 0, pts_cnt 0, grouped_xyz all +0.0 -- fixed values, so everything downstream stays in range and finite.
+// Nothing is read; the whole workgroup (NT threads) takes part, no barrier.
+template <int NT>
+__device__ __forceinline__ void bq_fill_rows(int r0, int r1, int nsample, int *__restrict__ idx, int *__restrict__ pts_cnt,
+                                             float *__restrict__ grouped)
+{
+    if (r0 >= r1) return;
+    const int t = threadIdx.x;
+    const size_t e0 = (size_t)r0 * nsample, e1 = (size_t)r1 * nsample;
+    if (idx)
+        for (size_t e = e0 + t; e < e1; e += NT) idx[e] = 0;
+    if (grouped)
+        for (size_t e = e0 * 3 + t; e < e1 * 3; e += NT) grouped[e] = 0.0f;
+    if (pts_cnt)
+        for (int r = r0 + t; r < r1; r += NT) pts_cnt[r] = 0;
+}
+
 // One workgroup's share of the ball queries of cloud `bi`: queries [q0, q1).
 // POLL: the query points are not read from xyz2; they are the FPS samples of the same launch, taken
 // from the tagged index stream as soon as they exist (and written to new_xyz on the way).

@@ -153,6 +153,37 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_ragged_kernel(int
                           xyz1 + (size_t)cloud * n * 3, xyz2 + rows * 3, subtract, rows, smem);
 }
 
+// Ragged on both sides (pn2_query_ball_group_xyz_msg_ragged_pair): cloud c also holds only m_c = lengths2[c] valid queries. The
+// body gets the query range cut at m_c; the workgroup's rows from m_c on are filled for EVERY radius (idx 0, pts_cnt 0, grouped
+// +0.0), and a workgroup of such rows alone leaves before any staging or binning (block-uniform).
+template <int NT>
+__global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_ragged_pair_kernel(int b, int n, int m, int qpb, int parts,
+                                                                                int use_cells, int max_ns, int wave_stride_b,
+                                                                                BqScales sc, const float *__restrict__ xyz1,
+                                                                                const int *__restrict__ lengths1,
+                                                                                const float *__restrict__ xyz2,
+                                                                                const int *__restrict__ lengths2, int subtract)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int cloud, part;
+    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
+    const int nc = bq_ragged_length(lengths1, cloud, n);
+    const int mc = bq_ragged_count(lengths2, cloud, m);
+    const int q0 = part * qpb;
+    const size_t rows = (size_t)cloud * m;
+    const int f0 = max(q0, mc), f1 = min(q0 + qpb, m);
+    if (f0 < f1) {                                               // block-uniform
+        for (int i = 0; i < sc.count; ++i) {
+            const BqScale &s = sc.s[i];
+            bq_fill_rows<NT>(f0, f1, s.nsample, s.idx ? s.idx + rows * (size_t)s.nsample : nullptr, s.cnt ? s.cnt + rows : nullptr,
+                             s.grouped ? s.grouped + rows * (size_t)s.nsample * 3 : nullptr);
+        }
+    }
+    if (q0 >= mc) return;
+    bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, mc), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
+                          xyz1 + (size_t)cloud * n * 3, xyz2 + rows * 3, subtract, rows, smem);
+}
+
 static size_t msg_sweep_bytes(int n, int max_ns, int nthreads)
 {
     return sizeof(float4) * (size_t)((n + 127) & ~127) + sizeof(int) * (size_t)max_ns * (nthreads / 64) * kBqQpw;
@@ -267,8 +298,14 @@ static int msg_plan(int b, int n, int m, int nscales, const float *radii, const 
 
 template <int NT>
 static int launch_msg(int b, int n, int m, const MsgPlan &p, const float *xyz1, const int *lengths1, const float *xyz2, int subtract,
-                      hipStream_t st)
+                      hipStream_t st, const int *lengths2 = nullptr)
 {
+    if (lengths2) {
+        auto kern = ball_query_msg_ragged_pair_kernel<NT>;
+        if (int rc = allow_dynamic_lds(kern, p.lds)) return rc;
+        return launch(kern, dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
+                      (int)p.wave_stride, p.sc, xyz1, lengths1, xyz2, lengths2, subtract);
+    }
     if (lengths1) {                                              // the same plan: every host decision is taken from the padded n
         auto kern = ball_query_msg_ragged_kernel<NT>;
         if (int rc = allow_dynamic_lds(kern, p.lds)) return rc;
@@ -300,10 +337,11 @@ extern "C" int pn2_query_ball_group_xyz_msg_plan(int b, int n, int m, int nscale
     return rc;
 }
 
-// lengths1: NULL = every cloud holds n points (the dense kernel); else the ragged kernel
+// lengths1: NULL = every cloud holds n points (the dense kernel); else the ragged kernel; lengths2 (with lengths1 only): the
+// valid queries per cloud, the ragged-pair kernel
 static int msg_run(int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *xyz1, const int *lengths1,
                    const float *xyz2, int subtract_centroid, int *const *idx, int *const *pts_cnt, float *const *grouped_xyz,
-                   void *stream)
+                   void *stream, const int *lengths2 = nullptr)
 {
     using namespace pn2;
     if (int rc = msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
@@ -319,8 +357,8 @@ static int msg_run(int b, int n, int m, int nscales, const float *radii, const i
         p.sc.s[i].grouped = grouped_xyz ? grouped_xyz[i] : nullptr;
     }
     hipStream_t st = as_stream(stream);
-    if (p.nt == 1024) return launch_msg<1024>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st);
-    return launch_msg<512>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st);
+    if (p.nt == 1024) return launch_msg<1024>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st, lengths2);
+    return launch_msg<512>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st, lengths2);
 }
 
 extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
@@ -343,4 +381,20 @@ extern "C" int pn2_query_ball_group_xyz_msg_ragged(int b, int n, int m, int nsca
     if (b == 0 || m == 0) return PN2_OK;
     if (!lengths1) return PN2_E_NULL;
     return msg_run(b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream);
+}
+
+// Ragged on both sides: cloud c additionally holds only lengths2[c] valid rows of xyz2 (clamped into 1..m on the device). Rows
+// below lengths2[c] = pn2_query_ball_group_xyz_msg on the slice pair = pn2_query_ball_group_xyz_ragged_pair per radius; the rows
+// from lengths2[c] on are written, for every radius, as idx 0, pts_cnt 0, grouped_xyz +0.0. Codes in the order of
+// pn2_query_ball_group_xyz_msg_ragged; both count arrays are required.
+extern "C" int pn2_query_ball_group_xyz_msg_ragged_pair(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
+                                                        const float *xyz1, const int *lengths1, const float *xyz2,
+                                                        const int *lengths2, int subtract_centroid, int *const *idx,
+                                                        int *const *pts_cnt, float *const *grouped_xyz, void *stream)
+{
+    if (int rc = pn2::msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (!lengths1 || !lengths2) return PN2_E_NULL;
+    return msg_run(b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream,
+                   lengths2);
 }

@@ -68,6 +68,35 @@ __global__ __launch_bounds__(T) void fps_reg_ragged_kernel(int n, int m, const f
                                       out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr, nullptr, smem);
 }
 
+// Ragged batch with a sample count per cloud (pn2_farthest_point_sample_ragged_counts): cloud c yields m_c = npoints[c] samples
+// of its n_c points, both clamped for memory safety only. The body runs with m = m_c on the cloud's slab, so rows below m_c are
+// the first m_c samples of the dense operator on the slice (the chain is prefix-consistent: round j depends on rounds < j
+// alone). Rows m_c .. m-1 repeat sample 0, the way a ball query pads with its first hit; sample 0 is point 0 by the reference's
+// rule (tf_sampling_g.cu:114-116), so the fill is index 0 and xyz[c, 0] and reads nothing back. The fill rows are disjoint from
+// the body's, so no barrier stands between the two.
+template <int T, int P, bool LDSXYZ>
+__global__ __launch_bounds__(T) void fps_reg_ragged_counts_kernel(int n, int m, const float *__restrict__ xyz,
+                                                                  const int *__restrict__ lengths, const int *__restrict__ npoints,
+                                                                  int *__restrict__ out, float *__restrict__ out_xyz)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c = blockIdx.x;
+    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[c]), 1), n);
+    const int mc = min(max(__builtin_amdgcn_readfirstlane(npoints[c]), 1), m);
+    const int Qc = (nc + kRefThreads - 1) / kRefThreads;
+    const float *__restrict__ src = xyz + (size_t)c * n * 3;
+    int *__restrict__ dst = out + (size_t)c * m;
+    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
+    fps_reg_body<T, P, LDSXYZ, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
+    if (mc < m) {                                          // block-uniform
+        const float x0 = src[0], y0 = src[1], z0 = src[2];
+        for (int j = mc + (int)threadIdx.x; j < m; j += T) {
+            dst[j] = 0;
+            if (dxyz) { dxyz[j * 3 + 0] = x0; dxyz[j * 3 + 1] = y0; dxyz[j * 3 + 2] = z0; }
+        }
+    }
+}
+
 // Pruned tier (fps_pruned_body.h): kd-grouped slots, per-round box tests, only the groups the new sample can reach are
 // updated. 2049..8192 rank slots, chains long enough to pay for the kd build.
 template <int P, int GS>
@@ -325,10 +354,17 @@ static int launch_reg(int b, int n, int m, int Q, const float *inp, int *out, fl
     return PN2_OK;
 }
 
+// npoints: NULL = m samples from every cloud (fps_reg_ragged_kernel); else the per-cloud sample counts
 template <int T, int P, bool LDSXYZ>
-static int launch_reg_ragged(int b, int n, int m, const float *inp, const int *lengths, int *out, float *oxyz, hipStream_t st)
+static int launch_reg_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
+                             hipStream_t st)
 {
     const size_t lds = 256 + (LDSXYZ ? sizeof(float4) : sizeof(int)) * (size_t)T * P;
+    if (npoints) {
+        auto kern = fps_reg_ragged_counts_kernel<T, P, LDSXYZ>;
+        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+        return launch(kern, dim3(b), dim3(T), lds, st, n, m, inp, lengths, npoints, out, oxyz);
+    }
     auto kern = fps_reg_ragged_kernel<T, P, LDSXYZ>;
     if (int rc = allow_dynamic_lds(kern, lds)) return rc;
     return launch(kern, dim3(b), dim3(T), lds, st, n, m, inp, lengths, out, oxyz);
@@ -485,13 +521,13 @@ extern "C" int pn2_farthest_point_sample_variant(int variant, int b, int n, int 
 // Ragged batch: cloud c is inp[c, :lengths[c]] of a padded (b, n, 3) tensor, lengths (b) int32 on the device, never read by
 // the host. Result per cloud = pn2_farthest_point_sample_gather on the slice, tie rule included. Register tier only (the
 // geometry fps_entry picks for PN2_FPS_FULL at the padded n); PN2_E_TOO_LARGE beyond 16384 points. out_xyz may be NULL.
-extern "C" int pn2_farthest_point_sample_ragged(int b, int n, int m, const float *inp, const int *lengths, int *out, float *out_xyz,
-                                                void *stream)
+static int fps_ragged_entry(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, bool counts, int *out,
+                            float *out_xyz, void *stream)
 {
     using namespace pn2;
     if (m <= 0 || b == 0) return PN2_OK;
     if (b < 0 || n <= 0) return PN2_E_SHAPE;
-    if (!inp || !out || !lengths) return PN2_E_NULL;
+    if (!inp || !out || !lengths || (counts && !npoints)) return PN2_E_NULL;
     if (n > kMaxRegPoints) return PN2_E_TOO_LARGE;
     if ((long long)b * n * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
     hipStream_t st = as_stream(stream);
@@ -499,7 +535,7 @@ extern "C" int pn2_farthest_point_sample_ragged(int b, int n, int m, const float
     const int T = ranks <= 2048 ? 256 : 512;
     const int P = next_pow2((ranks + T - 1) / T);
 #define PN2_FPS_RAGGED(TT, PP) \
-    if (T == TT && P == PP) return launch_reg_ragged<TT, PP, ((long long)TT * PP <= kMaxLdsSlots)>(b, n, m, inp, lengths, out, out_xyz, st)
+    if (T == TT && P == PP) return launch_reg_ragged<TT, PP, ((long long)TT * PP <= kMaxLdsSlots)>(b, n, m, inp, lengths, npoints, out, out_xyz, st)
     PN2_FPS_RAGGED(256, 2);
     PN2_FPS_RAGGED(256, 4);
     PN2_FPS_RAGGED(256, 8);
@@ -508,6 +544,21 @@ extern "C" int pn2_farthest_point_sample_ragged(int b, int n, int m, const float
     PN2_FPS_RAGGED(512, 32);
 #undef PN2_FPS_RAGGED
     return PN2_E_ARG;
+}
+
+extern "C" int pn2_farthest_point_sample_ragged(int b, int n, int m, const float *inp, const int *lengths, int *out, float *out_xyz,
+                                                void *stream)
+{
+    return fps_ragged_entry(b, n, m, inp, lengths, nullptr, false, out, out_xyz, stream);
+}
+
+// The same with a sample count per cloud: cloud c yields m_c = npoints[c] samples (b int32 on the device, clamped into 1..m,
+// never read by the host). Rows below m_c = the first m_c samples of pn2_farthest_point_sample_gather on the slice; rows
+// m_c .. m-1 repeat sample 0 (index 0, the cloud's first point). Codes and envelope of pn2_farthest_point_sample_ragged.
+extern "C" int pn2_farthest_point_sample_ragged_counts(int b, int n, int m, const float *inp, const int *lengths, const int *npoints,
+                                                       int *out, float *out_xyz, void *stream)
+{
+    return fps_ragged_entry(b, n, m, inp, lengths, npoints, true, out, out_xyz, stream);
 }
 
 // farthest_point_sample for input the caller BELIEVES to be in farthest-point order already (the previous level's samples:

@@ -77,10 +77,12 @@ __device__ __forceinline__ void nn_zero_row(float *__restrict__ od, int *__restr
 
 // Workgroup body of the sweep. nv = valid unknown points of cloud bi: n in the dense kernel; in the ragged one the cloud's own
 // length -- rows nv .. n-1 are then zero-filled and never read (RAGGED; the dense instantiation has none of it).
+// m: the known points swept; m_stride: rows between two clouds' known points when that is not m (the ragged KNOWN side,
+// three_nn_ragged_pair_kernel: m = the cloud's own count) -- a literal 0 everywhere else, which folds away.
 template <bool RAGGED>
 __device__ __forceinline__ void three_nn_sweep_body(int n, int nv, int m, int bi, const float *__restrict__ xyz1,
                                                     const float *__restrict__ xyz2, float *__restrict__ dist,
-                                                    int *__restrict__ idx, float4 *tile)
+                                                    int *__restrict__ idx, float4 *tile, int m_stride = 0)
 {
     const int sub = threadIdx.x & 3;                       // lane of the quad
     const int j = blockIdx.x * kNnPoints + (threadIdx.x >> 2);
@@ -91,7 +93,7 @@ __device__ __forceinline__ void three_nn_sweep_body(int n, int nv, int m, int bi
     }
     const float *u = xyz1 + ((size_t)bi * n + (live ? j : 0)) * 3;
     const float ux = u[0], uy = u[1], uz = u[2];
-    const float *__restrict__ known = xyz2 + (size_t)bi * m * 3;
+    const float *__restrict__ known = xyz2 + (size_t)bi * (m_stride ? m_stride : m) * 3;
 
     const double empty = __hiloint2double(0x7F800000, 0);  // (+inf : 0) = the reference's (float)1e40, index 0 (:67)
     double b1 = empty, b2 = empty, b3 = empty;
@@ -157,6 +159,20 @@ __global__ __launch_bounds__(kNnThreads) void three_nn_ragged_kernel(int n, int 
     three_nn_sweep_body<true>(n, nv, m, blockIdx.y, xyz1, xyz2, dist, idx, tile);
 }
 
+// Ragged on both sides (pn2_three_nn_ragged_pair): cloud c also holds only lengths2[c] of its m known points. The sweep runs on
+// those alone (rows at or beyond the count are never read); fewer than three leave the (+inf, 0) entries of the dense operator.
+__global__ __launch_bounds__(kNnThreads) void three_nn_ragged_pair_kernel(int n, int m, const float *__restrict__ xyz1,
+                                                                          const int *__restrict__ lengths,
+                                                                          const float *__restrict__ xyz2,
+                                                                          const int *__restrict__ lengths2,
+                                                                          float *__restrict__ dist, int *__restrict__ idx)
+{
+    __shared__ float4 tile[kNnTile];
+    const int nv = min(max(__builtin_amdgcn_readfirstlane(lengths[blockIdx.y]), 1), n);
+    const int mc = min(max(__builtin_amdgcn_readfirstlane(lengths2[blockIdx.y]), 1), m);
+    three_nn_sweep_body<true>(n, nv, mc, blockIdx.y, xyz1, xyz2, dist, idx, tile, m);
+}
+
 
 // ---- three_nn with a cell list (round 6) ---------------------------------------------------------
 // The sweep above tests every unknown point against every known point: 67 M pair tests at sem_seg's last feature-propagation
@@ -195,11 +211,14 @@ __device__ __forceinline__ void nn_merge_dpp(double &b1, double &b2, double &b3)
 
 // Workgroup body; lengths (RAGGED only): the clouds' numbers of valid unknown points -- a workgroup's rows at or beyond its
 // cloud's length are zero-filled and never read, and a workgroup made of such rows alone leaves before the binning.
-template <int NT, bool RAGGED>
+// PAIR (with RAGGED): lengths2 = the clouds' numbers of valid KNOWN points. m stays the stride between two clouds and the
+// size the LDS layout is derived from; binning, the sweep and the fail-list sweep run on mk = the cloud's own count, and a
+// cloud below 64 known points takes the cannot-be-binned sweep at once. Without PAIR mk IS m: the same code as before.
+template <int NT, bool RAGGED, bool PAIR = false>
 __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_part, int parts, int b, float factor,
                                                     const float *__restrict__ xyz1, const int *__restrict__ lengths,
                                                     const float *__restrict__ xyz2, float *__restrict__ dist,
-                                                    int *__restrict__ idx, char *smem)
+                                                    int *__restrict__ idx, char *smem, const int *__restrict__ lengths2 = nullptr)
 {
     float4 *sorted = reinterpret_cast<float4 *>(smem);                                  // [m] known points in cell order, .w = index
     int *tab = reinterpret_cast<int *>(smem + sizeof(float4) * (size_t)((m + 3) & ~3)); // tab[c] = start of cell c, tab[c + 1] = its end
@@ -208,6 +227,7 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
     int cloud, part;
     decode_cloud_block(blockIdx.x, parts, b, cloud, part);
     const int nv = RAGGED ? min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n) : n;
+    const int mk = PAIR ? min(max(__builtin_amdgcn_readfirstlane(lengths2[cloud]), 1), m) : m;
     const int rb = part * rows_per_part, re = min(rb + rows_per_part, nv);
     const float *__restrict__ known = xyz2 + (size_t)cloud * m * 3;
     const float *__restrict__ unk = xyz1 + (size_t)cloud * n * 3;
@@ -222,10 +242,10 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
 
     if (t == 0) { tab[0] = 0; fail[0] = 0; }
     BqGrid g;
-    const bool binned = bq_build_grid<NT>(m, -factor, known, sorted, tab + 1, misc, g);   // block-uniform; ends with a barrier when true
+    const bool binned = (!PAIR || mk >= 64) && bq_build_grid<NT>(mk, -factor, known, sorted, tab + 1, misc, g);   // block-uniform; ends with a barrier when true
     if (!binned) {
         __syncthreads();
-        for (int k = t; k < m; k += NT) {
+        for (int k = t; k < mk; k += NT) {
             const float *p = known + (size_t)k * 3;
             sorted[k] = make_float4(p[0], p[1], p[2], __int_as_float(k));
         }
@@ -311,7 +331,7 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
         const int j = fail[1 + f];
         const float ux = unk[(size_t)j * 3 + 0], uy = unk[(size_t)j * 3 + 1], uz = unk[(size_t)j * 3 + 2];
         double b1 = empty, b2 = empty, b3 = empty;
-        for (int k = lane; k < m; k += 64) {
+        for (int k = lane; k < mk; k += 64) {
             const float4 p = sorted[k];
             const float d = sqdist_key(p.x, p.y, p.z, ux, uy, uz);
             nn_insert(__hiloint2double(__float_as_int(d), __float_as_int(p.w)), b1, b2, b3);
@@ -349,6 +369,17 @@ __global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_ragged_k
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     three_nn_cells_body<NT, true>(n, m, rows_per_part, parts, b, factor, xyz1, lengths, xyz2, dist, idx, smem);
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_ragged_pair_kernel(int n, int m, int rows_per_part, int parts, int b,
+                                                            float factor, const float *__restrict__ xyz1,
+                                                            const int *__restrict__ lengths, const float *__restrict__ xyz2,
+                                                            const int *__restrict__ lengths2, float *__restrict__ dist,
+                                                            int *__restrict__ idx)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    three_nn_cells_body<NT, true, true>(n, m, rows_per_part, parts, b, factor, xyz1, lengths, xyz2, dist, idx, smem, lengths2);
 }
 
 static size_t three_nn_cells_lds(int m, int rows_per_part)
@@ -628,9 +659,10 @@ extern "C" int pn2_fp_interp_concat_grad_planned(int b, int n, int m, int c2, in
 
 // variant: 0 = the library's choice, 1 = the sweep (three_nn_kernel), 2 = the cell list (PN2_E_ARG where it does not exist:
 // fewer than 64 or more than 8192 known points)
-// lengths: NULL = the dense kernels; else the ragged ones (valid unknown points per cloud, device memory)
+// lengths: NULL = the dense kernels; else the ragged ones (valid unknown points per cloud, device memory); lengths2 (with
+// lengths only): valid known points per cloud, the ragged-pair kernels
 static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx, int variant, void *stream,
-                          const int *lengths = nullptr)
+                          const int *lengths = nullptr, const int *lengths2 = nullptr)
 {
     using namespace pn2;
     if (b < 0 || n < 0 || m < 0) return PN2_E_SHAPE;
@@ -654,6 +686,12 @@ static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *x
         const size_t lds = three_nn_cells_lds(m, rows);
 #define PN2_NN_CELLS(NT)                                                                                                          \
         {                                                                                                                         \
+            if (lengths2) {                                                                                                       \
+                auto kern = three_nn_cells_ragged_pair_kernel<NT>;                                                                \
+                if (int rc = allow_dynamic_lds(kern, lds)) return rc;                                                             \
+                return launch(kern, dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor,  \
+                              xyz1, lengths, xyz2, lengths2, dist, idx);                                                          \
+            }                                                                                                                     \
             if (lengths) {                                                                                                        \
                 auto kern = three_nn_cells_ragged_kernel<NT>;                                                                     \
                 if (int rc = allow_dynamic_lds(kern, lds)) return rc;                                                             \
@@ -670,6 +708,9 @@ static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *x
         PN2_NN_CELLS(kNnCellsThreads)
 #undef PN2_NN_CELLS
     }
+    if (lengths2)
+        return launch(three_nn_ragged_pair_kernel, dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n,
+                      m, xyz1, lengths, xyz2, lengths2, dist, idx);
     if (lengths)
         return launch(three_nn_ragged_kernel, dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n, m,
                       xyz1, lengths, xyz2, dist, idx);
@@ -700,6 +741,21 @@ extern "C" int pn2_three_nn_ragged(int b, int n, int m, const float *xyz1, const
     if (b == 0) return PN2_OK;
     if (!lengths1) return PN2_E_NULL;
     return three_nn_entry(b, n, m, xyz1, xyz2, dist, idx, variant, stream, lengths1);
+}
+
+// Ragged on both sides: cloud c additionally holds only lengths2[c] of its m known points (b int32 on the device, clamped into
+// 1..m, never read by the host). Valid rows = pn2_three_nn_ex on (xyz1[c, :lengths1[c]], xyz2[c, :lengths2[c]]) for every
+// variant, +inf / index 0 entries included where lengths2[c] < 3; every index is below max(lengths2[c], 1). Rows at or beyond
+// lengths1[c] as in pn2_three_nn_ragged. Variant 2 exists for 64..8192 PADDED known points (a cloud with fewer than 64 of its
+// own is swept inside the kernel). Both count arrays are required.
+extern "C" int pn2_three_nn_ragged_pair(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2,
+                                        const int *lengths2, float *dist, int *idx, int variant, void *stream)
+{
+    if (variant < 0 || variant > 2) return PN2_E_ARG;
+    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
+    if (b == 0) return PN2_OK;
+    if (!lengths1 || !lengths2) return PN2_E_NULL;
+    return three_nn_entry(b, n, m, xyz1, xyz2, dist, idx, variant, stream, lengths1, lengths2);
 }
 
 static int three_interpolate_entry(int b, int m, int c, int n, const float *points, const int *idx, const float *weight,

@@ -305,6 +305,34 @@ __global__ __launch_bounds__(64) void knn_wave_ragged_kernel(int n, int m, int k
     }
 }
 
+// Ragged on both sides (pn2_knn_point_ragged_pair): cloud c also holds only lengths2[c] valid queries. A wave whose row is at
+// or beyond that count writes idx 0 / val +0.0 into the whole row and leaves -- its query is never read (wave = workgroup here).
+__global__ __launch_bounds__(64) void knn_wave_ragged_pair_kernel(int n, int m, int k, const float *__restrict__ xyz1,
+                                                                  const int *__restrict__ lengths, const float *__restrict__ xyz2,
+                                                                  const int *__restrict__ lengths2, float *__restrict__ oval,
+                                                                  int *__restrict__ oidx)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t row = blockIdx.x;
+    const size_t cloud = row / m;
+    const int mc = min(max(__builtin_amdgcn_readfirstlane(lengths2[cloud]), 1), m);
+    float *ov = oval + row * k;
+    int *oi = oidx + row * k;
+    if ((int)(row - cloud * m) >= mc) {                          // wave-uniform
+        for (int s = (int)threadIdx.x; s < k; s += 64) { ov[s] = 0.0f; oi[s] = 0; }
+        return;
+    }
+    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
+    knn_wave_body(nc, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
+    if (k > nc) {                                                // wave-uniform; as in knn_wave_ragged_kernel
+        __syncthreads();
+        __threadfence_block();
+        const float v0 = ov[0];
+        const int i0 = oi[0];
+        for (int s = nc + (int)threadIdx.x; s < k; s += 64) { ov[s] = v0; oi[s] = i0; }
+    }
+}
+
 // fallback for very long rows: the reference's own mapping (one thread per row)
 __global__ __launch_bounds__(64) void selection_sort_serial_kernel(long long rows, int n, int k,
                                                                    const float *__restrict__ dist,
@@ -389,4 +417,23 @@ extern "C" int pn2_knn_point_ragged(int b, int n, int m, int k, const float *xyz
     auto kern = knn_wave_ragged_kernel;
     if (int rc = allow_dynamic_lds(kern, lds)) return rc;
     return launch(kern, dim3((unsigned)rows), dim3(64), lds, as_stream(stream), n, m, k, xyz1, lengths1, xyz2, val, idx);
+}
+
+// Ragged on both sides: cloud c additionally holds only lengths2[c] valid rows of xyz2 (clamped into 1..m on the device). Rows
+// below lengths2[c] = pn2_knn_point_ragged; the rows from lengths2[c] on are idx 0 / val +0.0, their queries never read.
+extern "C" int pn2_knn_point_ragged_pair(int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2,
+                                         const int *lengths2, float *val, int *idx, void *stream)
+{
+    using namespace pn2;
+    if (k <= 0) return PN2_E_ARG;
+    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
+    const long long rows = (long long)b * m;
+    if (rows == 0) return PN2_OK;
+    if (!xyz1 || !lengths1 || !xyz2 || !lengths2 || !val || !idx) return PN2_E_NULL;
+    if (rows > INT_MAX || k > n) return PN2_E_TOO_LARGE;
+    if (n > kSortMaxLdsN - 2048) return PN2_E_TOO_LARGE;
+    const size_t lds = 8 * (size_t)n + sizeof(int) * (256 + 3 * (size_t)kKnnCap);
+    auto kern = knn_wave_ragged_pair_kernel;
+    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+    return launch(kern, dim3((unsigned)rows), dim3(64), lds, as_stream(stream), n, m, k, xyz1, lengths1, xyz2, lengths2, val, idx);
 }

@@ -26,7 +26,7 @@ from .geometry import FPGeometry, SAGeometry
 from .index_plan import index_plan
 
 
-def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, fused=None, lengths=None):
+def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, fused=None, lengths=None, npoints=None):
     """reference: pointnet_util.py:22-56.
 
     xyz (b, ndataset, 3), points (b, ndataset, channel) or None
@@ -39,24 +39,33 @@ def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=Tr
     lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]], points[i, :lengths[i]]): sampling
     and grouping see each cloud's own points only (the ragged operators; FPS + gather and ball query + group as two
     launches), idx names valid rows only, so the padding rows are never gathered.
+    npoints: (b,) per-cloud sample counts (cloud i yields npoints[i] <= npoint centroids): centroid rows from npoints[i] on
+    repeat sample 0 and their groups are idx 0 (point 0: valid, so the padding rows of xyz / points are still never
+    gathered); on the fused ball-query route their grouped_xyz is +0.0, elsewhere point 0 minus the centroid (= +0.0 as well).
     """
     if fused is None:
         fused = not (torch.is_grad_enabled() and xyz.requires_grad)
     if lengths is not None:
         lengths = lengths_for(lengths, xyz)
+    if npoints is not None:
+        npoints = lengths_for(npoints, xyz, "npoints")
     if fused and not knn:
-        _, new_xyz, idx, _, grouped_xyz = sample_and_group_xyz(npoint, radius, nsample, xyz, True, lengths=lengths)   # :40-46
+        _, new_xyz, idx, _, grouped_xyz = sample_and_group_xyz(npoint, radius, nsample, xyz, True, lengths=lengths,
+                                                               npoints=npoints)   # :40-46
     elif fused:
-        _, new_xyz = farthest_point_sample_gather(npoint, xyz, lengths=lengths)   # :40 in one launch
+        _, new_xyz = farthest_point_sample_gather(npoint, xyz, lengths=lengths, npoints=npoints)   # :40 in one launch
     else:
-        new_xyz = mark_fps_ordered(gather_point(xyz, farthest_point_sample(npoint, xyz, lengths=lengths)))   # :40
+        fps_idx = farthest_point_sample(npoint, xyz, lengths=lengths, npoints=npoints)
+        new_xyz = gather_point(xyz, fps_idx)                                  # :40
+        if npoints is None:
+            new_xyz = mark_fps_ordered(new_xyz)
     if fused and not knn:
         pass
     elif knn:
-        _, idx = knn_point(nsample, xyz, new_xyz, lengths1=lengths)           # :42
+        _, idx = knn_point(nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)           # :42
         grouped_xyz = group_point(xyz, idx) - new_xyz.unsqueeze(2)
     else:
-        idx, _ = query_ball_point(radius, nsample, xyz, new_xyz, lengths1=lengths)   # :44
+        idx, _ = query_ball_point(radius, nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)   # :44
         grouped_xyz = group_point(xyz, idx)                                   # :45
         grouped_xyz = grouped_xyz - new_xyz.unsqueeze(2)                      # :46 translation normalisation
     if points is not None:
@@ -96,11 +105,13 @@ def _inverse_distance_weights(dist):
     return inv / inv.sum(dim=2, keepdim=True)                                 # :213-215
 
 
-def three_nn_weights(xyz1, xyz2, lengths1=None):
+def three_nn_weights(xyz1, xyz2, lengths1=None, lengths2=None):
     """Inverse-squared-distance weights of pointnet_fp_module (pointnet_util.py:211-215).
     lengths1: (b,) per-cloud counts of a ragged unknown side (three_nn): rows beyond the length get idx (0,0,0) and the
-    finite weights (1/3, 1/3, 1/3)."""
-    dist, idx = three_nn(xyz1, xyz2, lengths1=lengths1)
+    finite weights (1/3, 1/3, 1/3).
+    lengths2: (b,) per-cloud counts of a ragged known side (three_nn): a cloud with fewer than three known points has +inf
+    distances on the missing neighbours, hence weight 0 there -- the weights stay finite."""
+    dist, idx = three_nn(xyz1, xyz2, lengths1=lengths1, lengths2=lengths2)
     return idx, _inverse_distance_weights(dist)
 
 
@@ -171,6 +182,22 @@ def _train_mode(mod, stacks, pooling, group_all, xyz, points):
     if _train_fused_ok(mod, stacks, pooling, group_all, xyz, points):
         return "fused_train"
     return "fused_frozen" if _frozen_ok(mod, stacks, pooling, group_all, xyz, points) else None
+
+
+def _valid_rows(counts, b, m, dev, name="npoints"):
+    """(b, m) bool: row j of cloud c is below counts[c] (clamped into 1..m, as the kernels clamp it). No host synchronisation."""
+    cnts = ragged_lengths(counts, b, dev, name).clamp(1, max(m, 1))
+    return torch.arange(m, device=dev, dtype=torch.int32).unsqueeze(0) < cnts.unsqueeze(1)
+
+
+def _zero_padding_rows(out, valid):
+    """Exact zeros on the rows that belong to no valid centroid / point (a torch.where: NaN-proof, no host synchronisation)."""
+    return torch.where(valid.unsqueeze(2), out, torch.zeros((), dtype=out.dtype, device=out.device))
+
+
+def _scatter_rows(yv, rows, total_rows):
+    """(len(rows), C) -> (total_rows, C) with yv on `rows` and exact zeros elsewhere (differentiable)."""
+    return torch.zeros((total_rows, yv.shape[1]), dtype=yv.dtype, device=yv.device).index_copy(0, rows, yv)
 
 
 class _SharedMLP(nn.Module):
@@ -302,18 +329,30 @@ class PointnetSAModule(nn.Module):
             self._packed(device)
         return self
 
-    def geometry(self, xyz, plans=False, lengths=None):
+    def geometry(self, xyz, plans=False, lengths=None, npoints=None):
         """This level's sampling and grouping alone (:40-46; what forward() launches before its layer stack) -> SAGeometry, or
         None for a group_all level (no sampling, the group is the cloud). geometry.GeometryAhead calls it on its own stream.
         plans: with the index plan of idx, built right behind the launch that wrote it.
         lengths: (b,) per-cloud point counts of a ragged batch: the ragged operators (each cloud's geometry is the dense
-        geometry of its slice; idx and fps_idx name valid rows only). ValueError for a group_all level."""
+        geometry of its slice; idx and fps_idx name valid rows only). ValueError for a group_all level.
+        npoints: (b,) per-cloud sample counts (cloud c yields npoints[c] <= npoint centroids): rows below the count are the
+        slice's geometry, rows from it on hold the operators' fills -- sample 0 as the centroid, a group of nsample times
+        point 0. The caller hands npoints to the next level as its lengths."""
         if self.group_all:
-            if lengths is not None:
+            if lengths is not None or npoints is not None:
                 raise ValueError("group_all with lengths: the group would contain the padding rows")
             return None
         if lengths is not None:
             lengths = ragged_lengths(lengths, xyz.shape[0], xyz.device)
+        if npoints is not None:
+            npoints = ragged_lengths(npoints, xyz.shape[0], xyz.device, "npoints")
+            if self.knn:
+                fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths, npoints=npoints)
+                _, idx = knn_point(self.nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)
+            else:
+                fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True, lengths=lengths,
+                                                                   npoints=npoints)
+            return SAGeometry(new_xyz, idx, fps_idx, index_plan(idx, xyz.shape[1], "group") if plans else None)
         if self.knn:
             fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths)
             _, idx = knn_point(self.nsample, xyz, new_xyz, lengths1=lengths)
@@ -362,7 +401,37 @@ class PointnetSAModule(nn.Module):
             out = sa_mlp.sa_mlp_maxpool(xyz, None, points, None, self._packed(xyz.device, xyz.shape[1]))
         return new_xyz, self._post(out), idx
 
-    def forward(self, xyz, points, geometry=None, lengths=None):
+    def _forward_counts(self, xyz, points, g, npoints):
+        """forward() with per-cloud sample counts on the geometry g (geometry(npoints=)): cloud c has npoints[c] valid
+        centroids; output rows from the count on are exact zeros. eval(): the existing stack paths on all npoint rows -- the
+        padding centroids' groups are nsample copies of point 0, so everything is finite -- then a torch.where; no host
+        synchronisation. train(): the batch statistics must cover the valid groups only, so the valid centroids' grouped rows
+        are compacted to (1, total, nsample, C) and the stack, the pooling and mlp2 run layer by layer on them (every pooling
+        mode); plain PyTorch, synchronises, last_path "unfused_ragged". Nothing of a padding centroid reaches a statistic or
+        a gradient; the padding rows of xyz / points are never gathered, so their gradients are exactly zero."""
+        b, m = xyz.shape[0], self.npoint
+        valid = _valid_rows(npoints, b, m, xyz.device)
+        if not self.training:
+            mode = self._train_mode(xyz, points)
+            fused = mode is None and self._fused_ok(xyz, points)
+            new_xyz, out, idx = self._forward_on(xyz, points, g, mode or ("fused" if fused else "unfused"))
+            return new_xyz, _zero_padding_rows(out, valid), idx
+        self.last_path = "unfused_ragged"
+        new_xyz, idx, plan = g.new_xyz_for(xyz), g.idx, getattr(g, "plan", None)
+        grouped_xyz = group_point(xyz, idx, plan=plan) - new_xyz.unsqueeze(2)   # :45-46
+        if points is not None:
+            grouped_points = group_point(points, idx, plan=plan)                 # :48
+            new_points = torch.cat([grouped_xyz, grouped_points], dim=-1) if self.use_xyz else grouped_points   # :50
+        else:
+            new_points = grouped_xyz
+        rows = valid.reshape(-1).nonzero().squeeze(1)                           # (total,): synchronises
+        ns = idx.shape[2]
+        pv = new_points.reshape(b * m, ns, new_points.shape[3]).index_select(0, rows).unsqueeze(0)    # (1, total, nsample, C)
+        gv = grouped_xyz.reshape(b * m, ns, 3).index_select(0, rows).unsqueeze(0)
+        _, yv, _ = self._stack_and_pool(None, pv, None, gv)                     # (1, total, C'): statistics over the valid groups
+        return new_xyz, _scatter_rows(yv[0], rows, b * m).reshape(b, m, yv.shape[2]), idx
+
+    def forward(self, xyz, points, geometry=None, lengths=None, npoints=None):
         """Resolve the level's geometry, then run the layer stack on it (_forward_on): a geometry computed ahead
         (geometry=), the ragged operators' (lengths=), or this call's own (geometry()) for the training nodes and for the
         inference kernel behind kNN or a pooling other than max. Three routes are not "geometry, then stack" and stay apart:
@@ -373,9 +442,14 @@ class PointnetSAModule(nn.Module):
         lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]], points[i, :lengths[i]]): idx
         names valid rows only, so rows beyond a length are never gathered -- they must be finite (coordinates too when the
         module trains: a training node may run its first layer once per point, padding rows included, and a NaN times a zero
-        gradient is a NaN), they influence no output and no gradient, and their own gradients are exactly zero. Not for group_all levels (ValueError)."""
-        if lengths is not None and self.group_all:
+        gradient is a NaN), they influence no output and no gradient, and their own gradients are exactly zero. Not for group_all levels (ValueError).
+        npoints: (b,) per-cloud sample counts, with or without lengths (_forward_counts; a geometry= must come from
+        geometry(npoints=)): new_points rows from npoints[c] on are exact zeros; hand npoints to the next level as its lengths."""
+        if (lengths is not None or npoints is not None) and self.group_all:
             raise ValueError("group_all with lengths: the group would contain the padding rows")
+        if npoints is not None:
+            g = geometry.wait() if geometry is not None else self.geometry(xyz, lengths=lengths, npoints=npoints)
+            return self._forward_counts(xyz, points, g, npoints)
         mode = self._train_mode(xyz, points)
         if self.group_all and (mode is not None or self._fused_ok(xyz, points)):
             return self._forward_all(xyz, points, mode)
@@ -497,12 +571,26 @@ class PointnetSAModuleMSG(nn.Module):
             scales += [(i, g) for i, _, g in rest]
         return (new_xyz, scales, fps_idx) if with_fps else (new_xyz, scales)
 
-    def geometry(self, xyz, plans=False, lengths=None):
+    def geometry(self, xyz, plans=False, lengths=None, npoints=None):
         """This level's sampling and every radius' grouping alone (:173-180) -> SAGeometry with one idx per radius (plans: and
         one index plan per radius). lengths: (b,) per-cloud point counts of a ragged batch: ragged FPS + gather, then one
         ragged ball query per radius -- or, with ragged_one_launch, ONE ragged multi-radius launch for all radii (the first
-        included: there is no overlapped launch with lengths to serve it); the results are the same bit for bit."""
-        if lengths is not None:
+        included: there is no overlapped launch with lengths to serve it); the results are the same bit for bit.
+        npoints: (b,) per-cloud sample counts (see PointnetSAModule.geometry), with or without lengths: the two-sided ragged
+        operators, one launch per radius or -- ragged_one_launch -- one for all; same bits."""
+        if npoints is not None:
+            b, dev = xyz.shape[0], xyz.device
+            npoints = ragged_lengths(npoints, b, dev, "npoints")
+            if lengths is not None:
+                lengths = ragged_lengths(lengths, b, dev)
+            fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths, npoints=npoints)
+            if self.ragged_one_launch:
+                scales = [(i, g) for i, _, g in query_ball_group_xyz_msg(self.radius_list, self.nsample_list, xyz, new_xyz, True,
+                                                                         lengths1=lengths, lengths2=npoints)]
+            else:
+                scales = [query_ball_group_xyz(r, k, xyz, new_xyz, True, lengths1=lengths, lengths2=npoints)[0::2]
+                          for r, k in zip(self.radius_list, self.nsample_list)]
+        elif lengths is not None:
             lengths = ragged_lengths(lengths, xyz.shape[0], xyz.device)
             fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths)
             if self.ragged_one_launch:
@@ -570,13 +658,32 @@ class PointnetSAModuleMSG(nn.Module):
             outs.append(x.max(dim=3)[0])                                        # :193
         return new_xyz, torch.cat(outs, dim=1).permute(0, 2, 1).contiguous()    # :195
 
-    def forward(self, xyz, points, geometry=None, lengths=None):
-        """Resolve the level's geometry -- computed ahead (geometry=), the ragged operators' (lengths=, see
-        PointnetSAModule.forward) or, for the training nodes, this call's own (geometry()) -- then one function per path on it.
-        Without a geometry the inference kernels and the layer-by-layer path keep their own launches (_group_scales)."""
-        if geometry is None and lengths is not None:
-            geometry = self.geometry(xyz, lengths=lengths)
-        g = None if geometry is None else geometry.wait()
+    def _forward_counts(self, xyz, points, g, npoints):
+        """forward() with per-cloud sample counts, see PointnetSAModule._forward_counts: eval() runs the existing paths on all
+        rows and zeroes the padding rows; train() compacts the valid centroids' groups per radius and runs each stack layer by
+        layer on (1, C, total, nsample) -- last_path "unfused_ragged", synchronises."""
+        b, m = xyz.shape[0], self.npoint
+        valid = _valid_rows(npoints, b, m, xyz.device)
+        if not self.training:
+            new_xyz, out = self._forward_on_geometry(xyz, points, g)
+            return new_xyz, _zero_padding_rows(out, valid)
+        self.last_path = "unfused_ragged"
+        new_xyz = g.new_xyz_for(xyz)
+        rows = valid.reshape(-1).nonzero().squeeze(1)                           # (total,): synchronises
+        outs = []
+        for idx, mlp in zip(g.idx, self.mlps):
+            grouped = group_point(xyz, idx) - new_xyz.unsqueeze(2)              # :179-180
+            if points is not None:
+                feats = group_point(points, idx)                                # :182
+                grouped = torch.cat([feats, grouped], dim=-1) if self.use_xyz else feats   # :184 features FIRST
+            gv = grouped.reshape(b * m, idx.shape[2], grouped.shape[3]).index_select(0, rows)          # (total, nsample, C)
+            outs.append(mlp(gv.permute(2, 0, 1).unsqueeze(0)).max(dim=3)[0][0].t())                # (total, C')  :193
+        yv = torch.cat(outs, dim=1)                                             # :195
+        return new_xyz, _scatter_rows(yv, rows, b * m).reshape(b, m, yv.shape[1])
+
+    def _forward_on_geometry(self, xyz, points, g):
+        """One function per path on a geometry (g None: the inference kernels and the layer-by-layer path keep their own
+        launches, the training nodes take this call's own geometry())."""
         if self._fused_ok(xyz, points):
             self.last_path = "fused"
             return self._forward_fused(xyz, points, g)
@@ -586,6 +693,18 @@ class PointnetSAModuleMSG(nn.Module):
             return self._forward_train(xyz, points, g or self.geometry(xyz, plans=self.index_plans and torch.is_grad_enabled()), mode)
         self.last_path = "unfused"
         return self._forward_layers(xyz, points, g)
+
+    def forward(self, xyz, points, geometry=None, lengths=None, npoints=None):
+        """Resolve the level's geometry -- computed ahead (geometry=), the ragged operators' (lengths=, see
+        PointnetSAModule.forward) or, for the training nodes, this call's own (geometry()) -- then one function per path on it.
+        Without a geometry the inference kernels and the layer-by-layer path keep their own launches (_group_scales).
+        npoints: (b,) per-cloud sample counts, with or without lengths (_forward_counts)."""
+        if npoints is not None:
+            g = geometry.wait() if geometry is not None else self.geometry(xyz, lengths=lengths, npoints=npoints)
+            return self._forward_counts(xyz, points, g, npoints)
+        if geometry is None and lengths is not None:
+            geometry = self.geometry(xyz, lengths=lengths)
+        return self._forward_on_geometry(xyz, points, None if geometry is None else geometry.wait())
 
 
 class PointnetFPModule(nn.Module):
@@ -696,7 +815,7 @@ class PointnetFPModule(nn.Module):
         x, _ = fp_interp_concat(points2, points1, idx, dist, plan=plan)         # :212-219, on every row
         return train_mlp.fp_mlp_train(self.mlp.net, x, cin=c2 + c1, frozen=mode == "fused_frozen", lengths=lengths)
 
-    def _forward_ragged(self, xyz1, xyz2, points1, points2, lengths1, geometry=None):
+    def _forward_ragged(self, xyz1, xyz2, points1, points2, lengths1, geometry=None, lengths2=None):
         """forward() with a ragged unknown side: cloud i's unknown points are xyz1[i, :lengths1[i]] (points1 likewise; the
         known side is a previous level's dense output). three_nn never reads the padding rows; output rows beyond a length
         are exactly zero. eval(): the existing paths on all rows (the padding rows of points1 must be finite), then a
@@ -710,7 +829,10 @@ class PointnetFPModule(nn.Module):
         take the one-node form (fp_level_preferred) and train_mlp.fp_level_ragged_supported says yes: weights, interpolation,
         concatenation and the stack as ONE node with the row mask inside, layer 1 once per known point
         (fp_level_train(..., lengths=)); last_path "fused_train_ragged_node". Without that attribute the two-launch route is
-        taken even where fp_level_preferred would choose the node."""
+        taken even where fp_level_preferred would choose the node.
+        lengths2: a ragged KNOWN side as well (cloud i's known points are xyz2[i, :lengths2[i]], points2 likewise): only
+        three_nn changes -- idx stays below lengths2[i] on the valid rows, so the padding rows of points2 are never gathered
+        and their gradient is exactly zero; they must be finite (the one-node form multiplies every known row by W1a)."""
         b, n = xyz1.shape[0], xyz1.shape[1]
         dev = xyz1.device
         lens = ragged_lengths(lengths1, b, dev, "lengths1")
@@ -718,7 +840,7 @@ class PointnetFPModule(nn.Module):
         if geometry is not None:
             g = geometry.wait()
         else:
-            dist, idx = three_nn(xyz1, xyz2, lengths1=lens)                     # :211
+            dist, idx = three_nn(xyz1, xyz2, lengths1=lens, lengths2=lengths2)   # :211
             g = FPGeometry(dist, idx, self._plan_of(idx, xyz2.shape[1]))
         if not self.training:
             out = self._forward_on(xyz1, points1, points2, g)
@@ -737,12 +859,17 @@ class PointnetFPModule(nn.Module):
         out = torch.zeros((b * n, yv.shape[1]), dtype=yv.dtype, device=dev).index_copy(0, rows, yv)
         return out.reshape(b, n, yv.shape[1])
 
-    def forward(self, xyz1, xyz2, points1, points2, geometry=None, lengths1=None):
+    def forward(self, xyz1, xyz2, points1, points2, geometry=None, lengths1=None, lengths2=None):
         """three_nn -- computed ahead (geometry=) or here -- then the stack on its result (_stack_on). One route stays apart:
         inference without a geometry is ONE C call (sa_mlp.fp_level: three_nn and the level's kernel; it owns the level's
-        buffers). lengths1: a ragged unknown side, see _forward_ragged."""
+        buffers). lengths1: a ragged unknown side, see _forward_ragged. lengths2: a ragged known side (a previous level's
+        npoints); without lengths1 the unknown side is dense and the result is that of the dense routes on the two-sided
+        three_nn's result."""
         if lengths1 is not None:
-            return self._forward_ragged(xyz1, xyz2, points1, points2, lengths1, geometry)
+            return self._forward_ragged(xyz1, xyz2, points1, points2, lengths1, geometry, lengths2)
+        if geometry is None and lengths2 is not None:
+            dist, idx = three_nn(xyz1, xyz2, lengths2=lengths2)                  # :211
+            return self._forward_on(xyz1, points1, points2, FPGeometry(dist, idx, self._plan_of(idx, xyz2.shape[1])))
         if geometry is not None:
             return self._forward_on(xyz1, points1, points2, geometry.wait())
         kind = self._fused_kind(points1, points2, xyz1.shape[0] * xyz1.shape[1])

@@ -10,7 +10,7 @@ NoGradient (:21, :32).
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, f32, i32, lengths_for, on_device, ptr, ragged_lengths, require, same_device, scatter_grad,
+from ._tensors import (out_or_empty, f32, full_counts, i32, lengths_for, on_device, ptr, ragged_lengths, require, same_device, scatter_grad,
                        stream_ptr)
 
 
@@ -25,11 +25,22 @@ def set_ball_query_kernel(kernel=0, cells_qpb=0):
     _BQ_KERNEL[0], _BQ_KERNEL[1] = int(kernel), int(cells_qpb)
 
 
-def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None):
+def pair_counts(lengths1, lengths2, b, n, m, dev):
+    """Both count arrays of a two-sided ragged call as the *_ragged_pair entries take them: the side given as None becomes an
+    array of full counts made on the device (no synchronisation)."""
+    lens1 = ragged_lengths(lengths1, b, dev, "lengths1") if lengths1 is not None else full_counts(b, n, dev)
+    lens2 = ragged_lengths(lengths2, b, dev, "lengths2") if lengths2 is not None else full_counts(b, m, dev)
+    return lens1, lens2
+
+
+def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None, lengths2=None):
     """radius float, nsample int, xyz1 (b, ndataset, 3), xyz2 (b, npoint, 3)
     -> idx (b, npoint, nsample) i32, pts_cnt (b, npoint) i32.
     lengths1: (b,) per-cloud point counts of a ragged xyz1 (cloud i is xyz1[i, :lengths1[i]]): each cloud's result is the
     dense operator's on its slice, rows beyond the length are never read. None = every cloud holds all ndataset points.
+    lengths2: (b,) per-cloud counts of valid QUERY rows of xyz2 (cloud i asks xyz2[i, :lengths2[i]]): rows below the count are the
+    dense operator's on the slice pair, rows from the count on are never read and come back as idx 0 / pts_cnt 0 (and
+    grouped_xyz +0.0 in the fused operators). With one of lengths1 / lengths2 given the other side is dense.
 
     reference: tf_grouping.py:8-20, op QueryBallPoint tf_grouping.cpp:67-106.
     out: optional preallocated (idx, pts_cnt).
@@ -38,6 +49,8 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None):
     require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
+    if lengths2 is not None:
+        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
@@ -49,6 +62,13 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None):
     ns = int(nsample)
     idx = out_or_empty(out[0] if out is not None else None, (b, m, ns), torch.int32, dev, "out[0]")
     cnt = out_or_empty(out[1] if out is not None else None, (b, m), torch.int32, dev, "out[1]")
+    if lengths2 is not None:
+        lens, lens2 = pair_counts(lengths1, lengths2, b, n, m, dev)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_query_ball_group_xyz_ragged_pair(b, n, m, float(radius), ns, ptr(xyz1), ptr(lens), ptr(xyz2),
+                                                                   ptr(lens2), 0, ptr(idx), ptr(cnt), None, _BQ_KERNEL[0],
+                                                                   _BQ_KERNEL[1], stream_ptr(dev)), "query_ball_point")
+        return idx, cnt
     if lengths1 is not None:
         lens = ragged_lengths(lengths1, b, dev, "lengths1")
         with on_device(dev):
@@ -67,7 +87,7 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None):
     return idx, cnt
 
 
-def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None):
+def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None, lengths2=None):
     """Fused query_ball_point + group_point(xyz1, idx) [- centroid] in one pass
     (what pointnet_util.py:44-46 does with three ops). No reference counterpart
     (SURVEY.md 8f1); NOT differentiable -- used on the inference path and by
@@ -75,11 +95,14 @@ def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, wa
 
     -> idx (b,m,nsample) i32 or None, pts_cnt (b,m) i32, grouped_xyz (b,m,nsample,3) f32
     lengths1: (b,) per-cloud point counts of a ragged xyz1, see query_ball_point.
+    lengths2: (b,) per-cloud counts of valid query rows, see query_ball_point.
     """
     require(float(radius) > 0, "QueryBallPoint expects positive radius")
     require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
+    if lengths2 is not None:
+        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
@@ -92,6 +115,14 @@ def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, wa
     idx = torch.empty((b, m, ns), dtype=torch.int32, device=dev) if want_idx else None
     cnt = torch.empty((b, m), dtype=torch.int32, device=dev)
     grouped = torch.empty((b, m, ns, 3), dtype=torch.float32, device=dev)
+    if lengths2 is not None:
+        lens, lens2 = pair_counts(lengths1, lengths2, b, n, m, dev)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_query_ball_group_xyz_ragged_pair(b, n, m, float(radius), ns, ptr(xyz1), ptr(lens), ptr(xyz2),
+                                                                   ptr(lens2), 1 if subtract_centroid else 0, ptr(idx), ptr(cnt),
+                                                                   ptr(grouped), _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)),
+                     "query_ball_group_xyz")
+        return idx, cnt, grouped
     if lengths1 is not None:
         lens = ragged_lengths(lengths1, b, dev, "lengths1")
         with on_device(dev):
@@ -108,13 +139,16 @@ def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, wa
     return idx, cnt, grouped
 
 
-def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None):
+def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None,
+                             lengths2=None):
     """Every radius of a multi-scale-grouping level in ONE launch: the cloud is staged and binned once
     per workgroup and queried once per radius (pn2_query_ball_group_xyz_msg; reference loop
     pointnet_util.py:175-186 runs query_ball_point + group_point + subtraction per radius).
     Bit-identical to query_ball_group_xyz called per radius. Not differentiable.
     lengths1: (b,) per-cloud point counts of a ragged xyz1, see query_ball_point (pn2_query_ball_group_xyz_msg_ragged: still one
     launch, every cloud's own points staged and binned once); bit-identical to query_ball_group_xyz(..., lengths1=) per radius.
+    lengths2: (b,) per-cloud counts of valid query rows, see query_ball_point (pn2_query_ball_group_xyz_msg_ragged_pair: still
+    one launch); bit-identical to query_ball_group_xyz(..., lengths1=, lengths2=) per radius, fill rows included.
 
     -> [(idx (b,m,ns_i) i32 or None, pts_cnt (b,m) i32, grouped_xyz (b,m,ns_i,3) f32) for every scale]
     """
@@ -126,6 +160,8 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     require(all(k > 0 for k in nsample_list), "QueryBallPoint expects positive nsample")
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
+    if lengths2 is not None:
+        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
@@ -135,9 +171,13 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
     ns_count = len(radius_list)
-    lens = ragged_lengths(lengths1, b, dev, "lengths1") if lengths1 is not None else None
+    lens2 = None
+    if lengths2 is not None:
+        lens, lens2 = pair_counts(lengths1, lengths2, b, n, m, dev)
+    else:
+        lens = ragged_lengths(lengths1, b, dev, "lengths1") if lengths1 is not None else None
     if ns_count > 4 or n > 8192:                                  # outside the multi-radius kernel's envelope
-        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens)
+        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens, lengths2=lens2)
                 for r, k in zip(radius_list, nsample_list)]
     # one allocation per dtype, carved into per-scale views (allocations dominate the host time of this call)
     tot = sum(nsample_list)
@@ -160,7 +200,11 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     pc = (ctypes.c_void_p * ns_count)(*[ptr(o[1]) for o in outs])
     pg = (ctypes.c_void_p * ns_count)(*[ptr(o[2]) for o in outs])
     with on_device(dev):
-        if lens is not None:
+        if lens2 is not None:
+            rc = _C.lib().pn2_query_ball_group_xyz_msg_ragged_pair(b, n, m, ns_count, radii, nss, ptr(xyz1), ptr(lens), ptr(xyz2),
+                                                                   ptr(lens2), 1 if subtract_centroid else 0, pi, pc, pg,
+                                                                   stream_ptr(dev))
+        elif lens is not None:
             rc = _C.lib().pn2_query_ball_group_xyz_msg_ragged(b, n, m, ns_count, radii, nss, ptr(xyz1), ptr(lens), ptr(xyz2),
                                                               1 if subtract_centroid else 0, pi, pc, pg, stream_ptr(dev))
         else:
@@ -169,7 +213,7 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     if rc == -4:
         # PN2_E_TOO_LARGE: no LDS geometry fits this combination (e.g. n = 8192 with nsample >= 127 on a later radius);
         # nothing has been launched -- the per-radius operator covers every shape
-        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens)
+        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens, lengths2=lens2)
                 for r, k in zip(radius_list, nsample_list)]
     _C.check(rc, "query_ball_group_xyz_msg")
     return outs
@@ -370,16 +414,16 @@ def check_overlapped_launches(device=None):
         _check_status(ent, wait=True)
 
 
-def _two_launch_path(m, radius, ns, xyz, subtract_centroid, ordered=None, lengths=None):
+def _two_launch_path(m, radius, ns, xyz, subtract_centroid, ordered=None, lengths=None, npoints=None):
     """farthest_point_sample_gather + query_ball_group_xyz: what the overlapped launch computes, in two launches.
     ordered: the farthest-point-order hint of the CALLER's tensor (None = read it from xyz)."""
     from .tf_sampling import farthest_point_sample_gather
-    fps_idx, new_xyz = farthest_point_sample_gather(m, xyz, ordered=ordered, lengths=lengths)
-    idx, cnt, grouped = query_ball_group_xyz(radius, ns, xyz, new_xyz, subtract_centroid, lengths1=lengths)
+    fps_idx, new_xyz = farthest_point_sample_gather(m, xyz, ordered=ordered, lengths=lengths, npoints=npoints)
+    idx, cnt, grouped = query_ball_group_xyz(radius, ns, xyz, new_xyz, subtract_centroid, lengths1=lengths, lengths2=npoints)
     return fps_idx, new_xyz, idx, cnt, grouped
 
 
-def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, ordered=None, lengths=None):
+def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, ordered=None, lengths=None, npoints=None):
     """The xyz half of sample_and_group (pointnet_util.py:40-46) in ONE launch: farthest point
     sampling, gather, ball query and grouping of xyz, with the ball queries running on the idle CUs
     while the FPS chain is still selecting (csrc/sa_fused.hip). Bit-identical to the separate
@@ -391,6 +435,9 @@ def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, o
 
     lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]]): always the two launches
     (ragged farthest_point_sample_gather, ragged query_ball_group_xyz) -- the overlapped launch is not offered for ragged input.
+    npoints: (b,) per-cloud sample counts (farthest_point_sample_gather): the two launches again, the ball query ragged on its
+    query side (lengths2 = npoints). Centroid rows from npoints[i] on repeat sample 0 and their groups are idx 0 / pts_cnt 0 /
+    grouped_xyz +0.0.
 
     -> fps_idx (b,m) i32, new_xyz (b,m,3) f32, idx (b,m,nsample) i32, pts_cnt (b,m) i32,
        grouped_xyz (b,m,nsample,3) f32
@@ -401,6 +448,8 @@ def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, o
     from .tf_sampling import mark_fps_ordered, ordered_hint, ordered_worthwhile
     if lengths is not None:
         lengths = lengths_for(lengths, xyz)
+    if npoints is not None:
+        npoints = lengths_for(npoints, xyz, "npoints")
     if ordered is None:
         ordered = isinstance(xyz, torch.Tensor) and ordered_hint(xyz, int(npoint))
     xyz = f32(xyz, "xyz")
@@ -408,6 +457,9 @@ def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, o
     b, n, _ = xyz.shape
     m, ns = int(npoint), int(nsample)
     dev = xyz.device
+    if npoints is not None:
+        lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
+        return _two_launch_path(m, radius, ns, xyz, subtract_centroid, False, lens, ragged_lengths(npoints, b, dev, "npoints"))
     if lengths is not None:
         return _two_launch_path(m, radius, ns, xyz, subtract_centroid, False, ragged_lengths(lengths, b, dev))
     lib = _C.lib()
@@ -530,12 +582,14 @@ def group_point(points, idx, out=None, plan=None):
     return _GroupPoint.apply(points, idx, plan)
 
 
-def knn_point(k, xyz1, xyz2, lengths1=None):
+def knn_point(k, xyz1, xyz2, lengths1=None, lengths2=None):
     """k int, xyz1 (b, ndataset, c), xyz2 (b, npoint, c) -> val (b, npoint, k) f32
     squared L2 distances, idx (b, npoint, k) i32.
     lengths1: (b,) per-cloud point counts of a ragged xyz1 (cloud i is xyz1[i, :lengths1[i]]; 3-D points, at most 14336 per
     padded cloud, k <= ndataset -- ValueError outside): the first min(k, lengths1[i]) entries of a row are the dense
     operator's on the slice, and where k > lengths1[i] the rest repeat entry 0 (the way a ball query pads with its first hit).
+    lengths2: (b,) per-cloud counts of valid query rows of xyz2 (same envelope): rows from lengths2[i] on are never read and
+    come back as idx 0 / val +0.0. With one of lengths1 / lengths2 given the other side is dense.
 
     reference: tf_grouping.py:48-73 -- a pairwise squared-distance matrix
     reduce_sum((xyz1-xyz2)**2, -1) followed by select_top_k and a slice.
@@ -545,6 +599,8 @@ def knn_point(k, xyz1, xyz2, lengths1=None):
     """
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
+    if lengths2 is not None:
+        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz2.dim() == 3 and xyz1.shape[0] == xyz2.shape[0] and
@@ -552,6 +608,17 @@ def knn_point(k, xyz1, xyz2, lengths1=None):
     b, n, c = xyz1.shape
     m = xyz2.shape[1]
     require(int(k) > 0, "SelectionSort expects positive k")
+    if lengths2 is not None:
+        require(c == 3 and n <= 14336 and int(k) <= n,
+                "knn_point with lengths2 expects 3-D points, at most 14336 points per (padded) cloud and k <= ndataset")
+        dev = same_device(xyz1, xyz2)
+        lens, lens2 = pair_counts(lengths1, lengths2, b, n, m, dev)
+        val = torch.empty((b, m, int(k)), dtype=torch.float32, device=dev)
+        idx = torch.empty((b, m, int(k)), dtype=torch.int32, device=dev)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_knn_point_ragged_pair(b, n, m, int(k), ptr(xyz1), ptr(lens), ptr(xyz2), ptr(lens2), ptr(val),
+                                                        ptr(idx), stream_ptr(dev)), "knn_point")
+        return val, idx
     if lengths1 is not None:
         require(c == 3 and n <= 14336 and int(k) <= n,
                 "knn_point with lengths1 expects 3-D points, at most 14336 points per (padded) cloud and k <= ndataset")

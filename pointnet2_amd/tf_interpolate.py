@@ -10,21 +10,26 @@ gradient w.r.t. `points` only (tf_interpolate.py:29-34); ThreeNN is NoGradient (
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, f32, i32, is_deterministic, lengths_for, on_device, ptr, ragged_lengths, require, same_device,
+from ._tensors import (out_or_empty, f32, full_counts, i32, is_deterministic, lengths_for, on_device, ptr, ragged_lengths, require, same_device,
                        scatter_grad, seg_workspace, stream_ptr)
 
 
-def three_nn(xyz1, xyz2, out=None, lengths1=None):
+def three_nn(xyz1, xyz2, out=None, lengths1=None, lengths2=None):
     """xyz1 (b, n, 3) unknown, xyz2 (b, m, 3) known -> dist (b, n, 3) f32 SQUARED
     distances ascending, idx (b, n, 3) i32. out: optional preallocated (dist, idx).
     lengths1: (b,) per-cloud counts of a ragged UNKNOWN side (cloud i is xyz1[i, :lengths1[i]]; the known side is dense):
     valid rows are the dense operator's, rows beyond the length are never read and come back as idx (0,0,0), dist (0,0,0).
+    lengths2: (b,) per-cloud counts of a ragged KNOWN side (cloud i's known points are xyz2[i, :lengths2[i]]; rows beyond are
+    never read): every row is the dense operator's on the slice pair, so idx < lengths2[i], and fewer than three known points
+    leave the dense operator's +inf / index 0 entries. With one of lengths1 / lengths2 given the other side is dense.
 
     reference: tf_interpolate.py:8-17, op ThreeNN tf_interpolate.cpp:157-187,
     loop threenn_cpu :60-103.
     """
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
+    if lengths2 is not None:
+        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
     require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "ThreeNN expects (b,n,3) xyz1 shape")
@@ -35,6 +40,13 @@ def three_nn(xyz1, xyz2, out=None, lengths1=None):
     m = xyz2.shape[1]
     dist = out_or_empty(out[0] if out is not None else None, (b, n, 3), torch.float32, dev, "out[0]")
     idx = out_or_empty(out[1] if out is not None else None, (b, n, 3), torch.int32, dev, "out[1]")
+    if lengths2 is not None:
+        lens = ragged_lengths(lengths1, b, dev, "lengths1") if lengths1 is not None else full_counts(b, n, dev)
+        lens2 = ragged_lengths(lengths2, b, dev, "lengths2")
+        with on_device(dev):
+            _C.check(_C.lib().pn2_three_nn_ragged_pair(b, n, m, ptr(xyz1), ptr(lens), ptr(xyz2), ptr(lens2), ptr(dist), ptr(idx), 0,
+                                                       stream_ptr(dev)), "three_nn")
+        return dist, idx
     if lengths1 is not None:
         lens = ragged_lengths(lengths1, b, dev, "lengths1")
         with on_device(dev):

@@ -11,7 +11,7 @@ ProbSample are NoGradient (:22, :57).
 import torch
 
 from . import _C
-from ._tensors import (det_workspace, f32, i32, is_deterministic, lengths_for, on_device, out_or_empty, ptr, ragged_lengths,
+from ._tensors import (det_workspace, f32, full_counts, i32, is_deterministic, lengths_for, on_device, out_or_empty, ptr, ragged_lengths,
                        require, same_device, stream_ptr)
 
 
@@ -158,20 +158,31 @@ def ordered_workspace(lib, dev, stream, b):
 FPS_RAGGED_MAX_POINTS = 16384           # the register tier's envelope (pn2_farthest_point_sample_ragged)
 
 
-def _fps_ragged(m, inp, lengths, out, new_xyz, op):
+def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
     b, n, _ = inp.shape
     require(n <= FPS_RAGGED_MAX_POINTS, "%s with lengths supports at most %d points per (padded) cloud, got %d"
             % (op, FPS_RAGGED_MAX_POINTS, n))
     dev = inp.device
-    lens = ragged_lengths(lengths, b, dev)
+    if npoints is None:
+        lens = ragged_lengths(lengths, b, dev)
+        with on_device(dev):
+            _C.check(_C.lib().pn2_farthest_point_sample_ragged(b, n, m, ptr(inp), ptr(lens), ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
+        return
+    # per-cloud sample counts; without lengths every cloud holds all n points (an array of full counts made on the device)
+    lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
+    cnts = ragged_lengths(npoints, b, dev, "npoints")
     with on_device(dev):
-        _C.check(_C.lib().pn2_farthest_point_sample_ragged(b, n, m, ptr(inp), ptr(lens), ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
+        _C.check(_C.lib().pn2_farthest_point_sample_ragged_counts(b, n, m, ptr(inp), ptr(lens), ptr(cnts), ptr(out), ptr(new_xyz),
+                                                                  stream_ptr(dev)), op)
 
 
-def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None):
+def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoints=None):
     """Fused farthest_point_sample + gather_point (pointnet_util.py:40 in one launch).
     lengths: (b,) per-cloud point counts of a ragged batch (cloud i is inp[i, :lengths[i]]): each cloud's result is the
     dense operator's on its slice, rows beyond the length are never read. None = every cloud holds all n points.
+    npoints: (b,) per-cloud sample counts (cloud i yields m_i = npoints[i] <= npoint samples; clamped into 1..npoint on the
+    device, check_lengths(npoints, npoint) validates): rows below m_i are the first m_i samples of the slice, rows from m_i on
+    repeat sample 0 (idx 0, the cloud's first point). Without lengths every cloud holds all n points.
 
     npoint int, inp (b, ndataset, 3) f32 -> idx (b, npoint) i32, new_xyz (b, npoint, 3) f32
     with new_xyz == gather_point(inp, idx) bit for bit. No reference counterpart
@@ -182,6 +193,8 @@ def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None):
     require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
     if lengths is not None:
         lengths = lengths_for(lengths, inp)
+    if npoints is not None:
+        npoints = lengths_for(npoints, inp, "npoints")
     if ordered is None:                                    # (before detach(): the hint is an attribute of the caller's tensor object)
         ordered = isinstance(inp, torch.Tensor) and ordered_hint(inp, npoint)
     inp = f32(inp.detach() if isinstance(inp, torch.Tensor) else inp, "inp")
@@ -192,9 +205,9 @@ def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None):
     dev = inp.device
     out = torch.empty((b, m), dtype=torch.int32, device=dev)
     new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=dev)
-    if lengths is not None:
-        _fps_ragged(m, inp, lengths, out, new_xyz, "farthest_point_sample_gather")
-        return out, mark_fps_ordered(new_xyz)
+    if lengths is not None or npoints is not None:
+        _fps_ragged(m, inp, lengths, out, new_xyz, "farthest_point_sample_gather", npoints)
+        return out, (mark_fps_ordered(new_xyz) if npoints is None else new_xyz)   # fill rows break the farthest-point order
     lib = _C.lib()
     tf = lib.pn2_fps_temp_floats(b, n)
     temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None
@@ -213,9 +226,10 @@ def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None):
     return out, mark_fps_ordered(new_xyz)
 
 
-def farthest_point_sample(npoint, inp, out=None, lengths=None):
+def farthest_point_sample(npoint, inp, out=None, lengths=None, npoints=None):
     """npoint int, inp (b, ndataset, 3) f32 -> (b, npoint) i32, first index 0.
     lengths: (b,) per-cloud point counts of a ragged batch, see farthest_point_sample_gather.
+    npoints: (b,) per-cloud sample counts, see farthest_point_sample_gather.
 
     reference: tf_sampling.py:48-56, op FarthestPointSample tf_sampling.cpp:95-123,
     kernel tf_sampling_g.cu:105-170 (tie rule: smallest (k mod 512, k)).
@@ -224,6 +238,8 @@ def farthest_point_sample(npoint, inp, out=None, lengths=None):
     require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
     if lengths is not None:
         lengths = lengths_for(lengths, inp)
+    if npoints is not None:
+        npoints = lengths_for(npoints, inp, "npoints")
     hinted = isinstance(inp, torch.Tensor) and ordered_hint(inp, npoint)      # the previous level's samples: checked short cut
     inp = f32(inp.detach() if isinstance(inp, torch.Tensor) else inp, "inp")
     require(inp.dim() == 3 and inp.shape[2] == 3, "FarthestPointSample expects (batch_size,num_points,3) inp shape")
@@ -232,8 +248,8 @@ def farthest_point_sample(npoint, inp, out=None, lengths=None):
     m = int(npoint)
     dev = inp.device
     out = out_or_empty(out, (b, m), torch.int32, dev)
-    if lengths is not None:
-        _fps_ragged(m, inp, lengths, out, None, "farthest_point_sample")
+    if lengths is not None or npoints is not None:
+        _fps_ragged(m, inp, lengths, out, None, "farthest_point_sample", npoints)
         return out
     lib = _C.lib()
     tf = lib.pn2_fps_temp_floats(b, n)
