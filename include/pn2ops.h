@@ -820,6 +820,52 @@ int pn2_mlp_train_backward_fp_ragged(int nlayers, const pn2_bn_layer *layers, co
                                      float *grad_points1, int reproducible, const void *mask, void *ws, const pn2_train_opts *opts,
                                      void *stream);
 
+/* The training node on the GROUPED rows of a RAGGED batch (csrc/train_mlp_ragged_group.hip): pn2_mlp_train_forward_ex /
+ * _backward_ex with a group and the max pool (pool_rows == group->nsample), batch statistics, and counts (b) i32 ON THE DEVICE:
+ *   group->idx != NULL   counts[c] = valid centroids of cloud c, clamped into 1..m (the clamp of the _ragged_pair operators): row
+ *                        (c, j, k) of the flat order r = (c m + j) nsample + k is VALID iff j < counts[c];
+ *   group->idx == NULL   (group_all: m == 1, nsample == n) counts[c] = valid points of cloud c, clamped into 1..n: row (c, 0, k)
+ *                        is VALID iff k < counts[c].
+ * N_valid = unit * sum of the clamped counts, unit = nsample in the first case, 1 in the second. mask: the buffer of
+ * pn2_mlp_train_forward_ragged, 16 + 4 (rows / 32) bytes, 8-byte aligned: forward writes it, backward reads it.
+ * The contract is the plain-rows ragged node's: the batch moments, the running statistics and every gradient are those of the
+ * valid rows alone, by selects, never by products. Rows of xyz / points beyond a cloud's own points, the rows of a group_all level
+ * beyond counts[c] and the grad_out rows of padding groups may hold anything, NaN and Inf included. idx ON PADDING GROUPS MUST HOLD
+ * INDICES IN [0, n) (the _ragged_pair operators write 0 there). layers[l].z is all-zero bits on padding rows; out rows of padding
+ * groups are all-zero bits and their argsel is 0; grad_feat_rows ((rows, cfeat), the caller scatters it as the dense node's; for
+ * group_all it IS the gradient of points) is all-zero bits on padding rows; argsel of a valid group names a valid row of it. There
+ * is no zsel. No host synchronisation, no memset; capturable, a replay sees whatever counts holds then; reproducible run to run.
+ * Organisation: ONE fixed one (csrc/train_mlp.hip: ragged_group_opts): the plain-rows ragged node's, and of the grouped node's
+ * alternative forms none -- layer 1 is the gathered GEMM (tl_gemm_masked_kernel<NS, A_GATHER>) with the gathered masked
+ * weight-gradient pass (tl_wgrad_masked_gather_kernel<TPW, UPW>), z_L is always stored (the caller allocates every layers[l].z)
+ * and pooled over its valid rows by a vector-unit pass of its own, and backward forms the dense dy_L and runs an unpooled stack. The
+ * pn2_train_opts fields top_stored, top_sparse, l1_per_point, l1_coords, fuse_wgrad, pair_launch, side_stream and fold_finalize
+ * are IGNORED; force_stream, max_ns, nt and wgrad_two_per_cu act as in the dense entries. With full counts the results agree with
+ * the dense node's to rounding, not bit for bit (the dense node pools in the GEMM's epilogue and sums the top gradient per group).
+ * Not offered: frozen statistics, coordinate gradients, the pooling modes other than max.
+ * _supported: 1 where group_dims {b, n, m, nsample, cfeat, idx != NULL} describe the rows (b m nsample == rows, pool_rows ==
+ * nsample, widths[0] == 3 + cfeat, group_all: m == 1 and nsample == n) and pn2_mlp_train_ws_bytes_ex accepts the shape under that
+ * organisation in both directions (rows a positive multiple of 32 below 2^31, groups of 16 or a multiple of 32 rows, every cout
+ * a multiple of 4, 1..8 layers); _ws_bytes_group_ragged: -1 where it is 0. Before anything is launched: PN2_E_NULL without counts,
+ * mask, group or layers (and the dense entries' NULL checks: out, argsel, ws, layers[l].z ...), PN2_E_ARG where _supported says 0
+ * (and the dense entries' argument checks). backward takes counts for symmetry and does not read it. */
+int pn2_mlp_train_group_ragged_supported(long long rows, int nlayers, const int *widths, int pool_rows, const int *group_dims);
+long long pn2_mlp_train_ws_bytes_group_ragged(long long rows, int nlayers, const int *widths, int pool_rows, int backward,
+                                              const int *group_dims, const pn2_train_opts *opts);
+int pn2_mlp_train_forward_group_ragged(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                       int pool_rows, const int *counts, float *out, int *argsel, void *mask, void *ws,
+                                       const pn2_train_opts *opts, void *stream);
+int pn2_mlp_train_backward_group_ragged(long long rows, int nlayers, const pn2_bn_layer *layers, const pn2_group_src *group,
+                                        int pool_rows, const int *counts, const float *out, const int *argsel,
+                                        const float *grad_out, float *grad_feat_rows, int reproducible, const void *mask,
+                                        void *ws, const pn2_train_opts *opts, void *stream);
+/* ... and what one such call launches on the matrix cores, as pn2_mlp_train_ragged_plan below (records of
+ * PN2_RAGGED_PLAN_FIELDS ints): forward layer 1 is the masked gathered GEMM ([8] AMODE 1 = A_GATHER), backward layer 1 the gathered
+ * masked weight-gradient pass ([3] = 2: tl_wgrad_masked_gather_kernel<TPW, UPW>; shaped by wgrad_shape with gather) and, with
+ * cfeat > 0, the masked A_DZ GEMM onto the cfeat feature columns. The pool and its gradient are vector-unit passes, not listed. */
+int pn2_mlp_train_group_ragged_plan(long long rows, int nlayers, const int *widths, int pool_rows, const int *group_dims,
+                                    const pn2_train_opts *opts, int *passes, int cap);
+
 /* What a ragged training call launches on the matrix cores: host logic, no device work (tests, maintainers). The two entries
  * take the arguments of pn2_mlp_train_ws_bytes_ragged / _ws_bytes_fp_ragged without `backward` and describe BOTH directions of
  * one call that wants every gradient (grad_x; grad_points2 and grad_points1), in launch order: forward layers 1..L, then
@@ -830,9 +876,10 @@ int pn2_mlp_train_backward_fp_ragged(int nlayers, const pn2_bn_layer *layers, co
  * without widths. A record:
  *   [0] kind: 0 = GEMM (tl_gemm_masked_kernel<NS, AMODE> when masked, else tl_gemm_kernel), 1 = weight-gradient pass
  *       (tl_wgrad_masked_kernel<TPW, UPW> when masked, else tl_wgrad_kernel)
- *   [1] 0 forward, 1 backward   [2] layer, 1-based   [3] 1: the masked kernel, 0: the dense one   [4] rows
+ *   [1] 0 forward, 1 backward   [2] layer, 1-based   [3] 1: the masked kernel, 0: the dense one (2: the gathered masked
+ *       weight-gradient pass, pn2_mlp_train_group_ragged_plan only)   [4] rows
  *   [5] K, [6] N: GEMM: contraction and output channels as the shape rule gets them; weight gradient: input and output channels
- *   GEMM:            [7] NS  [8] AMODE (0 A_PLAIN, 2 A_RELU, 3 A_DZ)  [9] 1 resident weights, 0 streamed  [10] column slabs
+ *   GEMM:            [7] NS  [8] AMODE (0 A_PLAIN, 1 A_GATHER, 2 A_RELU, 3 A_DZ)  [9] 1 resident weights, 0 streamed  [10] column slabs
  *                    [11] 1: non-temporal stores (opts.nt, else from 128 MB of output)  [12] grid x  [13] 0
  *   weight gradient: [7] TPW [8] UPW  [9] `two` (two workgroups per CU)  [10] slabs (input slabs x output slabs)
  *                    [11] input tiles per slab  [12] grid x  [13] output tiles per slab

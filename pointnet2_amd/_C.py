@@ -131,6 +131,11 @@ _SIGNATURES = {
     "pn2_mlp_train_backward_fp_ragged": [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "pn2_mlp_train_ragged_plan": [_i, _i, _i, _vp, _vp, _vp, _i],
     "pn2_mlp_train_fp_ragged_plan": [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i],
+    "pn2_mlp_train_group_ragged_supported": [_ll, _i, _vp, _i, _vp],
+    "pn2_mlp_train_ws_bytes_group_ragged": [_ll, _i, _vp, _i, _i, _vp, _vp],
+    "pn2_mlp_train_forward_group_ragged": [_ll, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_mlp_train_backward_group_ragged": [_ll, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "pn2_mlp_train_group_ragged_plan": [_ll, _i, _vp, _i, _vp, _vp, _vp, _i],
     "pn2_farthest_point_sample_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pn2_query_ball_group_xyz_ragged": [_i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
     "pn2_query_ball_group_xyz_msg_ragged": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
@@ -159,6 +164,7 @@ _RESTYPES = {
     "pn2_mlp_train_ws_bytes_frozen": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_ragged": ctypes.c_longlong,
     "pn2_mlp_train_ws_bytes_fp_ragged": ctypes.c_longlong,
+    "pn2_mlp_train_ws_bytes_group_ragged": ctypes.c_longlong,
     "pn2_sample_and_group_status_offset": ctypes.c_longlong,
     "pn2_ball_threshold": ctypes.c_float,
     "pn2_version": ctypes.c_char_p,

@@ -39,7 +39,8 @@
 //     train_mlp_l1.hip     layer 1 of a grouped level on the vector units (tl_l1_*)
 //     train_mlp_small.hip  per-channel finalisations, the top of the stack, the pooling modes
 // train_mlp_device.h is the device code they share; train_mlp_fp / _xyz / _frozen.hip hold the entry points and kernels of
-// one node type each (train_mlp_internal.h); train_mlp_ragged.hip the plain rows of a ragged batch. A kernel that takes a row mask
+// one node type each (train_mlp_internal.h); train_mlp_ragged.hip the plain rows of a ragged batch, train_mlp_ragged_group.hip
+// its grouped rows (the masked gathered passes of layer 1; the pool over the valid rows is train_mlp_small.hip's). A kernel that takes a row mask
 // stands beside its dense twin; here c.mask only selects an ARGUMENT (mask_words(), row_count()), the launch function the kernel.
 #include "train_mlp_kernels.h"    // the parameter structs and launches of the kernels; TlCall, the shape structs (train_mlp_internal.h)
 
@@ -63,6 +64,15 @@ static inline Opts ragged_opts(const pn2_train_opts *o)
 {
     Opts d = opts_of(o);
     d.fuse_wgrad = PN2_OPT_OFF; d.pair_launch = PN2_OPT_OFF; d.side_stream = PN2_OPT_OFF; d.fold_finalize = PN2_OPT_OFF;
+    return d;
+}
+// The GROUPED rows of a ragged batch (TlCall::mask with a group, train_mlp_ragged_group.hip): ragged_opts, and of the grouped
+// node's alternative forms none -- z_L is always kept and pooled by a pass of its own, layer 1 is always the gathered GEMM with
+// the gathered weight-gradient pass: the only forms that have a masked kernel.
+static inline Opts ragged_group_opts(const pn2_train_opts *o)
+{
+    Opts d = ragged_opts(o);
+    d.top_stored = PN2_OPT_ON; d.top_sparse = PN2_OPT_OFF; d.l1_per_point = PN2_OPT_OFF; d.l1_coords = PN2_OPT_OFF;
     return d;
 }
 static inline int pick_ns(int tn, const Opts &o)
@@ -674,7 +684,8 @@ struct TlRun {
     bool fold = false;               // a layer's per-channel finalisation inside the pass that sums for it (TlFin)
 
     explicit TlRun(const TlCall &call)
-        : c(tl_pool_buffers(call)), o(call.mask ? ragged_opts(call.opts) : opts_of(call.opts)), fp(c.has_fp ? &c.fp : nullptr), base(static_cast<char *>(call.ws)),
+        : c(tl_pool_buffers(call)), o(!call.mask ? opts_of(call.opts) : call.group ? ragged_group_opts(call.opts) : ragged_opts(call.opts)),
+          fp(c.has_fp ? &c.fp : nullptr), base(static_cast<char *>(call.ws)),
           st(as_stream(call.stream)) {}
     TlRun(const TlRun &) = delete;
     TlRun &operator=(const TlRun &) = delete;
@@ -691,12 +702,17 @@ struct TlRun {
     {
         if (!layers_ok(c.rows, c.nlayers, c.layers, c.group, widths, fp)) return PN2_E_ARG;
         if (c.frozen && fp) return PN2_E_ARG;                     // (the FP node with layer 1 per known point has no frozen form)
-        if (c.mask && (c.group || c.frozen || c.pool_rows)) return PN2_E_ARG;      // (the row mask: plain rows or the FP node, batch statistics)
+        // the row mask: batch statistics; plain rows or the FP node unpooled, a grouped level with the max pool and no
+        // coordinate gradients (train_mlp_ragged_group.hip)
+        if (c.mask && (c.frozen || (c.group ? (c.pooling != 0 || c.pool_rows <= 0 || c.grad_xyz || c.grad_new_xyz) : c.pool_rows != 0)))
+            return PN2_E_ARG;
         return PN2_OK;
     }
+    bool masked_group() const { return c.mask && c.group; }        // the grouped rows of a ragged batch
     bool pool_buffers_missing(int pool_rows) const
     {
-        return (pool_rows && want_max() && (!c.argsel || !c.zsel)) || (c.pooling == 2 && !c.pool_w);
+        // (the masked pool pass reads z_L itself: no zsel)
+        return (pool_rows && want_max() && (!c.argsel || (!c.zsel && !c.mask))) || (c.pooling == 2 && !c.pool_w);
     }
     bool plan(int pool_rows, int backward)
     {
@@ -839,7 +855,7 @@ struct Fwd : TlRun {
         else { const pn2_bn_layer &D = c.layers[l - 1]; amode = A_RELU; p.A = D.z; p.p0 = D.save + 2 * D.cout; p.p1 = D.save + 3 * D.cout; }
         p.wpacked = at<const u32x4>(pl.pack[l]);
         p.bias = nullptr;                                        // see the comment above the layer loop
-        p.emode = (last && pool_rows && want_max()) ? E_POOL : E_STORE;
+        p.emode = (last && pool_rows && want_max() && !c.mask) ? E_POOL : E_STORE;    // (ragged rows: the pool is a pass of its own)
         p.out = (last && !keep_top) ? nullptr : L.z;              // the pooled top layer of a large level is never written
         p.stats = moments(l);
         p.nostats = c.frozen ? 1 : 0;                             // the GEMM's compile-time "no statistics" variant
@@ -857,6 +873,9 @@ struct Fwd : TlRun {
         if (int rc = launch_gemm(amode, p, g, st, o, &nparts)) return rc;
         if (!fold)
             if (int rc = finalize_moments(l, nparts)) return rc;
+        if (last && pool_rows && c.mask)                          // the grouped rows of a ragged batch: the max over the valid rows of z_L
+            return launch_pool_masked(rows / pool_rows, pool_rows, L.cout, L.z, L.gamma, L.save, mask_words(), out(),
+                                      const_cast<int *>(c.argsel), st);
         // max_and_avg: the max half as pooling 0 computes it, into the workspace behind the plan; the average kernel places it
         float *maxv = pooling == 3 ? at<float>(pl.total) : nullptr;
         if (last && pool_rows && want_max()) {
@@ -882,16 +901,16 @@ struct Fwd : TlRun {
         if ((!c.group && !c.x && !fp) || !c.out || !c.ws || pool_buffers_missing(c.pool_rows)) return PN2_E_NULL;
         if (c.mask && !c.lengths) return PN2_E_NULL;
         if (c.pool_rows && (c.rows % c.pool_rows || (c.group && c.pool_rows != c.group->nsample))) return PN2_E_ARG;
-        if (!plan(c.pool_rows, 0)) return PN2_E_ARG;
+        if (!plan(c.mask ? 0 : c.pool_rows, 0)) return PN2_E_ARG;  // (ragged rows: no partial extrema, tl_group_ragged_ws_bytes)
         per_point = c.group && l1_per_point(c.nlayers, widths, &gd, o);
         // forward: layer 1 on the vector units only WITHOUT features (with the input normals gathered per row the vector kernel
         // measured slower than the gathered GEMM: cls_msg forward 2.51 -> 2.57 ms; its backward counterpart is the one that pays)
         coords_only = c.group && gd.cfeat == 0 && l1_coords_only(c.nlayers, widths, &gd, o);
-        keep_top = c.pooling != 0 || top_stored(c.rows, c.nlayers, widths, c.pool_rows, o);    // a mean needs z_L itself
+        keep_top = c.pooling != 0 || c.mask || top_stored(c.rows, c.nlayers, widths, c.pool_rows, o);    // a mean needs z_L itself, the masked pool too
         for (int l = 0; l < c.nlayers; ++l)
             if (!c.layers[l].z && (keep_top || l < c.nlayers - 1)) return PN2_E_NULL;
         if (c.mask)                                               // ragged rows: lengths -> the validity words and the count
-            if (int rc = launch_ragged_mask(c.rg_b, c.rg_n, c.lengths, c.mask, st)) return rc;
+            if (int rc = launch_ragged_mask(c.rg_b, c.rg_n, c.lengths, c.mask, st, c.rg_unit, c.rg_cap)) return rc;
         if (int rc = pack_weights()) return rc;
         if (c.frozen)                                             // every layer's (m', invstd, a, c) from the running statistics
             if (int rc = frozen_launch_save(c.nlayers, c.layers, st)) return rc;
@@ -923,6 +942,7 @@ struct Bwd : TlRun {
     XyzPlan xp;
     // decided once
     int pool_rows = 0, avg_rows = 0;                    // the max's group size; > 0: the group size of the averaged top layer
+    int mask_rows = 0;                                  // > 0: the group size of the max over the valid rows (ragged grouped rows)
     bool want_xyz = false, want_dx = false, per_point = false, coords_only = false;
     bool ztop = false;                                  // pooled top layer without z_L (tl_top_mats_kernel)
     bool skip[8] = {false, false, false, false, false, false, false, false};
@@ -956,7 +976,11 @@ struct Bwd : TlRun {
         if ((!c.group && !c.x && !fp) || !c.out || !c.grad_out || !c.ws || pool_buffers_missing(c.pool_rows)) return PN2_E_NULL;
         avg_rows = c.pooling ? c.pool_rows : 0;
         if (c.pooling && (!c.group || avg_rows <= 0 || rows % avg_rows || avg_rows != c.group->nsample)) return PN2_E_ARG;
-        pool_rows = c.pooling ? 0 : c.pool_rows;
+        // the grouped rows of a ragged batch: the pooled top layer is an UNPOOLED one too -- its dense gradient comes from
+        // tl_pool_top_grad_masked_kernel and the masked passes of the plain rows run below it
+        mask_rows = masked_group() ? c.pool_rows : 0;
+        if (mask_rows && (rows % mask_rows || mask_rows != c.group->nsample)) return PN2_E_ARG;
+        pool_rows = (c.pooling || mask_rows) ? 0 : c.pool_rows;
         // frozen statistics: a layer whose four gradient slots are all NULL wants no parameter gradient -- no weight-gradient pass,
         // no per-channel sums (batch statistics cannot allow that: dz itself needs the sums)
         for (int l = 0; l < nlayers; ++l) {
@@ -1068,6 +1092,8 @@ struct Bwd : TlRun {
         const int parts = (int)gy;                          // rows of the partial sums = the kernels' gridDim.y
         nparts[nlayers - 1] = parts;
         double *sums = sums_of(nlayers - 1);
+        if (mask_rows)
+            return launch_pool_top_grad_masked(rows, mask_rows, T.cout, c.out, c.grad_out, c.argsel, mask_words(), T.z, gcur, sums, parts, st);
         if (avg_rows)
             return launch_pool_top_grad(rows, avg_rows, T.cout, c.grad_out, T.z, T.save, c.pool_w, c.pooling == 3 ? c.argsel : nullptr, gcur,
                                         sums, parts, st);
@@ -1492,6 +1518,32 @@ long long tl_ragged_ws_bytes(long long rows, int nlayers, const int *widths, int
     return (long long)pl.total;
 }
 
+// The grouped rows of a ragged batch (pn2_mlp_train_*_group_ragged, train_mlp_ragged_group.hip). Supported: the dims describe the
+// rows, and the dense node's plan takes the shape in both directions under ragged_group_opts (hence rows a positive multiple of
+// 32 and groups of 16 or a multiple of 32 rows). The workspace is planned WITHOUT the pool, as both directions run: forward keeps
+// no partial extrema, backward's top layer is an unpooled one.
+bool tl_group_ragged_supported(long long rows, int nlayers, const int *widths, int pool_rows, const int *group_dims)
+{
+    if (!widths || !group_dims || nlayers < 1 || nlayers > 8 || pool_rows <= 0) return false;
+    const GroupDims gd = group_dims_of(group_dims);
+    if (gd.b <= 0 || gd.n <= 0 || gd.m <= 0 || gd.nsample <= 0 || gd.cfeat < 0) return false;
+    if ((long long)gd.b * gd.m * gd.nsample != rows || pool_rows != gd.nsample || widths[0] != 3 + gd.cfeat) return false;
+    if (!gd.has_idx && (gd.m != 1 || gd.nsample != gd.n)) return false;
+    const Opts o = ragged_group_opts(nullptr);
+    TlPlan pl;
+    return tl_plan(rows, nlayers, widths, pool_rows, 0, pl, &gd, o) && tl_plan(rows, nlayers, widths, pool_rows, 1, pl, &gd, o);
+}
+
+long long tl_group_ragged_ws_bytes(long long rows, int nlayers, const int *widths, int pool_rows, int backward, const int *group_dims,
+                                   const pn2_train_opts *opts)
+{
+    if (!tl_group_ragged_supported(rows, nlayers, widths, pool_rows, group_dims)) return -1;
+    const GroupDims gd = group_dims_of(group_dims);
+    TlPlan pl;
+    if (!tl_plan(rows, nlayers, widths, 0, backward, pl, &gd, ragged_group_opts(opts))) return -1;
+    return (long long)pl.total;
+}
+
 // the workspace of the FP level with layer 1 per known point (pn2_mlp_train_ws_bytes_fp, train_mlp_fp.hip); ragged: of its
 // form with a row mask (pn2_mlp_train_ws_bytes_fp_ragged), planned under ragged_opts as its passes run
 long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts, bool ragged)
@@ -1536,12 +1588,14 @@ struct RaggedPlanOut {
         r[7] = g.ns; r[8] = amode; r[9] = g.resident ? 1 : 0; r[10] = g.slabs; r[11] = p.nt; r[12] = (int)grid.x;
     }
     // a weight-gradient pass over `rows` rows, KI input and NO output channels, as launch_wgrad(w, wgrad_shape(...), L, st) shapes it
-    void wgrad(int layer, bool masked, long long rows, int KI, int NO)
+    // (gather: layer 1 of a grouped level, tl_wgrad_masked_gather_kernel -- field [3] is 2 then)
+    void wgrad(int layer, bool masked, long long rows, int KI, int NO, bool gather = false)
     {
-        const WgradShape w = wgrad_shape(rows, KI, NO, false, cus, o.wgrad_two_per_cu);
+        const WgradShape w = wgrad_shape(rows, KI, NO, gather, cus, o.wgrad_two_per_cu);
         int *r = next();
         if (!r) return;
         head(r, 1, 1, layer, masked, rows, KI, NO);
+        if (gather) r[3] = 2;
         r[7] = w.tpw; r[8] = w.upw; r[9] = w.two ? 1 : 0; r[10] = w.uslabs * w.tslabs; r[11] = w.tus; r[12] = (int)w.gridx; r[13] = w.tts;
     }
     // layers lo..L-1 of a direction where they are Fwd / Bwd::generic_layer with the mask (plain rows: from layer 0; FP: from 1)
@@ -1563,6 +1617,22 @@ int tl_ragged_plan(long long rows, int nlayers, const int *widths, const pn2_tra
     RaggedPlanOut po = {passes, cap, 0, ragged_opts(opts), device_cus()};
     po.generic_forward(rows, nlayers, widths, 0);
     po.generic_backward(rows, nlayers, widths, 0);
+    return po.n;
+}
+
+// the grouped rows of a ragged batch, under ragged_group_opts: Fwd::generic_layer(0) is the masked gathered GEMM, the layers above
+// it the plain rows' masked passes; Bwd::generic_layer(0) the masked gathered weight-gradient pass and -- with features -- the
+// masked A_DZ GEMM onto their cfeat columns. The pool and its gradient are vector-unit passes and not listed.
+int tl_group_ragged_plan(long long rows, int nlayers, const int *widths, const int *group_dims, const pn2_train_opts *opts, int *passes,
+                         int cap)
+{
+    const GroupDims gd = group_dims_of(group_dims);
+    RaggedPlanOut po = {passes, cap, 0, ragged_group_opts(opts), device_cus()};
+    po.gemm(0, 0, true, rows, A_GATHER, widths[0], widths[1]);
+    po.generic_forward(rows, nlayers, widths, 1);
+    po.generic_backward(rows, nlayers, widths, 1);
+    po.wgrad(0, true, rows, widths[0], widths[1], true);
+    if (gd.cfeat > 0) po.gemm(1, 0, true, rows, A_DZ, widths[1], gd.cfeat);
     return po.n;
 }
 

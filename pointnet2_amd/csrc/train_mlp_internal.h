@@ -65,9 +65,13 @@ struct TlCall {
     // rg_n = fp.n; train_mlp_fp.hip): row c n + i is valid iff i < clamp(lengths[c], 1, n). `mask` is the
     // caller's buffer (the valid-row count, one validity word per 32 rows): forward writes it from `lengths` before its first
     // pass, backward reads it. nullptr: every row is valid.
+    // The GROUPED rows of a ragged batch (`group` with a mask; train_mlp_ragged_group.hip): rg_n = m nsample rows per cloud of
+    // which the first rg_unit * clamp(lengths[c], 1, rg_cap) are valid -- whole groups (rg_unit = nsample, rg_cap = m: lengths
+    // counts centroids), or the points of a group_all level (rg_unit = 1, rg_cap = n). rg_unit = 0: plain rows.
     void *mask;
     const int *lengths;              // forward only
     int rg_b, rg_n;
+    int rg_unit, rg_cap;
     // forward writes these, backward reads them. Whichever of argsel / zsel / pool_w the pooling mode does not use is
     // ignored, whatever the caller passed (tl_pool_buffers)
     const float *out;
@@ -106,6 +110,12 @@ long long tl_xyz_ws_bytes(long long rows, int nlayers, const int *widths, int po
 long long tl_fp_ws_bytes(const pn2_fp_src *s, int nlayers, const int *widths, int backward, const pn2_train_opts *opts,
                          bool ragged = false);
 long long tl_ragged_ws_bytes(long long rows, int nlayers, const int *widths, int backward, const pn2_train_opts *opts);
+// the grouped rows of a ragged batch (pn2_mlp_train_*_group_ragged, train_mlp_ragged_group.hip), under ragged_group_opts
+bool tl_group_ragged_supported(long long rows, int nlayers, const int *widths, int pool_rows, const int *group_dims);
+long long tl_group_ragged_ws_bytes(long long rows, int nlayers, const int *widths, int pool_rows, int backward, const int *group_dims,
+                                   const pn2_train_opts *opts);
+int tl_group_ragged_plan(long long rows, int nlayers, const int *widths, const int *group_dims, const pn2_train_opts *opts, int *passes,
+                         int cap);
 
 // ---- train_mlp_fp.hip ----
 int fp_launch_pad(const float *src, long long rows_in, int c, long long rows_out, int cp, float *dst, hipStream_t st);

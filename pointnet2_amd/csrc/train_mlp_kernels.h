@@ -233,6 +233,11 @@ int launch_pool_avg(long long groups, int ns, int N, const float *z, const float
 int launch_pool_top_grad(long long rows, int ns, int N, const float *gout, const float *z, const float *save, const float *pool_w,
                          const int *argsel, float *dy, double *stats, int parts, hipStream_t st);
 int launch_identity_coef(int C, float *coef, hipStream_t st);
+// (the grouped rows of a ragged batch: the max pool over the valid rows of the stored z_L, and the dense dy_L it routes back)
+int launch_pool_masked(long long groups, int ns, int N, const float *z, const float *gamma, const float *save, const unsigned *mask,
+                       float *out, int *argsel, hipStream_t st);
+int launch_pool_top_grad_masked(long long rows, int ns, int N, const float *out, const float *gout, const int *argsel,
+                                const unsigned *mask, const float *z, float *dy, double *stats, int parts, hipStream_t st);
 
 // ---- train_mlp_ragged.hip: plain rows of a ragged batch (pn2_mlp_train_*_ragged) ----
 // The caller's mask buffer: the number of valid rows as a double, then one validity word per 32 rows
@@ -242,8 +247,13 @@ inline const unsigned *ragged_words(const void *mask)
 {
     return reinterpret_cast<const unsigned *>(static_cast<const char *>(mask) + kRaggedWordsOff);
 }
-int launch_ragged_mask(int b, int n, const int *lengths, void *mask, hipStream_t st);
+// (b clouds of n rows, the first unit * clamp(lengths[c], 1, cap) of each valid; unit = 0: plain rows, unit 1 and cap n)
+int launch_ragged_mask(int b, int n, const int *lengths, void *mask, hipStream_t st, int unit = 0, int cap = 0);
 int launch_masked_gemm(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st);
 int launch_masked_wgrad(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st);
+
+// ---- train_mlp_ragged_group.hip: the grouped rows of a ragged batch (pn2_mlp_train_*_group_ragged): layer 1's gathered passes ----
+int launch_masked_gather_gemm(const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st);
+int launch_masked_gather_wgrad(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st);
 
 }  // namespace pn2

@@ -12,12 +12,13 @@
 // The row count of the two finalisations is the number of valid rows, read from device memory (tl_bn_*finalize_counted_kernel).
 //
 // What is here: the kernel that turns `lengths` into one validity word per 32 rows and the count; the MASKED instantiations of
-// the GEMM body (A_PLAIN / A_RELU / A_DZ) and of the weight-gradient body (dense rows, D_DZ) -- kernels of their own, the dense
-// ones are not touched, launch_gemm / launch_wgrad come here when the call has a mask; the entry points. The small masked and
+// the GEMM body (A_PLAIN / A_RELU / A_DZ; the kernel template: train_mlp_masked.h) and of the weight-gradient body (dense rows,
+// D_DZ) -- kernels of their own, the dense ones are not touched, launch_gemm / launch_wgrad come here when the call has a mask
+// (and go on to train_mlp_ragged_group.hip for the gathered layer 1 of a grouped level); the entry points. The small masked and
 // counted kernels stand beside their dense twins (train_mlp_small.hip: the apply, the finalisations; train_mlp_fp.hip: the FP
 // node's layer-1 passes) behind ONE launch function per pair. The host side is train_mlp.hip's, under one fixed organisation
 // (ragged_opts there): a data-gradient GEMM and a weight-gradient pass per layer, finalisations as launches of their own.
-#include "train_mlp_device.h"
+#include "train_mlp_masked.h"
 
 #include <type_traits>
 
@@ -26,20 +27,23 @@ namespace pn2 {
 __device__ __forceinline__ int rg_clamp(int len, int n) { return len < 1 ? 1 : len > n ? n : len; }
 
 // one thread per validity word (32 rows, which may hold the tail of one cloud, its padding and the head of the next);
-// block 0 also sums the clamped lengths -- integers: the count does not depend on the order
-__global__ __launch_bounds__(256) void tl_ragged_mask_kernel(int b, int n, const int *__restrict__ lengths, double *__restrict__ count,
-                                                             unsigned *__restrict__ words, long long nwords)
+// block 0 also sums the clamped lengths -- integers: the count does not depend on the order.
+// A cloud is n rows of which the first unit * clamp(lengths[c], 1, cap) are valid: unit 1 and cap n on plain rows and in a
+// group_all level (lengths = points per cloud), unit nsample and cap m on the n = m nsample grouped rows of a cloud (lengths =
+// centroids per cloud; train_mlp_ragged_group.hip)
+__global__ __launch_bounds__(256) void tl_ragged_mask_kernel(int b, int n, int unit, int cap, const int *__restrict__ lengths,
+                                                             double *__restrict__ count, unsigned *__restrict__ words, long long nwords)
 {
     for (long long w = (long long)blockIdx.x * 256 + threadIdx.x; w < nwords; w += (long long)gridDim.x * 256) {
         const long long r0 = w * 32;
         int c = (int)(r0 / n), i = (int)(r0 - (long long)c * n);
-        int len = rg_clamp(lengths[c], n);
+        int len = unit * rg_clamp(lengths[c], cap);
         unsigned m = 0u;
         for (int j = 0; j < 32; ++j) {
             if (i >= n) {
                 i = 0;
                 ++c;
-                len = c < b ? rg_clamp(lengths[c], n) : 0;
+                len = c < b ? unit * rg_clamp(lengths[c], cap) : 0;
             }
             m |= (i < len ? 1u : 0u) << j;
             ++i;
@@ -49,7 +53,7 @@ __global__ __launch_bounds__(256) void tl_ragged_mask_kernel(int b, int n, const
     if (blockIdx.x != 0) return;
     __shared__ long long sh[256];
     long long s = 0;
-    for (int c = threadIdx.x; c < b; c += 256) s += rg_clamp(lengths[c], n);
+    for (int c = threadIdx.x; c < b; c += 256) s += (long long)unit * rg_clamp(lengths[c], cap);
     sh[threadIdx.x] = s;
     __syncthreads();
     for (int k = 128; k > 0; k >>= 1) {
@@ -59,32 +63,18 @@ __global__ __launch_bounds__(256) void tl_ragged_mask_kernel(int b, int n, const
     if (threadIdx.x == 0) *count = (double)sh[0];
 }
 
-int launch_ragged_mask(int b, int n, const int *lengths, void *mask, hipStream_t st)
+int launch_ragged_mask(int b, int n, const int *lengths, void *mask, hipStream_t st, int unit, int cap)
 {
+    if (unit <= 0 || cap <= 0) { unit = 1; cap = n; }              // plain rows
     const long long nwords = (long long)b * n / 32;
     long long blocks = (nwords + 255) / 256;
     if (blocks > 1024) blocks = 1024;
-    return launch(tl_ragged_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b, n, lengths, const_cast<double *>(ragged_count(mask)),
+    return launch(tl_ragged_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, st, b, n, unit, cap, lengths,
+                  const_cast<double *>(ragged_count(mask)),
                   const_cast<unsigned *>(ragged_words(mask)), nwords);
 }
 
-// ---- the GEMM pass with the row mask (tl_gemm_body.inc, PN2_MASKED) ----
-template <int NS, int AMODE>
-__global__ __launch_bounds__(kTlThreads) void tl_gemm_masked_kernel(const TlGemm p)
-{
-#define PN2_BX blockIdx.x
-#define PN2_BY blockIdx.y
-#define PN2_GX gridDim.x
-#define PN2_STATS true
-#define PN2_MASKED true
-#include "tl_gemm_body.inc"
-#undef PN2_BX
-#undef PN2_BY
-#undef PN2_GX
-#undef PN2_STATS
-#undef PN2_MASKED
-}
-
+// ---- the GEMM pass with the row mask (tl_gemm_masked_kernel: train_mlp_masked.h) ----
 template <int NS>
 static int launch_masked_gemm_ns(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st)
 {
@@ -106,6 +96,7 @@ static int launch_masked_gemm_ns(int amode, const TlGemm &p, const GemmShape &g,
 int launch_masked_gemm(int amode, const TlGemm &p, const GemmShape &g, dim3 grid, hipStream_t st)
 {
     if (!p.mask || p.nostats || p.fin.ticket) return PN2_E_ARG;    // (no frozen form, no folded finalisation: its count is a value)
+    if (amode == A_GATHER) return launch_masked_gather_gemm(p, g, grid, st);       // layer 1 of a grouped level (train_mlp_ragged_group.hip)
     if (g.ns == 4) return launch_masked_gemm_ns<4>(amode, p, g, grid, st);
     if (g.ns == 2) return launch_masked_gemm_ns<2>(amode, p, g, grid, st);
     return launch_masked_gemm_ns<1>(amode, p, g, grid, st);
@@ -144,7 +135,9 @@ static int launch_masked_wgrad_tpw(const TlWgrad &p, const WgradShape &w, dim3 g
 
 int launch_masked_wgrad(const TlWgrad &p, const WgradShape &w, dim3 grid, hipStream_t st)
 {
-    if (!p.mask || p.dy_w || p.dmode != A_DZ || (p.amode != A_PLAIN && p.amode != A_RELU)) return PN2_E_ARG;
+    if (!p.mask || p.dy_w || p.dmode != A_DZ) return PN2_E_ARG;
+    if (p.amode == A_GATHER) return launch_masked_gather_wgrad(p, w, grid, st);     // layer 1 of a grouped level (train_mlp_ragged_group.hip)
+    if (p.amode != A_PLAIN && p.amode != A_RELU) return PN2_E_ARG;
     return w.tpw == 1 ? launch_masked_wgrad_tpw<1>(p, w, grid, st) : w.tpw == 2 ? launch_masked_wgrad_tpw<2>(p, w, grid, st)
                                                                                  : launch_masked_wgrad_tpw<4>(p, w, grid, st);
 }

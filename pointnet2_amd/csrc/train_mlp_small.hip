@@ -106,6 +106,51 @@ __global__ void tl_pool_finalize_kernel(long long groups, int N, int parts, int 
     }
 }
 
+// ... on the grouped rows of a ragged batch (train_mlp_ragged_group.hip): the pool as a pass of its own over the STORED z_L,
+// behind its finalisation. Per group and channel the extremum of z over the VALID rows (the dense rule: the max where
+// gamma >= 0, else the min; the first occurrence), then out = relu(a z_sel + c). The valid rows of a group are a prefix of it,
+// so a group whose first row is a padding row is a padding group: out = +0.0, argsel = 0. A thread owns four channels of a group.
+__global__ __launch_bounds__(256) void tl_pool_masked_kernel(long long groups, int ns, int N, const float *__restrict__ z,
+                                                             const float *__restrict__ gamma, const float *__restrict__ save,
+                                                             const unsigned *__restrict__ mask, float *__restrict__ out,
+                                                             int *__restrict__ argsel)
+{
+    const int n4 = N / 4;
+    const long long total = groups * n4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long g = i / n4;
+        const int c = (int)(i - g * n4) * 4;
+        const float4 a = ld4(save + 2 * N + c), cc = ld4(save + 3 * N + c);
+        const bool up[4] = {gamma[c] >= 0.0f, gamma[c + 1] >= 0.0f, gamma[c + 2] >= 0.0f, gamma[c + 3] >= 0.0f};
+        const long long row0 = g * ns;
+        const float *zr = z + (size_t)row0 * N + c;
+        const bool any = (mask[row0 >> 5] >> (unsigned)(row0 & 31)) & 1u;
+        const float4 first = ld4(zr);
+        float best[4] = {first.x, first.y, first.z, first.w};
+        int arg[4] = {0, 0, 0, 0};
+#pragma unroll 4
+        for (int k = 1; k < ns; ++k) {
+            const long long r = row0 + k;
+            const bool rv = (mask[r >> 5] >> (unsigned)(r & 31)) & 1u;
+            const float4 t = ld4(zr + (size_t)k * N);
+            const float v[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool take = rv && (up[j] ? v[j] > best[j] : v[j] < best[j]);
+                best[j] = take ? v[j] : best[j];
+                arg[j] = take ? k : arg[j];
+            }
+        }
+        float4 o;
+        o.x = any ? vmax(__fadd_rn(__fmul_rn(a.x, best[0]), cc.x), 0.0f) : 0.0f;
+        o.y = any ? vmax(__fadd_rn(__fmul_rn(a.y, best[1]), cc.y), 0.0f) : 0.0f;
+        o.z = any ? vmax(__fadd_rn(__fmul_rn(a.z, best[2]), cc.z), 0.0f) : 0.0f;
+        o.w = any ? vmax(__fadd_rn(__fmul_rn(a.w, best[3]), cc.w), 0.0f) : 0.0f;
+        *reinterpret_cast<float4 *>(out + g * N + c) = o;
+        *reinterpret_cast<int4 *>(argsel + g * N + c) = make_int4(any ? arg[0] : 0, any ? arg[1] : 0, any ? arg[2] : 0, any ? arg[3] : 0);
+    }
+}
+
 // pooled top layer: gq = grad_out . [out > 0]; sums of dy and dy z over all rows = over the selected entries
 __global__ __launch_bounds__(256) void tl_pool_grad_kernel(long long groups, int N, const float *__restrict__ out,
                                                            const float *__restrict__ gout, const float *__restrict__ zsel,
@@ -386,6 +431,53 @@ __global__ __launch_bounds__(256) void tl_pool_top_grad_kernel(long long rows, i
     }
 }
 
+// ... of the max pool over the valid rows of a ragged batch's grouped rows (tl_pool_masked_kernel; same grid, same `stats`
+// layout): the DENSE dy_L[row, c] = (row valid && k == argsel[g, c] && out[g, c] > 0) ? grad_out[g, c] : +0.0 -- selects: the
+// grad_out rows of padding groups may hold anything -- and its two column sums. From here on the stack is an unpooled one.
+__global__ __launch_bounds__(256) void tl_pool_top_grad_masked_kernel(long long rows, int ns, int N, const float *__restrict__ out,
+                                                                      const float *__restrict__ gout, const int *__restrict__ argsel,
+                                                                      const unsigned *__restrict__ mask, const float *__restrict__ z,
+                                                                      float *__restrict__ dy, double *__restrict__ stats)
+{
+    const int c = (blockIdx.x * 16 + (threadIdx.x & 15)) * 4;
+    const int ry = threadIdx.x >> 4;
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+    if (c < N) {
+        const long long rstep = (long long)gridDim.y * 16;
+#pragma unroll 2
+        for (long long r = (long long)blockIdx.y * 16 + ry; r < rows; r += rstep) {
+            const unsigned g = (unsigned)r / (unsigned)ns, k = (unsigned)r - g * (unsigned)ns;
+            const bool rv = (mask[r >> 5] >> (unsigned)(r & 31)) & 1u;
+            const size_t go = (size_t)g * N + c;
+            const float4 o = ld4(out + go), ga = ld4(gout + go), zz = ld4(z + (size_t)r * N + c);
+            const int4 s = *reinterpret_cast<const int4 *>(argsel + go);
+            const bool on[4] = {rv && (unsigned)s.x == k && o.x > 0.0f, rv && (unsigned)s.y == k && o.y > 0.0f,
+                                rv && (unsigned)s.z == k && o.z > 0.0f, rv && (unsigned)s.w == k && o.w > 0.0f};
+            const float4 q = make_float4(on[0] ? ga.x : 0.0f, on[1] ? ga.y : 0.0f, on[2] ? ga.z : 0.0f, on[3] ? ga.w : 0.0f);
+            *reinterpret_cast<float4 *>(dy + (size_t)r * N + c) = q;
+            const float zv[4] = {zz.x, zz.y, zz.z, zz.w}, qv[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                s1[j] += (double)qv[j];
+                s2[j] += on[j] ? (double)qv[j] * (double)zv[j] : 0.0;
+            }
+        }
+    }
+    __shared__ double sh[2][16][64];
+    const int x0 = (threadIdx.x & 15) * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { sh[0][ry][x0 + j] = s1[j]; sh[1][ry][x0 + j] = s2[j]; }
+    __syncthreads();
+    const int x = threadIdx.x, col = blockIdx.x * 64 + x;
+    if (stats && x < 64 && col < N) {
+        double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { t1 += sh[0][i][x]; t2 += sh[1][i][x]; }
+        stats[((size_t)blockIdx.y * 2) * N + col] = t1;
+        stats[((size_t)blockIdx.y * 2 + 1) * N + col] = t2;
+    }
+}
+
 __global__ void tl_identity_coef_kernel(int C, float *__restrict__ coef)       // dz = 1 * g - 0 - 0 * z
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -467,6 +559,21 @@ int launch_pool_top_grad(long long rows, int ns, int N, const float *gout, const
 {
     return launch(tl_pool_top_grad_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)parts), dim3(256), 0, st, rows, ns, N, gout, z, save,
                   pool_w, argsel, dy, stats);
+}
+
+int launch_pool_masked(long long groups, int ns, int N, const float *z, const float *gamma, const float *save, const unsigned *mask,
+                       float *out, int *argsel, hipStream_t st)
+{
+    long long blocks = (groups * (N / 4) + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    return launch(tl_pool_masked_kernel, dim3((unsigned)blocks), dim3(256), 0, st, groups, ns, N, z, gamma, save, mask, out, argsel);
+}
+
+int launch_pool_top_grad_masked(long long rows, int ns, int N, const float *out, const float *gout, const int *argsel,
+                                const unsigned *mask, const float *z, float *dy, double *stats, int parts, hipStream_t st)
+{
+    return launch(tl_pool_top_grad_masked_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)parts), dim3(256), 0, st, rows, ns, N, out,
+                  gout, argsel, mask, z, dy, stats);
 }
 
 int launch_identity_coef(int C, float *coef, hipStream_t st)

@@ -184,6 +184,41 @@ def _train_mode(mod, stacks, pooling, group_all, xyz, points):
     return "fused_frozen" if _frozen_ok(mod, stacks, pooling, group_all, xyz, points) else None
 
 
+def _ragged_train_ok(mod, stacks, group_all, xyz, points):
+    """fused_ragged_train (opt-in): can the masked fused training node (train_mlp.sa_mlp_train(..., counts=)) run this module's
+    stacks on the grouped rows of a ragged batch? Max pooling without mlp2 is the caller's to check; xyz must need no gradient
+    (the node has no coordinate gradients). stacks: [(net, nsample)], as _train_fused_ok."""
+    if not mod.fused_ragged_train or not mod.fused_mlp or not mod.training or not xyz.is_cuda:
+        return False
+    if (torch.is_grad_enabled() and xyz.requires_grad) or (points is not None and not mod.use_xyz):
+        return False
+    b, n, _ = xyz.shape
+    m = 1 if group_all else mod.npoint
+    cfeat = points.shape[2] if points is not None else 0
+    return all(train_mlp.group_ragged_supported(net, b, n, m, ns, cfeat, not group_all) for net, ns in stacks)
+
+
+def _masked_pool(x, valid, dists, pooling):
+    """pointnet_sa_module's pooling (:128-142) of x (b, C, m, k) over the VALID entries of its last axis: valid (b, k) bool,
+    dists (b, m, k, 1) the grouped points' distances from the centroid (weighted_avg). Selects, not products: an entry that is
+    not valid may hold anything. No host synchronisation."""
+    b, k = valid.shape
+    v = valid.view(b, 1, 1, k)
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    cnt = valid.sum(dim=1).clamp(min=1).to(x.dtype).view(b, 1, 1, 1)
+    if pooling == "max":
+        return torch.where(v, x, torch.full((), float("-inf"), dtype=x.dtype, device=x.device)).max(dim=3, keepdim=True)[0]
+    if pooling == "avg":
+        return torch.where(v, x, zero).sum(dim=3, keepdim=True) / cnt
+    if pooling == "weighted_avg":                                     # :130-136
+        w = torch.where(valid.view(b, 1, k, 1), torch.exp(-dists * 5), zero)
+        w = (w / w.sum(dim=2, keepdim=True)).permute(0, 3, 1, 2)
+        return (torch.where(v, x, zero) * w).sum(dim=3, keepdim=True)
+    if pooling == "max_and_avg":                                      # :137-140: concat([avg, max])
+        return torch.cat([_masked_pool(x, valid, dists, "avg"), _masked_pool(x, valid, dists, "max")], dim=1)
+    raise ValueError("unknown pooling %r" % (pooling,))
+
+
 def _valid_rows(counts, b, m, dev, name="npoints"):
     """(b, m) bool: row j of cloud c is below counts[c] (clamped into 1..m, as the kernels clamp it). No host synchronisation."""
     cnts = ragged_lengths(counts, b, dev, name).clamp(1, max(m, 1))
@@ -267,6 +302,15 @@ class PointnetSAModule(nn.Module):
         # frozen): take the fused node with frozen statistics (train_mlp.sa_mlp_train(..., frozen=True)) instead of the
         # layer-by-layer path; last_path "fused_frozen". Opt-in.
         self.fused_frozen_bn = False
+        # training with npoints= (per-cloud sample counts; _forward_counts) -- and, on a group_all level with ragged_group_all,
+        # with lengths=: take the fused node with a row mask (train_mlp.sa_mlp_train(..., counts=)) instead of compacting the
+        # valid rows and running the stack layer by layer: no nonzero(), no host synchronisation; last_path
+        # "fused_train_ragged". Max pooling without mlp2, an xyz that needs no gradient, a stack group_ragged_supported
+        # covers; anything else keeps the compacting path. Opt-in (the name is the FP module's).
+        self.fused_ragged_train = False
+        # a group_all level accepts lengths= (per-cloud point counts; _forward_all_ragged): the group is the cloud's VALID rows.
+        # Without it group_all refuses lengths. Opt-in.
+        self.ragged_group_all = False
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
@@ -339,7 +383,7 @@ class PointnetSAModule(nn.Module):
         slice's geometry, rows from it on hold the operators' fills -- sample 0 as the centroid, a group of nsample times
         point 0. The caller hands npoints to the next level as its lengths."""
         if self.group_all:
-            if lengths is not None or npoints is not None:
+            if npoints is not None or (lengths is not None and not self.ragged_group_all):
                 raise ValueError("group_all with lengths: the group would contain the padding rows")
             return None
         if lengths is not None:
@@ -401,6 +445,51 @@ class PointnetSAModule(nn.Module):
             out = sa_mlp.sa_mlp_maxpool(xyz, None, points, None, self._packed(xyz.device, xyz.shape[1]))
         return new_xyz, self._post(out), idx
 
+    def _forward_all_ragged(self, xyz, points, lengths):
+        """A group_all level with per-cloud point counts (ragged_group_all): the group of cloud c is its lengths[c] valid rows;
+        the output rows (b, 1, C) are all valid. Rows beyond a length may hold anything.
+        eval(): the layer stack on every row -- eval batch norm is row-wise -- and the pooling over the valid rows only
+        (_masked_pool); no host synchronisation, last_path "unfused".
+        train(): with fused_ragged_train and support (_ragged_train_ok; max pooling, no mlp2) the fused node with a row mask,
+        counts = lengths: no synchronisation, last_path "fused_train_ragged". Otherwise the valid rows of all clouds are compacted
+        to (1, C, total, 1), the stack runs on them in train mode (batch statistics over the valid rows) and each cloud's slice
+        is pooled (every pooling mode); plain PyTorch, synchronises, last_path "unfused_ragged"."""
+        b, n, _ = xyz.shape
+        lengths = ragged_lengths(lengths, b, xyz.device)
+        valid = _valid_rows(lengths, b, n, xyz.device, "lengths")               # (b, n)
+        new_xyz, idx = _all_in_one_group(xyz)
+        if self.training and self.pooling == "max" and self.mlp2 is None and \
+                _ragged_train_ok(self, [(self.mlp.net, n)], True, xyz, points):
+            self.last_path = "fused_train_ragged"
+            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, None, points, None, True, counts=lengths)
+            return new_xyz, out, idx
+        _, new_points, _, grouped_xyz = sample_and_group_all(xyz, points, self.use_xyz)    # (b, 1, n, C), (b, 1, n, 3)
+        # (zeros on the padding rows before anything is computed from them: a NaN there would otherwise reach the weights'
+        # gradients as NaN times a zero output gradient)
+        keep = valid.view(b, 1, n, 1)
+        zero = torch.zeros((), dtype=xyz.dtype, device=xyz.device)
+        new_points, grouped_xyz = torch.where(keep, new_points, zero), torch.where(keep, grouped_xyz, zero)
+        dists = grouped_xyz.norm(dim=-1, keepdim=True)
+        if not self.training:
+            self.last_path = "unfused"
+            x = _masked_pool(self.mlp(new_points.permute(0, 3, 1, 2)), valid, dists, self.pooling)
+        else:
+            self.last_path = "unfused_ragged"
+            rows = valid.reshape(-1).nonzero().squeeze(1)                       # (total,): synchronises
+            c = new_points.shape[3]
+            pv = new_points.reshape(b * n, c).index_select(0, rows)             # (total, C)
+            y = self.mlp(pv.t().reshape(1, c, -1, 1))                            # statistics over the valid rows of all clouds
+            dv = dists.reshape(b * n, 1).index_select(0, rows)
+            outs, start = [], 0
+            for k in lengths.clamp(1, n).tolist():                              # each cloud's slice of the compacted rows
+                every = torch.ones((1, k), dtype=torch.bool, device=xyz.device)
+                outs.append(_masked_pool(y[:, :, start:start + k, 0].unsqueeze(2), every, dv[start:start + k].view(1, 1, k, 1), self.pooling))
+                start += k
+            x = torch.cat(outs, dim=0)                                          # (b, C', 1, 1)
+        if self.mlp2 is not None:
+            x = self.mlp2(x)
+        return new_xyz, x.squeeze(3).permute(0, 2, 1).contiguous(), idx
+
     def _forward_counts(self, xyz, points, g, npoints):
         """forward() with per-cloud sample counts on the geometry g (geometry(npoints=)): cloud c has npoints[c] valid
         centroids; output rows from the count on are exact zeros. eval(): the existing stack paths on all npoint rows -- the
@@ -416,6 +505,14 @@ class PointnetSAModule(nn.Module):
             fused = mode is None and self._fused_ok(xyz, points)
             new_xyz, out, idx = self._forward_on(xyz, points, g, mode or ("fused" if fused else "unfused"))
             return new_xyz, _zero_padding_rows(out, valid), idx
+        if self.pooling == "max" and self.mlp2 is None and _ragged_train_ok(self, [(self.mlp.net, g.idx.shape[2])], False, xyz, points):
+            # fused_ragged_train: ONE autograd node on the geometry as it stands -- the padding centroids' groups stay where they
+            # are (nsample copies of point 0) and a row mask keeps them out of every statistic and gradient
+            self.last_path = "fused_train_ragged"
+            new_xyz = g.new_xyz_for(xyz)
+            out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, g.idx, True, plan=getattr(g, "plan", None),
+                                            counts=npoints)
+            return new_xyz, out, g.idx
         self.last_path = "unfused_ragged"
         new_xyz, idx, plan = g.new_xyz_for(xyz), g.idx, getattr(g, "plan", None)
         grouped_xyz = group_point(xyz, idx, plan=plan) - new_xyz.unsqueeze(2)   # :45-46
@@ -442,11 +539,15 @@ class PointnetSAModule(nn.Module):
         lengths: (b,) per-cloud point counts of a ragged batch (cloud i is xyz[i, :lengths[i]], points[i, :lengths[i]]): idx
         names valid rows only, so rows beyond a length are never gathered -- they must be finite (coordinates too when the
         module trains: a training node may run its first layer once per point, padding rows included, and a NaN times a zero
-        gradient is a NaN), they influence no output and no gradient, and their own gradients are exactly zero. Not for group_all levels (ValueError).
+        gradient is a NaN), they influence no output and no gradient, and their own gradients are exactly zero. Not for group_all
+        levels (ValueError) unless ragged_group_all is set (_forward_all_ragged: the group is the cloud's valid rows, which
+        may then hold anything beyond a length).
         npoints: (b,) per-cloud sample counts, with or without lengths (_forward_counts; a geometry= must come from
         geometry(npoints=)): new_points rows from npoints[c] on are exact zeros; hand npoints to the next level as its lengths."""
         if (lengths is not None or npoints is not None) and self.group_all:
-            raise ValueError("group_all with lengths: the group would contain the padding rows")
+            if npoints is not None or not self.ragged_group_all:
+                raise ValueError("group_all with lengths: the group would contain the padding rows")
+            return self._forward_all_ragged(xyz, points, lengths)
         if npoints is not None:
             g = geometry.wait() if geometry is not None else self.geometry(xyz, lengths=lengths, npoints=npoints)
             return self._forward_counts(xyz, points, g, npoints)
@@ -529,6 +630,9 @@ class PointnetSAModuleMSG(nn.Module):
         # each cloud staged and binned once) instead of one ragged ball query per radius -- same bits. Opt-in; measured in
         # profiles/ragged_msg/README.md.
         self.ragged_one_launch = False
+        # training with npoints=: one fused node with a row mask per scale instead of the compacting layer-by-layer path; see
+        # PointnetSAModule.fused_ragged_train. last_path "fused_train_ragged". Opt-in.
+        self.fused_ragged_train = False
         self.last_path = None
         self._pack_cache = {}
 
@@ -667,6 +771,14 @@ class PointnetSAModuleMSG(nn.Module):
         if not self.training:
             new_xyz, out = self._forward_on_geometry(xyz, points, g)
             return new_xyz, _zero_padding_rows(out, valid)
+        if _ragged_train_ok(self, [(mlp.net, idx.shape[2]) for mlp, idx in zip(self.mlps, g.idx)], False, xyz, points):
+            # fused_ragged_train: one masked node per scale on the geometry as it stands; channel order features FIRST (:184)
+            self.last_path = "fused_train_ragged"
+            new_xyz = g.new_xyz_for(xyz)
+            plans = getattr(g, "plan", None) or [None] * len(g.idx)
+            outs = [train_mlp.sa_mlp_train(mlp.net, xyz, new_xyz, points, idx, False, plan=plan, counts=npoints)[0]
+                    for mlp, idx, plan in zip(self.mlps, g.idx, plans)]
+            return new_xyz, torch.cat(outs, dim=2)
         self.last_path = "unfused_ragged"
         new_xyz = g.new_xyz_for(xyz)
         rows = valid.reshape(-1).nonzero().squeeze(1)                           # (total,): synchronises

@@ -206,6 +206,17 @@ def frozen_supported(net, rows, pool_rows=0, grouped=True, pooling="max", xyz_di
                                                         1 if xyz_dims is not None else 0))
 
 
+def group_ragged_supported(net, b, n, m, nsample, cfeat, has_idx=True):
+    """Can the fused training node run this stack on the GROUPED rows of a ragged batch -- sa_mlp_train(..., counts=): b clouds
+    of n points, m groups of nsample rows (has_idx=False: the group_all level, m = 1 and nsample = n), cfeat feature channels,
+    max pooling, batch statistics over the valid rows only? Mirrors pn2_mlp_train_group_ragged_supported."""
+    if min(b, n, m, nsample) <= 0 or cfeat < 0 or not stack_supported(net, b * m * nsample, nsample, True):
+        return False
+    widths = _stack_widths(conv_bn_pairs(net))
+    gdims = (ctypes.c_int * 6)(b, n, m, nsample, cfeat, 1 if has_idx else 0)
+    return bool(_C.lib().pn2_mlp_train_group_ragged_supported(b * m * nsample, len(widths) - 1, _widths_array(widths), nsample, gdims))
+
+
 def ragged_supported(net, b, n):
     """Can the fused training node run this stack on the plain rows of a RAGGED batch -- b clouds padded to n rows, batch
     statistics over the valid rows only (fp_mlp_train(..., lengths=), pn2_mlp_train_*_ragged)? Mirrors
@@ -217,7 +228,7 @@ def ragged_supported(net, b, n):
 
 
 _PLAN_FIELDS = 14                    # PN2_RAGGED_PLAN_FIELDS
-_PLAN_AMODES = {0: "A_PLAIN", 2: "A_RELU", 3: "A_DZ"}
+_PLAN_AMODES = {0: "A_PLAIN", 1: "A_GATHER", 2: "A_RELU", 3: "A_DZ"}
 
 
 def ragged_plan(b, n, widths, fp=None):
@@ -229,6 +240,21 @@ def ragged_plan(b, n, widths, fp=None):
     warr, opts = _widths_array(widths), _opts()
     head = (b, n) + (tuple(fp) if fp is not None else ()) + (len(widths) - 1, warr, opts)
     fn = _C.lib().pn2_mlp_train_fp_ragged_plan if fp is not None else _C.lib().pn2_mlp_train_ragged_plan
+    return _plan_passes(fn, head)
+
+
+def group_ragged_plan(b, n, m, nsample, cfeat, widths, has_idx=True):
+    """ragged_plan for the GROUPED rows of a ragged batch (sa_mlp_train(..., counts=), pn2_mlp_train_group_ragged_plan): b clouds
+    of n points, m groups of nsample rows each (has_idx=False: group_all, m = 1 and nsample = n), cfeat feature channels;
+    widths: 3 + cfeat, cout_1 .. cout_L. The same dicts; forward layer 1 has amode "A_GATHER", backward layer 1's weight
+    gradient `gather` True (on every other weight gradient it is False). The pool and its gradient are not listed."""
+    gdims = (ctypes.c_int * 6)(b, n, m, nsample, cfeat, 1 if has_idx else 0)
+    head = (b * m * nsample, len(widths) - 1, _widths_array(widths), nsample, gdims, _opts())
+    return _plan_passes(_C.lib().pn2_mlp_train_group_ragged_plan, head)
+
+
+def _plan_passes(fn, head):
+    """The records of a plan entry fn(*head, passes, cap) as dicts."""
     count = fn(*head, None, 0)
     require(count >= 0, "ragged_plan: unsupported shape (%s)" % _C.PN2_ERRORS.get(count, count))
     buf = (ctypes.c_int * (count * _PLAN_FIELDS))()
@@ -238,7 +264,7 @@ def ragged_plan(b, n, widths, fp=None):
         r = buf[i * _PLAN_FIELDS:(i + 1) * _PLAN_FIELDS]
         p = dict(kind="wgrad" if r[0] else "gemm", backward=bool(r[1]), layer=r[2], masked=bool(r[3]), rows=r[4], K=r[5], N=r[6])
         if r[0]:
-            p.update(tpw=r[7], upw=r[8], two=bool(r[9]), slabs=r[10], tus=r[11], grid=r[12], tts=r[13])
+            p.update(tpw=r[7], upw=r[8], two=bool(r[9]), slabs=r[10], tus=r[11], grid=r[12], tts=r[13], gather=r[3] == 2)
         else:
             p.update(ns=r[7], amode=_PLAN_AMODES[r[8]], resident=bool(r[9]), slabs=r[10], nt=bool(r[11]), grid=r[12])
         passes.append(p)
@@ -298,6 +324,9 @@ def _workspace(query_name, dev, error_text, *args):
 
 def _level_workspace(level, widths, code, backward, dev, gdims, opts, want_xyz=False, ragged=False):
     """... of an SA / plain-rows node: the query that belongs to the level's mode."""
+    if ragged and level.grouped:
+        return _workspace("pn2_mlp_train_ws_bytes_group_ragged", dev, "pn2_mlp_train_group_ragged: unsupported level",
+                          level.rows, len(widths) - 1, _widths_array(widths), level.pool_rows, backward, gdims, opts)
     if ragged:
         return _workspace("pn2_mlp_train_ws_bytes_ragged", dev, "pn2_mlp_train_ragged: unsupported stack (b n % 32, widths % 4)",
                           level.b, level.n, len(widths) - 1, _widths_array(widths), backward, opts)
@@ -515,7 +544,8 @@ def _saved_layers(ctx, n):
 class _TrainMLP(torch.autograd.Function):
     """inputs: level, x (points (b,n,c) when grouped -- may be None -- else the (rows, cin) input), xyz and new_xyz (the
     level's own tensors when their gradients are wanted, level.xyz_grad; else None: the coordinates are constants of the node),
-    lengths ((b,) i32 on the device: the plain rows of a RAGGED batch, pn2_mlp_train_*_ragged; else None), then per layer
+    lengths ((b,) i32 on the device: the plain rows of a RAGGED batch, pn2_mlp_train_*_ragged -- or, on a grouped level, its
+    per-cloud centroid counts / a group_all level's point counts, pn2_mlp_train_*_group_ragged; else None), then per layer
     conv.weight, conv.bias (or None), bn.weight, bn.bias. On ragged rows the node owns the validity mask: forward writes it, it
     is saved behind everything else with lengths, and the host never reads lengths -- no synchronisation in either direction."""
 
@@ -534,7 +564,8 @@ class _TrainMLP(torch.autograd.Function):
             out = torch.empty((groups, 2 * cl if code == 3 else cl), dtype=torch.float32, device=dev)
             # argsel / zsel: the max's selection (max, max_and_avg); an empty placeholder for the averages
             argsel = torch.empty((groups, cl) if code in (0, 3) else (0,), dtype=torch.int32, device=dev)
-            zsel = torch.empty((groups, cl), dtype=torch.float32, device=dev) if code in (0, 3) else None
+            # (ragged grouped rows: the pool is a pass over z_L itself, there is no zsel)
+            zsel = torch.empty((groups, cl), dtype=torch.float32, device=dev) if code in (0, 3) and not ragged else None
             if code == 2:
                 pool_w = torch.empty((rows,), dtype=torch.float32, device=dev)
         else:
@@ -545,7 +576,11 @@ class _TrainMLP(torch.autograd.Function):
         ws = _level_workspace(level, widths, code, 0, dev, _group_dims(level, x), opts, ragged=ragged)
         gptr, xptr = (ctypes.byref(grp), None) if level.grouped else (None, ptr(x))
         with on_device(dev):
-            if ragged:
+            if ragged and level.grouped:
+                _C.check(_C.lib().pn2_mlp_train_forward_group_ragged(rows, n, arr, gptr, level.pool_rows, ptr(lengths), ptr(out),
+                                                                     ptr(argsel), ptr(mask), ptr(ws), opts, stream_ptr(dev)),
+                         "mlp_train_forward_group_ragged")
+            elif ragged:
                 _C.check(_C.lib().pn2_mlp_train_forward_ragged(level.b, level.n, ptr(lengths), n, arr, xptr, ptr(out), ptr(mask),
                                                                ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward_ragged")
             elif level.frozen:      # running statistics (bn.eval()): read, never written -- no counter either
@@ -561,13 +596,13 @@ class _TrainMLP(torch.autograd.Function):
                                                            ptr(zsel), ptr(ws), opts, stream_ptr(dev)), "mlp_train_forward")
         if not level.frozen:
             _count_batch(level.pairs)
-        ctx.code = code
+        ctx.code, ctx.ragged = code, ragged
         if not level.pool_rows:
             _save_layers(ctx, level, widths, layers, [x], out, [mask, lengths] if ragged else ())
             return out
         ctx.mark_non_differentiable(argsel)
         _save_layers(ctx, level, widths, layers, [x] if x is not None else [], out,
-                     [argsel] + [t for t in (zsel, pool_w) if t is not None])
+                     [argsel] + [t for t in (zsel, pool_w) if t is not None] + ([mask, lengths] if ragged else []))
         return out, argsel
 
     @staticmethod
@@ -580,7 +615,8 @@ class _TrainMLP(torch.autograd.Function):
             ctx, [[bool(ctx.needs_input_grad[5 + 4 * l + k]) for k in range(4)] for l in range(n)] if frozen else None)
         x = head[0] if head else None
         argsel = tail.pop(0) if level.pool_rows else None
-        zsel = tail.pop(0) if level.pool_rows and code in (0, 3) else None
+        ragged = ctx.ragged                                     # (what forward ran)
+        zsel = tail.pop(0) if level.pool_rows and code in (0, 3) and not ragged else None
         pool_w = tail.pop(0) if code == 2 else None
         mask, lengths = tail if tail else (None, None)         # ragged rows: what forward saved last
         rows = level.rows
@@ -591,7 +627,8 @@ class _TrainMLP(torch.autograd.Function):
         grad_xyz = grad_new_xyz = None
         grad_x = grad_rows = grad_pts = None
         gdims = _group_dims(level, x)
-        per_point = level.grouped and bool(_C.lib().pn2_mlp_train_layer1_per_point_ex(n, _widths_array(widths), gdims, opts))
+        # (ragged grouped rows: one organisation, the gathered layer 1 -- the library writes the per-row gradient)
+        per_point = level.grouped and mask is None and bool(_C.lib().pn2_mlp_train_layer1_per_point_ex(n, _widths_array(widths), gdims, opts))
         if need_x and level.grouped and per_point:
             grad_pts = torch.empty(tuple(x.shape), dtype=torch.float32, device=dev)      # written by the library itself
         elif need_x and level.grouped:
@@ -607,7 +644,12 @@ class _TrainMLP(torch.autograd.Function):
             _KEEP_WS[1] = (ws, rows, widths, level.pool_rows)
         grp = _group_struct(level, x) if level.grouped else None
         with on_device(dev):
-            if mask is not None:
+            if mask is not None and level.grouped:
+                _C.check(_C.lib().pn2_mlp_train_backward_group_ragged(rows, n, arr, ctypes.byref(grp), level.pool_rows, ptr(lengths),
+                                                                      ptr(out), ptr(argsel), ptr(grad_out), ptr(grad_rows),
+                                                                      1 if is_deterministic() else 0, ptr(mask), ptr(ws), opts,
+                                                                      stream_ptr(dev)), "mlp_train_backward_group_ragged")
+            elif mask is not None:
                 _C.check(_C.lib().pn2_mlp_train_backward_ragged(level.b, level.n, ptr(lengths), n, arr, ptr(x), ptr(out), ptr(grad_out),
                                                                 ptr(grad_x), ptr(mask), ptr(ws), opts, stream_ptr(dev)),
                          "mlp_train_backward_ragged")
@@ -662,7 +704,7 @@ def _params(pairs):
     return out
 
 
-def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", xyz_grad=False, frozen=False, plan=None):
+def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", xyz_grad=False, frozen=False, plan=None, counts=None):
     """Training-mode shared MLP + pooling of one SA level / one MSG scale.
     net: nn.Sequential of (Conv2d 1x1, BatchNorm2d, ReLU) triples; xyz (b,n,3); new_xyz (b,m,3) or None and idx
     (b,m,nsample) i32 or None (both None: the group_all level); points (b,n,c) or None.
@@ -677,9 +719,21 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
     parameters that need no gradient get none (a layer none of whose parameters needs one runs no weight-gradient pass).
     plan: an IndexPlan of idx (index_plan(idx, n, "group")): the backward's scatters onto the points -- the features' and, with
     xyz_grad, the coordinates' -- reduce from it, and idx is inverted nowhere in the backward.
+    counts: (b,) per-cloud counts of a RAGGED batch (an int32 / int64 tensor or a sequence, ragged_lengths): with idx the number
+    of valid CENTROIDS of each cloud (group j of cloud c is valid iff j < counts[c]; what geometry(npoints=) produced -- idx of a
+    padding group must hold indices in [0, n), the two-sided ragged operators write 0), for the group_all form the number of valid
+    POINTS (row k of cloud c is valid iff k < counts[c]). The batch statistics, the running averages and every gradient are
+    those of the valid rows alone (group_ragged_supported; pn2_mlp_train_*_group_ragged). Rows of xyz / points beyond a cloud's
+    own points and the output gradient of padding groups may hold anything, NaN included; the output and argsel of a padding group
+    and the gradient of points on rows no valid group names are exactly zero. The host never reads the counts (no
+    synchronisation; a count outside its range is clamped). Only with pooling="max", and not with xyz_grad or frozen
+    (ValueError).
     -> (b, m, cout) pooled features (differentiable w.r.t. points and the parameters), argsel (b, m, cout) i32 -- the max's
     selection; None for avg and weighted_avg."""
     require(pooling in POOLING, "unknown pooling %r" % (pooling,))
+    if counts is not None:
+        bad = [t for t, on in (("pooling=%r" % (pooling,), pooling != "max"), ("xyz_grad=True", xyz_grad), ("frozen=True", frozen)) if on]
+        require(not bad, "sa_mlp_train: counts= is not offered with %s" % " and ".join(bad))
     pairs = conv_bn_pairs(net)
     require(pairs is not None, "sa_mlp_train expects Conv 1x1 + BatchNorm + ReLU triples")
     xyz = f32(xyz, "xyz")
@@ -726,7 +780,12 @@ def sa_mlp_train(net, xyz, new_xyz, points, idx, xyz_first=True, pooling="max", 
                 "unsupported stack for the fused training path with pooling %r" % (pooling,))
     same_device(xyz, pairs[0][0].weight)
     lv.xyz_grad = bool(xyz_grad)
-    if lv.xyz_grad:
+    if counts is not None:
+        counts = ragged_lengths(counts, b, xyz.device, "counts")
+        require(group_ragged_supported(net, b, n, lv.m, lv.nsample, points.shape[2] if points is not None else 0, idx is not None),
+                "unsupported level for the fused training path on ragged grouped rows")
+        out, argsel = _TrainMLP.apply(lv, points, None, None, counts, *_params(pairs))
+    elif lv.xyz_grad:
         require(lv.frozen or xyz_grad_supported(net, lv.rows, lv.pool_rows, pooling, b, n, lv.m, points.shape[2] if points is not None else 0,
                                    idx is not None),
                 "the fused training path has no coordinate gradients for this level (pooling %r)" % (pooling,))
