@@ -346,9 +346,11 @@ int pn2_three_nn_ex(int b, int n, int m, const float *xyz1, const float *xyz2, f
  * a length into 1..n for memory safety only -- validating is the caller's business (Python: pointnet2_amd.check_lengths).
  * A NULL lengths is PN2_E_NULL; the other argument checks and codes are the dense entries'.
  *
- * pn2_farthest_point_sample_ragged: the register tier only (every point updated every round, csrc/fps_body.h), one workgroup
- *   per cloud, geometry chosen from the padded n; PN2_E_TOO_LARGE for n > 16384. out_xyz (b,m,3) may be NULL.
- *   m > lengths[c] behaves as the dense operator with npoint > n.
+ * pn2_farthest_point_sample_ragged: one workgroup per cloud; the tier is chosen by the size rule of pn2_farthest_point_sample
+ *   applied to the PADDED n and m (the PN2_FPS_AUTO case of pn2_farthest_point_sample_ragged_variant below: batched, pruned or
+ *   register tier), template, threads and LDS from the padded n. Every tier obeys the slice rule, so the choice shows in time
+ *   alone. PN2_E_TOO_LARGE for n > 16384. out_xyz (b,m,3) may be NULL. m > lengths[c] behaves as the dense operator with
+ *   npoint > n.
  * pn2_query_ball_group_xyz_ragged: xyz1 ragged (lengths1), the queries xyz2 (b,m,3) dense; kernel / cells_qpb as
  *   pn2_query_ball_group_xyz_ex (a cloud below 64 points takes the sweep inside the cell-list kernel); grouped_xyz NULL =
  *   plain query_ball_point.
@@ -441,6 +443,19 @@ int pn2_farthest_point_sample_ex(int T, int P, int b, int n, int m, const float 
 #define PN2_FPS_BATCH 3
 int pn2_farthest_point_sample_variant(int variant, int b, int n, int m, const float *inp, float *temp, int *out,
                                       float *out_xyz, void *stream);
+/* The ragged entries (pn2_farthest_point_sample_ragged, and with npoints != NULL pn2_farthest_point_sample_ragged_counts) with
+ * the tier chosen by the caller; those two are this entry with PN2_FPS_AUTO. variant as above, the size rule applied to the
+ * padded n and m; PN2_FPS_FULL is the register tier in the geometry chosen from the padded n. The pruned and batched tiers run
+ * their dense bodies on each cloud's slice with (lengths[c], npoints[c], ceil(lengths[c] / 512)) in the template of the padded
+ * n: the slots beyond a cloud's points are the padding slots dense input has too (value 0, lowest key), up to all but one of
+ * them (DESIGN.md 4.11 "padding slots"). Results are the slice rule's whatever the tier; the fill rows of the counts form are
+ * index 0 and xyz[c, 0]. Neither count array is read by the host, no memset, capturable.
+ * Codes: a variant out of range is PN2_E_ARG, checked first; then the order and codes of pn2_farthest_point_sample_ragged
+ * (b = 0 or m <= 0 PN2_OK, extents PN2_E_SHAPE, inp / lengths / out NULL PN2_E_NULL, n > 16384 PN2_E_TOO_LARGE); a forced
+ * PN2_FPS_PRUNED / PN2_FPS_BATCH outside its rank-slot envelope (of the padded n) is PN2_E_ARG. */
+int pn2_farthest_point_sample_ragged_variant(int variant, int b, int n, int m, const float *inp, const int *lengths,
+                                             const int *npoints /* NULL: m samples from every cloud */,
+                                             int *out, float *out_xyz /* may be NULL */, void *stream);
 
 /* The whole xyz half of sample_and_group (pointnet_util.py:40-46) in ONE launch, with the ball
  * queries overlapped under the farthest-point-sampling chain: producer workgroups (one per cloud)

@@ -146,6 +146,7 @@ _SIGNATURES = {
     "pn2_query_ball_group_xyz_msg_ragged_pair": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "pn2_knn_point_ragged_pair": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_three_nn_ragged_pair": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "pn2_farthest_point_sample_ragged_variant": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "pn2_fps_temp_floats": ctypes.c_longlong,

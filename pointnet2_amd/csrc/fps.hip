@@ -73,7 +73,20 @@ __global__ __launch_bounds__(T) void fps_reg_ragged_kernel(int n, int m, const f
 // the first m_c samples of the dense operator on the slice (the chain is prefix-consistent: round j depends on rounds < j
 // alone). Rows m_c .. m-1 repeat sample 0, the way a ball query pads with its first hit; sample 0 is point 0 by the reference's
 // rule (tf_sampling_g.cu:114-116), so the fill is index 0 and xyz[c, 0] and reads nothing back. The fill rows are disjoint from
-// the body's, so no barrier stands between the two.
+// the body's, so no barrier stands between the two. (The fill is a function of its own: the wrappers of the other two tiers
+// below end with it too.)
+template <int T>
+__device__ __forceinline__ void fps_ragged_fill(int mc, int m, const float *__restrict__ src, int *__restrict__ dst, float *__restrict__ dxyz)
+{
+    if (mc < m) {                                          // block-uniform
+        const float x0 = src[0], y0 = src[1], z0 = src[2];
+        for (int j = mc + (int)threadIdx.x; j < m; j += T) {
+            dst[j] = 0;
+            if (dxyz) { dxyz[j * 3 + 0] = x0; dxyz[j * 3 + 1] = y0; dxyz[j * 3 + 2] = z0; }
+        }
+    }
+}
+
 template <int T, int P, bool LDSXYZ>
 __global__ __launch_bounds__(T) void fps_reg_ragged_counts_kernel(int n, int m, const float *__restrict__ xyz,
                                                                   const int *__restrict__ lengths, const int *__restrict__ npoints,
@@ -88,13 +101,7 @@ __global__ __launch_bounds__(T) void fps_reg_ragged_counts_kernel(int n, int m, 
     int *__restrict__ dst = out + (size_t)c * m;
     float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
     fps_reg_body<T, P, LDSXYZ, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
-    if (mc < m) {                                          // block-uniform
-        const float x0 = src[0], y0 = src[1], z0 = src[2];
-        for (int j = mc + (int)threadIdx.x; j < m; j += T) {
-            dst[j] = 0;
-            if (dxyz) { dxyz[j * 3 + 0] = x0; dxyz[j * 3 + 1] = y0; dxyz[j * 3 + 2] = z0; }
-        }
-    }
+    fps_ragged_fill<T>(mc, m, src, dst, dxyz);
 }
 
 // Pruned tier (fps_pruned_body.h): kd-grouped slots, per-round box tests, only the groups the new sample can reach are
@@ -115,6 +122,52 @@ __global__ __launch_bounds__(kBtT) void fps_batch_kernel(int n, int m, int Q, co
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     fps_batch_body<P, GS, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
+}
+
+// Ragged batch on the pruned and batched tiers (pn2_farthest_point_sample_ragged_variant). The slice rule of
+// fps_reg_ragged_kernel carries over unchanged, because both bodies take (n, m, Q, cloud, xyz, ...) like the register body: the
+// workgroup hands the body its own slab as cloud 0 with n = n_c, Q = ceil(n_c / 512) and -- with counts -- m = m_c. The template
+// (P, GS), the thread count and the LDS bytes come from the padded n: NS = threads * P >= 512 ceil(n / 512) >= 512 Q_c, so every
+// tie rank of the slice has a slot and fps_pruned_prologue deals the items i >= n_c as padding items at point 0's position (value
+// 0, key low word 0); rows at or beyond n_c are never addressed (k = i < n ? i : 0 there). A cloud may now be ONE point in 8192
+// slots, where dense input fills at least half of a template: DESIGN.md 4.11 goes through the prologue, COLLECT, the picker's
+// uncounted loop, the equal-keys rule, the value-0 tail, the slow-batch clock and the pruned tier's skipped reduction on such
+// clouds, and through the termination of every wait inside the workgroup (tests/test_fps_batch_padding_model.py is the CPU
+// model). n_c, m_c and Q_c are block-uniform scalars, so every wave of the workgroup -- the picker included -- executes the
+// barriers of the same chain. COUNTS: npoints is read and rows m_c .. m-1 are filled as in fps_reg_ragged_counts_kernel (index 0
+// and xyz[c, 0]; disjoint from the body's rows, so no barrier stands in between).
+template <int P, int GS, bool COUNTS>
+__global__ __launch_bounds__(kPrT) void fps_pruned_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
+                                                                 const int *__restrict__ npoints, int *__restrict__ out,
+                                                                 float *__restrict__ out_xyz)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c = blockIdx.x;
+    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[c]), 1), n);
+    const int mc = COUNTS ? min(max(__builtin_amdgcn_readfirstlane(npoints[c]), 1), m) : m;
+    const int Qc = (nc + kRefThreads - 1) / kRefThreads;
+    const float *__restrict__ src = xyz + (size_t)c * n * 3;
+    int *__restrict__ dst = out + (size_t)c * m;
+    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
+    fps_pruned_body<P, GS, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
+    if (COUNTS) fps_ragged_fill<kPrT>(mc, m, src, dst, dxyz);
+}
+
+template <int P, int GS, bool COUNTS>
+__global__ __launch_bounds__(kBtT) void fps_batch_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
+                                                                const int *__restrict__ npoints, int *__restrict__ out,
+                                                                float *__restrict__ out_xyz)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c = blockIdx.x;
+    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[c]), 1), n);
+    const int mc = COUNTS ? min(max(__builtin_amdgcn_readfirstlane(npoints[c]), 1), m) : m;
+    const int Qc = (nc + kRefThreads - 1) / kRefThreads;
+    const float *__restrict__ src = xyz + (size_t)c * n * 3;
+    int *__restrict__ dst = out + (size_t)c * m;
+    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
+    fps_batch_body<P, GS, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
+    if (COUNTS) fps_ragged_fill<kBtT>(mc, m, src, dst, dxyz);
 }
 
 // ---------------------------------------------------------------------------
@@ -416,6 +469,63 @@ static int fps_launch_batch(int b, int n, int m, const float *inp, int *out, flo
     return launch_batch<8192 / kBtUT, 8192 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, Q, inp, out, oxyz, st);
 }
 
+// The ragged wrappers of the two tiers: template, thread count and LDS bytes from the padded n, exactly as fps_launch_pruned /
+// fps_launch_batch choose them. npoints: NULL = m samples from every cloud.
+template <int P, int GS>
+static int launch_pruned_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
+                                hipStream_t st)
+{
+    const size_t lds = fps_pruned_lds_bytes(P);
+    if (npoints) {
+        auto kern = fps_pruned_ragged_kernel<P, GS, true>;
+        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+        return launch(kern, dim3(b), dim3(kPrT), lds, st, n, m, inp, lengths, npoints, out, oxyz);
+    }
+    auto kern = fps_pruned_ragged_kernel<P, GS, false>;
+    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+    return launch(kern, dim3(b), dim3(kPrT), lds, st, n, m, inp, lengths, npoints, out, oxyz);
+}
+
+static int fps_launch_pruned_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
+                                    hipStream_t st)
+{
+    const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
+    if (!pruned_covers(ranks)) return PN2_E_ARG;
+    if (ranks <= 4096) return launch_pruned_ragged<16, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+    return launch_pruned_ragged<32, 4>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+}
+
+template <int P, int GS>
+static int launch_batch_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
+                               hipStream_t st)
+{
+    const size_t lds = fps_batch_lds_bytes(P);
+    if (npoints) {
+        auto kern = fps_batch_ragged_kernel<P, GS, true>;
+        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+        return launch(kern, dim3(b), dim3(kBtT), lds, st, n, m, inp, lengths, npoints, out, oxyz);
+    }
+    auto kern = fps_batch_ragged_kernel<P, GS, false>;
+    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+    return launch(kern, dim3(b), dim3(kBtT), lds, st, n, m, inp, lengths, npoints, out, oxyz);
+}
+
+static int fps_launch_batch_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
+                                   hipStream_t st)
+{
+    const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
+    if (!fps_batch_covers(ranks)) return PN2_E_ARG;
+    if constexpr (kBtUT == 512) {
+        if (ranks <= 1024) return launch_batch_ragged<2, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+        if (ranks <= 2048) return launch_batch_ragged<4, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+    } else if (ranks <= 2048) {
+        return PN2_E_ARG;
+    }
+    if (ranks <= 4096)
+        return launch_batch_ragged<4096 / kBtUT, 4096 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+    return launch_batch_ragged<8192 / kBtUT, 8192 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+}
+
 constexpr int kMaxLdsSlots = 8192;     // 256 B + 16 B per rank slot <= 160 KiB
 constexpr int kMaxRegPoints = 16384;
 
@@ -519,10 +629,12 @@ extern "C" int pn2_farthest_point_sample_variant(int variant, int b, int n, int 
 }
 
 // Ragged batch: cloud c is inp[c, :lengths[c]] of a padded (b, n, 3) tensor, lengths (b) int32 on the device, never read by
-// the host. Result per cloud = pn2_farthest_point_sample_gather on the slice, tie rule included. Register tier only (the
-// geometry fps_entry picks for PN2_FPS_FULL at the padded n); PN2_E_TOO_LARGE beyond 16384 points. out_xyz may be NULL.
+// the host. Result per cloud = pn2_farthest_point_sample_gather on the slice, tie rule included, whatever the tier. The tier is
+// chosen as fps_entry chooses it, by the size rule on the PADDED n and m (the host knows no other): the batched tier, the pruned
+// tier, else -- and for PN2_FPS_FULL -- the register tier in the geometry fps_entry picks at the padded n. PN2_E_TOO_LARGE
+// beyond 16384 points. out_xyz may be NULL.
 static int fps_ragged_entry(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, bool counts, int *out,
-                            float *out_xyz, void *stream)
+                            float *out_xyz, void *stream, int variant = PN2_FPS_AUTO)
 {
     using namespace pn2;
     if (m <= 0 || b == 0) return PN2_OK;
@@ -532,6 +644,10 @@ static int fps_ragged_entry(int b, int n, int m, const float *inp, const int *le
     if ((long long)b * n * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
     hipStream_t st = as_stream(stream);
     const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
+    if (variant == PN2_FPS_BATCH || (variant == PN2_FPS_AUTO && fps_batch_pays(ranks, m)))
+        return fps_launch_batch_ragged(b, n, m, inp, lengths, npoints, out, out_xyz, st);
+    if (variant == PN2_FPS_PRUNED || (variant == PN2_FPS_AUTO && fps_pruned_pays(ranks, m)))
+        return fps_launch_pruned_ragged(b, n, m, inp, lengths, npoints, out, out_xyz, st);
     const int T = ranks <= 2048 ? 256 : 512;
     const int P = next_pow2((ranks + T - 1) / T);
 #define PN2_FPS_RAGGED(TT, PP) \
@@ -559,6 +675,16 @@ extern "C" int pn2_farthest_point_sample_ragged_counts(int b, int n, int m, cons
                                                        int *out, float *out_xyz, void *stream)
 {
     return fps_ragged_entry(b, n, m, inp, lengths, npoints, true, out, out_xyz, stream);
+}
+
+// Both ragged entries with the tier chosen by the caller (tests, A/B timing; results never depend on it): variant as in
+// pn2_farthest_point_sample_variant, the size rule on the padded n and m; npoints NULL = m samples from every cloud. The two
+// entries above are its PN2_FPS_AUTO case.
+extern "C" int pn2_farthest_point_sample_ragged_variant(int variant, int b, int n, int m, const float *inp, const int *lengths,
+                                                        const int *npoints, int *out, float *out_xyz, void *stream)
+{
+    if (variant < PN2_FPS_AUTO || variant > PN2_FPS_BATCH) return PN2_E_ARG;
+    return fps_ragged_entry(b, n, m, inp, lengths, npoints, false, out, out_xyz, stream, variant);
 }
 
 // farthest_point_sample for input the caller BELIEVES to be in farthest-point order already (the previous level's samples:

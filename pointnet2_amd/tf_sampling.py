@@ -98,8 +98,10 @@ _FPS_VARIANT = [FPS_AUTO]
 
 
 def set_fps_variant(variant=FPS_AUTO):
-    """Does not apply to calls with `lengths` (ragged batches): those always run the register tier, one workgroup per cloud
-    (pn2_farthest_point_sample_ragged); the pruned and batched tiers are not offered for ragged input."""
+    """Applies to calls with `lengths=` / `npoints=` (ragged batches) too: every tier runs on each cloud's slice and gives the
+    slice rule's result. With FPS_AUTO those calls go through pn2_farthest_point_sample_ragged / _ragged_counts, which apply
+    the library's size rule to the padded n and npoint; a forced tier goes through pn2_farthest_point_sample_ragged_variant
+    (ValueError where the padded n is outside the tier's rank-slot envelope, as for dense input)."""
     require(int(variant) in (FPS_AUTO, FPS_FULL, FPS_PRUNED, FPS_BATCH), "fps variant must be 0 (auto), 1 (full), 2 (pruned) or 3 (batched)")
     _FPS_VARIANT[0] = int(variant)
 
@@ -155,7 +157,7 @@ def ordered_workspace(lib, dev, stream, b):
     return ws
 
 
-FPS_RAGGED_MAX_POINTS = 16384           # the register tier's envelope (pn2_farthest_point_sample_ragged)
+FPS_RAGGED_MAX_POINTS = 16384           # the register tiers' envelope (pn2_farthest_point_sample_ragged)
 
 
 def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
@@ -163,6 +165,13 @@ def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
     require(n <= FPS_RAGGED_MAX_POINTS, "%s with lengths supports at most %d points per (padded) cloud, got %d"
             % (op, FPS_RAGGED_MAX_POINTS, n))
     dev = inp.device
+    if _FPS_VARIANT[0]:                     # a forced tier: one entry for both forms (npoints NULL = npoint samples from every cloud)
+        lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
+        cnts = ragged_lengths(npoints, b, dev, "npoints") if npoints is not None else None
+        with on_device(dev):
+            _C.check(_C.lib().pn2_farthest_point_sample_ragged_variant(_FPS_VARIANT[0], b, n, m, ptr(inp), ptr(lens), ptr(cnts), ptr(out),
+                                                                       ptr(new_xyz), stream_ptr(dev)), op)
+        return
     if npoints is None:
         lens = ragged_lengths(lengths, b, dev)
         with on_device(dev):
