@@ -412,6 +412,48 @@ int pn2_knn_point_ragged_pair(int b, int n, int m, int k, const float *xyz1, con
 int pn2_three_nn_ragged_pair(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2, const int *lengths2,
                              float *dist, int *idx, int variant, void *stream);
 
+/* ---- ragged inference: counts in the fused MLPs, one call per ragged level ------------------------------------------------------
+ * The fused inference kernels with count arrays (b) int32 in DEVICE memory, never read by the host; a count is clamped into
+ * 1..extent on the device, for memory safety only. THE SLICE RULE FOR THE FUSED MLPS: for cloud c the output rows below its count
+ * are bit-identical to the dense entry applied to the cloud's slices alone (b = 1); output rows at or beyond the count are fully
+ * written with all-zero bits (+0.0). Every row of the fused stacks is an independent fixed-order sum and the max pool is
+ * order-independent, so the rule holds exactly. No host synchronisation and no memset beyond the dense entry's own clear of a
+ * split group_all output; everything is stream-ordered and capturable.
+ * Rows of xyz / points / points1 / points2 at or beyond a length may hold anything, NaN included, and influence nothing -- a
+ * per-point pre-pass (the streamed SA kernel's layer 1, the FP kernels' Q = points2 . W1a) may still multiply them: those results
+ * are never gathered. Rows of new_xyz, idx, dist at or beyond a count are never dereferenced (a padding row gathers through valid
+ * row 0 of its own cloud, or is skipped). All host decisions (kernel family, grid, LDS, workspace bytes) come from the padded
+ * extents: pn2_sa_mlp3_ws_bytes and pn2_fp_mlp_ws_bytes serve these entries unchanged, and so do the packed weights.
+ *
+ * pn2_sa_mlp3_maxpool_ragged: pn2_sa_mlp3_maxpool_ex (max pooling) with `lengths` behind xyz and `npoints` behind new_xyz.
+ *   Grouped form: npoints is required (NULL: PN2_E_NULL) -- centroid row j of cloud c is valid for j < npoints[c]; lengths may be
+ *   NULL (idx of a valid row stays below its cloud's length; it would only let a per-point pre-pass skip rows, which none does).
+ *   group_all form (idx == NULL && new_xyz == NULL, m = 1, nsample = n): lengths is required (NULL: PN2_E_NULL) -- cloud c's group
+ *   is its first lengths[c] rows; a non-NULL npoints is PN2_E_ARG. Otherwise the validation order and codes are the dense
+ *   entry's: b == 0 / m == 0 is PN2_OK before any count pointer is looked at, a stack only the other pooling modes cover is
+ *   PN2_E_TOO_LARGE.
+ * pn2_fp_mlp_ragged: pn2_fp_mlp with `lengths1` (required) behind points1: rows of the unknown side at or beyond lengths1[c].
+ * pn2_sa_level_ragged: pn2_farthest_point_sample_ragged_counts, pn2_query_ball_group_xyz_ragged_pair (kernel 0, cells_qpb 0,
+ *   centroid subtracted), pn2_sa_mlp3_maxpool_ragged enqueued by one call; both count arrays are required (a caller with a dense
+ *   side passes full counts). No overlapped launch: no sample workspace, no generation, no FPS temp. The first failing part's
+ *   code is returned.
+ * pn2_fp_level_ragged: pn2_three_nn_ragged_pair (variant 0) + pn2_fp_mlp_ragged. */
+int pn2_sa_mlp3_maxpool_ragged(int b, int n, int m, int nsample, int cfeat, const float *xyz, const int *lengths,
+                               const float *new_xyz, const int *npoints, const float *points, const int *idx, int c1, int c2,
+                               int c3, const float *wpacked, const float *bpacked, float *out, void *ws, int variant,
+                               void *stream);
+int pn2_fp_mlp_ragged(int b, int n, int m, int c2, int c1, const float *points2, const float *points1, const int *lengths1,
+                      const int *idx, const float *dist, int nlayers, const int *widths, int kind, const float *wpacked,
+                      const float *bpacked, float *out, void *ws, void *stream);
+int pn2_sa_level_ragged(int b, int n, int m, float radius, int nsample, int cfeat, const float *xyz, const int *lengths,
+                        const int *npoints, const float *points, int c1, int c2, int c3, const float *wpacked,
+                        const float *bpacked, int *fps_idx, float *new_xyz, int *idx, int *pts_cnt, float *grouped_xyz,
+                        float *out, void *ws_mlp, void *stream);
+int pn2_fp_level_ragged(int b, int n, int m, int c2, int c1, const float *xyz1, const int *lengths1, const float *xyz2,
+                        const int *lengths2, const float *points2, const float *points1, int nlayers, const int *widths,
+                        int kind, const float *wpacked, const float *bpacked, float *dist, int *idx, float *out, void *ws,
+                        void *stream);
+
 /* pn2_group_point / pn2_three_interpolate with the kernel choice per call (parity tests force every kernel,
  * scripts/bw_probe.py times them). group: 0 automatic, 1 flat first-generation kernels, 2 row kernels,
  * 3 row kernels with non-temporal stores; three_interpolate: 0 automatic, 1 flat, 2 row kernel, 3 row kernel with

@@ -141,6 +141,10 @@ _SIGNATURES = {
     "pn2_query_ball_group_xyz_msg_ragged": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],
     "pn2_knn_point_ragged": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_three_nn_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp],
+    "pn2_sa_mlp3_maxpool_ragged": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp],
+    "pn2_fp_mlp_ragged": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    "pn2_sa_level_ragged": [_i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_fp_level_ragged": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_farthest_point_sample_ragged_counts": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_query_ball_group_xyz_ragged_pair": [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp],
     "pn2_query_ball_group_xyz_msg_ragged_pair": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp],

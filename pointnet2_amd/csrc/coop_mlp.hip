@@ -40,7 +40,14 @@ __device__ __forceinline__ float coop_interp3(float p1, float p2, float p3, floa
 // SPLIT_OUT (two grouped layers): the second layer is a HIDDEN layer whose output tiles leave for global memory
 // in their three-level operand form, [unit][tile][e][level][lane] -- the A operand of pool_gemm_kernel below,
 // which runs the wide last layer of such a stack as a tiled GEMM.
-template <int GATHER, int Q1, int Q2, int Q3, bool SPLIT_OUT = false>
+// RAGGED (p.counts, one int per cloud, clamped on the device; include/pn2ops.h "ragged inference"): the dense instantiations
+// have none of it. Grouped rows with idx: counts = npoints -- a centroid at or beyond its cloud's count is a work unit of its
+// own, so the whole workgroup leaves it before the first barrier (+0.0 stored; a split unit stores nothing: the output is
+// cleared, the GEMM skips the group). group_all (idx == NULL): counts = lengths -- the group is the cloud's first len rows,
+// ceil(len / 32) parts, the gather clamps to len - 1, later parts do no work. Feature propagation: counts = lengths1 -- a
+// padding lane gathers valid row 0 of its own cloud and its row is stored as +0.0; all four waves hold the same 32 rows, so
+// "every row of the unit is padding" is one ballot per wave with the same answer in each.
+template <int GATHER, int Q1, int Q2, int Q3, bool SPLIT_OUT = false, bool RAGGED = false>
 __global__ __launch_bounds__(kMlpThreads) void coop_mlp_kernel(CoopParams p)
 {
     constexpr int T1 = 4 * Q1, T2 = 4 * Q2, T3 = 4 * Q3;
@@ -106,11 +113,59 @@ __global__ __launch_bounds__(kMlpThreads) void coop_mlp_kernel(CoopParams p)
 
     for (long long unit_raw = blockIdx.x; unit_raw < units; unit_raw += gridDim.x) {
         const long long unit = p.split ? unit_raw / parts : unit_raw;       // centroid (SA) / group of 32 points (FP)
+        int len = p.n, parts_c = parts;                                     // RAGGED group_all: the cloud's rows and parts
+        unsigned int valid_rows = ~0u;                                      // RAGGED FP: bit v = the row of this lane's register v (row 32 unit + mlp_chan(v, h)) is valid
+        long long fp_row = 0;                                               // RAGGED FP: the row this lane gathers
+        if (RAGGED && POOL) {
+            if (p.idx) {
+                const long long cloud = unit / p.m;
+                const int cnt = min(max(p.counts[cloud], 1), p.m);
+                if ((int)(unit - cloud * p.m) >= cnt) {                     // workgroup-uniform, in front of every barrier
+                    if (!p.split) {
+#pragma unroll
+                        for (int g = 0; g < QL; ++g) {
+                            const int ch = 32 * (4 * g + w) + s;
+                            if (h == 0 && ch < p.cout) p.out[unit * p.cout + ch] = 0.0f;
+                        }
+                    }
+                    continue;
+                }
+            } else {
+                len = min(max(p.counts[unit / p.m], 1), p.n);
+                parts_c = (len + 31) / 32;
+                if (p.split && (int)(unit_raw % parts) >= parts_c) continue;
+            }
+        }
+        if (RAGGED && !POOL) {
+            const long long row = min(unit * 32 + s, p.rows - 1);
+            const long long cloud = row / p.n;
+            const bool ok = (int)(row - cloud * p.n) < min(max(p.counts[cloud], 1), p.n);
+            fp_row = ok ? row : cloud * p.n;
+            const unsigned int rows32 = (unsigned int)__ballot(ok);         // lanes 0-31: bit i = row 32 unit + i is a valid row
+            valid_rows = 0u;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) valid_rows |= ((rows32 >> mlp_chan(v, h)) & 1u) << v;
+            if (rows32 == 0u) {                                             // the same in all four waves
+#pragma unroll
+                for (int g = 0; g < QL; ++g) {
+                    const int ch = 32 * (4 * g + w) + s;
+                    if (ch < p.cout) {
+#pragma unroll
+                        for (int v = 0; v < 16; ++v) {
+                            const long long r = unit * 32 + mlp_chan(v, h);
+                            if (r < p.rows) p.out[r * p.cout + ch] = 0.0f;
+                        }
+                    }
+                }
+                continue;
+            }
+        }
         float best[QL];
 #pragma unroll
         for (int g = 0; g < QL; ++g) best[g] = -INFINITY;
         for (int part_i = 0; part_i < parts_in; ++part_i) {
             const int part = p.split ? (int)(unit_raw % parts) : part_i;
+            if (RAGGED && POOL && part >= parts_c) break;                  // (uniform; nothing of this part has begun)
             k = 0;
             // ---- per-lane gather context ----------------------------------------------------------------
             const float *gf = nullptr, *gx = nullptr, *gc = nullptr;       // grouped: feature row, xyz row, centroid
@@ -121,12 +176,12 @@ __global__ __launch_bounds__(kMlpThreads) void coop_mlp_kernel(CoopParams p)
                 const int smp = part * 32 + s;
                 int pt;
                 if (p.idx) pt = p.idx[unit * p.nsample + min(smp, p.nsample - 1)];
-                else pt = min(smp, p.n - 1);                               // group_all: the group IS the cloud
+                else pt = min(smp, (RAGGED ? len : p.n) - 1);              // group_all: the group IS the cloud
                 gf = p.feat + ((size_t)cloud * p.n + pt) * p.cf;
                 gx = p.xyz + ((size_t)cloud * p.n + pt) * 3;
                 gc = p.new_xyz ? p.new_xyz + unit * 3 : nullptr;
             } else {
-                const long long row = min(unit * 32 + s, p.rows - 1);
+                const long long row = RAGGED ? fp_row : min(unit * 32 + s, p.rows - 1);
                 const long long cloud = row / p.n;
                 const int *ip = p.idx + row * 3;
                 const float *dp = p.dist + row * 3;
@@ -229,7 +284,7 @@ __global__ __launch_bounds__(kMlpThreads) void coop_mlp_kernel(CoopParams p)
                         float mx = -INFINITY;
 #pragma unroll
                         for (int v = 0; v < 16; ++v)
-                            if (part * 32 + mlp_chan(v, h) < p.nsample) mx = fmaxf(mx, acc[g][v]);   // masked tail of the group
+                            if (part * 32 + mlp_chan(v, h) < ((RAGGED && !p.idx) ? len : p.nsample)) mx = fmaxf(mx, acc[g][v]);   // masked tail of the group
                         best[g] = fmaxf(best[g], mx);
                     } else {
                         const int ch = 32 * (4 * g + w) + s;
@@ -238,7 +293,8 @@ __global__ __launch_bounds__(kMlpThreads) void coop_mlp_kernel(CoopParams p)
 #pragma unroll
                             for (int v = 0; v < 16; ++v) {
                                 const long long r = unit * 32 + mlp_chan(v, h);
-                                if (r < p.rows) p.out[r * p.cout + ch] = fmaxf(__fadd_rn(acc[g][v], bias), 0.0f);
+                                const float val = fmaxf(__fadd_rn(acc[g][v], bias), 0.0f);
+                                if (r < p.rows) p.out[r * p.cout + ch] = (!RAGGED || ((valid_rows >> v) & 1u)) ? val : 0.0f;
                             }
                         }
                     }
@@ -303,10 +359,14 @@ __global__ __launch_bounds__(kMlpThreads) void coop_mlp_kernel(CoopParams p)
 constexpr int kGemmThreads = 512, kGemmColTiles = 4, kGemmRowTiles = 4;
 constexpr int kGemmStageVec = (kGemmColTiles + kGemmRowTiles) * (kPairWords / 4);   // 48 KiB per contraction step
 
+// RAGGED: 1 = grouped rows with npoints (a group at or beyond its cloud's count: +0.0, none of its split tiles exists),
+// 2 = group_all with lengths (the group has ceil(len / 32) parts: only those tiles were written, none of the others is read)
+template <int RAGGED>
 __global__ __launch_bounds__(kGemmThreads) void pool_gemm_kernel(int parts, int tk, int cout, long long groups,
                                                                 const float *__restrict__ asplit,
                                                                 const float *__restrict__ wgemm,
-                                                                const float *__restrict__ bias, float *__restrict__ out)
+                                                                const float *__restrict__ bias, float *__restrict__ out,
+                                                                const int *__restrict__ counts, int m, int n)
 {
     constexpr int kTileVec = kPairWords / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -324,12 +384,24 @@ __global__ __launch_bounds__(kGemmThreads) void pool_gemm_kernel(int parts, int 
     for (long long job = blockIdx.x; job < groups * colblocks; job += gridDim.x) {
         const long long grp = job / colblocks;
         const int cb = (int)(job % colblocks);
+        int parts_c = parts;
+        if (RAGGED == 1) {
+            const long long cloud = grp / m;
+            if ((int)(grp - cloud * m) >= min(max(counts[cloud], 1), m)) {      // workgroup-uniform, between two jobs
+                for (int i = tid; i < 32 * kGemmColTiles; i += kGemmThreads) {
+                    const int ch = 32 * kGemmColTiles * cb + i;
+                    if (ch < cout) out[grp * cout + ch] = 0.0f;
+                }
+                continue;
+            }
+        }
+        if (RAGGED == 2) parts_c = (min(max(counts[grp], 1), n) + 31) / 32;
         for (int i = tid; i < 32 * kGemmColTiles; i += kGemmThreads) colmax[i] = 0;
         const u32x4 *wsrc = reinterpret_cast<const u32x4 *>(wgemm) + (size_t)cb * tk * (kGemmColTiles * kTileVec) + tid;
-        for (int chunk = 0; chunk < parts; chunk += kGemmRowTiles) {
-            const u32x4 *a0 = reinterpret_cast<const u32x4 *>(asplit) + (size_t)(grp * parts + min(chunk + ar0, parts - 1)) * tk * kTileVec + ao0;
-            const u32x4 *a1 = reinterpret_cast<const u32x4 *>(asplit) + (size_t)(grp * parts + min(chunk + ar1, parts - 1)) * tk * kTileVec + ao1;
-            const u32x4 *a2 = reinterpret_cast<const u32x4 *>(asplit) + (size_t)(grp * parts + min(chunk + ar2, parts - 1)) * tk * kTileVec + ao2;
+        for (int chunk = 0; chunk < parts_c; chunk += kGemmRowTiles) {
+            const u32x4 *a0 = reinterpret_cast<const u32x4 *>(asplit) + (size_t)(grp * parts + min(chunk + ar0, parts_c - 1)) * tk * kTileVec + ao0;
+            const u32x4 *a1 = reinterpret_cast<const u32x4 *>(asplit) + (size_t)(grp * parts + min(chunk + ar1, parts_c - 1)) * tk * kTileVec + ao1;
+            const u32x4 *a2 = reinterpret_cast<const u32x4 *>(asplit) + (size_t)(grp * parts + min(chunk + ar2, parts_c - 1)) * tk * kTileVec + ao2;
             // two stages in flight in registers (sets E / O for even / odd contraction steps): a step is ~0.8 us of MFMA
             // work per SIMD, less than an L2 round trip under load, so one stage ahead left the loads exposed
             u32x4 e0, e1, e2, e3, e4, e5, o0, o1, o2, o3, o4, o5;
@@ -487,11 +559,11 @@ void mlp_coop_pack(const MlpCoopConfig &c, int cin, int nlayers, const int *widt
     }
 }
 
-template <int GATHER, int Q1, int Q2, int Q3, bool SPLIT_OUT = false>
+template <int GATHER, int Q1, int Q2, int Q3, bool SPLIT_OUT = false, bool RAGGED = false>
 static int launch_coop(const CoopParams &p, long long units, hipStream_t st)
 {
     const size_t lds = sizeof(float) * kPairWords * (size_t)(4 * Q1 + (Q3 > 0 ? 4 * Q2 : 0)) + sizeof(float) * 32 * (size_t)(4 * (Q1 + Q2 + Q3));
-    auto kern = coop_mlp_kernel<GATHER, Q1, Q2, Q3, SPLIT_OUT>;
+    auto kern = coop_mlp_kernel<GATHER, Q1, Q2, Q3, SPLIT_OUT, RAGGED>;
     if (int rc = allow_dynamic_lds(kern, lds)) return rc;
     long long blocks = units < 512 ? units : 512;
     return launch(kern, dim3((unsigned)blocks), dim3(kMlpThreads), lds, st, p);
@@ -507,14 +579,19 @@ static int launch_gemm_last(const MlpCoopConfig &c, const CoopParams &p_in, void
     p.split = 1;
     float *final_out = p.out;
     p.out = (float *)ws;
-    if (int rc = launch_coop<kGatherGrouped, Q1, Q2, 0, true>(p, p.rows * parts, st)) return rc;
+    if (p.counts) {
+        if (int rc = launch_coop<kGatherGrouped, Q1, Q2, 0, true, true>(p, p.rows * parts, st)) return rc;
+    } else if (int rc = launch_coop<kGatherGrouped, Q1, Q2, 0, true>(p, p.rows * parts, st)) {
+        return rc;
+    }
     const size_t two_layers = (size_t)kPairWords * 4 * (size_t)(c.ti * c.q1 + 4 * c.q1 * c.q2);      // words of layers 1-2
     const float *wgemm = p.wp + two_layers, *b3 = p.bp + 32 * (size_t)(4 * (c.q1 + c.q2));
     const size_t lds = sizeof(u32x4) * 2 * kGemmStageVec + sizeof(int) * 32 * kGemmColTiles;
-    if (int rc = allow_dynamic_lds(pool_gemm_kernel, lds)) return rc;
     const long long jobs = p.rows * ((p.cout + 32 * kGemmColTiles - 1) / (32 * kGemmColTiles));
-    return launch(pool_gemm_kernel, dim3((unsigned)(jobs < 1024 ? jobs : 1024)), dim3(kGemmThreads), lds, st, parts, t2, p.cout,
-                  p.rows, (const float *)ws, wgemm, b3, final_out);
+    auto kern = !p.counts ? pool_gemm_kernel<0> : p.idx ? pool_gemm_kernel<1> : pool_gemm_kernel<2>;
+    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+    return launch(kern, dim3((unsigned)(jobs < 1024 ? jobs : 1024)), dim3(kGemmThreads), lds, st, parts, t2, p.cout,
+                  p.rows, (const float *)ws, wgemm, b3, final_out, p.counts, p.m, p.n);
 }
 
 template <int G, int Q1, int Q2, int Q3, int ROUTE>
@@ -531,6 +608,7 @@ static int launch_coop_shape(const MlpCoopConfig &c, const CoopParams &p_in, hip
             if (int rc = clear_async(p.out, sizeof(float) * (size_t)p.rows * p.cout, st)) return rc;
         }
         const long long units = fp ? (p.rows + 31) / 32 : (p.split ? p.rows * parts : p.rows);
+        if (p.counts) return launch_coop<G, Q1, Q2, Q3, false, true>(p, units, st);
         return launch_coop<G, Q1, Q2, Q3>(p, units, st);
     }
 }

@@ -39,7 +39,10 @@ __device__ __forceinline__ float fp_interp3(float p1, float p2, float p3, float 
 }
 
 // T3 == 0: two layers (layer 2 is the last one). TL = tiles of the last layer.
-template <int T1, int T2, int T3>
+// RAGGED (lengths1 (b) in device memory, include/pn2ops.h "ragged inference"): lockstep like the streamed SA kernel, so by
+// redirect and select -- a lane whose point is at or beyond its cloud's length gathers through row 0 of its own cloud (idx,
+// dist and points1 of the padding row are not read) and the row is stored as +0.0. The dense instantiations have none of it.
+template <int T1, int T2, int T3, bool RAGGED = false>
 __global__ __launch_bounds__(kMlpThreads) void fp_mlp_stream_kernel(int n, int m, int c1, int cout, long long rows,
                                                                     int ti, const float *__restrict__ pre,
                                                                     const float *__restrict__ points1,
@@ -47,7 +50,8 @@ __global__ __launch_bounds__(kMlpThreads) void fp_mlp_stream_kernel(int n, int m
                                                                     const float *__restrict__ dist,
                                                                     const float *__restrict__ wstream,
                                                                     const float *__restrict__ bpacked,
-                                                                    float *__restrict__ out)
+                                                                    float *__restrict__ out,
+                                                                    const int *__restrict__ lengths1)
 {
     constexpr int TB = T1 + T2 + T3;
     __shared__ __attribute__((aligned(16))) u32x4 wbuf[2][kStageVec];
@@ -94,8 +98,12 @@ __global__ __launch_bounds__(kMlpThreads) void fp_mlp_stream_kernel(int n, int m
         const long long g = wave + trip * nwaves;
         const long long row0 = (g < groups ? g : groups - 1) * 32;
         const bool item_ok = g < groups;
-        const long long row = min(row0 + s, rows - 1);                       // this lane's point (clamped: loads stay valid)
-        const long long cloud = row / n;
+        const long long row_own = min(row0 + s, rows - 1);                   // this lane's point (clamped: loads stay valid)
+        const long long cloud = row_own / n;
+        bool ok = true;
+        if (RAGGED) ok = (int)(row_own - cloud * n) < min(max(lengths1[cloud], 1), n);
+        const long long row = ok ? row_own : cloud * n;
+        const unsigned long long valid_rows = RAGGED ? __ballot(ok) : ~0ull;  // bit i: point row0 + i is a valid row
         // inverse-distance weights, pointnet_util.py:212-215
         const int *ip = idx + row * 3;
         const float *dp = dist + row * 3;
@@ -171,7 +179,8 @@ __global__ __launch_bounds__(kMlpThreads) void fp_mlp_stream_kernel(int n, int m
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
                     const long long r = row0 + mlp_chan(v, h);
-                    if (r < rows) out[r * cout + ch] = fmaxf(__fadd_rn(acc[v], bias), 0.0f);
+                    const float val = fmaxf(__fadd_rn(acc[v], bias), 0.0f);
+                    if (r < rows) out[r * cout + ch] = (!RAGGED || ((valid_rows >> mlp_chan(v, h)) & 1ull)) ? val : 0.0f;
                 }
             }
         };
@@ -260,18 +269,19 @@ void fp_stream_pack(const FpConfig &c, int c1, int nlayers, const int *widths, c
 }
 
 int fp_stream_launch(const FpConfig &c, long long rows, int n, int m, int c1, int cout, const float *pre, const float *points1,
-                     const int *idx, const float *dist, const float *wp, const float *bp, float *out, hipStream_t st)
+                     const int *idx, const float *dist, const float *wp, const float *bp, float *out, hipStream_t st,
+                     const int *lengths1)
 {
     decltype(&fp_mlp_stream_kernel<4, 4, 0>) kern = nullptr;
 #define PN2_FP_KERNEL(A, B, C) \
-    if (c.t1 == A && c.t2 == B && c.t3 == C) kern = fp_mlp_stream_kernel<A, B, C>;
+    if (c.t1 == A && c.t2 == B && c.t3 == C) kern = lengths1 ? fp_mlp_stream_kernel<A, B, C, true> : fp_mlp_stream_kernel<A, B, C>;
     PN2_FP_SHAPES(PN2_FP_KERNEL)
 #undef PN2_FP_KERNEL
     if (!kern) return PN2_E_TOO_LARGE;
     const long long blocks = ((rows + 31) / 32 + 3) / 4;          // four 32-point items per workgroup
     // persistent, at most one workgroup per CU: every workgroup streams the weights
     return launch(kern, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(kMlpThreads), 0, st, n, m, c1, cout, rows, c.ti, pre,
-                  points1, idx, dist, wp, bp, out);
+                  points1, idx, dist, wp, bp, out, lengths1);
 }
 
 }  // namespace pn2

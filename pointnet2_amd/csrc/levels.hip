@@ -50,3 +50,27 @@ extern "C" int pn2_fp_level(int b, int n, int m, int c2, int c1, const float *xy
     if (int rc = pn2_three_nn(b, n, m, xyz1, xyz2, dist, idx, stream)) return rc;
     return pn2_fp_mlp(b, n, m, c2, c1, points2, points1, idx, dist, nlayers, widths, kind, wpacked, bpacked, out, ws, stream);
 }
+
+// The two levels on a ragged batch (include/pn2ops.h "ragged inference"): the ragged operators one after another, each under its
+// own slice rule. No overlapped launch: its producers and consumers take no counts.
+extern "C" int pn2_sa_level_ragged(int b, int n, int m, float radius, int nsample, int cfeat, const float *xyz, const int *lengths,
+                                   const int *npoints, const float *points, int c1, int c2, int c3, const float *wpacked,
+                                   const float *bpacked, int *fps_idx, float *new_xyz, int *idx, int *pts_cnt, float *grouped_xyz,
+                                   float *out, void *ws_mlp, void *stream)
+{
+    if (int rc = pn2_farthest_point_sample_ragged_counts(b, n, m, xyz, lengths, npoints, fps_idx, new_xyz, stream)) return rc;
+    if (int rc = pn2_query_ball_group_xyz_ragged_pair(b, n, m, radius, nsample, xyz, lengths, new_xyz, npoints, 1, idx, pts_cnt,
+                                                      grouped_xyz, 0, 0, stream)) return rc;
+    return pn2_sa_mlp3_maxpool_ragged(b, n, m, nsample, cfeat, xyz, lengths, new_xyz, npoints, points, idx, c1, c2, c3, wpacked, bpacked,
+                                      out, ws_mlp, 0, stream);
+}
+
+extern "C" int pn2_fp_level_ragged(int b, int n, int m, int c2, int c1, const float *xyz1, const int *lengths1, const float *xyz2,
+                                   const int *lengths2, const float *points2, const float *points1, int nlayers, const int *widths,
+                                   int kind, const float *wpacked, const float *bpacked, float *dist, int *idx, float *out, void *ws,
+                                   void *stream)
+{
+    if (int rc = pn2_three_nn_ragged_pair(b, n, m, xyz1, lengths1, xyz2, lengths2, dist, idx, 0, stream)) return rc;
+    return pn2_fp_mlp_ragged(b, n, m, c2, c1, points2, points1, lengths1, idx, dist, nlayers, widths, kind, wpacked, bpacked, out, ws,
+                             stream);
+}

@@ -52,10 +52,13 @@ static bool sa_plan(int cin, int c1, int c2, int c3, int nsample, SaPlan &p)
     return false;
 }
 
-// pn2_sa_mlp3_maxpool_ex and pn2_sa_mlp3_pool behind their own range checks
+// pn2_sa_mlp3_maxpool_ex, pn2_sa_mlp3_pool and pn2_sa_mlp3_maxpool_ragged behind their own range checks. ragged: the counts
+// form (max pooling) -- grouped rows take npoints, the group_all form takes lengths; the plan and every launch dimension come
+// from the padded extents as in the dense call, the kernels are the families' ragged twins.
 static int sa_mlp3_run(int b, int n, int m, int nsample, int cfeat, const float *xyz, const float *new_xyz, const float *points,
                        const int *idx, int c1, int c2, int c3, const float *wpacked, const float *bpacked, float *out, void *ws,
-                       int variant, int pooling, void *stream)
+                       int variant, int pooling, void *stream, bool ragged = false, const int *lengths = nullptr,
+                       const int *npoints = nullptr)
 {
     if (b < 0 || n <= 0 || m < 0 || cfeat < 0) return PN2_E_SHAPE;
     if (nsample <= 0) return PN2_E_ARG;
@@ -65,6 +68,9 @@ static int sa_mlp3_run(int b, int n, int m, int nsample, int cfeat, const float 
     const bool group_all = pooling == 0 && !idx && !new_xyz;
     if (group_all && (m != 1 || nsample != n)) return PN2_E_ARG;
     if (!xyz || (!group_all && (!new_xyz || !idx)) || !wpacked || !bpacked || !out || (cfeat > 0 && !points)) return PN2_E_NULL;
+    if (ragged && group_all && npoints) return PN2_E_ARG;
+    if (ragged && !(group_all ? lengths : npoints)) return PN2_E_NULL;
+    const int *counts = !ragged ? nullptr : group_all ? lengths : npoints;      // (grouped rows: lengths is not needed, idx stays below it)
     SaPlan p;
     if (!sa_plan(3 + cfeat, c1, c2, c3, nsample, p)) return PN2_E_TOO_LARGE;
     // only the cooperative kernel gathers without idx, and only the other two pool by anything but the maximum
@@ -73,12 +79,12 @@ static int sa_mlp3_run(int b, int n, int m, int nsample, int cfeat, const float 
     const float *pts = cfeat > 0 ? points : nullptr;
     switch (p.family) {
     case kSaResident:
-        return mlp_resident_launch(p.rc, b, n, m, nsample, cfeat, c3, xyz, new_xyz, pts, idx, wpacked, bpacked, out, st, variant, pooling);
+        return mlp_resident_launch(p.rc, b, n, m, nsample, cfeat, c3, xyz, new_xyz, pts, idx, wpacked, bpacked, out, st, variant, pooling, counts);
     case kSaStreamed:
-        return mlp_stream_launch(p.sc, b, n, m, nsample, cfeat, c3, xyz, new_xyz, pts ? pts : xyz, idx, wpacked, bpacked, out, ws, st, pooling);
+        return mlp_stream_launch(p.sc, b, n, m, nsample, cfeat, c3, xyz, new_xyz, pts ? pts : xyz, idx, wpacked, bpacked, out, ws, st, pooling, counts);
     default: {
         CoopParams cp = {n, m, nsample, cfeat, 0, c3, p.cc.ti, (long long)b * m, xyz, new_xyz, pts, nullptr, idx, nullptr,
-                         wpacked, bpacked, out, 0};
+                         wpacked, bpacked, out, 0, counts};
         return mlp_coop_launch(p.cc, 0, cp, st, ws);
     }
     }
@@ -202,6 +208,16 @@ extern "C" int pn2_sa_mlp3_maxpool_ex(int b, int n, int m, int nsample, int cfea
     return pn2::sa_mlp3_run(b, n, m, nsample, cfeat, xyz, new_xyz, points, idx, c1, c2, c3, wpacked, bpacked, out, ws, variant, 0, stream);
 }
 
+extern "C" int pn2_sa_mlp3_maxpool_ragged(int b, int n, int m, int nsample, int cfeat, const float *xyz, const int *lengths,
+                                          const float *new_xyz, const int *npoints, const float *points, const int *idx, int c1,
+                                          int c2, int c3, const float *wpacked, const float *bpacked, float *out, void *ws,
+                                          int variant, void *stream)
+{
+    if (variant < 0 || variant > 3) return PN2_E_ARG;
+    return pn2::sa_mlp3_run(b, n, m, nsample, cfeat, xyz, new_xyz, points, idx, c1, c2, c3, wpacked, bpacked, out, ws, variant, 0, stream,
+                            true, lengths, npoints);
+}
+
 extern "C" int pn2_sa_mlp3_pool_supported(int cin, int c1, int c2, int c3, int nsample, int pooling)
 {
     using namespace pn2;
@@ -270,9 +286,33 @@ extern "C" int pn2_fp_mlp_pack(int c2, int c1, int nlayers, const int *widths, i
     return PN2_OK;
 }
 
+namespace pn2 {
+static int fp_mlp_run(int b, int n, int m, int c2, int c1, const float *points2, const float *points1, const int *idx,
+                      const float *dist, int nlayers, const int *widths, int kind, const float *wpacked, const float *bpacked,
+                      float *out, void *ws, void *stream, bool ragged, const int *lengths1);
+}
+
 extern "C" int pn2_fp_mlp(int b, int n, int m, int c2, int c1, const float *points2, const float *points1, const int *idx,
                           const float *dist, int nlayers, const int *widths, int kind, const float *wpacked,
                           const float *bpacked, float *out, void *ws, void *stream)
+{
+    return pn2::fp_mlp_run(b, n, m, c2, c1, points2, points1, idx, dist, nlayers, widths, kind, wpacked, bpacked, out, ws, stream, false,
+                           nullptr);
+}
+
+extern "C" int pn2_fp_mlp_ragged(int b, int n, int m, int c2, int c1, const float *points2, const float *points1, const int *lengths1,
+                                 const int *idx, const float *dist, int nlayers, const int *widths, int kind, const float *wpacked,
+                                 const float *bpacked, float *out, void *ws, void *stream)
+{
+    return pn2::fp_mlp_run(b, n, m, c2, c1, points2, points1, idx, dist, nlayers, widths, kind, wpacked, bpacked, out, ws, stream, true,
+                           lengths1);
+}
+
+// pn2_fp_mlp (ragged == false) and pn2_fp_mlp_ragged (lengths1 required): Q = points2 . W1a for every known row either way
+// (rows of points2 beyond a cloud's known count are multiplied and never gathered), then the family's dense kernel or its twin
+int pn2::fp_mlp_run(int b, int n, int m, int c2, int c1, const float *points2, const float *points1, const int *idx,
+                           const float *dist, int nlayers, const int *widths, int kind, const float *wpacked, const float *bpacked,
+                           float *out, void *ws, void *stream, bool ragged, const int *lengths1)
 {
     using namespace pn2;
     if (b < 0 || n < 0 || m <= 0 || c2 <= 0 || c1 < 0) return PN2_E_SHAPE;
@@ -283,6 +323,7 @@ extern "C" int pn2_fp_mlp(int b, int n, int m, int c2, int c1, const float *poin
     const long long rows = (long long)b * n;
     if (rows == 0) return PN2_OK;
     if (!points2 || (c1 > 0 && !points1) || !idx || !dist || !wpacked || !bpacked || !out || !ws) return PN2_E_NULL;
+    if (ragged && !lengths1) return PN2_E_NULL;
     if ((long long)m * c2 > INT_MAX) return PN2_E_TOO_LARGE;
     const int cout = widths[nlayers - 1];
     hipStream_t st = as_stream(stream);
@@ -290,8 +331,8 @@ extern "C" int pn2_fp_mlp(int b, int n, int m, int c2, int c1, const float *poin
     if (int rc = fp_point_layer(p.tiles[1], (long long)b * m, c2, p.tif, points2, wpacked + p.wpoint, bpacked + p.zeros, pre, st)) return rc;
     if (p.family == kFpCooperative) {
         CoopParams cp = {n, m, 0, c2, c1, cout, p.cc.ti, rows, nullptr, nullptr, pre, c1 > 0 ? points1 : nullptr, idx, dist,
-                         wpacked, bpacked, out, 0};
+                         wpacked, bpacked, out, 0, ragged ? lengths1 : nullptr};
         return mlp_coop_launch(p.cc, 1, cp, st, nullptr);
     }
-    return fp_stream_launch(p.fc, rows, n, m, c1, cout, pre, points1, idx, dist, wpacked, bpacked, out, st);
+    return fp_stream_launch(p.fc, rows, n, m, c1, cout, pre, points1, idx, dist, wpacked, bpacked, out, st, ragged ? lengths1 : nullptr);
 }

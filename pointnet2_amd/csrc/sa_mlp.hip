@@ -104,15 +104,22 @@ __device__ __forceinline__ void mlp_layer(const float *wp, const float *bp, cons
 // samples of one channel, the sums of registers 0-7 and 8-15 are kept apart (SPAN = 16: two centroids), one exchange with
 // lane l ^ 32 at the end. The weights of mode 2 come from the layer-1 operand (lanes 0-31 hold their sample's centred
 // coordinates) through one ds_bpermute per register and 32-sample part.
-template <int T1, int T2, int T3, int SPAN, int NT, int POOL = 0>
+// RAGGED (max pooling only; npoints (b) in device memory, include/pn2ops.h "ragged inference"): centroid row j of cloud c is
+// padding when j >= clamp(npoints[c], 1, m). A lane whose row is padding gathers through row 0 of its own cloud (always valid:
+// finite arithmetic, nothing of the padding row is dereferenced) and its pooled result is stored as +0.0; at SPAN = 16 the two
+// rows of an item are judged apart (with an odd m they belong to different clouds). An item that is padding only is left
+// before its gather and its MFMAs. The dense instantiations have none of it.
+template <int T1, int T2, int T3, int SPAN, int NT, int POOL = 0, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void sa_mlp3_kernel(int n, int m, int nsample, int cfeat, int c3, long long rows,
                                                               const float *__restrict__ xyz,
                                                               const float *__restrict__ new_xyz,
                                                               const float *__restrict__ points,
                                                               const int *__restrict__ idx,
                                                               const float *__restrict__ wpacked,
-                                                              const float *__restrict__ bpacked, float *__restrict__ out)
+                                                              const float *__restrict__ bpacked, float *__restrict__ out,
+                                                              const int *__restrict__ npoints)
 {
+    static_assert(!RAGGED || POOL == 0, "counts: max pooling only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *w1 = reinterpret_cast<float *>(smem);
     float *w2 = w1 + mlp_w_floats(T1, 1);
@@ -147,15 +154,42 @@ __global__ __launch_bounds__(NT) void sa_mlp3_kernel(int n, int m, int nsample, 
         const long long r = SPAN == 32 ? g : g * 2 + (s >> 4);
         return r < rows ? r : rows - 1;                          // an odd tail at nsample = 16 recomputes the last row
     };
+    // RAGGED: is row r (< rows) below its cloud's count, and the row a lane gathers through
+    auto row_valid = [&](long long r) -> bool {
+        const long long cloud = r / m;
+        return (int)(r - cloud * m) < min(max(npoints[cloud], 1), m);
+    };
+    auto gather_row = [&](long long g) -> long long {
+        const long long r = item_row(g);
+        if (!RAGGED) return r;
+        return row_valid(r) ? r : r / m * m;
+    };
+    auto item_padding = [&](long long g) -> bool {              // wave-uniform: every row of the item is padding
+        if (SPAN == 32) return !row_valid(g);
+        return !row_valid(2 * g) && (2 * g + 1 >= rows || !row_valid(2 * g + 1));
+    };
+    auto store_zeros = [&](long long g) {
+#pragma unroll
+        for (int t = 0; t < T3; ++t) {
+            const int ch = 32 * t + s;
+            if (h == 0 && ch < c3) {
+                if (SPAN == 32) out[g * c3 + ch] = 0.0f;
+                else {
+                    out[(2 * g) * c3 + ch] = 0.0f;
+                    if (2 * g + 1 < rows) out[(2 * g + 1) * c3 + ch] = 0.0f;
+                }
+            }
+        }
+    };
     auto load_index = [&](long long g, int part) -> int {
         const int sample = SPAN == 32 ? part * 32 + s : (s & 15);
-        return idx[item_row(g) * nsample + sample];
+        return idx[gather_row(g) * nsample + sample];
     };
     // layer-1 operand: register v <- input channel mlp_chan(v, h) of this lane's sample. The loads only
     // (raw coordinates; `cen` = the centroid coordinate to subtract, 0 for feature channels): the
     // subtraction is done when the operand is consumed, one item later, so no wait sits in the MFMA stream
     auto load_x0 = [&](long long g, int p, f32x16 &cen) -> f32x16 {
-        const long long row = item_row(g), cloud = row / m;
+        const long long row = gather_row(g), cloud = row / m;
         const float *px = xyz + ((size_t)cloud * n + p) * 3;
         const float *pf = points ? points + ((size_t)cloud * n + p) * cfeat : nullptr;
         const float *c = new_xyz + row * 3;
@@ -186,13 +220,19 @@ __global__ __launch_bounds__(NT) void sa_mlp3_kernel(int n, int m, int nsample, 
     long long g = wave;
     int part = 0;
     f32x16 x0, cen;
+    if (RAGGED) {
+        while (g < groups && item_padding(g)) { store_zeros(g); g += nwaves; }
+    }
     if (g < groups) x0 = load_x0(g, load_index(g, 0), cen);
     f32x16 best[T3];
     float sa[T3], sb[T3], ma[T3], mb[T3], ea = 0.0f, eb = 0.0f;      // POOL != 0: sums / maxima of registers 0-7 and 8-15, weight sums
     while (g < groups) {
         // the item after this one
         const bool last_part = part + 1 == parts;
-        const long long gn = last_part ? g + nwaves : g;
+        long long gn = last_part ? g + nwaves : g;
+        if (RAGGED && last_part) {                               // items of padding only: their zeros, no gather, no MFMAs
+            while (gn < groups && item_padding(gn)) { store_zeros(gn); gn += nwaves; }
+        }
         const int partn = last_part ? 0 : part + 1;
         const bool more = gn < groups;
         int pn = 0;
@@ -301,7 +341,7 @@ __global__ __launch_bounds__(NT) void sa_mlp3_kernel(int n, int m, int nsample, 
 #pragma unroll
                 for (int v = 1; v < 16; ++v) mx = fmaxf(mx, best[t][v]);
                 mx = fmaxf(mx, __shfl_xor(mx, 32));
-                if (h == 0 && ch < c3) out[row * c3 + ch] = fmaxf(__fadd_rn(mx, bias), 0.0f);
+                if (h == 0 && ch < c3) out[row * c3 + ch] = fmaxf(__fadd_rn(mx, bias), 0.0f);      // (RAGGED: the item is a valid row)
             } else {
                 float m0 = best[t][0], m1 = best[t][8];
 #pragma unroll
@@ -309,8 +349,9 @@ __global__ __launch_bounds__(NT) void sa_mlp3_kernel(int n, int m, int nsample, 
                 m0 = fmaxf(m0, __shfl_xor(m0, 32));
                 m1 = fmaxf(m1, __shfl_xor(m1, 32));
                 if (h == 0 && ch < c3) {
-                    out[(2 * g) * c3 + ch] = fmaxf(__fadd_rn(m0, bias), 0.0f);
-                    if (2 * g + 1 < rows) out[(2 * g + 1) * c3 + ch] = fmaxf(__fadd_rn(m1, bias), 0.0f);
+                    const float v0 = fmaxf(__fadd_rn(m0, bias), 0.0f), v1 = fmaxf(__fadd_rn(m1, bias), 0.0f);
+                    out[(2 * g) * c3 + ch] = (!RAGGED || row_valid(2 * g)) ? v0 : 0.0f;
+                    if (2 * g + 1 < rows) out[(2 * g + 1) * c3 + ch] = (!RAGGED || row_valid(2 * g + 1)) ? v1 : 0.0f;
                 }
             }
         }
@@ -408,12 +449,14 @@ __device__ __forceinline__ void mlp_layer_host(const float *wp, const float *bp,
     }
 }
 
-template <int T1, int T2, int T3, int SPAN, int NT>
+// RAGGED: as in sa_mlp3_kernel, by redirect and select only -- the two items of a wave advance together through one
+// schedule of hosts and guests, so an item of padding only runs on row 0 of its cloud and stores +0.0.
+template <int T1, int T2, int T3, int SPAN, int NT, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void sa_mlp3_pair_kernel(int n, int m, int nsample, int cfeat, int c3, long long rows,
                                                            const float *__restrict__ xyz, const float *__restrict__ new_xyz,
                                                            const float *__restrict__ points, const int *__restrict__ idx,
                                                            const float *__restrict__ wpacked, const float *__restrict__ bpacked,
-                                                           float *__restrict__ out)
+                                                           float *__restrict__ out, const int *__restrict__ npoints)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *w1 = reinterpret_cast<float *>(smem);
@@ -443,13 +486,22 @@ __global__ __launch_bounds__(NT) void sa_mlp3_pair_kernel(int n, int m, int nsam
         const long long r = SPAN == 32 ? g : g * 2 + (s >> 4);
         return r < rows ? r : rows - 1;
     };
+    auto row_valid = [&](long long r) __attribute__((always_inline)) -> bool {
+        const long long cloud = r / m;
+        return (int)(r - cloud * m) < min(max(npoints[cloud], 1), m);
+    };
+    auto gather_row = [&](long long g) __attribute__((always_inline)) -> long long {
+        const long long r = item_row(g);
+        if (!RAGGED) return r;
+        return row_valid(r) ? r : r / m * m;
+    };
     auto load_index = [&](long long g) __attribute__((always_inline)) -> int {
         const int sample = SPAN == 32 ? s : (s & 15);
-        return idx[item_row(g) * nsample + sample];
+        return idx[gather_row(g) * nsample + sample];
     };
     // layer-1 operand registers 0 .. 7 of this lane's sample (channels mlp_chan(v, h)) and what to subtract from them
     auto load_x0 = [&](long long g, int p, float (&x0)[8], float (&cen)[8]) __attribute__((always_inline)) {
-        const long long row = item_row(g), cloud = row / m;
+        const long long row = gather_row(g), cloud = row / m;
         const float *px = xyz + ((size_t)cloud * n + p) * 3;
         const float *c = new_xyz + row * 3;
         if (!points) {                                   // xyz only: channels 0-2 live in registers 0-2 of lanes 0-31
@@ -497,7 +549,10 @@ __global__ __launch_bounds__(NT) void sa_mlp3_pair_kernel(int n, int m, int nsam
 #pragma unroll
             for (int v = 1; v < 16; ++v) mx = fmaxf(mx, best[t][v]);
             mx = fmaxf(mx, __shfl_xor(mx, 32));
-            if (live) out[row * c3 + ch] = fmaxf(__fadd_rn(mx, bias), 0.0f);
+            if (live) {
+                const float val = fmaxf(__fadd_rn(mx, bias), 0.0f);
+                out[row * c3 + ch] = (!RAGGED || row_valid(row)) ? val : 0.0f;
+            }
         } else {
             float m0 = best[t][0], m1 = best[t][8];
             asm volatile("" : "+v"(m0), "+v"(m1));
@@ -506,8 +561,9 @@ __global__ __launch_bounds__(NT) void sa_mlp3_pair_kernel(int n, int m, int nsam
             m0 = fmaxf(m0, __shfl_xor(m0, 32));
             m1 = fmaxf(m1, __shfl_xor(m1, 32));
             if (live) {
-                out[(2 * g) * c3 + ch] = fmaxf(__fadd_rn(m0, bias), 0.0f);
-                if (2 * g + 1 < rows) out[(2 * g + 1) * c3 + ch] = fmaxf(__fadd_rn(m1, bias), 0.0f);
+                const float v0 = fmaxf(__fadd_rn(m0, bias), 0.0f), v1 = fmaxf(__fadd_rn(m1, bias), 0.0f);
+                out[(2 * g) * c3 + ch] = (!RAGGED || row_valid(2 * g)) ? v0 : 0.0f;
+                if (2 * g + 1 < rows) out[(2 * g + 1) * c3 + ch] = (!RAGGED || row_valid(2 * g + 1)) ? v1 : 0.0f;
             }
         }
     };
@@ -613,7 +669,7 @@ void mlp_resident_pack(const MlpResidentConfig &c, int cin, int c1, int c2, int 
 template <int T1, int T2, int T3>
 static int launch_mlp(int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz, const float *new_xyz,
                       const float *points, const int *idx, const float *wp, const float *bp, float *out, hipStream_t st, int variant,
-                      int pooling = 0)
+                      int pooling, const int *npoints)
 {
     const size_t lds = resident_lds_bytes({T1, T2, T3});
     if (lds > (size_t)kMlpMaxLds) return PN2_E_TOO_LARGE;
@@ -633,8 +689,20 @@ static int launch_mlp(int b, int n, int m, int nsample, int cfeat, int c3, const
         const long long blocks = (groups + per_block - 1) / per_block;
         if (int rc = allow_dynamic_lds(kern, lds)) return rc;
         return launch(kern, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(threads), lds, st, n, m, nsample, cfeat, c3, rows, xyz,
-                      new_xyz, points, idx, wp, bp, out);
+                      new_xyz, points, idx, wp, bp, out, npoints);
     };
+    if (npoints) {
+        // the ragged twins: the dense choice above (from the padded extents), max pooling only
+        if (pooling != 0) return PN2_E_ARG;
+        if (pair_ok && variant >= 2) {
+            if constexpr (T2 <= 2) {
+                if (variant == 2)
+                    return run(half ? sa_mlp3_pair_kernel<T1, T2, T3, 16, 256, true> : sa_mlp3_pair_kernel<T1, T2, T3, 32, 256, true>, 256, 2);
+                return run(half ? sa_mlp3_pair_kernel<T1, T2, T3, 16, 512, true> : sa_mlp3_pair_kernel<T1, T2, T3, 32, 512, true>, 512, 2);
+            }
+        }
+        return run(half ? sa_mlp3_kernel<T1, T2, T3, 16, 512, 0, true> : sa_mlp3_kernel<T1, T2, T3, 32, 512, 0, true>, 512, 1);
+    }
     if (pooling != 0) {
         // avg / weighted_avg / max_and_avg (pointnet_util.py:130-140): one item per wave, eight waves (sa_mlp3_kernel<.., POOL>)
 #define PN2_POOL_CASE(P) \
@@ -658,11 +726,11 @@ static int launch_mlp(int b, int n, int m, int nsample, int cfeat, int c3, const
 
 int mlp_resident_launch(const MlpResidentConfig &c, int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz,
                         const float *new_xyz, const float *points, const int *idx, const float *wp, const float *bp,
-                        float *out, hipStream_t st, int variant, int pooling)
+                        float *out, hipStream_t st, int variant, int pooling, const int *npoints)
 {
 #define PN2_RESIDENT_LAUNCH(A, B, C)                 \
     if (c.t1 == A && c.t2 == B && c.t3 == C)         \
-        return launch_mlp<A, B, C>(b, n, m, nsample, cfeat, c3, xyz, new_xyz, points, idx, wp, bp, out, st, variant, pooling);
+        return launch_mlp<A, B, C>(b, n, m, nsample, cfeat, c3, xyz, new_xyz, points, idx, wp, bp, out, st, variant, pooling, npoints);
     PN2_RESIDENT_SHAPES(PN2_RESIDENT_LAUNCH)
 #undef PN2_RESIDENT_LAUNCH
     return PN2_E_TOO_LARGE;

@@ -127,7 +127,9 @@ void mlp_resident_pack(const MlpResidentConfig &c, int cin, int c1, int c2, int 
 // variant: 0 by the size rule, 1 one item per wave, 2 / 3 two items per wave (four / eight waves per workgroup)
 int mlp_resident_launch(const MlpResidentConfig &c, int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz,
                         const float *new_xyz, const float *points, const int *idx, const float *wp, const float *bp,
-                        float *out, hipStream_t st, int variant, int pooling = 0);
+                        float *out, hipStream_t st, int variant, int pooling = 0, const int *npoints = nullptr);
+// npoints / lengths1 (b ints in device memory) select the ragged twins of the kernels (include/pn2ops.h "ragged inference");
+// nullptr: the dense kernels
 
 // ---- streamed variant (sa_mlp_stream.hip) ------------------------------------------------------------
 constexpr int kMlpStagePairs = 4;          // 32x32 weight tile pairs per LDS stage (24 KiB in three-level form)
@@ -162,7 +164,7 @@ void mlp_stream_pack(const MlpStreamConfig &c, int cin, int c1, int c2, int c3, 
                      const float *const *bs, float *wpacked, float *bpacked);
 int mlp_stream_launch(const MlpStreamConfig &c, int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz,
                       const float *new_xyz, const float *points, const int *idx, const float *wp, const float *bp,
-                      float *out, void *ws, hipStream_t st, int pooling = 0);
+                      float *out, void *ws, hipStream_t st, int pooling = 0, const int *npoints = nullptr);
 
 int point_layer_launch(int t1, int cfeat, long long rows, int tif, const float *points, const float *wstream,
                        const float *bias, float *pre, int out_stride, int col0, hipStream_t st);
@@ -185,6 +187,8 @@ struct CoopParams {
     const float *wp, *bp;
     float *out;
     int split;                                        // set by mlp_coop_launch
+    const int *counts;                                // ragged twins (nullptr: the dense kernels): SA npoints (b), group_all lengths (b),
+                                                      // FP lengths1 (b); device memory, clamped where they are read
 };
 bool mlp_coop_pick(int cin, int nlayers, const int *widths, MlpCoopConfig &cfg);
 bool mlp_coop_has_kernel(const MlpCoopConfig &c, int fp);
@@ -203,6 +207,7 @@ size_t fp_stream_b_floats(const FpConfig &c);
 void fp_stream_pack(const FpConfig &c, int c1, int nlayers, const int *widths, const int *skip_row, const float *const *ws,
                     const float *const *bs, float *wpacked, float *bpacked);
 int fp_stream_launch(const FpConfig &c, long long rows, int n, int m, int c1, int cout, const float *pre, const float *points1,
-                     const int *idx, const float *dist, const float *wp, const float *bp, float *out, hipStream_t st);
+                     const int *idx, const float *dist, const float *wp, const float *bp, float *out, hipStream_t st,
+                     const int *lengths1 = nullptr);
 
 }  // namespace pn2

@@ -251,7 +251,11 @@ __global__ __launch_bounds__(256) void point_layer_few_rows_kernel(int cfeat, lo
 
 // POOL: 0 max, 1 avg, 2 weighted_avg, 3 max_and_avg (utils/pointnet_util.py:128-140; see sa_mlp3_kernel in sa_mlp.hip: modes 1-3
 // apply bias + ReLU per sample and keep a running (weighted) sum per lane and output tile beside / instead of the raw maximum)
-template <int T1, int T2, int T3, int POOL = 0>
+// RAGGED (max pooling only; npoints (b) in device memory, include/pn2ops.h "ragged inference"): the waves of a workgroup walk
+// their trips in lockstep behind the stream's barriers, so a padding row keeps every stage, barrier and MFMA of its trip: it
+// gathers through row 0 of its own cloud (nothing of the padding row is dereferenced, the arithmetic stays finite) and stores
+// +0.0. The dense instantiations have none of it.
+template <int T1, int T2, int T3, int POOL = 0, bool RAGGED = false>
 __global__ __launch_bounds__(kStreamThreads) void sa_mlp3_stream_kernel(int n, int m, int nsample, int c3, long long rows,
                                                                        const float *__restrict__ xyz,
                                                                        const float *__restrict__ new_xyz,
@@ -260,8 +264,10 @@ __global__ __launch_bounds__(kStreamThreads) void sa_mlp3_stream_kernel(int n, i
                                                                        const float *__restrict__ wstream,
                                                                        const float *__restrict__ wxyz,
                                                                        const float *__restrict__ bpacked,
-                                                                       float *__restrict__ out)
+                                                                       float *__restrict__ out,
+                                                                       const int *__restrict__ npoints)
 {
+    static_assert(!RAGGED || POOL == 0, "counts: max pooling only");
     __shared__ __attribute__((aligned(16))) u32x4 wbuf[2][kStageVec];
     __shared__ __attribute__((aligned(16))) u32x4 wx_s[T1 * kXyzVec];     // layer 1's xyz rows: [t][level][lane]
     __shared__ float bias_s[(T2 + T3) * 32];
@@ -286,8 +292,11 @@ __global__ __launch_bounds__(kStreamThreads) void sa_mlp3_stream_kernel(int n, i
     for (long long trip = 0; trip < trips; ++trip) {
         const long long row_raw = wave + trip * nwaves;
         const bool row_ok = row_raw < rows;
-        const long long row = row_ok ? row_raw : rows - 1;
-        const long long cloud = row / m;
+        const long long row_own = row_ok ? row_raw : rows - 1;
+        const long long cloud = row_own / m;
+        bool valid = true;                           // RAGGED: this wave's centroid is below its cloud's count
+        if (RAGGED) valid = (int)(row_own - cloud * m) < min(max(npoints[cloud], 1), m);
+        const long long row = valid ? row_own : cloud * m;
         const float *c = new_xyz + row * 3;
         const float cx = c[0], cy = c[1], cz = c[2];
         float best[T3];
@@ -403,7 +412,8 @@ __global__ __launch_bounds__(kStreamThreads) void sa_mlp3_stream_kernel(int n, i
         for (int t = 0; t < T3; ++t) {
             const int ch = 32 * t + s;
             const float mx = fmaxf(best[t], __shfl_xor(best[t], 32));
-            if (h == 0 && ch < c3 && row_ok) out[row * c3 + ch] = fmaxf(__fadd_rn(mx, b3_at(b3, ch)), 0.0f);
+            const float val = fmaxf(__fadd_rn(mx, b3_at(b3, ch)), 0.0f);
+            if (h == 0 && ch < c3 && row_ok) out[row_own * c3 + ch] = valid ? val : 0.0f;
         }
     }
 }
@@ -504,7 +514,7 @@ int point_layer_few_rows_launch(int tiles, int cfeat, long long rows, int tif, c
 template <int T1, int T2, int T3>
 static int launch_stream(const MlpStreamConfig &c, int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz,
                          const float *new_xyz, const float *points, const int *idx, const float *wp, const float *bp,
-                         float *out, float *pre, hipStream_t st, int pooling)
+                         float *out, float *pre, hipStream_t st, int pooling, const int *counts)
 {
     const long long cap = 256;                           // one workgroup (one weight stream) per CU
     const long long npoints = (long long)b * n;
@@ -524,7 +534,12 @@ static int launch_stream(const MlpStreamConfig &c, int b, int n, int m, int nsam
 #define PN2_STREAM_POOL(P)                                                                                                   \
     if (pooling == P)                                                                                                        \
         return launch((sa_mlp3_stream_kernel<T1, T2, T3, P>), dim3((unsigned)blocks), dim3(kStreamThreads), 0, st, n, m, nsample, c3, \
-                      rows, xyz, new_xyz, (const float *)pre, idx, wp, wxyz, bp, out);
+                      rows, xyz, new_xyz, (const float *)pre, idx, wp, wxyz, bp, out, counts);
+    if (counts) {
+        if (pooling != 0) return PN2_E_ARG;
+        return launch((sa_mlp3_stream_kernel<T1, T2, T3, 0, true>), dim3((unsigned)blocks), dim3(kStreamThreads), 0, st, n, m, nsample, c3,
+                      rows, xyz, new_xyz, (const float *)pre, idx, wp, wxyz, bp, out, counts);
+    }
     PN2_STREAM_POOL(0) PN2_STREAM_POOL(1) PN2_STREAM_POOL(2) PN2_STREAM_POOL(3)
 #undef PN2_STREAM_POOL
     return PN2_E_ARG;
@@ -532,13 +547,13 @@ static int launch_stream(const MlpStreamConfig &c, int b, int n, int m, int nsam
 
 int mlp_stream_launch(const MlpStreamConfig &c, int b, int n, int m, int nsample, int cfeat, int c3, const float *xyz,
                       const float *new_xyz, const float *points, const int *idx, const float *wp, const float *bp,
-                      float *out, void *ws, hipStream_t st, int pooling)
+                      float *out, void *ws, hipStream_t st, int pooling, const int *npoints)
 {
     if (nsample <= 0 || nsample % 32 != 0) return PN2_E_ARG;
     if (!ws) return PN2_E_NULL;
 #define PN2_STREAM_LAUNCH(A, B, C)                   \
     if (c.t1 == A && c.t2 == B && c.t3 == C)         \
-        return launch_stream<A, B, C>(c, b, n, m, nsample, cfeat, c3, xyz, new_xyz, points, idx, wp, bp, out, (float *)ws, st, pooling);
+        return launch_stream<A, B, C>(c, b, n, m, nsample, cfeat, c3, xyz, new_xyz, points, idx, wp, bp, out, (float *)ws, st, pooling, npoints);
     PN2_STREAM_SHAPES(PN2_STREAM_LAUNCH)
 #undef PN2_STREAM_LAUNCH
     return PN2_E_TOO_LARGE;

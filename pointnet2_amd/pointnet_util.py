@@ -311,6 +311,11 @@ class PointnetSAModule(nn.Module):
         # a group_all level accepts lengths= (per-cloud point counts; _forward_all_ragged): the group is the cloud's VALID rows.
         # Without it group_all refuses lengths. Opt-in.
         self.ragged_group_all = False
+        # eval() with lengths= / npoints= (/ lengths1=): the fused inference kernels with the counts inside
+        # (pn2_*_ragged, include/pn2ops.h "ragged inference") instead of the dense kernels on every row and a torch.where behind
+        # them: padding rows are neither gathered nor computed where a kernel can skip them, a level without a geometry is ONE
+        # C call; last_path "fused_ragged". Where the dense fused route would run (_fused_ok / _fused_kind), max pooling. Opt-in.
+        self.fused_ragged_eval = False
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
@@ -458,6 +463,11 @@ class PointnetSAModule(nn.Module):
         lengths = ragged_lengths(lengths, b, xyz.device)
         valid = _valid_rows(lengths, b, n, xyz.device, "lengths")               # (b, n)
         new_xyz, idx = _all_in_one_group(xyz)
+        if self.fused_ragged_eval and self.pooling == "max" and self._train_mode(xyz, points) is None and self._fused_ok(xyz, points):
+            # the cooperative kernel on each cloud's first lengths[c] rows (the padded n chooses the kernel): one launch
+            self.last_path = "fused_ragged"
+            out = sa_mlp.sa_mlp_maxpool(xyz, None, points, None, self._packed(xyz.device, n), lengths=lengths)
+            return new_xyz, self._post(out), idx
         if self.training and self.pooling == "max" and self.mlp2 is None and \
                 _ragged_train_ok(self, [(self.mlp.net, n)], True, xyz, points):
             self.last_path = "fused_train_ragged"
@@ -503,6 +513,13 @@ class PointnetSAModule(nn.Module):
         if not self.training:
             mode = self._train_mode(xyz, points)
             fused = mode is None and self._fused_ok(xyz, points)
+            if fused and self.fused_ragged_eval and self.pooling == "max":
+                # the counts inside the kernel: padding centroids are not gathered and come back as +0.0 (mlp2 maps a zero row to
+                # its bias, so the zeroing stays behind _post)
+                self.last_path = "fused_ragged"
+                new_xyz, idx = g.new_xyz_for(xyz), g.idx
+                out = sa_mlp.sa_mlp_maxpool(xyz, new_xyz, points, idx, self._packed(xyz.device), npoints=npoints)
+                return new_xyz, (out if self.mlp2 is None else _zero_padding_rows(self._post(out), valid)), idx
             new_xyz, out, idx = self._forward_on(xyz, points, g, mode or ("fused" if fused else "unfused"))
             return new_xyz, _zero_padding_rows(out, valid), idx
         if self.pooling == "max" and self.mlp2 is None and _ragged_train_ok(self, [(self.mlp.net, g.idx.shape[2])], False, xyz, points):
@@ -548,6 +565,17 @@ class PointnetSAModule(nn.Module):
             if npoints is not None or not self.ragged_group_all:
                 raise ValueError("group_all with lengths: the group would contain the padding rows")
             return self._forward_all_ragged(xyz, points, lengths)
+        if (lengths is not None or npoints is not None) and geometry is None and self.fused_ragged_eval and not self.knn and \
+                self.pooling == "max" and self._train_mode(xyz, points) is None and self._fused_ok(xyz, points):
+            # ONE C call (csrc/levels.hip: pn2_sa_level_ragged), full counts for a dense side
+            self.last_path = "fused_ragged"
+            new_xyz, out, idx, _, _, _ = sa_mlp.sa_level_ragged(self.npoint, self.radius, self.nsample, xyz, points,
+                                                                 self._packed(xyz.device), lengths, npoints, self._level_buffers())
+            if self.mlp2 is not None:
+                out = self._post(out)
+                if npoints is not None:
+                    out = _zero_padding_rows(out, _valid_rows(npoints, xyz.shape[0], self.npoint, xyz.device))
+            return new_xyz, out, idx
         if npoints is not None:
             g = geometry.wait() if geometry is not None else self.geometry(xyz, lengths=lengths, npoints=npoints)
             return self._forward_counts(xyz, points, g, npoints)
@@ -633,6 +661,11 @@ class PointnetSAModuleMSG(nn.Module):
         # training with npoints=: one fused node with a row mask per scale instead of the compacting layer-by-layer path; see
         # PointnetSAModule.fused_ragged_train. last_path "fused_train_ragged". Opt-in.
         self.fused_ragged_train = False
+        # eval() with lengths= / npoints= (/ lengths1=): the fused inference kernels with the counts inside
+        # (pn2_*_ragged, include/pn2ops.h "ragged inference") instead of the dense kernels on every row and a torch.where behind
+        # them: padding rows are neither gathered nor computed where a kernel can skip them, a level without a geometry is ONE
+        # C call; last_path "fused_ragged". Where the dense fused route would run (_fused_ok / _fused_kind), max pooling. Opt-in.
+        self.fused_ragged_eval = False
         self.last_path = None
         self._pack_cache = {}
 
@@ -769,6 +802,12 @@ class PointnetSAModuleMSG(nn.Module):
         b, m = xyz.shape[0], self.npoint
         valid = _valid_rows(npoints, b, m, xyz.device)
         if not self.training:
+            if self.fused_ragged_eval and self._fused_ok(xyz, points):
+                # one fused kernel with the counts inside per scale: padding centroids are skipped and stored as +0.0
+                self.last_path = "fused_ragged"
+                outs = [sa_mlp.sa_mlp_maxpool(xyz, g.new_xyz, points, idx, self._packed(si, xyz.device), npoints=npoints)
+                        for si, idx in enumerate(g.idx)]
+                return g.new_xyz, torch.cat(outs, dim=2)
             new_xyz, out = self._forward_on_geometry(xyz, points, g)
             return new_xyz, _zero_padding_rows(out, valid)
         if _ragged_train_ok(self, [(mlp.net, idx.shape[2]) for mlp, idx in zip(self.mlps, g.idx)], False, xyz, points):
@@ -839,6 +878,11 @@ class PointnetFPModule(nn.Module):
         # 0.64 ms and 288 -> 231 MB peak; part_seg FP3 0.525-0.530 -> 0.521-0.524 ms, which is within the spread of the medians
         # -- NOT faster there -- and 158 -> 132 MB peak. Folding it into the size rule is a later change.
         self.fused_ragged_node = False
+        # eval() with lengths= / npoints= (/ lengths1=): the fused inference kernels with the counts inside
+        # (pn2_*_ragged, include/pn2ops.h "ragged inference") instead of the dense kernels on every row and a torch.where behind
+        # them: padding rows are neither gathered nor computed where a kernel can skip them, a level without a geometry is ONE
+        # C call; last_path "fused_ragged". Where the dense fused route would run (_fused_ok / _fused_kind), max pooling. Opt-in.
+        self.fused_ragged_eval = False
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
@@ -948,6 +992,20 @@ class PointnetFPModule(nn.Module):
         b, n = xyz1.shape[0], xyz1.shape[1]
         dev = xyz1.device
         lens = ragged_lengths(lengths1, b, dev, "lengths1")
+        if self.fused_ragged_eval and not self.training:
+            kind = self._fused_kind(points1, points2, b * n)
+            if kind is not None:
+                # the level's kernel with lengths1 inside (padding rows gather nothing and come back as +0.0; points1 may hold
+                # anything there): ONE C call behind the two-sided three_nn, or the kernel alone on a geometry
+                self.last_path = "fused_ragged"
+                packed = self._packed(points2.shape[2], points1.shape[2] if points1 is not None else 0, kind, points2.device)
+                if geometry is not None:
+                    g = geometry.wait()
+                    return sa_mlp.fp_mlp(points2, points1, g.idx, g.dist, packed, lengths1=lens)
+                if self.reuse_buffers and self._lvl_buffers is None:
+                    self._lvl_buffers = sa_mlp.LevelBuffers()
+                return sa_mlp.fp_level_ragged(xyz1, xyz2, points1, points2, packed, lens, lengths2,
+                                              self._lvl_buffers if self.reuse_buffers else None)
         valid = torch.arange(n, device=dev, dtype=torch.int32).unsqueeze(0) < lens.unsqueeze(1)      # (b, n), no host sync
         if geometry is not None:
             g = geometry.wait()

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _C
-from ._tensors import f32, i32, on_device, ptr, require, same_device, stream_ptr
+from ._tensors import f32, full_counts, i32, on_device, ptr, ragged_lengths, require, same_device, stream_ptr
 
 
 _RESIDENT_VARIANT = 0
@@ -122,9 +122,19 @@ def pool_supported(cin, widths, nsample, pooling):
                                                     POOLING[pooling]))
 
 
-def _pooled_mlp(xyz, new_xyz, points, idx, packed, pooling):
-    """The one body of sa_mlp_maxpool ("max": the only mode with the group_all form and set_resident_variant) and sa_mlp_pool."""
+def _pooled_mlp(xyz, new_xyz, points, idx, packed, pooling, npoints=None, lengths=None):
+    """The one body of sa_mlp_maxpool ("max": the only mode with the group_all form, set_resident_variant and the counts) and
+    sa_mlp_pool."""
     xyz, points, b, n, cfeat = _level_inputs(xyz, points, packed)
+    ragged = npoints is not None or lengths is not None
+    if ragged:
+        require(pooling == "max", "npoints / lengths: max pooling only")
+        group_all = idx is None and new_xyz is None
+        require(not (group_all and npoints is not None), "the group_all form takes lengths, not npoints")
+        require(group_all or npoints is not None, "the grouped form needs npoints (full counts for a dense sample side)")
+        require(not group_all or lengths is not None, "the group_all form needs lengths")
+        npoints = None if npoints is None else ragged_lengths(npoints, b, xyz.device, "npoints")
+        lengths = None if lengths is None else ragged_lengths(lengths, b, xyz.device)
     if pooling == "max" and idx is None and new_xyz is None:
         m, ns = 1, n
     else:
@@ -145,7 +155,11 @@ def _pooled_mlp(xyz, new_xyz, points, idx, packed, pooling):
     lib = _C.lib()
     ws = _scratch(lib, packed, b, n, m, ns, dev)
     with on_device(dev):
-        if pooling == "max":
+        if ragged:
+            _C.check(lib.pn2_sa_mlp3_maxpool_ragged(b, n, m, ns, cfeat, ptr(xyz), ptr(lengths), ptr(new_xyz), ptr(npoints), ptr(points),
+                                                    ptr(idx), c1, c2, c3, ptr(packed.wp), ptr(packed.bp), ptr(out), ptr(ws),
+                                                    _RESIDENT_VARIANT, stream_ptr(dev)), "sa_mlp3_maxpool_ragged")
+        elif pooling == "max":
             _C.check(lib.pn2_sa_mlp3_maxpool_ex(b, n, m, ns, cfeat, ptr(xyz), ptr(new_xyz), ptr(points), ptr(idx), c1, c2, c3,
                                                 ptr(packed.wp), ptr(packed.bp), ptr(out), ptr(ws), _RESIDENT_VARIANT,
                                                 stream_ptr(dev)), "sa_mlp3_maxpool")
@@ -156,12 +170,16 @@ def _pooled_mlp(xyz, new_xyz, points, idx, packed, pooling):
     return out
 
 
-def sa_mlp_maxpool(xyz, new_xyz, points, idx, packed):
+def sa_mlp_maxpool(xyz, new_xyz, points, idx, packed, npoints=None, lengths=None):
     """xyz (b,n,3), new_xyz (b,m,3), points (b,n,c) or None, idx (b,m,nsample) i32, packed: PackedMLP3
     -> (b, m, c3) f32 = max over nsample of the three-layer MLP of [xyz[idx]-new_xyz, points[idx]].
     new_xyz is None and idx is None: the group_all level (sample_and_group_all, pointnet_util.py:59-84) ->
-    (b, 1, c3) = max over all n points of the MLP of [xyz, points] (no centroid)."""
-    return _pooled_mlp(xyz, new_xyz, points, idx, packed, "max")
+    (b, 1, c3) = max over all n points of the MLP of [xyz, points] (no centroid).
+    npoints (b,): per-cloud sample counts of the grouped form (pn2_sa_mlp3_maxpool_ragged): rows below a count are the dense
+    call's on the cloud's slices, rows from it on are +0.0, and nothing of new_xyz / idx there is read. lengths (b,): per-cloud
+    point counts; required by the group_all form (the group is the cloud's first lengths[c] rows), optional beside npoints.
+    Rows of xyz / points beyond a length may hold anything. No host synchronisation."""
+    return _pooled_mlp(xyz, new_xyz, points, idx, packed, "max", npoints, lengths)
 
 
 def sa_mlp_pool(xyz, new_xyz, points, idx, packed, pooling):
@@ -224,10 +242,12 @@ class PackedFPMLP:
         self.bp = torch.from_numpy(bp).to(device)
 
 
-def fp_mlp(points2, points1, idx, dist, packed):
+def fp_mlp(points2, points1, idx, dist, packed, lengths1=None):
     """points2 (b,m,c2) features of the known points, points1 (b,n,c1) skip features or None, idx / dist
     (b,n,3) from three_nn -> (b, n, widths[-1]) f32: the inverse-distance weights, the interpolation, the
-    concatenation and the layer stack of pointnet_fp_module (pointnet_util.py:211-226) in one launch."""
+    concatenation and the layer stack of pointnet_fp_module (pointnet_util.py:211-226) in one launch.
+    lengths1 (b,): per-cloud counts of the unknown side (pn2_fp_mlp_ragged): rows below a length are the dense call's on the
+    cloud's slices, rows from it on are +0.0; idx, dist and points1 there are not read and may hold anything."""
     points2, idx, dist = f32(points2, "points2"), i32(idx, "idx"), f32(dist, "dist")
     b, m, c2 = points2.shape
     n = idx.shape[1]
@@ -245,9 +265,15 @@ def fp_mlp(points2, points1, idx, dist, packed):
     nbytes = _C.lib().pn2_fp_mlp_ws_bytes(b, m, c2, c1, len(packed.widths), packed._warr, packed.kind)
     ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev)        # Q = points2 . W1a, one row per known point
     with on_device(dev):
-        _C.check(_C.lib().pn2_fp_mlp(b, n, m, c2, c1, ptr(points2), ptr(points1), ptr(idx), ptr(dist), len(packed.widths),
-                                     packed._warr, packed.kind, ptr(packed.wp), ptr(packed.bp), ptr(out), ptr(ws),
-                                     stream_ptr(dev)), "fp_mlp")
+        if lengths1 is not None:
+            lens = ragged_lengths(lengths1, b, dev, "lengths1")
+            _C.check(_C.lib().pn2_fp_mlp_ragged(b, n, m, c2, c1, ptr(points2), ptr(points1), ptr(lens), ptr(idx), ptr(dist),
+                                                len(packed.widths), packed._warr, packed.kind, ptr(packed.wp), ptr(packed.bp),
+                                                ptr(out), ptr(ws), stream_ptr(dev)), "fp_mlp_ragged")
+        else:
+            _C.check(_C.lib().pn2_fp_mlp(b, n, m, c2, c1, ptr(points2), ptr(points1), ptr(idx), ptr(dist), len(packed.widths),
+                                         packed._warr, packed.kind, ptr(packed.wp), ptr(packed.bp), ptr(out), ptr(ws),
+                                         stream_ptr(dev)), "fp_mlp")
     return out
 
 
@@ -357,4 +383,75 @@ def fp_level(xyz1, xyz2, points1, points2, packed, buffers=None):
         _C.check(lib.pn2_fp_level(b, n, m, c2, c1, ptr(xyz1), ptr(xyz2), ptr(points2), ptr(points1), len(packed.widths),
                                   packed._warr, packed.kind, ptr(packed.wp), ptr(packed.bp), ptr(dist), ptr(idx), ptr(out), ptr(ws),
                                   stream_ptr(dev)), "fp_level")
+    return out
+
+
+# ---- the same on ragged batches: pn2_sa_level_ragged / pn2_fp_level_ragged --------------------------------------------------
+def sa_level_ragged(npoint, radius, nsample, xyz, points, packed, lengths, npoints, buffers=None):
+    """sa_level on a ragged batch, ONE call: ragged FPS with per-cloud sample counts, the two-sided ragged ball query + grouping
+    and the fused MLP + max-pool with counts. lengths / npoints: (b,) per-cloud point / sample counts; None = that side is dense
+    (full counts are made on the device). Results as sa_level's: rows below a count are the slice's, rows from it on hold the
+    operators' fills and +0.0 pooled features. No overlapped launch, no host synchronisation; capturable once packed."""
+    xyz, points, b, n, cfeat = _level_inputs(xyz, points, packed)
+    m, ns = int(npoint), int(nsample)
+    require(m > 0 and ns > 0 and float(radius) > 0, "npoint, nsample and radius must be positive")
+    require(ns == packed.nsample or _same_kernel(packed, ns), "weights were packed for another kernel (nsample %d)" % packed.nsample)
+    dev = same_device(xyz, packed.wp) if points is None else same_device(xyz, points, packed.wp)
+    lengths = full_counts(b, n, dev) if lengths is None else ragged_lengths(lengths, b, dev)
+    npoints = full_counts(b, m, dev) if npoints is None else ragged_lengths(npoints, b, dev, "npoints")
+    lib = _C.lib()
+    key = ("ragged", b, n, m, ns, cfeat, packed.widths, dev)
+    if buffers is not None and buffers.key == key:
+        fps_idx, new_xyz, idx, cnt, grouped, out, ws = buffers.t
+    else:
+        fps_idx = torch.empty((b, m), dtype=torch.int32, device=dev)
+        new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=dev)
+        idx = torch.empty((b, m, ns), dtype=torch.int32, device=dev)
+        cnt = torch.empty((b, m), dtype=torch.int32, device=dev)
+        grouped = torch.empty((b, m, ns, 3), dtype=torch.float32, device=dev)
+        out = torch.empty((b, m, packed.widths[2]), dtype=torch.float32, device=dev)
+        ws = _scratch(lib, packed, b, n, m, ns, dev)
+        if buffers is not None:
+            buffers.key, buffers.t = key, (fps_idx, new_xyz, idx, cnt, grouped, out, ws)
+    with on_device(dev):
+        _C.check(lib.pn2_sa_level_ragged(b, n, m, float(radius), ns, cfeat, ptr(xyz), ptr(lengths), ptr(npoints), ptr(points),
+                                         packed.widths[0], packed.widths[1], packed.widths[2], ptr(packed.wp), ptr(packed.bp),
+                                         ptr(fps_idx), ptr(new_xyz), ptr(idx), ptr(cnt), ptr(grouped), ptr(out), ptr(ws),
+                                         stream_ptr(dev)), "sa_level_ragged")
+    return new_xyz, out, idx, fps_idx, cnt, grouped
+
+
+def fp_level_ragged(xyz1, xyz2, points1, points2, packed, lengths1, lengths2=None, buffers=None):
+    """fp_level on a ragged batch, ONE call: the two-sided ragged three_nn + the fused level with lengths1 -> (b, n, cout), rows
+    from lengths1[c] on +0.0. lengths2: (b,) counts of the known side, None = dense."""
+    xyz1, xyz2, points2 = f32(xyz1, "xyz1"), f32(xyz2, "xyz2"), f32(points2, "points2")
+    b, n, _ = xyz1.shape
+    m, c2 = points2.shape[1], points2.shape[2]
+    require(xyz1.dim() == 3 and xyz1.shape[2] == 3 and tuple(xyz2.shape) == (b, m, 3), "xyz1 (b,n,3), xyz2 (b,m,3) expected")
+    c1 = 0
+    if points1 is not None:
+        points1 = f32(points1, "points1")
+        require(points1.dim() == 3 and tuple(points1.shape[:2]) == (b, n), "points1 must be (b, n, c1)")
+        c1 = points1.shape[2]
+    require(c2 == packed.c2 and c1 == packed.c1, "packed FP MLP expects (%d, %d) channels, got (%d, %d)" % (packed.c2, packed.c1, c2, c1))
+    dev = same_device(xyz1, xyz2, points2, packed.wp)
+    require(lengths1 is not None, "fp_level_ragged needs lengths1")
+    lengths1 = ragged_lengths(lengths1, b, dev, "lengths1")
+    lengths2 = full_counts(b, m, dev) if lengths2 is None else ragged_lengths(lengths2, b, dev, "lengths2")
+    lib = _C.lib()
+    key = ("ragged", b, n, m, c2, c1, tuple(packed.widths), packed.kind, dev)
+    if buffers is not None and buffers.key == key:
+        dist, idx, out, ws = buffers.t
+    else:
+        dist = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+        idx = torch.empty((b, n, 3), dtype=torch.int32, device=dev)
+        out = torch.empty((b, n, packed.widths[-1]), dtype=torch.float32, device=dev)
+        nbytes = lib.pn2_fp_mlp_ws_bytes(b, m, c2, c1, len(packed.widths), packed._warr, packed.kind)
+        ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=dev)
+        if buffers is not None:
+            buffers.key, buffers.t = key, (dist, idx, out, ws)
+    with on_device(dev):
+        _C.check(lib.pn2_fp_level_ragged(b, n, m, c2, c1, ptr(xyz1), ptr(lengths1), ptr(xyz2), ptr(lengths2), ptr(points2),
+                                         ptr(points1), len(packed.widths), packed._warr, packed.kind, ptr(packed.wp), ptr(packed.bp),
+                                         ptr(dist), ptr(idx), ptr(out), ptr(ws), stream_ptr(dev)), "fp_level_ragged")
     return out
