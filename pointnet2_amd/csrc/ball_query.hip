@@ -38,66 +38,43 @@
 
 namespace pn2 {
 
-template <bool LDS_CLOUD, bool FUSE>
+// One kernel, three modes (pn2_device.h: Counts). No count array: the dense kernel, the cloud index addresses the tensors.
+// One (pn2_query_ball_group_xyz_ragged): cloud c holds lengths1[c] <= n points in its padded (n, 3) slab. The workgroup hands
+// the body its own slabs as cloud 0 with n = n_c: staging, the +inf pad and the sweep bounds are those of the dense kernel on
+// the slice, rows at or beyond n_c are never addressed. The LDS is sized on the host for the padded n (both layouts grow with n).
+// Two (pn2_query_ball_group_xyz_ragged_pair): cloud c also holds only m_c = lengths2[c] valid queries. The workgroup sweeps
+// [q0, min(q0 + qpb, m_c)) -- the body never reads a query row at or beyond its q1 --, fills its rows from m_c on (bq_fill_rows)
+// and, when it holds nothing else, leaves before the staging (block-uniform).
+template <bool LDS_CLOUD, bool FUSE, class... Cnt>
 __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(int n, int m, int nsample, float thr, int qpb,
                                                                 const float *__restrict__ xyz1,
                                                                 const float *__restrict__ xyz2, int *__restrict__ idx,
                                                                 int *__restrict__ pts_cnt,
-                                                                float *__restrict__ grouped, int subtract)
+                                                                float *__restrict__ grouped, int subtract, Cnt __restrict__... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int q0 = blockIdx.x * qpb;
-    bq_block_body<LDS_CLOUD, FUSE, false>(n, m, nsample, thr, blockIdx.y, q0, min(q0 + qpb, m), xyz1, xyz2, nullptr,
-                                          nullptr, idx, pts_cnt, grouped, subtract, smem);
-}
-
-// Ragged batch (pn2_query_ball_group_xyz_ragged): cloud c holds lengths1[c] <= n points in its padded (n, 3) slab. The
-// workgroup hands the body its own slabs as cloud 0 with n = n_c: staging, the +inf pad and the sweep bounds are those of the
-// dense kernel on the slice, rows at or beyond n_c are never addressed. The LDS is sized on the host for the padded n (both
-// layouts grow with n). The length is clamped into 1..n for memory safety only (bq_ragged_length, ball_query_body.h).
-template <bool LDS_CLOUD, bool FUSE>
-__global__ __launch_bounds__(kBqThreads) void ball_query_ragged_kernel(int n, int m, int nsample, float thr, int qpb,
-                                                                       const float *__restrict__ xyz1,
-                                                                       const int *__restrict__ lengths,
-                                                                       const float *__restrict__ xyz2, int *__restrict__ idx,
-                                                                       int *__restrict__ pts_cnt,
-                                                                       float *__restrict__ grouped, int subtract)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int c = blockIdx.y;
-    const int nc = bq_ragged_length(lengths, c, n);
-    const int q0 = blockIdx.x * qpb;
-    const size_t rows = (size_t)c * m;
-    bq_block_body<LDS_CLOUD, FUSE, false>(nc, m, nsample, thr, 0, q0, min(q0 + qpb, m), xyz1 + (size_t)c * n * 3, xyz2 + rows * 3,
-                                          nullptr, nullptr, idx ? idx + rows * nsample : nullptr, pts_cnt ? pts_cnt + rows : nullptr,
-                                          grouped ? grouped + rows * nsample * 3 : nullptr, subtract, smem);
-}
-
-// Ragged on both sides (pn2_query_ball_group_xyz_ragged_pair): cloud c also holds only m_c = lengths2[c] valid queries. The
-// workgroup sweeps [q0, min(q0 + qpb, m_c)) -- the body never reads a query row at or beyond its q1 --, fills its rows from m_c
-// on (bq_fill_rows) and, when it holds nothing else, leaves before the staging (block-uniform).
-template <bool LDS_CLOUD, bool FUSE>
-__global__ __launch_bounds__(kBqThreads) void ball_query_ragged_pair_kernel(int n, int m, int nsample, float thr, int qpb,
-                                                                            const float *__restrict__ xyz1,
-                                                                            const int *__restrict__ lengths,
-                                                                            const float *__restrict__ xyz2,
-                                                                            const int *__restrict__ lengths2, int *__restrict__ idx,
-                                                                            int *__restrict__ pts_cnt,
-                                                                            float *__restrict__ grouped, int subtract)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int c = blockIdx.y;
-    const int nc = bq_ragged_length(lengths, c, n);
-    const int mc = bq_ragged_count(lengths2, c, m);
-    const int q0 = blockIdx.x * qpb;
-    const size_t rows = (size_t)c * m;
-    int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
-    int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
-    float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
-    bq_fill_rows<kBqThreads>(max(q0, mc), min(q0 + qpb, m), nsample, oi, oc, og);
-    if (q0 >= mc) return;
-    bq_block_body<LDS_CLOUD, FUSE, false>(nc, m, nsample, thr, 0, q0, min(q0 + qpb, mc), xyz1 + (size_t)c * n * 3, xyz2 + rows * 3,
-                                          nullptr, nullptr, oi, oc, og, subtract, smem);
+    const Counts<Cnt...> counts(cnt...);
+    if constexpr (sizeof...(Cnt) == 0) {
+        const int q0 = blockIdx.x * qpb;
+        bq_block_body<LDS_CLOUD, FUSE, false>(n, m, nsample, thr, blockIdx.y, q0, min(q0 + qpb, m), xyz1, xyz2, nullptr,
+                                              nullptr, idx, pts_cnt, grouped, subtract, smem);
+    } else {
+        const int c = blockIdx.y;
+        const int nc = cloud_count(counts.side[0], c, n);
+        int mc = m;
+        if constexpr (sizeof...(Cnt) == 2) mc = cloud_count(counts.side[1], c, m);
+        const int q0 = blockIdx.x * qpb;
+        const size_t rows = (size_t)c * m;
+        int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
+        int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
+        float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
+        if constexpr (sizeof...(Cnt) == 2) {
+            bq_fill_rows<kBqThreads>(max(q0, mc), min(q0 + qpb, m), nsample, oi, oc, og);
+            if (q0 >= mc) return;
+        }
+        bq_block_body<LDS_CLOUD, FUSE, false>(nc, m, nsample, thr, 0, q0, min(q0 + qpb, mc), xyz1 + (size_t)c * n * 3, xyz2 + rows * 3,
+                                              nullptr, nullptr, oi, oc, og, subtract, smem);
+    }
 }
 
 template <bool LDS_CLOUD, bool FUSE>
@@ -114,107 +91,54 @@ static int launch_bq(int b, int n, int m, float thr, int nsample, const float *x
     const int gx = (m + qpb - 1) / qpb;
     const size_t lds = (LDS_CLOUD ? sizeof(float4) * (size_t)((n + 127) & ~127) : 0) + sizeof(int) * (size_t)nsample * kGran;
     if (lds > 160 * 1024) return PN2_E_TOO_LARGE;
-    if (lengths2) {
-        auto kern = ball_query_ragged_pair_kernel<LDS_CLOUD, FUSE>;
-        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        return launch(kern, dim3(gx, b), dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, lengths, xyz2, lengths2, idx, pts_cnt,
-                      grouped, subtract);
-    }
-    if (lengths) {
-        auto kern = ball_query_ragged_kernel<LDS_CLOUD, FUSE>;
-        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        return launch(kern, dim3(gx, b), dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, lengths, xyz2, idx, pts_cnt, grouped,
-                      subtract);
-    }
-    auto kern = ball_query_kernel<LDS_CLOUD, FUSE>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    if (int rc = launch(kern, dim3(gx, b), dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, xyz2, idx,
-                       pts_cnt, grouped, subtract)) return rc;
-    return PN2_OK;
+    return launch_counts([](auto... c) { return ball_query_kernel<LDS_CLOUD, FUSE, decltype(c)...>; }, lengths, lengths2, dim3(gx, b),
+                         dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, xyz2, idx, pts_cnt, grouped, subtract);
 }
 
 // Cell-list kernel (ball_query_body.h, second half): the grid is built per workgroup, so a workgroup
 // takes a larger share of the queries than in the sweep kernel to amortise the binning pass.
-template <int NT, int LPQ, bool FUSE>
+// With counts (as in ball_query_kernel; a workgroup of fill rows alone leaves before the binning): a cloud below 64 points takes
+// the sweep body at once (block-uniform; the host keeps such clouds off the cell list in the dense dispatch too, bq_use_cells);
+// larger ones bin their own n_c points, and the body's own fallback (coarse grid, crowded cells) uses the sweep layout inside
+// the same LDS, sized for the padded n.
+template <int NT, int LPQ, bool FUSE, class... Cnt>
 __global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_kernel(int b, int n, int m, int nsample, float thr,
                                                                       float radius, int qpb, int parts,
                                                                       const float *__restrict__ xyz1,
                                                                       const float *__restrict__ xyz2,
                                                                       int *__restrict__ idx,
                                                                       int *__restrict__ pts_cnt,
-                                                                      float *__restrict__ grouped, int subtract)
+                                                                      float *__restrict__ grouped, int subtract, Cnt __restrict__... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const Counts<Cnt...> counts(cnt...);
     int cloud, part;
     decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int q0 = part * qpb;
-    bq_cells_block_body<NT, LPQ, FUSE, false, true>(n, m, nsample, thr, radius, cloud, q0, min(q0 + qpb, m), xyz1, xyz2,   // BLK: crowded balls walk the first half of the indices first (ball_query_body.h)
-                                     nullptr, nullptr, idx, pts_cnt, grouped, subtract, smem);
-}
-
-// The cell-list kernel on a ragged batch. A cloud below 64 points takes the sweep body at once (block-uniform; the host keeps
-// such clouds off the cell list in the dense dispatch too, bq_use_cells); larger ones bin their own n_c points, and the
-// body's own fallback (coarse grid, crowded cells) uses the sweep layout inside the same LDS, sized for the padded n.
-template <int NT, int LPQ, bool FUSE>
-__global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_ragged_kernel(int b, int n, int m, int nsample, float thr,
-                                                                             float radius, int qpb, int parts,
-                                                                             const float *__restrict__ xyz1,
-                                                                             const int *__restrict__ lengths,
-                                                                             const float *__restrict__ xyz2,
-                                                                             int *__restrict__ idx,
-                                                                             int *__restrict__ pts_cnt,
-                                                                             float *__restrict__ grouped, int subtract)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int cloud, part;
-    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int nc = bq_ragged_length(lengths, cloud, n);
-    const int q0 = part * qpb, q1 = min(q0 + qpb, m);
-    const size_t rows = (size_t)cloud * m;
-    const float *__restrict__ x1 = xyz1 + (size_t)cloud * n * 3;
-    const float *__restrict__ x2 = xyz2 + rows * 3;
-    int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
-    int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
-    float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
-    if (nc < 64)
-        bq_block_body<true, FUSE, false, NT>(nc, m, nsample, thr, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og, subtract, smem);
-    else
-        bq_cells_block_body<NT, LPQ, FUSE, false, true>(nc, m, nsample, thr, radius, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og,
-                                                        subtract, smem);
-}
-
-// The cell-list kernel, ragged on both sides: the query range ends at m_c = lengths2[c], the rows from m_c on are filled, and a
-// workgroup of fill rows alone leaves before the binning (block-uniform). "Below 64 points: sweep" as above.
-template <int NT, int LPQ, bool FUSE>
-__global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_ragged_pair_kernel(int b, int n, int m, int nsample, float thr,
-                                                                                  float radius, int qpb, int parts,
-                                                                                  const float *__restrict__ xyz1,
-                                                                                  const int *__restrict__ lengths,
-                                                                                  const float *__restrict__ xyz2,
-                                                                                  const int *__restrict__ lengths2,
-                                                                                  int *__restrict__ idx,
-                                                                                  int *__restrict__ pts_cnt,
-                                                                                  float *__restrict__ grouped, int subtract)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int cloud, part;
-    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int nc = bq_ragged_length(lengths, cloud, n);
-    const int mc = bq_ragged_count(lengths2, cloud, m);
-    const int q0 = part * qpb, q1 = min(q0 + qpb, mc);
-    const size_t rows = (size_t)cloud * m;
-    const float *__restrict__ x1 = xyz1 + (size_t)cloud * n * 3;
-    const float *__restrict__ x2 = xyz2 + rows * 3;
-    int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
-    int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
-    float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
-    bq_fill_rows<NT>(max(q0, mc), min(q0 + qpb, m), nsample, oi, oc, og);
-    if (q0 >= mc) return;
-    if (nc < 64)
-        bq_block_body<true, FUSE, false, NT>(nc, m, nsample, thr, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og, subtract, smem);
-    else
-        bq_cells_block_body<NT, LPQ, FUSE, false, true>(nc, m, nsample, thr, radius, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og,
-                                                        subtract, smem);
+    if constexpr (sizeof...(Cnt) == 0) {
+        const int q0 = part * qpb;
+        bq_cells_block_body<NT, LPQ, FUSE, false, true>(n, m, nsample, thr, radius, cloud, q0, min(q0 + qpb, m), xyz1, xyz2,   // BLK: crowded balls walk the first half of the indices first (ball_query_body.h)
+                                         nullptr, nullptr, idx, pts_cnt, grouped, subtract, smem);
+    } else {
+        const int nc = cloud_count(counts.side[0], cloud, n);
+        int mc = m;
+        if constexpr (sizeof...(Cnt) == 2) mc = cloud_count(counts.side[1], cloud, m);
+        const int q0 = part * qpb, q1 = min(q0 + qpb, mc);
+        const size_t rows = (size_t)cloud * m;
+        const float *__restrict__ x1 = xyz1 + (size_t)cloud * n * 3;
+        const float *__restrict__ x2 = xyz2 + rows * 3;
+        int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
+        int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
+        float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
+        if constexpr (sizeof...(Cnt) == 2) {
+            bq_fill_rows<NT>(max(q0, mc), min(q0 + qpb, m), nsample, oi, oc, og);
+            if (q0 >= mc) return;
+        }
+        if (nc < 64)
+            bq_block_body<true, FUSE, false, NT>(nc, m, nsample, thr, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og, subtract, smem);
+        else
+            bq_cells_block_body<NT, LPQ, FUSE, false, true>(nc, m, nsample, thr, radius, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og,
+                                                            subtract, smem);
+    }
 }
 
 static size_t bq_sweep_lds_bytes(int n, int nsample, int nthreads = kBqThreads)
@@ -268,23 +192,9 @@ static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsa
     const int gx = (m + qpb - 1) / qpb;
     const size_t a = bq_cells_lds_bytes(n, nsample, LPQ, NT), s = bq_sweep_lds_bytes(n, nsample, NT);
     const size_t lds = a > s ? a : s;                       // the fallback inside the kernel uses the sweep layout
-    if (lengths2) {
-        auto kern = ball_query_cells_ragged_pair_kernel<NT, LPQ, FUSE>;
-        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        return launch(kern, dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx, xyz1, lengths, xyz2,
-                      lengths2, idx, pts_cnt, grouped, subtract);
-    }
-    if (lengths) {
-        auto kern = ball_query_cells_ragged_kernel<NT, LPQ, FUSE>;
-        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        return launch(kern, dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx, xyz1, lengths, xyz2, idx,
-                      pts_cnt, grouped, subtract);
-    }
-    auto kern = ball_query_cells_kernel<NT, LPQ, FUSE>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    if (int rc = launch(kern, dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx,
-                       xyz1, xyz2, idx, pts_cnt, grouped, subtract)) return rc;
-    return PN2_OK;
+    return launch_counts([](auto... c) { return ball_query_cells_kernel<NT, LPQ, FUSE, decltype(c)...>; }, lengths, lengths2,
+                         dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx, xyz1, xyz2, idx, pts_cnt,
+                         grouped, subtract);
 }
 
 template <bool FUSE>
@@ -304,8 +214,8 @@ static int dispatch_bq_cells(BqCellsGeom g, int b, int n, int m, float thr, floa
     return PN2_E_TOO_LARGE;
 }
 
-// lengths: NULL = every cloud holds n points (the dense kernels); else the ragged kernels. lengths2 (with lengths only): the
-// valid queries per cloud, the *_ragged_pair kernels
+// lengths: NULL = every cloud holds n points; else the points per cloud. lengths2 (with lengths only): the valid queries per
+// cloud (the count modes of the two kernels)
 static int ball_query_common(int b, int n, int m, float radius, int nsample, const float *xyz1, const float *xyz2,
                              int subtract, int *idx, int *pts_cnt, float *grouped, bool fuse, BqOpts opt, void *stream,
                              const int *lengths = nullptr, const int *lengths2 = nullptr)
@@ -382,6 +292,21 @@ extern "C" int pn2_query_ball_group_xyz_ex(int b, int n, int m, float radius, in
                                   grouped_xyz, grouped_xyz != nullptr, {kernel, cells_qpb}, stream);
 }
 
+// The ragged entries' prologue: the dense entry's attribute and extent checks, then nothing to do, and only then the `sides`
+// count arrays the entry requires (lengths2 with sides == 2).
+static int ball_query_ragged(int sides, int b, int n, int m, float radius, int nsample, const float *xyz1, const int *lengths1,
+                             const float *xyz2, const int *lengths2, int subtract_centroid, int *idx, int *pts_cnt, float *grouped_xyz,
+                             int kernel, int cells_qpb, void *stream)
+{
+    if (kernel < 0 || kernel > 3 || cells_qpb < 0) return PN2_E_ARG;
+    if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;
+    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (!lengths1 || (sides == 2 && !lengths2)) return PN2_E_NULL;
+    return pn2::ball_query_common(b, n, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt,
+                                  grouped_xyz, grouped_xyz != nullptr, {kernel, cells_qpb}, stream, lengths1, lengths2);
+}
+
 // Ragged batch: cloud c of xyz1 is xyz1[c, :lengths1[c]] of a padded (b, n, 3) tensor, lengths1 (b) int32 on the device, never
 // read by the host; the queries xyz2 (b, m, 3) are dense. Result per cloud = pn2_query_ball_group_xyz_ex on the slice, for
 // every `kernel`. grouped_xyz == NULL: plain query_ball_point.
@@ -389,13 +314,8 @@ extern "C" int pn2_query_ball_group_xyz_ragged(int b, int n, int m, float radius
                                                const float *xyz2, int subtract_centroid, int *idx, int *pts_cnt, float *grouped_xyz,
                                                int kernel, int cells_qpb, void *stream)
 {
-    if (kernel < 0 || kernel > 3 || cells_qpb < 0) return PN2_E_ARG;
-    if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;
-    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
-    if (b == 0 || m == 0) return PN2_OK;
-    if (!lengths1) return PN2_E_NULL;
-    return pn2::ball_query_common(b, n, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt,
-                                  grouped_xyz, grouped_xyz != nullptr, {kernel, cells_qpb}, stream, lengths1);
+    return ball_query_ragged(1, b, n, m, radius, nsample, xyz1, lengths1, xyz2, nullptr, subtract_centroid, idx, pts_cnt, grouped_xyz,
+                             kernel, cells_qpb, stream);
 }
 
 // Ragged on both sides: cloud c additionally holds only lengths2[c] valid rows of xyz2 (b int32 on the device, clamped into
@@ -406,11 +326,6 @@ extern "C" int pn2_query_ball_group_xyz_ragged_pair(int b, int n, int m, float r
                                                     const int *lengths1, const float *xyz2, const int *lengths2, int subtract_centroid,
                                                     int *idx, int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb, void *stream)
 {
-    if (kernel < 0 || kernel > 3 || cells_qpb < 0) return PN2_E_ARG;
-    if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;
-    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
-    if (b == 0 || m == 0) return PN2_OK;
-    if (!lengths1 || !lengths2) return PN2_E_NULL;
-    return pn2::ball_query_common(b, n, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt,
-                                  grouped_xyz, grouped_xyz != nullptr, {kernel, cells_qpb}, stream, lengths1, lengths2);
+    return ball_query_ragged(2, b, n, m, radius, nsample, xyz1, lengths1, xyz2, lengths2, subtract_centroid, idx, pts_cnt, grouped_xyz,
+                             kernel, cells_qpb, stream);
 }

@@ -129,20 +129,6 @@ __device__ __forceinline__ int bq_poll_sample(const unsigned long long *tagged, 
     }
 }
 
-// Ragged batches (ball_query.hip, ball_query_msg.hip): the point count of cloud `cloud`, read from the device array and clamped
-// into 1..n for memory safety only; wave-uniform.
-__device__ __forceinline__ int bq_ragged_length(const int *__restrict__ lengths, int cloud, int n)
-{
-    return min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
-}
-
-// Ragged QUERY side (the *_ragged_pair kernels): cloud `cloud` holds counts[cloud] valid rows of its (m, 3) query slab, clamped
-// into 1..m for memory safety only; wave-uniform.
-__device__ __forceinline__ int bq_ragged_count(const int *__restrict__ counts, int cloud, int m)
-{
-    return min(max(__builtin_amdgcn_readfirstlane(counts[cloud]), 1), m);
-}
-
 // The output rows [r0, r1) of one cloud (idx / pts_cnt / grouped already moved to the cloud's row 0) that belong to no valid
 // query: idx all 0, pts_cnt 0, grouped_xyz all +0.0 -- fixed values, so everything downstream stays in range and finite.
 // Nothing is read; the whole workgroup (NT threads) takes part, no barrier.

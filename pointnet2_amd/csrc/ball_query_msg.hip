@@ -113,75 +113,53 @@ __device__ __forceinline__ void bq_msg_block_body(int n, int m, int cloud, int q
     }
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int n, int m, int qpb, int parts,
-                                                                    int use_cells, int max_ns, int wave_stride_b, BqScales sc,
-                                                                    const float *__restrict__ xyz1,
-                                                                    const float *__restrict__ xyz2, int subtract)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int cloud, part;
-    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int q0 = part * qpb;
-    bq_msg_block_body<NT>(n, m, cloud, q0, min(q0 + qpb, m), use_cells, max_ns, wave_stride_b, sc, xyz1, xyz2, subtract, 0, smem);
-}
-
-// Ragged batch (pn2_query_ball_group_xyz_msg_ragged): cloud c holds nc = lengths1[c] <= n points in its padded (n, 3) slab. The
+// One kernel, three modes (pn2_device.h: Counts). No count array: the dense kernel. With counts
+// (pn2_query_ball_group_xyz_msg_ragged / _ragged_pair): cloud c holds nc = lengths1[c] <= n points in its padded (n, 3) slab. The
 // workgroup hands the body n = nc, cloud 0 and the cloud's own slabs of the padded tensors, the outputs moved by the cloud's
 // c m rows: layout, staging, binning, the +inf pad and every loop bound are those of the dense kernel on the slice, and rows
 // at or beyond nc are never addressed. Everything the HOST decided -- geometry, lanes per query, wave_stride, LDS bytes -- was
 // sized for the padded n (msg_plan), and what fits n fits nc: the sorted array (16 nc bytes), the sweep copy's npad = nc
 // rounded up to 128 and bq_cells_wave_bytes(nc, ., lpq) (windows of 4096 points) are all non-decreasing in the point count,
 // and wave_stride is passed in, never re-derived from nc. Per cloud, block-uniform: below 64 points the binning is skipped and
-// the cloud is swept (the rule of ball_query_cells_ragged_kernel); larger clouds bin their own nc points, so bq_build_grid's
+// the cloud is swept (the rule of ball_query_cells_kernel); larger clouds bin their own nc points, so bq_build_grid's
 // give-up rules and the half-of-the-grid rule of the body apply to that cloud's grid. No global atomics, no memset, nothing
 // that waits on another workgroup.
-template <int NT>
-__global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_ragged_kernel(int b, int n, int m, int qpb, int parts,
-                                                                           int use_cells, int max_ns, int wave_stride_b,
-                                                                           BqScales sc, const float *__restrict__ xyz1,
-                                                                           const int *__restrict__ lengths1,
-                                                                           const float *__restrict__ xyz2, int subtract)
+// Counts on both sides: cloud c also holds only m_c = lengths2[c] valid queries. The body gets the query range cut at m_c; the
+// workgroup's rows from m_c on are filled for EVERY radius (idx 0, pts_cnt 0, grouped +0.0), and a workgroup of such rows alone
+// leaves before any staging or binning (block-uniform).
+template <int NT, class... Cnt>
+__global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int n, int m, int qpb, int parts,
+                                                                    int use_cells, int max_ns, int wave_stride_b, BqScales sc,
+                                                                    const float *__restrict__ xyz1,
+                                                                    const float *__restrict__ xyz2, int subtract, Cnt __restrict__... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const Counts<Cnt...> counts(cnt...);
     int cloud, part;
     decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int nc = bq_ragged_length(lengths1, cloud, n);
-    const int q0 = part * qpb;
-    const size_t rows = (size_t)cloud * m;
-    bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, m), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
-                          xyz1 + (size_t)cloud * n * 3, xyz2 + rows * 3, subtract, rows, smem);
-}
-
-// Ragged on both sides (pn2_query_ball_group_xyz_msg_ragged_pair): cloud c also holds only m_c = lengths2[c] valid queries. The
-// body gets the query range cut at m_c; the workgroup's rows from m_c on are filled for EVERY radius (idx 0, pts_cnt 0, grouped
-// +0.0), and a workgroup of such rows alone leaves before any staging or binning (block-uniform).
-template <int NT>
-__global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_ragged_pair_kernel(int b, int n, int m, int qpb, int parts,
-                                                                                int use_cells, int max_ns, int wave_stride_b,
-                                                                                BqScales sc, const float *__restrict__ xyz1,
-                                                                                const int *__restrict__ lengths1,
-                                                                                const float *__restrict__ xyz2,
-                                                                                const int *__restrict__ lengths2, int subtract)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int cloud, part;
-    decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int nc = bq_ragged_length(lengths1, cloud, n);
-    const int mc = bq_ragged_count(lengths2, cloud, m);
-    const int q0 = part * qpb;
-    const size_t rows = (size_t)cloud * m;
-    const int f0 = max(q0, mc), f1 = min(q0 + qpb, m);
-    if (f0 < f1) {                                               // block-uniform
-        for (int i = 0; i < sc.count; ++i) {
-            const BqScale &s = sc.s[i];
-            bq_fill_rows<NT>(f0, f1, s.nsample, s.idx ? s.idx + rows * (size_t)s.nsample : nullptr, s.cnt ? s.cnt + rows : nullptr,
-                             s.grouped ? s.grouped + rows * (size_t)s.nsample * 3 : nullptr);
+    if constexpr (sizeof...(Cnt) == 0) {
+        const int q0 = part * qpb;
+        bq_msg_block_body<NT>(n, m, cloud, q0, min(q0 + qpb, m), use_cells, max_ns, wave_stride_b, sc, xyz1, xyz2, subtract, 0, smem);
+    } else {
+        const int nc = cloud_count(counts.side[0], cloud, n);
+        int mc = m;
+        if constexpr (sizeof...(Cnt) == 2) mc = cloud_count(counts.side[1], cloud, m);
+        const int q0 = part * qpb;
+        const size_t rows = (size_t)cloud * m;
+        if constexpr (sizeof...(Cnt) == 2) {
+            const int f0 = max(q0, mc), f1 = min(q0 + qpb, m);
+            if (f0 < f1) {                                           // block-uniform
+                for (int i = 0; i < sc.count; ++i) {
+                    const BqScale &s = sc.s[i];
+                    bq_fill_rows<NT>(f0, f1, s.nsample, s.idx ? s.idx + rows * (size_t)s.nsample : nullptr, s.cnt ? s.cnt + rows : nullptr,
+                                     s.grouped ? s.grouped + rows * (size_t)s.nsample * 3 : nullptr);
+                }
+            }
+            if (q0 >= mc) return;
         }
+        bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, mc), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
+                              xyz1 + (size_t)cloud * n * 3, xyz2 + rows * 3, subtract, rows, smem);
     }
-    if (q0 >= mc) return;
-    bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, mc), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
-                          xyz1 + (size_t)cloud * n * 3, xyz2 + rows * 3, subtract, rows, smem);
 }
 
 static size_t msg_sweep_bytes(int n, int max_ns, int nthreads)
@@ -300,22 +278,10 @@ template <int NT>
 static int launch_msg(int b, int n, int m, const MsgPlan &p, const float *xyz1, const int *lengths1, const float *xyz2, int subtract,
                       hipStream_t st, const int *lengths2 = nullptr)
 {
-    if (lengths2) {
-        auto kern = ball_query_msg_ragged_pair_kernel<NT>;
-        if (int rc = allow_dynamic_lds(kern, p.lds)) return rc;
-        return launch(kern, dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
-                      (int)p.wave_stride, p.sc, xyz1, lengths1, xyz2, lengths2, subtract);
-    }
-    if (lengths1) {                                              // the same plan: every host decision is taken from the padded n
-        auto kern = ball_query_msg_ragged_kernel<NT>;
-        if (int rc = allow_dynamic_lds(kern, p.lds)) return rc;
-        return launch(kern, dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
-                      (int)p.wave_stride, p.sc, xyz1, lengths1, xyz2, subtract);
-    }
-    auto kern = ball_query_msg_kernel<NT>;
-    if (int rc = allow_dynamic_lds(kern, p.lds)) return rc;
-    return launch(kern, dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
-                  (int)p.wave_stride, p.sc, xyz1, xyz2, subtract);
+    // with counts the same plan: every host decision is taken from the padded n
+    return launch_counts([](auto... c) { return ball_query_msg_kernel<NT, decltype(c)...>; }, lengths1, lengths2,
+                         dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
+                         (int)p.wave_stride, p.sc, xyz1, xyz2, subtract);
 }
 
 }  // namespace pn2
@@ -337,8 +303,8 @@ extern "C" int pn2_query_ball_group_xyz_msg_plan(int b, int n, int m, int nscale
     return rc;
 }
 
-// lengths1: NULL = every cloud holds n points (the dense kernel); else the ragged kernel; lengths2 (with lengths1 only): the
-// valid queries per cloud, the ragged-pair kernel
+// lengths1: NULL = every cloud holds n points; else the points per cloud; lengths2 (with lengths1 only): the valid queries per
+// cloud (the kernel's count modes)
 static int msg_run(int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *xyz1, const int *lengths1,
                    const float *xyz2, int subtract_centroid, int *const *idx, int *const *pts_cnt, float *const *grouped_xyz,
                    void *stream, const int *lengths2 = nullptr)
@@ -368,19 +334,29 @@ extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, co
     return msg_run(b, n, m, nscales, radii, nsamples, xyz1, nullptr, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream);
 }
 
+// The ragged entries' prologue, codes in the order of the single-radius ragged entries: attributes and extents, then nothing to
+// do, then the `sides` count arrays the entry requires, then the dense entry's remaining checks.
+static int msg_run_ragged(int sides, int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *xyz1,
+                          const int *lengths1, const float *xyz2, const int *lengths2, int subtract_centroid, int *const *idx,
+                          int *const *pts_cnt, float *const *grouped_xyz, void *stream)
+{
+    if (int rc = pn2::msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (!lengths1 || (sides == 2 && !lengths2)) return PN2_E_NULL;
+    return msg_run(b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream,
+                   lengths2);
+}
+
 // Ragged batch: cloud c of xyz1 is xyz1[c, :lengths1[c]] of a padded (b, n, 3) tensor, lengths1 (b) int32 on the device, never
 // read by the host; the queries xyz2 (b, m, 3) are dense. Result per cloud and radius = pn2_query_ball_group_xyz_msg on the
-// slice = pn2_query_ball_group_xyz_ragged per radius. Codes in the order of the single-radius ragged entry: attributes and
-// extents, then nothing to do, then a NULL lengths1, then the dense entry's remaining checks.
+// slice = pn2_query_ball_group_xyz_ragged per radius.
 extern "C" int pn2_query_ball_group_xyz_msg_ragged(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
                                                    const float *xyz1, const int *lengths1, const float *xyz2,
                                                    int subtract_centroid, int *const *idx, int *const *pts_cnt,
                                                    float *const *grouped_xyz, void *stream)
 {
-    if (int rc = pn2::msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
-    if (b == 0 || m == 0) return PN2_OK;
-    if (!lengths1) return PN2_E_NULL;
-    return msg_run(b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream);
+    return msg_run_ragged(1, b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, nullptr, subtract_centroid, idx, pts_cnt,
+                          grouped_xyz, stream);
 }
 
 // Ragged on both sides: cloud c additionally holds only lengths2[c] valid rows of xyz2 (clamped into 1..m on the device). Rows
@@ -392,9 +368,6 @@ extern "C" int pn2_query_ball_group_xyz_msg_ragged_pair(int b, int n, int m, int
                                                         const int *lengths2, int subtract_centroid, int *const *idx,
                                                         int *const *pts_cnt, float *const *grouped_xyz, void *stream)
 {
-    if (int rc = pn2::msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
-    if (b == 0 || m == 0) return PN2_OK;
-    if (!lengths1 || !lengths2) return PN2_E_NULL;
-    return msg_run(b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream,
-                   lengths2);
+    return msg_run_ragged(2, b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, lengths2, subtract_centroid, idx, pts_cnt,
+                          grouped_xyz, stream);
 }

@@ -55,26 +55,13 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(int n, int m, int Q, const f
 // workgroup hands the body its own slab as cloud 0 with n = n_c and Q = ceil(n_c / 512): the tie ranks, the dealing and the
 // padding slots are then exactly those of the dense kernel on the slice, and rows at or beyond n_c are never addressed
 // (fps_body.h: valid = ... && k < n). T, P and the LDS size come from the padded n: T P >= 512 ceil(n / 512) >= 512 Q_c.
-// The length is clamped into 1..n for memory safety only (check_lengths is the validation).
-template <int T, int P, bool LDSXYZ>
-__global__ __launch_bounds__(T) void fps_reg_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
-                                                           int *__restrict__ out, float *__restrict__ out_xyz)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int c = blockIdx.x;
-    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[c]), 1), n);
-    const int Qc = (nc + kRefThreads - 1) / kRefThreads;
-    fps_reg_body<T, P, LDSXYZ, false>(nc, m, Qc, 0, xyz + (size_t)c * n * 3, out + (size_t)c * m,
-                                      out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr, nullptr, smem);
-}
-
-// Ragged batch with a sample count per cloud (pn2_farthest_point_sample_ragged_counts): cloud c yields m_c = npoints[c] samples
-// of its n_c points, both clamped for memory safety only. The body runs with m = m_c on the cloud's slab, so rows below m_c are
+// COUNTS, a sample count per cloud (pn2_farthest_point_sample_ragged_counts): cloud c yields m_c = npoints[c] samples of its n_c
+// points (both counts: cloud_count, pn2_device.h). The body runs with m = m_c on the cloud's slab, so rows below m_c are
 // the first m_c samples of the dense operator on the slice (the chain is prefix-consistent: round j depends on rounds < j
 // alone). Rows m_c .. m-1 repeat sample 0, the way a ball query pads with its first hit; sample 0 is point 0 by the reference's
 // rule (tf_sampling_g.cu:114-116), so the fill is index 0 and xyz[c, 0] and reads nothing back. The fill rows are disjoint from
 // the body's, so no barrier stands between the two. (The fill is a function of its own: the wrappers of the other two tiers
-// below end with it too.)
+// below end with it too.) Without COUNTS npoints is never read.
 template <int T>
 __device__ __forceinline__ void fps_ragged_fill(int mc, int m, const float *__restrict__ src, int *__restrict__ dst, float *__restrict__ dxyz)
 {
@@ -87,21 +74,21 @@ __device__ __forceinline__ void fps_ragged_fill(int mc, int m, const float *__re
     }
 }
 
-template <int T, int P, bool LDSXYZ>
-__global__ __launch_bounds__(T) void fps_reg_ragged_counts_kernel(int n, int m, const float *__restrict__ xyz,
-                                                                  const int *__restrict__ lengths, const int *__restrict__ npoints,
-                                                                  int *__restrict__ out, float *__restrict__ out_xyz)
+template <int T, int P, bool LDSXYZ, bool COUNTS>
+__global__ __launch_bounds__(T) void fps_reg_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
+                                                           const int *__restrict__ npoints, int *__restrict__ out,
+                                                           float *__restrict__ out_xyz)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int c = blockIdx.x;
-    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[c]), 1), n);
-    const int mc = min(max(__builtin_amdgcn_readfirstlane(npoints[c]), 1), m);
+    const int nc = cloud_count(lengths, c, n);
+    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
     const int Qc = (nc + kRefThreads - 1) / kRefThreads;
     const float *__restrict__ src = xyz + (size_t)c * n * 3;
     int *__restrict__ dst = out + (size_t)c * m;
     float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
     fps_reg_body<T, P, LDSXYZ, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
-    fps_ragged_fill<T>(mc, m, src, dst, dxyz);
+    if (COUNTS) fps_ragged_fill<T>(mc, m, src, dst, dxyz);
 }
 
 // Pruned tier (fps_pruned_body.h): kd-grouped slots, per-round box tests, only the groups the new sample can reach are
@@ -134,7 +121,7 @@ __global__ __launch_bounds__(kBtT) void fps_batch_kernel(int n, int m, int Q, co
 // uncounted loop, the equal-keys rule, the value-0 tail, the slow-batch clock and the pruned tier's skipped reduction on such
 // clouds, and through the termination of every wait inside the workgroup (tests/test_fps_batch_padding_model.py is the CPU
 // model). n_c, m_c and Q_c are block-uniform scalars, so every wave of the workgroup -- the picker included -- executes the
-// barriers of the same chain. COUNTS: npoints is read and rows m_c .. m-1 are filled as in fps_reg_ragged_counts_kernel (index 0
+// barriers of the same chain. COUNTS: npoints is read and rows m_c .. m-1 are filled as in fps_reg_ragged_kernel (index 0
 // and xyz[c, 0]; disjoint from the body's rows, so no barrier stands in between).
 template <int P, int GS, bool COUNTS>
 __global__ __launch_bounds__(kPrT) void fps_pruned_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
@@ -143,8 +130,8 @@ __global__ __launch_bounds__(kPrT) void fps_pruned_ragged_kernel(int n, int m, c
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int c = blockIdx.x;
-    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[c]), 1), n);
-    const int mc = COUNTS ? min(max(__builtin_amdgcn_readfirstlane(npoints[c]), 1), m) : m;
+    const int nc = cloud_count(lengths, c, n);
+    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
     const int Qc = (nc + kRefThreads - 1) / kRefThreads;
     const float *__restrict__ src = xyz + (size_t)c * n * 3;
     int *__restrict__ dst = out + (size_t)c * m;
@@ -160,8 +147,8 @@ __global__ __launch_bounds__(kBtT) void fps_batch_ragged_kernel(int n, int m, co
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int c = blockIdx.x;
-    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[c]), 1), n);
-    const int mc = COUNTS ? min(max(__builtin_amdgcn_readfirstlane(npoints[c]), 1), m) : m;
+    const int nc = cloud_count(lengths, c, n);
+    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
     const int Qc = (nc + kRefThreads - 1) / kRefThreads;
     const float *__restrict__ src = xyz + (size_t)c * n * 3;
     int *__restrict__ dst = out + (size_t)c * m;
@@ -407,20 +394,14 @@ static int launch_reg(int b, int n, int m, int Q, const float *inp, int *out, fl
     return PN2_OK;
 }
 
-// npoints: NULL = m samples from every cloud (fps_reg_ragged_kernel); else the per-cloud sample counts
+// npoints: NULL = m samples from every cloud; else the per-cloud sample counts (COUNTS)
 template <int T, int P, bool LDSXYZ>
 static int launch_reg_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
                              hipStream_t st)
 {
     const size_t lds = 256 + (LDSXYZ ? sizeof(float4) : sizeof(int)) * (size_t)T * P;
-    if (npoints) {
-        auto kern = fps_reg_ragged_counts_kernel<T, P, LDSXYZ>;
-        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        return launch(kern, dim3(b), dim3(T), lds, st, n, m, inp, lengths, npoints, out, oxyz);
-    }
-    auto kern = fps_reg_ragged_kernel<T, P, LDSXYZ>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3(b), dim3(T), lds, st, n, m, inp, lengths, out, oxyz);
+    return launch_lds(npoints ? fps_reg_ragged_kernel<T, P, LDSXYZ, true> : fps_reg_ragged_kernel<T, P, LDSXYZ, false>, dim3(b), dim3(T),
+                      lds, st, n, m, inp, lengths, npoints, out, oxyz);
 }
 
 template <int P, int GS>
@@ -475,15 +456,8 @@ template <int P, int GS>
 static int launch_pruned_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
                                 hipStream_t st)
 {
-    const size_t lds = fps_pruned_lds_bytes(P);
-    if (npoints) {
-        auto kern = fps_pruned_ragged_kernel<P, GS, true>;
-        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        return launch(kern, dim3(b), dim3(kPrT), lds, st, n, m, inp, lengths, npoints, out, oxyz);
-    }
-    auto kern = fps_pruned_ragged_kernel<P, GS, false>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3(b), dim3(kPrT), lds, st, n, m, inp, lengths, npoints, out, oxyz);
+    return launch_lds(npoints ? fps_pruned_ragged_kernel<P, GS, true> : fps_pruned_ragged_kernel<P, GS, false>, dim3(b), dim3(kPrT),
+                      fps_pruned_lds_bytes(P), st, n, m, inp, lengths, npoints, out, oxyz);
 }
 
 static int fps_launch_pruned_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
@@ -499,15 +473,8 @@ template <int P, int GS>
 static int launch_batch_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
                                hipStream_t st)
 {
-    const size_t lds = fps_batch_lds_bytes(P);
-    if (npoints) {
-        auto kern = fps_batch_ragged_kernel<P, GS, true>;
-        if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-        return launch(kern, dim3(b), dim3(kBtT), lds, st, n, m, inp, lengths, npoints, out, oxyz);
-    }
-    auto kern = fps_batch_ragged_kernel<P, GS, false>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3(b), dim3(kBtT), lds, st, n, m, inp, lengths, npoints, out, oxyz);
+    return launch_lds(npoints ? fps_batch_ragged_kernel<P, GS, true> : fps_batch_ragged_kernel<P, GS, false>, dim3(b), dim3(kBtT),
+                      fps_batch_lds_bytes(P), st, n, m, inp, lengths, npoints, out, oxyz);
 }
 
 static int fps_launch_batch_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,

@@ -78,7 +78,7 @@ __device__ __forceinline__ void nn_zero_row(float *__restrict__ od, int *__restr
 // Workgroup body of the sweep. nv = valid unknown points of cloud bi: n in the dense kernel; in the ragged one the cloud's own
 // length -- rows nv .. n-1 are then zero-filled and never read (RAGGED; the dense instantiation has none of it).
 // m: the known points swept; m_stride: rows between two clouds' known points when that is not m (the ragged KNOWN side,
-// three_nn_ragged_pair_kernel: m = the cloud's own count) -- a literal 0 everywhere else, which folds away.
+// three_nn_kernel with two count arrays: m = the cloud's own count) -- a literal 0 everywhere else, which folds away.
 template <bool RAGGED>
 __device__ __forceinline__ void three_nn_sweep_body(int n, int nv, int m, int bi, const float *__restrict__ xyz1,
                                                     const float *__restrict__ xyz2, float *__restrict__ dist,
@@ -139,38 +139,26 @@ __device__ __forceinline__ void three_nn_sweep_body(int n, int nv, int m, int bi
     if (RAGGED && !live && j < n && sub == 0) nn_zero_row(dist + ((size_t)bi * n + j) * 3, idx + ((size_t)bi * n + j) * 3);
 }
 
+// One kernel, three modes (pn2_device.h: Counts). No count array: the dense kernel. One (pn2_three_nn_ragged): cloud c has
+// lengths[c] <= n unknown points, the known side is dense. Two (pn2_three_nn_ragged_pair): cloud c also holds only lengths2[c]
+// of its m known points; the sweep runs on those alone (rows at or beyond the count are never read), and fewer than three
+// leave the (+inf, 0) entries of the dense operator.
+template <class... Cnt>
 __global__ __launch_bounds__(kNnThreads) void three_nn_kernel(int n, int m, const float *__restrict__ xyz1,
                                                               const float *__restrict__ xyz2,
-                                                              float *__restrict__ dist, int *__restrict__ idx)
+                                                              float *__restrict__ dist, int *__restrict__ idx, Cnt __restrict__... cnt)
 {
     __shared__ float4 tile[kNnTile];
-    three_nn_sweep_body<false>(n, n, m, blockIdx.y, xyz1, xyz2, dist, idx, tile);
-}
-
-// Ragged unknown side (pn2_three_nn_ragged): cloud c has lengths[c] <= n unknown points; the known side is dense. The length
-// is clamped into 1..n for memory safety only.
-__global__ __launch_bounds__(kNnThreads) void three_nn_ragged_kernel(int n, int m, const float *__restrict__ xyz1,
-                                                                     const int *__restrict__ lengths,
-                                                                     const float *__restrict__ xyz2,
-                                                                     float *__restrict__ dist, int *__restrict__ idx)
-{
-    __shared__ float4 tile[kNnTile];
-    const int nv = min(max(__builtin_amdgcn_readfirstlane(lengths[blockIdx.y]), 1), n);
-    three_nn_sweep_body<true>(n, nv, m, blockIdx.y, xyz1, xyz2, dist, idx, tile);
-}
-
-// Ragged on both sides (pn2_three_nn_ragged_pair): cloud c also holds only lengths2[c] of its m known points. The sweep runs on
-// those alone (rows at or beyond the count are never read); fewer than three leave the (+inf, 0) entries of the dense operator.
-__global__ __launch_bounds__(kNnThreads) void three_nn_ragged_pair_kernel(int n, int m, const float *__restrict__ xyz1,
-                                                                          const int *__restrict__ lengths,
-                                                                          const float *__restrict__ xyz2,
-                                                                          const int *__restrict__ lengths2,
-                                                                          float *__restrict__ dist, int *__restrict__ idx)
-{
-    __shared__ float4 tile[kNnTile];
-    const int nv = min(max(__builtin_amdgcn_readfirstlane(lengths[blockIdx.y]), 1), n);
-    const int mc = min(max(__builtin_amdgcn_readfirstlane(lengths2[blockIdx.y]), 1), m);
-    three_nn_sweep_body<true>(n, nv, mc, blockIdx.y, xyz1, xyz2, dist, idx, tile, m);
+    const Counts<Cnt...> counts(cnt...);
+    if constexpr (sizeof...(Cnt) == 0) {
+        three_nn_sweep_body<false>(n, n, m, blockIdx.y, xyz1, xyz2, dist, idx, tile);
+    } else {
+        const int nv = cloud_count(counts.side[0], blockIdx.y, n);
+        if constexpr (sizeof...(Cnt) == 2)
+            three_nn_sweep_body<true>(n, nv, cloud_count(counts.side[1], blockIdx.y, m), blockIdx.y, xyz1, xyz2, dist, idx, tile, m);
+        else
+            three_nn_sweep_body<true>(n, nv, m, blockIdx.y, xyz1, xyz2, dist, idx, tile);
+    }
 }
 
 
@@ -226,8 +214,8 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
     int *fail = reinterpret_cast<int *>(reinterpret_cast<char *>(misc) + kBqMiscBytes); // [0] = count, [1 ..] = rows to sweep
     int cloud, part;
     decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int nv = RAGGED ? min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n) : n;
-    const int mk = PAIR ? min(max(__builtin_amdgcn_readfirstlane(lengths2[cloud]), 1), m) : m;
+    const int nv = RAGGED ? cloud_count(lengths, cloud, n) : n;
+    const int mk = PAIR ? cloud_count(lengths2, cloud, m) : m;
     const int rb = part * rows_per_part, re = min(rb + rows_per_part, nv);
     const float *__restrict__ known = xyz2 + (size_t)cloud * m * 3;
     const float *__restrict__ unk = xyz1 + (size_t)cloud * n * 3;
@@ -352,34 +340,15 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
     }
 }
 
-template <int NT>
+template <int NT, class... Cnt>
 __global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_kernel(int n, int m, int rows_per_part, int parts, int b, float factor,
                                                             const float *__restrict__ xyz1, const float *__restrict__ xyz2,
-                                                            float *__restrict__ dist, int *__restrict__ idx)
+                                                            float *__restrict__ dist, int *__restrict__ idx, Cnt __restrict__... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    three_nn_cells_body<NT, false>(n, m, rows_per_part, parts, b, factor, xyz1, nullptr, xyz2, dist, idx, smem);
-}
-
-template <int NT>
-__global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_ragged_kernel(int n, int m, int rows_per_part, int parts, int b,
-                                                            float factor, const float *__restrict__ xyz1,
-                                                            const int *__restrict__ lengths, const float *__restrict__ xyz2,
-                                                            float *__restrict__ dist, int *__restrict__ idx)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    three_nn_cells_body<NT, true>(n, m, rows_per_part, parts, b, factor, xyz1, lengths, xyz2, dist, idx, smem);
-}
-
-template <int NT>
-__global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_ragged_pair_kernel(int n, int m, int rows_per_part, int parts, int b,
-                                                            float factor, const float *__restrict__ xyz1,
-                                                            const int *__restrict__ lengths, const float *__restrict__ xyz2,
-                                                            const int *__restrict__ lengths2, float *__restrict__ dist,
-                                                            int *__restrict__ idx)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    three_nn_cells_body<NT, true, true>(n, m, rows_per_part, parts, b, factor, xyz1, lengths, xyz2, dist, idx, smem, lengths2);
+    const Counts<Cnt...> counts(cnt...);
+    three_nn_cells_body<NT, sizeof...(Cnt) != 0, sizeof...(Cnt) == 2>(n, m, rows_per_part, parts, b, factor, xyz1, counts.side[0], xyz2, dist,
+                                                                      idx, smem, counts.side[1]);
 }
 
 static size_t three_nn_cells_lds(int m, int rows_per_part)
@@ -659,8 +628,8 @@ extern "C" int pn2_fp_interp_concat_grad_planned(int b, int n, int m, int c2, in
 
 // variant: 0 = the library's choice, 1 = the sweep (three_nn_kernel), 2 = the cell list (PN2_E_ARG where it does not exist:
 // fewer than 64 or more than 8192 known points)
-// lengths: NULL = the dense kernels; else the ragged ones (valid unknown points per cloud, device memory); lengths2 (with
-// lengths only): valid known points per cloud, the ragged-pair kernels
+// lengths: NULL = dense; else the valid unknown points per cloud (device memory); lengths2 (with lengths only): the valid known
+// points per cloud (the count modes of the two kernels)
 static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx, int variant, void *stream,
                           const int *lengths = nullptr, const int *lengths2 = nullptr)
 {
@@ -685,37 +654,16 @@ static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *x
         const int parts = (n + rows - 1) / rows;
         const size_t lds = three_nn_cells_lds(m, rows);
 #define PN2_NN_CELLS(NT)                                                                                                          \
-        {                                                                                                                         \
-            if (lengths2) {                                                                                                       \
-                auto kern = three_nn_cells_ragged_pair_kernel<NT>;                                                                \
-                if (int rc = allow_dynamic_lds(kern, lds)) return rc;                                                             \
-                return launch(kern, dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor,  \
-                              xyz1, lengths, xyz2, lengths2, dist, idx);                                                          \
-            }                                                                                                                     \
-            if (lengths) {                                                                                                        \
-                auto kern = three_nn_cells_ragged_kernel<NT>;                                                                     \
-                if (int rc = allow_dynamic_lds(kern, lds)) return rc;                                                             \
-                return launch(kern, dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor,  \
-                              xyz1, lengths, xyz2, dist, idx);                                                                    \
-            }                                                                                                                     \
-            auto kern = three_nn_cells_kernel<NT>;                                                                                \
-            if (int rc = allow_dynamic_lds(kern, lds)) return rc;                                                                 \
-            return launch(kern, dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor, xyz1, xyz2,  \
-                          dist, idx);                                                                                             \
-        }
+        return launch_counts([](auto... c) { return three_nn_cells_kernel<NT, decltype(c)...>; }, lengths, lengths2,              \
+                             dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor, xyz1, xyz2,  \
+                             dist, idx);
         if (lab_nt == 256) PN2_NN_CELLS(256)
         if (lab_nt == 1024) PN2_NN_CELLS(1024)
         PN2_NN_CELLS(kNnCellsThreads)
 #undef PN2_NN_CELLS
     }
-    if (lengths2)
-        return launch(three_nn_ragged_pair_kernel, dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n,
-                      m, xyz1, lengths, xyz2, lengths2, dist, idx);
-    if (lengths)
-        return launch(three_nn_ragged_kernel, dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n, m,
-                      xyz1, lengths, xyz2, dist, idx);
-    return launch(three_nn_kernel, dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n, m, xyz1, xyz2,
-                  dist, idx);
+    return launch_counts([](auto... c) { return three_nn_kernel<decltype(c)...>; }, lengths, lengths2,
+                         dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n, m, xyz1, xyz2, dist, idx);
 }
 
 extern "C" int pn2_three_nn(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx,
@@ -730,17 +678,24 @@ extern "C" int pn2_three_nn_ex(int b, int n, int m, const float *xyz1, const flo
     return three_nn_entry(b, n, m, xyz1, xyz2, dist, idx, variant, stream);
 }
 
+// The ragged entries' prologue; `sides` = the count arrays the entry requires
+static int three_nn_ragged(int sides, int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2, const int *lengths2,
+                           float *dist, int *idx, int variant, void *stream)
+{
+    if (variant < 0 || variant > 2) return PN2_E_ARG;
+    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;     // a cloud holds at least one unknown point
+    if (b == 0) return PN2_OK;
+    if (!lengths1 || (sides == 2 && !lengths2)) return PN2_E_NULL;
+    return three_nn_entry(b, n, m, xyz1, xyz2, dist, idx, variant, stream, lengths1, lengths2);
+}
+
 // Ragged unknown side: cloud c of xyz1 is xyz1[c, :lengths1[c]] of a padded (b, n, 3) tensor, lengths1 (b) int32 on the device,
 // never read by the host; xyz2 (b, m, 3) is dense. Valid rows = pn2_three_nn_ex on the slice for every variant; rows at or
 // beyond lengths1[c] are written as idx (0,0,0), dist (0,0,0).
 extern "C" int pn2_three_nn_ragged(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2, float *dist, int *idx,
                                    int variant, void *stream)
 {
-    if (variant < 0 || variant > 2) return PN2_E_ARG;
-    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;     // a cloud holds at least one unknown point
-    if (b == 0) return PN2_OK;
-    if (!lengths1) return PN2_E_NULL;
-    return three_nn_entry(b, n, m, xyz1, xyz2, dist, idx, variant, stream, lengths1);
+    return three_nn_ragged(1, b, n, m, xyz1, lengths1, xyz2, nullptr, dist, idx, variant, stream);
 }
 
 // Ragged on both sides: cloud c additionally holds only lengths2[c] of its m known points (b int32 on the device, clamped into
@@ -751,11 +706,7 @@ extern "C" int pn2_three_nn_ragged(int b, int n, int m, const float *xyz1, const
 extern "C" int pn2_three_nn_ragged_pair(int b, int n, int m, const float *xyz1, const int *lengths1, const float *xyz2,
                                         const int *lengths2, float *dist, int *idx, int variant, void *stream)
 {
-    if (variant < 0 || variant > 2) return PN2_E_ARG;
-    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
-    if (b == 0) return PN2_OK;
-    if (!lengths1 || !lengths2) return PN2_E_NULL;
-    return three_nn_entry(b, n, m, xyz1, xyz2, dist, idx, variant, stream, lengths1, lengths2);
+    return three_nn_ragged(2, b, n, m, xyz1, lengths1, xyz2, lengths2, dist, idx, variant, stream);
 }
 
 static int three_interpolate_entry(int b, int m, int c, int n, const float *points, const int *idx, const float *weight,

@@ -11,6 +11,7 @@
 
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 
@@ -109,6 +110,25 @@ __device__ __forceinline__ void decode_cloud_block(unsigned i, int parts, int b,
     }
 }
 
+// ---- ragged batches: counts are a MODE of a family's one kernel, not a sibling kernel -----------------------------------------
+// A geometry kernel ends its parameter list with a pack `Cnt... cnt` of per-cloud count arrays ((b) int32 on the device, never
+// read by the host): none = the dense kernel, with exactly the dense argument list; one = counts on the first side (points of
+// xyz1); two = counts on both sides (valid rows of xyz2 as well). A kernel branches on sizeof...(Cnt) with `if constexpr` and
+// reads the arrays through Counts<Cnt...>.
+template <class... Cnt>
+struct Counts {
+    static_assert(sizeof...(Cnt) <= 2 && (std::is_same<Cnt, const int *>::value && ...), "at most two arrays of int counts");
+    const int *side[2];                                   // NULL past the arrays given
+    __device__ __forceinline__ Counts(Cnt... c) : side{c...} {}
+};
+
+// The count of cloud `cloud` (its points, queries or samples), clamped into 1..extent for memory safety only -- validation is
+// the caller's business (check_lengths); wave-uniform.
+__device__ __forceinline__ int cloud_count(const int *__restrict__ counts, size_t cloud, int extent)
+{
+    return min(max(__builtin_amdgcn_readfirstlane(counts[cloud]), 1), extent);
+}
+
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- host side: launching ---------------------------------------------------------------------
@@ -193,6 +213,25 @@ inline int allow_dynamic_lds(K kern, size_t bytes)
     }
     granted[key] = want;
     return 0;
+}
+
+// allow_dynamic_lds, then launch
+template <typename K, typename... Args>
+inline int launch_lds(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args)
+{
+    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
+    return launch(kern, grid, block, lds, st, args...);
+}
+
+// The one launch of a kernel family whose parameter list ends with a pack of count arrays (Counts above). `pick(c...)` returns
+// the instantiation for the pack it is given -- [](auto... c) { return some_kernel<..., decltype(c)...>; } --; counts1 / counts2
+// NULL choose how many arrays are passed (counts2 only with counts1), and they follow `args` as the kernel's last arguments.
+template <class Pick, typename... Args>
+inline int launch_counts(Pick pick, const int *counts1, const int *counts2, dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                         Args... args)
+{
+    auto go = [&](auto... c) { return launch_lds(pick(c...), grid, block, lds, st, args..., c...); };
+    return counts2 ? go(counts1, counts2) : counts1 ? go(counts1) : go();
 }
 
 // Workgroups of `kern` (threads, dynamic LDS bytes) the current device can hold at once: occupancy query x CU

@@ -272,64 +272,44 @@ __device__ __forceinline__ void knn_wave_body(int n, int k, const float *__restr
     }
 }
 
+// One kernel, three modes (pn2_device.h: Counts). No count array: the dense kernel. With counts (pn2_knn_point_ragged): the
+// query's cloud holds lengths[cloud] <= n points in its padded slab; the body runs on those alone (LDS laid out for n_c, sized
+// on the host for n). k > n_c: the row's entries from n_c on repeat entry 0, the way a ball query pads with its first hit, so
+// every row is fully written. Counts on both sides (pn2_knn_point_ragged_pair): cloud c also holds only lengths2[c] valid
+// queries. A wave whose row is at or beyond that count writes idx 0 / val +0.0 into the whole row and leaves -- its query is
+// never read (wave = workgroup here).
+template <class... Cnt>
 __global__ __launch_bounds__(64) void knn_wave_kernel(int n, int m, int k, const float *__restrict__ xyz1,
                                                       const float *__restrict__ xyz2, float *__restrict__ oval,
-                                                      int *__restrict__ oidx)
+                                                      int *__restrict__ oidx, Cnt __restrict__... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const Counts<Cnt...> counts(cnt...);
     const size_t row = blockIdx.x;                               // query number over all clouds
     const size_t cloud = row / m;
-    knn_wave_body(n, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
-}
-
-// Ragged batch (pn2_knn_point_ragged): the query's cloud holds lengths[cloud] <= n points in its padded slab; the body runs
-// on those alone (LDS laid out for n_c, sized on the host for n). k > n_c: the row's entries from n_c on repeat entry 0, the
-// way a ball query pads with its first hit, so every row is fully written. The length is clamped for memory safety only.
-__global__ __launch_bounds__(64) void knn_wave_ragged_kernel(int n, int m, int k, const float *__restrict__ xyz1,
-                                                             const int *__restrict__ lengths, const float *__restrict__ xyz2,
-                                                             float *__restrict__ oval, int *__restrict__ oidx)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const size_t row = blockIdx.x;
-    const size_t cloud = row / m;
-    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
-    knn_wave_body(nc, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
-    if (k > nc) {                                                // wave-uniform
-        float *ov = oval + row * k;
-        int *oi = oidx + row * k;
-        __syncthreads();                                         // one wave: orders the body's global stores before the reads below
-        __threadfence_block();
-        const float v0 = ov[0];
-        const int i0 = oi[0];
-        for (int s = nc + (int)threadIdx.x; s < k; s += 64) { ov[s] = v0; oi[s] = i0; }
-    }
-}
-
-// Ragged on both sides (pn2_knn_point_ragged_pair): cloud c also holds only lengths2[c] valid queries. A wave whose row is at
-// or beyond that count writes idx 0 / val +0.0 into the whole row and leaves -- its query is never read (wave = workgroup here).
-__global__ __launch_bounds__(64) void knn_wave_ragged_pair_kernel(int n, int m, int k, const float *__restrict__ xyz1,
-                                                                  const int *__restrict__ lengths, const float *__restrict__ xyz2,
-                                                                  const int *__restrict__ lengths2, float *__restrict__ oval,
-                                                                  int *__restrict__ oidx)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const size_t row = blockIdx.x;
-    const size_t cloud = row / m;
-    const int mc = min(max(__builtin_amdgcn_readfirstlane(lengths2[cloud]), 1), m);
-    float *ov = oval + row * k;
-    int *oi = oidx + row * k;
-    if ((int)(row - cloud * m) >= mc) {                          // wave-uniform
-        for (int s = (int)threadIdx.x; s < k; s += 64) { ov[s] = 0.0f; oi[s] = 0; }
-        return;
-    }
-    const int nc = min(max(__builtin_amdgcn_readfirstlane(lengths[cloud]), 1), n);
-    knn_wave_body(nc, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
-    if (k > nc) {                                                // wave-uniform; as in knn_wave_ragged_kernel
-        __syncthreads();
-        __threadfence_block();
-        const float v0 = ov[0];
-        const int i0 = oi[0];
-        for (int s = nc + (int)threadIdx.x; s < k; s += 64) { ov[s] = v0; oi[s] = i0; }
+    if constexpr (sizeof...(Cnt) == 0) {
+        knn_wave_body(n, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
+    } else {
+        if constexpr (sizeof...(Cnt) == 2) {
+            const int mc = cloud_count(counts.side[1], cloud, m);
+            float *ov = oval + row * k;
+            int *oi = oidx + row * k;
+            if ((int)(row - cloud * m) >= mc) {                  // wave-uniform
+                for (int s = (int)threadIdx.x; s < k; s += 64) { ov[s] = 0.0f; oi[s] = 0; }
+                return;
+            }
+        }
+        const int nc = cloud_count(counts.side[0], cloud, n);
+        knn_wave_body(nc, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
+        if (k > nc) {                                            // wave-uniform
+            float *ov = oval + row * k;
+            int *oi = oidx + row * k;
+            __syncthreads();                                     // one wave: orders the body's global stores before the reads below
+            __threadfence_block();
+            const float v0 = ov[0];
+            const int i0 = oi[0];
+            for (int s = nc + (int)threadIdx.x; s < k; s += 64) { ov[s] = v0; oi[s] = i0; }
+        }
     }
 }
 
@@ -382,22 +362,27 @@ extern "C" int pn2_selection_sort(int b, int n, int m, int k, const float *dist,
     return PN2_OK;
 }
 
-extern "C" int pn2_knn_point(int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx,
-                             void *stream)
+// The three entries of knn_point; `sides` = the count arrays the entry requires (lengths1, then lengths2)
+static int knn_entry(int sides, int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2, const int *lengths2,
+                     float *val, int *idx, void *stream)
 {
     using namespace pn2;
     if (k <= 0) return PN2_E_ARG;                       // tf_grouping.cpp:113
     if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
     const long long rows = (long long)b * m;
     if (rows == 0) return PN2_OK;
-    if (!xyz1 || !xyz2 || !val || !idx) return PN2_E_NULL;
+    if (!xyz1 || (sides >= 1 && !lengths1) || !xyz2 || (sides == 2 && !lengths2) || !val || !idx) return PN2_E_NULL;
     if (rows > INT_MAX || k > n) return PN2_E_TOO_LARGE;   // k > n: tf.slice would fail in the reference as well
     if (n > kSortMaxLdsN - 2048) return PN2_E_TOO_LARGE;    // callers keep the matrix + pn2_selection_sort path
     const size_t lds = 8 * (size_t)n + sizeof(int) * (256 + 3 * (size_t)kKnnCap);
-    auto kern = knn_wave_kernel;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    if (int rc = launch(kern, dim3((unsigned)rows), dim3(64), lds, as_stream(stream), n, m, k, xyz1, xyz2, val, idx)) return rc;
-    return PN2_OK;
+    return launch_counts([](auto... c) { return knn_wave_kernel<decltype(c)...>; }, lengths1, lengths2, dim3((unsigned)rows), dim3(64),
+                         lds, as_stream(stream), n, m, k, xyz1, xyz2, val, idx);
+}
+
+extern "C" int pn2_knn_point(int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx,
+                             void *stream)
+{
+    return knn_entry(0, b, n, m, k, xyz1, nullptr, xyz2, nullptr, val, idx, stream);
 }
 
 // Ragged batch: cloud c of xyz1 is xyz1[c, :lengths1[c]] of a padded (b, n, 3) tensor, lengths1 (b) int32 on the device, never
@@ -405,18 +390,7 @@ extern "C" int pn2_knn_point(int b, int n, int m, int k, const float *xyz1, cons
 extern "C" int pn2_knn_point_ragged(int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2, float *val,
                                     int *idx, void *stream)
 {
-    using namespace pn2;
-    if (k <= 0) return PN2_E_ARG;
-    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
-    const long long rows = (long long)b * m;
-    if (rows == 0) return PN2_OK;
-    if (!xyz1 || !lengths1 || !xyz2 || !val || !idx) return PN2_E_NULL;
-    if (rows > INT_MAX || k > n) return PN2_E_TOO_LARGE;
-    if (n > kSortMaxLdsN - 2048) return PN2_E_TOO_LARGE;
-    const size_t lds = 8 * (size_t)n + sizeof(int) * (256 + 3 * (size_t)kKnnCap);
-    auto kern = knn_wave_ragged_kernel;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3((unsigned)rows), dim3(64), lds, as_stream(stream), n, m, k, xyz1, lengths1, xyz2, val, idx);
+    return knn_entry(1, b, n, m, k, xyz1, lengths1, xyz2, nullptr, val, idx, stream);
 }
 
 // Ragged on both sides: cloud c additionally holds only lengths2[c] valid rows of xyz2 (clamped into 1..m on the device). Rows
@@ -424,16 +398,5 @@ extern "C" int pn2_knn_point_ragged(int b, int n, int m, int k, const float *xyz
 extern "C" int pn2_knn_point_ragged_pair(int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2,
                                          const int *lengths2, float *val, int *idx, void *stream)
 {
-    using namespace pn2;
-    if (k <= 0) return PN2_E_ARG;
-    if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
-    const long long rows = (long long)b * m;
-    if (rows == 0) return PN2_OK;
-    if (!xyz1 || !lengths1 || !xyz2 || !lengths2 || !val || !idx) return PN2_E_NULL;
-    if (rows > INT_MAX || k > n) return PN2_E_TOO_LARGE;
-    if (n > kSortMaxLdsN - 2048) return PN2_E_TOO_LARGE;
-    const size_t lds = 8 * (size_t)n + sizeof(int) * (256 + 3 * (size_t)kKnnCap);
-    auto kern = knn_wave_ragged_pair_kernel;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3((unsigned)rows), dim3(64), lds, as_stream(stream), n, m, k, xyz1, lengths1, xyz2, lengths2, val, idx);
+    return knn_entry(2, b, n, m, k, xyz1, lengths1, xyz2, lengths2, val, idx, stream);
 }

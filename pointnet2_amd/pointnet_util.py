@@ -395,18 +395,12 @@ class PointnetSAModule(nn.Module):
             lengths = ragged_lengths(lengths, xyz.shape[0], xyz.device)
         if npoints is not None:
             npoints = ragged_lengths(npoints, xyz.shape[0], xyz.device, "npoints")
-            if self.knn:
-                fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths, npoints=npoints)
-                _, idx = knn_point(self.nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)
-            else:
-                fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True, lengths=lengths,
-                                                                   npoints=npoints)
-            return SAGeometry(new_xyz, idx, fps_idx, index_plan(idx, xyz.shape[1], "group") if plans else None)
         if self.knn:
-            fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths)
-            _, idx = knn_point(self.nsample, xyz, new_xyz, lengths1=lengths)
+            fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths, npoints=npoints)
+            _, idx = knn_point(self.nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)
         else:
-            fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True, lengths=lengths)
+            fps_idx, new_xyz, idx, _, _ = sample_and_group_xyz(self.npoint, self.radius, self.nsample, xyz, True, lengths=lengths,
+                                                               npoints=npoints)
         return SAGeometry(new_xyz, idx, fps_idx, index_plan(idx, xyz.shape[1], "group") if plans else None)
 
     def _forward_on(self, xyz, points, g, path=None):
@@ -716,10 +710,12 @@ class PointnetSAModuleMSG(nn.Module):
         npoints: (b,) per-cloud sample counts (see PointnetSAModule.geometry), with or without lengths: the two-sided ragged
         operators, one launch per radius or -- ragged_one_launch -- one for all; same bits."""
         if npoints is not None:
-            b, dev = xyz.shape[0], xyz.device
-            npoints = ragged_lengths(npoints, b, dev, "npoints")
-            if lengths is not None:
-                lengths = ragged_lengths(lengths, b, dev)
+            npoints = ragged_lengths(npoints, xyz.shape[0], xyz.device, "npoints")
+        if lengths is not None:
+            lengths = ragged_lengths(lengths, xyz.shape[0], xyz.device)
+        if lengths is None and npoints is None:
+            new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
+        else:
             fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths, npoints=npoints)
             if self.ragged_one_launch:
                 scales = [(i, g) for i, _, g in query_ball_group_xyz_msg(self.radius_list, self.nsample_list, xyz, new_xyz, True,
@@ -727,17 +723,6 @@ class PointnetSAModuleMSG(nn.Module):
             else:
                 scales = [query_ball_group_xyz(r, k, xyz, new_xyz, True, lengths1=lengths, lengths2=npoints)[0::2]
                           for r, k in zip(self.radius_list, self.nsample_list)]
-        elif lengths is not None:
-            lengths = ragged_lengths(lengths, xyz.shape[0], xyz.device)
-            fps_idx, new_xyz = farthest_point_sample_gather(self.npoint, xyz, lengths=lengths)
-            if self.ragged_one_launch:
-                scales = [(i, g) for i, _, g in query_ball_group_xyz_msg(self.radius_list, self.nsample_list, xyz, new_xyz, True,
-                                                                         lengths1=lengths)]
-            else:
-                scales = [query_ball_group_xyz(r, k, xyz, new_xyz, True, lengths1=lengths)[0::2]
-                          for r, k in zip(self.radius_list, self.nsample_list)]
-        else:
-            new_xyz, scales, fps_idx = self._group_scales(xyz, True, with_fps=True)
         return SAGeometry(new_xyz, [idx for idx, _ in scales], fps_idx,
                           [index_plan(idx, xyz.shape[1], "group") for idx, _ in scales] if plans else None)
 
@@ -888,6 +873,8 @@ class PointnetFPModule(nn.Module):
         self._pack_cache = None
         self._lvl_buffers = None
 
+    _level_buffers = PointnetSAModule._level_buffers
+
     def _plan_of(self, idx, m, plan=None):
         """The level's index plan: the geometry's, or (index_plans) one built here, behind the launch that wrote idx."""
         if plan is None and self.index_plans and torch.is_grad_enabled():
@@ -1002,10 +989,7 @@ class PointnetFPModule(nn.Module):
                 if geometry is not None:
                     g = geometry.wait()
                     return sa_mlp.fp_mlp(points2, points1, g.idx, g.dist, packed, lengths1=lens)
-                if self.reuse_buffers and self._lvl_buffers is None:
-                    self._lvl_buffers = sa_mlp.LevelBuffers()
-                return sa_mlp.fp_level_ragged(xyz1, xyz2, points1, points2, packed, lens, lengths2,
-                                              self._lvl_buffers if self.reuse_buffers else None)
+                return sa_mlp.fp_level_ragged(xyz1, xyz2, points1, points2, packed, lens, lengths2, self._level_buffers())
         valid = torch.arange(n, device=dev, dtype=torch.int32).unsqueeze(0) < lens.unsqueeze(1)      # (b, n), no host sync
         if geometry is not None:
             g = geometry.wait()
@@ -1048,10 +1032,8 @@ class PointnetFPModule(nn.Module):
             # layer stack (:211-226)
             self.last_path = "fused"
             c1 = points1.shape[2] if points1 is not None else 0
-            if self.reuse_buffers and self._lvl_buffers is None:
-                self._lvl_buffers = sa_mlp.LevelBuffers()
             return sa_mlp.fp_level(xyz1, xyz2, points1, points2, self._packed(points2.shape[2], c1, kind, points2.device),
-                                   self._lvl_buffers if self.reuse_buffers else None)
+                                   self._level_buffers())
         return self._stack_on(xyz1, points1, points2, FPGeometry(*three_nn(xyz1, xyz2)))                  # :211
 
     def _after_weights(self, points1, points2, idx, weight, plan=None):

@@ -7,7 +7,10 @@ kernel_resources.py: two listings diff cleanly, and an unchanged line means the 
 Every object of pointnet2_amd/csrc/Makefile is compiled once more with its own flags (asked of `make -n`), device side only,
 to assembly. A kernel's text is what stands between its label and its .Lfunc_end label, without comments and blank lines;
 basic-block labels carry the function's number within its file (.LBB<function>_<block>), which moves when another function
-is added in front of it, so that number is dropped. One line per kernel, sorted:
+is added in front of it, so that number is dropped. The text runs on through the kernel's descriptor (.amdhsa_* : registers,
+kernel-argument bytes), which names the kernel's own mangled symbol; that name is replaced by a placeholder and the section
+directives around the descriptor (.text, or a template instantiation's own comdat section) are left out, so a kernel that
+only changes its name or becomes a template (one that gains an empty parameter pack) keeps its hash. One line per kernel, sorted:
 
     source  kernel(demangled)  instructions  sha256 of the text
 """
@@ -46,8 +49,8 @@ def listing(csrc, args):
             rows.append((name, text))
             name = None
             continue
-        code = re.sub(r"\.LBB\d+_", ".LBB_", line.split(";")[0]).strip()
-        if code:
+        code = re.sub(r"\.LBB\d+_", ".LBB_", line.split(";")[0]).replace(name, "<kernel>").strip()
+        if code and code != ".text" and not code.startswith(".section"):
             text.append(code)
     names = [n for n, _ in rows]
     plain = subprocess.run(["c++filt", "-p"] + names, capture_output=True, text=True).stdout.splitlines() if names else []
