@@ -499,6 +499,31 @@ int pn2_farthest_point_sample_ragged_variant(int variant, int b, int n, int m, c
                                              const int *npoints /* NULL: m samples from every cloud */,
                                              int *out, float *out_xyz /* may be NULL */, void *stream);
 
+/* farthest_point_sample [+ gather_point when out_xyz != NULL] for LARGE dense clouds, 16384 < n <= 1048576: the tier of
+ * csrc/fps_large.hip. Same indices as pn2_farthest_point_sample, tie rule (smallest (k mod 512, k)), inf
+ * distances clamped to the 1e38 start value, duplicates and m > n included; out_xyz == gather_point(inp, out) bit for bit, written
+ * as the samples are chosen. One launch of one workgroup per cloud: the cloud is sorted into the cells of a grid (records
+ * {x, y, z, k} in ws), cut into groups of group_len consecutive records with tight boxes, and a round updates only the groups the
+ * new sample can reach (the pruned tier's exact rule). No memset, no host synchronisation, capturable.
+ *   pn2_fps_large_supported(n, m)  1 inside the envelope (16384 < n <= 1048576, m >= 1), else 0;
+ *   pn2_fps_large_pays(n, m)       1 where the tier measured faster than the global-memory kernel of pn2_farthest_point_sample on
+ *                                  uniform AND sphere-surface clouds by more than the spread of the measurement
+ *                                  (profiles/fps_large/README.md); the Python operators follow it;
+ *   pn2_fps_large_ws_bytes(b, n)   size of ws: 20 bytes per point ((b, n) 16-byte records, then (b, n) running distances); 0
+ *                                  outside the envelope. ws needs no initialisation and must be 16-byte aligned (PN2_E_ARG).
+ *   group_len                      64, 128 or 256 records per group (the plain entry: 256). At most 4096 groups per cloud: 64 covers
+ *                                  n <= 262144, 128 n <= 524288, 256 the whole envelope (PN2_E_TOO_LARGE beyond).
+ * Codes, in this order, all before anything is launched: m <= 0 or b == 0 PN2_OK; b < 0 or n <= 0 PN2_E_SHAPE; inp, out or ws
+ * NULL PN2_E_NULL; n outside the envelope, or b n 3 / b m 3 beyond int32, PN2_E_TOO_LARGE; group_len not one of the three
+ * PN2_E_ARG. Ragged batches are out of this tier's scope (the _ragged entries stop at 16384 points). */
+long long pn2_fps_large_ws_bytes(int b, int n);
+int pn2_fps_large_supported(int n, int m);
+int pn2_fps_large_pays(int n, int m);
+int pn2_farthest_point_sample_large(int b, int n, int m, const float *inp, void *ws, int *out, float *out_xyz /* may be NULL */,
+                                    void *stream);
+int pn2_farthest_point_sample_large_ex(int group_len, int b, int n, int m, const float *inp, void *ws, int *out,
+                                       float *out_xyz /* may be NULL */, void *stream);
+
 /* The whole xyz half of sample_and_group (pointnet_util.py:40-46) in ONE launch, with the ball
  * queries overlapped under the farthest-point-sampling chain: producer workgroups (one per cloud)
  * publish each sample as they select it, consumer workgroups on the other CUs run query j as soon as

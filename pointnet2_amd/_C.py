@@ -151,10 +151,16 @@ _SIGNATURES = {
     "pn2_knn_point_ragged_pair": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_three_nn_ragged_pair": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp],
     "pn2_farthest_point_sample_ragged_variant": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_fps_large_ws_bytes": [_i, _i],
+    "pn2_fps_large_supported": [_i, _i],
+    "pn2_fps_large_pays": [_i, _i],
+    "pn2_farthest_point_sample_large": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pn2_farthest_point_sample_large_ex": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "pn2_fps_temp_floats": ctypes.c_longlong,
     "pn2_fps_ordered_ws_bytes": ctypes.c_longlong,
+    "pn2_fps_large_ws_bytes": ctypes.c_longlong,
     "pn2_det_grad_ws_bytes": ctypes.c_longlong,
     "pn2_seg_grad_ws_bytes": ctypes.c_longlong,
     "pn2_seg_plan_bytes": ctypes.c_longlong,

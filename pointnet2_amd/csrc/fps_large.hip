@@ -1,0 +1,434 @@
+// fps_large.hip -- farthest point sampling for clouds of 16385 .. 1048576 points: exact spatial pruning over a cell-sorted copy
+// of the cloud.
+//
+// Same results as fps_generic_kernel (fps.hip) / the reference kernel (tf_sampling_g.cu:105-170), index for index, tie rule
+// included (smallest (k mod 512, k) among equal running distances). What changes is how much of a round is done. The generic
+// kernel updates the running distance of EVERY point against the new sample: n distance tests, n running distances read and
+// written in global memory, per round. But a new sample can only lower running distances inside the ball of radius
+// sqrt(v*) around it (v* = the value that just won the arg-max; fps_pruned_body.h), and on a large cloud that ball holds a
+// few per cent of the points after a few dozen samples.
+//
+// Organisation. One 1024-thread workgroup per cloud, one launch, nothing waits on another workgroup.
+//   Prologue (passes over the cloud): bounding box; an LDS histogram over a 32 x 32 x 32 cell grid in Morton order; exclusive
+//   prefix sums; a scatter with returning LDS atomics that writes the cloud into the workspace in cell order as 16-byte
+//   records {x, y, z, original index k}. The sorted order is cut into GROUPS of L consecutive records (L = 64, 128 or 256); a
+//   Morton run of cells is a compact blob whatever the local density, so a group's tight bounding box is small. The order of
+//   the records inside a cell is the order of the atomics, i.e. timing dependent -- and irrelevant: any partition gives the
+//   same samples (fps_pruned_body.h), a compact one gives more skips.
+//   Ownership. Group g belongs to wave g mod 16; lane l of that wave owns the records g L + l + 64 r (r < L / 64), so every
+//   running distance is only ever read and written by ONE thread (as in the generic kernel) and no barrier or fence guards the
+//   distance array. Lane l of wave w also holds, in registers, the box and the cached key of the wave's groups number l,
+//   l + 64, l + 128, l + 192 (at most 4096 groups = 256 per wave).
+//   Chain, per round: every lane tests its (up to four) boxes against the new sample -- the pruned tier's rule, bd >= v* *
+//   1.00001f + 1e-30f means "cannot change" --, a ballot per box slot gives the wave its touched groups, and the wave walks them:
+//   L / 64 records per lane, sqdist, __builtin_fminf, the generic kernel's 64-bit key (value bits : 0xFFFFFFFF - tie key), a
+//   wave-wide maximum = the group's new key, cached by the owning lane. The coordinates of a group's best record go to an LDS
+//   table only its own wave touches. The wave key is the maximum of the cached group keys (recomputed only when a group
+//   changed); the lane that owns the winning group publishes (key, x, y, z) in the wave's LDS slot. One __syncthreads() per
+//   round; behind it every thread reads the 16 wave keys and the winner's coordinates from LDS: the winner never costs a
+//   dependent global-memory load. Slots are double buffered by the round's parity, as in the generic kernel.
+// Exactness: the skip rule and its proof are those of fps_pruned_body.h (header comment there); groups that are not skipped
+// compute exactly the generic kernel's values, and the arg-max over cached keys is the arg-max over all records because an
+// untouched group's records -- hence its key -- did not change.
+#include "fps_body.h"
+
+#include <limits.h>
+#include <math.h>
+
+namespace pn2 {
+
+constexpr int kLgT = 1024;                       // threads: 16 waves, the chain stays inside one CU
+constexpr int kLgW = kLgT / PN2_WAVE;
+constexpr int kLgMinPoints = 16384;              // exclusive: up to here the register tiers
+constexpr int kLgMaxPoints = 1 << 20;
+constexpr int kLgMaxGroups = 4096;               // box + key slots: four per lane
+constexpr int kLgNB = kLgMaxGroups / kLgW / PN2_WAVE;
+constexpr int kLgAxisCells = 32;                 // cells per axis
+constexpr int kLgCells = kLgAxisCells * kLgAxisCells * kLgAxisCells;
+constexpr int kLgCellsPerThread = kLgCells / kLgT;
+// LDS (bytes): [0, 128 Ki) the cell histogram of the prologue, afterwards its first 64 KiB = best-record coordinates per group |
+// wave keys [2][16] u64 | wave coordinates [2][16] float4 | bounding-box partials [16][8] f32 | scan totals [16] i32
+constexpr size_t kLgHistBytes = (size_t)kLgCells * 4;
+constexpr size_t kLgKeyOff = kLgHistBytes, kLgXyzOff = kLgKeyOff + 256, kLgRedOff = kLgXyzOff + 512, kLgTotOff = kLgRedOff + 512;
+constexpr size_t kLgLdsBytes = kLgTotOff + 64;
+static_assert((size_t)kLgMaxGroups * 16 <= kLgHistBytes && kLgLdsBytes <= 160 * 1024, "LDS layout");
+static_assert(kLgNB == 4, "four box slots per lane");
+
+__device__ __forceinline__ unsigned long long lg_shfl_xor_u64(unsigned long long v, int m)
+{
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, m, 64);
+    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// wave-wide maximum, in every lane
+__device__ __forceinline__ unsigned long long lg_wave_max_u64(unsigned long long v)
+{
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const unsigned long long o = lg_shfl_xor_u64(v, s);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+template <bool MAX>
+__device__ __forceinline__ float lg_wave_minmax(float v)
+{
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const float o = __shfl_xor(v, s, 64);
+        v = MAX ? fmaxf(v, o) : fminf(v, o);
+    }
+    return v;
+}
+
+// bin of a coordinate along one axis: 0 .. 31, NaN and everything out of range included (fmaxf(NaN, 0) = 0)
+__device__ __forceinline__ unsigned lg_axis_bin(float c, float lo, float scale)
+{
+    const float f = fminf(fmaxf(__fmul_rn(__fsub_rn(c, lo), scale), 0.0f), (float)(kLgAxisCells - 1));
+    return (unsigned)(int)f;
+}
+
+// five bits to every third bit
+__device__ __forceinline__ unsigned lg_spread5(unsigned v)
+{
+    return (v & 1u) | ((v & 2u) << 2) | ((v & 4u) << 4) | ((v & 8u) << 6) | ((v & 16u) << 8);
+}
+
+struct LgGrid {
+    float lx, ly, lz, sx, sy, sz;
+};
+
+__device__ __forceinline__ int lg_cell(const LgGrid &gr, float x, float y, float z)
+{
+    return (int)((lg_spread5(lg_axis_bin(x, gr.lx, gr.sx)) << 2) | (lg_spread5(lg_axis_bin(y, gr.ly, gr.sy)) << 1) |
+                 lg_spread5(lg_axis_bin(z, gr.lz, gr.sz)));
+}
+
+struct LgBox {
+    float lx, ly, lz, hx, hy, hz;
+};
+
+// The records of one group as its wave holds them: lane l has records base + l + 64 r (those below n exist).
+template <int R>
+struct LgRecs {
+    float4 p[R];
+    float d0[R];
+};
+
+// every load in flight before the first use; a missing record re-reads the cloud's last one (never used)
+template <int R, bool INIT>
+__device__ __forceinline__ void lg_group_load(int n, int g, int lane, const float4 *recs, const float *md, LgRecs<R> &q)
+{
+    const int base = g * (R * 64) + lane;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = min(base + r * 64, n - 1);
+        q.p[r] = recs[i];
+        q.d0[r] = INIT ? 1e38f : md[i];
+    }
+}
+
+// One pass of a wave over ONE group, behind lg_group_load: returns the group's key in every lane and leaves the coordinates of
+// the record that holds it in best[g]. INIT: the running distances are set to the reference's start value 1e38
+// (tf_sampling_g.cu:118) and the group's tight box is computed; else they are lowered against the sample (sx, sy, sz).
+template <int R, bool INIT>
+__device__ __forceinline__ unsigned long long lg_group_finish(int n, int g, int lane, const LgRecs<R> &q, float *md, float sx,
+                                                              float sy, float sz, float4 *best, LgBox &box)
+{
+    const int base = g * (R * 64) + lane;
+    unsigned long long lk = 0ull;
+    float bx = 0.0f, by = 0.0f, bz = 0.0f, bw = 0.0f;
+    if (INIT) {
+        box.lx = box.ly = box.lz = INFINITY;
+        box.hx = box.hy = box.hz = -INFINITY;
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = base + r * 64;
+        const bool real = i < n;
+        const float4 p = q.p[r];
+        float d2;
+        if (INIT) {
+            d2 = 1e38f;
+            if (real) {
+                box.lx = fminf(box.lx, p.x); box.ly = fminf(box.ly, p.y); box.lz = fminf(box.lz, p.z);
+                box.hx = fmaxf(box.hx, p.x); box.hy = fmaxf(box.hy, p.y); box.hz = fmaxf(box.hz, p.z);
+            }
+        } else {
+            d2 = __builtin_fminf(sqdist(p.x, p.y, p.z, sx, sy, sz), q.d0[r]);              // min(d, td), tf_sampling_g.cu:144
+        }
+        if (real) md[i] = d2;
+        const unsigned k = (unsigned)__float_as_int(p.w);
+        const unsigned tiekey = ((k & (unsigned)(kRefThreads - 1)) << 22) | (k >> 9);
+        const unsigned long long key = real ? ((unsigned long long)(unsigned)__float_as_int(d2) << 32) | (unsigned long long)(0xFFFFFFFFu - tiekey)
+                                            : 0ull;
+        if (key > lk) { lk = key; bx = p.x; by = p.y; bz = p.z; bw = p.w; }
+    }
+    const unsigned long long gkey = lg_wave_max_u64(lk);
+    if (lk == gkey && gkey != 0ull) best[g] = make_float4(bx, by, bz, bw);                 // keys are unique: one lane
+    if (INIT) {
+        box.lx = lg_wave_minmax<false>(box.lx); box.ly = lg_wave_minmax<false>(box.ly); box.lz = lg_wave_minmax<false>(box.lz);
+        box.hx = lg_wave_minmax<true>(box.hx); box.hy = lg_wave_minmax<true>(box.hy); box.hz = lg_wave_minmax<true>(box.hz);
+    }
+    return gkey;
+}
+
+template <int L>
+__global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const float *__restrict__ xyz, float4 *__restrict__ recs_all,
+                                                         float *__restrict__ md_all, int *__restrict__ out, float *__restrict__ out_xyz)
+{
+    constexpr int T = kLgT, W = kLgW, NB = kLgNB, R = L / 64;
+    static_assert(L == 64 || L == 128 || L == 256, "records per group");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int *hist = reinterpret_cast<int *>(smem);
+    float4 *best = reinterpret_cast<float4 *>(smem);                                       // [groups], after the prologue
+    unsigned long long *skey = reinterpret_cast<unsigned long long *>(smem + kLgKeyOff);   // [2][W]
+    float4 *sxyz = reinterpret_cast<float4 *>(smem + kLgXyzOff);                            // [2][W]
+    float *red = reinterpret_cast<float *>(smem + kLgRedOff);                               // [W][8]
+    int *wtot = reinterpret_cast<int *>(smem + kLgTotOff);                                  // [W]
+
+    const int cloud = blockIdx.x;
+    const float *__restrict__ src = xyz + (size_t)cloud * n * 3;
+    float4 *__restrict__ recs = recs_all + (size_t)cloud * n;
+    float *__restrict__ md = md_all + (size_t)cloud * n;
+    int *__restrict__ dst = out + (size_t)cloud * m;
+    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)cloud * m * 3 : nullptr;
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+
+    float sx = src[0], sy = src[1], sz = src[2];           // the first sample is point 0 (tf_sampling_g.cu:114-116)
+    if (t == 0) {
+        dst[0] = 0;
+        if (dxyz) { dxyz[0] = sx; dxyz[1] = sy; dxyz[2] = sz; }
+    }
+    if (m == 1) return;                                    // kernel-uniform
+
+    // ---- prologue 1: bounding box -------------------------------------------------------------------------------------------
+    LgGrid gr;
+    {
+        float lx = INFINITY, ly = INFINITY, lz = INFINITY, hx = -INFINITY, hy = -INFINITY, hz = -INFINITY;
+        for (int k = t; k < n; k += T) {
+            const float x = src[(size_t)k * 3 + 0], y = src[(size_t)k * 3 + 1], z = src[(size_t)k * 3 + 2];
+            lx = fminf(lx, x); ly = fminf(ly, y); lz = fminf(lz, z);
+            hx = fmaxf(hx, x); hy = fmaxf(hy, y); hz = fmaxf(hz, z);
+        }
+        lx = lg_wave_minmax<false>(lx); ly = lg_wave_minmax<false>(ly); lz = lg_wave_minmax<false>(lz);
+        hx = lg_wave_minmax<true>(hx); hy = lg_wave_minmax<true>(hy); hz = lg_wave_minmax<true>(hz);
+        if (lane == 0) {
+            red[w * 8 + 0] = lx; red[w * 8 + 1] = ly; red[w * 8 + 2] = lz;
+            red[w * 8 + 4] = hx; red[w * 8 + 5] = hy; red[w * 8 + 6] = hz;
+        }
+        for (int c = t; c < kLgCells; c += T) hist[c] = 0;
+        __syncthreads();
+        float lo[3], sc[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            float l = red[a], h = red[4 + a];
+#pragma unroll
+            for (int ww = 1; ww < W; ++ww) { l = fminf(l, red[ww * 8 + a]); h = fmaxf(h, red[ww * 8 + 4 + a]); }
+            const float e = __fsub_rn(h, l);
+            const bool ok = e > 0.0f && e < INFINITY;       // degenerate / non-finite axis: every point in bin 0
+            const float s = ok ? (float)kLgAxisCells / e : 0.0f;
+            lo[a] = ok ? l : 0.0f;
+            sc[a] = s < INFINITY ? s : 0.0f;                // an extent so small that the scale overflows: bin 0 as well
+        }
+        gr.lx = lo[0]; gr.ly = lo[1]; gr.lz = lo[2];
+        gr.sx = sc[0]; gr.sy = sc[1]; gr.sz = sc[2];
+    }
+
+    // ---- prologue 2: histogram over the cells, exclusive prefix sums --------------------------------------------------------
+    for (int k = t; k < n; k += T)
+        atomicAdd(&hist[lg_cell(gr, src[(size_t)k * 3 + 0], src[(size_t)k * 3 + 1], src[(size_t)k * 3 + 2])], 1);
+    __syncthreads();
+    {
+        int *mine = hist + t * kLgCellsPerThread;           // thread t scans cells 32 t .. 32 t + 31
+        int sum = 0;
+#pragma unroll 8
+        for (int c = 0; c < kLgCellsPerThread; ++c) sum += mine[c];
+        int incl = sum;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const int o = __shfl_up(incl, s, 64);
+            if (lane >= s) incl += o;
+        }
+        if (lane == 63) wtot[w] = incl;
+        __syncthreads();
+        int run = incl - sum;
+        for (int ww = 0; ww < w; ++ww) run += wtot[ww];
+#pragma unroll 8
+        for (int c = 0; c < kLgCellsPerThread; ++c) {
+            const int h = mine[c];
+            mine[c] = run;
+            run += h;
+        }
+    }
+    __syncthreads();
+
+    // ---- prologue 3: scatter into cell order (a returning atomic hands out the places of a cell) ----------------------------
+    for (int k = t; k < n; k += T) {
+        const float x = src[(size_t)k * 3 + 0], y = src[(size_t)k * 3 + 1], z = src[(size_t)k * 3 + 2];
+        const int at = atomicAdd(&hist[lg_cell(gr, x, y, z)], 1);
+        if ((unsigned)at < (unsigned)n) recs[at] = make_float4(x, y, z, __int_as_float(k));   // always: same cells as the histogram pass
+    }
+    __syncthreads();                                        // the records are visible to the workgroup; the histogram is dead
+
+    // ---- prologue 4: boxes, start distances and start keys of this wave's groups --------------------------------------------
+    const int G = (n + L - 1) / L;
+    unsigned long long gk[NB];                              // lane l, slot i: group w + 16 (l + 64 i); 0 = no such group
+    LgBox gb[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        gk[i] = 0ull;
+        gb[i].lx = gb[i].ly = gb[i].lz = gb[i].hx = gb[i].hy = gb[i].hz = 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        for (int bit = 0; bit < 64; ++bit) {
+            const int g = w + W * (i * 64 + bit);
+            if (g >= G) break;                              // wave-uniform
+            LgBox bx;
+            LgRecs<R> q;
+            lg_group_load<R, true>(n, g, lane, recs, md, q);
+            const unsigned long long k = lg_group_finish<R, true>(n, g, lane, q, md, 0.0f, 0.0f, 0.0f, best, bx);
+            if (lane == bit) { gk[i] = k; gb[i] = bx; }
+        }
+    }
+    unsigned long long wave_key;
+    {
+        unsigned long long lk = gk[0];
+#pragma unroll
+        for (int i = 1; i < NB; ++i) lk = gk[i] > lk ? gk[i] : lk;
+        wave_key = lg_wave_max_u64(lk);
+    }
+
+    // ---- the chain ----------------------------------------------------------------------------------------------------------
+    float vstar = 1e38f;                                    // every running distance is <= vstar
+    for (int j = 1; j < m; ++j) {
+        const int par = j & 1;
+        const float thr = __fadd_rn(__fmul_rn(vstar, 1.00001f), 1e-30f);
+        bool touched = false;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            if (w + W * (i * 64) >= G) break;               // wave-uniform: no group in this slot or the later ones
+            // distance from the sample to the box = sample - clamp(sample, lo, hi) per axis (v_med3_f32 is the clamp)
+            const float ax = __fsub_rn(sx, __builtin_amdgcn_fmed3f(sx, gb[i].lx, gb[i].hx));
+            const float ay = __fsub_rn(sy, __builtin_amdgcn_fmed3f(sy, gb[i].ly, gb[i].hy));
+            const float az = __fsub_rn(sz, __builtin_amdgcn_fmed3f(sz, gb[i].lz, gb[i].hz));
+            const float bd = __fadd_rn(__fadd_rn(__fmul_rn(ax, ax), __fmul_rn(ay, ay)), __fmul_rn(az, az));
+            unsigned long long todo = __ballot(!(bd >= thr) && gk[i] != 0ull);             // NaN -> not far -> updated
+            if (todo != 0ull) {                             // wave-uniform
+                // scalar loop over the touched groups; the next group's records are requested before this one's are used
+                touched = true;
+                int bit = __builtin_ctzll(todo);
+                todo &= todo - 1ull;
+                LgRecs<R> q;
+                lg_group_load<R, false>(n, w + W * (i * 64 + bit), lane, recs, md, q);
+                for (;;) {
+                    const bool more = todo != 0ull;
+                    int nbit = 0;
+                    LgRecs<R> qn;
+                    if (more) {
+                        nbit = __builtin_ctzll(todo);
+                        todo &= todo - 1ull;
+                        lg_group_load<R, false>(n, w + W * (i * 64 + nbit), lane, recs, md, qn);
+                    }
+                    LgBox unused;
+                    const unsigned long long k = lg_group_finish<R, false>(n, w + W * (i * 64 + bit), lane, q, md, sx, sy, sz, best, unused);
+                    if (lane == bit) gk[i] = k;
+                    if (!more) break;
+                    q = qn;
+                    bit = nbit;
+                }
+            }
+        }
+        if (touched) {                                      // wave-uniform; else the cached wave key stands
+            unsigned long long lk = gk[0];
+#pragma unroll
+            for (int i = 1; i < NB; ++i) lk = gk[i] > lk ? gk[i] : lk;
+            wave_key = lg_wave_max_u64(lk);
+        }
+        // the lane that owns the wave's best group publishes (key, coordinates of its best record)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            if (gk[i] == wave_key && wave_key != 0ull) {
+                skey[par * W + w] = wave_key;
+                sxyz[par * W + w] = best[w + W * (i * 64 + lane)];
+            }
+        }
+        __syncthreads();
+        unsigned long long bk = skey[par * W];
+        int bwv = 0;
+#pragma unroll
+        for (int ww = 1; ww < W; ++ww) {
+            const unsigned long long k = skey[par * W + ww];
+            if (k > bk) { bk = k; bwv = ww; }
+        }
+        const float4 s = sxyz[par * W + bwv];               // same address in every lane: LDS broadcast
+        sx = s.x; sy = s.y; sz = s.z;
+        vstar = __int_as_float((int)(unsigned)(bk >> 32));
+        if (t == 0) {
+            dst[j] = __float_as_int(s.w);
+            if (dxyz) { dxyz[j * 3 + 0] = s.x; dxyz[j * 3 + 1] = s.y; dxyz[j * 3 + 2] = s.z; }
+        }
+    }
+}
+
+template <int L>
+static int launch_large(int b, int n, int m, const float *inp, void *ws, int *out, float *oxyz, hipStream_t st)
+{
+    float4 *recs = static_cast<float4 *>(ws);
+    float *md = reinterpret_cast<float *>(recs + (size_t)b * n);
+    return launch_lds(fps_large_kernel<L>, dim3(b), dim3(kLgT), kLgLdsBytes, st, n, m, inp, recs, md, out, oxyz);
+}
+
+static bool large_covers(int n) { return n > kLgMinPoints && n <= kLgMaxPoints; }
+
+}  // namespace pn2
+
+extern "C" int pn2_fps_large_supported(int n, int m) { return (pn2::large_covers(n) && m > 0) ? 1 : 0; }
+
+// 16 bytes of record and 4 of running distance per point: (b, n) records first, then (b, n) distances
+extern "C" long long pn2_fps_large_ws_bytes(int b, int n)
+{
+    if (b <= 0 || !pn2::large_covers(n)) return 0;
+    return (long long)b * n * 20;
+}
+
+// Where the tier pays (measured, profiles/fps_large/README.md: medians of 20, two runs of every figure within 0.2 % of each
+// other). Against the global-memory kernel on uniform-cube / sphere-surface clouds, generic time over this tier's:
+//   n = 20000: 0.82 / 0.95 at m = 64, 1.20 / 1.38 at 256, 1.49 / 1.70 at 1024;   32768: 0.88 / 1.05, 1.39 / 1.70, 1.88 / 2.24;
+//   65536: 1.05 / 1.32 at m = 64, 1.88 / 2.42 at 256;   131072: 1.28 / 1.67, 2.50 / 3.46;   1048576: 2.57 / 3.39, 6.73 / 9.71.
+// The prologue (sort + boxes) is what a short chain cannot earn back: 1 only from the smallest measured m at which BOTH kinds
+// were ahead, and nowhere below the smallest m of the sweep.
+extern "C" int pn2_fps_large_pays(int n, int m)
+{
+    if (!pn2_fps_large_supported(n, m)) return 0;
+    return m >= (n >= 65536 ? 64 : 256) ? 1 : 0;
+}
+
+extern "C" int pn2_farthest_point_sample_large_ex(int group_len, int b, int n, int m, const float *inp, void *ws, int *out,
+                                                  float *out_xyz, void *stream)
+{
+    using namespace pn2;
+    if (m <= 0 || b == 0) return PN2_OK;                   // the dense entry's order (fps_entry, fps.hip)
+    if (b < 0 || n <= 0) return PN2_E_SHAPE;
+    if (!inp || !out || !ws) return PN2_E_NULL;
+    if (!large_covers(n)) return PN2_E_TOO_LARGE;
+    if ((long long)b * n * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
+    if (group_len != 64 && group_len != 128 && group_len != 256) return PN2_E_ARG;
+    if (((long long)n + group_len - 1) / group_len > kLgMaxGroups) return PN2_E_TOO_LARGE;   // four box slots per lane
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return PN2_E_ARG;                               // 16-byte records
+    hipStream_t st = as_stream(stream);
+    switch (group_len) {
+    case 64: return launch_large<64>(b, n, m, inp, ws, out, out_xyz, st);
+    case 128: return launch_large<128>(b, n, m, inp, ws, out, out_xyz, st);
+    default: return launch_large<256>(b, n, m, inp, ws, out, out_xyz, st);
+    }
+}
+
+extern "C" int pn2_farthest_point_sample_large(int b, int n, int m, const float *inp, void *ws, int *out, float *out_xyz, void *stream)
+{
+    return pn2_farthest_point_sample_large_ex(256, b, n, m, inp, ws, out, out_xyz, stream);
+}

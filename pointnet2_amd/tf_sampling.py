@@ -106,6 +106,32 @@ def set_fps_variant(variant=FPS_AUTO):
     _FPS_VARIANT[0] = int(variant)
 
 
+# Large dense clouds (16384 < n <= 1048576): the cell-sorted, box-pruned tier of csrc/fps_large.hip instead of the global-memory
+# kernel. None = where the library's measured size rule says it pays (pn2_fps_large_pays), True = wherever it is supported,
+# False = never. Dense input only (no lengths / npoints), and only while no tier is forced with set_fps_variant. Results never
+# depend on it.
+_FPS_LARGE = [None]
+FPS_REG_MAX_POINTS = 16384              # up to here the register-resident tiers (pn2_fps_temp_floats is 0)
+
+
+def set_fps_large(mode=None):
+    require(mode is None or isinstance(mode, bool), "fps large mode must be None (the size rule), True or False")
+    _FPS_LARGE[0] = mode
+
+
+def _fps_large_takes(lib, b, n, m):
+    if _FPS_VARIANT[0] or _FPS_LARGE[0] is False or b <= 0 or n <= FPS_REG_MAX_POINTS:   # the register tiers: not even a query
+        return False
+    return bool(lib.pn2_fps_large_supported(n, m) if _FPS_LARGE[0] else lib.pn2_fps_large_pays(n, m))
+
+
+def _fps_large(lib, b, n, m, inp, out, new_xyz, op):
+    dev = inp.device
+    ws = torch.empty((lib.pn2_fps_large_ws_bytes(b, n),), dtype=torch.uint8, device=dev)    # per call, as temp is
+    with on_device(dev):
+        _C.check(lib.pn2_farthest_point_sample_large(b, n, m, ptr(inp), ptr(ws), ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
+
+
 # ---- input that is already in farthest-point order ------------------------------------------------------------------------
 # The second and later levels of every network sample from the previous level's samples (pointnet2_sem_seg.py:28-31): the
 # first m of them are, up to exact ties and exhausted clouds, selected as 0 .. m-1. new_xyz tensors that come out of a
@@ -218,6 +244,9 @@ def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoint
         _fps_ragged(m, inp, lengths, out, new_xyz, "farthest_point_sample_gather", npoints)
         return out, (mark_fps_ordered(new_xyz) if npoints is None else new_xyz)   # fill rows break the farthest-point order
     lib = _C.lib()
+    if _fps_large_takes(lib, b, n, m):
+        _fps_large(lib, b, n, m, inp, out, new_xyz, "farthest_point_sample_gather")
+        return out, mark_fps_ordered(new_xyz)
     tf = lib.pn2_fps_temp_floats(b, n)
     temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None
     with on_device(dev):
@@ -261,6 +290,9 @@ def farthest_point_sample(npoint, inp, out=None, lengths=None, npoints=None):
         _fps_ragged(m, inp, lengths, out, None, "farthest_point_sample", npoints)
         return out
     lib = _C.lib()
+    if _fps_large_takes(lib, b, n, m):
+        _fps_large(lib, b, n, m, inp, out, None, "farthest_point_sample")
+        return out
     tf = lib.pn2_fps_temp_floats(b, n)
     temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None   # allocate_temp, tf_sampling.cpp:115
     with on_device(dev):
