@@ -515,7 +515,7 @@ int pn2_farthest_point_sample_ragged_variant(int variant, int b, int n, int m, c
  *                                  n <= 262144, 128 n <= 524288, 256 the whole envelope (PN2_E_TOO_LARGE beyond).
  * Codes, in this order, all before anything is launched: m <= 0 or b == 0 PN2_OK; b < 0 or n <= 0 PN2_E_SHAPE; inp, out or ws
  * NULL PN2_E_NULL; n outside the envelope, or b n 3 / b m 3 beyond int32, PN2_E_TOO_LARGE; group_len not one of the three
- * PN2_E_ARG. Ragged batches are out of this tier's scope (the _ragged entries stop at 16384 points). */
+ * PN2_E_ARG. Ragged batches: the _large_ragged entries below (the _ragged entries stop at 16384 points). */
 long long pn2_fps_large_ws_bytes(int b, int n);
 int pn2_fps_large_supported(int n, int m);
 int pn2_fps_large_pays(int n, int m);
@@ -523,6 +523,29 @@ int pn2_farthest_point_sample_large(int b, int n, int m, const float *inp, void 
                                     void *stream);
 int pn2_farthest_point_sample_large_ex(int group_len, int b, int n, int m, const float *inp, void *ws, int *out,
                                        float *out_xyz /* may be NULL */, void *stream);
+
+/* Ragged batches of LARGE clouds, padded n of 16385 .. 1048576: `lengths` (b) and `npoints` (b, or NULL: m samples from every
+ * cloud) int32 in DEVICE memory, clamped on the device into 1..n / 1..m, never read by the host. THE SLICE RULE of the ragged
+ * entries above: cloud c's rows below npoints[c] are the first npoints[c] samples of the dense operator on inp[c, :lengths[c]]
+ * alone, tie rule included (m > lengths[c] behaves as the dense operator with npoint > n); rows from npoints[c] on are index 0 and
+ * inp[c, 0]; rows of inp at or beyond lengths[c] are never read. One launch of one workgroup per cloud, no memset, no host
+ * synchronisation, capturable; nothing is kept between launches beyond ws.
+ *   ws         pn2_fps_large_ws_bytes(b, n) bytes on the PADDED n, 16-byte aligned, no initialisation;
+ *   kernel     0 = the library's rule, pn2_fps_large_pays(n, m) on the padded extents (the host knows no others);
+ *              1 = the global-memory kernel of pn2_farthest_point_sample with counts (its running distances in ws);
+ *              2 = the cell-sorted tier of pn2_farthest_point_sample_large (csrc/fps_large.hip);
+ *   group_len  64, 128 or 256, as pn2_farthest_point_sample_large_ex (kernel 1 ignores a valid value).
+ * The plain entry is _ex(0, 256, ...). Results never depend on kernel or group_len.
+ * Codes, in this order, all before anything is launched: m <= 0 or b == 0 PN2_OK; b < 0 or n <= 0 PN2_E_SHAPE; inp, out, ws or
+ * lengths NULL PN2_E_NULL; n outside the envelope, or b n 3 / b m 3 beyond int32, PN2_E_TOO_LARGE; kernel not 0..2 or group_len
+ * not one of the three PN2_E_ARG; more than 4096 groups of group_len records in n points where the tier would run
+ * PN2_E_TOO_LARGE; a misaligned ws PN2_E_ARG. */
+int pn2_farthest_point_sample_large_ragged(int b, int n, int m, const float *inp, const int *lengths,
+                                           const int *npoints /* NULL: m samples from every cloud */, void *ws, int *out,
+                                           float *out_xyz /* may be NULL */, void *stream);
+int pn2_farthest_point_sample_large_ragged_ex(int kernel, int group_len, int b, int n, int m, const float *inp, const int *lengths,
+                                              const int *npoints /* NULL: m samples from every cloud */, void *ws, int *out,
+                                              float *out_xyz /* may be NULL */, void *stream);
 
 /* The whole xyz half of sample_and_group (pointnet_util.py:40-46) in ONE launch, with the ball
  * queries overlapped under the farthest-point-sampling chain: producer workgroups (one per cloud)

@@ -156,6 +156,8 @@ _SIGNATURES = {
     "pn2_fps_large_pays": [_i, _i],
     "pn2_farthest_point_sample_large": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pn2_farthest_point_sample_large_ex": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "pn2_farthest_point_sample_large_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_farthest_point_sample_large_ragged_ex": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "pn2_fps_temp_floats": ctypes.c_longlong,

@@ -60,20 +60,8 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(int n, int m, int Q, const f
 // the first m_c samples of the dense operator on the slice (the chain is prefix-consistent: round j depends on rounds < j
 // alone). Rows m_c .. m-1 repeat sample 0, the way a ball query pads with its first hit; sample 0 is point 0 by the reference's
 // rule (tf_sampling_g.cu:114-116), so the fill is index 0 and xyz[c, 0] and reads nothing back. The fill rows are disjoint from
-// the body's, so no barrier stands between the two. (The fill is a function of its own: the wrappers of the other two tiers
-// below end with it too.) Without COUNTS npoints is never read.
-template <int T>
-__device__ __forceinline__ void fps_ragged_fill(int mc, int m, const float *__restrict__ src, int *__restrict__ dst, float *__restrict__ dxyz)
-{
-    if (mc < m) {                                          // block-uniform
-        const float x0 = src[0], y0 = src[1], z0 = src[2];
-        for (int j = mc + (int)threadIdx.x; j < m; j += T) {
-            dst[j] = 0;
-            if (dxyz) { dxyz[j * 3 + 0] = x0; dxyz[j * 3 + 1] = y0; dxyz[j * 3 + 2] = z0; }
-        }
-    }
-}
-
+// the body's, so no barrier stands between the two. (The fill is a function of its own, fps_ragged_fill in fps_body.h: the
+// wrappers of the other tiers end with it too.) Without COUNTS npoints is never read.
 template <int T, int P, bool LDSXYZ, bool COUNTS>
 __global__ __launch_bounds__(T) void fps_reg_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
                                                            const int *__restrict__ npoints, int *__restrict__ out,
@@ -324,19 +312,15 @@ __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v,
     return ((unsigned long long)hi << 32) | lo;
 }
 
-__global__ __launch_bounds__(1024) void fps_generic_kernel(int n, int m, const float *__restrict__ xyz,
-                                                           float *__restrict__ temp, int *__restrict__ out,
-                                                           float *__restrict__ out_xyz)
+// One cloud by one 1024-thread workgroup: n points at src, n running distances at mind, m samples to dst (and dxyz). n and m are
+// workgroup-uniform (the dense kernel: the launch's; fps_generic_ragged_kernel: the cloud's own).
+__device__ __forceinline__ void fps_generic_body(int n, int m, const float *__restrict__ src, float *__restrict__ mind,
+                                                 int *__restrict__ dst, float *__restrict__ dxyz)
 {
     constexpr int T = 1024, W = T / PN2_WAVE;
     __shared__ unsigned long long part[2][W];
-    const int cloud = blockIdx.x;
-    const float *__restrict__ src = xyz + (size_t)cloud * n * 3;
-    float *__restrict__ mind = temp + (size_t)cloud * n;
-    int *__restrict__ dst = out + (size_t)cloud * m;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     for (int k = t; k < n; k += T) mind[k] = 1e38f;
-    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)cloud * m * 3 : nullptr;
     int cur = 0;
     if (t == 0) {
         dst[0] = 0;
@@ -381,6 +365,35 @@ __global__ __launch_bounds__(1024) void fps_generic_kernel(int n, int m, const f
     }
 }
 
+__global__ __launch_bounds__(1024) void fps_generic_kernel(int n, int m, const float *__restrict__ xyz,
+                                                           float *__restrict__ temp, int *__restrict__ out,
+                                                           float *__restrict__ out_xyz)
+{
+    const int cloud = blockIdx.x;
+    fps_generic_body(n, m, xyz + (size_t)cloud * n * 3, temp + (size_t)cloud * n, out + (size_t)cloud * m,
+                     out_xyz ? out_xyz + (size_t)cloud * m * 3 : nullptr);
+}
+
+// Ragged batch beyond the register tiers (pn2_farthest_point_sample_large_ragged, kernel 1): the slice rule of
+// fps_reg_ragged_kernel on the global-memory body. Slabs addressed with the padded n and m, the body run with n_c and m_c: every
+// loop over the cloud is k < n_c (rows at or beyond n_c of the cloud and of temp are never addressed), a thread without a point
+// contributes key 0, below every real key, and the one barrier per round sits in the loop j < m_c of workgroup-uniform bound.
+// COUNTS: rows m_c .. m-1 are fps_ragged_fill's.
+template <bool COUNTS>
+__global__ __launch_bounds__(1024) void fps_generic_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
+                                                                  const int *__restrict__ npoints, float *__restrict__ temp,
+                                                                  int *__restrict__ out, float *__restrict__ out_xyz)
+{
+    const int c = blockIdx.x;
+    const int nc = cloud_count(lengths, c, n);
+    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
+    const float *__restrict__ src = xyz + (size_t)c * n * 3;
+    int *__restrict__ dst = out + (size_t)c * m;
+    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
+    fps_generic_body(nc, mc, src, temp + (size_t)c * n, dst, dxyz);
+    if (COUNTS) fps_ragged_fill<1024>(mc, m, src, dst, dxyz);
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -402,6 +415,15 @@ static int launch_reg_ragged(int b, int n, int m, const float *inp, const int *l
     const size_t lds = 256 + (LDSXYZ ? sizeof(float4) : sizeof(int)) * (size_t)T * P;
     return launch_lds(npoints ? fps_reg_ragged_kernel<T, P, LDSXYZ, true> : fps_reg_ragged_kernel<T, P, LDSXYZ, false>, dim3(b), dim3(T),
                       lds, st, n, m, inp, lengths, npoints, out, oxyz);
+}
+
+// the global-memory kernel with counts, for the ragged entry of fps_large.hip (declared there). npoints: NULL = m samples from
+// every cloud; temp: (b, n) floats
+int fps_launch_generic_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, float *temp, int *out,
+                              float *oxyz, hipStream_t st)
+{
+    return launch(npoints ? fps_generic_ragged_kernel<true> : fps_generic_ragged_kernel<false>, dim3(b), dim3(1024), 0, st, n, m, inp,
+                  lengths, npoints, temp, out, oxyz);
 }
 
 template <int P, int GS>

@@ -322,5 +322,18 @@ __device__ __forceinline__ void fps_reg_body(int n, int m, int Q, int cloud, con
     fps_gather_epilogue<T>(m, src, dst, dxyz);
 }
 
+// The rows m_c .. m-1 of a cloud that yields m_c < m samples (the ragged kernels with counts, fps.hip and fps_large.hip): sample
+// 0 repeated, i.e. index 0 and the cloud's first point -- nothing is read back.
+template <int T>
+__device__ __forceinline__ void fps_ragged_fill(int mc, int m, const float *__restrict__ src, int *__restrict__ dst, float *__restrict__ dxyz)
+{
+    if (mc < m) {                                          // block-uniform
+        const float x0 = src[0], y0 = src[1], z0 = src[2];
+        for (int j = mc + (int)threadIdx.x; j < m; j += T) {
+            dst[j] = 0;
+            if (dxyz) { dxyz[j * 3 + 0] = x0; dxyz[j * 3 + 1] = y0; dxyz[j * 3 + 2] = z0; }
+        }
+    }
+}
 
 }  // namespace pn2

@@ -30,6 +30,8 @@
 // Exactness: the skip rule and its proof are those of fps_pruned_body.h (header comment there); groups that are not skipped
 // compute exactly the generic kernel's values, and the arg-max over cached keys is the arg-max over all records because an
 // untouched group's records -- hence its key -- did not change.
+// Ragged batches (lengths / npoints on the device): the chain is a body that takes one cloud's extents; fps_large_ragged_kernel
+// runs it on each cloud's slice (pn2_farthest_point_sample_large_ragged).
 #include "fps_body.h"
 
 #include <limits.h>
@@ -175,13 +177,15 @@ __device__ __forceinline__ unsigned long long lg_group_finish(int n, int g, int 
     return gkey;
 }
 
-template <int L>
-__global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const float *__restrict__ xyz, float4 *__restrict__ recs_all,
-                                                         float *__restrict__ md_all, int *__restrict__ out, float *__restrict__ out_xyz)
+// The whole chain of ONE cloud by one workgroup: n points at src, their records and running distances at recs / md (n entries
+// each), m samples to dst (and dxyz). n and m are workgroup-uniform; nothing else about them is assumed, so the dense kernel
+// passes the launch's extents and the ragged kernel a cloud's own (fps_large_ragged_kernel below goes through what that needs).
+template <int L, bool SHORT>
+__device__ __forceinline__ void fps_large_body(int n, int m, const float *__restrict__ src, float4 *__restrict__ recs,
+                                               float *__restrict__ md, int *__restrict__ dst, float *__restrict__ dxyz, char *smem)
 {
     constexpr int T = kLgT, W = kLgW, NB = kLgNB, R = L / 64;
     static_assert(L == 64 || L == 128 || L == 256, "records per group");
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     int *hist = reinterpret_cast<int *>(smem);
     float4 *best = reinterpret_cast<float4 *>(smem);                                       // [groups], after the prologue
     unsigned long long *skey = reinterpret_cast<unsigned long long *>(smem + kLgKeyOff);   // [2][W]
@@ -189,12 +193,6 @@ __global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const flo
     float *red = reinterpret_cast<float *>(smem + kLgRedOff);                               // [W][8]
     int *wtot = reinterpret_cast<int *>(smem + kLgTotOff);                                  // [W]
 
-    const int cloud = blockIdx.x;
-    const float *__restrict__ src = xyz + (size_t)cloud * n * 3;
-    float4 *__restrict__ recs = recs_all + (size_t)cloud * n;
-    float *__restrict__ md = md_all + (size_t)cloud * n;
-    int *__restrict__ dst = out + (size_t)cloud * m;
-    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)cloud * m * 3 : nullptr;
     const int t = threadIdx.x, lane = t & 63;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
 
@@ -203,7 +201,7 @@ __global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const flo
         dst[0] = 0;
         if (dxyz) { dxyz[0] = sx; dxyz[1] = sy; dxyz[2] = sz; }
     }
-    if (m == 1) return;                                    // kernel-uniform
+    if (m == 1) return;                                    // workgroup-uniform, before any barrier
 
     // ---- prologue 1: bounding box -------------------------------------------------------------------------------------------
     LgGrid gr;
@@ -221,6 +219,9 @@ __global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const flo
             red[w * 8 + 4] = hx; red[w * 8 + 5] = hy; red[w * 8 + 6] = hz;
         }
         for (int c = t; c < kLgCells; c += T) hist[c] = 0;
+        // SHORT (clouds that may have fewer than 16 groups: a ragged batch; dense input has 65 or more): a wave without a group
+        // never publishes, and every thread reads all 16 slots of a round -- such a slot holds 0, below every real key, throughout.
+        if (SHORT && t < 2 * W) skey[t] = 0ull;
         __syncthreads();
         float lo[3], sc[3];
 #pragma unroll
@@ -376,12 +377,71 @@ __global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const flo
 }
 
 template <int L>
+__global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const float *__restrict__ xyz, float4 *__restrict__ recs_all,
+                                                         float *__restrict__ md_all, int *__restrict__ out, float *__restrict__ out_xyz)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int cloud = blockIdx.x;
+    fps_large_body<L, false>(n, m, xyz + (size_t)cloud * n * 3, recs_all + (size_t)cloud * n, md_all + (size_t)cloud * n,
+                      out + (size_t)cloud * m, out_xyz ? out_xyz + (size_t)cloud * m * 3 : nullptr, smem);
+}
+
+// Ragged batch (pn2_farthest_point_sample_large_ragged): cloud c holds n_c = lengths[c] <= n points in its padded (n, 3) slab and
+// -- with COUNTS -- yields m_c = npoints[c] <= m samples (both counts: cloud_count, pn2_device.h). The workgroup hands the body its
+// own slabs, all addressed with the PADDED n and m, and runs it with n = n_c, m = m_c: the cloud is computed exactly as if it were
+// alone (the slice rule of fps_reg_ragged_kernel, fps.hip; the chain is prefix-consistent, so m_c samples are the first m_c of m).
+// Rows m_c .. m-1 are fps_ragged_fill's: index 0 and xyz[c, 0], disjoint from the body's rows, so no barrier stands in between.
+// What the body assumed of kernel-uniform extents, per workgroup:
+//   * the return at m_c == 1 is a return from the body before its first barrier; the fill follows it;
+//   * every __syncthreads() sits at the top level of the body or of the chain's loop over j < m_c, and n_c, m_c are read through
+//     readfirstlane: all 1024 threads of the workgroup run the same barriers, whatever the other workgroups' counts are;
+//   * the passes over the cloud (box, histogram, scatter) run k < n_c, and the histogram then sums to n_c, so the scatter's
+//     places are 0 .. n_c-1: rows at or beyond n_c of the cloud, of the records and of the distances are never addressed;
+//   * G = ceil(n_c / L) may be as small as 1, with a single real record: lg_group_load's min(i, n_c - 1) keeps the reads of the
+//     missing records inside the slice, lg_group_finish gives them key 0 and stores nothing for them;
+//   * with G < 16 some waves own no group: their group keys and wave key stay 0, they never publish, and their key slots were
+//     zeroed in the prologue (SHORT; a dense cloud has at least 65 groups and compiles without the store);
+//   * a one-point or otherwise degenerate cloud has a box of extent 0: every point in cell 0, as for dense input;
+//   * m_c > n_c runs on at value 0, where the smallest tie key -- point 0 -- wins, as the dense operator with npoint > n.
+template <int L, bool COUNTS>
+__global__ __launch_bounds__(kLgT) void fps_large_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
+                                                                const int *__restrict__ npoints, float4 *__restrict__ recs_all,
+                                                                float *__restrict__ md_all, int *__restrict__ out,
+                                                                float *__restrict__ out_xyz)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c = blockIdx.x;
+    const int nc = cloud_count(lengths, c, n);
+    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
+    const float *__restrict__ src = xyz + (size_t)c * n * 3;
+    int *__restrict__ dst = out + (size_t)c * m;
+    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
+    fps_large_body<L, true>(nc, mc, src, recs_all + (size_t)c * n, md_all + (size_t)c * n, dst, dxyz, smem);
+    if (COUNTS) fps_ragged_fill<kLgT>(mc, m, src, dst, dxyz);
+}
+
+template <int L>
 static int launch_large(int b, int n, int m, const float *inp, void *ws, int *out, float *oxyz, hipStream_t st)
 {
     float4 *recs = static_cast<float4 *>(ws);
     float *md = reinterpret_cast<float *>(recs + (size_t)b * n);
     return launch_lds(fps_large_kernel<L>, dim3(b), dim3(kLgT), kLgLdsBytes, st, n, m, inp, recs, md, out, oxyz);
 }
+
+// npoints: NULL = m samples from every cloud
+template <int L>
+static int launch_large_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, void *ws, int *out,
+                               float *oxyz, hipStream_t st)
+{
+    float4 *recs = static_cast<float4 *>(ws);
+    float *md = reinterpret_cast<float *>(recs + (size_t)b * n);
+    return launch_lds(npoints ? fps_large_ragged_kernel<L, true> : fps_large_ragged_kernel<L, false>, dim3(b), dim3(kLgT), kLgLdsBytes, st,
+                      n, m, inp, lengths, npoints, recs, md, out, oxyz);
+}
+
+// fps.hip: the global-memory kernel with counts (running distances in temp, (b, n) floats)
+int fps_launch_generic_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, float *temp, int *out,
+                              float *oxyz, hipStream_t st);
 
 static bool large_covers(int n) { return n > kLgMinPoints && n <= kLgMaxPoints; }
 
@@ -431,4 +491,42 @@ extern "C" int pn2_farthest_point_sample_large_ex(int group_len, int b, int n, i
 extern "C" int pn2_farthest_point_sample_large(int b, int n, int m, const float *inp, void *ws, int *out, float *out_xyz, void *stream)
 {
     return pn2_farthest_point_sample_large_ex(256, b, n, m, inp, ws, out, out_xyz, stream);
+}
+
+// Ragged batch of large clouds: cloud c is inp[c, :lengths[c]] of a padded (b, n, 3) tensor, 16384 < n <= 1048576, and yields
+// npoints[c] samples (NULL: m). Both count arrays live on the device and are never read by the host, so every host decision is
+// taken on the padded extents: ws is pn2_fps_large_ws_bytes(b, n) bytes, and kernel 0 follows pn2_fps_large_pays(n, m). kernel 1
+// is the global-memory kernel with counts (its running distances in the workspace's distance array), kernel 2 the cell-sorted
+// tier. Result per cloud = the dense operator on the slice, whichever kernel runs.
+extern "C" int pn2_farthest_point_sample_large_ragged_ex(int kernel, int group_len, int b, int n, int m, const float *inp,
+                                                         const int *lengths, const int *npoints, void *ws, int *out, float *out_xyz,
+                                                         void *stream)
+{
+    using namespace pn2;
+    if (m <= 0 || b == 0) return PN2_OK;
+    if (b < 0 || n <= 0) return PN2_E_SHAPE;
+    if (!inp || !out || !ws || !lengths) return PN2_E_NULL;
+    if (!large_covers(n)) return PN2_E_TOO_LARGE;
+    if ((long long)b * n * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
+    if (kernel < 0 || kernel > 2) return PN2_E_ARG;
+    if (group_len != 64 && group_len != 128 && group_len != 256) return PN2_E_ARG;
+    const bool tier = kernel == 2 || (kernel == 0 && pn2_fps_large_pays(n, m));
+    if (tier && ((long long)n + group_len - 1) / group_len > kLgMaxGroups) return PN2_E_TOO_LARGE;   // four box slots per lane
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return PN2_E_ARG;                                       // 16-byte records
+    hipStream_t st = as_stream(stream);
+    if (!tier) {
+        float *md = reinterpret_cast<float *>(static_cast<float4 *>(ws) + (size_t)b * n);
+        return fps_launch_generic_ragged(b, n, m, inp, lengths, npoints, md, out, out_xyz, st);
+    }
+    switch (group_len) {
+    case 64: return launch_large_ragged<64>(b, n, m, inp, lengths, npoints, ws, out, out_xyz, st);
+    case 128: return launch_large_ragged<128>(b, n, m, inp, lengths, npoints, ws, out, out_xyz, st);
+    default: return launch_large_ragged<256>(b, n, m, inp, lengths, npoints, ws, out, out_xyz, st);
+    }
+}
+
+extern "C" int pn2_farthest_point_sample_large_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints,
+                                                      void *ws, int *out, float *out_xyz, void *stream)
+{
+    return pn2_farthest_point_sample_large_ragged_ex(0, 256, b, n, m, inp, lengths, npoints, ws, out, out_xyz, stream);
 }

@@ -108,8 +108,8 @@ def set_fps_variant(variant=FPS_AUTO):
 
 # Large dense clouds (16384 < n <= 1048576): the cell-sorted, box-pruned tier of csrc/fps_large.hip instead of the global-memory
 # kernel. None = where the library's measured size rule says it pays (pn2_fps_large_pays), True = wherever it is supported,
-# False = never. Dense input only (no lengths / npoints), and only while no tier is forced with set_fps_variant. Results never
-# depend on it.
+# False = never. Dense input (no lengths / npoints) -- ragged batches of this size only under set_fps_ragged_large(True) below,
+# where the same three modes choose the kernel --, and only while no tier is forced with set_fps_variant. Results never depend on it.
 _FPS_LARGE = [None]
 FPS_REG_MAX_POINTS = 16384              # up to here the register-resident tiers (pn2_fps_temp_floats is 0)
 
@@ -184,10 +184,39 @@ def ordered_workspace(lib, dev, stream, b):
 
 
 FPS_RAGGED_MAX_POINTS = 16384           # the register tiers' envelope (pn2_farthest_point_sample_ragged)
+FPS_RAGGED_LARGE_MAX_POINTS = 1048576   # the large-cloud entry's (pn2_farthest_point_sample_large_ragged)
+
+# Ragged batches beyond 16384 padded points: opt-in. Off (the default), `lengths=` / `npoints=` stop at FPS_RAGGED_MAX_POINTS with
+# the ValueError below. On, a padded n of 16385 .. 1048576 goes through pn2_farthest_point_sample_large_ragged_ex with a workspace
+# allocated per call; set_fps_large chooses its kernel (None = pn2_fps_large_pays on the padded n and npoint, True = the
+# cell-sorted tier, False = the global-memory kernel with counts). A tier forced with set_fps_variant keeps the 16384 limit.
+_FPS_RAGGED_LARGE = [False]
+
+
+def set_fps_ragged_large(flag=False):
+    require(isinstance(flag, bool), "fps ragged large flag must be True or False")
+    _FPS_RAGGED_LARGE[0] = flag
+
+
+def _fps_ragged_large(m, inp, lengths, out, new_xyz, op, npoints):
+    b, n, _ = inp.shape
+    require(n <= FPS_RAGGED_LARGE_MAX_POINTS, "%s with lengths supports at most %d points per (padded) cloud, got %d"
+            % (op, FPS_RAGGED_LARGE_MAX_POINTS, n))
+    dev = inp.device
+    lib = _C.lib()
+    lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
+    cnts = ragged_lengths(npoints, b, dev, "npoints") if npoints is not None else None
+    kernel = {None: 0, True: 2, False: 1}[_FPS_LARGE[0]]
+    ws = torch.empty((lib.pn2_fps_large_ws_bytes(b, n),), dtype=torch.uint8, device=dev)    # per call, on the padded n
+    with on_device(dev):
+        _C.check(lib.pn2_farthest_point_sample_large_ragged_ex(kernel, 256, b, n, m, ptr(inp), ptr(lens), ptr(cnts), ptr(ws), ptr(out),
+                                                               ptr(new_xyz), stream_ptr(dev)), op)
 
 
 def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
     b, n, _ = inp.shape
+    if _FPS_RAGGED_LARGE[0] and not _FPS_VARIANT[0] and n > FPS_RAGGED_MAX_POINTS:
+        return _fps_ragged_large(m, inp, lengths, out, new_xyz, op, npoints)
     require(n <= FPS_RAGGED_MAX_POINTS, "%s with lengths supports at most %d points per (padded) cloud, got %d"
             % (op, FPS_RAGGED_MAX_POINTS, n))
     dev = inp.device
