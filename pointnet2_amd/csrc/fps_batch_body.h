@@ -69,7 +69,8 @@
 //     ahead of the sample loop the adaptation sits on the chain and cost the metric 3 % -- profiles/fps_turnaround/README.md).
 //
 // Once a sample's value is 0 every running distance is 0 and the reference keeps selecting point 0 (its tie rule): the rest of
-// the output is filled directly.
+// the output is filled directly. A cloud on which a point still stands at the start value 1e38 at the end of the early rounds --
+// every cloud with a NaN or infinite coordinate -- gets no lists at all (the updaters' branch, "NO LISTS").
 //
 // Exactness of the acceptance rule in fp32 bit patterns: values are non-negative floats, so integer comparison of the bits is
 // the value order; "value > second-best" is "bits >= second-best bits + 1". A sample with value bits >= the maximum of the waves'
@@ -194,6 +195,14 @@ __device__ __forceinline__ int bt_wave_max_i32_lane63(int v)
 // 0.002 ms per step slower on the benchmark (-1.0 is an inline constant of the 64-bit move; the other pattern takes two literal
 // moves and a register pair that lives across the batch loop): profiles/fps_turnaround/README.md.
 __device__ __forceinline__ double kBtInvalidKey() { return -1.0; }
+
+// NO LISTS (the updaters' branch of the body): did the last sample but one of the early rounds still have the start value 1e38?
+// Read behind the last early round's barrier by every wave, the picker included; written once, in front of that barrier. Fewer
+// than two early rounds (a lab build, or a row of one or two samples, which has no lists anyway) leave the rule off.
+__device__ __forceinline__ bool bt_stands_at_start(const BtXchg *xch, int jE)
+{
+    return jE >= 3 && __builtin_amdgcn_readfirstlane((int)xch[0].spare1) == __float_as_int(1e38f);
+}
 
 // LDS atomic maximum without the compiler's wave-level pre-reduction (a readlane loop over the active lanes: ~50 cycles per
 // lane on a lone wave; the LDS unit serialises same-address atomics in a few cycles each)
@@ -358,6 +367,8 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             if (j == 8) e0 = (long long)__builtin_readcyclecounter();
             __syncthreads();
         }
+        if (bt_stands_at_start(xch, jE))         // NO LISTS (the updaters' branch): their rounds to the end of the row
+            for (; j < m; ++j) __syncthreads();
         // SLOW BATCHES: cycles of a one-per-exchange round (none measured: batches always pay), decayed cycles / samples of the
         // batches since the last such run, batches counted, length of the next run, clock at the previous idle point
         const float round_cyc = jE >= 24 ? (float)((long long)__builtin_readcyclecounter() - e0) / (float)(jE - 8) : 1e30f;
@@ -787,7 +798,10 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
                         asm("v_max_f64 %0, %1, %2" : "=v"(kd[i]) : "v"(kd[i]), "v"(kd[i + st]));
                 const double wd = wave_max_f64_lane63(kd[0]);
                 double *slot = partial + (j & 1) * W;
-                if (lane == 63) slot[w] = wd;
+                if (lane == 63) {
+                    slot[w] = wd;
+                    if (w == 0 && j == jE - 1) xch[0].spare1 = vlastb;           // NO LISTS (below): the previous sample's value, written once
+                }
                 __syncthreads();
                 double key[W];
 #pragma unroll
@@ -820,7 +834,18 @@ __device__ __forceinline__ void fps_batch_body(int n, int m, int Q, int cloud, c
             }
             thetab = __float_as_uint(__fmul_rn(__uint_as_float(vlastb), 1.0f - PN2_BT_G0));
         };
-        if (jE > 1) single_rounds(jE);
+        // NO LISTS while a point stands at the start value 1e38. A list is exact because a picked candidate leaves it: its distance
+        // to itself is 0. A point with a NaN or infinite coordinate is at distance NaN (or inf) from everything, itself included;
+        // min() leaves it at 1e38 for ever, and once the reference has picked it, it picks it in every later round (values only
+        // fall, and it had the best tie rank at 1e38 already) -- whatever else still stands at 1e38, which is what a list would
+        // go on to. While such a point exists every sample's value is 1e38, so: if the last sample but one of the early rounds
+        // (the word wave 0 left in front of the last round's barrier: the picker reads the same word behind it) still had that
+        // value, the rest of the row is taken one per exchange as well. Exact whatever the cause; a cloud of finite points that
+        // is still at 1e38 after 46 samples (46 clusters ~1e19 apart) merely runs at the full tier's pace.
+        for (int jend = jE; j < jend;) {
+            single_rounds(jend);
+            if (bt_stands_at_start(xch, jE)) jend = m;
+        }
         int par = 0;
         long long uend = 0;                          // lab: the clock when the previous batch's end flag was seen
         if (j < m)

@@ -21,8 +21,12 @@
 // of the group the exact |p - s|^2 >= the exact box distance; the fp32 evaluations of both carry relative errors below
 // 1e-6 and absolute errors (underflow) below 1e-37. The group is skipped only when bd >= v* * 1.00001f + 1e-30f, which
 // therefore implies d_fp32(p, s) >= v* >= mind[p] for every p in the group: min(d, mind[p]) = mind[p], exactly what the
-// reference computes. Non-finite coordinates (unspecified in the reference, as NaN is) can only make boxes infinite,
-// i.e. tests fail towards "update". Measured on the bench clouds (simulation of this exact test in numpy, then the
+// reference computes. Non-finite coordinates: a point with one keeps its start distance 1e38 whatever the sample (its distance
+// to anything is NaN or inf and min() keeps the other operand), so no skip can be wrong about IT -- which is why it does not
+// matter that fminf / fmaxf leave a NaN coordinate out of its group's box (an infinite one makes the box infinite). A sample
+// with a NaN coordinate gives bd = NaN, "not far": every group is updated, to no effect; one with an infinite coordinate gives
+// bd = inf for every finite box (skipped: every distance to it is inf) and NaN for its own (updated). The tiers and the reference's own
+// kernel are tested on such clouds (tests/fps_cases.py). Measured on the bench clouds (simulation of this exact test in numpy, then the
 // GPU): 2.6 of 16 slots per thread are updated per round at n = 4096 -> 1024 on sphere-surface clouds, 3.2 on
 // uniform-cube clouds, 3.5-4.6 of 32 at n = 8192; a cloud with 87 % of its points on one spot (provider.py:227-233)
 // prunes little (10 of 16) and costs what fps_reg_body costs.

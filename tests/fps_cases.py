@@ -31,8 +31,28 @@ def islands(c, shift):
     return c
 
 
+def poke(c, points):
+    """Every cloud with coordinate `axis` of point k set to `value`, for (k, axis, value) in points."""
+    c = np.array(c, dtype=np.float32)
+    for k, axis, value in points:
+        c[:, k, axis] = np.float32(value)
+    return c
+
+
+def denormal_z(c):
+    """z of point k = float32((k % 701) * 1e-42): 701 distinct denormals, an extent of 7e-40 whose reciprocal overflows fp32 (the
+    bin scale of a grouping prologue is cells / extent)."""
+    c = np.array(c, dtype=np.float32)
+    c[:, :, 2] = ((np.arange(c.shape[1]) % 701) * 1e-42).astype(np.float32)
+    return c
+
+
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+NAN, INF = float("nan"), float("inf")
+X, Y, Z = 0, 1, 2
 
 
 FPS_LITERAL_CASES = [
@@ -75,6 +95,21 @@ FPS_LITERAL_CASES = [
     ("n37_all", lambda: S.uniform_clouds(2, 37, 923), 37, False),
     # ---- the metric shape, B = 32
     ("metric32", lambda: S.sphere_clouds(32, 4096, 924), 1024, False),
+    # ---- non-finite coordinates inside the cloud. Such a point keeps its start distance 1e38 for ever (its distance to anything,
+    # itself included, is NaN or inf, and min() keeps the other operand): round 1 picks the non-finite point with the smallest
+    # (k mod 512, k), every later round picks it again, and no running distance changes.
+    ("nan_one_4096", lambda: poke(S.uniform_clouds(2, 4096, 1501), [(700, Y, NAN)]), 512, False),               # batched
+    ("nonfinite_ties_4096", lambda: poke(S.sphere_clouds(2, 4096, 1502),                 # batched; 518 and 1030 are both 6 mod 512
+                                         [(700, X, NAN), (1030, Z, INF), (3000, Y, -INF), (518, X, INF)]), 300, False),
+    ("nan_first_2049", lambda: poke(S.sphere_clouds(2, 2049, 1503), [(0, X, NAN)]), 300, False),                # batched; all 0
+    ("nonfinite_8192_pruned", lambda: poke(S.uniform_clouds(2, 8192, 1504), [(5000, X, INF), (4100, Y, NAN)]), 200, False),  # pruned
+    ("nan_12000", lambda: poke(S.uniform_clouds(2, 12000, 1505), [(11999, Z, NAN)]), 64, False),                # register
+    ("nonfinite_20000", lambda: poke(S.uniform_clouds(2, 20000, 1506), [(16400, X, -INF), (19999, Y, NAN)]), 48, False),  # global
+    ("inf_small37", lambda: poke(S.uniform_clouds(2, 37, 1507), [(36, X, INF)]), 37, False),                    # register
+    ("quarter_nan_4096", lambda: poke(S.uniform_clouds(2, 4096, 1508), [(k, X, NAN) for k in range(1, 4096, 4)]), 400, False),  # batched
+    # ---- an axis whose extent is a denormal: the bin scale of the grouping prologues overflows
+    ("denormal_extent_4096", lambda: denormal_z(S.uniform_clouds(2, 4096, 1509)), 512, False),                  # batched
+    ("denormal_extent_8192", lambda: denormal_z(S.uniform_clouds(2, 8192, 1510)), 200, False),                  # pruned
 ]
 
 FPS_LITERAL_NAMES = [c[0] for c in FPS_LITERAL_CASES]

@@ -9,6 +9,7 @@ tier is tested against the same oracle in tests/test_parity_gpu.py)."""
 import numpy as np
 import pytest
 
+from fps_cases import FPS_LITERAL_CASES, FPS_LITERAL_NAMES
 from pointnet2_amd import synthetic as S
 
 F = np.float32
@@ -29,7 +30,8 @@ def _lanes(x, slots):
     """point -> (wave, lane): 32 leaves of equal size along the axes sorted by extent, leaf (a, r) -> wave (r + a) % 8, position
     p of the leaf -> lane p % 64 (fps_pruned_prologue; any dealing gives the same samples, this one gives the kernel's lists)"""
     n = x.shape[0]
-    ext = x.max(axis=0) - x.min(axis=0)
+    with np.errstate(all="ignore"):
+        ext = np.fmax.reduce(x, axis=0) - np.fmin.reduce(x, axis=0)
     a0, a1, a2 = np.argsort(-ext, kind="stable")
     ids = np.arange(n)
     unit = np.zeros(n, dtype=np.int64)
@@ -41,16 +43,20 @@ def _lanes(x, slots):
     return unit
 
 
-def _batched_fps(x, m, early=EARLY, runs=None):
+def _batched_fps(x, m, early=EARLY, runs=None, no_lists_rule=True):
     """runs: None, or a function batch number -> how many samples to take one per exchange after that batch (the kernel decides
-    that by its clock -- SLOW BATCHES in fps_batch_body.h --, so any schedule must give the oracle's samples)"""
+    that by its clock -- SLOW BATCHES in fps_batch_body.h --, so any schedule must give the oracle's samples). no_lists_rule:
+    the kernel's NO LISTS -- if the last sample but one of the early rounds still had the start value 1e38, the whole row is
+    taken one per exchange. A list is exact because a picked candidate leaves it (its distance to itself is 0); a point with a
+    NaN or infinite coordinate stays at 1e38 for ever and is the reference's sample in every later round, where a list would go
+    on to the next point at 1e38. While such a point exists every sample's value is 1e38."""
     x = x.astype(F)
     n = x.shape[0]
     q = (n + REF_THREADS - 1) // REF_THREADS
     rank = (np.arange(n) % REF_THREADS) * q + np.arange(n) // REF_THREADS             # smaller wins a tie (tf_sampling_g.cu:146,153-163)
     unit = _lanes(x, 16)
     members = [np.nonzero(unit == u)[0] for u in range(64 * WAVES)]
-    td = np.minimum(np.full(n, 1e38, dtype=F), _sqdist(x, x[0]))
+    td = np.fmin(np.full(n, 1e38, dtype=F), _sqdist(x, x[0]))
     out = [0]
 
     def argmax_all():
@@ -59,10 +65,13 @@ def _batched_fps(x, m, early=EARLY, runs=None):
         return int(c[np.argmin(rank[c])]), best
 
     vlast = F(1e38)
-    while len(out) < min(early, m):                                                       # EARLY: one sample per exchange
-        p, vlast = argmax_all()
+    jE = min(early, m)
+    while len(out) < jE:                                                                  # EARLY: one sample per exchange
+        before, (p, vlast) = vlast, argmax_all()
         out.append(p)
-        td = np.minimum(td, _sqdist(x, x[p]))
+        td = np.fmin(td, _sqdist(x, x[p]))
+        if no_lists_rule and len(out) == jE and jE >= 3 and before == F(1e38):            # NO LISTS
+            jE = m
     g = G0
     theta_b = int(_bits(F(vlast * F(F(1.0) - g)))) if len(out) > 1 else int(_bits(F(1e38)))
     vlast_b = int(_bits(vlast))
@@ -137,8 +146,8 @@ def _batched_fps(x, m, early=EARLY, runs=None):
             vlast_b = bh
             alive[c] = False
             d = _sqdist(x, x[p])
-            td = np.minimum(td, d)
-            cv = np.minimum(cv, d[cp])
+            td = np.fmin(td, d)
+            cv = np.fmin(cv, d[cp])
             if bh == 0:
                 filled = True
                 break
@@ -157,7 +166,7 @@ def _batched_fps(x, m, early=EARLY, runs=None):
             for _ in range(single):
                 p, vlast = argmax_all()
                 out.append(p)
-                td = np.minimum(td, _sqdist(x, x[p]))
+                td = np.fmin(td, _sqdist(x, x[p]))
             vlast_b = int(_bits(vlast))
             theta_b = int(_bits(F(vlast * F(F(1.0) - G0))))
     return np.array(out, dtype=np.int32), batches
@@ -179,6 +188,26 @@ def test_a_list_determines_several_samples_and_they_are_the_oracles(oracle, name
     assert np.array_equal(got, want[0]), "%s: first mismatch at %s" % (name, np.argwhere(got != want[0])[:3].ravel())
     if name in ("sphere", "uniform"):
         assert np.mean(batches) > 4.0, "a batch should yield several samples on a smooth cloud: %.2f" % np.mean(batches)
+
+
+NONFINITE = ["nan_one_4096", "nonfinite_ties_4096", "nan_first_2049", "nonfinite_8192_pruned", "quarter_nan_4096"]
+
+
+@pytest.mark.parametrize("name", NONFINITE)
+def test_no_lists_while_a_point_stands_at_the_start_value(oracle, name):
+    """The non-finite clouds of tests/fps_cases.py. Where several non-finite points stand at 1e38 (nonfinite_ties_4096: 518,
+    1030, 700, 3000), lists WITHOUT the rule take them one after the other -- the wrong samples the device tier gave before it
+    had the rule (THE CLAIM of the pick loop fails at the second of them)."""
+    _, make, m, _ = FPS_LITERAL_CASES[FPS_LITERAL_NAMES.index(name)]
+    clouds = make()
+    want = oracle.farthest_point_sample(m, clouds)
+    with np.errstate(all="ignore"):
+        got, batches = _batched_fps(clouds[0], m)
+        assert np.array_equal(got, want[0]), "%s: first mismatch at %s" % (name, np.argwhere(got != want[0])[:3].ravel())
+        assert batches == []
+        if name == "nonfinite_ties_4096":
+            with pytest.raises(AssertionError, match="is not the cloud's arg-max"):
+                _batched_fps(clouds[0], m, no_lists_rule=False)
 
 
 def test_batches_without_the_early_phase_are_exact_too(oracle):

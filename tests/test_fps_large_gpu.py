@@ -2,13 +2,14 @@
 CPU oracle through pn2_farthest_point_sample_large_ex at every group length, on the clouds its CPU model has reproduced the oracle
 on (tests/fps_large_cases.py) and on the sizes where the grouping takes another shape (a one-record last group, a whole number
 of groups and one record either side of it, several clouds, more samples than points, one sample, degenerate boxes, a coarse fp32
-grid); out_xyz is the gather of the indices bit for bit; the Python operators give the same tensors whichever kernel runs; the
+grid, non-finite coordinates) and, at the group lengths that can hold them, on the clouds that fill all 4096 box slots of the
+kernel (1048576 points at L = 256); out_xyz is the gather of the indices bit for bit; the Python operators give the same tensors whichever kernel runs; the
 entry is one kernel node in a captured graph; and it is not slower than the global-memory kernel where the size rule sends it."""
 import numpy as np
 import pytest
 import torch
 
-from fps_large_cases import LARGE_CASES
+from fps_large_cases import FULL_TABLE_CASES, LARGE_CASES
 from pointnet2_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
@@ -33,13 +34,16 @@ EXTRA_CASES = [
     ("far_offset", lambda: _f32(S.sphere_clouds(1, 20000, 1231) * np.float32(1e-3) + np.float32(100.0)), 200),   # coarse fp32 grid
 ]
 CASES = [(c[0], c[1], c[2]) for c in LARGE_CASES] + EXTRA_CASES
+# the whole group table: a case at its own group length and every larger one (fewer groups: a smaller L is PN2_E_TOO_LARGE)
+FULL_TABLE_RUNS = [(c[0], L) for c in FULL_TABLE_CASES for L in GROUP_LENS if L >= c[3]]
 _WANT = {}
 
 
 def _case(oracle, name):
     """(cloud, oracle indices), computed once per case and shared by the group lengths."""
     if name not in _WANT:
-        _, make, m = CASES[[c[0] for c in CASES].index(name)]
+        table = CASES + [(c[0], c[1], c[2]) for c in FULL_TABLE_CASES]
+        _, make, m = table[[c[0] for c in table].index(name)]
         x = _f32(make())
         _WANT[name] = (x, oracle.farthest_point_sample(m, x))
     return _WANT[name]
@@ -66,14 +70,39 @@ def _large(x, m, group_len=None, want_xyz=True):
 @pytest.mark.parametrize("group_len", GROUP_LENS)
 @pytest.mark.parametrize("name", [c[0] for c in CASES])
 def test_index_exact_against_the_oracle(cuda, oracle, name, group_len):
+    _check_against_the_oracle(cuda, oracle, name, group_len)
+
+
+def _check_against_the_oracle(cuda, oracle, name, group_len):
     xyz, want = _case(oracle, name)
     x = torch.from_numpy(xyz).to(cuda)
-    m = want.shape[1]
-    out, oxyz = _large(x, m, group_len)
+    out, oxyz = _large(x, want.shape[1], group_len)
     got = out.cpu().numpy()
     assert np.array_equal(got, want), "%s L=%d: first difference at %s" % (name, group_len, np.argwhere(got != want)[:3].ravel())
     gathered = np.take_along_axis(xyz, want[:, :, None].astype(np.int64).repeat(3, axis=2), axis=1)
     assert np.array_equal(oxyz.cpu().numpy().view(np.uint32), gathered.view(np.uint32)), "out_xyz is not gather_point(inp, idx) bit for bit"
+
+
+@pytest.mark.parametrize("name,group_len", FULL_TABLE_RUNS, ids=["%s-L%d" % r for r in FULL_TABLE_RUNS])
+def test_the_whole_group_table(cuda, oracle, name, group_len):
+    """4096 groups, all four box slots of every lane (and 2049: a one-record group alone in slot 2), on the clouds whose winners
+    the CPU model has found in all four quarters of the table, every quarter both updated and skipped
+    (tests/test_fps_large_model.py)."""
+    _check_against_the_oracle(cuda, oracle, name, group_len)
+
+
+def test_the_python_operator_at_the_top_of_the_envelope(cuda, oracle):
+    """1048576 points, the largest cloud the tier takes: the size rule (None), the tier (True) and the global-memory kernel
+    (False) return the oracle's indices."""
+    import pointnet2_amd as P
+    xyz, want = _case(oracle, "full_table_256")
+    x = torch.from_numpy(xyz).to(cuda)
+    try:
+        for mode in (True, False, None):
+            P.set_fps_large(mode)
+            assert np.array_equal(P.farthest_point_sample(want.shape[1], x).cpu().numpy(), want), mode
+    finally:
+        P.set_fps_large(None)
 
 
 def test_the_plain_entry_and_a_null_out_xyz(cuda, oracle):

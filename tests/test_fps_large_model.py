@@ -9,7 +9,7 @@ the same clouds in tests/test_fps_large_gpu.py)."""
 import numpy as np
 import pytest
 
-from fps_large_cases import LARGE_CASES, LARGE_NAMES
+from fps_large_cases import FULL_TABLE_CASES, FULL_TABLE_NAMES, LARGE_CASES, LARGE_NAMES
 from pointnet2_amd import synthetic as S
 
 F = np.float32
@@ -30,20 +30,27 @@ def _cell_order(x):
     """The kernel's prologue: bounding box, 32 bins per axis (a degenerate axis: bin 0), Morton cell number, cell order. The
     order inside a cell is timing dependent on the device and irrelevant; here it is the input order."""
     with np.errstate(all="ignore"):
-        lo, hi = x.min(axis=0).astype(F), x.max(axis=0).astype(F)
+        lo, hi = np.fmin.reduce(x, axis=0).astype(F), np.fmax.reduce(x, axis=0).astype(F)     # fminf / fmaxf: NaNs drop out
         e = (hi - lo).astype(F)
         ok = (e > 0) & np.isfinite(e)
         scale = np.where(ok, F(AXIS_CELLS) / np.where(ok, e, F(1)), F(0)).astype(F)
         scale = np.where(np.isfinite(scale), scale, F(0)).astype(F)
         lo = np.where(ok, lo, F(0)).astype(F)
         f = ((x - lo[None, :]).astype(F) * scale[None, :]).astype(F)
-        bins = np.minimum(np.maximum(f, F(0)), F(AXIS_CELLS - 1)).astype(np.int64)      # fmaxf(NaN, 0) = 0
+        bins = np.fmin(np.fmax(f, F(0)), F(AXIS_CELLS - 1)).astype(np.int64)            # fmaxf(NaN, 0) = 0
     cell = (_spread5(bins[:, 0]) << 2) | (_spread5(bins[:, 1]) << 1) | _spread5(bins[:, 2])
     return np.argsort(cell, kind="stable")
 
 
-def _large_fps(x, m, L, check=True):
-    """-> (indices, updated share of (group, round) pairs)."""
+def _med3(s, lo, hi):
+    """v_med3_f32, the kernel's clamp: the median of three. A box axis without a finite-or-infinite member (all NaN) is
+    lo = inf, hi = -inf, whose median with s is s; a NaN sample gives NaN - something = NaN below whatever comes back here."""
+    return np.fmax(np.fmin(s, lo), np.fmin(np.fmax(s, lo), hi))
+
+
+def _large_fps(x, m, L, check=True, stats=None):
+    """-> (indices, updated share of (group, round) pairs). stats: a dict that receives "group_of" (point -> its group) and
+    "updates" (per group, the rounds it was updated in)."""
     x = np.ascontiguousarray(x, dtype=F)
     n = x.shape[0]
     order = _cell_order(x)                                   # record i of the sorted copy = point order[i]
@@ -56,9 +63,11 @@ def _large_fps(x, m, L, check=True):
     real = np.concatenate([np.ones(n, bool), np.zeros(pad, bool)])
     recp = np.concatenate([rec, np.repeat(rec[-1:], pad, axis=0)]) if pad else rec
     with np.errstate(all="ignore"):
-        lo = np.where(real[:, None], recp, F(np.inf)).reshape(G, L, 3).min(axis=1).astype(F)
-        hi = np.where(real[:, None], recp, F(-np.inf)).reshape(G, L, 3).max(axis=1).astype(F)
+        # tight boxes by fminf / fmaxf, as lg_group_finish builds them: a NaN coordinate drops out of its box
+        lo = np.fmin.reduce(np.where(real[:, None], recp, F(np.inf)).reshape(G, L, 3), axis=1).astype(F)
+        hi = np.fmax.reduce(np.where(real[:, None], recp, F(-np.inf)).reshape(G, L, 3), axis=1).astype(F)
     mind = np.full(G * L, 1e38, dtype=F)
+    updates = np.zeros(G, dtype=np.int64)
 
     def keys_of(rows):                                       # the generic kernel's key; a missing record: 0
         v = mind.reshape(G, L)[rows].view(np.uint32).astype(np.uint64)
@@ -72,26 +81,31 @@ def _large_fps(x, m, L, check=True):
     for j in range(1, m):
         with np.errstate(all="ignore"):
             thr = F(F(vstar * F(1.00001)) + F(1e-30))
-            a = (s[None, :] - np.clip(s[None, :], lo, hi)).astype(F)                       # sample - clamp(sample, lo, hi)
+            a = (s[None, :] - _med3(s[None, :], lo, hi)).astype(F)                         # sample - clamp(sample, lo, hi)
             bd = ((a[:, 0] * a[:, 0]).astype(F) + (a[:, 1] * a[:, 1]).astype(F)).astype(F) + (a[:, 2] * a[:, 2]).astype(F)
-            far = bd >= thr
+            far = bd >= thr                                                                # NaN -> not far -> updated
             if check:
                 d = _sqdist(recp, s)
                 skipped = np.repeat(far, L) & real
-                # THE CLAIM: skipping these groups changes nothing
-                assert (np.minimum(d[skipped], mind[skipped]) == mind[skipped]).all(), \
+                # THE CLAIM: skipping these groups changes nothing (fminf: a NaN distance lowers nothing either)
+                assert (np.fmin(d[skipped], mind[skipped]) == mind[skipped]).all(), \
                     "round %d: a skipped group holds a point the sample would have lowered" % j
             rows = np.nonzero(~far)[0]
             view = mind.reshape(G, L)
             view[rows] = np.fmin(_sqdist(recp.reshape(G, L, 3)[rows].reshape(-1, 3), s).reshape(-1, L), view[rows])
         gkey[rows] = keys_of(rows).max(axis=1)                # touched groups refresh their key, the others keep theirs
         updated += len(rows)
-        best = gkey.max()                                     # the arg-max runs over cached keys only
+        updates[rows] += 1
+        best = gkey.max()                                   # the arg-max runs over cached keys only
         tk = np.uint64(0xFFFFFFFF) - (best & np.uint64(0xFFFFFFFF))
         cur = int(((tk & np.uint64(0x3FFFFF)) << np.uint64(9)) | (tk >> np.uint64(22)))
         vstar = np.array([best >> np.uint64(32)], dtype=np.uint64).astype(np.uint32).view(F)[0]
         s = x[cur]
         out[j] = cur
+    if stats is not None:
+        stats["group_of"] = np.empty(n, dtype=np.int64)
+        stats["group_of"][order] = np.arange(n) // L
+        stats["updates"] = updates
     return out, updated / max(G * (m - 1), 1)
 
 
@@ -104,6 +118,36 @@ def test_cached_group_keys_and_the_skip_rule_give_the_oracles_samples(oracle, na
         assert np.array_equal(got, want[b]), "%s cloud %d: first difference at %s" % (name, b, np.argwhere(got != want[b])[:3].ravel())
         if name.startswith("identical"):
             assert share == 1.0, "every box of an identical cloud holds every sample: nothing can be pruned (%.3f)" % share
+
+
+SLOT_GROUPS = 1024                                           # groups per box slot: 16 waves x 64 lanes
+
+
+@pytest.mark.parametrize("name,make,m,L,groups", FULL_TABLE_CASES, ids=FULL_TABLE_NAMES)
+def test_the_whole_group_table(oracle, name, make, m, L, groups):
+    """The clouds that fill the kernel's four box slots per lane (slot i = groups 1024 i .. 1024 i + 1023). Besides the oracle's
+    samples, CONDITIONS ON THE CASE, so that the device test of the same cloud does run what it is there for: the winners come
+    from groups of all four quarters of the table (publishing from best[] at every slot), and in every quarter some (group,
+    round) pairs were updated and some skipped (both branches of every slot's ballot)."""
+    clouds = make()
+    n = clouds.shape[1]
+    assert (n + L - 1) // L == groups
+    want = oracle.farthest_point_sample(m, clouds)
+    for b in range(clouds.shape[0]):
+        stats = {}
+        got, share = _large_fps(clouds[b], m, L, stats=stats)
+        assert np.array_equal(got, want[b]), "%s cloud %d: first difference at %s" % (name, b, np.argwhere(got != want[b])[:3].ravel())
+        slots = (groups + SLOT_GROUPS - 1) // SLOT_GROUPS
+        winners = np.bincount(stats["group_of"][want[b][1:]] // SLOT_GROUPS, minlength=slots)
+        per_slot = [stats["updates"][q * SLOT_GROUPS:(q + 1) * SLOT_GROUPS] for q in range(slots)]
+        shares = [float(u.sum()) / (len(u) * (m - 1)) for u in per_slot]
+        print("%s cloud %d: winners per quarter %s, updated share per quarter %s" % (name, b, winners.tolist(), ["%.3f" % v for v in shares]))
+        if groups == 4096:
+            assert slots == 4 and (winners > 0).all(), winners
+            assert all(0.0 < v < 1.0 for v in shares), shares
+        else:                                                # slot2_first_group: one group in slot 2, one record in it
+            assert slots == 3 and len(per_slot[2]) == 1 and n - (groups - 1) * L == 1
+            assert 0 < per_slot[2][0] < m - 1, "the one-record group is both updated and skipped"
 
 
 SHARE_CASES = [("uniform131072", lambda: S.uniform_clouds(1, 131072, 1211), 1024, 256),

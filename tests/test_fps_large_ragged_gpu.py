@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from fps_large_ragged_cases import CASES, cloud, expected, lengths_of, slice_rule
+from fps_large_ragged_cases import CASES, TABLE_CASES, cloud, expected, lengths_of, slice_rule
 from pointnet2_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
@@ -94,6 +94,17 @@ def test_every_kernel_obeys_the_slice_rule(cuda, oracle, name, padding, kernel, 
     x = dev(padded(xyz, lengths, padding), cuda)
     cnts = lens_t(npoints, cuda) if npoints is not None else None
     out, oxyz = run(kernel, group_len, x, lens_t(lengths, cuda), cnts, m)
+    check_slice_rule(host(out), host(oxyz), xyz, want, lengths, m, npoints)
+
+
+@pytest.mark.parametrize("kernel,group_len", [(GENERIC, 256), (TIER, 64)], ids=["generic", "tier64"])
+@pytest.mark.parametrize("name", sorted(TABLE_CASES))
+def test_the_whole_group_table_beside_shorter_slices(cuda, oracle, name, kernel, group_len):
+    """4096 groups in one workgroup, 2049, 1094 and 1 in its neighbours (tests/fps_large_ragged_cases.py, TABLE_CASES)."""
+    _, _, n, lengths, m, npoints = TABLE_CASES[name]
+    xyz, want = cloud(name), expected(name)
+    x = dev(padded(xyz, lengths, "nan"), cuda)
+    out, oxyz = run(kernel, group_len, x, lens_t(lengths, cuda), None, m)
     check_slice_rule(host(out), host(oxyz), xyz, want, lengths, m, npoints)
 
 

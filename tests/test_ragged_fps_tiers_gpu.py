@@ -66,6 +66,21 @@ def forced(variant):
         tf_sampling.set_fps_variant(before)
 
 
+def nonfinite_clouds(b, n, seed):
+    """Six uniform clouds with non-finite coordinates placed against the lengths of the "nonfinite" case below (a non-finite point
+    keeps its start distance for ever and, once picked, is picked in every later round; tests/fps_cases.py): four kinds inside
+    cloud 0; the ONLY one of cloud 1 just below its length and that of cloud 2 just beyond (cloud 2 is a finite cloud: the point
+    is padding); cloud 3 starts on a NaN point (every sample 0); in cloud 4 it is the one point of the second rank; cloud 5 is
+    exhausted (m > n_c) with the chain locked on its last point."""
+    assert b == 6 and n == 4096
+    nan, inf = float("nan"), float("inf")
+    c = S.uniform_clouds(b, n, seed)
+    for cloud_no, k, axis, value in [(0, 700, 0, nan), (0, 1030, 2, inf), (0, 3000, 1, -inf), (0, 518, 0, inf), (1, 2999, 1, nan),
+                                     (2, 2049, 0, nan), (3, 0, 0, nan), (4, 512, 1, inf), (5, 36, 0, -inf)]:
+        c[cloud_no, k, axis] = value
+    return c
+
+
 # name: (generator, padded n, lengths, m, npoints or None)
 CASES = {
     # one case per batched-tier template; m = 300: AUTO takes the batched tier, m > n_c occurs
@@ -83,6 +98,8 @@ CASES = {
     "pruned_8192": (S.uniform_clouds, 8192, [8192, 5000, 4097, 4096, 1000, 1], 200, None),
     "pruned_4096": (S.sphere_clouds, 4096, [4096, 2049, 2048, 100], 130, None),
     "pruned_4096_counts": (S.sphere_clouds, 4096, [4096, 2049, 2048, 100], 130, [130, 1, 64, 129]),
+    # non-finite points INSIDE the valid lengths, on all four variants (m = 300: AUTO takes the batched tier)
+    "nonfinite": (nonfinite_clouds, 4096, [4096, 3000, 2049, 700, 513, 37], 300, None),
 }
 RUNS = [(name, v) for name in CASES for v in covering(CASES[name][1])]
 
