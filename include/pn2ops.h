@@ -499,6 +499,42 @@ int pn2_farthest_point_sample_ragged_variant(int variant, int b, int n, int m, c
                                              const int *npoints /* NULL: m samples from every cloud */,
                                              int *out, float *out_xyz /* may be NULL */, void *stream);
 
+/* ---- packed batches: clouds back to back with offsets, no padding ---------------------------------------------
+ * Layout: the first side's coordinates are ONE flat array (total, 3) plus `offsets` (b + 1) int32 in DEVICE memory,
+ * 0 = offsets[0] < offsets[1] < ... < offsets[b] = total; cloud c is rows offsets[c] .. offsets[c + 1] - 1. `nmax` is a HOST
+ * bound on every cloud's count, offsets[c + 1] - offsets[c] <= nmax: kernel choice, FPS tier, grid and LDS bytes come from it
+ * exactly as the _ragged entries take them from the padded n. The second side (the queries of the ball query, the known points
+ * of three_nn) and the sampling outputs stay dense (b, m, ...). THE SLICE RULE, PACKED: for every cloud c the result is bit-
+ * and index-identical to the dense entry applied to flat[offsets[c] : offsets[c + 1]] alone (b = 1) -- hence to the _ragged
+ * entry on the same clouds padded --, and no cloud reads a row of its neighbours. A slab may start at any row (coordinates are
+ * read as scalars).
+ * global_idx: 0 = indices are cloud-local, as the reference's; 1 = a point index of the packed side is written as
+ *   offsets[c] + k, a row of the flat array, and a known-point index of pn2_three_nn_packed as c m + j, a row of xyz2 viewed as
+ *   (b m, 3) -- what the index-driven operators (group_point, three_interpolate, the fused stacks) take on the flat views
+ *   (1, total, c) / (1, b m, c). One wave-uniform add where the index is stored; everything else is the local result.
+ * The host never reads `offsets` (no synchronisation, no memset, stream-ordered: capturable, and a replay follows offsets changed
+ * in place); the kernels clamp a cloud's start into 0..total-1 and its count into 1..min(nmax, total - start) for memory safety
+ * only -- validating is the caller's business (Python: pointnet2_amd.check_offsets).
+ * Codes, in this order (the _ragged entries'): attributes out of range PN2_E_ARG; b < 0, nmax <= 0, m < 0 PN2_E_SHAPE; b = 0 or
+ * m = 0 (three_nn: b = 0) PN2_OK before any pointer is looked at; total <= 0 PN2_E_SHAPE; a missing array PN2_E_NULL;
+ * total 3 > INT_MAX PN2_E_TOO_LARGE.
+ *
+ * pn2_farthest_point_sample_packed: variant as pn2_farthest_point_sample_ragged_variant, the size rule on nmax and m; tie rank
+ *   per cloud, Q_c = ceil(n_c / 512). out (b,m), out_xyz (b,m,3) or NULL (always the cloud's own points, whatever global_idx).
+ *   m > n_c behaves as the dense operator with npoint > n. PN2_E_TOO_LARGE for nmax > 16384.
+ * pn2_query_ball_group_xyz_packed: xyz1 (total,3) packed, the queries xyz2 (b,m,3) dense; kernel / cells_qpb as
+ *   pn2_query_ball_group_xyz_ragged; idx (b,m,nsample), pts_cnt (b,m), grouped_xyz (b,m,nsample,3) or NULL.
+ * pn2_three_nn_packed: the UNKNOWN side xyz1 (total,3) packed, the known side xyz2 (b,m,3) dense or -- lengths2 != NULL -- with
+ *   lengths2[c] valid rows as in pn2_three_nn_ragged_pair; variant as pn2_three_nn_ex. dist, idx (total,3): row offsets1[c] + i
+ *   belongs to point i of cloud c; there are no padding rows. */
+int pn2_farthest_point_sample_packed(int variant, int b, int total, int nmax, int m, const float *inp, const int *offsets,
+                                     int global_idx, int *out, float *out_xyz /* may be NULL */, void *stream);
+int pn2_query_ball_group_xyz_packed(int b, int total, int nmax, int m, float radius, int nsample, const float *xyz1,
+                                    const int *offsets1, const float *xyz2, int subtract_centroid, int global_idx, int *idx,
+                                    int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb, void *stream);
+int pn2_three_nn_packed(int b, int total, int nmax, int m, const float *xyz1, const int *offsets1, const float *xyz2,
+                        const int *lengths2 /* may be NULL */, int global_idx, float *dist, int *idx, int variant, void *stream);
+
 /* farthest_point_sample [+ gather_point when out_xyz != NULL] for LARGE dense clouds, 16384 < n <= 1048576: the tier of
  * csrc/fps_large.hip. Same indices as pn2_farthest_point_sample, tie rule (smallest (k mod 512, k)), inf
  * distances clamped to the 1e38 start value, duplicates and m > n included; out_xyz == gather_point(inp, out) bit for bit, written

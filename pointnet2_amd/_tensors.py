@@ -107,6 +107,80 @@ def check_lengths(lengths, n, b=None):
     return t.to(torch.int32)
 
 
+# ---- packed batches: clouds back to back in one (total, 3) array plus offsets (b + 1) -------------------------
+def packed_offsets(offsets, dev, b=None, name="offsets"):
+    """The offsets of a packed batch as the kernels take them: a contiguous int32 tensor (b + 1,) on `dev`. Accepts an int32 /
+    int64 tensor or a sequence; a tensor already on the device is converted there (no host synchronisation; the VALUES are not
+    looked at -- that is check_offsets, where the batch is built). b: the batch size where the call has a dense side to tell it."""
+    t = _lengths_tensor(offsets, name)
+    require(t.dim() == 1 and t.shape[0] >= 1 and (b is None or t.shape[0] == int(b) + 1),
+            "%s must have shape (batch_size + 1,)%s, got %s" % (name, "" if b is None else " = (%d,)" % (int(b) + 1), tuple(t.shape)))
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def packed_args(offsets, max_points, lengths, flat, what, name="offsets", max_name="max_points", b=None):
+    """The checks every operator makes on a packed call before anything else: offsets excludes lengths, max_points is a host
+    int (so nothing synchronises), the coordinate argument is (total, 3). -> (offsets int32 on the device, b, total, nmax)."""
+    require(lengths is None, "%s: %s and lengths are two layouts of a variable-size batch; give one" % (what, name))
+    require(max_points is not None, "%s: %s needs %s, a host int that bounds every cloud's count" % (what, name, max_name))
+    require(not isinstance(max_points, torch.Tensor), "%s must be a host int, not a tensor" % max_name)
+    nmax = int(max_points)
+    require(nmax >= 1, "%s must be positive" % max_name)
+    require(isinstance(flat, torch.Tensor) and flat.dim() == 2 and flat.shape[1] == 3,
+            "%s: with %s the coordinates are one flat (total, 3) array" % (what, name))
+    offs = packed_offsets(offsets, flat.device, b, name)
+    total = int(flat.shape[0])
+    require(total >= 1, "%s: a packed batch holds at least one point" % what)
+    return offs, int(offs.shape[0]) - 1, total, nmax
+
+
+def check_offsets(offsets, total, max_points=None):
+    """Validate the offsets of a packed batch of `total` rows: an int32 / int64 tensor (or a sequence) of shape (b + 1,) with
+    offsets[0] = 0, offsets[b] = total and every cloud's count offsets[c + 1] - offsets[c] in 1..max_points. Raises ValueError.
+    Like check_lengths this is the ONE place that looks at the values, and it synchronises: call it once where the batch is
+    built -- the operators never do (their kernels clamp for memory safety and compute on that).
+    -> offsets as an int32 tensor (on the device it came from)."""
+    t = _lengths_tensor(offsets, "offsets")
+    require(t.dim() == 1 and t.shape[0] >= 2, "offsets must have shape (batch_size + 1,) with at least one cloud, got %s" % (tuple(t.shape),))
+    require(int(total) >= 1, "total must be positive")
+    v = t.to(torch.int64).cpu()
+    require(int(v[0]) == 0, "offsets[0] must be 0 (found %d)" % int(v[0]))
+    require(int(v[-1]) == int(total), "offsets[-1] must be total = %d (found %d)" % (int(total), int(v[-1])))
+    counts = v[1:] - v[:-1]
+    lo, hi = int(counts.min()), int(counts.max())
+    require(lo >= 1, "every cloud of a packed batch holds at least 1 point (found a count of %d)" % lo)
+    require(max_points is None or hi <= int(max_points), "a cloud holds %d points, more than max_points = %s" % (hi, max_points))
+    return t.to(torch.int32)
+
+
+def pack_batch(padded, lengths):
+    """A padded ragged batch (b, n, c) with lengths (b,) -> (flat (total, c), offsets (b + 1,) int32 on the same device): the
+    valid rows back to back. Plain torch, for tests and users building a packed batch; may synchronise."""
+    require(isinstance(padded, torch.Tensor) and padded.dim() == 3, "pack_batch expects a (b, n, c) tensor")
+    b, n, _ = padded.shape
+    lens = check_lengths(lengths, n, b).to(device=padded.device, dtype=torch.int64)
+    keep = torch.arange(n, device=padded.device)[None, :] < lens[:, None]
+    offsets = torch.zeros((b + 1,), dtype=torch.int32, device=padded.device)
+    offsets[1:] = torch.cumsum(lens, 0).to(torch.int32)
+    return padded[keep].contiguous(), offsets
+
+
+def unpack_batch(flat, offsets, n=None, fill=0.0):
+    """The inverse: flat (total, c) with offsets (b + 1,) -> (padded (b, n, c) with `fill` in the padding rows, lengths (b,)
+    int32). n: the padded size, None = the longest cloud. Plain torch; synchronises."""
+    require(isinstance(flat, torch.Tensor) and flat.dim() == 2, "unpack_batch expects a (total, c) tensor")
+    offs = check_offsets(offsets, flat.shape[0]).to(device=flat.device, dtype=torch.int64)
+    lens = offs[1:] - offs[:-1]
+    longest = int(lens.max())
+    n = longest if n is None else int(n)
+    require(n >= longest, "n = %d is below the longest cloud (%d points)" % (n, longest))
+    b = lens.shape[0]
+    padded = torch.full((b, n, flat.shape[1]), fill, dtype=flat.dtype, device=flat.device)
+    keep = torch.arange(n, device=flat.device)[None, :] < lens[:, None]
+    padded[keep] = flat
+    return padded, lens.to(torch.int32)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 

@@ -45,12 +45,15 @@ namespace pn2 {
 // Two (pn2_query_ball_group_xyz_ragged_pair): cloud c also holds only m_c = lengths2[c] valid queries. The workgroup sweeps
 // [q0, min(q0 + qpb, m_c)) -- the body never reads a query row at or beyond its q1 --, fills its rows from m_c on (bq_fill_rows)
 // and, when it holds nothing else, leaves before the staging (block-uniform).
+// Packed (pn2_query_ball_group_xyz_packed; pn2_device.h: Packed): the one-array mode with the cloud's slab taken from the
+// offsets -- xyz1 is the flat (total, 3) array, n is nmax, the queries and the outputs stay dense (b, m, ...). With global_idx
+// the stored indices are rows of the flat array; the grouped rows are gathered with the local index as before.
 template <bool LDS_CLOUD, bool FUSE, class... Cnt>
 __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(int n, int m, int nsample, float thr, int qpb,
                                                                 const float *__restrict__ xyz1,
                                                                 const float *__restrict__ xyz2, int *__restrict__ idx,
                                                                 int *__restrict__ pts_cnt,
-                                                                float *__restrict__ grouped, int subtract, Cnt __restrict__... cnt)
+                                                                float *__restrict__ grouped, int subtract, CountArg<Cnt>... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Counts<Cnt...> counts(cnt...);
@@ -58,6 +61,16 @@ __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(int n, int m, in
         const int q0 = blockIdx.x * qpb;
         bq_block_body<LDS_CLOUD, FUSE, false>(n, m, nsample, thr, blockIdx.y, q0, min(q0 + qpb, m), xyz1, xyz2, nullptr,
                                               nullptr, idx, pts_cnt, grouped, subtract, smem);
+    } else if constexpr (Counts<Cnt...>::packed) {
+        const int c = blockIdx.y;
+        const int start = cloud_start(counts.pk, c);
+        const int nc = cloud_count(counts.pk, c, start, n);
+        const int q0 = blockIdx.x * qpb;
+        const size_t rows = (size_t)c * m;
+        bq_block_body<LDS_CLOUD, FUSE, false>(nc, m, nsample, thr, 0, q0, min(q0 + qpb, m), xyz1 + (size_t)start * 3, xyz2 + rows * 3,
+                                              nullptr, nullptr, idx ? idx + rows * nsample : nullptr, pts_cnt ? pts_cnt + rows : nullptr,
+                                              grouped ? grouped + rows * nsample * 3 : nullptr, subtract, smem, 1u, 0, nullptr,
+                                              counts.pk.global_idx ? start : 0);
     } else {
         const int c = blockIdx.y;
         const int nc = cloud_count(counts.side[0], c, n);
@@ -79,7 +92,7 @@ __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(int n, int m, in
 
 template <bool LDS_CLOUD, bool FUSE>
 static int launch_bq(int b, int n, int m, float thr, int nsample, const float *xyz1, const int *lengths, const float *xyz2, int *idx,
-                     int *pts_cnt, float *grouped, int subtract, hipStream_t st, const int *lengths2 = nullptr)
+                     int *pts_cnt, float *grouped, int subtract, hipStream_t st, const int *lengths2 = nullptr, const Packed *pk = nullptr)
 {
     // aim at ~2 workgroups per CU over the whole launch; each stages the cloud once
     constexpr int kGran = kBqWaves * kBqQpw;
@@ -91,6 +104,10 @@ static int launch_bq(int b, int n, int m, float thr, int nsample, const float *x
     const int gx = (m + qpb - 1) / qpb;
     const size_t lds = (LDS_CLOUD ? sizeof(float4) * (size_t)((n + 127) & ~127) : 0) + sizeof(int) * (size_t)nsample * kGran;
     if (lds > 160 * 1024) return PN2_E_TOO_LARGE;
+    if (pk)
+        return launch_counts_packed<false>([](auto... c) { return ball_query_kernel<LDS_CLOUD, FUSE, decltype(c)...>; }, *pk, nullptr,
+                                           dim3(gx, b), dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, xyz2, idx, pts_cnt, grouped,
+                                           subtract);
     return launch_counts([](auto... c) { return ball_query_kernel<LDS_CLOUD, FUSE, decltype(c)...>; }, lengths, lengths2, dim3(gx, b),
                          dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, xyz2, idx, pts_cnt, grouped, subtract);
 }
@@ -108,7 +125,7 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_kernel(int b, i
                                                                       const float *__restrict__ xyz2,
                                                                       int *__restrict__ idx,
                                                                       int *__restrict__ pts_cnt,
-                                                                      float *__restrict__ grouped, int subtract, Cnt __restrict__... cnt)
+                                                                      float *__restrict__ grouped, int subtract, CountArg<Cnt>... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Counts<Cnt...> counts(cnt...);
@@ -118,6 +135,23 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_kernel(int b, i
         const int q0 = part * qpb;
         bq_cells_block_body<NT, LPQ, FUSE, false, true>(n, m, nsample, thr, radius, cloud, q0, min(q0 + qpb, m), xyz1, xyz2,   // BLK: crowded balls walk the first half of the indices first (ball_query_body.h)
                                          nullptr, nullptr, idx, pts_cnt, grouped, subtract, smem);
+    } else if constexpr (Counts<Cnt...>::packed) {          // as in ball_query_kernel; a cloud below 64 points as in the count modes
+        const int start = cloud_start(counts.pk, cloud);
+        const int nc = cloud_count(counts.pk, cloud, start, n);
+        const int ibase = counts.pk.global_idx ? start : 0;
+        const int q0 = part * qpb, q1 = min(q0 + qpb, m);
+        const size_t rows = (size_t)cloud * m;
+        const float *__restrict__ x1 = xyz1 + (size_t)start * 3;
+        const float *__restrict__ x2 = xyz2 + rows * 3;
+        int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
+        int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
+        float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
+        if (nc < 64)
+            bq_block_body<true, FUSE, false, NT>(nc, m, nsample, thr, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og, subtract, smem, 1u, 0,
+                                                 nullptr, ibase);
+        else
+            bq_cells_block_body<NT, LPQ, FUSE, false, true>(nc, m, nsample, thr, radius, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og,
+                                                            subtract, smem, 1u, nullptr, 0, ibase);
     } else {
         const int nc = cloud_count(counts.side[0], cloud, n);
         int mc = m;
@@ -181,7 +215,7 @@ static bool bq_use_cells(int b, int n, int m, int kernel)
 template <int NT, int LPQ, bool FUSE>
 static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsample, const float *xyz1, const int *lengths,
                            const float *xyz2, int *idx, int *pts_cnt, float *grouped, int subtract, int opt_qpb,
-                           hipStream_t st, const int *lengths2 = nullptr)
+                           hipStream_t st, const int *lengths2 = nullptr, const Packed *pk = nullptr)
 {
     constexpr int kGran = (NT / 64) * (64 / LPQ);               // queries per workgroup trip
     long long total = (long long)b * m;
@@ -192,6 +226,10 @@ static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsa
     const int gx = (m + qpb - 1) / qpb;
     const size_t a = bq_cells_lds_bytes(n, nsample, LPQ, NT), s = bq_sweep_lds_bytes(n, nsample, NT);
     const size_t lds = a > s ? a : s;                       // the fallback inside the kernel uses the sweep layout
+    if (pk)
+        return launch_counts_packed<false>([](auto... c) { return ball_query_cells_kernel<NT, LPQ, FUSE, decltype(c)...>; }, *pk, nullptr,
+                                           dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx, xyz1, xyz2, idx,
+                                           pts_cnt, grouped, subtract);
     return launch_counts([](auto... c) { return ball_query_cells_kernel<NT, LPQ, FUSE, decltype(c)...>; }, lengths, lengths2,
                          dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx, xyz1, xyz2, idx, pts_cnt,
                          grouped, subtract);
@@ -200,11 +238,11 @@ static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsa
 template <bool FUSE>
 static int dispatch_bq_cells(BqCellsGeom g, int b, int n, int m, float thr, float radius, int nsample,
                              const float *xyz1, const int *lengths, const float *xyz2, int *idx, int *pts_cnt, float *grouped,
-                             int subtract, int qpb, hipStream_t st, const int *lengths2 = nullptr)
+                             int subtract, int qpb, hipStream_t st, const int *lengths2 = nullptr, const Packed *pk = nullptr)
 {
 #define PN2_BQ_CASE(NT, LPQ) \
     if (g.nthreads == NT && g.lpq == LPQ) \
-        return launch_bq_cells<NT, LPQ, FUSE>(b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, qpb, st, lengths2)
+        return launch_bq_cells<NT, LPQ, FUSE>(b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, qpb, st, lengths2, pk)
     PN2_BQ_CASE(1024, 8);
     PN2_BQ_CASE(1024, 16);
     PN2_BQ_CASE(512, 8);
@@ -215,10 +253,10 @@ static int dispatch_bq_cells(BqCellsGeom g, int b, int n, int m, float thr, floa
 }
 
 // lengths: NULL = every cloud holds n points; else the points per cloud. lengths2 (with lengths only): the valid queries per
-// cloud (the count modes of the two kernels)
+// cloud (the count modes of the two kernels). pk: the packed mode -- n is nmax, xyz1 holds pk->total rows.
 static int ball_query_common(int b, int n, int m, float radius, int nsample, const float *xyz1, const float *xyz2,
                              int subtract, int *idx, int *pts_cnt, float *grouped, bool fuse, BqOpts opt, void *stream,
-                             const int *lengths = nullptr, const int *lengths2 = nullptr)
+                             const int *lengths = nullptr, const int *lengths2 = nullptr, const Packed *pk = nullptr)
 {
     if (opt.kernel < 0 || opt.kernel > 3 || opt.qpb < 0) return PN2_E_ARG;
     if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;   // tf_grouping.cpp:71,74
@@ -226,7 +264,7 @@ static int ball_query_common(int b, int n, int m, float radius, int nsample, con
     if (b == 0 || m == 0) return PN2_OK;
     if (!xyz1 || !xyz2) return PN2_E_NULL;
     if (fuse ? !grouped : !idx) return PN2_E_NULL;
-    if ((long long)b * n * 3 > INT_MAX || (long long)b * m * nsample * 3 > (1ll << 40)) return PN2_E_TOO_LARGE;
+    if ((pk ? (long long)pk->total : (long long)b * n) * 3 > INT_MAX || (long long)b * m * nsample * 3 > (1ll << 40)) return PN2_E_TOO_LARGE;
     if (b > 65535) return PN2_E_TOO_LARGE;
     const float thr = pn2_ball_threshold(radius);
     hipStream_t st = as_stream(stream);
@@ -234,13 +272,13 @@ static int ball_query_common(int b, int n, int m, float radius, int nsample, con
                      sizeof(float4) * (size_t)((n + 127) & ~127) + sizeof(int) * (size_t)nsample * kBqWaves * kBqQpw <= 160 * 1024;
     BqCellsGeom geom;
     if (bq_use_cells(b, n, m, opt.kernel) && bq_cells_pick(n, nsample, opt.kernel, geom))
-        return fuse ? dispatch_bq_cells<true>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, opt.qpb, st, lengths2)
-                    : dispatch_bq_cells<false>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, opt.qpb, st, lengths2);
+        return fuse ? dispatch_bq_cells<true>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, opt.qpb, st, lengths2, pk)
+                    : dispatch_bq_cells<false>(geom, b, n, m, thr, radius, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, opt.qpb, st, lengths2, pk);
     if (fuse)
-        return lds ? launch_bq<true, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st, lengths2)
-                   : launch_bq<false, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st, lengths2);
-    return lds ? launch_bq<true, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st, lengths2)
-               : launch_bq<false, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st, lengths2);
+        return lds ? launch_bq<true, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st, lengths2, pk)
+                   : launch_bq<false, true>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, grouped, subtract, st, lengths2, pk);
+    return lds ? launch_bq<true, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st, lengths2, pk)
+               : launch_bq<false, false>(b, n, m, thr, nsample, xyz1, lengths, xyz2, idx, pts_cnt, nullptr, 0, st, lengths2, pk);
 }
 
 }  // namespace pn2
@@ -328,4 +366,24 @@ extern "C" int pn2_query_ball_group_xyz_ragged_pair(int b, int n, int m, float r
 {
     return ball_query_ragged(2, b, n, m, radius, nsample, xyz1, lengths1, xyz2, lengths2, subtract_centroid, idx, pts_cnt, grouped_xyz,
                              kernel, cells_qpb, stream);
+}
+
+// Packed batch: cloud c of xyz1 is xyz1[offsets1[c] : offsets1[c + 1]] of a flat (total, 3) array, offsets1 (b + 1) int32 on the
+// device, never read by the host; nmax bounds every cloud's count and takes the padded n's place in the kernel choice, the grid
+// and the LDS size. The queries xyz2 (b, m, 3) and the outputs are dense. Result per cloud = pn2_query_ball_group_xyz_ex on the
+// slice for every `kernel`; global_idx 1 writes idx as offsets1[c] + k. grouped_xyz == NULL: plain query_ball_point. Codes in
+// the order of pn2_query_ball_group_xyz_ragged (PN2_E_TOO_LARGE for total 3 > INT_MAX).
+extern "C" int pn2_query_ball_group_xyz_packed(int b, int total, int nmax, int m, float radius, int nsample, const float *xyz1,
+                                               const int *offsets1, const float *xyz2, int subtract_centroid, int global_idx, int *idx,
+                                               int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb, void *stream)
+{
+    if (kernel < 0 || kernel > 3 || cells_qpb < 0) return PN2_E_ARG;
+    if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;
+    if (b < 0 || nmax <= 0 || m < 0) return PN2_E_SHAPE;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (total <= 0) return PN2_E_SHAPE;
+    if (!offsets1) return PN2_E_NULL;
+    const pn2::Packed pk = {offsets1, total, global_idx ? 1 : 0};
+    return pn2::ball_query_common(b, nmax, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt, grouped_xyz,
+                                  grouped_xyz != nullptr, {kernel, cells_qpb}, stream, nullptr, nullptr, &pk);
 }

@@ -82,12 +82,12 @@ template <bool LDS_CLOUD, bool FUSE>
 __device__ __forceinline__ void bq_emit(size_t row, int nsample, int cnt, const int *rowbuf,
                                         const float4 *cloud, const float *__restrict__ data, float qx, float qy,
                                         float qz, int *__restrict__ idx, int *__restrict__ pts_cnt,
-                                        float *__restrict__ grouped, int subtract, int lane)
+                                        float *__restrict__ grouped, int subtract, int lane, int ibase = 0)
 {
     const int first = cnt > 0 ? rowbuf[0] : 0;   // the first hit pads the row; zeros when the ball is empty
     for (int l = lane; l < nsample; l += 64) {
         const int v = (l < cnt) ? rowbuf[l] : first;
-        if (idx) idx[row * nsample + l] = v;
+        if (idx) idx[row * nsample + l] = v + ibase;
         if (FUSE && grouped) {
             float gx, gy, gz;
             if (LDS_CLOUD) {
@@ -153,6 +153,8 @@ __device__ __forceinline__ void bq_fill_rows(int r0, int r1, int nsample, int *_
 // STAGED: the LDS copy of the cloud already exists (multi-radius kernel: staged once, swept per radius);
 // row_stride: ints between two row buffers (0 = nsample; the multi-radius kernel passes its largest nsample
 // so that waves working on different radii never share a buffer).
+// ibase: added to every index where it is stored (wave-uniform; the packed mode's global_idx, pn2_device.h) -- the grouped rows
+// are gathered with the cloud-local index. The literal 0 of every other caller folds away.
 template <bool LDS_CLOUD, bool FUSE, bool POLL, int NT = kBqThreads, bool STAGED = false>
 __device__ __forceinline__ bool bq_block_body(int n, int m, int nsample, float thr, int bi, int q0, int q1,
                                               const float *__restrict__ xyz1, const float *__restrict__ xyz2,
@@ -160,7 +162,7 @@ __device__ __forceinline__ bool bq_block_body(int n, int m, int nsample, float t
                                               float *__restrict__ new_xyz, int *__restrict__ idx,
                                               int *__restrict__ pts_cnt, float *__restrict__ grouped, int subtract,
                                               char *smem, unsigned tag = 1u, int row_stride = 0,
-                                              unsigned *status = nullptr)
+                                              unsigned *status = nullptr, int ibase = 0)
 {
     if (row_stride == 0) row_stride = nsample;
     float4 *cloud = reinterpret_cast<float4 *>(smem);                                   // [n] when LDS_CLOUD
@@ -258,10 +260,10 @@ __device__ __forceinline__ bool bq_block_body(int n, int m, int nsample, float t
         // LDS ops of one wave execute in order; only the compiler must not reorder
         asm volatile("" ::: "memory");
         bq_emit<LDS_CLOUD, FUSE>(row0, nsample, cnt0, rowbuf0, cloud, data, ax, ay, az, idx, pts_cnt, grouped,
-                                 subtract, lane);
+                                 subtract, lane, ibase);
         if (two)
             bq_emit<LDS_CLOUD, FUSE>(row1, nsample, cnt1, rowbuf1, cloud, data, bx, by, bz, idx, pts_cnt,
-                                     grouped, subtract, lane);
+                                     grouped, subtract, lane, ibase);
         asm volatile("" ::: "memory");
     }
     return true;
@@ -592,7 +594,8 @@ __device__ __forceinline__ bool bq_cells_query_loop(int n, int m, int nsample, f
                                                     int *__restrict__ pts_cnt, float *__restrict__ grouped,
                                                     int subtract, const float4 *sorted, const int *tab,
                                                     char *wave_area, size_t wave_stride = 0, unsigned tag = 1u,
-                                                    unsigned *status = nullptr, const unsigned short *pos_tab = nullptr)
+                                                    unsigned *status = nullptr, const unsigned short *pos_tab = nullptr,
+                                                    int ibase = 0)
 {
     constexpr int G = 64 / LPQ;
     constexpr int CW = 64 / LPQ;                                 // 64-bit bitmap words per lane and window
@@ -790,7 +793,7 @@ __device__ __forceinline__ bool bq_cells_query_loop(int n, int m, int nsample, f
                 const float4 hd = qhdr[gq];
                 const int c = __float_as_int(hd.w);
                 const int v = (l < c) ? rowflat[e] : (c > 0 ? rowflat[gq << lg] : 0);   // pad with the first hit; zeros when empty
-                if (idx) idx[row0 * nsample + e] = v;
+                if (idx) idx[row0 * nsample + e] = v + ibase;
                 if (FUSE && grouped) {
                     float gx = data[(size_t)v * 3 + 0], gy = data[(size_t)v * 3 + 1], gz = data[(size_t)v * 3 + 2];
                     if (subtract) { gx = __fsub_rn(gx, hd.x); gy = __fsub_rn(gy, hd.y); gz = __fsub_rn(gz, hd.z); }
@@ -803,7 +806,7 @@ __device__ __forceinline__ bool bq_cells_query_loop(int n, int m, int nsample, f
             const int first = cnt > 0 ? rowbuf[0] : 0;           // the first hit pads the row; zeros when empty
             for (int l = sub; l < nsample; l += LPQ) {
                 const int v = (l < cnt) ? rowbuf[l] : first;
-                if (idx) idx[row * nsample + l] = v;
+                if (idx) idx[row * nsample + l] = v + ibase;
                 if (FUSE && grouped) {
                     float gx = data[(size_t)v * 3 + 0], gy = data[(size_t)v * 3 + 1], gz = data[(size_t)v * 3 + 2];
                     if (subtract) { gx = __fsub_rn(gx, qx); gy = __fsub_rn(gy, qy); gz = __fsub_rn(gz, qz); }
@@ -832,7 +835,7 @@ __device__ __forceinline__ void bq_cells_block_body(int n, int m, int nsample, f
                                                     float *__restrict__ new_xyz, int *__restrict__ idx,
                                                     int *__restrict__ pts_cnt, float *__restrict__ grouped,
                                                     int subtract, char *smem, unsigned tag = 1u,
-                                                    unsigned *status = nullptr, int q_stride = 0)
+                                                    unsigned *status = nullptr, int q_stride = 0, int ibase = 0)
 {
     float4 *sorted = reinterpret_cast<float4 *>(smem);
     int *tab = reinterpret_cast<int *>(smem + sizeof(float4) * (size_t)n);
@@ -849,17 +852,17 @@ __device__ __forceinline__ void bq_cells_block_body(int n, int m, int nsample, f
         for (int a = q0; a < m; a += q_stride) {
             if (!bq_cells_query_loop<NT, LPQ, FUSE, POLL, BLK>(n, m, nsample, thr, radius, reach, bi, a, min(a + qlen, m), g, data, xyz2, tagged,
                                                        new_xyz, idx, pts_cnt, grouped, subtract, sorted, tab, wave_area, 0, tag,
-                                                       status, pos_tab)) return;
+                                                       status, pos_tab, ibase)) return;
             if (q_stride <= 0) break;
         }
     } else {
         __syncthreads();                                         // scratch was read by everyone before it is reused
         if (!bq_block_body<true, FUSE, POLL, NT>(n, m, nsample, thr, bi, q0, q1, xyz1, xyz2, tagged, new_xyz, idx, pts_cnt,
-                                                 grouped, subtract, smem, tag, 0, status)) return;
+                                                 grouped, subtract, smem, tag, 0, status, ibase)) return;
         if (q_stride > 0)
             for (int a = q0 + q_stride; a < m; a += q_stride)   // the LDS copy of the cloud stays
                 if (!bq_block_body<true, FUSE, POLL, NT, true>(n, m, nsample, thr, bi, a, min(a + qlen, m), xyz1, xyz2, tagged, new_xyz,
-                                                               idx, pts_cnt, grouped, subtract, smem, tag, 0, status)) return;
+                                                               idx, pts_cnt, grouped, subtract, smem, tag, 0, status, ibase)) return;
     }
 }
 

@@ -51,6 +51,39 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(int n, int m, int Q, const f
     fps_reg_body<T, P, LDSXYZ, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
 }
 
+// Where cloud c of a ragged launch lies and how many points it holds. No Pk: the padded layout, row c n and lengths[c]. A Packed
+// behind the kernel's argument list (pn2_farthest_point_sample_packed; pn2_device.h): rows offsets[c] .. offsets[c + 1] - 1 of
+// the flat array, n = nmax, lengths unused. The body is handed the slab as cloud 0 either way, so the slice rule below holds
+// for both layouts; coordinates are read as scalars, so a slab may start at any row. base: what fps_global_rows adds.
+template <class... Pk>
+struct FpsSlab {
+    size_t row;
+    int count, base;
+    __device__ __forceinline__ FpsSlab(int c, int n, const int *__restrict__ lengths) : row((size_t)c * n), count(cloud_count(lengths, c, n)), base(0) {}
+};
+template <>
+struct FpsSlab<Packed> {
+    size_t row;
+    int count, base;
+    __device__ __forceinline__ FpsSlab(int c, int n, const int *, Packed pk)
+    {
+        const int s = cloud_start(pk, c);
+        row = (size_t)s;
+        count = cloud_count(pk, c, s, n);
+        base = pk.global_idx ? s : 0;
+    }
+};
+
+// global_idx of the packed mode: the chain and its gather epilogue work on cloud-local indices (the epilogue reads them back);
+// the workgroup-uniform base is added to the finished rows behind them, off the chain. Block-uniform branch.
+template <int T>
+__device__ __forceinline__ void fps_global_rows(int m, int base, int *dst)
+{
+    if (base == 0) return;
+    __syncthreads();                                      // the index stores (and the epilogue's reads of them) are done
+    for (int j = threadIdx.x; j < m; j += T) dst[j] += base;
+}
+
 // Ragged batch (pn2_farthest_point_sample_ragged): cloud c holds lengths[c] <= n points in its padded (n, 3) slab. The
 // workgroup hands the body its own slab as cloud 0 with n = n_c and Q = ceil(n_c / 512): the tie ranks, the dealing and the
 // padding slots are then exactly those of the dense kernel on the slice, and rows at or beyond n_c are never addressed
@@ -62,20 +95,22 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(int n, int m, int Q, const f
 // rule (tf_sampling_g.cu:114-116), so the fill is index 0 and xyz[c, 0] and reads nothing back. The fill rows are disjoint from
 // the body's, so no barrier stands between the two. (The fill is a function of its own, fps_ragged_fill in fps_body.h: the
 // wrappers of the other tiers end with it too.) Without COUNTS npoints is never read.
-template <int T, int P, bool LDSXYZ, bool COUNTS>
+template <int T, int P, bool LDSXYZ, bool COUNTS, class... Pk>
 __global__ __launch_bounds__(T) void fps_reg_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
                                                            const int *__restrict__ npoints, int *__restrict__ out,
-                                                           float *__restrict__ out_xyz)
+                                                           float *__restrict__ out_xyz, Pk... pk)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int c = blockIdx.x;
-    const int nc = cloud_count(lengths, c, n);
+    const FpsSlab<Pk...> slab(c, n, lengths, pk...);
+    const int nc = slab.count;
     const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
     const int Qc = (nc + kRefThreads - 1) / kRefThreads;
-    const float *__restrict__ src = xyz + (size_t)c * n * 3;
+    const float *__restrict__ src = xyz + slab.row * 3;
     int *__restrict__ dst = out + (size_t)c * m;
     float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
     fps_reg_body<T, P, LDSXYZ, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
+    if constexpr (sizeof...(Pk) != 0) fps_global_rows<T>(mc, slab.base, dst);
     if (COUNTS) fps_ragged_fill<T>(mc, m, src, dst, dxyz);
 }
 
@@ -111,37 +146,41 @@ __global__ __launch_bounds__(kBtT) void fps_batch_kernel(int n, int m, int Q, co
 // model). n_c, m_c and Q_c are block-uniform scalars, so every wave of the workgroup -- the picker included -- executes the
 // barriers of the same chain. COUNTS: npoints is read and rows m_c .. m-1 are filled as in fps_reg_ragged_kernel (index 0
 // and xyz[c, 0]; disjoint from the body's rows, so no barrier stands in between).
-template <int P, int GS, bool COUNTS>
+template <int P, int GS, bool COUNTS, class... Pk>
 __global__ __launch_bounds__(kPrT) void fps_pruned_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
                                                                  const int *__restrict__ npoints, int *__restrict__ out,
-                                                                 float *__restrict__ out_xyz)
+                                                                 float *__restrict__ out_xyz, Pk... pk)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int c = blockIdx.x;
-    const int nc = cloud_count(lengths, c, n);
+    const FpsSlab<Pk...> slab(c, n, lengths, pk...);
+    const int nc = slab.count;
     const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
     const int Qc = (nc + kRefThreads - 1) / kRefThreads;
-    const float *__restrict__ src = xyz + (size_t)c * n * 3;
+    const float *__restrict__ src = xyz + slab.row * 3;
     int *__restrict__ dst = out + (size_t)c * m;
     float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
     fps_pruned_body<P, GS, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
+    if constexpr (sizeof...(Pk) != 0) fps_global_rows<kPrT>(mc, slab.base, dst);
     if (COUNTS) fps_ragged_fill<kPrT>(mc, m, src, dst, dxyz);
 }
 
-template <int P, int GS, bool COUNTS>
+template <int P, int GS, bool COUNTS, class... Pk>
 __global__ __launch_bounds__(kBtT) void fps_batch_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
                                                                 const int *__restrict__ npoints, int *__restrict__ out,
-                                                                float *__restrict__ out_xyz)
+                                                                float *__restrict__ out_xyz, Pk... pk)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int c = blockIdx.x;
-    const int nc = cloud_count(lengths, c, n);
+    const FpsSlab<Pk...> slab(c, n, lengths, pk...);
+    const int nc = slab.count;
     const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
     const int Qc = (nc + kRefThreads - 1) / kRefThreads;
-    const float *__restrict__ src = xyz + (size_t)c * n * 3;
+    const float *__restrict__ src = xyz + slab.row * 3;
     int *__restrict__ dst = out + (size_t)c * m;
     float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
     fps_batch_body<P, GS, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
+    if constexpr (sizeof...(Pk) != 0) fps_global_rows<kBtT>(mc, slab.base, dst);
     if (COUNTS) fps_ragged_fill<kBtT>(mc, m, src, dst, dxyz);
 }
 
@@ -410,9 +449,12 @@ static int launch_reg(int b, int n, int m, int Q, const float *inp, int *out, fl
 // npoints: NULL = m samples from every cloud; else the per-cloud sample counts (COUNTS)
 template <int T, int P, bool LDSXYZ>
 static int launch_reg_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                             hipStream_t st)
+                             hipStream_t st, const Packed *pk = nullptr)
 {
     const size_t lds = 256 + (LDSXYZ ? sizeof(float4) : sizeof(int)) * (size_t)T * P;
+    if (pk)                                                // the packed mode: lengths and npoints are NULL and never read
+        return launch_lds(fps_reg_ragged_kernel<T, P, LDSXYZ, false, Packed>, dim3(b), dim3(T), lds, st, n, m, inp, lengths, npoints, out,
+                          oxyz, *pk);
     return launch_lds(npoints ? fps_reg_ragged_kernel<T, P, LDSXYZ, true> : fps_reg_ragged_kernel<T, P, LDSXYZ, false>, dim3(b), dim3(T),
                       lds, st, n, m, inp, lengths, npoints, out, oxyz);
 }
@@ -476,43 +518,49 @@ static int fps_launch_batch(int b, int n, int m, const float *inp, int *out, flo
 // fps_launch_batch choose them. npoints: NULL = m samples from every cloud.
 template <int P, int GS>
 static int launch_pruned_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                                hipStream_t st)
+                                hipStream_t st, const Packed *pk = nullptr)
 {
+    if (pk)
+        return launch_lds(fps_pruned_ragged_kernel<P, GS, false, Packed>, dim3(b), dim3(kPrT), fps_pruned_lds_bytes(P), st, n, m, inp,
+                          lengths, npoints, out, oxyz, *pk);
     return launch_lds(npoints ? fps_pruned_ragged_kernel<P, GS, true> : fps_pruned_ragged_kernel<P, GS, false>, dim3(b), dim3(kPrT),
                       fps_pruned_lds_bytes(P), st, n, m, inp, lengths, npoints, out, oxyz);
 }
 
 static int fps_launch_pruned_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                                    hipStream_t st)
+                                    hipStream_t st, const Packed *pk = nullptr)
 {
     const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
     if (!pruned_covers(ranks)) return PN2_E_ARG;
-    if (ranks <= 4096) return launch_pruned_ragged<16, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st);
-    return launch_pruned_ragged<32, 4>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+    if (ranks <= 4096) return launch_pruned_ragged<16, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
+    return launch_pruned_ragged<32, 4>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
 }
 
 template <int P, int GS>
 static int launch_batch_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                               hipStream_t st)
+                               hipStream_t st, const Packed *pk = nullptr)
 {
+    if (pk)
+        return launch_lds(fps_batch_ragged_kernel<P, GS, false, Packed>, dim3(b), dim3(kBtT), fps_batch_lds_bytes(P), st, n, m, inp, lengths,
+                          npoints, out, oxyz, *pk);
     return launch_lds(npoints ? fps_batch_ragged_kernel<P, GS, true> : fps_batch_ragged_kernel<P, GS, false>, dim3(b), dim3(kBtT),
                       fps_batch_lds_bytes(P), st, n, m, inp, lengths, npoints, out, oxyz);
 }
 
 static int fps_launch_batch_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                                   hipStream_t st)
+                                   hipStream_t st, const Packed *pk = nullptr)
 {
     const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
     if (!fps_batch_covers(ranks)) return PN2_E_ARG;
     if constexpr (kBtUT == 512) {
-        if (ranks <= 1024) return launch_batch_ragged<2, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st);
-        if (ranks <= 2048) return launch_batch_ragged<4, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+        if (ranks <= 1024) return launch_batch_ragged<2, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
+        if (ranks <= 2048) return launch_batch_ragged<4, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
     } else if (ranks <= 2048) {
         return PN2_E_ARG;
     }
     if (ranks <= 4096)
-        return launch_batch_ragged<4096 / kBtUT, 4096 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, inp, lengths, npoints, out, oxyz, st);
-    return launch_batch_ragged<8192 / kBtUT, 8192 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, inp, lengths, npoints, out, oxyz, st);
+        return launch_batch_ragged<4096 / kBtUT, 4096 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
+    return launch_batch_ragged<8192 / kBtUT, 8192 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
 }
 
 constexpr int kMaxLdsSlots = 8192;     // 256 B + 16 B per rank slot <= 160 KiB
@@ -622,25 +670,26 @@ extern "C" int pn2_farthest_point_sample_variant(int variant, int b, int n, int 
 // chosen as fps_entry chooses it, by the size rule on the PADDED n and m (the host knows no other): the batched tier, the pruned
 // tier, else -- and for PN2_FPS_FULL -- the register tier in the geometry fps_entry picks at the padded n. PN2_E_TOO_LARGE
 // beyond 16384 points. out_xyz may be NULL.
+// pk: the packed mode (pn2_farthest_point_sample_packed): n is nmax, the flat array's extent is pk->total, lengths / npoints NULL.
 static int fps_ragged_entry(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, bool counts, int *out,
-                            float *out_xyz, void *stream, int variant = PN2_FPS_AUTO)
+                            float *out_xyz, void *stream, int variant = PN2_FPS_AUTO, const pn2::Packed *pk = nullptr)
 {
     using namespace pn2;
     if (m <= 0 || b == 0) return PN2_OK;
-    if (b < 0 || n <= 0) return PN2_E_SHAPE;
-    if (!inp || !out || !lengths || (counts && !npoints)) return PN2_E_NULL;
+    if (b < 0 || n <= 0 || (pk && pk->total <= 0)) return PN2_E_SHAPE;
+    if (!inp || !out || !(pk ? pk->offsets : lengths) || (counts && !npoints)) return PN2_E_NULL;
     if (n > kMaxRegPoints) return PN2_E_TOO_LARGE;
-    if ((long long)b * n * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
+    if ((pk ? (long long)pk->total : (long long)b * n) * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
     hipStream_t st = as_stream(stream);
     const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
     if (variant == PN2_FPS_BATCH || (variant == PN2_FPS_AUTO && fps_batch_pays(ranks, m)))
-        return fps_launch_batch_ragged(b, n, m, inp, lengths, npoints, out, out_xyz, st);
+        return fps_launch_batch_ragged(b, n, m, inp, lengths, npoints, out, out_xyz, st, pk);
     if (variant == PN2_FPS_PRUNED || (variant == PN2_FPS_AUTO && fps_pruned_pays(ranks, m)))
-        return fps_launch_pruned_ragged(b, n, m, inp, lengths, npoints, out, out_xyz, st);
+        return fps_launch_pruned_ragged(b, n, m, inp, lengths, npoints, out, out_xyz, st, pk);
     const int T = ranks <= 2048 ? 256 : 512;
     const int P = next_pow2((ranks + T - 1) / T);
 #define PN2_FPS_RAGGED(TT, PP) \
-    if (T == TT && P == PP) return launch_reg_ragged<TT, PP, ((long long)TT * PP <= kMaxLdsSlots)>(b, n, m, inp, lengths, npoints, out, out_xyz, st)
+    if (T == TT && P == PP) return launch_reg_ragged<TT, PP, ((long long)TT * PP <= kMaxLdsSlots)>(b, n, m, inp, lengths, npoints, out, out_xyz, st, pk)
     PN2_FPS_RAGGED(256, 2);
     PN2_FPS_RAGGED(256, 4);
     PN2_FPS_RAGGED(256, 8);
@@ -674,6 +723,19 @@ extern "C" int pn2_farthest_point_sample_ragged_variant(int variant, int b, int 
 {
     if (variant < PN2_FPS_AUTO || variant > PN2_FPS_BATCH) return PN2_E_ARG;
     return fps_ragged_entry(b, n, m, inp, lengths, npoints, false, out, out_xyz, stream, variant);
+}
+
+// Packed batch: cloud c is inp[offsets[c] : offsets[c + 1]] of a flat (total, 3) array, offsets (b + 1) int32 on the device, never
+// read by the host; nmax bounds every cloud's count and takes the padded n's place in the tier rule, the template and the LDS
+// size. Result per cloud = pn2_farthest_point_sample_gather on the slice, whatever the tier; global_idx 1 adds offsets[c] to the
+// cloud's indices. out (b, m) and out_xyz (b, m, 3, may be NULL) are dense. variant, codes and envelope as
+// pn2_farthest_point_sample_ragged_variant (PN2_E_TOO_LARGE for nmax > 16384 or total 3 > INT_MAX).
+extern "C" int pn2_farthest_point_sample_packed(int variant, int b, int total, int nmax, int m, const float *inp, const int *offsets,
+                                                int global_idx, int *out, float *out_xyz, void *stream)
+{
+    if (variant < PN2_FPS_AUTO || variant > PN2_FPS_BATCH) return PN2_E_ARG;
+    const pn2::Packed pk = {offsets, total, global_idx ? 1 : 0};
+    return fps_ragged_entry(b, nmax, m, inp, nullptr, nullptr, false, out, out_xyz, stream, variant, &pk);
 }
 
 // farthest_point_sample for input the caller BELIEVES to be in farthest-point order already (the previous level's samples:

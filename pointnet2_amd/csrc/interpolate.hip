@@ -79,10 +79,11 @@ __device__ __forceinline__ void nn_zero_row(float *__restrict__ od, int *__restr
 // length -- rows nv .. n-1 are then zero-filled and never read (RAGGED; the dense instantiation has none of it).
 // m: the known points swept; m_stride: rows between two clouds' known points when that is not m (the ragged KNOWN side,
 // three_nn_kernel with two count arrays: m = the cloud's own count) -- a literal 0 everywhere else, which folds away.
+// kbase: added to the three indices where they are stored (the packed mode's global_idx: c m; wave-uniform) -- likewise 0 elsewhere.
 template <bool RAGGED>
 __device__ __forceinline__ void three_nn_sweep_body(int n, int nv, int m, int bi, const float *__restrict__ xyz1,
                                                     const float *__restrict__ xyz2, float *__restrict__ dist,
-                                                    int *__restrict__ idx, float4 *tile, int m_stride = 0)
+                                                    int *__restrict__ idx, float4 *tile, int m_stride = 0, int kbase = 0)
 {
     const int sub = threadIdx.x & 3;                       // lane of the quad
     const int j = blockIdx.x * kNnPoints + (threadIdx.x >> 2);
@@ -134,7 +135,7 @@ __device__ __forceinline__ void three_nn_sweep_body(int n, int nv, int m, int bi
         int *oi = idx + ((size_t)bi * n + j) * 3;
         od[0] = __int_as_float(__double2hiint(b1)); od[1] = __int_as_float(__double2hiint(b2));
         od[2] = __int_as_float(__double2hiint(b3));
-        oi[0] = __double2loint(b1); oi[1] = __double2loint(b2); oi[2] = __double2loint(b3);
+        oi[0] = __double2loint(b1) + kbase; oi[1] = __double2loint(b2) + kbase; oi[2] = __double2loint(b3) + kbase;
     }
     if (RAGGED && !live && j < n && sub == 0) nn_zero_row(dist + ((size_t)bi * n + j) * 3, idx + ((size_t)bi * n + j) * 3);
 }
@@ -143,15 +144,28 @@ __device__ __forceinline__ void three_nn_sweep_body(int n, int nv, int m, int bi
 // lengths[c] <= n unknown points, the known side is dense. Two (pn2_three_nn_ragged_pair): cloud c also holds only lengths2[c]
 // of its m known points; the sweep runs on those alone (rows at or beyond the count are never read), and fewer than three
 // leave the (+inf, 0) entries of the dense operator.
+// Packed (pn2_three_nn_packed; pn2_device.h: Packed, optionally with the known side's counts behind it): the unknown side is the
+// flat (total, 3) array and dist / idx are (total, 3) like it, n is nmax. The workgroup runs the DENSE body on its cloud's slab
+// as cloud 0 with n = n_c -- no row beyond the slab is read or written, there are no padding rows to fill --, and one whose
+// rows all lie beyond n_c leaves at once (block-uniform, before any barrier). global_idx: the known-point indices leave as c m + j.
 template <class... Cnt>
 __global__ __launch_bounds__(kNnThreads) void three_nn_kernel(int n, int m, const float *__restrict__ xyz1,
                                                               const float *__restrict__ xyz2,
-                                                              float *__restrict__ dist, int *__restrict__ idx, Cnt __restrict__... cnt)
+                                                              float *__restrict__ dist, int *__restrict__ idx, CountArg<Cnt>... cnt)
 {
     __shared__ float4 tile[kNnTile];
     const Counts<Cnt...> counts(cnt...);
     if constexpr (sizeof...(Cnt) == 0) {
         three_nn_sweep_body<false>(n, n, m, blockIdx.y, xyz1, xyz2, dist, idx, tile);
+    } else if constexpr (Counts<Cnt...>::packed) {
+        const int c = blockIdx.y;
+        const int start = cloud_start(counts.pk, c);
+        const int nc = cloud_count(counts.pk, c, start, n);
+        if ((int)blockIdx.x * kNnPoints >= nc) return;
+        int mk = m;
+        if constexpr (sizeof...(Cnt) == 2) mk = cloud_count(counts.side[1], c, m);
+        three_nn_sweep_body<false>(nc, nc, mk, 0, xyz1 + (size_t)start * 3, xyz2 + (size_t)c * m * 3, dist + (size_t)start * 3,
+                                   idx + (size_t)start * 3, tile, 0, counts.pk.global_idx ? c * m : 0);
     } else {
         const int nv = cloud_count(counts.side[0], blockIdx.y, n);
         if constexpr (sizeof...(Cnt) == 2)
@@ -202,11 +216,15 @@ __device__ __forceinline__ void nn_merge_dpp(double &b1, double &b2, double &b3)
 // PAIR (with RAGGED): lengths2 = the clouds' numbers of valid KNOWN points. m stays the stride between two clouds and the
 // size the LDS layout is derived from; binning, the sweep and the fail-list sweep run on mk = the cloud's own count, and a
 // cloud below 64 known points takes the cannot-be-binned sweep at once. Without PAIR mk IS m: the same code as before.
-template <int NT, bool RAGGED, bool PAIR = false>
+// PACKED (with RAGGED; pk): the unknown side is the flat array -- the cloud's rows start at offsets[cloud] in xyz1, dist and idx,
+// nv is its own count (n = nmax only sizes the launch), and there are no padding rows: nothing is filled. kbase as in
+// three_nn_sweep_body. Without PACKED pk is never looked at.
+template <int NT, bool RAGGED, bool PAIR = false, bool PACKED = false>
 __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_part, int parts, int b, float factor,
                                                     const float *__restrict__ xyz1, const int *__restrict__ lengths,
                                                     const float *__restrict__ xyz2, float *__restrict__ dist,
-                                                    int *__restrict__ idx, char *smem, const int *__restrict__ lengths2 = nullptr)
+                                                    int *__restrict__ idx, char *smem, const int *__restrict__ lengths2 = nullptr,
+                                                    Packed pk = Packed{nullptr, 0, 0})
 {
     float4 *sorted = reinterpret_cast<float4 *>(smem);                                  // [m] known points in cell order, .w = index
     int *tab = reinterpret_cast<int *>(smem + sizeof(float4) * (size_t)((m + 3) & ~3)); // tab[c] = start of cell c, tab[c + 1] = its end
@@ -214,16 +232,20 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
     int *fail = reinterpret_cast<int *>(reinterpret_cast<char *>(misc) + kBqMiscBytes); // [0] = count, [1 ..] = rows to sweep
     int cloud, part;
     decode_cloud_block(blockIdx.x, parts, b, cloud, part);
-    const int nv = RAGGED ? cloud_count(lengths, cloud, n) : n;
+    const int start = PACKED ? cloud_start(pk, cloud) : 0;
+    const int nv = PACKED ? cloud_count(pk, cloud, start, n) : RAGGED ? cloud_count(lengths, cloud, n) : n;
     const int mk = PAIR ? cloud_count(lengths2, cloud, m) : m;
+    const int kbase = PACKED && pk.global_idx ? cloud * m : 0;
     const int rb = part * rows_per_part, re = min(rb + rows_per_part, nv);
     const float *__restrict__ known = xyz2 + (size_t)cloud * m * 3;
-    const float *__restrict__ unk = xyz1 + (size_t)cloud * n * 3;
-    float *__restrict__ od = dist + (size_t)cloud * n * 3;
-    int *__restrict__ oi = idx + (size_t)cloud * n * 3;
+    const size_t row0 = PACKED ? (size_t)start : (size_t)cloud * n;
+    const float *__restrict__ unk = xyz1 + row0 * 3;
+    float *__restrict__ od = dist + row0 * 3;
+    int *__restrict__ oi = idx + row0 * 3;
     const int t = threadIdx.x, lane = t & 63, sub = t & 3;
     if (RAGGED) {
-        for (int r = max(rb, nv) + t; r < min(rb + rows_per_part, n); r += NT) nn_zero_row(od + (size_t)r * 3, oi + (size_t)r * 3);
+        if (!PACKED)
+            for (int r = max(rb, nv) + t; r < min(rb + rows_per_part, n); r += NT) nn_zero_row(od + (size_t)r * 3, oi + (size_t)r * 3);
         if (rb >= nv) return;                              // block-uniform
     }
     const double empty = __hiloint2double(0x7F800000, 0);  // (+inf : 0) = the reference's (float)1e40, index 0 (:67)
@@ -305,7 +327,7 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
                 if (sure) {
                     od[(size_t)j * 3 + 0] = __int_as_float(__double2hiint(b1)); od[(size_t)j * 3 + 1] = __int_as_float(__double2hiint(b2));
                     od[(size_t)j * 3 + 2] = d3;
-                    oi[(size_t)j * 3 + 0] = __double2loint(b1); oi[(size_t)j * 3 + 1] = __double2loint(b2); oi[(size_t)j * 3 + 2] = __double2loint(b3);
+                    oi[(size_t)j * 3 + 0] = __double2loint(b1) + kbase; oi[(size_t)j * 3 + 1] = __double2loint(b2) + kbase; oi[(size_t)j * 3 + 2] = __double2loint(b3) + kbase;
                 } else {
                     fail[1 + atomicAdd(&fail[0], 1)] = j;
                 }
@@ -335,7 +357,7 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
         if (lane == 63) {
             od[(size_t)j * 3 + 0] = __int_as_float(__double2hiint(b1)); od[(size_t)j * 3 + 1] = __int_as_float(__double2hiint(b2));
             od[(size_t)j * 3 + 2] = __int_as_float(__double2hiint(b3));
-            oi[(size_t)j * 3 + 0] = __double2loint(b1); oi[(size_t)j * 3 + 1] = __double2loint(b2); oi[(size_t)j * 3 + 2] = __double2loint(b3);
+            oi[(size_t)j * 3 + 0] = __double2loint(b1) + kbase; oi[(size_t)j * 3 + 1] = __double2loint(b2) + kbase; oi[(size_t)j * 3 + 2] = __double2loint(b3) + kbase;
         }
     }
 }
@@ -343,12 +365,16 @@ __device__ __forceinline__ void three_nn_cells_body(int n, int m, int rows_per_p
 template <int NT, class... Cnt>
 __global__ __launch_bounds__(NT, NT == 256 ? 2 : 4) void three_nn_cells_kernel(int n, int m, int rows_per_part, int parts, int b, float factor,
                                                             const float *__restrict__ xyz1, const float *__restrict__ xyz2,
-                                                            float *__restrict__ dist, int *__restrict__ idx, Cnt __restrict__... cnt)
+                                                            float *__restrict__ dist, int *__restrict__ idx, CountArg<Cnt>... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Counts<Cnt...> counts(cnt...);
-    three_nn_cells_body<NT, sizeof...(Cnt) != 0, sizeof...(Cnt) == 2>(n, m, rows_per_part, parts, b, factor, xyz1, counts.side[0], xyz2, dist,
-                                                                      idx, smem, counts.side[1]);
+    if constexpr (Counts<Cnt...>::packed)
+        three_nn_cells_body<NT, true, sizeof...(Cnt) == 2, true>(n, m, rows_per_part, parts, b, factor, xyz1, nullptr, xyz2, dist, idx, smem,
+                                                                 counts.side[1], counts.pk);
+    else
+        three_nn_cells_body<NT, sizeof...(Cnt) != 0, sizeof...(Cnt) == 2>(n, m, rows_per_part, parts, b, factor, xyz1, counts.side[0], xyz2, dist,
+                                                                          idx, smem, counts.side[1]);
 }
 
 static size_t three_nn_cells_lds(int m, int rows_per_part)
@@ -630,8 +656,9 @@ extern "C" int pn2_fp_interp_concat_grad_planned(int b, int n, int m, int c2, in
 // fewer than 64 or more than 8192 known points)
 // lengths: NULL = dense; else the valid unknown points per cloud (device memory); lengths2 (with lengths only): the valid known
 // points per cloud (the count modes of the two kernels)
+// pk: the packed mode (pn2_three_nn_packed) -- n is nmax, the bound on a cloud's unknown points that sizes the grids
 static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist, int *idx, int variant, void *stream,
-                          const int *lengths = nullptr, const int *lengths2 = nullptr)
+                          const int *lengths = nullptr, const int *lengths2 = nullptr, const pn2::Packed *pk = nullptr)
 {
     using namespace pn2;
     if (b < 0 || n < 0 || m < 0) return PN2_E_SHAPE;
@@ -653,15 +680,23 @@ static int three_nn_entry(int b, int n, int m, const float *xyz1, const float *x
         const float factor = lab_f == 1 ? 1.2f : lab_f == 2 ? 1.6f : lab_f == 3 ? 2.0f : lab_f == 4 ? 1.45f : kNnCellFactor;
         const int parts = (n + rows - 1) / rows;
         const size_t lds = three_nn_cells_lds(m, rows);
+        // (ONE statement: the macro stands behind an `if`)
 #define PN2_NN_CELLS(NT)                                                                                                          \
-        return launch_counts([](auto... c) { return three_nn_cells_kernel<NT, decltype(c)...>; }, lengths, lengths2,              \
-                             dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor, xyz1, xyz2,  \
-                             dist, idx);
+        return pk ? launch_counts_packed<true>([](auto... c) { return three_nn_cells_kernel<NT, decltype(c)...>; }, *pk, lengths2, \
+                                               dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, \
+                                               factor, xyz1, xyz2, dist, idx)                                                     \
+                  : launch_counts([](auto... c) { return three_nn_cells_kernel<NT, decltype(c)...>; }, lengths, lengths2,         \
+                                  dim3((unsigned)(parts * b)), dim3(NT), lds, as_stream(stream), n, m, rows, parts, b, factor, xyz1, \
+                                  xyz2, dist, idx);
         if (lab_nt == 256) PN2_NN_CELLS(256)
         if (lab_nt == 1024) PN2_NN_CELLS(1024)
         PN2_NN_CELLS(kNnCellsThreads)
 #undef PN2_NN_CELLS
     }
+    if (pk)
+        return launch_counts_packed<true>([](auto... c) { return three_nn_kernel<decltype(c)...>; }, *pk, lengths2,
+                                          dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n, m, xyz1, xyz2,
+                                          dist, idx);
     return launch_counts([](auto... c) { return three_nn_kernel<decltype(c)...>; }, lengths, lengths2,
                          dim3((n + kNnPoints - 1) / kNnPoints, b), dim3(kNnThreads), 0, as_stream(stream), n, m, xyz1, xyz2, dist, idx);
 }
@@ -707,6 +742,24 @@ extern "C" int pn2_three_nn_ragged_pair(int b, int n, int m, const float *xyz1, 
                                         const int *lengths2, float *dist, int *idx, int variant, void *stream)
 {
     return three_nn_ragged(2, b, n, m, xyz1, lengths1, xyz2, lengths2, dist, idx, variant, stream);
+}
+
+// Packed unknown side: cloud c of xyz1 is xyz1[offsets1[c] : offsets1[c + 1]] of a flat (total, 3) array, offsets1 (b + 1) int32 on
+// the device, never read by the host; nmax bounds every cloud's count and sizes the grid. xyz2 (b, m, 3) is dense, or -- lengths2
+// != NULL -- holds lengths2[c] valid known points per cloud as in pn2_three_nn_ragged_pair. dist, idx are (total, 3): row
+// offsets1[c] + i belongs to point i of cloud c and = pn2_three_nn_ex on the slice for every variant. global_idx 1 writes a
+// known-point index as c m + j. Codes in the order of pn2_three_nn_ragged (PN2_E_TOO_LARGE for total 3 > INT_MAX).
+extern "C" int pn2_three_nn_packed(int b, int total, int nmax, int m, const float *xyz1, const int *offsets1, const float *xyz2,
+                                   const int *lengths2, int global_idx, float *dist, int *idx, int variant, void *stream)
+{
+    if (variant < 0 || variant > 2) return PN2_E_ARG;
+    if (b < 0 || nmax <= 0 || m < 0) return PN2_E_SHAPE;
+    if (b == 0) return PN2_OK;
+    if (total <= 0) return PN2_E_SHAPE;
+    if (!offsets1 || !xyz1 || !dist || !idx || (m > 0 && !xyz2)) return PN2_E_NULL;
+    if ((long long)total * 3 > INT_MAX) return PN2_E_TOO_LARGE;
+    const pn2::Packed pk = {offsets1, total, global_idx ? 1 : 0};
+    return three_nn_entry(b, nmax, m, xyz1, xyz2, dist, idx, variant, stream, nullptr, lengths2, &pk);
 }
 
 static int three_interpolate_entry(int b, int m, int c, int n, const float *points, const int *idx, const float *weight,

@@ -118,6 +118,7 @@ __device__ __forceinline__ void decode_cloud_block(unsigned i, int parts, int b,
 template <class... Cnt>
 struct Counts {
     static_assert(sizeof...(Cnt) <= 2 && (std::is_same<Cnt, const int *>::value && ...), "at most two arrays of int counts");
+    static constexpr bool packed = false;
     const int *side[2];                                   // NULL past the arrays given
     __device__ __forceinline__ Counts(Cnt... c) : side{c...} {}
 };
@@ -127,6 +128,44 @@ struct Counts {
 __device__ __forceinline__ int cloud_count(const int *__restrict__ counts, size_t cloud, int extent)
 {
     return min(max(__builtin_amdgcn_readfirstlane(counts[cloud]), 1), extent);
+}
+
+// ---- packed batches: the FIRST side's clouds lie back to back in one (total, 3) array -----------------------
+// A further mode of the same pack: its first element is a Packed instead of a count array. Cloud c is rows
+// offsets[c] .. offsets[c + 1] - 1 of the flat array ((b + 1) int32 on the device, never read by the host); the kernel's `n` is
+// then nmax, the host's bound on every cloud's count, from which grid, LDS and tier are derived as from a padded n.
+// global_idx: 0 = indices are cloud-local (the reference's); 1 = a point index leaves as offsets[c] + k, a row of the flat array
+// -- one wave-uniform add where the index is stored (a known-point index of three_nn: c m + j).
+struct Packed {
+    const int *offsets;
+    int total;                                            // rows of the flat array (host value: the clamps below rest on it)
+    int global_idx;
+};
+
+template <class... Rest>
+struct Counts<Packed, Rest...> {
+    static_assert(sizeof...(Rest) <= 1 && (std::is_same<Rest, const int *>::value && ...), "offsets, then at most one array of int counts");
+    static constexpr bool packed = true;
+    Packed pk;
+    const int *side[2];                                   // [0] = the offsets; [1] = the second side's counts or NULL
+    __device__ __forceinline__ Counts(Packed p, Rest... r) : pk(p), side{p.offsets, r...} {}
+};
+
+// The kernels declare their pack as `CountArg<Cnt>... cnt`: an array is __restrict__ as before, a Packed travels by value.
+template <class T> struct CountArgOf { typedef T type; };
+template <class T> struct CountArgOf<T *> { typedef T *__restrict__ type; };
+template <class T> using CountArg = typename CountArgOf<T>::type;
+
+// First row of cloud `cloud`, clamped into 0..total-1, and its count, clamped into 1..min(nmax, total - start): for memory
+// safety only, like cloud_count -- validation is check_offsets, where the batch is built. Wave-uniform, read once.
+__device__ __forceinline__ int cloud_start(const Packed &pk, size_t cloud)
+{
+    return min(max(__builtin_amdgcn_readfirstlane(pk.offsets[cloud]), 0), pk.total - 1);
+}
+__device__ __forceinline__ int cloud_count(const Packed &pk, size_t cloud, int start, int nmax)
+{
+    const int raw = __builtin_amdgcn_readfirstlane(pk.offsets[cloud + 1]) - __builtin_amdgcn_readfirstlane(pk.offsets[cloud]);
+    return min(max(raw, 1), min(nmax, pk.total - start));
 }
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
@@ -232,6 +271,17 @@ inline int launch_counts(Pick pick, const int *counts1, const int *counts2, dim3
 {
     auto go = [&](auto... c) { return launch_lds(pick(c...), grid, block, lds, st, args..., c...); };
     return counts2 ? go(counts1, counts2) : counts1 ? go(counts1) : go();
+}
+
+// The same launch in the packed mode: `pk` takes the place of counts1. PAIR: the family also has a ragged second side and
+// counts2 (NULL = dense) is passed behind pk; without PAIR only the one-element pack is instantiated.
+template <bool PAIR, class Pick, typename... Args>
+inline int launch_counts_packed(Pick pick, Packed pk, const int *counts2, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args)
+{
+    auto go = [&](auto... c) { return launch_lds(pick(c...), grid, block, lds, st, args..., c...); };
+    if constexpr (PAIR)
+        if (counts2) return go(pk, counts2);
+    return go(pk);
 }
 
 // Workgroups of `kern` (threads, dynamic LDS bytes) the current device can hold at once: occupancy query x CU

@@ -19,14 +19,32 @@ from .tf_sampling import farthest_point_sample, farthest_point_sample_gather, ga
 from .tf_grouping import (query_ball_point, group_point, knn_point, query_ball_group_xyz,
                           query_ball_group_xyz_msg, sample_and_group_xyz)
 from .tf_interpolate import three_nn, three_interpolate, fp_interp_concat
-from ._tensors import lengths_for, ragged_lengths, use_segmented_grad
+from ._tensors import lengths_for, packed_args, ragged_lengths, require, use_segmented_grad
 from . import sa_mlp
 from . import train_mlp
 from .geometry import FPGeometry, SAGeometry
 from .index_plan import index_plan
 
 
-def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, fused=None, lengths=None, npoints=None):
+def _sample_and_group_packed(npoint, radius, nsample, xyz, points, use_xyz, offsets, max_points):
+    """sample_and_group on a packed batch: packed FPS + gather and packed ball query + group (two launches, no host
+    synchronisation, capturable), indices GLOBAL -- rows of the flat array --, so the features are group_point on the flat view
+    (1, total, c). xyz carries no gradient here (the packed operators are not differentiable)."""
+    offs, b, total, nmax = packed_args(offsets, max_points, None, xyz, "sample_and_group")
+    m, ns = int(npoint), int(nsample)
+    _, new_xyz = farthest_point_sample_gather(m, xyz, offsets=offs, max_points=nmax)
+    idx, _, grouped_xyz = query_ball_group_xyz(radius, ns, xyz, new_xyz, True, offsets=offs, max_points=nmax, global_idx=True)
+    if points is not None:
+        require(points.dim() == 2 and points.shape[0] == total, "sample_and_group: with offsets, points is (total, channel)")
+        grouped_points = group_point(points.reshape(1, total, points.shape[1]), idx.view(1, b * m, ns)).view(b, m, ns, points.shape[1])
+        new_points = torch.cat([grouped_xyz, grouped_points], dim=-1) if use_xyz else grouped_points
+    else:
+        new_points = grouped_xyz
+    return new_xyz, new_points, idx, grouped_xyz
+
+
+def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, fused=None, lengths=None, npoints=None, offsets=None,
+                     max_points=None):
     """reference: pointnet_util.py:22-56.
 
     xyz (b, ndataset, 3), points (b, ndataset, channel) or None
@@ -42,7 +60,17 @@ def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=Tr
     npoints: (b,) per-cloud sample counts (cloud i yields npoints[i] <= npoint centroids): centroid rows from npoints[i] on
     repeat sample 0 and their groups are idx 0 (point 0: valid, so the padding rows of xyz / points are still never
     gathered); on the fused ball-query route their grouped_xyz is +0.0, elsewhere point 0 minus the centroid (= +0.0 as well).
+    offsets / max_points: a PACKED batch -- xyz (total, 3) and points (total, channel) hold the clouds back to back, cloud i is
+    rows offsets[i] .. offsets[i + 1] - 1 (offsets (b + 1,) on the device, max_points a host int bounding every cloud's count).
+    new_xyz, new_points and grouped_xyz come back dense (b, npoint, ...) and are each cloud's dense results; idx holds GLOBAL
+    rows of the flat arrays. Not with lengths / npoints / knn, and xyz gets no gradient (ValueError where it wants one).
     """
+    if offsets is not None:
+        require(lengths is None and npoints is None, "sample_and_group: offsets and lengths / npoints are two layouts; give one")
+        require(not knn, "sample_and_group: knn is not offered with offsets")
+        require(not (torch.is_grad_enabled() and isinstance(xyz, torch.Tensor) and xyz.requires_grad),
+                "sample_and_group: with offsets xyz gets no gradient; detach it")
+        return _sample_and_group_packed(npoint, radius, nsample, xyz, points, use_xyz, offsets, max_points)
     if fused is None:
         fused = not (torch.is_grad_enabled() and xyz.requires_grad)
     if lengths is not None:
@@ -139,18 +167,20 @@ def _no_packing_under_capture():
                            "or run one eager eval forward -- before capturing a graph")
 
 
-def _train_fused_ok(mod, stacks, pooling, group_all, xyz, points):
+def _train_fused_ok(mod, stacks, pooling, group_all, xyz, points, m=None):
     """Training (batch-statistics batch norm, autograd) of a set-abstraction module on stacks pn2_mlp_train_forward covers: conv
     1x1 + BN + ReLU triples, rows a multiple of 32, nsample 16 or a multiple of 32 (train_mlp.py); avg / weighted_avg /
     max_and_avg where pn2_mlp_train_pool_supported says so. stacks: [(net, nsample)] -- the module's one stack, or one per
-    radius of an MSG module (which asks with pooling "max"); every one of them must be covered."""
+    radius of an MSG module (which asks with pooling "max"); every one of them must be covered.
+    m: the centroid rows per cloud of xyz when that is not mod.npoint (the flat view of a packed batch: one cloud of
+    B npoint centroids)."""
     if not mod.fused_mlp or not mod.training or not xyz.is_cuda:
         return False
     want_xyz = torch.is_grad_enabled() and xyz.requires_grad
     if (want_xyz and not mod.fused_xyz_grad) or (points is not None and not mod.use_xyz):
         return False
     b, n, _ = xyz.shape
-    m = 1 if group_all else mod.npoint
+    m = 1 if group_all else (mod.npoint if m is None else m)
     if want_xyz:                                   # (never weighted_avg: its weights depend on xyz)
         cfeat = points.shape[2] if points is not None else 0
         return all(train_mlp.xyz_grad_supported(net, b * m * ns, ns, pooling, b, n, m, cfeat, not group_all) for net, ns in stacks)
@@ -159,7 +189,7 @@ def _train_fused_ok(mod, stacks, pooling, group_all, xyz, points):
     return all(train_mlp.stack_supported(net, b * m * ns, ns, True) for net, ns in stacks)
 
 
-def _frozen_ok(mod, stacks, pooling, group_all, xyz, points):
+def _frozen_ok(mod, stacks, pooling, group_all, xyz, points, m=None):
     """Autograd through stacks whose batch norms all normalise with their running statistics (fused_frozen_bn): something
     must want a gradient -- an input (xyz only with fused_xyz_grad, as in training) or a parameter of a stack -- and
     pn2_mlp_train_frozen_supported must cover every stack. What the batch-statistics node refuses is refused here too."""
@@ -172,16 +202,16 @@ def _frozen_ok(mod, stacks, pooling, group_all, xyz, points):
             any(p.requires_grad for net, _ in stacks for p in net.parameters())):
         return False
     b, n, _ = xyz.shape
-    m = 1 if group_all else mod.npoint
+    m = 1 if group_all else (mod.npoint if m is None else m)
     dims = (b, n, m, points.shape[2] if points is not None else 0, not group_all) if want_xyz else None
     return all(train_mlp.frozen_supported(net, b * m * ns, ns, True, pooling, dims) for net, ns in stacks)
 
 
-def _train_mode(mod, stacks, pooling, group_all, xyz, points):
+def _train_mode(mod, stacks, pooling, group_all, xyz, points, m=None):
     """"fused_train" (batch statistics), "fused_frozen" (running statistics, opt-in) or None: which fused autograd node."""
-    if _train_fused_ok(mod, stacks, pooling, group_all, xyz, points):
+    if _train_fused_ok(mod, stacks, pooling, group_all, xyz, points, m):
         return "fused_train"
-    return "fused_frozen" if _frozen_ok(mod, stacks, pooling, group_all, xyz, points) else None
+    return "fused_frozen" if _frozen_ok(mod, stacks, pooling, group_all, xyz, points, m) else None
 
 
 def _ragged_train_ok(mod, stacks, group_all, xyz, points):
@@ -321,10 +351,10 @@ class PointnetSAModule(nn.Module):
         self._pack_cache = None
         self._lvl_buffers = None
 
-    def _train_mode(self, xyz, points):
+    def _train_mode(self, xyz, points, m=None):
         """The module-level _train_mode on this module's one stack (a group_all level's group is the whole cloud)."""
         return _train_mode(self, [(self.mlp.net, xyz.shape[1] if self.group_all else self.nsample)], self.pooling, self.group_all,
-                           xyz, points)
+                           xyz, points, m)
 
     def _level_buffers(self):
         if not self.reuse_buffers:
@@ -539,7 +569,31 @@ class PointnetSAModule(nn.Module):
         _, yv, _ = self._stack_and_pool(None, pv, None, gv)                     # (1, total, C'): statistics over the valid groups
         return new_xyz, _scatter_rows(yv[0], rows, b * m).reshape(b, m, yv.shape[2]), idx
 
-    def forward(self, xyz, points, geometry=None, lengths=None, npoints=None):
+    def _forward_packed(self, xyz, points, offsets, max_points):
+        """forward() on a PACKED batch: xyz (total, 3), points (total, c) or None, cloud i = rows
+        offsets[i] .. offsets[i + 1] - 1. The geometry is built in the FLAT VIEW -- packed FPS + gather and packed ball query
+        with global indices give SAGeometry(new_xyz (1, B npoint, 3), idx (1, B npoint, nsample), fps_idx) on xyz (1, total, 3)
+        -- and handed to _forward_on: every route behind a geometry is index-driven, so the training nodes, the inference
+        kernels and the layer-by-layer path run unchanged on one cloud of `total` points and B npoint centroids. No padding
+        row exists, so nothing is masked. The route predicates get the true centroid count (m = B npoint). last_path is the
+        route's with "packed_" in front; where no fused route takes the flat view it is "packed_unfused", layer by layer.
+        -> new_xyz (B, npoint, 3), features (B, npoint, C), idx (B, npoint, nsample) global."""
+        offs, b, total, nmax = packed_args(offsets, max_points, None, xyz, "PointnetSAModule")
+        if points is not None:
+            require(points.dim() == 2 and points.shape[0] == total, "PointnetSAModule: with offsets, points is (total, channel)")
+        m, ns = self.npoint, self.nsample
+        flat = xyz.detach()
+        fps_idx, new_xyz = farthest_point_sample_gather(m, flat, offsets=offs, max_points=nmax, global_idx=True)
+        idx, _ = query_ball_point(self.radius, ns, flat, new_xyz, offsets=offs, max_points=nmax, global_idx=True)
+        g = SAGeometry(new_xyz.view(1, b * m, 3), idx.view(1, b * m, ns), fps_idx.view(1, b * m))
+        xf = xyz.reshape(1, total, 3)
+        pf = points.reshape(1, total, points.shape[1]) if points is not None else None
+        path = self._train_mode(xf, pf, b * m) or ("fused" if self._fused_ok(xf, pf) else "unfused")
+        new_xyz_f, out, _ = self._forward_on(xf, pf, g, path)
+        self.last_path = "packed_" + path
+        return new_xyz_f.view(b, m, 3), out.view(b, m, out.shape[2]), idx
+
+    def forward(self, xyz, points, geometry=None, lengths=None, npoints=None, offsets=None, max_points=None):
         """Resolve the level's geometry, then run the layer stack on it (_forward_on): a geometry computed ahead
         (geometry=), the ragged operators' (lengths=), or this call's own (geometry()) for the training nodes and for the
         inference kernel behind kNN or a pooling other than max. Three routes are not "geometry, then stack" and stay apart:
@@ -554,7 +608,16 @@ class PointnetSAModule(nn.Module):
         levels (ValueError) unless ragged_group_all is set (_forward_all_ragged: the group is the cloud's valid rows, which
         may then hold anything beyond a length).
         npoints: (b,) per-cloud sample counts, with or without lengths (_forward_counts; a geometry= must come from
-        geometry(npoints=)): new_points rows from npoints[c] on are exact zeros; hand npoints to the next level as its lengths."""
+        geometry(npoints=)): new_points rows from npoints[c] on are exact zeros; hand npoints to the next level as its lengths.
+        offsets / max_points: a packed batch, xyz (total, 3) and points (total, c), see _forward_packed. Single scale, ball
+        query; ValueError with group_all, knn, lengths / npoints, a geometry= or fused_xyz_grad."""
+        if offsets is not None:
+            require(lengths is None and npoints is None, "PointnetSAModule: offsets and lengths / npoints are two layouts; give one")
+            require(not self.group_all, "PointnetSAModule: group_all is not offered with offsets")
+            require(not self.knn, "PointnetSAModule: knn is not offered with offsets")
+            require(geometry is None, "PointnetSAModule: a geometry computed ahead is not offered with offsets")
+            require(not self.fused_xyz_grad, "PointnetSAModule: fused_xyz_grad is not offered with offsets")
+            return self._forward_packed(xyz, points, offsets, max_points)
         if (lengths is not None or npoints is not None) and self.group_all:
             if npoints is not None or not self.ragged_group_all:
                 raise ValueError("group_all with lengths: the group would contain the padding rows")
@@ -830,11 +893,13 @@ class PointnetSAModuleMSG(nn.Module):
         self.last_path = "unfused"
         return self._forward_layers(xyz, points, g)
 
-    def forward(self, xyz, points, geometry=None, lengths=None, npoints=None):
+    def forward(self, xyz, points, geometry=None, lengths=None, npoints=None, offsets=None, max_points=None):
         """Resolve the level's geometry -- computed ahead (geometry=), the ragged operators' (lengths=, see
         PointnetSAModule.forward) or, for the training nodes, this call's own (geometry()) -- then one function per path on it.
         Without a geometry the inference kernels and the layer-by-layer path keep their own launches (_group_scales).
-        npoints: (b,) per-cloud sample counts, with or without lengths (_forward_counts)."""
+        npoints: (b,) per-cloud sample counts, with or without lengths (_forward_counts).
+        offsets: packed batches are not offered for multi-scale grouping yet (ValueError)."""
+        require(offsets is None and max_points is None, "PointnetSAModuleMSG: packed batches (offsets=) are not offered for MSG levels")
         if npoints is not None:
             g = geometry.wait() if geometry is not None else self.geometry(xyz, lengths=lengths, npoints=npoints)
             return self._forward_counts(xyz, points, g, npoints)
@@ -1013,12 +1078,61 @@ class PointnetFPModule(nn.Module):
         out = torch.zeros((b * n, yv.shape[1]), dtype=yv.dtype, device=dev).index_copy(0, rows, yv)
         return out.reshape(b, n, yv.shape[1])
 
-    def forward(self, xyz1, xyz2, points1, points2, geometry=None, lengths1=None, lengths2=None):
+    def _forward_packed(self, xyz1, xyz2, points1, points2, offsets1, max_points1):
+        """forward() with a PACKED unknown side: xyz1 (total, 3), points1 (total, c1) or None, cloud i = rows
+        offsets1[i] .. offsets1[i + 1] - 1; the known side xyz2 (B, m, 3), points2 (B, m, c2) is a previous level's dense
+        output. Packed three_nn with global indices gives FPGeometry(dist, idx (1, total, 3)) in the FLAT VIEW, idx naming rows
+        of points2 viewed as (1, B m, c2); the inference kernel and _stack_on run unchanged on it. -> (total, C).
+        eval(): the fused kernel where _fused_kind has one for `total` rows. train(): `total` a multiple of 32 -- the dense
+        routes of _stack_on, no mask anywhere. Otherwise the stack's rows are extended to the next multiple of 32 (idx 0 /
+        dist 0 / points1 0 on the <= 31 tail rows) and the masked plain-rows node runs with b = 1 and lengths =
+        offsets1[B : B + 1] = total, already on the device: the tail is the only masked word, nothing synchronises; where the
+        masked node does not cover the stack, layer by layer on the `total` rows. last_path: the route's with "packed_" in front."""
+        dev = xyz1.device
+        b, m, c2 = points2.shape
+        offs, b, total, nmax = packed_args(offsets1, max_points1, None, xyz1, "PointnetFPModule", "offsets1", "max_points1", b=b)
+        c1 = 0
+        if points1 is not None:
+            require(points1.dim() == 2 and points1.shape[0] == total, "PointnetFPModule: with offsets1, points1 is (total, channel)")
+            c1 = points1.shape[1]
+        p2 = points2.reshape(1, b * m, c2)
+        kind = self._fused_kind(points1.view(1, total, c1) if points1 is not None else None, p2, total)
+        n32 = (total + 31) // 32 * 32
+        tail = kind is None and n32 != total and self.training and xyz1.is_cuda and self.fused_mlp and \
+            train_mlp.ragged_supported(self.mlp.net, 1, n32) and self._train_mode(None, p2, n32) == "fused_train"
+        rows = n32 if tail else total
+        # three_nn writes the first `total` rows of buffers that already have the stack's row count
+        dist = torch.zeros((rows, 3), dtype=torch.float32, device=dev) if tail else torch.empty((rows, 3), dtype=torch.float32, device=dev)
+        idx = torch.zeros((rows, 3), dtype=torch.int32, device=dev) if tail else torch.empty((rows, 3), dtype=torch.int32, device=dev)
+        three_nn(xyz1.detach(), xyz2.detach(), out=(dist[:total], idx[:total]), offsets1=offs, max_points1=nmax, global_idx=True)   # :211
+        g = FPGeometry(dist.view(1, rows, 3), idx.view(1, rows, 3), self._plan_of(idx.view(1, rows, 3), b * m))
+        if tail:
+            p1 = torch.nn.functional.pad(points1, (0, 0, 0, rows - total)).view(1, rows, c1) if points1 is not None else None
+            x1 = xyz1.new_empty((1, rows, 0))                                   # (_stack_on reads the row count off it, nothing else)
+            out = self._stack_on(x1, p1, p2, g, offs[b:b + 1], paths=("fused_train_ragged", "fused_train_ragged_node"),
+                                 node_ok=lambda *level: self.fused_ragged_node and train_mlp.fp_level_ragged_supported(*level))
+            self.last_path = "packed_" + self.last_path
+            return out[0, :total]
+        x1 = xyz1.reshape(1, total, 3)
+        p1 = points1.reshape(1, total, c1) if points1 is not None else None
+        if kind is not None:
+            self.last_path = "packed_fused"
+            return sa_mlp.fp_mlp(p2, p1, g.idx, g.dist, self._packed(c2, c1, kind, dev))[0]
+        out = self._stack_on(x1, p1, p2, g)
+        self.last_path = "packed_" + self.last_path
+        return out[0]
+
+    def forward(self, xyz1, xyz2, points1, points2, geometry=None, lengths1=None, lengths2=None, offsets1=None, max_points1=None):
         """three_nn -- computed ahead (geometry=) or here -- then the stack on its result (_stack_on). One route stays apart:
         inference without a geometry is ONE C call (sa_mlp.fp_level: three_nn and the level's kernel; it owns the level's
         buffers). lengths1: a ragged unknown side, see _forward_ragged. lengths2: a ragged known side (a previous level's
         npoints); without lengths1 the unknown side is dense and the result is that of the dense routes on the two-sided
-        three_nn's result."""
+        three_nn's result. offsets1 / max_points1: a packed unknown side, xyz1 (total, 3) and points1 (total, c1), see
+        _forward_packed; ValueError with lengths1 / lengths2 or a geometry=."""
+        if offsets1 is not None:
+            require(lengths1 is None and lengths2 is None, "PointnetFPModule: offsets1 and lengths1 / lengths2 are two layouts; give one")
+            require(geometry is None, "PointnetFPModule: a geometry computed ahead is not offered with offsets1")
+            return self._forward_packed(xyz1, xyz2, points1, points2, offsets1, max_points1)
         if lengths1 is not None:
             return self._forward_ragged(xyz1, xyz2, points1, points2, lengths1, geometry, lengths2)
         if geometry is None and lengths2 is not None:

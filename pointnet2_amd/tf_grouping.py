@@ -10,8 +10,8 @@ NoGradient (:21, :32).
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, f32, full_counts, i32, lengths_for, on_device, ptr, ragged_lengths, require, same_device, scatter_grad,
-                       stream_ptr)
+from ._tensors import (out_or_empty, f32, full_counts, i32, lengths_for, on_device, packed_args, ptr, ragged_lengths, require, same_device,
+                       scatter_grad, stream_ptr)
 
 
 # Ball-query kernel choice passed with every call (pn2_query_ball_group_xyz_ex): 0 automatic, 1 sweep,
@@ -33,9 +33,36 @@ def pair_counts(lengths1, lengths2, b, n, m, dev):
     return lens1, lens2
 
 
-def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None, lengths2=None):
+def _ball_query_packed(radius, nsample, xyz1, xyz2, offsets, max_points, lengths1, lengths2, global_idx, subtract, idx, cnt, fuse, op):
+    """The packed form of both ball-query operators (pn2_query_ball_group_xyz_packed): xyz1 (total, 3) with offsets (b + 1,) on
+    the device, the queries xyz2 (b, m, 3) dense. idx / cnt: preallocated outputs or None (idx None and fuse: no idx wanted)."""
+    require(lengths2 is None, "%s: a ragged query side (lengths2=) is not offered with offsets" % op)
+    require(isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 and xyz2.shape[2] == 3, "QueryBallPoint expects (batch_size, npoint, 3) xyz2 shape.")
+    b, m, _ = xyz2.shape
+    offs, b, total, nmax = packed_args(offsets, max_points, lengths1, xyz1, op, b=b)    # (before anything else, like lengths_for)
+    xyz1 = f32(xyz1, "xyz1")
+    xyz2 = f32(xyz2, "xyz2")
+    dev = same_device(xyz1, xyz2)
+    ns = int(nsample)
+    if idx is None and not fuse:
+        idx = torch.empty((b, m, ns), dtype=torch.int32, device=dev)
+    if cnt is None:
+        cnt = torch.empty((b, m), dtype=torch.int32, device=dev)
+    grouped = torch.empty((b, m, ns, 3), dtype=torch.float32, device=dev) if fuse else None
+    with on_device(dev):
+        _C.check(_C.lib().pn2_query_ball_group_xyz_packed(b, total, nmax, m, float(radius), ns, ptr(xyz1), ptr(offs), ptr(xyz2),
+                                                          1 if subtract else 0, 1 if global_idx else 0, ptr(idx), ptr(cnt), ptr(grouped),
+                                                          _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)), op)
+    return idx, cnt, grouped
+
+
+def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None, lengths2=None, offsets=None, max_points=None, global_idx=False):
     """radius float, nsample int, xyz1 (b, ndataset, 3), xyz2 (b, npoint, 3)
     -> idx (b, npoint, nsample) i32, pts_cnt (b, npoint) i32.
+    offsets / max_points: a PACKED xyz1 -- one flat (total, 3) array, cloud i is xyz1[offsets[i] : offsets[i + 1]] (offsets
+    (b + 1,) on the device; max_points a host int bounding every cloud's count, required); xyz2 and the outputs stay dense. Each
+    cloud's result is the dense operator's on its slice. global_idx: idx holds rows of the flat array (offsets[i] + k). Not
+    to be mixed with lengths1 / lengths2 (ValueError).
     lengths1: (b,) per-cloud point counts of a ragged xyz1 (cloud i is xyz1[i, :lengths1[i]]): each cloud's result is the
     dense operator's on its slice, rows beyond the length are never read. None = every cloud holds all ndataset points.
     lengths2: (b,) per-cloud counts of valid QUERY rows of xyz2 (cloud i asks xyz2[i, :lengths2[i]]): rows below the count are the
@@ -47,6 +74,13 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None, lengt
     """
     require(float(radius) > 0, "QueryBallPoint expects positive radius")
     require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
+    if offsets is not None:
+        if out is not None:
+            shape = (xyz2.shape[0], xyz2.shape[1]) if isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 else (0, 0)
+            out = (out_or_empty(out[0], shape + (int(nsample),), torch.int32, xyz2.device, "out[0]"),
+                   out_or_empty(out[1], shape, torch.int32, xyz2.device, "out[1]"))
+        return _ball_query_packed(radius, nsample, xyz1, xyz2, offsets, max_points, lengths1, lengths2, global_idx, False,
+                                  out[0] if out is not None else None, out[1] if out is not None else None, False, "query_ball_point")[:2]
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     if lengths2 is not None:
@@ -87,7 +121,8 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None, lengt
     return idx, cnt
 
 
-def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None, lengths2=None):
+def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None, lengths2=None, offsets=None,
+                         max_points=None, global_idx=False):
     """Fused query_ball_point + group_point(xyz1, idx) [- centroid] in one pass
     (what pointnet_util.py:44-46 does with three ops). No reference counterpart
     (SURVEY.md 8f1); NOT differentiable -- used on the inference path and by
@@ -96,9 +131,17 @@ def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, wa
     -> idx (b,m,nsample) i32 or None, pts_cnt (b,m) i32, grouped_xyz (b,m,nsample,3) f32
     lengths1: (b,) per-cloud point counts of a ragged xyz1, see query_ball_point.
     lengths2: (b,) per-cloud counts of valid query rows, see query_ball_point.
+    offsets / max_points / global_idx: a packed xyz1 (total, 3), see query_ball_point; grouped_xyz is gathered from each cloud's
+    own points whatever global_idx is.
     """
     require(float(radius) > 0, "QueryBallPoint expects positive radius")
     require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
+    if offsets is not None:
+        idx = None
+        if want_idx and isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3:
+            idx = torch.empty((xyz2.shape[0], xyz2.shape[1], int(nsample)), dtype=torch.int32, device=xyz2.device)
+        return _ball_query_packed(radius, nsample, xyz1, xyz2, offsets, max_points, lengths1, lengths2, global_idx, subtract_centroid,
+                                  idx, None, True, "query_ball_group_xyz")
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     if lengths2 is not None:

@@ -10,11 +10,16 @@ gradient w.r.t. `points` only (tf_interpolate.py:29-34); ThreeNN is NoGradient (
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, f32, full_counts, i32, is_deterministic, lengths_for, on_device, ptr, ragged_lengths, require, same_device,
-                       scatter_grad, seg_workspace, stream_ptr)
+from ._tensors import (out_or_empty, f32, full_counts, i32, is_deterministic, lengths_for, on_device, packed_args, ptr, ragged_lengths, require,
+                       same_device, scatter_grad, seg_workspace, stream_ptr)
 
 
-def three_nn(xyz1, xyz2, out=None, lengths1=None, lengths2=None):
+# three_nn kernel choice of the packed calls (pn2_three_nn_packed's variant): 0 the library's, 1 the sweep, 2 the cell list.
+# Results never depend on it; the tests force both.
+_NN_PACKED_VARIANT = [0]
+
+
+def three_nn(xyz1, xyz2, out=None, lengths1=None, lengths2=None, offsets1=None, max_points1=None, global_idx=False):
     """xyz1 (b, n, 3) unknown, xyz2 (b, m, 3) known -> dist (b, n, 3) f32 SQUARED
     distances ascending, idx (b, n, 3) i32. out: optional preallocated (dist, idx).
     lengths1: (b,) per-cloud counts of a ragged UNKNOWN side (cloud i is xyz1[i, :lengths1[i]]; the known side is dense):
@@ -22,10 +27,29 @@ def three_nn(xyz1, xyz2, out=None, lengths1=None, lengths2=None):
     lengths2: (b,) per-cloud counts of a ragged KNOWN side (cloud i's known points are xyz2[i, :lengths2[i]]; rows beyond are
     never read): every row is the dense operator's on the slice pair, so idx < lengths2[i], and fewer than three known points
     leave the dense operator's +inf / index 0 entries. With one of lengths1 / lengths2 given the other side is dense.
+    offsets1 / max_points1: a PACKED unknown side -- xyz1 is one flat (total, 3) array, cloud i is
+    xyz1[offsets1[i] : offsets1[i + 1]] (offsets1 (b + 1,) on the device; max_points1 a host int bounding every cloud's count,
+    required); xyz2 (b, m, 3) stays dense (lengths2 allowed). dist, idx are (total, 3), row offsets1[i] + j = point j of cloud i,
+    the dense operator's on the slice; no padding rows. global_idx: a known-point index is written as i m + k, a row of
+    xyz2.view(b m, 3). Not to be mixed with lengths1 (ValueError).
 
     reference: tf_interpolate.py:8-17, op ThreeNN tf_interpolate.cpp:157-187,
     loop threenn_cpu :60-103.
     """
+    if offsets1 is not None:
+        require(isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 and xyz2.shape[2] == 3, "ThreeNN expects (b,m,3) xyz2 shape")
+        b, m, _ = xyz2.shape
+        offs, b, total, nmax = packed_args(offsets1, max_points1, lengths1, xyz1, "three_nn", "offsets1", "max_points1", b=b)
+        xyz1 = f32(xyz1, "xyz1")
+        xyz2 = f32(xyz2, "xyz2")
+        dev = same_device(xyz1, xyz2)
+        lens2 = ragged_lengths(lengths_for(lengths2, xyz2, "lengths2"), b, dev, "lengths2") if lengths2 is not None else None
+        dist = out_or_empty(out[0] if out is not None else None, (total, 3), torch.float32, dev, "out[0]")
+        idx = out_or_empty(out[1] if out is not None else None, (total, 3), torch.int32, dev, "out[1]")
+        with on_device(dev):
+            _C.check(_C.lib().pn2_three_nn_packed(b, total, nmax, m, ptr(xyz1), ptr(offs), ptr(xyz2), ptr(lens2), 1 if global_idx else 0,
+                                                  ptr(dist), ptr(idx), _NN_PACKED_VARIANT[0], stream_ptr(dev)), "three_nn")
+        return dist, idx
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     if lengths2 is not None:

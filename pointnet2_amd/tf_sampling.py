@@ -11,8 +11,8 @@ ProbSample are NoGradient (:22, :57).
 import torch
 
 from . import _C
-from ._tensors import (det_workspace, f32, full_counts, i32, is_deterministic, lengths_for, on_device, out_or_empty, ptr, ragged_lengths,
-                       require, same_device, stream_ptr)
+from ._tensors import (det_workspace, f32, full_counts, i32, is_deterministic, lengths_for, on_device, out_or_empty, packed_args, ptr,
+                       ragged_lengths, require, same_device, stream_ptr)
 
 
 def prob_sample(inp, inpr):
@@ -240,8 +240,32 @@ def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
                                                                   stream_ptr(dev)), op)
 
 
-def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoints=None):
+def _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, out, want_xyz, op):
+    """The packed form of both sampling operators (pn2_farthest_point_sample_packed): inp (total, 3), offsets (b + 1,) on the
+    device, max_points a host int. -> idx (b, npoint), new_xyz (b, npoint, 3) or None. A tier forced with set_fps_variant
+    applies; nothing synchronises."""
+    require(npoints is None, "%s: per-cloud sample counts (npoints=) are not offered with offsets" % op)
+    offs, b, total, nmax = packed_args(offsets, max_points, lengths, inp, op)           # (before anything else, like lengths_for)
+    require(nmax <= FPS_RAGGED_MAX_POINTS, "%s with offsets supports at most %d points per cloud, got max_points = %d"
+            % (op, FPS_RAGGED_MAX_POINTS, nmax))
+    inp = f32(inp.detach(), "inp")
+    m = int(npoint)
+    dev = inp.device
+    out = out_or_empty(out, (b, m), torch.int32, dev)
+    new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if want_xyz else None
+    with on_device(dev):
+        _C.check(_C.lib().pn2_farthest_point_sample_packed(_FPS_VARIANT[0], b, total, nmax, m, ptr(inp), ptr(offs), 1 if global_idx else 0,
+                                                           ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
+    return out, new_xyz
+
+
+def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoints=None, offsets=None, max_points=None, global_idx=False):
     """Fused farthest_point_sample + gather_point (pointnet_util.py:40 in one launch).
+    offsets / max_points: a PACKED batch -- inp is one flat (total, 3) array, cloud i is inp[offsets[i] : offsets[i + 1]]
+    (offsets (b + 1,) on the device), max_points a host int that bounds every cloud's count (it takes the padded n's place in
+    the tier rule; required, so nothing synchronises). Each cloud's result is the dense operator's on its slice; idx and new_xyz
+    stay dense (b, npoint[, 3]). global_idx: indices are rows of the flat array (offsets[i] + k) instead of cloud-local.
+    Not to be mixed with lengths (ValueError).
     lengths: (b,) per-cloud point counts of a ragged batch (cloud i is inp[i, :lengths[i]]): each cloud's result is the
     dense operator's on its slice, rows beyond the length are never read. None = every cloud holds all n points.
     npoints: (b,) per-cloud sample counts (cloud i yields m_i = npoints[i] <= npoint samples; clamped into 1..npoint on the
@@ -255,6 +279,9 @@ def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoint
     farthest-point order (same results either way).
     """
     require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
+    if offsets is not None:
+        out, new_xyz = _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, None, True, "farthest_point_sample_gather")
+        return out, mark_fps_ordered(new_xyz)
     if lengths is not None:
         lengths = lengths_for(lengths, inp)
     if npoints is not None:
@@ -293,16 +320,19 @@ def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoint
     return out, mark_fps_ordered(new_xyz)
 
 
-def farthest_point_sample(npoint, inp, out=None, lengths=None, npoints=None):
+def farthest_point_sample(npoint, inp, out=None, lengths=None, npoints=None, offsets=None, max_points=None, global_idx=False):
     """npoint int, inp (b, ndataset, 3) f32 -> (b, npoint) i32, first index 0.
     lengths: (b,) per-cloud point counts of a ragged batch, see farthest_point_sample_gather.
     npoints: (b,) per-cloud sample counts, see farthest_point_sample_gather.
+    offsets / max_points / global_idx: a packed batch, inp (total, 3), see farthest_point_sample_gather.
 
     reference: tf_sampling.py:48-56, op FarthestPointSample tf_sampling.cpp:95-123,
     kernel tf_sampling_g.cu:105-170 (tie rule: smallest (k mod 512, k)).
     out: optional preallocated (b, npoint) i32 result.
     """
     require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
+    if offsets is not None:
+        return _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, out, False, "farthest_point_sample")[0]
     if lengths is not None:
         lengths = lengths_for(lengths, inp)
     if npoints is not None:
