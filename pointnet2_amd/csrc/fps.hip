@@ -33,11 +33,10 @@
 // scalar-unit resolution of lane/slot (SALU ops cost a 4-cycle issue slot); box-pruned
 // updates over Morton-sorted 64-point regions (exact, but 784 ns: the per-slot scalar
 // branches and a non-rank-ordered lane arg-max cost more than the skipped distances).
-// Clouds too large for the register tiers fall back to a global-memory tier
-// that keeps the running distances in the caller's `temp` buffer.
-#include "fps_body.h"
-#include "fps_pruned_body.h"
-#include "fps_batch_body.h"
+// The tiers that prune (fps_pruned_body.h, fps_batch_body.h), the rule that picks one and its geometry, and the step from that
+// choice to a kernel are fps_tier.h's. Clouds too large for the register tiers fall back to a global-memory tier that keeps the
+// running distances in the caller's `temp` buffer (or go to fps_large.hip).
+#include "fps_tier.h"
 
 #include <limits.h>
 
@@ -51,28 +50,22 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(int n, int m, int Q, const f
     fps_reg_body<T, P, LDSXYZ, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
 }
 
-// Where cloud c of a ragged launch lies and how many points it holds. No Pk: the padded layout, row c n and lengths[c]. A Packed
-// behind the kernel's argument list (pn2_farthest_point_sample_packed; pn2_device.h): rows offsets[c] .. offsets[c + 1] - 1 of
-// the flat array, n = nmax, lengths unused. The body is handed the slab as cloud 0 either way, so the slice rule below holds
-// for both layouts; coordinates are read as scalars, so a slab may start at any row. base: what fps_global_rows adds.
-template <class... Pk>
-struct FpsSlab {
-    size_t row;
-    int count, base;
-    __device__ __forceinline__ FpsSlab(int c, int n, const int *__restrict__ lengths) : row((size_t)c * n), count(cloud_count(lengths, c, n)), base(0) {}
-};
-template <>
-struct FpsSlab<Packed> {
-    size_t row;
-    int count, base;
-    __device__ __forceinline__ FpsSlab(int c, int n, const int *, Packed pk)
-    {
-        const int s = cloud_start(pk, c);
-        row = (size_t)s;
-        count = cloud_count(pk, c, s, n);
-        base = pk.global_idx ? s : 0;
-    }
-};
+// the pruned and the batched tier (PrunedTier, BatchTier: fps_tier.h) on dense input
+template <int P, int GS>
+__global__ __launch_bounds__(kPrT) void fps_pruned_kernel(int n, int m, int Q, const float *__restrict__ xyz,
+                                                          int *__restrict__ out, float *__restrict__ out_xyz)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fps_pruned_body<P, GS, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
+}
+
+template <int P, int GS>
+__global__ __launch_bounds__(kBtT) void fps_batch_kernel(int n, int m, int Q, const float *__restrict__ xyz,
+                                                         int *__restrict__ out, float *__restrict__ out_xyz)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    fps_batch_body<P, GS, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
+}
 
 // global_idx of the packed mode: the chain and its gather epilogue work on cloud-local indices (the epilogue reads them back);
 // the workgroup-uniform base is added to the finished rows behind them, off the chain. Block-uniform branch.
@@ -84,104 +77,34 @@ __device__ __forceinline__ void fps_global_rows(int m, int base, int *dst)
     for (int j = threadIdx.x; j < m; j += T) dst[j] += base;
 }
 
-// Ragged batch (pn2_farthest_point_sample_ragged): cloud c holds lengths[c] <= n points in its padded (n, 3) slab. The
-// workgroup hands the body its own slab as cloud 0 with n = n_c and Q = ceil(n_c / 512): the tie ranks, the dealing and the
-// padding slots are then exactly those of the dense kernel on the slice, and rows at or beyond n_c are never addressed
-// (fps_body.h: valid = ... && k < n). T, P and the LDS size come from the padded n: T P >= 512 ceil(n / 512) >= 512 Q_c.
-// COUNTS, a sample count per cloud (pn2_farthest_point_sample_ragged_counts): cloud c yields m_c = npoints[c] samples of its n_c
-// points (both counts: cloud_count, pn2_device.h). The body runs with m = m_c on the cloud's slab, so rows below m_c are
-// the first m_c samples of the dense operator on the slice (the chain is prefix-consistent: round j depends on rounds < j
-// alone). Rows m_c .. m-1 repeat sample 0, the way a ball query pads with its first hit; sample 0 is point 0 by the reference's
-// rule (tf_sampling_g.cu:114-116), so the fill is index 0 and xyz[c, 0] and reads nothing back. The fill rows are disjoint from
-// the body's, so no barrier stands between the two. (The fill is a function of its own, fps_ragged_fill in fps_body.h: the
-// wrappers of the other tiers end with it too.) Without COUNTS npoints is never read.
-template <int T, int P, bool LDSXYZ, bool COUNTS, class... Pk>
-__global__ __launch_bounds__(T) void fps_reg_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
-                                                           const int *__restrict__ npoints, int *__restrict__ out,
-                                                           float *__restrict__ out_xyz, Pk... pk)
+// Ragged batch on every tier (pn2_farthest_point_sample_ragged_variant; Pk = Packed: pn2_farthest_point_sample_packed). Cloud c
+// holds n_c = lengths[c] <= n points in its padded (n, 3) slab -- or its rows of the flat array (FpsSlab, fps_body.h). The
+// workgroup hands the tier's body its own slab as cloud 0 with n = n_c and Q = ceil(n_c / 512): every body takes (n, m, Q, cloud,
+// xyz, ...) alike, so the tie ranks, the dealing and the padding slots are exactly those of the dense kernel on the slice, and
+// rows at or beyond n_c are never addressed (fps_body.h: valid = ... && k < n; fps_pruned_prologue: k = i < n ? i : 0). The tier's
+// template, thread count and LDS bytes come from the padded n (fps_choose): threads * P >= 512 ceil(n / 512) >= 512 Q_c, so every
+// tie rank of the slice has a slot; the pruned and batched tiers deal the items i >= n_c as padding items at point 0's position
+// (value 0, key low word 0). There a cloud may be ONE point in 8192 slots, where dense input fills at least half of a template:
+// DESIGN.md 4.11 goes through the prologue, COLLECT, the picker's uncounted loop, the equal-keys rule, the value-0 tail, the
+// slow-batch clock and the pruned tier's skipped reduction on such clouds, and through the termination of every wait inside the
+// workgroup (tests/test_fps_batch_padding_model.py is the CPU model). n_c, m_c and Q_c are block-uniform scalars, so every wave
+// of the workgroup -- the batched tier's picker included -- executes the barriers of the same chain.
+// COUNTS, a sample count per cloud (pn2_farthest_point_sample_ragged_counts): cloud c yields m_c = npoints[c] samples. The body
+// runs with m = m_c on the cloud's slab, so rows below m_c are the first m_c samples of the dense operator on the slice (the chain
+// is prefix-consistent: round j depends on rounds < j alone). Rows m_c .. m-1 repeat sample 0, the way a ball query pads with its
+// first hit; sample 0 is point 0 by the reference's rule (tf_sampling_g.cu:114-116), so the fill is index 0 and xyz[c, 0] and
+// reads nothing back (fps_ragged_fill, fps_body.h). The fill rows are disjoint from the body's, so no barrier stands between the
+// two. Without COUNTS npoints is never read.
+template <class Tier, bool COUNTS, class... Pk>
+__global__ __launch_bounds__(Tier::threads) void fps_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
+                                                                   const int *__restrict__ npoints, int *__restrict__ out,
+                                                                   float *__restrict__ out_xyz, Pk... pk)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int c = blockIdx.x;
-    const FpsSlab<Pk...> slab(c, n, lengths, pk...);
-    const int nc = slab.count;
-    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
-    const int Qc = (nc + kRefThreads - 1) / kRefThreads;
-    const float *__restrict__ src = xyz + slab.row * 3;
-    int *__restrict__ dst = out + (size_t)c * m;
-    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
-    fps_reg_body<T, P, LDSXYZ, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
-    if constexpr (sizeof...(Pk) != 0) fps_global_rows<T>(mc, slab.base, dst);
-    if (COUNTS) fps_ragged_fill<T>(mc, m, src, dst, dxyz);
-}
-
-// Pruned tier (fps_pruned_body.h): kd-grouped slots, per-round box tests, only the groups the new sample can reach are
-// updated. 2049..8192 rank slots, chains long enough to pay for the kd build.
-template <int P, int GS>
-__global__ __launch_bounds__(kPrT) void fps_pruned_kernel(int n, int m, int Q, const float *__restrict__ xyz,
-                                                          int *__restrict__ out, float *__restrict__ out_xyz)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    fps_pruned_body<P, GS, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
-}
-
-// Batched tier (fps_batch_body.h): the pruned tier's slots and boxes, several samples per arg-max exchange.
-// P = slots per updater thread (kBtUT of them), GS slots per group
-template <int P, int GS>
-__global__ __launch_bounds__(kBtT) void fps_batch_kernel(int n, int m, int Q, const float *__restrict__ xyz,
-                                                         int *__restrict__ out, float *__restrict__ out_xyz)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    fps_batch_body<P, GS, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
-}
-
-// Ragged batch on the pruned and batched tiers (pn2_farthest_point_sample_ragged_variant). The slice rule of
-// fps_reg_ragged_kernel carries over unchanged, because both bodies take (n, m, Q, cloud, xyz, ...) like the register body: the
-// workgroup hands the body its own slab as cloud 0 with n = n_c, Q = ceil(n_c / 512) and -- with counts -- m = m_c. The template
-// (P, GS), the thread count and the LDS bytes come from the padded n: NS = threads * P >= 512 ceil(n / 512) >= 512 Q_c, so every
-// tie rank of the slice has a slot and fps_pruned_prologue deals the items i >= n_c as padding items at point 0's position (value
-// 0, key low word 0); rows at or beyond n_c are never addressed (k = i < n ? i : 0 there). A cloud may now be ONE point in 8192
-// slots, where dense input fills at least half of a template: DESIGN.md 4.11 goes through the prologue, COLLECT, the picker's
-// uncounted loop, the equal-keys rule, the value-0 tail, the slow-batch clock and the pruned tier's skipped reduction on such
-// clouds, and through the termination of every wait inside the workgroup (tests/test_fps_batch_padding_model.py is the CPU
-// model). n_c, m_c and Q_c are block-uniform scalars, so every wave of the workgroup -- the picker included -- executes the
-// barriers of the same chain. COUNTS: npoints is read and rows m_c .. m-1 are filled as in fps_reg_ragged_kernel (index 0
-// and xyz[c, 0]; disjoint from the body's rows, so no barrier stands in between).
-template <int P, int GS, bool COUNTS, class... Pk>
-__global__ __launch_bounds__(kPrT) void fps_pruned_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
-                                                                 const int *__restrict__ npoints, int *__restrict__ out,
-                                                                 float *__restrict__ out_xyz, Pk... pk)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int c = blockIdx.x;
-    const FpsSlab<Pk...> slab(c, n, lengths, pk...);
-    const int nc = slab.count;
-    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
-    const int Qc = (nc + kRefThreads - 1) / kRefThreads;
-    const float *__restrict__ src = xyz + slab.row * 3;
-    int *__restrict__ dst = out + (size_t)c * m;
-    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
-    fps_pruned_body<P, GS, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
-    if constexpr (sizeof...(Pk) != 0) fps_global_rows<kPrT>(mc, slab.base, dst);
-    if (COUNTS) fps_ragged_fill<kPrT>(mc, m, src, dst, dxyz);
-}
-
-template <int P, int GS, bool COUNTS, class... Pk>
-__global__ __launch_bounds__(kBtT) void fps_batch_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
-                                                                const int *__restrict__ npoints, int *__restrict__ out,
-                                                                float *__restrict__ out_xyz, Pk... pk)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int c = blockIdx.x;
-    const FpsSlab<Pk...> slab(c, n, lengths, pk...);
-    const int nc = slab.count;
-    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
-    const int Qc = (nc + kRefThreads - 1) / kRefThreads;
-    const float *__restrict__ src = xyz + slab.row * 3;
-    int *__restrict__ dst = out + (size_t)c * m;
-    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
-    fps_batch_body<P, GS, false>(nc, mc, Qc, 0, src, dst, dxyz, nullptr, smem);
-    if constexpr (sizeof...(Pk) != 0) fps_global_rows<kBtT>(mc, slab.base, dst);
-    if (COUNTS) fps_ragged_fill<kBtT>(mc, m, src, dst, dxyz);
+    const FpsSlab s = fps_slab<COUNTS>(blockIdx.x, n, m, xyz, lengths, npoints, out, out_xyz, pk...);
+    Tier::body(s.nc, s.mc, (s.nc + kRefThreads - 1) / kRefThreads, s.src, s.dst, s.dxyz, smem);
+    if constexpr (sizeof...(Pk) != 0) fps_global_rows<Tier::threads>(s.mc, s.base, s.dst);
+    if (COUNTS) fps_ragged_fill<Tier::threads>(s.mc, m, s.src, s.dst, s.dxyz);
 }
 
 // ---------------------------------------------------------------------------
@@ -414,7 +337,7 @@ __global__ __launch_bounds__(1024) void fps_generic_kernel(int n, int m, const f
 }
 
 // Ragged batch beyond the register tiers (pn2_farthest_point_sample_large_ragged, kernel 1): the slice rule of
-// fps_reg_ragged_kernel on the global-memory body. Slabs addressed with the padded n and m, the body run with n_c and m_c: every
+// fps_ragged_kernel on the global-memory body. Slabs addressed with the padded n and m, the body run with n_c and m_c: every
 // loop over the cloud is k < n_c (rows at or beyond n_c of the cloud and of temp are never addressed), a thread without a point
 // contributes key 0, below every real key, and the one barrier per round sits in the loop j < m_c of workgroup-uniform bound.
 // COUNTS: rows m_c .. m-1 are fps_ragged_fill's.
@@ -424,39 +347,46 @@ __global__ __launch_bounds__(1024) void fps_generic_ragged_kernel(int n, int m, 
                                                                   int *__restrict__ out, float *__restrict__ out_xyz)
 {
     const int c = blockIdx.x;
-    const int nc = cloud_count(lengths, c, n);
-    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
-    const float *__restrict__ src = xyz + (size_t)c * n * 3;
-    int *__restrict__ dst = out + (size_t)c * m;
-    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
-    fps_generic_body(nc, mc, src, temp + (size_t)c * n, dst, dxyz);
-    if (COUNTS) fps_ragged_fill<1024>(mc, m, src, dst, dxyz);
+    const FpsSlab s = fps_slab<COUNTS>(c, n, m, xyz, lengths, npoints, out, out_xyz);
+    fps_generic_body(s.nc, s.mc, s.src, temp + (size_t)c * n, s.dst, s.dxyz);
+    if (COUNTS) fps_ragged_fill<1024>(s.mc, m, s.src, s.dst, s.dxyz);
 }
 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+// the dense kernel of a tier
 template <int T, int P, bool LDSXYZ>
-static int launch_reg(int b, int n, int m, int Q, const float *inp, int *out, float *oxyz, hipStream_t st)
+static auto fps_dense_kernel(RegTier<T, P, LDSXYZ>) { return fps_reg_kernel<T, P, LDSXYZ>; }
+template <int P, int GS>
+static auto fps_dense_kernel(PrunedTier<P, GS>) { return fps_pruned_kernel<P, GS>; }
+template <int P, int GS>
+static auto fps_dense_kernel(BatchTier<P, GS>) { return fps_batch_kernel<P, GS>; }
+
+// The three launches, each a function of the tier's tag (fps_with_tier). Dense: one workgroup per cloud of n points.
+static auto fps_dense_launch(int b, int n, int m, int Q, const float *inp, int *out, float *oxyz, hipStream_t st)
 {
-    const size_t lds = 256 + (LDSXYZ ? sizeof(float4) : sizeof(int)) * (size_t)T * P;
-    auto kern = fps_reg_kernel<T, P, LDSXYZ>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    if (int rc = launch(kern, dim3(b), dim3(T), lds, st, n, m, Q, inp, out, oxyz)) return rc;
-    return PN2_OK;
+    return [=](auto tier) { return launch_lds(fps_dense_kernel(tier), dim3(b), dim3(tier.threads), tier.lds, st, n, m, Q, inp, out, oxyz); };
 }
 
-// npoints: NULL = m samples from every cloud; else the per-cloud sample counts (COUNTS)
-template <int T, int P, bool LDSXYZ>
-static int launch_reg_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                             hipStream_t st, const Packed *pk = nullptr)
+// Ragged: npoints NULL = m samples from every cloud; else the per-cloud sample counts (COUNTS)
+static auto fps_ragged_launch(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
+                              hipStream_t st)
 {
-    const size_t lds = 256 + (LDSXYZ ? sizeof(float4) : sizeof(int)) * (size_t)T * P;
-    if (pk)                                                // the packed mode: lengths and npoints are NULL and never read
-        return launch_lds(fps_reg_ragged_kernel<T, P, LDSXYZ, false, Packed>, dim3(b), dim3(T), lds, st, n, m, inp, lengths, npoints, out,
-                          oxyz, *pk);
-    return launch_lds(npoints ? fps_reg_ragged_kernel<T, P, LDSXYZ, true> : fps_reg_ragged_kernel<T, P, LDSXYZ, false>, dim3(b), dim3(T),
-                      lds, st, n, m, inp, lengths, npoints, out, oxyz);
+    return [=](auto tier) {
+        using Tier = decltype(tier);
+        return launch_lds(npoints ? fps_ragged_kernel<Tier, true> : fps_ragged_kernel<Tier, false>, dim3(b), dim3(tier.threads), tier.lds, st,
+                          n, m, inp, lengths, npoints, out, oxyz);
+    };
+}
+
+// Packed: n is nmax; lengths and npoints are NULL and never read
+static auto fps_packed_launch(int b, int n, int m, const float *inp, Packed pk, int *out, float *oxyz, hipStream_t st)
+{
+    return [=](auto tier) {
+        return launch_lds(fps_ragged_kernel<decltype(tier), false, Packed>, dim3(b), dim3(tier.threads), tier.lds, st, n, m, inp, nullptr,
+                          nullptr, out, oxyz, pk);
+    };
 }
 
 // the global-memory kernel with counts, for the ragged entry of fps_large.hip (declared there). npoints: NULL = m samples from
@@ -468,134 +398,36 @@ int fps_launch_generic_ragged(int b, int n, int m, const float *inp, const int *
                   lengths, npoints, temp, out, oxyz);
 }
 
-template <int P, int GS>
-static int launch_pruned(int b, int n, int m, int Q, const float *inp, int *out, float *oxyz, hipStream_t st)
-{
-    const size_t lds = fps_pruned_lds_bytes(P);
-    auto kern = fps_pruned_kernel<P, GS>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3(b), dim3(kPrT), lds, st, n, m, Q, inp, out, oxyz);
-}
-
-static bool pruned_covers(int ranks) { return ranks > 2048 && ranks <= 8192; }
-
-static int fps_launch_pruned(int b, int n, int m, const float *inp, int *out, float *oxyz, hipStream_t st)
-{
-    const int Q = (n + kRefThreads - 1) / kRefThreads;
-    const int ranks = kRefThreads * Q;
-    if (!pruned_covers(ranks)) return PN2_E_ARG;
-    // 32 groups either way: 16 slots per thread in groups of 2, 32 in groups of 4
-    if (ranks <= 4096) return launch_pruned<16, 2>(b, n, m, Q, inp, out, oxyz, st);
-    return launch_pruned<32, 4>(b, n, m, Q, inp, out, oxyz, st);
-}
-
-template <int P, int GS>
-static int launch_batch(int b, int n, int m, int Q, const float *inp, int *out, float *oxyz, hipStream_t st)
-{
-    const size_t lds = fps_batch_lds_bytes(P);
-    auto kern = fps_batch_kernel<P, GS>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3(b), dim3(kBtT), lds, st, n, m, Q, inp, out, oxyz);
-}
-
-static int fps_launch_batch(int b, int n, int m, const float *inp, int *out, float *oxyz, hipStream_t st)
-{
-    const int Q = (n + kRefThreads - 1) / kRefThreads;
-    const int ranks = kRefThreads * Q;
-    if (!fps_batch_covers(ranks)) return PN2_E_ARG;
-    if constexpr (kBtUT == 512) {
-        if (ranks <= 1024) return launch_batch<2, 2>(b, n, m, Q, inp, out, oxyz, st);   // 8 groups, one per updater wave
-        if (ranks <= 2048) return launch_batch<4, 2>(b, n, m, Q, inp, out, oxyz, st);   // 16 groups
-    } else if (ranks <= 2048) {
-        return PN2_E_ARG;
-    }
-    // 32 groups either way: at 512 updater threads 8 slots per thread in groups of 2 or 16 in groups of 4
-    if (ranks <= 4096) return launch_batch<4096 / kBtUT, 4096 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, Q, inp, out, oxyz, st);
-    return launch_batch<8192 / kBtUT, 8192 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, Q, inp, out, oxyz, st);
-}
-
-// The ragged wrappers of the two tiers: template, thread count and LDS bytes from the padded n, exactly as fps_launch_pruned /
-// fps_launch_batch choose them. npoints: NULL = m samples from every cloud.
-template <int P, int GS>
-static int launch_pruned_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                                hipStream_t st, const Packed *pk = nullptr)
-{
-    if (pk)
-        return launch_lds(fps_pruned_ragged_kernel<P, GS, false, Packed>, dim3(b), dim3(kPrT), fps_pruned_lds_bytes(P), st, n, m, inp,
-                          lengths, npoints, out, oxyz, *pk);
-    return launch_lds(npoints ? fps_pruned_ragged_kernel<P, GS, true> : fps_pruned_ragged_kernel<P, GS, false>, dim3(b), dim3(kPrT),
-                      fps_pruned_lds_bytes(P), st, n, m, inp, lengths, npoints, out, oxyz);
-}
-
-static int fps_launch_pruned_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                                    hipStream_t st, const Packed *pk = nullptr)
-{
-    const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
-    if (!pruned_covers(ranks)) return PN2_E_ARG;
-    if (ranks <= 4096) return launch_pruned_ragged<16, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
-    return launch_pruned_ragged<32, 4>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
-}
-
-template <int P, int GS>
-static int launch_batch_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                               hipStream_t st, const Packed *pk = nullptr)
-{
-    if (pk)
-        return launch_lds(fps_batch_ragged_kernel<P, GS, false, Packed>, dim3(b), dim3(kBtT), fps_batch_lds_bytes(P), st, n, m, inp, lengths,
-                          npoints, out, oxyz, *pk);
-    return launch_lds(npoints ? fps_batch_ragged_kernel<P, GS, true> : fps_batch_ragged_kernel<P, GS, false>, dim3(b), dim3(kBtT),
-                      fps_batch_lds_bytes(P), st, n, m, inp, lengths, npoints, out, oxyz);
-}
-
-static int fps_launch_batch_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, int *out, float *oxyz,
-                                   hipStream_t st, const Packed *pk = nullptr)
-{
-    const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
-    if (!fps_batch_covers(ranks)) return PN2_E_ARG;
-    if constexpr (kBtUT == 512) {
-        if (ranks <= 1024) return launch_batch_ragged<2, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
-        if (ranks <= 2048) return launch_batch_ragged<4, 2>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
-    } else if (ranks <= 2048) {
-        return PN2_E_ARG;
-    }
-    if (ranks <= 4096)
-        return launch_batch_ragged<4096 / kBtUT, 4096 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
-    return launch_batch_ragged<8192 / kBtUT, 8192 / kBtUT / (32 / (kBtUT / 64))>(b, n, m, inp, lengths, npoints, out, oxyz, st, pk);
-}
-
-constexpr int kMaxLdsSlots = 8192;     // 256 B + 16 B per rank slot <= 160 KiB
-constexpr int kMaxRegPoints = 16384;
-
-template <int T, bool LDSXYZ>
-static int dispatch_p(int P, int b, int n, int m, int Q, const float *inp, int *out, float *oxyz, hipStream_t st)
+// Every (T, P) of the register tier, for the tuning harness (bench.py --fps-sweep; pn2_farthest_point_sample_ex): fps_choose
+// names six of them.
+template <int T, bool LDSXYZ, class F>
+static int with_reg_p(int P, F f)
 {
     switch (P) {
-    case 1: return launch_reg<T, 1, LDSXYZ>(b, n, m, Q, inp, out, oxyz, st);
-    case 2: return launch_reg<T, 2, LDSXYZ>(b, n, m, Q, inp, out, oxyz, st);
-    case 4: return launch_reg<T, 4, LDSXYZ>(b, n, m, Q, inp, out, oxyz, st);
-    case 8: return launch_reg<T, 8, LDSXYZ>(b, n, m, Q, inp, out, oxyz, st);
-    case 16: return launch_reg<T, 16, LDSXYZ>(b, n, m, Q, inp, out, oxyz, st);
+    case 1: return f(RegTier<T, 1, LDSXYZ>{});
+    case 2: return f(RegTier<T, 2, LDSXYZ>{});
+    case 4: return f(RegTier<T, 4, LDSXYZ>{});
+    case 8: return f(RegTier<T, 8, LDSXYZ>{});
+    case 16: return f(RegTier<T, 16, LDSXYZ>{});
     case 32:
-        if constexpr (T <= 512) return launch_reg<T, 32, LDSXYZ>(b, n, m, Q, inp, out, oxyz, st);
+        if constexpr (T <= 512) return f(RegTier<T, 32, LDSXYZ>{});
         break;
     default: break;
     }
     return PN2_E_ARG;
 }
 
-static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-
-// force a (T,P) configuration: used by the tuning harness (bench.py --fps-sweep)
 static int fps_launch_config(int T, int P, int b, int n, int m, const float *inp, int *out, float *oxyz,
                              hipStream_t st)
 {
     const int Q = (n + kRefThreads - 1) / kRefThreads;
     if ((long long)T * P < (long long)kRefThreads * Q) return PN2_E_ARG;
     const bool lds = (long long)T * P <= kMaxLdsSlots;
+    const auto go = fps_dense_launch(b, n, m, Q, inp, out, oxyz, st);
     switch (T) {
-    case 256: return lds ? dispatch_p<256, true>(P, b, n, m, Q, inp, out, oxyz, st) : dispatch_p<256, false>(P, b, n, m, Q, inp, out, oxyz, st);
-    case 512: return lds ? dispatch_p<512, true>(P, b, n, m, Q, inp, out, oxyz, st) : dispatch_p<512, false>(P, b, n, m, Q, inp, out, oxyz, st);
-    case 1024: return lds ? dispatch_p<1024, true>(P, b, n, m, Q, inp, out, oxyz, st) : dispatch_p<1024, false>(P, b, n, m, Q, inp, out, oxyz, st);
+    case 256: return lds ? with_reg_p<256, true>(P, go) : with_reg_p<256, false>(P, go);
+    case 512: return lds ? with_reg_p<512, true>(P, go) : with_reg_p<512, false>(P, go);
+    case 1024: return lds ? with_reg_p<1024, true>(P, go) : with_reg_p<1024, false>(P, go);
     default: return PN2_E_ARG;
     }
 }
@@ -603,10 +435,7 @@ static int fps_launch_config(int T, int P, int b, int n, int m, const float *inp
 template <int P>
 static int launch_cond(int b, int n, int m, int Q, const float *inp, int *out, float *oxyz, int *flags, hipStream_t st)
 {
-    const size_t lds = 256 + sizeof(float4) * (size_t)256 * P;
-    auto kern = fps_reg_cond_kernel<P>;
-    if (int rc = allow_dynamic_lds(kern, lds)) return rc;
-    return launch(kern, dim3(b), dim3(256), lds, st, n, m, Q, inp, out, oxyz, flags);
+    return launch_lds(fps_reg_cond_kernel<P>, dim3(b), dim3(256), RegTier<256, P, true>::lds, st, n, m, Q, inp, out, oxyz, flags);
 }
 
 }  // namespace pn2
@@ -631,16 +460,9 @@ static int fps_entry(int b, int n, int m, const float *inp, float *temp, int *ou
         if (int rc = launch(fps_generic_kernel, dim3(b), dim3(1024), 0, st, n, m, inp, temp, out, out_xyz)) return rc;
         return PN2_OK;
     }
-    const int Q = (n + kRefThreads - 1) / kRefThreads;
-    const int ranks = kRefThreads * Q;
-    if (variant == PN2_FPS_BATCH || (variant == PN2_FPS_AUTO && fps_batch_pays(ranks, m))) return fps_launch_batch(b, n, m, inp, out, out_xyz, st);
-    if (variant == PN2_FPS_PRUNED || (variant == PN2_FPS_AUTO && fps_pruned_pays(ranks, m)))
-        return fps_launch_pruned(b, n, m, inp, out, out_xyz, st);
-    // default geometry (measured, scripts/fps_prod_lab.hip, ns per round at n = 1024/2048/4096/8192):
-    // 256 threads with the packed distance update 273/312/402/585, 512 threads (scalar) 288/326/393/552
-    const int T = ranks <= 2048 ? 256 : 512;
-    const int P = next_pow2((ranks + T - 1) / T);
-    return fps_launch_config(T, P, b, n, m, inp, out, out_xyz, st);
+    FpsChoice c;
+    if (int rc = fps_choose(variant, n, m, c)) return rc;
+    return fps_with_tier(c, fps_dense_launch(b, n, m, c.Q, inp, out, out_xyz, st));
 }
 
 extern "C" int pn2_farthest_point_sample(int b, int n, int m, const float *inp, float *temp, int *out, void *stream)
@@ -667,9 +489,7 @@ extern "C" int pn2_farthest_point_sample_variant(int variant, int b, int n, int 
 
 // Ragged batch: cloud c is inp[c, :lengths[c]] of a padded (b, n, 3) tensor, lengths (b) int32 on the device, never read by
 // the host. Result per cloud = pn2_farthest_point_sample_gather on the slice, tie rule included, whatever the tier. The tier is
-// chosen as fps_entry chooses it, by the size rule on the PADDED n and m (the host knows no other): the batched tier, the pruned
-// tier, else -- and for PN2_FPS_FULL -- the register tier in the geometry fps_entry picks at the padded n. PN2_E_TOO_LARGE
-// beyond 16384 points. out_xyz may be NULL.
+// fps_choose's at the PADDED n and m, as for dense input. PN2_E_TOO_LARGE beyond 16384 points. out_xyz may be NULL.
 // pk: the packed mode (pn2_farthest_point_sample_packed): n is nmax, the flat array's extent is pk->total, lengths / npoints NULL.
 static int fps_ragged_entry(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, bool counts, int *out,
                             float *out_xyz, void *stream, int variant = PN2_FPS_AUTO, const pn2::Packed *pk = nullptr)
@@ -681,23 +501,10 @@ static int fps_ragged_entry(int b, int n, int m, const float *inp, const int *le
     if (n > kMaxRegPoints) return PN2_E_TOO_LARGE;
     if ((pk ? (long long)pk->total : (long long)b * n) * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
     hipStream_t st = as_stream(stream);
-    const int ranks = kRefThreads * ((n + kRefThreads - 1) / kRefThreads);
-    if (variant == PN2_FPS_BATCH || (variant == PN2_FPS_AUTO && fps_batch_pays(ranks, m)))
-        return fps_launch_batch_ragged(b, n, m, inp, lengths, npoints, out, out_xyz, st, pk);
-    if (variant == PN2_FPS_PRUNED || (variant == PN2_FPS_AUTO && fps_pruned_pays(ranks, m)))
-        return fps_launch_pruned_ragged(b, n, m, inp, lengths, npoints, out, out_xyz, st, pk);
-    const int T = ranks <= 2048 ? 256 : 512;
-    const int P = next_pow2((ranks + T - 1) / T);
-#define PN2_FPS_RAGGED(TT, PP) \
-    if (T == TT && P == PP) return launch_reg_ragged<TT, PP, ((long long)TT * PP <= kMaxLdsSlots)>(b, n, m, inp, lengths, npoints, out, out_xyz, st, pk)
-    PN2_FPS_RAGGED(256, 2);
-    PN2_FPS_RAGGED(256, 4);
-    PN2_FPS_RAGGED(256, 8);
-    PN2_FPS_RAGGED(512, 8);
-    PN2_FPS_RAGGED(512, 16);
-    PN2_FPS_RAGGED(512, 32);
-#undef PN2_FPS_RAGGED
-    return PN2_E_ARG;
+    FpsChoice c;
+    if (int rc = fps_choose(variant, n, m, c)) return rc;
+    if (pk) return fps_with_tier(c, fps_packed_launch(b, n, m, inp, *pk, out, out_xyz, st));
+    return fps_with_tier(c, fps_ragged_launch(b, n, m, inp, lengths, npoints, out, out_xyz, st));
 }
 
 extern "C" int pn2_farthest_point_sample_ragged(int b, int n, int m, const float *inp, const int *lengths, int *out, float *out_xyz,
@@ -760,12 +567,12 @@ extern "C" int pn2_farthest_point_sample_ordered(int b, int n, int m, const floa
     hipStream_t st = as_stream(stream);
     int *flags = static_cast<int *>(ws);
     if (int rc = launch_verify(b, n, m, inp, flags, st)) return rc;
-    const int Q = (n + kRefThreads - 1) / kRefThreads;
-    const int P = next_pow2((kRefThreads * Q + 255) / 256);
-    switch (P) {
-    case 2: return launch_cond<2>(b, n, m, Q, inp, out, out_xyz, flags, st);
-    case 4: return launch_cond<4>(b, n, m, Q, inp, out, out_xyz, flags, st);
-    case 8: return launch_cond<8>(b, n, m, Q, inp, out, out_xyz, flags, st);
+    FpsChoice c;                                           // the register tier's geometry at n <= 2048: 256 threads
+    if (int rc = fps_choose(PN2_FPS_FULL, n, m, c)) return rc;
+    switch (c.T == 256 ? c.P : 0) {
+    case 2: return launch_cond<2>(b, n, m, c.Q, inp, out, out_xyz, flags, st);
+    case 4: return launch_cond<4>(b, n, m, c.Q, inp, out, out_xyz, flags, st);
+    case 8: return launch_cond<8>(b, n, m, c.Q, inp, out, out_xyz, flags, st);
     default: return PN2_E_ARG;
     }
 }

@@ -322,6 +322,47 @@ __device__ __forceinline__ void fps_reg_body(int n, int m, int Q, int cloud, con
     fps_gather_epilogue<T>(m, src, dst, dxyz);
 }
 
+// ---- ragged and packed batches: the prologue of the ragged FPS kernels (fps.hip; fps_large.hip spells the same rule out) ---------
+// First row and point count of cloud c. Padded layout: row c n and lengths[c]. Packed layout (a Packed behind the kernel's
+// argument list, pn2_device.h): rows offsets[c] .. offsets[c + 1] - 1 of the flat array, n = nmax, lengths unused; coordinates are
+// read as scalars, so a slab may start at any row. base: what the packed mode's global_idx adds to the finished indices.
+__device__ __forceinline__ void fps_slab_rows(int c, int n, const int *__restrict__ lengths, size_t &row, int &count, int &base)
+{
+    row = (size_t)c * n;
+    count = cloud_count(lengths, c, n);
+    base = 0;
+}
+__device__ __forceinline__ void fps_slab_rows(int c, int n, const int *, size_t &row, int &count, int &base, Packed pk)
+{
+    const int s = cloud_start(pk, c);
+    row = (size_t)s;
+    count = cloud_count(pk, c, s, n);
+    base = pk.global_idx ? s : 0;
+}
+
+// What the workgroup of cloud c works on: nc points at src, mc samples (COUNTS: npoints[c], else m; npoints is never read
+// without COUNTS) to dst and -- unless NULL -- dxyz, the cloud's rows of the dense (b, m) and (b, m, 3) outputs. All counts come
+// through cloud_count (pn2_device.h): clamped, block-uniform scalars.
+struct FpsSlab {
+    int nc, mc, base;
+    const float *src;
+    int *dst;
+    float *dxyz;
+};
+template <bool COUNTS, class... Pk>
+__device__ __forceinline__ FpsSlab fps_slab(int c, int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
+                                            const int *__restrict__ npoints, int *__restrict__ out, float *__restrict__ out_xyz, Pk... pk)
+{
+    size_t row;
+    int nc, base;
+    fps_slab_rows(c, n, lengths, row, nc, base, pk...);
+    const int mc = COUNTS ? cloud_count(npoints, c, m) : m;
+    const float *src = xyz + row * 3;
+    int *dst = out + (size_t)c * m;
+    float *dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
+    return {nc, mc, base, src, dst, dxyz};
+}
+
 // The rows m_c .. m-1 of a cloud that yields m_c < m samples (the ragged kernels with counts, fps.hip and fps_large.hip): sample
 // 0 repeated, i.e. index 0 and the cloud's first point -- nothing is read back.
 template <int T>

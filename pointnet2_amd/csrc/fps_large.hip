@@ -389,7 +389,9 @@ __global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const flo
 // Ragged batch (pn2_farthest_point_sample_large_ragged): cloud c holds n_c = lengths[c] <= n points in its padded (n, 3) slab and
 // -- with COUNTS -- yields m_c = npoints[c] <= m samples (both counts: cloud_count, pn2_device.h). The workgroup hands the body its
 // own slabs, all addressed with the PADDED n and m, and runs it with n = n_c, m = m_c: the cloud is computed exactly as if it were
-// alone (the slice rule of fps_reg_ragged_kernel, fps.hip; the chain is prefix-consistent, so m_c samples are the first m_c of m).
+// alone (the slice rule of fps_ragged_kernel, fps.hip; the chain is prefix-consistent, so m_c samples are the first m_c of m).
+// The prologue is fps_slab's (fps_body.h) written out: through that function the compiler orders this kernel's scalar address
+// arithmetic differently (profiles/fps_one_ladder/README.md), and the kernels' instruction text is kept as it was.
 // Rows m_c .. m-1 are fps_ragged_fill's: index 0 and xyz[c, 0], disjoint from the body's rows, so no barrier stands in between.
 // What the body assumed of kernel-uniform extents, per workgroup:
 //   * the return at m_c == 1 is a return from the body before its first barrier; the fill follows it;

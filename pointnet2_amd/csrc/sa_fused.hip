@@ -52,9 +52,7 @@
 // launch against 419 with roles by block index (the ticket winners are the workgroups closest to the
 // counter's memory channel, i.e. the producers end up bunched on one XCD). Not shipped.
 #include "ball_query_body.h"
-#include "fps_body.h"
-#include "fps_pruned_body.h"
-#include "fps_batch_body.h"
+#include "fps_tier.h"
 
 #include <limits.h>
 
@@ -334,13 +332,12 @@ static int sample_and_group_common(int b, int n, int m, float radius, int nsampl
         return pn2_query_ball_group_xyz(b, n, m, radius, nsample, xyz, new_xyz, subtract_centroid, idx, pts_cnt, grouped_xyz, stream);
     }
     // producers: the kd-grouped chain where it exists (4096 / 8192 rank slots) and the chain is long enough to pay for the
-    // kd build (the rule of pn2_farthest_point_sample, fps.hip)
+    // kd build: the tier rule of pn2_farthest_point_sample (fps_choose, PN2_E_ARG for a forced tier outside its rank-slot
+    // envelope). The template's P stays this launch's own, slots per thread of its 512-thread workgroups.
     if (fps_variant < PN2_FPS_AUTO || fps_variant > PN2_FPS_BATCH) return PN2_E_ARG;
-    if (fps_variant == PN2_FPS_PRUNED && P != 8 && P != 16) return PN2_E_ARG;
-    if (fps_variant == PN2_FPS_BATCH && !fps_batch_covers(ranks)) return PN2_E_ARG;
-    const int tier = fps_variant == PN2_FPS_BATCH || (fps_variant == PN2_FPS_AUTO && fps_batch_pays(ranks, m))     ? 2
-                     : fps_variant == PN2_FPS_PRUNED || (fps_variant == PN2_FPS_AUTO && fps_pruned_pays(ranks, m)) ? 1
-                                                                                                                    : 0;
+    FpsChoice choice;
+    if (int rc = fps_choose(fps_variant, n, m, choice)) return rc;
+    const int tier = choice.tier;
 #define PN2_FUSED_CASE(PP, LL, PR)                                                                                     \
     if (P == PP && lpq == LL && tier == PR)                                                                            \
         return launch_fused<PP, LL, PR>(b, n, m, Q, nsample, thr, radius, tag, xyz, w, fps_idx, new_xyz, idx, pts_cnt,   \

@@ -101,7 +101,8 @@ def set_fps_variant(variant=FPS_AUTO):
     """Applies to calls with `lengths=` / `npoints=` (ragged batches) too: every tier runs on each cloud's slice and gives the
     slice rule's result. With FPS_AUTO those calls go through pn2_farthest_point_sample_ragged / _ragged_counts, which apply
     the library's size rule to the padded n and npoint; a forced tier goes through pn2_farthest_point_sample_ragged_variant
-    (ValueError where the padded n is outside the tier's rank-slot envelope, as for dense input)."""
+    (ValueError where the padded n is outside the tier's rank-slot envelope, as for dense input). One preparation of the
+    counts serves all three (_fps_ragged)."""
     require(int(variant) in (FPS_AUTO, FPS_FULL, FPS_PRUNED, FPS_BATCH), "fps variant must be 0 (auto), 1 (full), 2 (pruned) or 3 (batched)")
     _FPS_VARIANT[0] = int(variant)
 
@@ -198,46 +199,34 @@ def set_fps_ragged_large(flag=False):
     _FPS_RAGGED_LARGE[0] = flag
 
 
-def _fps_ragged_large(m, inp, lengths, out, new_xyz, op, npoints):
+def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
+    """Both ragged forms, the counts prepared once: without lengths every cloud holds all n points (an array of full counts made on
+    the device), without npoints every cloud yields m samples (NULL). A tier forced with set_fps_variant applies up to 16384
+    padded points."""
     b, n, _ = inp.shape
-    require(n <= FPS_RAGGED_LARGE_MAX_POINTS, "%s with lengths supports at most %d points per (padded) cloud, got %d"
-            % (op, FPS_RAGGED_LARGE_MAX_POINTS, n))
+    large = _FPS_RAGGED_LARGE[0] and not _FPS_VARIANT[0] and n > FPS_RAGGED_MAX_POINTS
+    limit = FPS_RAGGED_LARGE_MAX_POINTS if large else FPS_RAGGED_MAX_POINTS
+    require(n <= limit, "%s with lengths supports at most %d points per (padded) cloud, got %d" % (op, limit, n))
     dev = inp.device
-    lib = _C.lib()
     lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
     cnts = ragged_lengths(npoints, b, dev, "npoints") if npoints is not None else None
+    lib = _C.lib()
+    if not large:
+        with on_device(dev):
+            tail = (ptr(out), ptr(new_xyz), stream_ptr(dev))
+            if _FPS_VARIANT[0]:             # a forced tier: one entry for both forms
+                rc = lib.pn2_farthest_point_sample_ragged_variant(_FPS_VARIANT[0], b, n, m, ptr(inp), ptr(lens), ptr(cnts), *tail)
+            elif cnts is None:              # the two entries that are its PN2_FPS_AUTO case (the modules' call census pins them)
+                rc = lib.pn2_farthest_point_sample_ragged(b, n, m, ptr(inp), ptr(lens), *tail)
+            else:
+                rc = lib.pn2_farthest_point_sample_ragged_counts(b, n, m, ptr(inp), ptr(lens), ptr(cnts), *tail)
+            _C.check(rc, op)
+        return
     kernel = {None: 0, True: 2, False: 1}[_FPS_LARGE[0]]
     ws = torch.empty((lib.pn2_fps_large_ws_bytes(b, n),), dtype=torch.uint8, device=dev)    # per call, on the padded n
     with on_device(dev):
         _C.check(lib.pn2_farthest_point_sample_large_ragged_ex(kernel, 256, b, n, m, ptr(inp), ptr(lens), ptr(cnts), ptr(ws), ptr(out),
                                                                ptr(new_xyz), stream_ptr(dev)), op)
-
-
-def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
-    b, n, _ = inp.shape
-    if _FPS_RAGGED_LARGE[0] and not _FPS_VARIANT[0] and n > FPS_RAGGED_MAX_POINTS:
-        return _fps_ragged_large(m, inp, lengths, out, new_xyz, op, npoints)
-    require(n <= FPS_RAGGED_MAX_POINTS, "%s with lengths supports at most %d points per (padded) cloud, got %d"
-            % (op, FPS_RAGGED_MAX_POINTS, n))
-    dev = inp.device
-    if _FPS_VARIANT[0]:                     # a forced tier: one entry for both forms (npoints NULL = npoint samples from every cloud)
-        lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
-        cnts = ragged_lengths(npoints, b, dev, "npoints") if npoints is not None else None
-        with on_device(dev):
-            _C.check(_C.lib().pn2_farthest_point_sample_ragged_variant(_FPS_VARIANT[0], b, n, m, ptr(inp), ptr(lens), ptr(cnts), ptr(out),
-                                                                       ptr(new_xyz), stream_ptr(dev)), op)
-        return
-    if npoints is None:
-        lens = ragged_lengths(lengths, b, dev)
-        with on_device(dev):
-            _C.check(_C.lib().pn2_farthest_point_sample_ragged(b, n, m, ptr(inp), ptr(lens), ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
-        return
-    # per-cloud sample counts; without lengths every cloud holds all n points (an array of full counts made on the device)
-    lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
-    cnts = ragged_lengths(npoints, b, dev, "npoints")
-    with on_device(dev):
-        _C.check(_C.lib().pn2_farthest_point_sample_ragged_counts(b, n, m, ptr(inp), ptr(lens), ptr(cnts), ptr(out), ptr(new_xyz),
-                                                                  stream_ptr(dev)), op)
 
 
 def _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, out, want_xyz, op):
@@ -259,6 +248,53 @@ def _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, 
     return out, new_xyz
 
 
+def _fps(npoint, inp, op, want_xyz, out=None, ordered=None, lengths=None, npoints=None, offsets=None, max_points=None, global_idx=False):
+    """The one body of farthest_point_sample and farthest_point_sample_gather -> idx (b, npoint), new_xyz (b, npoint, 3) or None.
+    op: the operator's name in messages; want_xyz: gather the samples too; out: optional preallocated idx; ordered: None = follow
+    inp's hint, True / False = force / forbid the checked short cut."""
+    require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
+    if offsets is not None:
+        out, new_xyz = _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, out, want_xyz, op)
+        return out, (mark_fps_ordered(new_xyz) if want_xyz else None)
+    if lengths is not None:
+        lengths = lengths_for(lengths, inp)
+    if npoints is not None:
+        npoints = lengths_for(npoints, inp, "npoints")
+    if ordered is None:                                    # (before detach(): the hint is an attribute of the caller's tensor object)
+        ordered = isinstance(inp, torch.Tensor) and ordered_hint(inp, npoint)      # the previous level's samples: checked short cut
+    inp = f32(inp.detach() if isinstance(inp, torch.Tensor) else inp, "inp")
+    require(inp.dim() == 3 and inp.shape[2] == 3, "FarthestPointSample expects (batch_size,num_points,3) inp shape")
+    b, n, _ = inp.shape
+    require(n > 0 or b == 0, "FarthestPointSample expects at least one point per cloud")
+    m = int(npoint)
+    dev = inp.device
+    out = out_or_empty(out, (b, m), torch.int32, dev)
+    new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if want_xyz else None
+    if lengths is not None or npoints is not None:
+        _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints)
+        return out, (mark_fps_ordered(new_xyz) if want_xyz and npoints is None else new_xyz)   # fill rows break the farthest-point order
+    lib = _C.lib()
+    if _fps_large_takes(lib, b, n, m):
+        _fps_large(lib, b, n, m, inp, out, new_xyz, op)
+        return out, (mark_fps_ordered(new_xyz) if want_xyz else None)
+    tf = lib.pn2_fps_temp_floats(b, n)
+    temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None   # allocate_temp, tf_sampling.cpp:115
+    with on_device(dev):
+        if ordered and b > 0 and n <= 16384:
+            st = stream_ptr(dev)
+            ws = ordered_workspace(lib, dev, st, b)
+            _C.check(lib.pn2_farthest_point_sample_ordered(b, n, m, ptr(inp), ptr(out), ptr(new_xyz), ptr(ws), st),
+                     "farthest_point_sample_ordered")
+        elif _FPS_VARIANT[0]:
+            _C.check(lib.pn2_farthest_point_sample_variant(_FPS_VARIANT[0], b, n, m, ptr(inp), ptr(temp), ptr(out), ptr(new_xyz),
+                                                           stream_ptr(dev)), op)
+        elif want_xyz:
+            _C.check(lib.pn2_farthest_point_sample_gather(b, n, m, ptr(inp), ptr(temp), ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
+        else:
+            _C.check(lib.pn2_farthest_point_sample(b, n, m, ptr(inp), ptr(temp), ptr(out), stream_ptr(dev)), op)
+    return out, (mark_fps_ordered(new_xyz) if want_xyz else None)
+
+
 def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoints=None, offsets=None, max_points=None, global_idx=False):
     """Fused farthest_point_sample + gather_point (pointnet_util.py:40 in one launch).
     offsets / max_points: a PACKED batch -- inp is one flat (total, 3) array, cloud i is inp[offsets[i] : offsets[i + 1]]
@@ -278,46 +314,7 @@ def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoint
     ordered: None = follow inp's hint (above), True / False = force / forbid the checked short cut for input in
     farthest-point order (same results either way).
     """
-    require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
-    if offsets is not None:
-        out, new_xyz = _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, None, True, "farthest_point_sample_gather")
-        return out, mark_fps_ordered(new_xyz)
-    if lengths is not None:
-        lengths = lengths_for(lengths, inp)
-    if npoints is not None:
-        npoints = lengths_for(npoints, inp, "npoints")
-    if ordered is None:                                    # (before detach(): the hint is an attribute of the caller's tensor object)
-        ordered = isinstance(inp, torch.Tensor) and ordered_hint(inp, npoint)
-    inp = f32(inp.detach() if isinstance(inp, torch.Tensor) else inp, "inp")
-    require(inp.dim() == 3 and inp.shape[2] == 3, "FarthestPointSample expects (batch_size,num_points,3) inp shape")
-    b, n, _ = inp.shape
-    require(n > 0 or b == 0, "FarthestPointSample expects at least one point per cloud")
-    m = int(npoint)
-    dev = inp.device
-    out = torch.empty((b, m), dtype=torch.int32, device=dev)
-    new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=dev)
-    if lengths is not None or npoints is not None:
-        _fps_ragged(m, inp, lengths, out, new_xyz, "farthest_point_sample_gather", npoints)
-        return out, (mark_fps_ordered(new_xyz) if npoints is None else new_xyz)   # fill rows break the farthest-point order
-    lib = _C.lib()
-    if _fps_large_takes(lib, b, n, m):
-        _fps_large(lib, b, n, m, inp, out, new_xyz, "farthest_point_sample_gather")
-        return out, mark_fps_ordered(new_xyz)
-    tf = lib.pn2_fps_temp_floats(b, n)
-    temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None
-    with on_device(dev):
-        if ordered and b > 0 and n <= 16384:
-            st = stream_ptr(dev)
-            ws = ordered_workspace(lib, dev, st, b)
-            _C.check(lib.pn2_farthest_point_sample_ordered(b, n, m, ptr(inp), ptr(out), ptr(new_xyz), ptr(ws), st),
-                     "farthest_point_sample_ordered")
-        elif _FPS_VARIANT[0]:
-            _C.check(lib.pn2_farthest_point_sample_variant(_FPS_VARIANT[0], b, n, m, ptr(inp), ptr(temp), ptr(out), ptr(new_xyz),
-                                                           stream_ptr(dev)), "farthest_point_sample_gather")
-        else:
-            _C.check(lib.pn2_farthest_point_sample_gather(b, n, m, ptr(inp), ptr(temp), ptr(out), ptr(new_xyz),
-                                                          stream_ptr(dev)), "farthest_point_sample_gather")
-    return out, mark_fps_ordered(new_xyz)
+    return _fps(npoint, inp, "farthest_point_sample_gather", True, None, ordered, lengths, npoints, offsets, max_points, global_idx)
 
 
 def farthest_point_sample(npoint, inp, out=None, lengths=None, npoints=None, offsets=None, max_points=None, global_idx=False):
@@ -330,39 +327,4 @@ def farthest_point_sample(npoint, inp, out=None, lengths=None, npoints=None, off
     kernel tf_sampling_g.cu:105-170 (tie rule: smallest (k mod 512, k)).
     out: optional preallocated (b, npoint) i32 result.
     """
-    require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
-    if offsets is not None:
-        return _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, out, False, "farthest_point_sample")[0]
-    if lengths is not None:
-        lengths = lengths_for(lengths, inp)
-    if npoints is not None:
-        npoints = lengths_for(npoints, inp, "npoints")
-    hinted = isinstance(inp, torch.Tensor) and ordered_hint(inp, npoint)      # the previous level's samples: checked short cut
-    inp = f32(inp.detach() if isinstance(inp, torch.Tensor) else inp, "inp")
-    require(inp.dim() == 3 and inp.shape[2] == 3, "FarthestPointSample expects (batch_size,num_points,3) inp shape")
-    b, n, _ = inp.shape
-    require(n > 0 or b == 0, "FarthestPointSample expects at least one point per cloud")
-    m = int(npoint)
-    dev = inp.device
-    out = out_or_empty(out, (b, m), torch.int32, dev)
-    if lengths is not None or npoints is not None:
-        _fps_ragged(m, inp, lengths, out, None, "farthest_point_sample", npoints)
-        return out
-    lib = _C.lib()
-    if _fps_large_takes(lib, b, n, m):
-        _fps_large(lib, b, n, m, inp, out, None, "farthest_point_sample")
-        return out
-    tf = lib.pn2_fps_temp_floats(b, n)
-    temp = torch.empty((tf,), dtype=torch.float32, device=dev) if tf > 0 else None   # allocate_temp, tf_sampling.cpp:115
-    with on_device(dev):
-        if hinted and b > 0 and n <= 16384:
-            st = stream_ptr(dev)
-            _C.check(lib.pn2_farthest_point_sample_ordered(b, n, m, ptr(inp), ptr(out), None, ptr(ordered_workspace(lib, dev, st, b)),
-                                                           st), "farthest_point_sample_ordered")
-        elif _FPS_VARIANT[0]:
-            _C.check(lib.pn2_farthest_point_sample_variant(_FPS_VARIANT[0], b, n, m, ptr(inp), ptr(temp), ptr(out), None,
-                                                           stream_ptr(dev)), "farthest_point_sample")
-        else:
-            _C.check(lib.pn2_farthest_point_sample(b, n, m, ptr(inp), ptr(temp), ptr(out), stream_ptr(dev)),
-                     "farthest_point_sample")
-    return out
+    return _fps(npoint, inp, "farthest_point_sample", False, out, None, lengths, npoints, offsets, max_points, global_idx)[0]
