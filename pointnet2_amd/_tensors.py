@@ -90,6 +90,26 @@ def full_counts(b, n, dev):
     return torch.full((b,), int(n), dtype=torch.int32, device=dev)
 
 
+def pair_counts(lengths1, lengths2, b, n, m, dev, names=("lengths1", "lengths2"), both=False):
+    """THE rule for which counted entry a call with optional per-cloud counts on its two sides takes:
+    -> (suffix of the C entry, lens1, lens2, behind1, behind2): the count arrays as int32 tensors on `dev` (None where the entry
+    takes none; the caller holds them until its launch is enqueued) and their pointers as the tuples that splice into the
+    entry's argument list behind the first and behind the second coordinate argument.
+      neither given                      ""              no counts
+      lengths1 only                      "_ragged"       lens1
+      lengths2, with or without lengths1 "_ragged_pair"  lens1 (full_counts of n for a dense first side) and lens2
+    both: the caller's entry has no unpaired variant (the level entries of sa_mlp.py): always the last row, a dense second side
+    of m rows gets full_counts too. names: what the two arguments are called in messages."""
+    if lengths2 is None and not both:
+        if lengths1 is None:
+            return "", None, None, (), ()
+        lens1 = ragged_lengths(lengths1, b, dev, names[0])
+        return "_ragged", lens1, None, (lens1.data_ptr(),), ()
+    lens1 = ragged_lengths(lengths1, b, dev, names[0]) if lengths1 is not None else full_counts(b, n, dev)
+    lens2 = ragged_lengths(lengths2, b, dev, names[1]) if lengths2 is not None else full_counts(b, m, dev)
+    return "_ragged_pair", lens1, lens2, (lens1.data_ptr(),), (lens2.data_ptr(),)
+
+
 def check_lengths(lengths, n, b=None):
     """Validate the per-cloud point counts of a ragged batch padded to n points: an int32 / int64 tensor (or a sequence) of
     shape (b,) with 1 <= lengths[i] <= n. Raises ValueError. This is the ONE place that looks at the values, and it

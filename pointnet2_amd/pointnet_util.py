@@ -26,6 +26,28 @@ from .geometry import FPGeometry, SAGeometry
 from .index_plan import index_plan
 
 
+def _grouped_input(xyz, points, idx, new_xyz, use_xyz, xyz_first, plan=None, grouped_xyz=None):
+    """The input of a level's layer stack behind idx (:45-50; the MSG module's :179-184): group xyz and subtract the centroid,
+    group the features, concatenate in the level's channel order -- xyz_first: [xyz, features], the single-scale module's (:50);
+    False: features FIRST, the MSG module's (:184). grouped_xyz: a fused launch has grouped and centred xyz already (xyz and
+    new_xyz are not looked at). plan: the index plan of idx for both gathers' backward.
+    -> new_points (b, m, nsample, C), grouped_xyz (b, m, nsample, 3)"""
+    if grouped_xyz is None:
+        grouped_xyz = group_point(xyz, idx, plan=plan) - new_xyz.unsqueeze(2)
+    if points is None:
+        return grouped_xyz, grouped_xyz
+    grouped_points = group_point(points, idx, plan=plan)
+    if use_xyz:
+        grouped_points = torch.cat([grouped_xyz, grouped_points] if xyz_first else [grouped_points, grouped_xyz], dim=-1)
+    return grouped_points, grouped_xyz
+
+
+def _valid_row_list(valid):
+    """The valid rows of a (b, m) mask as the (total,) row list of index_select / _scatter_rows. nonzero() SYNCHRONISES (the host
+    reads how many there are): only the compacting "unfused_ragged" paths come here."""
+    return valid.reshape(-1).nonzero().squeeze(1)
+
+
 def _sample_and_group_packed(npoint, radius, nsample, xyz, points, use_xyz, offsets, max_points):
     """sample_and_group on a packed batch: packed FPS + gather and packed ball query + group (two launches, no host
     synchronisation, capturable), indices GLOBAL -- rows of the flat array --, so the features are group_point on the flat view
@@ -36,11 +58,9 @@ def _sample_and_group_packed(npoint, radius, nsample, xyz, points, use_xyz, offs
     idx, _, grouped_xyz = query_ball_group_xyz(radius, ns, xyz, new_xyz, True, offsets=offs, max_points=nmax, global_idx=True)
     if points is not None:
         require(points.dim() == 2 and points.shape[0] == total, "sample_and_group: with offsets, points is (total, channel)")
-        grouped_points = group_point(points.reshape(1, total, points.shape[1]), idx.view(1, b * m, ns)).view(b, m, ns, points.shape[1])
-        new_points = torch.cat([grouped_xyz, grouped_points], dim=-1) if use_xyz else grouped_points
-    else:
-        new_points = grouped_xyz
-    return new_xyz, new_points, idx, grouped_xyz
+        points = points.reshape(1, total, points.shape[1])
+    new_points, _ = _grouped_input(None, points, idx.view(1, b * m, ns), None, use_xyz, True, grouped_xyz=grouped_xyz.view(1, b * m, ns, 3))
+    return new_xyz, new_points.view(b, m, ns, new_points.shape[3]), idx, grouped_xyz
 
 
 def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=True, fused=None, lengths=None, npoints=None, offsets=None,
@@ -77,33 +97,24 @@ def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=Tr
         lengths = lengths_for(lengths, xyz)
     if npoints is not None:
         npoints = lengths_for(npoints, xyz, "npoints")
+    grouped_xyz = None
     if fused and not knn:
         _, new_xyz, idx, _, grouped_xyz = sample_and_group_xyz(npoint, radius, nsample, xyz, True, lengths=lengths,
                                                                npoints=npoints)   # :40-46
-    elif fused:
-        _, new_xyz = farthest_point_sample_gather(npoint, xyz, lengths=lengths, npoints=npoints)   # :40 in one launch
     else:
-        fps_idx = farthest_point_sample(npoint, xyz, lengths=lengths, npoints=npoints)
-        new_xyz = gather_point(xyz, fps_idx)                                  # :40
-        if npoints is None:
-            new_xyz = mark_fps_ordered(new_xyz)
-    if fused and not knn:
-        pass
-    elif knn:
-        _, idx = knn_point(nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)           # :42
-        grouped_xyz = group_point(xyz, idx) - new_xyz.unsqueeze(2)
-    else:
-        idx, _ = query_ball_point(radius, nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)   # :44
-        grouped_xyz = group_point(xyz, idx)                                   # :45
-        grouped_xyz = grouped_xyz - new_xyz.unsqueeze(2)                      # :46 translation normalisation
-    if points is not None:
-        grouped_points = group_point(points, idx)                             # :48
-        if use_xyz:
-            new_points = torch.cat([grouped_xyz, grouped_points], dim=-1)     # :50 xyz FIRST
+        if fused:
+            _, new_xyz = farthest_point_sample_gather(npoint, xyz, lengths=lengths, npoints=npoints)   # :40 in one launch
         else:
-            new_points = grouped_points
-    else:
-        new_points = grouped_xyz
+            fps_idx = farthest_point_sample(npoint, xyz, lengths=lengths, npoints=npoints)
+            new_xyz = gather_point(xyz, fps_idx)                              # :40
+            if npoints is None:
+                new_xyz = mark_fps_ordered(new_xyz)
+        if knn:
+            _, idx = knn_point(nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)           # :42
+        else:
+            idx, _ = query_ball_point(radius, nsample, xyz, new_xyz, lengths1=lengths, lengths2=npoints)   # :44
+    # :45-50 (translation normalisation, xyz FIRST); the fused launch has done :45-46
+    new_points, grouped_xyz = _grouped_input(xyz, points, idx, new_xyz, use_xyz, True, grouped_xyz=grouped_xyz)
     return new_xyz, new_points, idx, grouped_xyz
 
 
@@ -453,12 +464,7 @@ class PointnetSAModule(nn.Module):
             return new_xyz, self._post(out), idx
         if path == "fused":
             return new_xyz, self._post(sa_mlp.sa_mlp_pool(xyz, new_xyz, points, idx, self._packed(xyz.device), self.pooling)), idx
-        grouped_xyz = group_point(xyz, idx, plan=plan) - new_xyz.unsqueeze(2)   # :45-46
-        if points is not None:
-            grouped_points = group_point(points, idx, plan=plan)                 # :48
-            new_points = torch.cat([grouped_xyz, grouped_points], dim=-1) if self.use_xyz else grouped_points   # :50
-        else:
-            new_points = grouped_xyz
+        new_points, grouped_xyz = _grouped_input(xyz, points, idx, new_xyz, self.use_xyz, True, plan)   # :45-50
         return self._stack_and_pool(new_xyz, new_points, idx, grouped_xyz)
 
     def _forward_all(self, xyz, points, mode):
@@ -509,7 +515,7 @@ class PointnetSAModule(nn.Module):
             x = _masked_pool(self.mlp(new_points.permute(0, 3, 1, 2)), valid, dists, self.pooling)
         else:
             self.last_path = "unfused_ragged"
-            rows = valid.reshape(-1).nonzero().squeeze(1)                       # (total,): synchronises
+            rows = _valid_row_list(valid)
             c = new_points.shape[3]
             pv = new_points.reshape(b * n, c).index_select(0, rows)             # (total, C)
             y = self.mlp(pv.t().reshape(1, c, -1, 1))                            # statistics over the valid rows of all clouds
@@ -556,13 +562,8 @@ class PointnetSAModule(nn.Module):
             return new_xyz, out, g.idx
         self.last_path = "unfused_ragged"
         new_xyz, idx, plan = g.new_xyz_for(xyz), g.idx, getattr(g, "plan", None)
-        grouped_xyz = group_point(xyz, idx, plan=plan) - new_xyz.unsqueeze(2)   # :45-46
-        if points is not None:
-            grouped_points = group_point(points, idx, plan=plan)                 # :48
-            new_points = torch.cat([grouped_xyz, grouped_points], dim=-1) if self.use_xyz else grouped_points   # :50
-        else:
-            new_points = grouped_xyz
-        rows = valid.reshape(-1).nonzero().squeeze(1)                           # (total,): synchronises
+        new_points, grouped_xyz = _grouped_input(xyz, points, idx, new_xyz, self.use_xyz, True, plan)   # :45-50
+        rows = _valid_row_list(valid)
         ns = idx.shape[2]
         pv = new_points.reshape(b * m, ns, new_points.shape[3]).index_select(0, rows).unsqueeze(0)    # (1, total, nsample, C)
         gv = grouped_xyz.reshape(b * m, ns, 3).index_select(0, rows).unsqueeze(0)
@@ -718,11 +719,7 @@ class PointnetSAModuleMSG(nn.Module):
         # training with npoints=: one fused node with a row mask per scale instead of the compacting layer-by-layer path; see
         # PointnetSAModule.fused_ragged_train. last_path "fused_train_ragged". Opt-in.
         self.fused_ragged_train = False
-        # eval() with lengths= / npoints= (/ lengths1=): the fused inference kernels with the counts inside
-        # (pn2_*_ragged, include/pn2ops.h "ragged inference") instead of the dense kernels on every row and a torch.where behind
-        # them: padding rows are neither gathered nor computed where a kernel can skip them, a level without a geometry is ONE
-        # C call; last_path "fused_ragged". Where the dense fused route would run (_fused_ok / _fused_kind), max pooling. Opt-in.
-        self.fused_ragged_eval = False
+        self.fused_ragged_eval = False  # see PointnetSAModule: eval() with counts on the fused inference kernels (opt-in)
         self.last_path = None
         self._pack_cache = {}
 
@@ -821,24 +818,15 @@ class PointnetSAModuleMSG(nn.Module):
         scales = None
         if g is not None:
             new_xyz = g.new_xyz_for(xyz)               # (re-gathered differentiably when xyz needs a gradient: tf_sampling.py:43-47)
-            scales = [(idx, group_point(xyz, idx) - new_xyz.unsqueeze(2)) for idx in g.idx]     # :179-180
+            scales = [(idx, None) for idx in g.idx]
         elif fused:
             new_xyz, scales = self._group_scales(xyz, points is not None)
         else:
             new_xyz = mark_fps_ordered(gather_point(xyz, farthest_point_sample(self.npoint, xyz)))   # :173
         outs = []
         for si, (radius, nsample, mlp) in enumerate(zip(self.radius_list, self.nsample_list, self.mlps)):
-            if fused:
-                idx, grouped_xyz = scales[si]
-            else:
-                idx, _ = query_ball_point(radius, nsample, xyz, new_xyz)       # :178
-                grouped_xyz = group_point(xyz, idx) - new_xyz.unsqueeze(2)     # :179-180
-            if points is not None:
-                grouped = group_point(points, idx)                             # :182
-                if self.use_xyz:
-                    grouped = torch.cat([grouped, grouped_xyz], dim=-1)        # :184 features FIRST
-            else:
-                grouped = grouped_xyz
+            idx, grouped_xyz = scales[si] if fused else (query_ball_point(radius, nsample, xyz, new_xyz)[0], None)   # :178
+            grouped, _ = _grouped_input(xyz, points, idx, new_xyz, self.use_xyz, False, grouped_xyz=grouped_xyz)   # :179-184
             x = mlp(grouped.permute(0, 3, 1, 2))
             outs.append(x.max(dim=3)[0])                                        # :193
         return new_xyz, torch.cat(outs, dim=1).permute(0, 2, 1).contiguous()    # :195
@@ -868,13 +856,10 @@ class PointnetSAModuleMSG(nn.Module):
             return new_xyz, torch.cat(outs, dim=2)
         self.last_path = "unfused_ragged"
         new_xyz = g.new_xyz_for(xyz)
-        rows = valid.reshape(-1).nonzero().squeeze(1)                           # (total,): synchronises
+        rows = _valid_row_list(valid)
         outs = []
         for idx, mlp in zip(g.idx, self.mlps):
-            grouped = group_point(xyz, idx) - new_xyz.unsqueeze(2)              # :179-180
-            if points is not None:
-                feats = group_point(points, idx)                                # :182
-                grouped = torch.cat([feats, grouped], dim=-1) if self.use_xyz else feats   # :184 features FIRST
+            grouped, _ = _grouped_input(xyz, points, idx, new_xyz, self.use_xyz, False)       # :179-184
             gv = grouped.reshape(b * m, idx.shape[2], grouped.shape[3]).index_select(0, rows)          # (total, nsample, C)
             outs.append(mlp(gv.permute(2, 0, 1).unsqueeze(0)).max(dim=3)[0][0].t())                # (total, C')  :193
         yv = torch.cat(outs, dim=1)                                             # :195
@@ -928,11 +913,7 @@ class PointnetFPModule(nn.Module):
         # 0.64 ms and 288 -> 231 MB peak; part_seg FP3 0.525-0.530 -> 0.521-0.524 ms, which is within the spread of the medians
         # -- NOT faster there -- and 158 -> 132 MB peak. Folding it into the size rule is a later change.
         self.fused_ragged_node = False
-        # eval() with lengths= / npoints= (/ lengths1=): the fused inference kernels with the counts inside
-        # (pn2_*_ragged, include/pn2ops.h "ragged inference") instead of the dense kernels on every row and a torch.where behind
-        # them: padding rows are neither gathered nor computed where a kernel can skip them, a level without a geometry is ONE
-        # C call; last_path "fused_ragged". Where the dense fused route would run (_fused_ok / _fused_kind), max pooling. Opt-in.
-        self.fused_ragged_eval = False
+        self.fused_ragged_eval = False  # see PointnetSAModule: eval() with counts on the fused inference kernels (opt-in)
         self.reuse_buffers = False     # eval: keep the level's result / scratch tensors and overwrite them on the next call
         self.last_path = None
         self._pack_cache = None
@@ -1071,12 +1052,11 @@ class PointnetFPModule(nn.Module):
         self.last_path = "unfused_ragged"
         interpolated = three_interpolate(points2, g.idx, _inverse_distance_weights(g.dist), plan=getattr(g, "plan", None))   # :212-216
         x = torch.cat([interpolated, points1], dim=2) if points1 is not None else interpolated   # :219
-        rows = valid.reshape(-1).nonzero().squeeze(1)                           # (total,): synchronises
+        rows = _valid_row_list(valid)
         xv = x.reshape(b * n, x.shape[2]).index_select(0, rows)                 # the valid rows of all clouds, (total, C)
         y = self.mlp(xv.t().unsqueeze(0).unsqueeze(3))                          # (1, C, total, 1): statistics over the valid rows
         yv = y[0, :, :, 0].t()
-        out = torch.zeros((b * n, yv.shape[1]), dtype=yv.dtype, device=dev).index_copy(0, rows, yv)
-        return out.reshape(b, n, yv.shape[1])
+        return _scatter_rows(yv, rows, b * n).reshape(b, n, yv.shape[1])
 
     def _forward_packed(self, xyz1, xyz2, points1, points2, offsets1, max_points1):
         """forward() with a PACKED unknown side: xyz1 (total, 3), points1 (total, c1) or None, cloud i = rows

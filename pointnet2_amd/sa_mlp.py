@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _C
-from ._tensors import f32, full_counts, i32, on_device, ptr, ragged_lengths, require, same_device, stream_ptr
+from ._tensors import f32, i32, on_device, pair_counts, ptr, ragged_lengths, require, same_device, stream_ptr
 
 
 _RESIDENT_VARIANT = 0
@@ -397,8 +397,7 @@ def sa_level_ragged(npoint, radius, nsample, xyz, points, packed, lengths, npoin
     require(m > 0 and ns > 0 and float(radius) > 0, "npoint, nsample and radius must be positive")
     require(ns == packed.nsample or _same_kernel(packed, ns), "weights were packed for another kernel (nsample %d)" % packed.nsample)
     dev = same_device(xyz, packed.wp) if points is None else same_device(xyz, points, packed.wp)
-    lengths = full_counts(b, n, dev) if lengths is None else ragged_lengths(lengths, b, dev)
-    npoints = full_counts(b, m, dev) if npoints is None else ragged_lengths(npoints, b, dev, "npoints")
+    _, lengths, npoints, _, _ = pair_counts(lengths, npoints, b, n, m, dev, ("lengths", "npoints"), both=True)
     lib = _C.lib()
     key = ("ragged", b, n, m, ns, cfeat, packed.widths, dev)
     if buffers is not None and buffers.key == key:
@@ -436,8 +435,7 @@ def fp_level_ragged(xyz1, xyz2, points1, points2, packed, lengths1, lengths2=Non
     require(c2 == packed.c2 and c1 == packed.c1, "packed FP MLP expects (%d, %d) channels, got (%d, %d)" % (packed.c2, packed.c1, c2, c1))
     dev = same_device(xyz1, xyz2, points2, packed.wp)
     require(lengths1 is not None, "fp_level_ragged needs lengths1")
-    lengths1 = ragged_lengths(lengths1, b, dev, "lengths1")
-    lengths2 = full_counts(b, m, dev) if lengths2 is None else ragged_lengths(lengths2, b, dev, "lengths2")
+    _, lengths1, lengths2, _, _ = pair_counts(lengths1, lengths2, b, n, m, dev, both=True)
     lib = _C.lib()
     key = ("ragged", b, n, m, c2, c1, tuple(packed.widths), packed.kind, dev)
     if buffers is not None and buffers.key == key:

@@ -10,8 +10,8 @@ NoGradient (:21, :32).
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, f32, full_counts, i32, lengths_for, on_device, packed_args, ptr, ragged_lengths, require, same_device,
-                       scatter_grad, stream_ptr)
+from ._tensors import (out_or_empty, f32, i32, lengths_for, on_device, packed_args, pair_counts, ptr, require, same_device, scatter_grad,
+                       stream_ptr)
 
 
 # Ball-query kernel choice passed with every call (pn2_query_ball_group_xyz_ex): 0 automatic, 1 sweep,
@@ -25,34 +25,67 @@ def set_ball_query_kernel(kernel=0, cells_qpb=0):
     _BQ_KERNEL[0], _BQ_KERNEL[1] = int(kernel), int(cells_qpb)
 
 
-def pair_counts(lengths1, lengths2, b, n, m, dev):
-    """Both count arrays of a two-sided ragged call as the *_ragged_pair entries take them: the side given as None becomes an
-    array of full counts made on the device (no synchronisation)."""
-    lens1 = ragged_lengths(lengths1, b, dev, "lengths1") if lengths1 is not None else full_counts(b, n, dev)
-    lens2 = ragged_lengths(lengths2, b, dev, "lengths2") if lengths2 is not None else full_counts(b, m, dev)
-    return lens1, lens2
+_XYZ1_SHAPE = "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape."
+_XYZ2_SHAPE = "QueryBallPoint expects (batch_size, npoint, 3) xyz2 shape."
 
 
-def _ball_query_packed(radius, nsample, xyz1, xyz2, offsets, max_points, lengths1, lengths2, global_idx, subtract, idx, cnt, fuse, op):
-    """The packed form of both ball-query operators (pn2_query_ball_group_xyz_packed): xyz1 (total, 3) with offsets (b + 1,) on
-    the device, the queries xyz2 (b, m, 3) dense. idx / cnt: preallocated outputs or None (idx None and fuse: no idx wanted)."""
-    require(lengths2 is None, "%s: a ragged query side (lengths2=) is not offered with offsets" % op)
-    require(isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 and xyz2.shape[2] == 3, "QueryBallPoint expects (batch_size, npoint, 3) xyz2 shape.")
-    b, m, _ = xyz2.shape
-    offs, b, total, nmax = packed_args(offsets, max_points, lengths1, xyz1, op, b=b)    # (before anything else, like lengths_for)
+def _ball_inputs(op, xyz1, xyz2, lengths1, lengths2, offsets=None, max_points=None):
+    """The preamble of every ball-query front, in the order the messages promise (a lengths / offsets complaint comes before a
+    dtype or device complaint), and the counted entry it leads to (pair_counts; "_packed" with offsets: xyz1 (total, 3), the
+    queries dense). -> xyz1, xyz2, device, the entry's extents (b, n, m) -- packed: (b, total, max_points, m) --, then what
+    pair_counts gives: the entry's suffix, the two count arrays (packed: the offsets in the place of the first), their pointers
+    as they splice in behind xyz1 and behind xyz2."""
+    if offsets is not None:
+        if lengths2 is not None:                                  # (a message costs more to format than its check)
+            raise ValueError("%s: a ragged query side (lengths2=) is not offered with offsets" % op)
+        require(isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 and xyz2.shape[2] == 3, _XYZ2_SHAPE)
+        b, m, _ = xyz2.shape
+        offs, b, total, nmax = packed_args(offsets, max_points, lengths1, xyz1, op, b=b)
+        xyz1 = f32(xyz1, "xyz1")
+        xyz2 = f32(xyz2, "xyz2")
+        return xyz1, xyz2, same_device(xyz1, xyz2), (b, total, nmax, m), "_packed", offs, None, (offs.data_ptr(),), ()
+    if lengths1 is not None:
+        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
+    if lengths2 is not None:
+        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
+    shape1, shape2 = xyz1.shape, xyz2.shape
+    require(len(shape1) == 3 and shape1[2] == 3, _XYZ1_SHAPE)
+    require(len(shape2) == 3 and shape2[2] == 3 and shape2[0] == shape1[0], _XYZ2_SHAPE)
     dev = same_device(xyz1, xyz2)
+    b, n, m = shape1[0], shape1[1], shape2[1]
+    return (xyz1, xyz2, dev, (b, n, m)) + pair_counts(lengths1, lengths2, b, n, m, dev)
+
+
+def _ball_query(op, radius, nsample, xyz1, xyz2, lengths1, lengths2, offsets, max_points, global_idx, subtract, fuse, want_idx, out):
+    """The one body of query_ball_point (fuse False) and query_ball_group_xyz (fuse True) on every layout: dense, lengths1,
+    lengths1 / lengths2, offsets. out: preallocated (idx, pts_cnt) or None. -> idx (None unless want_idx), pts_cnt, grouped_xyz
+    (None unless fuse). The entry is pn2_query_ball_group_xyz + pair_counts' suffix / "_packed" / "_ex" for a dense call; a dense
+    query_ball_point with no kernel forced takes the reference operator's own entry, pn2_query_ball_point."""
+    r = float(radius)
+    require(r > 0, "QueryBallPoint expects positive radius")
     ns = int(nsample)
-    if idx is None and not fuse:
-        idx = torch.empty((b, m, ns), dtype=torch.int32, device=dev)
-    if cnt is None:
+    require(ns > 0, "QueryBallPoint expects positive nsample")
+    xyz1, xyz2, dev, extents, entry, _lens1, _lens2, behind1, behind2 = _ball_inputs(op, xyz1, xyz2, lengths1, lengths2, offsets, max_points)
+    b, m = extents[0], extents[-1]
+    if out is None:                                           # (spelled out: two calls less on the path every module takes)
+        idx = torch.empty((b, m, ns), dtype=torch.int32, device=dev) if want_idx else None
         cnt = torch.empty((b, m), dtype=torch.int32, device=dev)
+    else:
+        idx, cnt = out_or_empty(out[0], (b, m, ns), torch.int32, dev, "out[0]"), out_or_empty(out[1], (b, m), torch.int32, dev, "out[1]")
     grouped = torch.empty((b, m, ns, 3), dtype=torch.float32, device=dev) if fuse else None
+    lib = _C.lib()
     with on_device(dev):
-        _C.check(_C.lib().pn2_query_ball_group_xyz_packed(b, total, nmax, m, float(radius), ns, ptr(xyz1), ptr(offs), ptr(xyz2),
-                                                          1 if subtract else 0, 1 if global_idx else 0, ptr(idx), ptr(cnt), ptr(grouped),
-                                                          _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)), op)
+        if not (fuse or entry or _BQ_KERNEL[0] or _BQ_KERNEL[1]):
+            rc = lib.pn2_query_ball_point(b, extents[1], m, r, ns, ptr(xyz1), ptr(xyz2), ptr(idx), ptr(cnt), stream_ptr(dev))
+        else:
+            flags = (1 if subtract else 0,) if offsets is None else (1 if subtract else 0, 1 if global_idx else 0)
+            rc = getattr(lib, "pn2_query_ball_group_xyz" + (entry or "_ex"))(
+                *extents, r, ns, ptr(xyz1), *behind1, ptr(xyz2), *behind2, *flags, ptr(idx), ptr(cnt),
+                ptr(grouped), _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev))
+    if rc:
+        _C.check(rc, op)
     return idx, cnt, grouped
 
 
@@ -72,53 +105,8 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None, lengt
     reference: tf_grouping.py:8-20, op QueryBallPoint tf_grouping.cpp:67-106.
     out: optional preallocated (idx, pts_cnt).
     """
-    require(float(radius) > 0, "QueryBallPoint expects positive radius")
-    require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
-    if offsets is not None:
-        if out is not None:
-            shape = (xyz2.shape[0], xyz2.shape[1]) if isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 else (0, 0)
-            out = (out_or_empty(out[0], shape + (int(nsample),), torch.int32, xyz2.device, "out[0]"),
-                   out_or_empty(out[1], shape, torch.int32, xyz2.device, "out[1]"))
-        return _ball_query_packed(radius, nsample, xyz1, xyz2, offsets, max_points, lengths1, lengths2, global_idx, False,
-                                  out[0] if out is not None else None, out[1] if out is not None else None, False, "query_ball_point")[:2]
-    if lengths1 is not None:
-        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
-    if lengths2 is not None:
-        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
-    xyz1 = f32(xyz1, "xyz1")
-    xyz2 = f32(xyz2, "xyz2")
-    require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
-    require(xyz2.dim() == 3 and xyz2.shape[2] == 3 and xyz2.shape[0] == xyz1.shape[0],
-            "QueryBallPoint expects (batch_size, npoint, 3) xyz2 shape.")
-    dev = same_device(xyz1, xyz2)
-    b, n, _ = xyz1.shape
-    m = xyz2.shape[1]
-    ns = int(nsample)
-    idx = out_or_empty(out[0] if out is not None else None, (b, m, ns), torch.int32, dev, "out[0]")
-    cnt = out_or_empty(out[1] if out is not None else None, (b, m), torch.int32, dev, "out[1]")
-    if lengths2 is not None:
-        lens, lens2 = pair_counts(lengths1, lengths2, b, n, m, dev)
-        with on_device(dev):
-            _C.check(_C.lib().pn2_query_ball_group_xyz_ragged_pair(b, n, m, float(radius), ns, ptr(xyz1), ptr(lens), ptr(xyz2),
-                                                                   ptr(lens2), 0, ptr(idx), ptr(cnt), None, _BQ_KERNEL[0],
-                                                                   _BQ_KERNEL[1], stream_ptr(dev)), "query_ball_point")
-        return idx, cnt
-    if lengths1 is not None:
-        lens = ragged_lengths(lengths1, b, dev, "lengths1")
-        with on_device(dev):
-            _C.check(_C.lib().pn2_query_ball_group_xyz_ragged(b, n, m, float(radius), ns, ptr(xyz1), ptr(lens), ptr(xyz2), 0, ptr(idx),
-                                                              ptr(cnt), None, _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)),
-                     "query_ball_point")
-        return idx, cnt
-    with on_device(dev):
-        if _BQ_KERNEL[0] or _BQ_KERNEL[1]:
-            _C.check(_C.lib().pn2_query_ball_group_xyz_ex(b, n, m, float(radius), ns, ptr(xyz1), ptr(xyz2), 0, ptr(idx),
-                                                          ptr(cnt), None, _BQ_KERNEL[0], _BQ_KERNEL[1],
-                                                          stream_ptr(dev)), "query_ball_point")
-        else:
-            _C.check(_C.lib().pn2_query_ball_point(b, n, m, float(radius), ns, ptr(xyz1), ptr(xyz2), ptr(idx),
-                                                   ptr(cnt), stream_ptr(dev)), "query_ball_point")
-    return idx, cnt
+    return _ball_query("query_ball_point", radius, nsample, xyz1, xyz2, lengths1, lengths2, offsets, max_points, global_idx, False,
+                       False, True, out)[:2]
 
 
 def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None, lengths2=None, offsets=None,
@@ -134,52 +122,8 @@ def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, wa
     offsets / max_points / global_idx: a packed xyz1 (total, 3), see query_ball_point; grouped_xyz is gathered from each cloud's
     own points whatever global_idx is.
     """
-    require(float(radius) > 0, "QueryBallPoint expects positive radius")
-    require(int(nsample) > 0, "QueryBallPoint expects positive nsample")
-    if offsets is not None:
-        idx = None
-        if want_idx and isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3:
-            idx = torch.empty((xyz2.shape[0], xyz2.shape[1], int(nsample)), dtype=torch.int32, device=xyz2.device)
-        return _ball_query_packed(radius, nsample, xyz1, xyz2, offsets, max_points, lengths1, lengths2, global_idx, subtract_centroid,
-                                  idx, None, True, "query_ball_group_xyz")
-    if lengths1 is not None:
-        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
-    if lengths2 is not None:
-        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
-    xyz1 = f32(xyz1, "xyz1")
-    xyz2 = f32(xyz2, "xyz2")
-    require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
-    require(xyz2.dim() == 3 and xyz2.shape[2] == 3 and xyz2.shape[0] == xyz1.shape[0],
-            "QueryBallPoint expects (batch_size, npoint, 3) xyz2 shape.")
-    dev = same_device(xyz1, xyz2)
-    b, n, _ = xyz1.shape
-    m = xyz2.shape[1]
-    ns = int(nsample)
-    idx = torch.empty((b, m, ns), dtype=torch.int32, device=dev) if want_idx else None
-    cnt = torch.empty((b, m), dtype=torch.int32, device=dev)
-    grouped = torch.empty((b, m, ns, 3), dtype=torch.float32, device=dev)
-    if lengths2 is not None:
-        lens, lens2 = pair_counts(lengths1, lengths2, b, n, m, dev)
-        with on_device(dev):
-            _C.check(_C.lib().pn2_query_ball_group_xyz_ragged_pair(b, n, m, float(radius), ns, ptr(xyz1), ptr(lens), ptr(xyz2),
-                                                                   ptr(lens2), 1 if subtract_centroid else 0, ptr(idx), ptr(cnt),
-                                                                   ptr(grouped), _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)),
-                     "query_ball_group_xyz")
-        return idx, cnt, grouped
-    if lengths1 is not None:
-        lens = ragged_lengths(lengths1, b, dev, "lengths1")
-        with on_device(dev):
-            _C.check(_C.lib().pn2_query_ball_group_xyz_ragged(b, n, m, float(radius), ns, ptr(xyz1), ptr(lens), ptr(xyz2),
-                                                              1 if subtract_centroid else 0, ptr(idx), ptr(cnt), ptr(grouped),
-                                                              _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)),
-                     "query_ball_group_xyz")
-        return idx, cnt, grouped
-    with on_device(dev):
-        _C.check(_C.lib().pn2_query_ball_group_xyz_ex(b, n, m, float(radius), ns, ptr(xyz1), ptr(xyz2),
-                                                      1 if subtract_centroid else 0, ptr(idx), ptr(cnt), ptr(grouped),
-                                                      _BQ_KERNEL[0], _BQ_KERNEL[1], stream_ptr(dev)),
-                 "query_ball_group_xyz")
-    return idx, cnt, grouped
+    return _ball_query("query_ball_group_xyz", radius, nsample, xyz1, xyz2, lengths1, lengths2, offsets, max_points, global_idx,
+                       subtract_centroid, True, want_idx, None)
 
 
 def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None,
@@ -201,62 +145,38 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     require(len(radius_list) == len(nsample_list) and 1 <= len(radius_list), "one nsample per radius")
     require(all(r > 0 for r in radius_list), "QueryBallPoint expects positive radius")
     require(all(k > 0 for k in nsample_list), "QueryBallPoint expects positive nsample")
-    if lengths1 is not None:
-        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
-    if lengths2 is not None:
-        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
-    xyz1 = f32(xyz1, "xyz1")
-    xyz2 = f32(xyz2, "xyz2")
-    require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "QueryBallPoint expects (batch_size, ndataset, 3) xyz1 shape.")
-    require(xyz2.dim() == 3 and xyz2.shape[2] == 3 and xyz2.shape[0] == xyz1.shape[0],
-            "QueryBallPoint expects (batch_size, npoint, 3) xyz2 shape.")
-    dev = same_device(xyz1, xyz2)
-    b, n, _ = xyz1.shape
-    m = xyz2.shape[1]
+    xyz1, xyz2, dev, (b, n, m), entry, lens1, lens2, behind1, behind2 = _ball_inputs("query_ball_group_xyz_msg", xyz1, xyz2, lengths1, lengths2)
     ns_count = len(radius_list)
-    lens2 = None
-    if lengths2 is not None:
-        lens, lens2 = pair_counts(lengths1, lengths2, b, n, m, dev)
-    else:
-        lens = ragged_lengths(lengths1, b, dev, "lengths1") if lengths1 is not None else None
-    if ns_count > 4 or n > 8192:                                  # outside the multi-radius kernel's envelope
-        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens, lengths2=lens2)
-                for r, k in zip(radius_list, nsample_list)]
-    # one allocation per dtype, carved into per-scale views (allocations dominate the host time of this call)
-    tot = sum(nsample_list)
-    ibuf = torch.empty((b * m * (tot + ns_count) if want_idx else b * m * ns_count,), dtype=torch.int32, device=dev)
-    gbuf = torch.empty((b * m * tot * 3,), dtype=torch.float32, device=dev)
-    outs, io, go = [], 0, 0
-    for k in nsample_list:
-        idx_k = None
-        if want_idx:
-            idx_k = ibuf[io:io + b * m * k].view(b, m, k)
-            io += b * m * k
-        cnt_k = ibuf[io:io + b * m].view(b, m)
-        io += b * m
-        grp_k = gbuf[go:go + b * m * k * 3].view(b, m, k, 3)
-        go += b * m * k * 3
-        outs.append((idx_k, cnt_k, grp_k))
-    radii = (ctypes.c_float * ns_count)(*radius_list)
-    nss = (ctypes.c_int * ns_count)(*nsample_list)
-    pi = (ctypes.c_void_p * ns_count)(*[ptr(o[0]) for o in outs])
-    pc = (ctypes.c_void_p * ns_count)(*[ptr(o[1]) for o in outs])
-    pg = (ctypes.c_void_p * ns_count)(*[ptr(o[2]) for o in outs])
-    with on_device(dev):
-        if lens2 is not None:
-            rc = _C.lib().pn2_query_ball_group_xyz_msg_ragged_pair(b, n, m, ns_count, radii, nss, ptr(xyz1), ptr(lens), ptr(xyz2),
-                                                                   ptr(lens2), 1 if subtract_centroid else 0, pi, pc, pg,
-                                                                   stream_ptr(dev))
-        elif lens is not None:
-            rc = _C.lib().pn2_query_ball_group_xyz_msg_ragged(b, n, m, ns_count, radii, nss, ptr(xyz1), ptr(lens), ptr(xyz2),
-                                                              1 if subtract_centroid else 0, pi, pc, pg, stream_ptr(dev))
-        else:
-            rc = _C.lib().pn2_query_ball_group_xyz_msg(b, n, m, ns_count, radii, nss, ptr(xyz1), ptr(xyz2),
-                                                       1 if subtract_centroid else 0, pi, pc, pg, stream_ptr(dev))
+    rc = -4                                                       # outside the multi-radius kernel's envelope
+    if ns_count <= 4 and n <= 8192:
+        # one allocation per dtype, carved into per-scale views (allocations dominate the host time of this call)
+        tot = sum(nsample_list)
+        ibuf = torch.empty((b * m * (tot + ns_count) if want_idx else b * m * ns_count,), dtype=torch.int32, device=dev)
+        gbuf = torch.empty((b * m * tot * 3,), dtype=torch.float32, device=dev)
+        outs, io, go = [], 0, 0
+        for k in nsample_list:
+            idx_k = None
+            if want_idx:
+                idx_k = ibuf[io:io + b * m * k].view(b, m, k)
+                io += b * m * k
+            cnt_k = ibuf[io:io + b * m].view(b, m)
+            io += b * m
+            grp_k = gbuf[go:go + b * m * k * 3].view(b, m, k, 3)
+            go += b * m * k * 3
+            outs.append((idx_k, cnt_k, grp_k))
+        radii = (ctypes.c_float * ns_count)(*radius_list)
+        nss = (ctypes.c_int * ns_count)(*nsample_list)
+        pi = (ctypes.c_void_p * ns_count)(*[ptr(o[0]) for o in outs])
+        pc = (ctypes.c_void_p * ns_count)(*[ptr(o[1]) for o in outs])
+        pg = (ctypes.c_void_p * ns_count)(*[ptr(o[2]) for o in outs])
+        with on_device(dev):
+            rc = getattr(_C.lib(), "pn2_query_ball_group_xyz_msg" + entry)(
+                b, n, m, ns_count, radii, nss, ptr(xyz1), *behind1, ptr(xyz2), *behind2,
+                1 if subtract_centroid else 0, pi, pc, pg, stream_ptr(dev))
     if rc == -4:
-        # PN2_E_TOO_LARGE: no LDS geometry fits this combination (e.g. n = 8192 with nsample >= 127 on a later radius);
+        # ... or PN2_E_TOO_LARGE: no LDS geometry fits this combination (e.g. n = 8192 with nsample >= 127 on a later radius);
         # nothing has been launched -- the per-radius operator covers every shape
-        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens, lengths2=lens2)
+        return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens1, lengths2=lens2)
                 for r, k in zip(radius_list, nsample_list)]
     _C.check(rc, "query_ball_group_xyz_msg")
     return outs
@@ -500,11 +420,9 @@ def sample_and_group_xyz(npoint, radius, nsample, xyz, subtract_centroid=True, o
     b, n, _ = xyz.shape
     m, ns = int(npoint), int(nsample)
     dev = xyz.device
-    if npoints is not None:
-        lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
-        return _two_launch_path(m, radius, ns, xyz, subtract_centroid, False, lens, ragged_lengths(npoints, b, dev, "npoints"))
-    if lengths is not None:
-        return _two_launch_path(m, radius, ns, xyz, subtract_centroid, False, ragged_lengths(lengths, b, dev))
+    if lengths is not None or npoints is not None:
+        _, lens, cnts, _, _ = pair_counts(lengths, npoints, b, n, m, dev, ("lengths", "npoints"))
+        return _two_launch_path(m, radius, ns, xyz, subtract_centroid, False, lens, cnts)
     lib = _C.lib()
     ordered = bool(ordered) and ordered_worthwhile(xyz, m)
     if b == 0 or not _OVERLAP[0] or not (b <= 256 and 64 <= n <= 8192 and ns <= 256) or ordered:
@@ -646,42 +564,27 @@ def knn_point(k, xyz1, xyz2, lengths1=None, lengths2=None):
         lengths2 = lengths_for(lengths2, xyz1, "lengths2")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
-    require(xyz1.dim() == 3 and xyz2.dim() == 3 and xyz1.shape[0] == xyz2.shape[0] and
-            xyz1.shape[2] == xyz2.shape[2], "knn_point expects (b,n,c) xyz1 and (b,m,c) xyz2")
-    b, n, c = xyz1.shape
-    m = xyz2.shape[1]
-    require(int(k) > 0, "SelectionSort expects positive k")
-    if lengths2 is not None:
-        require(c == 3 and n <= 14336 and int(k) <= n,
-                "knn_point with lengths2 expects 3-D points, at most 14336 points per (padded) cloud and k <= ndataset")
+    shape1, shape2 = xyz1.shape, xyz2.shape
+    require(len(shape1) == 3 and len(shape2) == 3 and shape1[0] == shape2[0] and shape1[2] == shape2[2],
+            "knn_point expects (b,n,c) xyz1 and (b,m,c) xyz2")
+    b, n, c = shape1
+    m = shape2[1]
+    k = int(k)
+    require(k > 0, "SelectionSort expects positive k")
+    if c == 3 and n <= 14336 and k <= n:
+        # one kernel, no (b, m, n) tensors: the distance row lives in LDS (csrc/topk.hip, pn2_knn_point); counts as a mode of it
         dev = same_device(xyz1, xyz2)
-        lens, lens2 = pair_counts(lengths1, lengths2, b, n, m, dev)
-        val = torch.empty((b, m, int(k)), dtype=torch.float32, device=dev)
-        idx = torch.empty((b, m, int(k)), dtype=torch.int32, device=dev)
+        entry, _lens1, _lens2, behind1, behind2 = pair_counts(lengths1, lengths2, b, n, m, dev)
+        val = torch.empty((b, m, k), dtype=torch.float32, device=dev)
+        idx = torch.empty((b, m, k), dtype=torch.int32, device=dev)
         with on_device(dev):
-            _C.check(_C.lib().pn2_knn_point_ragged_pair(b, n, m, int(k), ptr(xyz1), ptr(lens), ptr(xyz2), ptr(lens2), ptr(val),
-                                                        ptr(idx), stream_ptr(dev)), "knn_point")
+            rc = getattr(_C.lib(), "pn2_knn_point" + entry)(b, n, m, k, ptr(xyz1), *behind1, ptr(xyz2), *behind2, ptr(val), ptr(idx),
+                                                            stream_ptr(dev))
+        if rc:
+            _C.check(rc, "knn_point")
         return val, idx
-    if lengths1 is not None:
-        require(c == 3 and n <= 14336 and int(k) <= n,
-                "knn_point with lengths1 expects 3-D points, at most 14336 points per (padded) cloud and k <= ndataset")
-        dev = same_device(xyz1, xyz2)
-        lens = ragged_lengths(lengths1, b, dev, "lengths1")
-        val = torch.empty((b, m, int(k)), dtype=torch.float32, device=dev)
-        idx = torch.empty((b, m, int(k)), dtype=torch.int32, device=dev)
-        with on_device(dev):
-            _C.check(_C.lib().pn2_knn_point_ragged(b, n, m, int(k), ptr(xyz1), ptr(lens), ptr(xyz2), ptr(val), ptr(idx),
-                                                   stream_ptr(dev)), "knn_point")
-        return val, idx
-    if c == 3 and n <= 14336 and int(k) <= n:
-        # one kernel, no (b, m, n) tensors: the distance row lives in LDS (csrc/topk.hip, pn2_knn_point)
-        dev = same_device(xyz1, xyz2)
-        val = torch.empty((b, m, int(k)), dtype=torch.float32, device=dev)
-        idx = torch.empty((b, m, int(k)), dtype=torch.int32, device=dev)
-        with on_device(dev):
-            _C.check(_C.lib().pn2_knn_point(b, n, m, int(k), ptr(xyz1), ptr(xyz2), ptr(val), ptr(idx), stream_ptr(dev)),
-                     "knn_point")
-        return val, idx
+    require(lengths1 is None and lengths2 is None, "knn_point with %s expects 3-D points, at most 14336 points per (padded) cloud and "
+            "k <= ndataset" % ("lengths2" if lengths2 is not None else "lengths1"))
     diff = xyz1.unsqueeze(1) - xyz2.unsqueeze(2)           # (b, m, n, c)
     sq = diff * diff
     dist = sq[..., 0].clone()

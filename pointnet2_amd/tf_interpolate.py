@@ -10,7 +10,7 @@ gradient w.r.t. `points` only (tf_interpolate.py:29-34); ThreeNN is NoGradient (
 import torch
 
 from . import _C
-from ._tensors import (out_or_empty, f32, full_counts, i32, is_deterministic, lengths_for, on_device, packed_args, ptr, ragged_lengths, require,
+from ._tensors import (out_or_empty, f32, i32, is_deterministic, lengths_for, on_device, packed_args, pair_counts, ptr, ragged_lengths, require,
                        same_device, scatter_grad, seg_workspace, stream_ptr)
 
 
@@ -36,50 +36,40 @@ def three_nn(xyz1, xyz2, out=None, lengths1=None, lengths2=None, offsets1=None, 
     reference: tf_interpolate.py:8-17, op ThreeNN tf_interpolate.cpp:157-187,
     loop threenn_cpu :60-103.
     """
-    if offsets1 is not None:
+    packed = offsets1 is not None
+    if packed:
         require(isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 and xyz2.shape[2] == 3, "ThreeNN expects (b,m,3) xyz2 shape")
         b, m, _ = xyz2.shape
         offs, b, total, nmax = packed_args(offsets1, max_points1, lengths1, xyz1, "three_nn", "offsets1", "max_points1", b=b)
-        xyz1 = f32(xyz1, "xyz1")
-        xyz2 = f32(xyz2, "xyz2")
-        dev = same_device(xyz1, xyz2)
-        lens2 = ragged_lengths(lengths_for(lengths2, xyz2, "lengths2"), b, dev, "lengths2") if lengths2 is not None else None
-        dist = out_or_empty(out[0] if out is not None else None, (total, 3), torch.float32, dev, "out[0]")
-        idx = out_or_empty(out[1] if out is not None else None, (total, 3), torch.int32, dev, "out[1]")
-        with on_device(dev):
-            _C.check(_C.lib().pn2_three_nn_packed(b, total, nmax, m, ptr(xyz1), ptr(offs), ptr(xyz2), ptr(lens2), 1 if global_idx else 0,
-                                                  ptr(dist), ptr(idx), _NN_PACKED_VARIANT[0], stream_ptr(dev)), "three_nn")
-        return dist, idx
-    if lengths1 is not None:
-        lengths1 = lengths_for(lengths1, xyz1, "lengths1")
-    if lengths2 is not None:
-        lengths2 = lengths_for(lengths2, xyz1, "lengths2")
+    else:
+        if lengths1 is not None:
+            lengths1 = lengths_for(lengths1, xyz1, "lengths1")
+        if lengths2 is not None:
+            lengths2 = lengths_for(lengths2, xyz1, "lengths2")
     xyz1 = f32(xyz1, "xyz1")
     xyz2 = f32(xyz2, "xyz2")
-    require(xyz1.dim() == 3 and xyz1.shape[2] == 3, "ThreeNN expects (b,n,3) xyz1 shape")
-    require(xyz2.dim() == 3 and xyz2.shape[2] == 3 and xyz2.shape[0] == xyz1.shape[0],
-            "ThreeNN expects (b,m,3) xyz2 shape")
-    dev = same_device(xyz1, xyz2)
-    b, n, _ = xyz1.shape
-    m = xyz2.shape[1]
-    dist = out_or_empty(out[0] if out is not None else None, (b, n, 3), torch.float32, dev, "out[0]")
-    idx = out_or_empty(out[1] if out is not None else None, (b, n, 3), torch.int32, dev, "out[1]")
-    if lengths2 is not None:
-        lens = ragged_lengths(lengths1, b, dev, "lengths1") if lengths1 is not None else full_counts(b, n, dev)
-        lens2 = ragged_lengths(lengths2, b, dev, "lengths2")
-        with on_device(dev):
-            _C.check(_C.lib().pn2_three_nn_ragged_pair(b, n, m, ptr(xyz1), ptr(lens), ptr(xyz2), ptr(lens2), ptr(dist), ptr(idx), 0,
-                                                       stream_ptr(dev)), "three_nn")
-        return dist, idx
-    if lengths1 is not None:
-        lens = ragged_lengths(lengths1, b, dev, "lengths1")
-        with on_device(dev):
-            _C.check(_C.lib().pn2_three_nn_ragged(b, n, m, ptr(xyz1), ptr(lens), ptr(xyz2), ptr(dist), ptr(idx), 0, stream_ptr(dev)),
-                     "three_nn")
-        return dist, idx
+    if packed:
+        dev = same_device(xyz1, xyz2)
+        lens2 = ragged_lengths(lengths_for(lengths2, xyz2, "lengths2"), b, dev, "lengths2") if lengths2 is not None else None
+        entry, behind1, behind2 = "_packed", (ptr(offs),), (ptr(lens2),)        # (a NULL lens2: a dense known side)
+        extents, rows = (b, total, nmax, m), (total, 3)
+        flag, variant = (1 if global_idx else 0,), (_NN_PACKED_VARIANT[0],)     # the words in front of dist and behind idx
+    else:
+        shape1, shape2 = xyz1.shape, xyz2.shape
+        require(len(shape1) == 3 and shape1[2] == 3, "ThreeNN expects (b,n,3) xyz1 shape")
+        require(len(shape2) == 3 and shape2[2] == 3 and shape2[0] == shape1[0], "ThreeNN expects (b,m,3) xyz2 shape")
+        dev = same_device(xyz1, xyz2)
+        b, n, m = shape1[0], shape1[1], shape2[1]
+        entry, _lens1, _lens2, behind1, behind2 = pair_counts(lengths1, lengths2, b, n, m, dev)
+        extents, rows = (b, n, m), (b, n, 3)
+        flag, variant = (), ((0,) if entry else ())                            # (the counted entries' kernel choice: the library's)
+    dist = out_or_empty(out[0] if out is not None else None, rows, torch.float32, dev, "out[0]")
+    idx = out_or_empty(out[1] if out is not None else None, rows, torch.int32, dev, "out[1]")
     with on_device(dev):
-        _C.check(_C.lib().pn2_three_nn(b, n, m, ptr(xyz1), ptr(xyz2), ptr(dist), ptr(idx), stream_ptr(dev)),
-                 "three_nn")
+        rc = getattr(_C.lib(), "pn2_three_nn" + entry)(*extents, ptr(xyz1), *behind1, ptr(xyz2), *behind2, *flag, ptr(dist), ptr(idx),
+                                                       *variant, stream_ptr(dev))
+    if rc:
+        _C.check(rc, "three_nn")
     return dist, idx
 
 

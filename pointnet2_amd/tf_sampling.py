@@ -11,8 +11,8 @@ ProbSample are NoGradient (:22, :57).
 import torch
 
 from . import _C
-from ._tensors import (det_workspace, f32, full_counts, i32, is_deterministic, lengths_for, on_device, out_or_empty, packed_args, ptr,
-                       ragged_lengths, require, same_device, stream_ptr)
+from ._tensors import (det_workspace, f32, i32, is_deterministic, lengths_for, on_device, out_or_empty, packed_args, pair_counts, ptr,
+                       require, same_device, stream_ptr)
 
 
 def prob_sample(inp, inpr):
@@ -208,8 +208,7 @@ def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
     limit = FPS_RAGGED_LARGE_MAX_POINTS if large else FPS_RAGGED_MAX_POINTS
     require(n <= limit, "%s with lengths supports at most %d points per (padded) cloud, got %d" % (op, limit, n))
     dev = inp.device
-    lens = ragged_lengths(lengths, b, dev) if lengths is not None else full_counts(b, n, dev)
-    cnts = ragged_lengths(npoints, b, dev, "npoints") if npoints is not None else None
+    _, lens, cnts, _, _ = pair_counts(lengths, npoints, b, n, m, dev, ("lengths", "npoints"))
     lib = _C.lib()
     if not large:
         with on_device(dev):

@@ -55,6 +55,19 @@ print("group_point, out=         %.2f us" % host_us(lambda: P.group_point(xyz, i
 d3, i3 = P.three_nn(xyz, q)
 print("three_nn                  %.2f us" % host_us(lambda: P.three_nn(xyz, q)))
 print("three_nn, out=            %.2f us" % host_us(lambda: P.three_nn(xyz, q, out=(d3, i3))))
+# every other front and layout of the neighbour searches: counts / offsets already int32 on the device, as the modules pass them
+len1 = torch.full((b,), n - 3, dtype=torch.int32, device=dev)
+len2 = torch.full((b,), m - 3, dtype=torch.int32, device=dev)
+flat, offs = P.pack_batch(xyz, len1)
+print("query_ball_group_xyz      %.2f us" % host_us(lambda: P.query_ball_group_xyz(0.2, ns, xyz, q)))
+print("ball query, lengths1      %.2f us" % host_us(lambda: P.query_ball_point(0.2, ns, xyz, q, lengths1=len1)))
+print("ball query, pair          %.2f us" % host_us(lambda: P.query_ball_point(0.2, ns, xyz, q, lengths1=len1, lengths2=len2)))
+print("ball query, packed        %.2f us" % host_us(lambda: P.query_ball_point(0.2, ns, flat, q, offsets=offs, max_points=n)))
+print("ball query msg, 2 radii   %.2f us" % host_us(lambda: P.query_ball_group_xyz_msg([0.1, 0.2], [16, ns], xyz, q)))
+print("knn_point                 %.2f us" % host_us(lambda: P.knn_point(ns, xyz, q)))
+print("three_nn, lengths1        %.2f us" % host_us(lambda: P.three_nn(xyz, q, lengths1=len1)))
+print("three_nn, pair            %.2f us" % host_us(lambda: P.three_nn(xyz, q, lengths1=len1, lengths2=len2)))
+print("three_nn, packed          %.2f us" % host_us(lambda: P.three_nn(flat, q, offsets1=offs, max_points1=n)))
 print("torch op for scale (add)  %.2f us" % host_us(lambda: xyz + 1.0))
 
 # ---- one call per level (csrc/levels.hip): host time of an eager SA / FP level of the inference path

@@ -99,6 +99,54 @@ def test_python_wrappers_refuse_a_wrong_lengths_shape():
                 call()
 
 
+def test_operator_fronts_complain_in_the_promised_order():
+    """What a front says when several things are wrong at once, on CPU tensors (every call ends in a complaint before a device
+    is touched): radius and nsample first of all, then a wrong lengths shape (lengths2 included, every counted front), and only
+    then that there is no CPU path."""
+    import pointnet2_amd as P
+    xyz, q, bad, good = torch.zeros(2, 8, 3), torch.zeros(2, 4, 3), [1, 2, 3], [8, 8]
+    for front in (P.query_ball_point, P.query_ball_group_xyz):
+        for kw in ({"lengths1": bad}, {"offsets": [0, 8], "max_points": 8}):
+            with pytest.raises(ValueError, match="positive radius"):
+                front(0.0, 0, xyz, q, **kw)
+            with pytest.raises(ValueError, match="positive nsample"):
+                front(0.2, 0, xyz, q, **kw)
+    with pytest.raises(ValueError, match="positive radius"):
+        P.query_ball_group_xyz_msg([0.2, -1.0], [4, 4], xyz, q, lengths1=bad)
+    with pytest.raises(ValueError, match="positive nsample"):
+        P.query_ball_group_xyz_msg([0.2, 0.3], [4, 0], xyz, q, lengths1=bad)
+    counted = [lambda **kw: P.query_ball_point(0.2, 4, xyz, q, **kw), lambda **kw: P.query_ball_group_xyz(0.2, 4, xyz, q, **kw),
+               lambda **kw: P.query_ball_group_xyz_msg([0.2, 0.3], [4, 4], xyz, q, **kw), lambda **kw: P.knn_point(2, xyz, q, **kw),
+               lambda **kw: P.three_nn(xyz, q, **kw)]
+    for front in counted:
+        with pytest.raises(ValueError, match=r"lengths1 must have shape \(batch_size,\) = \(2,\)"):
+            front(lengths1=bad, lengths2=bad)
+        with pytest.raises(ValueError, match=r"lengths2 must have shape \(batch_size,\) = \(2,\)"):
+            front(lengths1=good, lengths2=bad)
+        with pytest.raises(ValueError, match="xyz1 must live on a ROCm device"):
+            front(lengths1=good, lengths2=good)
+    with pytest.raises(ValueError, match="lengths2=. is not offered with offsets"):
+        P.query_ball_point(0.2, 4, torch.zeros(8, 3), q, offsets=[0, 3, 8], max_points=5, lengths2=good)
+
+
+def test_pair_counts_is_the_rule_for_the_counted_entry():
+    """The one statement of which counted entry a call takes and with which count arrays (host logic; CPU tensors do)."""
+    from pointnet2_amd._tensors import pair_counts
+    cpu, l1, l2 = torch.device("cpu"), torch.tensor([5, 3], dtype=torch.int32), torch.tensor([2, 1], dtype=torch.int32)
+    assert pair_counts(None, None, 2, 5, 4, cpu) == ("", None, None, (), ())
+    suffix, c1, c2, p1, p2 = pair_counts(l1, None, 2, 5, 4, cpu)
+    assert suffix == "_ragged" and c1 is l1 and c2 is None and p1 == (l1.data_ptr(),) and p2 == ()   # int32 in place: handed on
+    suffix, c1, c2, p1, p2 = pair_counts(None, l2, 2, 5, 4, cpu)
+    assert suffix == "_ragged_pair" and c1.tolist() == [5, 5] and c1.dtype == torch.int32 and c2 is l2
+    assert p1 == (c1.data_ptr(),) and p2 == (l2.data_ptr(),)
+    suffix, c1, c2, p1, p2 = pair_counts(l1, l2, 2, 5, 4, cpu)
+    assert suffix == "_ragged_pair" and c1 is l1 and c2 is l2 and p1 == (l1.data_ptr(),) and p2 == (l2.data_ptr(),)
+    suffix, c1, c2, p1, p2 = pair_counts(l1, None, 2, 5, 4, cpu, both=True)          # an entry with no unpaired variant
+    assert suffix == "_ragged_pair" and c1 is l1 and c2.tolist() == [4, 4] and p2 == (c2.data_ptr(),)
+    with pytest.raises(ValueError, match="npoints must have shape"):
+        pair_counts(l1, [1, 2, 3], 2, 5, 4, cpu, ("lengths", "npoints"))
+
+
 def test_check_lengths():
     import pointnet2_amd as P
     got = P.check_lengths(torch.tensor([1, 8, 5], dtype=torch.int64), 8)
