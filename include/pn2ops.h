@@ -321,7 +321,8 @@ int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *
 
 /* What pn2_query_ball_group_xyz_msg launches for these shapes: host only, no device, and the launcher takes its decision through
  * the same function. It describes pn2_query_ball_group_xyz_msg_ragged (below, "ragged batches") as well: that launch takes every
- * host decision from the padded n, so threads, LDS, use_cells, qpb, parts and lanes per query are the same. Returns the launcher's code for the shapes (PN2_E_ARG / PN2_E_SHAPE as there, with nothing written;
+ * host decision from the padded n, so threads, LDS, use_cells, qpb, parts and lanes per query are the same; and
+ * pn2_query_ball_group_xyz_msg_packed ("packed batches") with n = nmax, for the same reason. Returns the launcher's code for the shapes (PN2_E_ARG / PN2_E_SHAPE as there, with nothing written;
  * PN2_E_TOO_LARGE: no LDS geometry fits, info[0] = 0). info (PN2_BQ_MSG_PLAN_FIELDS ints, may be NULL):
  *   [0] threads per workgroup (0: nothing is launched -- b = 0, m = 0 or an error)   [1] LDS cap of the chosen geometry, bytes
  *   [2] dynamic LDS requested, bytes   [3] use_cells: 1 = the workgroups try to bin their cloud, 0 = staged and swept
@@ -526,7 +527,18 @@ int pn2_farthest_point_sample_ragged_variant(int variant, int b, int n, int m, c
  *   pn2_query_ball_group_xyz_ragged; idx (b,m,nsample), pts_cnt (b,m), grouped_xyz (b,m,nsample,3) or NULL.
  * pn2_three_nn_packed: the UNKNOWN side xyz1 (total,3) packed, the known side xyz2 (b,m,3) dense or -- lengths2 != NULL -- with
  *   lengths2[c] valid rows as in pn2_three_nn_ragged_pair; variant as pn2_three_nn_ex. dist, idx (total,3): row offsets1[c] + i
- *   belongs to point i of cloud c; there are no padding rows. */
+ *   belongs to point i of cloud c; there are no padding rows.
+ * pn2_query_ball_group_xyz_msg_packed: pn2_query_ball_group_xyz_msg with xyz1 (total,3) packed, the queries xyz2 (b,m,3) dense:
+ *   ONE launch, one staging / binning of every cloud for all radii. Per cloud and radius the result equals
+ *   pn2_query_ball_group_xyz_msg on flat[offsets1[c] : offsets1[c + 1]] alone, hence pn2_query_ball_group_xyz_packed per radius
+ *   and pn2_query_ball_group_xyz_msg_ragged on the padded copy. idx[i] (b,m,nsamples[i]), pts_cnt[i] (b,m), grouped_xyz[i]
+ *   (b,m,nsamples[i],3); pts_cnt, as a whole or per scale, and idx[i] beside a grouped_xyz[i] may be NULL as in the other
+ *   multi-radius entries. Every host decision comes from nmax: pn2_query_ball_group_xyz_msg_plan(b, nmax, m, ...) reports what
+ *   is launched. Codes in the order of pn2_query_ball_group_xyz_msg_ragged with offsets1 where lengths1 stood: PN2_E_ARG
+ *   (nscales, radii, nsamples), PN2_E_SHAPE (b < 0, nmax <= 0, m < 0), PN2_OK for b = 0 or m = 0, PN2_E_SHAPE for total <= 0
+ *   or nmax > total, PN2_E_NULL for offsets1, then for a scale with neither idx nor grouped_xyz, PN2_E_TOO_LARGE for nmax above
+ *   the cell kernels' point limit (8192), a shape no LDS geometry fits, or total 3 > INT_MAX -- nothing is launched, call
+ *   pn2_query_ball_group_xyz_packed per radius then, as the Python operator does --, PN2_E_NULL for xyz1 / xyz2. */
 int pn2_farthest_point_sample_packed(int variant, int b, int total, int nmax, int m, const float *inp, const int *offsets,
                                      int global_idx, int *out, float *out_xyz /* may be NULL */, void *stream);
 int pn2_query_ball_group_xyz_packed(int b, int total, int nmax, int m, float radius, int nsample, const float *xyz1,
@@ -534,6 +546,9 @@ int pn2_query_ball_group_xyz_packed(int b, int total, int nmax, int m, float rad
                                     int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb, void *stream);
 int pn2_three_nn_packed(int b, int total, int nmax, int m, const float *xyz1, const int *offsets1, const float *xyz2,
                         const int *lengths2 /* may be NULL */, int global_idx, float *dist, int *idx, int variant, void *stream);
+int pn2_query_ball_group_xyz_msg_packed(int b, int total, int nmax, int m, int nscales, const float *radii, const int *nsamples,
+                                        const float *xyz1, const int *offsets1, const float *xyz2, int subtract_centroid,
+                                        int global_idx, int *const *idx, int *const *pts_cnt, float *const *grouped_xyz, void *stream);
 
 /* farthest_point_sample [+ gather_point when out_xyz != NULL] for LARGE dense clouds, 16384 < n <= 1048576: the tier of
  * csrc/fps_large.hip. Same indices as pn2_farthest_point_sample, tie rule (smallest (k mod 512, k)), inf

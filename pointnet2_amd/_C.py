@@ -154,6 +154,7 @@ _SIGNATURES = {
     "pn2_farthest_point_sample_packed": [_i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "pn2_query_ball_group_xyz_packed": [_i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "pn2_three_nn_packed": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp],
+    "pn2_query_ball_group_xyz_msg_packed": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
     "pn2_fps_large_ws_bytes": [_i, _i],
     "pn2_fps_large_supported": [_i, _i],
     "pn2_fps_large_pays": [_i, _i],

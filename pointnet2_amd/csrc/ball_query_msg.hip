@@ -39,10 +39,14 @@ struct BqScales {
 // kernel below. n: the points of the cloud (the LDS layout and every loop bound follow it); xyz1 / xyz2: bases such that the
 // cloud's slab is xyz1 + cloud n 3 and its queries xyz2 + cloud m 3; out_rows: rows of m-major output in front of row
 // cloud m + j (0 when the scales' pointers are the tensors' bases and `cloud` does the addressing). Block-uniform throughout.
+// ibase: added to every index where it is stored, for every radius, by the list passes and the sweep alike (the packed mode's
+// global_idx; an empty ball stores ibase + 0); grouped rows are gathered with the local index. Every other caller passes a
+// literal 0, which folds away.
 template <int NT>
 __device__ __forceinline__ void bq_msg_block_body(int n, int m, int cloud, int q0, int q1, int use_cells, int max_ns,
                                                   int wave_stride_b, const BqScales &sc, const float *__restrict__ xyz1,
-                                                  const float *__restrict__ xyz2, int subtract, size_t out_rows, char *smem)
+                                                  const float *__restrict__ xyz2, int subtract, size_t out_rows, char *smem,
+                                                  int ibase)
 {
     const float *__restrict__ data = xyz1 + (size_t)cloud * n * 3;
 
@@ -80,7 +84,7 @@ __device__ __forceinline__ void bq_msg_block_body(int n, int m, int cloud, int q
 #define PN2_MSG_LOOP(LPQ)                                                                                           \
     bq_cells_query_loop<NT, LPQ, true, false>(n, m, s.nsample, s.thr, s.radius, s.radius * 1.001f, cloud, q0, q1, g, data, \
                                               xyz2, nullptr, nullptr, s_idx, s_cnt, s_grouped, subtract, sorted, tab, \
-                                              wave_area, wave_stride)
+                                              wave_area, wave_stride, 1u, nullptr, nullptr, ibase)
             if (s.lpq == 8) PN2_MSG_LOOP(8);                      // block-uniform
             else if (s.lpq == 16) PN2_MSG_LOOP(16);
             else PN2_MSG_LOOP(32);
@@ -109,7 +113,7 @@ __device__ __forceinline__ void bq_msg_block_body(int n, int m, int cloud, int q
                                                    s.idx ? s.idx + out_rows * (size_t)s.nsample : nullptr,
                                                    s.cnt ? s.cnt + out_rows : nullptr,
                                                    s.grouped ? s.grouped + out_rows * (size_t)s.nsample * 3 : nullptr, subtract,
-                                                   smem, 1u, max_ns);
+                                                   smem, 1u, max_ns, nullptr, ibase);
     }
 }
 
@@ -127,11 +131,18 @@ __device__ __forceinline__ void bq_msg_block_body(int n, int m, int cloud, int q
 // Counts on both sides: cloud c also holds only m_c = lengths2[c] valid queries. The body gets the query range cut at m_c; the
 // workgroup's rows from m_c on are filled for EVERY radius (idx 0, pts_cnt 0, grouped +0.0), and a workgroup of such rows alone
 // leaves before any staging or binning (block-uniform).
+// Packed (pn2_query_ball_group_xyz_msg_packed; pn2_device.h: Packed): the one-sided count mode with the cloud's slab taken from
+// the offsets -- xyz1 is the flat (total, 3) array, n is nmax, the queries and the outputs stay dense (b, m, ...). The body gets
+// exactly the one-sided call: n = nc, cloud 0, xyz1 + start 3, the cloud's m query rows, out_rows = cloud m, and the same
+// per-cloud rule use_cells && nc >= 64. The host decided from nmax (msg_plan(b, nmax, m, ...)) as the ragged entry decides from
+// the padded n, and the argument above carries over word for word: what fits nmax fits nc. A slab may start at ANY row of the
+// flat array -- no alignment is asked of offsets -- because the body reads coordinates as scalars (staging, binning and the
+// FUSE gather all go through data[k * 3 + {0, 1, 2}]). With global_idx the stored indices are rows of the flat array.
 template <int NT, class... Cnt>
 __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int n, int m, int qpb, int parts,
                                                                     int use_cells, int max_ns, int wave_stride_b, BqScales sc,
                                                                     const float *__restrict__ xyz1,
-                                                                    const float *__restrict__ xyz2, int subtract, Cnt __restrict__... cnt)
+                                                                    const float *__restrict__ xyz2, int subtract, CountArg<Cnt>... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Counts<Cnt...> counts(cnt...);
@@ -139,7 +150,14 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int
     decode_cloud_block(blockIdx.x, parts, b, cloud, part);
     if constexpr (sizeof...(Cnt) == 0) {
         const int q0 = part * qpb;
-        bq_msg_block_body<NT>(n, m, cloud, q0, min(q0 + qpb, m), use_cells, max_ns, wave_stride_b, sc, xyz1, xyz2, subtract, 0, smem);
+        bq_msg_block_body<NT>(n, m, cloud, q0, min(q0 + qpb, m), use_cells, max_ns, wave_stride_b, sc, xyz1, xyz2, subtract, 0, smem, 0);
+    } else if constexpr (Counts<Cnt...>::packed) {
+        const int start = cloud_start(counts.pk, cloud);
+        const int nc = cloud_count(counts.pk, cloud, start, n);
+        const int q0 = part * qpb;
+        const size_t rows = (size_t)cloud * m;
+        bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, m), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
+                              xyz1 + (size_t)start * 3, xyz2 + rows * 3, subtract, rows, smem, counts.pk.global_idx ? start : 0);
     } else {
         const int nc = cloud_count(counts.side[0], cloud, n);
         int mc = m;
@@ -158,7 +176,7 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int
             if (q0 >= mc) return;
         }
         bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, mc), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
-                              xyz1 + (size_t)cloud * n * 3, xyz2 + rows * 3, subtract, rows, smem);
+                              xyz1 + (size_t)cloud * n * 3, xyz2 + rows * 3, subtract, rows, smem, 0);
     }
 }
 
@@ -276,9 +294,13 @@ static int msg_plan(int b, int n, int m, int nscales, const float *radii, const 
 
 template <int NT>
 static int launch_msg(int b, int n, int m, const MsgPlan &p, const float *xyz1, const int *lengths1, const float *xyz2, int subtract,
-                      hipStream_t st, const int *lengths2 = nullptr)
+                      hipStream_t st, const int *lengths2 = nullptr, const Packed *pk = nullptr)
 {
-    // with counts the same plan: every host decision is taken from the padded n
+    // with counts the same plan: every host decision is taken from the padded n (packed: from nmax)
+    if (pk)
+        return launch_counts_packed<false>([](auto... c) { return ball_query_msg_kernel<NT, decltype(c)...>; }, *pk, nullptr,
+                                           dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells,
+                                           p.max_ns, (int)p.wave_stride, p.sc, xyz1, xyz2, subtract);
     return launch_counts([](auto... c) { return ball_query_msg_kernel<NT, decltype(c)...>; }, lengths1, lengths2,
                          dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells, p.max_ns,
                          (int)p.wave_stride, p.sc, xyz1, xyz2, subtract);
@@ -304,10 +326,10 @@ extern "C" int pn2_query_ball_group_xyz_msg_plan(int b, int n, int m, int nscale
 }
 
 // lengths1: NULL = every cloud holds n points; else the points per cloud; lengths2 (with lengths1 only): the valid queries per
-// cloud (the kernel's count modes)
+// cloud (the kernel's count modes). pk: the packed mode -- n is nmax, xyz1 holds pk->total rows.
 static int msg_run(int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *xyz1, const int *lengths1,
                    const float *xyz2, int subtract_centroid, int *const *idx, int *const *pts_cnt, float *const *grouped_xyz,
-                   void *stream, const int *lengths2 = nullptr)
+                   void *stream, const int *lengths2 = nullptr, const pn2::Packed *pk = nullptr)
 {
     using namespace pn2;
     if (int rc = msg_check_args(b, n, m, nscales, radii, nsamples)) return rc;
@@ -316,6 +338,7 @@ static int msg_run(int b, int n, int m, int nscales, const float *radii, const i
     MsgPlan p;
     if (int rc = msg_plan(b, n, m, nscales, radii, nsamples, p)) return rc;
     if (p.nt == 0) return PN2_OK;                                // b == 0 or m == 0
+    if (pk && (long long)pk->total * 3 > INT_MAX) return PN2_E_TOO_LARGE;
     if (!xyz1 || !xyz2) return PN2_E_NULL;
     for (int i = 0; i < nscales; ++i) {
         p.sc.s[i].idx = idx ? idx[i] : nullptr;
@@ -323,8 +346,8 @@ static int msg_run(int b, int n, int m, int nscales, const float *radii, const i
         p.sc.s[i].grouped = grouped_xyz ? grouped_xyz[i] : nullptr;
     }
     hipStream_t st = as_stream(stream);
-    if (p.nt == 1024) return launch_msg<1024>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st, lengths2);
-    return launch_msg<512>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st, lengths2);
+    if (p.nt == 1024) return launch_msg<1024>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st, lengths2, pk);
+    return launch_msg<512>(b, n, m, p, xyz1, lengths1, xyz2, subtract_centroid, st, lengths2, pk);
 }
 
 extern "C" int pn2_query_ball_group_xyz_msg(int b, int n, int m, int nscales, const float *radii, const int *nsamples,
@@ -370,4 +393,25 @@ extern "C" int pn2_query_ball_group_xyz_msg_ragged_pair(int b, int n, int m, int
 {
     return msg_run_ragged(2, b, n, m, nscales, radii, nsamples, xyz1, lengths1, xyz2, lengths2, subtract_centroid, idx, pts_cnt,
                           grouped_xyz, stream);
+}
+
+// Packed batch: cloud c of xyz1 is xyz1[offsets1[c] : offsets1[c + 1]] of a flat (total, 3) array, offsets1 (b + 1) int32 on the
+// device, never read by the host; nmax bounds every cloud's count and takes the padded n's place in every host decision --
+// pn2_query_ball_group_xyz_msg_plan(b, nmax, m, ...) reports what is launched. The queries xyz2 (b, m, 3) and the outputs are
+// dense. Result per cloud and radius = pn2_query_ball_group_xyz_msg on the slice = pn2_query_ball_group_xyz_packed per radius =
+// pn2_query_ball_group_xyz_msg_ragged on the padded copy; global_idx 1 writes idx as offsets1[c] + k. Codes in the order of
+// pn2_query_ball_group_xyz_msg_ragged with offsets1 where lengths1 stood; total <= 0 or nmax > total is PN2_E_SHAPE, total 3 >
+// INT_MAX PN2_E_TOO_LARGE.
+extern "C" int pn2_query_ball_group_xyz_msg_packed(int b, int total, int nmax, int m, int nscales, const float *radii,
+                                                   const int *nsamples, const float *xyz1, const int *offsets1, const float *xyz2,
+                                                   int subtract_centroid, int global_idx, int *const *idx, int *const *pts_cnt,
+                                                   float *const *grouped_xyz, void *stream)
+{
+    if (int rc = pn2::msg_check_args(b, nmax, m, nscales, radii, nsamples)) return rc;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (total <= 0 || nmax > total) return PN2_E_SHAPE;
+    if (!offsets1) return PN2_E_NULL;
+    const pn2::Packed pk = {offsets1, total, global_idx ? 1 : 0};
+    return msg_run(b, nmax, m, nscales, radii, nsamples, xyz1, nullptr, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream,
+                   nullptr, &pk);
 }

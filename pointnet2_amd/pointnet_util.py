@@ -720,6 +720,10 @@ class PointnetSAModuleMSG(nn.Module):
         # PointnetSAModule.fused_ragged_train. last_path "fused_train_ragged". Opt-in.
         self.fused_ragged_train = False
         self.fused_ragged_eval = False  # see PointnetSAModule: eval() with counts on the fused inference kernels (opt-in)
+        # forward(offsets=, max_points=): a packed batch -- packed FPS + gather, then every radius in ONE packed
+        # multi-radius launch, the stacks on the flat view (_forward_packed). Opt-in: with it off the module refuses offsets as
+        # it always has (ValueError), which callers may rely on to learn that a level is not packed.
+        self.packed_batches = False
         self.last_path = None
         self._pack_cache = {}
 
@@ -865,25 +869,68 @@ class PointnetSAModuleMSG(nn.Module):
         yv = torch.cat(outs, dim=1)                                             # :195
         return new_xyz, _scatter_rows(yv, rows, b * m).reshape(b, m, yv.shape[1])
 
-    def _forward_on_geometry(self, xyz, points, g):
+    def _forward_on_geometry(self, xyz, points, g, m=None):
         """One function per path on a geometry (g None: the inference kernels and the layer-by-layer path keep their own
-        launches, the training nodes take this call's own geometry())."""
+        launches, the training nodes take this call's own geometry()). m: the centroid rows per cloud of xyz when that is not
+        npoint (the flat view of a packed batch)."""
         if self._fused_ok(xyz, points):
             self.last_path = "fused"
             return self._forward_fused(xyz, points, g)
-        mode = _train_mode(self, [(mlp.net, ns) for mlp, ns in zip(self.mlps, self.nsample_list)], "max", False, xyz, points)
+        mode = _train_mode(self, [(mlp.net, ns) for mlp, ns in zip(self.mlps, self.nsample_list)], "max", False, xyz, points, m)
         if mode is not None:
             self.last_path = mode
             return self._forward_train(xyz, points, g or self.geometry(xyz, plans=self.index_plans and torch.is_grad_enabled()), mode)
         self.last_path = "unfused"
         return self._forward_layers(xyz, points, g)
 
+    def packed_geometry(self, xyz, offsets, max_points, plans=False):
+        """geometry() of a PACKED batch (packed_batches), in the FLAT VIEW: packed FPS + gather, then every radius
+        in ONE packed multi-radius launch (each cloud's slab staged and binned once), both with global indices.
+        -> SAGeometry(new_xyz (1, B npoint, 3), [idx_i (1, B npoint, nsample_i)], fps_idx (1, B npoint)) on xyz (1, total, 3):
+        idx_i holds rows of the flat array (plans: one index plan per radius on `total` rows)."""
+        require(self.packed_batches, "PointnetSAModuleMSG: packed batches (offsets=) are not offered for MSG levels")
+        offs, b, total, nmax = packed_args(offsets, max_points, None, xyz, "PointnetSAModuleMSG")
+        m = self.npoint
+        flat = xyz.detach()
+        fps_idx, new_xyz = farthest_point_sample_gather(m, flat, offsets=offs, max_points=nmax, global_idx=True)
+        scales = query_ball_group_xyz_msg(self.radius_list, self.nsample_list, flat, new_xyz, True, offsets=offs, max_points=nmax,
+                                          global_idx=True)
+        idxs = [i.view(1, b * m, i.shape[2]) for i, _, _ in scales]
+        return SAGeometry(new_xyz.view(1, b * m, 3), idxs, fps_idx.view(1, b * m),
+                          [index_plan(i, total, "group") for i in idxs] if plans else None)
+
+    def _forward_packed(self, xyz, points, offsets, max_points):
+        """forward() on a PACKED batch: xyz (total, 3), points (total, c) or None, cloud i = rows offsets[i] .. offsets[i + 1] - 1.
+        The geometry is built in the flat view (packed_geometry) and handed to the existing function of each path
+        (_forward_on_geometry): every route behind a geometry is index-driven, so the training nodes, the inference kernels and
+        the layer-by-layer path run unchanged on one cloud of `total` points and B npoint centroids, and nothing is masked. The
+        route predicates get the true centroid count (m = B npoint). last_path is the route's with "packed_" in front.
+        -> new_xyz (B, npoint, 3), features (B, npoint, sum C_i); the per-scale global idx: packed_geometry()."""
+        require(not (torch.is_grad_enabled() and isinstance(xyz, torch.Tensor) and xyz.requires_grad),
+                "PointnetSAModuleMSG: with offsets xyz cannot require a gradient (detach it)")
+        offs, b, total, nmax = packed_args(offsets, max_points, None, xyz, "PointnetSAModuleMSG")
+        if points is not None:
+            require(points.dim() == 2 and points.shape[0] == total, "PointnetSAModuleMSG: with offsets, points is (total, channel)")
+        m = self.npoint
+        xf = xyz.reshape(1, total, 3)
+        pf = points.reshape(1, total, points.shape[1]) if points is not None else None
+        g = self.packed_geometry(xyz, offs, nmax)                  # (index_plans: _forward_train builds them, on `total` rows)
+        new_xyz_f, out = self._forward_on_geometry(xf, pf, g, b * m)
+        self.last_path = "packed_" + self.last_path
+        return new_xyz_f.view(b, m, 3), out.view(b, m, out.shape[2])
+
     def forward(self, xyz, points, geometry=None, lengths=None, npoints=None, offsets=None, max_points=None):
         """Resolve the level's geometry -- computed ahead (geometry=), the ragged operators' (lengths=, see
         PointnetSAModule.forward) or, for the training nodes, this call's own (geometry()) -- then one function per path on it.
         Without a geometry the inference kernels and the layer-by-layer path keep their own launches (_group_scales).
         npoints: (b,) per-cloud sample counts, with or without lengths (_forward_counts).
-        offsets: packed batches are not offered for multi-scale grouping yet (ValueError)."""
+        offsets / max_points: a packed batch, xyz (total, 3) and points (total, c), see _forward_packed -- with packed_batches
+        set; ValueError without it, and with lengths / npoints, a geometry=, fused_xyz_grad or an xyz that needs a gradient."""
+        if self.packed_batches and offsets is not None:
+            require(lengths is None and npoints is None, "PointnetSAModuleMSG: offsets and lengths / npoints are two layouts; give one")
+            require(geometry is None, "PointnetSAModuleMSG: a geometry computed ahead is not offered with offsets")
+            require(not self.fused_xyz_grad, "PointnetSAModuleMSG: fused_xyz_grad is not offered with offsets")
+            return self._forward_packed(xyz, points, offsets, max_points)
         require(offsets is None and max_points is None, "PointnetSAModuleMSG: packed batches (offsets=) are not offered for MSG levels")
         if npoints is not None:
             g = geometry.wait() if geometry is not None else self.geometry(xyz, lengths=lengths, npoints=npoints)

@@ -127,7 +127,7 @@ def query_ball_group_xyz(radius, nsample, xyz1, xyz2, subtract_centroid=True, wa
 
 
 def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_centroid=True, want_idx=True, lengths1=None,
-                             lengths2=None):
+                             lengths2=None, offsets=None, max_points=None, global_idx=False):
     """Every radius of a multi-scale-grouping level in ONE launch: the cloud is staged and binned once
     per workgroup and queried once per radius (pn2_query_ball_group_xyz_msg; reference loop
     pointnet_util.py:175-186 runs query_ball_point + group_point + subtraction per radius).
@@ -136,6 +136,9 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     launch, every cloud's own points staged and binned once); bit-identical to query_ball_group_xyz(..., lengths1=) per radius.
     lengths2: (b,) per-cloud counts of valid query rows, see query_ball_point (pn2_query_ball_group_xyz_msg_ragged_pair: still
     one launch); bit-identical to query_ball_group_xyz(..., lengths1=, lengths2=) per radius, fill rows included.
+    offsets / max_points / global_idx: a packed xyz1 (total, 3), see query_ball_point (pn2_query_ball_group_xyz_msg_packed: still
+    one launch, every cloud's slab staged and binned once); bit-identical to query_ball_group_xyz(..., offsets=, max_points=,
+    global_idx=) per radius. Not to be mixed with lengths1 / lengths2 (ValueError); the outputs stay dense (b, m, ...).
 
     -> [(idx (b,m,ns_i) i32 or None, pts_cnt (b,m) i32, grouped_xyz (b,m,ns_i,3) f32) for every scale]
     """
@@ -145,7 +148,14 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     require(len(radius_list) == len(nsample_list) and 1 <= len(radius_list), "one nsample per radius")
     require(all(r > 0 for r in radius_list), "QueryBallPoint expects positive radius")
     require(all(k > 0 for k in nsample_list), "QueryBallPoint expects positive nsample")
-    xyz1, xyz2, dev, (b, n, m), entry, lens1, lens2, behind1, behind2 = _ball_inputs("query_ball_group_xyz_msg", xyz1, xyz2, lengths1, lengths2)
+    xyz1, xyz2, dev, extents, entry, lens1, lens2, behind1, behind2 = _ball_inputs("query_ball_group_xyz_msg", xyz1, xyz2, lengths1, lengths2,
+                                                                                  offsets, max_points)
+    b, n, m = extents[0], extents[-2], extents[-1]                # n: the padded extent, packed: max_points
+    flags = (1 if subtract_centroid else 0,)
+    if offsets is not None:
+        # (max_points is a bound: one above total bounds nothing more, and the entry asks for nmax <= total)
+        extents = (b, extents[1], min(n, extents[1]), m)
+        flags += (1 if global_idx else 0,)
     ns_count = len(radius_list)
     rc = -4                                                       # outside the multi-radius kernel's envelope
     if ns_count <= 4 and n <= 8192:
@@ -171,11 +181,13 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
         pg = (ctypes.c_void_p * ns_count)(*[ptr(o[2]) for o in outs])
         with on_device(dev):
             rc = getattr(_C.lib(), "pn2_query_ball_group_xyz_msg" + entry)(
-                b, n, m, ns_count, radii, nss, ptr(xyz1), *behind1, ptr(xyz2), *behind2,
-                1 if subtract_centroid else 0, pi, pc, pg, stream_ptr(dev))
+                *extents, ns_count, radii, nss, ptr(xyz1), *behind1, ptr(xyz2), *behind2, *flags, pi, pc, pg, stream_ptr(dev))
     if rc == -4:
         # ... or PN2_E_TOO_LARGE: no LDS geometry fits this combination (e.g. n = 8192 with nsample >= 127 on a later radius);
         # nothing has been launched -- the per-radius operator covers every shape
+        if offsets is not None:
+            return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, offsets=lens1, max_points=max_points,
+                                         global_idx=global_idx) for r, k in zip(radius_list, nsample_list)]
         return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens1, lengths2=lens2)
                 for r, k in zip(radius_list, nsample_list)]
     _C.check(rc, "query_ball_group_xyz_msg")

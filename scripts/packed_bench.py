@@ -1,7 +1,7 @@
 """Packed batches (offsets= / max_points=, pn2_*_packed) against the padded layout (lengths=, pn2_*_ragged) on the SAME clouds,
 same process. Measurement aid; needs the GPU.
 
-    python scripts/packed_bench.py [--samples 20] [--reps 3] [--inner 10] [--parent-lib libpn2ops.so] [--json FILE]
+    python scripts/packed_bench.py [--samples 20] [--reps 3] [--inner 10] [--parent-lib libpn2ops.so] [--json FILE] [--only SECTION]
 
 Method (that of scripts/ragged_pair_bench.py): the C entries are called directly on preallocated outputs; one SAMPLE is `inner`
 back-to-back calls of a route between two device events, divided by `inner` (FPS: 3 calls); one repetition of a route is the
@@ -16,6 +16,14 @@ Operators, lengths uniform in n/2 .. n (seed fixed), the padded tensor sized by 
   FPS + gather        32 x 4096 -> 1024 (the library's size rule on n / max_points = 4096: the batched tier)
   ball query + group  the same clouds and samples, radius 0.2, nsample 32 (kernel 0: the library's choice)
   three_nn            sem_seg FP4: 8 x 8192 unknown, 1024 known
+  multi-radius group  cls_msg level 1: 32 x 4096, m 512, radii 0.1 / 0.2 / 0.4, nsample 16 / 32 / 128, on sphere-surface clouds
+                      and on uniform cubes (those of scripts/ragged_msg_bench.py); queries: each cloud's farthest-point samples.
+                      ONE pn2_query_ball_group_xyz_msg_packed launch against (a) what a packed user had before it, three
+                      pn2_query_ball_group_xyz_packed launches, and (b) pn2_query_ball_group_xyz_msg_ragged on the padded copy
+                      (both baselines from --parent-lib when given)
+MSG level (cls_msg level 1 with 6 feature channels, stacks 32-32-64 / 64-64-128 / 64-96-128, uniform cubes): PointnetSAModuleMSG
+with packed_batches on the packed batch against the padded lengths= forward with ragged_one_launch, eval() (no_grad) and train()
+(forward + backward); both routes are this tree's Python.
 Training level (sem_seg FP4, 128 -> 128 -> 128 -> 128, one warm forward + backward of PointnetFPModule per step, three_nn
 included): the packed route -- `total` made a multiple of 32 by the last cloud's length, so the dense node runs on `total`
 rows and nothing is masked -- against the padded route with fused_ragged_train (the masked node on b n rows); time and
@@ -40,7 +48,8 @@ from pointnet2_amd._tensors import stream_ptr
 
 def bind(path):
     lib = ctypes.CDLL(path)
-    for name in ("pn2_farthest_point_sample_ragged", "pn2_query_ball_group_xyz_ragged", "pn2_three_nn_ragged"):
+    for name in ("pn2_farthest_point_sample_ragged", "pn2_query_ball_group_xyz_ragged", "pn2_three_nn_ragged",
+                 "pn2_query_ball_group_xyz_packed", "pn2_query_ball_group_xyz_msg_ragged"):
         getattr(lib, name).argtypes = _C._SIGNATURES[name]
         getattr(lib, name).restype = ctypes.c_int
     return lib
@@ -141,6 +150,89 @@ def operators(base, a, dev, results):
     report("three_nn sem_seg FP4 (8 x 8192, 1024 known)", rts, same, a, results, b=b, n=n, m=m, total=total, mean_length=float(lengths.mean()))
 
 
+def msg_operator(base, a, dev, results):
+    """cls_msg level 1 on a packed batch: one packed multi-radius launch against the two routes the parent commit offers"""
+    from pointnet2_amd import synthetic as S
+    lib, st = _C.lib(), stream_ptr(dev)
+    b, n, m, radii_l, nss_l = 32, 4096, 512, [0.1, 0.2, 0.4], [16, 32, 128]
+    k = len(radii_l)
+    radii, nss = (ctypes.c_float * k)(*radii_l), (ctypes.c_int * k)(*nss_l)
+    for title, gen in (("sphere surface", S.sphere_clouds), ("uniform cube", S.uniform_clouds)):
+        xyz = torch.from_numpy(gen(b, n, 1)).to(dev)
+        lengths = np.random.default_rng(7).integers(n // 2, n + 1, size=b)
+        lens = torch.tensor(lengths, dtype=torch.int32, device=dev)
+        for c, nc in enumerate(lengths):
+            xyz[c, int(nc):] = float("nan")
+        flat, offs = P.pack_batch(xyz, lengths.tolist())
+        total = int(flat.shape[0])
+        _, q = P.farthest_point_sample_gather(m, xyz, lengths=lens)
+        outs = [[(torch.empty((b, m, ns), dtype=torch.int32, device=dev), torch.empty((b, m), dtype=torch.int32, device=dev),
+                  torch.empty((b, m, ns, 3), dtype=torch.float32, device=dev)) for ns in nss_l] for _ in range(3)]
+        tabs = [[(ctypes.c_void_p * k)(*[o[j].data_ptr() for o in out]) for j in range(3)] for out in outs]
+
+        def per_radius():
+            for r, ns, (i, c, g) in zip(radii_l, nss_l, outs[1]):
+                check(base.pn2_query_ball_group_xyz_packed(b, total, n, m, r, ns, flat.data_ptr(), offs.data_ptr(), q.data_ptr(), 1, 0,
+                                                           i.data_ptr(), c.data_ptr(), g.data_ptr(), 0, 0, st))
+        rts = {"packed, one multi-radius launch": lambda: check(lib.pn2_query_ball_group_xyz_msg_packed(
+                   b, total, n, m, k, radii, nss, flat.data_ptr(), offs.data_ptr(), q.data_ptr(), 1, 0, *tabs[0], st)),
+               "(a) packed, one launch per radius": per_radius,
+               "(b) padded, _msg_ragged": lambda: check(base.pn2_query_ball_group_xyz_msg_ragged(
+                   b, n, m, k, radii, nss, xyz.data_ptr(), lens.data_ptr(), q.data_ptr(), 1, *tabs[2], st))}
+        for fn in rts.values():
+            fn()
+        torch.cuda.synchronize()
+        same = all(torch.equal(bits(u), bits(v)) for other in outs[1:] for o, r in zip(other, outs[0]) for u, v in zip(o, r))
+        report("multi-radius group, cls_msg level 1, " + title, rts, same, a, results, b=b, n=n, m=m, total=total,
+               mean_length=float(lengths.mean()))
+
+
+def msg_level(a, dev, results):
+    """PointnetSAModuleMSG at cls_msg level 1 with 6 feature channels: packed_batches against the padded lengths= forward"""
+    from pointnet2_amd import synthetic as S
+    b, n, m, cfeat = 32, 4096, 512, 6
+    xyz = torch.from_numpy(S.uniform_clouds(b, n, 1)).to(dev)
+    lengths = np.random.default_rng(7).integers(n // 2, n + 1, size=b)
+    lens = torch.tensor(lengths, dtype=torch.int32, device=dev)
+    feats = torch.randn((b, n, cfeat), generator=torch.Generator().manual_seed(11)).to(dev)
+    flat, offs = P.pack_batch(xyz, lengths.tolist())
+    fflat, _ = P.pack_batch(feats, lengths.tolist())
+    torch.manual_seed(3)
+    mod = U.PointnetSAModuleMSG(cfeat, m, [0.1, 0.2, 0.4], [16, 32, 128], [[32, 32, 64], [64, 64, 128], [64, 96, 128]]).to(dev)
+    mod.packed_batches = mod.ragged_one_launch = True
+    for mode in ("eval", "train"):
+        mod.train(mode == "train")
+        taken = {}
+
+        def run(name, *args, **kw):
+            if mode == "eval":
+                with torch.no_grad():
+                    _, out = mod(*args, **kw)
+            else:
+                _, out = mod(*args, **kw)
+                torch.autograd.grad(out.sum(), list(mod.parameters()))
+            taken[name] = mod.last_path
+            return out
+        fns = {"padded, lengths= (ragged_one_launch)": lambda: run("padded", xyz, feats, lengths=lens),
+               "packed, packed_batches": lambda: run("packed", flat, fflat, offsets=offs, max_points=n)}
+        op, of = [fn() for fn in fns.values()]
+        torch.cuda.synchronize()
+        diff = float((op - of).abs().max() / of.abs().max().clamp(min=1.0))
+        meds = {key: [] for key in fns}
+        for _ in range(a.reps):
+            for key, fn in fns.items():
+                for _ in range(5):
+                    fn()
+                meds[key].append(statistics.median(sample(fn, 1) for _ in range(a.samples)))
+        row = dict(op="cls_msg level 1 MSG module, " + mode, b=b, n=n, m=m, total=int(flat.shape[0]), paths=dict(taken),
+                   output_difference_of_scale=diff,
+                   routes={key: {"median_us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for key, v in meds.items()})
+        results.append(row)
+        print("cls_msg level 1 MSG module, %s (paths %s; outputs differ by %.2e of scale)" % (mode, taken, diff), flush=True)
+        for key, r in row["routes"].items():
+            print("    %-38s %8.1f us   (repetitions %.1f .. %.1f)" % (key, r["median_us"], r["min_us"], r["max_us"]), flush=True)
+
+
 def training_level(a, dev, results):
     b, n, m, c2, widths = 8, 8192, 1024, 128, [128, 128, 128]
     lengths, xyz, lens, flat, offs = batch(b, n, 4, dev, multiple=32)
@@ -210,6 +302,7 @@ def main():
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--only", default=None, choices=["operators", "msg", "msg_level", "training"], help="one section alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("packed_bench.py measures on the GPU; none found")
@@ -217,8 +310,10 @@ def main():
     base = bind(a.parent_lib) if a.parent_lib else _C.lib()
     print("padded baseline: %s" % ("the _ragged entries of " + a.parent_lib if a.parent_lib else "this library's _ragged entries"))
     results = []
-    operators(base, a, dev, results)
-    training_level(a, dev, results)
+    for name, section in (("operators", lambda: operators(base, a, dev, results)), ("msg", lambda: msg_operator(base, a, dev, results)),
+                          ("msg_level", lambda: msg_level(a, dev, results)), ("training", lambda: training_level(a, dev, results))):
+        if a.only in (None, name):
+            section()
     if a.json:
         with open(a.json, "w") as f:
             json.dump({"samples": a.samples, "reps": a.reps, "inner": a.inner, "parent_lib": bool(a.parent_lib), "results": results}, f, indent=1)
