@@ -598,6 +598,31 @@ int pn2_farthest_point_sample_large_ragged_ex(int kernel, int group_len, int b, 
                                               const int *npoints /* NULL: m samples from every cloud */, void *ws, int *out,
                                               float *out_xyz /* may be NULL */, void *stream);
 
+/* Packed batches of LARGE clouds (the packed layout of pn2_farthest_point_sample_packed, which stops at nmax = 16384): cloud c is
+ * inp[offsets[c] : offsets[c + 1]] of a flat (total, 3) array, offsets (b + 1) int32 in DEVICE memory, clamped on the device and
+ * never read by the host; 16384 < nmax <= 1048576 bounds every cloud's count and stands for the padded n in every host decision.
+ * Result per cloud = the dense operator on the slice, tie rule included; global_idx 1 adds offsets[c] to the cloud's indices; out
+ * (b, m) and out_xyz (b, m, 3) are dense. One launch of one workgroup per cloud, no memset, no global atomics, no host
+ * synchronisation: capturable, and a replay follows offsets rewritten in place.
+ *   ws         pn2_fps_large_packed_ws_bytes(total) = 20 total bytes: total 16-byte records, then total floats (0 for total <= 0);
+ *              16-byte aligned, no initialisation. Cloud c uses the rows offsets[c] .. of both arrays;
+ *   kernel     0 = pn2_fps_large_pays(nmax, m), 1 = the global-memory kernel, 2 = the cell-sorted tier;
+ *   group_len  64, 128 or 256 (kernel 1 ignores a valid value);
+ *   short_max  the tier only (kernel 1 ignores a valid value): a cloud of at most short_max points is sampled by a body that
+ *              keeps it in LDS and registers -- no cell sort, ws untouched for that cloud. -1 = the library's measured rule
+ *              (profiles/fps_large_packed/README.md), 0 = never, 1 .. 8192 = that threshold.
+ * The plain entry is _ex(0, 256, -1, ...). Results never depend on kernel, group_len or short_max.
+ * Codes, in this order, all before anything is launched: m <= 0 or b == 0 PN2_OK; b < 0, nmax <= 0 or total <= 0 PN2_E_SHAPE; inp,
+ * offsets, out or ws NULL PN2_E_NULL; nmax outside the envelope, or total 3 / b m 3 beyond int32, PN2_E_TOO_LARGE; kernel not
+ * 0..2, group_len not one of the three or short_max not -1..8192 PN2_E_ARG; more than 4096 groups of group_len records in nmax
+ * points where the tier would run PN2_E_TOO_LARGE; a misaligned ws PN2_E_ARG. */
+long long pn2_fps_large_packed_ws_bytes(int total);
+int pn2_farthest_point_sample_large_packed(int b, int total, int nmax, int m, const float *inp, const int *offsets, int global_idx,
+                                           void *ws, int *out, float *out_xyz /* may be NULL */, void *stream);
+int pn2_farthest_point_sample_large_packed_ex(int kernel, int group_len, int short_max, int b, int total, int nmax, int m,
+                                              const float *inp, const int *offsets, int global_idx, void *ws, int *out,
+                                              float *out_xyz /* may be NULL */, void *stream);
+
 /* The whole xyz half of sample_and_group (pointnet_util.py:40-46) in ONE launch, with the ball
  * queries overlapped under the farthest-point-sampling chain: producer workgroups (one per cloud)
  * publish each sample as they select it, consumer workgroups on the other CUs run query j as soon as

@@ -162,11 +162,15 @@ _SIGNATURES = {
     "pn2_farthest_point_sample_large_ex": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "pn2_farthest_point_sample_large_ragged": [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pn2_farthest_point_sample_large_ragged_ex": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pn2_fps_large_packed_ws_bytes": [_i],
+    "pn2_farthest_point_sample_large_packed": [_i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
+    "pn2_farthest_point_sample_large_packed_ex": [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp],
 }
 _RESTYPES = {
     "pn2_fps_temp_floats": ctypes.c_longlong,
     "pn2_fps_ordered_ws_bytes": ctypes.c_longlong,
     "pn2_fps_large_ws_bytes": ctypes.c_longlong,
+    "pn2_fps_large_packed_ws_bytes": ctypes.c_longlong,
     "pn2_det_grad_ws_bytes": ctypes.c_longlong,
     "pn2_seg_grad_ws_bytes": ctypes.c_longlong,
     "pn2_seg_plan_bytes": ctypes.c_longlong,

@@ -67,16 +67,6 @@ __global__ __launch_bounds__(kBtT) void fps_batch_kernel(int n, int m, int Q, co
     fps_batch_body<P, GS, false>(n, m, Q, blockIdx.x, xyz, out, out_xyz, nullptr, smem);
 }
 
-// global_idx of the packed mode: the chain and its gather epilogue work on cloud-local indices (the epilogue reads them back);
-// the workgroup-uniform base is added to the finished rows behind them, off the chain. Block-uniform branch.
-template <int T>
-__device__ __forceinline__ void fps_global_rows(int m, int base, int *dst)
-{
-    if (base == 0) return;
-    __syncthreads();                                      // the index stores (and the epilogue's reads of them) are done
-    for (int j = threadIdx.x; j < m; j += T) dst[j] += base;
-}
-
 // Ragged batch on every tier (pn2_farthest_point_sample_ragged_variant; Pk = Packed: pn2_farthest_point_sample_packed). Cloud c
 // holds n_c = lengths[c] <= n points in its padded (n, 3) slab -- or its rows of the flat array (FpsSlab, fps_body.h). The
 // workgroup hands the tier's body its own slab as cloud 0 with n = n_c and Q = ceil(n_c / 512): every body takes (n, m, Q, cloud,
@@ -341,14 +331,20 @@ __global__ __launch_bounds__(1024) void fps_generic_kernel(int n, int m, const f
 // loop over the cloud is k < n_c (rows at or beyond n_c of the cloud and of temp are never addressed), a thread without a point
 // contributes key 0, below every real key, and the one barrier per round sits in the loop j < m_c of workgroup-uniform bound.
 // COUNTS: rows m_c .. m-1 are fps_ragged_fill's.
-template <bool COUNTS>
+// Pk = Packed (pn2_farthest_point_sample_large_packed, kernel 1): the slab is the cloud's rows of the flat array and its running
+// distances are the same rows of temp (total floats), so nothing is sized by b n; global_idx as in fps_ragged_kernel.
+__device__ __forceinline__ float *fps_generic_temp(float *__restrict__ temp, int c, int n) { return temp + (size_t)c * n; }
+__device__ __forceinline__ float *fps_generic_temp(float *__restrict__ temp, int c, int, Packed pk) { return temp + cloud_start(pk, c); }
+
+template <bool COUNTS, class... Pk>
 __global__ __launch_bounds__(1024) void fps_generic_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
                                                                   const int *__restrict__ npoints, float *__restrict__ temp,
-                                                                  int *__restrict__ out, float *__restrict__ out_xyz)
+                                                                  int *__restrict__ out, float *__restrict__ out_xyz, Pk... pk)
 {
     const int c = blockIdx.x;
-    const FpsSlab s = fps_slab<COUNTS>(c, n, m, xyz, lengths, npoints, out, out_xyz);
-    fps_generic_body(s.nc, s.mc, s.src, temp + (size_t)c * n, s.dst, s.dxyz);
+    const FpsSlab s = fps_slab<COUNTS>(c, n, m, xyz, lengths, npoints, out, out_xyz, pk...);
+    fps_generic_body(s.nc, s.mc, s.src, fps_generic_temp(temp, c, n, pk...), s.dst, s.dxyz);
+    if constexpr (sizeof...(Pk) != 0) fps_global_rows<1024>(s.mc, s.base, s.dst);
     if (COUNTS) fps_ragged_fill<1024>(s.mc, m, s.src, s.dst, s.dxyz);
 }
 
@@ -396,6 +392,12 @@ int fps_launch_generic_ragged(int b, int n, int m, const float *inp, const int *
 {
     return launch(npoints ? fps_generic_ragged_kernel<true> : fps_generic_ragged_kernel<false>, dim3(b), dim3(1024), 0, st, n, m, inp,
                   lengths, npoints, temp, out, oxyz);
+}
+
+// the same kernel in the packed mode, for the packed entry of fps_large.hip: n is nmax, temp pk.total floats
+int fps_launch_generic_packed(int b, int n, int m, const float *inp, Packed pk, float *temp, int *out, float *oxyz, hipStream_t st)
+{
+    return launch(fps_generic_ragged_kernel<false, Packed>, dim3(b), dim3(1024), 0, st, n, m, inp, nullptr, nullptr, temp, out, oxyz, pk);
 }
 
 // Every (T, P) of the register tier, for the tuning harness (bench.py --fps-sweep; pn2_farthest_point_sample_ex): fps_choose

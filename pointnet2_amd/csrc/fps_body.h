@@ -363,6 +363,16 @@ __device__ __forceinline__ FpsSlab fps_slab(int c, int n, int m, const float *__
     return {nc, mc, base, src, dst, dxyz};
 }
 
+// global_idx of the packed mode (fps.hip, fps_large.hip): the chain and its gather epilogue work on cloud-local indices (the
+// epilogue reads them back); the workgroup-uniform base is added to the finished rows behind them, off the chain. Block-uniform branch.
+template <int T>
+__device__ __forceinline__ void fps_global_rows(int m, int base, int *dst)
+{
+    if (base == 0) return;
+    __syncthreads();                                      // the index stores (and the epilogue's reads of them) are done
+    for (int j = threadIdx.x; j < m; j += T) dst[j] += base;
+}
+
 // The rows m_c .. m-1 of a cloud that yields m_c < m samples (the ragged kernels with counts, fps.hip and fps_large.hip): sample
 // 0 repeated, i.e. index 0 and the cloud's first point -- nothing is read back.
 template <int T>

@@ -32,6 +32,9 @@
 // untouched group's records -- hence its key -- did not change.
 // Ragged batches (lengths / npoints on the device): the chain is a body that takes one cloud's extents; fps_large_ragged_kernel
 // runs it on each cloud's slice (pn2_farthest_point_sample_large_ragged).
+// Packed batches (offsets on the device): fps_large_packed_kernel runs the same body on the cloud's rows of the flat array and
+// of the workspace, and a short-cloud body (fps_large_short_body) on clouds of at most 8192 points
+// (pn2_farthest_point_sample_large_packed).
 #include "fps_body.h"
 
 #include <limits.h>
@@ -376,6 +379,81 @@ __device__ __forceinline__ void fps_large_body(int n, int m, const float *__rest
     }
 }
 
+// A cloud of at most kLgShortCap points inside a launch of this tier (a packed batch whose nmax is large: fps_large_packed_kernel):
+// no cell sort, no records, no running distances in global memory -- recs / md are not even arguments. The cloud lies in the
+// 128 KiB the histogram would have used, as float4 {x, y, z, .} at its own index (8192 x 16 B = kLgHistBytes: the capacity), and
+// thread t owns the points t + 1024 r, r < 8: coordinates and running distances in registers for the whole chain. A round is
+// fps_generic_body's round (fps.hip) on those registers: the sample's coordinates from one broadcast LDS read, sqdist,
+// __builtin_fminf, the same 64-bit key, wave maximum, one slot per wave in the key array (parity double-buffered), one
+// __syncthreads(), 16 keys, decode. The arithmetic per point is the generic kernel's, hence its samples, ties, non-finite points
+// and m > n (value 0: point 0 wins) included. Slots r with 1024 r >= n are skipped by a workgroup-uniform branch; a thread without
+// a point in a slot that runs contributes key 0, below every real key.
+constexpr int kLgShortCap = (int)(kLgHistBytes / 16);
+constexpr int kLgShortP = kLgShortCap / kLgT;
+static_assert(kLgShortCap == 8192 && kLgShortP == 8, "short clouds: eight points per thread, the histogram's LDS");
+
+__device__ __forceinline__ void fps_large_short_body(int n, int m, const float *__restrict__ src, int *__restrict__ dst,
+                                                     float *__restrict__ dxyz, char *smem)
+{
+    constexpr int T = kLgT, W = kLgW, P = kLgShortP;
+    float4 *pts = reinterpret_cast<float4 *>(smem);                                        // [n]
+    unsigned long long *part = reinterpret_cast<unsigned long long *>(smem + kLgKeyOff);   // [2][W]
+    const int t = threadIdx.x, lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+
+    if (t == 0) {
+        dst[0] = 0;                                         // the first sample is point 0 (tf_sampling_g.cu:114-116)
+        if (dxyz) { dxyz[0] = src[0]; dxyz[1] = src[1]; dxyz[2] = src[2]; }
+    }
+    if (m == 1) return;                                     // workgroup-uniform, before any barrier
+
+    float px[P], py[P], pz[P], md[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const int k = t + T * r;
+        const int kk = k < n ? k : 0;                       // no such point: point 0's coordinates, key 0 below
+        px[r] = src[(size_t)kk * 3 + 0]; py[r] = src[(size_t)kk * 3 + 1]; pz[r] = src[(size_t)kk * 3 + 2];
+        md[r] = 1e38f;                                      // tf_sampling_g.cu:118
+        if (k < n) pts[k] = make_float4(px[r], py[r], pz[r], 0.0f);
+    }
+    __syncthreads();
+
+    int cur = 0;
+    for (int j = 1; j < m; ++j) {
+        const float4 s = pts[cur];                          // same address in every lane: LDS broadcast
+        unsigned long long best = 0ull;                     // (value bits << 32) | ~tiekey; real candidates are > 0
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+            if (T * r >= n) break;                          // workgroup-uniform
+            const int k = t + T * r;
+            const float d2 = __builtin_fminf(sqdist(px[r], py[r], pz[r], s.x, s.y, s.z), md[r]);   // min(d, td), tf_sampling_g.cu:144
+            md[r] = d2;
+            const unsigned tiekey = ((unsigned)(k & (kRefThreads - 1)) << 22) | (unsigned)(k >> 9);
+            const unsigned long long key =
+                k < n ? ((unsigned long long)(unsigned)__float_as_int(d2) << 32) | (unsigned long long)(0xFFFFFFFFu - tiekey) : 0ull;
+            best = key > best ? key : best;
+        }
+        best = lg_wave_max_u64(best);
+        if (lane == 0) part[(j & 1) * W + w] = best;
+        __syncthreads();
+        unsigned long long v = (lane < W) ? part[(j & 1) * W + lane] : 0ull;
+#pragma unroll
+        for (int sh = 1; sh < W; sh <<= 1) {
+            const unsigned long long o = lg_shfl_xor_u64(v, sh);
+            v = o > v ? o : v;
+        }
+        const unsigned tiekey = 0xFFFFFFFFu - (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+        cur = (int)(((tiekey & 0x3FFFFFu) << 9) | (tiekey >> 22));
+        if (t == 0) {
+            dst[j] = cur;
+            if (dxyz) {
+                const float4 q = pts[cur];
+                dxyz[j * 3 + 0] = q.x; dxyz[j * 3 + 1] = q.y; dxyz[j * 3 + 2] = q.z;
+            }
+        }
+    }
+}
+
 template <int L>
 __global__ __launch_bounds__(kLgT) void fps_large_kernel(int n, int m, const float *__restrict__ xyz, float4 *__restrict__ recs_all,
                                                          float *__restrict__ md_all, int *__restrict__ out, float *__restrict__ out_xyz)
@@ -422,6 +500,34 @@ __global__ __launch_bounds__(kLgT) void fps_large_ragged_kernel(int n, int m, co
     if (COUNTS) fps_ragged_fill<kLgT>(mc, m, src, dst, dxyz);
 }
 
+// Packed batch (pn2_farthest_point_sample_large_packed): cloud c is rows offsets[c] .. offsets[c + 1] - 1 of the flat (total, 3)
+// array, at most n = nmax of them (cloud_start / cloud_count, pn2_device.h: clamped, block-uniform scalars). The records and the
+// running distances of the cloud are the same rows of the workspace's two arrays (total entries each: recs_all + start stays
+// 16-byte aligned, coordinates are read as scalars), and the body runs on them with n = n_c exactly as in
+// fps_large_ragged_kernel: the list above that kernel holds word for word with n_c taken from offsets (there are no counts and no
+// fill here). A cloud of at most short_max <= kLgShortCap points takes fps_large_short_body instead: one block-uniform branch
+// behind the slab prologue, every barrier of either body inside its own side, and neither recs nor md touched. global_idx:
+// fps_global_rows (fps_body.h) behind the body -- both bodies return at m == 1 workgroup-uniformly and before any barrier, so its
+// barrier is reached by all threads.
+template <int L>
+__global__ __launch_bounds__(kLgT) void fps_large_packed_kernel(int n, int m, int short_max, const float *__restrict__ xyz,
+                                                                float4 *__restrict__ recs_all, float *__restrict__ md_all,
+                                                                int *__restrict__ out, float *__restrict__ out_xyz, Packed pk)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int c = blockIdx.x;
+    const int start = cloud_start(pk, c);
+    const int nc = cloud_count(pk, c, start, n);
+    const float *__restrict__ src = xyz + (size_t)start * 3;
+    int *__restrict__ dst = out + (size_t)c * m;
+    float *__restrict__ dxyz = out_xyz ? out_xyz + (size_t)c * m * 3 : nullptr;
+    if (nc <= min(__builtin_amdgcn_readfirstlane(short_max), kLgShortCap))
+        fps_large_short_body(nc, m, src, dst, dxyz, smem);
+    else
+        fps_large_body<L, true>(nc, m, src, recs_all + start, md_all + start, dst, dxyz, smem);
+    fps_global_rows<kLgT>(m, pk.global_idx ? start : 0, dst);
+}
+
 template <int L>
 static int launch_large(int b, int n, int m, const float *inp, void *ws, int *out, float *oxyz, hipStream_t st)
 {
@@ -444,6 +550,19 @@ static int launch_large_ragged(int b, int n, int m, const float *inp, const int 
 // fps.hip: the global-memory kernel with counts (running distances in temp, (b, n) floats)
 int fps_launch_generic_ragged(int b, int n, int m, const float *inp, const int *lengths, const int *npoints, float *temp, int *out,
                               float *oxyz, hipStream_t st);
+
+// ... and in the packed mode (temp: pk.total floats)
+int fps_launch_generic_packed(int b, int n, int m, const float *inp, Packed pk, float *temp, int *out, float *oxyz, hipStream_t st);
+
+// packed: the workspace is pk.total records, then pk.total running distances
+template <int L>
+static int launch_large_packed(int b, int n, int m, int short_max, const float *inp, Packed pk, void *ws, int *out, float *oxyz,
+                               hipStream_t st)
+{
+    float4 *recs = static_cast<float4 *>(ws);
+    float *md = reinterpret_cast<float *>(recs + (size_t)pk.total);
+    return launch_lds(fps_large_packed_kernel<L>, dim3(b), dim3(kLgT), kLgLdsBytes, st, n, m, short_max, inp, recs, md, out, oxyz, pk);
+}
 
 static bool large_covers(int n) { return n > kLgMinPoints && n <= kLgMaxPoints; }
 
@@ -531,4 +650,53 @@ extern "C" int pn2_farthest_point_sample_large_ragged(int b, int n, int m, const
                                                       void *ws, int *out, float *out_xyz, void *stream)
 {
     return pn2_farthest_point_sample_large_ragged_ex(0, 256, b, n, m, inp, lengths, npoints, ws, out, out_xyz, stream);
+}
+
+// Packed batch of large clouds: cloud c is inp[offsets[c] : offsets[c + 1]] of a flat (total, 3) array, offsets (b + 1) int32 on
+// the device and never read by the host; 16384 < nmax <= 1048576 bounds every cloud's count and takes the padded n's place in every
+// host decision. The workspace follows the flat array: total records, then total running distances.
+extern "C" long long pn2_fps_large_packed_ws_bytes(int total) { return total > 0 ? (long long)total * 20 : 0; }
+
+// short_max = -1, the library's rule (measured, profiles/fps_large_packed/README.md: medians of 20, b = 8 clouds of n_c points,
+// the tier's cell-sorted body over the short body, uniform-cube / sphere-surface clouds; nmax = 20000 and 131072 agree to 2 %):
+//   n_c = 1024: 1.67 / 1.67 at m = 256, 1.62 / 1.62 at m = 1024;   2048: 1.75 / 1.73, 1.68 / 1.66;
+//   4096: 1.93 / 1.85, 1.81 / 1.74;                                  8192: 2.05 / 1.91, 1.78 / 1.67.
+// The largest measured n_c at which the short body was ahead for both kinds and both m -- its capacity.
+constexpr int kLgShortRule = 8192;
+static_assert(kLgShortRule <= pn2::kLgShortCap, "the rule stays inside the short body's capacity");
+
+extern "C" int pn2_farthest_point_sample_large_packed_ex(int kernel, int group_len, int short_max, int b, int total, int nmax, int m,
+                                                         const float *inp, const int *offsets, int global_idx, void *ws, int *out,
+                                                         float *out_xyz, void *stream)
+{
+    using namespace pn2;
+    if (m <= 0 || b == 0) return PN2_OK;
+    if (b < 0 || nmax <= 0 || total <= 0) return PN2_E_SHAPE;
+    if (!inp || !offsets || !out || !ws) return PN2_E_NULL;
+    if (!large_covers(nmax)) return PN2_E_TOO_LARGE;
+    if ((long long)total * 3 > INT_MAX || (long long)b * m * 3 > INT_MAX) return PN2_E_TOO_LARGE;
+    if (kernel < 0 || kernel > 2) return PN2_E_ARG;
+    if (group_len != 64 && group_len != 128 && group_len != 256) return PN2_E_ARG;
+    if (short_max < -1 || short_max > kLgShortCap) return PN2_E_ARG;
+    const bool tier = kernel == 2 || (kernel == 0 && pn2_fps_large_pays(nmax, m));
+    if (tier && ((long long)nmax + group_len - 1) / group_len > kLgMaxGroups) return PN2_E_TOO_LARGE;   // four box slots per lane
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return PN2_E_ARG;                                          // 16-byte records
+    hipStream_t st = as_stream(stream);
+    const Packed pk = {offsets, total, global_idx ? 1 : 0};
+    if (!tier) {
+        float *md = reinterpret_cast<float *>(static_cast<float4 *>(ws) + (size_t)total);
+        return fps_launch_generic_packed(b, nmax, m, inp, pk, md, out, out_xyz, st);
+    }
+    const int sm = short_max < 0 ? kLgShortRule : short_max;
+    switch (group_len) {
+    case 64: return launch_large_packed<64>(b, nmax, m, sm, inp, pk, ws, out, out_xyz, st);
+    case 128: return launch_large_packed<128>(b, nmax, m, sm, inp, pk, ws, out, out_xyz, st);
+    default: return launch_large_packed<256>(b, nmax, m, sm, inp, pk, ws, out, out_xyz, st);
+    }
+}
+
+extern "C" int pn2_farthest_point_sample_large_packed(int b, int total, int nmax, int m, const float *inp, const int *offsets,
+                                                      int global_idx, void *ws, int *out, float *out_xyz, void *stream)
+{
+    return pn2_farthest_point_sample_large_packed_ex(0, 256, -1, b, total, nmax, m, inp, offsets, global_idx, ws, out, out_xyz, stream);
 }

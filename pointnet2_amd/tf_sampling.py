@@ -191,10 +191,14 @@ FPS_RAGGED_LARGE_MAX_POINTS = 1048576   # the large-cloud entry's (pn2_farthest_
 # the ValueError below. On, a padded n of 16385 .. 1048576 goes through pn2_farthest_point_sample_large_ragged_ex with a workspace
 # allocated per call; set_fps_large chooses its kernel (None = pn2_fps_large_pays on the padded n and npoint, True = the
 # cell-sorted tier, False = the global-memory kernel with counts). A tier forced with set_fps_variant keeps the 16384 limit.
+# The switch covers BOTH variable-size layouts: with `offsets=`, max_points of 16385 .. 1048576 goes through
+# pn2_farthest_point_sample_large_packed_ex (_fps_packed below) with the same three kernel modes and the library's short-cloud rule.
 _FPS_RAGGED_LARGE = [False]
 
 
 def set_fps_ragged_large(flag=False):
+    """Variable-size batches beyond 16384 points per cloud, in both layouts: padded (`lengths=` / `npoints=`, the padded n) and
+    packed (`offsets=` / `max_points=`). Off, both stop at 16384 with a ValueError; on, both reach 1048576."""
     require(isinstance(flag, bool), "fps ragged large flag must be True or False")
     _FPS_RAGGED_LARGE[0] = flag
 
@@ -231,16 +235,27 @@ def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
 def _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, out, want_xyz, op):
     """The packed form of both sampling operators (pn2_farthest_point_sample_packed): inp (total, 3), offsets (b + 1,) on the
     device, max_points a host int. -> idx (b, npoint), new_xyz (b, npoint, 3) or None. A tier forced with set_fps_variant
-    applies; nothing synchronises."""
+    applies; nothing synchronises. max_points of 16385 .. 1048576 under set_fps_ragged_large(True):
+    pn2_farthest_point_sample_large_packed_ex with a workspace of 20 bytes per row of the flat array, allocated per call."""
     require(npoints is None, "%s: per-cloud sample counts (npoints=) are not offered with offsets" % op)
     offs, b, total, nmax = packed_args(offsets, max_points, lengths, inp, op)           # (before anything else, like lengths_for)
-    require(nmax <= FPS_RAGGED_MAX_POINTS, "%s with offsets supports at most %d points per cloud, got max_points = %d"
-            % (op, FPS_RAGGED_MAX_POINTS, nmax))
+    large = _FPS_RAGGED_LARGE[0] and not _FPS_VARIANT[0] and nmax > FPS_RAGGED_MAX_POINTS
+    limit = FPS_RAGGED_LARGE_MAX_POINTS if large else FPS_RAGGED_MAX_POINTS
+    require(nmax <= limit, "%s with offsets supports at most %d points per cloud, got max_points = %d" % (op, limit, nmax))
     inp = f32(inp.detach(), "inp")
     m = int(npoint)
     dev = inp.device
     out = out_or_empty(out, (b, m), torch.int32, dev)
     new_xyz = torch.empty((b, m, 3), dtype=torch.float32, device=dev) if want_xyz else None
+    if large:
+        lib = _C.lib()
+        kernel = {None: 0, True: 2, False: 1}[_FPS_LARGE[0]]
+        ws = torch.empty((lib.pn2_fps_large_packed_ws_bytes(total),), dtype=torch.uint8, device=dev)    # per call, on the flat array
+        with on_device(dev):
+            _C.check(lib.pn2_farthest_point_sample_large_packed_ex(kernel, 256, -1, b, total, nmax, m, ptr(inp), ptr(offs),
+                                                                   1 if global_idx else 0, ptr(ws), ptr(out), ptr(new_xyz),
+                                                                   stream_ptr(dev)), op)
+        return out, new_xyz
     with on_device(dev):
         _C.check(_C.lib().pn2_farthest_point_sample_packed(_FPS_VARIANT[0], b, total, nmax, m, ptr(inp), ptr(offs), 1 if global_idx else 0,
                                                            ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
