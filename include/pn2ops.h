@@ -550,6 +550,44 @@ int pn2_query_ball_group_xyz_msg_packed(int b, int total, int nmax, int m, int n
                                         const float *xyz1, const int *offsets1, const float *xyz2, int subtract_centroid,
                                         int global_idx, int *const *idx, int *const *pts_cnt, float *const *grouped_xyz, void *stream);
 
+/* The second side, packed: a count per cloud behind the offsets -- the sample counts of FPS, the valid rows of the dense query
+ * side (b,m,3) of the ball queries and of kNN. THE PAIR SLICE RULE ("ragged batches, the second side") COMBINED WITH THE SLICE
+ * RULE, PACKED: for cloud c with n_c = offsets[c + 1] - offsets[c] points and m_c valid rows on the second side, the rows
+ * j < m_c are bit- and index-identical to the dense entry on (flat[offsets[c] : offsets[c + 1]], xyz2[c, :m_c]) alone and to the
+ * _ragged_counts / _ragged_pair entry on the same clouds padded. No cloud reads a row of its neighbours; no query row at or
+ * beyond m_c is read. The rows j >= m_c are fully written with the padded twin's fixed values, except that under
+ * global_idx = 1 every index fill is offsets[c], the cloud's own first row, where the local form writes 0 -- the rule an empty
+ * ball already follows --, so idx - offsets[c] equals the padded twin everywhere and every stored index names a row of its own
+ * cloud. Counts are (b) int32 on the device, never read by the host, clamped on the device into 1..m for memory safety only.
+ * Every host decision (FPS tier, grid, LDS bytes, queries per workgroup, the multi-radius plan) comes from nmax and m as in the
+ * one-sided entries; no memset, no synchronisation, capturable, and a replay follows offsets and counts changed in place.
+ * Codes: those of the one-sided packed entry of the same family, in its order; npoints / lengths2 are required in the _counts
+ * / _pair entries (PN2_E_NULL where the offsets are checked).
+ *
+ * pn2_farthest_point_sample_packed_counts: cloud c yields npoints[c] samples; rows from there on repeat sample 0 -- index 0
+ *   (offsets[c] under global_idx) and the cloud's first point. PN2_E_TOO_LARGE for nmax > 16384.
+ * pn2_query_ball_group_xyz_packed_pair: fill rows idx 0 (offsets1[c]), pts_cnt 0, grouped_xyz +0.0.
+ * pn2_query_ball_group_xyz_msg_packed_pair: the same for every radius of the one launch; the plan is
+ *   pn2_query_ball_group_xyz_msg_plan(b, nmax, m, ...).
+ * pn2_knn_point_packed: pn2_knn_point with xyz1 (total,3) packed, xyz2 (b,m,3), val / idx (b,m,k). The first min(k, n_c) entries
+ *   of a row are pn2_knn_point's on the slice, the rest repeat entry 0 (pn2_knn_point_ragged). lengths2 NULL: every query row is
+ *   valid; else fill rows are val +0.0, idx 0 (offsets1[c]). Codes of pn2_knn_point_ragged with nmax where n stood: k <= 0
+ *   PN2_E_ARG; b < 0, nmax <= 0, m < 0 PN2_E_SHAPE; b m = 0 PN2_OK; total <= 0 PN2_E_SHAPE; a missing array PN2_E_NULL; k > nmax,
+ *   nmax > 14336 or total 3 > INT_MAX PN2_E_TOO_LARGE. */
+int pn2_farthest_point_sample_packed_counts(int variant, int b, int total, int nmax, int m, const float *inp, const int *offsets,
+                                            const int *npoints, int global_idx, int *out, float *out_xyz /* may be NULL */,
+                                            void *stream);
+int pn2_query_ball_group_xyz_packed_pair(int b, int total, int nmax, int m, float radius, int nsample, const float *xyz1,
+                                         const int *offsets1, const float *xyz2, const int *lengths2, int subtract_centroid,
+                                         int global_idx, int *idx, int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb,
+                                         void *stream);
+int pn2_query_ball_group_xyz_msg_packed_pair(int b, int total, int nmax, int m, int nscales, const float *radii, const int *nsamples,
+                                             const float *xyz1, const int *offsets1, const float *xyz2, const int *lengths2,
+                                             int subtract_centroid, int global_idx, int *const *idx, int *const *pts_cnt,
+                                             float *const *grouped_xyz, void *stream);
+int pn2_knn_point_packed(int b, int total, int nmax, int m, int k, const float *xyz1, const int *offsets1, const float *xyz2,
+                         const int *lengths2 /* may be NULL */, int global_idx, float *val, int *idx, void *stream);
+
 /* farthest_point_sample [+ gather_point when out_xyz != NULL] for LARGE dense clouds, 16384 < n <= 1048576: the tier of
  * csrc/fps_large.hip. Same indices as pn2_farthest_point_sample, tie rule (smallest (k mod 512, k)), inf
  * distances clamped to the 1e38 start value, duplicates and m > n included; out_xyz == gather_point(inp, out) bit for bit, written

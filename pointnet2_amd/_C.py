@@ -155,6 +155,10 @@ _SIGNATURES = {
     "pn2_query_ball_group_xyz_packed": [_i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
     "pn2_three_nn_packed": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp],
     "pn2_query_ball_group_xyz_msg_packed": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "pn2_farthest_point_sample_packed_counts": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp],
+    "pn2_query_ball_group_xyz_packed_pair": [_i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "pn2_query_ball_group_xyz_msg_packed_pair": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp],
+    "pn2_knn_point_packed": [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp],
     "pn2_fps_large_ws_bytes": [_i, _i],
     "pn2_fps_large_supported": [_i, _i],
     "pn2_fps_large_pays": [_i, _i],

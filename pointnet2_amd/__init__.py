@@ -18,7 +18,7 @@ from .tf_grouping import (query_ball_point, group_point, knn_point, select_top_k
                           query_ball_group_xyz, query_ball_group_xyz_msg, sample_and_group_xyz)
 from .tf_interpolate import three_nn, three_interpolate  # noqa: F401
 from ._tensors import set_deterministic, is_deterministic, check_lengths  # noqa: F401
-from ._tensors import check_offsets, pack_batch, packed_offsets, unpack_batch  # noqa: F401
+from ._tensors import check_offsets, pack_batch, packed_offsets, set_packed_pairs, unpack_batch  # noqa: F401
 from .index_plan import IndexPlan, index_plan  # noqa: F401
 
 __version__ = "0.3.0"

@@ -154,6 +154,22 @@ def packed_args(offsets, max_points, lengths, flat, what, name="offsets", max_na
     return offs, int(offs.shape[0]) - 1, total, nmax
 
 
+_packed_pairs = False
+
+
+def set_packed_pairs(flag):
+    """Offer the second side of packed batches ("the second side, packed"): npoints= with offsets= in the sampling
+    operators, lengths2= with offsets= in the ball queries, knn= / npoints= with offsets= in sample_and_group and the SA module,
+    lengths2= with offsets1= in the FP module. Process-wide, off by default: every such call is refused as before."""
+    global _packed_pairs
+    require(isinstance(flag, bool), "set_packed_pairs expects a bool")
+    _packed_pairs = flag
+
+
+def packed_pairs():
+    return _packed_pairs
+
+
 def check_offsets(offsets, total, max_points=None):
     """Validate the offsets of a packed batch of `total` rows: an int32 / int64 tensor (or a sequence) of shape (b + 1,) with
     offsets[0] = 0, offsets[b] = total and every cloud's count offsets[c + 1] - offsets[c] in 1..max_points. Raises ValueError.

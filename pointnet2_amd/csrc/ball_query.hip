@@ -48,6 +48,8 @@ namespace pn2 {
 // Packed (pn2_query_ball_group_xyz_packed; pn2_device.h: Packed): the one-array mode with the cloud's slab taken from the
 // offsets -- xyz1 is the flat (total, 3) array, n is nmax, the queries and the outputs stay dense (b, m, ...). With global_idx
 // the stored indices are rows of the flat array; the grouped rows are gathered with the local index as before.
+// Packed with one count array (pn2_query_ball_group_xyz_packed_pair): the two combined -- the slab from the offsets, m_c from
+// lengths2; the fill rows store the cloud's own first row (offsets[c] under global_idx, else 0) as their index.
 template <bool LDS_CLOUD, bool FUSE, class... Cnt>
 __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(int n, int m, int nsample, float thr, int qpb,
                                                                 const float *__restrict__ xyz1,
@@ -67,7 +69,15 @@ __global__ __launch_bounds__(kBqThreads) void ball_query_kernel(int n, int m, in
         const int nc = cloud_count(counts.pk, c, start, n);
         const int q0 = blockIdx.x * qpb;
         const size_t rows = (size_t)c * m;
-        bq_block_body<LDS_CLOUD, FUSE, false>(nc, m, nsample, thr, 0, q0, min(q0 + qpb, m), xyz1 + (size_t)start * 3, xyz2 + rows * 3,
+        int mc = m;
+        if constexpr (sizeof...(Cnt) == 2) {
+            mc = cloud_count(counts.side[1], c, m);
+            bq_fill_rows<kBqThreads>(max(q0, mc), min(q0 + qpb, m), nsample, idx ? idx + rows * nsample : nullptr,
+                                     pts_cnt ? pts_cnt + rows : nullptr, grouped ? grouped + rows * nsample * 3 : nullptr,
+                                     counts.pk.global_idx ? start : 0);
+            if (q0 >= mc) return;
+        }
+        bq_block_body<LDS_CLOUD, FUSE, false>(nc, m, nsample, thr, 0, q0, min(q0 + qpb, mc), xyz1 + (size_t)start * 3, xyz2 + rows * 3,
                                               nullptr, nullptr, idx ? idx + rows * nsample : nullptr, pts_cnt ? pts_cnt + rows : nullptr,
                                               grouped ? grouped + rows * nsample * 3 : nullptr, subtract, smem, 1u, 0, nullptr,
                                               counts.pk.global_idx ? start : 0);
@@ -105,7 +115,7 @@ static int launch_bq(int b, int n, int m, float thr, int nsample, const float *x
     const size_t lds = (LDS_CLOUD ? sizeof(float4) * (size_t)((n + 127) & ~127) : 0) + sizeof(int) * (size_t)nsample * kGran;
     if (lds > 160 * 1024) return PN2_E_TOO_LARGE;
     if (pk)
-        return launch_counts_packed<false>([](auto... c) { return ball_query_kernel<LDS_CLOUD, FUSE, decltype(c)...>; }, *pk, nullptr,
+        return launch_counts_packed<true>([](auto... c) { return ball_query_kernel<LDS_CLOUD, FUSE, decltype(c)...>; }, *pk, lengths2,
                                            dim3(gx, b), dim3(kBqThreads), lds, st, n, m, nsample, thr, qpb, xyz1, xyz2, idx, pts_cnt, grouped,
                                            subtract);
     return launch_counts([](auto... c) { return ball_query_kernel<LDS_CLOUD, FUSE, decltype(c)...>; }, lengths, lengths2, dim3(gx, b),
@@ -139,13 +149,19 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_cells_kernel(int b, i
         const int start = cloud_start(counts.pk, cloud);
         const int nc = cloud_count(counts.pk, cloud, start, n);
         const int ibase = counts.pk.global_idx ? start : 0;
-        const int q0 = part * qpb, q1 = min(q0 + qpb, m);
+        int mc = m;
+        if constexpr (sizeof...(Cnt) == 2) mc = cloud_count(counts.side[1], cloud, m);
+        const int q0 = part * qpb, q1 = min(q0 + qpb, mc);
         const size_t rows = (size_t)cloud * m;
         const float *__restrict__ x1 = xyz1 + (size_t)start * 3;
         const float *__restrict__ x2 = xyz2 + rows * 3;
         int *__restrict__ oi = idx ? idx + rows * nsample : nullptr;
         int *__restrict__ oc = pts_cnt ? pts_cnt + rows : nullptr;
         float *__restrict__ og = grouped ? grouped + rows * nsample * 3 : nullptr;
+        if constexpr (sizeof...(Cnt) == 2) {
+            bq_fill_rows<NT>(max(q0, mc), min(q0 + qpb, m), nsample, oi, oc, og, ibase);
+            if (q0 >= mc) return;
+        }
         if (nc < 64)
             bq_block_body<true, FUSE, false, NT>(nc, m, nsample, thr, 0, q0, q1, x1, x2, nullptr, nullptr, oi, oc, og, subtract, smem, 1u, 0,
                                                  nullptr, ibase);
@@ -227,7 +243,7 @@ static int launch_bq_cells(int b, int n, int m, float thr, float radius, int nsa
     const size_t a = bq_cells_lds_bytes(n, nsample, LPQ, NT), s = bq_sweep_lds_bytes(n, nsample, NT);
     const size_t lds = a > s ? a : s;                       // the fallback inside the kernel uses the sweep layout
     if (pk)
-        return launch_counts_packed<false>([](auto... c) { return ball_query_cells_kernel<NT, LPQ, FUSE, decltype(c)...>; }, *pk, nullptr,
+        return launch_counts_packed<true>([](auto... c) { return ball_query_cells_kernel<NT, LPQ, FUSE, decltype(c)...>; }, *pk, lengths2,
                                            dim3((unsigned)gx * b), dim3(NT), lds, st, b, n, m, nsample, thr, radius, qpb, gx, xyz1, xyz2, idx,
                                            pts_cnt, grouped, subtract);
     return launch_counts([](auto... c) { return ball_query_cells_kernel<NT, LPQ, FUSE, decltype(c)...>; }, lengths, lengths2,
@@ -373,17 +389,40 @@ extern "C" int pn2_query_ball_group_xyz_ragged_pair(int b, int n, int m, float r
 // and the LDS size. The queries xyz2 (b, m, 3) and the outputs are dense. Result per cloud = pn2_query_ball_group_xyz_ex on the
 // slice for every `kernel`; global_idx 1 writes idx as offsets1[c] + k. grouped_xyz == NULL: plain query_ball_point. Codes in
 // the order of pn2_query_ball_group_xyz_ragged (PN2_E_TOO_LARGE for total 3 > INT_MAX).
-extern "C" int pn2_query_ball_group_xyz_packed(int b, int total, int nmax, int m, float radius, int nsample, const float *xyz1,
-                                               const int *offsets1, const float *xyz2, int subtract_centroid, int global_idx, int *idx,
-                                               int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb, void *stream)
+// The packed entries' prologue and launch; sides == 2 requires lengths2.
+static int ball_query_packed(int sides, int b, int total, int nmax, int m, float radius, int nsample, const float *xyz1,
+                             const int *offsets1, const float *xyz2, const int *lengths2, int subtract_centroid, int global_idx, int *idx,
+                             int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb, void *stream)
 {
     if (kernel < 0 || kernel > 3 || cells_qpb < 0) return PN2_E_ARG;
     if (!(radius > 0.0f) || nsample <= 0) return PN2_E_ARG;
     if (b < 0 || nmax <= 0 || m < 0) return PN2_E_SHAPE;
     if (b == 0 || m == 0) return PN2_OK;
     if (total <= 0) return PN2_E_SHAPE;
-    if (!offsets1) return PN2_E_NULL;
+    if (!offsets1 || (sides == 2 && !lengths2)) return PN2_E_NULL;
     const pn2::Packed pk = {offsets1, total, global_idx ? 1 : 0};
     return pn2::ball_query_common(b, nmax, m, radius, nsample, xyz1, xyz2, grouped_xyz ? subtract_centroid : 0, idx, pts_cnt, grouped_xyz,
-                                  grouped_xyz != nullptr, {kernel, cells_qpb}, stream, nullptr, nullptr, &pk);
+                                  grouped_xyz != nullptr, {kernel, cells_qpb}, stream, nullptr, lengths2, &pk);
+}
+
+extern "C" int pn2_query_ball_group_xyz_packed(int b, int total, int nmax, int m, float radius, int nsample, const float *xyz1,
+                                               const int *offsets1, const float *xyz2, int subtract_centroid, int global_idx, int *idx,
+                                               int *pts_cnt, float *grouped_xyz, int kernel, int cells_qpb, void *stream)
+{
+    return ball_query_packed(1, b, total, nmax, m, radius, nsample, xyz1, offsets1, xyz2, nullptr, subtract_centroid, global_idx, idx,
+                             pts_cnt, grouped_xyz, kernel, cells_qpb, stream);
+}
+
+// Packed on the first side, ragged on the second: cloud c additionally holds only lengths2[c] valid rows of xyz2 ((b) int32 on
+// the device, clamped into 1..m, never read by the host). Rows below lengths2[c] = pn2_query_ball_group_xyz_ex on the slice
+// pair = pn2_query_ball_group_xyz_ragged_pair on the padded copy; the rows from lengths2[c] on are written as pts_cnt 0,
+// grouped_xyz +0.0 and idx 0 -- offsets1[c] under global_idx, the cloud's own first row -- and their queries are never read.
+// Codes in the order of pn2_query_ball_group_xyz_packed; lengths2 is required (PN2_E_NULL where offsets1 is).
+extern "C" int pn2_query_ball_group_xyz_packed_pair(int b, int total, int nmax, int m, float radius, int nsample, const float *xyz1,
+                                                    const int *offsets1, const float *xyz2, const int *lengths2, int subtract_centroid,
+                                                    int global_idx, int *idx, int *pts_cnt, float *grouped_xyz, int kernel,
+                                                    int cells_qpb, void *stream)
+{
+    return ball_query_packed(2, b, total, nmax, m, radius, nsample, xyz1, offsets1, xyz2, lengths2, subtract_centroid, global_idx, idx,
+                             pts_cnt, grouped_xyz, kernel, cells_qpb, stream);
 }

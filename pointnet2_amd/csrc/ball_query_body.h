@@ -131,16 +131,17 @@ __device__ __forceinline__ int bq_poll_sample(const unsigned long long *tagged, 
 
 // The output rows [r0, r1) of one cloud (idx / pts_cnt / grouped already moved to the cloud's row 0) that belong to no valid
 // query: idx all 0, pts_cnt 0, grouped_xyz all +0.0 -- fixed values, so everything downstream stays in range and finite.
-// Nothing is read; the whole workgroup (NT threads) takes part, no barrier.
+// Nothing is read; the whole workgroup (NT threads) takes part, no barrier. ifill: the index written (block-uniform; the packed
+// mode's global_idx stores the cloud's own first row, like an empty ball's ibase + 0); the literal 0 of every other caller folds.
 template <int NT>
 __device__ __forceinline__ void bq_fill_rows(int r0, int r1, int nsample, int *__restrict__ idx, int *__restrict__ pts_cnt,
-                                             float *__restrict__ grouped)
+                                             float *__restrict__ grouped, int ifill = 0)
 {
     if (r0 >= r1) return;
     const int t = threadIdx.x;
     const size_t e0 = (size_t)r0 * nsample, e1 = (size_t)r1 * nsample;
     if (idx)
-        for (size_t e = e0 + t; e < e1; e += NT) idx[e] = 0;
+        for (size_t e = e0 + t; e < e1; e += NT) idx[e] = ifill;
     if (grouped)
         for (size_t e = e0 * 3 + t; e < e1 * 3; e += NT) grouped[e] = 0.0f;
     if (pts_cnt)

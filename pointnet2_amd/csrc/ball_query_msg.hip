@@ -138,6 +138,8 @@ __device__ __forceinline__ void bq_msg_block_body(int n, int m, int cloud, int q
 // the padded n, and the argument above carries over word for word: what fits nmax fits nc. A slab may start at ANY row of the
 // flat array -- no alignment is asked of offsets -- because the body reads coordinates as scalars (staging, binning and the
 // FUSE gather all go through data[k * 3 + {0, 1, 2}]). With global_idx the stored indices are rows of the flat array.
+// Packed with one count array (pn2_query_ball_group_xyz_msg_packed_pair): m_c = lengths2[c] as in the two-array mode; the fill
+// rows of every radius store the cloud's own first row (offsets[c] under global_idx, else 0) as their index.
 template <int NT, class... Cnt>
 __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int n, int m, int qpb, int parts,
                                                                     int use_cells, int max_ns, int wave_stride_b, BqScales sc,
@@ -156,7 +158,20 @@ __global__ __launch_bounds__(NT, NT / 256) void ball_query_msg_kernel(int b, int
         const int nc = cloud_count(counts.pk, cloud, start, n);
         const int q0 = part * qpb;
         const size_t rows = (size_t)cloud * m;
-        bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, m), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
+        int mc = m;
+        if constexpr (sizeof...(Cnt) == 2) {                         // the second side's counts, as in the two-array mode below
+            mc = cloud_count(counts.side[1], cloud, m);
+            const int f0 = max(q0, mc), f1 = min(q0 + qpb, m);
+            if (f0 < f1) {                                           // block-uniform
+                for (int i = 0; i < sc.count; ++i) {
+                    const BqScale &s = sc.s[i];
+                    bq_fill_rows<NT>(f0, f1, s.nsample, s.idx ? s.idx + rows * (size_t)s.nsample : nullptr, s.cnt ? s.cnt + rows : nullptr,
+                                     s.grouped ? s.grouped + rows * (size_t)s.nsample * 3 : nullptr, counts.pk.global_idx ? start : 0);
+                }
+            }
+            if (q0 >= mc) return;
+        }
+        bq_msg_block_body<NT>(nc, m, 0, q0, min(q0 + qpb, mc), (use_cells && nc >= 64) ? 1 : 0, max_ns, wave_stride_b, sc,
                               xyz1 + (size_t)start * 3, xyz2 + rows * 3, subtract, rows, smem, counts.pk.global_idx ? start : 0);
     } else {
         const int nc = cloud_count(counts.side[0], cloud, n);
@@ -298,7 +313,7 @@ static int launch_msg(int b, int n, int m, const MsgPlan &p, const float *xyz1, 
 {
     // with counts the same plan: every host decision is taken from the padded n (packed: from nmax)
     if (pk)
-        return launch_counts_packed<false>([](auto... c) { return ball_query_msg_kernel<NT, decltype(c)...>; }, *pk, nullptr,
+        return launch_counts_packed<true>([](auto... c) { return ball_query_msg_kernel<NT, decltype(c)...>; }, *pk, lengths2,
                                            dim3((unsigned)p.parts * b), dim3(NT), p.lds, st, b, n, m, p.qpb, p.parts, p.use_cells,
                                            p.max_ns, (int)p.wave_stride, p.sc, xyz1, xyz2, subtract);
     return launch_counts([](auto... c) { return ball_query_msg_kernel<NT, decltype(c)...>; }, lengths1, lengths2,
@@ -402,16 +417,37 @@ extern "C" int pn2_query_ball_group_xyz_msg_ragged_pair(int b, int n, int m, int
 // pn2_query_ball_group_xyz_msg_ragged on the padded copy; global_idx 1 writes idx as offsets1[c] + k. Codes in the order of
 // pn2_query_ball_group_xyz_msg_ragged with offsets1 where lengths1 stood; total <= 0 or nmax > total is PN2_E_SHAPE, total 3 >
 // INT_MAX PN2_E_TOO_LARGE.
+static int msg_run_packed(int sides, int b, int total, int nmax, int m, int nscales, const float *radii, const int *nsamples,
+                          const float *xyz1, const int *offsets1, const float *xyz2, const int *lengths2, int subtract_centroid,
+                          int global_idx, int *const *idx, int *const *pts_cnt, float *const *grouped_xyz, void *stream)
+{
+    if (int rc = pn2::msg_check_args(b, nmax, m, nscales, radii, nsamples)) return rc;
+    if (b == 0 || m == 0) return PN2_OK;
+    if (total <= 0 || nmax > total) return PN2_E_SHAPE;
+    if (!offsets1 || (sides == 2 && !lengths2)) return PN2_E_NULL;
+    const pn2::Packed pk = {offsets1, total, global_idx ? 1 : 0};
+    return msg_run(b, nmax, m, nscales, radii, nsamples, xyz1, nullptr, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream,
+                   lengths2, &pk);
+}
+
 extern "C" int pn2_query_ball_group_xyz_msg_packed(int b, int total, int nmax, int m, int nscales, const float *radii,
                                                    const int *nsamples, const float *xyz1, const int *offsets1, const float *xyz2,
                                                    int subtract_centroid, int global_idx, int *const *idx, int *const *pts_cnt,
                                                    float *const *grouped_xyz, void *stream)
 {
-    if (int rc = pn2::msg_check_args(b, nmax, m, nscales, radii, nsamples)) return rc;
-    if (b == 0 || m == 0) return PN2_OK;
-    if (total <= 0 || nmax > total) return PN2_E_SHAPE;
-    if (!offsets1) return PN2_E_NULL;
-    const pn2::Packed pk = {offsets1, total, global_idx ? 1 : 0};
-    return msg_run(b, nmax, m, nscales, radii, nsamples, xyz1, nullptr, xyz2, subtract_centroid, idx, pts_cnt, grouped_xyz, stream,
-                   nullptr, &pk);
+    return msg_run_packed(1, b, total, nmax, m, nscales, radii, nsamples, xyz1, offsets1, xyz2, nullptr, subtract_centroid, global_idx,
+                          idx, pts_cnt, grouped_xyz, stream);
+}
+
+// Packed on the first side, ragged on the second: rows below lengths2[c] = pn2_query_ball_group_xyz_msg on the slice pair =
+// pn2_query_ball_group_xyz_packed_pair per radius = pn2_query_ball_group_xyz_msg_ragged_pair on the padded copy; the rows from
+// lengths2[c] on are written, for every radius, as pts_cnt 0, grouped_xyz +0.0 and idx 0 (offsets1[c] under global_idx). Codes
+// in the order of pn2_query_ball_group_xyz_msg_packed; lengths2 is required.
+extern "C" int pn2_query_ball_group_xyz_msg_packed_pair(int b, int total, int nmax, int m, int nscales, const float *radii,
+                                                        const int *nsamples, const float *xyz1, const int *offsets1,
+                                                        const float *xyz2, const int *lengths2, int subtract_centroid, int global_idx,
+                                                        int *const *idx, int *const *pts_cnt, float *const *grouped_xyz, void *stream)
+{
+    return msg_run_packed(2, b, total, nmax, m, nscales, radii, nsamples, xyz1, offsets1, xyz2, lengths2, subtract_centroid, global_idx,
+                          idx, pts_cnt, grouped_xyz, stream);
 }

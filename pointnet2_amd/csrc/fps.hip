@@ -84,7 +84,8 @@ __global__ __launch_bounds__(kBtT) void fps_batch_kernel(int n, int m, int Q, co
 // is prefix-consistent: round j depends on rounds < j alone). Rows m_c .. m-1 repeat sample 0, the way a ball query pads with its
 // first hit; sample 0 is point 0 by the reference's rule (tf_sampling_g.cu:114-116), so the fill is index 0 and xyz[c, 0] and
 // reads nothing back (fps_ragged_fill, fps_body.h). The fill rows are disjoint from the body's, so no barrier stands between the
-// two. Without COUNTS npoints is never read.
+// two. Without COUNTS npoints is never read. COUNTS on packed input (pn2_farthest_point_sample_packed_counts) composes the two: the
+// slab from the offsets, m_c from npoints; under global_idx the fill index is the cloud's own first row, offsets[c].
 template <class Tier, bool COUNTS, class... Pk>
 __global__ __launch_bounds__(Tier::threads) void fps_ragged_kernel(int n, int m, const float *__restrict__ xyz, const int *__restrict__ lengths,
                                                                    const int *__restrict__ npoints, int *__restrict__ out,
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(Tier::threads) void fps_ragged_kernel(int n, int m,
     const FpsSlab s = fps_slab<COUNTS>(blockIdx.x, n, m, xyz, lengths, npoints, out, out_xyz, pk...);
     Tier::body(s.nc, s.mc, (s.nc + kRefThreads - 1) / kRefThreads, s.src, s.dst, s.dxyz, smem);
     if constexpr (sizeof...(Pk) != 0) fps_global_rows<Tier::threads>(s.mc, s.base, s.dst);
-    if (COUNTS) fps_ragged_fill<Tier::threads>(s.mc, m, s.src, s.dst, s.dxyz);
+    if (COUNTS) fps_ragged_fill<Tier::threads>(s.mc, m, s.src, s.dst, s.dxyz, sizeof...(Pk) != 0 ? s.base : 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -376,12 +377,13 @@ static auto fps_ragged_launch(int b, int n, int m, const float *inp, const int *
     };
 }
 
-// Packed: n is nmax; lengths and npoints are NULL and never read
-static auto fps_packed_launch(int b, int n, int m, const float *inp, Packed pk, int *out, float *oxyz, hipStream_t st)
+// Packed: n is nmax; lengths is NULL and never read; npoints NULL = m samples from every cloud, else the per-cloud counts (COUNTS)
+static auto fps_packed_launch(int b, int n, int m, const float *inp, Packed pk, const int *npoints, int *out, float *oxyz, hipStream_t st)
 {
     return [=](auto tier) {
-        return launch_lds(fps_ragged_kernel<decltype(tier), false, Packed>, dim3(b), dim3(tier.threads), tier.lds, st, n, m, inp, nullptr,
-                          nullptr, out, oxyz, pk);
+        using Tier = decltype(tier);
+        return launch_lds(npoints ? fps_ragged_kernel<Tier, true, Packed> : fps_ragged_kernel<Tier, false, Packed>, dim3(b),
+                          dim3(tier.threads), tier.lds, st, n, m, inp, nullptr, npoints, out, oxyz, pk);
     };
 }
 
@@ -505,7 +507,7 @@ static int fps_ragged_entry(int b, int n, int m, const float *inp, const int *le
     hipStream_t st = as_stream(stream);
     FpsChoice c;
     if (int rc = fps_choose(variant, n, m, c)) return rc;
-    if (pk) return fps_with_tier(c, fps_packed_launch(b, n, m, inp, *pk, out, out_xyz, st));
+    if (pk) return fps_with_tier(c, fps_packed_launch(b, n, m, inp, *pk, npoints, out, out_xyz, st));
     return fps_with_tier(c, fps_ragged_launch(b, n, m, inp, lengths, npoints, out, out_xyz, st));
 }
 
@@ -545,6 +547,20 @@ extern "C" int pn2_farthest_point_sample_packed(int variant, int b, int total, i
     if (variant < PN2_FPS_AUTO || variant > PN2_FPS_BATCH) return PN2_E_ARG;
     const pn2::Packed pk = {offsets, total, global_idx ? 1 : 0};
     return fps_ragged_entry(b, nmax, m, inp, nullptr, nullptr, false, out, out_xyz, stream, variant, &pk);
+}
+
+// The same with a sample count per cloud, as pn2_farthest_point_sample_ragged_counts: cloud c yields m_c = npoints[c] samples
+// ((b) int32 on the device, clamped into 1..m, never read by the host). Rows below m_c = the first m_c samples of
+// pn2_farthest_point_sample_gather on the slice = pn2_farthest_point_sample_ragged_counts on the padded copy; rows m_c .. m-1
+// repeat sample 0: index 0 (offsets[c] under global_idx) and the cloud's first point. npoints is required; codes and envelope of
+// pn2_farthest_point_sample_packed (PN2_E_TOO_LARGE for nmax > 16384).
+extern "C" int pn2_farthest_point_sample_packed_counts(int variant, int b, int total, int nmax, int m, const float *inp,
+                                                       const int *offsets, const int *npoints, int global_idx, int *out, float *out_xyz,
+                                                       void *stream)
+{
+    if (variant < PN2_FPS_AUTO || variant > PN2_FPS_BATCH) return PN2_E_ARG;
+    const pn2::Packed pk = {offsets, total, global_idx ? 1 : 0};
+    return fps_ragged_entry(b, nmax, m, inp, nullptr, npoints, true, out, out_xyz, stream, variant, &pk);
 }
 
 // farthest_point_sample for input the caller BELIEVES to be in farthest-point order already (the previous level's samples:

@@ -374,14 +374,16 @@ __device__ __forceinline__ void fps_global_rows(int m, int base, int *dst)
 }
 
 // The rows m_c .. m-1 of a cloud that yields m_c < m samples (the ragged kernels with counts, fps.hip and fps_large.hip): sample
-// 0 repeated, i.e. index 0 and the cloud's first point -- nothing is read back.
+// 0 repeated, i.e. index 0 and the cloud's first point -- nothing is read back. ifill: the index written, the packed mode's base
+// under global_idx (the cloud's own first row; these rows lie behind fps_global_rows' and are disjoint from them), else 0.
 template <int T>
-__device__ __forceinline__ void fps_ragged_fill(int mc, int m, const float *__restrict__ src, int *__restrict__ dst, float *__restrict__ dxyz)
+__device__ __forceinline__ void fps_ragged_fill(int mc, int m, const float *__restrict__ src, int *__restrict__ dst, float *__restrict__ dxyz,
+                                                int ifill = 0)
 {
     if (mc < m) {                                          // block-uniform
         const float x0 = src[0], y0 = src[1], z0 = src[2];
         for (int j = mc + (int)threadIdx.x; j < m; j += T) {
-            dst[j] = 0;
+            dst[j] = ifill;
             if (dxyz) { dxyz[j * 3 + 0] = x0; dxyz[j * 3 + 1] = y0; dxyz[j * 3 + 2] = z0; }
         }
     }

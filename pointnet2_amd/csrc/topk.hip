@@ -152,8 +152,10 @@ __device__ __forceinline__ void knn_find_bin(const int *hist, int lane, int want
 
 // One wave, one query: `pts` the n points of the query's cloud, `q` the query, entries row * k .. of oval / oidx its output
 // (the first min(k, n) are written). Shared by the dense kernel and the ragged one (n = the cloud's own length there).
+// ibase: added to every index where it is stored (wave-uniform; the packed mode's global_idx, pn2_device.h). Every other caller
+// passes a literal 0, which folds away.
 __device__ __forceinline__ void knn_wave_body(int n, int k, const float *__restrict__ pts, const float *__restrict__ q,
-                                              float *__restrict__ oval, int *__restrict__ oidx, size_t row, char *smem)
+                                              float *__restrict__ oval, int *__restrict__ oidx, size_t row, char *smem, int ibase)
 {
     float *val = reinterpret_cast<float *>(smem);                                  // [n]  the distance row
     int *ind = reinterpret_cast<int *>(smem + sizeof(float) * (size_t)n);          // [n]  only for the fallback
@@ -237,7 +239,7 @@ __device__ __forceinline__ void knn_wave_body(int n, int k, const float *__restr
             if (best == win && best < dead) {                     // exactly one lane holds the winner
                 const int orig = cidx[bslot];
                 oval[row * k + s] = val[orig];
-                oidx[row * k + s] = orig;
+                oidx[row * k + s] = orig + ibase;
                 ckey[bslot] = 0x7ff00000u;                        // dead: never wins again
                 cpos[bslot] = 0;
             }
@@ -267,9 +269,25 @@ __device__ __forceinline__ void knn_wave_body(int n, int k, const float *__restr
         }
         for (int s = lane; s < rounds; s += 64) {
             oval[row * k + s] = val[s];
-            oidx[row * k + s] = ind[s];
+            oidx[row * k + s] = ind[s] + ibase;
         }
     }
+}
+
+// The two pieces every counted mode of knn_wave_kernel shares (one wave = one row; ov / oi: the row's k entries).
+// A row that belongs to no valid query: val +0.0 and the index `ifill` (0; the packed mode's global_idx: the cloud's first row).
+__device__ __forceinline__ void knn_fill_row(int k, float *ov, int *oi, int ifill)
+{
+    for (int s = (int)threadIdx.x; s < k; s += 64) { ov[s] = 0.0f; oi[s] = ifill; }
+}
+// k > n_c: the entries from n_c on repeat entry 0 as the body stored it (with its ibase).
+__device__ __forceinline__ void knn_repeat_entry0(int nc, int k, float *ov, int *oi)
+{
+    __syncthreads();                                             // one wave: orders the body's global stores before the reads below
+    __threadfence_block();
+    const float v0 = ov[0];
+    const int i0 = oi[0];
+    for (int s = nc + (int)threadIdx.x; s < k; s += 64) { ov[s] = v0; oi[s] = i0; }
 }
 
 // One kernel, three modes (pn2_device.h: Counts). No count array: the dense kernel. With counts (pn2_knn_point_ragged): the
@@ -278,38 +296,46 @@ __device__ __forceinline__ void knn_wave_body(int n, int k, const float *__restr
 // every row is fully written. Counts on both sides (pn2_knn_point_ragged_pair): cloud c also holds only lengths2[c] valid
 // queries. A wave whose row is at or beyond that count writes idx 0 / val +0.0 into the whole row and leaves -- its query is
 // never read (wave = workgroup here).
+// Packed (pn2_knn_point_packed; pn2_device.h: Packed): the one-array mode with the cloud's points taken from the offsets -- xyz1
+// is the flat (total, 3) array, n is nmax (the host's LDS size), the queries and the outputs stay dense (b, m, k). With
+// global_idx the stored indices are rows of the flat array. Packed with one count array: lengths2 as above; a fill row stores the
+// cloud's own first row (offsets[c] under global_idx, else 0) and +0.0.
 template <class... Cnt>
 __global__ __launch_bounds__(64) void knn_wave_kernel(int n, int m, int k, const float *__restrict__ xyz1,
                                                       const float *__restrict__ xyz2, float *__restrict__ oval,
-                                                      int *__restrict__ oidx, Cnt __restrict__... cnt)
+                                                      int *__restrict__ oidx, CountArg<Cnt>... cnt)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Counts<Cnt...> counts(cnt...);
     const size_t row = blockIdx.x;                               // query number over all clouds
     const size_t cloud = row / m;
     if constexpr (sizeof...(Cnt) == 0) {
-        knn_wave_body(n, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
+        knn_wave_body(n, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem, 0);
     } else {
+        constexpr bool packed = Counts<Cnt...>::packed;
+        int start = 0, ibase = 0;                                // packed: the cloud's first row of the flat array
+        if constexpr (packed) {
+            start = cloud_start(counts.pk, cloud);
+            ibase = counts.pk.global_idx ? start : 0;
+        }
         if constexpr (sizeof...(Cnt) == 2) {
             const int mc = cloud_count(counts.side[1], cloud, m);
-            float *ov = oval + row * k;
+            float *ov = oval + row * k;                          // (formed in front of the branch, as the padded mode always did)
             int *oi = oidx + row * k;
             if ((int)(row - cloud * m) >= mc) {                  // wave-uniform
-                for (int s = (int)threadIdx.x; s < k; s += 64) { ov[s] = 0.0f; oi[s] = 0; }
+                knn_fill_row(k, ov, oi, ibase);
                 return;
             }
         }
-        const int nc = cloud_count(counts.side[0], cloud, n);
-        knn_wave_body(nc, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem);
-        if (k > nc) {                                            // wave-uniform
-            float *ov = oval + row * k;
-            int *oi = oidx + row * k;
-            __syncthreads();                                     // one wave: orders the body's global stores before the reads below
-            __threadfence_block();
-            const float v0 = ov[0];
-            const int i0 = oi[0];
-            for (int s = nc + (int)threadIdx.x; s < k; s += 64) { ov[s] = v0; oi[s] = i0; }
+        int nc;
+        if constexpr (packed) {
+            nc = cloud_count(counts.pk, cloud, start, n);
+            knn_wave_body(nc, k, xyz1 + (size_t)start * 3, xyz2 + row * 3, oval, oidx, row, smem, ibase);
+        } else {
+            nc = cloud_count(counts.side[0], cloud, n);
+            knn_wave_body(nc, k, xyz1 + cloud * n * 3, xyz2 + row * 3, oval, oidx, row, smem, 0);
         }
+        if (k > nc) knn_repeat_entry0(nc, k, oval + row * k, oidx + row * k);   // wave-uniform
     }
 }
 
@@ -362,19 +388,26 @@ extern "C" int pn2_selection_sort(int b, int n, int m, int k, const float *dist,
     return PN2_OK;
 }
 
-// The three entries of knn_point; `sides` = the count arrays the entry requires (lengths1, then lengths2)
+// The entries of knn_point; `sides` = the count arrays the entry requires (lengths1, then lengths2). pk: the packed mode -- n is
+// nmax, xyz1 holds pk->total rows, lengths1 is unused and lengths2 optional.
 static int knn_entry(int sides, int b, int n, int m, int k, const float *xyz1, const int *lengths1, const float *xyz2, const int *lengths2,
-                     float *val, int *idx, void *stream)
+                     float *val, int *idx, void *stream, const pn2::Packed *pk = nullptr)
 {
     using namespace pn2;
     if (k <= 0) return PN2_E_ARG;                       // tf_grouping.cpp:113
     if (b < 0 || n <= 0 || m < 0) return PN2_E_SHAPE;
     const long long rows = (long long)b * m;
     if (rows == 0) return PN2_OK;
-    if (!xyz1 || (sides >= 1 && !lengths1) || !xyz2 || (sides == 2 && !lengths2) || !val || !idx) return PN2_E_NULL;
+    if (pk && pk->total <= 0) return PN2_E_SHAPE;
+    if (!xyz1 || (sides >= 1 && !lengths1) || (pk && !pk->offsets) || !xyz2 || (sides == 2 && !lengths2) || !val || !idx) return PN2_E_NULL;
     if (rows > INT_MAX || k > n) return PN2_E_TOO_LARGE;   // k > n: tf.slice would fail in the reference as well
     if (n > kSortMaxLdsN - 2048) return PN2_E_TOO_LARGE;    // callers keep the matrix + pn2_selection_sort path
     const size_t lds = 8 * (size_t)n + sizeof(int) * (256 + 3 * (size_t)kKnnCap);
+    if (pk) {
+        if ((long long)pk->total * 3 > INT_MAX) return PN2_E_TOO_LARGE;
+        return launch_counts_packed<true>([](auto... c) { return knn_wave_kernel<decltype(c)...>; }, *pk, lengths2, dim3((unsigned)rows),
+                                          dim3(64), lds, as_stream(stream), n, m, k, xyz1, xyz2, val, idx);
+    }
     return launch_counts([](auto... c) { return knn_wave_kernel<decltype(c)...>; }, lengths1, lengths2, dim3((unsigned)rows), dim3(64),
                          lds, as_stream(stream), n, m, k, xyz1, xyz2, val, idx);
 }
@@ -399,4 +432,18 @@ extern "C" int pn2_knn_point_ragged_pair(int b, int n, int m, int k, const float
                                          const int *lengths2, float *val, int *idx, void *stream)
 {
     return knn_entry(2, b, n, m, k, xyz1, lengths1, xyz2, lengths2, val, idx, stream);
+}
+
+// Packed batch: cloud c of xyz1 is xyz1[offsets1[c] : offsets1[c + 1]] of a flat (total, 3) array, offsets1 (b + 1) int32 on the
+// device, never read by the host; nmax bounds every cloud's count and sizes the LDS. The queries xyz2 (b, m, 3) and the outputs
+// (b, m, k) are dense. The first min(k, n_c) entries of a row = pn2_knn_point on the slice, the rest repeat entry 0 =
+// pn2_knn_point_ragged on the padded copy; global_idx 1 writes idx as offsets1[c] + j. lengths2 (may be NULL): the valid rows of
+// xyz2 per cloud, as in pn2_knn_point_ragged_pair -- the rows from lengths2[c] on are val +0.0 / idx 0 (offsets1[c] under
+// global_idx), their queries never read. Codes in the order of pn2_knn_point_ragged with nmax where n stood; total <= 0 is
+// PN2_E_SHAPE behind the nothing-to-do return, total 3 > INT_MAX PN2_E_TOO_LARGE.
+extern "C" int pn2_knn_point_packed(int b, int total, int nmax, int m, int k, const float *xyz1, const int *offsets1, const float *xyz2,
+                                    const int *lengths2, int global_idx, float *val, int *idx, void *stream)
+{
+    const pn2::Packed pk = {offsets1, total, global_idx ? 1 : 0};
+    return knn_entry(0, b, nmax, m, k, xyz1, nullptr, xyz2, lengths2, val, idx, stream, &pk);
 }

@@ -19,7 +19,7 @@ from .tf_sampling import farthest_point_sample, farthest_point_sample_gather, ga
 from .tf_grouping import (query_ball_point, group_point, knn_point, query_ball_group_xyz,
                           query_ball_group_xyz_msg, sample_and_group_xyz)
 from .tf_interpolate import three_nn, three_interpolate, fp_interp_concat
-from ._tensors import lengths_for, packed_args, ragged_lengths, require, use_segmented_grad
+from ._tensors import lengths_for, packed_args, packed_pairs, ragged_lengths, require, use_segmented_grad
 from . import sa_mlp
 from . import train_mlp
 from .geometry import FPGeometry, SAGeometry
@@ -48,14 +48,26 @@ def _valid_row_list(valid):
     return valid.reshape(-1).nonzero().squeeze(1)
 
 
-def _sample_and_group_packed(npoint, radius, nsample, xyz, points, use_xyz, offsets, max_points):
+def _sample_and_group_packed(npoint, radius, nsample, xyz, points, use_xyz, offsets, max_points, knn=False, npoints=None):
     """sample_and_group on a packed batch: packed FPS + gather and packed ball query + group (two launches, no host
     synchronisation, capturable), indices GLOBAL -- rows of the flat array --, so the features are group_point on the flat view
-    (1, total, c). xyz carries no gradient here (the packed operators are not differentiable)."""
+    (1, total, c). xyz carries no gradient here (the packed operators are not differentiable).
+    knn / npoints (set_packed_pairs(True)): packed kNN in the ball query's place -- grouped_xyz is then the gathered rows minus
+    the centroid, as on the padded kNN route -- and per-cloud sample counts, which are the query side's lengths2; a fill row's
+    group is nsample times the cloud's own first row."""
     offs, b, total, nmax = packed_args(offsets, max_points, None, xyz, "sample_and_group")
     m, ns = int(npoint), int(nsample)
-    _, new_xyz = farthest_point_sample_gather(m, xyz, offsets=offs, max_points=nmax)
-    idx, _, grouped_xyz = query_ball_group_xyz(radius, ns, xyz, new_xyz, True, offsets=offs, max_points=nmax, global_idx=True)
+    if npoints is None and not knn:
+        _, new_xyz = farthest_point_sample_gather(m, xyz, offsets=offs, max_points=nmax)
+        idx, _, grouped_xyz = query_ball_group_xyz(radius, ns, xyz, new_xyz, True, offsets=offs, max_points=nmax, global_idx=True)
+    else:
+        _, new_xyz = farthest_point_sample_gather(m, xyz, npoints=npoints, offsets=offs, max_points=nmax)
+        if knn:
+            _, idx = knn_point(ns, xyz, new_xyz, lengths2=npoints, offsets=offs, max_points=nmax, global_idx=True)
+            grouped_xyz = group_point(xyz.reshape(1, total, 3), idx.view(1, b * m, ns)).view(b, m, ns, 3) - new_xyz.unsqueeze(2)
+        else:
+            idx, _, grouped_xyz = query_ball_group_xyz(radius, ns, xyz, new_xyz, True, lengths2=npoints, offsets=offs, max_points=nmax,
+                                                       global_idx=True)
     if points is not None:
         require(points.dim() == 2 and points.shape[0] == total, "sample_and_group: with offsets, points is (total, channel)")
         points = points.reshape(1, total, points.shape[1])
@@ -84,13 +96,16 @@ def sample_and_group(npoint, radius, nsample, xyz, points, knn=False, use_xyz=Tr
     rows offsets[i] .. offsets[i + 1] - 1 (offsets (b + 1,) on the device, max_points a host int bounding every cloud's count).
     new_xyz, new_points and grouped_xyz come back dense (b, npoint, ...) and are each cloud's dense results; idx holds GLOBAL
     rows of the flat arrays. Not with lengths / npoints / knn, and xyz gets no gradient (ValueError where it wants one).
+    Under set_packed_pairs(True) knn and npoints are offered with offsets too (_sample_and_group_packed): the results are the
+    padded call's with lengths= / npoints= on the padded copy, idx shifted by offsets[i].
     """
     if offsets is not None:
-        require(lengths is None and npoints is None, "sample_and_group: offsets and lengths / npoints are two layouts; give one")
-        require(not knn, "sample_and_group: knn is not offered with offsets")
+        pairs = packed_pairs()
+        require(lengths is None and (npoints is None or pairs), "sample_and_group: offsets and lengths / npoints are two layouts; give one")
+        require(not knn or pairs, "sample_and_group: knn is not offered with offsets")
         require(not (torch.is_grad_enabled() and isinstance(xyz, torch.Tensor) and xyz.requires_grad),
                 "sample_and_group: with offsets xyz gets no gradient; detach it")
-        return _sample_and_group_packed(npoint, radius, nsample, xyz, points, use_xyz, offsets, max_points)
+        return _sample_and_group_packed(npoint, radius, nsample, xyz, points, use_xyz, offsets, max_points, knn, npoints)
     if fused is None:
         fused = not (torch.is_grad_enabled() and xyz.requires_grad)
     if lengths is not None:
@@ -560,17 +575,22 @@ class PointnetSAModule(nn.Module):
             out, _ = train_mlp.sa_mlp_train(self.mlp.net, xyz, new_xyz, points, g.idx, True, plan=getattr(g, "plan", None),
                                             counts=npoints)
             return new_xyz, out, g.idx
+        return self._forward_compacted(xyz, points, g, valid)
+
+    def _forward_compacted(self, xyz, points, g, valid):
+        """The compacting training path of _forward_counts: valid marks the centroid rows of g, in their order, that take part
+        (any shape; a packed level's (B, npoint) mask over the flat view's one cloud of B npoint centroids)."""
         self.last_path = "unfused_ragged"
         new_xyz, idx, plan = g.new_xyz_for(xyz), g.idx, getattr(g, "plan", None)
         new_points, grouped_xyz = _grouped_input(xyz, points, idx, new_xyz, self.use_xyz, True, plan)   # :45-50
         rows = _valid_row_list(valid)
-        ns = idx.shape[2]
-        pv = new_points.reshape(b * m, ns, new_points.shape[3]).index_select(0, rows).unsqueeze(0)    # (1, total, nsample, C)
-        gv = grouped_xyz.reshape(b * m, ns, 3).index_select(0, rows).unsqueeze(0)
+        ns, every = idx.shape[2], valid.numel()
+        pv = new_points.reshape(every, ns, new_points.shape[3]).index_select(0, rows).unsqueeze(0)    # (1, total, nsample, C)
+        gv = grouped_xyz.reshape(every, ns, 3).index_select(0, rows).unsqueeze(0)
         _, yv, _ = self._stack_and_pool(None, pv, None, gv)                     # (1, total, C'): statistics over the valid groups
-        return new_xyz, _scatter_rows(yv[0], rows, b * m).reshape(b, m, yv.shape[2]), idx
+        return new_xyz, _scatter_rows(yv[0], rows, every).reshape(idx.shape[0], idx.shape[1], yv.shape[2]), idx
 
-    def _forward_packed(self, xyz, points, offsets, max_points):
+    def _forward_packed(self, xyz, points, offsets, max_points, npoints=None):
         """forward() on a PACKED batch: xyz (total, 3), points (total, c) or None, cloud i = rows
         offsets[i] .. offsets[i + 1] - 1. The geometry is built in the FLAT VIEW -- packed FPS + gather and packed ball query
         with global indices give SAGeometry(new_xyz (1, B npoint, 3), idx (1, B npoint, nsample), fps_idx) on xyz (1, total, 3)
@@ -578,17 +598,43 @@ class PointnetSAModule(nn.Module):
         kernels and the layer-by-layer path run unchanged on one cloud of `total` points and B npoint centroids. No padding
         row exists, so nothing is masked. The route predicates get the true centroid count (m = B npoint). last_path is the
         route's with "packed_" in front; where no fused route takes the flat view it is "packed_unfused", layer by layer.
+        Under set_packed_pairs(True): a knn module takes packed kNN where the ball query stands, nothing behind the geometry
+        changes. npoints (per-cloud sample counts, the next level's lengths=): the geometry carries the operators' fills on the
+        rows from npoints[c] on -- sample 0 as the centroid, a group of nsample times the cloud's own first row. eval(): the same
+        routes on every row, then exact zeros on those rows (_zero_padding_rows); no synchronisation. train(): the compacting
+        layer-by-layer path of _forward_counts on the flat view (_forward_compacted: the batch statistics cover the valid
+        groups only; synchronises), last_path "packed_unfused_ragged" -- the masked fused node wants (b, m) rows over b source
+        clouds and has no flat-view form.
         -> new_xyz (B, npoint, 3), features (B, npoint, C), idx (B, npoint, nsample) global."""
         offs, b, total, nmax = packed_args(offsets, max_points, None, xyz, "PointnetSAModule")
         if points is not None:
             require(points.dim() == 2 and points.shape[0] == total, "PointnetSAModule: with offsets, points is (total, channel)")
         m, ns = self.npoint, self.nsample
         flat = xyz.detach()
-        fps_idx, new_xyz = farthest_point_sample_gather(m, flat, offsets=offs, max_points=nmax, global_idx=True)
-        idx, _ = query_ball_point(self.radius, ns, flat, new_xyz, offsets=offs, max_points=nmax, global_idx=True)
+        if npoints is None and not self.knn:
+            fps_idx, new_xyz = farthest_point_sample_gather(m, flat, offsets=offs, max_points=nmax, global_idx=True)
+            idx, _ = query_ball_point(self.radius, ns, flat, new_xyz, offsets=offs, max_points=nmax, global_idx=True)
+        else:
+            if npoints is not None:
+                npoints = ragged_lengths(npoints, b, flat.device, "npoints")
+            fps_idx, new_xyz = farthest_point_sample_gather(m, flat, npoints=npoints, offsets=offs, max_points=nmax, global_idx=True)
+            if self.knn:
+                _, idx = knn_point(ns, flat, new_xyz, lengths2=npoints, offsets=offs, max_points=nmax, global_idx=True)
+            else:
+                idx, _ = query_ball_point(self.radius, ns, flat, new_xyz, lengths2=npoints, offsets=offs, max_points=nmax, global_idx=True)
         g = SAGeometry(new_xyz.view(1, b * m, 3), idx.view(1, b * m, ns), fps_idx.view(1, b * m))
         xf = xyz.reshape(1, total, 3)
         pf = points.reshape(1, total, points.shape[1]) if points is not None else None
+        if npoints is not None:
+            valid = _valid_rows(npoints, b, m, flat.device)
+            if self.training:
+                new_xyz_f, out, _ = self._forward_compacted(xf, pf, g, valid)
+                self.last_path = "packed_unfused_ragged"
+                return new_xyz_f.view(b, m, 3), out.view(b, m, out.shape[2]), idx
+            path = self._train_mode(xf, pf, b * m) or ("fused" if self._fused_ok(xf, pf) else "unfused")
+            new_xyz_f, out, _ = self._forward_on(xf, pf, g, path)
+            self.last_path = "packed_" + path
+            return new_xyz_f.view(b, m, 3), _zero_padding_rows(out.view(b, m, out.shape[2]), valid), idx
         path = self._train_mode(xf, pf, b * m) or ("fused" if self._fused_ok(xf, pf) else "unfused")
         new_xyz_f, out, _ = self._forward_on(xf, pf, g, path)
         self.last_path = "packed_" + path
@@ -611,14 +657,16 @@ class PointnetSAModule(nn.Module):
         npoints: (b,) per-cloud sample counts, with or without lengths (_forward_counts; a geometry= must come from
         geometry(npoints=)): new_points rows from npoints[c] on are exact zeros; hand npoints to the next level as its lengths.
         offsets / max_points: a packed batch, xyz (total, 3) and points (total, c), see _forward_packed. Single scale, ball
-        query; ValueError with group_all, knn, lengths / npoints, a geometry= or fused_xyz_grad."""
+        query; ValueError with group_all, knn, lengths / npoints, a geometry= or fused_xyz_grad. Under set_packed_pairs(True) a knn
+        module and npoints= are offered with offsets as well (_forward_packed)."""
         if offsets is not None:
-            require(lengths is None and npoints is None, "PointnetSAModule: offsets and lengths / npoints are two layouts; give one")
+            pairs = packed_pairs()
+            require(lengths is None and (npoints is None or pairs), "PointnetSAModule: offsets and lengths / npoints are two layouts; give one")
             require(not self.group_all, "PointnetSAModule: group_all is not offered with offsets")
-            require(not self.knn, "PointnetSAModule: knn is not offered with offsets")
+            require(not self.knn or pairs, "PointnetSAModule: knn is not offered with offsets")
             require(geometry is None, "PointnetSAModule: a geometry computed ahead is not offered with offsets")
             require(not self.fused_xyz_grad, "PointnetSAModule: fused_xyz_grad is not offered with offsets")
-            return self._forward_packed(xyz, points, offsets, max_points)
+            return self._forward_packed(xyz, points, offsets, max_points, npoints)
         if (lengths is not None or npoints is not None) and self.group_all:
             if npoints is not None or not self.ragged_group_all:
                 raise ValueError("group_all with lengths: the group would contain the padding rows")
@@ -1105,7 +1153,7 @@ class PointnetFPModule(nn.Module):
         yv = y[0, :, :, 0].t()
         return _scatter_rows(yv, rows, b * n).reshape(b, n, yv.shape[1])
 
-    def _forward_packed(self, xyz1, xyz2, points1, points2, offsets1, max_points1):
+    def _forward_packed(self, xyz1, xyz2, points1, points2, offsets1, max_points1, lengths2=None):
         """forward() with a PACKED unknown side: xyz1 (total, 3), points1 (total, c1) or None, cloud i = rows
         offsets1[i] .. offsets1[i + 1] - 1; the known side xyz2 (B, m, 3), points2 (B, m, c2) is a previous level's dense
         output. Packed three_nn with global indices gives FPGeometry(dist, idx (1, total, 3)) in the FLAT VIEW, idx naming rows
@@ -1114,7 +1162,9 @@ class PointnetFPModule(nn.Module):
         routes of _stack_on, no mask anywhere. Otherwise the stack's rows are extended to the next multiple of 32 (idx 0 /
         dist 0 / points1 0 on the <= 31 tail rows) and the masked plain-rows node runs with b = 1 and lengths =
         offsets1[B : B + 1] = total, already on the device: the tail is the only masked word, nothing synchronises; where the
-        masked node does not cover the stack, layer by layer on the `total` rows. last_path: the route's with "packed_" in front."""
+        masked node does not cover the stack, layer by layer on the `total` rows. last_path: the route's with "packed_" in front.
+        lengths2 (set_packed_pairs(True)): a previous level's npoints -- handed to the packed three_nn, so every idx names one of
+        its cloud's first lengths2[i] known rows; nothing else changes."""
         dev = xyz1.device
         b, m, c2 = points2.shape
         offs, b, total, nmax = packed_args(offsets1, max_points1, None, xyz1, "PointnetFPModule", "offsets1", "max_points1", b=b)
@@ -1131,7 +1181,8 @@ class PointnetFPModule(nn.Module):
         # three_nn writes the first `total` rows of buffers that already have the stack's row count
         dist = torch.zeros((rows, 3), dtype=torch.float32, device=dev) if tail else torch.empty((rows, 3), dtype=torch.float32, device=dev)
         idx = torch.zeros((rows, 3), dtype=torch.int32, device=dev) if tail else torch.empty((rows, 3), dtype=torch.int32, device=dev)
-        three_nn(xyz1.detach(), xyz2.detach(), out=(dist[:total], idx[:total]), offsets1=offs, max_points1=nmax, global_idx=True)   # :211
+        three_nn(xyz1.detach(), xyz2.detach(), out=(dist[:total], idx[:total]), lengths2=lengths2, offsets1=offs, max_points1=nmax,
+                 global_idx=True)                                               # :211
         g = FPGeometry(dist.view(1, rows, 3), idx.view(1, rows, 3), self._plan_of(idx.view(1, rows, 3), b * m))
         if tail:
             p1 = torch.nn.functional.pad(points1, (0, 0, 0, rows - total)).view(1, rows, c1) if points1 is not None else None
@@ -1155,11 +1206,12 @@ class PointnetFPModule(nn.Module):
         buffers). lengths1: a ragged unknown side, see _forward_ragged. lengths2: a ragged known side (a previous level's
         npoints); without lengths1 the unknown side is dense and the result is that of the dense routes on the two-sided
         three_nn's result. offsets1 / max_points1: a packed unknown side, xyz1 (total, 3) and points1 (total, c1), see
-        _forward_packed; ValueError with lengths1 / lengths2 or a geometry=."""
+        _forward_packed; ValueError with lengths1 / lengths2 or a geometry= (lengths2 is offered under set_packed_pairs(True))."""
         if offsets1 is not None:
-            require(lengths1 is None and lengths2 is None, "PointnetFPModule: offsets1 and lengths1 / lengths2 are two layouts; give one")
+            require(lengths1 is None and (lengths2 is None or packed_pairs()),
+                    "PointnetFPModule: offsets1 and lengths1 / lengths2 are two layouts; give one")
             require(geometry is None, "PointnetFPModule: a geometry computed ahead is not offered with offsets1")
-            return self._forward_packed(xyz1, xyz2, points1, points2, offsets1, max_points1)
+            return self._forward_packed(xyz1, xyz2, points1, points2, offsets1, max_points1, lengths2)
         if lengths1 is not None:
             return self._forward_ragged(xyz1, xyz2, points1, points2, lengths1, geometry, lengths2)
         if geometry is None and lengths2 is not None:

@@ -9,9 +9,9 @@ NoGradient (:21, :32).
 """
 import torch
 
-from . import _C
-from ._tensors import (out_or_empty, f32, i32, lengths_for, on_device, packed_args, pair_counts, ptr, require, same_device, scatter_grad,
-                       stream_ptr)
+from . import _C, _tensors
+from ._tensors import (out_or_empty, f32, i32, lengths_for, on_device, packed_args, pair_counts, ptr, ragged_lengths, require, same_device,
+                       scatter_grad, stream_ptr)
 
 
 # Ball-query kernel choice passed with every call (pn2_query_ball_group_xyz_ex): 0 automatic, 1 sweep,
@@ -36,14 +36,20 @@ def _ball_inputs(op, xyz1, xyz2, lengths1, lengths2, offsets=None, max_points=No
     pair_counts gives: the entry's suffix, the two count arrays (packed: the offsets in the place of the first), their pointers
     as they splice in behind xyz1 and behind xyz2."""
     if offsets is not None:
-        if lengths2 is not None:                                  # (a message costs more to format than its check)
+        if lengths2 is not None and not _tensors.packed_pairs():  # (a message costs more to format than its check)
             raise ValueError("%s: a ragged query side (lengths2=) is not offered with offsets" % op)
         require(isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 and xyz2.shape[2] == 3, _XYZ2_SHAPE)
         b, m, _ = xyz2.shape
         offs, b, total, nmax = packed_args(offsets, max_points, lengths1, xyz1, op, b=b)
+        if lengths2 is not None:
+            lengths2 = lengths_for(lengths2, xyz2, "lengths2")
         xyz1 = f32(xyz1, "xyz1")
         xyz2 = f32(xyz2, "xyz2")
-        return xyz1, xyz2, same_device(xyz1, xyz2), (b, total, nmax, m), "_packed", offs, None, (offs.data_ptr(),), ()
+        dev = same_device(xyz1, xyz2)
+        if lengths2 is not None:                                  # set_packed_pairs(True): the _packed_pair entries
+            lens2 = ragged_lengths(lengths2, b, dev, "lengths2")
+            return xyz1, xyz2, dev, (b, total, nmax, m), "_packed_pair", offs, lens2, (offs.data_ptr(),), (lens2.data_ptr(),)
+        return xyz1, xyz2, dev, (b, total, nmax, m), "_packed", offs, None, (offs.data_ptr(),), ()
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     if lengths2 is not None:
@@ -95,7 +101,9 @@ def query_ball_point(radius, nsample, xyz1, xyz2, out=None, lengths1=None, lengt
     offsets / max_points: a PACKED xyz1 -- one flat (total, 3) array, cloud i is xyz1[offsets[i] : offsets[i + 1]] (offsets
     (b + 1,) on the device; max_points a host int bounding every cloud's count, required); xyz2 and the outputs stay dense. Each
     cloud's result is the dense operator's on its slice. global_idx: idx holds rows of the flat array (offsets[i] + k). Not
-    to be mixed with lengths1 / lengths2 (ValueError).
+    to be mixed with lengths1 / lengths2 (ValueError) -- lengths2 is offered with offsets under set_packed_pairs(True)
+    (pn2_query_ball_group_xyz_packed_pair): rows below the count are the dense operator's on the slice pair, the fill rows are
+    idx 0 -- offsets[i] under global_idx --, pts_cnt 0, grouped_xyz +0.0.
     lengths1: (b,) per-cloud point counts of a ragged xyz1 (cloud i is xyz1[i, :lengths1[i]]): each cloud's result is the
     dense operator's on its slice, rows beyond the length are never read. None = every cloud holds all ndataset points.
     lengths2: (b,) per-cloud counts of valid QUERY rows of xyz2 (cloud i asks xyz2[i, :lengths2[i]]): rows below the count are the
@@ -138,7 +146,8 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
     one launch); bit-identical to query_ball_group_xyz(..., lengths1=, lengths2=) per radius, fill rows included.
     offsets / max_points / global_idx: a packed xyz1 (total, 3), see query_ball_point (pn2_query_ball_group_xyz_msg_packed: still
     one launch, every cloud's slab staged and binned once); bit-identical to query_ball_group_xyz(..., offsets=, max_points=,
-    global_idx=) per radius. Not to be mixed with lengths1 / lengths2 (ValueError); the outputs stay dense (b, m, ...).
+    global_idx=) per radius. Not to be mixed with lengths1 / lengths2 (ValueError; lengths2 under set_packed_pairs(True):
+    pn2_query_ball_group_xyz_msg_packed_pair, still one launch); the outputs stay dense (b, m, ...).
 
     -> [(idx (b,m,ns_i) i32 or None, pts_cnt (b,m) i32, grouped_xyz (b,m,ns_i,3) f32) for every scale]
     """
@@ -186,8 +195,8 @@ def query_ball_group_xyz_msg(radius_list, nsample_list, xyz1, xyz2, subtract_cen
         # ... or PN2_E_TOO_LARGE: no LDS geometry fits this combination (e.g. n = 8192 with nsample >= 127 on a later radius);
         # nothing has been launched -- the per-radius operator covers every shape
         if offsets is not None:
-            return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, offsets=lens1, max_points=max_points,
-                                         global_idx=global_idx) for r, k in zip(radius_list, nsample_list)]
+            return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths2=lens2, offsets=lens1,
+                                         max_points=max_points, global_idx=global_idx) for r, k in zip(radius_list, nsample_list)]
         return [query_ball_group_xyz(r, k, xyz1, xyz2, subtract_centroid, want_idx, lengths1=lens1, lengths2=lens2)
                 for r, k in zip(radius_list, nsample_list)]
     _C.check(rc, "query_ball_group_xyz_msg")
@@ -555,9 +564,44 @@ def group_point(points, idx, out=None, plan=None):
     return _GroupPoint.apply(points, idx, plan)
 
 
-def knn_point(k, xyz1, xyz2, lengths1=None, lengths2=None):
+KNN_MAX_POINTS = 14336                 # the one-kernel kNN's envelope (pn2_knn_point and its counted / packed modes)
+
+
+def _knn_point_packed(k, xyz1, xyz2, lengths1, lengths2, offsets, max_points, global_idx):
+    """knn_point on a packed xyz1 (pn2_knn_point_packed): the one kernel or a ValueError -- there is no matrix form of a flat array."""
+    op = "knn_point"
+    require(isinstance(xyz2, torch.Tensor) and xyz2.dim() == 3 and xyz2.shape[2] == 3,
+            "knn_point with offsets expects 3-D points: (total, 3) xyz1 and (b, m, 3) xyz2")
+    b, m, _ = xyz2.shape
+    offs, b, total, nmax = packed_args(offsets, max_points, lengths1, xyz1, op, b=b)
+    if lengths2 is not None:
+        lengths2 = lengths_for(lengths2, xyz2, "lengths2")
+    k = int(k)
+    require(k > 0, "SelectionSort expects positive k")
+    require(nmax <= KNN_MAX_POINTS and k <= nmax, "knn_point with offsets expects at most %d points per cloud and k <= max_points, got "
+            "max_points = %d, k = %d" % (KNN_MAX_POINTS, nmax, k))
+    xyz1 = f32(xyz1, "xyz1")
+    xyz2 = f32(xyz2, "xyz2")
+    dev = same_device(xyz1, xyz2)
+    lens2 = ragged_lengths(lengths2, b, dev, "lengths2") if lengths2 is not None else None
+    val = torch.empty((b, m, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((b, m, k), dtype=torch.int32, device=dev)
+    with on_device(dev):
+        rc = _C.lib().pn2_knn_point_packed(b, total, nmax, m, k, ptr(xyz1), ptr(offs), ptr(xyz2), ptr(lens2), 1 if global_idx else 0,
+                                           ptr(val), ptr(idx), stream_ptr(dev))
+    if rc:
+        _C.check(rc, op)
+    return val, idx
+
+
+def knn_point(k, xyz1, xyz2, lengths1=None, lengths2=None, offsets=None, max_points=None, global_idx=False):
     """k int, xyz1 (b, ndataset, c), xyz2 (b, npoint, c) -> val (b, npoint, k) f32
     squared L2 distances, idx (b, npoint, k) i32.
+    offsets / max_points: a PACKED xyz1 -- one flat (total, 3) array, cloud i is xyz1[offsets[i] : offsets[i + 1]] (offsets
+    (b + 1,) on the device; max_points a host int bounding every cloud's count, required); xyz2 (b, npoint, 3) and the outputs
+    stay dense. Each cloud's rows are the dense operator's on its slice, with the repeat-entry-0 rule of lengths1 where k exceeds
+    the cloud; lengths2 as below, its fill rows idx 0 -- offsets[i] under global_idx, which writes idx as rows of the flat array.
+    3-D points, max_points <= 14336 and k <= max_points (ValueError outside: no matrix form). Not to be mixed with lengths1.
     lengths1: (b,) per-cloud point counts of a ragged xyz1 (cloud i is xyz1[i, :lengths1[i]]; 3-D points, at most 14336 per
     padded cloud, k <= ndataset -- ValueError outside): the first min(k, lengths1[i]) entries of a row are the dense
     operator's on the slice, and where k > lengths1[i] the rest repeat entry 0 (the way a ball query pads with its first hit).
@@ -570,6 +614,8 @@ def knn_point(k, xyz1, xyz2, lengths1=None, lengths2=None):
     (pn2_knn_point); other channel counts build the matrix with torch elementwise ops (same per-pair
     arithmetic: differences, squares, a left-to-right sum over c) and run the HIP selection sort.
     """
+    if offsets is not None:
+        return _knn_point_packed(k, xyz1, xyz2, lengths1, lengths2, offsets, max_points, global_idx)
     if lengths1 is not None:
         lengths1 = lengths_for(lengths1, xyz1, "lengths1")
     if lengths2 is not None:

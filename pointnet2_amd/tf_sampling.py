@@ -10,9 +10,9 @@ ProbSample are NoGradient (:22, :57).
 """
 import torch
 
-from . import _C
+from . import _C, _tensors
 from ._tensors import (det_workspace, f32, i32, is_deterministic, lengths_for, on_device, out_or_empty, packed_args, pair_counts, ptr,
-                       require, same_device, stream_ptr)
+                       ragged_lengths, require, same_device, stream_ptr)
 
 
 def prob_sample(inp, inpr):
@@ -233,12 +233,18 @@ def _fps_ragged(m, inp, lengths, out, new_xyz, op, npoints=None):
 
 
 def _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, out, want_xyz, op):
-    """The packed form of both sampling operators (pn2_farthest_point_sample_packed): inp (total, 3), offsets (b + 1,) on the
+    """The packed form of both sampling operators (pn2_farthest_point_sample_packed; with npoints, under set_packed_pairs(True),
+    pn2_farthest_point_sample_packed_counts): inp (total, 3), offsets (b + 1,) on the
     device, max_points a host int. -> idx (b, npoint), new_xyz (b, npoint, 3) or None. A tier forced with set_fps_variant
     applies; nothing synchronises. max_points of 16385 .. 1048576 under set_fps_ragged_large(True):
     pn2_farthest_point_sample_large_packed_ex with a workspace of 20 bytes per row of the flat array, allocated per call."""
-    require(npoints is None, "%s: per-cloud sample counts (npoints=) are not offered with offsets" % op)
+    require(npoints is None or _tensors.packed_pairs(), "%s: per-cloud sample counts (npoints=) are not offered with offsets" % op)
     offs, b, total, nmax = packed_args(offsets, max_points, lengths, inp, op)           # (before anything else, like lengths_for)
+    cnts = None
+    if npoints is not None:                                # set_packed_pairs(True): pn2_farthest_point_sample_packed_counts
+        cnts = ragged_lengths(npoints, b, inp.device, "npoints")               # (shape and dtype complaints before the device's)
+        require(nmax <= FPS_RAGGED_MAX_POINTS, "%s: npoints with offsets supports at most %d points per cloud, got max_points = %d"
+                % (op, FPS_RAGGED_MAX_POINTS, nmax))
     large = _FPS_RAGGED_LARGE[0] and not _FPS_VARIANT[0] and nmax > FPS_RAGGED_MAX_POINTS
     limit = FPS_RAGGED_LARGE_MAX_POINTS if large else FPS_RAGGED_MAX_POINTS
     require(nmax <= limit, "%s with offsets supports at most %d points per cloud, got max_points = %d" % (op, limit, nmax))
@@ -256,6 +262,11 @@ def _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, 
                                                                    1 if global_idx else 0, ptr(ws), ptr(out), ptr(new_xyz),
                                                                    stream_ptr(dev)), op)
         return out, new_xyz
+    if cnts is not None:
+        with on_device(dev):
+            _C.check(_C.lib().pn2_farthest_point_sample_packed_counts(_FPS_VARIANT[0], b, total, nmax, m, ptr(inp), ptr(offs), ptr(cnts),
+                                                                      1 if global_idx else 0, ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
+        return out, new_xyz
     with on_device(dev):
         _C.check(_C.lib().pn2_farthest_point_sample_packed(_FPS_VARIANT[0], b, total, nmax, m, ptr(inp), ptr(offs), 1 if global_idx else 0,
                                                            ptr(out), ptr(new_xyz), stream_ptr(dev)), op)
@@ -269,7 +280,7 @@ def _fps(npoint, inp, op, want_xyz, out=None, ordered=None, lengths=None, npoint
     require(int(npoint) > 0, "FarthestPointSample expects positive npoint")
     if offsets is not None:
         out, new_xyz = _fps_packed(npoint, inp, offsets, max_points, lengths, npoints, global_idx, out, want_xyz, op)
-        return out, (mark_fps_ordered(new_xyz) if want_xyz else None)
+        return out, (mark_fps_ordered(new_xyz) if want_xyz and npoints is None else new_xyz)   # fill rows break the farthest-point order
     if lengths is not None:
         lengths = lengths_for(lengths, inp)
     if npoints is not None:
@@ -315,7 +326,8 @@ def farthest_point_sample_gather(npoint, inp, ordered=None, lengths=None, npoint
     (offsets (b + 1,) on the device), max_points a host int that bounds every cloud's count (it takes the padded n's place in
     the tier rule; required, so nothing synchronises). Each cloud's result is the dense operator's on its slice; idx and new_xyz
     stay dense (b, npoint[, 3]). global_idx: indices are rows of the flat array (offsets[i] + k) instead of cloud-local.
-    Not to be mixed with lengths (ValueError).
+    Not to be mixed with lengths (ValueError). npoints with offsets is offered under set_packed_pairs(True), up to 16384 points per
+    cloud (pn2_farthest_point_sample_packed_counts): rows from npoints[i] on repeat sample 0, idx 0 -- offsets[i] under global_idx.
     lengths: (b,) per-cloud point counts of a ragged batch (cloud i is inp[i, :lengths[i]]): each cloud's result is the
     dense operator's on its slice, rows beyond the length are never read. None = every cloud holds all n points.
     npoints: (b,) per-cloud sample counts (cloud i yields m_i = npoints[i] <= npoint samples; clamped into 1..npoint on the

@@ -21,6 +21,10 @@ Operators, lengths uniform in n/2 .. n (seed fixed), the padded tensor sized by 
                       ONE pn2_query_ball_group_xyz_msg_packed launch against (a) what a packed user had before it, three
                       pn2_query_ball_group_xyz_packed launches, and (b) pn2_query_ball_group_xyz_msg_ragged on the padded copy
                       (both baselines from --parent-lib when given)
+The second side, packed (--only pair, --only knn; profiles/packed_pair/README.md): FPS + gather with per-cloud sample counts,
+the ball query with a ragged query side and kNN (8 x 4096 -> 1024 x 32) through the packed entries against the same clouds
+padded through the _ragged_counts / _ragged_pair entries, counts uniform in m/2 .. m; then full counts against the one-sided
+packed entries.
 MSG level (cls_msg level 1 with 6 feature channels, stacks 32-32-64 / 64-64-128 / 64-96-128, uniform cubes): PointnetSAModuleMSG
 with packed_batches on the packed batch against the padded lengths= forward with ragged_one_launch, eval() (no_grad) and train()
 (forward + backward); both routes are this tree's Python.
@@ -49,7 +53,9 @@ from pointnet2_amd._tensors import stream_ptr
 def bind(path):
     lib = ctypes.CDLL(path)
     for name in ("pn2_farthest_point_sample_ragged", "pn2_query_ball_group_xyz_ragged", "pn2_three_nn_ragged",
-                 "pn2_query_ball_group_xyz_packed", "pn2_query_ball_group_xyz_msg_ragged"):
+                 "pn2_query_ball_group_xyz_packed", "pn2_query_ball_group_xyz_msg_ragged", "pn2_farthest_point_sample_ragged_counts",
+                 "pn2_query_ball_group_xyz_ragged_pair", "pn2_knn_point_ragged_pair", "pn2_knn_point_ragged",
+                 "pn2_farthest_point_sample_packed"):
         getattr(lib, name).argtypes = _C._SIGNATURES[name]
         getattr(lib, name).restype = ctypes.c_int
     return lib
@@ -148,6 +154,77 @@ def operators(base, a, dev, results):
     torch.cuda.synchronize()
     same = torch.equal(valid_rows(pi, lengths), fi) and torch.equal(bits(valid_rows(pd, lengths)), bits(fd))
     report("three_nn sem_seg FP4 (8 x 8192, 1024 known)", rts, same, a, results, b=b, n=n, m=m, total=total, mean_length=float(lengths.mean()))
+
+
+def pair_operators(base, a, dev, results, knn):
+    """The second side, packed (pn2_farthest_point_sample_packed_counts, pn2_query_ball_group_xyz_packed_pair; knn:
+    pn2_knn_point_packed) against what a user does without them: the same clouds padded through the _ragged_counts / _ragged_pair
+    entries (from --parent-lib when given). Counts uniform in m/2 .. m, lengths uniform in n/2 .. n. Then full counts against the
+    one-sided packed entries: the price of the second array."""
+    lib, st = _C.lib(), stream_ptr(dev)
+    I, F = torch.int32, torch.float32
+    rng = np.random.default_rng(9)
+    if knn:
+        b, n, m, k = 8, 4096, 1024, 32
+        lengths, xyz, lens, flat, offs = batch(b, n, 5, dev)
+        total = int(flat.shape[0])
+        cnts = torch.tensor(rng.integers(m // 2, m + 1, size=b), dtype=I, device=dev)
+        full = torch.full((b,), m, dtype=I, device=dev)
+        _, q = P.farthest_point_sample_gather(m, xyz, lengths=lens)
+        o = [[torch.empty((b, m, k), dtype=F, device=dev), torch.empty((b, m, k), dtype=I, device=dev)] for _ in range(4)]
+        rts = {"padded (_ragged_pair, baseline)": lambda: check(base.pn2_knn_point_ragged_pair(b, n, m, k, xyz.data_ptr(), lens.data_ptr(), q.data_ptr(), cnts.data_ptr(), o[0][0].data_ptr(), o[0][1].data_ptr(), st)),
+               "packed, lengths2": lambda: check(lib.pn2_knn_point_packed(b, total, n, m, k, flat.data_ptr(), offs.data_ptr(), q.data_ptr(), cnts.data_ptr(), 0, o[1][0].data_ptr(), o[1][1].data_ptr(), st))}
+        for fn in rts.values():
+            fn()
+        torch.cuda.synchronize()
+        same = torch.equal(bits(o[0][0]), bits(o[1][0])) and torch.equal(o[0][1], o[1][1])
+        report("kNN (8, 4096) -> (1024, 32), counts m/2 .. m", rts, same, a, results, b=b, n=n, m=m, total=total, inner=3)
+        rts = {"padded (_ragged, baseline)": lambda: check(base.pn2_knn_point_ragged(b, n, m, k, xyz.data_ptr(), lens.data_ptr(), q.data_ptr(), o[0][0].data_ptr(), o[0][1].data_ptr(), st)),
+               "packed, no lengths2": lambda: check(lib.pn2_knn_point_packed(b, total, n, m, k, flat.data_ptr(), offs.data_ptr(), q.data_ptr(), None, 0, o[2][0].data_ptr(), o[2][1].data_ptr(), st)),
+               "packed, full lengths2": lambda: check(lib.pn2_knn_point_packed(b, total, n, m, k, flat.data_ptr(), offs.data_ptr(), q.data_ptr(), full.data_ptr(), 0, o[3][0].data_ptr(), o[3][1].data_ptr(), st))}
+        for fn in rts.values():
+            fn()
+        torch.cuda.synchronize()
+        same = all(torch.equal(bits(o[0][0]), bits(x[0])) and torch.equal(o[0][1], x[1]) for x in o[2:])
+        report("kNN (8, 4096) -> (1024, 32), full counts", rts, same, a, results, b=b, n=n, m=m, total=total, inner=3)
+        return
+    b, n, m, radius, ns = 32, 4096, 1024, 0.2, 32
+    lengths, xyz, lens, flat, offs = batch(b, n, 1, dev)
+    total = int(flat.shape[0])
+    cnts = torch.tensor(rng.integers(m // 2, m + 1, size=b), dtype=I, device=dev)
+    full = torch.full((b,), m, dtype=I, device=dev)
+    o = [[torch.empty((b, m), dtype=I, device=dev), torch.empty((b, m, 3), dtype=F, device=dev)] for _ in range(4)]
+    rts = {"padded (_ragged_counts, baseline)": lambda: check(base.pn2_farthest_point_sample_ragged_counts(b, n, m, xyz.data_ptr(), lens.data_ptr(), cnts.data_ptr(), o[0][0].data_ptr(), o[0][1].data_ptr(), st)),
+           "packed, npoints": lambda: check(lib.pn2_farthest_point_sample_packed_counts(0, b, total, n, m, flat.data_ptr(), offs.data_ptr(), cnts.data_ptr(), 0, o[1][0].data_ptr(), o[1][1].data_ptr(), st))}
+    for fn in rts.values():
+        fn()
+    torch.cuda.synchronize()
+    same = torch.equal(o[0][0], o[1][0]) and torch.equal(bits(o[0][1]), bits(o[1][1]))
+    report("FPS + gather 32 x 4096 -> 1024, counts m/2 .. m", rts, same, a, results, b=b, n=n, m=m, total=total, inner=3)
+    rts = {"packed, one-sided (baseline)": lambda: check(base.pn2_farthest_point_sample_packed(0, b, total, n, m, flat.data_ptr(), offs.data_ptr(), 0, o[2][0].data_ptr(), o[2][1].data_ptr(), st)),
+           "packed, full npoints": lambda: check(lib.pn2_farthest_point_sample_packed_counts(0, b, total, n, m, flat.data_ptr(), offs.data_ptr(), full.data_ptr(), 0, o[3][0].data_ptr(), o[3][1].data_ptr(), st))}
+    for fn in rts.values():
+        fn()
+    torch.cuda.synchronize()
+    same = torch.equal(o[2][0], o[3][0]) and torch.equal(bits(o[2][1]), bits(o[3][1]))
+    report("FPS + gather 32 x 4096 -> 1024, full counts", rts, same, a, results, b=b, n=n, m=m, total=total, inner=3)
+    q = o[1][1].clone()
+    g = [[torch.empty((b, m, ns), dtype=I, device=dev), torch.empty((b, m), dtype=I, device=dev), torch.empty((b, m, ns, 3), dtype=F, device=dev)]
+         for _ in range(4)]
+    rts = {"padded (_ragged_pair, baseline)": lambda: check(base.pn2_query_ball_group_xyz_ragged_pair(b, n, m, radius, ns, xyz.data_ptr(), lens.data_ptr(), q.data_ptr(), cnts.data_ptr(), 1, g[0][0].data_ptr(), g[0][1].data_ptr(), g[0][2].data_ptr(), 0, 0, st)),
+           "packed, lengths2": lambda: check(lib.pn2_query_ball_group_xyz_packed_pair(b, total, n, m, radius, ns, flat.data_ptr(), offs.data_ptr(), q.data_ptr(), cnts.data_ptr(), 1, 0, g[1][0].data_ptr(), g[1][1].data_ptr(), g[1][2].data_ptr(), 0, 0, st))}
+    for fn in rts.values():
+        fn()
+    torch.cuda.synchronize()
+    same = all(torch.equal(bits(u), bits(v)) for u, v in zip(g[0], g[1]))
+    report("ball query + group r 0.2, nsample 32, counts m/2 .. m", rts, same, a, results, b=b, n=n, m=m, total=total)
+    rts = {"packed, one-sided (baseline)": lambda: check(base.pn2_query_ball_group_xyz_packed(b, total, n, m, radius, ns, flat.data_ptr(), offs.data_ptr(), q.data_ptr(), 1, 0, g[2][0].data_ptr(), g[2][1].data_ptr(), g[2][2].data_ptr(), 0, 0, st)),
+           "packed, full lengths2": lambda: check(lib.pn2_query_ball_group_xyz_packed_pair(b, total, n, m, radius, ns, flat.data_ptr(), offs.data_ptr(), q.data_ptr(), full.data_ptr(), 1, 0, g[3][0].data_ptr(), g[3][1].data_ptr(), g[3][2].data_ptr(), 0, 0, st))}
+    for fn in rts.values():
+        fn()
+    torch.cuda.synchronize()
+    same = all(torch.equal(bits(u), bits(v)) for u, v in zip(g[2], g[3]))
+    report("ball query + group r 0.2, nsample 32, full counts", rts, same, a, results, b=b, n=n, m=m, total=total)
 
 
 def msg_operator(base, a, dev, results):
@@ -302,7 +379,7 @@ def main():
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--only", default=None, choices=["operators", "msg", "msg_level", "training"], help="one section alone")
+    ap.add_argument("--only", default=None, choices=["operators", "msg", "msg_level", "training", "pair", "knn"], help="one section alone")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("packed_bench.py measures on the GPU; none found")
@@ -311,7 +388,9 @@ def main():
     print("padded baseline: %s" % ("the _ragged entries of " + a.parent_lib if a.parent_lib else "this library's _ragged entries"))
     results = []
     for name, section in (("operators", lambda: operators(base, a, dev, results)), ("msg", lambda: msg_operator(base, a, dev, results)),
-                          ("msg_level", lambda: msg_level(a, dev, results)), ("training", lambda: training_level(a, dev, results))):
+                          ("msg_level", lambda: msg_level(a, dev, results)), ("training", lambda: training_level(a, dev, results)),
+                          ("pair", lambda: pair_operators(base, a, dev, results, False)),
+                          ("knn", lambda: pair_operators(base, a, dev, results, True))):
         if a.only in (None, name):
             section()
     if a.json:
